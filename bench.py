@@ -28,6 +28,10 @@ Prints ONE JSON line on rank 0. Extra legs (rank 0, N=1 only): `roofline` — th
 1024^3 MFMA GEMM) timed per launch with HIP events on its own stream in a separate instrumented pass of the
 same loop; `cpu_baseline` — a torch-CPU twin of the reference's update (oracle/torch_twin.py: the library ops the reference
 uses, pinned to the reference's recorded trajectory) on the host cores this process may use, with the numpy oracle beside it.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last of them left the caller — the actor, critic and critic-target parameters
+(update() returns {} with use_tb=False) — as DIR/<net>.<key>.npy in float32, about 21 MB. The replay, the initial weights and the Philox
+streams depend only on the arguments, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -174,6 +178,9 @@ def main():
     ap.add_argument('--branches', type=int, default=int(os.environ.get('EXORL_BRANCHES', '0')))
     ap.add_argument('--native-comm', type=int, default=int(os.environ.get('EXORL_BENCH_NATIVE', '1')),
                     help='N > 1 on nccl: after the torch.distributed-path number, try the library\'s own RCCL communicator + captured step behind a watchdog')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step left the caller (actor, critic and critic-target parameters) '
+                         'as DIR/<net>.<key>.npy, float32 (rank 0)')
     ap.add_argument('--dp1', action='store_true', help='N=1 only: attach a 1-rank RCCL communicator, i.e. time the library-driven data-parallel step '
                     '(finalised gradients -> ncclAllReduce -> unfused Adam) on one GPU; a diagnostic, not the metric')
     args = ap.parse_args()
@@ -264,8 +271,26 @@ def main():
             dt = float(t.item())
         return dt
 
+    def dump_outputs(ag):
+        """The state update() leaves behind after the last timed step: its return value is {} (use_tb=False), so the caller receives the
+        three networks. Same arguments -> same replay, initial weights and Philox streams, so two builds can be compared file by file."""
+        done = args.warmup + args.steps
+        if ag.engine.opt_steps()[1] != done:       # the critic steps once per update(): the count proves how many steps ran
+            raise RuntimeError(f'critic optimiser stepped {ag.engine.opt_steps()[1]} times, expected warmup + steps = {done}')
+        arrays = {f'{name}.{k}': p.detach().float().cpu().numpy() for name, net in (('actor', ag.actor), ('critic', ag.critic),
+                  ('critic_target', ag.critic_target)) for k, p in net.named_parameters()}
+        total = sum(a.nbytes for a in arrays.values())
+        if total > 64 << 20:
+            raise RuntimeError(f'--dump-outputs: {total} bytes exceed the 64 MB budget')
+        d = Path(args.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        for k, a in arrays.items():
+            np.save(d / f'{k}.npy', np.ascontiguousarray(a, np.float32))
+
     agent, it, use_graph = build(args.precision)
     dt = timed(agent, it)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(agent)
     ranks_seen = [0]
     if world > 1:
         seen = [torch.zeros(1, device=device, dtype=torch.int64) for _ in range(world)]
@@ -364,6 +389,8 @@ def main():
                     first['dp_collectives'], first['hip_graph'] = out['config']['dp_collectives'], out['config']['hip_graph']
                     out = result(dt2, g2, collectives_of(ag2))
                     out['torch_distributed_path'] = first
+                    if args.dump_outputs:
+                        dump_outputs(ag2)
             else:
                 native = {'status': 'RCCL communicator refused; torch.distributed path stands'}
         except Exception as e:                  # any failure of the unverified leg leaves the first number standing

@@ -11,6 +11,21 @@ import torch
 ROOT = Path(__file__).resolve().parent.parent
 
 
+# The reference's weight_init draws every Linear weight with nn.init.orthogonal_, i.e. a QR factorisation in the host's LAPACK. The fixtures
+# were recorded with MKL's AVX-512 kernels on an Intel host; other CPUs (AMD EPYC) take other MKL code paths that round the factor a few
+# float32 ulp differently (<= 1.3e-6 measured over MKL's code paths). The Gaussian draws are host-independent, and a draw-order error moves
+# the weights by O(0.1), so the matrices get a fixed absolute bound and everything else (biases, LayerNorm) stays bit-exact.
+ORTHO_ATOL = 1e-5
+
+
+def _assert_init_equal(got, want, name):
+    got = got.numpy()
+    if got.ndim >= 2:
+        np.testing.assert_allclose(got, want, rtol=0, atol=ORTHO_ATOL, err_msg=name)
+    else:
+        np.testing.assert_array_equal(got, want, err_msg=name)
+
+
 def _declared_symbols():
     text = (ROOT / 'include' / 'exorl_hip.h').read_text()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
@@ -52,12 +67,12 @@ def test_init_matches_reference_rng_order(gold, kind):
     actor0 = agents._mlp_init(O, H, A, 1, 1)
     keys = agents._DDPG_ACTOR_KEYS if kind == 'ddpg' else agents._OFFLINE_ACTOR_KEYS
     for k, w in zip(keys, actor0):
-        np.testing.assert_array_equal(w.numpy(), z[f'init/actor/{k}'], err_msg=k)
+        _assert_init_equal(w, z[f'init/actor/{k}'], k)
     if kind != 'bc':
         critic0 = agents._mlp_init(O + A, H, 1, 1 if kind == 'ddpg' else 2, 2)
         ckeys = agents._DDPG_CRITIC_KEYS if kind == 'ddpg' else agents._OFFLINE_CRITIC_KEYS
         for k, w in zip(ckeys, critic0):
-            np.testing.assert_array_equal(w.numpy(), z[f'init/critic/{k}'], err_msg=k)
+            _assert_init_equal(w, z[f'init/critic/{k}'], k)
 
 
 @pytest.mark.parametrize('kind', ['rnd', 'icm', 'icm_apt'])
@@ -79,7 +94,7 @@ def test_intr_module_init_matches_reference_rng_order(gold, kind):
         keys, mod = agents._APT_KEYS, 'icm'
     assert len(w) == len(keys)
     for k, t in zip(keys, w):
-        np.testing.assert_array_equal(t.numpy(), z[f'init/{mod}/{k}'], err_msg=k)
+        _assert_init_equal(t, z[f'init/{mod}/{k}'], k)
 
 
 def test_aps_init_matches_reference_rng_order(gold):
@@ -95,11 +110,11 @@ def test_aps_init_matches_reference_rng_order(gold):
     agents._mlp_init(O + S + A, H, S, 1, 2)
     w = agents._seq_init([('lin', O, H), ('lin', H, H), ('lin', H, S)])
     for k, t in zip(agents._DDPG_ACTOR_KEYS, actor0):
-        np.testing.assert_array_equal(t.numpy(), z[f'init/actor/{k}'], err_msg=k)
+        _assert_init_equal(t, z[f'init/actor/{k}'], k)
     for k, t in zip(agents._DDPG_CRITIC_KEYS, critic0):
-        np.testing.assert_array_equal(t.numpy(), z[f'init/critic/{k}'], err_msg=k)
+        _assert_init_equal(t, z[f'init/critic/{k}'], k)
     for k, t in zip(agents._APS_KEYS, w):
-        np.testing.assert_array_equal(t.numpy(), z[f'init/aps/{k}'], err_msg=k)
+        _assert_init_equal(t, z[f'init/aps/{k}'], k)
 
 
 def test_pixel_init_matches_reference_rng_order(gold):
@@ -111,7 +126,8 @@ def test_pixel_init_matches_reference_rng_order(gold):
     w = agents._pixel_init(C_, HW, A, F, H)
     for nm in ('encoder', 'actor', 'critic'):
         got = np.array([[float(t.double().sum()), float((t.double() ** 2).sum())] for t in w[nm]])
-        np.testing.assert_allclose(got, z[f'init_sums/{nm}'], rtol=1e-6, atol=1e-6, err_msg=nm)
+        # float64 sums over orthogonal factors: the host-LAPACK rounding above, summed (<= 1.1e-6 relative measured)
+        np.testing.assert_allclose(got, z[f'init_sums/{nm}'], rtol=1e-5, atol=1e-6, err_msg=nm)
 
 
 def test_proto_init_matches_reference_rng_order(gold):
@@ -127,7 +143,7 @@ def test_proto_init_matches_reference_rng_order(gold):
     keys = ['predictor/weight', 'predictor/bias', 'projector/trunk.0.weight', 'projector/trunk.0.bias', 'projector/trunk.2.weight',
             'projector/trunk.2.bias', 'protos/weight']
     for k, t in zip(keys, w):
-        np.testing.assert_array_equal(t.numpy(), z[f'init/{k}'], err_msg=k)
+        _assert_init_equal(t, z[f'init/{k}'], k)
 
 
 def test_schedule_and_helpers(gold):

@@ -121,7 +121,9 @@ def test_torch_twin_proto_pixels_matches_reference_miniature(gold):
         np.testing.assert_allclose([m[k] for k in keys], z['metrics'][i], rtol=2e-5, atol=1e-6, err_msg=f'step {i} {keys}')
     for k, v in tw.encoder.state_dict().items():
         np.testing.assert_allclose(v.numpy(), z[f'final/encoder/{k}'], rtol=1e-5, atol=1e-6, err_msg=k)
-    np.testing.assert_allclose(tw.queue.numpy(), z['final/queue'], rtol=1e-5, atol=1e-6)
+    # the queue holds normalised projections of the last batch: three updates of host conv / GEMM kernels whose summation order differs
+    # between MKL code paths (Intel AVX-512 recording vs other CPUs: up to 5e-6 measured), hence the metrics' rtol and an absolute floor
+    np.testing.assert_allclose(tw.queue.numpy(), z['final/queue'], rtol=2e-5, atol=1e-5)
     assert tw.queue_ptr == int(z['final/queue_ptr'])
 
 
