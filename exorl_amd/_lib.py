@@ -1,7 +1,6 @@
 """ctypes binding of libexorl_hip.so (include/exorl_hip.h). No fallback: if the HIP library is
 missing or a call fails, this raises — the product path never routes around the GPU kernels."""
 import ctypes as C
-import os
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
@@ -164,8 +163,6 @@ PROTOTYPES = {
                                     c_void_p, c_int64, c_int32, c_void_p]),
     'exorl_gemm_tune': (C.c_int, [c_int32]),
     'exorl_debug_precision_override': (C.c_int, [c_int32]),
-    'exorl_debug_gemm_stamps': (C.c_int, [c_void_p, c_int32]),
-    'exorl_debug_conv_stamps': (C.c_int, [c_void_p, c_int32]),
     'exorl_profile_gemm': (C.c_int, [c_int32]),
     'exorl_profile_gemm_read': (C.c_int, [c_void_p, c_void_p, c_int32, P(c_int32)]),
     'exorl_profile_event_overhead': (C.c_int, [c_void_p, c_void_p]),
@@ -198,9 +195,6 @@ def load():
         fn.restype = res
         fn.argtypes = args
     _lib = lib
-    tune = os.environ.get('EXORL_GEMM_TUNE')        # kernel-variant experiments (tools/micro): bit mask for exorl_gemm_tune
-    if tune:
-        lib.exorl_gemm_tune(int(tune))
     return lib
 
 

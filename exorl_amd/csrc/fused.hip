@@ -469,10 +469,9 @@ int trunk_fwd16_batch(const TrunkBatch& tb, int count, int64_t ldx, int rows, in
     const bool x3 = tb.it[0].W0l != nullptr;
     for (int i = 0; i < count; ++i)
         EXORL_REQUIRE((tb.it[i].W0l != nullptr) == x3 && (!x3 || (tb.it[i].hl && (!tb.it[i].xhb || tb.it[i].xhl))), "trunk_fwd16: inconsistent lo planes");
-    const int var = tune_variant();
     // 8-row workgroups where 16-row ones would leave CUs idle (measured, H = 1024: 2048 rows x 1 net 13.4 -> 10.3 us, 1024 x 2 nets 12.9 -> 10.0);
     // at 256 or more 16-row workgroups the 8-row grid is two rounds per CU and slower (1024 rows x 4 nets: 13.1 -> 16.2 us)
-    const bool rows8 = H % 256 == 0 && !(var & 4194304) && ((var & 8388608) || cdiv(rows, 16) * count < 256);
+    const bool rows8 = H % 256 == 0 && cdiv(rows, 16) * count < 256;
     if (rows8) {
         const dim3 grid8(cdiv(rows, 8), count);
 #define EXORL_TF8(T) do { if (x3) hipLaunchKernelGGL((trunk_fwd8_kernel<T, true>), grid8, dim3(512), 0, s, tb, ldx, rows, in_dim, Kp); \
@@ -1382,29 +1381,12 @@ __device__ __forceinline__ void step_small(const FusedAdamArgs& a, const AdamCon
     }
 }
 
-typedef float v4f_nt __attribute__((ext_vector_type(4)));
-typedef unsigned v4u_nt __attribute__((ext_vector_type(4)));
-// Measured and NOT adopted (round 3; exorl_gemm_tune bit 4 switches it on): non-temporal loads and stores for the optimiser pass's streams, on
-// the theory that 117 MB touched once per step should not churn a 32 MB L2. The step got SLOWER — 0.3035 ms against 0.2868 ms with plain
-// accesses (bench.py, same box): the gradient the wgrad GEMM has just written and the weights the next forward reads are served from the L2 /
+// Plain loads and stores for the optimiser pass's streams. Non-temporal ones (round 3) made the step SLOWER — 0.3035 ms against 0.2868 ms
+// (bench.py, same box): the gradient the wgrad GEMM has just written and the weights the next forward reads are served from the L2 /
 // Infinity Cache when they are left there.
-template <bool NT>
-__device__ __forceinline__ float4 ld4(const float* p, int64_t i4) {
-    if constexpr (NT) { const v4f_nt v = __builtin_nontemporal_load(reinterpret_cast<const v4f_nt*>(p) + i4); return make_float4(v.x, v.y, v.z, v.w); }
-    else return reinterpret_cast<const float4*>(p)[i4];
-}
-template <bool NT>
-__device__ __forceinline__ void st4(float* p, int64_t i4, const float4& v) {
-    if constexpr (NT) { const v4f_nt w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<v4f_nt*>(p) + i4); }
-    else reinterpret_cast<float4*>(p)[i4] = v;
-}
-template <bool NT>
-__device__ __forceinline__ void st4u(unsigned short* p, int64_t i8, const uint4& v) {
-    if constexpr (NT) { const v4u_nt w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<v4u_nt*>(p) + i8); }
-    else reinterpret_cast<uint4*>(p)[i8] = v;
-}
+__device__ __forceinline__ float4 ld4(const float* p, int64_t i4) { return reinterpret_cast<const float4*>(p)[i4]; }
+__device__ __forceinline__ void st4(float* p, int64_t i4, const float4& v) { reinterpret_cast<float4*>(p)[i4] = v; }
 
-template <bool NT>
 __global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, FusedAdamArgs a, ShadowSpec sh, int nb_fin) {
     const AdamConst c = *a.c;
     if (a.bump && blockIdx.x == 0 && threadIdx.x == 0) *a.bump += 1ull;
@@ -1419,25 +1401,25 @@ __global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, Fuse
             float4 pv[2], gv[2], mv[2], vv[2], tv[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                pv[u] = ld4<NT>(a.p, gi4 + u);
-                gv[u] = ld4<NT>(a.g, gi4 + u);
-                mv[u] = ld4<NT>(a.m, gi4 + u);
-                vv[u] = ld4<NT>(a.v, gi4 + u);
-                tv[u] = a.target ? ld4<NT>(a.target, gi4 + u) : make_float4(0.f, 0.f, 0.f, 0.f);
+                pv[u] = ld4(a.p, gi4 + u);
+                gv[u] = ld4(a.g, gi4 + u);
+                mv[u] = ld4(a.m, gi4 + u);
+                vv[u] = ld4(a.v, gi4 + u);
+                tv[u] = a.target ? ld4(a.target, gi4 + u) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             ushort4 bh[2], bl[2], th[2], tl[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 adam_elem(pv[u].x, gv[u].x, mv[u].x, vv[u].x, c); adam_elem(pv[u].y, gv[u].y, mv[u].y, vv[u].y, c);
                 adam_elem(pv[u].z, gv[u].z, mv[u].z, vv[u].z, c); adam_elem(pv[u].w, gv[u].w, mv[u].w, vv[u].w, c);
-                st4<NT>(a.p, gi4 + u, pv[u]);
-                st4<NT>(a.m, gi4 + u, mv[u]);
-                st4<NT>(a.v, gi4 + u, vv[u]);
+                st4(a.p, gi4 + u, pv[u]);
+                st4(a.m, gi4 + u, mv[u]);
+                st4(a.v, gi4 + u, vv[u]);
                 bh[u] = f4_to_bf4(pv[u]); bl[u] = f4_to_bf4_lo(pv[u]);
                 if (a.target) {
                     tv[u].x = polyak(pv[u].x, tv[u].x, c.tau, c.one_minus_tau); tv[u].y = polyak(pv[u].y, tv[u].y, c.tau, c.one_minus_tau);
                     tv[u].z = polyak(pv[u].z, tv[u].z, c.tau, c.one_minus_tau); tv[u].w = polyak(pv[u].w, tv[u].w, c.tau, c.one_minus_tau);
-                    st4<NT>(a.target, gi4 + u, tv[u]);
+                    st4(a.target, gi4 + u, tv[u]);
                     th[u] = f4_to_bf4(tv[u]); tl[u] = f4_to_bf4_lo(tv[u]);
                 }
             }
@@ -1500,22 +1482,14 @@ __global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, Fuse
     }
 }
 
-// part 0: the whole optimiser pass; 1: everything but the H x H weights; 2: the H x H weights only (their gradient is complete as soon
-// as the wgrad GEMM is, so that ~80 % of the pass — the HBM-bound part — can run beside the LayerNorm-backward / first-layer-wgrad chain
-// that produces the other gradients; `f` is not read then)
-int finalize_adam(const FinalizeArgs& f, const FusedAdamArgs& a, const ShadowSpec& sh, hipStream_t s, int part) {
-    EXORL_REQUIRE(sh.H % 4 == 0 && a.n_heads >= 1 && a.n_heads <= 2 && part >= 0 && part <= 2, "finalize_adam: unsupported geometry");
+int finalize_adam(const FinalizeArgs& f, const FusedAdamArgs& a, const ShadowSpec& sh, hipStream_t s) {
+    EXORL_REQUIRE(sh.H % 4 == 0 && a.n_heads >= 1 && a.n_heads <= 2, "finalize_adam: unsupported geometry");
     const int H = sh.H;
-    const int64_t total = part == 2 ? 0 : f.n_heads * ((int64_t)(f.nout + 1) * f.H + (f.nout > 16 ? 32 : 16)) + f.n_trunks * (int64_t)(3 + f.in_dim) * f.H;
+    const int64_t total = f.n_heads * ((int64_t)(f.nout + 1) * f.H + (f.nout > 16 ? 32 : 16)) + f.n_trunks * (int64_t)(3 + f.in_dim) * f.H;
     const int nb_fin = cdiv(total, 256);
-    int nb_w1 = part == 1 ? 0 : cdiv((int64_t)a.n_heads * H * H / 8, 256);
+    int nb_w1 = cdiv((int64_t)a.n_heads * H * H / 8, 256);
     if (nb_w1 > 2048) nb_w1 = 2048;
-    FusedAdamArgs aa = a;
-    if (part == 2) aa.bump = nullptr;
-    FinalizeArgs ff = f;
-    if (part == 2) ff.H = H;
-    if (tune_variant() & 4) hipLaunchKernelGGL(finalize_adam_kernel<true>, dim3(nb_fin + nb_w1), dim3(256), 0, s, ff, aa, sh, nb_fin);
-    else hipLaunchKernelGGL(finalize_adam_kernel<false>, dim3(nb_fin + nb_w1), dim3(256), 0, s, ff, aa, sh, nb_fin);
+    hipLaunchKernelGGL(finalize_adam_kernel, dim3(nb_fin + nb_w1), dim3(256), 0, s, f, a, sh, nb_fin);
     EXORL_LAUNCH_CHECK();
     return 0;
 }

@@ -141,9 +141,6 @@ __device__ __forceinline__ void store_tile(unsigned char* lds, int tid, const fl
 
 // measured (round 3): one LDS stage pays for three planes (Proto pixels 9.8 -> 9.5 ms, ICM pixels 27.2 -> 22.8 ms per update in bf16x6) and is
 // neutral to slightly worse for two (rnd 1528 -> 1514, icm_apt 1186 -> 1172 update()/s): two planes keep the double buffer
-#ifndef EXORL_GEMM_X3_SINGLE_STAGE
-#define EXORL_GEMM_X3_SINGLE_STAGE 0
-#endif
 template <int PREC, int AL, int BL, bool VEC>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmBatch gb) {
     constexpr int KU = (PREC == EXORL_PREC_F32) ? 4 : 8;   // k elements per 16-byte unit
@@ -152,7 +149,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmBatch gb) {
     constexpr int NT = X6 ? 6 : (X3 ? 4 : 2);              // LDS tiles per stage: [A p0][B p0][A p1][B p1][A p2][B p2]
     // two stages; the three-plane mode needs 96 KB, past the 64 KB a static array may have: dynamic there
     extern __shared__ __attribute__((aligned(16))) unsigned char gk_dyn[];
-    __shared__ __attribute__((aligned(16))) unsigned char gk_static[X6 ? 16 : ((X3 && EXORL_GEMM_X3_SINGLE_STAGE) ? 1 : 2) * NT * TILEB];
+    __shared__ __attribute__((aligned(16))) unsigned char gk_static[X6 ? 16 : 2 * NT * TILEB];
     unsigned char* const smem_base = X6 ? gk_dyn : gk_static;
     auto smem = [&](int stage, int tile) { return smem_base + (stage * NT + tile) * TILEB; };
 
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmBatch gb) {
 
     // three planes: ONE LDS stage (48 KB, three workgroups per CU) instead of two (96 KB, one workgroup of four waves per CU — one wave per SIMD
     // with nothing to hide a barrier or an LDS round trip behind); the next tile still travels in registers while this one is multiplied
-    constexpr bool SS = X6 || (X3 && EXORL_GEMM_X3_SINGLE_STAGE);
+    constexpr bool SS = X6;
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = SS ? 0 : (kt & 1);
         if (kt + 1 < nk) {
@@ -349,16 +346,7 @@ __device__ __forceinline__ XcdTile xcd_tile(int id, int count, int tiles_m, int 
     t.ok = slot < bm * bn;
     return t;
 }
-static bool xcd_map_ok(const Gemm16Batch& gb, int count, int tile) {
-    if (!(count == 1 || count == 2 || count == 4)) return false;
-    const int X = 8 / count, sm = X == 8 ? 4 : 2, sn = X == 2 ? 1 : 2;
-    for (int i = 0; i < count; ++i) {
-        if (gb.p[i].M != gb.p[0].M || gb.p[i].N != gb.p[0].N) return false;
-        if ((gb.p[i].M / tile) % sm != 0 || (gb.p[i].N / tile) % sn != 0) return false;
-    }
-    return true;
-}
-static int g_gemm16_variant = -1;    // experiment switch (exorl_gemm_tune): -1 = default heuristics
+static int g_gemm16_variant = -1;    // exorl_gemm_tune: the TUNE_* reference-path bits (kernels.h); -1 or 0 = defaults
 
 template <int AL, int BL, int BM, int NS, bool GUARD>
 __global__ __launch_bounds__(256) void gemm16_kernel(const Gemm16Batch gb) {
@@ -389,6 +377,7 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const Gemm16Batch gb) {
     const int wm = wave >> 1, wn = wave & 1;
     const int h = lane >> 5;
 
+    static_assert(NS == 2 || NS == 3, "register stages");
     uint4 ra[NS][NUA], rb[NS][NUB];      // NS register stages: loads run NS-1 k-tiles ahead of their LDS store
     f32x16 acc[MT];
 #pragma unroll
@@ -439,14 +428,12 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const Gemm16Batch gb) {
     issue(std::integral_constant<int, 0>{}, 0);
     if constexpr (NS > 1) issue(std::integral_constant<int, 1>{}, 1);
     if constexpr (NS > 2) issue(std::integral_constant<int, 2>{}, 2);
-    if constexpr (NS > 3) issue(std::integral_constant<int, 3>{}, 3);
     commit(std::integral_constant<int, 0>{}, 0);
     __syncthreads();
     for (int kt = 0; kt < nk; kt += NS) {
         step(std::integral_constant<int, 0>{}, kt);
         if constexpr (NS > 1) { if (kt + 1 >= nk) break; step(std::integral_constant<int, 1>{}, kt + 1); }
         if constexpr (NS > 2) { if (kt + 2 >= nk) break; step(std::integral_constant<int, 2>{}, kt + 2); }
-        if constexpr (NS > 3) { if (kt + 3 >= nk) break; step(std::integral_constant<int, 3>{}, kt + 3); }
     }
 
     const int n = n0 + wn * 32 + (lane & 31);
@@ -502,20 +489,13 @@ template <bool AT, bool BT, int NSTG = G16G_NSTG, bool X3 = false>
 __device__ __forceinline__ void gemm16g_body(const Gemm16Batch& gb, unsigned char* smem) {
     constexpr int IMG = G16G_IMG;
 
-    int pidx = blockIdx.z, m0, n0;
-    if (gb.xcd_map) {
-        const XcdTile xt = xcd_tile(blockIdx.x, gb.count, gb.p[0].M >> 6, gb.p[0].N >> 6);
-        if (!xt.ok) return;
-        pidx = xt.p; m0 = xt.tm << 6; n0 = xt.tn << 6;
-    } else {
-        const int tiles_n = gb.p[pidx].N >> 6, ntiles = tiles_n * (gb.p[pidx].M >> 6);
-        if ((int)blockIdx.x >= ntiles) return;
-        int tile = blockIdx.x;
-        if (gb.swizzle && (ntiles & 7) == 0) tile = (tile & 7) * (ntiles >> 3) + (tile >> 3);
-        m0 = (tile / tiles_n) << 6;
-        n0 = (tile % tiles_n) << 6;
-    }
-    const Gemm16Problem& P = gb.p[pidx];
+    const Gemm16Problem& P = gb.p[blockIdx.z];
+    const int tiles_n = P.N >> 6, ntiles = tiles_n * (P.M >> 6);
+    if ((int)blockIdx.x >= ntiles) return;
+    int tile = blockIdx.x;
+    if (gb.swizzle && (ntiles & 7) == 0) tile = (tile & 7) * (ntiles >> 3) + (tile >> 3);
+    const int m0 = (tile / tiles_n) << 6;
+    const int n0 = (tile % tiles_n) << 6;
     const int K = P.K;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -863,17 +843,16 @@ __device__ __forceinline__ void gemm16h_body(const Gemm16Batch& gb, unsigned cha
         }
 }
 
-template <bool AT, bool BT, int NSTG>
+template <bool AT, bool BT>
 __global__ __launch_bounds__(256) void gemm16h_kernel(const Gemm16Batch gb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
-    gemm16h_body<AT, BT, NSTG>(gb, smem_h);
+    gemm16h_body<AT, BT, G16G_NSTG>(gb, smem_h);
 }
 
-template <int NSTG>
 __global__ __launch_bounds__(256) void gemm16h_mixed_kernel(const Gemm16Batch gb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
-    if (gb.a_t[blockIdx.z]) gemm16h_body<true, true, NSTG>(gb, smem_h);
-    else gemm16h_body<false, true, NSTG>(gb, smem_h);
+    if (gb.a_t[blockIdx.z]) gemm16h_body<true, true, G16G_NSTG>(gb, smem_h);
+    else gemm16h_body<false, true, G16G_NSTG>(gb, smem_h);
 }
 
 template <bool AT, bool BT>
@@ -899,40 +878,34 @@ static int g16hx3_enable() {
 }
 // 128 x 128 tiles pay off when they still fill the chip: 4-problem launches of 1024^2 outputs are 256 workgroups
 static bool g16hx3_fits(const Gemm16Batch& gb, int count) {
-    if (g_gemm16_variant >= 0 && (g_gemm16_variant & 65536)) return false;        // experiment switch: off
     int tiles = 0;
     for (int i = 0; i < count; ++i) {
         if (gb.p[i].M % 128 != 0 || gb.p[i].N % 128 != 0 || gb.p[i].K % 128 != 0) return false;
         tiles += (gb.p[i].M >> 7) * (gb.p[i].N >> 7);
     }
-    return tiles >= 256 || (g_gemm16_variant >= 0 && (g_gemm16_variant & 131072));
+    return tiles >= 256;
 }
-constexpr size_t G16H_LDS = (size_t)G16G_NSTG * G16H_STAGE;      // 128 KB at 4 stages; 64 KB at 2 (two workgroups per CU)
-static int g16h_stages() { return (g_gemm16_variant >= 0 && (g_gemm16_variant & 512)) ? 2 : 4; }
-template <int NSTG>
-static int g16h_enable_n() {          // > 64 KB of dynamic LDS needs the opt-in, once per kernel
+constexpr size_t G16H_LDS = (size_t)G16G_NSTG * G16H_STAGE;      // 128 KB
+static int g16h_enable() {          // > 64 KB of dynamic LDS needs the opt-in, once per kernel
     static bool done = false;
     if (done) return 0;
-    const int lds = NSTG * G16H_STAGE;
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<false, false, NSTG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<false, true, NSTG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<true, true, NSTG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_mixed_kernel<NSTG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
+    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
+    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
+    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_mixed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
     done = true;
     return 0;
 }
-static int g16h_enable() { return g16h_stages() == 2 ? g16h_enable_n<2>() : g16h_enable_n<4>(); }
 static bool g16h_fits(const Gemm16Batch& gb, int count) {
     // measured slower than the 64 x 64 tiles on the 1024-wide layers (15-17 us vs 9-12 us per problem: one workgroup per CU leaves
-    // the k-tile chain wait -> barrier -> DMA issue -> LDS reads -> MFMA exposed): opt-in through tuning bit 1024
-    if (g_gemm16_variant >= 0 && (g_gemm16_variant & 65536)) return false;
+    // the k-tile chain wait -> barrier -> DMA issue -> LDS reads -> MFMA exposed): only where 128 x 128 tiles still give every CU a
+    // workgroup (the 4-problem launches)
     int tiles = 0;
     for (int i = 0; i < count; ++i) {
         if (gb.p[i].M % 128 != 0 || gb.p[i].N % 128 != 0) return false;
         tiles += (gb.p[i].M >> 7) * (gb.p[i].N >> 7);
     }
-    // by default only where 128 x 128 tiles still give every CU a workgroup (the 4-problem launches); bit 1024 forces them everywhere
-    return tiles >= 256 || (g_gemm16_variant >= 0 && (g_gemm16_variant & 1024));
+    return tiles >= 256;
 }
 
 // ---- "p" kernels: 128 x TN workgroup tile (TN = 128 or 64), k32 stages, 4-deep LDS-DMA ring, XCD-local tile blocks -----------
@@ -979,102 +952,35 @@ __device__ __forceinline__ void g16p_lds_fence(G16pFrag& f) {
 // KS = k per stage (32: 64-byte row-image rows = half cache lines, four stages fit the 128 x 128 split-bf16 tile; 64: whole lines, the
 // 64-wide images and swizzle of the gemm16g kernels above), NSTG = ring depth. A stage's slot is refilled with the stage NSTG ahead as soon
 // as its last fragments have been read, i.e. behind the barrier that opens the stage's last k16.
-// MS = MFMA shape: 32 -> v_mfma_f32_32x32x16_bf16 (a region = one k16), 16 -> v_mfma_f32_16x16x32_bf16 (a region = one k32; row images on
-// 64-wide stages only). Same wave tile, same LDS images, same fragment bytes and MFMA cycles per region pair; the chip holds a higher clock
-// on the 16 x 16 shape under a dense bf16 load (MI355X_MICROARCH.md, DVFS give-back (7)), so the faster one is picked by wall time.
-// WS = wave-specialised workgroup of 512 threads: waves 0-3 (one per SIMD) run the MFMA + fragment-read stream only, waves 4-7 — their SIMD
-// partners — issue the LDS-DMA fills and certify them (vmcnt) in front of the stage barrier. An LDS-DMA instruction costs its wave ~60-180
-// issue cycles (MI355X_MICROARCH.md constants), eight of them per k32 stage oversubscribe the gaps of the 24 MFMAs of that stage; in a
-// partner wave they cost the computing wave next to nothing (same guide, "Two waves per SIMD" item 7).
-// STAMP (diagnostic build, tuning bit 33554432; no product launch takes it): wave 0 of every workgroup records s_memtime (shader clock) and
-// s_memrealtime (100 MHz) at entry, at the first k-step, after the last k-step and after its stores have drained, into g16p_stamps —
-// the in-kernel clock and the split prologue / k-loop / epilogue (MI355X_MICROARCH.md, DVFS give-back (6)). Nothing is computed from them.
-__device__ unsigned long long g16p_stamps[8 * 1024];
-// ABL (stamped builds only): 1 = no DMA after the prologue, 2 = no fragment reads, 3 = no MFMAs — what each part costs in CYCLES
-// SPREAD = number of consecutive k-regions over which the LDS-DMA pieces of one stage refill are issued (1: all of them in the region behind
-// the barrier that frees the slot). Stamps (tools/micro/stamp_bench.py) put the k-loop at MFMA cycles + ~60 cycles per DMA piece of the
-// wave: the four waves issue their pieces together, the CU's vector-memory path takes them one at a time, and a wave blocked on an issue
-// cannot feed its matrix pipe. Spread over two regions the same pieces have twice the MFMAs to hide behind.
-// STAG = 0 | 2 | 4: the waves of a workgroup run in lockstep between barriers, so with one instruction stream they issue their DMA pieces
-// in the same MFMA gaps. With STAG phases, wave w places its pieces in the gaps g = w mod STAG (mod STAG): STAG copies of the k-loop that
-// differ only in that placement, chosen once per wave in front of the loop.
-// NW = waves per workgroup, all of them loading and computing (4, or 8 = 512 threads on the same 128 x TN tile with half-size wave tiles).
-// tools/micro/fill_bench.hip: ONE wave issues an LDS-DMA piece about every 100 cycles whatever it keeps in flight (4 waves per CU deliver
-// 85 GB/s at 8, 16 or 32 pieces in flight each; 8 waves 117 GB/s, where the CU's L2 path saturates) — a 128 x 64 tile needs 24 pieces per
-// 384 MFMA-cycles, i.e. more issue slots than four waves have.
-// PFD > 0: one more wave (id NW) that computes nothing: it walks PFD stages ahead of the ring and touches this workgroup's 1/32 share of the
-// lines the XCD's tile block will need (one dword per 128-byte line into a dead register), so that the fabric round trip of the FIRST touch of
-// every operand line — each XCD fetches each of its lines exactly once per launch — is taken ahead of the LDS-DMA stream instead of inside it.
-// It joins every stage barrier (that is its pacing: far-ahead lines would push unread ones out of a 4 MB L2) and exits after the last one.
-template <bool AT, bool BT, bool X3, int TN, int KS, int NSTG, int MS = 32, bool WS = false, bool STAMP = false, int ABL = 0, int SPREAD = 1, int STAG = 0,
-          int NW = 4, int PFD = 0>
+// The refill of a stage slot is spread over two consecutive k-regions. Stamps of the in-kernel clock (a diagnostic build removed after
+// commit d23b35a) put the k-loop at MFMA cycles + ~60 cycles per DMA piece of the wave: the four waves issue their pieces together, the
+// CU's vector-memory path takes them one at a time, and a wave blocked on an issue cannot feed its matrix pipe. Spread over two regions
+// the same pieces have twice the MFMAs to hide behind.
+template <bool AT, bool BT, bool X3, int TN, int KS, int NSTG>
 __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned char* smem, int pidx, int m0, int n0) {
-    constexpr int NBA = 2, NBB = TN / 64, NPL = X3 ? 2 : 1;
-    constexpr int WR = (NW == 8 && TN == 64) ? 32 : 64;     // wave tile: WR rows x WC columns
-    constexpr int WC = NW == 8 ? 32 : TN / 2;
+    constexpr int NW = 4, NBA = 2, NBB = TN / 64, NPL = X3 ? 2 : 1;
+    constexpr int WR = 64, WC = TN / 2;                     // wave tile: WR rows x WC columns
     constexpr int WN = TN / WC;                             // waves along N (the rest along M)
-    static_assert((NW == 4 || (NW == 8 && MS == 32 && !WS && KS == 64)) && (128 / WR) * WN == NW, "wave grid");
     constexpr int BLK = 64 * 2 * KS;                        // one 64-row block of one plane and stage (either image kind)
     constexpr int PLANE = (NBA + NBB) * BLK;                // [A blk0][A blk1][B blk0][B blk1]
     constexpr int STAGE = NPL * PLANE;                      // hi plane, then lo plane
     constexpr int PPW = KS / 8 / NW;                        // 1-KB DMA pieces per wave and block
     constexpr int NP = (NBA + NBB) * NPL * PPW;             // DMA pieces per wave and stage
-    constexpr int NQ = MS == 16 ? KS / 32 : KS / 16;        // regions (k16 / k32) per stage
-    constexpr int SA = WR / MS;                             // MS-row sub-tiles of a wave along M
-    constexpr int SB = WC / MS;                             // MS-column sub-tiles of a wave along N
-    constexpr int NPAIR = SA * SB;                          // MS x MS accumulators of a wave
+    constexpr int NQ = KS / 16;                             // regions (k16) per stage
+    constexpr int SA = WR / 32;                             // 32-row sub-tiles of a wave along M
+    constexpr int SB = WC / 32;                             // 32-column sub-tiles of a wave along N
+    constexpr int NPAIR = SA * SB;                          // 32 x 32 accumulators of a wave
     constexpr int NM = NPAIR * (X3 ? 3 : 1);                // MFMAs per region
     constexpr int NF = (SA + SB) * NPL;                     // fragments per region
     constexpr int SMIN = SA < SB ? SA : SB;
-    static_assert(MS == 32 || (MS == 16 && !AT && !BT && KS == 64), "16 x 16 x 32 fragments are built for row images on 64-wide stages");
-    typedef float acc_t __attribute__((ext_vector_type(MS == 16 ? 4 : 16)));
+    typedef float acc_t __attribute__((ext_vector_type(16)));
     constexpr int FPG = (NF + NM - 2) / (NM - 1);           // fragments read per MFMA gap: all of them behind the first NM-1 MFMAs
     static_assert(NQ % 2 == 0 && NP * (NSTG - 1) <= 63 && NSTG >= 2, "stage geometry");
     const Gemm16Problem& P = gb.p[pidx];
     const int nst = P.K / KS;                               // multiple of NSTG, >= NSTG (launcher)
-    unsigned long long st_t[4] = {0, 0, 0, 0}, st_r[4] = {0, 0, 0, 0}, wacc_v = 0, wacc_b = 0;      // wacc: cycles in the stage waits (own DMA | barrier)
-    auto stamp = [&](int i) {
-        if constexpr (STAMP) { st_t[i] = __builtin_amdgcn_s_memtime(); st_r[i] = __builtin_amdgcn_s_memrealtime(); }
-    };
-    stamp(0);
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool loader = WS && wave_id >= 4;                 // wave-uniform role
-    if constexpr (PFD > 0) {
-        static_assert(!AT && !BT && KS == 64 && !WS, "the prefetch wave is written for row images on 64-wide stages (one line per row and stage)");
-        if (wave_id == NW) {
-            int nA = 0, nB = 0, rA = 0, rB = 0;
-            if (gb.xcd_map) {                   // the XCD's tile block (xcd_tile): rows rA .. rA + nA of A, rows rB .. rB + nB of B
-                const int X = 8 / gb.count, sm = X == 8 ? 4 : 2, sn = X == 2 ? 1 : 2, xq = (blockIdx.x & 7) % X;
-                const int bm = (P.M >> 7) / sm, bn = (P.N / TN) / sn;
-                nA = bm * 128; rA = (xq / sn) * nA;
-                nB = bn * TN;  rB = (xq % sn) * nB;
-            }
-            const int nl = (nA + nB) * NPL, slot = blockIdx.x >> 3;
-            // every touch loads into the SAME register, which stays live (read-write operand) until the loads have landed: an asm output the
-            // compiler believes dead would be handed to the next value and overwritten when the data arrives
-            unsigned dead = 0;
-            auto touch = [&](int t) {           // this workgroup's share of stage t's lines: line l = (operand, plane, row)
-                for (int l = slot * 64 + lane; l < nl; l += 32 * 64) {
-                    const bool isB = l >= nA * NPL;
-                    const int ll = isB ? l - nA * NPL : l, n = isB ? nB : nA, pl = ll / n, r = ll % n;
-                    const unsigned short* base = isB ? (pl ? P.B_lo : P.B) : (pl ? P.A_lo : P.A);
-                    const unsigned short* ptr = base + (int64_t)((isB ? rB : rA) + r) * (isB ? P.ldb : P.lda) + (int64_t)t * KS;
-                    asm volatile("global_load_dword %0, %1, off" : "+v"(dead) : "v"(ptr) : "memory");
-                }
-            };
-            for (int t = NSTG; t < PFD && t < nst; ++t) touch(t);
-            __builtin_amdgcn_s_barrier();                               // B_0
-            for (int t = 0; t + 1 < nst; ++t) {
-                if (t + PFD < nst) touch(t + PFD);
-                __builtin_amdgcn_s_barrier();                           // B_{t+1}
-            }
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(dead) :: "memory");
-            return;
-        }
-    }
-    const int wave = WS ? (wave_id & 3) : wave_id;          // consumer: its 64 x TN/2 quadrant; loader: which pieces of a block it fetches
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int h = lane >> 5;
     const int arow0 = (wm * WR) & 63, ablk = (wm * WR) >> 6;        // this wave's rows inside A block ablk
@@ -1084,7 +990,7 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
 #pragma unroll
     for (int a = 0; a < NPAIR; ++a)
 #pragma unroll
-        for (int i = 0; i < (MS == 16 ? 4 : 16); ++i) { acc[a][i] = 0.f; if constexpr (X3) accx[a][i] = 0.f; }
+        for (int i = 0; i < 16; ++i) { acc[a][i] = 0.f; if constexpr (X3) accx[a][i] = 0.f; }
 
     // row image: 2*KS-byte rows, 16-byte units swizzled so that the 16 lanes of a ds_read_b128 group hit 16 distinct bank quads
     auto row_off = [](int row, int unit) {
@@ -1128,15 +1034,12 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
 #pragma unroll
-        for (int u = 0; u < SA; ++u) {
-            if constexpr (MS == 16) aoff[u][q] = ablk * BLK + row_off(arow0 + u * 16 + (lane & 15), 4 * q + (lane >> 4));    // lane: row l & 15, k = 8 (l >> 4) ..+7
-            else aoff[u][q] = ablk * BLK + (AT ? tr_off(arow0 + u * 32) + q * 16 * ROWB : row_off(arow0 + u * 32 + (lane & 31), 2 * q + h));
-        }
+        for (int u = 0; u < SA; ++u)
+            aoff[u][q] = ablk * BLK + (AT ? tr_off(arow0 + u * 32) + q * 16 * ROWB : row_off(arow0 + u * 32 + (lane & 31), 2 * q + h));
 #pragma unroll
         for (int u = 0; u < SB; ++u) {
-            const int blk = bblk, r0 = bcol0 + u * MS;
-            if constexpr (MS == 16) boff[u][q] = (NBA + blk) * BLK + row_off(r0 + (lane & 15), 4 * q + (lane >> 4));
-            else boff[u][q] = (NBA + blk) * BLK + (BT ? tr_off(r0) + q * 16 * ROWB : row_off(r0 + (lane & 31), 2 * q + h));
+            const int r0 = bcol0 + u * 32;
+            boff[u][q] = (NBA + bblk) * BLK + (BT ? tr_off(r0) + q * 16 * ROWB : row_off(r0 + (lane & 31), 2 * q + h));
         }
     }
 
@@ -1186,39 +1089,27 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
     auto mfma_one = [&](const Frags& f, auto ic) {
         constexpr int I = decltype(ic)::value;
         constexpr int pair = X3 ? I / 3 : I, term = X3 ? I % 3 : 0, ua = pair / SB, ub = pair % SB;
-        if constexpr (MS == 16) {       // D[n][m]: lane = output row (lane & 15), registers 0..3 = columns 4 (lane >> 4) ..+3
-            if constexpr (term == 0) acc[pair] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.bh[ub].v, f.ah[ua].v, acc[pair], 0, 0, 0);
-            else if constexpr (term == 1) accx[pair] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.bl[ub].v, f.ah[ua].v, accx[pair], 0, 0, 0);
-            else accx[pair] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.bh[ub].v, f.al[ua].v, accx[pair], 0, 0, 0);
-        } else {
         if constexpr (term == 0) acc[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bh[ub].v, f.ah[ua].v, acc[pair], 0, 0, 0);
         else if constexpr (term == 1) accx[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bl[ub].v, f.ah[ua].v, accx[pair], 0, 0, 0);
         else accx[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bh[ub].v, f.al[ua].v, accx[pair], 0, 0, 0);
-        }
     };
     // One scheduling region = the NM MFMAs of a k16 on `cur`, with the reads of the NEXT k16's fragments (stage slot nst_, region NQn) into
-    // `nxt` (FPG per MFMA gap) and, when NFILL > 0, the DMA issues of stage slot `fst` written out between them; sched_barrier(0)
+    // `nxt` (FPG per MFMA gap) and, when NFILL > 0, this region's half (chunk) of the DMA issues of stage slot `fst` written out between them; sched_barrier(0)
     // after every piece keeps the machine scheduler from regrouping them (left alone it sinks the reads to just before their use; issued
     // as one block they exceed the 4-bit lgkmcnt and the compiler waits for all of them). The reads complete in the shadow of the matrix
     // pipe, the next region opens with waits that cost nothing.
-    auto region = [&](Frags& cur, Frags& nxt, auto has_next, int nst_, auto nq, auto nfill, int fst, auto chunk, auto phase) {
-        constexpr int PH = decltype(phase)::value;           // -1: pieces in the first gaps; >= 0: in the gaps congruent to PH mod STAG
+    auto region = [&](Frags& cur, Frags& nxt, auto has_next, int nst_, auto nq, auto nfill, int fst, auto chunk) {
         constexpr bool HN = decltype(has_next)::value;
         constexpr int NFILL = decltype(nfill)::value;
-        constexpr int F0 = decltype(chunk)::value * NP / SPREAD, F1 = (decltype(chunk)::value + 1) * NP / SPREAD;      // this region's share of the refill
+        constexpr int F0 = decltype(chunk)::value * NP / 2, F1 = (decltype(chunk)::value + 1) * NP / 2;      // this region's share of the refill
         g16p_static_for<0, NM>([&](auto ic) {
             constexpr int I = decltype(ic)::value;
-            if constexpr (ABL != 3) mfma_one(cur, ic);
+            mfma_one(cur, ic);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (HN && ABL != 2) g16p_static_for<I * FPG, ((I + 1) * FPG < NF ? (I + 1) * FPG : NF)>([&](auto jc) { read_one(nxt, nst_, nq, jc); });
+            if constexpr (HN) g16p_static_for<I * FPG, ((I + 1) * FPG < NF ? (I + 1) * FPG : NF)>([&](auto jc) { read_one(nxt, nst_, nq, jc); });
             constexpr int PPG = (F1 - F0 + NM - 1) / NM;     // DMA pieces per gap
-            if constexpr (NFILL > 0 && ABL != 1) {
-                if constexpr (PH < 0) g16p_static_for<F0 + I * PPG, (F0 + (I + 1) * PPG < F1 ? F0 + (I + 1) * PPG : F1)>([&](auto pc) { fill_one(fst, pc); });
-                else g16p_static_for<0, F1 - F0>([&](auto ii) {
-                    constexpr int i = decltype(ii)::value;
-                    if constexpr ((PH + STAG * i) % NM == I) fill_one(fst, std::integral_constant<int, F0 + i>{});
-                });
-            }
+            if constexpr (NFILL > 0)
+                g16p_static_for<F0 + I * PPG, (F0 + (I + 1) * PPG < F1 ? F0 + (I + 1) * PPG : F1)>([&](auto pc) { fill_one(fst, pc); });
             __builtin_amdgcn_sched_barrier(0);
         });
         // The fence of the fragments just requested closes the region that issued them — the same place in the instruction stream as the head
@@ -1227,7 +1118,7 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
         // resolve the join with v_mov copies of the asm outputs BEFORE the wait, i.e. copies of registers the LDS had not written yet
         // (tools/check_async_reads.py shows them in the round-2 ISA of every SPREAD = 2 kernel with a k-image operand, split-bf16 included;
         // the plain-bf16 launches — 2-4 MFMAs between the reads and the copy — lost that race visibly: DESIGN 4, "the SPREAD = 2 anomaly").
-        if constexpr (HN && ABL != 2) fence(nxt);
+        if constexpr (HN) fence(nxt);
     };
     // a stage has landed for this wave once at most `younger` younger stages' pieces are outstanding (NP per stage)
     auto wait_landed = [&](auto younger) {
@@ -1242,120 +1133,53 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
     // NSTG stages on slots 0..NSTG-1; LAST = the final group (nothing left to refill, no barrier after the last stage). Every condition is
     // a compile-time constant: a run-time branch in here makes the compiler fall back to lgkmcnt(0) / vmcnt(0)
     using C0 = std::integral_constant<int, 0>;
-    static_assert(SPREAD >= 1 && SPREAD <= NQ && (SPREAD == 1 || !WS), "refill spread");
-    auto group = [&](auto first, auto last, auto phase) {
+    auto group = [&](auto first, auto last) {
         constexpr bool FIRST = decltype(first)::value, LAST = decltype(last)::value;
         g16p_static_for<0, NSTG>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
-            // the refill the previous stage began behind its barrier (chunk 0) continues in this stage's first SPREAD-1 regions
-            constexpr bool PENDING = SPREAD > 1 && (s > 0 ? !LAST : !FIRST);
+            // the refill the previous stage began behind its barrier (chunk 0) continues in this stage's first region
+            constexpr bool PENDING = s > 0 ? !LAST : !FIRST;
             g16p_static_for<0, NQ - 1>([&](auto qc) {        // all but the last k16 of the stage: read the next k16 of the same stage
                 constexpr int q = decltype(qc)::value;
-                if constexpr (PENDING && q < SPREAD - 1) {
-                    region(fr[q & 1], fr[(q + 1) & 1], T{}, s, std::integral_constant<int, q + 1>{}, Fill{}, (s + NSTG - 1) % NSTG, std::integral_constant<int, q + 1>{}, phase);
-                }
+                if constexpr (PENDING && q == 0)
+                    region(fr[q & 1], fr[(q + 1) & 1], T{}, s, std::integral_constant<int, q + 1>{}, Fill{}, (s + NSTG - 1) % NSTG, std::integral_constant<int, 1>{});
                 else
-                    region(fr[q & 1], fr[(q + 1) & 1], T{}, s, std::integral_constant<int, q + 1>{}, NoFill{}, 0, C0{}, phase);
+                    region(fr[q & 1], fr[(q + 1) & 1], T{}, s, std::integral_constant<int, q + 1>{}, NoFill{}, 0, C0{});
             });
             Frags& cur = fr[(NQ - 1) & 1];
             Frags& nxt = fr[NQ & 1];
             if constexpr (!LAST || s < NSTG - 1) {
                 // the next stage has landed for this wave when only the stages younger than it are outstanding: NSTG-2 of them in the steady
                 // state, NSTG-2-s in the last group (nothing is issued there any more)
-                unsigned long long w0 = 0, w1 = 0;
-                if constexpr (STAMP) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); w0 = __builtin_amdgcn_s_memtime(); }
-                if constexpr (!WS && ABL != 1) wait_landed(std::integral_constant<int, LAST ? NSTG - 2 - s : NSTG - 2>{});
+                wait_landed(std::integral_constant<int, LAST ? NSTG - 2 - s : NSTG - 2>{});
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's reads of stage s are done: its slot may be refilled
-                if constexpr (STAMP) w1 = __builtin_amdgcn_s_memtime();
                 __builtin_amdgcn_s_barrier();                           // ... by anyone; and the next stage has landed for everyone
                 asm volatile("" ::: "memory");
-                if constexpr (STAMP) { const unsigned long long w2 = __builtin_amdgcn_s_memtime(); wacc_v += w1 - w0; wacc_b += w2 - w1; }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!LAST && !WS) region(cur, nxt, T{}, (s + 1) % NSTG, std::integral_constant<int, 0>{}, Fill{}, s, C0{}, phase);
-                else region(cur, nxt, T{}, (s + 1) % NSTG, std::integral_constant<int, 0>{}, NoFill{}, 0, C0{}, phase);
+                if constexpr (!LAST) region(cur, nxt, T{}, (s + 1) % NSTG, std::integral_constant<int, 0>{}, Fill{}, s, C0{});
+                else region(cur, nxt, T{}, (s + 1) % NSTG, std::integral_constant<int, 0>{}, NoFill{}, 0, C0{});
             } else {
-                region(cur, nxt, F{}, 0, std::integral_constant<int, 0>{}, NoFill{}, 0, C0{}, phase);
+                region(cur, nxt, F{}, 0, std::integral_constant<int, 0>{}, NoFill{}, 0, C0{});
             }
         });
     };
 
-    if constexpr (WS) {
-        if (loader) {
-            // the same barriers as the consumers, in the same order: B_0 = stage 0 has landed; B_{s+1} = stage s + 1 has landed (this wave's
-            // pieces: vmcnt; everyone's: the barrier) and every consumer has finished reading stage s, whose slot takes stage s + NSTG
-            g16p_static_for<0, NSTG>([&](auto sc) { fill(decltype(sc)::value); });
-            wait_landed(std::integral_constant<int, NSTG - 1>{});
-            __builtin_amdgcn_s_barrier();
-            auto lgroup = [&](auto last) {
-                constexpr bool LAST = decltype(last)::value;
-                g16p_static_for<0, NSTG>([&](auto sc) {
-                    constexpr int s = decltype(sc)::value;
-                    if constexpr (!LAST || s < NSTG - 1) {
-                        wait_landed(std::integral_constant<int, LAST ? NSTG - 2 - s : NSTG - 2>{});
-                        __builtin_amdgcn_s_barrier();
-                        asm volatile("" ::: "memory");
-                        if constexpr (!LAST) fill(s);
-                    }
-                });
-            };
-            for (int t = 0; t + NSTG < nst; t += NSTG) lgroup(F{});
-            lgroup(T{});
-            return;
-        }
-    } else {
-        g16p_static_for<0, NSTG>([&](auto sc) { fill(decltype(sc)::value); });
-        wait_landed(std::integral_constant<int, NSTG - 1>{});
-    }
+    g16p_static_for<0, NSTG>([&](auto sc) { fill(decltype(sc)::value); });
+    wait_landed(std::integral_constant<int, NSTG - 1>{});
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    stamp(1);
     g16p_static_for<0, NF>([&](auto jc) { read_one(fr[0], 0, std::integral_constant<int, 0>{}, jc); });
     fence(fr[0]);                               // before any control flow (see region())
-    auto kloop = [&](auto phase) {
-        if constexpr (SPREAD == 1) {
-            for (int t = 0; t + NSTG < nst; t += NSTG) group(F{}, F{}, phase);
-            group(F{}, T{}, phase);
-        } else if (nst == NSTG) {
-            group(T{}, T{}, phase);
-        } else {
-            group(T{}, F{}, phase);
-            for (int t = NSTG; t + NSTG < nst; t += NSTG) group(F{}, F{}, phase);
-            group(F{}, T{}, phase);
-        }
-    };
-    static_assert(STAG <= 0 || ((STAG == 2 || STAG == 4) && NM % STAG == 0 && !WS), "stagger");
-    if constexpr (STAG <= 0) kloop(std::integral_constant<int, -1>{});
-    else if constexpr (STAG == 2) { if (wave & 1) kloop(std::integral_constant<int, 1>{}); else kloop(C0{}); }
-    else {
-        if (wave == 0) kloop(C0{});
-        else if (wave == 1) kloop(std::integral_constant<int, 1>{});
-        else if (wave == 2) kloop(std::integral_constant<int, 2>{});
-        else kloop(std::integral_constant<int, 3>{});
+    if (nst == NSTG) {
+        group(T{}, T{});
+    } else {
+        group(T{}, F{});
+        for (int t = NSTG; t + NSTG < nst; t += NSTG) group(F{}, F{});
+        group(F{}, T{});
     }
-    stamp(2);
 
     const bool relu = gb.relu != 0;
-    if constexpr (MS == 16) {
-#pragma unroll
-        for (int ta = 0; ta < SA; ++ta)
-#pragma unroll
-            for (int tb = 0; tb < SB; ++tb) {
-                const int nb = n0 + wn * WC + tb * 16 + 4 * (lane >> 4);
-                if (P.n_store && nb >= P.n_store) continue;
-                float4* dst = reinterpret_cast<float4*>(P.C + (int64_t)(m0 + wm * WR + ta * 16 + (lane & 15)) * P.ldc + nb);
-                const float4 bias = P.bias ? *reinterpret_cast<const float4*>(P.bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const acc_t& a0 = acc[ta * SB + tb];
-                const acc_t& ax = accx[X3 ? ta * SB + tb : 0];
-                float4 v;
-                v.x = (X3 ? ax[0] + a0[0] : a0[0]) + bias.x;
-                v.y = (X3 ? ax[1] + a0[1] : a0[1]) + bias.y;
-                v.z = (X3 ? ax[2] + a0[2] : a0[2]) + bias.z;
-                v.w = (X3 ? ax[3] + a0[3] : a0[3]) + bias.w;
-                if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                if (gb.accumulate) { const float4 o = *dst; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-                *dst = v;
-            }
-    } else if (P.head_part) {
+    if (P.head_part) {
         // folded scalar head: this wave's share of relu(acc + bias) . head_w for each of its rows; lanes l and l + 32 hold the two column
         // interleaves of one row. Nothing of C is stored.
 #pragma unroll
@@ -1408,15 +1232,6 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
             }
         }
     }
-    if constexpr (STAMP) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(3);
-        if (lane == 0 && blockIdx.x < 256 && wave_id < 4) {             // 32 words per workgroup: wave w (< 4) at [8 w .. 8 w + 7]
-            unsigned long long* o = g16p_stamps + blockIdx.x * 32 + wave_id * 8;
-            o[0] = st_t[0]; o[1] = st_t[1]; o[2] = st_t[2]; o[3] = st_t[3];
-            o[4] = st_r[1]; o[5] = st_r[2]; o[6] = wacc_v; o[7] = wacc_b;
-        }
-    }
 }
 // workgroup id -> (problem, tile origin): XCD-local blocks when the launcher found the problems uniform, id order otherwise
 template <int TN>
@@ -1436,59 +1251,26 @@ __device__ __forceinline__ bool g16p_tile(const Gemm16Batch& gb, int& pidx, int&
     return true;
 }
 
-template <bool AT, bool BT, bool X3, int TN, int KS = 32, int NSTG = 4, int MS = 32, bool STAMP = false, int ABL = 0, int SPREAD = 1, int STAG = 0>
+template <bool AT, bool BT, bool X3, int TN, int KS = 32, int NSTG = 4>
 __global__ __launch_bounds__(256) void gemm16p_kernel(const Gemm16Batch gb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
     int pidx, m0, n0;
     if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    gemm16p_body<AT, BT, X3, TN, KS, NSTG, MS, false, STAMP, ABL, SPREAD, STAG>(gb, smem_p, pidx, m0, n0);
+    gemm16p_body<AT, BT, X3, TN, KS, NSTG>(gb, smem_p, pidx, m0, n0);
 }
 
-#ifdef EXORL_GEMM_EXPERIMENTS
-template <bool X3, int TN, int NWV, int PFD, bool STAMP = false>      // NWV computing waves + one prefetch wave PFD stages ahead (forward launches)
-__global__ __launch_bounds__(64 * (NWV + 1)) void gemm16pf_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
-    int pidx, m0, n0;
-    if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    gemm16p_body<false, false, X3, TN, 64, 2, 32, false, STAMP, 0, 2, 0, NWV, PFD>(gb, smem_p, pidx, m0, n0);
-}
-template <bool AT, bool BT, bool X3, int TN, bool STAMP = false>      // 8 waves per workgroup, all loading and computing; 64-wide stages x 2
-__global__ __launch_bounds__(512) void gemm16p8_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
-    int pidx, m0, n0;
-    if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    gemm16p_body<AT, BT, X3, TN, 64, 2, 32, false, STAMP, 0, 2, 0, 8>(gb, smem_p, pidx, m0, n0);
-}
-template <bool AT, bool BT, bool X3, int TN>      // wave-specialised (512 threads: 4 MFMA waves + 4 loader waves), k32 stages x 4
-__global__ __launch_bounds__(512) void gemm16w_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
-    int pidx, m0, n0;
-    if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    gemm16p_body<AT, BT, X3, TN, 32, 4, 32, true>(gb, smem_p, pidx, m0, n0);
-}
-template <bool X3, int TN>
-__global__ __launch_bounds__(512) void gemm16w_mixed_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
-    int pidx, m0, n0;
-    if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    if (gb.a_t[pidx]) gemm16p_body<true, true, X3, TN, 32, 4, 32, true>(gb, smem_p, pidx, m0, n0);
-    else gemm16p_body<false, true, X3, TN, 32, 4, 32, true>(gb, smem_p, pidx, m0, n0);
-}
-#endif
-
-template <bool X3, int TN, int SPREAD = 1>      // wgrad (A as a k image) and dgrad (A as a row image) of one Linear(H,H) in one launch; B is a k image in both
+template <bool X3, int TN>      // wgrad (A as a k image) and dgrad (A as a row image) of one Linear(H,H) in one launch; B is a k image in both
 __global__ __launch_bounds__(256) void gemm16p_mixed_kernel(const Gemm16Batch gb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
     int pidx, m0, n0;
     if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    if (gb.a_t[pidx]) gemm16p_body<true, true, X3, TN, 32, 4, 32, false, false, 0, SPREAD>(gb, smem_p, pidx, m0, n0);
-    else gemm16p_body<false, true, X3, TN, 32, 4, 32, false, false, 0, SPREAD>(gb, smem_p, pidx, m0, n0);
+    if (gb.a_t[pidx]) gemm16p_body<true, true, X3, TN, 32, 4>(gb, smem_p, pidx, m0, n0);
+    else gemm16p_body<false, true, X3, TN, 32, 4>(gb, smem_p, pidx, m0, n0);
 }
 constexpr int g16p_lds(bool x3, int tn, int ks = 32, int nstg = 4) { return nstg * (x3 ? 2 : 1) * (2 + tn / 64) * 64 * 2 * ks; }
 
 // Tile width for a launch (0 = these kernels do not apply): 128 x 128 when that still gives every CU a workgroup, else 128 x 64.
 static int g16p_pick(const Gemm16Batch& gb, int count, bool x3) {
-    if (g_gemm16_variant >= 0 && (g_gemm16_variant & 262144)) return 0;          // experiment switch: off
     int t128 = 0;
     for (int i = 0; i < count; ++i) {
         const Gemm16Problem& p = gb.p[i];
@@ -1500,11 +1282,9 @@ static int g16p_pick(const Gemm16Batch& gb, int count, bool x3) {
     }
     bool n128 = true;
     for (int i = 0; i < count; ++i) n128 = n128 && gb.p[i].N % 128 == 0;
-    if (g_gemm16_variant >= 0 && (g_gemm16_variant & 524288)) return n128 ? 128 : 64;      // experiment: 128 x 128 wherever it tiles
     return (n128 && t128 >= 256) ? 128 : 64;
 }
 static bool g16p_uniform(const Gemm16Batch& gb, int count, int tn) {       // xcd_tile()'s preconditions
-    if (g_gemm16_variant >= 0 && (g_gemm16_variant & 1048576)) return false;     // experiment: id order
     if (!(count == 1 || count == 2 || count == 4)) return false;
     const int X = 8 / count, sm = X == 8 ? 4 : 2, sn = X == 2 ? 1 : 2;
     for (int i = 0; i < count; ++i) {
@@ -1514,7 +1294,7 @@ static bool g16p_uniform(const Gemm16Batch& gb, int count, int tn) {       // xc
     return true;
 }
 template <typename K>
-static int g16p_launch(K kernel, Gemm16Batch& gb, int count, bool x3, int tn, hipStream_t s, int ks = 32, int nstg = 4, int threads = 256) {
+static int g16p_launch(K kernel, Gemm16Batch& gb, int count, bool x3, int tn, hipStream_t s, int ks = 32, int nstg = 4) {
     const int lds = g16p_lds(x3, tn, ks, nstg);
     static std::vector<const void*> enabled;         // > 64 KB of dynamic LDS needs the opt-in, once per kernel
     if (std::find(enabled.begin(), enabled.end(), (const void*)kernel) == enabled.end()) {
@@ -1525,7 +1305,7 @@ static int g16p_launch(K kernel, Gemm16Batch& gb, int count, bool x3, int tn, hi
     gb.xcd_map = g16p_uniform(gb, count, tn) ? 1 : 0;
     int tmax = 0, ttot = 0;
     for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N / tn); tmax = t > tmax ? t : tmax; ttot += t; }
-    hipLaunchKernelGGL(kernel, gb.xcd_map ? dim3(ttot, 1, 1) : dim3(tmax, 1, count), dim3(threads), lds, s, gb);
+    hipLaunchKernelGGL(kernel, gb.xcd_map ? dim3(ttot, 1, 1) : dim3(tmax, 1, count), dim3(256), lds, s, gb);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
@@ -1544,54 +1324,16 @@ __global__ __launch_bounds__(256) void gemm16x3_kernel(const Gemm16Batch gb) {
 }
 __global__ __launch_bounds__(256) void gemm16x3_mixed_kernel(const Gemm16Batch gb) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 4 * G16G_IMG];
-    const int p = gb.xcd_map ? (int)(blockIdx.x & 7) / (8 / gb.count) : (int)blockIdx.z;
-    if (gb.a_t[p]) gemm16g_body<true, true, 2, true>(gb, smem);
+    if (gb.a_t[blockIdx.z]) gemm16g_body<true, true, 2, true>(gb, smem);
     else gemm16g_body<false, true, 2, true>(gb, smem);
 }
-
-// Deep-pipeline variants (experiment, tuning bits 16384 / 32768): dynamic LDS up to the full 160 KB of a CU, to test whether the
-// k-loop is bound by bytes in flight (in-flight bytes <= LDS bytes). It is not: 5 x 32 KB split-bf16 stages with one workgroup per CU
-// run 35.8 us per launch against 24.6 us for 2 stages x 2 workgroups; plain bf16 10 stages x 1 workgroup 23.8 us against 13.7 us, and
-// 5 stages x 2 workgroups 13.75 us (no change). The XCD-block mapping changes nothing either (23.3 vs 23.4 us), so it is not fabric
-// traffic, and the LDS array is at ~half its rate (128 KB of ds_read_b128 at 256 B/clk + 64 KB of DMA writes per CU and k-tile pair
-// = ~1000 of the ~2100 cycles). What is left is the operand delivery rate of a CU through the LDS-DMA path: 64 KB per 2100 cycles =
-// 73 GB/s, the same ~75 GB/s the plain bf16 kernel sustains and the 68-90 GB/s per CU MI355X_MICROARCH.md lists for LDS-DMA fills
-// ("ldsdma-fill", "ring-gemm"); it needs >= 2 workgroups per CU to be reached. Split-bf16 moves twice the bytes and takes twice the
-// time. Fewer operand bytes per FLOP (64 x 32 / 64 x 64 wave tiles) is the lever, at the price of half as many workgroups on a
-// batch-1024 problem (the 128 x 128 experiment above).
-template <bool AT, bool BT, int NSTG, bool X3>
-__global__ __launch_bounds__(256) void gemm16d_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_d[];
-    gemm16g_body<AT, BT, NSTG, X3>(gb, smem_d);
-}
-template <int NSTG, bool X3>
-__global__ __launch_bounds__(256) void gemm16d_mixed_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_d[];
-    const int p = gb.xcd_map ? (int)(blockIdx.x & 7) / (8 / gb.count) : (int)blockIdx.z;
-    if (gb.a_t[p]) gemm16g_body<true, true, NSTG, X3>(gb, smem_d);
-    else gemm16g_body<false, true, NSTG, X3>(gb, smem_d);
-}
-template <int NSTG, bool X3>
-static int g16d_enable() {
-    static bool done = false;
-    if (done) return 0;
-    const int lds = NSTG * (X3 ? 4 : 2) * G16G_IMG;
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16d_kernel<false, false, NSTG, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16d_kernel<false, true, NSTG, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16d_kernel<true, true, NSTG, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16d_mixed_kernel<NSTG, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    done = true;
-    return 0;
-}
-constexpr int G16D_X3_STAGES = 5;      // 5 x 32 KB = 160 KB: one workgroup per CU, four k-tiles (128 KB) in flight
 
 // One launch for the wgrad and dgrad GEMMs of a Linear(H,H) backward: both read dZ (wgrad as a k image, dgrad as a row image)
 // and are independent, so 2 x 512 tiles fill the 256 CUs four deep instead of two launches two deep, and one kernel boundary
 // (~4.5 us of drain + cache write-back + ramp on this part) disappears. B is a k image in both.
 __global__ __launch_bounds__(256) void gemm16g_mixed_kernel(const Gemm16Batch gb) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[G16G_NSTG * 2 * G16G_IMG];
-    const int p = gb.xcd_map ? (int)(blockIdx.x & 7) / (8 / gb.count) : (int)blockIdx.z;
-    if (gb.a_t[p]) gemm16g_body<true, true>(gb, smem);
+    if (gb.a_t[blockIdx.z]) gemm16g_body<true, true>(gb, smem);
     else gemm16g_body<false, true>(gb, smem);
 }
 
@@ -1611,16 +1353,12 @@ static int launch16(const Gemm16Batch& gb, int count, int tiles64, int tiles128,
         g_prof.flops.push_back(f);
         EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used], s));
     }
-    // variant bits (tuning): 1 = force BM 64, 2 = force BM 128, 8 = no XCD swizzle, 16 = keep guards,
-    // 32 = 2 register stages, 64 = 4 register stages (default 3)
-    const int var = g_gemm16_variant < 0 ? 0 : g_gemm16_variant;
-    const bool big = (var & 2) ? true : ((var & 1) ? false : tiles128 * count >= 256);
+    const bool big = tiles128 * count >= 256;
     Gemm16Batch g2 = gb;
-    g2.swizzle = (var & 8) ? 0 : 1;
+    g2.swizzle = 1;
     bool exact = true;      // every problem tiles exactly: loads need no bounds guards
     for (int i = 0; i < count; ++i)
         exact = exact && gb.p[i].M % 128 == 0 && gb.p[i].N % 64 == 0 && gb.p[i].K % 64 == 0;
-    if (var & 16) exact = false;
     bool exact64 = true;
     for (int i = 0; i < count; ++i)
         exact64 = exact64 && gb.p[i].M % 64 == 0 && gb.p[i].N % 64 == 0 && gb.p[i].K % 256 == 0 && gb.p[i].lda % 8 == 0 &&
@@ -1628,161 +1366,51 @@ static int launch16(const Gemm16Batch& gb, int count, int tiles64, int tiles128,
     bool x3 = false;
     for (int i = 0; i < count; ++i) x3 = x3 || gb.p[i].A_lo || gb.p[i].B_lo;
     if (const int tn = g16p_pick(g2, count, x3)) {          // 128 x TN tiles, k32 stages, XCD-local blocks (see gemm16p_body)
-        // both operands row images (the forward launches): 64-wide stages, two deep — whole cache lines per DMA row instead of halves, which
-        // halves the requests the XCD L2s serve (critic fwd 21.8 -> 19.5 us, actor fwd 21.1 -> 18.9, critic+target fwd 33.7 -> 32.4); bit
-        // 2097152 of the tuning variant switches back to the 32-wide stages
-        const bool k64 = AL == 0 && BL == 0 && !(g_gemm16_variant >= 0 && (g_gemm16_variant & 2097152));
-        const int var_ = g_gemm16_variant < 0 ? 0 : g_gemm16_variant;
-        const bool sp1 = (var_ & 536870912) != 0;            // the previous schedule: a stage's refill issued in one region (SPREAD = 1)
-        const bool stamped = (var_ & 33554432) != 0;        // diagnostic build with in-kernel clock stamps (tools/micro/stamp_bench.py)
-        bool done = false;
-#ifdef EXORL_GEMM_EXPERIMENTS      // measured and not adopted ("what was tried on the GEMM"): kept reproducible, not in the default build
-        if (x3 && !done) {
-            done = true;
-            if (k64 && (var_ & 134217728) && !(var_ & 67108864) && !stamped) {        // + a prefetch wave (bit 27): 8 + 1 waves on 128 x 64 tiles (with bit
-                if constexpr (AL == 0 && BL == 0) {                                  // 28), 4 + 1 otherwise; bit 30 = 10 instead of 6 stages ahead
-                    const bool far = (var_ & 1073741824) != 0;
-                    if (tn == 64 && (var_ & 268435456) && far) EXORL_TRY(g16p_launch(gemm16pf_kernel<true, 64, 8, 10>, g2, count, true, 64, s, 64, 2, 576));
-                    else if (tn == 64 && (var_ & 268435456)) EXORL_TRY(g16p_launch(gemm16pf_kernel<true, 64, 8, 6>, g2, count, true, 64, s, 64, 2, 576));
-                    else if (tn == 64 && far) EXORL_TRY(g16p_launch(gemm16pf_kernel<true, 64, 4, 10>, g2, count, true, 64, s, 64, 2, 320));
-                    else if (tn == 64) EXORL_TRY(g16p_launch(gemm16pf_kernel<true, 64, 4, 6>, g2, count, true, 64, s, 64, 2, 320));
-                    else if (var_ & 268435456) EXORL_TRY(g16p_launch(gemm16p8_kernel<false, false, true, 128>, g2, count, true, 128, s, 64, 2, 512));
-                    else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, false, 0, 2>, g2, count, true, 128, s, 64, 2));
-                }
-            } else if (k64 && (var_ & 268435456)) {        // 8 waves per workgroup, all loading and computing (forward launches)
-                if constexpr (AL == 0 && BL == 0) {
-                    if (tn == 128 && stamped) EXORL_TRY(g16p_launch(gemm16p8_kernel<false, false, true, 128, true>, g2, count, true, 128, s, 64, 2, 512));
-                    else if (tn == 128) EXORL_TRY(g16p_launch(gemm16p8_kernel<false, false, true, 128>, g2, count, true, 128, s, 64, 2, 512));
-                    else if (stamped) EXORL_TRY(g16p_launch(gemm16p8_kernel<false, false, true, 64, true>, g2, count, true, 64, s, 64, 2, 512));
-                    else EXORL_TRY(g16p_launch(gemm16p8_kernel<false, false, true, 64>, g2, count, true, 64, s, 64, 2, 512));
-                }
-            } else if (var_ & 8388608) {          // wave-specialised workgroups
-                if (tn == 128) EXORL_TRY(g16p_launch(gemm16w_kernel<AL != 0, BL != 0, true, 128>, g2, count, true, 128, s, 32, 4, 512));
-                else EXORL_TRY(g16p_launch(gemm16w_kernel<AL != 0, BL != 0, true, 64>, g2, count, true, 64, s, 32, 4, 512));
-            } else if (k64 && (var_ & 4194304) && !(var_ & 1073741824)) {          // 16 x 16 x 32 MFMAs
-                if constexpr (AL == 0 && BL == 0) {
-                    if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 16>, g2, count, true, 128, s, 64, 2));
-                    else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2, 16>, g2, count, true, 64, s, 64, 2));
-                }
-            } else if (k64 && (var_ & 1073741824)) {                              // per-wave DMA placement (2 phases; 4 with bit 4194304)
-                if constexpr (AL == 0 && BL == 0) {
-                    if (tn == 128 && (var_ & 4194304)) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, false, 0, 2, 4>, g2, count, true, 128, s, 64, 2));
-                    else if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, false, 0, 2, 2>, g2, count, true, 128, s, 64, 2));
-                    else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2, 32, false, 0, 2, 2>, g2, count, true, 64, s, 64, 2));
-                }
-            } else done = false;
-        }
-#endif
-        if (done) {
-        } else if (x3 && k64) {
-            if constexpr (AL == 0 && BL == 0) {
-                if (stamped) {
-                    const int abl = (var_ >> 26) & 3;
-                    if (tn == 128 && abl == 1) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, true, 1>, g2, count, true, 128, s, 64, 2));
-                    else if (tn == 128 && abl == 2) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, true, 2>, g2, count, true, 128, s, 64, 2));
-                    else if (tn == 128 && abl == 3) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, true, 3>, g2, count, true, 128, s, 64, 2));
-                    else if (tn == 128 && sp1) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, true>, g2, count, true, 128, s, 64, 2));
-                    else if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, true, 0, 2>, g2, count, true, 128, s, 64, 2));
-                    else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2, 32, true, 0, 2>, g2, count, true, 64, s, 64, 2));
-                } else if (sp1) {
-                    if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2>, g2, count, true, 128, s, 64, 2));
-                    else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2>, g2, count, true, 64, s, 64, 2));
-                } else if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2, 32, false, 0, 2>, g2, count, true, 128, s, 64, 2));
-                else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2, 32, false, 0, 2>, g2, count, true, 64, s, 64, 2));
-            }
-        } else if (x3 && stamped) {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 128, 32, 4, 32, true, 0, 2>, g2, count, true, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 64, 32, 4, 32, true, 0, 2>, g2, count, true, 64, s));
-        } else if (x3 && sp1) {
+        if (x3 && AL == 0 && BL == 0) {
+            // both operands row images (the forward launches): 64-wide stages, two deep — whole cache lines per DMA row instead of halves, which
+            // halves the requests the XCD L2s serve (critic fwd 21.8 -> 19.5 us, actor fwd 21.1 -> 18.9, critic+target fwd 33.7 -> 32.4)
+            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2>, g2, count, true, 128, s, 64, 2));
+            else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2>, g2, count, true, 64, s, 64, 2));
+        } else if (x3) {
             if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 128>, g2, count, true, 128, s));
             else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 64>, g2, count, true, 64, s));
-        } else if (x3) {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 128, 32, 4, 32, false, 0, 2>, g2, count, true, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 64, 32, 4, 32, false, 0, 2>, g2, count, true, 64, s));
-        } else if (sp1) {
+        } else {
+            // plain bf16 planes take the two-region refill as well (round 3). Round 2 kept them on a one-region refill because the k-image B operand
+            // came out wrong, run-to-run different, under the two-region one: that was the pre-fence register copy described in region() — a
+            // compiler-placed v_mov of an asm-issued LDS read's destination — not the schedule (tests/test_gpu_ops.py::test_gemm_plain_bf16_k_image_regression).
             if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, false, 128>, g2, count, false, 128, s));
             else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, false, 64>, g2, count, false, 64, s));
-        } else {
-            // plain bf16 planes take the two-region refill as well (round 3). Round 2 kept them on SPREAD = 1 because the k-image B operand came out
-            // wrong, run-to-run different, under SPREAD = 2: that was the pre-fence register copy described in region() — a compiler-placed v_mov of
-            // an asm-issued LDS read's destination — not the schedule (tests/test_gpu_ops.py::test_gemm_plain_bf16_k_image_regression).
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, false, 128, 32, 4, 32, false, 0, 2>, g2, count, false, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, false, 64, 32, 4, 32, false, 0, 2>, g2, count, false, 64, s));
         }
-        if (prof) {
-            EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
-            g_prof.used += 1;
-        }
-        return 0;
-    }
-    if (x3) {
+    } else if (x3) {
         bool okx = true;
         for (int i = 0; i < count; ++i)
             okx = okx && gb.p[i].A_lo && gb.p[i].B_lo && gb.p[i].M % 64 == 0 && gb.p[i].N % 64 == 0 && gb.p[i].K % 64 == 0 && gb.p[i].lda % 8 == 0 &&
                   gb.p[i].ldb % 8 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].A_lo) % 16 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].B_lo) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(gb.p[i].A) % 16 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].B) % 16 == 0;
         EXORL_REQUIRE(okx, "gemm16_grouped: split-bf16 operands need M, N, K multiples of 64 and 16-byte aligned hi/lo planes");
-        g2.count = count;
-        g2.xcd_map = ((var & 2048) && xcd_map_ok(g2, count, 64)) ? 1 : 0;
         if (g16hx3_fits(g2, count)) {
             EXORL_TRY(g16hx3_enable());
             int t128 = 0;
             for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-            g2.xcd_map = 0;
             hipLaunchKernelGGL((gemm16hx3_kernel<AL != 0, BL != 0>), dim3(t128, 1, count), dim3(256), G16HX3_LDS, s, g2);
-        } else if (var & 16384) {
-            EXORL_TRY((g16d_enable<G16D_X3_STAGES, true>()));
-            hipLaunchKernelGGL((gemm16d_kernel<AL != 0, BL != 0, G16D_X3_STAGES, true>), g2.xcd_map ? dim3(tiles64 * count, 1, 1) : dim3(tiles64, 1, count),
-                               dim3(256), G16D_X3_STAGES * 4 * G16G_IMG, s, g2);
-        } else if (g2.xcd_map) hipLaunchKernelGGL((gemm16x3_kernel<AL != 0, BL != 0>), dim3(tiles64 * count, 1, 1), dim3(256), 0, s, g2);
-        else hipLaunchKernelGGL((gemm16x3_kernel<AL != 0, BL != 0>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
+        } else hipLaunchKernelGGL((gemm16x3_kernel<AL != 0, BL != 0>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
         EXORL_LAUNCH_CHECK();
-        if (prof) {
-            EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
-            g_prof.used += 1;
-        }
-        return 0;
-    }
-    if (exact64 && !(var & 128)) {         // LDS-DMA pipeline (bit 128 of the tuning variant forces the register-staged kernels)
+    } else if (exact64) {         // LDS-DMA pipeline
         if (g16h_fits(g2, count)) {
             EXORL_TRY(g16h_enable());
             int t128 = 0;
             for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-            if (g16h_stages() == 2) hipLaunchKernelGGL((gemm16h_kernel<AL != 0, BL != 0, 2>), dim3(t128, 1, count), dim3(256), 2 * G16H_STAGE, s, g2);
-            else hipLaunchKernelGGL((gemm16h_kernel<AL != 0, BL != 0, 4>), dim3(t128, 1, count), dim3(256), G16H_LDS, s, g2);
-        } else {
-            g2.count = count;
-            g2.xcd_map = ((var & 2048) && xcd_map_ok(g2, count, 64)) ? 1 : 0;     // measured: no gain over id order (12.8 vs 12.5 us) -> opt-in
-            if (var & 16384) {            // 10 x 16 KB = 160 KB, one workgroup per CU
-                EXORL_TRY((g16d_enable<10, false>()));
-                hipLaunchKernelGGL((gemm16d_kernel<AL != 0, BL != 0, 10, false>), g2.xcd_map ? dim3(tiles64 * count, 1, 1) : dim3(tiles64, 1, count),
-                                   dim3(256), 10 * 2 * G16G_IMG, s, g2);
-            } else if (var & 32768) {     // 5 x 16 KB = 80 KB, two workgroups per CU
-                EXORL_TRY((g16d_enable<5, false>()));
-                hipLaunchKernelGGL((gemm16d_kernel<AL != 0, BL != 0, 5, false>), g2.xcd_map ? dim3(tiles64 * count, 1, 1) : dim3(tiles64, 1, count),
-                                   dim3(256), 5 * 2 * G16G_IMG, s, g2);
-            } else if (g2.xcd_map) hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0>), dim3(tiles64 * count, 1, 1), dim3(256), 0, s, g2);
-            else if (var & 4096) hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0, 3>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);   // 3 WGs/CU
-            else if (var & 8192) hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0, 2>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);   // 5 WGs/CU
-            else hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
-        }
+            hipLaunchKernelGGL((gemm16h_kernel<AL != 0, BL != 0>), dim3(t128, 1, count), dim3(256), G16H_LDS, s, g2);
+        } else hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
         EXORL_LAUNCH_CHECK();
-        if (prof) {
-            EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
-            g_prof.used += 1;
-        }
-        return 0;
-    }
-    const int ns = (var & 32) ? 2 : ((var & 64) ? 4 : 3);
-#define EXORL_G16(BMv, NSv, Gv) hipLaunchKernelGGL((gemm16_kernel<AL, BL, BMv, NSv, Gv>), dim3(big ? tiles128 : tiles64, 1, count), dim3(256), 0, s, g2)
-    if (exact) {
-        if (big) { if (ns == 2) EXORL_G16(128, 2, false); else if (ns == 3) EXORL_G16(128, 3, false); else EXORL_G16(128, 4, false); }
-        else     { if (ns == 2) EXORL_G16(64, 2, false); else if (ns == 3) EXORL_G16(64, 3, false); else EXORL_G16(64, 4, false); }
     } else {
-        if (big) EXORL_G16(128, 2, true); else EXORL_G16(64, 2, true);
+        // register-staged: three register stages where every problem tiles exactly, else two with bounds guards
+        if (exact && big) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 128, 3, false>), dim3(tiles128, 1, count), dim3(256), 0, s, g2);
+        else if (exact) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 64, 3, false>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
+        else if (big) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 128, 2, true>), dim3(tiles128, 1, count), dim3(256), 0, s, g2);
+        else hipLaunchKernelGGL((gemm16_kernel<AL, BL, 64, 2, true>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
+        EXORL_LAUNCH_CHECK();
     }
-#undef EXORL_G16
-    EXORL_LAUNCH_CHECK();
     if (prof) {
         EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
         g_prof.used += 1;
@@ -1796,7 +1424,7 @@ int gemm16_grouped_mixed(const int* a_layouts, const Gemm16Problem* probs, int c
     EXORL_REQUIRE(count >= 1 && count <= 4, "gemm16_grouped_mixed: count %d out of range", count);
     Gemm16Batch gb;
     memset(&gb, 0, sizeof(gb));
-    bool ok = g_gemm16_variant < 0 || !(g_gemm16_variant & 128);
+    bool ok = true;
     int t64 = 0;
     double flops = 0;
     for (int i = 0; i < count; ++i) {
@@ -1815,7 +1443,7 @@ int gemm16_grouped_mixed(const int* a_layouts, const Gemm16Problem* probs, int c
         for (int i = 0; i < count; ++i) EXORL_TRY(gemm16_grouped(a_layouts[i], 1, probs + i, 1, false, false, s));
         return 0;
     }
-    gb.swizzle = (g_gemm16_variant >= 0 && (g_gemm16_variant & 8)) ? 0 : 1;
+    gb.swizzle = 1;
     const bool prof = g_prof.on && g_prof.used < PROF_MAX_LAUNCHES;
     if (prof) {
         if (g_prof.ev.size() < 2 * (g_prof.used + 1)) {
@@ -1829,62 +1457,24 @@ int gemm16_grouped_mixed(const int* a_layouts, const Gemm16Problem* probs, int c
         EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used], s));
     }
     if (const int tn = g16p_pick(gb, count, x3)) {
-        const int var_ = g_gemm16_variant < 0 ? 0 : g_gemm16_variant;
-        const bool sp1 = (var_ & 536870912) != 0;            // the previous schedule (SPREAD = 1)
-        bool done = false;
-#ifdef EXORL_GEMM_EXPERIMENTS
-        if (x3 && (var_ & 8388608)) {
-            done = true;
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16w_mixed_kernel<true, 128>, gb, count, true, 128, s, 32, 4, 512));
-            else EXORL_TRY(g16p_launch(gemm16w_mixed_kernel<true, 64>, gb, count, true, 64, s, 32, 4, 512));
-        }
-#endif
-        if (done) {
-        } else if (x3 && sp1) {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 128>, gb, count, true, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 64>, gb, count, true, 64, s));
-        } else if (x3) {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 128, 2>, gb, count, true, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 64, 2>, gb, count, true, 64, s));
-        } else if (sp1) {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 128>, gb, count, false, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 64>, gb, count, false, 64, s));
-        } else {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 128, 2>, gb, count, false, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 64, 2>, gb, count, false, 64, s));
-        }
+        if (x3 && tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 128>, gb, count, true, 128, s));
+        else if (x3) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 64>, gb, count, true, 64, s));
+        else if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 128>, gb, count, false, 128, s));
+        else EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 64>, gb, count, false, 64, s));
     } else if (x3) {
-        gb.count = count;
-        gb.xcd_map = (g_gemm16_variant >= 0 && (g_gemm16_variant & 2048) && xcd_map_ok(gb, count, 64)) ? 1 : 0;
         if (g16hx3_fits(gb, count)) {
             EXORL_TRY(g16hx3_enable());
             int t128 = 0;
             for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-            gb.xcd_map = 0;
             hipLaunchKernelGGL(gemm16hx3_mixed_kernel, dim3(t128, 1, count), dim3(256), G16HX3_LDS, s, gb);
-        } else if (g_gemm16_variant >= 0 && (g_gemm16_variant & 16384)) {
-            EXORL_TRY((g16d_enable<G16D_X3_STAGES, true>()));
-            hipLaunchKernelGGL((gemm16d_mixed_kernel<G16D_X3_STAGES, true>), gb.xcd_map ? dim3(t64 * count, 1, 1) : dim3(t64, 1, count), dim3(256),
-                               G16D_X3_STAGES * 4 * G16G_IMG, s, gb);
-        } else if (gb.xcd_map) hipLaunchKernelGGL(gemm16x3_mixed_kernel, dim3(t64 * count, 1, 1), dim3(256), 0, s, gb);
-        else hipLaunchKernelGGL(gemm16x3_mixed_kernel, dim3(t64, 1, count), dim3(256), 0, s, gb);
+        } else hipLaunchKernelGGL(gemm16x3_mixed_kernel, dim3(t64, 1, count), dim3(256), 0, s, gb);
     } else if (g16h_fits(gb, count)) {
         EXORL_TRY(g16h_enable());
         int t128 = 0;
         for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-        if (g16h_stages() == 2) hipLaunchKernelGGL(gemm16h_mixed_kernel<2>, dim3(t128, 1, count), dim3(256), 2 * G16H_STAGE, s, gb);
-        else hipLaunchKernelGGL(gemm16h_mixed_kernel<4>, dim3(t128, 1, count), dim3(256), G16H_LDS, s, gb);
+        hipLaunchKernelGGL(gemm16h_mixed_kernel, dim3(t128, 1, count), dim3(256), G16H_LDS, s, gb);
     } else {
-        gb.count = count;
-        gb.xcd_map = (g_gemm16_variant >= 0 && (g_gemm16_variant & 2048) && xcd_map_ok(gb, count, 64)) ? 1 : 0;
-        if (g_gemm16_variant >= 0 && (g_gemm16_variant & 16384)) {
-            EXORL_TRY((g16d_enable<10, false>()));
-            hipLaunchKernelGGL((gemm16d_mixed_kernel<10, false>), gb.xcd_map ? dim3(t64 * count, 1, 1) : dim3(t64, 1, count), dim3(256), 10 * 2 * G16G_IMG, s, gb);
-        } else if (g_gemm16_variant >= 0 && (g_gemm16_variant & 32768)) {
-            EXORL_TRY((g16d_enable<5, false>()));
-            hipLaunchKernelGGL((gemm16d_mixed_kernel<5, false>), gb.xcd_map ? dim3(t64 * count, 1, 1) : dim3(t64, 1, count), dim3(256), 5 * 2 * G16G_IMG, s, gb);
-        } else if (gb.xcd_map) hipLaunchKernelGGL(gemm16g_mixed_kernel, dim3(t64 * count, 1, 1), dim3(256), 0, s, gb);
-        else hipLaunchKernelGGL(gemm16g_mixed_kernel, dim3(t64, 1, count), dim3(256), 0, s, gb);
+        hipLaunchKernelGGL(gemm16g_mixed_kernel, dim3(t64, 1, count), dim3(256), 0, s, gb);
     }
     EXORL_LAUNCH_CHECK();
     if (prof) {
@@ -1934,8 +1524,7 @@ int gemm16_grouped(int a_layout, int b_layout, const Gemm16Problem* probs, int c
     gb.accumulate = accumulate ? 1 : 0;
     for (int i = 0; i < count; ++i)
         if (probs[i].head_part)
-            EXORL_REQUIRE(probs[i].head_w && a_layout == 0 && b_layout == 0 && !accumulate && gemm16_head_slots(probs, count) > 0 &&
-                          !(g_gemm16_variant >= 0 && (g_gemm16_variant & 4194304)),
+            EXORL_REQUIRE(probs[i].head_w && a_layout == 0 && b_layout == 0 && !accumulate && gemm16_head_slots(probs, count) > 0,
                           "gemm16_grouped: a folded head needs a forward launch on the 128 x TN kernels (ask gemm16_head_slots first)");
     if (a_layout == 0 && b_layout == 0) return launch16<0, 0>(gb, count, t64, t128, s);
     if (a_layout == 0 && b_layout == 1) return launch16<0, 1>(gb, count, t64, t128, s);
@@ -2006,7 +1595,7 @@ static bool aligned_for_vec(const GemmProblem& p, int al, int bl) {
 // bf16 planes in memory, M % 128 = 0, N % 64 = 0, K % 128 = 0. For problems large enough to pay for it this adapter writes zero-padded hi/lo
 // planes of both operands into a scratch arena (one elementwise pass each: 8 B per element moved), runs the plane kernels, and — when C does
 // not tile — copies the padded result back (bias, ReLU in the GEMM epilogue as always; accumulate in the copy). Groups of more than four
-// problems (Disagreement's five models) go in chunks. exorl_gemm_tune bit 65536 switches it off (A/B).
+// problems (Disagreement's five models) go in chunks.
 struct PlaneArena { unsigned char* buf = nullptr; size_t bytes = 0; };
 static PlaneArena g_plane_arena;
 
@@ -2049,7 +1638,6 @@ __global__ void pad_bias_kernel(const float* __restrict__ b, float* __restrict__
 }
 
 static bool planes_adapter_wants(int al, int bl, const GemmProblem* probs, int count) {
-    if (g_gemm16_variant >= 0 && (g_gemm16_variant & (65536 | 262144))) return false;
     if (!((al == 0 && bl == 0) || (al == 0 && bl == 1) || (al == 1 && bl == 1))) return false;
     for (int i = 0; i < count; ++i)
         if (probs[i].M < 256 || probs[i].N < 256 || probs[i].K < 256) return false;       // conversion passes + padded tiles must be worth it
@@ -2059,9 +1647,9 @@ static bool planes_adapter_wants(int al, int bl, const GemmProblem* probs, int c
 // 0 = done; -1 = not taken (the caller runs the generic kernel); > 0 = error
 // C written in place by the plane kernels: whole row tiles, 16-byte rows and bias; a width that is not a multiple of the 128-column tile is
 // handled by the epilogue's column guard (n_store) as long as it is a multiple of 4 (round 3: the padded copy + from_padded_kernel pass of the
-// 39200-wide module layers was 0.7 ms of an ICM update on pixels and 2.0 ms of a Disagreement update; exorl_gemm_tune bit 134217728 brings it back)
+// 39200-wide module layers was 0.7 ms of an ICM update on pixels and 2.0 ms of a Disagreement update; TUNE_ADAPTER_PADDED brings it back)
 static bool adapter_direct(const GemmProblem& p) {
-    const bool wide_ok = p.N % 128 == 0 || (p.N % 4 == 0 && !(tune_variant() & 134217728));
+    const bool wide_ok = p.N % 128 == 0 || (p.N % 4 == 0 && !(tune_variant() & TUNE_ADAPTER_PADDED));
     return p.M % 128 == 0 && wide_ok && p.ldc % 4 == 0 && reinterpret_cast<uintptr_t>(p.C) % 16 == 0 &&
            (!p.bias || reinterpret_cast<uintptr_t>(p.bias) % 16 == 0);
 }
@@ -2241,13 +1829,6 @@ extern "C" int exorl_profile_event_overhead(float* ms_out, void* stream) {
 }
 
 namespace exorl { int tune_variant() { return g_gemm16_variant < 0 ? 0 : g_gemm16_variant; } }
-
-extern "C" int exorl_debug_gemm_stamps(uint64_t* out_host, int32_t n_words) {
-    EXORL_REQUIRE(out_host && n_words > 0 && n_words <= 8 * 1024, "debug_gemm_stamps: bad arguments");
-    EXORL_CHECK_HIP(hipDeviceSynchronize());
-    EXORL_CHECK_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(exorl::g16p_stamps), (size_t)n_words * sizeof(uint64_t)));
-    return 0;
-}
 
 extern "C" int exorl_debug_precision_override(int32_t mask) {
     exorl::g_prec_override = mask;

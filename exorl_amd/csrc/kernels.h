@@ -139,7 +139,12 @@ struct DoutSpec {
 int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, unsigned short* dz_bf16, float* P, int rows,
              int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, unsigned short* dz_lo = nullptr);
 int head_chunks(int rows);
-int tune_variant();      // exorl_gemm_tune's experiment bits (0 = defaults)
+int tune_variant();      // exorl_gemm_tune's bits (0 = defaults): the reference paths below, each read at one decision point
+constexpr int TUNE_CONV_WGRAD_TILE = 64;             // 32 -> 32 conv weight gradient on the tile kernel, not conv_wgrad_ws_kernel
+constexpr int TUNE_ACT_GENERIC = 256;                // act() on the generic multi-launch path
+constexpr int TUNE_CONV_PER_IMAGE = 8388608;         // wave-specialised conv forward / dgrad: one image per workgroup, not the persistent form
+constexpr int TUNE_ADAPTER_PADDED = 134217728;       // planes adapter: ragged widths through the padded copy
+constexpr int TUNE_CONV_STRIP = 1073741824;          // 32 -> 32 conv forward / dgrad on the strip kernel, not conv3x3_ws_kernel
 int prec_override_mask();    // exorl_debug_precision_override's bits (0 = none; diagnostic)
 // Scalar critic heads, forward and backward in one kernel (single-GPU whole-step path, no metrics): Q1,Q2 (and the target's
 // Q1',Q2') row dots, the loss gradient at the head output, dz2 = dQ * W2 * [h2 > 0] and the per-chunk parameter partials.
@@ -190,7 +195,7 @@ struct FusedAdamArgs {
     unsigned long long* bump;
 };
 struct ShadowSpec;
-int finalize_adam(const FinalizeArgs& f, const FusedAdamArgs& a, const ShadowSpec& sh, hipStream_t s, int part = 0);
+int finalize_adam(const FinalizeArgs& f, const FusedAdamArgs& a, const ShadowSpec& sh, hipStream_t s);
 
 // Derived copies of a net's weights that the kernels read: W0T[in][H] per trunk (coalesced first-layer reads)
 // and, in bf16 mode, W1 as bf16 per head (MFMA operand). Kept current by the Adam kernel itself.

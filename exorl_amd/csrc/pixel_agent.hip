@@ -583,7 +583,7 @@ int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t
     }
     a->have_feat_o = a->have_feat_n = false;
     // ---- update_critic (ddpg.py:240-268)
-    const bool pair = c.meta_dim == 0 && !(tune_variant() & 4096);      // exorl_gemm_tune bit 4096: separate trunk launches (A/B)
+    const bool pair = c.meta_dim == 0;
     if (pair) EXORL_TRY(trunk_forward_pair(a, a->actor, Pa, a->ta_n, a->critic, Pt, a->tt, a->feat_n, B, prec, s));
     else EXORL_TRY(trunk_forward(a, a->actor, Pa, a->feat_n, mt, B, a->ta_n, prec, s));
     Mlp& pol = a->actor.head[0];
@@ -669,7 +669,7 @@ int exorl_pixel_agent_act(exorl_pixel_agent_t* a, const unsigned char* obs_dev, 
     float* feat = nullptr;
     EXORL_TRY(exorl_encoder_forward_prec(a->flat[0][0], c.c_in, c.hw, x, 1, ews, &feat, a->cfg.precision, s));
     Mlp& pol0 = a->actor.head[0];
-    if (act_fast_supported(1, F, c.hidden_dim, A) && F <= 256 && !(tune_variant() & 256)) {
+    if (act_fast_supported(1, F, c.hidden_dim, A) && F <= 256 && !(tune_variant() & TUNE_ACT_GENERIC)) {
         // two launches behind the encoder: the 39200-wide trunk with an in-launch combine + LayerNorm + tanh, then the policy
         // (Linear + ReLU recomputed per workgroup, four Linear(H, H) neurons per workgroup, head + tanh + TruncatedNormal draw in the last one)
         const float* Pa = a->flat[1][0];

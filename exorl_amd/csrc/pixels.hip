@@ -10,7 +10,7 @@
 // In the bf16 / split-bf16 / three-plane precision modes the three 32 -> 32 stride-1 layers run as MFMA implicit GEMMs instead. Product path
 // (round 3): conv3x3_ws_kernel (forward, dgrad; persistent form for batches) and conv_wgrad_ws_kernel — wave-specialised workgroups over a
 // circular row buffer in LDS; the round-2 kernels conv3x3_mfma_kernel / conv_wgrad_mfma_kernel remain as the fallback for geometries those
-// decline and for A/B (exorl_gemm_tune bits 1073741824 / 64). The first layer: forward over row-major strips (conv1_strip_kernel, every mode),
+// decline and as reference paths (TUNE_CONV_STRIP / TUNE_CONV_WGRAD_TILE). The first layer: forward over row-major strips (conv1_strip_kernel, every mode),
 // weight gradients on MFMA with operands built in registers (conv1_wgrad_mfma_kernel); the tile kernels stay for precision fp32's other
 // layers and as fallbacks.
 #include <type_traits>
@@ -278,11 +278,7 @@ constexpr int CM_IPT = 15;                 // staged (channel pair, y, x) items 
 // NPL = operand planes: 1 plain bf16, 2 split-bf16 (hi*hi + hi*lo + lo*hi), 3 three-plane split (EXORL_PREC_BF16X6: + hi*l3 + l3*hi + lo*lo,
 // products accurate to 3 * 2^-24 — the parity-grade convolution of the pixel agents at ~2x the split-bf16 kernel's MFMA time, where the fp32
 // FMA kernel it replaces took 5.8x)
-// STAMP (diagnostic build, exorl_gemm_tune bit 8192; no product launch takes it): waves 0 and 7 of every workgroup add up the shader-clock
-// cycles of each phase of a pass (convert + LDS write | barrier | fetch issue | MFMA loop with its LDS reads | stores | barrier) over
-// the workgroup's passes and leave them in g_conv_stamps[workgroup][2][8] (exorl_debug_conv_stamps reads them back).
-__device__ unsigned long long g_conv_stamps[1024 * 2 * 8];
-template <int NPL, bool MASK, bool STAMP = false>
+template <int NPL, bool MASK>
 __global__ __launch_bounds__(CM_THREADS) void conv3x3_mfma_kernel(const float* __restrict__ in, const float* __restrict__ Wt,
                                                                   const float* __restrict__ bias, const float* __restrict__ mask,
                                                                   float* __restrict__ out, int ih, int iw, int oh, int ow, int pad, int relu,
@@ -347,18 +343,11 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_mfma_kernel(const float* _
     // body has NO run-time branch around a memory instruction — which is what lets the compiler count: the wait in front of the next pass's
     // conversion becomes vmcnt(<this pass's stores>) instead of vmcnt(0), i.e. the stores of pass t drain under pass t + 1 instead of in
     // front of it (gfx9 counts stores in vmcnt too; with the guarded tail path in the loop every pass waited for its predecessor's stores).
-    unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto now = [&]() -> unsigned long long {
-        if constexpr (STAMP) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return __builtin_amdgcn_s_memtime(); }
-        return 0ull;
-    };
-    const unsigned long long t_begin = now();
     auto body = [&](int pass, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         int y0, rows;
         strip(pass, y0, rows);
         const int nj = rows * sw, p0 = pass * CM_PASS;
-        const unsigned long long t0 = now();
 #pragma unroll
         for (int u = 0; u < CM_IPT; ++u) {
             const int j = jl + 32 * u;
@@ -378,11 +367,8 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_mfma_kernel(const float* _
                 }
             }
         }
-        const unsigned long long t1 = now();
         __syncthreads();
-        const unsigned long long t2 = now();
         if constexpr (FULL) fetch(pass + 1);
-        const unsigned long long t3 = now();
         // C layout of the 32x32 MFMA: reg r of lane l = pixel (r & 3) + 8 (r >> 2) + 4 (l >> 5) of the wave's 32, channel l & 31 — four
         // consecutive pixels of one channel per register quad, i.e. 16 contiguous bytes of the NCHW map: the lane stores them itself
         // (and fetches the dgrad mask the same way, now, behind the MFMA work); no output staging, no second barrier.
@@ -428,8 +414,6 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_mfma_kernel(const float* _
                 }
             }
         }
-        if constexpr (STAMP) asm volatile("" :: "v"(acc[0]), "v"(accx[0]), "v"(accy[0]));
-        const unsigned long long t4 = now();
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             float v[4];
@@ -450,19 +434,7 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_mfma_kernel(const float* _
                     if (pp + e < npix) orow[pp + e] = v[e];
             }
         }
-        const unsigned long long t5 = now();
         __syncthreads();                   // every wave is past its MFMA reads before the next pass rewrites the input planes
-        if constexpr (STAMP) {
-            const unsigned long long t6 = now();
-            st[0] += t1 - t0; st[1] += t2 - t1; st[2] += t3 - t2; st[3] += t4 - t3; st[4] += t5 - t4; st[5] += t6 - t5;
-        }
-    };
-    auto leave = [&]() {
-        if constexpr (STAMP) {
-            st[6] = now() - t_begin;
-            if ((wave == 0 || wave == 7) && lane == 0 && blockIdx.x < 1024 && blockIdx.y == 0)
-                for (int i = 0; i < 8; ++i) g_conv_stamps[(blockIdx.x * 2 + (wave ? 1 : 0)) * 8 + i] = st[i];
-        }
     };
     if (gridDim.y > 1) {                   // few images (act() on one frame): one pass per workgroup, gridDim.y = npass workgroups per image
         if ((int)blockIdx.y < npass) body((int)blockIdx.y, std::false_type{});
@@ -470,11 +442,10 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_mfma_kernel(const float* _
     }
     for (int pass = 0; pass + 1 < npass; ++pass) body(pass, std::true_type{});
     body(npass - 1, std::false_type{});
-    leave();
 }
 
 // ---- the same implicit GEMM with the waves specialised (round 3) ------------------------------------------------------------------------
-// Stamps of the kernel above (tools/micro/conv_stamp_bench.py, profiles/r03_conv_phase_stamps.txt): inside its MFMA loop the matrix pipe is
+// In-kernel clock stamps of the kernel above (profiles/r03_conv_phase_stamps.txt): inside its MFMA loop the matrix pipe is
 // at its issue floor, but the loop is 41-45 % of the kernel — conversion + LDS writes (15 %), issuing the next strip's loads (13-15 %), stores and
 // the two barriers run with the pipe idle, because all eight waves walk the phases together and one workgroup owns the CU. Here waves 0-3
 // (one per SIMD) only multiply — a pass is 128 pixels, 32 per wave — and waves 4-7 (their SIMD mates) only stage: the input rows live in a
@@ -492,11 +463,11 @@ constexpr int CW_DUMMY = 256 * 8 + 176;    // a dummy 8-byte word per producer t
 // PERSIST: the workgroup walks images blockIdx.x, + gridDim.x, ... (launched with one workgroup per CU): the weight fragments are loaded once, and
 // the loads the producers issue past an image's last pass — wasted in the one-image form — fetch the first rows of the workgroup's NEXT image,
 // so that between two images only their conversion stands in front of the consumers (the per-image prologue was 15-20 % of the kernel).
-template <int NPL, bool MASK, bool STAMP = false, bool PERSIST = false>           // MASK = the dgrad launches: ReLU mask of the layer below AND zero padding (pad = 2)
+template <int NPL, bool MASK, bool PERSIST = false>           // MASK = the dgrad launches: ReLU mask of the layer below AND zero padding (pad = 2)
 __global__ __launch_bounds__(CM_THREADS) void conv3x3_ws_kernel(const float* __restrict__ in, const float* __restrict__ Wt,
                                                                 const float* __restrict__ bias, const float* __restrict__ mask,
                                                                 float* __restrict__ out, int ih, int iw, int oh, int ow, int pad, int relu,
-                                                                int rb, int flags, int nimg) {
+                                                                int rb, int nimg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cm_lds[];
     constexpr bool X3 = NPL >= 2, X6 = NPL == 3;
     constexpr int PIXB = cw_pixb(NPL);
@@ -506,7 +477,7 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_ws_kernel(const float* __r
     cbf16x8* wh = reinterpret_cast<cbf16x8*>(cm_lds + ((ring_b + CW_DUMMY + 15) & ~15));   // [NPL][18 k-steps][64 lanes] B fragments
     int n = blockIdx.x;                                                                    // the image (PERSIST: the current one)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool producer = (flags & 2) ? wave >= 4 : wave < 4;                              // wave-uniform role; the older half stages (measured)
+    const bool producer = wave < 4;                              // wave-uniform role; the older half stages (measured)
     const int cw = wave & 3;                                                               // consumer index: pixels 32 cw .. of a pass
     const int kg = lane >> 5, col = lane & 31;
     {
@@ -723,14 +694,6 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_ws_kernel(const float* __r
             if ((i & 3) == 3) out_store(pass, i >> 2, pass + 1 < npass);
         }
     };
-    // STAMP (diagnostic, tuning bit 8192): consumer wave 0 {pass work, barrier wait, -, -, -, -, whole kernel, prologue} and the first producer wave
-    // {even passes: commit, fetch issue, barrier; odd passes: commit + fetch, barrier; -, whole kernel, prologue} into g_conv_stamps, summed over the passes
-    unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto now = [&]() -> unsigned long long {
-        if constexpr (STAMP) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return __builtin_amdgcn_s_memtime(); }
-        return 0ull;
-    };
-    const unsigned long long t_begin = now();
     // The two roles run SEPARATE loops with the same number of barriers (one after the prologue, one per pass). In one shared loop the
     // compiler's wait-count analysis merges the roles at the loop head: the consumers then wait out their own stores (vmcnt(0)) in front of
     // every pass because their registers alias the producers' pending loads, and the producers cannot tell which of their two batches is the
@@ -749,57 +712,39 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_ws_kernel(const float* __r
             };
             if (odd) { fetch(0, QA); fetch(ym, QB); } else { fetch(0, QB); fetch(ym, QA); }
             for (; n < nimg; n += G) {
-                const unsigned long long tw = now();
                 if (odd) { commit(0, ym, QA); commit(ym, need, QB); } else { commit(0, ym, QB); commit(ym, need, QA); }
                 fetch(end_row(0), QA);
                 fetch(end_row(1), QB);
                 __syncthreads();
-                st[7] += now() - tw;
                 int t = 0;
                 for (; t + 1 < npass; t += 2) {
-                    const unsigned long long ta = now();
                     commit(end_row(t), end_row(t + 1), QA);
-                    const unsigned long long tb = now();
                     fetch_k(t + 3, QA);
-                    const unsigned long long tc = now();
                     __syncthreads();
-                    const unsigned long long td = now();
                     commit(end_row(t + 1), end_row(t + 2), QB);
                     fetch_k(t + 4, QB);
-                    const unsigned long long te = now();
                     __syncthreads();
-                    if constexpr (STAMP) { st[0] += tb - ta; st[1] += tc - tb; st[2] += td - tc; st[3] += te - td; st[4] += now() - te; }
                 }
                 if (t < npass) __syncthreads();
             }
         } else {
             for (; n < nimg; n += G) {
-                const unsigned long long tw = now();
                 first_pixel();
                 prep(0);
                 __syncthreads();
-                st[7] += now() - tw;
-                unsigned long long ta = now();
                 kloop(0, std::false_type{}, a0, a1, a2, a0, a1, a2);
-                unsigned long long tc = now();
                 __syncthreads();
                 prep(1);
-                if constexpr (STAMP) { st[0] += tc - ta; st[1] += now() - tc; }
                 int t = 1;
                 for (; t + 1 < npass; t += 2) {
-                    ta = now();
                     mask_load(t - 1);
                     kloop(t, std::true_type{}, b0, b1, b2, a0, a1, a2);
-                    tc = now();
                     __syncthreads();
                     prep(t + 1);
-                    const unsigned long long td = now();
                     mask_load(t);
                     kloop(t + 1, std::true_type{}, a0, a1, a2, b0, b1, b2);
-                    const unsigned long long te = now();
                     __syncthreads();
                     prep(t + 2);
-                    if constexpr (STAMP) { st[0] += (tc - ta) + (te - td); st[1] += (td - tc) + (now() - te); }
                 }
                 if (t < npass) {
                     mask_load(t - 1);
@@ -827,50 +772,33 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_ws_kernel(const float* __r
         fetch(end_row(t0), QA);
         fetch(end_row(t0 + 1), QB);
         __syncthreads();
-        st[7] = now() - t_begin;
         int t = t0;
         for (; t + 1 < t1; t += 2) {
-            const unsigned long long ta = now();
-            if constexpr (STAMP) { asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); st[5] += now() - ta; }      // the wait for batch A alone
             commit(end_row(t), end_row(t + 1), QA);                // the rows pass t + 1 adds, into slots pass t - 1 released at the last barrier
-            const unsigned long long tb = now();
             fetch(end_row(t + 2), QA);
-            const unsigned long long tc = now();
             __syncthreads();
-            const unsigned long long td = now();
             commit(end_row(t + 1), end_row(t + 2), QB);
             fetch(end_row(t + 3), QB);
-            const unsigned long long te = now();
             __syncthreads();
-            if constexpr (STAMP) { st[0] += tb - ta; st[1] += tc - tb; st[2] += td - tc; st[3] += te - td; st[4] += now() - te; }
         }
         if (t < t1) __syncthreads();                               // the last pass of an odd count: nothing left to stage
     } else {
         prep(t0);
         __syncthreads();
-        st[7] = now() - t_begin;
         // pass t0 into set a; then pairs (b with a leaving, a with b leaving); the mask of pass t - 1 is fetched at the head of pass t's k-loop
-        unsigned long long ta = now();
         kloop(t0, std::false_type{}, a0, a1, a2, a0, a1, a2);          // no previous pass: the last three arguments are not read
-        unsigned long long tc = now();
         __syncthreads();
         prep(t0 + 1);
-        if constexpr (STAMP) { st[0] += tc - ta; st[1] += now() - tc; }
         int t = t0 + 1;
         for (; t + 1 < t1; t += 2) {
-            ta = now();
             mask_load(t - 1);
             kloop(t, std::true_type{}, b0, b1, b2, a0, a1, a2);
-            tc = now();
             __syncthreads();
             prep(t + 1);
-            const unsigned long long td = now();
             mask_load(t);
             kloop(t + 1, std::true_type{}, a0, a1, a2, b0, b1, b2);
-            const unsigned long long te = now();
             __syncthreads();
             prep(t + 2);
-            if constexpr (STAMP) { st[0] += (tc - ta) + (te - td); st[1] += (td - tc) + (now() - te); }
         }
         if (t < t1) {
             mask_load(t - 1);
@@ -878,11 +806,6 @@ __global__ __launch_bounds__(CM_THREADS) void conv3x3_ws_kernel(const float* __r
             __syncthreads();
             epilogue(t, b0, b1, b2);
         } else epilogue(t - 1, a0, a1, a2);
-    }
-    if constexpr (STAMP) {
-        st[6] = now() - t_begin;
-        if ((wave == 0 || wave == 4) && lane == 0 && blockIdx.x < 1024 && blockIdx.y == 0)
-            for (int i = 0; i < 8; ++i) g_conv_stamps[(blockIdx.x * 2 + (producer ? 1 : 0)) * 8 + i] = st[i];
     }
 }
 
@@ -929,19 +852,18 @@ static int conv3x3_mfma(const float* in, const float* Wt, const float* bias, con
         attr = true;
     }
     // the wave-specialised kernel: forward launches (no mask, no padding) and dgrad launches (mask and padding); 32-bit buffer offsets.
-    // exorl_gemm_tune bit 1073741824 keeps the strip kernel (A/B)
-    if (!(tune_variant() & 1073741824) && conv3x3_ws_fits(oh, ow, npl) && (int64_t)n * CONV_CO * ih * iw * 4 < (1ll << 31) && ((mask != nullptr) == (pad != 0))) {
+    // TUNE_CONV_STRIP keeps the strip kernel (reference path)
+    if (!(tune_variant() & TUNE_CONV_STRIP) && conv3x3_ws_fits(oh, ow, npl) && (int64_t)n * CONV_CO * ih * iw * 4 < (1ll << 31) && ((mask != nullptr) == (pad != 0))) {
         const int rb = conv3x3_ws_rows(ow);
         const size_t wlds = conv3x3_ws_lds(ow, npl);
         static bool wattr = false;
         static int ncu = 256;
         if (!wattr) {
-#define EXORL_WA(NN, MM, SS, PP) EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_ws_kernel<NN, MM, SS, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-            EXORL_WA(3, true, false, false); EXORL_WA(3, false, false, false); EXORL_WA(2, true, false, false); EXORL_WA(2, false, false, false);
-            EXORL_WA(1, true, false, false); EXORL_WA(1, false, false, false);
-            EXORL_WA(3, true, false, true); EXORL_WA(3, false, false, true); EXORL_WA(2, true, false, true); EXORL_WA(2, false, false, true);
-            EXORL_WA(1, true, false, true); EXORL_WA(1, false, false, true);
-            EXORL_WA(3, false, true, true); EXORL_WA(2, false, true, true);
+#define EXORL_WA(NN, MM, PP) EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_ws_kernel<NN, MM, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+            EXORL_WA(3, true, false); EXORL_WA(3, false, false); EXORL_WA(2, true, false); EXORL_WA(2, false, false);
+            EXORL_WA(1, true, false); EXORL_WA(1, false, false);
+            EXORL_WA(3, true, true); EXORL_WA(3, false, true); EXORL_WA(2, true, true); EXORL_WA(2, false, true);
+            EXORL_WA(1, true, true); EXORL_WA(1, false, true);
 #undef EXORL_WA
             int dev = 0, v = 0;
             EXORL_CHECK_HIP(hipGetDevice(&dev));
@@ -949,20 +871,17 @@ static int conv3x3_mfma(const float* in, const float* Wt, const float* bias, con
             wattr = true;
         }
         const int wpass = (oh * ow + CW_PASS - 1) / CW_PASS, wgy = n <= 8 ? wpass : 1;
-        const int wflags = (tune_variant() & 32) ? 2 : 0;          // experiment: the younger half of the workgroup stages
-        // persistent form: one workgroup per CU walks the images; needs the first pass's rows in two batches. exorl_gemm_tune bit 8388608: one image per workgroup (A/B)
+        // persistent form: one workgroup per CU walks the images; needs the first pass's rows in two batches. TUNE_CONV_PER_IMAGE: one image per workgroup (reference path)
         const int wchunk = (32 * CW_PI) / (ow + 2), wneed = ((CW_PASS < oh * ow ? CW_PASS : oh * ow) - 1) / ow + 3;
-        const bool persist = wgy == 1 && wneed <= 2 * wchunk && !(npl == 3 && mask) && !(tune_variant() & 8388608);      // (three planes + mask: 256 VGPRs and a spill)
+        const bool persist = wgy == 1 && wneed <= 2 * wchunk && !(npl == 3 && mask) && !(tune_variant() & TUNE_CONV_PER_IMAGE);      // (three planes + mask: 256 VGPRs and a spill)
         const int gx = persist ? (n < ncu ? n : ncu) : n;
-#define EXORL_CW(NN, MM, SS) do { \
-            if (persist) hipLaunchKernelGGL((conv3x3_ws_kernel<NN, MM, SS, true>), dim3(gx, 1), dim3(CM_THREADS), wlds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, rb, wflags, n); \
-            else hipLaunchKernelGGL((conv3x3_ws_kernel<NN, MM, false, false>), dim3(n, wgy), dim3(CM_THREADS), wlds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, rb, wflags, n); \
+#define EXORL_CW(NN, MM) do { \
+            if (persist) hipLaunchKernelGGL((conv3x3_ws_kernel<NN, MM, true>), dim3(gx, 1), dim3(CM_THREADS), wlds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, rb, n); \
+            else hipLaunchKernelGGL((conv3x3_ws_kernel<NN, MM, false>), dim3(n, wgy), dim3(CM_THREADS), wlds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, rb, n); \
         } while (0)
-        if ((tune_variant() & 8192) && !mask && npl >= 2 && persist) {          // diagnostic: the stamped build (persistent form)
-            if (npl == 3) EXORL_CW(3, false, true); else EXORL_CW(2, false, true);
-        } else if (npl == 3) { if (mask) EXORL_CW(3, true, false); else EXORL_CW(3, false, false); }
-        else if (npl == 2) { if (mask) EXORL_CW(2, true, false); else EXORL_CW(2, false, false); }
-        else               { if (mask) EXORL_CW(1, true, false); else EXORL_CW(1, false, false); }
+        if (npl == 3)      { if (mask) EXORL_CW(3, true); else EXORL_CW(3, false); }
+        else if (npl == 2) { if (mask) EXORL_CW(2, true); else EXORL_CW(2, false); }
+        else               { if (mask) EXORL_CW(1, true); else EXORL_CW(1, false); }
 #undef EXORL_CW
         EXORL_LAUNCH_CHECK();
         return 0;
@@ -970,18 +889,6 @@ static int conv3x3_mfma(const float* in, const float* Wt, const float* bias, con
     // a handful of images (act(): one) cannot fill the chip with one workgroup each: spread an image's 256-pixel passes over workgroups
     const int npass = (oh * ow + CM_PASS - 1) / CM_PASS, gy = n <= 8 ? npass : 1;
 #define EXORL_CM(NN, MM) hipLaunchKernelGGL((conv3x3_mfma_kernel<NN, MM>), dim3(n, gy), dim3(CM_THREADS), lds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, plane)
-    if ((tune_variant() & 8192) && !mask && npl >= 2) {          // diagnostic: the stamped build of the forward kernel
-        static bool sattr = false;
-        if (!sattr) {
-            EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_mfma_kernel<3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_mfma_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            sattr = true;
-        }
-        if (npl == 3) hipLaunchKernelGGL((conv3x3_mfma_kernel<3, false, true>), dim3(n, gy), dim3(CM_THREADS), lds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, plane);
-        else hipLaunchKernelGGL((conv3x3_mfma_kernel<2, false, true>), dim3(n, gy), dim3(CM_THREADS), lds, s, in, Wt, bias, mask, out, ih, iw, oh, ow, pad, relu, plane);
-        EXORL_LAUNCH_CHECK();
-        return 0;
-    }
     if (npl == 3)      { if (mask) EXORL_CM(3, true); else EXORL_CM(3, false); }
     else if (npl == 2) { if (mask) EXORL_CM(2, true); else EXORL_CM(2, false); }
     else               { if (mask) EXORL_CM(1, true); else EXORL_CM(1, false); }
@@ -995,7 +902,7 @@ static int conv3x3(const float* in, const float* Wt, const float* bias, const fl
                    int oh, int ow, int stride, int pad, int in_scale, int relu, hipStream_t s, int prec = EXORL_PREC_F32, const float* frag = nullptr) {
     if (prec != EXORL_PREC_F32 && ci_n == CONV_CO && co_n == CONV_CO && stride == 1 && !in_scale && frag && conv3x3_mfma_fits(oh, ow, prec))
         return conv3x3_mfma(in, frag, bias, mask, out, n, ih, iw, oh, ow, pad, relu, prec, s);
-    if (stride == 2 && pad == 0 && !mask && co_n == CONV_CO && ow >= 8 && !(tune_variant() & 16)) {      // first layer forward; exorl_gemm_tune bit 16: the tile kernel (A/B)
+    if (stride == 2 && pad == 0 && !mask && co_n == CONV_CO && ow >= 8) {      // first layer forward
         const int max_rows = 2 * ((C1_PASS + ow - 2) / ow) + 3;
         const size_t slds = (size_t)ci_n * max_rows * 2 * ((iw + 1) / 2) * sizeof(float);
         if (slds <= 160 * 1024) {
@@ -1546,7 +1453,7 @@ static bool conv_wgrad_ws_fits(int n, int ih, int iw, int oh, int ow, int npl) {
 
 static int conv_wgrad_mfma(const float* dy, const float* in, float* P, float* Pb, int n, int ih, int iw, int oh, int ow, int prec, hipStream_t s) {
     const int npl = prec == EXORL_PREC_BF16X6 ? 3 : (prec == EXORL_PREC_BF16X3 ? 2 : 1);
-    if (!(tune_variant() & 64) && conv_wgrad_ws_fits(n, ih, iw, oh, ow, npl)) {          // exorl_gemm_tune bit 64: the tile kernel below (A/B)
+    if (!(tune_variant() & TUNE_CONV_WGRAD_TILE) && conv_wgrad_ws_fits(n, ih, iw, oh, ow, npl)) {          // TUNE_CONV_WGRAD_TILE: the tile kernel below (reference path)
         const size_t wlds = conv_wgrad_ws_lds(ow, npl);
         static bool wattr = false;
         if (!wattr) {
@@ -1562,19 +1469,16 @@ static int conv_wgrad_mfma(const float* dy, const float* in, float* P, float* Pb
         EXORL_LAUNCH_CHECK();
         return 0;
     }
-    const bool th4 = npl == 3 && (tune_variant() & 2048);            // measured and not adopted: 4 x 16 tiles (74 KB, two workgroups per CU): 9.6 vs 9.3 ms per Proto update
-    const int th = npl == 3 ? (th4 ? 4 : 8) : 16;
+    const int th = npl == 3 ? 8 : 16;      // 4 x 16 tiles for three planes (74 KB, two workgroups per CU) measured slower: 9.6 vs 9.3 ms per Proto update
     const size_t lds = (size_t)npl * (CONV_CO * (th * CONV_TILE + 8) + 3 * CONV_CO * ((th + 2) * CONV_TILE + 8)) * sizeof(unsigned short);
     static bool attr = false;
     if (!attr) {
         EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv_wgrad_mfma_kernel<3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv_wgrad_mfma_kernel<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv_wgrad_mfma_kernel<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)conv_wgrad_mfma_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr = true;
     }
-    if (th4)           hipLaunchKernelGGL((conv_wgrad_mfma_kernel<3, 4>), dim3(n), dim3(WM_THREADS), lds, s, dy, in, P, Pb, ih, iw, oh, ow);
-    else if (npl == 3) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<3, 8>), dim3(n), dim3(WM_THREADS), lds, s, dy, in, P, Pb, ih, iw, oh, ow);
+    if (npl == 3)      hipLaunchKernelGGL((conv_wgrad_mfma_kernel<3, 8>), dim3(n), dim3(WM_THREADS), lds, s, dy, in, P, Pb, ih, iw, oh, ow);
     else if (npl == 2) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<2, 16>), dim3(n), dim3(WM_THREADS), lds, s, dy, in, P, Pb, ih, iw, oh, ow);
     else               hipLaunchKernelGGL((conv_wgrad_mfma_kernel<1, 16>), dim3(n), dim3(WM_THREADS), lds, s, dy, in, P, Pb, ih, iw, oh, ow);
     EXORL_LAUNCH_CHECK();
@@ -1795,12 +1699,6 @@ int exorl_aug_shift(const unsigned char* x_dev, int32_t n, int32_t c, int32_t h,
 __global__ __launch_bounds__(256) void u8_to_f32_kernel(const unsigned char* __restrict__ x, float* __restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = (float)x[i];
 }
-int exorl_debug_conv_stamps(uint64_t* out_host, int32_t n_words) {
-    EXORL_REQUIRE(out_host && n_words > 0 && n_words <= 1024 * 2 * 8, "debug_conv_stamps: bad arguments");
-    EXORL_CHECK_HIP(hipDeviceSynchronize());
-    EXORL_CHECK_HIP(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(exorl::g_conv_stamps), (size_t)n_words * sizeof(uint64_t)));
-    return 0;
-}
 int exorl_u8_to_f32(const unsigned char* x_dev, int64_t n, float* out_dev, void* stream) {
     EXORL_REQUIRE(x_dev && out_dev && n > 0, "u8_to_f32: bad arguments");
     const int64_t blocks = (n + 255) / 256;
@@ -1901,8 +1799,8 @@ int exorl_encoder_backward_prec(const float* params_dev, int32_t c_in, int32_t h
         const int prec_w = (ov & 256) ? EXORL_PREC_F32 : prec, prec_d = (ov & 128) ? EXORL_PREC_F32 : prec;
         if (prec_w != EXORL_PREC_F32 && l > 0)
             EXORL_TRY(conv_wgrad_mfma(d, in, w.P, w.Pb, n, ih, ih, oh, oh, prec_w, s));
-        else if (prec_w != EXORL_PREC_F32 && l == 0 && conv1_wgrad_mfma_fits(ci, ih, oh, oh, stride) && !(tune_variant() & 131072))
-            EXORL_TRY(conv1_wgrad_mfma(d, in, w.P, w.Pb, n, ci, ih, ih, oh, oh, prec_w, s));     // exorl_gemm_tune bit 131072: the fp32 FMA kernel (A/B)
+        else if (prec_w != EXORL_PREC_F32 && l == 0 && conv1_wgrad_mfma_fits(ci, ih, oh, oh, stride))
+            EXORL_TRY(conv1_wgrad_mfma(d, in, w.P, w.Pb, n, ci, ih, ih, oh, oh, prec_w, s));
         else {
             hipLaunchKernelGGL(conv_wgrad_kernel, dim3(n), dim3(1024), lds, s, d, in, w.P, w.Pb, ci, ih, ih, oh, oh, stride, l == 0 ? 1 : 0);
             EXORL_LAUNCH_CHECK();

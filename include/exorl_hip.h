@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define EXORL_ABI_VERSION 8      /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override */
+#define EXORL_ABI_VERSION 9      /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
+                                    9: exorl_debug_gemm_stamps and exorl_debug_conv_stamps removed; exorl_gemm_tune keeps five bits */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -285,19 +286,17 @@ int exorl_gemm_planes(int32_t count, const int32_t* a_layouts, int32_t b_layout,
                       const uint16_t* const* A_hi_dev, const uint16_t* const* A_lo_dev, int64_t lda,
                       const uint16_t* const* B_hi_dev, const uint16_t* const* B_lo_dev, int64_t ldb,
                       float* const* C_dev, int64_t ldc, int32_t relu, void* stream);
-/* Tuning switch for the bf16-operand GEMM (tools/micro/gemm_bench.py): -1 = default heuristics. */
+/* Reference-path switches for tests and A/B runs; -1 or 0 = defaults. Bits (any combination):
+ *   64          32 -> 32 convolution weight gradient on the tile kernel instead of the wave-specialised one
+ *   256         act() on the generic multi-launch path
+ *   8388608     wave-specialised convolution forward / dgrad: one image per workgroup instead of the persistent form
+ *   134217728   planes adapter: ragged output widths through the padded copy
+ *   1073741824  32 -> 32 convolution forward / dgrad on the strip kernel instead of the wave-specialised one */
 int exorl_gemm_tune(int32_t variant);
 /* Diagnostic only (tools/debug/config4_ablation.py): in EXORL_PREC_BF16X3 mode, run the selected product families with exact fp32 products.
  * bits 1/2 forward GEMM narrow/wide, 4/8 wgrad, 16/32 dgrad ("wide": a dimension >= 8192), 64/128/256 convolution forward/dgrad/wgrad.
  * No reference counterpart; the product never calls it. */
 int exorl_debug_precision_override(int32_t mask);
-/* Diagnostic (tools/micro/stamp_bench.py; tuning bit 33554432 selects the stamped build of the forward H x H GEMM): per workgroup
- * {s_memtime x 4, s_memrealtime x 4} at entry / first k-step / last k-step / stores drained; 8 words per workgroup, <= 1024 workgroups. */
-int exorl_debug_gemm_stamps(uint64_t* out_host, int32_t n_words);
-/* Diagnostic (tools/micro/conv_stamp_bench.py; tuning bit 8192 selects the stamped build of the 32 -> 32 forward convolution): per
- * workgroup (= image) and for waves 0 and 7, shader-clock cycles summed over the image's passes: {convert + LDS write, barrier, fetch
- * issue, MFMA loop incl. its LDS reads, stores, barrier, whole kernel, 0}; 16 words per workgroup, <= 1024 workgroups. */
-int exorl_debug_conv_stamps(uint64_t* out_host, int32_t n_words);
 /* Measurement hook (bench.py roofline leg): time every GEMM launch with HIP events on its own stream. */
 int exorl_profile_gemm(int32_t enable);
 int exorl_profile_gemm_read(double* flops_out_host, float* ms_out_host, int32_t cap, int32_t* n_out);

@@ -1,4 +1,4 @@
-"""Times the bf16-operand GEMM variants (exorl_gemm_tune bits) on the agent's layer shapes with HIP events."""
+"""Times the bf16-operand GEMM on the agent's layer shapes with HIP events."""
 import sys
 from pathlib import Path
 
@@ -12,8 +12,7 @@ lib = L.load()
 H = 1024
 
 
-def run(al, bl, M, N, K, variant, iters=50):
-    lib.exorl_gemm_tune(variant)
+def run(al, bl, M, N, K, iters=50):
     a = torch.randn(M * K, device='cuda').to(torch.bfloat16)
     b = torch.randn(K * N, device='cuda').to(torch.bfloat16)
     c = torch.empty(M, N, device='cuda')
@@ -36,9 +35,7 @@ def run(al, bl, M, N, K, variant, iters=50):
     return float(np.median(ms[:n.value])) * 1e3
 
 
-names = {0: 'glds 64x64 s4', 4096: 'glds 64x64 s3', 8192: 'glds 64x64 s2'}
 for (al, bl, M, N, K, tag) in [(0, 0, 2048, H, H, 'fwd 2048'), (0, 0, 1024, H, H, 'fwd 1024'), (0, 0, 4096, H, H, 'fwd 4096'), (0, 1, 1024, H, H, 'dgrad'),
                                (1, 1, H, H, 1024, 'wgrad')]:
-    for v, nm in names.items():
-        us = run(al, bl, M, N, K, v)
-        print(f'{tag:10s} {nm:16s} {us:8.2f} us  {2.0 * M * N * K / us / 1e6:8.1f} TFLOP/s', flush=True)
+    us = run(al, bl, M, N, K)
+    print(f'{tag:10s} {us:8.2f} us  {2.0 * M * N * K / us / 1e6:8.1f} TFLOP/s', flush=True)

@@ -35,7 +35,6 @@ def timed(al, bl, M, N, K, lda=None, ldb=None, iters=40):
     return float(np.median(ms[:n.value])) * 1e3, float(np.min(ms[:n.value])) * 1e3
 
 
-lib.exorl_gemm_tune(0)
 print('K sweep (M=N=1024, fwd):')
 for K in (64, 128, 256, 512, 1024, 2048, 4096):
     print(f'  K={K:5d}  median {timed(0, 0, 1024, 1024, K)[0]:7.2f} us', flush=True)

@@ -1,6 +1,5 @@
 """Grouped GEMM on bf16 hi/lo planes (exorl_gemm_planes) at the agent's launch shapes: correctness against a float64 product of the
-SAME planes, and time per launch by variant (exorl_gemm_tune bits: 262144 = previous kernels, 0 = 128 x TN / k32 / XCD-local,
-1048576 = the same in id order, 524288 = 128 x 128 everywhere, 2097152 = 32-wide stages also for the row-image (forward) launches, whose default is 64-wide x 2).   python tools/micro/planes_bench.py [check]"""
+SAME planes, and time per launch.   python tools/micro/planes_bench.py [check]"""
 import sys
 from pathlib import Path
 
@@ -55,8 +54,7 @@ def reference(p, al, bl, x3):
     return full
 
 
-def timed(ps, a_layouts, bl, M, N, K, x3, variant, iters=40):
-    lib.exorl_gemm_tune(variant)
+def timed(ps, a_layouts, bl, M, N, K, x3, iters=40):
     for _ in range(5):
         launch(ps, a_layouts, bl, M, N, K, x3)
     torch.cuda.synchronize()
@@ -67,7 +65,6 @@ def timed(ps, a_layouts, bl, M, N, K, x3, variant, iters=40):
     fl, ms, n = np.zeros(cap, np.float64), np.zeros(cap, np.float32), C.c_int32()
     L.check(lib.exorl_profile_gemm_read(fl.ctypes.data, ms.ctypes.data, cap, C.byref(n)))
     L.check(lib.exorl_profile_gemm(0))
-    lib.exorl_gemm_tune(-1)
     return float(np.median(ms[:n.value])) * 1e3
 
 
@@ -86,23 +83,19 @@ if __name__ == '__main__':
     for x3 in (True, False):
         for tag, count, lay, bl, M, N, K in SHAPES:
             ps = make(count, lay, bl, M, N, K, x3)
-            for variant in (0, 524288, 2097152):
-                lib.exorl_gemm_tune(variant)
-                for p in ps:
-                    p[2].zero_()
-                launch(ps, lay, bl, M, N, K, x3)
-                torch.cuda.synchronize()
-                worst = 0.0
-                for i, p in enumerate(ps):
-                    ref = reference(p, lay[i], bl, x3)
-                    err = float((p[2].double() - ref).abs().max() / ref.abs().max())
-                    worst = max(worst, err)
-                assert worst < 2e-6, (tag, x3, variant, worst)
-            lib.exorl_gemm_tune(-1)
+            for p in ps:
+                p[2].zero_()
+            launch(ps, lay, bl, M, N, K, x3)
+            torch.cuda.synchronize()
+            worst = 0.0
+            for i, p in enumerate(ps):
+                ref = reference(p, lay[i], bl, x3)
+                err = float((p[2].double() - ref).abs().max() / ref.abs().max())
+                worst = max(worst, err)
+            assert worst < 2e-6, (tag, x3, worst)
             if check_only:
                 print(f'{"x3" if x3 else "bf16":5s} {tag:26s} ok (max rel err {worst:.1e})', flush=True)
                 continue
-            ts = {v: timed(ps, lay, bl, M, N, K, x3, v) for v in (262144, 0, 1048576, 524288, 2097152)}
+            t = timed(ps, lay, bl, M, N, K, x3)
             fl = 2.0 * M * N * K * count
-            print(f'{"x3" if x3 else "bf16":5s} {tag:26s} old {ts[262144]:6.2f} us | new {ts[0]:6.2f} us ({fl / ts[0] / 1e6:6.0f} TF/s) | new, id order '
-                  f'{ts[1048576]:6.2f} | 128x128 everywhere {ts[524288]:6.2f} | fwd on k32 stages {ts[2097152]:6.2f}   (err {worst:.1e})', flush=True)
+            print(f'{"x3" if x3 else "bf16":5s} {tag:26s} {t:6.2f} us ({fl / t / 1e6:6.0f} TF/s)   (err {worst:.1e})', flush=True)
