@@ -586,14 +586,28 @@ class DDPGAgent(_AgentBase):
         self.update_every_steps, self.use_tb, self.use_wandb = update_every_steps, use_tb, use_wandb
         self.num_expl_steps, self.stddev_schedule, self.stddev_clip, self.init_critic = num_expl_steps, stddev_schedule, stddev_clip, init_critic
         self.solved_meta = None
-        self.world_size = 1
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            raise NotImplementedError('exorl_amd: the pixel path is single-GPU this round')
+        ws = 1
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            ws = torch.distributed.get_world_size()
+        if ws > 1 and reward_free and type(self) is not DDPGAgent:
+            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU: its module step needs "
+                                      "the global batch's encodings (BatchNorm2d statistics, kNN over the batch, Sinkhorn and the queue). Under "
+                                      "data parallelism the pixel path runs DDPGAgent (any reward_free) and every agent with reward_free=False "
+                                      "(fine-tuning: the DDPG pixel step)")
+        if ws > 1:          # every rank draws its own rows of the global batch's shifts and noise (as _AgentBase._build does for states)
+            seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF
+        self.world_size = ws
         c = obs_shape[0]
         sf_dim = self._engine_kw().get('sf_dim', 0)         # APS: CriticSF heads (aps.py:94-104)
         w = _pixel_init(c, obs_shape[1], self.action_dim, feature_dim, hidden_dim, meta_dim, sf_dim)
         self.engine = PixelEngine(obs_shape, self.action_dim, feature_dim, hidden_dim, batch_size, lr=lr, tau=critic_target_tau,
-                                  stddev_clip=stddev_clip, precision=precision, seed=seed, device=device, meta_dim=meta_dim, sf_dim=sf_dim)
+                                  stddev_clip=stddev_clip, precision=precision, seed=seed, device=device, meta_dim=meta_dim, sf_dim=sf_dim,
+                                  world_size=ws)
+        if ws > 1:
+            from .comm import native_comm
+            comm = native_comm(self.engine.device)          # RCCL inside the library when torch.distributed runs on nccl
+            if comm is not None:
+                self.engine.set_comm(comm)
         self.obs_dim = w['repr_dim'] + meta_dim          # ddpg.py:176 obs_dim = encoder.repr_dim + meta_dim
         conv_shapes = [s for l in range(4) for s in ((32, c if l == 0 else 32, 3, 3), (32,))]
         self.encoder = _PixelNetView(self.engine, 0, _ENC_KEYS, conv_shapes)
@@ -625,14 +639,25 @@ class DDPGAgent(_AgentBase):
         sn = self.shift_hook(B) if self.shift_hook else None
         nc = self.noise_hook((B, A)) if self.noise_hook else None
         na = self.noise_hook((B, A)) if self.noise_hook else None
-        eng.update(stddev, so, sn, nc, na)
+        self._pix_step(stddev, so, sn, nc, na)
         metrics = dict()
         if self.use_tb or self.use_wandb:
-            raw = eng.metrics_raw()
-            for idx, name in _CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')]:
-                metrics[name] = float(raw[idx])
-            metrics['actor_ent'] = float(np.float32(0.5 + 0.5 * np.log(2 * np.pi) + np.log(stddev)) * self.action_dim)
+            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
         return metrics
+
+    def _pix_step(self, stddev, so=None, sn=None, nc=None, na=None, keep_augmented=False, keep_encoded=False):
+        """The DDPG pixel step. Under torch.distributed each rank runs it on its rows and the gradients are sum-all-reduced between the
+        phases (every mean in it is over the global batch): exchange 0 = critic (+ encoder) gradients, exchange 1 = actor gradients."""
+        eng = self.engine
+        if self.world_size == 1 or eng.comm is not None:      # one host call: with a communicator the library all-reduces between its phases
+            eng.update(stddev, so, sn, nc, na, keep_augmented=keep_augmented, keep_encoded=keep_encoded)
+            return
+        dist = torch.distributed                              # gloo / EXORL_DP_COMM=torch: the collectives stay here
+        eng.update_phase(0, stddev, so, sn, nc, None, keep_augmented=keep_augmented, keep_encoded=keep_encoded)
+        dist.all_reduce(eng.grad_buffer(0))
+        eng.update_phase(1, stddev, noise_actor=na)
+        dist.all_reduce(eng.grad_buffer(1))
+        eng.update_phase(2, stddev)
 
     def train(self, training=True):
         if getattr(self, 'obs_type', 'states') == 'pixels':
@@ -839,14 +864,11 @@ class _IntrAgent(DDPGAgent):
             eng.encoder_step(self._PIX_GRAD, self._dobs.data_ptr(), 0)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        eng.update(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
-                   keep_encoded=True)
+        self._pix_step(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
+                       keep_encoded=True)
         metrics = dict()
         if self.use_tb or self.use_wandb:
-            raw = eng.metrics_raw()
-            for idx, name in _CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')]:
-                metrics[name] = float(raw[idx])
-            metrics['actor_ent'] = float(np.float32(0.5 + 0.5 * np.log(2 * np.pi) + np.log(stddev)) * self.action_dim)
+            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
             if self.reward_free:
                 ri = self.intr.metrics_raw()
                 metrics[self.LOSS_KEY] = float(ri[L.IM_LOSS])
@@ -992,13 +1014,10 @@ class RNDAgent(_IntrAgent):
             self.intr.update(fp, None, ft, s.reward, s.reward, False)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        eng.update(stddev, sh(), sh(), self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None)
+        self._pix_step(stddev, sh(), sh(), self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None)
         metrics = dict()
         if self.use_tb or self.use_wandb:
-            raw = eng.metrics_raw()
-            for idx, name in _CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')]:
-                metrics[name] = float(raw[idx])
-            metrics['actor_ent'] = float(np.float32(0.5 + 0.5 * np.log(2 * np.pi) + np.log(stddev)) * self.action_dim)
+            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
             ri = self.intr.metrics_raw()
             if self.reward_free:
                 metrics['rnd_loss'] = float(ri[L.IM_LOSS])
@@ -1510,15 +1529,12 @@ class ProtoAgent(_IntrAgent):
             eng.encode(0)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        eng.update(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
-                   keep_augmented=not self.reward_free, keep_encoded=self.reward_free)
+        self._pix_step(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
+                       keep_augmented=not self.reward_free, keep_encoded=self.reward_free)
         eng.encoder_target(self.encoder_target_tau)
         metrics = dict()
         if self.use_tb or self.use_wandb:
-            raw = eng.metrics_raw()
-            for idx, name in _CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')]:
-                metrics[name] = float(raw[idx])
-            metrics['actor_ent'] = float(np.float32(0.5 + 0.5 * np.log(2 * np.pi) + np.log(stddev)) * self.action_dim)
+            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
             if self.reward_free:
                 ri = self.intr.metrics_raw()
                 metrics['repr_loss'] = float(ri[L.IM_LOSS])

@@ -172,6 +172,12 @@ struct exorl_pixel_agent {
     bool augmented = false;
     bool have_feat_o = false, have_feat_n = false;     // feat_o / feat_n hold the online encoder's pass of exorl_pixel_agent_encode
     bool train_encoder = true;      // false: update_critic received obs.detach() (proto.py:190-193): encoder_opt.step() finds no gradients
+    // data parallel: every mean over the batch is over batch * world_size rows (the gradients are partial sums the ranks add up)
+    int world = 1;
+    float inv_bg = 0.f;
+    exorl_comm* comm = nullptr;                  // exorl_pixel_agent_set_comm: exorl_pixel_agent_update all-reduces between its phases
+    hipStream_t comm_stream = nullptr;           // the critic's gradients travel here while the encoder's backward pass runs
+    hipEvent_t ev_critic_ready = nullptr, ev_critic_done = nullptr;
 };
 
 namespace exorl {
@@ -194,10 +200,15 @@ static void take_mlp(Mlp& m, PCarver& c, int64_t rows, float* last_act, float* l
 static void pcarve(exorl_pixel_agent* a, PCarver& c) {
     const auto& g = a->cfg;
     const int64_t B = g.batch, A = g.act_dim, F = g.feature_dim, R = a->R, img = (int64_t)g.c_in * g.hw * g.hw;
+    // exchange 0 of a data-parallel step is the critic's gradients followed by the encoder's: one contiguous range
+    // (critic.total is a multiple of 64 floats, so the encoder's gradients start right where the critic's end)
     a->flat[0][0] = c.take(a->enc_total);
-    for (int w = 1; w < 4; ++w) a->flat[0][w] = c.take(a->enc_total);
+    a->flat[0][2] = c.take(a->enc_total); a->flat[0][3] = c.take(a->enc_total);
     for (int w = 0; w < 4; ++w) a->flat[1][w] = c.take(a->actor.total);
-    for (int w = 0; w < 4; ++w) a->flat[2][w] = c.take(a->critic.total);
+    a->flat[2][0] = c.take(a->critic.total);
+    a->flat[2][1] = c.take(a->critic.total);
+    a->flat[0][1] = c.take(a->enc_total);
+    a->flat[2][2] = c.take(a->critic.total); a->flat[2][3] = c.take(a->critic.total);
     a->flat[3][0] = c.take(a->critic.total);
     a->enc_target = c.take(a->enc_total); a->enc_m2 = c.take(a->enc_total); a->enc_v2 = c.take(a->enc_total);
     a->bn2d = c.take(2 * 16 + 1);
@@ -323,6 +334,7 @@ static int check_pcfg(const exorl_pixel_cfg* c) {
     EXORL_REQUIRE(c->meta_dim >= 0 && c->meta_dim <= 256, "pixel_agent: meta_dim=%d unsupported (0..256)", c->meta_dim);
     EXORL_REQUIRE(c->sf_dim == 0 || (c->sf_dim >= 1 && c->sf_dim == c->meta_dim), "pixel_agent: sf_dim=%d must equal meta_dim=%d (the task vector is the meta row, aps.py:236-238)",
                   c->sf_dim, c->meta_dim);
+    EXORL_REQUIRE(c->world_size >= 0, "pixel_agent: world_size=%d must be >= 0 (0 and 1: one rank)", c->world_size);
     return 0;
 }
 
@@ -353,6 +365,8 @@ int exorl_pixel_agent_create(const exorl_pixel_cfg* cfg, void* workspace, size_t
     auto* a = new exorl_pixel_agent();
     a->cfg = *cfg;
     pdescribe(a);
+    a->world = cfg->world_size > 1 ? cfg->world_size : 1;
+    a->inv_bg = 1.0f / ((float)cfg->batch * (float)a->world);
     a->ws = static_cast<float*>(workspace);
     PCarver c(a->ws);
     pcarve(a, c);
@@ -369,6 +383,9 @@ int exorl_pixel_agent_create(const exorl_pixel_cfg* cfg, void* workspace, size_t
 int exorl_pixel_agent_destroy(exorl_pixel_agent_t* a) {
     if (!a) return 0;
     (void)hipDeviceSynchronize();
+    if (a->ev_critic_ready) (void)hipEventDestroy(a->ev_critic_ready);
+    if (a->ev_critic_done) (void)hipEventDestroy(a->ev_critic_done);
+    if (a->comm_stream) (void)hipStreamDestroy(a->comm_stream);
     delete a;
     return 0;
 }
@@ -544,30 +561,37 @@ int exorl_pixel_agent_encoder_opt2(exorl_pixel_agent_t* a, void** m_dev, void** 
     return 0;
 }
 
-int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next, const float* noise_c,
-                             const float* noise_a, void* stream) {
-    EXORL_REQUIRE(a && stddev > 0.f, "pixel_agent_update: bad arguments");
-    hipStream_t s = as_stream(stream);
+}  // extern "C"
+
+namespace exorl {
+
+static int sf_q(exorl_pixel_agent* a, hipStream_t s) {          // Q_n = task . features_n (aps.py:55-58) -> a->q
+    const int B = a->cfg.batch, S = a->cfg.sf_dim;
+    if (S == 0) return 0;
+    hipLaunchKernelGGL(sf_dot_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, s, a->critic.head[0].act[2], a->critic.head[1].act[2], a->meta,
+                       (int64_t)a->cfg.meta_dim, a->q, B, S);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+static int sf_dout(exorl_pixel_agent* a, hipStream_t s) {       // dQ_n -> gradient at the heads' feature outputs
+    const int B = a->cfg.batch, S = a->cfg.sf_dim;
+    if (S == 0) return 0;
+    hipLaunchKernelGGL(sf_dout_kernel, dim3(cdiv(2 * B * S, 256)), dim3(256), 0, s, a->dq, a->meta, (int64_t)a->cfg.meta_dim, a->critic.head[0].dact[2],
+                       a->critic.head[1].dact[2], B, S);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+// Phase 0: aug_and_encode, update_critic's forward and backward (ddpg.py:213-215, 240-268). Leaves the critic's and (train_encoder) the
+// encoder's gradients in exchange 0. side != nullptr (exorl_pixel_agent_update with a communicator): the critic's gradients are final when
+// its trunk backward returns, so they are all-reduced on comm_stream while the encoder's backward pass runs, the encoder's after it on s.
+static int pphase0(exorl_pixel_agent* a, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next, const float* noise_c, exorl_comm* side,
+                   hipStream_t s) {
     const auto& c = a->cfg;
     const int B = c.batch, A = c.act_dim, F = c.feature_dim, FA = F + A, prec = c.precision;
-    const float inv_b = 1.0f / (float)B;
     float *Pe = a->flat[0][0], *Pa = a->flat[1][0], *Pc = a->flat[2][0], *Pt = a->flat[3][0];
-    float *Ge = a->flat[0][1], *Ga = a->flat[1][1], *Gc = a->flat[2][1];
-    a->t += 1;
+    float *Ge = a->flat[0][1], *Gc = a->flat[2][1];
     const float* mt = c.meta_dim > 0 ? a->meta : nullptr;
-    const int S = c.sf_dim;
-    auto sf_q = [&]() -> int {                 // Q_n = task . features_n (aps.py:55-58) -> a->q
-        if (S == 0) return 0;
-        hipLaunchKernelGGL(sf_dot_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, s, a->critic.head[0].act[2], a->critic.head[1].act[2], mt, (int64_t)c.meta_dim, a->q, B, S);
-        EXORL_LAUNCH_CHECK();
-        return 0;
-    };
-    auto sf_dout = [&]() -> int {              // dQ_n -> gradient at the heads' feature outputs
-        if (S == 0) return 0;
-        hipLaunchKernelGGL(sf_dout_kernel, dim3(cdiv(2 * B * S, 256)), dim3(256), 0, s, a->dq, mt, (int64_t)c.meta_dim, a->critic.head[0].dact[2], a->critic.head[1].dact[2], B, S);
-        EXORL_LAUNCH_CHECK();
-        return 0;
-    };
     // ---- aug_and_encode (ddpg.py:213-215, 312-315); shifts_obs == (const int32_t*)-1: keep the images exorl_pixel_agent_augment made;
     // (const int32_t*)-2: keep the encodings exorl_pixel_agent_encode(0 / 1, online) made as well — the agents that step the encoder
     // through their own module pass the critic the encodings computed BEFORE that step (icm.py:97-131, diayn.py:137-170), detached
@@ -576,7 +600,7 @@ int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t
         EXORL_REQUIRE(a->have_feat_o && a->have_feat_n && !a->train_encoder, "pixel_agent_update: kept encodings need exorl_pixel_agent_encode(0) and (1) "
                       "with the online encoder first, and set_train_encoder(0) (they are detached)");
     } else {
-        if (shifts_obs != reinterpret_cast<const int32_t*>(-1)) EXORL_TRY(exorl_pixel_agent_augment(a, shifts_obs, shifts_next, stream));
+        if (shifts_obs != reinterpret_cast<const int32_t*>(-1)) EXORL_TRY(exorl_pixel_agent_augment(a, shifts_obs, shifts_next, s));
         EXORL_REQUIRE(a->augmented, "pixel_agent_update: no augmented batch");
         EXORL_TRY(exorl_encoder_forward_prec(Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, &a->feat_o, a->cfg.precision, s));
         EXORL_TRY(exorl_encoder_forward_prec(Pe, c.c_in, c.hw, a->aug_n, B, a->enc_ws_n, &a->feat_n, a->cfg.precision, s));
@@ -597,24 +621,48 @@ int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t
     EXORL_TRY(sample_action(a->mu_n, nc, stddev, c.stddev_clip, 1, a->xq_t + F, FA, B, A, nullptr, s));
     // the target's Q heads reuse the critic's Mlp buffers (outputs to q), then are copied to tq
     EXORL_TRY(mlp_forward_many(a->critic.head, 2, Pt, a->xq_t, FA, B, prec, s));          // Q1 and Q2 layer by layer in shared launches
-    EXORL_TRY(sf_q());
+    EXORL_TRY(sf_q(a, s));
     EXORL_CHECK_HIP(hipMemcpyAsync(a->tq, a->q, sizeof(float) * 2 * B, hipMemcpyDeviceToDevice, s));
     EXORL_TRY(trunk_forward(a, a->critic, Pc, a->feat_o, mt, B, a->tc, prec, s));
     EXORL_TRY(launch_concat(a->tc.h, F, F, a->action, A, A, a->xq_c, B, s));
     EXORL_TRY(mlp_forward_many(a->critic.head, 2, Pc, a->xq_c, FA, B, prec, s));
-    EXORL_TRY(sf_q());
-    EXORL_TRY(critic_loss(a->q, a->tq, a->reward, a->discount, a->dq, a->metrics, B, inv_b, s));
-    EXORL_TRY(sf_dout());
+    EXORL_TRY(sf_q(a, s));
+    EXORL_TRY(critic_loss(a->q, a->tq, a->reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));
+    EXORL_TRY(sf_dout(a, s));
     // both heads' backward passes layer by layer in shared launches; d/d(input) of the two is summed by the second head's accumulating dgrad
     // (dx0 + dx1, the same fp32 addition add_cols_kernel used to make of two buffers)
     EXORL_TRY(mlp_backward_many(a->critic.head, 2, Pc, Gc, a->xq_c, FA, B, prec, s, a->dxq[0]));
     hipLaunchKernelGGL(add_cols_kernel, dim3(grid1((int64_t)B * F)), dim3(256), 0, s, a->dxq[0], (int64_t)FA, (const float*)nullptr, (int64_t)FA, 0, F, a->dh, B);
     EXORL_LAUNCH_CHECK();
     EXORL_TRY(trunk_backward(a, a->critic, Pc, Gc, a->feat_o, mt, B, a->tc, a->dh, a->train_encoder ? a->dfeat : nullptr, prec, s));
-    if (a->train_encoder) EXORL_TRY(exorl_encoder_backward_prec(Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, a->dfeat, Ge, a->cfg.precision, s));
+    if (!a->train_encoder) return side ? comm_allreduce_sum(side, Gc, a->critic.total, s) : 0;
+    if (side) {
+        EXORL_CHECK_HIP(hipEventRecord(a->ev_critic_ready, s));
+        EXORL_CHECK_HIP(hipStreamWaitEvent(a->comm_stream, a->ev_critic_ready, 0));
+        EXORL_TRY(comm_allreduce_sum(side, Gc, a->critic.total, a->comm_stream));
+        EXORL_CHECK_HIP(hipEventRecord(a->ev_critic_done, a->comm_stream));
+    }
+    EXORL_TRY(exorl_encoder_backward_prec(Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, a->dfeat, Ge, a->cfg.precision, s));
+    if (side) {
+        EXORL_TRY(comm_allreduce_sum(side, Ge, a->enc_total, s));
+        EXORL_CHECK_HIP(hipStreamWaitEvent(s, a->ev_critic_done, 0));          // Adam (phase 1) reads both halves of exchange 0
+    }
+    return 0;
+}
+
+// Phase 1: critic_opt / encoder_opt step, then update_actor's forward and backward on obs.detach() with the stepped critic (ddpg.py:270-292).
+// Leaves the actor's gradients in exchange 1.
+static int pphase1(exorl_pixel_agent* a, float stddev, const float* noise_a, hipStream_t s) {
+    const auto& c = a->cfg;
+    const int B = c.batch, A = c.act_dim, F = c.feature_dim, FA = F + A, prec = c.precision;
+    float *Pa = a->flat[1][0], *Pc = a->flat[2][0];
+    float *Ga = a->flat[1][1], *Gc = a->flat[2][1];
+    const float* mt = c.meta_dim > 0 ? a->meta : nullptr;
+    a->t += 1;
     EXORL_TRY(padam(a, 2, a->critic.total, nullptr, s));
     if (a->train_encoder) { a->t_enc += 1; EXORL_TRY(padam(a, 0, a->enc_total, nullptr, s)); }
-    // ---- update_actor (ddpg.py:270-292) on obs.detach(): the encoding computed above, the critic just updated
+    const bool pair = c.meta_dim == 0;
+    Mlp& pol = a->actor.head[0];
     if (pair) EXORL_TRY(trunk_forward_pair(a, a->actor, Pa, a->ta_o, a->critic, Pc, a->tc, a->feat_o, B, prec, s));
     else EXORL_TRY(trunk_forward(a, a->actor, Pa, a->feat_o, mt, B, a->ta_o, prec, s));
     EXORL_TRY(mlp_forward(pol, Pa, a->ta_o.h, F, B, prec, s));
@@ -624,32 +672,85 @@ int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t
     if (!pair) EXORL_TRY(trunk_forward(a, a->critic, Pc, a->feat_o, mt, B, a->tc, prec, s));
     EXORL_TRY(launch_concat(a->tc.h, F, F, a->mu_o, A, A, a->xq_c, B, s));
     NoiseSpec na{noise_a, c.seed, 2 * a->noise_counter + 1, nullptr};
-    EXORL_TRY(sample_action(a->mu_o, na, stddev, c.stddev_clip, 1, a->xq_c + F, FA, B, A, a->metrics + EXORL_M_ACTOR_LOGPROB, s));
+    EXORL_TRY(sample_action(a->mu_o, na, stddev, c.stddev_clip, 1, a->xq_c + F, FA, B, A, a->metrics + EXORL_M_ACTOR_LOGPROB, s, nullptr, a->world));
     a->noise_counter += 1;
     EXORL_TRY(mlp_forward_many(a->critic.head, 2, Pc, a->xq_c, FA, B, prec, s));
-    EXORL_TRY(sf_q());
+    EXORL_TRY(sf_q(a, s));
     EXORL_TRY(actor_stats(a->q, a->stats, B, s));
-    EXORL_TRY(actor_dq(a->q, a->stats, a->dq, B, inv_b, 0.f, 0, s));
-    EXORL_TRY(sf_dout());
+    EXORL_TRY(actor_dq(a->q, a->stats, a->dq, B, a->inv_bg, 0.f, 0, s));
+    EXORL_TRY(sf_dout(a, s));
     EXORL_TRY(mlp_backward_many(a->critic.head, 2, Pc, Gc, a->xq_c, FA, B, prec, s, a->dxq[0]));     // Gc: scratch now
     hipLaunchKernelGGL(add_cols_kernel, dim3(grid1((int64_t)B * A)), dim3(256), 0, s, a->dxq[0], (int64_t)FA, (const float*)nullptr, (int64_t)FA, F, A, a->dmu, B);
     hipLaunchKernelGGL(dpre_kernel, dim3(grid1((int64_t)B * A)), dim3(256), 0, s, a->dmu, a->mu_o, pol.dact[2], (int64_t)B * A);
     EXORL_LAUNCH_CHECK();
     EXORL_TRY(mlp_backward(pol, Pa, Ga, a->ta_o.h, F, B, a->dh, prec, s));
-    EXORL_TRY(trunk_backward(a, a->actor, Pa, Ga, a->feat_o, mt, B, a->ta_o, a->dh, nullptr, prec, s));
-    EXORL_TRY(padam(a, 1, a->actor.total, nullptr, s));
-    // ---- soft update (ddpg.py:326-327)
-    return soft_update(Pc, Pt, a->critic.total, c.tau, s);
+    return trunk_backward(a, a->actor, Pa, Ga, a->feat_o, mt, B, a->ta_o, a->dh, nullptr, prec, s);
 }
 
-// actor_loss = -mean(min Q) is stats[1] / B (actor_stats); the rest comes from critic_loss / sample_action
+// Phase 2: actor_opt step and the critic's soft update (ddpg.py:326-327).
+static int pphase2(exorl_pixel_agent* a, hipStream_t s) {
+    EXORL_TRY(padam(a, 1, a->actor.total, nullptr, s));
+    return soft_update(a->flat[2][0], a->flat[3][0], a->critic.total, a->cfg.tau, s);
+}
+
+}  // namespace exorl
+
+extern "C" {
+
+int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next,
+                                   const float* noise_c, const float* noise_a, void* stream) {
+    EXORL_REQUIRE(a && stddev > 0.f, "pixel_agent_update_phase: bad arguments");
+    hipStream_t s = as_stream(stream);
+    switch (phase) {
+        case 0: return pphase0(a, stddev, shifts_obs, shifts_next, noise_c, nullptr, s);
+        case 1: return pphase1(a, stddev, noise_a, s);
+        case 2: return pphase2(a, s);
+    }
+    set_error("pixel_agent_update_phase: phase %d out of range (0..2)", phase);
+    return 2;
+}
+
+int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next, const float* noise_c,
+                             const float* noise_a, void* stream) {
+    EXORL_REQUIRE(a && stddev > 0.f, "pixel_agent_update: bad arguments");
+    EXORL_REQUIRE(a->world == 1 || a->comm, "pixel_agent_update: world_size=%d needs a communicator (exorl_pixel_agent_set_comm), or drive "
+                  "exorl_pixel_agent_update_phase and all-reduce exorl_pixel_agent_grad_buffer 0 / 1 between the phases yourself", a->world);
+    hipStream_t s = as_stream(stream);
+    EXORL_TRY(pphase0(a, stddev, shifts_obs, shifts_next, noise_c, a->comm, s));
+    EXORL_TRY(pphase1(a, stddev, noise_a, s));
+    if (a->comm) EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[1][1], a->actor.total, s));
+    return pphase2(a, s);
+}
+
+// exchange 0: critic gradients, then (train_encoder) the encoder's, contiguous; exchange 1: actor gradients
+int exorl_pixel_agent_grad_buffer(exorl_pixel_agent_t* a, int32_t exchange, float** ptr, int64_t* n) {
+    EXORL_REQUIRE(a && ptr && n && (exchange == 0 || exchange == 1), "pixel_agent_grad_buffer: bad arguments (exchange 0 or 1)");
+    if (exchange == 0) { *ptr = a->flat[2][1]; *n = a->critic.total + (a->train_encoder ? a->enc_total : 0); }
+    else { *ptr = a->flat[1][1]; *n = a->actor.total; }
+    return 0;
+}
+
+int exorl_pixel_agent_set_comm(exorl_pixel_agent_t* a, exorl_comm_t* c) {
+    EXORL_REQUIRE(a, "pixel_agent_set_comm: null handle");
+    EXORL_REQUIRE(!c || comm_nranks(c) == a->world, "pixel_agent_set_comm: communicator has %d ranks, the agent was built for world_size=%d "
+                  "(its means are over batch * world_size)", comm_nranks(c), a->world);
+    if (c && !a->comm_stream) {
+        EXORL_CHECK_HIP(hipStreamCreateWithFlags(&a->comm_stream, hipStreamNonBlocking));
+        EXORL_CHECK_HIP(hipEventCreateWithFlags(&a->ev_critic_ready, hipEventDisableTiming));
+        EXORL_CHECK_HIP(hipEventCreateWithFlags(&a->ev_critic_done, hipEventDisableTiming));
+    }
+    a->comm = c;
+    return 0;
+}
+
+// actor_loss = -mean(min Q) is stats[1] / (B * world_size) (actor_stats); the rest comes from critic_loss / sample_action
 int exorl_pixel_agent_metrics(exorl_pixel_agent_t* a, float* host, void* stream) {
     EXORL_REQUIRE(a && host, "pixel_agent_metrics: null argument");
     float buf[4 + EXORL_N_METRICS];
     EXORL_CHECK_HIP(hipMemcpyAsync(buf, a->stats, sizeof(buf), hipMemcpyDeviceToHost, as_stream(stream)));
     EXORL_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));
     for (int i = 0; i < EXORL_N_METRICS; ++i) host[i] = buf[4 + i];
-    host[EXORL_M_ACTOR_LOSS] = -buf[1] / (float)a->cfg.batch;
+    host[EXORL_M_ACTOR_LOSS] = -buf[1] / ((float)a->cfg.batch * (float)a->world);     // partial mean over the global batch
     return 0;
 }
 

@@ -321,15 +321,17 @@ class PixelEngine:
     NETS = {'encoder': 0, 'actor': 1, 'critic': 2, 'critic_target': 3}
 
     def __init__(self, obs_shape, act_dim, feature_dim, hidden_dim, batch, lr=1e-4, tau=0.01, stddev_clip=0.3, precision='fp32', seed=0,
-                 device='cuda', meta_dim=0, sf_dim=0):
+                 device='cuda', meta_dim=0, sf_dim=0, world_size=1):
         self.lib = L.load()
         self.device = _require_gpu(device)
+        self.world_size = world_size
+        self.comm = None
         c, h, w = obs_shape
         if h != w:
             raise L.ExorlError(f'pixel observations must be square, got {obs_shape}')
         self.obs_shape, self.act_dim, self.batch, self.meta_dim = tuple(obs_shape), act_dim, batch, meta_dim
         self.cfg = L.PixelCfg(c, h, act_dim, feature_dim, hidden_dim, batch, PRECISION[precision], meta_dim, lr, tau,
-                              stddev_clip if stddev_clip is not None else 0.0, sf_dim, seed)
+                              stddev_clip if stddev_clip is not None else 0.0, sf_dim, seed, world_size)
         nbytes = self.lib.exorl_pixel_agent_workspace_bytes(C.byref(self.cfg))
         if nbytes == 0:
             raise L.ExorlError(self.lib.exorl_last_error().decode())
@@ -387,7 +389,7 @@ class PixelEngine:
     def _i32(self, x):
         return None if x is None else torch.as_tensor(np.ascontiguousarray(x, np.int32)).to(self.device)
 
-    def update(self, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False, keep_encoded=False):
+    def _update_args(self, shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded):
         f32 = lambda x: None if x is None else self._f(x)
         ts = [self._i32(shifts_obs), self._i32(shifts_next), f32(noise_critic), f32(noise_actor)]
         ptrs = [L.ptr(t) for t in ts]
@@ -395,8 +397,29 @@ class PixelEngine:
             ptrs[0] = C.c_void_p(-2)
         elif keep_augmented:                # reuse the images exorl_pixel_agent_augment made
             ptrs[0] = C.c_void_p(-1)
-        L.check(self.lib.exorl_pixel_agent_update(self.h, stddev, *ptrs, L.current_stream()))
         self._keep_u = ts
+        return ptrs
+
+    def update(self, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False, keep_encoded=False):
+        ptrs = self._update_args(shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
+        L.check(self.lib.exorl_pixel_agent_update(self.h, stddev, *ptrs, L.current_stream()))
+
+    def update_phase(self, phase, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False,
+                     keep_encoded=False):
+        """One of the three phases of update() (exorl_pixel_agent_update_phase): 0 -> grad_buffer(0) ready, 1 -> grad_buffer(1) ready, 2."""
+        ptrs = self._update_args(shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
+        L.check(self.lib.exorl_pixel_agent_update_phase(self.h, phase, stddev, *ptrs, L.current_stream()))
+
+    def grad_buffer(self, exchange):
+        """Device view of what a data-parallel step sum-all-reduces after phase `exchange`: 0 critic (+ encoder) gradients, 1 actor gradients."""
+        p, n = C.c_void_p(), C.c_int64()
+        L.check(self.lib.exorl_pixel_agent_grad_buffer(self.h, exchange, C.byref(p), C.byref(n)))
+        return self._view(p.value, n.value)
+
+    def set_comm(self, comm):
+        """Attach an exorl_amd.comm.Comm of world_size ranks: update() then runs the data-parallel step in one call."""
+        L.check(self.lib.exorl_pixel_agent_set_comm(self.h, comm.h if comm is not None else None))
+        self.comm = comm
 
     def augment(self, shifts_obs=None, shifts_next=None):
         ts = [self._i32(shifts_obs), self._i32(shifts_next)]

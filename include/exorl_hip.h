@@ -32,8 +32,9 @@
 extern "C" {
 #endif
 
-#define EXORL_ABI_VERSION 9      /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
-                                    9: exorl_debug_gemm_stamps and exorl_debug_conv_stamps removed; exorl_gemm_tune keeps five bits */
+#define EXORL_ABI_VERSION 10     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
+                                    9: exorl_debug_gemm_stamps and exorl_debug_conv_stamps removed; exorl_gemm_tune keeps five bits
+                                    10: exorl_pixel_cfg.world_size; exorl_pixel_agent_update_phase / _grad_buffer / _set_comm */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -459,6 +460,7 @@ typedef struct exorl_pixel_cfg {
     float lr, tau, stddev_clip;
     int32_t sf_dim;            /* > 0: CriticSF (aps.py:17-60) — each Q head emits sf_dim successor features, Q = task . features, the task being the meta row */
     uint64_t seed;
+    int32_t world_size;        /* data-parallel ranks (0 and 1: one): every mean over the batch is over batch * world_size rows, metrics are partial means */
 } exorl_pixel_cfg;
 typedef struct exorl_pixel_agent exorl_pixel_agent_t;
 #define EXORL_PNET_ENCODER 0
@@ -480,6 +482,21 @@ int exorl_pixel_agent_set_batch(exorl_pixel_agent_t* a, const unsigned char* obs
  * noise_*: (batch, act_dim) standard normals for the TruncatedNormal draws (critic target first, actor second) or null. */
 int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev,
                              const float* noise_critic_dev, const float* noise_actor_dev, void* stream);
+/* The same update as three phases, for data parallelism (world_size > 1; exorl_pixel_agent_update then refuses without a communicator).
+ * Arguments as exorl_pixel_agent_update's; each phase reads only its own (phase 0 the shifts and noise_critic, phase 1 noise_actor).
+ *   phase 0 -> augmentation (or the -1 / -2 sentinels), encoding, critic forward + backward, encoder backward when it trains:
+ *              exchange 0 ready (sum-all-reduce it)
+ *   phase 1 -> critic Adam, encoder Adam, actor forward + backward on the stepped critic: exchange 1 ready (sum-all-reduce it)
+ *   phase 2 -> actor Adam, critic soft update
+ * With world_size == 1, phases 0, 1, 2 back to back are exorl_pixel_agent_update bit for bit. */
+int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, float stddev, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev,
+                                   const float* noise_critic_dev, const float* noise_actor_dev, void* stream);
+/* The gradients a rank contributes: exchange 0 = the critic's then (set_train_encoder(1)) the encoder's, one contiguous range; exchange 1 = the
+ * actor's. *n in floats (padding included: it stays zero). */
+int exorl_pixel_agent_grad_buffer(exorl_pixel_agent_t* a, int32_t exchange, float** ptr_dev, int64_t* n);
+/* Attach a communicator of world_size ranks (NULL detaches): exorl_pixel_agent_update then all-reduces both exchanges between its phases on
+ * `stream`. The critic's part of exchange 0 is reduced on a second stream while the encoder's backward pass runs. */
+int exorl_pixel_agent_set_comm(exorl_pixel_agent_t* a, exorl_comm_t* c);
 int exorl_pixel_agent_metrics(exorl_pixel_agent_t* a, float* host_out /* EXORL_N_METRICS */, void* stream);
 /* Primitives for agents that put a module between augmentation and the DDPG step (Proto on pixels, proto.py:159-207): augment once,
  * encode with the online or the target encoder, push a feature gradient back through the encoder with a chosen optimiser state,

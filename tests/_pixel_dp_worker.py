@@ -1,0 +1,108 @@
+"""One data-parallel rank of the pixel product path, run as a fresh child process (tests/test_gpu_pixel_dp.py starts two of them). Both
+ranks sit on cuda:0 and talk gloo, so DDPGAgent._pix_step's phase split + torch.distributed.all_reduce of the exchange buffers and _metrics'
+all-reduce execute for real on a one-GPU box."""
+import json
+import os
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / 'tests'))
+
+C_, HW, A, F, H, B_GLOBAL, STEPS, SKILLS = 3, 84, 6, 50, 256, 128, 3, 8
+
+
+def _kw(kind, batch, reward_free):
+    return dict(name=kind, reward_free=reward_free, obs_type='pixels', obs_shape=(C_, HW, HW), action_shape=(A,), device='cuda:0', lr=1e-4,
+                feature_dim=F, hidden_dim=H, critic_target_tau=0.01, num_expl_steps=0, update_every_steps=1, stddev_schedule=0.2, nstep=3,
+                batch_size=batch, stddev_clip=0.3, init_critic=True, use_tb=True, use_wandb=False)
+
+
+def build(kind, batch):
+    """Same seed -> same initial weights in every process (the reference's RNG consumption does not depend on the batch size)."""
+    from exorl_amd import agents
+    torch.manual_seed(33)
+    if kind == 'ddpg':             # plain DDPG has no module: its pretraining step (reward_free=True) is the DDPG pixel step too
+        return agents.DDPGAgent(**_kw(kind, batch, True))
+    return agents.DIAYNAgent(update_skill_every_step=50, skill_dim=SKILLS, diayn_scale=1.0, update_encoder=True, skill_type='uniform',
+                             **_kw(kind, batch, False))
+
+
+def hooks(ag, rows):
+    """Shifts and noise drawn for the GLOBAL batch in every process (one stream), each rank keeping its rows."""
+    import _synth
+    rs, ns = np.random.RandomState(11), _synth.NoiseStream(9)
+    ag.shift_hook = lambda n: np.ascontiguousarray(rs.randint(0, 9, (B_GLOBAL, 2)).astype(np.int32)[rows])
+    ag.noise_hook = lambda shape: np.ascontiguousarray(ns.draw((B_GLOBAL, shape[1]))[rows])
+
+
+def batch(kind, step, rows=slice(None)):
+    rs = np.random.RandomState(700 + step)
+    obs = rs.randint(0, 256, (B_GLOBAL, C_, HW, HW)).astype(np.uint8)
+    nxt = rs.randint(0, 256, (B_GLOBAL, C_, HW, HW)).astype(np.uint8)
+    b = [obs, rs.uniform(-1, 1, (B_GLOBAL, A)).astype(np.float32), rs.uniform(0, 1, B_GLOBAL).astype(np.float32),
+         np.full(B_GLOBAL, 0.99, np.float32), nxt]
+    if kind == 'diayn':
+        b.append(np.eye(SKILLS, dtype=np.float32)[rs.randint(0, SKILLS, B_GLOBAL)])
+    return tuple(np.ascontiguousarray(x[rows]) for x in b)
+
+
+def views(ag):
+    return [('encoder', ag.encoder), ('actor', ag.actor), ('critic', ag.critic), ('critic_target', ag.critic_target)]
+
+
+def flat(view):
+    return torch.cat([p.reshape(-1) for p in view.parameters()]).cpu().numpy()
+
+
+def main(out):
+    rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
+    torch.cuda.set_device(0)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    Br = B_GLOBAL // world
+    rows = slice(rank * Br, (rank + 1) * Br)
+    for kind in ('ddpg', 'diayn'):
+        ag = build(kind, Br)
+        assert ag.world_size == world and ag.engine.batch == Br
+        hooks(ag, rows)
+        metrics = []
+        for step in range(STEPS):
+            m = ag.update(iter([batch(kind, step, rows)]), step)
+            metrics.append({k: float(v) for k, v in m.items()})
+        torch.cuda.synchronize()
+        np.savez(out / f'{kind}_rank{rank}.npz', **{n: flat(v) for n, v in views(ag)})
+        json.dump(metrics, open(out / f'metrics_{kind}_rank{rank}.json', 'w'))
+        del ag
+    # no hooks: identical frames on both ranks, the device's shifts and noise
+    from exorl_amd import _lib as L
+    ag = build('ddpg', Br)
+    eng = ag.engine
+    b = batch('ddpg', 0, slice(0, Br))
+    eng.set_batch(*b)
+    eng.augment()
+    feat = eng.feature_view(eng.encode(0))[:4].cpu().numpy()
+    noise = torch.empty(Br * A, dtype=torch.float32, device=eng.device)
+    L.check(eng.lib.exorl_debug_philox_normal(eng.cfg.seed, 0, noise.numel(), noise.data_ptr(), L.current_stream()))
+    np.savez(out / f'unhooked_rank{rank}.npz', seed=np.uint64(eng.cfg.seed), feat=feat, noise=noise.cpu().numpy())
+    del ag, eng
+    # reward-free module agents keep refusing under data parallelism
+    from exorl_amd import agents
+    try:
+        agents.ProtoAgent(pred_dim=16, proj_dim=32, queue_size=256, num_protos=16, tau=0.1, encoder_target_tau=0.05, topk=3, update_encoder=True,
+                          **_kw('proto', Br, True))
+        res = {'type': None, 'msg': 'constructed'}
+    except Exception as e:           # noqa: BLE001 — recorded for the parent's assertion
+        res = {'type': type(e).__name__, 'msg': str(e)}
+    json.dump(res, open(out / f'refusal_rank{rank}.json', 'w'))
+    torch.cuda.synchronize()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+if __name__ == '__main__':
+    main(Path(sys.argv[1]))
