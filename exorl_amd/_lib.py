@@ -23,6 +23,9 @@ N_METRICS = 16
 INTR_RND, INTR_ICM, INTR_ICM_APT, INTR_DISAGREEMENT, INTR_DIAYN, INTR_PROTO, INTR_APS, INTR_SMM = 0, 1, 2, 3, 4, 5, 6, 7
 IM_LOSS, IM_INTR_REWARD, IM_EXTR_REWARD, IM_RMS_MEAN, IM_RMS_STD, IM_ACC, IM_ENT_REWARD, IM_SF_REWARD = range(8)
 N_INTR_METRICS = 8
+INTR_XCHG_GRAD, INTR_XCHG_REP, INTR_XCHG_MOMENTS = 0, 1, 2
+XCHG_F32, XCHG_F64 = 0, 1
+XCHG_SUM, XCHG_GATHER = 0, 1
 
 
 class ReplayCfg(C.Structure):
@@ -50,7 +53,7 @@ class IntrCfg(C.Structure):
                 ('n_models', c_int32), ('flags', c_int32), ('lr', c_float), ('scale', c_float), ('knn_clip', c_float), ('clip_val', c_float),
                 ('num_protos', c_int32), ('queue_size', c_int32), ('tau', c_float), ('target_tau', c_float),
                 ('sp_lr', c_float), ('vae_lr', c_float), ('vae_beta', c_float), ('state_ent_coef', c_float), ('latent_ent_coef', c_float),
-                ('latent_cond_ent_coef', c_float), ('goal_x', c_float), ('goal_y', c_float)]
+                ('latent_cond_ent_coef', c_float), ('goal_x', c_float), ('goal_y', c_float), ('world_size', c_int32), ('rank', c_int32)]
 
 
 class IntrBatch(C.Structure):
@@ -91,6 +94,9 @@ PROTOTYPES = {
     'exorl_pixel_agent_update_phase': (C.c_int, [c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_pixel_agent_grad_buffer': (C.c_int, [c_void_p, c_int32, P(c_void_p), P(c_int64)]),
     'exorl_pixel_agent_set_comm': (C.c_int, [c_void_p, c_void_p]),
+    'exorl_pixel_agent_encoder_step_phase': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    'exorl_pixel_agent_rnd_features_phase': (C.c_int, [c_void_p, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    'exorl_pixel_agent_bn_partials': (C.c_int, [c_void_p, P(c_void_p), P(c_int64)]),
     'exorl_pixel_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
     'exorl_pixel_agent_act': (C.c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_aug_shift': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
@@ -110,6 +116,8 @@ PROTOTYPES = {
     'exorl_intr_state': (C.c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_int64)]),
     'exorl_intr_queue': (C.c_int, [c_void_p, P(c_void_p), P(c_int64), P(c_int64), P(c_int64), c_int32]),
     'exorl_intr_update': (C.c_int, [c_void_p, P(IntrBatch), c_int32, c_void_p]),
+    'exorl_intr_update_phase': (C.c_int, [c_void_p, P(IntrBatch), c_int32, c_int32, P(c_int32), c_void_p]),
+    'exorl_intr_exchange': (C.c_int, [c_void_p, c_int32, P(c_void_p), P(c_int64), P(c_int32), P(c_int32)]),
     'exorl_intr_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
     'exorl_intr_opt_steps': (C.c_int, [c_void_p, P(c_int64), c_int32]),
     'exorl_intr_counter': (C.c_int, [c_void_p, c_void_p, c_int32]),

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import utils
-from .engine import AgentEngine, IntrEngine, PixelEngine
+from .engine import AgentEngine, IntrEngine, PixelEngine, drive_phases
 
 _OFFLINE_ACTOR_KEYS = ['policy.0.weight', 'policy.0.bias', 'policy.1.weight', 'policy.1.bias',
                        'policy.3.weight', 'policy.3.bias', 'policy.5.weight', 'policy.5.bias']
@@ -589,11 +589,11 @@ class DDPGAgent(_AgentBase):
         ws = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             ws = torch.distributed.get_world_size()
-        if ws > 1 and reward_free and type(self) is not DDPGAgent:
-            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU: its module step needs "
-                                      "the global batch's encodings (BatchNorm2d statistics, kNN over the batch, Sinkhorn and the queue). Under "
-                                      "data parallelism the pixel path runs DDPGAgent (any reward_free) and every agent with reward_free=False "
-                                      "(fine-tuning: the DDPG pixel step)")
+        if ws > 1 and reward_free and isinstance(self, ProtoAgent):
+            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU: Proto is the one "
+                                      "pixel agent whose pretraining step does not shard (its candidate queue draws rows from the global batch's "
+                                      "softmax and its Sinkhorn runs over the batch). Under data parallelism the pixel path runs every agent with "
+                                      "reward_free=False (fine-tuning: the DDPG pixel step) and every other agent's pretraining step")
         if ws > 1:          # every rank draws its own rows of the global batch's shifts and noise (as _AgentBase._build does for states)
             seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF
         self.world_size = ws
@@ -790,6 +790,13 @@ class _IntrAgent(DDPGAgent):
     def _module_batch(self):
         return self.engine.batch * getattr(self, 'world_size', 1)
 
+    def _intr_dp(self):
+        """IntrEngine's batch arguments. On states the module stays replicated on the gathered global batch (_intr_step_dp); on pixels under
+        torch.distributed it is sharded: this rank's rows, with world_size and rank (exorl_intr_update_phase and its exchanges)."""
+        if getattr(self, 'obs_type', 'states') == 'pixels' and self.world_size > 1:
+            return dict(batch=self.engine.batch, world_size=self.world_size, rank=torch.distributed.get_rank())
+        return dict(batch=self._module_batch)
+
     def _dp_buffers(self):
         if getattr(self, '_dp', None) is None:
             eng, ws = self.engine, self.world_size
@@ -836,9 +843,43 @@ class _IntrAgent(DDPGAgent):
     # second .step() inside update_critic finds no gradients (Adam skips parameters whose .grad is None, step counts included).
     _PIX_GRAD = 0                        # which encoding carries the graph into the module's loss: 0 obs, 1 next_obs
 
+    # Under torch.distributed every rank runs the module step, the encoder step and BatchNorm2d on its own rows: each loss is a mean over
+    # the global batch, so the gradients are partial sums the ranks add up (one exchange each), and the batch-global quantities — RND's
+    # BatchNorm2d statistics, the running RMS's batch moments, the kNN targets of ICM-APT and APS — are small exchanges of their own.
+    @property
+    def _pix_dp(self):
+        return getattr(self, 'obs_type', 'states') == 'pixels' and self.world_size > 1
+
+    def _intr_run(self, *a, **k):
+        """self.intr.update, or its phases with the exchanges each one names run over torch.distributed."""
+        if not self._pix_dp:
+            return self.intr.update(*a, **k)
+        drive_phases(lambda ph: self.intr.update_phase(ph, *a, **k), self.intr.exchange, self.intr.rank)
+
+    def _encoder_step(self, which, dfeat_ptr, opt):
+        eng = self.engine
+        if not self._pix_dp:
+            return eng.encoder_step(which, dfeat_ptr, opt)
+        eng.encoder_step_phase(0, which, dfeat_ptr, opt)
+        torch.distributed.all_reduce(eng.grad_buffer(2))
+        eng.encoder_step_phase(1, which, dfeat_ptr, opt)
+
+    def _intr_metrics(self):
+        """The module's metrics as global means: its partial means summed over the ranks; the RMS state (slots 3, 4 of RND, ICM-APT and
+        APS) is the same on every rank and is not summed."""
+        raw = self.intr.metrics_raw()
+        if not self._pix_dp:
+            return raw
+        t = torch.from_numpy(raw.copy()).to(self.engine.device)
+        torch.distributed.all_reduce(t)
+        out = t.cpu().numpy()
+        if self.intr.kind in ('rnd', 'icm_apt', 'aps'):
+            out[L.IM_RMS_MEAN:L.IM_RMS_STD + 1] = raw[L.IM_RMS_MEAN:L.IM_RMS_STD + 1]
+        return out
+
     def _pix_module(self, fo, fn, s):
         """Module step + intrinsic reward on the encodings (device pointers); d(loss)/d(encoding) lands in self._dobs."""
-        self.intr.update(fo, s.action, fn, s.reward, s.reward, True, dobs_out=self._dobs.data_ptr())
+        self._intr_run(fo, s.action, fn, s.reward, s.reward, True, dobs_out=self._dobs.data_ptr())
 
     def _pix_alloc(self):
         """Called by the subclass constructors once self.intr exists."""
@@ -861,7 +902,7 @@ class _IntrAgent(DDPGAgent):
         fo, fn = eng.encode(0), eng.encode(1)
         if self.reward_free:
             self._pix_module(fo, fn, s)
-            eng.encoder_step(self._PIX_GRAD, self._dobs.data_ptr(), 0)
+            self._encoder_step(self._PIX_GRAD, self._dobs.data_ptr(), 0)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
         self._pix_step(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
@@ -870,7 +911,7 @@ class _IntrAgent(DDPGAgent):
         if self.use_tb or self.use_wandb:
             metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
             if self.reward_free:
-                ri = self.intr.metrics_raw()
+                ri = self._intr_metrics()
                 metrics[self.LOSS_KEY] = float(ri[L.IM_LOSS])
                 metrics['intr_reward'] = float(ri[L.IM_INTR_REWARD])
                 metrics['extr_reward'] = float(ri[L.IM_EXTR_REWARD])
@@ -975,7 +1016,7 @@ class RNDAgent(_IntrAgent):
                 view_p.zero_()
         else:
             w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, rnd_rep_dim)] * 2)      # predictor then target (rnd.py:28-43)
-        self.intr = IntrEngine('rnd', O, self.action_dim, H, self._module_batch, rep_dim=rnd_rep_dim, lr=self.lr, scale=rnd_scale,
+        self.intr = IntrEngine('rnd', O, self.action_dim, H, **self._intr_dp(), rep_dim=rnd_rep_dim, lr=self.lr, scale=rnd_scale,
                                precision=self._precision, device=self.device, encoded=pixels)
         if pixels:
             conv_shapes = [s_ for l in range(4) for s_ in ((32, self.obs_shape[0] if l == 0 else 32, 3, 3), (32,))]
@@ -993,6 +1034,16 @@ class RNDAgent(_IntrAgent):
         self.intrinsic_reward_rms = _RmsView(self.intr)
         self._pix_alloc()
 
+    def _rnd_features(self, shifts, clip_val=5.0):
+        """RND.forward's front end; under torch.distributed the BatchNorm2d statistics are over every rank's frames."""
+        eng = self.engine
+        if not self._pix_dp:
+            return eng.rnd_features(shifts, clip_val)
+        for phase in range(2):
+            eng.rnd_features_phase(phase, shifts, clip_val)
+            torch.distributed.all_reduce(eng.bn_partials())
+        return eng.rnd_features_phase(2, None, clip_val)
+
     def _update_pixels(self, replay_iter, step):
         """rnd.py:110-159 on pixels. RND.forward augments the raw frames itself, normalises them with a BatchNorm2d and runs the agent's
         encoder inside its predictor (and a frozen copy inside its target): update_rnd steps that encoder twice on the same gradients
@@ -1007,18 +1058,18 @@ class RNDAgent(_IntrAgent):
         B, A = eng.batch, self.action_dim
         sh = lambda: self.shift_hook(B) if self.shift_hook else None
         if self.reward_free:
-            fp, ft = eng.rnd_features(sh(), 5.0)
-            self.intr.update(fp, None, ft, s.reward, s.reward, 2, dobs_out=self._dobs.data_ptr())
-            eng.encoder_step(0, self._dobs.data_ptr(), 2)
-            fp, ft = eng.rnd_features(sh(), 5.0)
-            self.intr.update(fp, None, ft, s.reward, s.reward, False)
+            fp, ft = self._rnd_features(sh())
+            self._intr_run(fp, None, ft, s.reward, s.reward, 2, dobs_out=self._dobs.data_ptr())
+            self._encoder_step(0, self._dobs.data_ptr(), 2)
+            fp, ft = self._rnd_features(sh())
+            self._intr_run(fp, None, ft, s.reward, s.reward, False)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
         self._pix_step(stddev, sh(), sh(), self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None)
         metrics = dict()
         if self.use_tb or self.use_wandb:
             metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-            ri = self.intr.metrics_raw()
+            ri = self._intr_metrics() if self.reward_free else self.intr.metrics_raw()
             if self.reward_free:
                 metrics['rnd_loss'] = float(ri[L.IM_LOSS])
                 metrics['intr_reward'] = float(ri[L.IM_INTR_REWARD])
@@ -1042,7 +1093,7 @@ class ICMAgent(_IntrAgent):
         self.update_encoder = update_encoder
         O, A, H = self.obs_dim, self.action_dim, self.hidden_dim
         w = _seq_init([('lin', O + A, H), ('lin', H, O), ('lin', 2 * O, H), ('lin', H, A)])
-        self.intr = IntrEngine('icm', O, A, H, self._module_batch, lr=self.lr, scale=icm_scale, precision=self._precision,
+        self.intr = IntrEngine('icm', O, A, H, **self._intr_dp(), lr=self.lr, scale=icm_scale, precision=self._precision,
                                device=self.device)
         self.icm = NetView(self.intr, None, _ICM_KEYS)
         for p, t in zip(self.icm.parameters(), w):
@@ -1066,7 +1117,7 @@ class ICMAPTAgent(_IntrAgent):
         self.update_encoder = update_encoder
         O, A, H, R = self.obs_dim, self.action_dim, self.hidden_dim, icm_rep_dim
         w = _seq_init([('lin', O, R), ('ln', R), ('lin', R + A, H), ('lin', H, R), ('lin', 2 * R, H), ('lin', H, A)])
-        self.intr = IntrEngine('icm_apt', O, A, H, self._module_batch, rep_dim=R, lr=self.lr, scale=icm_scale, knn_k=knn_k,
+        self.intr = IntrEngine('icm_apt', O, A, H, **self._intr_dp(), rep_dim=R, lr=self.lr, scale=icm_scale, knn_k=knn_k,
                                knn_avg=knn_avg, knn_rms=knn_rms, knn_clip=knn_clip, precision=self._precision, device=self.device)
         self.icm = NetView(self.intr, None, _APT_KEYS)
         for p, t in zip(self.icm.parameters(), w):
@@ -1093,7 +1144,7 @@ class DisagreementAgent(_IntrAgent):
         for _ in range(5):
             for m in (nn.Linear(O + A, H), nn.Linear(H, O)):
                 w += [m.weight.data, m.bias.data]
-        self.intr = IntrEngine('disagreement', O, A, H, self._module_batch, lr=self.lr, n_models=5, precision=self._precision,
+        self.intr = IntrEngine('disagreement', O, A, H, **self._intr_dp(), lr=self.lr, n_models=5, precision=self._precision,
                                device=self.device)
         self.disagreement = NetView(self.intr, None, _DIS_KEYS)
         for p, t in zip(self.disagreement.parameters(), w):
@@ -1154,7 +1205,7 @@ class DIAYNAgent(_MetaObsMixin, _IntrAgent):
         super().__init__(**kwargs)
         O, H = self.obs_dim - self.skill_dim, self.hidden_dim
         w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, skill_dim)])
-        self.intr = IntrEngine('diayn', O, self.action_dim, H, self._module_batch, rep_dim=skill_dim, lr=self.lr, scale=diayn_scale,
+        self.intr = IntrEngine('diayn', O, self.action_dim, H, **self._intr_dp(), rep_dim=skill_dim, lr=self.lr, scale=diayn_scale,
                                precision=self._precision, device=self.device)
         self.diayn = NetView(self.intr, None, _DIAYN_KEYS)
         for p, t in zip(self.diayn.parameters(), w):
@@ -1162,7 +1213,7 @@ class DIAYNAgent(_MetaObsMixin, _IntrAgent):
         self._pix_alloc()
 
     def _pix_module(self, fo, fn, s):          # the discriminator reads the next frame's encoding (diayn.py:141-147)
-        self.intr.update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.skill_dim, dobs_out=self._dobs.data_ptr())
+        self._intr_run(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.skill_dim, dobs_out=self._dobs.data_ptr())
 
     def get_meta_specs(self):
         return (_Spec((self.skill_dim,), np.float32, 'skill'),)
@@ -1195,7 +1246,7 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
     _PIX_GRAD = 1                        # update_aps reaches the encoder through next_obs (aps.py:147-159,203-204)
 
     def _pix_module(self, fo, fn, s):
-        self.intr.update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.sf_dim, dobs_out=self._dobs.data_ptr())
+        self._intr_run(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.sf_dim, dobs_out=self._dobs.data_ptr())
 
     def __init__(self, update_task_every_step, sf_dim, knn_rms, knn_k, knn_avg, knn_clip, num_init_steps, lstsq_batch_size, update_encoder,
                  **kwargs):
@@ -1208,7 +1259,7 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
         super().__init__(**kwargs)
         O, H = self.obs_dim - self.sf_dim, self.hidden_dim
         w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, sf_dim)])
-        self.intr = IntrEngine('aps', O, self.action_dim, H, self._module_batch, rep_dim=sf_dim, lr=self.lr, knn_k=knn_k, knn_avg=knn_avg,
+        self.intr = IntrEngine('aps', O, self.action_dim, H, **self._intr_dp(), rep_dim=sf_dim, lr=self.lr, knn_k=knn_k, knn_avg=knn_avg,
                                knn_rms=knn_rms, knn_clip=knn_clip, precision=self._precision, device=self.device)
         self.aps = NetView(self.intr, None, _APS_KEYS)
         for p, t in zip(self.aps.parameters(), w):
@@ -1316,7 +1367,7 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         O, H = self.obs_dim - z_dim, self.hidden_dim
         self.goal = (150, 75)
         w = _smm_init(O, z_dim, H)
-        self.intr = IntrEngine('smm', O, self.action_dim, H, self._module_batch, rep_dim=z_dim, sp_lr=sp_lr, vae_lr=vae_lr, vae_beta=vae_beta,
+        self.intr = IntrEngine('smm', O, self.action_dim, H, **self._intr_dp(), rep_dim=z_dim, sp_lr=sp_lr, vae_lr=vae_lr, vae_beta=vae_beta,
                                state_ent_coef=state_ent_coef, latent_ent_coef=latent_ent_coef, latent_cond_ent_coef=latent_cond_ent_coef,
                                goal=self.goal, precision=self._precision, device=self.device, encoded=self.obs_type == 'pixels')
         self.smm = NetView(self.intr, None, _SMM_KEYS)
@@ -1337,8 +1388,8 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         eng = self.engine
         xz = torch.cat([eng.feature_view(fo), eng.meta_rows()], 1).contiguous()
         e = self._eps()
-        self.intr.update(xz.data_ptr(), None, None, s.reward, s.reward, True, skill=s.meta, obs_ld=xz.shape[1], skill_ld=self.z_dim,
-                         cat_uniform=e.data_ptr() if e is not None else None, dobs_out=self._dobs.data_ptr())
+        self._intr_run(xz.data_ptr(), None, None, s.reward, s.reward, True, skill=s.meta, obs_ld=xz.shape[1], skill_ld=self.z_dim,
+                       cat_uniform=e.data_ptr() if e is not None else None, dobs_out=self._dobs.data_ptr())
         self._keep_eps = (e, xz)
 
     def get_meta_specs(self):
@@ -1395,7 +1446,7 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         metrics = super().update(replay_iter, step)
         if self.obs_type == 'pixels':                    # smm.py:260-265: loss_vae / loss_pred ride with use_tb, nothing else is added
             if self.reward_free and (self.use_tb or self.use_wandb):
-                metrics['loss_pred'] = float(self.intr.metrics_raw()[5])
+                metrics['loss_pred'] = float(self._intr_metrics()[5])
             return metrics
         if self.reward_free:                             # smm.py:249-258: these are reported whatever use_tb says
             raw = self.intr.metrics_raw()

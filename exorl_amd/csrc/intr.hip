@@ -81,12 +81,13 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(float* __restrict__ d, co
         d[i] = a[i] > 0.f ? d[i] : 0.f;
 }
 
-// err[b] = mean_j (t - p)^2 (rnd.py:54-56); dpred = d(mean_b err)/dp = -2 (t - p) / R / B. One wave per row.
+// err[b] = mean_j (t - p)^2 (rnd.py:54-56); dpred = d(mean_b err)/dp = -2 (t - p) / R / B. One wave per row. grows: the rows the
+// loss mean is over (batch * world_size; the gradients are then partial sums the ranks add up)
 __global__ __launch_bounds__(256) void rnd_err_kernel(const float* __restrict__ pred, const float* __restrict__ targ, float* __restrict__ err,
-                                                      float* __restrict__ dpred, int rows, int R) {
+                                                      float* __restrict__ dpred, int rows, int R, int grows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const float invR = 1.0f / (float)R, invB = 1.0f / (float)rows;
+    const float invR = 1.0f / (float)R, invB = 1.0f / (float)grows;
     float s = 0.f;
     for (int j = lane; j < R; j += 64) {
         const float d = targ[(int64_t)row * R + j] - pred[(int64_t)row * R + j];
@@ -219,7 +220,7 @@ static void launch_icm_err(const float* pred, int D, const float* tgt, int64_t l
 
 // reward = log(fe * scale + 1) (icm.py:86-92) + reward bookkeeping; single block
 __global__ __launch_bounds__(1024) void icm_reward_kernel(const float* __restrict__ fe, const float* extr, float* reward, int B, float scale,
-                                                          float* __restrict__ metrics) {
+                                                          float* __restrict__ metrics, int Bg) {
     __shared__ float red[17];
     float e = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(1024) void icm_reward_kernel(const float* __restric
         rs += r;
     }
     rs = block_sum(rs, red);
-    if (threadIdx.x == 0) { metrics[EXORL_IM_EXTR_REWARD] = e / (float)B; metrics[EXORL_IM_INTR_REWARD] = rs / (float)B; }
+    if (threadIdx.x == 0) { metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg; metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg; }
 }
 
 // utils.PBE.__call__ after the top-k (utils.py:301-319): topk (B,k) ascending; single block
@@ -281,6 +282,103 @@ __global__ __launch_bounds__(1024) void pbe_reward_kernel(const float* __restric
     if (threadIdx.x == 0) {
         metrics[EXORL_IM_EXTR_REWARD] = e / (float)B;
         metrics[EXORL_IM_INTR_REWARD] = rs / (float)B;
+        metrics[EXORL_IM_RMS_MEAN] = st->M;
+        metrics[EXORL_IM_RMS_STD] = sqrtf(st->S);
+    }
+}
+
+// ---- data parallel: utils.RMS over the global batch (rnd.py:98-103, utils.py:264-276,301-319) ------------------------------
+// Each rank reduces its own values to (n, mean, M2) — the mean and the centred sum in fp32 as the single-rank kernels above form them —
+// and the ranks' moments are all-gathered. The combine merges them in rank order in double (Chan et al.), so every rank computes the
+// same RMS update bit for bit; for one rank it passes the fp32 moments through. Values: RND's per-row error (k = 1, avg = 0), or PBE's
+// top-k distances (all B*k with avg, else the k-th of each row).
+__global__ __launch_bounds__(1024) void rms_moments_kernel(const float* __restrict__ x, int B, int k, int avg, double* __restrict__ mom) {
+    __shared__ float red[17];
+    const int n = avg ? B * k : B;
+    auto val = [&](int i) { return avg ? x[i] : x[(int64_t)i * k + (k - 1)]; };
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) s += val(i);
+    const float mean = block_sum(s, red) / (float)n;
+    float q = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) { const float d = val(i) - mean; q += d * d; }
+    q = block_sum(q, red);
+    if (threadIdx.x == 0) { mom[0] = (double)n; mom[1] = (double)mean; mom[2] = (double)q; }
+}
+// merge `world` (n, mean, M2) triples in rank order, then utils.RMS.__call__ with the merged batch mean and unbiased variance
+__device__ void rms_combine_update(RmsState* st, const double* __restrict__ mom, int world) {
+    double n = mom[0], mean = mom[1], m2 = mom[2];
+    for (int r = 1; r < world; ++r) {
+        const double nr = mom[3 * r], d = mom[3 * r + 1] - mean, tot = n + nr;
+        mean += d * nr / tot;
+        m2 += mom[3 * r + 2] + d * d * n * nr / tot;
+        n = tot;
+    }
+    rms_update(st, (float)mean, (float)(m2 / (n > 1.0 ? n - 1.0 : 1.0)), (int)n);
+}
+// rnd_reward_kernel on this rank's rows after the moment exchange; metrics are partial means over Bg rows
+__global__ __launch_bounds__(1024) void rnd_reward_dp_kernel(const float* __restrict__ err, const float* extr, float* reward, int B, int Bg, float scale,
+                                                             RmsState* st, const double* __restrict__ mom, int world, float* __restrict__ metrics) {
+    __shared__ float red[17];
+    __shared__ float sh_S;
+    float e = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
+    e = block_sum(e, red);
+    if (threadIdx.x == 0) {
+        rms_combine_update(st, mom, world);
+        sh_S = st->S;
+        metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg;
+        metrics[EXORL_IM_RMS_MEAN] = st->M;
+        metrics[EXORL_IM_RMS_STD] = sqrtf(st->S);
+    }
+    __syncthreads();
+    const float denom = sqrtf(sh_S) + 1e-8f;
+    float rs = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) {
+        const float r = scale * err[i] / denom;
+        reward[i] = r;
+        rs += r;
+    }
+    rs = block_sum(rs, red);
+    if (threadIdx.x == 0) metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg;
+}
+// pbe_reward_kernel on this rank's rows (topk: its rows against the gathered batch); mom == null: no RMS (knn_rms false)
+__global__ __launch_bounds__(1024) void pbe_reward_dp_kernel(const float* __restrict__ topk, const float* extr, float* reward, int B, int Bg, int k,
+                                                             int avg, float clip, RmsState* st, const double* __restrict__ mom, int world,
+                                                             float* __restrict__ metrics) {
+    __shared__ float red[17];
+    __shared__ float sh_M;
+    float e = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
+    e = block_sum(e, red);
+    if (threadIdx.x == 0 && mom) { rms_combine_update(st, mom, world); sh_M = st->M; }
+    __syncthreads();
+    const bool use_rms = mom != nullptr;
+    const float M = use_rms ? sh_M : 1.0f;
+    float rs = 0.f;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        float r;
+        if (avg) {
+            float acc = 0.f;
+            for (int j = 0; j < k; ++j) {
+                float v = topk[(int64_t)b * k + j];
+                if (use_rms) v = v / M;
+                if (clip >= 0.f) v = fmaxf(v - clip, 0.f);
+                acc += v;
+            }
+            r = acc / (float)k;
+        } else {
+            r = topk[(int64_t)b * k + (k - 1)];
+            if (use_rms) r = r / M;
+            if (clip >= 0.f) r = fmaxf(r - clip, 0.f);
+        }
+        r = logf(r + 1.0f);
+        reward[b] = r;
+        rs += r;
+    }
+    rs = block_sum(rs, red);
+    if (threadIdx.x == 0) {
+        metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg;
+        metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg;
         metrics[EXORL_IM_RMS_MEAN] = st->M;
         metrics[EXORL_IM_RMS_STD] = sqrtf(st->S);
     }
@@ -374,7 +472,7 @@ __global__ __launch_bounds__(256) void disagreement_reward_wide_kernel(PredSet p
 // dlogits = (softmax - onehot(z)) / B (CrossEntropyLoss, mean), reward = (lsm[z] - log(1/S)) * scale. One wave per row.
 __global__ __launch_bounds__(256) void diayn_kernel(const float* __restrict__ logits, const float* __restrict__ skill, int64_t lds_, int S,
                                                     float* __restrict__ nll, float* __restrict__ hit, float* __restrict__ dlogits,
-                                                    float* reward, float scale, int rows) {
+                                                    float* reward, float scale, int rows, int grows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     float mx = -INFINITY, smx = -INFINITY;
@@ -400,7 +498,7 @@ __global__ __launch_bounds__(256) void diayn_kernel(const float* __restrict__ lo
         if (reward) reward[row] = (lz - logf(1.0f / (float)S)) * scale;
     }
     if (dlogits) {
-        const float invB = 1.0f / (float)rows;
+        const float invB = 1.0f / (float)grows;
         for (int j = lane; j < S; j += 64)
             dlogits[(int64_t)row * S + j] = (expf(logits[(int64_t)row * S + j] - lse) - (j == asx ? 1.f : 0.f)) * invB;
     }
@@ -574,14 +672,14 @@ __global__ __launch_bounds__(1024) void kth_reward_kernel(const float* __restric
 // ---- APS (aps.py:147-175) ---------------------------------------------------------------------------
 // loss_b = -task . fn with fn = F.normalize(f); df = (dfn - fn (fn . dfn)) / max(||f||, 1e-12), dfn = -task / B. One wave per row.
 __global__ __launch_bounds__(256) void aps_loss_kernel(const float* __restrict__ f, const float* __restrict__ task, int64_t ldt,
-                                                       float* __restrict__ df, float* __restrict__ loss_row, int rows, int D) {
+                                                       float* __restrict__ df, float* __restrict__ loss_row, int rows, int D, int grows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     float s = 0.f, tf = 0.f;
     for (int j = lane; j < D; j += 64) { const float v = f[(int64_t)row * D + j]; s += v * v; tf += v * task[(int64_t)row * ldt + j]; }
     const float n = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
     const float tfn = wave_sum(tf) / n;                 // task . fn
-    const float invB = 1.0f / (float)rows;
+    const float invB = 1.0f / (float)grows;
     for (int j = lane; j < D; j += 64) {
         const float fn = f[(int64_t)row * D + j] / n, dfn = -task[(int64_t)row * ldt + j] * invB;
         df[(int64_t)row * D + j] = (dfn - fn * (-tfn * invB)) / n;
@@ -590,7 +688,7 @@ __global__ __launch_bounds__(256) void aps_loss_kernel(const float* __restrict__
 }
 // reward += task . rep / ||rep|| (aps.py:164-168), metrics split into the two parts; single block
 __global__ __launch_bounds__(1024) void aps_sf_reward_kernel(const float* __restrict__ rep, const float* __restrict__ task, int64_t ldt,
-                                                             float* reward, int B, int D, float* __restrict__ metrics) {
+                                                             float* reward, int B, int D, float* __restrict__ metrics, int Bg) {
     __shared__ float red[17];
     float ss = 0.f;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
@@ -603,8 +701,8 @@ __global__ __launch_bounds__(1024) void aps_sf_reward_kernel(const float* __rest
     ss = block_sum(ss, red);
     if (threadIdx.x == 0) {
         metrics[EXORL_IM_ENT_REWARD] = metrics[EXORL_IM_INTR_REWARD];
-        metrics[EXORL_IM_SF_REWARD] = ss / (float)B;
-        metrics[EXORL_IM_INTR_REWARD] += ss / (float)B;
+        metrics[EXORL_IM_SF_REWARD] = ss / (float)Bg;
+        metrics[EXORL_IM_INTR_REWARD] += ss / (float)Bg;
     }
 }
 
@@ -616,21 +714,23 @@ __device__ __forceinline__ float philox_normal_i(uint64_t seed, uint64_t counter
     const float u1 = ((float)c[0] + 1.0f) * 2.3283064365386963e-10f, u2 = (float)c[1] * 2.3283064365386963e-10f;
     return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
 }
-// code = eps * exp(0.5 logvar) + mu (smm.py:54-58); eps kept for the backward pass
+// code = eps * exp(0.5 logvar) + mu (smm.py:54-58); eps kept for the backward pass. elem0: element index of this rank's first row in the
+// global batch, so that each rank draws the single-process epsilon of its rows
 __global__ __launch_bounds__(256) void vae_code_kernel(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ eps_in,
-                                                       uint64_t seed, uint64_t counter, float* __restrict__ eps, float* __restrict__ code, int64_t n) {
+                                                       uint64_t seed, uint64_t counter, float* __restrict__ eps, float* __restrict__ code, int64_t n,
+                                                       int64_t elem0) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float e = eps_in ? eps_in[i] : philox_normal_i(seed, counter, (uint32_t)i);
+        const float e = eps_in ? eps_in[i] : philox_normal_i(seed, counter, (uint32_t)(elem0 + i));
         eps[i] = e;
         code[i] = e * expf(0.5f * lv[i]) + mu[i];
     }
 }
 // per row: h_s_z = sum_j (x - out)^2 (smm.py:66-70), d(mean squared error)/d out
 __global__ __launch_bounds__(256) void vae_out_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ out, float* __restrict__ dout,
-                                                      float* __restrict__ hsz, int rows, int W) {
+                                                      float* __restrict__ hsz, int rows, int W, int grows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const float sc = -2.0f / ((float)rows * (float)W);
+    const float sc = -2.0f / ((float)grows * (float)W);
     float s = 0.f;
     for (int j = lane; j < W; j += 64) {
         const float d = x[(int64_t)row * ldx + j] - out[(int64_t)row * W + j];
@@ -642,10 +742,11 @@ __global__ __launch_bounds__(256) void vae_out_kernel(const float* __restrict__ 
 }
 // wide rows (pixel encodings, W = 39200): one workgroup per row, 16-byte accesses (the wave-per-row kernel took 309 us for 480 MB)
 __global__ __launch_bounds__(256) void vae_out_wide_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ out, float* __restrict__ dout,
-                                                           float* __restrict__ hsz, int rows, int W) {
+                                                           float* __restrict__ hsz, int rows, int W, int grows) {
     __shared__ float red[17];
     const int row = blockIdx.x, n4 = W >> 2;
-    const float sc = -2.0f / ((float)rows * (float)W);
+    const float sc = -2.0f / ((float)grows * (float)W);
+    (void)rows;
     const float4* x4 = reinterpret_cast<const float4*>(x + (int64_t)row * ldx);
     const float4* o4 = reinterpret_cast<const float4*>(out + (int64_t)row * W);
     float4* g4 = reinterpret_cast<float4*>(dout + (int64_t)row * W);
@@ -662,10 +763,10 @@ __global__ __launch_bounds__(256) void vae_out_wide_kernel(const float* __restri
 // gradients at (mu, logvar) of beta * KL + reconstruction, given d/d code; kle_row = -0.5 sum (1 + lv - mu^2 - e^lv)
 __global__ __launch_bounds__(256) void vae_latent_kernel(const float* __restrict__ dcode, const float* __restrict__ mu, const float* __restrict__ lv,
                                                          const float* __restrict__ eps, float* __restrict__ dmu, float* __restrict__ dlv,
-                                                         float* __restrict__ kle_row, int rows, int C, float beta) {
+                                                         float* __restrict__ kle_row, int rows, int C, float beta, int grows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const float invB = 1.0f / (float)rows;
+    const float invB = 1.0f / (float)grows;
     float k = 0.f;
     for (int j = lane; j < C; j += 64) {
         const int64_t i = (int64_t)row * C + j;
@@ -681,7 +782,8 @@ __global__ __launch_bounds__(256) void vae_latent_kernel(const float* __restrict
 // sample that is rest_i + mean_j log_p_star_j for the TD gradient, plus var_j(log_p_star_j) in each critic's loss value.
 __global__ __launch_bounds__(1024) void smm_reward_kernel(const float* __restrict__ obs, int64_t ld, const float* __restrict__ hsz,
                                                           const float* __restrict__ hzs, const float* extr, float* reward, int B, int Z,
-                                                          float sec, float lec, float lcec, float gx, float gy, float* __restrict__ metrics, int encoded) {
+                                                          float sec, float lec, float lcec, float gx, float gy, float* __restrict__ metrics, int encoded,
+                                                          int Bg) {
     __shared__ float red[17];
     float e = 0.f, sl = 0.f, s1 = 0.f, s2 = 0.f;
     if (encoded) {                 // pixels: p*(s) is ignored (smm.py:232-235), the reward is a plain (B, 1) column
@@ -697,7 +799,7 @@ __global__ __launch_bounds__(1024) void smm_reward_kernel(const float* __restric
         }
         e = block_sum(e, red); s1 = block_sum(s1, red); s2 = block_sum(s2, red); rs = block_sum(rs, red);
         if (threadIdx.x == 0) {
-            metrics[1] = rs / (float)B; metrics[2] = e / (float)B; metrics[3] = 0.f; metrics[4] = s1 / (float)B; metrics[6] = s2 / (float)B; metrics[7] = 0.f;
+            metrics[1] = rs / (float)Bg; metrics[2] = e / (float)Bg; metrics[3] = 0.f; metrics[4] = s1 / (float)Bg; metrics[6] = s2 / (float)Bg; metrics[7] = 0.f;
         }
         return;
     }
@@ -849,6 +951,11 @@ struct exorl_intr {
     int64_t vae_off = 0;
     float *mu = nullptr, *lv = nullptr, *eps = nullptr, *code = nullptr, *dcode = nullptr, *dmu = nullptr, *dlv = nullptr, *hsz = nullptr, *hzs = nullptr;
     int64_t t = 0;                         // optimiser steps taken
+    // data parallel (cfg.world_size > 1): this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch
+    int world = 1, rank = 0;
+    float* gat = nullptr;                  // ICM-APT / APS: the gathered representation rows (world slots of batch x rep_dim, rank order)
+    double* mom = nullptr;                 // RND / ICM-APT / APS: the gathered RMS moments, (n, mean, M2) per rank
+    int Bg() const { return cfg.batch * world; }
 };
 
 namespace exorl {
@@ -920,7 +1027,7 @@ static void describe_intr(exorl_intr* it) {
 
 static void carve_intr(exorl_intr* it, ICarver& c) {
     const auto& g = it->cfg;
-    const int64_t B = g.batch, O = g.obs_dim, R = g.rep_dim;
+    const int64_t B = g.batch, O = g.obs_dim, R = g.rep_dim, W = g.world_size > 1 ? g.world_size : 1;
     it->flat[EXORL_T_PARAM] = c.take(it->total);
     for (int w = 1; w < 4; ++w) it->flat[w] = c.take(it->trainable);
     for (int n = 0; n < it->n_nets; ++n) {
@@ -934,6 +1041,8 @@ static void carve_intr(exorl_intr* it, ICarver& c) {
     it->fe = c.take(B * (g.kind == EXORL_INTR_DISAGREEMENT ? it->n_nets : 1)); it->be = c.take(B);
     it->metrics = c.take(EXORL_N_INTR_METRICS);
     it->rms = reinterpret_cast<RmsState*>(c.take(4));
+    if (W > 1 && (g.kind == EXORL_INTR_RND || g.kind == EXORL_INTR_ICM_APT || g.kind == EXORL_INTR_APS))
+        it->mom = reinterpret_cast<double*>(c.take(2 * 3 * W));
     if (g.kind == EXORL_INTR_RND) {
         if (!(g.flags & EXORL_INTR_ENCODED)) {     // encoded rows arrive normalised (BatchNorm2d ran on the frames)
             it->xn = c.take(B * O);
@@ -941,7 +1050,8 @@ static void carve_intr(exorl_intr* it, ICarver& c) {
         }
     } else if (g.kind == EXORL_INTR_APS) {
         it->topk = c.take(B * g.knn_k);
-        it->d2 = c.take(B * round_up(B, 64));
+        it->d2 = c.take(B * round_up(B * W, 64));
+        if (W > 1) it->gat = c.take(W * B * R);
     } else if (g.kind == EXORL_INTR_SMM) {
         const int64_t C = SMM_CODE_DIM;
         it->mu = c.take(B * C); it->lv = c.take(B * C); it->eps = c.take(B * C); it->code = c.take(B * C); it->dcode = c.take(B * C);
@@ -967,7 +1077,8 @@ static void carve_intr(exorl_intr* it, ICarver& c) {
             it->x2 = c.take(2 * B * O); it->z = c.take(2 * B * R); it->rep = c.take(2 * B * R); it->xhat = c.take(2 * B * R);
             it->rstd = c.take(2 * B); it->drep = c.take(2 * B * R); it->dz = c.take(2 * B * R);
             it->topk = c.take(B * g.knn_k);
-            it->d2 = c.take(B * round_up(B, 64));
+            it->d2 = c.take(B * round_up(B * W, 64));
+            if (W > 1) it->gat = c.take(W * B * R);
         }
     }
 }
@@ -1001,6 +1112,13 @@ int launch_concat(const float* a, int64_t lda, int ca, const float* b, int64_t l
     return 0;
 }
 
+// ---- staged module steps ------------------------------------------------------------------------------
+// Every module step below is a sequence of stages; a stage ends where the data-parallel step needs an exchange across the ranks and
+// names it in *next (EXORL_INTR_XCHG_*; -1: the step is complete). Stage 0 is the loss's forward and backward pass (train != 0 only) and
+// ends in the gradient exchange; stage 1 steps the optimiser and computes the reward; ICM-APT and APS then gather the representation
+// rows, and the RMS kinds gather their moments. With world_size 1 no stage after 0 names an exchange, and stage 0's (a sum over one
+// rank) is the identity, so exorl_intr_update runs the stages back to back.
+
 // ---- RND -------------------------------------------------------------------------------------------
 static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_target, float* dpred, hipStream_t s) {
     const auto& c = it->cfg;
@@ -1018,29 +1136,46 @@ static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_targ
         if (with_target) EXORL_TRY(mlp_forward_many(it->net, 2, P, it->xn, O, B, c.precision, s));      // predictor and frozen target: same input, same shapes
         else EXORL_TRY(mlp_forward(it->net[0], P, it->xn, O, B, c.precision, s));
     }
-    hipLaunchKernelGGL(rnd_err_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], it->net[1].act[2], it->fe, dpred, B, R);
+    hipLaunchKernelGGL(rnd_err_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], it->net[1].act[2], it->fe, dpred, B, R, it->Bg());
     EXORL_LAUNCH_CHECK();
     return 0;
 }
 
 // train: 0 reward only, 1 step + reward on the same rows, 2 step only (pixels: the reward pass draws a new augmentation and runs the
 // encoder the step has just moved, rnd.py:98-103, so the caller encodes again in between)
-static int rnd_update(exorl_intr* it, const exorl_intr_batch& b, int train, hipStream_t s) {
+static int rnd_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch;
     const bool enc = (c.flags & EXORL_INTR_ENCODED) != 0;
     EXORL_REQUIRE(enc || train != 2, "intr_update: RND's step-only call belongs to the encoded (pixel) variant");
-    if (train) {                                                                                     // rnd.py:79-96
+    *next = -1;
+    if (stage == 0) {                                                                                // rnd.py:79-96
         EXORL_TRY(rnd_forward(it, b, true, it->net[0].dact[2], s));
-        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));
+        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)it->Bg(), it->metrics + EXORL_IM_LOSS, 0, s));
         EXORL_TRY(mlp_backward(it->net[0], it->flat[EXORL_T_PARAM], it->flat[EXORL_T_GRAD], enc ? b.obs : it->xn, enc ? b.obs_ld : (int64_t)c.obs_dim, B,
                                enc ? b.dobs_out : nullptr, c.precision, s));
-        EXORL_TRY(intr_adam(it, s));
-        if (train == 2) return 0;
+        *next = EXORL_INTR_XCHG_GRAD;
+        return 0;
     }
-    // compute_intr_reward (rnd.py:98-103); states: same batch -> same BatchNorm output and frozen target, only the predictor moved
-    EXORL_TRY(rnd_forward(it, b, !train, nullptr, s));
-    hipLaunchKernelGGL(rnd_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, c.scale, it->rms, it->metrics);
+    if (stage == 1) {
+        if (train) {
+            EXORL_TRY(intr_adam(it, s));
+            if (train == 2) return 0;
+        }
+        // compute_intr_reward (rnd.py:98-103); states: same batch -> same BatchNorm output and frozen target, only the predictor moved
+        EXORL_TRY(rnd_forward(it, b, !train, nullptr, s));
+        if (it->world == 1) {
+            hipLaunchKernelGGL(rnd_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, c.scale, it->rms, it->metrics);
+            EXORL_LAUNCH_CHECK();
+            return 0;
+        }
+        hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->fe, B, 1, 0, it->mom + 3 * it->rank);
+        EXORL_LAUNCH_CHECK();
+        *next = EXORL_INTR_XCHG_MOMENTS;
+        return 0;
+    }
+    hipLaunchKernelGGL(rnd_reward_dp_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, it->Bg(), c.scale, it->rms,
+                       (const double*)it->mom, it->world, it->metrics);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
@@ -1051,35 +1186,40 @@ static int icm_errors(exorl_intr* it, const float* tgt, int64_t ldt, const float
     const int D = it->net[0].L[1].out;
     EXORL_REQUIRE(!inverse || lda == c.act_dim, "intr: ICM needs a dense action matrix (ld == action_dim)");
     launch_icm_err(it->net[0].act[1], D, tgt, ldt, inverse ? it->net[1].act[1] : nullptr, action, c.act_dim, it->fe, it->be,
-                   grads ? it->net[0].dact[1] : nullptr, grads ? it->net[1].dact[1] : nullptr, c.batch, 1.0f / (float)c.batch, s);
+                   grads ? it->net[0].dact[1] : nullptr, grads ? it->net[1].dact[1] : nullptr, c.batch, 1.0f / (float)it->Bg(), s);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
 
-static int icm_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s) {
+static int icm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, A = c.act_dim, prec = c.precision;
+    const float invBg = 1.0f / (float)it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
-    EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
-    if (train) {                                                                                     // icm.py:64-84
+    *next = -1;
+    if (stage == 0) {                                                                                // icm.py:64-84
+        EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
         EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.next_obs, b.next_obs_ld, O, it->xb, B, s));
         EXORL_TRY(mlp_forward(it->net[0], P, it->xf, O + A, B, prec, s));
         EXORL_TRY(mlp_forward(it->net[1], P, it->xb, 2 * O, B, prec, s));
         EXORL_TRY(icm_errors(it, b.next_obs, b.next_obs_ld, b.action, b.action_ld, true, true, s));
-        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(launch_mean(it->be, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 1, s));
+        EXORL_TRY(launch_mean(it->fe, B, invBg, it->metrics + EXORL_IM_LOSS, 0, s));
+        EXORL_TRY(launch_mean(it->be, B, invBg, it->metrics + EXORL_IM_LOSS, 1, s));
         EXORL_TRY(mlp_backward(it->net[0], P, G, it->xf, O + A, B, b.dobs_out ? it->dxf : nullptr, prec, s));
         EXORL_TRY(mlp_backward(it->net[1], P, G, it->xb, 2 * O, B, b.dobs_out ? it->dxb : nullptr, prec, s));
         if (b.dobs_out) {                          // obs is an encoding: the caller's encoder continues the backward pass (icm.py:64-78)
             hipLaunchKernelGGL(icm_dobs_kernel, dim3(grid_for((int64_t)B * O)), dim3(256), 0, s, it->dxf, (int64_t)(O + A), it->dxb, (int64_t)(2 * O), b.dobs_out, B, O);
             EXORL_LAUNCH_CHECK();
         }
-        EXORL_TRY(intr_adam(it, s));
+        *next = EXORL_INTR_XCHG_GRAD;
+        return 0;
     }
+    if (train) EXORL_TRY(intr_adam(it, s));
+    else EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
     EXORL_TRY(mlp_forward(it->net[0], P, it->xf, O + A, B, prec, s));                                // icm.py:86-92
     EXORL_TRY(icm_errors(it, b.next_obs, b.next_obs_ld, b.action, b.action_ld, false, false, s));
-    hipLaunchKernelGGL(icm_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, c.scale, it->metrics);
+    hipLaunchKernelGGL(icm_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, c.scale, it->metrics, it->Bg());
     EXORL_LAUNCH_CHECK();
     return 0;
 }
@@ -1092,12 +1232,47 @@ static int apt_trunk(exorl_intr* it, const float* x, int64_t ldx, int rows, hipS
     return ln_tanh_fwd(it->z, P + it->ln_g, P + it->ln_b, it->rep, it->xhat, it->rstd, rows, c.rep_dim, 1, 0, 0, s);
 }
 
-static int apt_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s) {
+// utils.PBE on the representation rows `rep` (batch x rep_dim) of ICM-APT / APS: stage 1 (after the optimiser step and the forward pass that
+// made rep), 2 (the rows gathered: this rank's rows against the global batch) and 3 (the moments gathered)
+static int pbe_stage(exorl_intr* it, const exorl_intr_batch& b, const float* rep, int stage, int* next, hipStream_t s) {
+    const auto& c = it->cfg;
+    const int B = c.batch, R = c.rep_dim;
+    *next = -1;
+    if (stage == 1) {
+        if (it->world == 1) {
+            EXORL_TRY(knn_topk(rep, B, rep, B, R, c.knn_k, it->topk, it->d2, s));
+            hipLaunchKernelGGL(pbe_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, c.knn_k, c.knn_avg, c.knn_rms,
+                               c.knn_clip, it->rms, it->metrics);
+            EXORL_LAUNCH_CHECK();
+            return 0;
+        }
+        EXORL_CHECK_HIP(hipMemcpyAsync(it->gat + (int64_t)it->rank * B * R, rep, sizeof(float) * B * R, hipMemcpyDeviceToDevice, s));
+        *next = EXORL_INTR_XCHG_REP;
+        return 0;
+    }
+    if (stage == 2) {
+        EXORL_TRY(knn_topk(rep, B, it->gat, it->Bg(), R, c.knn_k, it->topk, it->d2, s));
+        if (c.knn_rms) {
+            hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->topk, B, c.knn_k, c.knn_avg, it->mom + 3 * it->rank);
+            EXORL_LAUNCH_CHECK();
+            *next = EXORL_INTR_XCHG_MOMENTS;
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL(pbe_reward_dp_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, it->Bg(), c.knn_k, c.knn_avg,
+                       c.knn_clip, it->rms, c.knn_rms ? (const double*)it->mom : nullptr, it->world, it->metrics);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+static int apt_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, A = c.act_dim, R = c.rep_dim, prec = c.precision;
+    const float invBg = 1.0f / (float)it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
-    if (train) {                                                                                     // icm_apt.py:33-50,86-104
+    *next = -1;
+    if (stage == 0) {                                                                                // icm_apt.py:33-50,86-104
         EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, nullptr, 0, 0, it->x2, B, s));                   // x2 = [obs; next_obs] stacked by rows
         EXORL_TRY(launch_concat(b.next_obs, b.next_obs_ld, O, nullptr, 0, 0, it->x2 + (int64_t)B * O, B, s));
         EXORL_TRY(apt_trunk(it, it->x2, O, 2 * B, s));
@@ -1107,8 +1282,8 @@ static int apt_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hip
         EXORL_TRY(mlp_forward(it->net[0], P, it->xf, R + A, B, prec, s));
         EXORL_TRY(mlp_forward(it->net[1], P, it->xb, 2 * R, B, prec, s));
         EXORL_TRY(icm_errors(it, rn, R, b.action, b.action_ld, true, true, s));
-        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(launch_mean(it->be, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 1, s));
+        EXORL_TRY(launch_mean(it->fe, B, invBg, it->metrics + EXORL_IM_LOSS, 0, s));
+        EXORL_TRY(launch_mean(it->be, B, invBg, it->metrics + EXORL_IM_LOSS, 1, s));
         EXORL_TRY(mlp_backward(it->net[0], P, G, it->xf, R + A, B, it->dxf, prec, s));
         EXORL_TRY(mlp_backward(it->net[1], P, G, it->xb, 2 * R, B, it->dxb, prec, s));
         hipLaunchKernelGGL(apt_drep_kernel, dim3(grid_for((int64_t)B * R)), dim3(256), 0, s, it->dxf, (int64_t)(R + A), it->dxb,
@@ -1123,69 +1298,77 @@ static int apt_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hip
             GemmProblem gx{it->dz, P + it->trunk.W, b.dobs_out, nullptr, B, O, R, R, O, O};
             EXORL_TRY(gemm_grouped(prec, 0, 1, &gx, 1, false, false, s));
         }
-        EXORL_TRY(intr_adam(it, s));
+        *next = EXORL_INTR_XCHG_GRAD;
+        return 0;
     }
-    EXORL_TRY(apt_trunk(it, b.obs, b.obs_ld, B, s));                                                 // icm_apt.py:106-110
-    EXORL_TRY(knn_topk(it->rep, B, it->rep, B, R, c.knn_k, it->topk, it->d2, s));
-    hipLaunchKernelGGL(pbe_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, c.knn_k, c.knn_avg, c.knn_rms,
-                       c.knn_clip, it->rms, it->metrics);
-    EXORL_LAUNCH_CHECK();
-    return 0;
+    if (stage == 1) {
+        if (train) EXORL_TRY(intr_adam(it, s));
+        EXORL_TRY(apt_trunk(it, b.obs, b.obs_ld, B, s));                                             // icm_apt.py:106-110
+    }
+    return pbe_stage(it, b, it->rep, stage, next, s);
 }
 
 // ---- Disagreement ----------------------------------------------------------------------------------
-static int disagreement_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s) {
+static int disagreement_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, A = c.act_dim, prec = c.precision, n = it->n_nets;
+    const float invBg = 1.0f / (float)it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
-    EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
-    if (train) {                                                                                     // disagreement.py:19-33,64-80
+    *next = -1;
+    if (stage == 0) {                                                                                // disagreement.py:19-33,64-80
+        EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
         EXORL_TRY(mlp_forward_many(it->net, n, P, it->xf, O + A, B, prec, s));          // the 5 models' layers share launches
         for (int m = 0; m < n; ++m) {
             launch_icm_err(it->net[m].act[1], O, b.next_obs, b.next_obs_ld, nullptr, nullptr, A, it->fe + (int64_t)m * B, nullptr, it->net[m].dact[1],
-                           nullptr, B, 1.0f / ((float)B * (float)n), s);
+                           nullptr, B, 1.0f / ((float)it->Bg() * (float)n), s);
             EXORL_LAUNCH_CHECK();
         }
         EXORL_TRY(mlp_backward_many(it->net, n, P, G, it->xf, O + A, B, prec, s, b.dobs_out ? it->dxf : nullptr));
         if (b.dobs_out) EXORL_TRY(launch_concat(it->dxf, O + A, O, nullptr, 0, 0, b.dobs_out, B, s));
-        EXORL_TRY(launch_mean(it->fe, B * n, 1.0f / ((float)B * (float)n), it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(intr_adam(it, s));
+        EXORL_TRY(launch_mean(it->fe, B * n, 1.0f / ((float)it->Bg() * (float)n), it->metrics + EXORL_IM_LOSS, 0, s));
+        *next = EXORL_INTR_XCHG_GRAD;
+        return 0;
     }
+    if (train) EXORL_TRY(intr_adam(it, s));
+    else EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
     PredSet ps{};
     EXORL_TRY(mlp_forward_many(it->net, n, P, it->xf, O + A, B, prec, s));                           // disagreement.py:35-47
     for (int m = 0; m < n; ++m) ps.p[m] = it->net[m].act[1];
-    if (b.extr_reward) EXORL_TRY(launch_mean(b.extr_reward, B, 1.0f / (float)B, it->metrics + EXORL_IM_EXTR_REWARD, 0, s));
+    if (b.extr_reward) EXORL_TRY(launch_mean(b.extr_reward, B, invBg, it->metrics + EXORL_IM_EXTR_REWARD, 0, s));
     bool wide = O >= 2048 && O % 4 == 0;
     for (int m = 0; m < n; ++m) wide = wide && reinterpret_cast<uintptr_t>(ps.p[m]) % 16 == 0;
     if (wide) hipLaunchKernelGGL(disagreement_reward_wide_kernel, dim3(B), dim3(256), 0, s, ps, n, b.reward_out, O);
     else hipLaunchKernelGGL(disagreement_reward_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, ps, n, b.reward_out, B, O);
     EXORL_LAUNCH_CHECK();
-    return launch_mean(b.reward_out, B, 1.0f / (float)B, it->metrics + EXORL_IM_INTR_REWARD, 0, s);
+    return launch_mean(b.reward_out, B, invBg, it->metrics + EXORL_IM_INTR_REWARD, 0, s);
 }
 
 // ---- DIAYN -----------------------------------------------------------------------------------------
-static int diayn_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s) {
+static int diayn_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
-    const int B = c.batch, O = c.obs_dim, S = c.rep_dim, prec = c.precision;
+    const int B = c.batch, S = c.rep_dim, prec = c.precision, Bg = it->Bg();
+    const float invBg = 1.0f / (float)Bg;
     const float* P = it->flat[EXORL_T_PARAM];
-    if (train) {                                                                                     // diayn.py:78-92,107-127
+    *next = -1;
+    if (stage == 0) {                                                                                // diayn.py:78-92,107-127
         EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));
         hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, S, it->fe, it->be,
-                           it->net[0].dact[2], (float*)nullptr, c.scale, B);
+                           it->net[0].dact[2], (float*)nullptr, c.scale, B, Bg);
         EXORL_LAUNCH_CHECK();
-        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(launch_mean(it->be, B, 1.0f / (float)B, it->metrics + EXORL_IM_ACC, 0, s));
+        EXORL_TRY(launch_mean(it->fe, B, invBg, it->metrics + EXORL_IM_LOSS, 0, s));
+        EXORL_TRY(launch_mean(it->be, B, invBg, it->metrics + EXORL_IM_ACC, 0, s));
         EXORL_TRY(mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s));   // dobs_out: d/d(next_obs)
-        EXORL_TRY(intr_adam(it, s));
+        *next = EXORL_INTR_XCHG_GRAD;
+        return 0;
     }
+    if (train) EXORL_TRY(intr_adam(it, s));
     EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));                    // diayn.py:94-105
-    if (b.extr_reward) EXORL_TRY(launch_mean(b.extr_reward, B, 1.0f / (float)B, it->metrics + EXORL_IM_EXTR_REWARD, 0, s));
+    if (b.extr_reward) EXORL_TRY(launch_mean(b.extr_reward, B, invBg, it->metrics + EXORL_IM_EXTR_REWARD, 0, s));
     hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, S, (float*)nullptr,
-                       (float*)nullptr, (float*)nullptr, b.reward_out, c.scale, B);
+                       (float*)nullptr, (float*)nullptr, b.reward_out, c.scale, B, Bg);
     EXORL_LAUNCH_CHECK();
-    (void)O;
-    return launch_mean(b.reward_out, B, 1.0f / (float)B, it->metrics + EXORL_IM_INTR_REWARD, 0, s);
+    return launch_mean(b.reward_out, B, invBg, it->metrics + EXORL_IM_INTR_REWARD, 0, s);
 }
 
 // ---- SMM --------------------------------------------------------------------------------------------
@@ -1194,14 +1377,26 @@ static int adam_range(exorl_intr* it, int64_t off, int64_t n, float lr, hipStrea
                      lr, 0.9f, 0.999f, 1e-8f, it->t, nullptr, 0.f, s);
 }
 
-static int smm_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s) {
+// Both optimisers' gradients (vae_opt's and pred_opt's ranges) are ready after stage 0: one exchange, then the two Adam steps. update_pred
+// neither reads the VAE's parameters nor writes its range, so running its passes before vae_opt.step() changes nothing.
+static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
-    const int B = c.batch, O = c.obs_dim, Z = c.rep_dim, W = O + Z, V = SMM_VAE_HIDDEN, C = SMM_CODE_DIM, prec = c.precision;
+    const int B = c.batch, O = c.obs_dim, Z = c.rep_dim, W = O + Z, V = SMM_VAE_HIDDEN, C = SMM_CODE_DIM, prec = c.precision, Bg = it->Bg();
     EXORL_REQUIRE(b.obs_ld >= W, "intr_update: SMM reads [obs | z] rows (obs_ld >= obs_dim + z_dim)");
     EXORL_REQUIRE(train, "intr_update: SMM's reward is defined by the losses of its own update step (smm.py:226-241); train must be set");
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
     Mlp &zp = it->net[0], &enc = it->net[1], &dec = it->net[2];
+    *next = -1;
+    if (stage == 1) {
+        EXORL_TRY(adam_range(it, it->vae_off, it->trainable - it->vae_off, c.vae_lr, s));
+        EXORL_TRY(adam_range(it, 0, it->vae_off, c.sp_lr, s));
+        // ---- reward (smm.py:229-246)
+        hipLaunchKernelGGL(smm_reward_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, it->hsz, it->hzs, b.extr_reward, b.reward_out, B, Z,
+                           c.state_ent_coef, c.latent_ent_coef, c.latent_cond_ent_coef, c.goal_x, c.goal_y, it->metrics, (c.flags & EXORL_INTR_ENCODED) ? 1 : 0, Bg);
+        EXORL_LAUNCH_CHECK();
+        return 0;
+    }
     it->t += 1;
     // ---- update_vae (smm.py:173-185, VAE.loss :61-70) on obs_z
     EXORL_TRY(mlp_forward(enc, P, b.obs, b.obs_ld, B, prec, s));
@@ -1209,19 +1404,19 @@ static int smm_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hip
                          {enc.act[1], P + it->enc_lv.W, it->lv, P + it->enc_lv.b, B, C, V, V, V, C}};
     EXORL_TRY(gemm_grouped(prec, 0, 0, hd, 2, false, false, s));
     hipLaunchKernelGGL(vae_code_kernel, dim3(grid_for((int64_t)B * C)), dim3(256), 0, s, it->mu, it->lv, b.cat_uniform, 0x736d6dull, it->cat_counter++,
-                       it->eps, it->code, (int64_t)B * C);
+                       it->eps, it->code, (int64_t)B * C, (int64_t)it->rank * B * C);
     EXORL_LAUNCH_CHECK();
     EXORL_TRY(mlp_forward(dec, P, it->code, C, B, prec, s));
     if (W >= 2048 && W % 4 == 0 && b.obs_ld % 4 == 0 && reinterpret_cast<uintptr_t>(b.obs) % 16 == 0 && reinterpret_cast<uintptr_t>(dec.act[2]) % 16 == 0 &&
         reinterpret_cast<uintptr_t>(dec.dact[2]) % 16 == 0)
-        hipLaunchKernelGGL(vae_out_wide_kernel, dim3(B), dim3(256), 0, s, b.obs, b.obs_ld, dec.act[2], dec.dact[2], it->hsz, B, W);
-    else hipLaunchKernelGGL(vae_out_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, b.obs, b.obs_ld, dec.act[2], dec.dact[2], it->hsz, B, W);
+        hipLaunchKernelGGL(vae_out_wide_kernel, dim3(B), dim3(256), 0, s, b.obs, b.obs_ld, dec.act[2], dec.dact[2], it->hsz, B, W, Bg);
+    else hipLaunchKernelGGL(vae_out_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, b.obs, b.obs_ld, dec.act[2], dec.dact[2], it->hsz, B, W, Bg);
     EXORL_LAUNCH_CHECK();
     EXORL_TRY(mlp_backward(dec, P, G, it->code, C, B, it->dcode, prec, s));
-    hipLaunchKernelGGL(vae_latent_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->dcode, it->mu, it->lv, it->eps, it->dmu, it->dlv, it->fe, B, C, c.vae_beta);
+    hipLaunchKernelGGL(vae_latent_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->dcode, it->mu, it->lv, it->eps, it->dmu, it->dlv, it->fe, B, C, c.vae_beta, Bg);
     EXORL_LAUNCH_CHECK();
-    EXORL_TRY(launch_mean(it->fe, B, c.vae_beta / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));            // beta * kle
-    EXORL_TRY(launch_mean(it->hsz, B, 1.0f / ((float)B * (float)W), it->metrics + EXORL_IM_LOSS, 1, s));    // + mse.mean()
+    EXORL_TRY(launch_mean(it->fe, B, c.vae_beta / (float)Bg, it->metrics + EXORL_IM_LOSS, 0, s));            // beta * kle
+    EXORL_TRY(launch_mean(it->hsz, B, 1.0f / ((float)Bg * (float)W), it->metrics + EXORL_IM_LOSS, 1, s));    // + mse.mean()
     EXORL_TRY(colsum(it->dmu, G + it->enc_mu.b, B, C, 1, 0, 0, s));
     EXORL_TRY(colsum(it->dlv, G + it->enc_lv.b, B, C, 1, 0, 0, s));
     GemmProblem wg[2] = {{it->dmu, enc.act[1], G + it->enc_mu.W, nullptr, C, V, B, C, V, V}, {it->dlv, enc.act[1], G + it->enc_lv.W, nullptr, C, V, B, C, V, V}};
@@ -1234,42 +1429,53 @@ static int smm_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hip
         hipLaunchKernelGGL(smm_dobs_kernel, dim3(grid_for((int64_t)B * O)), dim3(256), 0, s, it->dxf, dec.dact[2], (int64_t)W, b.dobs_out, B, O);
         EXORL_LAUNCH_CHECK();
     }
-    EXORL_TRY(adam_range(it, it->vae_off, it->trainable - it->vae_off, c.vae_lr, s));
     // ---- update_pred (smm.py:187-200): skill discriminator on the raw observation columns
     EXORL_TRY(mlp_forward(zp, P, b.obs, b.obs_ld, B, prec, s));
-    hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, zp.act[2], b.skill, b.skill_ld, Z, it->hzs, it->be, zp.dact[2], (float*)nullptr, 1.0f, B);
+    hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, zp.act[2], b.skill, b.skill_ld, Z, it->hzs, it->be, zp.dact[2], (float*)nullptr, 1.0f, B, Bg);
     EXORL_LAUNCH_CHECK();
-    EXORL_TRY(launch_mean(it->hzs, B, 1.0f / (float)B, it->metrics + 5, 0, s));
+    EXORL_TRY(launch_mean(it->hzs, B, 1.0f / (float)Bg, it->metrics + 5, 0, s));
     EXORL_TRY(mlp_backward(zp, P, G, b.obs, b.obs_ld, B, nullptr, prec, s));
-    EXORL_TRY(adam_range(it, 0, it->vae_off, c.sp_lr, s));
-    // ---- reward (smm.py:229-246)
-    hipLaunchKernelGGL(smm_reward_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, it->hsz, it->hzs, b.extr_reward, b.reward_out, B, Z,
-                       c.state_ent_coef, c.latent_ent_coef, c.latent_cond_ent_coef, c.goal_x, c.goal_y, it->metrics, (c.flags & EXORL_INTR_ENCODED) ? 1 : 0);
-    EXORL_LAUNCH_CHECK();
+    *next = EXORL_INTR_XCHG_GRAD;
     return 0;
 }
 
 // ---- APS -------------------------------------------------------------------------------------------
-static int aps_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s) {
+static int aps_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
-    const int B = c.batch, D = c.rep_dim, prec = c.precision;
+    const int B = c.batch, D = c.rep_dim, prec = c.precision, Bg = it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
-    if (train) {                                                                                     // aps.py:147-159,170-175
-        EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));
-        hipLaunchKernelGGL(aps_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, it->net[0].dact[2], it->fe, B, D);
-        EXORL_LAUNCH_CHECK();
-        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s));   // dobs_out: d/d(next_obs)
-        EXORL_TRY(intr_adam(it, s));
-    }
-    EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));                    // aps.py:161-168
     const float* rep = it->net[0].act[2];
-    EXORL_TRY(knn_topk(rep, B, rep, B, D, c.knn_k, it->topk, it->d2, s));
-    hipLaunchKernelGGL(pbe_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, c.knn_k, c.knn_avg, c.knn_rms,
-                       c.knn_clip, it->rms, it->metrics);
-    hipLaunchKernelGGL(aps_sf_reward_kernel, dim3(1), dim3(1024), 0, s, rep, b.skill, b.skill_ld, b.reward_out, B, D, it->metrics);
+    *next = -1;
+    if (stage == 0) {                                                                                // aps.py:147-159,170-175
+        EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));
+        hipLaunchKernelGGL(aps_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, it->net[0].dact[2], it->fe, B, D, Bg);
+        EXORL_LAUNCH_CHECK();
+        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)Bg, it->metrics + EXORL_IM_LOSS, 0, s));
+        EXORL_TRY(mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s));   // dobs_out: d/d(next_obs)
+        *next = EXORL_INTR_XCHG_GRAD;
+        return 0;
+    }
+    if (stage == 1) {
+        if (train) EXORL_TRY(intr_adam(it, s));
+        EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));                // aps.py:161-168
+    }
+    EXORL_TRY(pbe_stage(it, b, rep, stage, next, s));
+    if (*next >= 0) return 0;
+    hipLaunchKernelGGL(aps_sf_reward_kernel, dim3(1), dim3(1024), 0, s, rep, b.skill, b.skill_ld, b.reward_out, B, D, it->metrics, Bg);
     EXORL_LAUNCH_CHECK();
     return 0;
+}
+
+static int intr_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+    switch (it->cfg.kind) {
+        case EXORL_INTR_RND: return rnd_stage(it, b, train, stage, next, s);
+        case EXORL_INTR_ICM: return icm_stage(it, b, train, stage, next, s);
+        case EXORL_INTR_ICM_APT: return apt_stage(it, b, train, stage, next, s);
+        case EXORL_INTR_DISAGREEMENT: return disagreement_stage(it, b, train, stage, next, s);
+        case EXORL_INTR_APS: return aps_stage(it, b, train, stage, next, s);
+        case EXORL_INTR_SMM: return smm_stage(it, b, train, stage, next, s);
+        default: return diayn_stage(it, b, train, stage, next, s);
+    }
 }
 
 // ---- Proto ------------------------------------------------------------------------------------------
@@ -1373,8 +1579,16 @@ static int check_intr_cfg(const exorl_intr_cfg* cfg) {
     EXORL_REQUIRE(cfg->kind >= EXORL_INTR_RND && cfg->kind <= EXORL_INTR_SMM, "intr: unknown kind %d", cfg->kind);
     EXORL_REQUIRE(cfg->kind != EXORL_INTR_SMM || (cfg->rep_dim >= 1 && cfg->rep_dim <= 1024 && cfg->obs_dim >= 2 && cfg->sp_lr > 0.f && cfg->vae_lr > 0.f),
                   "intr: SMM needs z_dim in [1, 1024], obs_dim >= 2 (p* reads obs[:, :2]) and positive sp_lr / vae_lr");
-    EXORL_REQUIRE(cfg->kind != EXORL_INTR_APS || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= cfg->batch && cfg->batch <= 4096),
-                  "intr: APS needs 1 <= knn_k <= min(64, batch) and batch <= 4096 (got k=%d B=%d)", cfg->knn_k, cfg->batch);
+    EXORL_REQUIRE(cfg->world_size >= 0 && cfg->rank >= 0 && cfg->rank < (cfg->world_size > 1 ? cfg->world_size : 1),
+                  "intr: world_size=%d / rank=%d out of range (world_size 0 and 1: one rank)", cfg->world_size, cfg->rank);
+    const int world = cfg->world_size > 1 ? cfg->world_size : 1, Bg = cfg->batch * world;     // kNN rows: this rank's against the gathered batch
+    EXORL_REQUIRE(world == 1 || cfg->kind != EXORL_INTR_PROTO, "intr: Proto is single-GPU (world_size=%d): its candidate queue draws from the "
+                  "global batch's softmax and its Sinkhorn runs over the batch", cfg->world_size);
+    EXORL_REQUIRE(world == 1 || (cfg->flags & EXORL_INTR_ENCODED) || (cfg->kind != EXORL_INTR_RND && cfg->kind != EXORL_INTR_SMM),
+                  "intr: RND and SMM on state rows are single-rank modules (BatchNorm1d / mean_j log p*(s_j) over the batch); world_size=%d "
+                  "needs EXORL_INTR_ENCODED", cfg->world_size);
+    EXORL_REQUIRE(cfg->kind != EXORL_INTR_APS || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= Bg && Bg <= 4096),
+                  "intr: APS needs 1 <= knn_k <= min(64, batch * world_size) and batch * world_size <= 4096 (got k=%d B=%d)", cfg->knn_k, Bg);
     EXORL_REQUIRE(cfg->kind != EXORL_INTR_PROTO || (cfg->num_protos >= 1 && cfg->queue_size >= cfg->num_protos && cfg->queue_size % cfg->num_protos == 0 &&
                   cfg->queue_size <= 4096 && cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= cfg->queue_size && cfg->tau > 0.f && cfg->batch <= 8192),
                   "intr: Proto needs num_protos >= 1, queue_size a multiple of num_protos and <= 4096, 1 <= topk <= 64, tau > 0 (got %d, %d, %d, %g)",
@@ -1384,8 +1598,8 @@ static int check_intr_cfg(const exorl_intr_cfg* cfg) {
                   "intr: unsupported dims O=%d A=%d (<=64) H=%d B=%d", cfg->obs_dim, cfg->act_dim, cfg->hidden_dim, cfg->batch);
     EXORL_REQUIRE(cfg->kind == EXORL_INTR_ICM || cfg->kind == EXORL_INTR_DISAGREEMENT || (cfg->rep_dim > 0 && (cfg->kind != EXORL_INTR_ICM_APT || cfg->rep_dim <= 1024)),
                   "intr: rep_dim=%d out of range (ICM-APT trunk: <= 1024)", cfg->rep_dim);
-    EXORL_REQUIRE(cfg->kind != EXORL_INTR_ICM_APT || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= cfg->batch && cfg->batch <= 4096),
-                  "intr: ICM-APT needs 1 <= knn_k <= min(64, batch) and batch <= 4096 (got k=%d B=%d)", cfg->knn_k, cfg->batch);
+    EXORL_REQUIRE(cfg->kind != EXORL_INTR_ICM_APT || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= Bg && Bg <= 4096),
+                  "intr: ICM-APT needs 1 <= knn_k <= min(64, batch * world_size) and batch * world_size <= 4096 (got k=%d B=%d)", cfg->knn_k, Bg);
     EXORL_REQUIRE(cfg->precision >= EXORL_PREC_F32 && cfg->precision <= EXORL_PREC_BF16X6, "intr: unknown precision %d", cfg->precision);
     return 0;
 }
@@ -1408,6 +1622,8 @@ int exorl_intr_create(const exorl_intr_cfg* cfg, void* workspace, size_t workspa
                   "intr_create: workspace of %zu bytes (need %zu, 256-byte aligned)", workspace_bytes, bytes);
     auto* it = new exorl_intr();
     it->cfg = *cfg;
+    it->world = cfg->world_size > 1 ? cfg->world_size : 1;
+    it->rank = cfg->rank;
     describe_intr(it);
     if (workspace) {
         it->ws = static_cast<float*>(workspace);
@@ -1467,7 +1683,7 @@ int exorl_intr_state(exorl_intr_t* it, void** rms_dev, void** bn_dev, int64_t* b
     return 0;
 }
 
-int exorl_intr_update(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train, void* stream) {
+static int check_intr_batch(exorl_intr_t* it, const exorl_intr_batch* b) {
     EXORL_REQUIRE(it && b && b->obs && b->reward_out, "intr_update: null argument");
     const int k = it->cfg.kind;
     EXORL_REQUIRE(k == EXORL_INTR_RND || k == EXORL_INTR_SMM || b->next_obs, "intr_update: this module needs next_obs");
@@ -1475,17 +1691,49 @@ int exorl_intr_update(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train
     EXORL_REQUIRE((k != EXORL_INTR_DIAYN && k != EXORL_INTR_APS && k != EXORL_INTR_SMM) || b->skill, "intr_update: DIAYN / APS / SMM need the skill / task matrix");
     EXORL_REQUIRE(b->obs_ld >= it->cfg.obs_dim && (!b->next_obs || b->next_obs_ld >= it->cfg.obs_dim) && (!b->action || b->action_ld >= it->cfg.act_dim) &&
                   (!b->skill || (k != EXORL_INTR_DIAYN && k != EXORL_INTR_APS && k != EXORL_INTR_SMM) || b->skill_ld >= it->cfg.rep_dim), "intr_update: a leading dimension is smaller than its row width");
+    return 0;
+}
+
+int exorl_intr_update(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train, void* stream) {
+    EXORL_TRY(check_intr_batch(it, b));
+    EXORL_REQUIRE(it->world == 1, "intr_update: world_size=%d: drive exorl_intr_update_phase and run the exchange each phase names "
+                  "(exorl_intr_exchange) across the ranks in between", it->world);
     hipStream_t s = as_stream(stream);
-    switch (k) {
-        case EXORL_INTR_RND: return rnd_update(it, *b, train, s);
-        case EXORL_INTR_ICM: return icm_update(it, *b, train != 0, s);
-        case EXORL_INTR_ICM_APT: return apt_update(it, *b, train != 0, s);
-        case EXORL_INTR_DISAGREEMENT: return disagreement_update(it, *b, train != 0, s);
-        case EXORL_INTR_PROTO: return proto_update(it, *b, train != 0, s, train != 2);
-        case EXORL_INTR_APS: return aps_update(it, *b, train != 0, s);
-        case EXORL_INTR_SMM: return smm_update(it, *b, train != 0, s);
-        default: return diayn_update(it, *b, train != 0, s);
+    if (it->cfg.kind == EXORL_INTR_PROTO) return proto_update(it, *b, train != 0, s, train != 2);
+    int next = -1;
+    for (int stage = train ? 0 : 1;; ++stage) {      // one rank: the gradient exchange is the identity and no later stage names one
+        EXORL_TRY(intr_stage(it, *b, train, stage, &next, s));
+        if (next < 0) return 0;
     }
+}
+
+int exorl_intr_update_phase(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train, int32_t phase, int32_t* next_exchange, void* stream) {
+    EXORL_REQUIRE(next_exchange, "intr_update_phase: null next_exchange");
+    *next_exchange = -1;
+    EXORL_TRY(check_intr_batch(it, b));
+    EXORL_REQUIRE(it->cfg.kind != EXORL_INTR_PROTO, "intr_update_phase: Proto runs as one call (exorl_intr_update, world_size 1)");
+    const int stage = phase + (train ? 0 : 1);
+    EXORL_REQUIRE(phase >= 0 && stage <= 3, "intr_update_phase: phase %d out of range", phase);
+    int next = -1;
+    EXORL_TRY(intr_stage(it, *b, train, stage, &next, as_stream(stream)));
+    *next_exchange = next;
+    return 0;
+}
+
+int exorl_intr_exchange(exorl_intr_t* it, int32_t id, void** ptr_dev, int64_t* count, int32_t* dtype, int32_t* op) {
+    EXORL_REQUIRE(it && ptr_dev && count && dtype && op, "intr_exchange: null argument");
+    if (id == EXORL_INTR_XCHG_GRAD) {
+        *ptr_dev = it->flat[EXORL_T_GRAD]; *count = it->trainable; *dtype = EXORL_XCHG_F32; *op = EXORL_XCHG_SUM;
+    } else if (id == EXORL_INTR_XCHG_REP) {
+        EXORL_REQUIRE(it->gat, "intr_exchange: exchange %d belongs to ICM-APT / APS with world_size > 1", id);
+        *ptr_dev = it->gat; *count = (int64_t)it->cfg.batch * it->cfg.rep_dim; *dtype = EXORL_XCHG_F32; *op = EXORL_XCHG_GATHER;
+    } else if (id == EXORL_INTR_XCHG_MOMENTS) {
+        EXORL_REQUIRE(it->mom, "intr_exchange: exchange %d belongs to RND / ICM-APT / APS with world_size > 1", id);
+        *ptr_dev = it->mom; *count = 3; *dtype = EXORL_XCHG_F64; *op = EXORL_XCHG_GATHER;
+    } else {
+        EXORL_REQUIRE(false, "intr_exchange: unknown exchange %d", id);
+    }
+    return 0;
 }
 
 int exorl_intr_queue(exorl_intr_t* it, void** queue_dev, int64_t* rows, int64_t* cols, int64_t* ptr_inout, int32_t set) {

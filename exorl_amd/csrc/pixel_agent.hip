@@ -473,12 +473,16 @@ int exorl_pixel_agent_encode(exorl_pixel_agent_t* a, int32_t which, int32_t targ
 
 // Backward through the encoder pass last run by exorl_pixel_agent_encode(which, 0) from dfeat_dev (batch, repr_dim; overwritten), then
 // one Adam step of the encoder with optimiser state `opt` (0: encoder_opt, ddpg.py:188-190; 1: the encoder's slots in proto_opt, proto.py:75-78)
-int exorl_pixel_agent_encoder_step(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, void* stream) {
-    EXORL_REQUIRE(a && dfeat_dev && (which == 0 || which == 1) && opt >= 0 && opt <= 2, "pixel_agent_encoder_step: bad arguments");
+// Data parallel: phase 0 is the backward pass (the encoder's gradients, exchange 2 of exorl_pixel_agent_grad_buffer, are this rank's partial
+// sum), phase 1 the optimiser step(s).
+int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, int32_t phase, void* stream) {
+    EXORL_REQUIRE(a && (which == 0 || which == 1) && opt >= 0 && opt <= 2 && (phase == 1 || (phase == 0 && dfeat_dev)),
+                  "pixel_agent_encoder_step: bad arguments");
     hipStream_t s = as_stream(stream);
     const auto& c = a->cfg;
-    EXORL_TRY(exorl_encoder_backward_prec(a->flat[0][0], c.c_in, c.hw, which ? a->aug_n : a->aug_o, c.batch, which ? a->enc_ws_n : a->enc_ws_o, dfeat_dev,
-                                     a->flat[0][1], a->cfg.precision, s));
+    if (phase == 0)
+        return exorl_encoder_backward_prec(a->flat[0][0], c.c_in, c.hw, which ? a->aug_n : a->aug_o, c.batch, which ? a->enc_ws_n : a->enc_ws_o, dfeat_dev,
+                                           a->flat[0][1], a->cfg.precision, s);
     if (opt == 0) { a->t_enc += 1; return padam(a, 0, a->enc_total, nullptr, s); }
     a->t2 += 1;
     EXORL_TRY(adam_step(a->flat[0][0], a->flat[0][1], a->enc_m2, a->enc_v2, a->enc_total, c.lr, 0.9f, 0.999f, 1e-8f, a->t2, nullptr, 0.f, s));
@@ -486,28 +490,63 @@ int exorl_pixel_agent_encoder_step(exorl_pixel_agent_t* a, int32_t which, float*
     return 0;
 }
 
+int exorl_pixel_agent_encoder_step(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, void* stream) {
+    EXORL_REQUIRE(a && dfeat_dev, "pixel_agent_encoder_step: bad arguments");
+    EXORL_REQUIRE(a->world == 1, "pixel_agent_encoder_step: world_size=%d: run exorl_pixel_agent_encoder_step_phase 0, sum-all-reduce "
+                  "exorl_pixel_agent_grad_buffer 2, then phase 1", a->world);
+    EXORL_TRY(exorl_pixel_agent_encoder_step_phase(a, which, dfeat_dev, opt, 0, stream));
+    return exorl_pixel_agent_encoder_step_phase(a, which, dfeat_dev, opt, 1, stream);
+}
+
 // RND on pixels (rnd.py:47-53): x = clamp(BatchNorm2d(RandomShiftsAug(obs))) -> the agent's encoder (*feat_pred_dev, kept for
 // exorl_pixel_agent_encoder_step(0, ...)) and the frozen copy held in the encoder_target slot (*feat_target_dev). shifts_dev: (batch, 2) or null.
-int exorl_pixel_agent_rnd_features(exorl_pixel_agent_t* a, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev, float** feat_target_dev,
-                                   void* stream) {
-    EXORL_REQUIRE(a && feat_pred_dev && feat_target_dev && clip_val > 0.f, "pixel_agent_rnd_features: bad arguments");
+// Data parallel: phases 0 and 1 end in the per-channel double partials of the BatchNorm2d statistics (exorl_pixel_agent_bn_partials), which
+// the ranks sum-all-reduce; the statistics are then over batch * world_size images and the running statistics stay replicated.
+int exorl_pixel_agent_rnd_features_phase(exorl_pixel_agent_t* a, int32_t phase, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev,
+                                         float** feat_target_dev, void* stream) {
+    EXORL_REQUIRE(a && clip_val > 0.f && phase >= 0 && phase <= 2 && (phase < 2 || (feat_pred_dev && feat_target_dev)),
+                  "pixel_agent_rnd_features: bad arguments");
     hipStream_t s = as_stream(stream);
     const auto& c = a->cfg;
     const int64_t hw = (int64_t)c.hw * c.hw, total = (int64_t)c.batch * c.c_in * hw;
-    EXORL_TRY(exorl_aug_shift(a->obs, c.batch, c.c_in, c.hw, 4, shifts_dev, c.seed, (1ull << 62) | a->rnd_aug_counter, a->aug_o, s));
-    a->rnd_aug_counter += 1;
     double *mean = a->bn_scratch, *var = mean + 16, *part = mean + 32;
-    const double count = (double)c.batch * (double)hw;
-    hipLaunchKernelGGL(bn2d_partial_kernel, dim3(c.c_in, BN2_CHUNKS), dim3(256), 0, s, a->aug_o, c.batch, c.c_in, hw, (const double*)nullptr, part);
-    hipLaunchKernelGGL(bn2d_finish_kernel, dim3(1), dim3(16), 0, s, part, mean, var, a->bn2d, c.c_in, count, 0);
-    hipLaunchKernelGGL(bn2d_partial_kernel, dim3(c.c_in, BN2_CHUNKS), dim3(256), 0, s, a->aug_o, c.batch, c.c_in, hw, (const double*)mean, part);
+    const double count = (double)c.batch * (double)a->world * (double)hw;
+    if (phase == 0) {
+        EXORL_TRY(exorl_aug_shift(a->obs, c.batch, c.c_in, c.hw, 4, shifts_dev, c.seed, (1ull << 62) | a->rnd_aug_counter, a->aug_o, s));
+        a->rnd_aug_counter += 1;
+        a->augmented = false;                    // aug_o no longer holds a plain augmentation; aug_n is stale
+        a->have_feat_o = a->have_feat_n = false;
+        hipLaunchKernelGGL(bn2d_partial_kernel, dim3(c.c_in, BN2_CHUNKS), dim3(256), 0, s, a->aug_o, c.batch, c.c_in, hw, (const double*)nullptr, part);
+        EXORL_LAUNCH_CHECK();
+        return 0;
+    }
+    if (phase == 1) {
+        hipLaunchKernelGGL(bn2d_finish_kernel, dim3(1), dim3(16), 0, s, part, mean, var, a->bn2d, c.c_in, count, 0);
+        hipLaunchKernelGGL(bn2d_partial_kernel, dim3(c.c_in, BN2_CHUNKS), dim3(256), 0, s, a->aug_o, c.batch, c.c_in, hw, (const double*)mean, part);
+        EXORL_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(bn2d_finish_kernel, dim3(1), dim3(16), 0, s, part, mean, var, a->bn2d, c.c_in, count, 1);
     hipLaunchKernelGGL(bn2d_apply_kernel, dim3(grid1(total)), dim3(256), 0, s, a->aug_o, c.c_in, hw, total, (const double*)mean, (const double*)var, clip_val);
     EXORL_LAUNCH_CHECK();
-    a->augmented = false;                        // aug_o no longer holds a plain augmentation; aug_n is stale
-    a->have_feat_o = a->have_feat_n = false;
     EXORL_TRY(exorl_encoder_forward_prec(a->flat[0][0], c.c_in, c.hw, a->aug_o, c.batch, a->enc_ws_o, feat_pred_dev, c.precision, stream));
     return exorl_encoder_forward_prec(a->enc_target, c.c_in, c.hw, a->aug_o, c.batch, a->enc_ws_n, feat_target_dev, c.precision, stream);
+}
+
+int exorl_pixel_agent_rnd_features(exorl_pixel_agent_t* a, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev, float** feat_target_dev,
+                                   void* stream) {
+    EXORL_REQUIRE(a && feat_pred_dev && feat_target_dev && clip_val > 0.f, "pixel_agent_rnd_features: bad arguments");
+    EXORL_REQUIRE(a->world == 1, "pixel_agent_rnd_features: world_size=%d: run exorl_pixel_agent_rnd_features_phase 0, 1, 2 and sum-all-reduce "
+                  "exorl_pixel_agent_bn_partials after phases 0 and 1", a->world);
+    for (int phase = 0; phase < 3; ++phase) EXORL_TRY(exorl_pixel_agent_rnd_features_phase(a, phase, shifts_dev, clip_val, feat_pred_dev, feat_target_dev, stream));
+    return 0;
+}
+
+// the BatchNorm2d partial sums the ranks add up between the phases of exorl_pixel_agent_rnd_features_phase: c_in x BN2_CHUNKS doubles
+int exorl_pixel_agent_bn_partials(exorl_pixel_agent_t* a, void** ptr_dev, int64_t* n_doubles) {
+    EXORL_REQUIRE(a && ptr_dev && n_doubles, "pixel_agent_bn_partials: null argument");
+    *ptr_dev = a->bn_scratch + 32; *n_doubles = (int64_t)a->cfg.c_in * BN2_CHUNKS;
+    return 0;
 }
 
 // BatchNorm2d buffers of RND's normalize_obs: running_mean[c_in], running_var[c_in], num_batches_tracked (as float)
@@ -724,8 +763,9 @@ int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t
 
 // exchange 0: critic gradients, then (train_encoder) the encoder's, contiguous; exchange 1: actor gradients
 int exorl_pixel_agent_grad_buffer(exorl_pixel_agent_t* a, int32_t exchange, float** ptr, int64_t* n) {
-    EXORL_REQUIRE(a && ptr && n && (exchange == 0 || exchange == 1), "pixel_agent_grad_buffer: bad arguments (exchange 0 or 1)");
+    EXORL_REQUIRE(a && ptr && n && exchange >= 0 && exchange <= 2, "pixel_agent_grad_buffer: bad arguments (exchange 0, 1 or 2)");
     if (exchange == 0) { *ptr = a->flat[2][1]; *n = a->critic.total + (a->train_encoder ? a->enc_total : 0); }
+    else if (exchange == 2) { *ptr = a->flat[0][1]; *n = a->enc_total; }
     else { *ptr = a->flat[1][1]; *n = a->actor.total; }
     return 0;
 }

@@ -219,13 +219,14 @@ class IntrEngine:
     def __init__(self, kind, obs_dim, act_dim, hidden_dim, batch, rep_dim=0, lr=1e-4, scale=1.0, knn_k=12, knn_avg=True,
                  knn_rms=True, knn_clip=0.0, clip_val=5.0, n_models=0, num_protos=0, queue_size=0, tau=0.1, target_tau=0.05, sp_lr=1e-3, vae_lr=1e-2,
                  vae_beta=0.5, state_ent_coef=1.0, latent_ent_coef=1.0, latent_cond_ent_coef=1.0, goal=(150.0, 75.0), precision='fp32',
-                 device='cuda', encoded=False):
+                 device='cuda', encoded=False, world_size=1, rank=0):
         self.lib = L.load()
         self.device = _require_gpu(device)
         self.kind, self.batch, self.obs_dim, self.act_dim = kind, batch, obs_dim, act_dim
+        self.world_size, self.rank = world_size, rank
         self.cfg = L.IntrCfg(self.KINDS[kind], obs_dim, act_dim, hidden_dim, rep_dim, batch, PRECISION[precision], knn_k, int(bool(knn_avg)),
                              int(bool(knn_rms)), n_models, 1 if encoded else 0, lr, scale, knn_clip, clip_val, num_protos, queue_size, tau, target_tau,
-                             sp_lr, vae_lr, vae_beta, state_ent_coef, latent_ent_coef, latent_cond_ent_coef, goal[0], goal[1])
+                             sp_lr, vae_lr, vae_beta, state_ent_coef, latent_ent_coef, latent_cond_ent_coef, goal[0], goal[1], world_size, rank)
         nbytes = self.lib.exorl_intr_workspace_bytes(C.byref(self.cfg))
         if nbytes == 0:
             raise L.ExorlError(self.lib.exorl_last_error().decode())
@@ -289,12 +290,35 @@ class IntrEngine:
         raw[2:4] = np.array([n], np.float64).view(np.float32)
         self._rms.copy_(torch.from_numpy(raw))
 
-    def update(self, obs, action, next_obs, extr_reward, reward_out, train=True, skill=None, obs_ld=None, action_ld=None,
-               next_obs_ld=None, skill_ld=0, cat_uniform=None, next_obs_target=None, dobs_out=None):
+    def _batch(self, obs, action, next_obs, extr_reward, reward_out, skill=None, obs_ld=None, action_ld=None, next_obs_ld=None, skill_ld=0,
+               cat_uniform=None, next_obs_target=None, dobs_out=None):
+        return L.IntrBatch(obs, obs_ld or self.obs_dim, action, action_ld or self.act_dim, next_obs, next_obs_ld or self.obs_dim,
+                           skill, skill_ld, extr_reward, reward_out, next_obs_target, self.obs_dim, dobs_out, cat_uniform)
+
+    def update(self, obs, action, next_obs, extr_reward, reward_out, train=True, **kw):
         """Device pointers (ints) + row strides in floats; see exorl_intr_batch. train: True/1, False/0, or 2 (optimiser step only)."""
-        b = L.IntrBatch(obs, obs_ld or self.obs_dim, action, action_ld or self.act_dim, next_obs, next_obs_ld or self.obs_dim,
-                        skill, skill_ld, extr_reward, reward_out, next_obs_target, self.obs_dim, dobs_out, cat_uniform)
+        b = self._batch(obs, action, next_obs, extr_reward, reward_out, **kw)
         L.check(self.lib.exorl_intr_update(self.h, C.byref(b), 2 if train == 2 else int(bool(train)), L.current_stream()))
+
+    def update_phase(self, phase, obs, action, next_obs, extr_reward, reward_out, train=True, **kw):
+        """One phase of the data-parallel module step (exorl_intr_update_phase); returns the exchange to run before the next phase
+        (L.INTR_XCHG_*) or -1 when the step is complete."""
+        b = self._batch(obs, action, next_obs, extr_reward, reward_out, **kw)
+        nxt = C.c_int32()
+        L.check(self.lib.exorl_intr_update_phase(self.h, C.byref(b), 2 if train == 2 else int(bool(train)), phase, C.byref(nxt), L.current_stream()))
+        return nxt.value
+
+    def exchange(self, xid):
+        """(device tensor, op) of exchange `xid`: op L.XCHG_SUM -> sum-all-reduce the tensor in place; L.XCHG_GATHER -> the tensor is
+        (world_size, count), rank r's row being its slot, all-gathered in rank order."""
+        p, n, dt, op = C.c_void_p(), C.c_int64(), C.c_int32(), C.c_int32()
+        L.check(self.lib.exorl_intr_exchange(self.h, xid, C.byref(p), C.byref(n), C.byref(dt), C.byref(op)))
+        slots = self.world_size if op.value == L.XCHG_GATHER else 1
+        words = 2 if dt.value == L.XCHG_F64 else 1
+        t = self._view(p.value, slots * n.value * words)
+        if dt.value == L.XCHG_F64:
+            t = t.view(torch.float64)
+        return (t.view(slots, n.value) if op.value == L.XCHG_GATHER else t), op.value
 
     def metrics_raw(self):
         host = np.zeros(L.N_INTR_METRICS, np.float32)
@@ -314,6 +338,29 @@ class IntrEngine:
         c = C.c_uint64(0 if set_to is None else int(set_to))
         L.check(self.lib.exorl_intr_counter(self.h, C.byref(c), 0 if set_to is None else 1))
         return int(c.value)
+
+
+def run_exchange(buf, op, rank, dist=None):
+    """One exchange of a phased call under torch.distributed: sum all-reduce in place, or all-gather of the (world_size, count) slots in
+    rank order (into views of the slots: gloo has no all_gather_into_tensor)."""
+    dist = dist or torch.distributed
+    if op == L.XCHG_SUM:
+        dist.all_reduce(buf)
+    else:
+        slots = list(buf.unbind(0))
+        dist.all_gather(slots, slots[rank].clone())
+
+
+def drive_phases(phase_fn, exchange_fn, rank, dist=None):
+    """Runs phase_fn(0), phase_fn(1), ... to completion: each returns the exchange id to run before the next phase (-1: done), and
+    exchange_fn(id) -> (buffer, op) names its buffer."""
+    phase = 0
+    while True:
+        nxt = phase_fn(phase)
+        if nxt < 0:
+            return
+        run_exchange(*exchange_fn(nxt), rank, dist)
+        phase += 1
 
 
 class PixelEngine:
@@ -435,6 +482,10 @@ class PixelEngine:
     def encoder_step(self, which, dfeat_ptr, opt):
         L.check(self.lib.exorl_pixel_agent_encoder_step(self.h, which, dfeat_ptr, opt, L.current_stream()))
 
+    def encoder_step_phase(self, phase, which, dfeat_ptr, opt):
+        """encoder_step in two phases: 0 the backward pass (then sum-all-reduce grad_buffer(2)), 1 the optimiser step(s)."""
+        L.check(self.lib.exorl_pixel_agent_encoder_step_phase(self.h, which, dfeat_ptr, opt, phase, L.current_stream()))
+
     def encoder_target(self, tau=0.0, init=False):
         L.check(self.lib.exorl_pixel_agent_encoder_target(self.h, tau, int(bool(init)), L.current_stream()))
 
@@ -511,6 +562,21 @@ class PixelEngine:
         L.check(self.lib.exorl_pixel_agent_rnd_features(self.h, L.ptr(sh), clip_val, C.byref(fp), C.byref(ft), L.current_stream()))
         self._keep_r = sh
         return fp.value, ft.value
+
+    def rnd_features_phase(self, phase, shifts=None, clip_val=5.0):
+        """rnd_features in three phases: sum-all-reduce bn_partials() after phases 0 and 1; phase 2 returns the two feature pointers."""
+        fp, ft = C.c_void_p(), C.c_void_p()
+        if phase == 0:
+            self._keep_r = self._i32(shifts)
+        L.check(self.lib.exorl_pixel_agent_rnd_features_phase(self.h, phase, L.ptr(self._keep_r) if phase == 0 else None, clip_val,
+                                                              C.byref(fp), C.byref(ft), L.current_stream()))
+        return (fp.value, ft.value) if phase == 2 else None
+
+    def bn_partials(self):
+        """(c_in * chunks,) float64 device view of the BatchNorm2d partial sums the ranks add up between the rnd_features phases."""
+        p, n = C.c_void_p(), C.c_int64()
+        L.check(self.lib.exorl_pixel_agent_bn_partials(self.h, C.byref(p), C.byref(n)))
+        return self._view(p.value, 2 * n.value).view(torch.float64)
 
     def meta_rows(self):
         """(batch, meta_dim) device view of the skill / task rows the trunks read (filled by the sampler or by the caller)."""

@@ -32,9 +32,11 @@
 extern "C" {
 #endif
 
-#define EXORL_ABI_VERSION 10     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
+#define EXORL_ABI_VERSION 11     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
                                     9: exorl_debug_gemm_stamps and exorl_debug_conv_stamps removed; exorl_gemm_tune keeps five bits
-                                    10: exorl_pixel_cfg.world_size; exorl_pixel_agent_update_phase / _grad_buffer / _set_comm */
+                                    10: exorl_pixel_cfg.world_size; exorl_pixel_agent_update_phase / _grad_buffer / _set_comm
+                                    11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
+                                        _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2 */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -353,6 +355,10 @@ typedef struct exorl_intr_cfg {
     float sp_lr, vae_lr, vae_beta;
     float state_ent_coef, latent_ent_coef, latent_cond_ent_coef;
     float goal_x, goal_y; /* smm.py:139 self.goal = (150, 75): p*(s) is 1/dist of obs[:, :2] to it beyond distance 1 */
+    int32_t world_size;   /* data-parallel ranks (0 and 1: one): every loss mean, loss gradient and metric is over batch * world_size rows
+                             (the gradients and the metrics are then this rank's partial sums / means); not Proto, and RND / SMM only with
+                             EXORL_INTR_ENCODED */
+    int32_t rank;         /* this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch (SMM's epsilon draws) */
 } exorl_intr_cfg;
 
 typedef struct exorl_intr exorl_intr_t;
@@ -414,6 +420,22 @@ typedef struct exorl_intr_batch {
  * diayn.py:143-147); train == 0: compute_intr_reward only; train == 2 (Proto): the optimiser step only — with an encoder in front
  * the reward is computed from features re-encoded after that step (proto.py:173-177). */
 int exorl_intr_update(exorl_intr_t* m, const exorl_intr_batch* batch, int32_t train, void* stream);
+/* The same step in phases, for data parallelism (world_size > 1: exorl_intr_update then refuses; not Proto). Call phase 0, 1, ... with the
+ * same arguments; each returns in *next_exchange the exchange the ranks run before the next phase, or -1 when the step is complete:
+ *   EXORL_INTR_XCHG_GRAD     the module's flat gradients (every kind that trains; SMM's two optimisers share the range): sum all-reduce
+ *   EXORL_INTR_XCHG_REP      ICM-APT / APS: the representation rows the kNN reward reads (ICM-APT: trunk(obs); APS: features of next_obs)
+ *   EXORL_INTR_XCHG_MOMENTS  RND / ICM-APT / APS (knn_rms): each rank's (n, mean, M2) of the RMS input, merged in rank order in double
+ * With world_size 1 the phases back to back are exorl_intr_update bit for bit (only the gradient exchange is named: a sum over one rank). */
+#define EXORL_INTR_XCHG_GRAD    0
+#define EXORL_INTR_XCHG_REP     1
+#define EXORL_INTR_XCHG_MOMENTS 2
+#define EXORL_XCHG_F32    0
+#define EXORL_XCHG_F64    1
+#define EXORL_XCHG_SUM    0      /* sum all-reduce of count elements in place */
+#define EXORL_XCHG_GATHER 1      /* all-gather: rank r's count elements sit at slot r (ptr + r * count) of world_size slots, rank order */
+int exorl_intr_update_phase(exorl_intr_t* m, const exorl_intr_batch* batch, int32_t train, int32_t phase, int32_t* next_exchange, void* stream);
+int exorl_intr_exchange(exorl_intr_t* m, int32_t id, void** ptr_dev, int64_t* count, int32_t* dtype /* EXORL_XCHG_F32 / _F64 */,
+                        int32_t* op /* EXORL_XCHG_SUM / _GATHER */);
 int exorl_intr_metrics(exorl_intr_t* m, float* host_out /* EXORL_N_INTR_METRICS */, void* stream);
 /* optimiser step count of the module's Adam: set == 0 reads into *steps, else writes it (snapshot restore) */
 int exorl_intr_opt_steps(exorl_intr_t* m, int64_t* steps, int32_t set);
@@ -492,7 +514,7 @@ int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t
 int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, float stddev, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev,
                                    const float* noise_critic_dev, const float* noise_actor_dev, void* stream);
 /* The gradients a rank contributes: exchange 0 = the critic's then (set_train_encoder(1)) the encoder's, one contiguous range; exchange 1 = the
- * actor's. *n in floats (padding included: it stays zero). */
+ * actor's; exchange 2 = the encoder's alone (exorl_pixel_agent_encoder_step_phase). *n in floats (padding included: it stays zero). */
 int exorl_pixel_agent_grad_buffer(exorl_pixel_agent_t* a, int32_t exchange, float** ptr_dev, int64_t* n);
 /* Attach a communicator of world_size ranks (NULL detaches): exorl_pixel_agent_update then all-reduces both exchanges between its phases on
  * `stream`. The critic's part of exchange 0 is reduced on a second stream while the encoder's backward pass runs. */
@@ -507,6 +529,10 @@ int exorl_pixel_agent_metrics(exorl_pixel_agent_t* a, float* host_out /* EXORL_N
 int exorl_pixel_agent_augment(exorl_pixel_agent_t* a, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev, void* stream);
 int exorl_pixel_agent_encode(exorl_pixel_agent_t* a, int32_t which, int32_t target, float** feat_out_dev, void* stream);
 int exorl_pixel_agent_encoder_step(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt /* 0 encoder_opt, 1 second state, 2 both */, void* stream);
+/* The same in two phases (world_size > 1: exorl_pixel_agent_encoder_step then refuses): phase 0 the backward pass into exchange 2 of
+ * exorl_pixel_agent_grad_buffer (sum-all-reduce it), phase 1 the optimiser step(s) `opt` chooses (dfeat_dev unused). With world_size 1 the two
+ * phases are exorl_pixel_agent_encoder_step bit for bit. */
+int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, int32_t phase, void* stream);
 int exorl_pixel_agent_encoder_target(exorl_pixel_agent_t* a, float tau, int32_t init, void* stream);
 /* RND on pixels (rnd.py:26-27,35-39,47-53): x = clamp(BatchNorm2d(RandomShiftsAug(obs)), +-clip_val), then the agent's encoder on x
  * (*feat_pred_dev; exorl_pixel_agent_encoder_step(0, dfeat, 2) continues its backward pass and steps the encoder with rnd_opt's state and
@@ -514,6 +540,13 @@ int exorl_pixel_agent_encoder_target(exorl_pixel_agent_t* a, float tau, int32_t 
  * augmentation and updates the BatchNorm running statistics, as RND.forward does. */
 int exorl_pixel_agent_rnd_features(exorl_pixel_agent_t* a, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev, float** feat_target_dev,
                                    void* stream);
+/* The same in three phases (world_size > 1: exorl_pixel_agent_rnd_features then refuses): phase 0 augments and sums the BatchNorm2d inputs,
+ * phase 1 the centred squares, each into the per-channel double partials of exorl_pixel_agent_bn_partials (sum-all-reduce them after each);
+ * phase 2 normalises over batch * world_size images, updates the running statistics and encodes (the feature pointers are read in phase 2
+ * only, shifts_dev in phase 0 only). With world_size 1 the three phases are exorl_pixel_agent_rnd_features bit for bit. */
+int exorl_pixel_agent_rnd_features_phase(exorl_pixel_agent_t* a, int32_t phase, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev,
+                                         float** feat_target_dev, void* stream);
+int exorl_pixel_agent_bn_partials(exorl_pixel_agent_t* a, void** ptr_dev, int64_t* n_doubles);
 int exorl_pixel_agent_bn_state(exorl_pixel_agent_t* a, void** ptr_dev, int64_t* n_floats);   /* running_mean[c] running_var[c] num_batches_tracked */
 int exorl_pixel_agent_encoder_target_ptr(exorl_pixel_agent_t* a, void** ptr_dev);
 /* Whole-agent pickling (pretrain.py:293-300): steps3 = {Adam step count of critic_opt/actor_opt, of proto_opt's encoder state, of encoder_opt},
