@@ -589,11 +589,13 @@ class DDPGAgent(_AgentBase):
         ws = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             ws = torch.distributed.get_world_size()
-        if ws > 1 and reward_free and isinstance(self, ProtoAgent):
-            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU: Proto is the one "
-                                      "pixel agent whose pretraining step does not shard (its candidate queue draws rows from the global batch's "
-                                      "softmax and its Sinkhorn runs over the batch). Under data parallelism the pixel path runs every agent with "
-                                      "reward_free=False (fine-tuning: the DDPG pixel step) and every other agent's pretraining step")
+        if ws > 1 and reward_free and isinstance(self, ProtoAgent) and not getattr(self, 'shard_pretraining', False):
+            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU by default: Proto is the "
+                                      "one pixel agent whose sharded pretraining step is opt-in (its candidate queue draws rows from the global "
+                                      "batch's softmax and its Sinkhorn runs over the batch; every rank gathers the rows and runs both "
+                                      "redundantly). Pass shard_pretraining=True (Hydra: +agent.shard_pretraining=true) to shard it. Under data "
+                                      "parallelism the pixel path runs every agent with reward_free=False (fine-tuning: the DDPG pixel step) and "
+                                      "every other agent's pretraining step")
         if ws > 1:          # every rank draws its own rows of the global batch's shifts and noise (as _AgentBase._build does for states)
             seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF
         self.world_size = ws
@@ -1497,7 +1499,12 @@ class ProtoAgent(_IntrAgent):
     LOSS_KEY = 'repr_loss'
     _PIXELS_OK = True
 
-    def __init__(self, pred_dim, proj_dim, queue_size, num_protos, tau, encoder_target_tau, topk, update_encoder, **kwargs):
+    def __init__(self, pred_dim, proj_dim, queue_size, num_protos, tau, encoder_target_tau, topk, update_encoder, shard_pretraining=False,
+                 **kwargs):
+        # shard_pretraining: under torch.distributed on pixels, run the reward-free module step data-parallel (each rank's rows, the target
+        # and reward rows all-gathered, Sinkhorn and the candidate draw run identically on every rank). Off by default: DDPGAgent._init_pixels
+        # refuses that case without it, so the flag is set before the base constructor runs. No effect on states or at world size 1.
+        self.shard_pretraining = bool(shard_pretraining)
         super().__init__(**kwargs)
         self.tau = tau
         self.encoder_target_tau = encoder_target_tau
@@ -1514,7 +1521,8 @@ class ProtoAgent(_IntrAgent):
             self._dobs = torch.zeros(self.engine.batch, self.obs_dim, device=self.engine.device)
         O = self.obs_dim
         w = _proto_init(O, pred_dim, proj_dim, num_protos)
-        self.intr = IntrEngine('proto', O, self.action_dim, proj_dim, self._module_batch, rep_dim=pred_dim, lr=self.lr, knn_k=topk,
+        dp = self._intr_dp() if self.shard_pretraining and self._pix_dp else dict(batch=self._module_batch)
+        self.intr = IntrEngine('proto', O, self.action_dim, proj_dim, **dp, rep_dim=pred_dim, lr=self.lr, knn_k=topk,
                                num_protos=num_protos, queue_size=queue_size, tau=tau, target_tau=encoder_target_tau,
                                precision=self._precision, device=self.device)
         self.predictor = _TensorsView(self.intr, [0, 1], ['weight', 'bias'])
@@ -1568,11 +1576,13 @@ class ProtoAgent(_IntrAgent):
         if self.reward_free:
             fo = eng.encode(0)
             ft = eng.encode(1, target=True)
-            self.intr.update(fo, None, ft, None, s.reward, 2, next_obs_target=ft, dobs_out=self._dobs.data_ptr())
-            eng.encoder_step(0, self._dobs.data_ptr(), 1)
+            # under torch.distributed (shard_pretraining): the module's phases with their exchanges, and the encoder's share of proto_opt
+            # summed across the ranks; with one process these are the one-call forms
+            self._intr_run(fo, None, ft, None, s.reward, 2, next_obs_target=ft, dobs_out=self._dobs.data_ptr())
+            self._encoder_step(0, self._dobs.data_ptr(), 1)
             fn = eng.encode(1)
             u = self._cat_u()
-            self.intr.update(fo, None, fn, s.reward, s.reward, False, cat_uniform=u.data_ptr() if u is not None else None)
+            self._intr_run(fo, None, fn, s.reward, s.reward, False, cat_uniform=u.data_ptr() if u is not None else None)
             self._keep_u = u
             # proto.py:190-191 encodes obs and next_obs again for the actor / critic: next_obs with the weights and the input of the reward
             # pass above — the same values, kept — and obs with the stepped encoder, the one pass left to make (4 of the update's 20
@@ -1587,7 +1597,7 @@ class ProtoAgent(_IntrAgent):
         if self.use_tb or self.use_wandb:
             metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
             if self.reward_free:
-                ri = self.intr.metrics_raw()
+                ri = self._intr_metrics()
                 metrics['repr_loss'] = float(ri[L.IM_LOSS])
                 metrics['intr_reward'] = float(ri[L.IM_INTR_REWARD])
                 metrics['extr_reward'] = float(ri[L.IM_EXTR_REWARD])

@@ -571,9 +571,9 @@ __global__ __launch_bounds__(256) void sk_row_kernel(float* __restrict__ E, cons
     s = wave_sum(s);
     for (int j = lane; j < P; j += 64) E[(int64_t)row * P + j] = E[(int64_t)row * P + j] * (target / s);
 }
-// loss_b = -sum_p q log_softmax(scores/tau); dscores = (softmax * sum_p q - q) / (B tau). One wave per row.
+// loss_b = -sum_p q log_softmax(scores/tau); dscores = (softmax * sum_p q - q) / (grows tau), grows the global batch's rows. One wave per row.
 __global__ __launch_bounds__(256) void proto_loss_kernel(const float* __restrict__ scores, const float* __restrict__ q, float* __restrict__ dscores,
-                                                         float* __restrict__ loss_row, int rows, int P, float inv_tau) {
+                                                         float* __restrict__ loss_row, int rows, int P, float inv_tau, int grows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     float mx = -INFINITY, qs = 0.f;
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(256) void proto_loss_kernel(const float* __restrict
     for (int j = lane; j < P; j += 64) se += expf(scores[(int64_t)row * P + j] * inv_tau - mx);
     const float lse = mx + logf(wave_sum(se));
     float l = 0.f;
-    const float sc = inv_tau / (float)rows;
+    const float sc = inv_tau / (float)grows;
     for (int j = lane; j < P; j += 64) {
         const float lp = scores[(int64_t)row * P + j] * inv_tau - lse, qq = q[(int64_t)row * P + j];
         l -= qq * lp;
@@ -656,9 +656,105 @@ __global__ __launch_bounds__(256) void proto_candidates_kernel(const float* __re
         for (int j = threadIdx.x; j < D; j += blockDim.x) queue[(qrow0 + p0 + q) * D + j] = z[(int64_t)k * D + j];
     }
 }
-// reward = topk-th smallest distance (proto.py:119-124) + reward bookkeeping; single block
+// Multi-workgroup form of the draw above, for batches whose (B, PC_P + 1) slab does not fit in LDS (B > 3276). The rows fall into
+// chunks of PCM_CHUNK rows and each chunk into 16 blocks of 16 rows; both sizes are constants, so every sum below is associated by B
+// alone, whatever the grid, the rank or the device. Three launches, the kernel boundaries being the only hand-offs:
+//   proto_cand_max : (chunk, 16-prototype group): the chunk's column maxima                                      -> cmax[chunk][p]
+//   proto_cand_sum : (chunk, group): mx_p = max over the chunks (exact in any order); each block's sum of exp(S - mx_p) in double in
+//                    row order, then the 16 block sums in order                                                      -> csum[chunk][p]
+//   proto_cand_pick: (group): a lane per prototype walks the chunk totals in chunk order to the chunk that crosses u * total, the
+//                    workgroup recomputes that chunk's 16 block sums (the same code, so the same values), the lane walks them and then
+//                    the rows of the chosen block; the chosen z rows go into the queue.
+// The probabilities are the LDS kernel's (expf of the same float differences); the sums' association differs from its blocking, so the
+// two forms can pick differently only where u * total lies within double rounding of a CDF boundary.
+constexpr int PCM_CHUNK = 256, PCM_G = 16, PCM_BLK = 16;
+static_assert(PCM_CHUNK == PCM_BLK * (256 / PCM_G), "a 256-thread workgroup covers one chunk of a 16-prototype group");
+__global__ __launch_bounds__(256) void proto_cand_max_kernel(const float* __restrict__ S, int B, int P, float* __restrict__ cmax) {
+    __shared__ float red[256 / PCM_G][PCM_G];
+    const int pl = threadIdx.x % PCM_G, bl = threadIdx.x / PCM_G, p = blockIdx.y * PCM_G + pl, c = blockIdx.x;
+    float m = -INFINITY;
+    if (p < P)
+        for (int i = 0; i < PCM_BLK; ++i) {
+            const int b = c * PCM_CHUNK + bl * PCM_BLK + i;
+            if (b < B) m = fmaxf(m, S[(int64_t)b * P + p]);
+        }
+    red[bl][pl] = m;
+    __syncthreads();
+    if (threadIdx.x < PCM_G && p < P) {
+        for (int i = 1; i < 256 / PCM_G; ++i) m = fmaxf(m, red[i][pl]);
+        cmax[(int64_t)c * P + p] = m;
+    }
+}
+__device__ __forceinline__ float pcm_colmax(const float* __restrict__ cmax, int nch, int P, int p) {
+    float mx = cmax[p];
+    for (int c = 1; c < nch; ++c) mx = fmaxf(mx, cmax[(int64_t)c * P + p]);
+    return mx;
+}
+// sum over the rows [b0, b0 + PCM_BLK) below B of exp(S[b, p] - mx), in double, in row order
+__device__ __forceinline__ double pcm_block_sum(const float* __restrict__ S, int B, int P, int p, int b0, float mx) {
+    double acc = 0.0;
+    for (int i = 0; i < PCM_BLK; ++i) {
+        const int b = b0 + i;
+        if (b < B) acc += (double)expf(S[(int64_t)b * P + p] - mx);
+    }
+    return acc;
+}
+__global__ __launch_bounds__(256) void proto_cand_sum_kernel(const float* __restrict__ S, int B, int P, int nch, const float* __restrict__ cmax,
+                                                             double* __restrict__ csum) {
+    __shared__ double bs[256 / PCM_G][PCM_G];
+    const int pl = threadIdx.x % PCM_G, bl = threadIdx.x / PCM_G, p = blockIdx.y * PCM_G + pl, c = blockIdx.x;
+    if (p < P) bs[bl][pl] = pcm_block_sum(S, B, P, p, c * PCM_CHUNK + bl * PCM_BLK, pcm_colmax(cmax, nch, P, p));
+    __syncthreads();
+    if (threadIdx.x < PCM_G && p < P) {
+        double acc = 0.0;
+        for (int i = 0; i < 256 / PCM_G; ++i) acc += bs[i][pl];
+        csum[(int64_t)c * P + p] = acc;
+    }
+}
+__global__ __launch_bounds__(256) void proto_cand_pick_kernel(const float* __restrict__ S, const float* __restrict__ z, const float* __restrict__ cmax,
+                                                              const double* __restrict__ csum, int nch, const float* __restrict__ u_in, uint64_t seed,
+                                                              uint64_t counter, float* __restrict__ queue, int64_t qrow0, int B, int P, int D) {
+    __shared__ double bs[256 / PCM_G][PCM_G];
+    __shared__ double run_s[PCM_G], thr_s[PCM_G];
+    __shared__ float mx_s[PCM_G];
+    __shared__ int ch_s[PCM_G], pick[PCM_G];
+    const int p0 = blockIdx.x * PCM_G, pl = threadIdx.x % PCM_G, bl = threadIdx.x / PCM_G, p = p0 + pl;
+    if (threadIdx.x < PCM_G && p < P) {
+        double total = 0.0;
+        for (int c = 0; c < nch; ++c) total += csum[(int64_t)c * P + p];
+        float u;
+        if (u_in) u = u_in[p];
+        else { uint32_t c4[4] = {(uint32_t)p, 7u, (uint32_t)counter, (uint32_t)(counter >> 32)}; Philox::gen(c4, seed); u = (float)c4[0] * 2.3283064365386963e-10f; }
+        const double thr = (double)u * total;
+        double run = 0.0;
+        int j = 0;
+        while (j < nch - 1 && !(run + csum[(int64_t)j * P + p] > thr)) { run += csum[(int64_t)j * P + p]; ++j; }
+        run_s[pl] = run; thr_s[pl] = thr; ch_s[pl] = j; mx_s[pl] = pcm_colmax(cmax, nch, P, p);
+    }
+    __syncthreads();
+    if (p < P) bs[bl][pl] = pcm_block_sum(S, B, P, p, ch_s[pl] * PCM_CHUNK + bl * PCM_BLK, mx_s[pl]);
+    __syncthreads();
+    if (threadIdx.x < PCM_G && p < P) {
+        const double thr = thr_s[pl];
+        const float mx = mx_s[pl];
+        double run = run_s[pl];
+        int j = 0;
+        while (j < 256 / PCM_G - 1 && !(run + bs[j][pl] > thr)) { run += bs[j][pl]; ++j; }
+        const int b0 = ch_s[pl] * PCM_CHUNK + j * PCM_BLK, b1 = b0 + PCM_BLK < B ? b0 + PCM_BLK : B;
+        int k = b1 < B - 1 ? b1 : B - 1;          // reached only if rounding keeps the block's own walk at or below thr
+        for (int b = b0; b < b1; ++b) { run += (double)expf(S[(int64_t)b * P + p] - mx); if (run > thr) { k = b; break; } }
+        pick[pl] = k;
+    }
+    __syncthreads();
+    for (int q = 0; q < PCM_G && p0 + q < P; ++q) {
+        const int k = pick[q];
+        for (int j = threadIdx.x; j < D; j += blockDim.x) queue[(qrow0 + p0 + q) * D + j] = z[(int64_t)k * D + j];
+    }
+}
+// reward = topk-th smallest distance (proto.py:119-124) + reward bookkeeping; single block. The metrics are this rank's partial means over
+// the global batch's Bg rows
 __global__ __launch_bounds__(1024) void kth_reward_kernel(const float* __restrict__ topk, const float* extr, float* reward, int B, int k,
-                                                          float* __restrict__ metrics) {
+                                                          float* __restrict__ metrics, int Bg) {
     __shared__ float red[17];
     float e = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
@@ -666,7 +762,7 @@ __global__ __launch_bounds__(1024) void kth_reward_kernel(const float* __restric
     float rs = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) { const float r = topk[(int64_t)i * k + (k - 1)]; reward[i] = r; rs += r; }
     rs = block_sum(rs, red);
-    if (threadIdx.x == 0) { metrics[EXORL_IM_EXTR_REWARD] = e / (float)B; metrics[EXORL_IM_INTR_REWARD] = rs / (float)B; }
+    if (threadIdx.x == 0) { metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg; metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg; }
 }
 
 // ---- APS (aps.py:147-175) ---------------------------------------------------------------------------
@@ -944,6 +1040,8 @@ struct exorl_intr {
     int64_t protos = 0;
     float *z1 = nullptr, *dz1 = nullptr, *sn = nullptr, *nrm = nullptr, *tn = nullptr, *scores_s = nullptr, *scores_t = nullptr,
           *dscores = nullptr, *dsn = nullptr, *colsum_p = nullptr, *scal = nullptr, *queue = nullptr;
+    float* pcm_max = nullptr;              // candidate draw over more rows than the LDS form holds: chunk maxima (float), chunk sums (double)
+    double* pcm_sum = nullptr;
     int64_t queue_ptr = 0;
     uint64_t cat_counter = 0;
     // SMM: net[0] = z_pred_net, net[1] = vae.enc (ReLU after both layers), net[2] = vae.dec; the two heads; sub-range of the vae
@@ -953,7 +1051,7 @@ struct exorl_intr {
     int64_t t = 0;                         // optimiser steps taken
     // data parallel (cfg.world_size > 1): this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch
     int world = 1, rank = 0;
-    float* gat = nullptr;                  // ICM-APT / APS: the gathered representation rows (world slots of batch x rep_dim, rank order)
+    float* gat = nullptr;                  // ICM-APT / APS / Proto: the gathered representation rows (world slots of batch x rep_dim, rank order)
     double* mom = nullptr;                 // RND / ICM-APT / APS: the gathered RMS moments, (n, mean, M2) per rank
     int Bg() const { return cfg.batch * world; }
 };
@@ -965,6 +1063,8 @@ struct ICarver {
     explicit ICarver(float* b) : base(b) {}
     float* take(int64_t n) { float* p = base ? base + off : nullptr; off += round_up(n, 64); return p; }
 };
+
+static bool proto_cand_lds_fits(int64_t rows) { return (size_t)rows * 5 * sizeof(float) <= 64 * 1024; }     // proto_candidates_kernel<4>
 
 static int n_models_of(const exorl_intr_cfg& c) { return c.n_models > 0 ? c.n_models : 5; }     // disagreement.py:12 default
 
@@ -1058,10 +1158,15 @@ static void carve_intr(exorl_intr* it, ICarver& c) {
         it->dmu = c.take(B * C); it->dlv = c.take(B * C); it->hsz = c.take(B); it->hzs = c.take(B);
         it->dxf = c.take(B * (O + R));                           // d/d(obs_z) of the VAE encoder (dobs_out)
     } else if (g.kind == EXORL_INTR_PROTO) {
-        const int64_t P = g.num_protos;
+        const int64_t P = g.num_protos, Bg = B * W;                // Sinkhorn and the candidate draw run over the global batch's rows
         it->z1 = c.take(B * R); it->dz1 = c.take(B * R); it->sn = c.take(B * R); it->nrm = c.take(B); it->tn = c.take(B * R);
-        it->scores_s = c.take(B * P); it->scores_t = c.take(B * P); it->dscores = c.take(B * P); it->dsn = c.take(B * R);
-        it->colsum_p = c.take(P); it->scal = c.take(4); it->skr = c.take(2 * B);
+        it->scores_s = c.take(Bg * P); it->scores_t = c.take(Bg * P); it->dscores = c.take(B * P); it->dsn = c.take(B * R);
+        it->colsum_p = c.take(P); it->scal = c.take(4); it->skr = c.take(2 * Bg);
+        if (W > 1) it->gat = c.take(W * B * R);
+        if (!proto_cand_lds_fits(Bg)) {
+            it->pcm_max = c.take(cdiv(Bg, PCM_CHUNK) * P);
+            it->pcm_sum = reinterpret_cast<double*>(c.take(2 * cdiv(Bg, PCM_CHUNK) * P));
+        }
         if (O >= 4096) it->splitk = c.take(16 * B * R);              // pixel features: split-K scratch of the predictor
         it->queue = c.take((int64_t)g.queue_size * R);
         it->topk = c.take(B * g.knn_k);
@@ -1494,14 +1599,54 @@ static int proto_predict(exorl_intr* it, const float* x, int64_t ldx, const floa
     return gemm_grouped(c.precision, 0, 0, &p, 1, false, false, s);
 }
 
-static int proto_update(exorl_intr* it, const exorl_intr_batch& b, bool train, hipStream_t s, bool want_reward = true) {
+// Categorical(softmax over the rows of scores[:, p]).sample() for every prototype (proto.py:109-112), the chosen rows of z written into
+// the queue at queue_ptr (proto.py:115-117). Every rank draws from the same gathered rows with the same seed and counter, so every
+// rank writes the same queue rows.
+static int proto_candidates(exorl_intr* it, const float* scores, const float* z, const float* u, int rows, hipStream_t s) {
+    const int P = it->cfg.num_protos, D = it->cfg.rep_dim;
+    const uint64_t seed = 0x70726f746full, ctr = it->cat_counter++;
+    if (proto_cand_lds_fits(rows)) {
+#define EXORL_PCAND(PP) hipLaunchKernelGGL(proto_candidates_kernel<PP>, dim3(cdiv(P, PP)), dim3(256), (size_t)rows * (PP + 1) * sizeof(float), s, scores, \
+                                            z, u, seed, ctr, it->queue, it->queue_ptr, rows, P, D, (int*)nullptr)
+        if ((size_t)rows * 17 * sizeof(float) <= 64 * 1024) EXORL_PCAND(16);
+        else if ((size_t)rows * 9 * sizeof(float) <= 64 * 1024) EXORL_PCAND(8);
+        else EXORL_PCAND(4);
+#undef EXORL_PCAND
+    } else {
+        EXORL_REQUIRE(it->pcm_max && it->pcm_sum, "intr: Proto candidate sampling over %d rows without its scratch", rows);
+        const int nch = cdiv(rows, PCM_CHUNK);
+        hipLaunchKernelGGL(proto_cand_max_kernel, dim3(nch, cdiv(P, PCM_G)), dim3(256), 0, s, scores, rows, P, it->pcm_max);
+        hipLaunchKernelGGL(proto_cand_sum_kernel, dim3(nch, cdiv(P, PCM_G)), dim3(256), 0, s, scores, rows, P, nch, it->pcm_max, it->pcm_sum);
+        hipLaunchKernelGGL(proto_cand_pick_kernel, dim3(cdiv(P, PCM_G)), dim3(256), 0, s, scores, z, it->pcm_max, it->pcm_sum, nch, u, seed, ctr,
+                           it->queue, it->queue_ptr, rows, P, D);
+    }
+    EXORL_LAUNCH_CHECK();
+    it->queue_ptr = (it->queue_ptr + P) % it->cfg.queue_size;
+    return 0;
+}
+
+// Proto's step in stages (proto.py:103-157):
+//   0  normalize_protos; the online branch on this rank's rows (scores_s); the target branch's normalised rows, written into this rank's
+//      slot of the gather buffer                                                                      -> EXORL_INTR_XCHG_REP (world > 1)
+//   1  the targets' scores and Sinkhorn-Knopp over all Bg gathered rows (every rank the same, in the same order); loss and dscores of this
+//      rank's rows against its rows of the assignment, as means over Bg; backward into the gradients and dobs_out -> EXORL_INTR_XCHG_GRAD
+//   2  Adam; predictor_target's Polyak step
+//   3  the reward pass: normalize_protos; z = l2norm(predictor(next_obs)) of this rank's rows into its slot -> EXORL_INTR_XCHG_REP (world > 1)
+//   4  scores of all Bg rows; the candidate draw over them (same seed and counter on every rank: the same queue rows, queue_ptr and
+//      counter); kNN of this rank's rows against the queue; the k-th-distance reward; the metrics as partial means over Bg
+// train 2 runs stages 0-2, train 1 stages 0-4, train 0 stages 3-4. A phase runs stages until one names an exchange; with world_size 1
+// only stage 1 names one (a sum over one rank: the identity), so the stages run as before, back to back.
+static bool proto_ends_phase(int stage, int world) { return stage == 1 || (world > 1 && (stage == 0 || stage == 3)); }
+
+static int proto_stage(exorl_intr* it, const exorl_intr_batch& b, int stage, hipStream_t s) {
     const auto& c = it->cfg;
-    const int B = c.batch, O = c.obs_dim, D = c.rep_dim, P = c.num_protos, prec = c.precision;
+    const int B = c.batch, O = c.obs_dim, D = c.rep_dim, P = c.num_protos, prec = c.precision, Bg = it->Bg();
     float* Pm = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
     float* C = Pm + it->protos;
     const float inv_tau = 1.0f / c.tau;
-    if (train) {                                                                                     // proto.py:126-157
+    float* mine = it->world > 1 ? it->gat + (int64_t)it->rank * B * D : nullptr;      // this rank's slot of the gathered rows
+    if (stage == 0) {                                                                                // proto.py:126-157
         EXORL_TRY(launch_l2norm(C, C, nullptr, P, D, s));                                            // normalize_protos
         EXORL_TRY(proto_predict(it, b.obs, b.obs_ld, Pm + it->pred.W, Pm + it->pred.b, it->z1, s));
         EXORL_TRY(mlp_forward(it->net[0], Pm, it->z1, D, B, prec, s));
@@ -1512,22 +1657,26 @@ static int proto_update(exorl_intr* it, const exorl_intr_batch& b, bool train, h
         const float* nt = b.next_obs_target ? b.next_obs_target : b.next_obs;
         const int64_t nt_ld = b.next_obs_target ? b.next_obs_target_ld : b.next_obs_ld;
         EXORL_TRY(proto_predict(it, nt, nt_ld, Pm + it->pred_t.W, Pm + it->pred_t.b, it->tn, s));
-        EXORL_TRY(launch_l2norm(it->tn, it->tn, nullptr, B, D, s));
-        GemmProblem pq{it->tn, C, it->scores_t, nullptr, B, P, D, D, D, P};
+        return launch_l2norm(it->tn, mine ? mine : it->tn, nullptr, B, D, s);
+    }
+    if (stage == 1) {
+        const float* t = it->world > 1 ? it->gat : it->tn;
+        GemmProblem pq{t, C, it->scores_t, nullptr, Bg, P, D, D, D, P};
         EXORL_TRY(gemm_grouped(prec, 0, 0, &pq, 1, false, false, s));
-        hipLaunchKernelGGL(sk_rowmax_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->scores_t, B, P, it->skr);
-        hipLaunchKernelGGL(sk_exp_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->scores_t, it->scores_t, B, P, inv_tau, it->skr);
-        hipLaunchKernelGGL(sk_row_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->scores_t, it->colsum_p, it->skr, B, P, 1, 0.f, 0.f);
+        hipLaunchKernelGGL(sk_rowmax_kernel, dim3(cdiv(Bg, 4)), dim3(256), 0, s, it->scores_t, Bg, P, it->skr);
+        hipLaunchKernelGGL(sk_exp_kernel, dim3(cdiv(Bg, 4)), dim3(256), 0, s, it->scores_t, it->scores_t, Bg, P, inv_tau, it->skr);
+        hipLaunchKernelGGL(sk_row_kernel, dim3(cdiv(Bg, 4)), dim3(256), 0, s, it->scores_t, it->colsum_p, it->skr, Bg, P, 1, 0.f, 0.f);
         EXORL_LAUNCH_CHECK();
         for (int iter = 0; iter < 3; ++iter) {     // u = r / Q.sum(1); Q *= u; Q *= c / Q.sum(0)   (+ the final Q / Q.sum(0) folded into the last pass)
-            EXORL_TRY(colsum(it->scores_t, it->colsum_p, B, P, 1, 0, 0, s));
-            hipLaunchKernelGGL(sk_row_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->scores_t, it->colsum_p, it->skr, B, P, 0, 1.0f / (float)P,
-                               iter == 2 ? 1.0f : 1.0f / (float)B);
+            EXORL_TRY(colsum(it->scores_t, it->colsum_p, Bg, P, 1, 0, 0, s));
+            hipLaunchKernelGGL(sk_row_kernel, dim3(cdiv(Bg, 4)), dim3(256), 0, s, it->scores_t, it->colsum_p, it->skr, Bg, P, 0, 1.0f / (float)P,
+                               iter == 2 ? 1.0f : 1.0f / (float)Bg);
             EXORL_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(proto_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->scores_s, it->scores_t, it->dscores, it->fe, B, P, inv_tau);
+        hipLaunchKernelGGL(proto_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->scores_s, it->scores_t + (int64_t)it->rank * B * P, it->dscores,
+                           it->fe, B, P, inv_tau, Bg);
         EXORL_LAUNCH_CHECK();
-        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)B, it->metrics + EXORL_IM_LOSS, 0, s));
+        EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)Bg, it->metrics + EXORL_IM_LOSS, 0, s));
         GemmProblem gc{it->dscores, it->sn, G + it->protos, nullptr, P, D, B, P, D, D};              // dC = dscores^T sn
         EXORL_TRY(gemm_grouped(prec, 1, 1, &gc, 1, false, false, s));
         GemmProblem gs{it->dscores, C, it->dsn, nullptr, B, D, P, P, D, D};                          // dsn = dscores C
@@ -1542,31 +1691,45 @@ static int proto_update(exorl_intr* it, const exorl_intr_batch& b, bool train, h
             GemmProblem gx{it->dz1, Pm + it->pred.W, b.dobs_out, nullptr, B, O, D, D, O, O};
             EXORL_TRY(gemm_grouped(prec, 0, 1, &gx, 1, false, false, s));
         }
+        return 0;
+    }
+    if (stage == 2) {
         EXORL_TRY(intr_adam(it, s));
         // utils.soft_update_params(predictor, predictor_target, encoder_target_tau) (proto.py:202-203): nothing reads the target before the next update
-        EXORL_TRY(soft_update(Pm + it->pred.W, Pm + it->pred_t.W, it->pred_t.b + round_up(c.rep_dim, 4) - it->pred_t.W, c.target_tau, s));
+        return soft_update(Pm + it->pred.W, Pm + it->pred_t.W, it->pred_t.b + round_up(c.rep_dim, 4) - it->pred_t.W, c.target_tau, s);
     }
-    if (!want_reward) return 0;
-    // compute_intr_reward(next_obs) (proto.py:103-124)
-    EXORL_TRY(launch_l2norm(C, C, nullptr, P, D, s));
-    EXORL_TRY(proto_predict(it, b.next_obs, b.next_obs_ld, Pm + it->pred.W, Pm + it->pred.b, it->sn, s));
-    EXORL_TRY(launch_l2norm(it->sn, it->sn, nullptr, B, D, s));
-    GemmProblem pc{it->sn, C, it->scores_s, nullptr, B, P, D, D, D, P};
+    if (stage == 3) {                                                                                // compute_intr_reward(next_obs) (proto.py:103-124)
+        EXORL_TRY(launch_l2norm(C, C, nullptr, P, D, s));
+        EXORL_TRY(proto_predict(it, b.next_obs, b.next_obs_ld, Pm + it->pred.W, Pm + it->pred.b, it->sn, s));
+        return launch_l2norm(it->sn, mine ? mine : it->sn, nullptr, B, D, s);
+    }
+    const float* z = it->world > 1 ? it->gat : it->sn;
+    GemmProblem pc{z, C, it->scores_s, nullptr, Bg, P, D, D, D, P};
     EXORL_TRY(gemm_grouped(prec, 0, 0, &pc, 1, false, false, s));
-#define EXORL_PCAND(PP) hipLaunchKernelGGL(proto_candidates_kernel<PP>, dim3(cdiv(P, PP)), dim3(256), (size_t)B * (PP + 1) * sizeof(float), s, it->scores_s, \
-                                            it->sn, b.cat_uniform, 0x70726f746full, it->cat_counter++, it->queue, it->queue_ptr, B, P, D, (int*)nullptr)
-    if ((size_t)B * 17 * sizeof(float) <= 64 * 1024) EXORL_PCAND(16);
-    else if ((size_t)B * 9 * sizeof(float) <= 64 * 1024) EXORL_PCAND(8);
-    else {
-        EXORL_REQUIRE((size_t)B * 5 * sizeof(float) <= 64 * 1024, "intr: Proto candidate sampling supports batch <= 3276 (got %d)", B);
-        EXORL_PCAND(4);
+    EXORL_TRY(proto_candidates(it, it->scores_s, z, b.cat_uniform, Bg, s));
+    EXORL_TRY(knn_topk(mine ? mine : it->sn, B, it->queue, c.queue_size, D, c.knn_k, it->topk, it->d2, s));
+    hipLaunchKernelGGL(kth_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, c.knn_k, it->metrics, Bg);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+// one phase of the staged step: the stages of the phases before it are skipped, then stages run until one names an exchange
+static int proto_phase(exorl_intr* it, const exorl_intr_batch& b, int train, int phase, int* next, hipStream_t s) {
+    const int last = train == 2 ? 2 : 4;
+    int stage = train ? 0 : 3;
+    for (int p = 0; p < phase && stage <= last; ++p) {
+        while (stage < last && !proto_ends_phase(stage, it->world)) ++stage;
+        ++stage;
     }
-#undef EXORL_PCAND
-    EXORL_LAUNCH_CHECK();
-    it->queue_ptr = (it->queue_ptr + P) % c.queue_size;
-    EXORL_TRY(knn_topk(it->sn, B, it->queue, c.queue_size, D, c.knn_k, it->topk, it->d2, s));
-    hipLaunchKernelGGL(kth_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, c.knn_k, it->metrics);
-    EXORL_LAUNCH_CHECK();
+    EXORL_REQUIRE(phase >= 0 && stage <= last, "intr_update_phase: phase %d out of range", phase);
+    *next = -1;
+    for (; stage <= last; ++stage) {
+        EXORL_TRY(proto_stage(it, b, stage, s));
+        if (proto_ends_phase(stage, it->world)) {
+            *next = stage == 1 ? EXORL_INTR_XCHG_GRAD : EXORL_INTR_XCHG_REP;
+            return 0;
+        }
+    }
     return 0;
 }
 
@@ -1582,8 +1745,8 @@ static int check_intr_cfg(const exorl_intr_cfg* cfg) {
     EXORL_REQUIRE(cfg->world_size >= 0 && cfg->rank >= 0 && cfg->rank < (cfg->world_size > 1 ? cfg->world_size : 1),
                   "intr: world_size=%d / rank=%d out of range (world_size 0 and 1: one rank)", cfg->world_size, cfg->rank);
     const int world = cfg->world_size > 1 ? cfg->world_size : 1, Bg = cfg->batch * world;     // kNN rows: this rank's against the gathered batch
-    EXORL_REQUIRE(world == 1 || cfg->kind != EXORL_INTR_PROTO, "intr: Proto is single-GPU (world_size=%d): its candidate queue draws from the "
-                  "global batch's softmax and its Sinkhorn runs over the batch", cfg->world_size);
+    EXORL_REQUIRE(cfg->kind != EXORL_INTR_PROTO || (int64_t)cfg->batch * world <= 8192, "intr: Proto supports batch * world_size <= 8192 (its "
+                  "Sinkhorn and candidate draw run over the global batch; got %d x %d)", cfg->batch, world);
     EXORL_REQUIRE(world == 1 || (cfg->flags & EXORL_INTR_ENCODED) || (cfg->kind != EXORL_INTR_RND && cfg->kind != EXORL_INTR_SMM),
                   "intr: RND and SMM on state rows are single-rank modules (BatchNorm1d / mean_j log p*(s_j) over the batch); world_size=%d "
                   "needs EXORL_INTR_ENCODED", cfg->world_size);
@@ -1699,8 +1862,13 @@ int exorl_intr_update(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train
     EXORL_REQUIRE(it->world == 1, "intr_update: world_size=%d: drive exorl_intr_update_phase and run the exchange each phase names "
                   "(exorl_intr_exchange) across the ranks in between", it->world);
     hipStream_t s = as_stream(stream);
-    if (it->cfg.kind == EXORL_INTR_PROTO) return proto_update(it, *b, train != 0, s, train != 2);
     int next = -1;
+    if (it->cfg.kind == EXORL_INTR_PROTO) {           // one rank: the gradient exchange after stage 1 is the identity
+        for (int phase = 0;; ++phase) {
+            EXORL_TRY(proto_phase(it, *b, train, phase, &next, s));
+            if (next < 0) return 0;
+        }
+    }
     for (int stage = train ? 0 : 1;; ++stage) {      // one rank: the gradient exchange is the identity and no later stage names one
         EXORL_TRY(intr_stage(it, *b, train, stage, &next, s));
         if (next < 0) return 0;
@@ -1711,10 +1879,14 @@ int exorl_intr_update_phase(exorl_intr_t* it, const exorl_intr_batch* b, int32_t
     EXORL_REQUIRE(next_exchange, "intr_update_phase: null next_exchange");
     *next_exchange = -1;
     EXORL_TRY(check_intr_batch(it, b));
-    EXORL_REQUIRE(it->cfg.kind != EXORL_INTR_PROTO, "intr_update_phase: Proto runs as one call (exorl_intr_update, world_size 1)");
+    int next = -1;
+    if (it->cfg.kind == EXORL_INTR_PROTO) {
+        EXORL_TRY(proto_phase(it, *b, train, phase, &next, as_stream(stream)));
+        *next_exchange = next;
+        return 0;
+    }
     const int stage = phase + (train ? 0 : 1);
     EXORL_REQUIRE(phase >= 0 && stage <= 3, "intr_update_phase: phase %d out of range", phase);
-    int next = -1;
     EXORL_TRY(intr_stage(it, *b, train, stage, &next, as_stream(stream)));
     *next_exchange = next;
     return 0;
@@ -1725,7 +1897,7 @@ int exorl_intr_exchange(exorl_intr_t* it, int32_t id, void** ptr_dev, int64_t* c
     if (id == EXORL_INTR_XCHG_GRAD) {
         *ptr_dev = it->flat[EXORL_T_GRAD]; *count = it->trainable; *dtype = EXORL_XCHG_F32; *op = EXORL_XCHG_SUM;
     } else if (id == EXORL_INTR_XCHG_REP) {
-        EXORL_REQUIRE(it->gat, "intr_exchange: exchange %d belongs to ICM-APT / APS with world_size > 1", id);
+        EXORL_REQUIRE(it->gat, "intr_exchange: exchange %d belongs to ICM-APT / APS / Proto with world_size > 1", id);
         *ptr_dev = it->gat; *count = (int64_t)it->cfg.batch * it->cfg.rep_dim; *dtype = EXORL_XCHG_F32; *op = EXORL_XCHG_GATHER;
     } else if (id == EXORL_INTR_XCHG_MOMENTS) {
         EXORL_REQUIRE(it->mom, "intr_exchange: exchange %d belongs to RND / ICM-APT / APS with world_size > 1", id);

@@ -356,8 +356,9 @@ typedef struct exorl_intr_cfg {
     float state_ent_coef, latent_ent_coef, latent_cond_ent_coef;
     float goal_x, goal_y; /* smm.py:139 self.goal = (150, 75): p*(s) is 1/dist of obs[:, :2] to it beyond distance 1 */
     int32_t world_size;   /* data-parallel ranks (0 and 1: one): every loss mean, loss gradient and metric is over batch * world_size rows
-                             (the gradients and the metrics are then this rank's partial sums / means); not Proto, and RND / SMM only with
-                             EXORL_INTR_ENCODED */
+                             (the gradients and the metrics are then this rank's partial sums / means); RND / SMM only with
+                             EXORL_INTR_ENCODED; Proto with batch * world_size <= 8192 (its Sinkhorn and candidate draw run over the
+                             gathered global batch, redundantly and identically on every rank) */
     int32_t rank;         /* this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch (SMM's epsilon draws) */
 } exorl_intr_cfg;
 
@@ -420,10 +421,12 @@ typedef struct exorl_intr_batch {
  * diayn.py:143-147); train == 0: compute_intr_reward only; train == 2 (Proto): the optimiser step only — with an encoder in front
  * the reward is computed from features re-encoded after that step (proto.py:173-177). */
 int exorl_intr_update(exorl_intr_t* m, const exorl_intr_batch* batch, int32_t train, void* stream);
-/* The same step in phases, for data parallelism (world_size > 1: exorl_intr_update then refuses; not Proto). Call phase 0, 1, ... with the
+/* The same step in phases, for data parallelism (world_size > 1: exorl_intr_update then refuses). Call phase 0, 1, ... with the
  * same arguments; each returns in *next_exchange the exchange the ranks run before the next phase, or -1 when the step is complete:
  *   EXORL_INTR_XCHG_GRAD     the module's flat gradients (every kind that trains; SMM's two optimisers share the range): sum all-reduce
- *   EXORL_INTR_XCHG_REP      ICM-APT / APS: the representation rows the kNN reward reads (ICM-APT: trunk(obs); APS: features of next_obs)
+ *   EXORL_INTR_XCHG_REP      ICM-APT / APS: the representation rows the kNN reward reads (ICM-APT: trunk(obs); APS: features of next_obs);
+ *                            Proto: l2norm(predictor_target(next_obs_target)) for the Sinkhorn assignment (the step) and
+ *                            l2norm(predictor(next_obs)) for the candidate draw (the reward), batch x pred_dim per rank
  *   EXORL_INTR_XCHG_MOMENTS  RND / ICM-APT / APS (knn_rms): each rank's (n, mean, M2) of the RMS input, merged in rank order in double
  * With world_size 1 the phases back to back are exorl_intr_update bit for bit (only the gradient exchange is named: a sum over one rank). */
 #define EXORL_INTR_XCHG_GRAD    0
