@@ -24,7 +24,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import utils
-from .engine import AgentEngine, IntrEngine, PixelEngine, drive_phases
+from .comm import all_ranks, native_comm
+from .engine import AgentEngine, IntrEngine, PixelEngine, global_means
 
 _OFFLINE_ACTOR_KEYS = ['policy.0.weight', 'policy.0.bias', 'policy.1.weight', 'policy.1.bias',
                        'policy.3.weight', 'policy.3.bias', 'policy.5.weight', 'policy.5.bias']
@@ -214,7 +215,6 @@ class _AgentBase:
         self.engine.params_changed(sync_target=True)                   # critic_target.load_state_dict(critic.state_dict())
         self.engine.set_metrics(bool(getattr(self, 'use_tb', False) or getattr(self, 'use_wandb', False)))
         if ws > 1:
-            from .comm import native_comm
             comm = native_comm(self.engine.device)          # RCCL inside the library when torch.distributed runs on nccl
             if comm is not None:
                 self.engine.set_comm(comm)
@@ -257,13 +257,10 @@ class _AgentBase:
             if self.world_size == 1:
                 raise
             ok = False
-        if self.world_size != 1:                 # a capture refused on one rank must send EVERY rank down the eager path
-            flag = torch.tensor([1.0 if ok else 0.0], device=self.engine.device)
-            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
-            if float(flag[0]) == 0.0:
-                if ok:
-                    self.engine.disable_graph()
-                return False
+        if self.world_size != 1 and not all_ranks(ok, self.engine.device):      # a capture refused on one rank sends EVERY rank down the eager path
+            if ok:
+                self.engine.disable_graph()
+            return False
         self._graph_iter = replay_iter
         return True
 
@@ -294,33 +291,16 @@ class _AgentBase:
         return self.noise_hook((rows or self.engine.batch, self.action_dim))
 
     def _run_update(self, stddev):
-        """One gradient step; under torch.distributed the three global quantities are sum-all-reduced."""
-        eng = self.engine
+        """One gradient step on the loaded batch."""
         if self.KIND == 'bc':
             nc = na = None
         else:
             # reference draw order: critic target, then actor (SURVEY A9); CRR's second draw is (B*n, A) (crr.py:125)
             nc, na = self._noise(), self._noise(getattr(self, '_second_noise_rows', None))
-        if self.world_size == 1 or eng.comm is not None:      # one host call: with a communicator the library all-reduces between its phases
-            eng.update(stddev, nc, na)
-            return
-        dist = torch.distributed                              # gloo / EXORL_DP_COMM=torch: the collectives stay here
-        eng.update_phase(0, stddev, nc, na)
-        if eng.has_critic:
-            dist.all_reduce(eng.flat(L.NET_CRITIC, L.T_GRAD))
-        eng.update_phase(1, stddev, nc, na)
-        if self.KIND == 'td3_bc':                    # only TD3+BC's lambda needs a batch-global statistic
-            dist.all_reduce(eng.stats())
-        eng.update_phase(2, stddev, nc, na)
-        dist.all_reduce(eng.flat(L.NET_ACTOR, L.T_GRAD))
-        eng.update_phase(3, stddev, nc, na)
+        self.engine.run_update(stddev, nc, na)
 
     def _metrics(self, keys, stddev):
-        raw = self.engine.metrics_raw()
-        if self.world_size > 1:                          # partial means -> global means
-            t = torch.from_numpy(raw.copy()).to(self.engine.device)
-            torch.distributed.all_reduce(t)
-            raw = t.cpu().numpy()
+        raw = global_means(self.engine)
         m = {}
         for idx, name in keys:
             m[name] = float(raw[idx])
@@ -472,33 +452,13 @@ class CQLAgent(_AgentBase):
             z_cur, z_nxt = self.noise_hook((n, B, A)), self.noise_hook((n, B, A))
             nc = np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in (z_next, u_rand, z_cur, z_nxt)])
             na = np.asarray(self.noise_hook((B, A)), np.float32)
-        eng = self.engine
-        if self.world_size == 1 or eng.comm is not None:
-            eng.update(1.0, nc, na)
-            return
-        dist = torch.distributed
-        if self.use_critic_lagrange:              # the multiplier steps on the GLOBAL penalty before any critic gradient is formed (cql.py:199-213)
-            eng.update_phase(4, 1.0, nc, na)
-            dist.all_reduce(eng.stats())          # this rank's sum of logsumexp and of Q1 + Q2
-            eng.update_phase(5, 1.0, nc, na)
-        else:
-            eng.update_phase(0, 1.0, nc, na)
-        dist.all_reduce(eng.flat(L.NET_CRITIC, L.T_GRAD))
-        eng.update_phase(1, 1.0, nc, na)
-        dist.all_reduce(eng.stats())              # sum of log_pi for the entropy temperature (cql.py:242-243)
-        eng.update_phase(2, 1.0, nc, na)
-        dist.all_reduce(eng.flat(L.NET_ACTOR, L.T_GRAD))
-        eng.update_phase(3, 1.0, nc, na)
+        self.engine.run_update(1.0, nc, na)
 
     def update(self, replay_iter, step):
         metrics = dict()
         self._step(replay_iter, 1.0)
         if self.use_tb:
-            raw = self.engine.metrics_raw()
-            if self.world_size > 1:
-                t = torch.from_numpy(raw.copy()).to(self.engine.device)
-                torch.distributed.all_reduce(t)
-                raw = t.cpu().numpy()
+            raw = global_means(self.engine)
             for idx, name in _CRITIC_METRICS + [(L.M_CRITIC_CQL, 'critic_cql'), (L.M_CRITIC_CQL_LOGSUM, 'critic_cql_logsum'),
                                                 (L.M_ACTOR_ENT, 'actor_ent'), (L.M_ACTOR_ALPHA, 'actor_alpha'),
                                                 (L.M_ACTOR_ALPHA_LOSS, 'actor_alpha_loss')]:
@@ -606,7 +566,6 @@ class DDPGAgent(_AgentBase):
                                   stddev_clip=stddev_clip, precision=precision, seed=seed, device=device, meta_dim=meta_dim, sf_dim=sf_dim,
                                   world_size=ws)
         if ws > 1:
-            from .comm import native_comm
             comm = native_comm(self.engine.device)          # RCCL inside the library when torch.distributed runs on nccl
             if comm is not None:
                 self.engine.set_comm(comm)
@@ -641,25 +600,11 @@ class DDPGAgent(_AgentBase):
         sn = self.shift_hook(B) if self.shift_hook else None
         nc = self.noise_hook((B, A)) if self.noise_hook else None
         na = self.noise_hook((B, A)) if self.noise_hook else None
-        self._pix_step(stddev, so, sn, nc, na)
+        eng.run_update(stddev, so, sn, nc, na)
         metrics = dict()
         if self.use_tb or self.use_wandb:
             metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
         return metrics
-
-    def _pix_step(self, stddev, so=None, sn=None, nc=None, na=None, keep_augmented=False, keep_encoded=False):
-        """The DDPG pixel step. Under torch.distributed each rank runs it on its rows and the gradients are sum-all-reduced between the
-        phases (every mean in it is over the global batch): exchange 0 = critic (+ encoder) gradients, exchange 1 = actor gradients."""
-        eng = self.engine
-        if self.world_size == 1 or eng.comm is not None:      # one host call: with a communicator the library all-reduces between its phases
-            eng.update(stddev, so, sn, nc, na, keep_augmented=keep_augmented, keep_encoded=keep_encoded)
-            return
-        dist = torch.distributed                              # gloo / EXORL_DP_COMM=torch: the collectives stay here
-        eng.update_phase(0, stddev, so, sn, nc, None, keep_augmented=keep_augmented, keep_encoded=keep_encoded)
-        dist.all_reduce(eng.grad_buffer(0))
-        eng.update_phase(1, stddev, noise_actor=na)
-        dist.all_reduce(eng.grad_buffer(1))
-        eng.update_phase(2, stddev)
 
     def train(self, training=True):
         if getattr(self, 'obs_type', 'states') == 'pixels':
@@ -848,40 +793,16 @@ class _IntrAgent(DDPGAgent):
     # Under torch.distributed every rank runs the module step, the encoder step and BatchNorm2d on its own rows: each loss is a mean over
     # the global batch, so the gradients are partial sums the ranks add up (one exchange each), and the batch-global quantities — RND's
     # BatchNorm2d statistics, the running RMS's batch moments, the kNN targets of ICM-APT and APS — are small exchanges of their own.
-    @property
-    def _pix_dp(self):
-        return getattr(self, 'obs_type', 'states') == 'pixels' and self.world_size > 1
-
-    def _intr_run(self, *a, **k):
-        """self.intr.update, or its phases with the exchanges each one names run over torch.distributed."""
-        if not self._pix_dp:
-            return self.intr.update(*a, **k)
-        drive_phases(lambda ph: self.intr.update_phase(ph, *a, **k), self.intr.exchange, self.intr.rank)
-
-    def _encoder_step(self, which, dfeat_ptr, opt):
-        eng = self.engine
-        if not self._pix_dp:
-            return eng.encoder_step(which, dfeat_ptr, opt)
-        eng.encoder_step_phase(0, which, dfeat_ptr, opt)
-        torch.distributed.all_reduce(eng.grad_buffer(2))
-        eng.encoder_step_phase(1, which, dfeat_ptr, opt)
-
+    # The engines' run_* calls (engine.py) take the phased forms in that case.
     def _intr_metrics(self):
-        """The module's metrics as global means: its partial means summed over the ranks; the RMS state (slots 3, 4 of RND, ICM-APT and
-        APS) is the same on every rank and is not summed."""
-        raw = self.intr.metrics_raw()
-        if not self._pix_dp:
-            return raw
-        t = torch.from_numpy(raw.copy()).to(self.engine.device)
-        torch.distributed.all_reduce(t)
-        out = t.cpu().numpy()
-        if self.intr.kind in ('rnd', 'icm_apt', 'aps'):
-            out[L.IM_RMS_MEAN:L.IM_RMS_STD + 1] = raw[L.IM_RMS_MEAN:L.IM_RMS_STD + 1]
-        return out
+        """The module's metrics as global means; the RMS state (slots 3, 4 of RND, ICM-APT and APS) is the same on every rank and is not
+        summed."""
+        rms = self.intr.kind in ('rnd', 'icm_apt', 'aps')
+        return global_means(self.intr, slice(L.IM_RMS_MEAN, L.IM_RMS_STD + 1) if rms else None)
 
     def _pix_module(self, fo, fn, s):
         """Module step + intrinsic reward on the encodings (device pointers); d(loss)/d(encoding) lands in self._dobs."""
-        self._intr_run(fo, s.action, fn, s.reward, s.reward, True, dobs_out=self._dobs.data_ptr())
+        self.intr.run_update(fo, s.action, fn, s.reward, s.reward, True, dobs_out=self._dobs.data_ptr())
 
     def _pix_alloc(self):
         """Called by the subclass constructors once self.intr exists."""
@@ -904,10 +825,10 @@ class _IntrAgent(DDPGAgent):
         fo, fn = eng.encode(0), eng.encode(1)
         if self.reward_free:
             self._pix_module(fo, fn, s)
-            self._encoder_step(self._PIX_GRAD, self._dobs.data_ptr(), 0)
+            eng.run_encoder_step(self._PIX_GRAD, self._dobs.data_ptr(), 0)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        self._pix_step(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
+        eng.run_update(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
                        keep_encoded=True)
         metrics = dict()
         if self.use_tb or self.use_wandb:
@@ -1036,16 +957,6 @@ class RNDAgent(_IntrAgent):
         self.intrinsic_reward_rms = _RmsView(self.intr)
         self._pix_alloc()
 
-    def _rnd_features(self, shifts, clip_val=5.0):
-        """RND.forward's front end; under torch.distributed the BatchNorm2d statistics are over every rank's frames."""
-        eng = self.engine
-        if not self._pix_dp:
-            return eng.rnd_features(shifts, clip_val)
-        for phase in range(2):
-            eng.rnd_features_phase(phase, shifts, clip_val)
-            torch.distributed.all_reduce(eng.bn_partials())
-        return eng.rnd_features_phase(2, None, clip_val)
-
     def _update_pixels(self, replay_iter, step):
         """rnd.py:110-159 on pixels. RND.forward augments the raw frames itself, normalises them with a BatchNorm2d and runs the agent's
         encoder inside its predictor (and a frozen copy inside its target): update_rnd steps that encoder twice on the same gradients
@@ -1060,14 +971,14 @@ class RNDAgent(_IntrAgent):
         B, A = eng.batch, self.action_dim
         sh = lambda: self.shift_hook(B) if self.shift_hook else None
         if self.reward_free:
-            fp, ft = self._rnd_features(sh())
-            self._intr_run(fp, None, ft, s.reward, s.reward, 2, dobs_out=self._dobs.data_ptr())
-            self._encoder_step(0, self._dobs.data_ptr(), 2)
-            fp, ft = self._rnd_features(sh())
-            self._intr_run(fp, None, ft, s.reward, s.reward, False)
+            fp, ft = eng.run_rnd_features(sh())
+            self.intr.run_update(fp, None, ft, s.reward, s.reward, 2, dobs_out=self._dobs.data_ptr())
+            eng.run_encoder_step(0, self._dobs.data_ptr(), 2)
+            fp, ft = eng.run_rnd_features(sh())
+            self.intr.run_update(fp, None, ft, s.reward, s.reward, False)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        self._pix_step(stddev, sh(), sh(), self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None)
+        eng.run_update(stddev, sh(), sh(), self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None)
         metrics = dict()
         if self.use_tb or self.use_wandb:
             metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
@@ -1215,7 +1126,7 @@ class DIAYNAgent(_MetaObsMixin, _IntrAgent):
         self._pix_alloc()
 
     def _pix_module(self, fo, fn, s):          # the discriminator reads the next frame's encoding (diayn.py:141-147)
-        self._intr_run(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.skill_dim, dobs_out=self._dobs.data_ptr())
+        self.intr.run_update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.skill_dim, dobs_out=self._dobs.data_ptr())
 
     def get_meta_specs(self):
         return (_Spec((self.skill_dim,), np.float32, 'skill'),)
@@ -1248,7 +1159,7 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
     _PIX_GRAD = 1                        # update_aps reaches the encoder through next_obs (aps.py:147-159,203-204)
 
     def _pix_module(self, fo, fn, s):
-        self._intr_run(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.sf_dim, dobs_out=self._dobs.data_ptr())
+        self.intr.run_update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.sf_dim, dobs_out=self._dobs.data_ptr())
 
     def __init__(self, update_task_every_step, sf_dim, knn_rms, knn_k, knn_avg, knn_clip, num_init_steps, lstsq_batch_size, update_encoder,
                  **kwargs):
@@ -1390,7 +1301,7 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         eng = self.engine
         xz = torch.cat([eng.feature_view(fo), eng.meta_rows()], 1).contiguous()
         e = self._eps()
-        self._intr_run(xz.data_ptr(), None, None, s.reward, s.reward, True, skill=s.meta, obs_ld=xz.shape[1], skill_ld=self.z_dim,
+        self.intr.run_update(xz.data_ptr(), None, None, s.reward, s.reward, True, skill=s.meta, obs_ld=xz.shape[1], skill_ld=self.z_dim,
                        cat_uniform=e.data_ptr() if e is not None else None, dobs_out=self._dobs.data_ptr())
         self._keep_eps = (e, xz)
 
@@ -1521,7 +1432,7 @@ class ProtoAgent(_IntrAgent):
             self._dobs = torch.zeros(self.engine.batch, self.obs_dim, device=self.engine.device)
         O = self.obs_dim
         w = _proto_init(O, pred_dim, proj_dim, num_protos)
-        dp = self._intr_dp() if self.shard_pretraining and self._pix_dp else dict(batch=self._module_batch)
+        dp = self._intr_dp() if self.shard_pretraining else dict(batch=self._module_batch)
         self.intr = IntrEngine('proto', O, self.action_dim, proj_dim, **dp, rep_dim=pred_dim, lr=self.lr, knn_k=topk,
                                num_protos=num_protos, queue_size=queue_size, tau=tau, target_tau=encoder_target_tau,
                                precision=self._precision, device=self.device)
@@ -1578,11 +1489,11 @@ class ProtoAgent(_IntrAgent):
             ft = eng.encode(1, target=True)
             # under torch.distributed (shard_pretraining): the module's phases with their exchanges, and the encoder's share of proto_opt
             # summed across the ranks; with one process these are the one-call forms
-            self._intr_run(fo, None, ft, None, s.reward, 2, next_obs_target=ft, dobs_out=self._dobs.data_ptr())
-            self._encoder_step(0, self._dobs.data_ptr(), 1)
+            self.intr.run_update(fo, None, ft, None, s.reward, 2, next_obs_target=ft, dobs_out=self._dobs.data_ptr())
+            eng.run_encoder_step(0, self._dobs.data_ptr(), 1)
             fn = eng.encode(1)
             u = self._cat_u()
-            self._intr_run(fo, None, fn, s.reward, s.reward, False, cat_uniform=u.data_ptr() if u is not None else None)
+            self.intr.run_update(fo, None, fn, s.reward, s.reward, False, cat_uniform=u.data_ptr() if u is not None else None)
             self._keep_u = u
             # proto.py:190-191 encodes obs and next_obs again for the actor / critic: next_obs with the weights and the input of the reward
             # pass above — the same values, kept — and obs with the stepped encoder, the one pass left to make (4 of the update's 20
@@ -1590,7 +1501,7 @@ class ProtoAgent(_IntrAgent):
             eng.encode(0)
         stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        self._pix_step(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
+        eng.run_update(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
                        keep_augmented=not self.reward_free, keep_encoded=self.reward_free)
         eng.encoder_target(self.encoder_target_tau)
         metrics = dict()

@@ -45,6 +45,13 @@ class Comm:
             self.lib.exorl_comm_destroy(h)
 
 
+def all_ranks(ok, device):
+    """True when `ok` holds on every rank of torch.distributed (collective), so all ranks take the same path."""
+    flag = torch.tensor([1.0 if ok else 0.0], device=device)
+    torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
+    return float(flag[0]) != 0.0
+
+
 def native_comm(device):
     """The communicator spanning torch.distributed's ranks, created on first use (collective: every rank must get here), or None
     when the collectives stay with torch.distributed (not initialised, gloo backend, EXORL_DP_COMM != native, or RCCL refused)."""
@@ -73,9 +80,7 @@ def native_comm(device):
                 raise L.ExorlError(f'probe all-reduce returned {float(probe[0])}')
     except L.ExorlError as e:
         comm, err = None, str(e)
-    ok = torch.tensor([1.0 if comm is not None else 0.0], device=device)
-    dist.all_reduce(ok, op=dist.ReduceOp.MIN)              # all ranks take the same path
-    if float(ok[0]) == 0.0:
+    if not all_ranks(comm is not None, device):
         if rank == 0:
             warnings.warn(f'exorl_amd: native RCCL communicator unavailable ({err or "another rank failed"}); using torch.distributed')
         _cached = False

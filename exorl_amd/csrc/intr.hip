@@ -117,22 +117,57 @@ __device__ inline void rms_update(RmsState* st, float mean, float var, int bs) {
     st->M = newM; st->S = newS; st->n += (double)bs;
 }
 
-// compute_intr_reward (rnd.py:98-103) + the update()'s reward bookkeeping (:131-137): single block
-__global__ __launch_bounds__(1024) void rnd_reward_kernel(const float* __restrict__ err, const float* extr, float* reward, int B, float scale,
-                                                          RmsState* st, float* __restrict__ metrics) {
+// The moments utils.RMS takes of a batch, as every thread of the block gets them: the fp32 mean of val(0..n-1), then the fp32 sum of the
+// squared distances from it
+template <class V>
+__device__ __forceinline__ void block_moments(V val, int n, float* red, float& mean, float& q) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) s += val(i);
+    mean = block_sum(s, red) / (float)n;
+    q = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) { const float d = val(i) - mean; q += d * d; }
+    q = block_sum(q, red);
+}
+
+// ---- utils.RMS over the global batch of a data-parallel step (rnd.py:98-103, utils.py:264-276,301-319) -----------------------
+// Each rank reduces its own values to (n, mean, M2) with block_moments and the ranks' moments are all-gathered. The combine merges them
+// in rank order in double (Chan et al.), so every rank computes the same RMS update bit for bit. Values: RND's per-row error (k = 1,
+// avg = 0), or PBE's top-k distances (all B*k with avg, else the k-th of each row).
+__global__ __launch_bounds__(1024) void rms_moments_kernel(const float* __restrict__ x, int B, int k, int avg, double* __restrict__ mom) {
+    __shared__ float red[17];
+    const int n = avg ? B * k : B;
+    float mean, q;
+    block_moments([&](int i) { return avg ? x[i] : x[(int64_t)i * k + (k - 1)]; }, n, red, mean, q);
+    if (threadIdx.x == 0) { mom[0] = (double)n; mom[1] = (double)mean; mom[2] = (double)q; }
+}
+// merge `world` (n, mean, M2) triples in rank order, then utils.RMS.__call__ with the merged batch mean and unbiased variance
+__device__ void rms_combine_update(RmsState* st, const double* __restrict__ mom, int world) {
+    double n = mom[0], mean = mom[1], m2 = mom[2];
+    for (int r = 1; r < world; ++r) {
+        const double nr = mom[3 * r], d = mom[3 * r + 1] - mean, tot = n + nr;
+        mean += d * nr / tot;
+        m2 += mom[3 * r + 2] + d * d * n * nr / tot;
+        n = tot;
+    }
+    rms_update(st, (float)mean, (float)(m2 / (n > 1.0 ? n - 1.0 : 1.0)), (int)n);
+}
+
+// compute_intr_reward (rnd.py:98-103) + the update()'s reward bookkeeping (:131-137) on this rank's B rows of the Bg-row batch: single
+// block. mom: the `world` ranks' gathered moments of err, or null with one rank (the kernel takes them itself); metrics are partial
+// means over Bg rows
+__global__ __launch_bounds__(1024) void rnd_reward_kernel(const float* __restrict__ err, const float* extr, float* reward, int B, int Bg, float scale,
+                                                          RmsState* st, const double* __restrict__ mom, int world, float* __restrict__ metrics) {
     __shared__ float red[17];
     __shared__ float sh_S;
-    float s = 0.f, e = 0.f;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) { s += err[i]; e += extr ? extr[i] : 0.f; }
-    const float mean = block_sum(s, red) / (float)B;
+    float e = 0.f, mean = 0.f, q = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
     e = block_sum(e, red);
-    float q = 0.f;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) { const float d = err[i] - mean; q += d * d; }
-    const float var = block_sum(q, red) / (float)(B > 1 ? B - 1 : 1);
+    if (!mom) block_moments([&](int i) { return err[i]; }, B, red, mean, q);
     if (threadIdx.x == 0) {
-        rms_update(st, mean, var, B);
+        if (mom) rms_combine_update(st, mom, world);
+        else rms_update(st, mean, q / (float)(B > 1 ? B - 1 : 1), B);
         sh_S = st->S;
-        metrics[EXORL_IM_EXTR_REWARD] = e / (float)B;
+        metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg;
         metrics[EXORL_IM_RMS_MEAN] = st->M;
         metrics[EXORL_IM_RMS_STD] = sqrtf(st->S);
     }
@@ -145,7 +180,7 @@ __global__ __launch_bounds__(1024) void rnd_reward_kernel(const float* __restric
         rs += r;
     }
     rs = block_sum(rs, red);
-    if (threadIdx.x == 0) metrics[EXORL_IM_INTR_REWARD] = rs / (float)B;
+    if (threadIdx.x == 0) metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg;
 }
 
 // ICM errors (icm.py:28-45): fe = ||tgt - pred||_2, be = ||a - tanh(apre)||_2 per row, and the gradients of
@@ -235,125 +270,29 @@ __global__ __launch_bounds__(1024) void icm_reward_kernel(const float* __restric
     if (threadIdx.x == 0) { metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg; metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg; }
 }
 
-// utils.PBE.__call__ after the top-k (utils.py:301-319): topk (B,k) ascending; single block
-__global__ __launch_bounds__(1024) void pbe_reward_kernel(const float* __restrict__ topk, const float* extr, float* reward, int B, int k,
-                                                          int avg, int use_rms, float clip, RmsState* st, float* __restrict__ metrics) {
+// utils.PBE.__call__ after the top-k (utils.py:301-319) on this rank's B rows of the Bg-row batch: topk (B,k) ascending, against the whole
+// batch; single block. mom as in rnd_reward_kernel (read only with use_rms)
+__global__ __launch_bounds__(1024) void pbe_reward_kernel(const float* __restrict__ topk, const float* extr, float* reward, int B, int Bg, int k,
+                                                          int avg, int use_rms, float clip, RmsState* st, const double* __restrict__ mom, int world,
+                                                          float* __restrict__ metrics) {
     __shared__ float red[17];
     __shared__ float sh_M;
-    const int n = avg ? B * k : B;
-    auto val = [&](int i) { return avg ? topk[i] : topk[(int64_t)i * k + (k - 1)]; };
     float e = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
     e = block_sum(e, red);
     float M = 1.0f;
     if (use_rms) {
-        float s = 0.f;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) s += val(i);
-        const float mean = block_sum(s, red) / (float)n;
-        float q = 0.f;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) { const float d = val(i) - mean; q += d * d; }
-        const float var = block_sum(q, red) / (float)(n > 1 ? n - 1 : 1);
-        if (threadIdx.x == 0) { rms_update(st, mean, var, n); sh_M = st->M; }
+        const int n = avg ? B * k : B;
+        float mean = 0.f, q = 0.f;
+        if (!mom) block_moments([&](int i) { return avg ? topk[i] : topk[(int64_t)i * k + (k - 1)]; }, n, red, mean, q);
+        if (threadIdx.x == 0) {
+            if (mom) rms_combine_update(st, mom, world);
+            else rms_update(st, mean, q / (float)(n > 1 ? n - 1 : 1), n);
+            sh_M = st->M;
+        }
         __syncthreads();
         M = sh_M;
     }
-    float rs = 0.f;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        float r;
-        if (avg) {
-            float acc = 0.f;
-            for (int j = 0; j < k; ++j) {
-                float v = topk[(int64_t)b * k + j];
-                if (use_rms) v = v / M;
-                if (clip >= 0.f) v = fmaxf(v - clip, 0.f);
-                acc += v;
-            }
-            r = acc / (float)k;
-        } else {
-            r = topk[(int64_t)b * k + (k - 1)];
-            if (use_rms) r = r / M;
-            if (clip >= 0.f) r = fmaxf(r - clip, 0.f);
-        }
-        r = logf(r + 1.0f);
-        reward[b] = r;
-        rs += r;
-    }
-    rs = block_sum(rs, red);
-    if (threadIdx.x == 0) {
-        metrics[EXORL_IM_EXTR_REWARD] = e / (float)B;
-        metrics[EXORL_IM_INTR_REWARD] = rs / (float)B;
-        metrics[EXORL_IM_RMS_MEAN] = st->M;
-        metrics[EXORL_IM_RMS_STD] = sqrtf(st->S);
-    }
-}
-
-// ---- data parallel: utils.RMS over the global batch (rnd.py:98-103, utils.py:264-276,301-319) ------------------------------
-// Each rank reduces its own values to (n, mean, M2) — the mean and the centred sum in fp32 as the single-rank kernels above form them —
-// and the ranks' moments are all-gathered. The combine merges them in rank order in double (Chan et al.), so every rank computes the
-// same RMS update bit for bit; for one rank it passes the fp32 moments through. Values: RND's per-row error (k = 1, avg = 0), or PBE's
-// top-k distances (all B*k with avg, else the k-th of each row).
-__global__ __launch_bounds__(1024) void rms_moments_kernel(const float* __restrict__ x, int B, int k, int avg, double* __restrict__ mom) {
-    __shared__ float red[17];
-    const int n = avg ? B * k : B;
-    auto val = [&](int i) { return avg ? x[i] : x[(int64_t)i * k + (k - 1)]; };
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) s += val(i);
-    const float mean = block_sum(s, red) / (float)n;
-    float q = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { const float d = val(i) - mean; q += d * d; }
-    q = block_sum(q, red);
-    if (threadIdx.x == 0) { mom[0] = (double)n; mom[1] = (double)mean; mom[2] = (double)q; }
-}
-// merge `world` (n, mean, M2) triples in rank order, then utils.RMS.__call__ with the merged batch mean and unbiased variance
-__device__ void rms_combine_update(RmsState* st, const double* __restrict__ mom, int world) {
-    double n = mom[0], mean = mom[1], m2 = mom[2];
-    for (int r = 1; r < world; ++r) {
-        const double nr = mom[3 * r], d = mom[3 * r + 1] - mean, tot = n + nr;
-        mean += d * nr / tot;
-        m2 += mom[3 * r + 2] + d * d * n * nr / tot;
-        n = tot;
-    }
-    rms_update(st, (float)mean, (float)(m2 / (n > 1.0 ? n - 1.0 : 1.0)), (int)n);
-}
-// rnd_reward_kernel on this rank's rows after the moment exchange; metrics are partial means over Bg rows
-__global__ __launch_bounds__(1024) void rnd_reward_dp_kernel(const float* __restrict__ err, const float* extr, float* reward, int B, int Bg, float scale,
-                                                             RmsState* st, const double* __restrict__ mom, int world, float* __restrict__ metrics) {
-    __shared__ float red[17];
-    __shared__ float sh_S;
-    float e = 0.f;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
-    e = block_sum(e, red);
-    if (threadIdx.x == 0) {
-        rms_combine_update(st, mom, world);
-        sh_S = st->S;
-        metrics[EXORL_IM_EXTR_REWARD] = e / (float)Bg;
-        metrics[EXORL_IM_RMS_MEAN] = st->M;
-        metrics[EXORL_IM_RMS_STD] = sqrtf(st->S);
-    }
-    __syncthreads();
-    const float denom = sqrtf(sh_S) + 1e-8f;
-    float rs = 0.f;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) {
-        const float r = scale * err[i] / denom;
-        reward[i] = r;
-        rs += r;
-    }
-    rs = block_sum(rs, red);
-    if (threadIdx.x == 0) metrics[EXORL_IM_INTR_REWARD] = rs / (float)Bg;
-}
-// pbe_reward_kernel on this rank's rows (topk: its rows against the gathered batch); mom == null: no RMS (knn_rms false)
-__global__ __launch_bounds__(1024) void pbe_reward_dp_kernel(const float* __restrict__ topk, const float* extr, float* reward, int B, int Bg, int k,
-                                                             int avg, float clip, RmsState* st, const double* __restrict__ mom, int world,
-                                                             float* __restrict__ metrics) {
-    __shared__ float red[17];
-    __shared__ float sh_M;
-    float e = 0.f;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) e += extr ? extr[i] : 0.f;
-    e = block_sum(e, red);
-    if (threadIdx.x == 0 && mom) { rms_combine_update(st, mom, world); sh_M = st->M; }
-    __syncthreads();
-    const bool use_rms = mom != nullptr;
-    const float M = use_rms ? sh_M : 1.0f;
     float rs = 0.f;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         float r;
@@ -1269,18 +1208,15 @@ static int rnd_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
         }
         // compute_intr_reward (rnd.py:98-103); states: same batch -> same BatchNorm output and frozen target, only the predictor moved
         EXORL_TRY(rnd_forward(it, b, !train, nullptr, s));
-        if (it->world == 1) {
-            hipLaunchKernelGGL(rnd_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, c.scale, it->rms, it->metrics);
+        if (it->world > 1) {                        // exchange the batch moments of the error; the reward is stage 2
+            hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->fe, B, 1, 0, it->mom + 3 * it->rank);
             EXORL_LAUNCH_CHECK();
+            *next = EXORL_INTR_XCHG_MOMENTS;
             return 0;
         }
-        hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->fe, B, 1, 0, it->mom + 3 * it->rank);
-        EXORL_LAUNCH_CHECK();
-        *next = EXORL_INTR_XCHG_MOMENTS;
-        return 0;
     }
-    hipLaunchKernelGGL(rnd_reward_dp_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, it->Bg(), c.scale, it->rms,
-                       (const double*)it->mom, it->world, it->metrics);
+    hipLaunchKernelGGL(rnd_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, it->Bg(), c.scale, it->rms,
+                       it->world > 1 ? (const double*)it->mom : nullptr, it->world, it->metrics);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
@@ -1344,16 +1280,12 @@ static int pbe_stage(exorl_intr* it, const exorl_intr_batch& b, const float* rep
     const int B = c.batch, R = c.rep_dim;
     *next = -1;
     if (stage == 1) {
-        if (it->world == 1) {
-            EXORL_TRY(knn_topk(rep, B, rep, B, R, c.knn_k, it->topk, it->d2, s));
-            hipLaunchKernelGGL(pbe_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, c.knn_k, c.knn_avg, c.knn_rms,
-                               c.knn_clip, it->rms, it->metrics);
-            EXORL_LAUNCH_CHECK();
+        if (it->world > 1) {                            // gather the rows: the neighbours are sought in the global batch (stage 2)
+            EXORL_CHECK_HIP(hipMemcpyAsync(it->gat + (int64_t)it->rank * B * R, rep, sizeof(float) * B * R, hipMemcpyDeviceToDevice, s));
+            *next = EXORL_INTR_XCHG_REP;
             return 0;
         }
-        EXORL_CHECK_HIP(hipMemcpyAsync(it->gat + (int64_t)it->rank * B * R, rep, sizeof(float) * B * R, hipMemcpyDeviceToDevice, s));
-        *next = EXORL_INTR_XCHG_REP;
-        return 0;
+        EXORL_TRY(knn_topk(rep, B, rep, B, R, c.knn_k, it->topk, it->d2, s));
     }
     if (stage == 2) {
         EXORL_TRY(knn_topk(rep, B, it->gat, it->Bg(), R, c.knn_k, it->topk, it->d2, s));
@@ -1364,8 +1296,8 @@ static int pbe_stage(exorl_intr* it, const exorl_intr_batch& b, const float* rep
             return 0;
         }
     }
-    hipLaunchKernelGGL(pbe_reward_dp_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, it->Bg(), c.knn_k, c.knn_avg,
-                       c.knn_clip, it->rms, c.knn_rms ? (const double*)it->mom : nullptr, it->world, it->metrics);
+    hipLaunchKernelGGL(pbe_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, it->Bg(), c.knn_k, c.knn_avg, c.knn_rms,
+                       c.knn_clip, it->rms, it->world > 1 ? (const double*)it->mom : nullptr, it->world, it->metrics);
     EXORL_LAUNCH_CHECK();
     return 0;
 }

@@ -28,7 +28,18 @@ def _require_gpu(device):
     return dev
 
 
-class AgentEngine:
+class _Phased:
+    """What the engines with phased calls share: the choice between a call's one-call form and its phases under torch.distributed."""
+    world_size, rank, comm = 1, None, None
+
+    def _run(self, one_call, steps, *a, **k):
+        """one_call(*a, **k) on one rank, else its phases steps(*a, **k) with the exchanges run over torch.distributed."""
+        if self.world_size == 1:
+            return one_call(*a, **k)
+        return run_steps(steps(*a, **k), self.rank)
+
+
+class AgentEngine(_Phased):
     def __init__(self, kind, obs_dim, act_dim, hidden_dim, batch, lr=1e-4, tau=0.01, alpha=2.5, stddev_clip=0.3,
                  precision='fp32', world_size=1, seed=0, device='cuda', num_value_samples=10, weight_func='indicator',
                  n_samples=3, use_critic_lagrange=False, target_cql_penalty=5.0, sf_dim=0):
@@ -39,6 +50,7 @@ class AgentEngine:
                               lr, tau, alpha, stddev_clip if stddev_clip is not None else 0.0, seed, num_value_samples,
                               L.CRR_WEIGHT[weight_func], n_samples, int(bool(use_critic_lagrange)), target_cql_penalty, 0)
         self.obs_dim, self.act_dim, self.hidden_dim, self.batch = obs_dim, act_dim, hidden_dim, batch
+        self.world_size, self.lagrange = world_size, kind == 'cql' and bool(use_critic_lagrange)
         nbytes = self.lib.exorl_agent_workspace_bytes(C.byref(self.cfg))
         if nbytes == 0:
             raise L.ExorlError(self.lib.exorl_last_error().decode())
@@ -51,7 +63,6 @@ class AgentEngine:
         self.h = handle
         self._f32 = self.workspace[self._ws_off:self._ws_off + nbytes].view(torch.float32)
         self.has_critic = kind != 'bc'
-        self.comm = None
 
     def __del__(self):
         h, self.h = getattr(self, 'h', None), None
@@ -125,6 +136,35 @@ class AgentEngine:
         na = self._dev(noise_actor) if noise_actor is not None else None
         L.check(self.lib.exorl_agent_update_phase(self.h, phase, stddev, L.ptr(nc), L.ptr(na), L.current_stream()))
         self._keep_noise = (nc, na)
+
+    def update_steps(self, stddev, noise_critic=None, noise_actor=None):
+        """update() as its phases, for run_steps: yields the (buffer, op) to exchange across the ranks before the next phase. The
+        three global quantities are sum-all-reduced: the critic's gradients, the batch statistic of the kinds that have one (TD3+BC's
+        lambda; CQL's sum of log_pi for the entropy temperature, cql.py:242-243), the actor's gradients. With CQL's Lagrange weight
+        phases 4, 5 stand for phase 0: the multiplier steps on the GLOBAL penalty (this rank's sum of logsumexp and of Q1 + Q2) before
+        any critic gradient is formed (cql.py:199-213)."""
+        phase = lambda p: self.update_phase(p, stddev, noise_critic, noise_actor)
+        if self.lagrange:
+            phase(4)
+            yield self.stats(), L.XCHG_SUM
+            phase(5)
+        else:
+            phase(0)
+        if self.has_critic:
+            yield self.flat(L.NET_CRITIC, L.T_GRAD), L.XCHG_SUM
+        phase(1)
+        if self.kind in ('td3_bc', 'cql'):
+            yield self.stats(), L.XCHG_SUM
+        phase(2)
+        yield self.flat(L.NET_ACTOR, L.T_GRAD), L.XCHG_SUM
+        phase(3)
+
+    def run_update(self, *a, **k):
+        """One gradient step on any world size: update() — one host call; with a communicator the library all-reduces between its
+        phases — or, with the collectives left to torch.distributed (gloo / EXORL_DP_COMM=torch), update_steps()."""
+        if self.comm is not None:
+            return self.update(*a, **k)
+        self._run(self.update, self.update_steps, *a, **k)
 
     def act(self, obs, stddev, eval_mode, noise=None):
         o = self._dev(obs).view(-1, self.obs_dim)
@@ -210,7 +250,7 @@ class AgentEngine:
         L.check(self.lib.exorl_agent_set_opt_steps(self.h, actor_steps, critic_steps))
 
 
-class IntrEngine:
+class IntrEngine(_Phased):
     """Intrinsic-reward module (exorl_intr_t): RND / ICM / ICM-APT. Parameters live in a torch-owned workspace so they
     can be exposed as tensors (state_dict, snapshots)."""
     KINDS = {'rnd': L.INTR_RND, 'icm': L.INTR_ICM, 'icm_apt': L.INTR_ICM_APT, 'disagreement': L.INTR_DISAGREEMENT, 'diayn': L.INTR_DIAYN,
@@ -308,6 +348,14 @@ class IntrEngine:
         L.check(self.lib.exorl_intr_update_phase(self.h, C.byref(b), 2 if train == 2 else int(bool(train)), phase, C.byref(nxt), L.current_stream()))
         return nxt.value
 
+    def update_steps(self, *a, **k):
+        """update() as its phases, for run_steps: the library names the exchange that follows each phase."""
+        return phase_steps(lambda phase: self.update_phase(phase, *a, **k), self.exchange)
+
+    def run_update(self, *a, **k):
+        """update(), or for a sharded module its phases with the exchanges each one names."""
+        self._run(self.update, self.update_steps, *a, **k)
+
     def exchange(self, xid):
         """(device tensor, op) of exchange `xid`: op L.XCHG_SUM -> sum-all-reduce the tensor in place; L.XCHG_GATHER -> the tensor is
         (world_size, count), rank r's row being its slot, all-gathered in rank order."""
@@ -340,7 +388,7 @@ class IntrEngine:
         return int(c.value)
 
 
-def run_exchange(buf, op, rank, dist=None):
+def run_exchange(buf, op, rank=None, dist=None):
     """One exchange of a phased call under torch.distributed: sum all-reduce in place, or all-gather of the (world_size, count) slots in
     rank order (into views of the slots: gloo has no all_gather_into_tensor)."""
     dist = dist or torch.distributed
@@ -351,19 +399,46 @@ def run_exchange(buf, op, rank, dist=None):
         dist.all_gather(slots, slots[rank].clone())
 
 
-def drive_phases(phase_fn, exchange_fn, rank, dist=None):
-    """Runs phase_fn(0), phase_fn(1), ... to completion: each returns the exchange id to run before the next phase (-1: done), and
-    exchange_fn(id) -> (buffer, op) names its buffer."""
+def phase_steps(phase_fn, exchange_fn):
+    """The steps of a call whose phases name their own exchange: phase_fn(0), phase_fn(1), ... each return the exchange id to run before
+    the next phase (-1: done), and exchange_fn(id) -> (buffer, op) names its buffer."""
     phase = 0
-    while True:
-        nxt = phase_fn(phase)
-        if nxt < 0:
-            return
-        run_exchange(*exchange_fn(nxt), rank, dist)
+    while (xid := phase_fn(phase)) >= 0:
+        yield exchange_fn(xid)
         phase += 1
 
 
-class PixelEngine:
+def run_steps(steps, rank=None, dist=None):
+    """The one loop behind every phased engine call: runs a *_steps generator to completion, exchanging every (buffer, op) it yields across
+    the ranks before it resumes with its next phase. `rank` is this rank's slot in a gather. Returns what the call returns."""
+    while True:
+        try:
+            buf, op = next(steps)
+        except StopIteration as done:
+            return done.value
+        run_exchange(buf, op, rank, dist)
+
+
+def drive_phases(phase_fn, exchange_fn, rank, dist=None):
+    """run_steps for a caller that holds the phase function itself (see phase_steps)."""
+    run_steps(phase_steps(phase_fn, exchange_fn), rank, dist)
+
+
+def global_means(engine, keep=None):
+    """engine.metrics_raw() as means over the global batch: a sharded engine's partial means summed over the ranks. `keep` slices the
+    slots that hold the same value on every rank already (the RMS state) and are not summed."""
+    raw = engine.metrics_raw()
+    if engine.world_size == 1:
+        return raw
+    t = torch.from_numpy(raw.copy()).to(engine.device)
+    run_exchange(t, L.XCHG_SUM)
+    out = t.cpu().numpy()
+    if keep is not None:
+        out[keep] = raw[keep]
+    return out
+
+
+class PixelEngine(_Phased):
     """DDPG on pixel observations (exorl_pixel_agent_t): augmentation, conv encoder, pixel actor/critic and their update."""
     NETS = {'encoder': 0, 'actor': 1, 'critic': 2, 'critic_target': 3}
 
@@ -372,7 +447,6 @@ class PixelEngine:
         self.lib = L.load()
         self.device = _require_gpu(device)
         self.world_size = world_size
-        self.comm = None
         c, h, w = obs_shape
         if h != w:
             raise L.ExorlError(f'pixel observations must be square, got {obs_shape}')
@@ -457,8 +531,25 @@ class PixelEngine:
         ptrs = self._update_args(shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
         L.check(self.lib.exorl_pixel_agent_update_phase(self.h, phase, stddev, *ptrs, L.current_stream()))
 
+    def update_steps(self, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False,
+                     keep_encoded=False):
+        """update() as its phases, for run_steps. Each rank runs the step on its rows and every mean in it is over the global batch, so
+        the gradients are sum-all-reduced between the phases: the critic's (+ the encoder's), then the actor's."""
+        self.update_phase(0, stddev, shifts_obs, shifts_next, noise_critic, None, keep_augmented=keep_augmented, keep_encoded=keep_encoded)
+        yield self.grad_buffer(0), L.XCHG_SUM
+        self.update_phase(1, stddev, noise_actor=noise_actor)
+        yield self.grad_buffer(1), L.XCHG_SUM
+        self.update_phase(2, stddev)
+
+    def run_update(self, *a, **k):
+        """The DDPG pixel step on any world size, as AgentEngine.run_update."""
+        if self.comm is not None:
+            return self.update(*a, **k)
+        self._run(self.update, self.update_steps, *a, **k)
+
     def grad_buffer(self, exchange):
-        """Device view of what a data-parallel step sum-all-reduces after phase `exchange`: 0 critic (+ encoder) gradients, 1 actor gradients."""
+        """Device view of what a data-parallel step sum-all-reduces: 0 critic (+ encoder) gradients, 1 actor gradients, 2 the encoder's
+        gradients of encoder_step."""
         p, n = C.c_void_p(), C.c_int64()
         L.check(self.lib.exorl_pixel_agent_grad_buffer(self.h, exchange, C.byref(p), C.byref(n)))
         return self._view(p.value, n.value)
@@ -485,6 +576,15 @@ class PixelEngine:
     def encoder_step_phase(self, phase, which, dfeat_ptr, opt):
         """encoder_step in two phases: 0 the backward pass (then sum-all-reduce grad_buffer(2)), 1 the optimiser step(s)."""
         L.check(self.lib.exorl_pixel_agent_encoder_step_phase(self.h, which, dfeat_ptr, opt, phase, L.current_stream()))
+
+    def encoder_step_steps(self, which, dfeat_ptr, opt):
+        """encoder_step() as its phases, for run_steps."""
+        self.encoder_step_phase(0, which, dfeat_ptr, opt)
+        yield self.grad_buffer(2), L.XCHG_SUM
+        self.encoder_step_phase(1, which, dfeat_ptr, opt)
+
+    def run_encoder_step(self, *a):
+        self._run(self.encoder_step, self.encoder_step_steps, *a)
 
     def encoder_target(self, tau=0.0, init=False):
         L.check(self.lib.exorl_pixel_agent_encoder_target(self.h, tau, int(bool(init)), L.current_stream()))
@@ -571,6 +671,16 @@ class PixelEngine:
         L.check(self.lib.exorl_pixel_agent_rnd_features_phase(self.h, phase, L.ptr(self._keep_r) if phase == 0 else None, clip_val,
                                                               C.byref(fp), C.byref(ft), L.current_stream()))
         return (fp.value, ft.value) if phase == 2 else None
+
+    def rnd_features_steps(self, shifts=None, clip_val=5.0):
+        """rnd_features() as its phases, for run_steps: the BatchNorm2d statistics are over every rank's frames."""
+        for phase in range(2):
+            self.rnd_features_phase(phase, shifts, clip_val)
+            yield self.bn_partials(), L.XCHG_SUM
+        return self.rnd_features_phase(2, None, clip_val)
+
+    def run_rnd_features(self, *a):
+        return self._run(self.rnd_features, self.rnd_features_steps, *a)
 
     def bn_partials(self):
         """(c_in * chunks,) float64 device view of the BatchNorm2d partial sums the ranks add up between the rnd_features phases."""

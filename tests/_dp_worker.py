@@ -1,6 +1,6 @@
 """One data-parallel rank of the product path, run as a fresh child process (tests/test_gpu_dp.py starts two of them before the
 parent touches the GPU; bench.py --gpus N does the same with its own children). Every rank sits on cuda:0 and talks gloo, so the
-multi-process branch of exorl_amd.agents (_run_update's phase split + torch.distributed.all_reduce, _metrics' all-reduce,
+multi-process branch of exorl_amd (AgentEngine.run_update's phases with torch.distributed.all_reduce between them, _metrics' all-reduce,
 make_replay_loader(..., worker_ids=[rank])) executes for real on a one-GPU box."""
 import json
 import os
@@ -64,7 +64,7 @@ def sliced_noise_hook(ns, rows, local_rows):
     return hook
 
 
-HOOKED = [('td3', 'fp32'), ('cql', 'fp32'), ('cqll', 'fp32'), ('crr', 'fp32')]          # the kinds run through sliced_noise_hook (CQL: its own _run_update branch under torch.distributed)
+HOOKED = [('td3', 'fp32'), ('cql', 'fp32'), ('cqll', 'fp32'), ('crr', 'fp32')]          # the kinds run through sliced_noise_hook (CQL: its own exchanges under torch.distributed)
 
 
 # ---- reward-free agents (sharded actor / critic step, module step on the all-gathered batch: agents._IntrAgent._intr_step_dp) ----------

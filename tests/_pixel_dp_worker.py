@@ -1,18 +1,15 @@
 """One data-parallel rank of the pixel product path, run as a fresh child process (tests/test_gpu_pixel_dp.py starts two of them). Both
-ranks sit on cuda:0 and talk gloo, so DDPGAgent._pix_step's phase split + torch.distributed.all_reduce of the exchange buffers and _metrics'
+ranks sit on cuda:0 and talk gloo, so PixelEngine.run_update's phases with torch.distributed.all_reduce of the exchange buffers between them and _metrics'
 all-reduce execute for real on a one-GPU box."""
 import json
-import os
 import sys
 from pathlib import Path
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / 'tests'))
+import _pixel_dp_common as common
+from _pixel_dp_common import flat  # noqa: F401 — the parent test's W.flat
 
 C_, HW, A, F, H, B_GLOBAL, STEPS, SKILLS = 3, 84, 6, 50, 256, 128, 3, 8
 
@@ -34,49 +31,27 @@ def build(kind, batch):
 
 
 def hooks(ag, rows):
-    """Shifts and noise drawn for the GLOBAL batch in every process (one stream), each rank keeping its rows."""
-    import _synth
-    rs, ns = np.random.RandomState(11), _synth.NoiseStream(9)
-    ag.shift_hook = lambda n: np.ascontiguousarray(rs.randint(0, 9, (B_GLOBAL, 2)).astype(np.int32)[rows])
-    ag.noise_hook = lambda shape: np.ascontiguousarray(ns.draw((B_GLOBAL, shape[1]))[rows])
+    common.hooks(ag, rows, B_GLOBAL)
 
 
 def batch(kind, step, rows=slice(None)):
-    rs = np.random.RandomState(700 + step)
-    obs = rs.randint(0, 256, (B_GLOBAL, C_, HW, HW)).astype(np.uint8)
-    nxt = rs.randint(0, 256, (B_GLOBAL, C_, HW, HW)).astype(np.uint8)
-    b = [obs, rs.uniform(-1, 1, (B_GLOBAL, A)).astype(np.float32), rs.uniform(0, 1, B_GLOBAL).astype(np.float32),
-         np.full(B_GLOBAL, 0.99, np.float32), nxt]
-    if kind == 'diayn':
-        b.append(np.eye(SKILLS, dtype=np.float32)[rs.randint(0, SKILLS, B_GLOBAL)])
-    return tuple(np.ascontiguousarray(x[rows]) for x in b)
+    skills = (lambda rs: np.eye(SKILLS, dtype=np.float32)[rs.randint(0, SKILLS, B_GLOBAL)]) if kind == 'diayn' else None
+    return common.batch(step, rows, B_GLOBAL, C_, HW, A, skills)
 
 
 def views(ag):
     return [('encoder', ag.encoder), ('actor', ag.actor), ('critic', ag.critic), ('critic_target', ag.critic_target)]
 
 
-def flat(view):
-    return torch.cat([p.reshape(-1) for p in view.parameters()]).cpu().numpy()
-
-
 def main(out):
-    rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
-    Br = B_GLOBAL // world
-    rows = slice(rank * Br, (rank + 1) * Br)
+    rank, world = common.init_ranks()
+    Br, rows = common.rank_rows(B_GLOBAL, rank, world)
     for kind in ('ddpg', 'diayn'):
         ag = build(kind, Br)
         assert ag.world_size == world and ag.engine.batch == Br
         hooks(ag, rows)
-        metrics = []
-        for step in range(STEPS):
-            m = ag.update(iter([batch(kind, step, rows)]), step)
-            metrics.append({k: float(v) for k, v in m.items()})
-        torch.cuda.synchronize()
-        np.savez(out / f'{kind}_rank{rank}.npz', **{n: flat(v) for n, v in views(ag)})
-        json.dump(metrics, open(out / f'metrics_{kind}_rank{rank}.json', 'w'))
+        metrics = common.run_updates(ag, (batch(kind, step, rows) for step in range(STEPS)))
+        common.save(out, kind, rank, {n: flat(v) for n, v in views(ag)}, metrics)
         del ag
     # no hooks: identical frames on both ranks, the device's shifts and noise
     from exorl_amd import _lib as L
@@ -99,9 +74,7 @@ def main(out):
     except Exception as e:           # noqa: BLE001 — recorded for the parent's assertion
         res = {'type': type(e).__name__, 'msg': str(e)}
     json.dump(res, open(out / f'refusal_rank{rank}.json', 'w'))
-    torch.cuda.synchronize()
-    dist.barrier()
-    dist.destroy_process_group()
+    common.finish_ranks()
 
 
 if __name__ == '__main__':

@@ -1,18 +1,14 @@
 """One data-parallel rank of the pixel pretraining path (reward_free=True), run as a fresh child process (tests/test_gpu_pixel_module_dp.py
 starts two of them). Both ranks sit on cuda:0 and talk gloo, so the module phases and their exchanges, the encoder-step phases, RND's
 BatchNorm2d exchanges, the sharded DDPG pixel step and the metric all-reduces execute for real on a one-GPU box."""
-import json
-import os
 import sys
 from pathlib import Path
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / 'tests'))
+import _pixel_dp_common as common
+from _pixel_dp_common import flat  # noqa: F401 — the parent test's W.flat
 
 C_, HW, A, F, H, B_GLOBAL, STEPS = 3, 64, 6, 32, 128, 64, 3
 KINDS = ['rnd', 'icm', 'icm_apt', 'disagreement', 'diayn', 'aps', 'smm']
@@ -48,69 +44,42 @@ def build(kind, batch):
 
 
 def hooks(ag, rows, eps=True):
-    """Shifts, noise and (SMM) the VAE's epsilon drawn for the GLOBAL batch in every process (one stream each), each rank keeping its rows."""
-    import _synth
-    rs, ns, es = np.random.RandomState(11), _synth.NoiseStream(9), np.random.RandomState(13)
-    ag.shift_hook = lambda n: np.ascontiguousarray(rs.randint(0, 9, (B_GLOBAL, 2)).astype(np.int32)[rows])
-    ag.noise_hook = lambda shape: np.ascontiguousarray(ns.draw((B_GLOBAL, shape[1]))[rows])
-    if eps and hasattr(ag, 'eps_hook'):
-        ag.eps_hook = lambda shape: np.ascontiguousarray(es.standard_normal((B_GLOBAL, shape[1])).astype(np.float32)[rows])
+    common.hooks(ag, rows, B_GLOBAL, eps)
 
 
 def batch(kind, step, rows=slice(None)):
-    rs = np.random.RandomState(700 + step)
-    obs = rs.randint(0, 256, (B_GLOBAL, C_, HW, HW)).astype(np.uint8)
-    nxt = rs.randint(0, 256, (B_GLOBAL, C_, HW, HW)).astype(np.uint8)
-    b = [obs, rs.uniform(-1, 1, (B_GLOBAL, A)).astype(np.float32), rs.uniform(0, 1, B_GLOBAL).astype(np.float32),
-         np.full(B_GLOBAL, 0.99, np.float32), nxt]
-    if kind in ('diayn', 'smm'):
-        b.append(np.eye(META[kind], dtype=np.float32)[rs.randint(0, META[kind], B_GLOBAL)])
-    elif kind == 'aps':
-        t = rs.standard_normal((B_GLOBAL, META[kind])).astype(np.float32)
-        b.append(t / np.linalg.norm(t, axis=1, keepdims=True))
-    return tuple(np.ascontiguousarray(x[rows]) for x in b)
+    def meta(rs):
+        if kind in ('diayn', 'smm'):
+            return np.eye(META[kind], dtype=np.float32)[rs.randint(0, META[kind], B_GLOBAL)]
+        if kind == 'aps':
+            t = rs.standard_normal((B_GLOBAL, META[kind])).astype(np.float32)
+            return t / np.linalg.norm(t, axis=1, keepdims=True)
+    return common.batch(step, rows, B_GLOBAL, C_, HW, A, meta)
 
 
 def views(ag):
     return [('encoder', ag.encoder), ('actor', ag.actor), ('critic', ag.critic), ('module', ag.intr)]
 
 
-def flat(view):
-    from exorl_amd import _lib as L
-    if hasattr(view, 'flat'):                       # the module engine: every parameter, frozen ones included
-        return view.flat(L.T_PARAM).cpu().numpy()
-    return torch.cat([p.reshape(-1) for p in view.parameters()]).cpu().numpy()
-
-
 def _run(kind, rank, world, out, name, eps=True):
-    Br = B_GLOBAL // world
-    rows = slice(rank * Br, (rank + 1) * Br)
+    Br, rows = common.rank_rows(B_GLOBAL, rank, world)
     ag = build(kind, Br)
     assert ag.world_size == world and ag.engine.batch == Br and ag.intr.batch == Br and ag.intr.world_size == world
     hooks(ag, rows, eps)
-    metrics = []
-    for step in range(STEPS):
-        m = ag.update(iter([batch(kind, step, rows)]), step)
-        metrics.append({k: float(v) for k, v in m.items()})
-    torch.cuda.synchronize()
+    metrics = common.run_updates(ag, (batch(kind, step, rows) for step in range(STEPS)))
     arrays = {n: flat(v) for n, v in views(ag)}
     arrays['rms'] = ag.intr._rms.cpu().numpy()
     arrays['bn2d'] = ag.engine.bn2d().cpu().numpy()
-    np.savez(out / f'{name}_rank{rank}.npz', **arrays)
-    json.dump(metrics, open(out / f'metrics_{name}_rank{rank}.json', 'w'))
+    common.save(out, name, rank, arrays, metrics)
     del ag
 
 
 def main(out):
-    rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+    rank, world = common.init_ranks()
     for kind in KINDS:
         _run(kind, rank, world, out, kind)
     _run('smm', rank, world, out, 'smm_unhooked', eps=False)          # the device's epsilon: each rank draws its rows of the global draw
-    torch.cuda.synchronize()
-    dist.barrier()
-    dist.destroy_process_group()
+    common.finish_ranks()
 
 
 if __name__ == '__main__':

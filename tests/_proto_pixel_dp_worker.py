@@ -4,19 +4,15 @@ gathers and gradient sums, the encoder step's exchange, the sharded DDPG pixel s
 
 Two workloads, each on its golden fixture with every rank holding its rows of the global batch: the miniature of
 tests/golden/pixel_proto.npz (2 ranks x 2 rows) and config 4 (tests/golden/config4_proto_b1024.npz, 2 ranks x 512 rows) in fp32 and bf16x6."""
-import json
-import os
 import sys
 from pathlib import Path
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / 'tests'))
-GOLD = ROOT / 'tests' / 'golden'
+import _pixel_dp_common as common
+
+GOLD = common.ROOT / 'tests' / 'golden'
 CONFIG4_PRECISIONS = ('fp32', 'bf16x6')
 
 
@@ -109,35 +105,25 @@ def state(ag, sample=False):
     return out
 
 
-def _save(out, name, rank, ag, ms, sample=False):
-    torch.cuda.synchronize()
-    np.savez(out / f'{name}_rank{rank}.npz', **state(ag, sample))
-    json.dump(ms, open(out / f'metrics_{name}_rank{rank}.json', 'w'))
-
-
 def main(out):
-    rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+    rank, world = common.init_ranks()
     z = np.load(GOLD / 'pixel_proto.npz')
-    Br = int(z['dims'][5]) // world
-    rows = slice(rank * Br, (rank + 1) * Br)
+    Br, rows = common.rank_rows(int(z['dims'][5]), rank, world)
     ag = proto_agent(z, Br)
     assert ag.world_size == world and ag.intr.world_size == world and ag.intr.batch == Br
     load_fixture_params(ag, z)
-    _save(out, 'fixture', rank, ag, run_fixture(ag, z, rows))
+    ms = run_fixture(ag, z, rows)
+    common.save(out, 'fixture', rank, state(ag), ms)
     del ag
     z = np.load(GOLD / 'config4_proto_b1024.npz')
-    Br = int(z['dims'][5]) // world
-    rows = slice(rank * Br, (rank + 1) * Br)
+    Br, rows = common.rank_rows(int(z['dims'][5]), rank, world)
     for precision in CONFIG4_PRECISIONS:
         ag = proto_agent(z, Br, precision)
         load_config4_params(ag, z)
-        _save(out, f'config4_{precision}', rank, ag, run_config4(ag, z, rows), sample=True)
+        ms = run_config4(ag, z, rows)
+        common.save(out, f'config4_{precision}', rank, state(ag, sample=True), ms)
         del ag
-    torch.cuda.synchronize()
-    dist.barrier()
-    dist.destroy_process_group()
+    common.finish_ranks()
 
 
 if __name__ == '__main__':

@@ -1,4 +1,4 @@
-"""The multi-process data-parallel branch of the PRODUCT (exorl_amd.agents._run_update under torch.distributed) executed for real:
+"""The multi-process data-parallel branch of the PRODUCT (AgentEngine.run_update under torch.distributed) executed for real:
 two fresh child processes (tests/_dp_worker.py, started by conftest.py before this process touches the GPU), both on cuda:0 over
 gloo, each an exorl_amd agent of batch B/2 fed by make_replay_loader(..., num_workers=2, worker_ids=[rank]). Bars: the replicas end
 bit-identical, and equal the single-process update of the concatenated batch (mean over the global batch: td3_bc.py:133-137,154)."""
@@ -74,7 +74,7 @@ def test_two_process_dp_equals_single_process(dp_run, tag):
 
 @pytest.mark.parametrize('tag', ['td3_fp32', 'cql_fp32', 'cqll_fp32', 'crr_fp32'])
 def test_two_process_dp_equals_single_process_hooked(dp_run, tag):
-    """TD3 (no batch-global statistic), CRR (value samples repeated n times per row) and CQL — whose _run_update has its own torch.distributed branch (critic gradients, the summed log pi
+    """TD3 (no batch-global statistic), CRR (value samples repeated n times per row) and CQL — whose step has its own exchanges under torch.distributed (critic gradients, the summed log pi
     behind the entropy temperature, actor gradients) and five noise tensors per step — as two ranks x B/2 against one process x B.
     `cqll` = CQL with use_critic_lagrange: the multiplier steps on the penalty of the GLOBAL batch before any critic gradient exists
     (cql.py:199-213), so phase 0 runs as phases 4 and 5 around a sum-all-reduce of the two penalty sums; the multiplier and its Adam moments
