@@ -165,6 +165,7 @@ PROTOTYPES = {
     'exorl_agent_step_graph': (C.c_int, [c_void_p, c_float, c_void_p]),
     'exorl_agent_noise_counter': (C.c_int, [c_void_p, P(c_uint64), c_void_p]),
     'exorl_debug_philox_normal': (C.c_int, [c_uint64, c_uint64, c_int64, c_void_p, c_void_p]),
+    'exorl_debug_agent_poison_scratch': (C.c_int, [c_void_p, c_void_p]),
     'exorl_agent_disable_graph': (C.c_int, [c_void_p]),
     'exorl_gemm': (C.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                              c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p]),

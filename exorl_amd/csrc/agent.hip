@@ -268,11 +268,18 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
     } else {
         GemmProblem p[2];
         if (G) {
-            for (int i = 0; i < d.n_heads; ++i)
-                p[i] = GemmProblem{b.dz2 + i * act, f.h1 + (paired ? i : 0) * act, G + d.W1 + i * d.head_stride, nullptr,
-                                   H, H, rows, H, H, H};
             EXORL_TRY(fk.fork(s));
-            EXORL_TRY(gemm_grouped(prec, 1, 1, p, d.n_heads, false, false, fk.side(s)));
+            // the wgrad sums over the rows in one float32 accumulator per element: from 8192 rows on (the row kernels' own threshold) it runs as
+            // slabs of 1024 rows accumulated into G, so that no running sum is longer than 1024 terms (one pass over 8200 rows left dW1
+            // 1.6e-6 of its largest element off the float64 value, 13 times the float32 reference's own error)
+            const int slab = rows >= 8192 ? 1024 : rows;
+            for (int r0 = 0; r0 < rows; r0 += slab) {
+                const int kr = rows - r0 < slab ? rows - r0 : slab;
+                for (int i = 0; i < d.n_heads; ++i)
+                    p[i] = GemmProblem{b.dz2 + i * act + (int64_t)r0 * H, f.h1 + (paired ? i : 0) * act + (int64_t)r0 * H,
+                                       G + d.W1 + i * d.head_stride, nullptr, H, H, kr, H, H, H};
+                EXORL_TRY(gemm_grouped(prec, 1, 1, p, d.n_heads, false, r0 > 0, fk.side(s)));
+            }
         }
         for (int i = 0; i < d.n_heads; ++i)
             p[i] = GemmProblem{b.dz2 + i * act, P + d.W1 + i * d.head_stride, b.dh1 + (paired ? i : 0) * act, nullptr,
@@ -309,10 +316,22 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
 struct Carver {           // lays sub-buffers out in one workspace; base == nullptr -> sizing pass
     float* base;
     int64_t off = 0;
+    // exorl_debug_agent_poison_scratch: carve() marks the takes a step writes before it reads (scratch = true); `fill` collects those whole,
+    // and of every other take only the alignment padding behind it, as (offset, floats) runs
+    bool scratch = false;
+    std::vector<std::pair<int64_t, int64_t>>* fill = nullptr;
     explicit Carver(float* b) : base(b) {}
     float* take(int64_t n) {
         float* p = base ? base + off : nullptr;
-        off += round_up(n, 64);
+        const int64_t padded = round_up(n, 64);
+        if (fill) {
+            const int64_t o = scratch ? off : off + n, len = scratch ? padded : padded - n;
+            if (len > 0) {
+                if (!fill->empty() && fill->back().first + fill->back().second == o) fill->back().second += len;
+                else fill->push_back({o, len});
+            }
+        }
+        off += padded;
         return p;
     }
 };
@@ -396,6 +415,7 @@ static void carve(exorl_agent* a, Carver& c) {
         a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM] = c.take(a->critic.total);
     }
     a->obs = c.take(B * O); a->action = c.take(B * A); a->reward = c.take(B); a->discount = c.take(B); a->next_obs = c.take(B * O);
+    c.scratch = true;       // from here on: c.scratch says whether a step writes the sub-buffer before it reads it (see Carver)
     a->xa = c.take(2 * B * O);
     auto take_u16 = [&](int64_t n) { return reinterpret_cast<unsigned short*>(c.take((n + 1) / 2)); };
     const bool x3 = planes_ok(cfg);
@@ -404,11 +424,14 @@ static void carve(exorl_agent* a, Carver& c) {
     a->fa = FwdBufs{c.take(2 * B * H), c.take(2 * B * H), c.take(2 * B), c.take(2 * B * H), c.take(2 * B * AO), bf ? take_u16(2 * B * H) : nullptr,
                     bf ? take_u16(2 * B * H) : nullptr, take_lo(2 * B * H), take_lo(2 * B * H)};
     a->ba = BwdBufs{c.take(B * H), c.take(B * H), bf ? take_u16(B * H) : nullptr, take_lo(B * H)};
+    c.scratch = false;
     a->sh_actor = NetShadow{c.take(O * H), bf ? take_u16(H * H) : nullptr, bf ? take_u16(H * round_up(O, 32)) : nullptr, take_lo(H * H),
                             take_lo(H * round_up(O, 32))};
+    c.scratch = true;
     a->pa = Partials{c.take((int64_t)head_chunks(B) * ((AO + 1) * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
                      c.take((int64_t)outer_chunks(B) * O * H)};
     a->dpre = c.take(B * AO);
+    c.scratch = false;      // statistics, metrics, step state, act()'s own scratch and ticket
     a->stats = c.take(4 + EXORL_N_METRICS);
     a->metrics = a->stats ? a->stats + 4 : nullptr;
     a->state = reinterpret_cast<StepState*>(c.take((sizeof(StepState) + 3) / 4));
@@ -420,6 +443,7 @@ static void carve(exorl_agent* a, Carver& c) {
                       nullptr, nullptr};
     if (a->has_critic) {
         const int64_t nt = a->critic.n_trunks;
+        c.scratch = true;
         a->xc_cur = c.take(B * W); a->xc_next = c.take(B * W); a->xc_pi = c.take(B * W);
         const int64_t od = a->critic.out_dim;
         a->ft = FwdBufs{c.take(nt * B * H), nullptr, nullptr, c.take(2 * B * H), c.take(2 * B * od), bf ? take_u16(nt * B * H) : nullptr, nullptr,
@@ -430,7 +454,9 @@ static void carve(exorl_agent* a, Carver& c) {
         if (cfg.kind == EXORL_AGENT_CQL) {
             a->x_all = c.take(RC * W);
             a->dq_all = c.take(2 * RC);
+            c.scratch = false;
             a->cql = reinterpret_cast<CqlScalars*>(c.take(16));
+            c.scratch = true;
         }
         a->dq = c.take(2 * B);
         if (cfg.kind == EXORL_AGENT_APS) { a->sfq = c.take(2 * B); a->sftq = c.take(2 * B); }
@@ -443,13 +469,16 @@ static void carve(exorl_agent* a, Carver& c) {
             a->fr = FwdBufs{bf ? nullptr : c.take(nt * R * H), nullptr, nullptr, c.take(2 * R * H), c.take(2 * R), bf ? take_u16(nt * R * H) : nullptr, nullptr,
                             take_lo(nt * R * H), nullptr};
         }
+        c.scratch = false;
         a->sh_critic = NetShadow{c.take(nt * W * H), bf ? take_u16(2 * H * H) : nullptr, bf ? take_u16(nt * H * round_up(W, 32)) : nullptr,
                                  take_lo(2 * H * H), take_lo(nt * H * round_up(W, 32))};
         a->sh_target = NetShadow{c.take(nt * W * H), bf ? take_u16(2 * H * H) : nullptr, bf ? take_u16(nt * H * round_up(W, 32)) : nullptr,
                                  take_lo(2 * H * H), take_lo(nt * H * round_up(W, 32))};
+        c.scratch = true;
         a->pc = Partials{c.take(2 * (int64_t)qhead_chunks(RC) * ((od + 1) * H + 32)), c.take(nt * (int64_t)trunk_chunks(RC) * 3 * H),
                          c.take(nt * (int64_t)outer_chunks(RC) * W * H)};
     }
+    c.scratch = false;
 }
 
 static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
@@ -1137,6 +1166,20 @@ int exorl_agent_noise_counter(exorl_agent_t* a, uint64_t* counter_out, void* str
     hipStream_t s = as_stream(stream);
     EXORL_CHECK_HIP(hipMemcpyAsync(counter_out, &a->state->noise_counter, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream) {
+    EXORL_REQUIRE(a, "debug_agent_poison_scratch: null handle");
+    hipStream_t s = as_stream(stream);
+    exorl_agent layout;              // a second carve over the same configuration: same offsets, nothing of `a` is touched
+    layout.cfg = a->cfg; layout.actor = a->actor; layout.critic = a->critic; layout.has_critic = a->has_critic;
+    std::vector<std::pair<int64_t, int64_t>> runs;
+    Carver c(nullptr);
+    c.fill = &runs;
+    carve(&layout, c);
+    EXORL_REQUIRE((size_t)c.off * sizeof(float) == a->ws_bytes, "debug_agent_poison_scratch: layout mismatch");
+    for (const auto& r : runs) EXORL_CHECK_HIP(hipMemsetAsync(a->ws + r.first, 0xFF, (size_t)r.second * sizeof(float), s));
     return 0;
 }
 

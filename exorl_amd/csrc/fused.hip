@@ -771,16 +771,18 @@ __global__ __launch_bounds__(256) void outer_reduce_kernel(const float* __restri
             const int nr = rows - row0 < OR_ROWS ? rows - row0 : OR_ROWS;       // <= 0 past the end: nothing staged, nothing added
             // all OR_ROWS rows of this thread's column and the staged u values are requested up front, unconditionally (row clamped; the
             // staged u of a row past the end is 0, so whatever the clamped v row holds contributes nothing): one memory round trip per
-            // sub-block instead of four guarded ones
+            // sub-block instead of four guarded ones. A sub-block wholly past the end (nr <= 0) clamps to the last row: row0 itself is
+            // then outside v and u, and 0 times whatever lies there is not 0 when it is a NaN
+            const int rclamp = nr > 0 ? row0 : rows - 1;
             float vall[OR_ROWS];
             const int cc = c < H ? c : 0;
 #pragma unroll
-            for (int r = 0; r < OR_ROWS; ++r) vall[r] = v[net * vstride + (int64_t)(row0 + (r < nr ? r : 0)) * H + cc];
+            for (int r = 0; r < OR_ROWS; ++r) vall[r] = v[net * vstride + (int64_t)(r < nr ? row0 + r : rclamp) * H + cc];
             float ust[OR_ROWS * 32 / 256];
 #pragma unroll
             for (int q = 0; q < OR_ROWS * 32 / 256; ++q) {
                 const int i = threadIdx.x + 256 * q, r = i >> 5, j = i & 31;
-                ust[q] = u[(int64_t)(row0 + (r < nr ? r : 0)) * ldu + (j0 + j < J ? j0 + j : 0)];
+                ust[q] = u[(int64_t)(r < nr ? row0 + r : rclamp) * ldu + (j0 + j < J ? j0 + j : 0)];
             }
             __syncthreads();
 #pragma unroll
@@ -1312,6 +1314,16 @@ int qhead(const QHeadArgs& q, hipStream_t s) {
 __device__ __forceinline__ float chunk_sum(const float* __restrict__ p, int n, int64_t stride) {
     float acc = 0.f;
     int ch = 0;
+    if (n > 1024) {          // thousands of partials (8192 rows and more): sub-sums of 32 added to a second accumulator. One running float32 sum
+        for (; ch + 32 <= n; ch += 32) {        // of n terms drifts by about sqrt(n) ulp of the total: 2050 qhead partials at B = 8200 left
+            float t[32], sub = 0.f;             // a bias gradient 1.1e-6 off its float64 value, where the float32 reference is 4e-8 off
+#pragma unroll
+            for (int q = 0; q < 32; ++q) t[q] = p[(int64_t)(ch + q) * stride];
+#pragma unroll
+            for (int q = 0; q < 32; ++q) sub += t[q];
+            acc += sub;
+        }
+    }
     for (; ch + 32 <= n; ch += 32) {            // 32 in flight: the 256 qhead chunks are 8 dependent rounds instead of 16 (same order of adds)
         float t[32];
 #pragma unroll

@@ -221,6 +221,11 @@ class AgentEngine(_Phased):
         L.check(self.lib.exorl_debug_philox_normal(seed, counter, out.numel(), out.data_ptr(), L.current_stream()))
         return out
 
+    def poison_scratch(self):
+        """Fills the scratch a step writes before it reads, and the padding between all sub-buffers, with NaN bit patterns (test hook:
+        the next step must not notice)."""
+        L.check(self.lib.exorl_debug_agent_poison_scratch(self.h, L.current_stream()))
+
     def set_parallel_branches(self, enable):
         L.check(self.lib.exorl_agent_set_parallel_branches(self.h, int(bool(enable))))
 

@@ -32,11 +32,12 @@
 extern "C" {
 #endif
 
-#define EXORL_ABI_VERSION 11     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
+#define EXORL_ABI_VERSION 12     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
                                     9: exorl_debug_gemm_stamps and exorl_debug_conv_stamps removed; exorl_gemm_tune keeps five bits
                                     10: exorl_pixel_cfg.world_size; exorl_pixel_agent_update_phase / _grad_buffer / _set_comm
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
-                                        _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2 */
+                                        _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
+                                    12: exorl_debug_agent_poison_scratch */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -268,6 +269,12 @@ int exorl_agent_disable_graph(exorl_agent_t* a);
  * can replay a captured-graph trajectory (device sampler + device noise) through the CPU oracle. */
 int exorl_agent_noise_counter(exorl_agent_t* a, uint64_t* counter_out, void* stream);
 int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float* out_dev, void* stream);
+/* Diagnostic only: fills with 0xFF bytes (NaN as fp32 and as bf16) every workspace sub-buffer that a step writes before it reads — the
+ * staged inputs, activations, backward buffers, per-chunk partials, per-row loss gradients and weights — and the alignment padding
+ * behind every sub-buffer. Parameters, gradients, optimiser state, weight shadows, step state, CQL scalars, batch slots, statistics,
+ * metrics and act()'s scratch keep their contents. A step after this call must give bit-identical results: anything else is a read of
+ * memory the step did not write. Enqueued on `stream`. */
+int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stand-alone operators (used by the agents above; exported for tests and for callers' own nets)

@@ -33,7 +33,7 @@ def test_library_exports_the_module_dp_entry_points():
     for s in NEW:
         assert hasattr(lib, s), f'{s} is not exported by libexorl_hip.so'
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 11
+    assert lib.exorl_abi_version() == 12
 
 
 def test_prototypes_declare_the_module_dp_entry_points():
