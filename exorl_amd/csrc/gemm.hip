@@ -1,24 +1,59 @@
-// Grouped MFMA GEMM for the 1024-wide actor/critic layers: forward (x W^T),
-// dgrad (dZ W) and wgrad (dZ^T H) of nn.Linear as used at
-//   /root/reference/agents/offline_learning/td3_bc.py:16-20,37-47 and unsupervised_learning/ddpg.py:48-62,86-108.
+// Grouped MFMA GEMMs for the hidden layers: forward (x W^T), dgrad (dZ W) and wgrad (dZ^T H) of nn.Linear, several
+// independent problems per launch. Layout 0 / "row image": element (r, k) at ptr[r * ld + k]; layout 1 / "k image": at ptr[k * ld + r].
 //
-// gfx950 design:
-//  * 64x64 output tile per 256-thread workgroup (4 waves, one 32x32 MFMA accumulator each) so a
-//    1024x1024 layer yields 256 workgroups per net — twin critics / stacked actor batches fill 256 CUs twice.
-//  * fp32 parity mode: v_mfma_f32_32x32x2_f32 (exact fp32 products, k-ordered fmaf chain);
-//    fast mode: v_mfma_f32_32x32x16_bf16 on operands rounded fp32->bf16 while staging (fp32 accumulate).
-//  * LDS tile = 64 rows x 128 B, 16-byte units XOR-swizzled by (row>>1)&7 so the ds_read_b128 fragment
-//    reads (16-lane groups on distinct rows) are bank-conflict free; one unit = 4 fp32 k's or 8 bf16 k's.
-//    The k order inside a step is permuted identically for A and B (unit 2q+h feeds lane-half h).
-//  * register-staged double buffering: global loads for tile t+1 are issued before the MFMAs of tile t
-//    and written to the other LDS buffer after them — one barrier per k-tile.
-//  * operands whose reduction index is the slow dimension (dgrad B, wgrad A and B) are transposed in
-//    registers on the way to LDS (two rows x KU k's per thread), so all three GEMM forms share one inner loop.
+// Map of the file: the kernel families, when each is taken, and who reaches it in the product.
+//
+//  fp32-source operands (gemm_grouped; the intrinsic modules in intr.hip, the pixel agents' heads and module layers in pixel_agent.hip, and the
+//  actor / critic layers of agent.hip in fp32 precision)
+//  * gemm_kernel<PREC, AL, BL, VEC>: 64 x 64 tile, register-staged double buffer, all four layout pairs, any shape (bounds-guarded; VEC = the
+//    16-byte loads where pointers and pitches allow). PREC picks the product: exact fp32 (v_mfma_f32_32x32x2_f32), bf16, split bf16 in two
+//    (bf16x3) or three (bf16x6) planes made while staging. Taken whenever planes_adapter is not.
+//  * planes_adapter: bf16x3 problems with M, N, K >= 256 in one of the three nn.Linear layout pairs, outside a stream capture. Writes zero-padded
+//    hi/lo bf16 planes of both operands into a scratch arena and hands them to gemm16_grouped, where (padded to multiples of 128) they take the
+//    gemm16p kernels: the same arithmetic at about four times the rate of gemm_kernel. The reward-free agents' updates reach it.
+//
+//  bf16 operands in memory, plain or as hi/lo planes (gemm16_grouped, gemm16_grouped_mixed; the H x H layers of every actor / critic in
+//  agent.hip in bf16 and bf16x3 precision, and planes_adapter). One ladder, pick16(), first match wins:
+//  * gemm16p_kernel / gemm16p_mixed_kernel: 128 x TN tiles, LDS-DMA stage ring, XCD-local tile blocks, float4 epilogue. Needs M % 128, N % 64,
+//    K % 128 = 0, 16-byte aligned operands, lo planes, C and bias, ldc % 4 = 0. TN = 128 when every N allows it and the launch still has 256
+//    workgroups, else 64. Every launch of the product at hidden_dim and batch multiples of 128 (the 1024-wide flagship step among them).
+//  * gemm16x3_kernel / gemm16x3_mixed_kernel (split planes), gemm16g_kernel / gemm16g_mixed_kernel (plain): 64 x 64 tiles, LDS-DMA, scalar
+//    stores. Need M, N % 64 = 0, aligned operands, and K % 64 = 0 (split) or K % 256 = 0 (plain, four-stage ring); nothing of C. E.g.
+//    split-bf16 planes at a batch that is a multiple of 64 but not of 128, or any launch whose output is not 16-byte aligned.
+//  * gemm16_kernel<AL, BL, BM, NS, GUARD>: BM x 64 tiles (BM = 128 from 256 workgroups), register-staged, bounds-guarded unless M % 128, N % 64,
+//    K % 64 = 0. Plain bf16 only, no mixed form; everything else the entry point's alignment rules admit, e.g. plain bf16 at hidden_dim 192,
+//    where K is no multiple of 256.
+//  The mixed entry (wgrad + dgrad of one backward pass in one launch) has a precondition of its own and otherwise falls back to one
+//  gemm16_grouped call per problem; see gemm16_grouped_mixed.
+//
+// Shared by all of them: 256-thread workgroups of four waves on 32 x 32 MFMA accumulators (v_mfma_f32_32x32x16_bf16, fp32 accumulate), LDS rows
+// of 16-byte units XOR-swizzled so the ds_read_b128 fragment reads are bank-conflict free, and — for operands whose reduction index is the slow
+// dimension (dgrad B, wgrad A and B) — a transpose on the way in (registers) or out (ds_read_b64_tr_b16) of LDS, so that the three GEMM forms
+// share one inner loop per family. Each family's own design notes and measurements stand in front of its kernels.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
 
 #include "kernels.h"
+
+// ---- debug state (no product path sets it), read through tune_variant() / prec_override_mask() here and in pixels.hip, agent.hip, pixel_agent.hip
+namespace exorl {
+static int g_tune_variant = 0;       // exorl_gemm_tune: the TUNE_* reference-path bits (kernels.h), each read at one decision point; 0 = defaults
+// exorl_debug_precision_override (tools/debug/config4_ablation.py): which split-bf16 products run with exact fp32 products instead.
+// bits: 1 / 2 forward (row-image A, row-image B) narrow / wide; 4 / 8 wgrad (k-image A and B); 16 / 32 dgrad (row-image A, k-image B);
+// "wide" = a problem dimension >= 8192 (the 39200-wide layers of the pixel agents); 64 / 128 / 256 = conv forward / dgrad / wgrad (pixels.hip)
+static int g_prec_override = 0;
+int tune_variant() { return g_tune_variant; }
+int prec_override_mask() { return g_prec_override; }
+}  // namespace exorl
+extern "C" int exorl_gemm_tune(int32_t variant) {
+    exorl::g_tune_variant = variant < 0 ? 0 : variant;
+    return 0;
+}
+extern "C" int exorl_debug_precision_override(int32_t mask) {
+    exorl::g_prec_override = mask;
+    return 0;
+}
 
 namespace exorl {
 
@@ -32,6 +67,31 @@ struct GemmProfile {
 };
 static GemmProfile g_prof;
 constexpr size_t PROF_MAX_LAUNCHES = 1 << 15;
+
+// The event pair around one GEMM launch: begin() before it, end() after it, both on the launch stream.
+struct ProfBracket {
+    bool on = false;
+    int begin(hipStream_t s, double flops) {
+        on = g_prof.on && g_prof.used < PROF_MAX_LAUNCHES;
+        if (!on) return 0;
+        if (g_prof.ev.size() < 2 * (g_prof.used + 1)) {
+            hipEvent_t a, b;
+            EXORL_CHECK_HIP(hipEventCreate(&a));
+            EXORL_CHECK_HIP(hipEventCreate(&b));
+            g_prof.ev.push_back(a);
+            g_prof.ev.push_back(b);
+        }
+        g_prof.flops.push_back(flops);
+        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used], s));
+        return 0;
+    }
+    int end(hipStream_t s) {
+        if (!on) return 0;
+        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
+        g_prof.used += 1;
+        return 0;
+    }
+};
 
 constexpr int GEMM_MAX_GROUP = 32;     // problems per launch of the generic kernel (split-K slabs of one layer share a launch)
 struct GemmBatch {
@@ -346,7 +406,6 @@ __device__ __forceinline__ XcdTile xcd_tile(int id, int count, int tiles_m, int 
     t.ok = slot < bm * bn;
     return t;
 }
-static int g_gemm16_variant = -1;    // exorl_gemm_tune: the TUNE_* reference-path bits (kernels.h); -1 or 0 = defaults
 
 template <int AL, int BL, int BM, int NS, bool GUARD>
 __global__ __launch_bounds__(256) void gemm16_kernel(const Gemm16Batch gb) {
@@ -668,255 +727,18 @@ __device__ __forceinline__ void gemm16g_body(const Gemm16Batch& gb, unsigned cha
     }
 }
 
-// ---- 128 x 128 workgroup tile (4 waves, each 64 x 64 = 2 x 2 MFMA sub-tiles) ------------------------------------------
-// The 64 x 64 kernel above re-reads every operand byte from LDS for 32 x 32 of output per wave: 8 KB of ds_read per 4 MFMAs,
-// twice what the CU's 128 B/clk LDS port can feed while the MFMAs run (PMC: the pipe is LDS-bound). A 64 x 64 wave tile reuses
-// each fragment twice (16 KB per 16 MFMAs: LDS and MFMA time balance) and halves the L2->LDS bytes per FLOP. An operand tile is
-// two of the 64-row images of the kernel above side by side (same swizzles, same fragment reads); 4 stages x 32 KB = 128 KB of
-// LDS, one workgroup per CU.
-constexpr int G16H_STAGE = 4 * G16G_IMG;           // A0 A1 B0 B1
-
-template <bool AT, bool BT, int NSTG, bool X3 = false>
-__device__ __forceinline__ void gemm16h_body(const Gemm16Batch& gb, unsigned char* smem) {
-    constexpr int IMG = G16G_IMG;
-    const Gemm16Problem& P = gb.p[blockIdx.z];
-    const int M = P.M, N = P.N, K = P.K;
-    const int tiles_n = N >> 7, tiles_m = M >> 7;
-    const int ntiles = tiles_n * tiles_m;
-    if ((int)blockIdx.x >= ntiles) return;
-    int tile = blockIdx.x;
-    if (gb.swizzle && (ntiles & 7) == 0) tile = (tile & 7) * (ntiles >> 3) + (tile >> 3);
-    const int m0 = (tile / tiles_n) << 7;
-    const int n0 = (tile % tiles_n) << 7;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int h = lane >> 5;
-    const int nk = K >> 6;                         // multiple of NSTG (checked by the launcher)
-
-    constexpr int STAGE = (X3 ? 8 : 4) * IMG;      // A0 A1 B0 B1 [A0l A1l B0l B1l]
-    f32x16 acc[2][2], accx[X3 ? 2 : 1][X3 ? 2 : 1];      // accx: the two cross terms hi*lo + lo*hi of the split-bf16 product, summed
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { acc[a][b][i] = 0.f; if constexpr (X3) accx[a][b][i] = 0.f; }
-
-    // DMA source pointers: for each of the 4 images this wave's two 1-KB pieces (image rows 16*wave + 8j + lane/8)
-    const unsigned short* src[X3 ? 16 : 8];
-    int64_t kstep[2];
-#pragma unroll
-    for (int img = 0; img < 2; ++img)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int rr = 16 * wave + 8 * j + (lane >> 3), p = lane & 7;
-            const int ma = m0 + 64 * img, nb = n0 + 64 * img;
-            const int64_t oa = !AT ? (int64_t)(ma + rr) * P.lda + 8 * (p ^ ((rr >> 1) & 7)) : (int64_t)rr * P.lda + ma + 8 * (p ^ (4 * ((rr >> 1) & 1)));
-            const int64_t ob = !BT ? (int64_t)(nb + rr) * P.ldb + 8 * (p ^ ((rr >> 1) & 7)) : (int64_t)rr * P.ldb + nb + 8 * (p ^ (4 * ((rr >> 1) & 1)));
-            src[2 * img + j] = P.A + oa;
-            src[4 + 2 * img + j] = P.B + ob;
-            if constexpr (X3) { src[8 + 2 * img + j] = P.A_lo + oa; src[12 + 2 * img + j] = P.B_lo + ob; }
-        }
-    kstep[0] = AT ? 64 * P.lda : 64;
-    kstep[1] = BT ? 64 * P.ldb : 64;
-    const int piece = 16 * wave * ROWB;
-
-    const int g = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-    auto tr_off = [&](int rbase) {
-        const int c = rbase + 16 * (g & 1) + 4 * pp;
-        return (8 * (g >> 1) + qq) * ROWB + (((c >> 3) ^ (4 * ((qq >> 1) & 1))) << 4) + ((c & 7) << 1);
-    };
-    int aoff[2][4], boff[2][4];                    // [sub-tile][q]: fragment offsets inside this wave's A / B image
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            aoff[t][q] = AT ? tr_off(t * 32) + q * 16 * ROWB : lds_off(t * 32 + (lane & 31), 2 * q + h);
-            boff[t][q] = BT ? tr_off(t * 32) + q * 16 * ROWB : lds_off(t * 32 + (lane & 31), 2 * q + h);
-        }
-
-    auto fill = [&](auto sc) {
-        constexpr int st = decltype(sc)::value;
-        unsigned char* base = smem + st * STAGE + piece;
-#pragma unroll
-        for (int i = 0; i < (X3 ? 8 : 4); ++i) {   // images A0 A1 B0 B1 [A0l A1l B0l B1l]
-            __builtin_amdgcn_global_load_lds((const void*)src[2 * i], (lds_void*)(base + i * IMG), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const void*)src[2 * i + 1], (lds_void*)(base + i * IMG + 8 * ROWB), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            src[i] += kstep[0]; src[4 + i] += kstep[1];
-            if constexpr (X3) { src[8 + i] += kstep[0]; src[12 + i] += kstep[1]; }
-        }
-    };
-    auto frag = [&](const unsigned char* img, bool tr, int off) -> bf16x8 {
-        if (!tr) return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(img + off));
-        const v4s16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16*)(img + off));
-        const v4s16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16*)(img + off + 4 * ROWB));
-        typedef short v8s16 __attribute__((ext_vector_type(8)));
-        const v8s16 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        return __builtin_bit_cast(bf16x8, v);
-    };
-    auto step = [&](auto sc, int t) {
-        constexpr int st = decltype(sc)::value;
-        // tile t has landed once at most the fills of the two younger tiles remain outstanding (8 DMA pieces per tile per wave)
-        const int younger = nk - 1 - t;            // NSTG - 2 younger tiles may still be in flight
-        static_assert(!X3 || NSTG == 2, "split-bf16 128 x 128 tiles: 2 stages of 64 KB");
-        if (NSTG >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (NSTG >= 3 && younger >= 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (t + NSTG - 1 < nk) fill(std::integral_constant<int, (st + NSTG - 1) % NSTG>{});
-        const unsigned char* As = smem + st * STAGE + wm * IMG;
-        const unsigned char* Bs = smem + st * STAGE + (2 + wn) * IMG;
-        if constexpr (X3) {                        // one q (k16) at a time: 8 fragments live instead of 32
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    ah[u] = frag(As, AT, aoff[u][q]);
-                    bh[u] = frag(Bs, BT, boff[u][q]);
-                    al[u] = frag(As + 4 * IMG, AT, aoff[u][q]);
-                    bl[u] = frag(Bs + 4 * IMG, BT, boff[u][q]);
-                }
-#pragma unroll
-                for (int ua = 0; ua < 2; ++ua)
-#pragma unroll
-                    for (int ub = 0; ub < 2; ++ub) {
-                        acc[ua][ub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ua], bh[ub], acc[ua][ub], 0, 0, 0);
-                        accx[ua][ub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ua], bl[ub], accx[ua][ub], 0, 0, 0);
-                        accx[ua][ub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ua], bh[ub], accx[ua][ub], 0, 0, 0);
-                    }
-            }
-            return;
-        }
-        bf16x8 af[2][4], bfr[2][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {              // q-major: the first MFMAs only wait for the first reads
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                af[u][q] = frag(As, AT, aoff[u][q]);
-                bfr[u][q] = frag(Bs, BT, boff[u][q]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][q], bfr[0][q], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][q], bfr[1][q], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][q], bfr[0][q], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][q], bfr[1][q], acc[1][1], 0, 0, 0);
-        }
-    };
-
-    fill(std::integral_constant<int, 0>{});
-    if constexpr (NSTG >= 3) fill(std::integral_constant<int, 1>{});
-    if constexpr (NSTG >= 4) fill(std::integral_constant<int, 2>{});
-    for (int t = 0; t < nk; t += NSTG) {
-        step(std::integral_constant<int, 0>{}, t);
-        step(std::integral_constant<int, 1>{}, t + 1);
-        if constexpr (NSTG >= 4) {
-            step(std::integral_constant<int, 2>{}, t + 2);
-            step(std::integral_constant<int, 3>{}, t + 3);
-        }
-    }
-
-    const bool relu = gb.relu != 0;
-#pragma unroll
-    for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-        for (int tb = 0; tb < 2; ++tb) {
-            const int n = n0 + wn * 64 + tb * 32 + (lane & 31);
-            const float bias = P.bias ? P.bias[n] : 0.f;
-            float* crow = P.C + (int64_t)(m0 + wm * 64 + ta * 32 + 4 * h) * P.ldc + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float* dst = crow + (int64_t)((r & 3) + 8 * (r >> 2)) * P.ldc;
-                float v = (X3 ? accx[ta][tb][r] + acc[ta][tb][r] : acc[ta][tb][r]) + bias;
-                if (relu) v = fmaxf(v, 0.f);
-                *dst = gb.accumulate ? v + *dst : v;
-            }
-        }
-}
-
-template <bool AT, bool BT>
-__global__ __launch_bounds__(256) void gemm16h_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
-    gemm16h_body<AT, BT, G16G_NSTG>(gb, smem_h);
-}
-
-__global__ __launch_bounds__(256) void gemm16h_mixed_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
-    if (gb.a_t[blockIdx.z]) gemm16h_body<true, true, G16G_NSTG>(gb, smem_h);
-    else gemm16h_body<false, true, G16G_NSTG>(gb, smem_h);
-}
-
-template <bool AT, bool BT>
-__global__ __launch_bounds__(256) void gemm16hx3_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
-    gemm16h_body<AT, BT, 2, true>(gb, smem_h);
-}
-__global__ __launch_bounds__(256) void gemm16hx3_mixed_kernel(const Gemm16Batch gb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
-    if (gb.a_t[blockIdx.z]) gemm16h_body<true, true, 2, true>(gb, smem_h);
-    else gemm16h_body<false, true, 2, true>(gb, smem_h);
-}
-constexpr int G16HX3_LDS = 2 * 8 * G16G_IMG;       // 128 KB: one workgroup per CU
-static int g16hx3_enable() {
-    static bool done = false;
-    if (done) return 0;
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16hx3_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, G16HX3_LDS));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16hx3_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G16HX3_LDS));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16hx3_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G16HX3_LDS));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16hx3_mixed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G16HX3_LDS));
-    done = true;
-    return 0;
-}
-// 128 x 128 tiles pay off when they still fill the chip: 4-problem launches of 1024^2 outputs are 256 workgroups
-static bool g16hx3_fits(const Gemm16Batch& gb, int count) {
-    int tiles = 0;
-    for (int i = 0; i < count; ++i) {
-        if (gb.p[i].M % 128 != 0 || gb.p[i].N % 128 != 0 || gb.p[i].K % 128 != 0) return false;
-        tiles += (gb.p[i].M >> 7) * (gb.p[i].N >> 7);
-    }
-    return tiles >= 256;
-}
-constexpr size_t G16H_LDS = (size_t)G16G_NSTG * G16H_STAGE;      // 128 KB
-static int g16h_enable() {          // > 64 KB of dynamic LDS needs the opt-in, once per kernel
-    static bool done = false;
-    if (done) return 0;
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
-    EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)gemm16h_mixed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G16H_LDS));
-    done = true;
-    return 0;
-}
-static bool g16h_fits(const Gemm16Batch& gb, int count) {
-    // measured slower than the 64 x 64 tiles on the 1024-wide layers (15-17 us vs 9-12 us per problem: one workgroup per CU leaves
-    // the k-tile chain wait -> barrier -> DMA issue -> LDS reads -> MFMA exposed): only where 128 x 128 tiles still give every CU a
-    // workgroup (the 4-problem launches)
-    int tiles = 0;
-    for (int i = 0; i < count; ++i) {
-        if (gb.p[i].M % 128 != 0 || gb.p[i].N % 128 != 0) return false;
-        tiles += (gb.p[i].M >> 7) * (gb.p[i].N >> 7);
-    }
-    return tiles >= 256;
-}
-
 // ---- "p" kernels: 128 x TN workgroup tile (TN = 128 or 64), k32 stages, 4-deep LDS-DMA ring, XCD-local tile blocks -----------
+// Why a wave owns 64 x TN/2 of output here: the 64 x 64 kernel above re-reads every operand byte from LDS for 32 x 32 of output per wave, 8 KB
+// of ds_read per 4 MFMAs, twice what the CU's 128 B/clk LDS port can feed while the MFMAs run (PMC: the pipe is LDS-bound). A 64 x 64 wave
+// tile reuses each fragment twice (16 KB per 16 MFMAs: LDS and MFMA time balance) and halves the L2->LDS bytes per FLOP.
 // What round 2's measurements changed (tools/micro/fill_bench.hip): a CU pulls ~115 GB/s from its XCD's L2 on EVERY path (LDS-DMA,
 // registers, both) but only 30-40 GB/s from the Infinity Cache, so the ~75 GB/s the kernels above sustain is an L2 miss rate, not a
 // DMA limit: with tiles dealt in id order an XCD walks one tile-row of every problem and re-fetches each B strip once per tile.
 // Here (a) workgroup id -> tile goes through xcd_tile(): the 32 workgroups of an XCD (one per CU, all resident) form a compact block
 // of ONE problem's output (512 x 512 or 512 x 1024), so every operand strip an XCD touches is fetched once and reused 4-8 times while
 // the CUs walk k together; (b) the stage is 32 k wide (32 KB for a split-bf16 128 x 128 tile), four stages deep: two to three
-// stages are always in flight, which a single workgroup per CU needs to cover the DMA latency (the 2 x 64 KB ring above could keep
-// only one); (c) the k-loop is software-pipelined across the barrier: the fragments of the next k16 are read while the MFMAs of the
+// stages are always in flight, which a single workgroup per CU needs to cover the DMA latency (the 2 x 64 KB ring of the round-1
+// 128 x 128 kernels, since removed, could keep only one); (c) the k-loop is software-pipelined across the barrier: the fragments of the next k16 are read while the MFMAs of the
 // current one issue, the barrier that certifies stage t+1 sits in the middle of step t.
 // LDS images per 64-row block and stage (4 KB): "row image" [64 rows][32 k] with 64-byte rows, 16-byte units swizzled by
 // (row >> 2) & 3 (the 16 lanes of a ds_read_b128 group then hit 16 distinct bank quads); "k image" [32 k][64 rows] = the first half
@@ -1269,21 +1091,6 @@ __global__ __launch_bounds__(256) void gemm16p_mixed_kernel(const Gemm16Batch gb
 }
 constexpr int g16p_lds(bool x3, int tn, int ks = 32, int nstg = 4) { return nstg * (x3 ? 2 : 1) * (2 + tn / 64) * 64 * 2 * ks; }
 
-// Tile width for a launch (0 = these kernels do not apply): 128 x 128 when that still gives every CU a workgroup, else 128 x 64.
-static int g16p_pick(const Gemm16Batch& gb, int count, bool x3) {
-    int t128 = 0;
-    for (int i = 0; i < count; ++i) {
-        const Gemm16Problem& p = gb.p[i];
-        const bool al = p.lda % 8 == 0 && p.ldb % 8 == 0 && reinterpret_cast<uintptr_t>(p.A) % 16 == 0 && reinterpret_cast<uintptr_t>(p.B) % 16 == 0 &&
-                        (!x3 || (p.A_lo && p.B_lo && reinterpret_cast<uintptr_t>(p.A_lo) % 16 == 0 && reinterpret_cast<uintptr_t>(p.B_lo) % 16 == 0));
-        const bool cal = p.ldc % 4 == 0 && reinterpret_cast<uintptr_t>(p.C) % 16 == 0 && reinterpret_cast<uintptr_t>(p.bias) % 16 == 0;     // float4 epilogue
-        if (!al || !cal || p.M % 128 != 0 || p.N % 64 != 0 || p.K % 128 != 0 || p.K < 128) return 0;
-        t128 += p.N % 128 == 0 ? (p.M >> 7) * (p.N >> 7) : 0;
-    }
-    bool n128 = true;
-    for (int i = 0; i < count; ++i) n128 = n128 && gb.p[i].N % 128 == 0;
-    return (n128 && t128 >= 256) ? 128 : 64;
-}
 static bool g16p_uniform(const Gemm16Batch& gb, int count, int tn) {       // xcd_tile()'s preconditions
     if (!(count == 1 || count == 2 || count == 4)) return false;
     const int X = 8 / count, sm = X == 8 ? 4 : 2, sn = X == 2 ? 1 : 2;
@@ -1306,7 +1113,6 @@ static int g16p_launch(K kernel, Gemm16Batch& gb, int count, bool x3, int tn, hi
     int tmax = 0, ttot = 0;
     for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N / tn); tmax = t > tmax ? t : tmax; ttot += t; }
     hipLaunchKernelGGL(kernel, gb.xcd_map ? dim3(ttot, 1, 1) : dim3(tmax, 1, count), dim3(256), lds, s, gb);
-    EXORL_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1337,176 +1143,128 @@ __global__ __launch_bounds__(256) void gemm16g_mixed_kernel(const Gemm16Batch gb
     else gemm16g_body<false, true>(gb, smem);
 }
 
-template <int AL, int BL>
-static int launch16(const Gemm16Batch& gb, int count, int tiles64, int tiles128, hipStream_t s) {
-    const bool prof = g_prof.on && g_prof.used < PROF_MAX_LAUNCHES;
-    if (prof) {
-        if (g_prof.ev.size() < 2 * (g_prof.used + 1)) {
-            hipEvent_t a, b;
-            EXORL_CHECK_HIP(hipEventCreate(&a));
-            EXORL_CHECK_HIP(hipEventCreate(&b));
-            g_prof.ev.push_back(a);
-            g_prof.ev.push_back(b);
-        }
-        double f = 0;
-        for (int i = 0; i < count; ++i) f += 2.0 * gb.p[i].M * (double)gb.p[i].N * gb.p[i].K;
-        g_prof.flops.push_back(f);
-        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used], s));
+// ---- which bf16 kernel serves a launch (the map at the head of this file, as code) ---------------------------------------------------
+// Every entry point gathers the same facts about its problems in one pass (gather16), asks the one ladder (pick16) for a kernel family,
+// and launches the instantiation of that family for its operand form (launch16).
+enum class Form { row_row, row_k, k_k, mixed };      // (A, B) images; mixed: A per problem (Gemm16Batch::a_t), B a k image
+enum class Family { p, x3, g, reg, none };           // none: split-bf16 planes that no kernel can read (missing, misaligned, M/N/K not of 64)
+
+struct Facts16 {
+    int m_div = 256, n_div = 256, k_div = 256;       // largest power of two, up to 256, that divides every problem's M / N / K
+    int k_min = 1 << 30;
+    bool ab16 = true;        // A, B 16-byte aligned with pitches that are multiples of 8 bf16: what every LDS-DMA kernel asks of its operands
+    bool has_lo = false;     // some problem carries a lo plane: a split-bf16 launch
+    bool lo16 = true;        // every problem carries both lo planes, 16-byte aligned
+    bool c16 = true;         // C and bias 16-byte aligned, ldc a multiple of 4 floats: the float4 epilogue of the p kernels
+    int t64 = 0, t128x64 = 0;      // most 64 x 64 / 128 x 64 tiles (partial ones included) any one problem has: grid.x of the 64-wide kernels
+    int t128 = 0;            // 128 x 128 tiles of the whole launch
+    double flops = 0;
+};
+static int pow2_div(int v) { const int d = v & -v; return d == 0 || d > 256 ? 256 : d; }
+
+static Facts16 gather16(const Gemm16Problem* probs, int count, Gemm16Batch& gb) {      // also fills gb.p
+    Facts16 f;
+    auto al16 = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; };
+    for (int i = 0; i < count; ++i) {
+        const Gemm16Problem& p = gb.p[i] = probs[i];
+        f.m_div = std::min(f.m_div, pow2_div(p.M));
+        f.n_div = std::min(f.n_div, pow2_div(p.N));
+        f.k_div = std::min(f.k_div, pow2_div(p.K));
+        f.k_min = std::min(f.k_min, p.K);
+        f.ab16 = f.ab16 && p.lda % 8 == 0 && p.ldb % 8 == 0 && al16(p.A) && al16(p.B);
+        f.has_lo = f.has_lo || p.A_lo || p.B_lo;
+        f.lo16 = f.lo16 && p.A_lo && p.B_lo && al16(p.A_lo) && al16(p.B_lo);
+        f.c16 = f.c16 && p.ldc % 4 == 0 && al16(p.C) && al16(p.bias);
+        f.t64 = std::max(f.t64, cdiv(p.M, 64) * cdiv(p.N, 64));
+        f.t128x64 = std::max(f.t128x64, cdiv(p.M, 128) * cdiv(p.N, 64));
+        f.t128 += (p.M >> 7) * (p.N >> 7);
+        f.flops += 2.0 * p.M * (double)p.N * p.K;
     }
-    const bool big = tiles128 * count >= 256;
-    Gemm16Batch g2 = gb;
-    g2.swizzle = 1;
-    bool exact = true;      // every problem tiles exactly: loads need no bounds guards
-    for (int i = 0; i < count; ++i)
-        exact = exact && gb.p[i].M % 128 == 0 && gb.p[i].N % 64 == 0 && gb.p[i].K % 64 == 0;
-    bool exact64 = true;
-    for (int i = 0; i < count; ++i)
-        exact64 = exact64 && gb.p[i].M % 64 == 0 && gb.p[i].N % 64 == 0 && gb.p[i].K % 256 == 0 && gb.p[i].lda % 8 == 0 &&
-                  gb.p[i].ldb % 8 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].A) % 16 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].B) % 16 == 0;
-    bool x3 = false;
-    for (int i = 0; i < count; ++i) x3 = x3 || gb.p[i].A_lo || gb.p[i].B_lo;
-    if (const int tn = g16p_pick(g2, count, x3)) {          // 128 x TN tiles, k32 stages, XCD-local blocks (see gemm16p_body)
-        if (x3 && AL == 0 && BL == 0) {
-            // both operands row images (the forward launches): 64-wide stages, two deep — whole cache lines per DMA row instead of halves, which
-            // halves the requests the XCD L2s serve (critic fwd 21.8 -> 19.5 us, actor fwd 21.1 -> 18.9, critic+target fwd 33.7 -> 32.4)
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 128, 64, 2>, g2, count, true, 128, s, 64, 2));
-            else EXORL_TRY(g16p_launch(gemm16p_kernel<false, false, true, 64, 64, 2>, g2, count, true, 64, s, 64, 2));
-        } else if (x3) {
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 128>, g2, count, true, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, true, 64>, g2, count, true, 64, s));
-        } else {
-            // plain bf16 planes take the two-region refill as well (round 3). Round 2 kept them on a one-region refill because the k-image B operand
-            // came out wrong, run-to-run different, under the two-region one: that was the pre-fence register copy described in region() — a
-            // compiler-placed v_mov of an asm-issued LDS read's destination — not the schedule (tests/test_gpu_ops.py::test_gemm_plain_bf16_k_image_regression).
-            if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, false, 128>, g2, count, false, 128, s));
-            else EXORL_TRY(g16p_launch(gemm16p_kernel<AL != 0, BL != 0, false, 64>, g2, count, false, 64, s));
-        }
-    } else if (x3) {
-        bool okx = true;
-        for (int i = 0; i < count; ++i)
-            okx = okx && gb.p[i].A_lo && gb.p[i].B_lo && gb.p[i].M % 64 == 0 && gb.p[i].N % 64 == 0 && gb.p[i].K % 64 == 0 && gb.p[i].lda % 8 == 0 &&
-                  gb.p[i].ldb % 8 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].A_lo) % 16 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].B_lo) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(gb.p[i].A) % 16 == 0 && reinterpret_cast<uintptr_t>(gb.p[i].B) % 16 == 0;
-        EXORL_REQUIRE(okx, "gemm16_grouped: split-bf16 operands need M, N, K multiples of 64 and 16-byte aligned hi/lo planes");
-        if (g16hx3_fits(g2, count)) {
-            EXORL_TRY(g16hx3_enable());
-            int t128 = 0;
-            for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-            hipLaunchKernelGGL((gemm16hx3_kernel<AL != 0, BL != 0>), dim3(t128, 1, count), dim3(256), G16HX3_LDS, s, g2);
-        } else hipLaunchKernelGGL((gemm16x3_kernel<AL != 0, BL != 0>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
-        EXORL_LAUNCH_CHECK();
-    } else if (exact64) {         // LDS-DMA pipeline
-        if (g16h_fits(g2, count)) {
-            EXORL_TRY(g16h_enable());
-            int t128 = 0;
-            for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-            hipLaunchKernelGGL((gemm16h_kernel<AL != 0, BL != 0>), dim3(t128, 1, count), dim3(256), G16H_LDS, s, g2);
-        } else hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
-        EXORL_LAUNCH_CHECK();
-    } else {
-        // register-staged: three register stages where every problem tiles exactly, else two with bounds guards
-        if (exact && big) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 128, 3, false>), dim3(tiles128, 1, count), dim3(256), 0, s, g2);
-        else if (exact) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 64, 3, false>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
-        else if (big) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 128, 2, true>), dim3(tiles128, 1, count), dim3(256), 0, s, g2);
-        else hipLaunchKernelGGL((gemm16_kernel<AL, BL, 64, 2, true>), dim3(tiles64, 1, count), dim3(256), 0, s, g2);
-        EXORL_LAUNCH_CHECK();
-    }
-    if (prof) {
-        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
-        g_prof.used += 1;
-    }
-    return 0;
+    return f;
 }
 
-// probs[i] with a_layouts[i] in {0,1}, b_layout 1 for all, no bias/relu/accumulate. Falls back to one launch per layout when a
-// problem does not meet the LDS-DMA kernel's tiling rules.
-int gemm16_grouped_mixed(const int* a_layouts, const Gemm16Problem* probs, int count, hipStream_t s) {
-    EXORL_REQUIRE(count >= 1 && count <= 4, "gemm16_grouped_mixed: count %d out of range", count);
-    Gemm16Batch gb;
-    memset(&gb, 0, sizeof(gb));
-    bool ok = true;
-    int t64 = 0;
-    double flops = 0;
-    for (int i = 0; i < count; ++i) {
-        const Gemm16Problem& p = probs[i];
-        gb.p[i] = p;
-        gb.a_t[i] = a_layouts[i] != 0;
-        ok = ok && p.M > 0 && p.M % 64 == 0 && p.N % 64 == 0 && p.K % 256 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && !p.bias &&
-             reinterpret_cast<uintptr_t>(p.A) % 16 == 0 && reinterpret_cast<uintptr_t>(p.B) % 16 == 0;
-        const int a64 = cdiv(p.M, 64) * cdiv(p.N, 64);
-        t64 = a64 > t64 ? a64 : t64;
-        flops += 2.0 * p.M * (double)p.N * p.K;
-    }
-    bool x3 = false;
-    for (int i = 0; i < count; ++i) x3 = x3 || probs[i].A_lo;
-    if (!ok || (x3 && count > 0 && !probs[0].B_lo)) {
-        for (int i = 0; i < count; ++i) EXORL_TRY(gemm16_grouped(a_layouts[i], 1, probs + i, 1, false, false, s));
-        return 0;
-    }
+// The ladder. The operand form never changes the family, only which instantiation of it launch16 takes.
+struct Pick16 { Family family; int tn; };            // tn: tile width of the p kernels
+static Pick16 pick16(const Facts16& f) {
+    // 128 x TN tiles on the k32 / k64 stage rings: whole 128-row tiles, K a whole number of rings, float4 stores.
+    // TN = 128 only when that still gives every CU a workgroup (4-problem launches of 1024^2 outputs are 256 of them): with fewer, one
+    // workgroup per CU leaves the k-tile chain wait -> barrier -> DMA issue -> LDS reads -> MFMA exposed and 128-wide tiles measured slower
+    // than narrower ones on the 1024-wide layers (profiles/r02_gemm_shapes_old_vs_new.txt, "128x128 everywhere").
+    if (f.ab16 && (!f.has_lo || f.lo16) && f.c16 && f.m_div >= 128 && f.n_div >= 64 && f.k_div >= 128 && f.k_min >= 128)
+        return {Family::p, f.n_div >= 128 && f.t128 >= 256 ? 128 : 64};
+    // 64 x 64 LDS-DMA tiles, scalar epilogue stores (nothing asked of C): split planes two stages deep, plain ones four (K a multiple of 4 x 64)
+    if (f.has_lo) return {f.ab16 && f.lo16 && f.m_div >= 64 && f.n_div >= 64 && f.k_div >= 64 ? Family::x3 : Family::none, 0};
+    if (f.ab16 && f.m_div >= 64 && f.n_div >= 64 && f.k_div >= 256) return {Family::g, 0};
+    return {Family::reg, 0};                         // register-staged, any shape the entry point's alignment rules admit
+}
+
+template <Form F, bool X3, int TN>
+static int launch16p(Gemm16Batch& gb, int count, hipStream_t s) {
+    if constexpr (F == Form::mixed) return g16p_launch(gemm16p_mixed_kernel<X3, TN>, gb, count, X3, TN, s);
+    // split planes, both operands row images (the forward launches): 64-wide stages, two deep — whole cache lines per DMA row instead of halves, which
+    // halves the requests the XCD L2s serve (critic fwd 21.8 -> 19.5 us, actor fwd 21.1 -> 18.9, critic+target fwd 33.7 -> 32.4)
+    else if constexpr (F == Form::row_row && X3) return g16p_launch(gemm16p_kernel<false, false, true, TN, 64, 2>, gb, count, true, TN, s, 64, 2);
+    // plain bf16 planes take the two-region refill as well (round 3). Round 2 kept them on a one-region refill because the k-image B operand
+    // came out wrong, run-to-run different, under the two-region one: that was the pre-fence register copy described in region() — a
+    // compiler-placed v_mov of an asm-issued LDS read's destination — not the schedule (tests/test_gpu_ops.py::test_gemm_plain_bf16_k_image_regression).
+    else return g16p_launch(gemm16p_kernel<F == Form::k_k, F != Form::row_row, X3, TN>, gb, count, X3, TN, s);
+}
+
+template <Form F>
+static int launch16(Gemm16Batch& gb, int count, const Facts16& f, Pick16 pk, hipStream_t s) {
+    constexpr bool MIXED = F == Form::mixed;
+    constexpr int AL = F == Form::k_k, BL = F != Form::row_row;      // the uniform forms' layouts
     gb.swizzle = 1;
-    const bool prof = g_prof.on && g_prof.used < PROF_MAX_LAUNCHES;
-    if (prof) {
-        if (g_prof.ev.size() < 2 * (g_prof.used + 1)) {
-            hipEvent_t a, b;
-            EXORL_CHECK_HIP(hipEventCreate(&a));
-            EXORL_CHECK_HIP(hipEventCreate(&b));
-            g_prof.ev.push_back(a);
-            g_prof.ev.push_back(b);
+    const dim3 grid64(f.t64, 1, count), grid128(f.t128x64, 1, count), block(256);
+    ProfBracket prof;
+    EXORL_TRY(prof.begin(s, f.flops));
+    switch (pk.family) {
+    case Family::p:
+        if (f.has_lo) EXORL_TRY((pk.tn == 128 ? launch16p<F, true, 128>(gb, count, s) : launch16p<F, true, 64>(gb, count, s)));
+        else EXORL_TRY((pk.tn == 128 ? launch16p<F, false, 128>(gb, count, s) : launch16p<F, false, 64>(gb, count, s)));
+        break;
+    case Family::x3:
+        if constexpr (MIXED) hipLaunchKernelGGL(gemm16x3_mixed_kernel, grid64, block, 0, s, gb);
+        else hipLaunchKernelGGL((gemm16x3_kernel<AL != 0, BL != 0>), grid64, block, 0, s, gb);
+        break;
+    case Family::g:
+        if constexpr (MIXED) hipLaunchKernelGGL(gemm16g_mixed_kernel, grid64, block, 0, s, gb);
+        else hipLaunchKernelGGL((gemm16g_kernel<AL != 0, BL != 0>), grid64, block, 0, s, gb);
+        break;
+    case Family::reg:
+        if constexpr (!MIXED) {      // no mixed form (gemm16_grouped_mixed refuses)
+            // three register stages where every problem tiles exactly, else two with bounds guards; 128-row tiles from 256 workgroups
+            const bool exact = f.m_div >= 128 && f.n_div >= 64 && f.k_div >= 64, big = f.t128x64 * count >= 256;
+            if (exact && big) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 128, 3, false>), grid128, block, 0, s, gb);
+            else if (exact) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 64, 3, false>), grid64, block, 0, s, gb);
+            else if (big) hipLaunchKernelGGL((gemm16_kernel<AL, BL, 128, 2, true>), grid128, block, 0, s, gb);
+            else hipLaunchKernelGGL((gemm16_kernel<AL, BL, 64, 2, true>), grid64, block, 0, s, gb);
         }
-        g_prof.flops.push_back(flops);
-        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used], s));
-    }
-    if (const int tn = g16p_pick(gb, count, x3)) {
-        if (x3 && tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 128>, gb, count, true, 128, s));
-        else if (x3) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<true, 64>, gb, count, true, 64, s));
-        else if (tn == 128) EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 128>, gb, count, false, 128, s));
-        else EXORL_TRY(g16p_launch(gemm16p_mixed_kernel<false, 64>, gb, count, false, 64, s));
-    } else if (x3) {
-        if (g16hx3_fits(gb, count)) {
-            EXORL_TRY(g16hx3_enable());
-            int t128 = 0;
-            for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-            hipLaunchKernelGGL(gemm16hx3_mixed_kernel, dim3(t128, 1, count), dim3(256), G16HX3_LDS, s, gb);
-        } else hipLaunchKernelGGL(gemm16x3_mixed_kernel, dim3(t64, 1, count), dim3(256), 0, s, gb);
-    } else if (g16h_fits(gb, count)) {
-        EXORL_TRY(g16h_enable());
-        int t128 = 0;
-        for (int i = 0; i < count; ++i) { const int t = (gb.p[i].M >> 7) * (gb.p[i].N >> 7); t128 = t > t128 ? t : t128; }
-        hipLaunchKernelGGL(gemm16h_mixed_kernel, dim3(t128, 1, count), dim3(256), G16H_LDS, s, gb);
-    } else {
-        hipLaunchKernelGGL(gemm16g_mixed_kernel, dim3(t64, 1, count), dim3(256), 0, s, gb);
+        break;
+    case Family::none: break;        // refused by both entry points
     }
     EXORL_LAUNCH_CHECK();
-    if (prof) {
-        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
-        g_prof.used += 1;
-    }
-    return 0;
+    return prof.end(s);
 }
 
-// bf16-in-memory operands, fp32 output. Requirements (checked): 16-byte aligned rows for layout 0 (ld % 8 == 0,
-// K % 8 == 0), 4-byte aligned pairs for layout 1 (ld % 2 == 0, R % 2 == 0).
+// How many head_part slots per row a folded-head forward launch of these problems writes; 0 = the launch would not take the p kernels.
 int gemm16_head_slots(const Gemm16Problem* probs, int count) {
     if (count < 1 || count > 4) return 0;
     Gemm16Batch gb;
     memset(&gb, 0, sizeof(gb));
-    bool x3 = true;
-    for (int i = 0; i < count; ++i) { gb.p[i] = probs[i]; x3 = x3 && probs[i].A_lo && probs[i].B_lo; }
-    const int tn = g16p_pick(gb, count, x3);
-    if (!tn) return 0;
+    const Pick16 pk = pick16(gather16(probs, count, gb));
+    if (pk.family != Family::p) return 0;
     for (int i = 0; i < count; ++i)
         if (probs[i].N != probs[0].N) return 0;
-    return probs[0].N / (tn / 2);               // four waves: 2 x 2, each TN / 2 columns wide
+    return probs[0].N / (pk.tn / 2);            // four waves: 2 x 2, each TN / 2 columns wide
 }
 
+// bf16-in-memory operands, fp32 output. Requirements (checked): 16-byte aligned rows for layout 0 (ld % 8 == 0,
+// K % 8 == 0), 4-byte aligned pairs for layout 1 (ld % 2 == 0, R % 2 == 0).
 int gemm16_grouped(int a_layout, int b_layout, const Gemm16Problem* probs, int count, bool relu, bool accumulate, hipStream_t s) {
     EXORL_REQUIRE(count >= 1 && count <= 4, "gemm16_grouped: count %d out of range", count);
-    Gemm16Batch gb;
-    memset(&gb, 0, sizeof(gb));
-    int t64 = 0, t128 = 0;
     for (int i = 0; i < count; ++i) {
         const Gemm16Problem& p = probs[i];
-        gb.p[i] = p;
         EXORL_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm16_grouped: empty problem %d", i);
         auto ok = [](const unsigned short* ptr, int64_t ld, int R, int K, int layout) {
             const uintptr_t a = reinterpret_cast<uintptr_t>(ptr);
@@ -1516,40 +1274,56 @@ int gemm16_grouped(int a_layout, int b_layout, const Gemm16Problem* probs, int c
         EXORL_REQUIRE(ok(p.A, p.lda, p.M, p.K, a_layout) && ok(p.B, p.ldb, p.N, p.K, b_layout),
                       "gemm16_grouped: problem %d (M=%d N=%d K=%d lda=%lld ldb=%lld) violates the bf16 path's alignment rules "
                       "(hidden_dim and batch must be multiples of 8 in bf16 precision)", i, p.M, p.N, p.K, (long long)p.lda, (long long)p.ldb);
-        const int a64 = cdiv(p.M, 64) * cdiv(p.N, 64), a128 = cdiv(p.M, 128) * cdiv(p.N, 64);
-        t64 = a64 > t64 ? a64 : t64;
-        t128 = a128 > t128 ? a128 : t128;
     }
+    Gemm16Batch gb;
+    memset(&gb, 0, sizeof(gb));
+    const Facts16 f = gather16(probs, count, gb);
+    const Pick16 pk = pick16(f);
     gb.relu = relu ? 1 : 0;
     gb.accumulate = accumulate ? 1 : 0;
     for (int i = 0; i < count; ++i)
         if (probs[i].head_part)
             EXORL_REQUIRE(probs[i].head_w && a_layout == 0 && b_layout == 0 && !accumulate && gemm16_head_slots(probs, count) > 0,
                           "gemm16_grouped: a folded head needs a forward launch on the 128 x TN kernels (ask gemm16_head_slots first)");
-    if (a_layout == 0 && b_layout == 0) return launch16<0, 0>(gb, count, t64, t128, s);
-    if (a_layout == 0 && b_layout == 1) return launch16<0, 1>(gb, count, t64, t128, s);
-    if (a_layout == 1 && b_layout == 1) return launch16<1, 1>(gb, count, t64, t128, s);
+    EXORL_REQUIRE(pk.family != Family::none, "gemm16_grouped: split-bf16 operands need M, N, K multiples of 64 and 16-byte aligned hi/lo planes");
+    if (a_layout == 0 && b_layout == 0) return launch16<Form::row_row>(gb, count, f, pk, s);
+    if (a_layout == 0 && b_layout == 1) return launch16<Form::row_k>(gb, count, f, pk, s);
+    if (a_layout == 1 && b_layout == 1) return launch16<Form::k_k>(gb, count, f, pk, s);
     set_error("gemm16_grouped: unsupported layout combination %d %d", a_layout, b_layout);
     return 2;
+}
+
+// probs[i] with a_layouts[i] in {0,1}, b_layout 1 for all, no bias/relu/accumulate. Falls back to one launch per layout when a
+// problem does not meet the 64 x 64 LDS-DMA kernel's tiling rules.
+// That precondition is stricter than the ladder needs: K % 256 is gemm16g's four-stage ring, while the p kernels, which take every
+// launch the product makes here, want only K % 128. It is left as it is: lifting it would turn the two launches of a backward pass at a
+// batch that is an odd multiple of 128 (the wgrad's K) into one — a change of launch counts, to be measured on its own.
+int gemm16_grouped_mixed(const int* a_layouts, const Gemm16Problem* probs, int count, hipStream_t s) {
+    EXORL_REQUIRE(count >= 1 && count <= 4, "gemm16_grouped_mixed: count %d out of range", count);
+    Gemm16Batch gb;
+    memset(&gb, 0, sizeof(gb));
+    const Facts16 f = gather16(probs, count, gb);
+    const Pick16 pk = pick16(f);
+    bool ok = f.ab16 && f.m_div >= 64 && f.n_div >= 64 && f.k_div >= 256 && pk.family != Family::none;
+    for (int i = 0; i < count; ++i) {
+        gb.a_t[i] = a_layouts[i] != 0;
+        ok = ok && probs[i].M > 0 && !probs[i].bias;
+    }
+    if (!ok) {
+        for (int i = 0; i < count; ++i) EXORL_TRY(gemm16_grouped(a_layouts[i], 1, probs + i, 1, false, false, s));
+        return 0;
+    }
+    EXORL_REQUIRE(pk.family != Family::reg, "gemm16_grouped_mixed: the register-staged kernel has no mixed form");
+    return launch16<Form::mixed>(gb, count, f, pk, s);
 }
 
 template <int PREC, int AL, int BL>
 static int launch_layout(const GemmBatch& gb, int count, int max_tiles, bool vec, hipStream_t s) {
     dim3 grid(max_tiles, 1, count), block(256);
-    const bool prof = g_prof.on && g_prof.used < PROF_MAX_LAUNCHES;
-    if (prof) {
-        if (g_prof.ev.size() < 2 * (g_prof.used + 1)) {
-            hipEvent_t a, b;
-            EXORL_CHECK_HIP(hipEventCreate(&a));
-            EXORL_CHECK_HIP(hipEventCreate(&b));
-            g_prof.ev.push_back(a);
-            g_prof.ev.push_back(b);
-        }
-        double f = 0;
-        for (int i = 0; i < count; ++i) f += 2.0 * gb.p[i].M * (double)gb.p[i].N * gb.p[i].K;
-        g_prof.flops.push_back(f);
-        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used], s));
-    }
+    double flops = 0;
+    for (int i = 0; i < count; ++i) flops += 2.0 * gb.p[i].M * (double)gb.p[i].N * gb.p[i].K;
+    ProfBracket prof;
+    EXORL_TRY(prof.begin(s, flops));
     constexpr size_t dyn = PREC == EXORL_PREC_BF16X6 ? 6 * TILEB : 0;          // 48 KB: one stage of three planes of A and B
     if constexpr (PREC == EXORL_PREC_BF16X6) {
         static bool attr = false;
@@ -1562,11 +1336,7 @@ static int launch_layout(const GemmBatch& gb, int count, int max_tiles, bool vec
     if (vec) hipLaunchKernelGGL((gemm_kernel<PREC, AL, BL, true>), grid, block, dyn, s, gb);
     else     hipLaunchKernelGGL((gemm_kernel<PREC, AL, BL, false>), grid, block, dyn, s, gb);
     EXORL_LAUNCH_CHECK();
-    if (prof) {
-        EXORL_CHECK_HIP(hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s));
-        g_prof.used += 1;
-    }
-    return 0;
+    return prof.end(s);
 }
 
 template <int PREC>
@@ -1731,13 +1501,7 @@ static int planes_adapter(int al, int bl, const GemmProblem* probs, int count, b
     return 0;
 }
 
-// Launches up to 4 independent problems (same layouts / epilogue flags) as one grid.
-// Diagnostic (tools/debug/config4_ablation.py; no product path sets it): which split-bf16 products run with exact fp32 products instead.
-// bits: 1 / 2 forward (row-image A, row-image B) narrow / wide; 4 / 8 wgrad (k-image A and B); 16 / 32 dgrad (row-image A, k-image B);
-// "wide" = a problem dimension >= 8192 (the 39200-wide layers of the pixel agents); 64 / 128 / 256 = conv forward / dgrad / wgrad (pixels.hip)
-static int g_prec_override = 0;
-int prec_override_mask() { return g_prec_override; }
-
+// Launches up to GEMM_MAX_GROUP independent problems (same layouts / epilogue flags) as one grid.
 int gemm_grouped(int precision, int a_layout, int b_layout, const GemmProblem* probs, int count, bool relu,
                  bool accumulate, hipStream_t s) {
     EXORL_REQUIRE(count >= 1 && count <= GEMM_MAX_GROUP, "gemm_grouped: count %d out of range", count);
@@ -1825,18 +1589,6 @@ extern "C" int exorl_profile_event_overhead(float* ms_out, void* stream) {
     for (int i = 0; i < 2 * n; ++i) (void)hipEventDestroy(ev[i]);
     std::sort(t.begin(), t.end());
     *ms_out = t[n / 2];
-    return 0;
-}
-
-namespace exorl { int tune_variant() { return g_gemm16_variant < 0 ? 0 : g_gemm16_variant; } }
-
-extern "C" int exorl_debug_precision_override(int32_t mask) {
-    exorl::g_prec_override = mask;
-    return 0;
-}
-
-extern "C" int exorl_gemm_tune(int32_t variant) {
-    exorl::g_gemm16_variant = variant;
     return 0;
 }
 

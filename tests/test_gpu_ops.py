@@ -101,9 +101,12 @@ def test_gemm_split_bf16_adapter_ragged_width_in_place(lib, al, bl, M, N, K):
 
 @pytest.mark.parametrize('al,bl', [(0, 0), (0, 1), (1, 1)])
 @pytest.mark.parametrize('M,N,K', [(64, 64, 64), (128, 64, 32), (1024, 1024, 1024), (2048, 1024, 1024), (96, 200, 72), (8, 32, 8),
-                                   (256, 384, 512), (128, 128, 256), (192, 128, 256)])
+                                   (256, 384, 512), (128, 128, 256), (192, 128, 256), (2048, 2048, 256)])
 def test_gemm_bf16_operands(lib, al, bl, M, N, K):
-    """Fast-mode kernel: operands already bf16 in memory; exact up to fp32 accumulation order."""
+    """Fast-mode kernel: operands already bf16 in memory; exact up to fp32 accumulation order. Every shape with the output placed three ways:
+    16-byte aligned rows (pitch N), a pitch of N + 1 floats, and the C pointer one float past an aligned address. The last two are what the
+    128 x TN kernels' float4 epilogue cannot store (at 2048 x 2048 x 256, 256 tiles of 128 x 128, nothing else keeps a launch off them): the
+    64 x 64 or register-staged kernels serve them. Whatever is not C[:, :N] stays untouched, and a repeated launch gives the same bits."""
     from exorl_amd import _lib as L
     rs = np.random.RandomState(M + N + K + 5 * al + bl)
     A = bf16_round(rs.standard_normal((M, K)).astype(np.float32))
@@ -111,25 +114,37 @@ def test_gemm_bf16_operands(lib, al, bl, M, N, K):
     B[0, :] += bf16_round(np.arange(N, dtype=np.float32) % 7)       # asymmetric
     B = bf16_round(B)
     bias = rs.standard_normal(N).astype(np.float32)
-    C0 = rs.standard_normal((M, N)).astype(np.float32)
     A_st = A if al == 0 else np.ascontiguousarray(A.T)
     B_st = np.ascontiguousarray(B.T) if bl == 0 else B
     a = torch.from_numpy(A_st).cuda().to(torch.bfloat16).contiguous()
     b = torch.from_numpy(B_st).cuda().to(torch.bfloat16).contiguous()
-    c, bi = dev(C0.copy()), dev(bias)
-    for relu, acc in ((0, 0), (1, 0), (0, 1)):
-        c.copy_(torch.from_numpy(C0))
-        L.check(lib.exorl_gemm_bf16(al, bl, M, N, K, a.data_ptr(), A_st.shape[1], b.data_ptr(), B_st.shape[1], c.data_ptr(), N,
-                                    bi.data_ptr(), relu, acc, None))
-        torch.cuda.synchronize()
-        ref = A.astype(np.float64) @ B.astype(np.float64) + bias
-        if relu:
-            ref = np.maximum(ref, 0)
-        if acc:
-            ref = ref + C0
-        scale = np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64) + 1.0
-        err = np.abs(c.cpu().numpy() - ref) / scale
-        assert err.max() < 2e-6, (al, bl, M, N, K, relu, acc, err.max())
+    bi = dev(bias)
+    prod = A.astype(np.float64) @ B.astype(np.float64) + bias
+    scale = np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64) + 1.0
+    for off, ldc in ((0, N), (0, N + 1), (1, N)):
+        init = rs.standard_normal(off + M * ldc + 8).astype(np.float32)
+        inside = np.zeros(init.size, bool)
+        inside[off:off + M * ldc].reshape(M, ldc)[:, :N] = True
+        C0 = init[inside].reshape(M, N)
+        buf = dev(init)
+        assert buf.data_ptr() % 16 == 0
+        for relu, acc in ((0, 0), (1, 0), (0, 1)):
+            def launch():
+                buf.copy_(torch.from_numpy(init))
+                L.check(lib.exorl_gemm_bf16(al, bl, M, N, K, a.data_ptr(), A_st.shape[1], b.data_ptr(), B_st.shape[1], buf.data_ptr() + 4 * off,
+                                            ldc, bi.data_ptr(), relu, acc, None))
+                torch.cuda.synchronize()
+                return buf.cpu().numpy()
+            out = launch()
+            ref = prod
+            if relu:
+                ref = np.maximum(ref, 0)
+            if acc:
+                ref = ref + C0
+            err = np.abs(out[inside].reshape(M, N) - ref) / scale
+            assert err.max() < 2e-6, (al, bl, M, N, K, off, ldc, relu, acc, err.max())
+            assert np.array_equal(out[~inside], init[~inside]), (al, bl, M, N, K, off, ldc, relu, acc)
+            assert np.array_equal(launch(), out), (al, bl, M, N, K, off, ldc, relu, acc)
 
 
 @pytest.mark.parametrize('al', [0, 1])
@@ -330,11 +345,16 @@ def test_knn_golden_pbe_and_proto(lib, gold):
     (2, [0, 0], 0, 1024, 1024, 1024), (2, [0, 0], 1, 1024, 1024, 1024), (2, [1, 0], 1, 1024, 1024, 1024), (1, [0], 0, 2048, 1024, 1024),
     (1, [0], 1, 128, 128, 256), (1, [0], 1, 128, 64, 512), (1, [1], 1, 256, 384, 512), (2, [0, 0], 0, 128, 128, 128), (1, [0], 0, 128, 192, 384),
     (4, [0, 0, 0, 0], 1, 512, 512, 256), (2, [1, 1], 1, 256, 128, 640),
-    (2, [0, 0], 0, 10240, 1024, 1024), (2, [0, 0], 1, 4096, 1024, 1024), (2, [1, 1], 1, 1024, 1024, 4096)])       # CQL's 10 B-row pass; B = 4096: dgrad rows, wgrad reduction length
+    (2, [0, 0], 0, 10240, 1024, 1024), (2, [0, 0], 1, 4096, 1024, 1024), (2, [1, 1], 1, 1024, 1024, 4096),       # CQL's 10 B-row pass; B = 4096: dgrad rows, wgrad reduction length
+    (1, [0], 0, 2048, 2048, 256), (1, [0], 1, 2048, 2048, 256), (1, [1], 1, 2048, 2048, 256),      # 256 tiles of 128 x 128 in one problem ...
+    (4, [0, 0, 0, 0], 1, 1024, 1024, 1024), (4, [1, 1, 1, 1], 1, 1024, 1024, 1024)])               # ... and in four (with the first two cases)
 def test_gemm_planes_shapes(lib, x3, count, a_layouts, bl, M, N, K):
     """The grouped H x H GEMM on bf16 hi/lo planes (exorl_gemm_planes: what the agent's six launches call), every operand layout, launch shapes
     from one stage ring (K = 128) to 32, with REAL lo planes: equal to the float64 product of the same planes (minus lo*lo, which the kernel
-    drops) to fp32 accumulation order, and bit-identical over repeated launches (a stage-ring race shows up as a result that moves)."""
+    drops) to fp32 accumulation order, and bit-identical over repeated launches (a stage-ring race shows up as a result that moves).
+    Every case with the outputs placed three ways: 16-byte aligned rows (pitch N), a pitch of N + 1 floats, and every C pointer one float past
+    an aligned address. The last two are what the 128 x TN kernels' float4 epilogue cannot store (for the launches of 256 tiles of 128 x 128
+    nothing else keeps them off those kernels): the 64 x 64 kernels serve them. Whatever is not C[:, :N] stays untouched."""
     from exorl_amd import _lib as L
     C = L.C
     g = torch.Generator(device='cuda').manual_seed(M + N + K + count + bl)
@@ -346,19 +366,12 @@ def test_gemm_planes_shapes(lib, x3, count, a_layouts, bl, M, N, K):
     for i in range(count):
         A = torch.randn((M, K) if a_layouts[i] == 0 else (K, M), device='cuda', generator=g)
         B = torch.randn((N, K) if bl == 0 else (K, N), device='cuda', generator=g)
-        ps.append((split(A), split(B), torch.zeros(M, N, device='cuda')))
+        ps.append((split(A), split(B)))
     arr = lambda xs: (C.c_void_p * count)(*[x.data_ptr() for x in xs])
     lay = (C.c_int32 * count)(*a_layouts)
     lda, ldb = (K if a_layouts[0] == 0 else M), (K if bl == 0 else N)
-
-    def launch():
-        L.check(lib.exorl_gemm_planes(count, lay, bl, M, N, K, arr([p[0][0] for p in ps]), arr([p[0][1] for p in ps]) if x3 else None, lda,
-                                      arr([p[1][0] for p in ps]), arr([p[1][1] for p in ps]) if x3 else None, ldb, arr([p[2] for p in ps]), N, 0,
-                                      torch.cuda.current_stream().cuda_stream))
-        torch.cuda.synchronize()
-        return [p[2].clone() for p in ps]
-    first = launch()
-    for i, ((ah, alo), (bh, blo), _) in enumerate(ps):
+    refs = []
+    for i, ((ah, alo), (bh, blo)) in enumerate(ps):
         Ad = ah.double() + (alo.double() if x3 else 0)
         Bd = bh.double() + (blo.double() if x3 else 0)
         Ad = Ad if a_layouts[i] == 0 else Ad.t()
@@ -366,8 +379,28 @@ def test_gemm_planes_shapes(lib, x3, count, a_layouts, bl, M, N, K):
         ref = Ad @ Bd
         if x3:
             ref = ref - (alo.double() if a_layouts[i] == 0 else alo.double().t()) @ (blo.double().t() if bl == 0 else blo.double())
-        err = float((first[i].double() - ref).abs().max() / ref.abs().max())
-        assert err < 2e-6, (i, err)
-    for _ in range(6):
-        again = launch()
-        assert all(torch.equal(a, b) for a, b in zip(first, again))
+        refs.append(ref)
+    GUARD = -123.0
+    for off, ldc in ((0, N), (0, N + 1), (1, N)):
+        bufs = [torch.full((off + M * ldc + 8,), GUARD, device='cuda') for _ in range(count)]
+        assert all(t.data_ptr() % 16 == 0 for t in bufs)
+        cptr = (C.c_void_p * count)(*[t.data_ptr() + 4 * off for t in bufs])
+        inside = torch.zeros(off + M * ldc + 8, dtype=torch.bool, device='cuda')
+        inside[off:off + M * ldc].view(M, ldc)[:, :N] = True
+
+        def launch():
+            for t in bufs:
+                t.fill_(GUARD)
+            L.check(lib.exorl_gemm_planes(count, lay, bl, M, N, K, arr([p[0][0] for p in ps]), arr([p[0][1] for p in ps]) if x3 else None, lda,
+                                          arr([p[1][0] for p in ps]), arr([p[1][1] for p in ps]) if x3 else None, ldb, cptr, ldc, 0,
+                                          torch.cuda.current_stream().cuda_stream))
+            torch.cuda.synchronize()
+            return [t.clone() for t in bufs]
+        first = launch()
+        for i, ref in enumerate(refs):
+            err = float((first[i][inside].view(M, N).double() - ref).abs().max() / ref.abs().max())
+            assert err < 2e-6, (i, off, ldc, err)
+            assert bool((first[i][~inside] == GUARD).all()), (i, off, ldc)
+        for _ in range(6):
+            again = launch()
+            assert all(torch.equal(a, b) for a, b in zip(first, again)), (off, ldc)
