@@ -23,7 +23,7 @@ N_METRICS = 16
 INTR_RND, INTR_ICM, INTR_ICM_APT, INTR_DISAGREEMENT, INTR_DIAYN, INTR_PROTO, INTR_APS, INTR_SMM = 0, 1, 2, 3, 4, 5, 6, 7
 IM_LOSS, IM_INTR_REWARD, IM_EXTR_REWARD, IM_RMS_MEAN, IM_RMS_STD, IM_ACC, IM_ENT_REWARD, IM_SF_REWARD = range(8)
 N_INTR_METRICS = 8
-INTR_XCHG_GRAD, INTR_XCHG_REP, INTR_XCHG_MOMENTS = 0, 1, 2
+INTR_XCHG_GRAD, INTR_XCHG_REP, INTR_XCHG_MOMENTS, INTR_XCHG_BN = 0, 1, 2, 3
 XCHG_F32, XCHG_F64 = 0, 1
 XCHG_SUM, XCHG_GATHER = 0, 1
 

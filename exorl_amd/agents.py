@@ -720,7 +720,7 @@ class _IntrAgent(DDPGAgent):
 
     def _intr_step(self):
         s = self._slots = self._slots or self.engine.batch_slots()
-        self.intr.update(s.obs, s.action, s.next_obs, s.reward, s.reward, True)
+        self.intr.run_update(s.obs, s.action, s.next_obs, s.reward, s.reward, True)
 
     def enable_graph(self, replay_iter, step=0):
         return False                     # the module step is launched eagerly in front of the DDPG chain
@@ -733,16 +733,29 @@ class _IntrAgent(DDPGAgent):
     # and runs the module step on the GLOBAL batch: the kernels are deterministic, so the replicas of the module stay bit-identical
     # without a gradient exchange, every statistic is the single-process one, and each rank keeps its own rows of the reward. The
     # actor / critic step — the 1024-wide layers, 35 of the step's ~45 GFLOP — runs sharded like the offline agents' (_run_update).
+    # That replicated step is the default (its replicas equal the single process bit for bit). With shard_pretraining=True the module step
+    # is sharded on states as it is on pixels: each rank runs the module on its own rows through IntrEngine.run_update, the gradients are
+    # summed, and the batch-global statistics travel as small exchanges — RND's BatchNorm1d moments, the RMS moments, the kNN targets of
+    # ICM-APT and APS, Proto's target and reward rows, SMM's moments of log p*. No rows are gathered and each rank's rewards land in its
+    # own reward slot. The gradient sum's order differs from the single process's, so the replicas agree with it to rounding only.
+    shard_pretraining = False
+
     @property
     def _module_batch(self):
         return self.engine.batch * getattr(self, 'world_size', 1)
 
     def _intr_dp(self):
-        """IntrEngine's batch arguments. On states the module stays replicated on the gathered global batch (_intr_step_dp); on pixels under
-        torch.distributed it is sharded: this rank's rows, with world_size and rank (exorl_intr_update_phase and its exchanges)."""
-        if getattr(self, 'obs_type', 'states') == 'pixels' and self.world_size > 1:
+        """IntrEngine's batch arguments. Under torch.distributed the module is sharded on pixels, and on states where shard_pretraining asks
+        for it: this rank's rows, with world_size and rank (exorl_intr_update_phase and its exchanges). Otherwise it stays replicated on
+        the gathered global batch (_intr_step_dp)."""
+        if self.world_size > 1 and (getattr(self, 'obs_type', 'states') == 'pixels' or self._sharded_states):
             return dict(batch=self.engine.batch, world_size=self.world_size, rank=torch.distributed.get_rank())
         return dict(batch=self._module_batch)
+
+    @property
+    def _sharded_states(self):
+        return (getattr(self, 'obs_type', 'states') == 'states' and self.shard_pretraining and self.reward_free and
+                getattr(self, 'world_size', 1) > 1)
 
     def _dp_buffers(self):
         if getattr(self, '_dp', None) is None:
@@ -795,10 +808,14 @@ class _IntrAgent(DDPGAgent):
     # BatchNorm2d statistics, the running RMS's batch moments, the kNN targets of ICM-APT and APS — are small exchanges of their own.
     # The engines' run_* calls (engine.py) take the phased forms in that case.
     def _intr_metrics(self):
-        """The module's metrics as global means; the RMS state (slots 3, 4 of RND, ICM-APT and APS) is the same on every rank and is not
-        summed."""
-        rms = self.intr.kind in ('rnd', 'icm_apt', 'aps')
-        return global_means(self.intr, slice(L.IM_RMS_MEAN, L.IM_RMS_STD + 1) if rms else None)
+        """The module's metrics as global means; the RMS state (slots 3, 4 of RND, ICM-APT and APS) and SMM's mean and variance of log p*
+        on states (slots 3, 7) are the same on every rank and are not summed."""
+        keep = None
+        if self.intr.kind in ('rnd', 'icm_apt', 'aps'):
+            keep = slice(L.IM_RMS_MEAN, L.IM_RMS_STD + 1)
+        elif self.intr.kind == 'smm' and self.obs_type == 'states':
+            keep = [3, 7]
+        return global_means(self.intr, keep)
 
     def _pix_module(self, fo, fn, s):
         """Module step + intrinsic reward on the encodings (device pointers); d(loss)/d(encoding) lands in self._dobs."""
@@ -856,7 +873,7 @@ class _IntrAgent(DDPGAgent):
         stddev = self._stddev(step)
         self._load_batch(replay_iter)
         if self.reward_free:
-            if self.world_size != 1:
+            if self.world_size != 1 and not self._sharded_states:
                 self._intr_step_dp()
             else:
                 self._intr_step()
@@ -864,7 +881,7 @@ class _IntrAgent(DDPGAgent):
         if self.use_tb or self.use_wandb:
             metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
             if self.reward_free:
-                raw = self.intr.metrics_raw()
+                raw = self._intr_metrics()              # a replicated module's engine has world_size 1: its own metrics
                 metrics[self.LOSS_KEY] = float(raw[L.IM_LOSS])
                 metrics['intr_reward'] = float(raw[L.IM_INTR_REWARD])
                 metrics['extr_reward'] = float(raw[L.IM_EXTR_REWARD])
@@ -914,7 +931,8 @@ class RNDAgent(_IntrAgent):
     LOSS_KEY = 'rnd_loss'
     _PIXELS_OK = True
 
-    def __init__(self, rnd_rep_dim, update_encoder, rnd_scale=1., **kwargs):
+    def __init__(self, rnd_rep_dim, update_encoder, rnd_scale=1., shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         super().__init__(**kwargs)
         self.rnd_scale = rnd_scale
         self.update_encoder = update_encoder
@@ -1000,7 +1018,8 @@ class ICMAgent(_IntrAgent):
     LOSS_KEY = 'icm_loss'
     _PIXELS_OK = True
 
-    def __init__(self, icm_scale, update_encoder, **kwargs):
+    def __init__(self, icm_scale, update_encoder, shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         super().__init__(**kwargs)
         self.icm_scale = icm_scale
         self.update_encoder = update_encoder
@@ -1024,7 +1043,8 @@ class ICMAPTAgent(_IntrAgent):
     LOSS_KEY = 'icm_loss'
     _PIXELS_OK = True
 
-    def __init__(self, icm_scale, knn_rms, knn_k, knn_avg, knn_clip, update_encoder, icm_rep_dim, **kwargs):
+    def __init__(self, icm_scale, knn_rms, knn_k, knn_avg, knn_clip, update_encoder, icm_rep_dim, shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         super().__init__(**kwargs)
         self.icm_scale = icm_scale
         self.update_encoder = update_encoder
@@ -1048,7 +1068,8 @@ class DisagreementAgent(_IntrAgent):
     LOSS_KEY = 'disagreement_loss'
     _PIXELS_OK = True
 
-    def __init__(self, update_encoder, **kwargs):
+    def __init__(self, update_encoder, shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         super().__init__(**kwargs)
         self.update_encoder = update_encoder
         O, A, H = self.obs_dim, self.action_dim, self.hidden_dim
@@ -1098,7 +1119,7 @@ class _MetaObsMixin:
     def _intr_step(self):
         O, W = self.obs_dim - self._meta_dim, self.obs_dim
         s = self._slots
-        self.intr.update(s.obs, None, s.next_obs, s.reward, s.reward, True, skill=s.obs + 4 * O, obs_ld=W, next_obs_ld=W, skill_ld=W)
+        self.intr.run_update(s.obs, None, s.next_obs, s.reward, s.reward, True, skill=s.obs + 4 * O, obs_ld=W, next_obs_ld=W, skill_ld=W)
 
 
 class DIAYNAgent(_MetaObsMixin, _IntrAgent):
@@ -1108,7 +1129,8 @@ class DIAYNAgent(_MetaObsMixin, _IntrAgent):
     _PIXELS_OK = True
     _PIX_GRAD = 1
 
-    def __init__(self, update_skill_every_step, skill_dim, diayn_scale, update_encoder, **kwargs):
+    def __init__(self, update_skill_every_step, skill_dim, diayn_scale, update_encoder, shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         self.skill_dim = self._meta_dim = skill_dim
         self.update_skill_every_step = update_skill_every_step
         self.diayn_scale = diayn_scale
@@ -1162,7 +1184,8 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
         self.intr.run_update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.sf_dim, dobs_out=self._dobs.data_ptr())
 
     def __init__(self, update_task_every_step, sf_dim, knn_rms, knn_k, knn_avg, knn_clip, num_init_steps, lstsq_batch_size, update_encoder,
-                 **kwargs):
+                 shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         self.sf_dim = self._meta_dim = sf_dim
         self.update_task_every_step = update_task_every_step
         self.num_init_steps = num_init_steps
@@ -1269,7 +1292,9 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
     _PIXELS_OK = True                    # smm.py:264-331 with obs_type == 'pixels': the VAE and the skill predictor read the encoding, p*(s) is dropped
     _PIX_GRAD = 0
 
-    def __init__(self, z_dim, sp_lr, vae_lr, vae_beta, state_ent_coef, latent_ent_coef, latent_cond_ent_coef, update_encoder, **kwargs):
+    def __init__(self, z_dim, sp_lr, vae_lr, vae_beta, state_ent_coef, latent_ent_coef, latent_cond_ent_coef, update_encoder,
+                 shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)
         self.z_dim = self._meta_dim = z_dim
         self.state_ent_coef = state_ent_coef
         self.latent_ent_coef = latent_ent_coef
@@ -1349,8 +1374,8 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         e = None
         if self.eps_hook is not None:
             e = torch.as_tensor(np.asarray(self.eps_hook((self.intr.batch, 128)), np.float32), device=self.engine.device).contiguous()
-        self.intr.update(s.obs, None, None, s.reward, s.reward, True, skill=s.obs + 4 * O, obs_ld=W, skill_ld=W,
-                         cat_uniform=e.data_ptr() if e is not None else None)
+        self.intr.run_update(s.obs, None, None, s.reward, s.reward, True, skill=s.obs + 4 * O, obs_ld=W, skill_ld=W,
+                             cat_uniform=e.data_ptr() if e is not None else None)
         self._keep_eps = e
 
     def update(self, replay_iter, step):
@@ -1362,7 +1387,7 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
                 metrics['loss_pred'] = float(self._intr_metrics()[5])
             return metrics
         if self.reward_free:                             # smm.py:249-258: these are reported whatever use_tb says
-            raw = self.intr.metrics_raw()
+            raw = self._intr_metrics()
             for k in ('icm_loss', 'loss_vae'):
                 metrics.pop(k, None)
             metrics.update(intr_reward=float(raw[1]), log_p_star=float(raw[3]), pred_log_ratios=float(raw[4]),
@@ -1412,9 +1437,10 @@ class ProtoAgent(_IntrAgent):
 
     def __init__(self, pred_dim, proj_dim, queue_size, num_protos, tau, encoder_target_tau, topk, update_encoder, shard_pretraining=False,
                  **kwargs):
-        # shard_pretraining: under torch.distributed on pixels, run the reward-free module step data-parallel (each rank's rows, the target
-        # and reward rows all-gathered, Sinkhorn and the candidate draw run identically on every rank). Off by default: DDPGAgent._init_pixels
-        # refuses that case without it, so the flag is set before the base constructor runs. No effect on states or at world size 1.
+        # shard_pretraining: under torch.distributed, run the reward-free module step data-parallel (each rank's rows, the target and reward
+        # rows all-gathered, Sinkhorn and the candidate draw run identically on every rank). Off by default: on pixels
+        # DDPGAgent._init_pixels refuses that case without it, so the flag is set before the base constructor runs; on states the default
+        # is the replicated module on the gathered batch. No effect at world size 1.
         self.shard_pretraining = bool(shard_pretraining)
         super().__init__(**kwargs)
         self.tau = tau
@@ -1468,7 +1494,7 @@ class ProtoAgent(_IntrAgent):
     def _intr_step(self):
         s = self._slots = self._slots or self.engine.batch_slots()
         u = self._cat_u()
-        self.intr.update(s.obs, None, s.next_obs, s.reward, s.reward, True, cat_uniform=u.data_ptr() if u is not None else None)
+        self.intr.run_update(s.obs, None, s.next_obs, s.reward, s.reward, True, cat_uniform=u.data_ptr() if u is not None else None)
         self._keep_u = u
 
     def _update_pixels(self, replay_iter, step):

@@ -64,6 +64,47 @@ __global__ __launch_bounds__(256) void bn_clamp_kernel(const float* __restrict__
     }
 }
 
+// ---- the same BatchNorm1d over the global batch of a data-parallel step ----------------------------------------------------------------
+// Each rank reduces its rows to per-feature (n, mean, M2) — the two passes of bn_clamp_kernel — and the ranks' moments are all-gathered
+// (EXORL_INTR_XCHG_BN). Every rank then merges them in rank order in double (Chan et al., as rms_combine_update), so the normalisation and
+// the running statistics are the same bits on every rank. mom: [rank][feature][3] doubles.
+__global__ __launch_bounds__(256) void bn_moments_kernel(const float* __restrict__ x, int64_t ldx, int rows, int O, double* __restrict__ mom) {
+    __shared__ float red[17];
+    const int c = blockIdx.x;
+    float s = 0.f;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) s += x[(int64_t)r * ldx + c];
+    const float mean = block_sum(s, red) / (float)rows;
+    float q = 0.f;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) { const float d = x[(int64_t)r * ldx + c] - mean; q += d * d; }
+    q = block_sum(q, red);
+    if (threadIdx.x == 0) { mom[3 * c] = (double)rows; mom[3 * c + 1] = (double)mean; mom[3 * c + 2] = (double)q; }
+}
+// normalise this rank's rows with the merged statistics, clamp, and step the running statistics (momentum 0.1, unbiased variance over the
+// global batch's rows); every thread merges the `world` triples of its feature itself (a few dozen double operations)
+__global__ __launch_bounds__(256) void bn_merged_clamp_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ out, int rows, int O,
+                                                              float clip, float* __restrict__ running, const double* __restrict__ mom, int world) {
+    const int c = blockIdx.x;
+    double n = mom[3 * c], dmean = mom[3 * c + 1], m2 = mom[3 * c + 2];
+    for (int r = 1; r < world; ++r) {
+        const double* m = mom + 3 * ((int64_t)r * O + c);
+        const double nr = m[0], d = m[1] - dmean, tot = n + nr;
+        dmean += d * nr / tot;
+        m2 += m[2] + d * d * n * nr / tot;
+        n = tot;
+    }
+    const float mean = (float)dmean, var = (float)(m2 / n);
+    const float rstd = 1.0f / sqrtf(var + 1e-5f);
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        const float v = (x[(int64_t)r * ldx + c] - mean) * rstd;
+        out[(int64_t)r * O + c] = fminf(fmaxf(v, -clip), clip);
+    }
+    if (threadIdx.x == 0) {
+        running[c] = 0.9f * running[c] + 0.1f * mean;
+        running[O + c] = 0.9f * running[O + c] + 0.1f * (float)(m2 / (n > 1.0 ? n - 1.0 : 1.0));
+        if (c == 0) running[2 * O] += 1.0f;
+    }
+}
+
 // dst[r] = [a[r, 0:ca] | b[r, 0:cb]]
 __global__ __launch_bounds__(256) void concat2_kernel(const float* __restrict__ a, int64_t lda, int ca, const float* __restrict__ b, int64_t ldb,
                                                       int cb, float* __restrict__ dst, int rows) {
@@ -813,12 +854,27 @@ __global__ __launch_bounds__(256) void vae_latent_kernel(const float* __restrict
     k = wave_sum(k);
     if (lane == 0) kle_row[row] = -0.5f * k;
 }
-// reward and bookkeeping (smm.py:229-258); single block. The reference's 1-D log_p_star broadcasts its reward to (B,B): per
-// sample that is rest_i + mean_j log_p_star_j for the TD gradient, plus var_j(log_p_star_j) in each critic's loss value.
+__device__ __forceinline__ float smm_log_p_star(const float* __restrict__ obs, int64_t ld, int b, float gx, float gy) {
+    const float dx = obs[(int64_t)b * ld] - gx, dy = obs[(int64_t)b * ld + 1] - gy;
+    const float dist = sqrtf(dx * dx + dy * dy);
+    return logf(dist > 1.0f ? 1.0f / dist : 1.0f);
+}
+// this rank's (n, mean, M2) of log p*(s_j) for the data-parallel step: the ranks' triples are gathered and merged in rank order in double
+__global__ __launch_bounds__(1024) void smm_logp_moments_kernel(const float* __restrict__ obs, int64_t ld, int B, float gx, float gy,
+                                                                double* __restrict__ mom) {
+    __shared__ float red[17];
+    float mean, q;
+    block_moments([&](int i) { return smm_log_p_star(obs, ld, i, gx, gy); }, B, red, mean, q);
+    if (threadIdx.x == 0) { mom[0] = (double)B; mom[1] = (double)mean; mom[2] = (double)q; }
+}
+// reward and bookkeeping (smm.py:229-258); single block. mom: the `world` ranks' gathered moments of log p* (states, world > 1: slots 3
+// and 7 then hold the global mean and variance on every rank, the other slots this rank's partial means over Bg), else null. The
+// reference's 1-D log_p_star broadcasts its reward to (B,B): per sample that is rest_i + mean_j log_p_star_j for the TD gradient, plus
+// var_j(log_p_star_j) in each critic's loss value.
 __global__ __launch_bounds__(1024) void smm_reward_kernel(const float* __restrict__ obs, int64_t ld, const float* __restrict__ hsz,
                                                           const float* __restrict__ hzs, const float* extr, float* reward, int B, int Z,
                                                           float sec, float lec, float lcec, float gx, float gy, float* __restrict__ metrics, int encoded,
-                                                          int Bg) {
+                                                          int Bg, const double* __restrict__ mom, int world) {
     __shared__ float red[17];
     float e = 0.f, sl = 0.f, s1 = 0.f, s2 = 0.f;
     if (encoded) {                 // pixels: p*(s) is ignored (smm.py:232-235), the reward is a plain (B, 1) column
@@ -847,7 +903,17 @@ __global__ __launch_bounds__(1024) void smm_reward_kernel(const float* __restric
         s2 += lcec * hzs[b];
     }
     e = block_sum(e, red);
-    const float lm = block_sum(sl, red) / (float)B;
+    float lm = block_sum(sl, red) / (float)B, gvar = 0.f;
+    if (mom) {                     // every thread merges the same few triples
+        double n = mom[0], mean = mom[1], m2 = mom[2];
+        for (int r = 1; r < world; ++r) {
+            const double nr = mom[3 * r], d = mom[3 * r + 1] - mean, tot = n + nr;
+            mean += d * nr / tot;
+            m2 += mom[3 * r + 2] + d * d * n * nr / tot;
+            n = tot;
+        }
+        lm = (float)mean; gvar = (float)(m2 / n);
+    }
     s1 = block_sum(s1, red); s2 = block_sum(s2, red);
     float var = 0.f, rs = 0.f;
     const float hz = lec * logf((float)Z);
@@ -861,9 +927,9 @@ __global__ __launch_bounds__(1024) void smm_reward_kernel(const float* __restric
         rs += r;
     }
     var = block_sum(var, red); rs = block_sum(rs, red);
-    if (threadIdx.x == 0) {
-        metrics[1] = rs / (float)B; metrics[2] = e / (float)B; metrics[3] = lm; metrics[4] = s1 / (float)B; metrics[6] = s2 / (float)B;
-        metrics[7] = var / (float)B;
+    if (threadIdx.x == 0) {          // one rank: Bg == B
+        metrics[1] = rs / (float)Bg; metrics[2] = e / (float)Bg; metrics[3] = lm; metrics[4] = s1 / (float)Bg; metrics[6] = s2 / (float)Bg;
+        metrics[7] = mom ? gvar : var / (float)B;
     }
 }
 
@@ -991,7 +1057,9 @@ struct exorl_intr {
     // data parallel (cfg.world_size > 1): this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch
     int world = 1, rank = 0;
     float* gat = nullptr;                  // ICM-APT / APS / Proto: the gathered representation rows (world slots of batch x rep_dim, rank order)
-    double* mom = nullptr;                 // RND / ICM-APT / APS: the gathered RMS moments, (n, mean, M2) per rank
+    double* mom = nullptr;                 // RND / ICM-APT / APS: the gathered RMS moments, (n, mean, M2) per rank; SMM on states: those of log p*
+    double* bnmom = nullptr;               // RND on states: the gathered BatchNorm1d moments, (n, mean, M2) per feature per rank
+    bool bn_dp() const { return cfg.kind == EXORL_INTR_RND && world > 1 && !(cfg.flags & EXORL_INTR_ENCODED); }
     int Bg() const { return cfg.batch * world; }
 };
 
@@ -1080,16 +1148,18 @@ static void carve_intr(exorl_intr* it, ICarver& c) {
     it->fe = c.take(B * (g.kind == EXORL_INTR_DISAGREEMENT ? it->n_nets : 1)); it->be = c.take(B);
     it->metrics = c.take(EXORL_N_INTR_METRICS);
     it->rms = reinterpret_cast<RmsState*>(c.take(4));
-    if (W > 1 && (g.kind == EXORL_INTR_RND || g.kind == EXORL_INTR_ICM_APT || g.kind == EXORL_INTR_APS))
+    if (W > 1 && (g.kind == EXORL_INTR_RND || g.kind == EXORL_INTR_ICM_APT || g.kind == EXORL_INTR_APS ||
+                  (g.kind == EXORL_INTR_SMM && !(g.flags & EXORL_INTR_ENCODED))))
         it->mom = reinterpret_cast<double*>(c.take(2 * 3 * W));
     if (g.kind == EXORL_INTR_RND) {
         if (!(g.flags & EXORL_INTR_ENCODED)) {     // encoded rows arrive normalised (BatchNorm2d ran on the frames)
             it->xn = c.take(B * O);
             it->bn = c.take(2 * O + 1);
+            if (W > 1) it->bnmom = reinterpret_cast<double*>(c.take(2 * 3 * O * W));
         }
     } else if (g.kind == EXORL_INTR_APS) {
         it->topk = c.take(B * g.knn_k);
-        it->d2 = c.take(B * round_up(B * W, 64));
+        it->d2 = c.take(knn_scratch_floats((int)B, (int)(B * W)));
         if (W > 1) it->gat = c.take(W * B * R);
     } else if (g.kind == EXORL_INTR_SMM) {
         const int64_t C = SMM_CODE_DIM;
@@ -1121,7 +1191,7 @@ static void carve_intr(exorl_intr* it, ICarver& c) {
             it->x2 = c.take(2 * B * O); it->z = c.take(2 * B * R); it->rep = c.take(2 * B * R); it->xhat = c.take(2 * B * R);
             it->rstd = c.take(2 * B); it->drep = c.take(2 * B * R); it->dz = c.take(2 * B * R);
             it->topk = c.take(B * g.knn_k);
-            it->d2 = c.take(B * round_up(B * W, 64));
+            it->d2 = c.take(knn_scratch_floats((int)B, (int)(B * W)));
             if (W > 1) it->gat = c.take(W * B * R);
         }
     }
@@ -1161,7 +1231,8 @@ int launch_concat(const float* a, int64_t lda, int ca, const float* b, int64_t l
 // names it in *next (EXORL_INTR_XCHG_*; -1: the step is complete). Stage 0 is the loss's forward and backward pass (train != 0 only) and
 // ends in the gradient exchange; stage 1 steps the optimiser and computes the reward; ICM-APT and APS then gather the representation
 // rows, and the RMS kinds gather their moments. With world_size 1 no stage after 0 names an exchange, and stage 0's (a sum over one
-// rank) is the identity, so exorl_intr_update runs the stages back to back.
+// rank) is the identity, so exorl_intr_update runs the stages back to back. On state rows two more statistics are over the global batch:
+// RND's BatchNorm1d moments (gathered in a stage in front of stage 0) and SMM's mean_j / var_j of log p*(s_j) (gathered after stage 1).
 
 // ---- RND -------------------------------------------------------------------------------------------
 static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_target, float* dpred, hipStream_t s) {
@@ -1175,7 +1246,9 @@ static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_targ
         EXORL_TRY(mlp_forward(it->net[0], P, b.obs, b.obs_ld, B, c.precision, s));
         EXORL_TRY(mlp_forward(it->net[1], P, b.next_obs, b.next_obs_ld, B, c.precision, s));
     } else {
-        hipLaunchKernelGGL(bn_clamp_kernel, dim3(O), dim3(256), 0, s, b.obs, b.obs_ld, it->xn, B, O, c.clip_val, it->bn);
+        if (it->bn_dp()) hipLaunchKernelGGL(bn_merged_clamp_kernel, dim3(O), dim3(256), 0, s, b.obs, b.obs_ld, it->xn, B, O, c.clip_val, it->bn,
+                                            (const double*)it->bnmom, it->world);
+        else hipLaunchKernelGGL(bn_clamp_kernel, dim3(O), dim3(256), 0, s, b.obs, b.obs_ld, it->xn, B, O, c.clip_val, it->bn);
         EXORL_LAUNCH_CHECK();
         if (with_target) EXORL_TRY(mlp_forward_many(it->net, 2, P, it->xn, O, B, c.precision, s));      // predictor and frozen target: same input, same shapes
         else EXORL_TRY(mlp_forward(it->net[0], P, it->xn, O, B, c.precision, s));
@@ -1186,13 +1259,22 @@ static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_targ
 }
 
 // train: 0 reward only, 1 step + reward on the same rows, 2 step only (pixels: the reward pass draws a new augmentation and runs the
-// encoder the step has just moved, rnd.py:98-103, so the caller encodes again in between)
+// encoder the step has just moved, rnd.py:98-103, so the caller encodes again in between).
+// On state rows with world_size > 1 a stage of its own comes first (stage -1, the first phase of either call): each rank's BatchNorm1d
+// moments, gathered before anything reads the normalised rows. The reward pass normalises the same rows in training mode again
+// (rnd.py:98-100): the merged moments are still in place, so rnd_forward steps the running statistics a second time without an exchange.
 static int rnd_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch;
     const bool enc = (c.flags & EXORL_INTR_ENCODED) != 0;
     EXORL_REQUIRE(enc || train != 2, "intr_update: RND's step-only call belongs to the encoded (pixel) variant");
     *next = -1;
+    if (stage < 0) {
+        hipLaunchKernelGGL(bn_moments_kernel, dim3(c.obs_dim), dim3(256), 0, s, b.obs, b.obs_ld, B, c.obs_dim, it->bnmom + (int64_t)3 * c.obs_dim * it->rank);
+        EXORL_LAUNCH_CHECK();
+        *next = EXORL_INTR_XCHG_BN;
+        return 0;
+    }
     if (stage == 0) {                                                                                // rnd.py:79-96
         EXORL_TRY(rnd_forward(it, b, true, it->net[0].dact[2], s));
         EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)it->Bg(), it->metrics + EXORL_IM_LOSS, 0, s));
@@ -1428,9 +1510,19 @@ static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
     if (stage == 1) {
         EXORL_TRY(adam_range(it, it->vae_off, it->trainable - it->vae_off, c.vae_lr, s));
         EXORL_TRY(adam_range(it, 0, it->vae_off, c.sp_lr, s));
+        if (it->world > 1 && !(c.flags & EXORL_INTR_ENCODED)) {      // mean_j and var_j of log p*(s_j) are over the global batch: stage 2
+            hipLaunchKernelGGL(smm_logp_moments_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, B, c.goal_x, c.goal_y, it->mom + 3 * it->rank);
+            EXORL_LAUNCH_CHECK();
+            *next = EXORL_INTR_XCHG_MOMENTS;
+            return 0;
+        }
+    }
+    if (stage >= 1) {
         // ---- reward (smm.py:229-246)
+        const bool merged = it->world > 1 && !(c.flags & EXORL_INTR_ENCODED);
         hipLaunchKernelGGL(smm_reward_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, it->hsz, it->hzs, b.extr_reward, b.reward_out, B, Z,
-                           c.state_ent_coef, c.latent_ent_coef, c.latent_cond_ent_coef, c.goal_x, c.goal_y, it->metrics, (c.flags & EXORL_INTR_ENCODED) ? 1 : 0, Bg);
+                           c.state_ent_coef, c.latent_ent_coef, c.latent_cond_ent_coef, c.goal_x, c.goal_y, it->metrics, (c.flags & EXORL_INTR_ENCODED) ? 1 : 0, Bg,
+                           merged ? (const double*)it->mom : nullptr, it->world);
         EXORL_LAUNCH_CHECK();
         return 0;
     }
@@ -1679,11 +1771,9 @@ static int check_intr_cfg(const exorl_intr_cfg* cfg) {
     const int world = cfg->world_size > 1 ? cfg->world_size : 1, Bg = cfg->batch * world;     // kNN rows: this rank's against the gathered batch
     EXORL_REQUIRE(cfg->kind != EXORL_INTR_PROTO || (int64_t)cfg->batch * world <= 8192, "intr: Proto supports batch * world_size <= 8192 (its "
                   "Sinkhorn and candidate draw run over the global batch; got %d x %d)", cfg->batch, world);
-    EXORL_REQUIRE(world == 1 || (cfg->flags & EXORL_INTR_ENCODED) || (cfg->kind != EXORL_INTR_RND && cfg->kind != EXORL_INTR_SMM),
-                  "intr: RND and SMM on state rows are single-rank modules (BatchNorm1d / mean_j log p*(s_j) over the batch); world_size=%d "
-                  "needs EXORL_INTR_ENCODED", cfg->world_size);
-    EXORL_REQUIRE(cfg->kind != EXORL_INTR_APS || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= Bg && Bg <= 4096),
-                  "intr: APS needs 1 <= knn_k <= min(64, batch * world_size) and batch * world_size <= 4096 (got k=%d B=%d)", cfg->knn_k, Bg);
+    EXORL_REQUIRE(cfg->kind != EXORL_INTR_APS || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= Bg && (int64_t)cfg->batch * world <= 8192),
+                  "intr: APS needs 1 <= knn_k <= min(64, batch * world_size) and batch * world_size <= 8192 (got k=%d, %d x %d)", cfg->knn_k,
+                  cfg->batch, world);
     EXORL_REQUIRE(cfg->kind != EXORL_INTR_PROTO || (cfg->num_protos >= 1 && cfg->queue_size >= cfg->num_protos && cfg->queue_size % cfg->num_protos == 0 &&
                   cfg->queue_size <= 4096 && cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= cfg->queue_size && cfg->tau > 0.f && cfg->batch <= 8192),
                   "intr: Proto needs num_protos >= 1, queue_size a multiple of num_protos and <= 4096, 1 <= topk <= 64, tau > 0 (got %d, %d, %d, %g)",
@@ -1693,8 +1783,9 @@ static int check_intr_cfg(const exorl_intr_cfg* cfg) {
                   "intr: unsupported dims O=%d A=%d (<=64) H=%d B=%d", cfg->obs_dim, cfg->act_dim, cfg->hidden_dim, cfg->batch);
     EXORL_REQUIRE(cfg->kind == EXORL_INTR_ICM || cfg->kind == EXORL_INTR_DISAGREEMENT || (cfg->rep_dim > 0 && (cfg->kind != EXORL_INTR_ICM_APT || cfg->rep_dim <= 1024)),
                   "intr: rep_dim=%d out of range (ICM-APT trunk: <= 1024)", cfg->rep_dim);
-    EXORL_REQUIRE(cfg->kind != EXORL_INTR_ICM_APT || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= Bg && Bg <= 4096),
-                  "intr: ICM-APT needs 1 <= knn_k <= min(64, batch * world_size) and batch * world_size <= 4096 (got k=%d B=%d)", cfg->knn_k, Bg);
+    EXORL_REQUIRE(cfg->kind != EXORL_INTR_ICM_APT || (cfg->knn_k >= 1 && cfg->knn_k <= 64 && cfg->knn_k <= Bg && (int64_t)cfg->batch * world <= 8192),
+                  "intr: ICM-APT needs 1 <= knn_k <= min(64, batch * world_size) and batch * world_size <= 8192 (got k=%d, %d x %d)", cfg->knn_k,
+                  cfg->batch, world);
     EXORL_REQUIRE(cfg->precision >= EXORL_PREC_F32 && cfg->precision <= EXORL_PREC_BF16X6, "intr: unknown precision %d", cfg->precision);
     return 0;
 }
@@ -1817,7 +1908,8 @@ int exorl_intr_update_phase(exorl_intr_t* it, const exorl_intr_batch* b, int32_t
         *next_exchange = next;
         return 0;
     }
-    const int stage = phase + (train ? 0 : 1);
+    int stage = phase + (train ? 0 : 1);
+    if (it->bn_dp()) stage = phase == 0 ? -1 : stage - 1;          // RND on state rows: the BatchNorm1d exchange comes first
     EXORL_REQUIRE(phase >= 0 && stage <= 3, "intr_update_phase: phase %d out of range", phase);
     EXORL_TRY(intr_stage(it, *b, train, stage, &next, as_stream(stream)));
     *next_exchange = next;
@@ -1832,8 +1924,11 @@ int exorl_intr_exchange(exorl_intr_t* it, int32_t id, void** ptr_dev, int64_t* c
         EXORL_REQUIRE(it->gat, "intr_exchange: exchange %d belongs to ICM-APT / APS / Proto with world_size > 1", id);
         *ptr_dev = it->gat; *count = (int64_t)it->cfg.batch * it->cfg.rep_dim; *dtype = EXORL_XCHG_F32; *op = EXORL_XCHG_GATHER;
     } else if (id == EXORL_INTR_XCHG_MOMENTS) {
-        EXORL_REQUIRE(it->mom, "intr_exchange: exchange %d belongs to RND / ICM-APT / APS with world_size > 1", id);
+        EXORL_REQUIRE(it->mom, "intr_exchange: exchange %d belongs to RND / ICM-APT / APS / SMM on states with world_size > 1", id);
         *ptr_dev = it->mom; *count = 3; *dtype = EXORL_XCHG_F64; *op = EXORL_XCHG_GATHER;
+    } else if (id == EXORL_INTR_XCHG_BN) {
+        EXORL_REQUIRE(it->bnmom, "intr_exchange: exchange %d belongs to RND on state rows with world_size > 1", id);
+        *ptr_dev = it->bnmom; *count = (int64_t)3 * it->cfg.obs_dim; *dtype = EXORL_XCHG_F64; *op = EXORL_XCHG_GATHER;
     } else {
         EXORL_REQUIRE(false, "intr_exchange: unknown exchange %d", id);
     }

@@ -316,7 +316,8 @@ int exorl_adam_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev
 int exorl_soft_update(const float* p_dev, float* target_dev, int64_t n, float tau, void* stream);
 int exorl_ln_tanh_fwd(const float* z_dev, const float* gain_dev, const float* beta_dev, float* h_dev,
                       float* xhat_dev, float* rstd_dev, int32_t rows, int32_t H, void* stream);
-/* kNN particle-entropy building block: out[i][j] = j-th smallest L2 distance from src row i to the tgt rows (sorted). */
+/* kNN particle-entropy building block: out[i][j] = j-th smallest L2 distance from src row i to the tgt rows (sorted). n_tgt <= 8192,
+ * k <= 64; up to 4096 targets a wave holds a row of distances in LDS, above it walks the row in fixed chunks with a running top-k. */
 int exorl_knn_topk(const float* src_dev, int32_t n_src, const float* tgt_dev, int32_t n_tgt, int32_t dim,
                    int32_t k, float* out_dev, void* stream);
 
@@ -363,9 +364,9 @@ typedef struct exorl_intr_cfg {
     float state_ent_coef, latent_ent_coef, latent_cond_ent_coef;
     float goal_x, goal_y; /* smm.py:139 self.goal = (150, 75): p*(s) is 1/dist of obs[:, :2] to it beyond distance 1 */
     int32_t world_size;   /* data-parallel ranks (0 and 1: one): every loss mean, loss gradient and metric is over batch * world_size rows
-                             (the gradients and the metrics are then this rank's partial sums / means); RND / SMM only with
-                             EXORL_INTR_ENCODED; Proto with batch * world_size <= 8192 (its Sinkhorn and candidate draw run over the
-                             gathered global batch, redundantly and identically on every rank) */
+                             (the gradients and the metrics are then this rank's partial sums / means); Proto, ICM-APT and APS with
+                             batch * world_size <= 8192 (Proto's Sinkhorn and candidate draw run over the gathered global batch, redundantly
+                             and identically on every rank; the kNN reward of the other two seeks its neighbours in it) */
     int32_t rank;         /* this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch (SMM's epsilon draws) */
 } exorl_intr_cfg;
 
@@ -434,11 +435,16 @@ int exorl_intr_update(exorl_intr_t* m, const exorl_intr_batch* batch, int32_t tr
  *   EXORL_INTR_XCHG_REP      ICM-APT / APS: the representation rows the kNN reward reads (ICM-APT: trunk(obs); APS: features of next_obs);
  *                            Proto: l2norm(predictor_target(next_obs_target)) for the Sinkhorn assignment (the step) and
  *                            l2norm(predictor(next_obs)) for the candidate draw (the reward), batch x pred_dim per rank
- *   EXORL_INTR_XCHG_MOMENTS  RND / ICM-APT / APS (knn_rms): each rank's (n, mean, M2) of the RMS input, merged in rank order in double
+ *   EXORL_INTR_XCHG_MOMENTS  RND / ICM-APT / APS (knn_rms): each rank's (n, mean, M2) of the RMS input, merged in rank order in double;
+ *                            SMM on state rows: those of log p*(s_j) (metric slots 3 and 7 are then the global values on every rank)
+ *   EXORL_INTR_XCHG_BN       RND on state rows: each rank's per-feature (n, mean, M2) of BatchNorm1d's input, 3 * obs_dim doubles, merged
+ *                            the same way; it is the first exchange of the step, and running_var takes the unbiased estimate over
+ *                            batch * world_size rows
  * With world_size 1 the phases back to back are exorl_intr_update bit for bit (only the gradient exchange is named: a sum over one rank). */
 #define EXORL_INTR_XCHG_GRAD    0
 #define EXORL_INTR_XCHG_REP     1
 #define EXORL_INTR_XCHG_MOMENTS 2
+#define EXORL_INTR_XCHG_BN      3
 #define EXORL_XCHG_F32    0
 #define EXORL_XCHG_F64    1
 #define EXORL_XCHG_SUM    0      /* sum all-reduce of count elements in place */
