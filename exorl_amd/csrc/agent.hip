@@ -92,9 +92,16 @@ struct Fork {
 };
 
 // *l: lo planes of the split-bf16 mode (same shapes as the bf16 buffers; x = hi + lo), null otherwise
-struct FwdBufs { float *h1, *xhat, *rstd, *h2, *out; unsigned short *h1b, *xhatb, *h1l, *xhatl; };
-struct BwdBufs { float *dz2, *dh1; unsigned short *dz2b, *dz2l; };
-struct NetShadow { float* w0t; unsigned short* w1b; unsigned short* w0b; unsigned short *w1l, *w0l; };   // W0 transposed per trunk; W1 as bf16 per head; W0 as K-padded bf16
+// bf16x6 precision on the plane kernel (planes3_ok): hi / mid / lo bf16 images of an fp32 buffer, same shape and pitch (x = hi + mid + lo); all null otherwise
+struct P3 {
+    unsigned short *hi = nullptr, *mid = nullptr, *lo = nullptr;
+    P3 at(int64_t off) const { return hi ? P3{hi + off, mid + off, lo + off} : P3{}; }
+};
+// *p: three-plane images (bf16x6): of h1, written by the forward pass behind the trunk; of dz2, by the backward pass behind the head; of W1
+// ([n_heads][H][H]), behind every optimiser step and exorl_agent_params_changed. One image serves every layout its buffer is read in.
+struct FwdBufs { float *h1, *xhat, *rstd, *h2, *out; unsigned short *h1b, *xhatb, *h1l, *xhatl; P3 h1p; };
+struct BwdBufs { float *dz2, *dh1; unsigned short *dz2b, *dz2l; P3 dz2p; };
+struct NetShadow { float* w0t; unsigned short* w1b; unsigned short* w0b; unsigned short *w1l, *w0l; P3 w1p; };   // W0 transposed per trunk; W1 as bf16 per head; W0 as K-padded bf16
 // bf16 activation pipeline: plain bf16 mode, or split-bf16 with hi/lo planes (H, batch multiples of 64: see planes_ok)
 static bool fast16(int prec, const NetShadow& sh) { return prec == EXORL_PREC_BF16 || (prec == EXORL_PREC_BF16X3 && sh.w1l); }
 static Gemm16Problem g16(const unsigned short* A, const unsigned short* Al, const unsigned short* B, const unsigned short* Bl, int64_t aoff,
@@ -102,6 +109,23 @@ static Gemm16Problem g16(const unsigned short* A, const unsigned short* Al, cons
     Gemm16Problem p{A + aoff, B + boff, C, bias, M, N, K, lda, ldb, ldc};
     if (Al && Bl) { p.A_lo = Al + aoff; p.B_lo = Bl + boff; }
     return p;
+}
+static Gemm16Problem g16x6(const P3& A, const P3& B, int64_t aoff, int64_t boff, float* C, const float* bias, int M, int N, int K, int64_t lda,
+                           int64_t ldb, int64_t ldc) {
+    Gemm16Problem p{A.hi + aoff, B.hi + boff, C, bias, M, N, K, lda, ldb, ldc};
+    p.A_mid = A.mid + aoff; p.B_mid = B.mid + boff; p.A_lo = A.lo + aoff; p.B_lo = B.lo + boff;
+    return p;
+}
+// the H x H products of a bf16x6 agent take the three-plane kernel when the buffers carry plane images (carve: planes3_ok) and the rows tile by
+// 128 (act()'s 64-row chunks do not); otherwise gemm_kernel<EXORL_PREC_BF16X6> splits the fp32 operands while staging
+static bool planes3_route(int prec, const P3& act, const P3& w1, int rows) {
+    return prec == EXORL_PREC_BF16X6 && act.hi && w1.hi && rows % 128 == 0;
+}
+// W1 of every head -> its three plane images, one launch. Once per optimiser step (and per exorl_agent_params_changed) rather than once per use:
+// a TD3+BC step reads the critic's W1 in five launches and the actor's in two.
+static int refresh_w1_planes(const NetDesc& d, const float* P, const NetShadow& sh, hipStream_t s) {
+    if (!sh.w1p.hi) return 0;
+    return to_planes3(P + d.W1, d.H, d.H, d.H, sh.w1p.hi, sh.w1p.mid, sh.w1p.lo, d.H, d.H, d.n_heads, d.head_stride, (int64_t)d.H * d.H, s);
 }
 struct Partials { float *Ph, *Pt, *Pw; };                  // per-chunk partial gradients (fused.hip)
 
@@ -138,6 +162,13 @@ static int net_forward(const NetDesc& d, const float* P, const NetShadow& sh, co
         for (int i = 0; i < d.n_heads; ++i)
             q[i] = g16(f.h1b, f.h1l, sh.w1b, sh.w1l, (d.n_trunks == d.n_heads ? i : 0) * act, (int64_t)i * H * H, f.h2 + i * act,
                        P + d.b1 + i * d.head_stride, rows, H, H, H, H, H);
+        EXORL_TRY(gemm16_grouped(0, 0, q, d.n_heads, true, false, s));
+    } else if (planes3_route(prec, f.h1p, sh.w1p, rows)) {
+        EXORL_TRY(to_planes3(f.h1, H, d.n_trunks * rows, H, f.h1p.hi, f.h1p.mid, f.h1p.lo, d.n_trunks * rows, H, 1, 0, 0, s));
+        Gemm16Problem q[2];
+        for (int i = 0; i < d.n_heads; ++i)
+            q[i] = g16x6(f.h1p, sh.w1p, (d.n_trunks == d.n_heads ? i : 0) * act, (int64_t)i * H * H, f.h2 + i * act, P + d.b1 + i * d.head_stride,
+                         rows, H, H, H, H, H);
         EXORL_TRY(gemm16_grouped(0, 0, q, d.n_heads, true, false, s));
     } else {
         GemmProblem p[2];
@@ -264,6 +295,28 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
             } else {
                 for (int i = 0; i < d.n_heads; ++i) EXORL_TRY(gemm16_grouped(0, 1, q + i, 1, false, i > 0, s));
             }
+        }
+    } else if (planes3_route(prec, f.h1p, sh.w1p, rows) && b.dz2p.hi) {
+        // the fp32 pipeline's launches (below) on three planes: dz2 converted once for the wgrad and the dgrad, h1's images are the forward pass's
+        EXORL_TRY(to_planes3(b.dz2, H, d.n_heads * rows, H, b.dz2p.hi, b.dz2p.mid, b.dz2p.lo, d.n_heads * rows, H, 1, 0, 0, s));
+        Gemm16Problem q[2];
+        if (G) {
+            EXORL_TRY(fk.fork(s));
+            const int slab = rows >= 8192 ? 1024 : rows;        // as below: no running sum longer than 1024 terms
+            for (int r0 = 0; r0 < rows; r0 += slab) {
+                const int kr = rows - r0 < slab ? rows - r0 : slab;
+                for (int i = 0; i < d.n_heads; ++i)
+                    q[i] = g16x6(b.dz2p, f.h1p, i * act + (int64_t)r0 * H, (paired ? i : 0) * act + (int64_t)r0 * H, G + d.W1 + i * d.head_stride, nullptr,
+                                 H, H, kr, H, H, H);
+                EXORL_TRY(gemm16_grouped(1, 1, q, d.n_heads, false, r0 > 0, fk.side(s)));
+            }
+        }
+        for (int i = 0; i < d.n_heads; ++i)
+            q[i] = g16x6(b.dz2p, sh.w1p, i * act, (int64_t)i * H * H, b.dh1 + (paired ? i : 0) * act, nullptr, rows, H, H, H, H, H);
+        if (paired) {
+            EXORL_TRY(gemm16_grouped(0, 1, q, d.n_heads, false, false, s));
+        } else {
+            for (int i = 0; i < d.n_heads; ++i) EXORL_TRY(gemm16_grouped(0, 1, q + i, 1, false, i > 0, s));
         }
     } else {
         GemmProblem p[2];
@@ -404,6 +457,13 @@ static bool planes_ok(const exorl_agent_cfg& cfg) {
     return cfg.precision == EXORL_PREC_BF16X3 && cfg.hidden_dim % 64 == 0 && cfg.batch % 64 == 0 && trunk_fwd16_supported(cfg.hidden_dim);
 }
 
+// bf16x6 mode runs fp32 mode's pipeline with the H x H products on the three-plane kernel when every one of them tiles by 128 (the kernel has no
+// edge handling): hidden_dim and every row count of the step — B, 2B, CQL's (3n + 1) B, CRR's B num_value_samples, all multiples of B. Other
+// shapes keep the operands fp32 and split them inside the GEMM (gemm_kernel<BF16X6>). The choice is made from the shape alone.
+static bool planes3_ok(const exorl_agent_cfg& cfg) {
+    return cfg.precision == EXORL_PREC_BF16X6 && cfg.hidden_dim % 128 == 0 && cfg.batch % 128 == 0;
+}
+
 static void carve(exorl_agent* a, Carver& c) {
     const auto& cfg = a->cfg;
     const int64_t B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, H = cfg.hidden_dim, W = O + A;
@@ -421,12 +481,18 @@ static void carve(exorl_agent* a, Carver& c) {
     const bool x3 = planes_ok(cfg);
     const bool bf = cfg.precision == EXORL_PREC_BF16 || x3;
     auto take_lo = [&](int64_t n) { return x3 ? take_u16(n) : nullptr; };
+    // three-plane images, from this agent's own workspace and under bf16x6 only: no other precision's layout or size moves
+    const bool p3 = planes3_ok(cfg);
+    auto take_p3 = [&](int64_t n) { P3 p; if (p3) { p.hi = take_u16(n); p.mid = take_u16(n); p.lo = take_u16(n); } return p; };
     a->fa = FwdBufs{c.take(2 * B * H), c.take(2 * B * H), c.take(2 * B), c.take(2 * B * H), c.take(2 * B * AO), bf ? take_u16(2 * B * H) : nullptr,
                     bf ? take_u16(2 * B * H) : nullptr, take_lo(2 * B * H), take_lo(2 * B * H)};
     a->ba = BwdBufs{c.take(B * H), c.take(B * H), bf ? take_u16(B * H) : nullptr, take_lo(B * H)};
+    a->fa.h1p = take_p3(2 * B * H);
+    a->ba.dz2p = take_p3(B * H);
     c.scratch = false;
     a->sh_actor = NetShadow{c.take(O * H), bf ? take_u16(H * H) : nullptr, bf ? take_u16(H * round_up(O, 32)) : nullptr, take_lo(H * H),
                             take_lo(H * round_up(O, 32))};
+    a->sh_actor.w1p = take_p3(H * H);
     c.scratch = true;
     a->pa = Partials{c.take((int64_t)head_chunks(B) * ((AO + 1) * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
                      c.take((int64_t)outer_chunks(B) * O * H)};
@@ -451,6 +517,9 @@ static void carve(exorl_agent* a, Carver& c) {
         a->fc = FwdBufs{c.take(nt * RC * H), c.take(nt * RC * H), c.take(nt * RC), c.take(2 * RC * H), c.take(2 * RC * od), bf ? take_u16(nt * RC * H) : nullptr,
                         bf ? take_u16(nt * RC * H) : nullptr, take_lo(nt * RC * H), take_lo(nt * RC * H)};
         a->bc = BwdBufs{c.take(2 * RC * H), c.take(nt * RC * H), bf ? take_u16(2 * RC * H) : nullptr, take_lo(2 * RC * H)};
+        a->ft.h1p = take_p3(nt * B * H);
+        a->fc.h1p = take_p3(nt * RC * H);
+        a->bc.dz2p = take_p3(2 * RC * H);
         if (cfg.kind == EXORL_AGENT_CQL) {
             a->x_all = c.take(RC * W);
             a->dq_all = c.take(2 * RC);
@@ -468,12 +537,15 @@ static void carve(exorl_agent* a, Carver& c) {
             a->crr_w = c.take(B);
             a->fr = FwdBufs{bf ? nullptr : c.take(nt * R * H), nullptr, nullptr, c.take(2 * R * H), c.take(2 * R), bf ? take_u16(nt * R * H) : nullptr, nullptr,
                             take_lo(nt * R * H), nullptr};
+            a->fr.h1p = take_p3(nt * R * H);
         }
         c.scratch = false;
         a->sh_critic = NetShadow{c.take(nt * W * H), bf ? take_u16(2 * H * H) : nullptr, bf ? take_u16(nt * H * round_up(W, 32)) : nullptr,
                                  take_lo(2 * H * H), take_lo(nt * H * round_up(W, 32))};
         a->sh_target = NetShadow{c.take(nt * W * H), bf ? take_u16(2 * H * H) : nullptr, bf ? take_u16(nt * H * round_up(W, 32)) : nullptr,
                                  take_lo(2 * H * H), take_lo(nt * H * round_up(W, 32))};
+        a->sh_critic.w1p = take_p3(2 * H * H);
+        a->sh_target.w1p = take_p3(2 * H * H);
         c.scratch = true;
         a->pc = Partials{c.take(2 * (int64_t)qhead_chunks(RC) * ((od + 1) * H + 32)), c.take(nt * (int64_t)trunk_chunks(RC) * 3 * H),
                          c.take(nt * (int64_t)outer_chunks(RC) * W * H)};
@@ -496,7 +568,8 @@ static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
                   cfg->obs_dim + cfg->act_dim <= 256 &&
                   cfg->batch > 0, "agent: unsupported dims O=%d A=%d (<=16) H=%d (multiple of 4, <=1024) B=%d; O+A <= 256", cfg->obs_dim, cfg->act_dim,
                   cfg->hidden_dim, cfg->batch);
-    EXORL_REQUIRE(cfg->precision == EXORL_PREC_F32 || cfg->precision == EXORL_PREC_BF16 || cfg->precision == EXORL_PREC_BF16X3, "agent: unknown precision %d", cfg->precision);
+    EXORL_REQUIRE(cfg->precision == EXORL_PREC_F32 || cfg->precision == EXORL_PREC_BF16 || cfg->precision == EXORL_PREC_BF16X3 ||
+                  cfg->precision == EXORL_PREC_BF16X6, "agent: unknown precision %d", cfg->precision);
     EXORL_REQUIRE(cfg->world_size >= 1, "agent: world_size must be >= 1");
     EXORL_REQUIRE(cfg->precision != EXORL_PREC_BF16 || (cfg->hidden_dim % 8 == 0 && cfg->batch % 8 == 0),
                   "agent: bf16 precision needs hidden_dim and batch to be multiples of 8 (got H=%d B=%d)", cfg->hidden_dim, cfg->batch);
@@ -541,8 +614,12 @@ static FusedAdamArgs fused_adam_args(exorl_agent* a, int net, const NetDesc& d, 
 static int opt_step(exorl_agent* a, int net, const NetDesc& d, const FinalizeArgs& pend, const AdamConst* c, float* target, const ShadowSpec& spec,
                     uint64_t* bump, hipStream_t s) {
     float** f = a->flat[net];
-    if (a->fuse_opt) return finalize_adam(pend, fused_adam_args(a, net, d, c, target, bump), spec, s);
-    return adam_step_dev(f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], d.total, c, target, &spec, s, bump);
+    if (a->fuse_opt) EXORL_TRY(finalize_adam(pend, fused_adam_args(a, net, d, c, target, bump), spec, s));
+    else EXORL_TRY(adam_step_dev(f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], d.total, c, target, &spec, s, bump));
+    // bf16x6 on the plane kernel: the stepped W1 (and the Polyak target's) as three planes for the next step's launches
+    EXORL_TRY(refresh_w1_planes(d, f[EXORL_T_PARAM], net == EXORL_NET_ACTOR ? a->sh_actor : a->sh_critic, s));
+    if (target) EXORL_TRY(refresh_w1_planes(d, target, a->sh_target, s));
+    return 0;
 }
 static int opt_step_critic(exorl_agent* a, hipStream_t s) {
     return opt_step(a, EXORL_NET_CRITIC, a->critic, a->pend_c, &a->state->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->spec_critic,
@@ -692,6 +769,7 @@ static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
               a->fa.out + (int64_t)B * A, a->fa.h1b ? a->fa.h1b + (int64_t)B * H : nullptr,
               a->fa.xhatb ? a->fa.xhatb + (int64_t)B * H : nullptr, a->fa.h1l ? a->fa.h1l + (int64_t)B * H : nullptr,
               a->fa.xhatl ? a->fa.xhatl + (int64_t)B * H : nullptr};
+    f.h1p = a->fa.h1p.at((int64_t)B * H);
     if (!a->has_critic)       // BC (bc.py:82): the only forward of the step
         EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa + (int64_t)B * O, O, B, f, true, true, prec, s));
     if (a->want_metrics)                        // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
@@ -795,6 +873,7 @@ static int cql_phase2(exorl_agent* a, hipStream_t s) {
               a->fa.out + (int64_t)B * 2 * A, a->fa.h1b ? a->fa.h1b + (int64_t)B * H : nullptr,
               a->fa.xhatb ? a->fa.xhatb + (int64_t)B * H : nullptr, a->fa.h1l ? a->fa.h1l + (int64_t)B * H : nullptr,
               a->fa.xhatl ? a->fa.xhatl + (int64_t)B * H : nullptr};
+    f.h1p = a->fa.h1p.at((int64_t)B * H);
     DoutSpec dm{};
     dm.mode = EXORL_DOUT_CQL_ACTOR; dm.da = a->da; dm.da_nets = a->critic.n_trunks; dm.raw = f.out; dm.z = a->noise_a;
     dm.alpha_ptr = &a->cql->alpha; dm.inv_bg = a->inv_bg; dm.seed = cfg.seed; dm.counter = 4; dm.counter_ptr = &a->state->noise_counter;
@@ -915,7 +994,10 @@ int exorl_agent_params_changed(exorl_agent_t* a, int32_t sync_target, void* stre
     if (a->has_critic) {
         EXORL_TRY(refresh_shadows(a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->critic.total, a->spec_critic, false, s));
         EXORL_TRY(refresh_shadows(a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->critic.total, a->spec_critic, true, s));
+        EXORL_TRY(refresh_w1_planes(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, s));
+        EXORL_TRY(refresh_w1_planes(a->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->sh_target, s));
     }
+    EXORL_TRY(refresh_w1_planes(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, s));
     return 0;
 }
 

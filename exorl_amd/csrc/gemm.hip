@@ -7,13 +7,18 @@
 //  actor / critic layers of agent.hip in fp32 precision)
 //  * gemm_kernel<PREC, AL, BL, VEC>: 64 x 64 tile, register-staged double buffer, all four layout pairs, any shape (bounds-guarded; VEC = the
 //    16-byte loads where pointers and pitches allow). PREC picks the product: exact fp32 (v_mfma_f32_32x32x2_f32), bf16, split bf16 in two
-//    (bf16x3) or three (bf16x6) planes made while staging. Taken whenever planes_adapter is not.
+//    (bf16x3) or three (bf16x6) planes made while staging. Taken whenever planes_adapter is not. (bf16x6 state agents whose shapes tile by 128
+//    do not come here: agent.hip converts their operands to three planes and calls gemm16_grouped, below.)
 //  * planes_adapter: bf16x3 problems with M, N, K >= 256 in one of the three nn.Linear layout pairs, outside a stream capture. Writes zero-padded
 //    hi/lo bf16 planes of both operands into a scratch arena and hands them to gemm16_grouped, where (padded to multiples of 128) they take the
 //    gemm16p kernels: the same arithmetic at about four times the rate of gemm_kernel. The reward-free agents' updates reach it.
 //
-//  bf16 operands in memory, plain or as hi/lo planes (gemm16_grouped, gemm16_grouped_mixed; the H x H layers of every actor / critic in
-//  agent.hip in bf16 and bf16x3 precision, and planes_adapter). One ladder, pick16(), first match wins:
+//  bf16 operands in memory, plain, as hi/lo planes or as hi/mid/lo planes (gemm16_grouped, gemm16_grouped_mixed; the H x H layers of every actor /
+//  critic in agent.hip in bf16, bf16x3 and — at hidden_dim and batch multiples of 128 — bf16x6 precision, and planes_adapter). One ladder,
+//  pick16(), first match wins:
+//  * three planes (Gemm16Problem::A_mid; exorl_gemm_planes3, agent.hip's bf16x6 route): gemm16p_kernel<AT, BT, 3, 64> or an error — 128 x 64
+//    tiles, k32 stages four deep (144 KB of LDS), gemm_kernel<BF16X6>'s six products in three accumulator classes; the three uniform forms, no
+//    mixed one. Needs what the next entry needs. The planes come from to_planes3_kernel (fp32 -> three bf16 images, one pass per buffer).
 //  * gemm16p_kernel / gemm16p_mixed_kernel: 128 x TN tiles, LDS-DMA stage ring, XCD-local tile blocks, float4 epilogue. Needs M % 128, N % 64,
 //    K % 128 = 0, 16-byte aligned operands, lo planes, C and bias, ldc % 4 = 0. TN = 128 when every N allows it and the launch still has 256
 //    workgroups, else 64. Every launch of the product at hidden_dim and batch multiples of 128 (the 1024-wide flagship step among them).
@@ -778,21 +783,27 @@ __device__ __forceinline__ void g16p_lds_fence(G16pFrag& f) {
 // commit d23b35a) put the k-loop at MFMA cycles + ~60 cycles per DMA piece of the wave: the four waves issue their pieces together, the
 // CU's vector-memory path takes them one at a time, and a wave blocked on an issue cannot feed its matrix pipe. Spread over two regions
 // the same pieces have twice the MFMAs to hide behind.
-template <bool AT, bool BT, bool X3, int TN, int KS, int NSTG>
+// NPL = operand planes: 1 plain bf16; 2 split bf16 (hi, lo: hi*hi + hi*lo + lo*hi); 3 three-plane split (hi, mid, lo: + mid*hi + hi*mid in the
+// second accumulator class, hi*lo + lo*hi + mid*mid in a third; Gemm16Problem::A_mid). Three planes at TN = 64, KS = 32, NSTG = 4 are
+// (128 + 64) rows x 64 B x 3 x 4 = 144 KB of the 160 KB of LDS, 9 DMA pieces per wave and stage, 12 MFMAs and 9 fragments per k16.
+template <bool AT, bool BT, int NPL, int TN, int KS, int NSTG>
 __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned char* smem, int pidx, int m0, int n0) {
-    constexpr int NW = 4, NBA = 2, NBB = TN / 64, NPL = X3 ? 2 : 1;
+    constexpr int NW = 4, NBA = 2, NBB = TN / 64;
+    constexpr bool X3 = NPL == 2, X6 = NPL == 3;
+    static_assert(NPL >= 1 && NPL <= 3, "operand planes");
     constexpr int WR = 64, WC = TN / 2;                     // wave tile: WR rows x WC columns
     constexpr int WN = TN / WC;                             // waves along N (the rest along M)
     constexpr int BLK = 64 * 2 * KS;                        // one 64-row block of one plane and stage (either image kind)
     constexpr int PLANE = (NBA + NBB) * BLK;                // [A blk0][A blk1][B blk0][B blk1]
-    constexpr int STAGE = NPL * PLANE;                      // hi plane, then lo plane
+    constexpr int STAGE = NPL * PLANE;                      // hi plane, then (mid plane and) lo plane
     constexpr int PPW = KS / 8 / NW;                        // 1-KB DMA pieces per wave and block
     constexpr int NP = (NBA + NBB) * NPL * PPW;             // DMA pieces per wave and stage
     constexpr int NQ = KS / 16;                             // regions (k16) per stage
     constexpr int SA = WR / 32;                             // 32-row sub-tiles of a wave along M
     constexpr int SB = WC / 32;                             // 32-column sub-tiles of a wave along N
     constexpr int NPAIR = SA * SB;                          // 32 x 32 accumulators of a wave
-    constexpr int NM = NPAIR * (X3 ? 3 : 1);                // MFMAs per region
+    constexpr int TERMS = X6 ? 6 : (X3 ? 3 : 1);            // plane products formed per accumulator tile
+    constexpr int NM = NPAIR * TERMS;                       // MFMAs per region
     constexpr int NF = (SA + SB) * NPL;                     // fragments per region
     constexpr int SMIN = SA < SB ? SA : SB;
     typedef float acc_t __attribute__((ext_vector_type(16)));
@@ -808,11 +819,13 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
     const int arow0 = (wm * WR) & 63, ablk = (wm * WR) >> 6;        // this wave's rows inside A block ablk
     const int bcol0 = (wn * WC) & 63, bblk = (wn * WC) >> 6;        // this wave's columns inside B block bblk
 
-    acc_t acc[NPAIR], accx[X3 ? NPAIR : 1];                 // [ua * SB + ub]; accx: the two cross terms hi*lo + lo*hi
+    // [ua * SB + ub]; accx: the cross terms with the second plane (hi*lo + lo*hi; three planes: hi*mid + mid*hi); accy: three planes' third
+    // class hi*lo + lo*hi + mid*mid
+    acc_t acc[NPAIR], accx[NPL > 1 ? NPAIR : 1], accy[X6 ? NPAIR : 1];
 #pragma unroll
     for (int a = 0; a < NPAIR; ++a)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[a][i] = 0.f; if constexpr (X3) accx[a][i] = 0.f; }
+        for (int i = 0; i < 16; ++i) { acc[a][i] = 0.f; if constexpr (NPL > 1) accx[a][i] = 0.f; if constexpr (X6) accy[a][i] = 0.f; }
 
     // row image: 2*KS-byte rows, 16-byte units swizzled so that the 16 lanes of a ds_read_b128 group hit 16 distinct bank quads
     auto row_off = [](int row, int unit) {
@@ -840,13 +853,14 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
                     const int usrc = KS == 32 ? (ur ^ ((irow >> 2) & 3)) : (ur ^ ((irow >> 1) & 7));
                     const int64_t o = !tr ? (int64_t)(r0 + irow) * ld + 8 * usrc
                                           : (int64_t)(8 * pc + r8) * ld + r0 + 8 * (u8 ^ (4 * ((r8 >> 1) & 1)));
-                    const unsigned short* base = isA ? (pl ? P.A_lo : P.A) : (pl ? P.B_lo : P.B);
+                    // plane order in LDS: hi, [mid,] lo
+                    const unsigned short* base = isA ? (pl == 0 ? P.A : (X6 && pl == 1 ? P.A_mid : P.A_lo)) : (pl == 0 ? P.B : (X6 && pl == 1 ? P.B_mid : P.B_lo));
                     src[(pl * (NBA + NBB) + b) * PPW + j] = base + o;
                 }
     }
     const int64_t kstepA = AT ? KS * P.lda : KS, kstepB = BT ? KS * P.ldb : KS;
 
-    // ---- fragment offsets inside a stage's hi plane (lo plane: + PLANE)
+    // ---- fragment offsets inside a stage's hi plane (the next planes: + PLANE each)
     const int g = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
     auto tr_off = [&](int rbase) {      // k image: k-row 8*(g>>1)+qq (+4 for the second half), columns rbase + 16*(g&1) + 4*pp ..+3
         const int c = rbase + 16 * (g & 1) + 4 * pp;
@@ -874,46 +888,52 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
     auto fill = [&](int st) { g16p_static_for<0, NP>([&](auto ic) { fill_one(st, ic); }); };
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;       // LDS byte address of the ring
-    auto frag = [&](G16pFrag& f, auto plane, bool tr, int st, int off) {     // plane 0 = hi, 1 = lo
+    auto frag = [&](G16pFrag& f, auto plane, bool tr, int st, int off) {     // plane 0 = hi, 1 = lo (three planes: 1 = mid, 2 = lo)
         constexpr int PL = decltype(plane)::value * PLANE;
         if (!tr) { f.v = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(smem + st * STAGE + PL + off)); return; }
         const unsigned a = lds0 + st * STAGE + off;
         f.lo = g16p_read_tr<PL>(a);
         f.hi = g16p_read_tr<PL + 4 * ROWB>(a);
     };
-    struct Frags { G16pFrag ah[SA], bh[SB], al[X3 ? SA : 1], bl[X3 ? SB : 1]; };
+    struct Frags { G16pFrag ah[SA], bh[SB], al[NPL > 1 ? SA : 1], bl[NPL > 1 ? SB : 1], at[X6 ? SA : 1], bt[X6 ? SB : 1]; };     // planes 0, 1, 2
     // fragment J of a region, in the order the MFMAs want them: per plane A0 B0 A1 B1 ... interleaved, then the rest of the longer list
     auto read_one = [&](Frags& f, int st, auto qc, auto jc) {
         constexpr int J = decltype(jc)::value, q = decltype(qc)::value;
-        constexpr int pl = X3 ? J % 2 : 0, k = X3 ? J / 2 : J;           // k: 0 = A0, 1 = B0, 2 = A1, 3 = B1, ...
+        constexpr int pl = J % NPL, k = J / NPL;                         // k: 0 = A0, 1 = B0, 2 = A1, 3 = B1, ...
         constexpr bool isA = k < 2 * SMIN ? k % 2 == 0 : SA > SB;
         constexpr int u = k < 2 * SMIN ? k / 2 : k - SMIN;
         if constexpr (isA) {
             if constexpr (pl == 0) frag(f.ah[u], std::integral_constant<int, 0>{}, AT, st, aoff[u][q]);
-            else frag(f.al[u], std::integral_constant<int, 1>{}, AT, st, aoff[u][q]);
+            else if constexpr (pl == 1) frag(f.al[u], std::integral_constant<int, 1>{}, AT, st, aoff[u][q]);
+            else frag(f.at[u], std::integral_constant<int, 2>{}, AT, st, aoff[u][q]);
         } else {
             if constexpr (pl == 0) frag(f.bh[u], std::integral_constant<int, 0>{}, BT, st, boff[u][q]);
-            else frag(f.bl[u], std::integral_constant<int, 1>{}, BT, st, boff[u][q]);
+            else if constexpr (pl == 1) frag(f.bl[u], std::integral_constant<int, 1>{}, BT, st, boff[u][q]);
+            else frag(f.bt[u], std::integral_constant<int, 2>{}, BT, st, boff[u][q]);
         }
     };
     auto fence = [&](Frags& f) {               // the asm-issued transposed reads of f have landed (see g16p_read_tr)
         if constexpr (AT) {
 #pragma unroll
-            for (int u = 0; u < SA; ++u) { g16p_lds_fence(f.ah[u]); if constexpr (X3) g16p_lds_fence(f.al[u]); }
+            for (int u = 0; u < SA; ++u) { g16p_lds_fence(f.ah[u]); if constexpr (NPL > 1) g16p_lds_fence(f.al[u]); if constexpr (X6) g16p_lds_fence(f.at[u]); }
         }
         if constexpr (BT) {
 #pragma unroll
-            for (int u = 0; u < SB; ++u) { g16p_lds_fence(f.bh[u]); if constexpr (X3) g16p_lds_fence(f.bl[u]); }
+            for (int u = 0; u < SB; ++u) { g16p_lds_fence(f.bh[u]); if constexpr (NPL > 1) g16p_lds_fence(f.bl[u]); if constexpr (X6) g16p_lds_fence(f.bt[u]); }
         }
     };
     // MFMA I of a k16. Operands swapped: the accumulator is the TRANSPOSED 32 x 32 block, i.e. lane = output row, registers r..r+3 =
     // four consecutive output columns -> the epilogue stores 16 bytes per lane (16 stores per wave instead of 64)
     auto mfma_one = [&](const Frags& f, auto ic) {
         constexpr int I = decltype(ic)::value;
-        constexpr int pair = X3 ? I / 3 : I, term = X3 ? I % 3 : 0, ua = pair / SB, ub = pair % SB;
+        constexpr int pair = I / TERMS, term = I % TERMS, ua = pair / SB, ub = pair % SB;
         if constexpr (term == 0) acc[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bh[ub].v, f.ah[ua].v, acc[pair], 0, 0, 0);
         else if constexpr (term == 1) accx[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bl[ub].v, f.ah[ua].v, accx[pair], 0, 0, 0);
-        else accx[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bh[ub].v, f.al[ua].v, accx[pair], 0, 0, 0);
+        else if constexpr (term == 2) accx[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bh[ub].v, f.al[ua].v, accx[pair], 0, 0, 0);
+        // three planes (al / bl hold mid, at / bt hold lo): A_hi B_lo, A_lo B_hi, A_mid B_mid
+        else if constexpr (term == 3) accy[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bt[ub].v, f.ah[ua].v, accy[pair], 0, 0, 0);
+        else if constexpr (term == 4) accy[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bh[ub].v, f.at[ua].v, accy[pair], 0, 0, 0);
+        else accy[pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.bl[ub].v, f.al[ua].v, accy[pair], 0, 0, 0);
     };
     // One scheduling region = the NM MFMAs of a k16 on `cur`, with the reads of the NEXT k16's fragments (stage slot nst_, region NQn) into
     // `nxt` (FPG per MFMA gap) and, when NFILL > 0, this region's half (chunk) of the DMA issues of stage slot `fst` written out between them; sched_barrier(0)
@@ -1001,6 +1021,12 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
     }
 
     const bool relu = gb.relu != 0;
+    // the accumulator classes of output element (pair, i), smallest class first
+    auto total = [&](int pair, int i) {
+        if constexpr (X6) return (accy[pair][i] + accx[pair][i]) + acc[pair][i];
+        else if constexpr (X3) return accx[pair][i] + acc[pair][i];
+        else return acc[pair][i];
+    };
     if (P.head_part) {
         // folded scalar head: this wave's share of relu(acc + bias) . head_w for each of its rows; lanes l and l + 32 hold the two column
         // interleaves of one row. Nothing of C is stored.
@@ -1010,17 +1036,15 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
 #pragma unroll
             for (int tb = 0; tb < SB; ++tb) {
                 const int nb = n0 + wn * WC + tb * 32 + 4 * h;
-                const acc_t& a0 = acc[ta * SB + tb];
-                const acc_t& ax = accx[X3 ? ta * SB + tb : 0];
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const float4 bias = P.bias ? *reinterpret_cast<const float4*>(P.bias + nb + 8 * g4) : make_float4(0.f, 0.f, 0.f, 0.f);
                     const float4 w = *reinterpret_cast<const float4*>(P.head_w + nb + 8 * g4);
                     float4 v;
-                    v.x = (X3 ? ax[4 * g4 + 0] + a0[4 * g4 + 0] : a0[4 * g4 + 0]) + bias.x;
-                    v.y = (X3 ? ax[4 * g4 + 1] + a0[4 * g4 + 1] : a0[4 * g4 + 1]) + bias.y;
-                    v.z = (X3 ? ax[4 * g4 + 2] + a0[4 * g4 + 2] : a0[4 * g4 + 2]) + bias.z;
-                    v.w = (X3 ? ax[4 * g4 + 3] + a0[4 * g4 + 3] : a0[4 * g4 + 3]) + bias.w;
+                    v.x = total(ta * SB + tb, 4 * g4 + 0) + bias.x;
+                    v.y = total(ta * SB + tb, 4 * g4 + 1) + bias.y;
+                    v.z = total(ta * SB + tb, 4 * g4 + 2) + bias.z;
+                    v.w = total(ta * SB + tb, 4 * g4 + 3) + bias.w;
                     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     dot += (v.x * w.x + v.y * w.y) + (v.z * w.z + v.w * w.w);
                 }
@@ -1036,18 +1060,16 @@ __device__ __forceinline__ void gemm16p_body(const Gemm16Batch& gb, unsigned cha
             // lane: output row m0 + .. + (lane & 31); registers 4g..4g+3: columns nb + 8g + 4h .. +3
             const int nb = n0 + wn * WC + tb * 32 + 4 * h;
             float* crow = P.C + (int64_t)(m0 + wm * WR + ta * 32 + (lane & 31)) * P.ldc + nb;
-            const acc_t& a0 = acc[ta * SB + tb];
-            const acc_t& ax = accx[X3 ? ta * SB + tb : 0];
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 if (P.n_store && nb + 8 * g4 >= P.n_store) continue;        // columns of the padded operand planes that C does not have
                 float4* dst = reinterpret_cast<float4*>(crow + 8 * g4);
                 const float4 bias = P.bias ? *reinterpret_cast<const float4*>(P.bias + nb + 8 * g4) : make_float4(0.f, 0.f, 0.f, 0.f);
                 float4 v;
-                v.x = (X3 ? ax[4 * g4 + 0] + a0[4 * g4 + 0] : a0[4 * g4 + 0]) + bias.x;
-                v.y = (X3 ? ax[4 * g4 + 1] + a0[4 * g4 + 1] : a0[4 * g4 + 1]) + bias.y;
-                v.z = (X3 ? ax[4 * g4 + 2] + a0[4 * g4 + 2] : a0[4 * g4 + 2]) + bias.z;
-                v.w = (X3 ? ax[4 * g4 + 3] + a0[4 * g4 + 3] : a0[4 * g4 + 3]) + bias.w;
+                v.x = total(ta * SB + tb, 4 * g4 + 0) + bias.x;
+                v.y = total(ta * SB + tb, 4 * g4 + 1) + bias.y;
+                v.z = total(ta * SB + tb, 4 * g4 + 2) + bias.z;
+                v.w = total(ta * SB + tb, 4 * g4 + 3) + bias.w;
                 if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 if (gb.accumulate) { const float4 o = *dst; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
                 *dst = v;
@@ -1073,23 +1095,24 @@ __device__ __forceinline__ bool g16p_tile(const Gemm16Batch& gb, int& pidx, int&
     return true;
 }
 
-template <bool AT, bool BT, bool X3, int TN, int KS = 32, int NSTG = 4>
+template <bool AT, bool BT, int NPL, int TN, int KS = 32, int NSTG = 4>
 __global__ __launch_bounds__(256) void gemm16p_kernel(const Gemm16Batch gb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
     int pidx, m0, n0;
     if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    gemm16p_body<AT, BT, X3, TN, KS, NSTG>(gb, smem_p, pidx, m0, n0);
+    gemm16p_body<AT, BT, NPL, TN, KS, NSTG>(gb, smem_p, pidx, m0, n0);
 }
 
-template <bool X3, int TN>      // wgrad (A as a k image) and dgrad (A as a row image) of one Linear(H,H) in one launch; B is a k image in both
+template <int NPL, int TN>      // wgrad (A as a k image) and dgrad (A as a row image) of one Linear(H,H) in one launch; B is a k image in both
 __global__ __launch_bounds__(256) void gemm16p_mixed_kernel(const Gemm16Batch gb) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
     int pidx, m0, n0;
     if (!g16p_tile<TN>(gb, pidx, m0, n0)) return;
-    if (gb.a_t[pidx]) gemm16p_body<true, true, X3, TN, 32, 4>(gb, smem_p, pidx, m0, n0);
-    else gemm16p_body<false, true, X3, TN, 32, 4>(gb, smem_p, pidx, m0, n0);
+    if (gb.a_t[pidx]) gemm16p_body<true, true, NPL, TN, 32, 4>(gb, smem_p, pidx, m0, n0);
+    else gemm16p_body<false, true, NPL, TN, 32, 4>(gb, smem_p, pidx, m0, n0);
 }
-constexpr int g16p_lds(bool x3, int tn, int ks = 32, int nstg = 4) { return nstg * (x3 ? 2 : 1) * (2 + tn / 64) * 64 * 2 * ks; }
+constexpr int g16p_lds(int npl, int tn, int ks = 32, int nstg = 4) { return nstg * npl * (2 + tn / 64) * 64 * 2 * ks; }
+static_assert(g16p_lds(3, 64) == 147456, "three planes, 128 x 64 tile, four k32 stages");
 
 static bool g16p_uniform(const Gemm16Batch& gb, int count, int tn) {       // xcd_tile()'s preconditions
     if (!(count == 1 || count == 2 || count == 4)) return false;
@@ -1101,8 +1124,8 @@ static bool g16p_uniform(const Gemm16Batch& gb, int count, int tn) {       // xc
     return true;
 }
 template <typename K>
-static int g16p_launch(K kernel, Gemm16Batch& gb, int count, bool x3, int tn, hipStream_t s, int ks = 32, int nstg = 4) {
-    const int lds = g16p_lds(x3, tn, ks, nstg);
+static int g16p_launch(K kernel, Gemm16Batch& gb, int count, int npl, int tn, hipStream_t s, int ks = 32, int nstg = 4) {
+    const int lds = g16p_lds(npl, tn, ks, nstg);
     static std::vector<const void*> enabled;         // > 64 KB of dynamic LDS needs the opt-in, once per kernel
     if (std::find(enabled.begin(), enabled.end(), (const void*)kernel) == enabled.end()) {
         EXORL_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -1147,7 +1170,7 @@ __global__ __launch_bounds__(256) void gemm16g_mixed_kernel(const Gemm16Batch gb
 // Every entry point gathers the same facts about its problems in one pass (gather16), asks the one ladder (pick16) for a kernel family,
 // and launches the instantiation of that family for its operand form (launch16).
 enum class Form { row_row, row_k, k_k, mixed };      // (A, B) images; mixed: A per problem (Gemm16Batch::a_t), B a k image
-enum class Family { p, x3, g, reg, none };           // none: split-bf16 planes that no kernel can read (missing, misaligned, M/N/K not of 64)
+enum class Family { p, x3, g, reg, none };           // none: split-bf16 planes that no kernel can read (missing, misaligned, M/N/K not of 64; three planes: not of 128 x 64 x 128)
 
 struct Facts16 {
     int m_div = 256, n_div = 256, k_div = 256;       // largest power of two, up to 256, that divides every problem's M / N / K
@@ -1155,6 +1178,8 @@ struct Facts16 {
     bool ab16 = true;        // A, B 16-byte aligned with pitches that are multiples of 8 bf16: what every LDS-DMA kernel asks of its operands
     bool has_lo = false;     // some problem carries a lo plane: a split-bf16 launch
     bool lo16 = true;        // every problem carries both lo planes, 16-byte aligned
+    bool has_mid = false;    // some problem carries a mid plane: a three-plane launch
+    bool mid16 = true;       // every problem carries both mid planes, 16-byte aligned
     bool c16 = true;         // C and bias 16-byte aligned, ldc a multiple of 4 floats: the float4 epilogue of the p kernels
     int t64 = 0, t128x64 = 0;      // most 64 x 64 / 128 x 64 tiles (partial ones included) any one problem has: grid.x of the 64-wide kernels
     int t128 = 0;            // 128 x 128 tiles of the whole launch
@@ -1174,6 +1199,8 @@ static Facts16 gather16(const Gemm16Problem* probs, int count, Gemm16Batch& gb) 
         f.ab16 = f.ab16 && p.lda % 8 == 0 && p.ldb % 8 == 0 && al16(p.A) && al16(p.B);
         f.has_lo = f.has_lo || p.A_lo || p.B_lo;
         f.lo16 = f.lo16 && p.A_lo && p.B_lo && al16(p.A_lo) && al16(p.B_lo);
+        f.has_mid = f.has_mid || p.A_mid || p.B_mid;
+        f.mid16 = f.mid16 && p.A_mid && p.B_mid && al16(p.A_mid) && al16(p.B_mid);
         f.c16 = f.c16 && p.ldc % 4 == 0 && al16(p.C) && al16(p.bias);
         f.t64 = std::max(f.t64, cdiv(p.M, 64) * cdiv(p.N, 64));
         f.t128x64 = std::max(f.t128x64, cdiv(p.M, 128) * cdiv(p.N, 64));
@@ -1190,24 +1217,29 @@ static Pick16 pick16(const Facts16& f) {
     // TN = 128 only when that still gives every CU a workgroup (4-problem launches of 1024^2 outputs are 256 of them): with fewer, one
     // workgroup per CU leaves the k-tile chain wait -> barrier -> DMA issue -> LDS reads -> MFMA exposed and 128-wide tiles measured slower
     // than narrower ones on the 1024-wide layers (profiles/r02_gemm_shapes_old_vs_new.txt, "128x128 everywhere").
-    if (f.ab16 && (!f.has_lo || f.lo16) && f.c16 && f.m_div >= 128 && f.n_div >= 64 && f.k_div >= 128 && f.k_min >= 128)
-        return {Family::p, f.n_div >= 128 && f.t128 >= 256 ? 128 : 64};
+    const bool p_ok = f.ab16 && (!f.has_lo || f.lo16) && f.c16 && f.m_div >= 128 && f.n_div >= 64 && f.k_div >= 128 && f.k_min >= 128;
+    // three planes: the 128 x 64 p kernel or nothing (the callers route other shapes to gemm_kernel<EXORL_PREC_BF16X6>)
+    if (f.has_mid) return {p_ok && f.mid16 && f.lo16 ? Family::p : Family::none, 64};
+    if (p_ok) return {Family::p, f.n_div >= 128 && f.t128 >= 256 ? 128 : 64};
     // 64 x 64 LDS-DMA tiles, scalar epilogue stores (nothing asked of C): split planes two stages deep, plain ones four (K a multiple of 4 x 64)
     if (f.has_lo) return {f.ab16 && f.lo16 && f.m_div >= 64 && f.n_div >= 64 && f.k_div >= 64 ? Family::x3 : Family::none, 0};
     if (f.ab16 && f.m_div >= 64 && f.n_div >= 64 && f.k_div >= 256) return {Family::g, 0};
     return {Family::reg, 0};                         // register-staged, any shape the entry point's alignment rules admit
 }
 
-template <Form F, bool X3, int TN>
+template <Form F, int NPL, int TN>
 static int launch16p(Gemm16Batch& gb, int count, hipStream_t s) {
-    if constexpr (F == Form::mixed) return g16p_launch(gemm16p_mixed_kernel<X3, TN>, gb, count, X3, TN, s);
+    constexpr bool X3 = NPL == 2;
+    // three planes: one instantiation per uniform form (TN = 64, k32 stages, four deep); no caller needs the mixed form (refused at the entry)
+    if constexpr (NPL == 3 && (F == Form::mixed || TN != 64)) { set_error("gemm16: no three-plane kernel of this form"); return 2; }
+    else if constexpr (F == Form::mixed) return g16p_launch(gemm16p_mixed_kernel<NPL, TN>, gb, count, NPL, TN, s);
     // split planes, both operands row images (the forward launches): 64-wide stages, two deep — whole cache lines per DMA row instead of halves, which
     // halves the requests the XCD L2s serve (critic fwd 21.8 -> 19.5 us, actor fwd 21.1 -> 18.9, critic+target fwd 33.7 -> 32.4)
-    else if constexpr (F == Form::row_row && X3) return g16p_launch(gemm16p_kernel<false, false, true, TN, 64, 2>, gb, count, true, TN, s, 64, 2);
+    else if constexpr (F == Form::row_row && X3) return g16p_launch(gemm16p_kernel<false, false, 2, TN, 64, 2>, gb, count, 2, TN, s, 64, 2);
     // plain bf16 planes take the two-region refill as well (round 3). Round 2 kept them on a one-region refill because the k-image B operand
     // came out wrong, run-to-run different, under the two-region one: that was the pre-fence register copy described in region() — a
     // compiler-placed v_mov of an asm-issued LDS read's destination — not the schedule (tests/test_gpu_ops.py::test_gemm_plain_bf16_k_image_regression).
-    else return g16p_launch(gemm16p_kernel<F == Form::k_k, F != Form::row_row, X3, TN>, gb, count, X3, TN, s);
+    else return g16p_launch(gemm16p_kernel<F == Form::k_k, F != Form::row_row, NPL, TN>, gb, count, NPL, TN, s);
 }
 
 template <Form F>
@@ -1220,8 +1252,9 @@ static int launch16(Gemm16Batch& gb, int count, const Facts16& f, Pick16 pk, hip
     EXORL_TRY(prof.begin(s, f.flops));
     switch (pk.family) {
     case Family::p:
-        if (f.has_lo) EXORL_TRY((pk.tn == 128 ? launch16p<F, true, 128>(gb, count, s) : launch16p<F, true, 64>(gb, count, s)));
-        else EXORL_TRY((pk.tn == 128 ? launch16p<F, false, 128>(gb, count, s) : launch16p<F, false, 64>(gb, count, s)));
+        if (f.has_mid) EXORL_TRY((launch16p<F, 3, 64>(gb, count, s)));
+        else if (f.has_lo) EXORL_TRY((pk.tn == 128 ? launch16p<F, 2, 128>(gb, count, s) : launch16p<F, 2, 64>(gb, count, s)));
+        else EXORL_TRY((pk.tn == 128 ? launch16p<F, 1, 128>(gb, count, s) : launch16p<F, 1, 64>(gb, count, s)));
         break;
     case Family::x3:
         if constexpr (MIXED) hipLaunchKernelGGL(gemm16x3_mixed_kernel, grid64, block, 0, s, gb);
@@ -1247,13 +1280,18 @@ static int launch16(Gemm16Batch& gb, int count, const Facts16& f, Pick16 pk, hip
     return prof.end(s);
 }
 
+static bool pk3_has_mid(const Gemm16Problem* probs, int count) {
+    for (int i = 0; i < count; ++i)
+        if (probs[i].A_mid || probs[i].B_mid) return true;
+    return false;
+}
 // How many head_part slots per row a folded-head forward launch of these problems writes; 0 = the launch would not take the p kernels.
 int gemm16_head_slots(const Gemm16Problem* probs, int count) {
     if (count < 1 || count > 4) return 0;
     Gemm16Batch gb;
     memset(&gb, 0, sizeof(gb));
     const Pick16 pk = pick16(gather16(probs, count, gb));
-    if (pk.family != Family::p) return 0;
+    if (pk.family != Family::p || pk3_has_mid(probs, count)) return 0;
     for (int i = 0; i < count; ++i)
         if (probs[i].N != probs[0].N) return 0;
     return probs[0].N / (pk.tn / 2);            // four waves: 2 x 2, each TN / 2 columns wide
@@ -1285,6 +1323,11 @@ int gemm16_grouped(int a_layout, int b_layout, const Gemm16Problem* probs, int c
         if (probs[i].head_part)
             EXORL_REQUIRE(probs[i].head_w && a_layout == 0 && b_layout == 0 && !accumulate && gemm16_head_slots(probs, count) > 0,
                           "gemm16_grouped: a folded head needs a forward launch on the 128 x TN kernels (ask gemm16_head_slots first)");
+    EXORL_REQUIRE(!f.has_mid || pk.family == Family::p, "gemm16_grouped: three-plane operands need M %% 128 = 0, N %% 64 = 0, K %% 128 = 0 (K >= 128), 16-byte aligned "
+                  "hi/mid/lo planes with pitches that are multiples of 8, 16-byte aligned C and bias, ldc %% 4 = 0 (problem 0: M=%d N=%d K=%d)",
+                  probs[0].M, probs[0].N, probs[0].K);
+    for (int i = 0; i < count; ++i)
+        EXORL_REQUIRE(!f.has_mid || !probs[i].head_part, "gemm16_grouped: no folded head on three-plane operands");
     EXORL_REQUIRE(pk.family != Family::none, "gemm16_grouped: split-bf16 operands need M, N, K multiples of 64 and 16-byte aligned hi/lo planes");
     if (a_layout == 0 && b_layout == 0) return launch16<Form::row_row>(gb, count, f, pk, s);
     if (a_layout == 0 && b_layout == 1) return launch16<Form::row_k>(gb, count, f, pk, s);
@@ -1303,6 +1346,7 @@ int gemm16_grouped_mixed(const int* a_layouts, const Gemm16Problem* probs, int c
     Gemm16Batch gb;
     memset(&gb, 0, sizeof(gb));
     const Facts16 f = gather16(probs, count, gb);
+    EXORL_REQUIRE(!f.has_mid, "gemm16_grouped_mixed: three-plane operands have no mixed wgrad + dgrad form");
     const Pick16 pk = pick16(f);
     bool ok = f.ab16 && f.m_div >= 64 && f.n_div >= 64 && f.k_div >= 256 && pk.family != Family::none;
     for (int i = 0; i < count; ++i) {
@@ -1391,6 +1435,50 @@ __global__ __launch_bounds__(256) void to_planes_kernel(const float* __restrict_
         *reinterpret_cast<uint4*>(hi + (int64_t)r * cols_p + c0) = h;
         *reinterpret_cast<uint4*>(lo + (int64_t)r * cols_p + c0) = l;
     }
+}
+// three-plane sibling: hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid); blockIdx.y = image (see to_planes3 in kernels.h)
+__global__ __launch_bounds__(256) void to_planes3_kernel(const float* __restrict__ src, int64_t ld, int rows, int cols, unsigned short* __restrict__ hi,
+                                                         unsigned short* __restrict__ mid, unsigned short* __restrict__ lo, int rows_p, int cols_p,
+                                                         int64_t src_stride, int64_t dst_stride) {
+    src += blockIdx.y * src_stride;
+    const int64_t dst0 = blockIdx.y * dst_stride;
+    const int64_t groups = (int64_t)rows_p * (cols_p / 8);
+    const bool vec = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / (cols_p / 8)), c0 = (int)(i % (cols_p / 8)) * 8;
+        float v[8], m[8], l[8];
+        if (r < rows && vec && c0 + 8 <= cols) {
+            const float4 a = *reinterpret_cast<const float4*>(src + (int64_t)r * ld + c0), b = *reinterpret_cast<const float4*>(src + (int64_t)r * ld + c0 + 4);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (r < rows && c0 + j < cols) ? src[(int64_t)r * ld + c0 + j] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { m[j] = bf16_residual(v[j]); l[j] = bf16_residual(m[j]); }
+        uint4 h, md, lw;
+        h.x = pack_bf16(v[0], v[1]); h.y = pack_bf16(v[2], v[3]); h.z = pack_bf16(v[4], v[5]); h.w = pack_bf16(v[6], v[7]);
+        md.x = pack_bf16(m[0], m[1]); md.y = pack_bf16(m[2], m[3]); md.z = pack_bf16(m[4], m[5]); md.w = pack_bf16(m[6], m[7]);
+        lw.x = pack_bf16(l[0], l[1]); lw.y = pack_bf16(l[2], l[3]); lw.z = pack_bf16(l[4], l[5]); lw.w = pack_bf16(l[6], l[7]);
+        const int64_t o = dst0 + (int64_t)r * cols_p + c0;
+        *reinterpret_cast<uint4*>(hi + o) = h;
+        *reinterpret_cast<uint4*>(mid + o) = md;
+        *reinterpret_cast<uint4*>(lo + o) = lw;
+    }
+}
+int to_planes3(const float* src, int64_t ld, int rows, int cols, unsigned short* hi, unsigned short* mid, unsigned short* lo, int rows_p, int cols_p,
+               int nb, int64_t src_stride, int64_t dst_stride, hipStream_t s) {
+    auto al16 = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; };
+    EXORL_REQUIRE(src && hi && mid && lo && rows > 0 && cols > 0 && rows_p >= rows && cols_p >= cols && cols_p % 8 == 0 && nb >= 1 && ld >= cols &&
+                  al16(hi) && al16(mid) && al16(lo) && dst_stride % 8 == 0 && (nb == 1 || dst_stride >= (int64_t)rows_p * cols_p),
+                  "to_planes3: bad arguments (rows=%d cols=%d rows_p=%d cols_p=%d nb=%d)", rows, cols, rows_p, cols_p, nb);
+    const int64_t blocks = ((int64_t)rows_p * (cols_p / 8) + 255) / 256;
+    ProfBracket prof;                  // exorl_profile_gemm lists the conversion passes too, with 0 FLOPs (tools/micro/planes_bench.py planes3)
+    EXORL_TRY(prof.begin(s, 0.0));
+    hipLaunchKernelGGL(to_planes3_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks), nb), dim3(256), 0, s, src, ld, rows, cols, hi, mid, lo, rows_p, cols_p,
+                       src_stride, dst_stride);
+    EXORL_LAUNCH_CHECK();
+    return prof.end(s);
 }
 // C[m][n] (+)= Cp[m][n] for the unpadded block
 __global__ __launch_bounds__(256) void from_padded_kernel(const float* __restrict__ cp, int64_t ldp, float* __restrict__ c, int64_t ldc, int M, int N, int accumulate) {
@@ -1616,6 +1704,24 @@ extern "C" int exorl_gemm_planes(int32_t count, const int32_t* a_layouts, int32_
         int at[4];
         for (int i = 0; i < count; ++i) at[i] = a_layouts[i];
         return gemm16_grouped_mixed(at, p, count, as_stream(stream));
+    }
+    return gemm16_grouped(a_layouts[0], b_layout, p, count, relu != 0, false, as_stream(stream));
+}
+
+extern "C" int exorl_gemm_planes3(int32_t count, const int32_t* a_layouts, int32_t b_layout, int32_t M, int32_t N, int32_t K,
+                                  const uint16_t* const* A_hi, const uint16_t* const* A_mid, const uint16_t* const* A_lo, int64_t lda,
+                                  const uint16_t* const* B_hi, const uint16_t* const* B_mid, const uint16_t* const* B_lo, int64_t ldb, float* const* C,
+                                  int64_t ldc, int32_t relu, void* stream) {
+    using namespace exorl;
+    EXORL_REQUIRE(count >= 1 && count <= 4 && a_layouts && A_hi && A_mid && A_lo && B_hi && B_mid && B_lo && C, "gemm_planes3: bad arguments");
+    EXORL_REQUIRE(M > 0 && N > 0 && K > 0 && lda > 0 && ldb > 0 && ldc >= N, "gemm_planes3: bad shape M=%d N=%d K=%d lda=%lld ldb=%lld ldc=%lld", M, N, K,
+                  (long long)lda, (long long)ldb, (long long)ldc);
+    Gemm16Problem p[4];
+    for (int i = 0; i < count; ++i) {
+        EXORL_REQUIRE(a_layouts[i] == a_layouts[0], "gemm_planes3: three-plane operands have no mixed wgrad + dgrad form (one A layout per launch)");
+        EXORL_REQUIRE(A_hi[i] && A_mid[i] && A_lo[i] && B_hi[i] && B_mid[i] && B_lo[i] && C[i], "gemm_planes3: problem %d has a null plane or output", i);
+        p[i] = Gemm16Problem{A_hi[i], B_hi[i], C[i], nullptr, M, N, K, lda, ldb, ldc};
+        p[i].A_mid = A_mid[i]; p[i].B_mid = B_mid[i]; p[i].A_lo = A_lo[i]; p[i].B_lo = B_lo[i];
     }
     return gemm16_grouped(a_layouts[0], b_layout, p, count, relu != 0, false, as_stream(stream));
 }

@@ -36,7 +36,17 @@ struct Gemm16Problem {
     // > 0 (the 128 x TN "p" kernels only; a multiple of 4): only columns [0, n_store) of C exist — N is the padded width of the operand planes.
     // The planes adapter uses it for outputs whose width is not a multiple of the tile (39200-wide module layers) instead of a padded C + copy.
     int n_store = 0;
+    // three-plane split-bf16 ("bf16x6") operands: x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), i.e. the 24
+    // significand bits of an fp32 value. A problem with mid planes carries A_lo / B_lo as its third planes; the product is formed as hi*hi,
+    // hi*mid + mid*hi, hi*lo + lo*hi + mid*mid in three fp32 accumulators summed small-first (mid*lo, lo*mid, lo*lo are dropped: relative error
+    // <= 3 * 2^-24 of |a||b|). One kernel takes such a launch (gemm16p, TN = 64): M % 128, N % 64, K % 128 = 0, 16-byte aligned planes, C and bias.
+    const unsigned short* A_mid = nullptr;
+    const unsigned short* B_mid = nullptr;
 };
+// fp32 (rows x cols, pitch ld) -> three bf16 planes of rows_p x cols_p (>= rows x cols, cols_p % 8 = 0; the padding is written as zeros), for
+// `nb` images `src_stride` floats / `dst_stride` bf16 apart (the heads of a net share a launch). gemm.hip, to_planes3_kernel.
+int to_planes3(const float* src, int64_t ld, int rows, int cols, unsigned short* hi, unsigned short* mid, unsigned short* lo, int rows_p, int cols_p,
+               int nb, int64_t src_stride, int64_t dst_stride, hipStream_t s);
 // slots per row the "p" kernels would write for these problems' head_part (N / wave column block), or 0 when the launch would not take them
 int gemm16_head_slots(const Gemm16Problem* probs, int count);
 // operands stored as bf16 in memory (fast mode); same layout conventions as gemm_grouped

@@ -37,7 +37,8 @@ extern "C" {
                                     10: exorl_pixel_cfg.world_size; exorl_pixel_agent_update_phase / _grad_buffer / _set_comm
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
-                                    12: exorl_debug_agent_poison_scratch */
+                                    12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
+                                        exorl_agent_cfg.precision) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -138,11 +139,14 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_PREC_BF16X3 2    /* split-bf16: every GEMM operand x = hi + lo (two bf16), product = hi*hi + hi*lo + lo*hi on the bf16 MFMA,
                                   fp32 accumulate; everything else as EXORL_PREC_F32. ~2^-16 relative product error: per-step losses stay
                                   within the 1e-4 parity bar of the fp32 reference (tests/test_gpu_agent.py) at about twice fp32 mode's rate */
-#define EXORL_PREC_BF16X6 3    /* three-plane split-bf16 (pixel agents and intrinsic modules only): x = hi + mid + lo, three bf16 planes = the 24
-                                  significand bits of fp32 held exactly; product = hi*hi + (hi*mid + mid*hi) + (hi*lo + lo*hi + mid*mid) on the bf16
-                                  MFMA, fp32 accumulate, the three dropped terms <= 3 * 2^-24 per product — fp32-grade products at 6 / 16 of the fp32
-                                  MFMA's cycles. Generic GEMMs and the 32-channel convolutions (forward, dgrad); the convolution weight gradients
-                                  and the first layer run as in EXORL_PREC_F32. */
+#define EXORL_PREC_BF16X6 3    /* three-plane split-bf16: x = hi + mid + lo, three bf16 planes = the 24 significand bits of fp32 held exactly;
+                                  product = hi*hi + (hi*mid + mid*hi) + (hi*lo + lo*hi + mid*mid) on the bf16 MFMA, fp32 accumulate, the three
+                                  dropped terms <= 3 * 2^-24 per product — fp32-grade products at 6 / 16 of the fp32 MFMA's cycles.
+                                  Pixel agents and intrinsic modules: generic GEMMs and the 32-channel convolutions (forward, dgrad); the
+                                  convolution weight gradients and the first layer run as in EXORL_PREC_F32.
+                                  State agents (every kind): the pipeline of EXORL_PREC_F32 with the H x H products (forward, dgrad, wgrad) in
+                                  three planes — on the 128 x 64 plane kernel (exorl_gemm_planes3's) when hidden_dim and batch are multiples
+                                  of 128, else split inside the generic GEMM; first layer, LayerNorm, heads, losses and Adam are fp32 mode's. */
 
 #define EXORL_NET_ACTOR         0
 #define EXORL_NET_CRITIC        1
@@ -296,6 +300,14 @@ int exorl_gemm_planes(int32_t count, const int32_t* a_layouts, int32_t b_layout,
                       const uint16_t* const* A_hi_dev, const uint16_t* const* A_lo_dev, int64_t lda,
                       const uint16_t* const* B_hi_dev, const uint16_t* const* B_lo_dev, int64_t ldb,
                       float* const* C_dev, int64_t ldc, int32_t relu, void* stream);
+/* The same on three planes per operand (EXORL_PREC_BF16X6's arithmetic): x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi),
+ * lo = bf16(x - hi - mid); C = hi*hi + (hi*mid + mid*hi) + (hi*lo + lo*hi + mid*mid), three fp32 accumulators summed small-first. One kernel
+ * (128 x 64 tiles): M % 128 = 0, N % 64 = 0, K % 128 = 0, 16-byte aligned planes and C, lda and ldb multiples of 8, ldc a multiple of 4; every
+ * problem of a launch has the same A layout (there is no mixed wgrad + dgrad form); anything else is an error, nothing is launched. */
+int exorl_gemm_planes3(int32_t count, const int32_t* a_layouts, int32_t b_layout, int32_t M, int32_t N, int32_t K,
+                       const uint16_t* const* A_hi_dev, const uint16_t* const* A_mid_dev, const uint16_t* const* A_lo_dev, int64_t lda,
+                       const uint16_t* const* B_hi_dev, const uint16_t* const* B_mid_dev, const uint16_t* const* B_lo_dev, int64_t ldb,
+                       float* const* C_dev, int64_t ldc, int32_t relu, void* stream);
 /* Reference-path switches for tests and A/B runs; -1 or 0 = defaults. Bits (any combination):
  *   64          32 -> 32 convolution weight gradient on the tile kernel instead of the wave-specialised one
  *   256         act() on the generic multi-launch path

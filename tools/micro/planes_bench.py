@@ -1,5 +1,8 @@
 """Grouped GEMM on bf16 hi/lo planes (exorl_gemm_planes) at the agent's launch shapes: correctness against a float64 product of the
-SAME planes, and time per launch.   python tools/micro/planes_bench.py [check]"""
+SAME planes, and time per launch.   python tools/micro/planes_bench.py [check]
+python tools/micro/planes_bench.py planes3: the three-plane kernel (exorl_gemm_planes3) against gemm_kernel<EXORL_PREC_BF16X6> (exorl_gemm,
+precision 3) on the same fp32 operands, alternating, HIP-event time per launch; plus the to_planes3 conversion passes, read off a profiled
+bf16x6 TD3+BC update (the conversion kernel has no export of its own)."""
 import sys
 from pathlib import Path
 
@@ -78,7 +81,99 @@ SHAPES = [  # (tag, count, a_layouts, b_layout, M, N, K)
     ('actor fwd 2B (1)', 1, [0], 0, 2048, H, H),
 ]
 
+def split3(x):
+    hi = x.to(torch.bfloat16)
+    r = x - hi.float()
+    mid = r.to(torch.bfloat16)
+    return hi, mid, (r - mid.float()).to(torch.bfloat16)
+
+
+def profiled(fn, iters):
+    """(flops, us) of every launch fn() records, `iters` calls."""
+    L.check(lib.exorl_profile_gemm(1))
+    for _ in range(iters):
+        fn()
+    cap = 8192
+    fl, ms, n = np.zeros(cap, np.float64), np.zeros(cap, np.float32), C.c_int32()
+    L.check(lib.exorl_profile_gemm_read(fl.ctypes.data, ms.ctypes.data, cap, C.byref(n)))
+    L.check(lib.exorl_profile_gemm(0))
+    return fl[:n.value], ms[:n.value] * 1e3
+
+
+def conversion_times(H=1024, B=1024, iters=20):
+    """Median us of to_planes3 on 2 x B x H elements (h1 / dz2 of a twin net, W1 of two heads) and on B x H (the actor's dz2 and W1), from eager
+    bf16x6 TD3+BC updates under exorl_profile_gemm: the records with 0 FLOPs, told apart by their duration rank within a step."""
+    from exorl_amd.engine import AgentEngine
+    eng = AgentEngine('td3_bc', 24, 6, H, B, precision='bf16x6')
+    g = torch.Generator(device='cuda').manual_seed(0)
+    for net in (0, 1):
+        eng.flat(net).copy_(0.05 * torch.randn(eng.flat(net).numel(), device='cuda', generator=g))
+    eng.params_changed(sync_target=True)
+    r = lambda *sh: torch.randn(*sh, device='cuda', generator=g)
+    eng.set_batch(r(B, 24), r(B, 6).tanh(), r(B), torch.full((B,), 0.99, device='cuda'), r(B, 24))
+    for _ in range(3):
+        eng.update(0.2)
+    torch.cuda.synchronize()
+    fl, us = profiled(lambda: eng.update(0.2), iters)
+    conv = us[fl == 0].reshape(iters, -1)
+    per_step = conv.shape[1]
+    # 2BH-element passes: actor h1 (2B rows), target h1, critic h1 (twice), critic dz2 (twice), both W1 pairs; BH: actor dz2, actor W1
+    med = np.median(conv, 0)
+    small = np.sort(med)[:2]
+    big = np.sort(med)[2:]
+    return float(np.median(big)), float(np.median(small)), per_step, float(conv.sum(1).mean())
+
+
+def planes3_table(iters=30):
+    M = N = K = 1024
+    t2, t1, per_step, conv_step = conversion_times()
+    print(f'# to_planes3 (from {per_step} conversion launches per eager bf16x6 TD3+BC update, H = B = 1024): {t2:.2f} us per 2 x 1024 x 1024 elements, '
+          f'{t1:.2f} us per 1024 x 1024; {conv_step:.1f} us of conversions per update')
+    print('# form count | three-plane GEMM us | + conversions of both operands us | gemm_kernel<3> us (count launches summed) | ratio incl. conversions | TF/s incl.')
+    rows = []
+    for count in (2, 4):
+        for tag, al, bl in (('fwd', 0, 0), ('dgrad', 0, 1), ('wgrad', 1, 1)):
+            g = torch.Generator(device='cuda').manual_seed(count + 2 * al + bl)
+            A = [torch.randn(1024, 1024, device='cuda', generator=g) for _ in range(count)]       # square: the stored shape is the same in both layouts
+            B = [torch.randn(1024, 1024, device='cuda', generator=g) for _ in range(count)]
+            a3, b3 = [split3(x) for x in A], [split3(x) for x in B]
+            c3 = [torch.zeros(M, N, device='cuda') for _ in range(count)]
+            cg = [torch.zeros(M, N, device='cuda') for _ in range(count)]
+            arr = lambda xs: (C.c_void_p * count)(*[x.data_ptr() for x in xs])
+            lay = (C.c_int32 * count)(*([al] * count))
+            stream = torch.cuda.current_stream().cuda_stream
+
+            def three():
+                L.check(lib.exorl_gemm_planes3(count, lay, bl, M, N, K, arr([p[0] for p in a3]), arr([p[1] for p in a3]), arr([p[2] for p in a3]), 1024,
+                                               arr([p[0] for p in b3]), arr([p[1] for p in b3]), arr([p[2] for p in b3]), 1024, arr(c3), N, 0, stream))
+
+            def generic():
+                for i in range(count):
+                    L.check(lib.exorl_gemm(3, al, bl, M, N, K, A[i].data_ptr(), 1024, B[i].data_ptr(), 1024, cg[i].data_ptr(), N, None, 0, 0, stream))
+
+            def both():
+                three()
+                generic()
+            for _ in range(5):
+                both()
+            torch.cuda.synchronize()
+            err = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(c3, cg))
+            assert err < 2e-6, (tag, count, err)
+            fl, us = profiled(both, iters)                      # per call: 1 three-plane launch, then `count` generic ones
+            us = us.reshape(iters, 1 + count)
+            t3, tg = float(np.median(us[:, 0])), float(np.median(us[:, 1:].sum(1)))
+            conv = (count // 2) * 2 * t2                        # A and B of every problem, two problems per 2 x 1024 x 1024 pass
+            flops = 2.0 * M * N * K * count
+            rows.append((tag, count, t3, t3 + conv, tg))
+            print(f'{tag:6s} {count} | {t3:7.2f} | {t3 + conv:7.2f} | {tg:7.2f} | {tg / (t3 + conv):5.2f} x | {flops / (t3 + conv) / 1e6:5.0f} (kernel alone {flops / t3 / 1e6:5.0f}, '
+                  f'gemm_kernel<3> {flops / tg / 1e6:5.0f})', flush=True)
+    return rows
+
+
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'planes3':
+        planes3_table()
+        sys.exit(0)
     check_only = len(sys.argv) > 1 and sys.argv[1] == 'check'
     for x3 in (True, False):
         for tag, count, lay, bl, M, N, K in SHAPES:
