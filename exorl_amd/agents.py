@@ -62,14 +62,12 @@ class NetView:
     """Stands where the reference has an nn.Module (agent.actor / .critic / .critic_target): parameters(),
     state_dict(), load_state_dict(), train() over torch views of the engine's device buffers."""
 
-    def __init__(self, engine, net, keys, on_change=None):
-        self._engine, self._net, self._keys, self._on_change = engine, net, keys, on_change
+    def __init__(self, keys, params, grads=None, on_change=None):
+        """keys[i] names the tensor params[i]; grads() -> their gradient tensors (None: a copy nothing differentiates, such as a Polyak
+        target outside the engine's net table); on_change() runs after the parameters were written (see _AgentBase.params_changed)."""
+        self._keys, self._params, self._grads, self._on_change = list(keys), list(params), grads, on_change
+        assert len(self._keys) == len(self._params), (len(self._keys), len(self._params))
         self.training = True
-        self._params = []
-        n = engine.num_tensors(net)
-        assert n == len(keys), (n, len(keys))
-        for i in range(n):
-            self._params.append(engine.tensor(net, i, L.T_PARAM))
 
     def parameters(self):
         return list(self._params)
@@ -78,7 +76,7 @@ class NetView:
         return list(zip(self._keys, self._params))
 
     def grads(self):
-        return [self._engine.tensor(self._net, i, L.T_GRAD) for i in range(len(self._keys))]
+        return self._grads()
 
     def state_dict(self):
         return OrderedDict((k, p.detach().clone()) for k, p in zip(self._keys, self._params))
@@ -99,6 +97,41 @@ class NetView:
 
     def eval(self):
         return self.train(False)
+
+
+def _engine_tensors(engine, net, indices, shapes=None):
+    """NetView's (params, grads) over the tensors `indices` of an engine's net; `shapes` re-views the parameters (conv weights)."""
+    params = [engine.tensor(net, i, L.T_PARAM) for i in indices]
+    if shapes:
+        params = [p.view(*s) for p, s in zip(params, shapes)]
+    return params, lambda: [engine.tensor(net, i, L.T_GRAD) for i in indices]
+
+
+def _net_view(engine, net, keys, on_change=None, indices=None, shapes=None):
+    """A NetView over an engine's net: all of its tensors, or the subset `indices` (agent.predictor / .projector / .protos /
+    .predictor_target share Proto's module engine); a pixel engine's conv weights are exposed in torch's (co, ci, 3, 3) `shapes`."""
+    if indices is None:
+        n = engine.num_tensors(net)
+        assert n == len(keys), (n, len(keys))
+        indices = range(n)
+    return NetView(keys, *_engine_tensors(engine, net, indices, shapes), on_change)
+
+
+def _load(view, tensors):
+    """Writes a net's initial tensors (drawn on the CPU) into its device views."""
+    for p, t in zip(view.parameters(), tensors):
+        p.copy_(t.reshape(p.shape))
+
+
+def _conv_shapes(c):
+    """torch's shapes of the Encoder's four Conv2d weights and biases (ddpg.py:12-39), c input channels."""
+    return [s for l in range(4) for s in ((32, c if l == 0 else 32, 3, 3), (32,))]
+
+
+def _world_size():
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        return torch.distributed.get_world_size()
+    return 1
 
 
 class _AgentBase:
@@ -183,13 +216,6 @@ class _AgentBase:
     def _build(self, obs_dim, action_dim, hidden_dim, batch_size, lr, tau, alpha, stddev_clip, device, precision, seed,
                **engine_kw):
         ddpg = self.KIND in ('ddpg', 'aps')
-        ws = 1
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            ws = torch.distributed.get_world_size()
-            # every rank draws its own rows of the global batch's noise: without this all ranks share one Philox stream and the global
-            # batch repeats each noise block world_size times (the reference's single process draws B x A iid normals)
-            seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF if ws > 1 else seed
-        self.world_size = ws
         # initial weights first (CPU RNG order: actor, critic, critic_target — td3_bc.py:86-93)
         actor0 = _mlp_init(obs_dim, hidden_dim, 2 * action_dim if self.KIND == 'cql' else action_dim, 1, 1)
         critic0 = None
@@ -200,20 +226,28 @@ class _AgentBase:
             if self.KIND == 'aps':      # APSAgent builds DDPG's scalar critics first, then replaces both with CriticSF (aps.py:94-104)
                 critic0 = _mlp_init(obs_dim + action_dim, hidden_dim, engine_kw['sf_dim'], 1, 2)
                 _mlp_init(obs_dim + action_dim, hidden_dim, engine_kw['sf_dim'], 1, 2)
-        self.engine = AgentEngine(self.KIND, obs_dim, action_dim, hidden_dim, batch_size, lr=lr, tau=tau, alpha=alpha,
-                                  stddev_clip=stddev_clip, precision=precision, world_size=ws, seed=seed, device=device,
-                                  **engine_kw)
-        self.actor = NetView(self.engine, L.NET_ACTOR, _DDPG_ACTOR_KEYS if ddpg else _OFFLINE_ACTOR_KEYS, self.params_changed)
-        for p, w in zip(self.actor.parameters(), actor0):
-            p.copy_(w.reshape(p.shape))
+        self._dp_engine(seed, lambda ws, seed: AgentEngine(self.KIND, obs_dim, action_dim, hidden_dim, batch_size, lr=lr, tau=tau, alpha=alpha,
+                                                           stddev_clip=stddev_clip, precision=precision, world_size=ws, seed=seed,
+                                                           device=device, **engine_kw))
+        self.actor = _net_view(self.engine, L.NET_ACTOR, _DDPG_ACTOR_KEYS if ddpg else _OFFLINE_ACTOR_KEYS, self.params_changed)
+        _load(self.actor, actor0)
         if critic0 is not None:
             keys = _DDPG_CRITIC_KEYS if ddpg else _OFFLINE_CRITIC_KEYS
-            self.critic = NetView(self.engine, L.NET_CRITIC, keys, self.params_changed)
-            self.critic_target = NetView(self.engine, L.NET_CRITIC_TARGET, keys, self.params_changed)
-            for p, w in zip(self.critic.parameters(), critic0):
-                p.copy_(w.reshape(p.shape))
+            self.critic = _net_view(self.engine, L.NET_CRITIC, keys, self.params_changed)
+            self.critic_target = _net_view(self.engine, L.NET_CRITIC_TARGET, keys, self.params_changed)
+            _load(self.critic, critic0)
         self.engine.params_changed(sync_target=True)                   # critic_target.load_state_dict(critic.state_dict())
         self.engine.set_metrics(bool(getattr(self, 'use_tb', False) or getattr(self, 'use_wandb', False)))
+
+    def _dp_engine(self, seed, make):
+        """self.engine = make(world_size, seed) for this process, on states and on pixels: under torch.distributed the rank is folded into
+        the seed and the native communicator, where there is one, is attached."""
+        ws = self.world_size = _world_size()
+        if ws > 1:
+            # every rank draws its own rows of the global batch's shifts and noise: without this all ranks share one Philox stream and the
+            # global batch repeats each noise block world_size times (the reference's single process draws B x A iid normals)
+            seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF
+        self.engine = make(ws, seed)
         if ws > 1:
             comm = native_comm(self.engine.device)          # RCCL inside the library when torch.distributed runs on nccl
             if comm is not None:
@@ -221,7 +255,7 @@ class _AgentBase:
         self._slots = None
         self._graph_iter = None
         self._graph_stddev = None
-        self.noise_hook = None      # tests: callable(shape) -> np.ndarray standing in for _standard_normal
+        self.noise_hook = None      # tests: callable(shape) -> np.ndarray standing in for _standard_normal (TruncatedNormal's draws)
 
     def params_changed(self):
         """Call after writing parameter tensors in place (copy_ on .parameters(), dist.broadcast, ...): the kernels
@@ -276,14 +310,22 @@ class _AgentBase:
         self._load_batch(replay_iter)
         self._run_update(stddev)
 
+    def _batch_slots(self):
+        if self._slots is None:
+            self._slots = self.engine.batch_slots()
+        return self._slots
+
     def _load_batch(self, replay_iter):
+        """The next batch into the engine's slots, on states and on pixels (_MetaObsMixin: the [obs | meta] rows on states)."""
+        eng = self.engine
         if hasattr(replay_iter, 'sample_into'):                                         # HBM sampler: replay -> update, zero copy
-            if self._slots is None:
-                self._slots = self.engine.batch_slots()
-            replay_iter.sample_into(self._slots, self.engine.batch)
+            replay_iter.sample_into(self._batch_slots(), eng.batch)
         else:
             batch = next(replay_iter)                                                   # any iterator of 5-tuples
-            self.engine.set_batch(*batch[:5])
+            eng.set_batch(*batch[:5])
+            M = getattr(self, '_pix_meta_dim', 0)
+            if M:                                                                       # pixels: the skill / task rows, a 6th tensor
+                eng.meta_rows().copy_(torch.as_tensor(batch[5]).to(eng.device, torch.float32).reshape(eng.batch, M))
 
     def _noise(self, rows=None):
         if self.noise_hook is None:
@@ -308,6 +350,27 @@ class _AgentBase:
         m['actor_ent'] = float(np.float32(0.5 + 0.5 * np.log(2 * np.pi) + np.log(stddev)) * self.action_dim)
         return m
 
+    METRICS = ()                # per class: (slot, name) pairs of the engine's metrics that update() reports
+
+    def _update_metrics(self, stddev):
+        """update()'s return value on both observation types: the class's table of engine metrics, then what its module adds."""
+        metrics = dict()
+        if self.use_tb or getattr(self, 'use_wandb', False):
+            metrics.update(self._metrics(self.METRICS, stddev))
+            self._module_metrics(metrics)
+        return metrics
+
+    def _module_metrics(self, metrics):
+        pass
+
+    def act(self, obs, step, eval_mode):
+        return self._act(np.asarray(obs, np.float32), step, eval_mode)
+
+    def update(self, replay_iter, step):
+        stddev = self._stddev(step)
+        self._step(replay_iter, stddev)
+        return self._update_metrics(stddev)
+
     def _act(self, obs_vec, step, eval_mode):
         stddev = self._stddev(step)
         noise = self.noise_hook((1, self.action_dim)) if (self.noise_hook and not eval_mode) else None
@@ -331,6 +394,7 @@ _CRITIC_METRICS = [(L.M_BATCH_REWARD, 'batch_reward'), (L.M_CRITIC_TARGET_Q, 'cr
 
 class TD3BCAgent(_AgentBase):
     KIND = 'td3_bc'
+    METRICS = _CRITIC_METRICS
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, stddev_schedule, nstep,
                  batch_size, stddev_clip, use_tb, alpha, has_next_action=False, *, precision='fp32', seed=0):
@@ -348,17 +412,6 @@ class TD3BCAgent(_AgentBase):
         self.train()
         self.critic_target.train()
 
-    def act(self, obs, step, eval_mode):
-        return self._act(np.asarray(obs, np.float32), step, eval_mode)
-
-    def update(self, replay_iter, step):
-        metrics = dict()
-        stddev = self._stddev(step)
-        self._step(replay_iter, stddev)
-        if self.use_tb:
-            metrics.update(self._metrics(_CRITIC_METRICS, stddev))
-        return metrics
-
 
 class TD3Agent(TD3BCAgent):
     KIND = 'td3'
@@ -372,6 +425,7 @@ class TD3Agent(TD3BCAgent):
 class CRRAgent(_AgentBase):
     """agents/offline_learning/crr.py:59-219."""
     KIND = 'crr'
+    METRICS = _CRITIC_METRICS
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, num_value_samples, weight_func,
                  stddev_schedule, nstep, batch_size, stddev_clip, use_tb, has_next_action=False, *, precision='fp32', seed=0):
@@ -391,17 +445,6 @@ class CRRAgent(_AgentBase):
         self._second_noise_rows = batch_size * num_value_samples
         self.train()
         self.critic_target.train()
-
-    def act(self, obs, step, eval_mode):
-        return self._act(np.asarray(obs, np.float32), step, eval_mode)
-
-    def update(self, replay_iter, step):
-        metrics = dict()
-        stddev = self._stddev(step)
-        self._step(replay_iter, stddev)
-        if self.use_tb:
-            metrics.update(self._metrics(_CRITIC_METRICS, stddev))
-        return metrics
 
 
 class CQLAgent(_AgentBase):
@@ -436,9 +479,6 @@ class CQLAgent(_AgentBase):
     def log_critic_alpha(self):
         return torch.tensor([self.engine.cql_alpha_state()[3]])
 
-    def act(self, obs, step, eval_mode):
-        return self._act(np.asarray(obs, np.float32), step, eval_mode)
-
     def _noise(self, rows=None):
         raise RuntimeError('CQL draws five noise tensors; see _run_update')
 
@@ -468,6 +508,7 @@ class CQLAgent(_AgentBase):
 
 class BCAgent(_AgentBase):
     KIND = 'bc'
+    METRICS = [(L.M_BATCH_REWARD, 'batch_reward'), (L.M_ACTOR_LOSS, 'actor_loss')]
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, batch_size, stddev_schedule, use_tb,
                  has_next_action=False, *, precision='fp32', seed=0):
@@ -480,36 +521,30 @@ class BCAgent(_AgentBase):
         self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, 0.0, 0.0, 0.0, device, precision, seed)
         self.train()
 
-    def act(self, obs, step, eval_mode):
-        return self._act(np.asarray(obs, np.float32), step, eval_mode)
-
-    def update(self, replay_iter, step):
-        metrics = dict()
-        stddev = self._stddev(step)
-        self._step(replay_iter, stddev)
-        if self.use_tb:
-            metrics.update(self._metrics([(L.M_BATCH_REWARD, 'batch_reward'), (L.M_ACTOR_LOSS, 'actor_loss')], stddev))
-        return metrics
-
 
 class DDPGAgent(_AgentBase):
     KIND = 'ddpg'
+    METRICS = _CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')]
 
     def __init__(self, name, reward_free, obs_type, obs_shape, action_shape, device, lr, feature_dim, hidden_dim,
                  critic_target_tau, num_expl_steps, update_every_steps, stddev_schedule, nstep, batch_size, stddev_clip,
                  init_critic, use_tb, use_wandb, meta_dim=0, skill_type='uniform', *, precision='fp32', seed=0):
-        if obs_type == 'pixels':
-            if not (type(self) is DDPGAgent or getattr(self, '_PIXELS_OK', False)):
-                raise NotImplementedError(f"exorl_amd: obs_type='pixels' is not built for {type(self).__name__} yet (DDPG, Proto, ICM, ICM-APT, "
-                                          "Disagreement, DIAYN, APS, SMM and RND are)")
-            return self._init_pixels(reward_free, obs_shape, action_shape, device, lr, feature_dim, hidden_dim, critic_target_tau, num_expl_steps,
-                                     update_every_steps, stddev_schedule, batch_size, stddev_clip, init_critic, use_tb, use_wandb, precision, seed,
-                                     meta_dim)
-        if obs_type != 'states':
+        pixels = obs_type == 'pixels'
+        if pixels and not (type(self) is DDPGAgent or getattr(self, '_PIXELS_OK', False)):
+            raise NotImplementedError(f"exorl_amd: obs_type='pixels' is not built for {type(self).__name__} yet (DDPG, Proto, ICM, ICM-APT, "
+                                      "Disagreement, DIAYN, APS, SMM and RND are)")
+        if obs_type not in ('pixels', 'states'):
             raise NotImplementedError(f"exorl_amd DDPGAgent: unknown obs_type {obs_type!r}")
+        if (pixels and reward_free and isinstance(self, ProtoAgent) and not getattr(self, 'shard_pretraining', False) and
+                _world_size() > 1):
+            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU by default: Proto is the "
+                                      "one pixel agent whose sharded pretraining step is opt-in (its candidate queue draws rows from the global "
+                                      "batch's softmax and its Sinkhorn runs over the batch; every rank gathers the rows and runs both "
+                                      "redundantly). Pass shard_pretraining=True (Hydra: +agent.shard_pretraining=true) to shard it. Under data "
+                                      "parallelism the pixel path runs every agent with reward_free=False (fine-tuning: the DDPG pixel step) and "
+                                      "every other agent's pretraining step")
         self.reward_free = reward_free
         self.obs_type = obs_type
-        self.obs_shape = obs_shape
         self.action_dim = action_shape[0]
         self.hidden_dim = hidden_dim
         self.lr = lr
@@ -524,12 +559,17 @@ class DDPGAgent(_AgentBase):
         self.init_critic = init_critic
         self.feature_dim = feature_dim
         self.solved_meta = None
-        self.obs_dim = obs_shape[0] + meta_dim
-        self.aug = self.encoder = _Identity()
-        self.encoder_opt = None
         self._precision = precision
-        self._build(self.obs_dim, action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, stddev_clip, device,
-                    precision, seed, **self._engine_kw())
+        if pixels:
+            self.obs_shape, self._pix_meta_dim = tuple(obs_shape), meta_dim
+            self._init_pixels(obs_shape, batch_size, seed, meta_dim)
+        else:
+            self.obs_shape = obs_shape
+            self.obs_dim = obs_shape[0] + meta_dim
+            self.aug = self.encoder = _Identity()
+            self.encoder_opt = None
+            self._build(self.obs_dim, action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, stddev_clip, device,
+                        precision, seed, **self._engine_kw())
         self.train()
         self.critic_target.train()
 
@@ -537,74 +577,46 @@ class DDPGAgent(_AgentBase):
         return {}
 
     # ---- obs_type == 'pixels' (ddpg.py:12-39 Encoder, :42-123 pixel Actor/Critic, :213-328) -----------------------------------------
-    def _init_pixels(self, reward_free, obs_shape, action_shape, device, lr, feature_dim, hidden_dim, critic_target_tau, num_expl_steps,
-                     update_every_steps, stddev_schedule, batch_size, stddev_clip, init_critic, use_tb, use_wandb, precision, seed, meta_dim=0):
-        self.reward_free, self.obs_type, self.obs_shape = reward_free, 'pixels', tuple(obs_shape)
-        self._precision, self._pix_meta_dim = precision, meta_dim
-        self.action_dim, self.hidden_dim, self.feature_dim = action_shape[0], hidden_dim, feature_dim
-        self.lr, self.device, self.critic_target_tau = lr, device, critic_target_tau
-        self.update_every_steps, self.use_tb, self.use_wandb = update_every_steps, use_tb, use_wandb
-        self.num_expl_steps, self.stddev_schedule, self.stddev_clip, self.init_critic = num_expl_steps, stddev_schedule, stddev_clip, init_critic
-        self.solved_meta = None
-        ws = 1
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            ws = torch.distributed.get_world_size()
-        if ws > 1 and reward_free and isinstance(self, ProtoAgent) and not getattr(self, 'shard_pretraining', False):
-            raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU by default: Proto is the "
-                                      "one pixel agent whose sharded pretraining step is opt-in (its candidate queue draws rows from the global "
-                                      "batch's softmax and its Sinkhorn runs over the batch; every rank gathers the rows and runs both "
-                                      "redundantly). Pass shard_pretraining=True (Hydra: +agent.shard_pretraining=true) to shard it. Under data "
-                                      "parallelism the pixel path runs every agent with reward_free=False (fine-tuning: the DDPG pixel step) and "
-                                      "every other agent's pretraining step")
-        if ws > 1:          # every rank draws its own rows of the global batch's shifts and noise (as _AgentBase._build does for states)
-            seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF
-        self.world_size = ws
+    def _init_pixels(self, obs_shape, batch_size, seed, meta_dim):
         c = obs_shape[0]
         sf_dim = self._engine_kw().get('sf_dim', 0)         # APS: CriticSF heads (aps.py:94-104)
-        w = _pixel_init(c, obs_shape[1], self.action_dim, feature_dim, hidden_dim, meta_dim, sf_dim)
-        self.engine = PixelEngine(obs_shape, self.action_dim, feature_dim, hidden_dim, batch_size, lr=lr, tau=critic_target_tau,
-                                  stddev_clip=stddev_clip, precision=precision, seed=seed, device=device, meta_dim=meta_dim, sf_dim=sf_dim,
-                                  world_size=ws)
-        if ws > 1:
-            comm = native_comm(self.engine.device)          # RCCL inside the library when torch.distributed runs on nccl
-            if comm is not None:
-                self.engine.set_comm(comm)
+        w = _pixel_init(c, obs_shape[1], self.action_dim, self.feature_dim, self.hidden_dim, meta_dim, sf_dim)
+        self._dp_engine(seed, lambda ws, seed: PixelEngine(obs_shape, self.action_dim, self.feature_dim, self.hidden_dim, batch_size, lr=self.lr,
+                                                           tau=self.critic_target_tau, stddev_clip=self.stddev_clip,
+                                                           precision=self._precision, seed=seed, device=self.device, meta_dim=meta_dim,
+                                                           sf_dim=sf_dim, world_size=ws))
         self.obs_dim = w['repr_dim'] + meta_dim          # ddpg.py:176 obs_dim = encoder.repr_dim + meta_dim
-        conv_shapes = [s for l in range(4) for s in ((32, c if l == 0 else 32, 3, 3), (32,))]
-        self.encoder = _PixelNetView(self.engine, 0, _ENC_KEYS, conv_shapes)
-        self.actor = _PixelNetView(self.engine, 1, _PIX_ACTOR_KEYS)
-        self.critic = _PixelNetView(self.engine, 2, _PIX_CRITIC_KEYS)
-        self.critic_target = _PixelNetView(self.engine, 3, _PIX_CRITIC_KEYS)
+        self.encoder = _net_view(self.engine, 0, _ENC_KEYS, shapes=_conv_shapes(c))
+        self.actor = _net_view(self.engine, 1, _PIX_ACTOR_KEYS)
+        self.critic = _net_view(self.engine, 2, _PIX_CRITIC_KEYS)
+        self.critic_target = _net_view(self.engine, 3, _PIX_CRITIC_KEYS)
         for view, ts in ((self.encoder, w['encoder']), (self.actor, w['actor']), (self.critic, w['critic'])):
-            for p, t in zip(view.parameters(), ts):
-                p.copy_(t.reshape(p.shape))
+            _load(view, ts)
         self.engine.sync_target()
         self.aug = _Identity()
         self.encoder_opt = True            # the reference's `if self.encoder_opt is not None` checks hold for pixels
-        self.noise_hook = None             # tests: callable(shape) -> standard normals for the TruncatedNormal draws
         self.shift_hook = None             # tests: callable(batch) -> (batch, 2) RandomShiftsAug draws
-        self._slots = None
-        self.training = True
+
+    def _shifts(self):
+        """One RandomShiftsAug draw for the batch (None: the engine draws its own)."""
+        return self.shift_hook(self.engine.batch) if self.shift_hook else None
+
+    def _pix_before_step(self):
+        """What a class does on the loaded frames before the DDPG step; returns how engine.run_update takes its images: fresh shifts
+        (here), or keep_augmented / keep_encoded for those a module agent has augmented or encoded already."""
+        return dict(shifts_obs=self._shifts(), shifts_next=self._shifts())
+
+    def _pix_after_step(self):
+        pass
 
     def _update_pixels(self, replay_iter, step):
-        eng = self.engine
-        if hasattr(replay_iter, 'sample_into'):
-            self._slots = self._slots or eng.batch_slots()
-            replay_iter.sample_into(self._slots, eng.batch)
-        else:
-            obs, action, reward, discount, next_obs = next(replay_iter)[:5]
-            eng.set_batch(obs, action, reward, discount, next_obs)
+        self._load_batch(replay_iter)
+        images = self._pix_before_step()
         stddev = self._stddev(step)
-        B, A = eng.batch, self.action_dim
-        so = self.shift_hook(B) if self.shift_hook else None
-        sn = self.shift_hook(B) if self.shift_hook else None
-        nc = self.noise_hook((B, A)) if self.noise_hook else None
-        na = self.noise_hook((B, A)) if self.noise_hook else None
-        eng.run_update(stddev, so, sn, nc, na)
-        metrics = dict()
-        if self.use_tb or self.use_wandb:
-            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-        return metrics
+        # reference draw order: the augmentations, then the critic target's noise, then the actor's
+        self.engine.run_update(stddev, noise_critic=self._noise(), noise_actor=self._noise(), **images)
+        self._pix_after_step()
+        return self._update_metrics(stddev)
 
     def train(self, training=True):
         if getattr(self, 'obs_type', 'states') == 'pixels':
@@ -646,16 +658,11 @@ class DDPGAgent(_AgentBase):
         return self._act(np.concatenate(parts), step, eval_mode)
 
     def update(self, replay_iter, step):
-        metrics = dict()
         if step % self.update_every_steps != 0:      # ddpg.py:302-303 — no batch is consumed
-            return metrics
+            return dict()
         if self.obs_type == 'pixels':
             return self._update_pixels(replay_iter, step)
-        stddev = self._stddev(step)
-        self._step(replay_iter, stddev)
-        if self.use_tb or self.use_wandb:
-            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-        return metrics
+        return super().update(replay_iter, step)
 
 
 def _seq_init(spec):
@@ -679,9 +686,13 @@ _APT_KEYS = ['trunk.0.weight', 'trunk.0.bias', 'trunk.1.weight', 'trunk.1.bias']
 class _RndView(NetView):
     """agent.rnd: the parameters plus BatchNorm1d's buffers under the reference's state_dict keys (rnd.py:24-27)."""
 
+    def __init__(self, intr):
+        super().__init__(_RND_KEYS, *_engine_tensors(intr, None, range(len(_RND_KEYS))))
+        self._intr = intr
+
     def _bn(self):
-        O = self._engine.obs_dim
-        bn = self._engine.bn
+        O = self._intr.obs_dim
+        bn = self._intr.bn
         return bn[:O], bn[O:2 * O], bn[2 * O:]
 
     def state_dict(self):
@@ -716,10 +727,28 @@ class _RmsView:
 class _IntrAgent(DDPGAgent):
     """Shared update() of the reward-free agents (rnd.py:110-159, icm.py:94-139, icm_apt.py:112-158): module step and
     intrinsic reward on the sampled batch (libexorl_hip: exorl_intr_update), then the DDPG update on that reward."""
-    LOSS_KEY = None
+    MODULE_METRICS = ()         # per class: (slot, name) pairs of the module's metrics reported while reward_free (_module_table)
+    STATE_METRICS = ()          # ... and those reported on state observations only
+
+    def __init__(self, shard_pretraining=False, **kwargs):
+        self.shard_pretraining = bool(shard_pretraining)        # before the base constructor: Proto's pixel refusal reads it
+        super().__init__(**kwargs)
+
+    def _module(self, kind, obs_dim, hidden_dim, keys, tensors, dp=None, **kw):
+        """The tail of every subclass constructor: builds the module engine self.intr from the shared arguments plus the kind's own
+        keywords, loads the initial `tensors` and allocates the pixel path's gradient buffer. Returns the view of the module's tensors
+        under the reference's state_dict `keys` (None: the subclass wraps them itself)."""
+        self.intr = IntrEngine(kind, obs_dim, self.action_dim, hidden_dim, **(self._intr_dp() if dp is None else dp), lr=self.lr,
+                               precision=self._precision, device=self.device, **kw)
+        view = _net_view(self.intr, None, keys) if keys is not None else None
+        if view is not None:
+            _load(view, tensors)
+        if self.obs_type == 'pixels':       # d(module loss)/d(encoding), see _pix_module
+            self._dobs = torch.zeros(self.engine.batch, self.obs_dim - self._pix_meta_dim, dtype=torch.float32, device=self.engine.device)
+        return view
 
     def _intr_step(self):
-        s = self._slots = self._slots or self.engine.batch_slots()
+        s = self._batch_slots()
         self.intr.run_update(s.obs, s.action, s.next_obs, s.reward, s.reward, True)
 
     def enable_graph(self, replay_iter, step=0):
@@ -776,7 +805,7 @@ class _IntrAgent(DDPGAgent):
         dist = torch.distributed
         eng, ws, rank = self.engine, self.world_size, torch.distributed.get_rank()
         B, W, A = eng.batch, self.obs_dim, self.action_dim
-        local = self._slots = self._slots or eng.batch_slots()
+        local = self._batch_slots()
         pack, gpack, g, gslots = self._dp_buffers()
         view = lambda ptr, cols: eng._view(ptr, B * cols).view(B, cols)
         pack[:, :W].copy_(view(local.obs, W))
@@ -821,56 +850,25 @@ class _IntrAgent(DDPGAgent):
         """Module step + intrinsic reward on the encodings (device pointers); d(loss)/d(encoding) lands in self._dobs."""
         self.intr.run_update(fo, s.action, fn, s.reward, s.reward, True, dobs_out=self._dobs.data_ptr())
 
-    def _pix_alloc(self):
-        """Called by the subclass constructors once self.intr exists."""
-        if getattr(self, 'obs_type', 'states') == 'pixels':
-            self._dobs = torch.empty(self.engine.batch, self.obs_dim - self._pix_meta_dim, dtype=torch.float32, device=self.engine.device)
-
-    def _update_pixels(self, replay_iter, step):
+    def _pix_before_step(self):
         eng = self.engine
-        M = self._pix_meta_dim
-        s = self._slots = self._slots or eng.batch_slots()
-        if hasattr(replay_iter, 'sample_into'):
-            replay_iter.sample_into(s, eng.batch)
-        else:
-            b = next(replay_iter)
-            eng.set_batch(*b[:5])
-            if M:
-                eng.meta_rows().copy_(torch.as_tensor(b[5]).to(eng.device, torch.float32).reshape(eng.batch, M))
-        B, A = eng.batch, self.action_dim
-        eng.augment(self.shift_hook(B) if self.shift_hook else None, self.shift_hook(B) if self.shift_hook else None)
+        eng.augment(self._shifts(), self._shifts())         # drawn in fine-tuning too
         fo, fn = eng.encode(0), eng.encode(1)
         if self.reward_free:
-            self._pix_module(fo, fn, s)
+            self._pix_module(fo, fn, self._batch_slots())
             eng.run_encoder_step(self._PIX_GRAD, self._dobs.data_ptr(), 0)
-        stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        eng.run_update(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
-                       keep_encoded=True)
-        metrics = dict()
-        if self.use_tb or self.use_wandb:
-            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-            if self.reward_free:
-                ri = self._intr_metrics()
-                metrics[self.LOSS_KEY] = float(ri[L.IM_LOSS])
-                metrics['intr_reward'] = float(ri[L.IM_INTR_REWARD])
-                metrics['extr_reward'] = float(ri[L.IM_EXTR_REWARD])
-                if self.LOSS_KEY == 'diayn_loss':
-                    metrics['diayn_acc'] = float(ri[L.IM_ACC])
-                if self.LOSS_KEY == 'aps_loss':
-                    metrics['intr_ent_reward'] = float(ri[L.IM_ENT_REWARD])
-                    metrics['intr_sf_reward'] = float(ri[L.IM_SF_REWARD])
-            else:
-                metrics['extr_reward'] = metrics['batch_reward']
-        return metrics
+        return dict(keep_encoded=True)
 
-    def update(self, replay_iter, step):
-        metrics = dict()
-        if step % self.update_every_steps != 0:
-            return metrics
-        if self.obs_type == 'pixels':
-            return self._update_pixels(replay_iter, step)
-        stddev = self._stddev(step)
+    def _module_metrics(self, metrics):
+        if self.reward_free:
+            raw = self._intr_metrics()              # a replicated module's engine has world_size 1: its own metrics
+            table = self.MODULE_METRICS + (self.STATE_METRICS if self.obs_type == 'states' else ())
+            metrics.update((name, float(raw[slot])) for slot, name in table)
+        else:
+            metrics['extr_reward'] = metrics['batch_reward']
+
+    def _step(self, replay_iter, stddev):
         self._load_batch(replay_iter)
         if self.reward_free:
             if self.world_size != 1 and not self._sharded_states:
@@ -878,24 +876,11 @@ class _IntrAgent(DDPGAgent):
             else:
                 self._intr_step()
         self._run_update(stddev)
-        if self.use_tb or self.use_wandb:
-            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-            if self.reward_free:
-                raw = self._intr_metrics()              # a replicated module's engine has world_size 1: its own metrics
-                metrics[self.LOSS_KEY] = float(raw[L.IM_LOSS])
-                metrics['intr_reward'] = float(raw[L.IM_INTR_REWARD])
-                metrics['extr_reward'] = float(raw[L.IM_EXTR_REWARD])
-                if self.LOSS_KEY == 'diayn_loss':
-                    metrics['diayn_acc'] = float(raw[L.IM_ACC])
-                if self.LOSS_KEY == 'aps_loss':
-                    metrics['intr_ent_reward'] = float(raw[L.IM_ENT_REWARD])
-                    metrics['intr_sf_reward'] = float(raw[L.IM_SF_REWARD])
-                if self.LOSS_KEY == 'rnd_loss':
-                    metrics['pred_error_mean'] = float(raw[L.IM_RMS_MEAN])
-                    metrics['pred_error_std'] = float(raw[L.IM_RMS_STD])
-            else:
-                metrics['extr_reward'] = metrics['batch_reward']
-        return metrics
+
+
+def _module_table(loss_key, *more):
+    """A class's MODULE_METRICS: the three every module reports, its loss under the reference's name, then its own."""
+    return ((L.IM_LOSS, loss_key), (L.IM_INTR_REWARD, 'intr_reward'), (L.IM_EXTR_REWARD, 'extr_reward')) + more
 
 
 class _RndPixelView(_RndView):
@@ -903,7 +888,7 @@ class _RndPixelView(_RndView):
     agent's encoder, target.0 its frozen copy (the pixel engine's encoder_target slot); the six Linear layers live in the module engine."""
 
     def __init__(self, intr, pixel, encoder_view, target_view):
-        super().__init__(intr, None, _RND_KEYS)
+        super().__init__(intr)
         self._pixel, self._enc, self._tgt = pixel, encoder_view, target_view
 
     def _bn(self):
@@ -928,12 +913,12 @@ class _RndPixelView(_RndView):
 
 class RNDAgent(_IntrAgent):
     """agents/unsupervised_learning/rnd.py:63-159 (configs/agent/rnd.yaml)."""
-    LOSS_KEY = 'rnd_loss'
+    MODULE_METRICS = _module_table('rnd_loss')
+    STATE_METRICS = ((L.IM_RMS_MEAN, 'pred_error_mean'), (L.IM_RMS_STD, 'pred_error_std'))
     _PIXELS_OK = True
 
     def __init__(self, rnd_rep_dim, update_encoder, rnd_scale=1., shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         self.rnd_scale = rnd_scale
         self.update_encoder = update_encoder
         O, H = self.obs_dim, self.hidden_dim
@@ -941,96 +926,64 @@ class RNDAgent(_IntrAgent):
         if pixels:      # RND(...) construction order (rnd.py:28-45): the six Linears, then weight_init over predictor (the shared encoder's
             # convolutions are drawn AGAIN, then its Linears) and target (the copied encoder's convolutions get draws of their own)
             lins = [nn.Linear(*d) for d in ((O, H), (H, H), (H, rnd_rep_dim)) * 2]
-            c = self.obs_shape[0]
-            shapes = [(32, c if l == 0 else 32, 3, 3) for l in range(4)]
+            conv_shapes = _conv_shapes(self.obs_shape[0])
             w, convs = [], []
             for half in range(2):
-                cw = [nn.init.orthogonal_(torch.empty(sh), nn.init.calculate_gain('relu')) for sh in shapes]
-                convs.append(cw)
+                cw = [nn.init.orthogonal_(torch.empty(sh), nn.init.calculate_gain('relu')) for sh in conv_shapes[0::2]]
+                convs.append([t for cv in cw for t in (cv, torch.zeros(32))])
                 for m in lins[3 * half:3 * half + 3]:
                     nn.init.orthogonal_(m.weight.data)
                     m.bias.data.fill_(0.0)
                     w += [m.weight.data, m.bias.data]
-            for view_p, cw in zip(self.encoder.parameters()[0::2], convs[0]):
-                view_p.copy_(cw.reshape(view_p.shape))
-            for view_p in self.encoder.parameters()[1::2]:
-                view_p.zero_()
+            _load(self.encoder, convs[0])
         else:
             w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, rnd_rep_dim)] * 2)      # predictor then target (rnd.py:28-43)
-        self.intr = IntrEngine('rnd', O, self.action_dim, H, **self._intr_dp(), rep_dim=rnd_rep_dim, lr=self.lr, scale=rnd_scale,
-                               precision=self._precision, device=self.device, encoded=pixels)
+        self._module('rnd', O, H, None, None, rep_dim=rnd_rep_dim, scale=rnd_scale, encoded=pixels)
         if pixels:
-            conv_shapes = [s_ for l in range(4) for s_ in ((32, self.obs_shape[0] if l == 0 else 32, 3, 3), (32,))]
-            self.rnd_target_encoder = _ParamList(_ENC_KEYS, self.engine.encoder_target_tensors(conv_shapes))
-            for p, cw in zip(self.rnd_target_encoder.parameters()[0::2], convs[1]):
-                p.copy_(cw)
-            for p in self.rnd_target_encoder.parameters()[1::2]:
-                p.zero_()
+            self.rnd_target_encoder = NetView(_ENC_KEYS, self.engine.encoder_target_tensors(conv_shapes))
+            _load(self.rnd_target_encoder, convs[1])
             self.rnd = _RndPixelView(self.intr, self.engine, self.encoder, self.rnd_target_encoder)
-            NetView.load_state_dict(self.rnd, {k: t for k, t in zip(_RND_KEYS, w)})
         else:
-            self.rnd = _RndView(self.intr, None, _RND_KEYS)
-            for p, t in zip(self.rnd.parameters(), w):
-                p.copy_(t.reshape(p.shape))
+            self.rnd = _RndView(self.intr)
+        _load(self.rnd, w)
         self.intrinsic_reward_rms = _RmsView(self.intr)
-        self._pix_alloc()
 
-    def _update_pixels(self, replay_iter, step):
+    def _pix_before_step(self):
         """rnd.py:110-159 on pixels. RND.forward augments the raw frames itself, normalises them with a BatchNorm2d and runs the agent's
         encoder inside its predictor (and a frozen copy inside its target): update_rnd steps that encoder twice on the same gradients
         (rnd_opt, then encoder_opt), compute_intr_reward draws another augmentation and runs the moved encoder, and only then are obs and
         next_obs augmented and encoded for the critic and the actor (detached)."""
         eng = self.engine
-        s = self._slots = self._slots or eng.batch_slots()
-        if hasattr(replay_iter, 'sample_into'):
-            replay_iter.sample_into(s, eng.batch)
-        else:
-            eng.set_batch(*next(replay_iter)[:5])
-        B, A = eng.batch, self.action_dim
-        sh = lambda: self.shift_hook(B) if self.shift_hook else None
         if self.reward_free:
-            fp, ft = eng.run_rnd_features(sh())
+            s = self._batch_slots()
+            fp, ft = eng.run_rnd_features(self._shifts())
             self.intr.run_update(fp, None, ft, s.reward, s.reward, 2, dobs_out=self._dobs.data_ptr())
             eng.run_encoder_step(0, self._dobs.data_ptr(), 2)
-            fp, ft = eng.run_rnd_features(sh())
+            fp, ft = eng.run_rnd_features(self._shifts())
             self.intr.run_update(fp, None, ft, s.reward, s.reward, False)
-        stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        eng.run_update(stddev, sh(), sh(), self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None)
-        metrics = dict()
-        if self.use_tb or self.use_wandb:
-            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-            ri = self._intr_metrics() if self.reward_free else self.intr.metrics_raw()
-            if self.reward_free:
-                metrics['rnd_loss'] = float(ri[L.IM_LOSS])
-                metrics['intr_reward'] = float(ri[L.IM_INTR_REWARD])
-                metrics['extr_reward'] = float(ri[L.IM_EXTR_REWARD])
-            else:
-                metrics['extr_reward'] = metrics['batch_reward']
+        return dict(shifts_obs=self._shifts(), shifts_next=self._shifts())
+
+    def _module_metrics(self, metrics):
+        super()._module_metrics(metrics)
+        if self.obs_type == 'pixels':           # the running RMS itself, in fine-tuning too
             M, S_, _n = self.intr.rms_state()
             metrics['pred_error_mean'] = float(M)
             metrics['pred_error_std'] = float(np.sqrt(np.float32(S_)))
-        return metrics
 
 
 class ICMAgent(_IntrAgent):
     """agents/unsupervised_learning/icm.py:48-139 (configs/agent/icm.yaml)."""
-    LOSS_KEY = 'icm_loss'
+    MODULE_METRICS = _module_table('icm_loss')
     _PIXELS_OK = True
 
     def __init__(self, icm_scale, update_encoder, shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         self.icm_scale = icm_scale
         self.update_encoder = update_encoder
         O, A, H = self.obs_dim, self.action_dim, self.hidden_dim
         w = _seq_init([('lin', O + A, H), ('lin', H, O), ('lin', 2 * O, H), ('lin', H, A)])
-        self.intr = IntrEngine('icm', O, A, H, **self._intr_dp(), lr=self.lr, scale=icm_scale, precision=self._precision,
-                               device=self.device)
-        self.icm = NetView(self.intr, None, _ICM_KEYS)
-        for p, t in zip(self.icm.parameters(), w):
-            p.copy_(t.reshape(p.shape))
-        self._pix_alloc()
+        self.icm = self._module('icm', O, H, _ICM_KEYS, w, scale=icm_scale)
 
 
 class _PbeView:
@@ -1040,23 +993,18 @@ class _PbeView:
 
 class ICMAPTAgent(_IntrAgent):
     """agents/unsupervised_learning/icm_apt.py:60-158 (configs/agent/icm_apt.yaml)."""
-    LOSS_KEY = 'icm_loss'
+    MODULE_METRICS = _module_table('icm_loss')
     _PIXELS_OK = True
 
     def __init__(self, icm_scale, knn_rms, knn_k, knn_avg, knn_clip, update_encoder, icm_rep_dim, shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         self.icm_scale = icm_scale
         self.update_encoder = update_encoder
         O, A, H, R = self.obs_dim, self.action_dim, self.hidden_dim, icm_rep_dim
         w = _seq_init([('lin', O, R), ('ln', R), ('lin', R + A, H), ('lin', H, R), ('lin', 2 * R, H), ('lin', H, A)])
-        self.intr = IntrEngine('icm_apt', O, A, H, **self._intr_dp(), rep_dim=R, lr=self.lr, scale=icm_scale, knn_k=knn_k,
-                               knn_avg=knn_avg, knn_rms=knn_rms, knn_clip=knn_clip, precision=self._precision, device=self.device)
-        self.icm = NetView(self.intr, None, _APT_KEYS)
-        for p, t in zip(self.icm.parameters(), w):
-            p.copy_(t.reshape(p.shape))
+        self.icm = self._module('icm_apt', O, H, _APT_KEYS, w, rep_dim=R, scale=icm_scale, knn_k=knn_k, knn_avg=knn_avg, knn_rms=knn_rms,
+                                knn_clip=knn_clip)
         self.pbe = _PbeView(self.intr)
-        self._pix_alloc()
 
 
 _DIS_KEYS = [f'ensemble.{m}.{i}.{w}' for m in range(5) for i in (0, 2) for w in ('weight', 'bias')]
@@ -1065,12 +1013,11 @@ _DIAYN_KEYS = [f'skill_pred_net.{i}.{w}' for i in (0, 2, 4) for w in ('weight', 
 
 class DisagreementAgent(_IntrAgent):
     """agents/unsupervised_learning/disagreement.py:50-136 (configs/agent/disagreement.yaml)."""
-    LOSS_KEY = 'disagreement_loss'
+    MODULE_METRICS = _module_table('disagreement_loss')
     _PIXELS_OK = True
 
     def __init__(self, update_encoder, shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         self.update_encoder = update_encoder
         O, A, H = self.obs_dim, self.action_dim, self.hidden_dim
         # the ensemble keeps nn.Linear's default initialisation: Disagreement never applies utils.weight_init (disagreement.py:12-18)
@@ -1078,12 +1025,7 @@ class DisagreementAgent(_IntrAgent):
         for _ in range(5):
             for m in (nn.Linear(O + A, H), nn.Linear(H, O)):
                 w += [m.weight.data, m.bias.data]
-        self.intr = IntrEngine('disagreement', O, A, H, **self._intr_dp(), lr=self.lr, n_models=5, precision=self._precision,
-                               device=self.device)
-        self.disagreement = NetView(self.intr, None, _DIS_KEYS)
-        for p, t in zip(self.disagreement.parameters(), w):
-            p.copy_(t.reshape(p.shape))
-        self._pix_alloc()
+        self.disagreement = self._module('disagreement', O, H, _DIS_KEYS, w, n_models=5)
 
 
 class _Spec:
@@ -1100,11 +1042,13 @@ class _MetaObsMixin:
     _meta_dim = 0
 
     def _views(self):
-        s = self._slots = self._slots or self.engine.batch_slots()
+        s = self._batch_slots()
         B, W = self.engine.batch, self.obs_dim
         return s, self.engine._view(s.obs, B * W).view(B, W), self.engine._view(s.next_obs, B * W).view(B, W)
 
     def _load_batch(self, replay_iter):
+        if self.obs_type == 'pixels':                # the frames and the meta rows have slots of their own
+            return super()._load_batch(replay_iter)
         O, S = self.obs_dim - self._meta_dim, self._meta_dim
         s, obs_v, next_v = self._views()
         if hasattr(replay_iter, 'sample_into'):      # HBM sampler: obs and the meta columns land in the [obs | meta] rows
@@ -1125,27 +1069,21 @@ class _MetaObsMixin:
 class DIAYNAgent(_MetaObsMixin, _IntrAgent):
     """agents/unsupervised_learning/diayn.py:32-176 (configs/agent/diayn.yaml): the skill rides in the batch as a 6th tensor and
     is appended to obs / next_obs for the actor and critic; the discriminator sees the raw next_obs."""
-    LOSS_KEY = 'diayn_loss'
+    MODULE_METRICS = _module_table('diayn_loss', (L.IM_ACC, 'diayn_acc'))
     _PIXELS_OK = True
     _PIX_GRAD = 1
 
     def __init__(self, update_skill_every_step, skill_dim, diayn_scale, update_encoder, shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
         self.skill_dim = self._meta_dim = skill_dim
         self.update_skill_every_step = update_skill_every_step
         self.diayn_scale = diayn_scale
         self.update_encoder = update_encoder
         kwargs['meta_dim'] = self.skill_dim
         self.skill_type = kwargs['skill_type']
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         O, H = self.obs_dim - self.skill_dim, self.hidden_dim
         w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, skill_dim)])
-        self.intr = IntrEngine('diayn', O, self.action_dim, H, **self._intr_dp(), rep_dim=skill_dim, lr=self.lr, scale=diayn_scale,
-                               precision=self._precision, device=self.device)
-        self.diayn = NetView(self.intr, None, _DIAYN_KEYS)
-        for p, t in zip(self.diayn.parameters(), w):
-            p.copy_(t.reshape(p.shape))
-        self._pix_alloc()
+        self.diayn = self._module('diayn', O, H, _DIAYN_KEYS, w, rep_dim=skill_dim, scale=diayn_scale)
 
     def _pix_module(self, fo, fn, s):          # the discriminator reads the next frame's encoding (diayn.py:141-147)
         self.intr.run_update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.skill_dim, dobs_out=self._dobs.data_ptr())
@@ -1176,7 +1114,7 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
     """agents/unsupervised_learning/aps.py:82-320 (configs/agent/aps.yaml): DDPG whose critic emits sf_dim successor features per
     head, Q = task . features (CriticSF, aps.py:12-60); the task vector rides in the batch and in the trailing columns of obs."""
     KIND = 'aps'
-    LOSS_KEY = 'aps_loss'
+    MODULE_METRICS = _module_table('aps_loss', (L.IM_ENT_REWARD, 'intr_ent_reward'), (L.IM_SF_REWARD, 'intr_sf_reward'))
     _PIXELS_OK = True
     _PIX_GRAD = 1                        # update_aps reaches the encoder through next_obs (aps.py:147-159,203-204)
 
@@ -1185,23 +1123,17 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
 
     def __init__(self, update_task_every_step, sf_dim, knn_rms, knn_k, knn_avg, knn_clip, num_init_steps, lstsq_batch_size, update_encoder,
                  shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
         self.sf_dim = self._meta_dim = sf_dim
         self.update_task_every_step = update_task_every_step
         self.num_init_steps = num_init_steps
         self.lstsq_batch_size = lstsq_batch_size
         self.update_encoder = update_encoder
         kwargs['meta_dim'] = self.sf_dim
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         O, H = self.obs_dim - self.sf_dim, self.hidden_dim
         w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, sf_dim)])
-        self.intr = IntrEngine('aps', O, self.action_dim, H, **self._intr_dp(), rep_dim=sf_dim, lr=self.lr, knn_k=knn_k, knn_avg=knn_avg,
-                               knn_rms=knn_rms, knn_clip=knn_clip, precision=self._precision, device=self.device)
-        self.aps = NetView(self.intr, None, _APS_KEYS)
-        for p, t in zip(self.aps.parameters(), w):
-            p.copy_(t.reshape(p.shape))
+        self.aps = self._module('aps', O, H, _APS_KEYS, w, rep_dim=sf_dim, knn_k=knn_k, knn_avg=knn_avg, knn_rms=knn_rms, knn_clip=knn_clip)
         self.pbe = _PbeView(self.intr)
-        self._pix_alloc()
 
     def _engine_kw(self):
         return {'sf_dim': self.sf_dim}
@@ -1235,7 +1167,7 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
             if self.obs_type == 'pixels':          # aug_and_encode (aps.py:262) through the engine, one batch of frames at a time
                 eng = self.engine
                 eng.set_batch(*batch[:5])
-                eng.augment(self.shift_hook(eng.batch) if self.shift_hook else None, self.shift_hook(eng.batch) if self.shift_hook else None)
+                eng.augment(self._shifts(), self._shifts())
                 o = eng.feature_view(eng.encode(0)).clone()
             else:
                 o = torch.as_tensor(batch[0]).to(self.device, torch.float32)
@@ -1288,33 +1220,28 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
     TD target are (B,B) matrices and `mse_loss` averages over all pairs. Per sample that is the TD loss against
     rest_i + mean_j log_p_star_j, plus var_j(log_p_star_j) in each critic's loss value; the module writes exactly that reward and
     `critic_loss` carries the variance term (tests/golden/tiny_smm.npz reproduces the reference's numbers)."""
-    LOSS_KEY = 'loss_vae'
+    MODULE_METRICS = _module_table('loss_vae')
     _PIXELS_OK = True                    # smm.py:264-331 with obs_type == 'pixels': the VAE and the skill predictor read the encoding, p*(s) is dropped
     _PIX_GRAD = 0
 
     def __init__(self, z_dim, sp_lr, vae_lr, vae_beta, state_ent_coef, latent_ent_coef, latent_cond_ent_coef, update_encoder,
                  shard_pretraining=False, **kwargs):
-        self.shard_pretraining = bool(shard_pretraining)
         self.z_dim = self._meta_dim = z_dim
         self.state_ent_coef = state_ent_coef
         self.latent_ent_coef = latent_ent_coef
         self.latent_cond_ent_coef = latent_cond_ent_coef
         self.update_encoder = update_encoder
         kwargs['meta_dim'] = self.z_dim
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         O, H = self.obs_dim - z_dim, self.hidden_dim
         self.goal = (150, 75)
         w = _smm_init(O, z_dim, H)
-        self.intr = IntrEngine('smm', O, self.action_dim, H, **self._intr_dp(), rep_dim=z_dim, sp_lr=sp_lr, vae_lr=vae_lr, vae_beta=vae_beta,
-                               state_ent_coef=state_ent_coef, latent_ent_coef=latent_ent_coef, latent_cond_ent_coef=latent_cond_ent_coef,
-                               goal=self.goal, precision=self._precision, device=self.device, encoded=self.obs_type == 'pixels')
-        self.smm = NetView(self.intr, None, _SMM_KEYS)
-        for p, t in zip(self.smm.parameters(), w):
-            p.copy_(t.reshape(p.shape))
+        self.smm = self._module('smm', O, H, _SMM_KEYS, w, rep_dim=z_dim, sp_lr=sp_lr, vae_lr=vae_lr, vae_beta=vae_beta,
+                                state_ent_coef=state_ent_coef, latent_ent_coef=latent_ent_coef, latent_cond_ent_coef=latent_cond_ent_coef,
+                                goal=self.goal, encoded=self.obs_type == 'pixels')
         self.ft_returns = np.zeros(z_dim, dtype=np.float32)
         self.ft_not_finished = [True for _ in range(z_dim)]
         self.eps_hook = None            # tests: callable(shape) -> the VAE's epsilon (torch.randn in smm.py:62)
-        self._pix_alloc()
 
     def _eps(self):
         if self.eps_hook is None:
@@ -1398,19 +1325,6 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         return metrics
 
 
-class _TensorsView(NetView):
-    """A NetView over a subset of an engine's tensors (agent.predictor / .projector / .protos / .predictor_target)."""
-
-    def __init__(self, engine, indices, keys):
-        self._engine, self._net, self._keys, self._on_change = engine, None, list(keys), None
-        self.training = True
-        self._idx = list(indices)
-        self._params = [engine.tensor(None, i, L.T_PARAM) for i in self._idx]
-
-    def grads(self):
-        return [self._engine.tensor(None, i, L.T_GRAD) for i in self._idx]
-
-
 def _proto_init(O, pred_dim, proj_dim, num_protos):
     """proto.py:55-67: predictor (Linear + weight_init), projector (Projector applies weight_init itself, then the agent applies it
     again), protos (bias-free Linear + weight_init) — the same RNG consumption, tensor by tensor."""
@@ -1432,43 +1346,36 @@ def _proto_init(O, pred_dim, proj_dim, num_protos):
 class ProtoAgent(_IntrAgent):
     """agents/unsupervised_learning/proto.py:46-207 (configs/agent/proto.yaml) on state observations: the encoder is the identity,
     so encoder_target and the encoder's share of proto_opt vanish; the intrinsic reward is computed on next_obs (proto.py:175-177)."""
-    LOSS_KEY = 'repr_loss'
+    MODULE_METRICS = _module_table('repr_loss')
     _PIXELS_OK = True
 
     def __init__(self, pred_dim, proj_dim, queue_size, num_protos, tau, encoder_target_tau, topk, update_encoder, shard_pretraining=False,
                  **kwargs):
         # shard_pretraining: under torch.distributed, run the reward-free module step data-parallel (each rank's rows, the target and reward
         # rows all-gathered, Sinkhorn and the candidate draw run identically on every rank). Off by default: on pixels
-        # DDPGAgent._init_pixels refuses that case without it, so the flag is set before the base constructor runs; on states the default
+        # DDPGAgent.__init__ refuses that case without it, so _IntrAgent sets the flag before the base constructor runs; on states the default
         # is the replicated module on the gathered batch. No effect at world size 1.
-        self.shard_pretraining = bool(shard_pretraining)
-        super().__init__(**kwargs)
+        super().__init__(shard_pretraining, **kwargs)
         self.tau = tau
         self.encoder_target_tau = encoder_target_tau
         self.topk = topk
         self.num_protos = num_protos
         self.update_encoder = update_encoder
         self.encoder_target = _Identity()
-        self._precision = kwargs.get('precision', 'fp32')
         if self.obs_type == 'pixels':            # encoder_target = deepcopy(encoder) (proto.py:55): no RNG draws
-            c = self.obs_shape[0]
-            shapes = [s for l in range(4) for s in ((32, c if l == 0 else 32, 3, 3), (32,))]
             self.engine.encoder_target(init=True)
-            self.encoder_target = _ParamList(_ENC_KEYS, self.engine.encoder_target_tensors(shapes))
-            self._dobs = torch.zeros(self.engine.batch, self.obs_dim, device=self.engine.device)
+            self.encoder_target = NetView(_ENC_KEYS, self.engine.encoder_target_tensors(_conv_shapes(self.obs_shape[0])))
         O = self.obs_dim
         w = _proto_init(O, pred_dim, proj_dim, num_protos)
         dp = self._intr_dp() if self.shard_pretraining else dict(batch=self._module_batch)
-        self.intr = IntrEngine('proto', O, self.action_dim, proj_dim, **dp, rep_dim=pred_dim, lr=self.lr, knn_k=topk,
-                               num_protos=num_protos, queue_size=queue_size, tau=tau, target_tau=encoder_target_tau,
-                               precision=self._precision, device=self.device)
-        self.predictor = _TensorsView(self.intr, [0, 1], ['weight', 'bias'])
-        self.projector = _TensorsView(self.intr, [2, 3, 4, 5], ['trunk.0.weight', 'trunk.0.bias', 'trunk.2.weight', 'trunk.2.bias'])
-        self.protos = _TensorsView(self.intr, [6], ['weight'])
-        self.predictor_target = _TensorsView(self.intr, [7, 8], ['weight', 'bias'])
+        self._module('proto', O, proj_dim, None, None, dp=dp, rep_dim=pred_dim, knn_k=topk, num_protos=num_protos, queue_size=queue_size,
+                     tau=tau, target_tau=encoder_target_tau)
+        self.predictor = _net_view(self.intr, None, ['weight', 'bias'], indices=[0, 1])
+        self.projector = _net_view(self.intr, None, ['trunk.0.weight', 'trunk.0.bias', 'trunk.2.weight', 'trunk.2.bias'], indices=[2, 3, 4, 5])
+        self.protos = _net_view(self.intr, None, ['weight'], indices=[6])
+        self.predictor_target = _net_view(self.intr, None, ['weight', 'bias'], indices=[7, 8])
         for view, ts in ((self.predictor, w[0:2]), (self.projector, w[2:6]), (self.protos, w[6:7]), (self.predictor_target, w[0:2])):
-            for p, t in zip(view.parameters(), ts):
-                p.copy_(t.reshape(p.shape))
+            _load(view, ts)
         self.queue = self.intr.queue
         self.cat_hook = None            # tests: callable(num_protos) -> uniforms standing in for Categorical(prob).sample()
 
@@ -1492,25 +1399,18 @@ class ProtoAgent(_IntrAgent):
         return torch.as_tensor(np.asarray(self.cat_hook(self.num_protos), np.float32), device=self.engine.device)
 
     def _intr_step(self):
-        s = self._slots = self._slots or self.engine.batch_slots()
+        s = self._batch_slots()
         u = self._cat_u()
         self.intr.run_update(s.obs, None, s.next_obs, s.reward, s.reward, True, cat_uniform=u.data_ptr() if u is not None else None)
         self._keep_u = u
 
-    def _update_pixels(self, replay_iter, step):
+    def _pix_before_step(self):
         """proto.py:159-207 on pixels: augment once; the proto step reaches the encoder through proto_opt; reward from the re-encoded
-        next_obs; DDPG step with the encoding detached in update_critic; Polyak updates."""
+        next_obs; DDPG step with the encoding detached in update_critic; Polyak updates (_pix_after_step)."""
         eng = self.engine
-        if hasattr(replay_iter, 'sample_into'):
-            self._slots = self._slots or eng.batch_slots()
-            replay_iter.sample_into(self._slots, eng.batch)
-        else:
-            obs, action, reward, discount, next_obs = next(replay_iter)[:5]
-            eng.set_batch(obs, action, reward, discount, next_obs)
-        s = self._slots = self._slots or eng.batch_slots()
-        B, A = eng.batch, self.action_dim
-        eng.augment(self.shift_hook(B) if self.shift_hook else None, self.shift_hook(B) if self.shift_hook else None)
+        eng.augment(self._shifts(), self._shifts())         # drawn in fine-tuning too
         if self.reward_free:
+            s = self._batch_slots()
             fo = eng.encode(0)
             ft = eng.encode(1, target=True)
             # under torch.distributed (shard_pretraining): the module's phases with their exchanges, and the encoder's share of proto_opt
@@ -1525,57 +1425,21 @@ class ProtoAgent(_IntrAgent):
             # pass above — the same values, kept — and obs with the stepped encoder, the one pass left to make (4 of the update's 20
             # forward convolutions gone)
             eng.encode(0)
-        stddev = self._stddev(step)
         eng.set_train_encoder(False)
-        eng.run_update(stddev, None, None, self.noise_hook((B, A)) if self.noise_hook else None, self.noise_hook((B, A)) if self.noise_hook else None,
-                       keep_augmented=not self.reward_free, keep_encoded=self.reward_free)
-        eng.encoder_target(self.encoder_target_tau)
-        metrics = dict()
-        if self.use_tb or self.use_wandb:
-            metrics.update(self._metrics(_CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')], stddev))
-            if self.reward_free:
-                ri = self._intr_metrics()
-                metrics['repr_loss'] = float(ri[L.IM_LOSS])
-                metrics['intr_reward'] = float(ri[L.IM_INTR_REWARD])
-                metrics['extr_reward'] = float(ri[L.IM_EXTR_REWARD])
-        return metrics
+        return dict(keep_augmented=not self.reward_free, keep_encoded=self.reward_free)
 
-    def update(self, replay_iter, step):
-        if self.obs_type == 'pixels':
-            if step % self.update_every_steps != 0:
-                return dict()
-            return self._update_pixels(replay_iter, step)
-        return super().update(replay_iter, step)
+    def _pix_after_step(self):
+        self.engine.encoder_target(self.encoder_target_tau)
+
+    def _module_metrics(self, metrics):
+        if self.reward_free or self.obs_type == 'states':       # on pixels, fine-tuning reports no extr_reward
+            super()._module_metrics(metrics)
 
 
 _ENC_KEYS = [f'convnet.{i}.{w}' for i in (0, 2, 4, 6) for w in ('weight', 'bias')]
 _PIX_ACTOR_KEYS = ['trunk.0.weight', 'trunk.0.bias', 'trunk.1.weight', 'trunk.1.bias'] + [f'policy.{i}.{w}' for i in (0, 2, 4) for w in ('weight', 'bias')]
 _PIX_CRITIC_KEYS = (['trunk.0.weight', 'trunk.0.bias', 'trunk.1.weight', 'trunk.1.bias'] +
                     [f'{q}.{i}.{w}' for q in ('Q1', 'Q2') for i in (0, 2, 4) for w in ('weight', 'bias')])
-
-
-class _ParamList(NetView):
-    """A NetView over explicit tensors (encoder_target: a Polyak copy that lives outside the engine's net table)."""
-
-    def __init__(self, keys, tensors):
-        self._engine, self._net, self._keys, self._on_change = None, None, list(keys), None
-        self.training = True
-        self._params = list(tensors)
-
-
-class _PixelNetView(NetView):
-    """NetView over a PixelEngine net; conv weights are exposed in torch's (co, ci, 3, 3) shape."""
-
-    def __init__(self, engine, net, keys, shapes=None):
-        self._engine, self._net, self._keys, self._on_change = engine, net, list(keys), None
-        self.training = True
-        self._params = []
-        for i in range(len(keys)):
-            t = engine.tensor(net, i, L.T_PARAM)
-            self._params.append(t.view(*shapes[i]) if shapes else t)
-
-    def grads(self):
-        return [self._engine.tensor(self._net, i, L.T_GRAD) for i in range(len(self._keys))]
 
 
 def _pixel_init(c_in, hw, A, F, H, meta_dim=0, sf_dim=0):

@@ -29,8 +29,52 @@ def _require_gpu(device):
 
 
 class _Phased:
-    """What the engines with phased calls share: the choice between a call's one-call form and its phases under torch.distributed."""
+    """What the engines with phased calls share: the library handle over a torch-owned workspace with its tensor views (exorl_<prefix>_*
+    for prefix agent / intr / pixel_agent), and the choice between a call's one-call form and its phases under torch.distributed."""
     world_size, rank, comm = 1, None, None
+
+    def _create(self, prefix, cfg):
+        """self.h = exorl_<prefix>_create(cfg) on a zeroed workspace of exorl_<prefix>_workspace_bytes(cfg), aligned to 256 bytes; the
+        workspace is a torch tensor so that parameters can be exposed as tensors (state_dict, pickling, all-reduce)."""
+        self.lib, self.cfg, self._prefix = L.load(), cfg, prefix
+        nbytes = self._fn('workspace_bytes')(C.byref(cfg))
+        if nbytes == 0:
+            raise L.ExorlError(self.lib.exorl_last_error().decode())
+        with torch.cuda.device(self.device):
+            self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
+            base = self.workspace.data_ptr()
+            off = (-base) % 256
+            handle = C.c_void_p()
+            L.check(self._fn('create')(C.byref(cfg), base + off, nbytes, C.byref(handle)))
+        self.h = handle
+        self._f32 = self.workspace[off:off + nbytes].view(torch.float32)
+
+    def _fn(self, name):
+        return getattr(self.lib, f'exorl_{self._prefix}_{name}')
+
+    def __del__(self):
+        h, self.h = getattr(self, 'h', None), None
+        if h:
+            self._fn('destroy')(h)
+
+    # ---- views of library-laid-out memory as torch tensors ------------------------------------------
+    def _view(self, ptr, numel):
+        off = (ptr - self._f32.data_ptr()) // 4
+        return self._f32[off:off + numel]
+
+    def _net(self, net):
+        return () if net is None else (net,)        # the module engine has one net and its calls take no net argument
+
+    def num_tensors(self, net=None):
+        n = C.c_int32()
+        L.check(self._fn('num_tensors')(self.h, *self._net(net), C.byref(n)))
+        return n.value
+
+    def tensor(self, net, index, what=L.T_PARAM):
+        p, r, c = C.c_void_p(), C.c_int64(), C.c_int64()
+        L.check(self._fn('tensor')(self.h, *self._net(net), index, what, C.byref(p), C.byref(r), C.byref(c)))
+        v = self._view(p.value, r.value * c.value)
+        return v.view(r.value, c.value) if c.value > 1 else v
 
     def _run(self, one_call, steps, *a, **k):
         """one_call(*a, **k) on one rank, else its phases steps(*a, **k) with the exchanges run over torch.distributed."""
@@ -43,53 +87,15 @@ class AgentEngine(_Phased):
     def __init__(self, kind, obs_dim, act_dim, hidden_dim, batch, lr=1e-4, tau=0.01, alpha=2.5, stddev_clip=0.3,
                  precision='fp32', world_size=1, seed=0, device='cuda', num_value_samples=10, weight_func='indicator',
                  n_samples=3, use_critic_lagrange=False, target_cql_penalty=5.0, sf_dim=0):
-        self.lib = L.load()
         self.device = _require_gpu(device)
         self.kind = kind
-        self.cfg = L.AgentCfg(KIND[kind], obs_dim, act_dim, hidden_dim, batch, PRECISION[precision], world_size, sf_dim,
+        cfg = L.AgentCfg(KIND[kind], obs_dim, act_dim, hidden_dim, batch, PRECISION[precision], world_size, sf_dim,
                               lr, tau, alpha, stddev_clip if stddev_clip is not None else 0.0, seed, num_value_samples,
                               L.CRR_WEIGHT[weight_func], n_samples, int(bool(use_critic_lagrange)), target_cql_penalty, 0)
         self.obs_dim, self.act_dim, self.hidden_dim, self.batch = obs_dim, act_dim, hidden_dim, batch
         self.world_size, self.lagrange = world_size, kind == 'cql' and bool(use_critic_lagrange)
-        nbytes = self.lib.exorl_agent_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise L.ExorlError(self.lib.exorl_last_error().decode())
-        with torch.cuda.device(self.device):
-            self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-            base = self.workspace.data_ptr()
-            self._ws_off = (-base) % 256
-            handle = C.c_void_p()
-            L.check(self.lib.exorl_agent_create(C.byref(self.cfg), base + self._ws_off, nbytes, C.byref(handle)))
-        self.h = handle
-        self._f32 = self.workspace[self._ws_off:self._ws_off + nbytes].view(torch.float32)
+        self._create('agent', cfg)
         self.has_critic = kind != 'bc'
-
-    def __del__(self):
-        h, self.h = getattr(self, 'h', None), None
-        if h:
-            self.lib.exorl_agent_destroy(h)
-
-    # ---- views of library-laid-out memory as torch tensors ------------------------------------------
-    def _view(self, ptr, numel):
-        off = (ptr - self._f32.data_ptr()) // 4
-        return self._f32[off:off + numel]
-
-    def num_tensors(self, net):
-        n = C.c_int32()
-        L.check(self.lib.exorl_agent_num_tensors(self.h, net, C.byref(n)))
-        return n.value
-
-    def tensor(self, net, index, what=L.T_PARAM):
-        p, r, c = C.c_void_p(), C.c_int64(), C.c_int64()
-        L.check(self.lib.exorl_agent_tensor(self.h, net, index, what, C.byref(p), C.byref(r), C.byref(c)))
-        v = self._view(p.value, r.value * c.value)
-        return v.view(r.value, c.value) if c.value > 1 else v
-
-    def tensor_shaped(self, net, index, shape, what=L.T_PARAM):
-        p, r, c = C.c_void_p(), C.c_int64(), C.c_int64()
-        L.check(self.lib.exorl_agent_tensor(self.h, net, index, what, C.byref(p), C.byref(r), C.byref(c)))
-        assert int(np.prod(shape)) == r.value * c.value, (shape, r.value, c.value)
-        return self._view(p.value, r.value * c.value).view(*shape)
 
     def flat(self, net, what=L.T_PARAM):
         p, n = C.c_void_p(), C.c_int64()
@@ -265,24 +271,13 @@ class IntrEngine(_Phased):
                  knn_rms=True, knn_clip=0.0, clip_val=5.0, n_models=0, num_protos=0, queue_size=0, tau=0.1, target_tau=0.05, sp_lr=1e-3, vae_lr=1e-2,
                  vae_beta=0.5, state_ent_coef=1.0, latent_ent_coef=1.0, latent_cond_ent_coef=1.0, goal=(150.0, 75.0), precision='fp32',
                  device='cuda', encoded=False, world_size=1, rank=0):
-        self.lib = L.load()
         self.device = _require_gpu(device)
         self.kind, self.batch, self.obs_dim, self.act_dim = kind, batch, obs_dim, act_dim
         self.world_size, self.rank = world_size, rank
-        self.cfg = L.IntrCfg(self.KINDS[kind], obs_dim, act_dim, hidden_dim, rep_dim, batch, PRECISION[precision], knn_k, int(bool(knn_avg)),
+        cfg = L.IntrCfg(self.KINDS[kind], obs_dim, act_dim, hidden_dim, rep_dim, batch, PRECISION[precision], knn_k, int(bool(knn_avg)),
                              int(bool(knn_rms)), n_models, 1 if encoded else 0, lr, scale, knn_clip, clip_val, num_protos, queue_size, tau, target_tau,
                              sp_lr, vae_lr, vae_beta, state_ent_coef, latent_ent_coef, latent_cond_ent_coef, goal[0], goal[1], world_size, rank)
-        nbytes = self.lib.exorl_intr_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise L.ExorlError(self.lib.exorl_last_error().decode())
-        with torch.cuda.device(self.device):
-            self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-            base = self.workspace.data_ptr()
-            off = (-base) % 256
-            handle = C.c_void_p()
-            L.check(self.lib.exorl_intr_create(C.byref(self.cfg), base + off, nbytes, C.byref(handle)))
-        self.h = handle
-        self._f32 = self.workspace[off:off + nbytes].view(torch.float32)
+        self._create('intr', cfg)
         rms, bn, nbn = C.c_void_p(), C.c_void_p(), C.c_int64()
         L.check(self.lib.exorl_intr_state(self.h, C.byref(rms), C.byref(bn), C.byref(nbn)))
         self._rms = self._view(rms.value, 4)                       # {float M, float S, double n}
@@ -298,26 +293,6 @@ class IntrEngine(_Phased):
         ptr = C.c_int64(0 if set_to is None else int(set_to))
         L.check(self.lib.exorl_intr_queue(self.h, C.byref(q), C.byref(r), C.byref(c), C.byref(ptr), int(set_to is not None)))
         return ptr.value
-
-    def __del__(self):
-        h, self.h = getattr(self, 'h', None), None
-        if h:
-            self.lib.exorl_intr_destroy(h)
-
-    def _view(self, ptr, numel):
-        off = (ptr - self._f32.data_ptr()) // 4
-        return self._f32[off:off + numel]
-
-    def num_tensors(self, net=None):
-        n = C.c_int32()
-        L.check(self.lib.exorl_intr_num_tensors(self.h, C.byref(n)))
-        return n.value
-
-    def tensor(self, net, index, what=L.T_PARAM):
-        p, r, c = C.c_void_p(), C.c_int64(), C.c_int64()
-        L.check(self.lib.exorl_intr_tensor(self.h, index, what, C.byref(p), C.byref(r), C.byref(c)))
-        v = self._view(p.value, r.value * c.value)
-        return v.view(r.value, c.value) if c.value > 1 else v
 
     def flat(self, what=L.T_PARAM):
         p, n = C.c_void_p(), C.c_int64()
@@ -449,46 +424,15 @@ class PixelEngine(_Phased):
 
     def __init__(self, obs_shape, act_dim, feature_dim, hidden_dim, batch, lr=1e-4, tau=0.01, stddev_clip=0.3, precision='fp32', seed=0,
                  device='cuda', meta_dim=0, sf_dim=0, world_size=1):
-        self.lib = L.load()
         self.device = _require_gpu(device)
         self.world_size = world_size
         c, h, w = obs_shape
         if h != w:
             raise L.ExorlError(f'pixel observations must be square, got {obs_shape}')
         self.obs_shape, self.act_dim, self.batch, self.meta_dim = tuple(obs_shape), act_dim, batch, meta_dim
-        self.cfg = L.PixelCfg(c, h, act_dim, feature_dim, hidden_dim, batch, PRECISION[precision], meta_dim, lr, tau,
+        cfg = L.PixelCfg(c, h, act_dim, feature_dim, hidden_dim, batch, PRECISION[precision], meta_dim, lr, tau,
                               stddev_clip if stddev_clip is not None else 0.0, sf_dim, seed, world_size)
-        nbytes = self.lib.exorl_pixel_agent_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise L.ExorlError(self.lib.exorl_last_error().decode())
-        with torch.cuda.device(self.device):
-            self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-            base = self.workspace.data_ptr()
-            off = (-base) % 256
-            handle = C.c_void_p()
-            L.check(self.lib.exorl_pixel_agent_create(C.byref(self.cfg), base + off, nbytes, C.byref(handle)))
-        self.h = handle
-        self._f32 = self.workspace[off:off + nbytes].view(torch.float32)
-
-    def __del__(self):
-        h, self.h = getattr(self, 'h', None), None
-        if h:
-            self.lib.exorl_pixel_agent_destroy(h)
-
-    def _view(self, ptr, numel):
-        off = (ptr - self._f32.data_ptr()) // 4
-        return self._f32[off:off + numel]
-
-    def num_tensors(self, net):
-        n = C.c_int32()
-        L.check(self.lib.exorl_pixel_agent_num_tensors(self.h, net, C.byref(n)))
-        return n.value
-
-    def tensor(self, net, index, what=L.T_PARAM):
-        p, r, c = C.c_void_p(), C.c_int64(), C.c_int64()
-        L.check(self.lib.exorl_pixel_agent_tensor(self.h, net, index, what, C.byref(p), C.byref(r), C.byref(c)))
-        v = self._view(p.value, r.value * c.value)
-        return v.view(r.value, c.value) if c.value > 1 else v
+        self._create('pixel_agent', cfg)
 
     def sync_target(self):
         L.check(self.lib.exorl_pixel_agent_sync_target(self.h, L.current_stream()))

@@ -1,0 +1,320 @@
+"""Digests of everything the agent classes compute, for comparing two trees bit for bit (a refactor of exorl_amd/agents.py or engine.py
+must leave every line equal). Run it from each tree in a fresh process per listing, then compare the listings:
+
+    python tools/agent_digests.py part1 OUT.txt [PICKLE_DIR]   every agent class, three update() calls; writes pickle.dumps(agent) per case
+    python tools/agent_digests.py part2 OUT.txt PICKLE_DIR     loads those pickles (written by either tree), one more update()
+    python tools/agent_digests.py part3 OUT.txt                the five two-process gloo workers of tests/, every array and json they save
+    python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
+
+A listing has one line per entry, `case what value`; a value is the first 32 hex digits of a sha256 or a float.hex(). Inputs come from
+tests/_synth.py and seeded numpy streams only. Needs a GPU (there is no CPU path)."""
+import hashlib
+import json
+import os
+import pickle
+import socket
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / 'tests'))
+
+O, A, H, B = 24, 6, 256, 256                        # states
+PC, PHW, PF, PH, PB = 3, 64, 32, 128, 64            # pixels: the two-process workers' frames and widths
+OFFLINE = ['td3_bc', 'td3', 'bc', 'crr', 'cql', 'cql_lagrange']
+MODULES = ['rnd', 'icm', 'icm_apt', 'disagreement', 'diayn', 'aps', 'smm', 'proto']
+META = {'states': {'diayn': 16, 'aps': 10, 'smm': 4}, 'pixels': {'diayn': 8, 'aps': 5, 'smm': 4}}
+PRECISIONS = {'states': ('fp32', 'bf16x3'), 'pixels': ('fp32', 'bf16x6')}
+
+
+def sha(x):
+    if hasattr(x, 'detach'):
+        x = x.detach().cpu().numpy()
+    if isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x).tobytes()
+    if isinstance(x, str):
+        x = x.encode()
+    return hashlib.sha256(x).hexdigest()[:32]
+
+
+def build(kind, obs_type, reward_free, precision, use_tb=True):
+    import torch
+    from exorl_amd import agents
+    torch.manual_seed(7)
+    if kind in OFFLINE:
+        a = ('x', (O,), (A,), 'cuda:0', 1e-4, H, 0.01)
+        if kind == 'td3_bc':
+            return agents.TD3BCAgent(*a, '0.2', 1, B, 0.3, use_tb, 2.5, precision=precision)
+        if kind == 'td3':
+            return agents.TD3Agent(*a, '0.2', 1, B, 0.3, use_tb, precision=precision)
+        if kind == 'crr':
+            return agents.CRRAgent(*a, 4, 'exp', '0.2', 1, B, 0.3, use_tb, precision=precision)
+        if kind == 'bc':
+            return agents.BCAgent('x', (O,), (A,), 'cuda:0', 1e-4, H, B, '0.2', use_tb, precision=precision)
+        return agents.CQLAgent(*a, 1, B, use_tb, 0.01, 3, 5.0, kind == 'cql_lagrange', precision=precision)
+    pix = obs_type == 'pixels'
+    kw = dict(name=kind, reward_free=reward_free, obs_type=obs_type, obs_shape=(PC, PHW, PHW) if pix else (O,), action_shape=(A,),
+              device='cuda:0', lr=1e-4, feature_dim=PF if pix else 50, hidden_dim=PH if pix else H, critic_target_tau=0.01, num_expl_steps=0,
+              update_every_steps=1, stddev_schedule=0.2, nstep=3, batch_size=PB if pix else B, stddev_clip=0.3, init_critic=True, use_tb=use_tb,
+              use_wandb=False, precision=precision)
+    M = META[obs_type].get(kind, 0)
+    knn = dict(knn_rms=True, knn_k=12, knn_avg=True, knn_clip=0.0)
+    if kind == 'ddpg':
+        return agents.DDPGAgent(**kw)
+    if kind == 'rnd':
+        return agents.RNDAgent(rnd_rep_dim=32, update_encoder=True, rnd_scale=1.0, **kw)
+    if kind == 'icm':
+        return agents.ICMAgent(icm_scale=1.0, update_encoder=True, **kw)
+    if kind == 'icm_apt':
+        return agents.ICMAPTAgent(icm_scale=1.0, update_encoder=True, icm_rep_dim=32, **knn, **kw)
+    if kind == 'disagreement':
+        return agents.DisagreementAgent(update_encoder=True, **kw)
+    if kind == 'diayn':
+        return agents.DIAYNAgent(update_skill_every_step=50, skill_dim=M, diayn_scale=1.0, update_encoder=True, skill_type='uniform', **kw)
+    if kind == 'aps':
+        return agents.APSAgent(update_task_every_step=50, sf_dim=M, num_init_steps=0, lstsq_batch_size=64, update_encoder=True, **knn, **kw)
+    if kind == 'smm':
+        return agents.SMMAgent(z_dim=M, sp_lr=1e-3, vae_lr=1e-2, vae_beta=0.5, state_ent_coef=1.0, latent_ent_coef=1.0,
+                               latent_cond_ent_coef=1.0, update_encoder=True, **kw)
+    return agents.ProtoAgent(pred_dim=32, proj_dim=64, queue_size=256, num_protos=32, tau=0.1, encoder_target_tau=0.05, topk=3,
+                             update_encoder=True, **kw)
+
+
+def arena(kind, obs_type, seed=5):
+    """An ArenaIterator with the Philox sampler over synthetic episodes: the loader's sample_into branch."""
+    import _synth
+    from exorl_amd.engine import ReplayEngine
+    from exorl_amd.replay_buffer import ArenaIterator
+    pix = obs_type == 'pixels'
+    M = META[obs_type].get(kind, 0)
+    shape, rows, batch = ((PC, PHW, PHW), 60, PB) if pix else ((O,), 300, B)
+    eps = _synth.synth_episodes(seed, [rows] * 3, int(np.prod(shape)), A, M, obs_u8=pix)
+    eng = ReplayEngine(shape, np.uint8 if pix else np.float32, A, M, 3 * (rows + 1) + 64, 16, 'cuda:0')
+    eng.set_order([eng.append_episode(ep, ('skill',) if M else ()) for ep in eps])
+    eng.seed_philox(seed)
+    return ArenaIterator(eng, batch, 1 if kind in OFFLINE else 3, 0.99, 'philox')
+
+
+def batches(kind, obs_type, first, n):
+    """A plain iterator of 5- or 6-tuples: the loader's next() branch."""
+    import _synth
+    pix = obs_type == 'pixels'
+    M = META[obs_type].get(kind, 0)
+    for step in range(first, first + n):
+        rs = np.random.RandomState(900 + step)
+        if pix:
+            frames = [rs.randint(0, 256, (PB, PC, PHW, PHW)).astype(np.uint8) for _ in range(2)]
+            _, act, rew, disc, _ = _synth.synth_batch(41, step, PB, 4, A)
+            b = [frames[0], act, rew, disc, frames[1]]
+        else:
+            b = list(_synth.synth_batch(41, step, B, O, A))
+        if M:
+            m = rs.standard_normal((b[1].shape[0], M)).astype(np.float32)
+            b.append(m / np.linalg.norm(m, axis=1, keepdims=True) if kind == 'aps' else np.eye(M, dtype=np.float32)[m.argmax(1)])
+        yield tuple(b)
+
+
+def set_hooks(ag, seed):
+    """Every hook an agent has, all fed from ONE stream: a changed call order changes every later draw."""
+    rs = np.random.RandomState(seed)
+    normal = lambda shape: rs.standard_normal(tuple(shape)).astype(np.float32)
+    ag.noise_hook = lambda shape, dist='normal': np.tanh(normal(shape)) if dist == 'uniform' else normal(shape)
+    if hasattr(ag, 'shift_hook'):
+        ag.shift_hook = lambda n: rs.randint(0, 9, (n, 2)).astype(np.int32)
+    if hasattr(ag, 'cat_hook'):
+        ag.cat_hook = lambda n: rs.uniform(size=n).astype(np.float32)
+    if hasattr(ag, 'eps_hook'):
+        ag.eps_hook = normal
+
+
+def digest(ag, emit):
+    """Everything that defines the agent's state, one entry each."""
+    import torch
+    from exorl_amd import _lib as L
+    torch.cuda.synchronize()
+    eng = ag.engine
+    emit('engine.workspace', sha(eng.workspace))
+    if getattr(ag, 'obs_type', 'states') == 'pixels':
+        st = eng.export_state()
+        emit('engine.steps', sha(st['steps'])), emit('engine.counters', sha(st['counters'])), emit('engine.bn2d', sha(st['bn2d']))
+        for (net, what), ts in sorted(st['tensors'].items()):
+            emit(f'engine.net{net}.what{what}', sha(torch.cat([t.reshape(-1) for t in ts])))
+        for i, t in enumerate(st['enc_extra']):
+            emit(f'engine.enc_extra{i}', sha(t))
+        for name in ('encoder', 'actor', 'critic'):
+            emit(f'engine.{name}.grads', sha(torch.cat([g.reshape(-1) for g in getattr(ag, name).grads()])))
+    else:
+        for net in [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else []):
+            for what in ((L.T_PARAM,) if net == L.NET_CRITIC_TARGET else (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V, L.T_GRAD)):
+                emit(f'engine.net{net}.what{what}', sha(eng.flat(net, what)))
+        emit('engine.opt_steps', sha(repr(eng.opt_steps()))), emit('engine.noise_counter', sha(repr(eng.noise_counter())))
+        if ag.KIND == 'cql':
+            emit('engine.cql_alpha', sha(eng.cql_alpha_state()))
+    if hasattr(ag, 'intr'):
+        it = ag.intr
+        emit('intr.workspace', sha(it.workspace))
+        for what in (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V, L.T_GRAD):
+            emit(f'intr.what{what}', sha(it.flat(what)))
+        emit('intr.rms', sha(it._rms)), emit('intr.opt_steps', sha(repr(it.opt_steps()))), emit('intr.counter', sha(repr(it.counter())))
+        if it.bn is not None:
+            emit('intr.bn', sha(it.bn))
+        if it.queue is not None:
+            emit('intr.queue', sha(it.queue)), emit('intr.queue_ptr', sha(repr(it.queue_ptr())))
+    for name in ('encoder_target', 'rnd_target_encoder', 'rnd', 'predictor_target'):       # views that add buffers or sit outside the net table
+        view = getattr(ag, name, None)
+        if hasattr(view, 'state_dict'):
+            emit(f'{name}.state_dict', sha(','.join(f'{k}={sha(v)}' for k, v in view.state_dict().items())))
+    emit('getstate.attrs', sha(','.join(sorted(ag.__getstate__()['attrs']))))
+
+
+def emit_metrics(emit, tag, m):
+    emit(f'{tag}.keys', sha(','.join(sorted(m))))
+    for k in sorted(m):
+        emit(f'{tag}.{k}', float(m[k]).hex())
+
+
+def act_inputs(ag, kind, obs_type):
+    rs = np.random.RandomState(77)
+    obs = rs.randint(0, 256, (PC, PHW, PHW)).astype(np.uint8) if obs_type == 'pixels' else rs.standard_normal(O).astype(np.float32)
+    if kind in OFFLINE:
+        return (obs,)
+    M = META[obs_type].get(kind, 0)
+    meta = {'m': np.eye(M, dtype=np.float32)[1]} if M else {}
+    return (obs, meta)
+
+
+def run_case(emit, kind, obs_type, reward_free, precision, mode, first, n, ag=None, use_tb=True):
+    """`n` update() calls from step `first` over an ArenaIterator without hooks (mode 'arena'), a plain iterator with every hook set
+    ('hooks'), or a captured graph ('graph'); then the digests and one act() in each mode."""
+    ag = ag or build(kind, obs_type, reward_free, precision, use_tb)
+    if not hasattr(ag, 'num_expl_steps'):
+        ag.num_expl_steps = 0              # the offline classes leave it to the training script; act() reads it
+    if mode == 'hooks':
+        set_hooks(ag, 100 + first)
+        it = batches(kind, obs_type, first, n)
+    else:
+        it = arena(kind, obs_type, 5 + first)
+        if mode == 'graph':
+            assert ag.enable_graph(it)
+    for i in range(first, first + n):
+        emit_metrics(emit, f'metrics{i}', ag.update(it, i))
+    digest(ag, emit)
+    for eval_mode in (True, False):
+        emit(f'act.eval{int(eval_mode)}', sha(np.asarray(ag.act(*act_inputs(ag, kind, obs_type), 10, eval_mode), np.float32)))
+    return ag
+
+
+def cases():
+    """(name, kind, obs_type, reward_free, precision, mode, use_tb) of every case."""
+    def case(kind, obs_type, reward_free, precision, mode, use_tb=True):
+        name = f'{obs_type}/{kind}/{"pretrain" if reward_free else "finetune"}/{precision}/{mode}' + ('' if use_tb else '/no_tb')
+        return name, kind, obs_type, reward_free, precision, mode, use_tb
+    for mode in ('arena', 'hooks'):
+        for precision in PRECISIONS['states']:
+            for kind in OFFLINE:
+                yield case(kind, 'states', False, precision, mode)
+        for obs_type in ('states', 'pixels'):
+            for precision in PRECISIONS[obs_type]:
+                for kind in ['ddpg'] + MODULES:
+                    for reward_free in (True, False):
+                        yield case(kind, obs_type, reward_free, precision, mode)
+    yield case('td3_bc', 'states', False, 'bf16x3', 'graph', use_tb=False)
+    yield case('smm', 'states', True, 'fp32', 'hooks', use_tb=False)     # SMM reports its module's metrics whatever use_tb says
+
+
+def listing(path, body):
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit('agent_digests: needs a GPU')
+    lines = []
+    body(lambda case: (lambda what, value: lines.append(f'{case} {what} {value}')))
+    Path(path).write_text('\n'.join(lines) + '\n')
+    print(f'{path}: {len(lines)} entries')
+
+
+def part1(out, pickle_dir=None):
+    def body(emitter):
+        for name, *c, use_tb in cases():
+            ag = run_case(emitter(name), *c, 0, 3, use_tb=use_tb)
+            if pickle_dir:
+                if c[-1] == 'graph':
+                    ag.disable_graph()
+                Path(pickle_dir, name.replace('/', '__') + '.pkl').write_bytes(pickle.dumps(ag))
+            print(name, flush=True)
+    if pickle_dir:
+        Path(pickle_dir).mkdir(parents=True, exist_ok=True)
+    listing(out, body)
+
+
+def part2(out, pickle_dir):
+    def body(emitter):
+        for name, *c, use_tb in cases():
+            ag = pickle.loads(Path(pickle_dir, name.replace('/', '__') + '.pkl').read_bytes())
+            run_case(emitter(name), *c, 3, 1, ag=ag)
+            print(name, flush=True)
+    listing(out, body)
+
+
+WORKERS = ['_dp_worker.py', '_pixel_dp_worker.py', '_pixel_module_dp_worker.py', '_proto_pixel_dp_worker.py', '_state_module_dp_worker.py']
+
+
+def part3(out):
+    """Each worker script as its test fixture starts it: two fresh rank processes on cuda:0 over gloo."""
+    def body(emitter):
+        for worker in WORKERS:
+            tmp = Path(tempfile.mkdtemp(prefix='agent_digests_'))
+            args = [str(tmp)]
+            if worker == '_dp_worker.py':
+                import _dp_worker
+                _dp_worker.write_dataset(tmp / 'buffer')
+                (tmp / 'out').mkdir()
+                args = [str(tmp / 'buffer'), str(tmp / 'out')]
+            with socket.socket() as s:
+                s.bind(('127.0.0.1', 0))
+                port = s.getsockname()[1]
+            procs = []
+            for rank in range(2):
+                env = dict(os.environ, RANK=str(rank), WORLD_SIZE='2', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+                procs.append(subprocess.Popen([sys.executable, str(ROOT / 'tests' / worker), *args], env=env,
+                                              stdout=open(tmp / f'rank{rank}.log', 'w'), stderr=subprocess.STDOUT))
+            try:
+                rcs = [p.wait(timeout=600) for p in procs]
+            finally:
+                for p in procs:
+                    if p.poll() is None:
+                        p.kill()
+            if any(rcs):
+                sys.exit(f'{worker}: exit status {rcs}\n' + ''.join((tmp / f'rank{r}.log').read_text()[-3000:] for r in range(2)))
+            emit = emitter(worker)
+            for f in sorted(tmp.rglob('*.npz')):
+                if 'buffer' in f.relative_to(tmp).parts:
+                    continue
+                z = np.load(f, allow_pickle=False)
+                for k in sorted(z.files):
+                    emit(f'{f.name}:{k}', sha(z[k]))
+            for f in sorted(tmp.rglob('*.json')):
+                emit(f.name, sha(json.dumps(json.load(open(f)), sort_keys=True)))
+            print(worker, flush=True)
+    listing(out, body)
+
+
+def compare(a, b):
+    la, lb = Path(a).read_text().splitlines(), Path(b).read_text().splitlines()
+    key = lambda l: l.rsplit(' ', 1)[0]
+    da, db = {key(l): l for l in la}, {key(l): l for l in lb}
+    diff = [f'{da.get(k, k + " <missing>")}  |  {db.get(k, "<missing>").rsplit(" ", 1)[-1]}' for k in sorted(set(da) | set(db))
+            if da.get(k) != db.get(k)]
+    print(f'{len(set(da) | set(db))} entries, {len(diff)} differ')
+    for d in diff:
+        print(d)
+    return 1 if diff else 0
+
+
+if __name__ == '__main__':
+    cmd, args = sys.argv[1], sys.argv[2:]
+    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'compare': compare}[cmd](*args))
