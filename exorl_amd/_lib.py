@@ -162,6 +162,7 @@ PROTOTYPES = {
     'exorl_agent_opt_steps': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_agent_set_opt_steps': (C.c_int, [c_void_p, c_int64, c_int64]),
     'exorl_agent_enable_graph': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_float, c_void_p]),
+    'exorl_agent_enable_graph_intr': (C.c_int, [c_void_p, c_void_p, P(IntrBatch), c_int32, c_void_p, c_int32, c_float, c_float, c_void_p]),
     'exorl_agent_step_graph': (C.c_int, [c_void_p, c_float, c_void_p]),
     'exorl_agent_noise_counter': (C.c_int, [c_void_p, P(c_uint64), c_void_p]),
     'exorl_debug_philox_normal': (C.c_int, [c_uint64, c_uint64, c_int64, c_void_p, c_void_p]),

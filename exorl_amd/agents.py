@@ -747,12 +747,39 @@ class _IntrAgent(DDPGAgent):
             self._dobs = torch.zeros(self.engine.batch, self.obs_dim - self._pix_meta_dim, dtype=torch.float32, device=self.engine.device)
         return view
 
-    def _intr_step(self):
+    def _intr_args(self):
+        """The module's view of the batch slots on states: IntrEngine.update's five pointers and its stride keywords."""
         s = self._batch_slots()
-        self.intr.run_update(s.obs, s.action, s.next_obs, s.reward, s.reward, True)
+        return (s.obs, s.action, s.next_obs, s.reward, s.reward), {}
+
+    def _intr_hooks(self):
+        """Host-supplied draws of the module step (tests): IntrEngine.update keywords; empty when no hook is set."""
+        return {}
+
+    def _intr_step(self):
+        a, k = self._intr_args()
+        self.intr.run_update(*a, True, **k, **self._intr_hooks())
+
+    def _hooked(self):
+        return any(getattr(self, h, None) is not None for h in ('noise_hook', 'cat_hook', 'eps_hook'))
 
     def enable_graph(self, replay_iter, step=0):
-        return False                     # the module step is launched eagerly in front of the DDPG chain
+        """One hipGraph per update on state observations in one process: sample -> module step and intrinsic reward -> DDPG step
+        (reward_free), or sample -> DDPG step (fine-tuning: the module is not stepped). Returns False and stays eager on pixels, under
+        torch.distributed (the replicated and the sharded module step run their collectives in Python), for an iterator without the
+        Philox HBM sampler, and while a test hook supplies draws from the host. A hook set later sends that step down the eager path."""
+        eng = getattr(replay_iter, 'engine', None)
+        if (self.obs_type != 'states' or self.world_size != 1 or eng is None or getattr(replay_iter, 'sampler', None) != L.SAMPLER_PHILOX or
+                self._hooked()):
+            return False
+        self._graph_stddev = self._stddev(step)
+        intr = batch = None
+        if self.reward_free:
+            a, k = self._intr_args()
+            intr, batch = self.intr, self.intr._batch(*a, **k)
+        self.engine.enable_graph_intr(eng, replay_iter.nstep, replay_iter.discount, self._graph_stddev, intr, batch, getattr(self, '_meta_dim', 0))
+        self._graph_iter = replay_iter
+        return True
 
     # ---- data parallel (SURVEY 8e, last row) ----------------------------------------------------------------------------------------
     # What these modules compute is batch-global: BatchNorm statistics and the running RMS of the rewards (rnd.py:24,47-60,
@@ -869,6 +896,9 @@ class _IntrAgent(DDPGAgent):
             metrics['extr_reward'] = metrics['batch_reward']
 
     def _step(self, replay_iter, stddev):
+        if replay_iter is self._graph_iter and not self._hooked():
+            self.engine.step_graph(stddev)            # the module's counters and the std live in device memory: no re-capture
+            return
         self._load_batch(replay_iter)
         if self.reward_free:
             if self.world_size != 1 and not self._sharded_states:
@@ -1060,10 +1090,10 @@ class _MetaObsMixin:
         obs, action, reward, discount, next_obs, meta = [torch.as_tensor(x).to(self.engine.device, torch.float32) for x in next(replay_iter)[:6]]
         self.engine.set_batch(torch.cat([obs, meta], 1), action, reward, discount, torch.cat([next_obs, meta], 1))
 
-    def _intr_step(self):
+    def _intr_args(self):
         O, W = self.obs_dim - self._meta_dim, self.obs_dim
-        s = self._slots
-        self.intr.run_update(s.obs, None, s.next_obs, s.reward, s.reward, True, skill=s.obs + 4 * O, obs_ld=W, next_obs_ld=W, skill_ld=W)
+        s = self._batch_slots()
+        return (s.obs, None, s.next_obs, s.reward, s.reward), dict(skill=s.obs + 4 * O, obs_ld=W, next_obs_ld=W, skill_ld=W)
 
 
 class DIAYNAgent(_MetaObsMixin, _IntrAgent):
@@ -1295,15 +1325,17 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
                 meta['z'] = new_z
         return meta
 
-    def _intr_step(self):
+    def _intr_args(self):
         O, W = self.obs_dim - self._meta_dim, self.obs_dim
-        s = self._slots
+        s = self._batch_slots()
+        return (s.obs, None, None, s.reward, s.reward), dict(skill=s.obs + 4 * O, obs_ld=W, skill_ld=W)
+
+    def _intr_hooks(self):
         e = None
         if self.eps_hook is not None:
             e = torch.as_tensor(np.asarray(self.eps_hook((self.intr.batch, 128)), np.float32), device=self.engine.device).contiguous()
-        self.intr.run_update(s.obs, None, None, s.reward, s.reward, True, skill=s.obs + 4 * O, obs_ld=W, skill_ld=W,
-                             cat_uniform=e.data_ptr() if e is not None else None)
         self._keep_eps = e
+        return dict(cat_uniform=e.data_ptr()) if e is not None else {}
 
     def update(self, replay_iter, step):
         if step % self.update_every_steps != 0:
@@ -1398,11 +1430,13 @@ class ProtoAgent(_IntrAgent):
             return None
         return torch.as_tensor(np.asarray(self.cat_hook(self.num_protos), np.float32), device=self.engine.device)
 
-    def _intr_step(self):
+    def _intr_args(self):
         s = self._batch_slots()
-        u = self._cat_u()
-        self.intr.run_update(s.obs, None, s.next_obs, s.reward, s.reward, True, cat_uniform=u.data_ptr() if u is not None else None)
-        self._keep_u = u
+        return (s.obs, None, s.next_obs, s.reward, s.reward), {}
+
+    def _intr_hooks(self):
+        u = self._keep_u = self._cat_u()
+        return dict(cat_uniform=u.data_ptr()) if u is not None else {}
 
     def _pix_before_step(self):
         """proto.py:159-207 on pixels: augment once; the proto step reaches the encoder through proto_opt; reward from the re-encoded

@@ -434,6 +434,8 @@ struct exorl_agent {
     hipGraph_t graph = nullptr;
     hipStream_t capture_stream = nullptr;
     exorl_replay* graph_replay = nullptr;
+    uint64_t graph_replay_ctr = 0;           // host mirror of state->replay_counter: eager samples drawn between two launches move the replay's own
+    exorl_intr* graph_intr = nullptr;        // joint graph (exorl_agent_enable_graph_intr): the module whose step rides in front of the agent's
     bool capturing = false;
     Fork fk{};                   // parallel-branch plumbing (active while capturing)
     bool parallel_branches = false;  // measured slower than one chain on MI355X (2987 vs 3259 steps/s): opt-in
@@ -886,6 +888,7 @@ static int release_graph(exorl_agent* a) {
     if (a->graph_exec) { EXORL_CHECK_HIP(hipGraphExecDestroy(a->graph_exec)); a->graph_exec = nullptr; }
     if (a->graph) { EXORL_CHECK_HIP(hipGraphDestroy(a->graph)); a->graph = nullptr; }
     a->graph_replay = nullptr;
+    a->graph_intr = nullptr;
     return 0;
 }
 
@@ -1189,7 +1192,9 @@ int exorl_agent_set_opt_steps(exorl_agent_t* a, int64_t actor_steps, int64_t cri
     return push_opt_steps(a);
 }
 
-int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep, float gamma, float stddev, void* stream) {
+// sample -> [meta columns into the next_obs rows] -> [module step + intrinsic reward] -> the agent's step, captured once
+static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_intr_batch* ib, int32_t meta_dim, exorl_replay_t* r, int32_t nstep,
+                             float gamma, float stddev, void* stream) {
     EXORL_REQUIRE(a && r, "agent_enable_graph: null argument");
     // a previous step (eager or a graph launch) may still be running on the caller's stream and reads the buffers the new graph is
     // built over; releasing a graph exec that is executing is not allowed either. Setup call: a full stream sync is fine here.
@@ -1201,6 +1206,21 @@ int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep,
     if (!a->capture_stream) EXORL_CHECK_HIP(hipStreamCreateWithFlags(&a->capture_stream, hipStreamNonBlocking));
     exorl_batch_out slots;
     EXORL_TRY(exorl_agent_batch_slots(a, &slots));
+    const int O_raw = a->cfg.obs_dim - meta_dim;
+    if (meta_dim > 0) {          // [obs | meta] rows: the gather fills the obs rows' meta columns, a second kernel the next_obs rows'
+        int r_act = 0, r_meta = 0;
+        replay_dims(r, &r_act, &r_meta);
+        EXORL_REQUIRE(O_raw > 0 && replay_obs_bytes(r) == O_raw * 4 && r_act == a->cfg.act_dim && r_meta == meta_dim,
+                      "agent_enable_graph_intr: the replay's rows (%d obs bytes, %d action, %d meta columns) do not fill [obs | meta] rows of "
+                      "%d + %d floats and %d actions", replay_obs_bytes(r), r_act, r_meta, O_raw, meta_dim, a->cfg.act_dim);
+        slots.meta = a->obs + O_raw;
+        slots.meta_stride = a->cfg.obs_dim;
+    }
+    if (it) {
+        EXORL_REQUIRE(ib && ib->reward_out == a->reward && (!ib->extr_reward || ib->extr_reward == a->reward),
+                      "agent_enable_graph_intr: the module writes its reward into the agent's reward slot");
+        EXORL_TRY(intr_graph_prepare(it, ib, a->capture_stream));
+    }
     // what a sample call would do on the host side (episode table upload, pair buffer, nstep vs episode lengths) — no draw is spent
     EXORL_TRY(replay_prepare(r, a->cfg.batch, nstep, a->capture_stream));
     const uint64_t ctr = replay_philox_counter(r);
@@ -1223,6 +1243,10 @@ int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep,
     a->staged_by_sampler = replay_obs_bytes(r) == a->cfg.obs_dim * 4;
     int rc = replay_sample_impl(r, a->cfg.batch, nstep, gamma, EXORL_SAMPLER_PHILOX, nullptr, &slots, nullptr, a->capture_stream,
                                 &a->state->replay_counter, a->staged_by_sampler ? &stage : nullptr);
+    if (rc == 0 && meta_dim > 0) rc = copy_meta_columns(a->obs, a->next_obs, a->cfg.obs_dim, a->cfg.batch, O_raw, meta_dim, a->capture_stream);
+    // the module reads the batch slots and writes the reward slot only: what the sampler staged for the networks (observations and actions)
+    // stays valid, and the agent's step reads the reward from its slot after this
+    if (rc == 0 && it) rc = intr_graph_capture(it, ib, a->capture_stream);
     a->fuse_opt = !a->comm && !a->fk.on;
     a->whole_step = true;
     if (rc == 0) rc = whole_step_body(a, stddev, nullptr, nullptr, a->capture_stream);      // RCCL's all-reduces are captured with the kernels around them
@@ -1240,7 +1264,21 @@ int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep,
     a->graph = g;
     EXORL_CHECK_HIP(hipGraphInstantiate(&a->graph_exec, g, nullptr, nullptr, 0));
     a->graph_replay = r;
+    a->graph_replay_ctr = ctr;
+    a->graph_intr = it;
     return 0;
+}
+
+int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep, float gamma, float stddev, void* stream) {
+    return enable_graph_impl(a, nullptr, nullptr, 0, r, nstep, gamma, stddev, stream);
+}
+
+int exorl_agent_enable_graph_intr(exorl_agent_t* a, exorl_intr_t* intr, const exorl_intr_batch* batch, int32_t meta_dim, exorl_replay_t* r,
+                                  int32_t nstep, float gamma, float stddev, void* stream) {
+    EXORL_REQUIRE(a, "agent_enable_graph_intr: null argument");
+    EXORL_REQUIRE(meta_dim >= 0 && meta_dim < a->cfg.obs_dim, "agent_enable_graph_intr: meta_dim=%d out of range", meta_dim);
+    EXORL_REQUIRE(!intr || a->cfg.world_size == 1, "agent_enable_graph_intr: the joint graph is the one-process step");
+    return enable_graph_impl(a, intr, batch, meta_dim, r, nstep, gamma, stddev, stream);
 }
 
 int exorl_agent_noise_counter(exorl_agent_t* a, uint64_t* counter_out, void* stream) {
@@ -1298,6 +1336,7 @@ int exorl_agent_set_metrics(exorl_agent_t* a, int32_t enable) {
 
 int exorl_agent_disable_graph(exorl_agent_t* a) {
     EXORL_REQUIRE(a, "agent_disable_graph: null handle");
+    if (a->graph_intr) intr_graph_release(a->graph_intr);
     return release_graph(a);
 }
 
@@ -1309,10 +1348,15 @@ int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
         EXORL_TRY(set_device_float(&a->state->stddev, stddev, as_stream(stream)));
         a->dev_stddev = stddev;
     }
+    const uint64_t ctr = replay_philox_counter(a->graph_replay);
+    if (ctr != a->graph_replay_ctr) EXORL_TRY(set_device_u64(&a->state->replay_counter, ctr, as_stream(stream)));      // eager batches were drawn in between
+    a->graph_replay_ctr = ctr + 1;
+    if (a->graph_intr) EXORL_TRY(intr_graph_before_launch(a->graph_intr, as_stream(stream)));      // counters an eager step or a setter moved
     EXORL_CHECK_HIP(hipGraphLaunch(a->graph_exec, as_stream(stream)));
     a->actor_t += 1;
     if (a->has_critic) a->critic_t += 1;
     replay_advance_philox(a->graph_replay, 1);
+    if (a->graph_intr) intr_graph_after_launch(a->graph_intr);
     return 0;
 }
 

@@ -1412,6 +1412,13 @@ static bool aligned_for_vec(const GemmProblem& p, int al, int bl) {
 // problems (Disagreement's five models) go in chunks.
 struct PlaneArena { unsigned char* buf = nullptr; size_t bytes = 0; };
 static PlaneArena g_plane_arena;
+// A stream capture may take the adapter only where its caller asks for it (gemm_planes_capture: the joint module + agent graph of
+// exorl_agent_enable_graph_intr), and only into an arena that is large enough already: nothing may be allocated while capturing. The caller
+// sizes the arena first — a throw-away capture of the same launches with g_plane_probe set records the largest chunk, gemm_planes_reserve
+// grows the arena to it — so the captured step takes exactly the kernels the eager step takes. A graph keeps the arena's address: once one
+// has captured it, a later growth leaves the old buffer allocated (g_plane_captured) instead of freeing it under the graph.
+static bool g_plane_capture_ok = false, g_plane_captured = false;
+static size_t* g_plane_probe = nullptr;
 
 __global__ __launch_bounds__(256) void to_planes_kernel(const float* __restrict__ src, int64_t ld, int rows, int cols, unsigned short* __restrict__ hi,
                                                         unsigned short* __restrict__ lo, int rows_p, int cols_p) {
@@ -1513,10 +1520,28 @@ static bool adapter_direct(const GemmProblem& p) {
 }
 static int planes_adapter(int al, int bl, const GemmProblem* probs, int count, bool relu, bool accumulate, hipStream_t s) {
     struct Plan { int Mp, Np, Kp; size_t a_hi, a_lo, b_hi, b_lo, cp, bias; bool direct; };
-    {   // never inside a stream capture: the arena may be re-allocated later, a captured graph would keep the old addresses
+    auto take_all = [](const GemmProblem& p, size_t& need) {
+        auto take = [&](size_t bytes) { need += (bytes + 255) & ~(size_t)255; };
+        const size_t Mp = round_up(p.M, 128), Np = round_up(p.N, 128), Kp = round_up(p.K, 128);
+        take(Mp * Kp * 2); take(Mp * Kp * 2); take(Np * Kp * 2); take(Np * Kp * 2);
+        if (!adapter_direct(p)) { take(Mp * Np * 4); if (p.bias) take(Np * 4); }
+    };
+    {   // inside a stream capture only by request and without touching the allocation: the arena may be re-allocated later, a captured
+        // graph would keep the old addresses
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         EXORL_CHECK_HIP(hipStreamIsCapturing(s, &cs));
-        if (cs != hipStreamCaptureStatusNone) return -1;
+        if (cs != hipStreamCaptureStatusNone) {
+            if (!g_plane_capture_ok) return -1;
+            size_t most = 0;
+            for (int c0 = 0; c0 < count; c0 += 4) {
+                size_t need = 0;
+                for (int i = c0; i < count && i < c0 + 4; ++i) take_all(probs[i], need);
+                most = need > most ? need : most;
+            }
+            if (g_plane_probe && most > *g_plane_probe) *g_plane_probe = most;
+            if (most > g_plane_arena.bytes) return -1;
+            g_plane_captured = true;
+        }
     }
     for (int c0 = 0; c0 < count; c0 += 4) {
         const int nc = count - c0 < 4 ? count - c0 : 4;
@@ -1535,7 +1560,8 @@ static int planes_adapter(int al, int bl, const GemmProblem* probs, int count, b
         }
         if (need > g_plane_arena.bytes) {
             EXORL_CHECK_HIP(hipDeviceSynchronize());                                // nothing in flight may still read the old arena
-            if (g_plane_arena.buf) EXORL_CHECK_HIP(hipFree(g_plane_arena.buf));
+            if (g_plane_arena.buf && !g_plane_captured) EXORL_CHECK_HIP(hipFree(g_plane_arena.buf));
+            g_plane_captured = false;
             g_plane_arena.buf = nullptr; g_plane_arena.bytes = 0;
             const size_t want = need + need / 8;
             if (hipMalloc((void**)&g_plane_arena.buf, want) != hipSuccess) {
@@ -1586,6 +1612,24 @@ static int planes_adapter(int al, int bl, const GemmProblem* probs, int count, b
             EXORL_LAUNCH_CHECK();
         }
     }
+    return 0;
+}
+
+void gemm_planes_capture(bool allow, size_t* probe) { g_plane_capture_ok = allow; g_plane_probe = probe; }
+
+int gemm_planes_reserve(size_t bytes) {
+    if (bytes <= g_plane_arena.bytes) return 0;
+    EXORL_CHECK_HIP(hipDeviceSynchronize());
+    if (g_plane_arena.buf && !g_plane_captured) EXORL_CHECK_HIP(hipFree(g_plane_arena.buf));
+    g_plane_captured = false;
+    g_plane_arena.buf = nullptr; g_plane_arena.bytes = 0;
+    const size_t want = bytes + bytes / 8;
+    if (hipMalloc((void**)&g_plane_arena.buf, want) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("gemm_planes_reserve: could not grow the plane arena to %zu bytes", want);
+        return 3;
+    }
+    g_plane_arena.bytes = want;
     return 0;
 }
 

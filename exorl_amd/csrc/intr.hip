@@ -580,7 +580,8 @@ template <int PC_P>
 __global__ __launch_bounds__(256) void proto_candidates_kernel(const float* __restrict__ scores, const float* __restrict__ z,
                                                                const float* __restrict__ u_in, uint64_t seed, uint64_t counter,
                                                                float* __restrict__ queue, int64_t qrow0, int B, int P, int D,
-                                                               int* __restrict__ cand_out) {
+                                                               int* __restrict__ cand_out, const IntrStepState* __restrict__ st) {
+    if (st) { counter = st->draw_counter; qrow0 = st->qrow0; }      // captured step: this step's values live in device memory
     extern __shared__ float pr[];               // [B][PC_P + 1] unnormalised probabilities
     __shared__ float cmax[256 / PC_P][PC_P];
     __shared__ double csum[256 / PC_P][PC_P];
@@ -693,7 +694,9 @@ __global__ __launch_bounds__(256) void proto_cand_sum_kernel(const float* __rest
 }
 __global__ __launch_bounds__(256) void proto_cand_pick_kernel(const float* __restrict__ S, const float* __restrict__ z, const float* __restrict__ cmax,
                                                               const double* __restrict__ csum, int nch, const float* __restrict__ u_in, uint64_t seed,
-                                                              uint64_t counter, float* __restrict__ queue, int64_t qrow0, int B, int P, int D) {
+                                                              uint64_t counter, float* __restrict__ queue, int64_t qrow0, int B, int P, int D,
+                                                              const IntrStepState* __restrict__ st) {
+    if (st) { counter = st->draw_counter; qrow0 = st->qrow0; }
     __shared__ double bs[256 / PCM_G][PCM_G];
     __shared__ double run_s[PCM_G], thr_s[PCM_G];
     __shared__ float mx_s[PCM_G];
@@ -794,7 +797,8 @@ __device__ __forceinline__ float philox_normal_i(uint64_t seed, uint64_t counter
 // global batch, so that each rank draws the single-process epsilon of its rows
 __global__ __launch_bounds__(256) void vae_code_kernel(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ eps_in,
                                                        uint64_t seed, uint64_t counter, float* __restrict__ eps, float* __restrict__ code, int64_t n,
-                                                       int64_t elem0) {
+                                                       int64_t elem0, const IntrStepState* __restrict__ st) {
+    if (st) counter = st->draw_counter;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float e = eps_in ? eps_in[i] : philox_normal_i(seed, counter, (uint32_t)(elem0 + i));
         eps[i] = e;
@@ -1054,6 +1058,12 @@ struct exorl_intr {
     int64_t vae_off = 0;
     float *mu = nullptr, *lv = nullptr, *eps = nullptr, *code = nullptr, *dcode = nullptr, *dmu = nullptr, *dlv = nullptr, *hsz = nullptr, *hzs = nullptr;
     int64_t t = 0;                         // optimiser steps taken
+    // joint graph with the agent (exorl_agent_enable_graph_intr): t, cat_counter and queue_ptr above stay the truth; `dev` is their
+    // device copy, library-allocated on first capture, which the captured step advances itself (intr_step_begin_kernel)
+    IntrStepState* dev = nullptr;
+    bool dev_stale = true;                 // an eager step or a setter moved the host values since the last push
+    bool capturing = false;                // the stages enqueue the forms that read `dev`
+    const IntrStepState* st() const { return capturing ? dev : nullptr; }
     // data parallel (cfg.world_size > 1): this rank's batch rows are rows [rank * batch, (rank + 1) * batch) of the global batch
     int world = 1, rank = 0;
     float* gat = nullptr;                  // ICM-APT / APS / Proto: the gathered representation rows (world slots of batch x rep_dim, rank order)
@@ -1216,6 +1226,9 @@ static int launch_mean(const float* x, int n, float scale, float* out, int accum
 
 static int intr_adam(exorl_intr* it, hipStream_t s) {
     it->t += 1;
+    if (it->capturing)
+        return adam_step_dev(it->flat[EXORL_T_PARAM], it->flat[EXORL_T_GRAD], it->flat[EXORL_T_ADAM_M], it->flat[EXORL_T_ADAM_V], it->trainable,
+                             &it->dev->c[0], nullptr, nullptr, s);
     return adam_step(it->flat[EXORL_T_PARAM], it->flat[EXORL_T_GRAD], it->flat[EXORL_T_ADAM_M], it->flat[EXORL_T_ADAM_V], it->trainable,
                      it->cfg.lr, 0.9f, 0.999f, 1e-8f, it->t, nullptr, 0.f, s);
 }
@@ -1491,7 +1504,10 @@ static int diayn_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int
 }
 
 // ---- SMM --------------------------------------------------------------------------------------------
-static int adam_range(exorl_intr* it, int64_t off, int64_t n, float lr, hipStream_t s) {
+static int adam_range(exorl_intr* it, int64_t off, int64_t n, float lr, int opt, hipStream_t s) {      // opt: IntrStepState::lr's slot of `lr`
+    if (it->capturing)
+        return adam_step_dev(it->flat[EXORL_T_PARAM] + off, it->flat[EXORL_T_GRAD] + off, it->flat[EXORL_T_ADAM_M] + off, it->flat[EXORL_T_ADAM_V] + off, n,
+                             &it->dev->c[opt], nullptr, nullptr, s);
     return adam_step(it->flat[EXORL_T_PARAM] + off, it->flat[EXORL_T_GRAD] + off, it->flat[EXORL_T_ADAM_M] + off, it->flat[EXORL_T_ADAM_V] + off, n,
                      lr, 0.9f, 0.999f, 1e-8f, it->t, nullptr, 0.f, s);
 }
@@ -1508,8 +1524,8 @@ static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
     Mlp &zp = it->net[0], &enc = it->net[1], &dec = it->net[2];
     *next = -1;
     if (stage == 1) {
-        EXORL_TRY(adam_range(it, it->vae_off, it->trainable - it->vae_off, c.vae_lr, s));
-        EXORL_TRY(adam_range(it, 0, it->vae_off, c.sp_lr, s));
+        EXORL_TRY(adam_range(it, it->vae_off, it->trainable - it->vae_off, c.vae_lr, 2, s));
+        EXORL_TRY(adam_range(it, 0, it->vae_off, c.sp_lr, 1, s));
         if (it->world > 1 && !(c.flags & EXORL_INTR_ENCODED)) {      // mean_j and var_j of log p*(s_j) are over the global batch: stage 2
             hipLaunchKernelGGL(smm_logp_moments_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, B, c.goal_x, c.goal_y, it->mom + 3 * it->rank);
             EXORL_LAUNCH_CHECK();
@@ -1533,7 +1549,7 @@ static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
                          {enc.act[1], P + it->enc_lv.W, it->lv, P + it->enc_lv.b, B, C, V, V, V, C}};
     EXORL_TRY(gemm_grouped(prec, 0, 0, hd, 2, false, false, s));
     hipLaunchKernelGGL(vae_code_kernel, dim3(grid_for((int64_t)B * C)), dim3(256), 0, s, it->mu, it->lv, b.cat_uniform, 0x736d6dull, it->cat_counter++,
-                       it->eps, it->code, (int64_t)B * C, (int64_t)it->rank * B * C);
+                       it->eps, it->code, (int64_t)B * C, (int64_t)it->rank * B * C, it->st());
     EXORL_LAUNCH_CHECK();
     EXORL_TRY(mlp_forward(dec, P, it->code, C, B, prec, s));
     if (W >= 2048 && W % 4 == 0 && b.obs_ld % 4 == 0 && reinterpret_cast<uintptr_t>(b.obs) % 16 == 0 && reinterpret_cast<uintptr_t>(dec.act[2]) % 16 == 0 &&
@@ -1631,7 +1647,7 @@ static int proto_candidates(exorl_intr* it, const float* scores, const float* z,
     const uint64_t seed = 0x70726f746full, ctr = it->cat_counter++;
     if (proto_cand_lds_fits(rows)) {
 #define EXORL_PCAND(PP) hipLaunchKernelGGL(proto_candidates_kernel<PP>, dim3(cdiv(P, PP)), dim3(256), (size_t)rows * (PP + 1) * sizeof(float), s, scores, \
-                                            z, u, seed, ctr, it->queue, it->queue_ptr, rows, P, D, (int*)nullptr)
+                                            z, u, seed, ctr, it->queue, it->queue_ptr, rows, P, D, (int*)nullptr, it->st())
         if ((size_t)rows * 17 * sizeof(float) <= 64 * 1024) EXORL_PCAND(16);
         else if ((size_t)rows * 9 * sizeof(float) <= 64 * 1024) EXORL_PCAND(8);
         else EXORL_PCAND(4);
@@ -1642,7 +1658,7 @@ static int proto_candidates(exorl_intr* it, const float* scores, const float* z,
         hipLaunchKernelGGL(proto_cand_max_kernel, dim3(nch, cdiv(P, PCM_G)), dim3(256), 0, s, scores, rows, P, it->pcm_max);
         hipLaunchKernelGGL(proto_cand_sum_kernel, dim3(nch, cdiv(P, PCM_G)), dim3(256), 0, s, scores, rows, P, nch, it->pcm_max, it->pcm_sum);
         hipLaunchKernelGGL(proto_cand_pick_kernel, dim3(cdiv(P, PCM_G)), dim3(256), 0, s, scores, z, it->pcm_max, it->pcm_sum, nch, u, seed, ctr,
-                           it->queue, it->queue_ptr, rows, P, D);
+                           it->queue, it->queue_ptr, rows, P, D, it->st());
     }
     EXORL_LAUNCH_CHECK();
     it->queue_ptr = (it->queue_ptr + P) % it->cfg.queue_size;
@@ -1757,6 +1773,117 @@ static int proto_phase(exorl_intr* it, const exorl_intr_batch& b, int train, int
     return 0;
 }
 
+// ---- the module's side of the joint graph ---------------------------------------------------------------
+__global__ void intr_step_begin_kernel(IntrStepState* st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) intr_step_begin_device(st);
+}
+// stream-ordered upload of the host's counters (kernel argument: no host buffer whose lifetime would matter)
+__global__ void intr_state_set_kernel(IntrStepState* st, IntrStepState v) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *st = v;
+}
+__global__ __launch_bounds__(256) void copy_meta_columns_kernel(const float* __restrict__ obs, float* __restrict__ next_obs, int64_t ld, int rows,
+                                                                int O, int M) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)rows * M; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / M, j = O + i % M;
+        next_obs[r * ld + j] = obs[r * ld + j];
+    }
+}
+int copy_meta_columns(const float* obs, float* next_obs, int64_t ld, int rows, int O, int M, hipStream_t s) {
+    EXORL_REQUIRE(obs && next_obs && rows > 0 && O > 0 && M > 0 && ld >= O + M, "copy_meta_columns: bad arguments");
+    hipLaunchKernelGGL(copy_meta_columns_kernel, dim3(grid_for((int64_t)rows * M)), dim3(256), 0, s, obs, next_obs, ld, rows, O, M);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+// the device step state that the host's counters imply: beta^t by pow(), as adam_step computes it for an eager step
+static IntrStepState intr_host_state(const exorl_intr* it) {
+    const auto& c = it->cfg;
+    IntrStepState v{};
+    v.counter = v.draw_counter = it->cat_counter;
+    v.t = it->t;
+    v.queue_ptr = v.qrow0 = it->queue_ptr;
+    const bool proto = c.kind == EXORL_INTR_PROTO;
+    v.queue_size = proto ? c.queue_size : 0;
+    v.num_protos = proto ? c.num_protos : 0;
+    v.draws = (proto || c.kind == EXORL_INTR_SMM) ? 1 : 0;
+    v.b1 = dec7(0.9f); v.b2 = dec7(0.999f); v.eps = dec7(1e-8f);
+    v.b1t = pow(v.b1, (double)it->t); v.b2t = pow(v.b2, (double)it->t);
+    v.lr[0] = dec7(c.lr); v.lr[1] = dec7(c.sp_lr); v.lr[2] = dec7(c.vae_lr);
+    return v;
+}
+
+static int intr_push_state(exorl_intr* it, hipStream_t s) {
+    hipLaunchKernelGGL(intr_state_set_kernel, dim3(1), dim3(64), 0, s, it->dev, intr_host_state(it));
+    EXORL_LAUNCH_CHECK();
+    it->dev_stale = false;
+    return 0;
+}
+
+static int check_intr_batch(exorl_intr* it, const exorl_intr_batch* b);
+static int intr_run_stages(exorl_intr* it, const exorl_intr_batch& b, int train, hipStream_t s);
+
+// the step's launches in their captured form; the host's counters are put back afterwards (nothing ran)
+static int intr_capture_body(exorl_intr* it, const exorl_intr_batch* b, hipStream_t s) {
+    const int64_t t = it->t, qp = it->queue_ptr;
+    const uint64_t ctr = it->cat_counter;
+    it->capturing = true;
+    hipLaunchKernelGGL(intr_step_begin_kernel, dim3(1), dim3(64), 0, s, it->dev);
+    int rc = hipGetLastError() == hipSuccess ? 0 : 1;
+    if (rc != 0) set_error("intr_graph_capture: intr_step_begin_kernel failed to launch");
+    if (rc == 0) rc = intr_run_stages(it, *b, 1, s);
+    it->capturing = false;
+    it->t = t; it->queue_ptr = qp; it->cat_counter = ctr;
+    return rc;
+}
+
+int intr_graph_prepare(exorl_intr* it, const exorl_intr_batch* b, hipStream_t capture) {
+    EXORL_TRY(check_intr_batch(it, b));
+    EXORL_REQUIRE(it->world == 1, "agent_enable_graph_intr: a module with world_size=%d steps in phases with exchanges between them; "
+                  "only the one-rank step is captured", it->world);
+    EXORL_REQUIRE(!b->cat_uniform && !b->dobs_out, "agent_enable_graph_intr: a captured step draws from Philox (cat_uniform) and has no "
+                  "encoder behind it (dobs_out): both must be null");
+    if (!it->dev) EXORL_CHECK_HIP(hipMalloc((void**)&it->dev, sizeof(IntrStepState)));
+    if (it->cfg.precision == EXORL_PREC_BF16X3) {
+        // what the step's GEMMs ask of the plane arena: a throw-away capture of the same launches (nothing runs), then the arena is grown
+        // outside any capture, so that the graph proper takes the kernels the eager step takes
+        size_t need = 0;
+        EXORL_CHECK_HIP(hipStreamBeginCapture(capture, hipStreamCaptureModeThreadLocal));
+        gemm_planes_capture(true, &need);
+        const int rc = intr_capture_body(it, b, capture);
+        gemm_planes_capture(false, nullptr);
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(capture, &g);
+        if (g) (void)hipGraphDestroy(g);
+        if (rc != 0) return rc;
+        if (e != hipSuccess) { set_error("agent_enable_graph_intr: sizing capture -> %s", hipGetErrorString(e)); return 1; }
+        EXORL_TRY(gemm_planes_reserve(need));
+    }
+    EXORL_TRY(intr_push_state(it, capture));
+    return 0;
+}
+
+int intr_graph_capture(exorl_intr* it, const exorl_intr_batch* b, hipStream_t capture) {
+    EXORL_REQUIRE(it && it->dev, "intr_graph_capture: intr_graph_prepare first");
+    gemm_planes_capture(true, nullptr);
+    const int rc = intr_capture_body(it, b, capture);
+    gemm_planes_capture(false, nullptr);
+    return rc;
+}
+
+int intr_graph_before_launch(exorl_intr* it, hipStream_t s) {
+    if (it->dev_stale) EXORL_TRY(intr_push_state(it, s));
+    return 0;
+}
+
+void intr_graph_after_launch(exorl_intr* it) {      // what one exorl_intr_update(train = 1) does to the host's counters
+    const auto& c = it->cfg;
+    it->t += 1;
+    if (c.kind == EXORL_INTR_PROTO || c.kind == EXORL_INTR_SMM) it->cat_counter += 1;
+    if (c.kind == EXORL_INTR_PROTO) it->queue_ptr = (it->queue_ptr + c.num_protos) % c.queue_size;
+}
+
+void intr_graph_release(exorl_intr* it) { it->dev_stale = true; }
+
 }  // namespace exorl
 
 extern "C" {
@@ -1834,6 +1961,7 @@ int exorl_intr_create(const exorl_intr_cfg* cfg, void* workspace, size_t workspa
 int exorl_intr_destroy(exorl_intr_t* it) {
     if (!it) return 0;
     (void)hipDeviceSynchronize();
+    if (it->dev) (void)hipFree(it->dev);
     if (it->owns_ws) (void)hipFree(it->ws);
     delete it;
     return 0;
@@ -1869,7 +1997,10 @@ int exorl_intr_state(exorl_intr_t* it, void** rms_dev, void** bn_dev, int64_t* b
     return 0;
 }
 
-static int check_intr_batch(exorl_intr_t* it, const exorl_intr_batch* b) {
+}  // extern "C"
+
+namespace exorl {
+static int check_intr_batch(exorl_intr* it, const exorl_intr_batch* b) {
     EXORL_REQUIRE(it && b && b->obs && b->reward_out, "intr_update: null argument");
     const int k = it->cfg.kind;
     EXORL_REQUIRE(k == EXORL_INTR_RND || k == EXORL_INTR_SMM || b->next_obs, "intr_update: this module needs next_obs");
@@ -1880,28 +2011,37 @@ static int check_intr_batch(exorl_intr_t* it, const exorl_intr_batch* b) {
     return 0;
 }
 
-int exorl_intr_update(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train, void* stream) {
-    EXORL_TRY(check_intr_batch(it, b));
-    EXORL_REQUIRE(it->world == 1, "intr_update: world_size=%d: drive exorl_intr_update_phase and run the exchange each phase names "
-                  "(exorl_intr_exchange) across the ranks in between", it->world);
-    hipStream_t s = as_stream(stream);
+// the one-rank step: its stages back to back
+static int intr_run_stages(exorl_intr* it, const exorl_intr_batch& b, int train, hipStream_t s) {
     int next = -1;
     if (it->cfg.kind == EXORL_INTR_PROTO) {           // one rank: the gradient exchange after stage 1 is the identity
         for (int phase = 0;; ++phase) {
-            EXORL_TRY(proto_phase(it, *b, train, phase, &next, s));
+            EXORL_TRY(proto_phase(it, b, train, phase, &next, s));
             if (next < 0) return 0;
         }
     }
     for (int stage = train ? 0 : 1;; ++stage) {      // one rank: the gradient exchange is the identity and no later stage names one
-        EXORL_TRY(intr_stage(it, *b, train, stage, &next, s));
+        EXORL_TRY(intr_stage(it, b, train, stage, &next, s));
         if (next < 0) return 0;
     }
+}
+}  // namespace exorl
+
+extern "C" {
+
+int exorl_intr_update(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train, void* stream) {
+    EXORL_TRY(check_intr_batch(it, b));
+    EXORL_REQUIRE(it->world == 1, "intr_update: world_size=%d: drive exorl_intr_update_phase and run the exchange each phase names "
+                  "(exorl_intr_exchange) across the ranks in between", it->world);
+    it->dev_stale = true;                              // a joint graph re-reads the host's counters before its next launch
+    return intr_run_stages(it, *b, train, as_stream(stream));
 }
 
 int exorl_intr_update_phase(exorl_intr_t* it, const exorl_intr_batch* b, int32_t train, int32_t phase, int32_t* next_exchange, void* stream) {
     EXORL_REQUIRE(next_exchange, "intr_update_phase: null next_exchange");
     *next_exchange = -1;
     EXORL_TRY(check_intr_batch(it, b));
+    it->dev_stale = true;
     int next = -1;
     if (it->cfg.kind == EXORL_INTR_PROTO) {
         EXORL_TRY(proto_phase(it, *b, train, phase, &next, as_stream(stream)));
@@ -1941,6 +2081,7 @@ int exorl_intr_queue(exorl_intr_t* it, void** queue_dev, int64_t* rows, int64_t*
     if (set) {
         EXORL_REQUIRE(*ptr_inout >= 0 && *ptr_inout < it->cfg.queue_size && *ptr_inout % it->cfg.num_protos == 0, "intr_queue: bad write pointer");
         it->queue_ptr = *ptr_inout;
+        it->dev_stale = true;
     } else {
         *ptr_inout = it->queue_ptr;
     }
@@ -1956,14 +2097,14 @@ int exorl_intr_metrics(exorl_intr_t* it, float* host, void* stream) {
 
 int exorl_intr_opt_steps(exorl_intr_t* it, int64_t* steps, int32_t set) {
     EXORL_REQUIRE(it && steps, "intr_opt_steps: null argument");
-    if (set) { EXORL_REQUIRE(*steps >= 0, "intr_opt_steps: negative step count"); it->t = *steps; }
+    if (set) { EXORL_REQUIRE(*steps >= 0, "intr_opt_steps: negative step count"); it->t = *steps; it->dev_stale = true; }
     else *steps = it->t;
     return 0;
 }
 
 int exorl_intr_counter(exorl_intr_t* m, uint64_t* counter_inout, int32_t set) {
     EXORL_REQUIRE(m && counter_inout, "intr_counter: null argument");
-    if (set) m->cat_counter = *counter_inout;
+    if (set) { m->cat_counter = *counter_inout; m->dev_stale = true; }
     else *counter_inout = m->cat_counter;
     return 0;
 }

@@ -16,6 +16,11 @@ struct GemmProblem {
 };
 int gemm_grouped(int precision, int a_layout, int b_layout, const GemmProblem* probs, int count, bool relu,
                  bool accumulate, hipStream_t s);
+// bf16x3's plane adapter inside a stream capture (off by default: such launches take the generic kernel). allow: launches captured from now on
+// take the adapter where its scratch arena is large enough already; probe (optional) receives the largest arena size they ask for.
+// gemm_planes_reserve grows the arena to `bytes` (synchronises; never while capturing).
+void gemm_planes_capture(bool allow, size_t* probe);
+int gemm_planes_reserve(size_t bytes);
 
 struct Gemm16Problem {
     const unsigned short* A;
@@ -260,6 +265,23 @@ struct StepState {
                                  // that moves every step needs no re-capture of the hipGraph
 };
 int step_begin(StepState* st, int advance_replay, hipStream_t s);
+
+// The same for an intrinsic-reward module (intr.hip): what changes from one exorl_intr_update to the next. The host keeps the truth
+// (exorl_intr::t, cat_counter, queue_ptr) and pushes it here before a graph launch whenever an eager step or a setter moved it; a captured
+// module step starts with intr_step_begin, which advances everything for the step and leaves the values the step's kernels read.
+struct IntrStepState {
+    uint64_t counter;            // Philox draw counter after this step's draw
+    uint64_t draw_counter;       // ... and the one this step's draw uses (vae_code_kernel, Proto's candidate draw)
+    long long t;                 // Adam step count
+    long long queue_ptr;         // Proto: the queue's write pointer after this step
+    long long qrow0;             // ... and the first row this step's candidates are written to
+    int queue_size, num_protos;  // 0, 0 for the other kinds
+    int draws;                   // Philox draws per step (SMM and Proto: 1)
+    double b1t, b2t;             // running beta^t products, as StepState keeps them
+    double b1, b2, eps;
+    double lr[3];                // the optimisers of the kind: [0] cfg.lr; SMM: [1] sp_lr, [2] vae_lr
+    AdamConst c[3];
+};
 // act() for up to ACT_FAST_ROWS observation rows in one launch (loss.hip, act_fast_kernel): trunk + LayerNorm + tanh + Linear(H,H) + ReLU +
 // head + tanh + TruncatedNormal draw. x_host / noise_host (host pointers) travel as kernel arguments; `out` may be pinned host memory.
 constexpr int ACT_FAST_ROWS = 2;            // x 256 floats of embedded observation: the kernel-argument block stays under 4 KB
@@ -285,6 +307,7 @@ int trunk_one(const float* x, const float* meta, const float* W, const float* b,
 // statistics buffer that is all-reduced under data parallelism)
 int reduce_pairs(const float* parts, int chunks, float* out, hipStream_t s);
 int set_device_float(float* dst, float value, hipStream_t s);
+int set_device_u64(uint64_t* dst, uint64_t value, hipStream_t s);
 
 __host__ __device__ inline void fill_adam_const(AdamConst& c, double b1t, double b2t, double lr, double b1, double b2, double eps, double tau) {
     // double-precision scalar math, as torch's _single_tensor_adam does in Python floats; beta^t comes from a running
@@ -317,6 +340,18 @@ __device__ inline void step_begin_device(StepState* st, int advance_replay) {
     }
 }
 
+
+// One thread: advance the module's counters and pre-compute its optimisers' scalars for this step.
+__device__ inline void intr_step_begin_device(IntrStepState* st) {
+    st->t += 1;
+    st->b1t *= st->b1;
+    st->b2t *= st->b2;
+    for (int i = 0; i < 3; ++i) fill_adam_const(st->c[i], st->b1t, st->b2t, st->lr[i], st->b1, st->b2, st->eps, 0.0);
+    st->draw_counter = st->counter;
+    st->counter += (uint64_t)st->draws;
+    st->qrow0 = st->queue_ptr;
+    if (st->queue_size > 0) st->queue_ptr = (st->queue_ptr + st->num_protos) % st->queue_size;
+}
 
 int prepare_inputs(const float* obs, const float* action, const float* next_obs, float* xa, float* xc_cur,
                    float* xc_next, float* xc_pi, int B, int O, int A, int has_critic, StepState* st, int advance_replay,
@@ -396,6 +431,20 @@ int mlp_forward_many(const Mlp* nets, int n, const float* P, const float* x, int
 int mlp_backward_many(const Mlp* nets, int n, const float* P, float* G, const float* x, int64_t ldx, int rows, int prec, hipStream_t s, float* dx);
 int launch_concat(const float* a, int64_t lda, int ca, const float* b, int64_t ldb, int cb, float* dst, int rows, hipStream_t s);
 
+// ---- the module's side of the joint graph (intr.hip), used by exorl_agent_enable_graph_intr
+// intr_graph_prepare: outside a capture — checks the batch, allocates the device step state on first use, sizes the bf16x3 plane arena for
+// the step's GEMMs (a throw-away capture on `capture`) and pushes the host's counters. intr_graph_capture: the launches of
+// exorl_intr_update(train = 1) on `b`, reading the device step state; enqueues nothing that runs now and leaves the host's counters alone.
+// intr_graph_before_launch: re-pushes the counters on `s` if an eager step or a setter moved them; intr_graph_after_launch: advances the
+// host mirrors by one step.
+int intr_graph_prepare(exorl_intr* it, const exorl_intr_batch* b, hipStream_t capture);
+int intr_graph_capture(exorl_intr* it, const exorl_intr_batch* b, hipStream_t capture);
+int intr_graph_before_launch(exorl_intr* it, hipStream_t s);
+void intr_graph_after_launch(exorl_intr* it);
+void intr_graph_release(exorl_intr* it);
+// meta agents: next_obs[:, O:O+M] = obs[:, O:O+M] on [obs | meta] rows of `ld` floats (the replay gather fills the obs rows' meta columns)
+int copy_meta_columns(const float* obs, float* next_obs, int64_t ld, int rows, int O, int M, hipStream_t s);
+
 // ---- replay (replay.hip) internal entry points used by the agent's graph capture
 // Optional fan-out of the sampled rows into the agent's staged network inputs (what prepare_inputs would do in a second
 // kernel): xa = [next_obs ; obs], xc_cur = [obs | action], xc_next[:, :O] = next_obs, xc_pi[:, :O] = obs. fp32 state
@@ -409,6 +458,7 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
                        const uint64_t* dev_counter, const StageOut* stage = nullptr);
 int replay_obs_bytes(exorl_replay* r);
+void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim);
 // comm.cpp (exorl_comm is the C ABI's opaque struct, declared at global scope in exorl_hip.h)
 int comm_allreduce_sum(exorl_comm* c, float* buf, int64_t n, hipStream_t s);
 int comm_nranks(const exorl_comm* c);

@@ -146,6 +146,16 @@ int set_device_float(float* dst, float value, hipStream_t s) {
     return 0;
 }
 
+__global__ void set_device_u64_kernel(uint64_t* dst, uint64_t value) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
+}
+
+int set_device_u64(uint64_t* dst, uint64_t value, hipStream_t s) {
+    hipLaunchKernelGGL(set_device_u64_kernel, dim3(1), dim3(64), 0, s, dst, value);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
 int step_begin(StepState* st, int advance_replay, hipStream_t s) {
     hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(64), 0, s, st, advance_replay);
     EXORL_LAUNCH_CHECK();

@@ -455,6 +455,7 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
 
 uint64_t replay_philox_counter(exorl_replay* r) { return r->philox_counter; }
 int replay_obs_bytes(exorl_replay* r) { return r->cfg.obs_bytes; }
+void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }
 void replay_advance_philox(exorl_replay* r, uint64_t n) { r->philox_counter += n; }
 }  // namespace exorl
 

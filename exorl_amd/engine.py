@@ -208,8 +208,17 @@ class AgentEngine(_Phased):
         L.check(self.lib.exorl_agent_enable_graph(self.h, replay_engine.h, nstep, gamma, stddev, L.current_stream()))
         self.graph_captures = getattr(self, 'graph_captures', 0) + 1
 
+    def enable_graph_intr(self, replay_engine, nstep, gamma, stddev, intr=None, batch=None, meta_dim=0):
+        """enable_graph with a reward-free agent's module step in front of the agent's (exorl_agent_enable_graph_intr): `batch` is the
+        module's L.IntrBatch over this engine's batch slots; meta_dim > 0 for [obs | meta] rows. intr=None: the agent's step alone."""
+        L.check(self.lib.exorl_agent_enable_graph_intr(self.h, intr.h if intr is not None else None, C.byref(batch) if batch is not None else None,
+                                                       meta_dim, replay_engine.h, nstep, gamma, stddev, L.current_stream()))
+        self._graph_keep = (intr, batch)          # the graph holds the module's buffers
+        self.graph_captures = getattr(self, 'graph_captures', 0) + 1
+
     def disable_graph(self):
         L.check(self.lib.exorl_agent_disable_graph(self.h))
+        self._graph_keep = None
 
     def step_graph(self, stddev):
         L.check(self.lib.exorl_agent_step_graph(self.h, stddev, L.current_stream()))

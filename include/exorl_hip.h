@@ -38,7 +38,7 @@ extern "C" {
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
-                                        exorl_agent_cfg.precision) */
+                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -465,6 +465,23 @@ int exorl_intr_update_phase(exorl_intr_t* m, const exorl_intr_batch* batch, int3
 int exorl_intr_exchange(exorl_intr_t* m, int32_t id, void** ptr_dev, int64_t* count, int32_t* dtype /* EXORL_XCHG_F32 / _F64 */,
                         int32_t* op /* EXORL_XCHG_SUM / _GATHER */);
 int exorl_intr_metrics(exorl_intr_t* m, float* host_out /* EXORL_N_INTR_METRICS */, void* stream);
+/* exorl_agent_enable_graph with a reward-free agent's module in front of the agent's step: one hipGraph of
+ *   replay sample (PHILOX) into the agent's batch slots -> the meta columns into the next_obs rows (meta_dim > 0) ->
+ *   exorl_intr_update(intr, batch, train = 1) -> exorl_agent_update.
+ * batch: the module's view of the agent's batch slots (exorl_agent_batch_slots), fixed for the graph's life; reward_out (and extr_reward,
+ *   if set) is the agent's reward slot; cat_uniform and dobs_out are null (a captured step draws from Philox and has no encoder behind it).
+ * meta_dim > 0: the agent's rows are [obs | meta] (DIAYN's skill, APS's task, SMM's z): the replay's obs_bytes is (obs_dim - meta_dim) * 4
+ *   and its meta columns are meta_dim wide; the gather writes them behind the obs rows and one more kernel copies them behind the next_obs rows.
+ * intr == NULL (batch ignored): the agent's step alone, with the meta columns where meta_dim > 0 (fine-tuning); with meta_dim 0 that is
+ *   exorl_agent_enable_graph.
+ * What moves from one module step to the next — the Adam step count and the scalars of its optimisers, the Philox draw counter, Proto's
+ * queue pointer — lives in a device struct the library allocates on first capture; the captured step advances it itself.
+ * exorl_agent_step_graph advances the module's host counters with the agent's, so exorl_intr_opt_steps / _counter / _queue keep answering
+ * without a read-back; their setters and eager exorl_intr_update calls in between are pushed to the device before the next launch.
+ * One process only (world_size 1 on both handles). exorl_agent_step_graph / exorl_agent_disable_graph serve this graph too; the module
+ * must outlive it. */
+int exorl_agent_enable_graph_intr(exorl_agent_t* a, exorl_intr_t* intr, const exorl_intr_batch* batch, int32_t meta_dim, exorl_replay_t* r,
+                                  int32_t nstep, float gamma, float stddev, void* stream);
 /* optimiser step count of the module's Adam: set == 0 reads into *steps, else writes it (snapshot restore) */
 int exorl_intr_opt_steps(exorl_intr_t* m, int64_t* steps, int32_t set);
 /* Philox counter of the module's own random draws (Proto's categorical candidate picks, SMM's VAE epsilon): part of the pickled state */

@@ -1,9 +1,11 @@
 """update()/s of the DDPG-backbone reward-free agents on states at their shipped widths (configs/agent/*.yaml: hidden 1024,
 batch 1024, nstep 3; walker shapes O=24, A=6), HBM replay + Philox sampler, per precision mode.
 
-    python tools/micro/unsup_bench.py [agent ...] [--precision fp32,bf16x3] [--steps 300]
+    python tools/micro/unsup_bench.py [agent ...] [--precision fp32,bf16x3] [--steps 300] [--repeats 1] [--graph]
 
-One update() = module step + intrinsic reward + DDPG step (ddpg.py:294-328 and the per-agent update methods)."""
+One update() = module step + intrinsic reward + DDPG step (ddpg.py:294-328 and the per-agent update methods). --graph: the update is
+replayed as one captured hipGraph (agent.enable_graph; a refused capture is an error), otherwise it is launched eagerly. --repeats: that
+many timed windows per row, each printed, so that the run-to-run spread can be read off the output."""
 import argparse
 import sys
 import time
@@ -83,22 +85,30 @@ def main():
     ap.add_argument('agents', nargs='*', default=['ddpg', 'rnd', 'icm', 'icm_apt', 'disagreement', 'diayn', 'aps', 'smm', 'proto'])
     ap.add_argument('--precision', default='fp32,bf16x3')
     ap.add_argument('--steps', type=int, default=300)
+    ap.add_argument('--repeats', type=int, default=1)
+    ap.add_argument('--graph', action='store_true')
     args = ap.parse_args()
+    mode = 'graph' if args.graph else 'eager'
     for kind in args.agents:
         for prec in args.precision.split(','):
             torch.manual_seed(1)
             np.random.seed(1)
             ag = make(kind, prec)
             it = ArenaIterator(replay_for(ag), B, 3, 0.99, 'philox')
+            if args.graph and not ag.enable_graph(it):
+                raise SystemExit(f'{kind} {prec}: enable_graph refused the capture')
             for i in range(30):
                 ag.update(it, 2 * i)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(args.steps):
-                ag.update(it, 2 * (30 + i))
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            print(f'{kind:13s} {prec:7s} {args.steps / dt:9.1f} update()/s  {1e3 * dt / args.steps:7.3f} ms', flush=True)
+            step = 30
+            for _ in range(args.repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(args.steps):
+                    ag.update(it, 2 * (step + i))
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                step += args.steps
+                print(f'{kind:13s} {prec:7s} {mode:5s} {args.steps / dt:9.1f} update()/s  {1e3 * dt / args.steps:7.3f} ms', flush=True)
             del ag, it
 
 
