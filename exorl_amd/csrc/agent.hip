@@ -19,8 +19,6 @@
 
 namespace exorl {
 
-struct TensorDesc { int64_t off, rows, cols; };
-
 // A net = n_trunks x [Linear(in,H) LN Tanh] feeding n_heads x [Linear(H,H) ReLU Linear(H,out)].
 // twin critic: 2 trunks, 2 heads (head i on trunk i); shared critic: 1 trunk, 2 heads; actor: 1, 1.
 struct NetDesc {
@@ -91,41 +89,65 @@ struct Fork {
     hipStream_t side(hipStream_t s) const { return on ? aux : s; }
 };
 
-// *l: lo planes of the split-bf16 mode (same shapes as the bf16 buffers; x = hi + lo), null otherwise
-// bf16x6 precision on the plane kernel (planes3_ok): hi / mid / lo bf16 images of an fp32 buffer, same shape and pitch (x = hi + mid + lo); all null otherwise
-struct P3 {
-    unsigned short *hi = nullptr, *mid = nullptr, *lo = nullptr;
-    P3 at(int64_t off) const { return hi ? P3{hi + off, mid + off, lo + off} : P3{}; }
+// The bf16 images (Planes, kernels.h) sit beside the fp32 buffer they mirror; carve() fills the planes the agent's precision reads. h1's are written
+// by the trunk kernels (bf16 routes) or by to_planes3 behind the trunk (three-plane route), dz2's by the head kernels or by to_planes3 behind
+// them, W1's and W0's by the optimiser kernel (ShadowSpec) or, three planes, by refresh_w1_planes. One image serves every layout its buffer is read in.
+struct FwdBufs {
+    float *h1, *xhat, *rstd, *h2, *out;
+    Planes h1q, xhatq;
+    // rows row0.. of a one-trunk, one-head net's buffers (the obs half of the actor's stacked forward)
+    FwdBufs rows_from(int64_t row0, int64_t H, int64_t out_cols) const {
+        return FwdBufs{h1 + row0 * H, xhat + row0 * H, rstd + row0, h2 + row0 * H, out + row0 * out_cols, h1q.at(row0 * H), xhatq.at(row0 * H)};
+    }
 };
-// *p: three-plane images (bf16x6): of h1, written by the forward pass behind the trunk; of dz2, by the backward pass behind the head; of W1
-// ([n_heads][H][H]), behind every optimiser step and exorl_agent_params_changed. One image serves every layout its buffer is read in.
-struct FwdBufs { float *h1, *xhat, *rstd, *h2, *out; unsigned short *h1b, *xhatb, *h1l, *xhatl; P3 h1p; };
-struct BwdBufs { float *dz2, *dh1; unsigned short *dz2b, *dz2l; P3 dz2p; };
-struct NetShadow { float* w0t; unsigned short* w1b; unsigned short* w0b; unsigned short *w1l, *w0l; P3 w1p; };   // W0 transposed per trunk; W1 as bf16 per head; W0 as K-padded bf16
-// bf16 activation pipeline: plain bf16 mode, or split-bf16 with hi/lo planes (H, batch multiples of 64: see planes_ok)
-static bool fast16(int prec, const NetShadow& sh) { return prec == EXORL_PREC_BF16 || (prec == EXORL_PREC_BF16X3 && sh.w1l); }
-static Gemm16Problem g16(const unsigned short* A, const unsigned short* Al, const unsigned short* B, const unsigned short* Bl, int64_t aoff,
-                         int64_t boff, float* C, const float* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc) {
-    Gemm16Problem p{A + aoff, B + boff, C, bias, M, N, K, lda, ldb, ldc};
-    if (Al && Bl) { p.A_lo = Al + aoff; p.B_lo = Bl + boff; }
+struct BwdBufs { float *dz2, *dh1; Planes dz2q; };
+struct NetShadow { float* w0t; Planes w1q, w0q; };   // W0 transposed per trunk; W1 per head ([n_heads][H][H]); W0 K-padded per trunk (hi, lo only)
+
+// Which operands the H x H products of a net read.
+enum class Route {
+    F32,       // fp32 buffers through gemm_grouped(prec): fp32 mode, and bf16x3 / bf16x6 at shapes that do not tile (the split happens inside the GEMM)
+    Planes,    // bf16 activation pipeline through gemm16_grouped: hi planes (plain bf16) or hi + lo (bf16x3; H, batch multiples of 64: see planes_ok)
+    Planes3,   // fp32 activation pipeline with hi + mid + lo images of the products' operands (bf16x6; carve: planes3_ok), gemm16_grouped
+};
+// bf16x3 takes the plane pipeline only when the shadow has lo planes (act() hides them: its rows do not tile by 64). bf16x6 takes the three-plane
+// kernel when activation and weight images exist and the rows tile by 128 (act()'s 64-row chunks do not).
+static Route route_of(int prec, const Planes& act, const Planes& w1, int rows) {
+    if (prec == EXORL_PREC_BF16 || (prec == EXORL_PREC_BF16X3 && w1.lo)) return Route::Planes;
+    if (prec == EXORL_PREC_BF16X6 && act && w1 && rows % 128 == 0) return Route::Planes3;
+    return Route::F32;
+}
+// One GEMM operand in both forms, each at its own offset (W1 is strided by head_stride in the parameters and by H * H in its images).
+struct Operand {
+    const float* f; Planes q;
+    Operand() : f(nullptr) {}
+    Operand(const float* f32, int64_t foff, const Planes& planes, int64_t qoff) : f(f32 ? f32 + foff : nullptr), q(planes.at(qoff)) {}
+};
+struct Product { Operand A, B; float* C; const float* bias; int M, N, K; };      // every pitch is H
+// A problem carries mid planes only when both operands have them, and likewise lo planes. (act()'s buffers have a hi plane at most: a plain-bf16
+// act() multiplies hi planes, and a bf16x3 act() never comes here — route_of sends it to Route::F32.)
+static Gemm16Problem g16(const Planes& A, const Planes& B, float* C, const float* bias, int M, int N, int K, int64_t ld) {
+    Gemm16Problem p{A.hi, B.hi, C, bias, M, N, K, ld, ld, ld};
+    if (A.mid && B.mid) { p.A_mid = A.mid; p.B_mid = B.mid; }
+    if (A.lo && B.lo) { p.A_lo = A.lo; p.B_lo = B.lo; }
     return p;
 }
-static Gemm16Problem g16x6(const P3& A, const P3& B, int64_t aoff, int64_t boff, float* C, const float* bias, int M, int N, int K, int64_t lda,
-                           int64_t ldb, int64_t ldc) {
-    Gemm16Problem p{A.hi + aoff, B.hi + boff, C, bias, M, N, K, lda, ldb, ldc};
-    p.A_mid = A.mid + aoff; p.B_mid = B.mid + boff; p.A_lo = A.lo + aoff; p.B_lo = B.lo + boff;
-    return p;
-}
-// the H x H products of a bf16x6 agent take the three-plane kernel when the buffers carry plane images (carve: planes3_ok) and the rows tile by
-// 128 (act()'s 64-row chunks do not); otherwise gemm_kernel<EXORL_PREC_BF16X6> splits the fp32 operands while staging
-static bool planes3_route(int prec, const P3& act, const P3& w1, int rows) {
-    return prec == EXORL_PREC_BF16X6 && act.hi && w1.hi && rows % 128 == 0;
+static Gemm16Problem g16(const Product& p, int64_t ld) { return g16(p.A.q, p.B.q, p.C, p.bias, p.M, p.N, p.K, ld); }
+// `count` (<= 4) products of one shape class in one grouped launch on the route's GEMM
+static int products(Route rt, int prec, int a_layout, int b_layout, const Product* p, int count, int64_t ld, bool relu, bool accumulate, hipStream_t s) {
+    if (rt == Route::F32) {
+        GemmProblem g[4];
+        for (int i = 0; i < count; ++i) g[i] = GemmProblem{p[i].A.f, p[i].B.f, p[i].C, p[i].bias, p[i].M, p[i].N, p[i].K, ld, ld, ld};
+        return gemm_grouped(prec, a_layout, b_layout, g, count, relu, accumulate, s);
+    }
+    Gemm16Problem q[4];
+    for (int i = 0; i < count; ++i) q[i] = g16(p[i], ld);
+    return gemm16_grouped(a_layout, b_layout, q, count, relu, accumulate, s);
 }
 // W1 of every head -> its three plane images, one launch. Once per optimiser step (and per exorl_agent_params_changed) rather than once per use:
 // a TD3+BC step reads the critic's W1 in five launches and the actor's in two.
 static int refresh_w1_planes(const NetDesc& d, const float* P, const NetShadow& sh, hipStream_t s) {
-    if (!sh.w1p.hi) return 0;
-    return to_planes3(P + d.W1, d.H, d.H, d.H, sh.w1p.hi, sh.w1p.mid, sh.w1p.lo, d.H, d.H, d.n_heads, d.head_stride, (int64_t)d.H * d.H, s);
+    if (!sh.w1q.mid) return 0;
+    return to_planes3(P + d.W1, d.H, d.H, d.H, sh.w1q.hi, sh.w1q.mid, sh.w1q.lo, d.H, d.H, d.n_heads, d.head_stride, (int64_t)d.H * d.H, s);
 }
 struct Partials { float *Ph, *Pt, *Pw; };                  // per-chunk partial gradients (fused.hip)
 
@@ -134,12 +156,13 @@ static ShadowSpec shadow_spec(const NetDesc& d, const NetShadow& sh, const NetSh
     s.n_trunks = d.n_trunks; s.n_heads = d.n_heads; s.in_dim = d.in_dim; s.H = d.H;
     for (int t = 0; t < d.n_trunks; ++t) s.w0_off[t] = d.W0 + t * d.trunk_stride;
     for (int i = 0; i < d.n_heads; ++i) s.w1_off[i] = d.W1 + i * d.head_stride;
-    s.w0t = sh.w0t; s.w1b = sh.w1b; s.w0b = sh.w0b; s.w1l = sh.w1l; s.w0l = sh.w0l;
-    s.t_w0t = target ? target->w0t : nullptr;
-    s.t_w1b = target ? target->w1b : nullptr;
-    s.t_w0b = target ? target->w0b : nullptr;
-    s.t_w1l = target ? target->w1l : nullptr;
-    s.t_w0l = target ? target->w0l : nullptr;
+    // the optimiser kernel keeps the one- and two-plane images current; three-plane images are refresh_w1_planes' and stay out of its sight
+    const NetShadow none{};
+    const NetShadow& t = target ? *target : none;
+    const bool own = !sh.w1q.mid;
+    s.w0t = sh.w0t; s.t_w0t = t.w0t;
+    if (own) { s.w1b = sh.w1q.hi; s.w1l = sh.w1q.lo; s.t_w1b = t.w1q.hi; s.t_w1l = t.w1q.lo; }
+    s.w0b = sh.w0q.hi; s.w0l = sh.w0q.lo; s.t_w0b = t.w0q.hi; s.t_w0l = t.w0q.lo;
     return s;
 }
 
@@ -148,35 +171,25 @@ static int net_forward(const NetDesc& d, const float* P, const NetShadow& sh, co
                        bool no_head = false) {
     const int H = d.H;
     const int64_t act = (int64_t)rows * H;
-    const bool bf = fast16(prec, sh);
-    // fast mode keeps the trunk activations as bf16 only (MFMA operand + LN backward input): 4 B/elem written instead of 10
-    if (bf && sh.w0b && trunk_fwd16_supported(H))
-        EXORL_TRY(trunk_fwd16(x, ldx, sh.w0b, P + d.b0, P + d.g, P + d.beta, save ? f.rstd : nullptr, f.h1b, save ? f.xhatb : nullptr, rows,
-                              d.in_dim, H, d.n_trunks, act, d.trunk_stride, s, sh.w0l, f.h1l, f.xhatl));
+    const Route rt = route_of(prec, f.h1q, sh.w1q, rows);
+    const bool bf = rt == Route::Planes;
+    // fast mode keeps the trunk activations as bf16 only (MFMA operand + LN backward input): 4 B/elem written instead of 10. The MFMA trunk needs
+    // W0's image and H % 128 == 0; plain bf16 at other widths (H = 192) takes the fp32 trunk kernel with bf16 outputs.
+    if (bf && sh.w0q && trunk_fwd16_supported(H))
+        EXORL_TRY(trunk_fwd16(x, ldx, sh.w0q, P + d.b0, P + d.g, P + d.beta, save ? f.rstd : nullptr, f.h1q, save ? f.xhatq : Planes{}, rows,
+                              d.in_dim, H, d.n_trunks, act, d.trunk_stride, s));
     else
         EXORL_TRY(trunk_fwd(x, ldx, sh.w0t, P + d.b0, P + d.g, P + d.beta, bf ? nullptr : f.h1, (save && !bf) ? f.xhat : nullptr,
-                            save ? f.rstd : nullptr, bf ? f.h1b : nullptr, (bf && save) ? f.xhatb : nullptr, rows, d.in_dim, H,
+                            save ? f.rstd : nullptr, bf ? f.h1q.hi : nullptr, (bf && save) ? f.xhatq.hi : nullptr, rows, d.in_dim, H,
                             d.n_trunks, act, d.trunk_stride, (int64_t)d.in_dim * H, s));
-    if (bf) {
-        Gemm16Problem q[2];
-        for (int i = 0; i < d.n_heads; ++i)
-            q[i] = g16(f.h1b, f.h1l, sh.w1b, sh.w1l, (d.n_trunks == d.n_heads ? i : 0) * act, (int64_t)i * H * H, f.h2 + i * act,
-                       P + d.b1 + i * d.head_stride, rows, H, H, H, H, H);
-        EXORL_TRY(gemm16_grouped(0, 0, q, d.n_heads, true, false, s));
-    } else if (planes3_route(prec, f.h1p, sh.w1p, rows)) {
-        EXORL_TRY(to_planes3(f.h1, H, d.n_trunks * rows, H, f.h1p.hi, f.h1p.mid, f.h1p.lo, d.n_trunks * rows, H, 1, 0, 0, s));
-        Gemm16Problem q[2];
-        for (int i = 0; i < d.n_heads; ++i)
-            q[i] = g16x6(f.h1p, sh.w1p, (d.n_trunks == d.n_heads ? i : 0) * act, (int64_t)i * H * H, f.h2 + i * act, P + d.b1 + i * d.head_stride,
-                         rows, H, H, H, H, H);
-        EXORL_TRY(gemm16_grouped(0, 0, q, d.n_heads, true, false, s));
-    } else {
-        GemmProblem p[2];
-        for (int i = 0; i < d.n_heads; ++i)
-            p[i] = GemmProblem{f.h1 + (d.n_trunks == d.n_heads ? i : 0) * act, P + d.W1 + i * d.head_stride, f.h2 + i * act,
-                               P + d.b1 + i * d.head_stride, rows, H, H, H, H, H};
-        EXORL_TRY(gemm_grouped(prec, 0, 0, p, d.n_heads, true, false, s));
+    if (rt == Route::Planes3) EXORL_TRY(to_planes3(f.h1, H, d.n_trunks * rows, H, f.h1q.hi, f.h1q.mid, f.h1q.lo, d.n_trunks * rows, H, 1, 0, 0, s));
+    Product p[2];
+    for (int i = 0; i < d.n_heads; ++i) {        // h2_i = relu(h1 W1_i^T + b1_i), head i on trunk i (paired) or on the one trunk (shared)
+        const int64_t t = (d.n_trunks == d.n_heads ? i : 0) * act;
+        p[i] = Product{Operand(f.h1, t, f.h1q, t), Operand(P + d.W1, i * d.head_stride, sh.w1q, (int64_t)i * H * H), f.h2 + i * act,
+                       P + d.b1 + i * d.head_stride, rows, H, H};
     }
+    EXORL_TRY(products(rt, prec, 0, 0, p, d.n_heads, H, true, false, s));
     if (no_head) return 0;                       // the caller runs the fused head forward+backward (qhead)
     if (H % 4 == 0)
         EXORL_TRY(head_fwd4(f.h2, P + d.W2, P + d.b2, f.out, rows, H, d.out_dim, tanh_out ? 1 : 0, d.n_heads, act, d.head_stride,
@@ -189,8 +202,9 @@ static int net_forward(const NetDesc& d, const float* P, const NetShadow& sh, co
 
 // The critic on (obs, a_data) and its Polyak target on (next_obs, next_action) in shared launches (bf16 mode): the two forward
 // chains are independent, same shapes, different weights -> 3 launches instead of 6, each filling the chip twice as deep.
-static bool forward2_supported(const NetDesc& d, int prec, const NetShadow& sa, const NetShadow& sb) {
-    return fast16(prec, sa) && fast16(prec, sb) && sa.w0b && sb.w0b && trunk_fwd16_supported(d.H) && d.out_dim == 1 && d.n_heads == 2 && d.H % 4 == 0;
+static bool forward2_supported(const NetDesc& d, int prec, const NetShadow& sa, const FwdBufs& fa, const NetShadow& sb, const FwdBufs& fb, int rows) {
+    const bool planes = route_of(prec, fa.h1q, sa.w1q, rows) == Route::Planes && route_of(prec, fb.h1q, sb.w1q, rows) == Route::Planes;
+    return planes && sa.w0q && sb.w0q && trunk_fwd16_supported(d.H) && d.out_dim == 1 && d.n_heads == 2 && d.H % 4 == 0;
 }
 // fold_a (with no_head): net A's scalar heads are folded into the GEMM epilogue (Gemm16Problem::head_part) when the launch takes the 128 x TN
 // kernels — A's h2 buffer then holds, per head, rows x *slots_a partial dots instead of hidden activations (qhead sums them)
@@ -207,19 +221,19 @@ static int net_forward2(const NetDesc& d, const float* Pa, const NetShadow& sa, 
     TrunkBatch tb{};
     int nt = 0;
     for (int k = 0; k < 2; ++k)
-        for (int t = 0; t < d.n_trunks; ++t)
-            tb.it[nt++] = TrunkItem{x[k], sh[k]->w0b + t * wst, P[k] + d.b0 + t * d.trunk_stride, P[k] + d.g + t * d.trunk_stride,
-                                    P[k] + d.beta + t * d.trunk_stride, save[k] ? f[k]->rstd + (int64_t)t * rows : nullptr,
-                                    f[k]->h1b + t * act, save[k] ? f[k]->xhatb + t * act : nullptr, sh[k]->w0l ? sh[k]->w0l + t * wst : nullptr,
-                                    f[k]->h1l ? f[k]->h1l + t * act : nullptr, (save[k] && f[k]->xhatl) ? f[k]->xhatl + t * act : nullptr};
+        for (int t = 0; t < d.n_trunks; ++t) {
+            const Planes w = sh[k]->w0q.at(t * wst), h = f[k]->h1q.at(t * act), xh = save[k] ? f[k]->xhatq.at(t * act) : Planes{};
+            tb.it[nt++] = TrunkItem{x[k], w.hi, P[k] + d.b0 + t * d.trunk_stride, P[k] + d.g + t * d.trunk_stride, P[k] + d.beta + t * d.trunk_stride,
+                                    save[k] ? f[k]->rstd + (int64_t)t * rows : nullptr, h.hi, xh.hi, w.lo, h.lo, xh.lo};
+        }
     EXORL_TRY(trunk_fwd16_batch(tb, nt, ldx, rows, d.in_dim, H, s));
     Gemm16Problem q[4];
     HeadBatch hb{};
     int nq = 0;
     for (int k = 0; k < 2; ++k)
         for (int i = 0; i < d.n_heads; ++i) {
-            q[nq] = g16(f[k]->h1b, f[k]->h1l, sh[k]->w1b, sh[k]->w1l, (d.n_trunks == d.n_heads ? i : 0) * act, (int64_t)i * H * H, f[k]->h2 + i * act,
-                        P[k] + d.b1 + i * d.head_stride, rows, H, H, H, H, H);
+            q[nq] = g16(f[k]->h1q.at((d.n_trunks == d.n_heads ? i : 0) * act), sh[k]->w1q.at((int64_t)i * H * H), f[k]->h2 + i * act,
+                        P[k] + d.b1 + i * d.head_stride, rows, H, H, H);
             hb.it[nq] = HeadItem{f[k]->h2 + i * act, P[k] + d.W2 + i * d.head_stride, P[k] + d.b2 + i * d.head_stride, f[k]->out + (int64_t)i * rows};
             ++nq;
         }
@@ -247,106 +261,68 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
     const int H = d.H;
     const int64_t act = (int64_t)rows * H;
     const bool paired = d.n_trunks == d.n_heads;
-    const bool bf = fast16(prec, sh);
+    Route rt = route_of(prec, f.h1q, sh.w1q, rows);
+    if (rt == Route::Planes3 && !b.dz2q) rt = Route::F32;      // the three-plane kernel wants dz2's images too
+    const bool bf = rt == Route::Planes;
+    // the bf16 route's row kernels read and write the images in place of the fp32 buffers; on the other routes they see no image
+    const Planes none{};
+    const Planes &dz2q = bf ? b.dz2q : none, &h1q = bf ? f.h1q : none, &xhatq = bf ? f.xhatq : none;
     if (have_dz2) {
         // dz2 and the head partials were produced by qhead
     } else if (d.out_dim > 16) {
         EXORL_REQUIRE(d.n_heads == 1, "net_backward: wide heads are single-net only");
-        EXORL_TRY(head_bwd_wide(dout, P + d.W2, f.h2, bf ? nullptr : b.dz2, bf ? b.dz2b : nullptr, G ? pt.Ph : nullptr, rows, H, d.out_dim,
-                                act, d.head_stride, G ? 1 : 0, s, bf ? b.dz2l : nullptr));
+        EXORL_TRY(head_bwd_wide(dout, P + d.W2, f.h2, bf ? nullptr : b.dz2, dz2q, G ? pt.Ph : nullptr, rows, H, d.out_dim, act, d.head_stride,
+                                G ? 1 : 0, s));
     } else {
-        EXORL_TRY(head_bwd(dout, P + d.W2, f.h2, bf ? nullptr : b.dz2, bf ? b.dz2b : nullptr, G ? pt.Ph : nullptr, rows, H, d.out_dim,
-                           d.n_heads, act, d.head_stride, G ? 1 : 0, s, bf ? b.dz2l : nullptr));
+        EXORL_TRY(head_bwd(dout, P + d.W2, f.h2, bf ? nullptr : b.dz2, dz2q, G ? pt.Ph : nullptr, rows, H, d.out_dim, d.n_heads, act,
+                           d.head_stride, G ? 1 : 0, s));
     }
-    if (bf) {
+    // dz2 converted once for the wgrad and the dgrad; h1's images are the forward pass's
+    if (rt == Route::Planes3) EXORL_TRY(to_planes3(b.dz2, H, d.n_heads * rows, H, b.dz2q.hi, b.dz2q.mid, b.dz2q.lo, d.n_heads * rows, H, 1, 0, 0, s));
+    auto trunk_of = [&](int i) { return (paired ? i : 0) * act; };
+    auto wgrad = [&](int i, int r0, int kr) {      // dW1_i[n][k] = sum_{m in r0 .. r0 + kr} dz2_i[m][n] h1[m][k]
+        const int64_t o = (int64_t)r0 * H;
+        return Product{Operand(b.dz2, i * act + o, b.dz2q, i * act + o), Operand(f.h1, trunk_of(i) + o, f.h1q, trunk_of(i) + o),
+                       G + d.W1 + i * d.head_stride, nullptr, H, H, kr};
+    };
+    auto dgrad = [&](int i) {                      // dh1[m][k] = sum_n dz2_i[m][n] W1_i[n][k]
+        return Product{Operand(b.dz2, i * act, b.dz2q, i * act), Operand(P + d.W1, i * d.head_stride, sh.w1q, (int64_t)i * H * H),
+                       b.dh1 + trunk_of(i), nullptr, rows, H, H};
+    };
+    Product p[2];
+    int dgrads_done = 0;
+    if (bf && G && !fk.on) {
+        // bf16 route only, no side stream: wgrad + dgrad in one launch (independent readers of dz2). With a shared trunk the heads' dgrads add into
+        // one dh1, so only the first joins the launch; the others follow below as accumulating launches.
         Gemm16Problem q[4];
-        int at[4];
-        int nq = 0;
-        if (G && !fk.on) {                           // wgrad + dgrad in one launch (independent readers of dz2)
-            for (int i = 0; i < d.n_heads; ++i) {    // dW1_i[n][k] = sum_m dz2_i[m][n] h1[m][k]
-                at[nq] = 1;
-                q[nq++] = g16(b.dz2b, b.dz2l, f.h1b, f.h1l, i * act, (paired ? i : 0) * act, G + d.W1 + i * d.head_stride, nullptr,
-                              H, H, rows, H, H, H);
-            }
-            const int nd = paired ? d.n_heads : 1;   // shared trunk: the heads' dgrads add into one dh1 -> only the first joins
-            for (int i = 0; i < nd; ++i) {           // dh1[m][k] = sum_n dz2_i[m][n] W1_i[n][k]
-                at[nq] = 0;
-                q[nq++] = g16(b.dz2b, b.dz2l, sh.w1b, sh.w1l, i * act, (int64_t)i * H * H, b.dh1 + (paired ? i : 0) * act, nullptr,
-                              rows, H, H, H, H, H);
-            }
-            EXORL_TRY(gemm16_grouped_mixed(at, q, nq, s));
-            for (int i = nd; i < d.n_heads; ++i) {
-                Gemm16Problem r = g16(b.dz2b, b.dz2l, sh.w1b, sh.w1l, i * act, (int64_t)i * H * H, b.dh1, nullptr, rows, H, H, H, H, H);
-                EXORL_TRY(gemm16_grouped(0, 1, &r, 1, false, true, s));
-            }
-        } else {
-            if (G) {
-                for (int i = 0; i < d.n_heads; ++i)
-                    q[i] = g16(b.dz2b, b.dz2l, f.h1b, f.h1l, i * act, (paired ? i : 0) * act, G + d.W1 + i * d.head_stride, nullptr,
-                               H, H, rows, H, H, H);
-                EXORL_TRY(fk.fork(s));                 // wgrad only feeds the optimiser: off the dgrad -> LN-backward chain
-                EXORL_TRY(gemm16_grouped(1, 1, q, d.n_heads, false, false, fk.side(s)));
-            }
-            for (int i = 0; i < d.n_heads; ++i)
-                q[i] = g16(b.dz2b, b.dz2l, sh.w1b, sh.w1l, i * act, (int64_t)i * H * H, b.dh1 + (paired ? i : 0) * act, nullptr,
-                           rows, H, H, H, H, H);
-            if (paired) {
-                EXORL_TRY(gemm16_grouped(0, 1, q, d.n_heads, false, false, s));
-            } else {
-                for (int i = 0; i < d.n_heads; ++i) EXORL_TRY(gemm16_grouped(0, 1, q + i, 1, false, i > 0, s));
-            }
+        int at[4], nq = 0;
+        for (int i = 0; i < d.n_heads; ++i) { at[nq] = 1; q[nq++] = g16(wgrad(i, 0, rows), H); }
+        dgrads_done = paired ? d.n_heads : 1;
+        for (int i = 0; i < dgrads_done; ++i) { at[nq] = 0; q[nq++] = g16(dgrad(i), H); }
+        EXORL_TRY(gemm16_grouped_mixed(at, q, nq, s));
+    } else if (G) {
+        EXORL_TRY(fk.fork(s));                     // wgrad only feeds the optimiser: off the dgrad -> LN-backward chain
+        // F32 and Planes3 routes: the wgrad sums over the rows in one float32 accumulator per element; from 8192 rows on (the row kernels' own
+        // threshold) it runs as slabs of 1024 rows accumulated into G, so that no running sum is longer than 1024 terms (one pass over 8200 rows
+        // left dW1 1.6e-6 of its largest element off the float64 value, 13 times the float32 reference's own error). The bf16 route (bf16-grade
+        // operands) keeps one pass.
+        const int slab = (!bf && rows >= 8192) ? 1024 : rows;
+        for (int r0 = 0; r0 < rows; r0 += slab) {
+            for (int i = 0; i < d.n_heads; ++i) p[i] = wgrad(i, r0, rows - r0 < slab ? rows - r0 : slab);
+            EXORL_TRY(products(rt, prec, 1, 1, p, d.n_heads, H, false, r0 > 0, fk.side(s)));
         }
-    } else if (planes3_route(prec, f.h1p, sh.w1p, rows) && b.dz2p.hi) {
-        // the fp32 pipeline's launches (below) on three planes: dz2 converted once for the wgrad and the dgrad, h1's images are the forward pass's
-        EXORL_TRY(to_planes3(b.dz2, H, d.n_heads * rows, H, b.dz2p.hi, b.dz2p.mid, b.dz2p.lo, d.n_heads * rows, H, 1, 0, 0, s));
-        Gemm16Problem q[2];
-        if (G) {
-            EXORL_TRY(fk.fork(s));
-            const int slab = rows >= 8192 ? 1024 : rows;        // as below: no running sum longer than 1024 terms
-            for (int r0 = 0; r0 < rows; r0 += slab) {
-                const int kr = rows - r0 < slab ? rows - r0 : slab;
-                for (int i = 0; i < d.n_heads; ++i)
-                    q[i] = g16x6(b.dz2p, f.h1p, i * act + (int64_t)r0 * H, (paired ? i : 0) * act + (int64_t)r0 * H, G + d.W1 + i * d.head_stride, nullptr,
-                                 H, H, kr, H, H, H);
-                EXORL_TRY(gemm16_grouped(1, 1, q, d.n_heads, false, r0 > 0, fk.side(s)));
-            }
-        }
-        for (int i = 0; i < d.n_heads; ++i)
-            q[i] = g16x6(b.dz2p, sh.w1p, i * act, (int64_t)i * H * H, b.dh1 + (paired ? i : 0) * act, nullptr, rows, H, H, H, H, H);
-        if (paired) {
-            EXORL_TRY(gemm16_grouped(0, 1, q, d.n_heads, false, false, s));
-        } else {
-            for (int i = 0; i < d.n_heads; ++i) EXORL_TRY(gemm16_grouped(0, 1, q + i, 1, false, i > 0, s));
-        }
-    } else {
-        GemmProblem p[2];
-        if (G) {
-            EXORL_TRY(fk.fork(s));
-            // the wgrad sums over the rows in one float32 accumulator per element: from 8192 rows on (the row kernels' own threshold) it runs as
-            // slabs of 1024 rows accumulated into G, so that no running sum is longer than 1024 terms (one pass over 8200 rows left dW1
-            // 1.6e-6 of its largest element off the float64 value, 13 times the float32 reference's own error)
-            const int slab = rows >= 8192 ? 1024 : rows;
-            for (int r0 = 0; r0 < rows; r0 += slab) {
-                const int kr = rows - r0 < slab ? rows - r0 : slab;
-                for (int i = 0; i < d.n_heads; ++i)
-                    p[i] = GemmProblem{b.dz2 + i * act + (int64_t)r0 * H, f.h1 + (paired ? i : 0) * act + (int64_t)r0 * H,
-                                       G + d.W1 + i * d.head_stride, nullptr, H, H, kr, H, H, H};
-                EXORL_TRY(gemm_grouped(prec, 1, 1, p, d.n_heads, false, r0 > 0, fk.side(s)));
-            }
-        }
-        for (int i = 0; i < d.n_heads; ++i)
-            p[i] = GemmProblem{b.dz2 + i * act, P + d.W1 + i * d.head_stride, b.dh1 + (paired ? i : 0) * act, nullptr,
-                               rows, H, H, H, H, H};
-        if (paired) {
-            EXORL_TRY(gemm_grouped(prec, 0, 1, p, d.n_heads, false, false, s));
-        } else {
-            for (int i = 0; i < d.n_heads; ++i) EXORL_TRY(gemm_grouped(prec, 0, 1, p + i, 1, false, i > 0, s));
-        }
+    }
+    for (int i = 0; i < d.n_heads; ++i) p[i] = dgrad(i);
+    if (!paired) {                                 // shared trunk: one launch per head, accumulating into the one dh1
+        for (int i = dgrads_done; i < d.n_heads; ++i) EXORL_TRY(products(rt, prec, 0, 1, p + i, 1, H, false, i > 0, s));
+    } else if (dgrads_done == 0) {                 // paired: one grouped launch
+        EXORL_TRY(products(rt, prec, 0, 1, p, d.n_heads, H, false, false, s));
     }
     const bool dx_fused = dx && !G;              // dgrad-only pass: d/d(input columns) in the LayerNorm-backward kernel itself
-    EXORL_TRY(ln_bwd(b.dh1, f.h1, f.xhat, bf ? f.h1b : nullptr, bf ? f.xhatb : nullptr, f.rstd, P + d.g, pt.Pt, rows, H, d.n_trunks,
-                     act, d.trunk_stride, G ? 1 : 0, s, dx_fused ? sh.w0t + (int64_t)dx_col0 * H : nullptr, (int64_t)d.in_dim * H,
-                     dx_fused ? dx : nullptr, dx_cols, bf ? f.h1l : nullptr, bf ? f.xhatl : nullptr, (bf && trunk_fwd16_supported(H)) ? P + d.beta : nullptr));
+    // beta: with the MFMA trunk's images (bf16 route, trunk_fwd16_supported) the kernel rebuilds the LayerNorm input from h
+    EXORL_TRY(ln_bwd(b.dh1, f.h1, f.xhat, h1q, xhatq, f.rstd, P + d.g, pt.Pt, rows, H, d.n_trunks, act, d.trunk_stride, G ? 1 : 0, s,
+                     dx_fused ? sh.w0t + (int64_t)dx_col0 * H : nullptr, (int64_t)d.in_dim * H, dx_fused ? dx : nullptr, dx_cols,
+                     (bf && trunk_fwd16_supported(H)) ? P + d.beta : nullptr));
     if (dx && !dx_fused)       // dx[m][j] = sum_c dz0[m][c] W0[c][col0+j]: a row-dot against rows col0.. of the transposed shadow
         EXORL_TRY(head_fwd4(b.dh1, sh.w0t + (int64_t)dx_col0 * H, nullptr, dx, rows, H, dx_cols, 0, d.n_trunks, act,
                             (int64_t)d.in_dim * H, (int64_t)rows * dx_cols, s));
@@ -366,26 +342,21 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
     return 0;
 }
 
-struct Carver {           // lays sub-buffers out in one workspace; base == nullptr -> sizing pass
-    float* base;
-    int64_t off = 0;
+struct Carver : SimpleCarver {
     // exorl_debug_agent_poison_scratch: carve() marks the takes a step writes before it reads (scratch = true); `fill` collects those whole,
     // and of every other take only the alignment padding behind it, as (offset, floats) runs
     bool scratch = false;
     std::vector<std::pair<int64_t, int64_t>>* fill = nullptr;
-    explicit Carver(float* b) : base(b) {}
+    using SimpleCarver::SimpleCarver;
     float* take(int64_t n) {
-        float* p = base ? base + off : nullptr;
-        const int64_t padded = round_up(n, 64);
         if (fill) {
-            const int64_t o = scratch ? off : off + n, len = scratch ? padded : padded - n;
+            const int64_t padded = round_up(n, 64), o = scratch ? off : off + n, len = scratch ? padded : padded - n;
             if (len > 0) {
                 if (!fill->empty() && fill->back().first + fill->back().second == o) fill->back().second += len;
                 else fill->push_back({o, len});
             }
         }
-        off += padded;
-        return p;
+        return SimpleCarver::take(n);
     }
 };
 
@@ -477,24 +448,46 @@ static void carve(exorl_agent* a, Carver& c) {
         a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM] = c.take(a->critic.total);
     }
     a->obs = c.take(B * O); a->action = c.take(B * A); a->reward = c.take(B); a->discount = c.take(B); a->next_obs = c.take(B * O);
+    // Images per buffer: 1 plain bf16, 2 bf16x3 on the plane pipeline, 3 bf16x6 on the plane route, 0 otherwise (planes_ok and planes3_ok exclude
+    // each other by precision). The one- and two-plane images follow their struct's fp32 buffers, hi planes first; the three-plane images
+    // (three_planes below, no-ops otherwise) follow their group of structs. The order is part of the contract: exorl_debug_agent_poison_scratch
+    // and the whole-workspace digests of tools/agent_digests.py see it.
+    const int np = cfg.precision == EXORL_PREC_BF16 ? 1 : planes_ok(cfg) ? 2 : planes3_ok(cfg) ? 3 : 0;
+    const int nb = np == 3 ? 0 : np;                // images the row kernels write: the bf16 routes' only
+    auto take_u16 = [&](int64_t n) { return reinterpret_cast<unsigned short*>(c.take((n + 1) / 2)); };
+    auto take_hi_lo = [&](Planes& x, int64_t nx, Planes* y, int64_t ny, int planes) {
+        if (planes >= 1) { x.hi = take_u16(nx); if (y) y->hi = take_u16(ny); }
+        if (planes >= 2) { x.lo = take_u16(nx); if (y) y->lo = take_u16(ny); }
+    };
+    auto three_planes = [&](Planes& x, int64_t n) { if (np == 3) { x.hi = take_u16(n); x.mid = take_u16(n); x.lo = take_u16(n); } };
+    // saved: xhat and rstd are kept for a backward pass. f32_h1 = false: nobody reads h1 as fp32 (CRR's value samples on the bf16 routes).
+    auto take_fwd = [&](int64_t trunk_rows, int64_t head_rows, int64_t out_cols, bool saved, bool f32_h1, int planes) {
+        FwdBufs f{};
+        if (f32_h1) f.h1 = c.take(trunk_rows * H);
+        if (saved) { f.xhat = c.take(trunk_rows * H); f.rstd = c.take(trunk_rows); }
+        f.h2 = c.take(head_rows * H); f.out = c.take(head_rows * out_cols);
+        take_hi_lo(f.h1q, trunk_rows * H, saved ? &f.xhatq : nullptr, trunk_rows * H, planes);
+        return f;
+    };
+    auto take_bwd = [&](int64_t head_rows, int64_t trunk_rows) {
+        BwdBufs b{c.take(head_rows * H), c.take(trunk_rows * H), {}};
+        take_hi_lo(b.dz2q, head_rows * H, nullptr, 0, nb);
+        return b;
+    };
+    auto take_shadow = [&](int64_t n_trunks, int64_t n_heads, int64_t in_dim) {      // W0 has no three-plane image: the trunk kernels read fp32
+        NetShadow sh{c.take(n_trunks * in_dim * H), {}, {}};
+        take_hi_lo(sh.w1q, n_heads * H * H, &sh.w0q, n_trunks * H * round_up(in_dim, 32), nb);
+        return sh;
+    };
     c.scratch = true;       // from here on: c.scratch says whether a step writes the sub-buffer before it reads it (see Carver)
     a->xa = c.take(2 * B * O);
-    auto take_u16 = [&](int64_t n) { return reinterpret_cast<unsigned short*>(c.take((n + 1) / 2)); };
-    const bool x3 = planes_ok(cfg);
-    const bool bf = cfg.precision == EXORL_PREC_BF16 || x3;
-    auto take_lo = [&](int64_t n) { return x3 ? take_u16(n) : nullptr; };
-    // three-plane images, from this agent's own workspace and under bf16x6 only: no other precision's layout or size moves
-    const bool p3 = planes3_ok(cfg);
-    auto take_p3 = [&](int64_t n) { P3 p; if (p3) { p.hi = take_u16(n); p.mid = take_u16(n); p.lo = take_u16(n); } return p; };
-    a->fa = FwdBufs{c.take(2 * B * H), c.take(2 * B * H), c.take(2 * B), c.take(2 * B * H), c.take(2 * B * AO), bf ? take_u16(2 * B * H) : nullptr,
-                    bf ? take_u16(2 * B * H) : nullptr, take_lo(2 * B * H), take_lo(2 * B * H)};
-    a->ba = BwdBufs{c.take(B * H), c.take(B * H), bf ? take_u16(B * H) : nullptr, take_lo(B * H)};
-    a->fa.h1p = take_p3(2 * B * H);
-    a->ba.dz2p = take_p3(B * H);
+    a->fa = take_fwd(2 * B, 2 * B, AO, true, true, nb);
+    a->ba = take_bwd(B, B);
+    three_planes(a->fa.h1q, 2 * B * H);
+    three_planes(a->ba.dz2q, B * H);
     c.scratch = false;
-    a->sh_actor = NetShadow{c.take(O * H), bf ? take_u16(H * H) : nullptr, bf ? take_u16(H * round_up(O, 32)) : nullptr, take_lo(H * H),
-                            take_lo(H * round_up(O, 32))};
-    a->sh_actor.w1p = take_p3(H * H);
+    a->sh_actor = take_shadow(1, 1, O);
+    three_planes(a->sh_actor.w1q, H * H);
     c.scratch = true;
     a->pa = Partials{c.take((int64_t)head_chunks(B) * ((AO + 1) * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
                      c.take((int64_t)outer_chunks(B) * O * H)};
@@ -507,21 +500,18 @@ static void carve(exorl_agent* a, Carver& c) {
     a->act_noise = c.take(ACT_ROWS * A);
     a->act_part = c.take((int64_t)cdiv(H, 4) * ACT_FAST_ROWS * 16);
     a->act_ticket = reinterpret_cast<unsigned int*>(c.take(4));
-    a->fact = FwdBufs{c.take(ACT_ROWS * H), nullptr, nullptr, c.take(ACT_ROWS * H), c.take(ACT_ROWS * AO), bf ? take_u16(ACT_ROWS * H) : nullptr, nullptr,
-                      nullptr, nullptr};
+    a->fact = take_fwd(ACT_ROWS, ACT_ROWS, AO, false, true, nb ? 1 : 0);      // act(): a hi plane at most (see g16)
     if (a->has_critic) {
         const int64_t nt = a->critic.n_trunks;
         c.scratch = true;
         a->xc_cur = c.take(B * W); a->xc_next = c.take(B * W); a->xc_pi = c.take(B * W);
         const int64_t od = a->critic.out_dim;
-        a->ft = FwdBufs{c.take(nt * B * H), nullptr, nullptr, c.take(2 * B * H), c.take(2 * B * od), bf ? take_u16(nt * B * H) : nullptr, nullptr,
-                        take_lo(nt * B * H), nullptr};
-        a->fc = FwdBufs{c.take(nt * RC * H), c.take(nt * RC * H), c.take(nt * RC), c.take(2 * RC * H), c.take(2 * RC * od), bf ? take_u16(nt * RC * H) : nullptr,
-                        bf ? take_u16(nt * RC * H) : nullptr, take_lo(nt * RC * H), take_lo(nt * RC * H)};
-        a->bc = BwdBufs{c.take(2 * RC * H), c.take(nt * RC * H), bf ? take_u16(2 * RC * H) : nullptr, take_lo(2 * RC * H)};
-        a->ft.h1p = take_p3(nt * B * H);
-        a->fc.h1p = take_p3(nt * RC * H);
-        a->bc.dz2p = take_p3(2 * RC * H);
+        a->ft = take_fwd(nt * B, 2 * B, od, false, true, nb);
+        a->fc = take_fwd(nt * RC, 2 * RC, od, true, true, nb);
+        a->bc = take_bwd(2 * RC, nt * RC);
+        three_planes(a->ft.h1q, nt * B * H);
+        three_planes(a->fc.h1q, nt * RC * H);
+        three_planes(a->bc.dz2q, 2 * RC * H);
         if (cfg.kind == EXORL_AGENT_CQL) {
             a->x_all = c.take(RC * W);
             a->dq_all = c.take(2 * RC);
@@ -537,17 +527,14 @@ static void carve(exorl_agent* a, Carver& c) {
             const int64_t R = B * cfg.num_value_samples;
             a->xc_rep = c.take(R * W);
             a->crr_w = c.take(B);
-            a->fr = FwdBufs{bf ? nullptr : c.take(nt * R * H), nullptr, nullptr, c.take(2 * R * H), c.take(2 * R), bf ? take_u16(nt * R * H) : nullptr, nullptr,
-                            take_lo(nt * R * H), nullptr};
-            a->fr.h1p = take_p3(nt * R * H);
+            a->fr = take_fwd(nt * R, 2 * R, 1, false, nb == 0, nb);
+            three_planes(a->fr.h1q, nt * R * H);
         }
         c.scratch = false;
-        a->sh_critic = NetShadow{c.take(nt * W * H), bf ? take_u16(2 * H * H) : nullptr, bf ? take_u16(nt * H * round_up(W, 32)) : nullptr,
-                                 take_lo(2 * H * H), take_lo(nt * H * round_up(W, 32))};
-        a->sh_target = NetShadow{c.take(nt * W * H), bf ? take_u16(2 * H * H) : nullptr, bf ? take_u16(nt * H * round_up(W, 32)) : nullptr,
-                                 take_lo(2 * H * H), take_lo(nt * H * round_up(W, 32))};
-        a->sh_critic.w1p = take_p3(2 * H * H);
-        a->sh_target.w1p = take_p3(2 * H * H);
+        a->sh_critic = take_shadow(nt, 2, W);
+        a->sh_target = take_shadow(nt, 2, W);
+        three_planes(a->sh_critic.w1q, 2 * H * H);
+        three_planes(a->sh_target.w1q, 2 * H * H);
         c.scratch = true;
         a->pc = Partials{c.take(2 * (int64_t)qhead_chunks(RC) * ((od + 1) * H + 32)), c.take(nt * (int64_t)trunk_chunks(RC) * 3 * H),
                          c.take(nt * (int64_t)outer_chunks(RC) * W * H)};
@@ -639,7 +626,7 @@ static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
     const int64_t act = (int64_t)B * H;
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
     const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
-    const bool bf = a->bc.dz2b != nullptr;
+    const bool bf = route_of(a->cfg.precision, a->fc.h1q, a->sh_critic.w1q, B) == Route::Planes;       // as net_backward decides it
     QHeadArgs q{};
     for (int i = 0; i < 2; ++i) {
         q.a[i] = a->fc.h2 + i * act; q.W[i] = Pc + d.W2 + i * d.head_stride; q.b[i] = Pc + d.b2 + i * d.head_stride;
@@ -650,7 +637,7 @@ static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
     if (mode == 0 && a->tq_slots > 0) {          // the target's heads were folded into its forward GEMM (net_forward2): ft.h2 holds partial dots
         q.tpart[0] = a->ft.h2; q.tpart[1] = a->ft.h2 + act; q.tslots = a->tq_slots;
     }
-    q.dz = bf ? nullptr : a->bc.dz2; q.dzb = bf ? a->bc.dz2b : nullptr; q.dzl = bf ? a->bc.dz2l : nullptr; q.act = act;
+    q.dz = bf ? nullptr : a->bc.dz2; q.dzb = bf ? a->bc.dz2q.hi : nullptr; q.dzl = bf ? a->bc.dz2q.lo : nullptr; q.act = act;
     q.P = mode == 0 ? a->pc.Ph : nullptr;
     q.abs_part = a->abs_part;
     q.rows = B; q.H = H; q.mode = mode; q.inv_bg = a->inv_bg;
@@ -684,7 +671,7 @@ static int phase0(exorl_agent* a, float stddev, const float* noise_c, hipStream_
                                   &a->state->noise_counter, stddev, cfg.stddev_clip, a->xc_next + O, a->xc_pi + O, W, B, A, s, &a->state->stddev));
     const bool qf = qfuse(a);
     a->tq_slots = 0;
-    if (!a->fk.on && forward2_supported(a->critic, prec, a->sh_target, a->sh_critic)) {
+    if (!a->fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
         EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s, qf, qf,
                                &a->tq_slots));
     } else {
@@ -767,11 +754,7 @@ static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
                                dq, a->bc, a->da, O, A, prec, s, a->fk, nullptr, qf));
     }
     // the obs half (rows B..2B) of the stacked actor forward
-    FwdBufs f{a->fa.h1 + (int64_t)B * H, a->fa.xhat + (int64_t)B * H, a->fa.rstd + B, a->fa.h2 + (int64_t)B * H,
-              a->fa.out + (int64_t)B * A, a->fa.h1b ? a->fa.h1b + (int64_t)B * H : nullptr,
-              a->fa.xhatb ? a->fa.xhatb + (int64_t)B * H : nullptr, a->fa.h1l ? a->fa.h1l + (int64_t)B * H : nullptr,
-              a->fa.xhatl ? a->fa.xhatl + (int64_t)B * H : nullptr};
-    f.h1p = a->fa.h1p.at((int64_t)B * H);
+    const FwdBufs f = a->fa.rows_from(B, H, A);
     if (!a->has_critic)       // BC (bc.py:82): the only forward of the step
         EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa + (int64_t)B * O, O, B, f, true, true, prec, s));
     if (a->want_metrics)                        // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
@@ -871,11 +854,7 @@ static int cql_phase2(exorl_agent* a, hipStream_t s) {
     dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.use_lambda = 0;
     EXORL_TRY(net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, nullptr, a->pc, a->xc_pi, W, B, a->fc, dq,
                            a->bc, a->da, O, A, prec, s, a->fk));
-    FwdBufs f{a->fa.h1 + (int64_t)B * H, a->fa.xhat + (int64_t)B * H, a->fa.rstd + B, a->fa.h2 + (int64_t)B * H,
-              a->fa.out + (int64_t)B * 2 * A, a->fa.h1b ? a->fa.h1b + (int64_t)B * H : nullptr,
-              a->fa.xhatb ? a->fa.xhatb + (int64_t)B * H : nullptr, a->fa.h1l ? a->fa.h1l + (int64_t)B * H : nullptr,
-              a->fa.xhatl ? a->fa.xhatl + (int64_t)B * H : nullptr};
-    f.h1p = a->fa.h1p.at((int64_t)B * H);
+    const FwdBufs f = a->fa.rows_from(B, H, 2 * A);
     DoutSpec dm{};
     dm.mode = EXORL_DOUT_CQL_ACTOR; dm.da = a->da; dm.da_nets = a->critic.n_trunks; dm.raw = f.out; dm.z = a->noise_a;
     dm.alpha_ptr = &a->cql->alpha; dm.inv_bg = a->inv_bg; dm.seed = cfg.seed; dm.counter = 4; dm.counter_ptr = &a->state->noise_counter;
@@ -1152,7 +1131,7 @@ int exorl_agent_act(exorl_agent_t* a, const float* obs, int32_t n, float stddev,
     for (int r0 = 0; r0 < n; r0 += ACT_ROWS) {
         const int rows = n - r0 < ACT_ROWS ? n - r0 : ACT_ROWS;
         NetShadow sh = a->sh_actor;                 // act() rows do not tile by 64: split-bf16 takes the in-GEMM split here
-        sh.w1l = sh.w0l = nullptr;
+        sh.w1q.lo = sh.w0q.lo = nullptr;
         EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], sh, obs + (int64_t)r0 * O, O, rows, a->fact, false,
                               a->cfg.kind != EXORL_AGENT_CQL,
                               a->cfg.precision, s));

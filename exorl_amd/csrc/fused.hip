@@ -503,16 +503,16 @@ int trunk_fwd16_batch(const TrunkBatch& tb, int count, int64_t ldx, int rows, in
     return 0;
 }
 
-int trunk_fwd16(const float* x, int64_t ldx, const unsigned short* W0b, const float* b0, const float* gain, const float* beta, float* rstd,
-                unsigned short* h_bf16, unsigned short* xhat_bf16, int rows, int in_dim, int H, int nets, int64_t astride, int64_t pstride,
-                hipStream_t s, const unsigned short* W0l, unsigned short* h_lo, unsigned short* xhat_lo) {
-    EXORL_REQUIRE(h_bf16 && nets >= 1 && nets <= 4, "trunk_fwd16: bad arguments");
+int trunk_fwd16(const float* x, int64_t ldx, const Planes& W0q, const float* b0, const float* gain, const float* beta, float* rstd,
+                const Planes& hq, const Planes& xhatq, int rows, int in_dim, int H, int nets, int64_t astride, int64_t pstride, hipStream_t s) {
+    EXORL_REQUIRE(W0q && hq && nets >= 1 && nets <= 4, "trunk_fwd16: bad arguments");
     TrunkBatch tb{};
     const int64_t wstride = (int64_t)H * round_up(in_dim, 32);
-    for (int n = 0; n < nets; ++n)
-        tb.it[n] = TrunkItem{x, W0b + n * wstride, b0 + n * pstride, gain + n * pstride, beta + n * pstride, rstd ? rstd + (int64_t)n * rows : nullptr,
-                             h_bf16 + n * astride, xhat_bf16 ? xhat_bf16 + n * astride : nullptr, W0l ? W0l + n * wstride : nullptr,
-                             h_lo ? h_lo + n * astride : nullptr, (xhat_bf16 && xhat_lo) ? xhat_lo + n * astride : nullptr};
+    for (int n = 0; n < nets; ++n) {
+        const Planes w = W0q.at(n * wstride), h = hq.at(n * astride), xh = xhatq.at(n * astride);
+        tb.it[n] = TrunkItem{x, w.hi, b0 + n * pstride, gain + n * pstride, beta + n * pstride, rstd ? rstd + (int64_t)n * rows : nullptr,
+                             h.hi, xh.hi, w.lo, h.lo, xh.lo};
+    }
     return trunk_fwd16_batch(tb, nets, ldx, rows, in_dim, H, s);
 }
 
@@ -728,10 +728,10 @@ __global__ __launch_bounds__(512) void ln_bwd_kernel(float* dh, const float* __r
     }
 }
 
-int ln_bwd(float* dh, const float* h, const float* xhat, const unsigned short* h_bf16, const unsigned short* xhat_bf16,
-           const float* rstd, const float* gain, float* P, int rows, int H, int nets, int64_t astride, int64_t pstride,
-           int want_params, hipStream_t s, const float* w0t, int64_t tstride, float* dx, int dx_cols, const unsigned short* h_lo,
-           const unsigned short* xhat_lo, const float* beta) {
+int ln_bwd(float* dh, const float* h, const float* xhat, const Planes& hq, const Planes& xhatq, const float* rstd, const float* gain, float* P,
+           int rows, int H, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, const float* w0t, int64_t tstride,
+           float* dx, int dx_cols, const float* beta) {
+    const unsigned short *h_bf16 = hq.hi, *xhat_bf16 = xhatq.hi, *h_lo = hq.lo, *xhat_lo = xhatq.lo;
     EXORL_REQUIRE(H >= 4 && H <= 1024 && H % 4 == 0, "ln_bwd: unsupported H=%d", H);
     EXORL_REQUIRE(!dx || (!want_params && w0t && dx_cols >= 1), "ln_bwd: the dx epilogue belongs to the dgrad-only pass");
     const dim3 grid(trunk_chunks(rows), nets);
@@ -1096,8 +1096,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
     }
 }
 
-int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, unsigned short* dz_bf16, float* P, int rows,
-             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, unsigned short* dz_lo) {
+int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, const Planes& dzq, float* P, int rows,
+             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s) {
+    unsigned short *dz_bf16 = dzq.hi, *dz_lo = dzq.lo;
     EXORL_REQUIRE(nout >= 1 && nout <= 16 && H % 4 == 0 && H <= 1024, "head_bwd: nout=%d H=%d unsupported", nout, H);
     dim3 grid(cdiv(rows, HB_ROWS), nets);
     if (nout == 1) hipLaunchKernelGGL((head_bwd_kernel<1>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
@@ -1162,8 +1163,9 @@ __global__ __launch_bounds__(256) void head_bwd_wide_kernel(const DoutSpec dspec
     }
 }
 
-int head_bwd_wide(const DoutSpec& dspec, const float* W, const float* a, float* dz, unsigned short* dz_bf16, float* P, int rows, int H,
-                  int nout, int64_t astride, int64_t pstride, int want_params, hipStream_t s, unsigned short* dz_lo) {
+int head_bwd_wide(const DoutSpec& dspec, const float* W, const float* a, float* dz, const Planes& dzq, float* P, int rows, int H,
+                  int nout, int64_t astride, int64_t pstride, int want_params, hipStream_t s) {
+    unsigned short *dz_bf16 = dzq.hi, *dz_lo = dzq.lo;
     EXORL_REQUIRE(nout > 16 && nout <= 32, "head_bwd_wide: nout=%d out of range", nout);
     hipLaunchKernelGGL(head_bwd_wide_kernel, dim3(cdiv(H, 256), cdiv(rows, HB_ROWS), 1), dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows,
                        H, nout, astride, pstride, want_params, dz_lo);

@@ -23,7 +23,6 @@
 
 namespace exorl {
 
-struct ITensor { int64_t off, rows, cols; };
 struct RmsState { float M, S; double n; };          // utils.RMS: running mean / variance / count (n starts at 1e-4)
 
 __device__ __forceinline__ float block_sum(float v, float* red) {      // all threads get the total; red: >= 17 floats
@@ -1031,7 +1030,7 @@ using namespace exorl;
 
 struct exorl_intr {
     exorl_intr_cfg cfg;
-    std::vector<ITensor> tensors;          // module.parameters() order
+    std::vector<TensorDesc> tensors;          // module.parameters() order
     int64_t total = 0, trainable = 0;      // flat sizes (floats): all parameters / the prefix the optimiser steps
     float* ws = nullptr;
     bool owns_ws = false;
@@ -1074,12 +1073,6 @@ struct exorl_intr {
 };
 
 namespace exorl {
-
-struct ICarver {
-    float* base; int64_t off = 0;
-    explicit ICarver(float* b) : base(b) {}
-    float* take(int64_t n) { float* p = base ? base + off : nullptr; off += round_up(n, 64); return p; }
-};
 
 static bool proto_cand_lds_fits(int64_t rows) { return (size_t)rows * 5 * sizeof(float) <= 64 * 1024; }     // proto_candidates_kernel<4>
 
@@ -1142,7 +1135,7 @@ static void describe_intr(exorl_intr* it) {
     it->total = round_up(off, 64);
 }
 
-static void carve_intr(exorl_intr* it, ICarver& c) {
+static void carve_intr(exorl_intr* it, SimpleCarver& c) {
     const auto& g = it->cfg;
     const int64_t B = g.batch, O = g.obs_dim, R = g.rep_dim, W = g.world_size > 1 ? g.world_size : 1;
     it->flat[EXORL_T_PARAM] = c.take(it->total);
@@ -1922,7 +1915,7 @@ size_t exorl_intr_workspace_bytes(const exorl_intr_cfg* cfg) {
     exorl_intr tmp;
     tmp.cfg = *cfg;
     describe_intr(&tmp);
-    ICarver sizing(nullptr);
+    SimpleCarver sizing(nullptr);
     carve_intr(&tmp, sizing);
     return (size_t)sizing.off * sizeof(float);
 }
@@ -1948,7 +1941,7 @@ int exorl_intr_create(const exorl_intr_cfg* cfg, void* workspace, size_t workspa
         }
         it->owns_ws = true;
     }
-    ICarver c(it->ws);
+    SimpleCarver c(it->ws);
     carve_intr(it, c);
     int rc = hipMemset(it->ws, 0, bytes) == hipSuccess ? 0 : 1;
     if (rc != 0) set_error("intr_create: hipMemset failed");
@@ -1977,7 +1970,7 @@ int exorl_intr_tensor(exorl_intr_t* it, int32_t index, int32_t what, void** ptr,
     EXORL_REQUIRE(it && ptr && rows && cols, "intr_tensor: null argument");
     EXORL_REQUIRE(index >= 0 && index < (int32_t)it->tensors.size(), "intr_tensor: index %d out of range", index);
     EXORL_REQUIRE(what >= EXORL_T_PARAM && what <= EXORL_T_ADAM_V, "intr_tensor: unknown buffer %d", what);
-    const ITensor& t = it->tensors[index];
+    const TensorDesc& t = it->tensors[index];
     EXORL_REQUIRE(what == EXORL_T_PARAM || t.off < it->trainable, "intr_tensor: tensor %d is frozen (no gradient / optimiser state)", index);
     *ptr = it->flat[what] + t.off; *rows = t.rows; *cols = t.cols;
     return 0;

@@ -6,6 +6,23 @@
 
 namespace exorl {
 
+struct TensorDesc { int64_t off, rows, cols; };      // one parameter tensor inside a flat buffer (floats), torch shape rows x cols
+
+// Lays sub-buffers out in one workspace, each padded to 64 floats; base == nullptr -> sizing pass.
+struct SimpleCarver {
+    float* base; int64_t off = 0;
+    explicit SimpleCarver(float* b) : base(b) {}
+    float* take(int64_t n) { float* p = base ? base + off : nullptr; off += round_up(n, 64); return p; }
+};
+
+// The bf16 images of one fp32 buffer, same shape and pitch: hi = bf16(x) alone (plain bf16), hi + lo with lo = bf16(x - hi) (bf16x3 on the
+// plane pipeline), or hi + mid + lo = the 24 significand bits of x (bf16x6 on the plane route). A plane the precision does not use is null.
+struct Planes {
+    unsigned short *hi = nullptr, *mid = nullptr, *lo = nullptr;
+    Planes at(int64_t off) const { return Planes{hi ? hi + off : nullptr, mid ? mid + off : nullptr, lo ? lo + off : nullptr}; }
+    explicit operator bool() const { return hi != nullptr; }
+};
+
 struct GemmProblem {
     const float* A;
     const float* B;
@@ -42,7 +59,8 @@ struct Gemm16Problem {
     // The planes adapter uses it for outputs whose width is not a multiple of the tile (39200-wide module layers) instead of a padded C + copy.
     int n_store = 0;
     // three-plane split-bf16 ("bf16x6") operands: x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), i.e. the 24
-    // significand bits of an fp32 value. A problem with mid planes carries A_lo / B_lo as its third planes; the product is formed as hi*hi,
+    // significand bits of an fp32 value (a Planes with all three set). A problem with mid planes carries A_lo / B_lo as its third planes —
+    // Planes::lo is the last plane of a two-plane and of a three-plane image alike; the product is formed as hi*hi,
     // hi*mid + mid*hi, hi*lo + lo*hi + mid*mid in three fp32 accumulators summed small-first (mid*lo, lo*mid, lo*lo are dropped: relative error
     // <= 3 * 2^-24 of |a||b|). One kernel takes such a launch (gemm16p, TN = 64): M % 128, N % 64, K % 128 = 0, 16-byte aligned planes, C and bias.
     const unsigned short* A_mid = nullptr;
@@ -96,13 +114,13 @@ struct HeadBatch { HeadItem it[4]; };
 int head_fwd1_batch(const HeadBatch& hb, int count, int rows, int H, hipStream_t s);
 // MFMA variant for the bf16 fast mode (H % 128 == 0): W0b = bf16 shadow [nets][H][round_up(in_dim, 32)], zero padded
 bool trunk_fwd16_supported(int H);
-int trunk_fwd16(const float* x, int64_t ldx, const unsigned short* W0b, const float* b0, const float* gain, const float* beta, float* rstd,
-                unsigned short* h_bf16, unsigned short* xhat_bf16, int rows, int in_dim, int H, int nets, int64_t astride, int64_t pstride,
-                hipStream_t s, const unsigned short* W0l = nullptr, unsigned short* h_lo = nullptr, unsigned short* xhat_lo = nullptr);
-int ln_bwd(float* dh, const float* h, const float* xhat, const unsigned short* h_bf16, const unsigned short* xhat_bf16,
-           const float* rstd, const float* gain, float* P, int rows, int H, int nets, int64_t astride, int64_t pstride,
-           int want_params, hipStream_t s, const float* w0t = nullptr, int64_t tstride = 0, float* dx = nullptr, int dx_cols = 0,
-           const unsigned short* h_lo = nullptr, const unsigned short* xhat_lo = nullptr, const float* beta = nullptr);
+// W0q, hq, xhatq: hi planes, and lo planes in split-bf16 mode (x = hi + lo); xhatq empty -> h only (nobody runs a backward pass over it)
+int trunk_fwd16(const float* x, int64_t ldx, const Planes& W0q, const float* b0, const float* gain, const float* beta, float* rstd,
+                const Planes& hq, const Planes& xhatq, int rows, int in_dim, int H, int nets, int64_t astride, int64_t pstride, hipStream_t s);
+// hq, xhatq: both empty -> reads the fp32 h / xhat; otherwise the bf16 images (hi, or hi + lo) in their place
+int ln_bwd(float* dh, const float* h, const float* xhat, const Planes& hq, const Planes& xhatq, const float* rstd, const float* gain, float* P,
+           int rows, int H, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, const float* w0t, int64_t tstride,
+           float* dx, int dx_cols, const float* beta);
 int trunk_chunks(int rows);
 // k smallest L2 distances of every src row to the tgt rows (at most 8192), ascending (knn.hip); d2 = scratch of knn_scratch_floats(n_src, n_tgt)
 // floats: n_src x round_up(n_tgt, 64) up to 4096 targets, at most 1024 such rows above
@@ -153,8 +171,9 @@ struct DoutSpec {
     float inv_bg, alpha, stddev;
     const float* stddev_ptr;   // BC / CRR: device-resident std (StepState::stddev); null -> `stddev`
 };
-int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, unsigned short* dz_bf16, float* P, int rows,
-             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, unsigned short* dz_lo = nullptr);
+// dz (fp32) and / or dzq (hi, or hi + lo) receive the gradient at the hidden layer: whichever is non-null
+int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, const Planes& dzq, float* P, int rows,
+             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s);
 int head_chunks(int rows);
 int tune_variant();      // exorl_gemm_tune's bits (0 = defaults): the reference paths below, each read at one decision point
 constexpr int TUNE_CONV_WGRAD_TILE = 64;             // 32 -> 32 conv weight gradient on the tile kernel, not conv_wgrad_ws_kernel
@@ -389,8 +408,8 @@ int cql_alpha_step(CqlScalars* sc, const float* stats, const AdamConst* c_dev, f
                    hipStream_t s);
 // policy output for act(): tanh(mu) (eval) or tanh(mu + std z)
 int cql_act(const float* raw, const float* noise, uint64_t seed, uint64_t counter, int eval_mode, float* out, int rows, int A, hipStream_t s);
-int head_bwd_wide(const DoutSpec& dspec, const float* W, const float* a, float* dz, unsigned short* dz_bf16, float* P, int rows, int H,
-                  int nout, int64_t astride, int64_t pstride, int want_params, hipStream_t s, unsigned short* dz_lo = nullptr);
+int head_bwd_wide(const DoutSpec& dspec, const float* W, const float* a, float* dz, const Planes& dzq, float* P, int rows, int H,
+                  int nout, int64_t astride, int64_t pstride, int want_params, hipStream_t s);
 
 // CRR (crr.py:121-142): xc_rep[(b*n+i)] = [obs_b | TruncatedNormal(mu_b).sample(clip)] for i < n
 int repeat_sample(const float* obs, const float* mu, const float* noise, uint64_t seed, const uint64_t* counter_ptr, uint64_t counter,

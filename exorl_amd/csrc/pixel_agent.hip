@@ -13,14 +13,13 @@
 
 namespace exorl {
 
-struct PTensor { int64_t off, rows, cols; };
 struct PNet {                       // trunk Linear(D, F) + LayerNorm(F) + Tanh, then n_heads three-layer heads on F (+A)
     int D = 0, F = 0, H = 0, head_in = 0, out = 0, n_heads = 0;
     Lin trunk{};
     int64_t g = 0, beta = 0;
     Mlp head[2];
     int64_t total = 0;
-    std::vector<PTensor> tensors;
+    std::vector<TensorDesc> tensors;
 };
 
 static PNet make_pnet(int D, int F, int H, int head_in, int out, int n_heads) {
@@ -182,13 +181,7 @@ struct exorl_pixel_agent {
 
 namespace exorl {
 
-struct PCarver {
-    float* base; int64_t off = 0;
-    explicit PCarver(float* b) : base(b) {}
-    float* take(int64_t n) { float* p = base ? base + off : nullptr; off += round_up(n, 64); return p; }
-};
-
-static void take_mlp(Mlp& m, PCarver& c, int64_t rows, float* last_act, float* last_dact) {
+static void take_mlp(Mlp& m, SimpleCarver& c, int64_t rows, float* last_act, float* last_dact) {
     m.act.clear(); m.dact.clear();
     for (size_t l = 0; l < m.L.size(); ++l) {
         const bool last = l + 1 == m.L.size();
@@ -197,7 +190,7 @@ static void take_mlp(Mlp& m, PCarver& c, int64_t rows, float* last_act, float* l
     }
 }
 
-static void pcarve(exorl_pixel_agent* a, PCarver& c) {
+static void pcarve(exorl_pixel_agent* a, SimpleCarver& c) {
     const auto& g = a->cfg;
     const int64_t B = g.batch, A = g.act_dim, F = g.feature_dim, R = a->R, img = (int64_t)g.c_in * g.hw * g.hw;
     // exchange 0 of a data-parallel step is the critic's gradients followed by the encoder's: one contiguous range
@@ -351,7 +344,7 @@ size_t exorl_pixel_agent_workspace_bytes(const exorl_pixel_cfg* cfg) {
     exorl_pixel_agent tmp;
     tmp.cfg = *cfg;
     pdescribe(&tmp);
-    PCarver c(nullptr);
+    SimpleCarver c(nullptr);
     pcarve(&tmp, c);
     return (size_t)c.off * sizeof(float);
 }
@@ -368,7 +361,7 @@ int exorl_pixel_agent_create(const exorl_pixel_cfg* cfg, void* workspace, size_t
     a->world = cfg->world_size > 1 ? cfg->world_size : 1;
     a->inv_bg = 1.0f / ((float)cfg->batch * (float)a->world);
     a->ws = static_cast<float*>(workspace);
-    PCarver c(a->ws);
+    SimpleCarver c(a->ws);
     pcarve(a, c);
     if (hipMemset(a->ws, 0, bytes) != hipSuccess) { set_error("pixel_agent_create: hipMemset failed"); delete a; return 1; }
     {                                            // BatchNorm2d buffers: running_mean 0, running_var 1, num_batches_tracked 0

@@ -49,6 +49,31 @@ WORKSPACE_BYTES = [
     ((5, 24, 6, 128, 128, 0), 11627520),         # cql, fp32
     ((4, 24, 6, 128, 128, 2), 7326464),          # crr, bf16x3
     ((3, 24, 6, 384, 1024, 1), 54670848),        # ddpg, bf16
+    # every kind in every precision, on and off the plane routes; a seventh entry is sf_dim (APS)
+    ((0, 24, 6, 128, 128, 3), 4638976),          # td3_bc, bf16x6 on the plane route
+    ((3, 24, 6, 128, 128, 3), 3975424),          # ddpg, bf16x6 on the plane route
+    ((2, 24, 6, 128, 128, 3), 1538816),          # bc, bf16x6 on the plane route
+    ((4, 24, 6, 128, 128, 3), 9390848),          # crr, bf16x6 on the plane route
+    ((5, 24, 6, 128, 128, 3), 16542720),         # cql, bf16x6 on the plane route
+    ((1, 24, 6, 128, 128, 3), 4638976),          # td3, bf16x6 on the plane route
+    ((0, 24, 6, 192, 72, 3), 4316416),           # td3_bc, bf16x6 off it
+    ((5, 24, 6, 128, 64, 2), 9103360),           # cql, bf16x3 on the plane pipeline
+    ((4, 24, 6, 128, 64, 2), 4537344),           # crr, bf16x3 on the plane pipeline
+    ((2, 24, 6, 128, 64, 2), 1047296),           # bc, bf16x3 on the plane pipeline
+    ((1, 24, 6, 128, 64, 2), 3144448),           # td3, bf16x3 on the plane pipeline
+    ((3, 24, 6, 192, 72, 2), 3830528),           # ddpg, bf16x3 off it
+    ((1, 24, 6, 192, 72, 1), 5130496),           # td3, bf16
+    ((2, 24, 6, 256, 256, 1), 4950784),          # bc, bf16
+    ((4, 24, 6, 256, 256, 1), 22636032),         # crr, bf16
+    ((5, 24, 6, 256, 256, 1), 54419712),         # cql, bf16
+    ((1, 24, 6, 100, 7, 0), 993792),             # td3, fp32
+    ((2, 24, 6, 100, 7, 0), 330752),             # bc, fp32
+    ((4, 24, 6, 100, 8, 0), 1141248),            # crr, fp32
+    ((3, 24, 6, 320, 1000, 0), 36042752),        # ddpg, fp32
+    ((6, 34, 6, 128, 128, 0, 10), 3298048),      # aps, fp32
+    ((6, 34, 6, 128, 128, 1, 10), 3855104),      # aps, bf16
+    ((6, 34, 6, 128, 128, 2, 10), 4395776),      # aps, bf16x3 on the plane pipeline
+    ((6, 34, 6, 128, 128, 3, 10), 4477696),      # aps, bf16x6 on the plane route
 ]
 
 
@@ -56,8 +81,8 @@ WORKSPACE_BYTES = [
 def test_workspace_bytes_of_the_other_precisions_are_unchanged(lib, cfg, want):
     from exorl_amd import _lib as L
     lib.exorl_agent_workspace_bytes.restype = ctypes.c_size_t
-    kind, O, A, H, B, prec = cfg
-    c = L.AgentCfg(kind, O, A, H, B, prec, 1, 0, 1e-4, 0.01, 2.5, 0.3, 0, 10, 1, 3, 0, 5.0, 0)
+    kind, O, A, H, B, prec, *sf_dim = cfg
+    c = L.AgentCfg(kind, O, A, H, B, prec, 1, sf_dim[0] if sf_dim else 0, 1e-4, 0.01, 2.5, 0.3, 0, 10, 1, 3, 0, 5.0, 0)
     assert lib.exorl_agent_workspace_bytes(ctypes.byref(c)) == want
 
 

@@ -4,6 +4,7 @@ must leave every line equal). Run it from each tree in a fresh process per listi
     python tools/agent_digests.py part1 OUT.txt [PICKLE_DIR]   every agent class, three update() calls; writes pickle.dumps(agent) per case
     python tools/agent_digests.py part2 OUT.txt PICKLE_DIR     loads those pickles (written by either tree), one more update()
     python tools/agent_digests.py part3 OUT.txt                the five two-process gloo workers of tests/, every array and json they save
+    python tools/agent_digests.py grid OUT.txt                 one update() of every case of the state agents' kernel dispatch grids, per route
     python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
 
 A listing has one line per entry, `case what value`; a value is the first 32 hex digits of a sha256 or a float.hex(). Inputs come from
@@ -29,7 +30,7 @@ PC, PHW, PF, PH, PB = 3, 64, 32, 128, 64            # pixels: the two-process wo
 OFFLINE = ['td3_bc', 'td3', 'bc', 'crr', 'cql', 'cql_lagrange']
 MODULES = ['rnd', 'icm', 'icm_apt', 'disagreement', 'diayn', 'aps', 'smm', 'proto']
 META = {'states': {'diayn': 16, 'aps': 10, 'smm': 4}, 'pixels': {'diayn': 8, 'aps': 5, 'smm': 4}}
-PRECISIONS = {'states': ('fp32', 'bf16x3'), 'pixels': ('fp32', 'bf16x6')}
+PRECISIONS = {'states': ('fp32', 'bf16', 'bf16x3', 'bf16x6'), 'pixels': ('fp32', 'bf16x6')}
 
 
 def sha(x):
@@ -303,6 +304,26 @@ def part3(out):
     listing(out, body)
 
 
+def grid(out):
+    """tests/_grad_grid.CASES and tests/_state_bf16x6_cases.CASES on the three routes of tests/test_gpu_grad_grid.py: one update() as its run()
+    does it, then every tensor of its state_of()."""
+    import _grad_grid as G
+    import _state_bf16x6_cases as S
+    import test_gpu_grad_grid as T
+
+    def body(emitter):
+        for c in list(G.CASES) + list(S.CASES):
+            for route in T.ROUTES:
+                name = f'grid/{G.case_id(c)}/{route}'
+                ag, m = T.run(c, route, False)
+                emit = emitter(name)
+                emit_metrics(emit, 'metrics', m)
+                for k, v in T.state_of(ag).items():
+                    emit(k, sha(v))
+                print(name, flush=True)
+    listing(out, body)
+
+
 def compare(a, b):
     la, lb = Path(a).read_text().splitlines(), Path(b).read_text().splitlines()
     key = lambda l: l.rsplit(' ', 1)[0]
@@ -317,4 +338,4 @@ def compare(a, b):
 
 if __name__ == '__main__':
     cmd, args = sys.argv[1], sys.argv[2:]
-    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'compare': compare}[cmd](*args))
+    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'compare': compare}[cmd](*args))
