@@ -158,6 +158,9 @@ PROTOTYPES = {
     'exorl_agent_act_host': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
     'exorl_agent_set_metrics': (C.c_int, [c_void_p, c_int32]),
+    'exorl_agent_metric_window_bytes': (c_size_t, [P(AgentCfg)]),
+    'exorl_agent_set_metric_window': (C.c_int, [c_void_p, c_void_p, c_size_t]),
+    'exorl_agent_metric_window_read': (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     'exorl_agent_set_parallel_branches': (C.c_int, [c_void_p, c_int32]),
     'exorl_agent_opt_steps': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_agent_set_opt_steps': (C.c_int, [c_void_p, c_int64, c_int64]),

@@ -176,7 +176,8 @@ class _AgentBase:
                           'queue': (it.queue.cpu(), it.queue_ptr()) if it.queue is not None else None, 'counter': it.counter()}
         skip = {'engine', 'intr', 'actor', 'critic', 'critic_target', 'rnd', 'icm', 'pbe', 'intrinsic_reward_rms', 'disagreement', 'diayn',
                 'predictor', 'predictor_target', 'projector', 'protos', 'queue', 'encoder_target', 'cat_hook', 'aps', 'smm', 'eps_hook', 'aug', 'encoder',
-                'noise_hook', 'shift_hook', '_slots', '_graph_iter', '_graph_stddev', '_ctor', 'rnd_target_encoder', '_dobs', '_dp'}
+                'noise_hook', 'shift_hook', '_slots', '_graph_iter', '_graph_stddev', '_ctor', 'rnd_target_encoder', '_dobs', '_dp',
+                '_metric_window'}
         st['attrs'] = {k: v for k, v in self.__dict__.items() if k not in skip and not k.startswith('_keep')}
         return st
 
@@ -255,6 +256,7 @@ class _AgentBase:
         self._slots = None
         self._graph_iter = None
         self._graph_stddev = None
+        self._metric_window = False
         self.noise_hook = None      # tests: callable(shape) -> np.ndarray standing in for _standard_normal (TruncatedNormal's draws)
 
     def params_changed(self):
@@ -297,6 +299,35 @@ class _AgentBase:
             return False
         self._graph_iter = replay_iter
         return True
+
+    # -- windowed metrics: the step's metrics accumulate in device memory and are read once per logging interval
+    METRIC_WINDOW = True        # False on the classes whose update() reports more than the engine's metric block (the module agents)
+
+    def enable_metric_window(self):
+        """Collects update()'s metrics in a window on the device: update() then returns {} with no device-to-host read (whatever use_tb
+        says) and pop_metrics() returns their means over the steps since the last pop. TD3+BC, TD3 and DDPG keep the fused fast path.
+        Returns False, and changes nothing, for pixel agents, the module agents and under data parallelism. Call it before enable_graph
+        (the capture holds the window's kernels); with a graph captured it raises. Not pickled: an unpickled agent has no window."""
+        if not self.METRIC_WINDOW or getattr(self, 'obs_type', 'states') == 'pixels' or self.world_size != 1:
+            return False
+        if self._graph_iter is not None:
+            raise RuntimeError('enable_metric_window() must be called before enable_graph(): the captured step has no window kernels')
+        self.engine.set_metric_window()
+        self._metric_window = True
+        return True
+
+    def pop_metrics(self):
+        """Means over the window of the keys update() returns with use_tb=True, plus metric_steps; {} when no step ran since the last
+        pop. Resets the window. One small device-to-host copy: the only one of the logging interval."""
+        if not self._metric_window:
+            raise RuntimeError('pop_metrics() needs enable_metric_window()')
+        sums, steps = self.engine.metric_window_read(reset=True)
+        if steps == 0:
+            return {}
+        m = {name: float(sums[idx] / steps) for idx, name in self.METRICS}
+        m.setdefault('actor_ent', float(sums[L.M_ACTOR_ENT] / steps))
+        m['metric_steps'] = steps
+        return m
 
     def disable_graph(self):
         if self._graph_iter is not None:
@@ -355,6 +386,8 @@ class _AgentBase:
     def _update_metrics(self, stddev):
         """update()'s return value on both observation types: the class's table of engine metrics, then what its module adds."""
         metrics = dict()
+        if self._metric_window:         # collected on the device: pop_metrics()
+            return metrics
         if self.use_tb or getattr(self, 'use_wandb', False):
             metrics.update(self._metrics(self.METRICS, stddev))
             self._module_metrics(metrics)
@@ -451,6 +484,8 @@ class CQLAgent(_AgentBase):
     """agents/offline_learning/cql.py:59-286 (both the shipped cql.yaml and use_critic_lagrange=True; under torch.distributed the latter splits
     phase 0 around a sum-all-reduce of the penalty, _run_update)."""
     KIND = 'cql'
+    METRICS = _CRITIC_METRICS + [(L.M_CRITIC_CQL, 'critic_cql'), (L.M_CRITIC_CQL_LOGSUM, 'critic_cql_logsum'), (L.M_ACTOR_ENT, 'actor_ent'),
+                                 (L.M_ACTOR_ALPHA, 'actor_alpha'), (L.M_ACTOR_ALPHA_LOSS, 'actor_alpha_loss')]
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, nstep, batch_size, use_tb, alpha,
                  n_samples, target_cql_penalty, use_critic_lagrange, has_next_action=False, *, precision='fp32', seed=0):
@@ -497,11 +532,9 @@ class CQLAgent(_AgentBase):
     def update(self, replay_iter, step):
         metrics = dict()
         self._step(replay_iter, 1.0)
-        if self.use_tb:
+        if self.use_tb and not self._metric_window:
             raw = global_means(self.engine)
-            for idx, name in _CRITIC_METRICS + [(L.M_CRITIC_CQL, 'critic_cql'), (L.M_CRITIC_CQL_LOGSUM, 'critic_cql_logsum'),
-                                                (L.M_ACTOR_ENT, 'actor_ent'), (L.M_ACTOR_ALPHA, 'actor_alpha'),
-                                                (L.M_ACTOR_ALPHA_LOSS, 'actor_alpha_loss')]:
+            for idx, name in self.METRICS:
                 metrics[name] = float(raw[idx])
         return metrics
 
@@ -727,6 +760,7 @@ class _RmsView:
 class _IntrAgent(DDPGAgent):
     """Shared update() of the reward-free agents (rnd.py:110-159, icm.py:94-139, icm_apt.py:112-158): module step and
     intrinsic reward on the sampled batch (libexorl_hip: exorl_intr_update), then the DDPG update on that reward."""
+    METRIC_WINDOW = False       # the modules' metrics live in their own engines
     MODULE_METRICS = ()         # per class: (slot, name) pairs of the module's metrics reported while reward_free (_module_table)
     STATE_METRICS = ()          # ... and those reported on state observations only
 

@@ -275,7 +275,7 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
                                 G ? 1 : 0, s));
     } else {
         EXORL_TRY(head_bwd(dout, P + d.W2, f.h2, bf ? nullptr : b.dz2, dz2q, G ? pt.Ph : nullptr, rows, H, d.out_dim, d.n_heads, act,
-                           d.head_stride, G ? 1 : 0, s));
+                           d.head_stride, G ? 1 : 0, s, dout.mode == EXORL_DOUT_ACTOR_MU && dout.bc_part));
     }
     // dz2 converted once for the wgrad and the dgrad; h1's images are the forward pass's
     if (rt == Route::Planes3) EXORL_TRY(to_planes3(b.dz2, H, d.n_heads * rows, H, b.dz2q.hi, b.dz2q.mid, b.dz2q.lo, d.n_heads * rows, H, 1, 0, 0, s));
@@ -420,6 +420,10 @@ struct exorl_agent {
     bool staged_by_sampler = false;  // captured step: the sampler's gather kernel writes the staged inputs and runs step_begin
     bool want_metrics = true;    // the (B,1)-sized metric reductions are skipped when the caller never reads them (use_tb=False)
     int tq_slots = 0;            // > 0: this step's target critic left per-row partial head dots in ft.h2 (folded into the forward GEMM)
+    // windowed metrics (exorl_agent_set_metric_window; win_sums != nullptr is the mode): views of the caller's buffer, laid out as
+    // [EXORL_N_METRICS double sums | int64 steps | pad to 256 B][qhead_chunks(B) x 6 critic partials][head_chunks(B) BC partials]
+    double* win_sums = nullptr; long long* win_steps = nullptr;
+    float *win_crit = nullptr, *win_bc = nullptr;
 };
 
 namespace exorl {
@@ -615,10 +619,29 @@ static int opt_step_critic(exorl_agent* a, hipStream_t s) {
                     nullptr, s);
 }
 
-// fused scalar-head path: whole-step call on one GPU, nobody reads the metrics, twin scalar heads
+// fused scalar-head path: whole-step call on one GPU, twin scalar heads, and nobody reads the step's metrics or they are collected in a window
+// (the kernels' metrics variants then leave per-chunk sums for metrics_window)
 static bool qfuse(const exorl_agent* a) {
-    return a->whole_step && !a->fk.on && !a->want_metrics && a->has_critic && a->critic.n_heads == 2 && a->critic.out_dim == 1 && a->cfg.hidden_dim % 4 == 0 &&
+    return a->whole_step && !a->fk.on && (!a->want_metrics || a->win_sums) && a->has_critic && a->critic.n_heads == 2 && a->critic.out_dim == 1 && a->cfg.hidden_dim % 4 == 0 &&
            (a->cfg.kind == EXORL_AGENT_TD3_BC || a->cfg.kind == EXORL_AGENT_TD3 || a->cfg.kind == EXORL_AGENT_DDPG);
+}
+// the step's metric kernels (critic_loss, actor_dmu) run: always in window mode off the fused path, else when the caller reads the metrics
+static bool step_metrics(const exorl_agent* a) { return a->win_sums ? !qfuse(a) : a->want_metrics; }
+constexpr size_t WIN_HEAD_BYTES = 256;       // the window's sums and step count
+static_assert(EXORL_N_METRICS * sizeof(double) + sizeof(long long) <= WIN_HEAD_BYTES, "the window's sums and step count fit its head");
+static size_t window_bytes(const exorl_agent_cfg& cfg) {
+    return WIN_HEAD_BYTES + sizeof(float) * (size_t)round_up(6 * (int64_t)qhead_chunks(cfg.batch) + head_chunks(cfg.batch), 64);
+}
+static int run_metrics_window(exorl_agent* a, hipStream_t s) {
+    const int B = a->cfg.batch;
+    MetricsWindowArgs w{};
+    w.fused = qfuse(a) ? 1 : 0;
+    w.crit_part = a->win_crit; w.abs_part = a->abs_part; w.bc_part = a->win_bc;
+    w.q_chunks = qhead_chunks(B); w.bc_chunks = a->cfg.kind == EXORL_AGENT_TD3_BC ? head_chunks(B) : 0;
+    w.kind = a->cfg.kind; w.act_dim = a->cfg.act_dim; w.ent_from_std = a->cfg.kind != EXORL_AGENT_CQL;
+    w.inv_bg = a->inv_bg; w.alpha = a->cfg.alpha; w.stddev = &a->state->stddev;
+    w.metrics = a->metrics; w.sums = a->win_sums; w.steps = a->win_steps;
+    return metrics_window(w, s);
 }
 static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
     const NetDesc& d = a->critic;
@@ -639,9 +662,10 @@ static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
     }
     q.dz = bf ? nullptr : a->bc.dz2; q.dzb = bf ? a->bc.dz2q.hi : nullptr; q.dzl = bf ? a->bc.dz2q.lo : nullptr; q.act = act;
     q.P = mode == 0 ? a->pc.Ph : nullptr;
-    q.abs_part = a->abs_part;
+    const bool met = mode == 0 && a->win_sums;       // the critic metrics' per-chunk sums ride in mode 0's otherwise unused abs_part
+    q.abs_part = met ? a->win_crit : a->abs_part;
     q.rows = B; q.H = H; q.mode = mode; q.inv_bg = a->inv_bg;
-    return qhead(q, s);
+    return qhead(q, s, met);
 }
 
 // -- phase 0: everything up to the critic gradients -------------------------------------------------
@@ -689,7 +713,7 @@ static int phase0(exorl_agent* a, float stddev, const float* noise_c, hipStream_
         EXORL_TRY(sf_q(a->fc.out, task, O, a->sfq, B, cfg.sf_dim, 2, s));
         qv = a->sfq; tqv = a->sftq;
     }
-    if (a->want_metrics)
+    if (step_metrics(a))
         EXORL_TRY(critic_loss(qv, tqv, a->reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));   // :133-137
     DoutSpec td{};                              // d(2 x MSE)/dQ computed where it is consumed (:127-131)
     td.mode = EXORL_DOUT_TD; td.q = qv; td.tq = tqv; td.reward = a->reward; td.discount = a->discount; td.inv_bg = a->inv_bg;
@@ -716,7 +740,7 @@ static int phase1(exorl_agent* a, float stddev, const float* noise_a, hipStream_
         return 0;
     }
     // pi(obs) sample already sits in xc_pi (phase 0); DDPG logs its log-prob (ddpg.py:276,289)
-    if ((cfg.kind == EXORL_AGENT_DDPG || cfg.kind == EXORL_AGENT_APS) && a->want_metrics)
+    if ((cfg.kind == EXORL_AGENT_DDPG || cfg.kind == EXORL_AGENT_APS) && (a->want_metrics || a->win_sums))
         EXORL_TRY(sample_action(a->fa.out + (int64_t)B * A, noise_spec(a, noise_a, 1), stddev, cfg.stddev_clip, 1, a->xc_pi + O, W, B, A,
                                 a->metrics + EXORL_M_ACTOR_LOGPROB, s, &a->state->stddev, cfg.world_size));
     const bool qf = qfuse(a);
@@ -757,7 +781,7 @@ static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
     const FwdBufs f = a->fa.rows_from(B, H, A);
     if (!a->has_critic)       // BC (bc.py:82): the only forward of the step
         EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa + (int64_t)B * O, O, B, f, true, true, prec, s));
-    if (a->want_metrics)                        // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
+    if (step_metrics(a))                        // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
         EXORL_TRY(actor_dmu(a->da, A, a->has_critic ? a->critic.n_trunks : 0, (int64_t)B * A, f.out, a->action,
                             a->has_critic ? nullptr : a->reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A, a->inv_bg, cfg.alpha,
                             cfg.kind, stddev, s, &a->state->stddev));
@@ -770,6 +794,7 @@ static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
             EXORL_CHECK_HIP(hipStreamWaitEvent(s, a->ev_stats_done, 0));
             dm.lam_parts = a->stats; dm.lam_chunks = 1;
         }
+        if (a->win_sums && cfg.kind == EXORL_AGENT_TD3_BC) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
     }
     EXORL_TRY(net_backward(a->actor, Pa, a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa, a->xa + (int64_t)B * O, O, B, f,
                            dm, a->ba, nullptr, 0, 0, prec, s, a->fk, a->fuse_opt ? &a->pend_a : nullptr));
@@ -1058,6 +1083,7 @@ static int whole_step_body(exorl_agent* a, float stddev, const float* noise_c, c
     if (rc == 0) rc = exorl_agent_update_phase(a, 2, stddev, noise_c, noise_a, s);
     if (rc == 0 && dp) rc = comm_allreduce_sum(a->comm, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->actor.total, s);
     if (rc == 0) rc = exorl_agent_update_phase(a, 3, stddev, noise_c, noise_a, s);
+    if (rc == 0 && a->win_sums) rc = run_metrics_window(a, s);      // the step's metrics into the window (and, on the fused path, into a->metrics)
     return rc;
 }
 
@@ -1310,6 +1336,44 @@ int exorl_agent_set_metrics(exorl_agent_t* a, int32_t enable) {
     EXORL_REQUIRE(a, "agent_set_metrics: null handle");
     EXORL_REQUIRE(!a->graph_exec, "agent_set_metrics: disable the captured graph first");
     a->want_metrics = enable != 0;
+    return 0;
+}
+
+size_t exorl_agent_metric_window_bytes(const exorl_agent_cfg* cfg) {
+    exorl_agent tmp;
+    if (describe(&tmp, cfg) != 0) return 0;
+    return window_bytes(*cfg);
+}
+
+int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes) {
+    EXORL_REQUIRE(a, "agent_set_metric_window: null handle");
+    EXORL_REQUIRE(!a->graph_exec, "agent_set_metric_window: disable the captured graph first");
+    if (!buf_dev) {
+        a->win_sums = nullptr; a->win_steps = nullptr; a->win_crit = a->win_bc = nullptr;
+        return 0;
+    }
+    EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
+                  "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
+    const size_t need = window_bytes(a->cfg);
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_metric_window: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
+    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));      // an empty window; the partials behind it are written before they are read
+    a->win_sums = static_cast<double*>(buf_dev);
+    a->win_steps = reinterpret_cast<long long*>(a->win_sums + EXORL_N_METRICS);
+    a->win_crit = reinterpret_cast<float*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
+    a->win_bc = a->win_crit + 6 * (int64_t)qhead_chunks(a->cfg.batch);
+    return 0;
+}
+
+int exorl_agent_metric_window_read(exorl_agent_t* a, double* sums_host, int64_t* steps_host, int32_t reset, void* stream) {
+    EXORL_REQUIRE(a && sums_host && steps_host, "agent_metric_window_read: null argument");
+    EXORL_REQUIRE(a->win_sums, "agent_metric_window_read: no metric window (exorl_agent_set_metric_window)");
+    hipStream_t s = as_stream(stream);
+    struct { double sums[EXORL_N_METRICS]; long long steps; } host;
+    EXORL_CHECK_HIP(hipMemcpyAsync(&host, a->win_sums, sizeof(host), hipMemcpyDeviceToHost, s));
+    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(a->win_sums, 0, sizeof(host), s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < EXORL_N_METRICS; ++i) sums_host[i] = host.sums[i];
+    *steps_host = host.steps;
     return 0;
 }
 

@@ -1000,7 +1000,8 @@ __device__ __forceinline__ float dout_value(const DoutSpec& d, int net, int m, i
     return dmu * (1.0f - mv * mv);
 }
 
-template <int NO>
+// MET (windowed metrics, TD3+BC's ACTOR_MU, one net): the chunk's sum of (mu - a_data)^2 goes to dspec.bc_part[chunk]
+template <int NO, bool MET = false>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, const float* __restrict__ W,
                                                        const float* __restrict__ a, float* __restrict__ dz,
                                                        unsigned short* __restrict__ dzb, float* __restrict__ P, int rows,
@@ -1058,6 +1059,16 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
         }
         ds[threadIdx.x] = dv;
     }
+    if constexpr (MET) {          // waves 0 and 1 hold the chunk's HB_ROWS x 16 elements: one wave sum each, added by thread 0
+        __shared__ float bc_s[2];
+        if (threadIdx.x < HB_ROWS * 16) {
+            const float d = dlive ? mu_v - ad_v : 0.f;
+            const float sq = wave_sum(d * d);
+            if ((threadIdx.x & 63) == 0) bc_s[threadIdx.x >> 6] = sq;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) dspec.bc_part[blockIdx.x] = bc_s[0] + bc_s[1];
+    }
     __syncthreads();
     const int64_t nh = (int64_t)(nout + 1) * H + 16;
     float* Pn = P ? P + ((int64_t)net * gridDim.x + blockIdx.x) * nh : nullptr;
@@ -1097,11 +1108,17 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
 }
 
 int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, const Planes& dzq, float* P, int rows,
-             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s) {
+             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, bool metrics) {
     unsigned short *dz_bf16 = dzq.hi, *dz_lo = dzq.lo;
     EXORL_REQUIRE(nout >= 1 && nout <= 16 && H % 4 == 0 && H <= 1024, "head_bwd: nout=%d H=%d unsupported", nout, H);
     dim3 grid(cdiv(rows, HB_ROWS), nets);
-    if (nout == 1) hipLaunchKernelGGL((head_bwd_kernel<1>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
+    if (metrics) {
+        EXORL_REQUIRE(dspec.mode == EXORL_DOUT_ACTOR_MU && dspec.kind == EXORL_AGENT_TD3_BC && nets == 1 && dspec.bc_part,
+                      "head_bwd: the metrics variant is TD3+BC's actor gradient on one net");
+        if (nout == 1) hipLaunchKernelGGL((head_bwd_kernel<1, true>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
+        else if (nout <= 8) hipLaunchKernelGGL((head_bwd_kernel<8, true>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
+        else hipLaunchKernelGGL((head_bwd_kernel<16, true>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
+    } else if (nout == 1) hipLaunchKernelGGL((head_bwd_kernel<1>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
     else if (nout <= 8) hipLaunchKernelGGL((head_bwd_kernel<8>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
     else hipLaunchKernelGGL((head_bwd_kernel<16>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
     EXORL_LAUNCH_CHECK();
@@ -1181,10 +1198,12 @@ constexpr int QH_ROWS = 4;      // rows per workgroup: 256 workgroups at B = 102
 // columns of both critic nets; the h2 rows read for the dot products stay in registers for the dz2 pass.
 // TP (mode 0): the target critic's two Q values arrive as per-row partial dots from the forward GEMM's epilogue (QHeadArgs::tpart, Gemm16Problem::
 // head_part) — its hidden activations were never written: 8 MB less stored by the GEMM and 8 MB less read here at H = B = 1024
-template <int MODE, bool TP>
+// MET (mode 0, windowed metrics): the chunk's sums of r, y, q1, q2, (q1 - y)^2, (q2 - y)^2 go to abs_part[6 chunk ..], which mode 0 leaves alone otherwise
+template <int MODE, bool TP, bool MET = false>
 __global__ __launch_bounds__(256) void qhead_kernel(const QHeadArgs g) {
     __shared__ float part[4][4 * QH_ROWS];      // [wave][net * QH_ROWS + r]
     __shared__ float dq[2 * QH_ROWS];
+    __shared__ float met[6 * QH_ROWS];           // MET: per-row terms of the six sums, [quantity][row]
     const int row0 = blockIdx.x * QH_ROWS;
     const int c4 = threadIdx.x, H = g.H, H4 = H >> 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1246,18 +1265,25 @@ __global__ __launch_bounds__(256) void qhead_kernel(const QHeadArgs g) {
     __syncthreads();
     if (threadIdx.x < 2 * QH_ROWS) {
         const int n = threadIdx.x / QH_ROWS, r = threadIdx.x % QH_ROWS;
-        float d = 0.f;
+        float d = 0.f, m_r = 0.f, m_y = 0.f, m_q = 0.f, m_e = 0.f;
         if (r < nr) {
             const float q1 = part[0][r], q2 = part[0][QH_ROWS + r];
             if (MODE == 0) {
-                const float y = g.reward[row0 + r] + g.discount[row0 + r] * fminf(part[0][2 * QH_ROWS + r], part[0][3 * QH_ROWS + r]);
+                const float rw = g.reward[row0 + r];
+                const float y = rw + g.discount[row0 + r] * fminf(part[0][2 * QH_ROWS + r], part[0][3 * QH_ROWS + r]);
                 d = 2.0f * ((n == 0 ? q1 : q2) - y) * g.inv_bg;
+                m_r = rw; m_y = y; m_q = n == 0 ? q1 : q2; m_e = (m_q - y) * (m_q - y);
             } else {
                 const float w1 = q1 < q2 ? 1.0f : (q1 == q2 ? 0.5f : 0.0f);
                 d = -g.inv_bg * (n == 0 ? w1 : 1.0f - w1);
             }
         }
         dq[threadIdx.x] = d;
+        if (MODE == 0 && MET) {                  // the threads that formed dq hold r, y and their net's q: rows past nr leave zeros
+            if (n == 0) { met[r] = m_r; met[QH_ROWS + r] = m_y; }
+            met[(2 + n) * QH_ROWS + r] = m_q;
+            met[(4 + n) * QH_ROWS + r] = m_e;
+        }
     }
     if (MODE == 1 && threadIdx.x == 0) {
         float sa = 0.f, sm = 0.f;
@@ -1266,6 +1292,11 @@ __global__ __launch_bounds__(256) void qhead_kernel(const QHeadArgs g) {
         g.abs_part[2 * blockIdx.x + 1] = sm;
     }
     __syncthreads();
+    if (MODE == 0 && MET && threadIdx.x < 6) {   // thread k: quantity k of the chunk, rows in order
+        float sk = 0.f;
+        for (int r = 0; r < QH_ROWS; ++r) sk += met[threadIdx.x * QH_ROWS + r];
+        g.abs_part[6 * blockIdx.x + threadIdx.x] = sk;
+    }
     const int64_t nh = 2 * (int64_t)H + 16;
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
@@ -1301,9 +1332,11 @@ __global__ __launch_bounds__(256) void qhead_kernel(const QHeadArgs g) {
 
 int qhead_chunks(int rows) { return cdiv(rows, QH_ROWS); }
 
-int qhead(const QHeadArgs& q, hipStream_t s) {
+int qhead(const QHeadArgs& q, hipStream_t s, bool metrics) {
     EXORL_REQUIRE(q.H % 4 == 0 && q.H <= 1024 && q.rows > 0 && (q.mode == 0 || q.mode == 1), "qhead: unsupported H=%d rows=%d", q.H, q.rows);
-    if (q.mode == 0 && q.tpart[0]) hipLaunchKernelGGL((qhead_kernel<0, true>), dim3(cdiv(q.rows, QH_ROWS)), dim3(256), 0, s, q);
+    if (q.mode == 0 && metrics && q.tpart[0]) hipLaunchKernelGGL((qhead_kernel<0, true, true>), dim3(cdiv(q.rows, QH_ROWS)), dim3(256), 0, s, q);
+    else if (q.mode == 0 && metrics) hipLaunchKernelGGL((qhead_kernel<0, false, true>), dim3(cdiv(q.rows, QH_ROWS)), dim3(256), 0, s, q);
+    else if (q.mode == 0 && q.tpart[0]) hipLaunchKernelGGL((qhead_kernel<0, true>), dim3(cdiv(q.rows, QH_ROWS)), dim3(256), 0, s, q);
     else if (q.mode == 0) hipLaunchKernelGGL((qhead_kernel<0, false>), dim3(cdiv(q.rows, QH_ROWS)), dim3(256), 0, s, q);
     else hipLaunchKernelGGL((qhead_kernel<1, false>), dim3(cdiv(q.rows, QH_ROWS)), dim3(256), 0, s, q);
     EXORL_LAUNCH_CHECK();
@@ -1312,38 +1345,7 @@ int qhead(const QHeadArgs& q, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------------
 // finalize: sums the per-chunk partials in chunk order and scatters into the flat gradient buffer.
-// sum of n partials spaced `stride` apart, 16 loads in flight
-__device__ __forceinline__ float chunk_sum(const float* __restrict__ p, int n, int64_t stride) {
-    float acc = 0.f;
-    int ch = 0;
-    if (n > 1024) {          // thousands of partials (8192 rows and more): sub-sums of 32 added to a second accumulator. One running float32 sum
-        for (; ch + 32 <= n; ch += 32) {        // of n terms drifts by about sqrt(n) ulp of the total: 2050 qhead partials at B = 8200 left
-            float t[32], sub = 0.f;             // a bias gradient 1.1e-6 off its float64 value, where the float32 reference is 4e-8 off
-#pragma unroll
-            for (int q = 0; q < 32; ++q) t[q] = p[(int64_t)(ch + q) * stride];
-#pragma unroll
-            for (int q = 0; q < 32; ++q) sub += t[q];
-            acc += sub;
-        }
-    }
-    for (; ch + 32 <= n; ch += 32) {            // 32 in flight: the 256 qhead chunks are 8 dependent rounds instead of 16 (same order of adds)
-        float t[32];
-#pragma unroll
-        for (int q = 0; q < 32; ++q) t[q] = p[(int64_t)(ch + q) * stride];
-#pragma unroll
-        for (int q = 0; q < 32; ++q) acc += t[q];
-    }
-    for (; ch + 16 <= n; ch += 16) {
-        float t[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) t[q] = p[(int64_t)(ch + q) * stride];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc += t[q];
-    }
-    for (; ch < n; ++ch) acc += p[(int64_t)ch * stride];
-    return acc;
-}
-
+// (chunk_sum, kernels.h: n partials spaced `stride` apart, in chunk order)
 __global__ __launch_bounds__(256) void finalize_grads_kernel(FinalizeArgs f) {
     const int H = f.H;
     const int64_t nh = (int64_t)(f.nout + 1) * H + (f.nout > 16 ? 32 : 16);   // head elements per net (head_bwd[_wide]_kernel)

@@ -153,7 +153,12 @@ int head_fwd4(const float* a, const float* W, const float* b, float* out, int ro
 #define EXORL_DOUT_ACTOR_MU 3   /* (sum_t da_t + bc term) * (1 - mu^2)  /  BC: -(a-mu)/std^2*inv_bg td3_bc.py:155, bc.py:83 */
 struct DoutSpec {
     int mode;
-    const float* buf;        // BUFFER: (nets, rows, nout)
+    union {
+        const float* buf;    // BUFFER: (nets, rows, nout)
+        // `buf` must stay null in ACTOR_MU mode: there a non-null value is bc_part and selects head_bwd's metrics variant (net_backward),
+        // which writes through it
+        float* bc_part;      // ACTOR_MU, TD3+BC, metrics variant (head_bwd's `metrics`): per-chunk sum (mu - a_data)^2 out, head_chunks(rows) floats
+    };
     const float *q, *tq, *reward, *discount;   // TD / ACTOR_Q: q, tq are (2, rows)
     const float* stats;      // ACTOR_Q: stats[0] = sum |Q| over the global batch
     const float *da, *mu, *a_data;             // ACTOR_MU: da (da_nets, rows, nout), mu / a_data (rows, nout)
@@ -172,8 +177,9 @@ struct DoutSpec {
     const float* stddev_ptr;   // BC / CRR: device-resident std (StepState::stddev); null -> `stddev`
 };
 // dz (fp32) and / or dzq (hi, or hi + lo) receive the gradient at the hidden layer: whichever is non-null
+// metrics: ACTOR_MU of TD3+BC also leaves per-chunk sums of (mu - a_data)^2 in dspec.bc_part (one net)
 int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, const Planes& dzq, float* P, int rows,
-             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s);
+             int H, int nout, int nets, int64_t astride, int64_t pstride, int want_params, hipStream_t s, bool metrics = false);
 int head_chunks(int rows);
 int tune_variant();      // exorl_gemm_tune's bits (0 = defaults): the reference paths below, each read at one decision point
 constexpr int TUNE_CONV_WGRAD_TILE = 64;             // 32 -> 32 conv weight gradient on the tile kernel, not conv_wgrad_ws_kernel
@@ -194,14 +200,48 @@ struct QHeadArgs {
     const float *reward, *discount;
     float* dz; unsigned short* dzb; unsigned short* dzl; int64_t act;     // dzl: lo plane (split-bf16) or null
     float* P;                // head partials [net][chunk][(1+1)H + 16] or null
-    float* abs_part;         // [chunk][2]
+    float* abs_part;         // mode 1: [chunk][2]; mode 0 with `metrics`: [chunk][6] = sum r, y, q1, q2, (q1 - y)^2, (q2 - y)^2 (y = r + D min(Q1', Q2'))
     const float* tpart[2];   // mode 0, folded target heads: per row `tslots` partial dots of target net 0 / 1 (gemm16 head_part) instead of a[2], a[3]
     int tslots;
     int rows, H, mode;
     float inv_bg;
 };
-int qhead(const QHeadArgs& q, hipStream_t s);
+// metrics (windowed metrics on the fused path): mode 0 also leaves the critic metrics' per-chunk sums in abs_part
+int qhead(const QHeadArgs& q, hipStream_t s, bool metrics = false);
 int qhead_chunks(int rows);     // partial rows qhead writes per net (finer than head_chunks)
+// Per-chunk partials are summed in chunk order by one thread per element (finalize_grads, finalize_adam, metrics_window).
+// sum of n partials spaced `stride` apart, 16 loads in flight
+__device__ __forceinline__ float chunk_sum(const float* __restrict__ p, int n, int64_t stride) {
+    float acc = 0.f;
+    int ch = 0;
+    if (n > 1024) {          // thousands of partials (8192 rows and more): sub-sums of 32 added to a second accumulator. One running float32 sum
+        for (; ch + 32 <= n; ch += 32) {        // of n terms drifts by about sqrt(n) ulp of the total: 2050 qhead partials at B = 8200 left
+            float t[32], sub = 0.f;             // a bias gradient 1.1e-6 off its float64 value, where the float32 reference is 4e-8 off
+#pragma unroll
+            for (int q = 0; q < 32; ++q) t[q] = p[(int64_t)(ch + q) * stride];
+#pragma unroll
+            for (int q = 0; q < 32; ++q) sub += t[q];
+            acc += sub;
+        }
+    }
+    for (; ch + 32 <= n; ch += 32) {            // 32 in flight: the 256 qhead chunks are 8 dependent rounds instead of 16 (same order of adds)
+        float t[32];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) t[q] = p[(int64_t)(ch + q) * stride];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) acc += t[q];
+    }
+    for (; ch + 16 <= n; ch += 16) {
+        float t[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) t[q] = p[(int64_t)(ch + q) * stride];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc += t[q];
+    }
+    for (; ch < n; ++ch) acc += p[(int64_t)ch * stride];
+    return acc;
+}
+
 struct FinalizeArgs {
     const float* Ph; int head_chunks; int n_heads; int64_t head_stride;    // head partials; stride between heads in G
     int64_t gW2, gb1, gb2;                                                 // offsets of head 0's tensors in G
@@ -325,6 +365,18 @@ int trunk_one(const float* x, const float* meta, const float* W, const float* b,
 // out[0] = sum_i parts[2i], out[1] = sum_i parts[2i+1] in a fixed order (qhead's per-chunk [sum |min Q|, sum min Q] -> the 4-float
 // statistics buffer that is all-reduced under data parallelism)
 int reduce_pairs(const float* parts, int chunks, float* out, hipStream_t s);
+// End-of-step kernel of the windowed metrics (loss.hip, metrics_window_kernel)
+struct MetricsWindowArgs {
+    const float *crit_part, *abs_part, *bc_part;   // fused: qhead mode 0's [chunk][6], mode 1's [chunk][2], head_bwd's [chunk] (TD3+BC)
+    int q_chunks, bc_chunks;                       // qhead_chunks(B); head_chunks(B), or 0 when the kind has no BC term
+    int fused;                                     // 1: form the step's metrics from the partials; 0: the step's metric kernels wrote them
+    int kind, act_dim, ent_from_std;
+    float inv_bg, alpha;
+    const float* stddev;                           // StepState::stddev
+    float* metrics;                                // EXORL_N_METRICS slots (EXORL_M_*)
+    double* sums; long long* steps;                // the window: EXORL_N_METRICS sums, one step count
+};
+int metrics_window(const MetricsWindowArgs& w, hipStream_t s);
 int set_device_float(float* dst, float value, hipStream_t s);
 int set_device_u64(uint64_t* dst, uint64_t value, hipStream_t s);
 

@@ -609,6 +609,65 @@ int actor_dmu(const float* da, int64_t da_ld, int da_nets, int64_t da_net_stride
     return 0;
 }
 
+// ---- windowed metrics (exorl_agent_set_metric_window): the last kernel of a step, one wave. In the captured single-chain graph it is the last
+// node, so its serial work (one thread per quantity over the chunk partials, 32 loads in flight) adds to the step: DESIGN §4 has the measured cost.
+// fused: the step ran the fused scalar-head kernels, whose metrics variants left per-chunk sums behind (qhead mode 0: r, y, q1, q2, (q1 - y)^2,
+// (q2 - y)^2; qhead mode 1: |min Q|, min Q; TD3+BC's head_bwd: (mu - a)^2). Threads 0..8 sum one quantity each in chunk order (chunk_sum), thread 0
+// forms the metrics as the reference defines them (td3_bc.py:131-137, 154-155, 176; td3.py, ddpg.py:240-292) — the arithmetic of critic_loss_kernel
+// and actor_dmu_kernel. Otherwise the step's own metric kernels have filled `metrics`.
+// Both: actor_ent from the device-resident std (a moving stddev_schedule is averaged without the host); then thread i < EXORL_N_METRICS adds slot
+// i to the window's double sum and thread EXORL_N_METRICS counts the step. One thread owns each slot: no atomics. Loads are unconditional
+// (indices clamped); a quantity that does not exist for the kind has zero chunks.
+static_assert(EXORL_N_METRICS < 64, "metrics_window_kernel: thread EXORL_N_METRICS of the one wave counts the step");
+__global__ __launch_bounds__(64) void metrics_window_kernel(const MetricsWindowArgs w) {
+    __shared__ float tot[9];
+    __shared__ float m[EXORL_N_METRICS];
+    const int t = threadIdx.x;
+    const float old = w.metrics[t < EXORL_N_METRICS ? t : 0];
+    const float sd = *w.stddev;
+    if (w.fused) {
+        const int k = t < 9 ? t : 8;          // surplus lanes: a clamped pointer and zero chunks
+        const float* p = k < 6 ? w.crit_part + k : (k < 8 ? w.abs_part + (k - 6) : w.bc_part);
+        const float sum = chunk_sum(p, t >= 9 ? 0 : (k < 8 ? w.q_chunks : w.bc_chunks), k < 6 ? 6 : (k < 8 ? 2 : 1));
+        if (t < 9) tot[t] = sum;
+    }
+    if (t < EXORL_N_METRICS) m[t] = old;
+    __syncthreads();
+    if (t == 0) {
+        if (w.fused) {
+            m[EXORL_M_BATCH_REWARD] = tot[0] * w.inv_bg;
+            m[EXORL_M_CRITIC_TARGET_Q] = tot[1] * w.inv_bg;
+            m[EXORL_M_CRITIC_Q1] = tot[2] * w.inv_bg;
+            m[EXORL_M_CRITIC_Q2] = tot[3] * w.inv_bg;
+            m[EXORL_M_CRITIC_LOSS] = (tot[4] + tot[5]) * w.inv_bg;
+            m[EXORL_M_Q_ABS_SUM] = tot[6];
+            m[EXORL_M_Q_SUM] = tot[7];
+            if (w.kind == EXORL_AGENT_TD3_BC) {
+                const float lambda = w.alpha / (tot[6] * w.inv_bg);
+                m[EXORL_M_ACTOR_LOSS] = -lambda * tot[7] * w.inv_bg + tot[8] * w.inv_bg / (float)w.act_dim;
+                m[EXORL_M_BC_SUM] = tot[8];
+            } else {
+                m[EXORL_M_ACTOR_LOSS] = -tot[7] * w.inv_bg;
+            }
+        }
+        // TruncatedNormal inherits Normal.entropy: 0.5 + 0.5 log(2 pi) + log(std), summed over the action dims (CQL writes its own)
+        if (w.ent_from_std) m[EXORL_M_ACTOR_ENT] = (1.4189385332046727f + logf(sd)) * (float)w.act_dim;
+    }
+    __syncthreads();
+    if (t < EXORL_N_METRICS) {
+        const float v = m[t];
+        w.metrics[t] = v;
+        w.sums[t] += (double)v;
+    }
+    if (t == EXORL_N_METRICS) *w.steps += 1;
+}
+
+int metrics_window(const MetricsWindowArgs& w, hipStream_t s) {
+    hipLaunchKernelGGL(metrics_window_kernel, dim3(1), dim3(64), 0, s, w);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace exorl
 
 extern "C" int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float* out_dev, void* stream) {

@@ -247,6 +247,28 @@ class AgentEngine(_Phased):
     def set_metrics(self, enable):
         L.check(self.lib.exorl_agent_set_metrics(self.h, int(bool(enable))))
 
+    def metric_window_bytes(self):
+        return int(self.lib.exorl_agent_metric_window_bytes(C.byref(self.cfg)))
+
+    def set_metric_window(self, buf=True):
+        """Windowed metrics (exorl_agent_set_metric_window) on a torch-owned buffer: True allocates one, a uint8 tensor of at least
+        metric_window_bytes() is taken as it is (its contents do not matter), None switches the mode off."""
+        if buf is None:
+            L.check(self.lib.exorl_agent_set_metric_window(self.h, None, 0))
+            self._window = None
+            return
+        if buf is True:
+            buf = torch.empty(self.metric_window_bytes(), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
+        L.check(self.lib.exorl_agent_set_metric_window(self.h, buf.data_ptr(), buf.numel()))
+        self._window = buf
+
+    def metric_window_read(self, reset=True):
+        """(sums, steps) of the window: float64 sums per metric slot and the number of steps in them; reset empties the window."""
+        sums, steps = np.zeros(L.N_METRICS, np.float64), C.c_int64()
+        L.check(self.lib.exorl_agent_metric_window_read(self.h, sums.ctypes.data, C.byref(steps), int(bool(reset)), L.current_stream()))
+        return sums, int(steps.value)
+
     def cql_alpha_state(self):
         host = np.zeros(6, np.float32)
         L.check(self.lib.exorl_agent_cql_alpha(self.h, host.ctypes.data, 0))

@@ -12,14 +12,19 @@ from .replay_buffer import make_replay_loader
 
 
 def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, replay_buffer_size=10**7, eval_every_steps=10000,
-                  log_every_steps=1000, eval_fn=None, log_fn=None, env=None, sampler='philox', use_graph=True, start_step=0):
+                  log_every_steps=1000, eval_fn=None, log_fn=None, env=None, sampler='philox', use_graph=True, start_step=0,
+                  metric_window=False):
     """train_offline.py:90-123. Returns the list of (step, metrics) rows that were logged.
 
     eval_fn(step, agent): called every eval_every_steps (train_offline.py:108-112).
     log_fn(step, metrics): called with the agent's metrics (only non-empty when the agent was built with use_tb=True)
-    plus fps / total_time every log_every_steps (train_offline.py:114-121)."""
+    plus fps / total_time every log_every_steps (train_offline.py:114-121).
+    metric_window=True: the metrics are collected on the device (agent.enable_metric_window(), whatever use_tb says) and every logged row
+    carries agent.pop_metrics(): the means over the steps since the previous row, which is what the reference's averaging meters write.
+    An agent without the window (enable_metric_window() returns False) logs its per-step metrics as before."""
     loader = make_replay_loader(env, replay_dir, replay_buffer_size, batch_size, 0, discount, sampler=sampler)
     replay_iter = iter(loader)
+    windowed = bool(metric_window) and hasattr(agent, 'enable_metric_window') and agent.enable_metric_window()      # before the capture
     if use_graph and hasattr(agent, 'enable_graph'):
         agent.enable_graph(replay_iter, start_step)      # False (and eager launches) when the pairing cannot be captured
     import torch
@@ -32,6 +37,8 @@ def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, repla
         if log_every_steps and global_step % log_every_steps == 0:
             torch.cuda.synchronize()
             now = time.time()
+            if windowed:
+                metrics = agent.pop_metrics()
             row = dict(metrics, fps=log_every_steps / max(now - t_last, 1e-9), total_time=now - t_start, step=global_step)
             t_last = now
             rows.append((global_step, row))

@@ -255,6 +255,18 @@ int exorl_agent_metrics(exorl_agent_t* a, float* metrics_host, void* stream);
 /* The reference computes its metrics dict only under use_tb (td3_bc.py:133,162,175); enable = 0 skips the metric
  * reductions of the step (default: enabled). */
 int exorl_agent_set_metrics(exorl_agent_t* a, int32_t enable);
+/* Windowed metrics: every whole step (exorl_agent_update, exorl_agent_step_graph) ends in one kernel that writes the step's metrics to the
+ * EXORL_M_* slots (exorl_agent_metrics still returns the last step's) and adds each slot to a window of double sums with an int64 step count,
+ * all in device memory: nothing is copied to the host until the window is read. TD3+BC, TD3 and DDPG then stay on the fused scalar-head path,
+ * whose kernels leave the metrics' per-chunk sums behind; the other kinds run the metric kernels they run under exorl_agent_set_metrics(1).
+ * The buffer is the caller's: exorl_agent_metric_window_bytes(cfg) bytes of device memory, 256-byte aligned, alive while it is set; NULL
+ * switches the mode off. Refused while a graph is captured (set the window first: the capture then holds its kernels) and for
+ * world_size > 1. */
+size_t exorl_agent_metric_window_bytes(const exorl_agent_cfg* cfg);
+int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes);
+/* Synchronous: sums_host[EXORL_N_METRICS] and *steps_host = the window since the last reset (mean of slot i = sums_host[i] / *steps_host).
+ * One copy and, with reset != 0, one hipMemsetAsync, both enqueued on `stream`: they order against the graph replays on it. */
+int exorl_agent_metric_window_read(exorl_agent_t* a, double* sums_host, int64_t* steps_host, int32_t reset, void* stream);
 /* Captured graphs run independent parts of the step (target || critic forward, wgrad || dgrad chain) as parallel
  * branches on a second stream (default: off — one chain measured faster on MI355X). */
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable);

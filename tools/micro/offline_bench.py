@@ -4,6 +4,9 @@
     python tools/micro/offline_bench.py td3 17 6 512              # configs[4]: TD3 cheetah_run, the per-GPU share of batch 4096 on 8 GPUs
     python tools/micro/offline_bench.py cql 78 12 1024 bf16x3 --roofline     # + a roofline JSON line for the dominant kernel (HIP events per GEMM launch)
     python tools/micro/offline_bench.py cql 78 12 1024 bf16x3 --eager        # eager launches (for rocprofv3 --kernel-trace + tools/prof_summary.py)
+    python tools/micro/offline_bench.py td3_bc 24 6 1024 bf16x3 --metrics window --steps 2000 --warmup 200 --repeats 3
+        # --metrics off (default): use_tb=False; step: use_tb=True, every update() reads its metrics; window: enable_metric_window(),
+        # pop_metrics() every 1000 steps. --hidden H (default 1024). One line per repeat, then the median.
 """
 import json
 import sys
@@ -22,19 +25,28 @@ from exorl_amd.replay_buffer import ArenaIterator
 kind, O, A, B = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 precisions = (sys.argv[5] if len(sys.argv) > 5 and not sys.argv[5].startswith('--') else 'fp32,bf16x3,bf16').split(',')
 ROOFLINE, EAGER = '--roofline' in sys.argv, '--eager' in sys.argv
-H, EPISODES, EP_LEN = 1024, 300, 1000
+
+
+def option(name, default):
+    return type(default)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+METRICS, STEPS, WARMUP, REPEATS = option('--metrics', 'off'), option('--steps', 0), option('--warmup', -1), option('--repeats', 1)
+assert METRICS in ('off', 'step', 'window'), METRICS
+TB = METRICS == 'step'
+H, EPISODES, EP_LEN = option('--hidden', 1024), 300, 1000
 
 
 def make(precision):
     if kind == 'cql':
-        return agents.CQLAgent('cql', (O,), (A,), 'cuda', 1e-4, H, 0.01, 1, B, False, 0.01, 3, 5.0, False, precision=precision)
+        return agents.CQLAgent('cql', (O,), (A,), 'cuda', 1e-4, H, 0.01, 1, B, TB, 0.01, 3, 5.0, False, precision=precision)
     if kind == 'td3':
-        return agents.TD3Agent('td3', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, False, precision=precision)
+        return agents.TD3Agent('td3', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, TB, precision=precision)
     if kind == 'crr':
-        return agents.CRRAgent('crr', (O,), (A,), 'cuda', 1e-4, H, 0.01, 10, 'indicator', 0.2, 1, B, 0.3, False, precision=precision)
+        return agents.CRRAgent('crr', (O,), (A,), 'cuda', 1e-4, H, 0.01, 10, 'indicator', 0.2, 1, B, 0.3, TB, precision=precision)
     if kind == 'bc':
-        return agents.BCAgent('bc', (O,), (A,), 'cuda', 1e-4, H, B, 0.2, False, precision=precision)
-    return agents.TD3BCAgent('td3_bc', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, False, 2.5, precision=precision)
+        return agents.BCAgent('bc', (O,), (A,), 'cuda', 1e-4, H, B, 0.2, TB, precision=precision)
+    return agents.TD3BCAgent('td3_bc', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, TB, 2.5, precision=precision)
 
 
 eng = ReplayEngine((O,), np.float32, A, 0, EPISODES * (EP_LEN + 1) + 64, EPISODES + 8, 'cuda')
@@ -51,17 +63,31 @@ for prec in precisions:
     eng.seed_philox(2)
     ag = make(prec)
     it = ArenaIterator(eng, B, 1, 0.99, 'philox')
+    if METRICS == 'window':
+        assert ag.enable_metric_window()
     graph = False if EAGER else ag.enable_graph(it)
     n, w = (100, 20) if EAGER else (500, 50)
-    for i in range(w):
-        ag.update(it, i)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(n):
-        ag.update(it, w + i)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f'{kind} O={O} A={A} B={B} {prec:7s} graph={graph}: {n / dt:8.1f} update()/s  {1e3 * dt / n:7.3f} ms', flush=True)
+    n, w = STEPS or n, (WARMUP if WARMUP >= 0 else w)
+    rates, done = [], 0
+    for _ in range(REPEATS):
+        for i in range(w):
+            ag.update(it, done + i)
+        if METRICS == 'window':
+            ag.pop_metrics()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n):
+            ag.update(it, done + w + i)
+            if METRICS == 'window' and (i + 1) % 1000 == 0:
+                ag.pop_metrics()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        done += w + n
+        rates.append(n / dt)
+        print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} graph={graph} metrics={METRICS}: {n / dt:8.1f} update()/s  {1e3 * dt / n:7.3f} ms', flush=True)
+    if REPEATS > 1:
+        print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} metrics={METRICS}: median {float(np.median(rates)):8.1f} update()/s, min {min(rates):.1f}, '
+              f'max {max(rates):.1f} over {REPEATS} repeats of {n} steps', flush=True)
     if ROOFLINE:
         # the dominant kernel's launches bracketed by HIP events on the stream they run on (an instrumented eager pass of the same loop,
         # as bench.py does for the headline): algorithmic FLOPs = 2 M N K per problem, the 0.7 x event-bracket calibration of bench.py
@@ -71,7 +97,7 @@ for prec in precisions:
         L.check(lib.exorl_profile_gemm(1))
         nprof = 20
         for i in range(nprof):
-            ag.update(it, w + n + i)
+            ag.update(it, done + i)
         cap = 1 << 15
         fl, ms, cnt = np.zeros(cap, np.float64), np.zeros(cap, np.float32), L.C.c_int32()
         L.check(lib.exorl_profile_gemm_read(fl.ctypes.data, ms.ctypes.data, cap, L.C.byref(cnt)))
