@@ -938,16 +938,6 @@ __global__ __launch_bounds__(1024) void smm_reward_kernel(const float* __restric
 
 static int grid_for(int64_t n) { const int64_t b = (n + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
 
-int mlp_forward(const Mlp& m, const float* P, const float* x, int64_t ldx, int rows, int prec, hipStream_t s) {
-    const int n = (int)m.L.size();
-    for (int l = 0; l < n; ++l) {
-        const Lin& L = m.L[l];
-        GemmProblem p{l ? m.act[l - 1] : x, P + L.W, m.act[l], P + L.b, rows, L.out, L.in, l ? (int64_t)L.in : ldx, L.in, L.out};
-        EXORL_TRY(gemm_grouped(prec, 0, 0, &p, 1, l < n - 1 || m.relu_last, false, s));
-    }
-    return 0;
-}
-
 // n nets of identical shape on the same input (an ensemble): each layer's GEMMs of all nets share one grouped launch
 int mlp_forward_many(const Mlp* nets, int n, const float* P, const float* x, int64_t ldx, int rows, int prec, hipStream_t s) {
     EXORL_REQUIRE(n >= 1 && n <= 16, "mlp_forward_many: %d nets", n);
@@ -973,7 +963,7 @@ int mlp_backward_many(const Mlp* nets, int n, const float* P, float* G, const fl
             float* d = nets[m].dact[l];
             bool summed = false;
             if (l < nl - 1 || nets[m].relu_last) {
-                summed = relu_bwd_colsum(d, nets[m].act[l], G + L.b, rows, L.out, s) == 0;
+                summed = relu_bwd_colsum(d, nets[m].act[l], G + L.b, rows, L.out, s) == 0;      // mask and bias gradient in one pass over dZ
                 if (!summed) {
                     const int64_t cnt = (int64_t)rows * L.out;
                     hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(cnt)), dim3(256), 0, s, d, nets[m].act[l], cnt);
@@ -981,8 +971,8 @@ int mlp_backward_many(const Mlp* nets, int n, const float* P, float* G, const fl
                 }
             }
             if (!summed) EXORL_TRY(colsum(d, G + L.b, rows, L.out, 1, 0, 0, s));
-            w[m] = GemmProblem{d, l ? nets[m].act[l - 1] : x, G + L.W, nullptr, L.out, L.in, rows, L.out, l ? (int64_t)L.in : ldx, L.in};
-            if (l) g[m] = GemmProblem{d, P + L.W, nets[m].dact[l - 1], nullptr, rows, L.in, L.out, L.out, L.in, L.in};
+            w[m] = GemmProblem{d, l ? nets[m].act[l - 1] : x, G + L.W, nullptr, L.out, L.in, rows, L.out, l ? (int64_t)L.in : ldx, L.in};      // dW[o][i] = sum_r d[r][o] in[r][i]
+            if (l) g[m] = GemmProblem{d, P + L.W, nets[m].dact[l - 1], nullptr, rows, L.in, L.out, L.out, L.in, L.in};      // din[r][i] = sum_o d[r][o] W[o][i]
         }
         EXORL_TRY(gemm_grouped(prec, 1, 1, w, n, false, false, s));
         if (l) EXORL_TRY(gemm_grouped(prec, 0, 1, g, n, false, false, s));
@@ -996,32 +986,12 @@ int mlp_backward_many(const Mlp* nets, int n, const float* P, float* G, const fl
     return 0;
 }
 
-// dact[last] holds d(loss)/d(output); writes parameter gradients into G and, if dx, d(loss)/d(input) (rows, in0)
+// the single net is the ensemble of one: the same launches with the same arguments (dact[last] holds d(loss)/d(output))
+int mlp_forward(const Mlp& m, const float* P, const float* x, int64_t ldx, int rows, int prec, hipStream_t s) {
+    return mlp_forward_many(&m, 1, P, x, ldx, rows, prec, s);
+}
 int mlp_backward(const Mlp& m, const float* P, float* G, const float* x, int64_t ldx, int rows, float* dx, int prec, hipStream_t s) {
-    const int n = (int)m.L.size();
-    for (int l = n - 1; l >= 0; --l) {
-        const Lin& L = m.L[l];
-        float* d = m.dact[l];
-        bool summed = false;
-        if (l < n - 1 || m.relu_last) {
-            summed = relu_bwd_colsum(d, m.act[l], G + L.b, rows, L.out, s) == 0;      // mask and bias gradient in one pass over dZ
-            if (!summed) {
-                const int64_t cnt = (int64_t)rows * L.out;
-                hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(cnt)), dim3(256), 0, s, d, m.act[l], cnt);
-                EXORL_LAUNCH_CHECK();
-            }
-        }
-        if (!summed) EXORL_TRY(colsum(d, G + L.b, rows, L.out, 1, 0, 0, s));
-        const float* in = l ? m.act[l - 1] : x;
-        GemmProblem w{d, in, G + L.W, nullptr, L.out, L.in, rows, L.out, l ? (int64_t)L.in : ldx, L.in};          // dW[o][i] = sum_r d[r][o] in[r][i]
-        EXORL_TRY(gemm_grouped(prec, 1, 1, &w, 1, false, false, s));
-        float* dst = l ? m.dact[l - 1] : dx;
-        if (dst) {
-            GemmProblem g{d, P + L.W, dst, nullptr, rows, L.in, L.out, L.out, L.in, L.in};      // din[r][i] = sum_o d[r][o] W[o][i]
-            EXORL_TRY(gemm_grouped(prec, 0, 1, &g, 1, false, false, s));
-        }
-    }
-    return 0;
+    return mlp_backward_many(&m, 1, P, G, x, ldx, rows, prec, s, dx);
 }
 
 }  // namespace exorl
@@ -1135,6 +1105,8 @@ static void describe_intr(exorl_intr* it) {
     it->total = round_up(off, 64);
 }
 
+static bool intr_exchanges(const exorl_intr_cfg& c, int xchg);      // asks the plan (below)
+
 static void carve_intr(exorl_intr* it, SimpleCarver& c) {
     const auto& g = it->cfg;
     const int64_t B = g.batch, O = g.obs_dim, R = g.rep_dim, W = g.world_size > 1 ? g.world_size : 1;
@@ -1151,19 +1123,19 @@ static void carve_intr(exorl_intr* it, SimpleCarver& c) {
     it->fe = c.take(B * (g.kind == EXORL_INTR_DISAGREEMENT ? it->n_nets : 1)); it->be = c.take(B);
     it->metrics = c.take(EXORL_N_INTR_METRICS);
     it->rms = reinterpret_cast<RmsState*>(c.take(4));
-    if (W > 1 && (g.kind == EXORL_INTR_RND || g.kind == EXORL_INTR_ICM_APT || g.kind == EXORL_INTR_APS ||
-                  (g.kind == EXORL_INTR_SMM && !(g.flags & EXORL_INTR_ENCODED))))
+    // ICM-APT / APS: the slot is in the layout whether or not knn_rms is on, so for them the kind decides and not the plan
+    if (intr_exchanges(g, EXORL_INTR_XCHG_MOMENTS) || (W > 1 && (g.kind == EXORL_INTR_ICM_APT || g.kind == EXORL_INTR_APS)))
         it->mom = reinterpret_cast<double*>(c.take(2 * 3 * W));
     if (g.kind == EXORL_INTR_RND) {
         if (!(g.flags & EXORL_INTR_ENCODED)) {     // encoded rows arrive normalised (BatchNorm2d ran on the frames)
             it->xn = c.take(B * O);
             it->bn = c.take(2 * O + 1);
-            if (W > 1) it->bnmom = reinterpret_cast<double*>(c.take(2 * 3 * O * W));
+            if (intr_exchanges(g, EXORL_INTR_XCHG_BN)) it->bnmom = reinterpret_cast<double*>(c.take(2 * 3 * O * W));
         }
     } else if (g.kind == EXORL_INTR_APS) {
         it->topk = c.take(B * g.knn_k);
         it->d2 = c.take(knn_scratch_floats((int)B, (int)(B * W)));
-        if (W > 1) it->gat = c.take(W * B * R);
+        if (intr_exchanges(g, EXORL_INTR_XCHG_REP)) it->gat = c.take(W * B * R);
     } else if (g.kind == EXORL_INTR_SMM) {
         const int64_t C = SMM_CODE_DIM;
         it->mu = c.take(B * C); it->lv = c.take(B * C); it->eps = c.take(B * C); it->code = c.take(B * C); it->dcode = c.take(B * C);
@@ -1174,7 +1146,7 @@ static void carve_intr(exorl_intr* it, SimpleCarver& c) {
         it->z1 = c.take(B * R); it->dz1 = c.take(B * R); it->sn = c.take(B * R); it->nrm = c.take(B); it->tn = c.take(B * R);
         it->scores_s = c.take(Bg * P); it->scores_t = c.take(Bg * P); it->dscores = c.take(B * P); it->dsn = c.take(B * R);
         it->colsum_p = c.take(P); it->scal = c.take(4); it->skr = c.take(2 * Bg);
-        if (W > 1) it->gat = c.take(W * B * R);
+        if (intr_exchanges(g, EXORL_INTR_XCHG_REP)) it->gat = c.take(W * B * R);
         if (!proto_cand_lds_fits(Bg)) {
             it->pcm_max = c.take(cdiv(Bg, PCM_CHUNK) * P);
             it->pcm_sum = reinterpret_cast<double*>(c.take(2 * cdiv(Bg, PCM_CHUNK) * P));
@@ -1195,7 +1167,7 @@ static void carve_intr(exorl_intr* it, SimpleCarver& c) {
             it->rstd = c.take(2 * B); it->drep = c.take(2 * B * R); it->dz = c.take(2 * B * R);
             it->topk = c.take(B * g.knn_k);
             it->d2 = c.take(knn_scratch_floats((int)B, (int)(B * W)));
-            if (W > 1) it->gat = c.take(W * B * R);
+            if (intr_exchanges(g, EXORL_INTR_XCHG_REP)) it->gat = c.take(W * B * R);
         }
     }
 }
@@ -1233,12 +1205,79 @@ int launch_concat(const float* a, int64_t lda, int ca, const float* b, int64_t l
 }
 
 // ---- staged module steps ------------------------------------------------------------------------------
-// Every module step below is a sequence of stages; a stage ends where the data-parallel step needs an exchange across the ranks and
-// names it in *next (EXORL_INTR_XCHG_*; -1: the step is complete). Stage 0 is the loss's forward and backward pass (train != 0 only) and
-// ends in the gradient exchange; stage 1 steps the optimiser and computes the reward; ICM-APT and APS then gather the representation
-// rows, and the RMS kinds gather their moments. With world_size 1 no stage after 0 names an exchange, and stage 0's (a sum over one
-// rank) is the identity, so exorl_intr_update runs the stages back to back. On state rows two more statistics are over the global batch:
-// RND's BatchNorm1d moments (gathered in a stage in front of stage 0) and SMM's mean_j / var_j of log p*(s_j) (gathered after stage 1).
+// A module's step is a flat list of steps, its plan. A step is a fixed piece of work (xxx_step runs exactly one); where the data-parallel
+// step needs an exchange across the ranks after it, the plan names the exchange (EXORL_INTR_XCHG_*). Which steps there are and what
+// follows them depends on the configuration and on `train` alone, so intr_plan knows it before the first launch, and carve_intr asks the
+// same plan which exchange buffers a configuration needs. A phase (exorl_intr_update_phase) runs steps until one is followed by an
+// exchange; the one-rank step (exorl_intr_update, the joint graph) runs the phases back to back. The gradient exchange is named at one
+// rank too, where a sum over one rank is the identity; no other exchange is named there.
+// train: 0 reward only, 1 step + reward on the same rows, 2 step only (RND on encodings and Proto: the pixel reward pass draws a new
+// augmentation and runs the encoder the step has just moved, rnd.py:98-103, so the caller encodes again in between).
+// "-> X": exchange X follows; [..]: the step exists only then; dp: world_size > 1.
+//   RND                         [dp, states] BN_MOMENTS -> BN | [train] LOSS -> GRAD | [train] ADAM | then unless train == 2:
+//                               FORWARD (the errors the reward reads) | [dp] MOMENTS -> MOMENTS | REWARD
+//   ICM, Disagreement, DIAYN    [train] LOSS -> GRAD | [train] ADAM | REWARD (forward pass and reward)
+//   ICM-APT, APS                [train] LOSS -> GRAD | [train] ADAM | FORWARD (the representation rows) | [dp] ROWS (into this rank's slot)
+//                               -> REP | KNN (own rows at one rank, the gathered rows otherwise) | [dp, knn_rms] MOMENTS -> MOMENTS | REWARD
+//   SMM (train is required)     LOSS (vae + pred) -> GRAD | ADAM (both ranges) | [dp, states] MOMENTS (of log p*) -> MOMENTS | REWARD
+//   Proto                       see proto_step
+enum { ST_BN_MOMENTS, ST_LOSS, ST_ADAM, ST_FORWARD, ST_ROWS, ST_KNN, ST_MOMENTS, ST_REWARD };
+
+struct IntrPlan {
+    int n = 0;
+    int step[8], xchg[8];          // xchg: the exchange that follows the step, or -1
+    void add(bool on, int st, int x = -1) { if (on) { step[n] = st; xchg[n++] = x; } }
+};
+
+static IntrPlan intr_plan(const exorl_intr_cfg& c, int train) {
+    const bool dp = c.world_size > 1, states = !(c.flags & EXORL_INTR_ENCODED), reward = train != 2;
+    const int rep = dp ? EXORL_INTR_XCHG_REP : -1;
+    IntrPlan p;
+    switch (c.kind) {
+        case EXORL_INTR_RND:
+            p.add(dp && states, ST_BN_MOMENTS, EXORL_INTR_XCHG_BN);
+            p.add(train, ST_LOSS, EXORL_INTR_XCHG_GRAD);
+            p.add(train, ST_ADAM);
+            p.add(reward, ST_FORWARD);
+            p.add(reward && dp, ST_MOMENTS, EXORL_INTR_XCHG_MOMENTS);
+            p.add(reward, ST_REWARD);
+            break;
+        case EXORL_INTR_ICM_APT: case EXORL_INTR_APS:
+            p.add(train, ST_LOSS, EXORL_INTR_XCHG_GRAD);
+            p.add(train, ST_ADAM);
+            p.add(true, ST_FORWARD);
+            p.add(dp, ST_ROWS, EXORL_INTR_XCHG_REP);
+            p.add(true, ST_KNN);
+            p.add(dp && c.knn_rms, ST_MOMENTS, EXORL_INTR_XCHG_MOMENTS);
+            p.add(true, ST_REWARD);
+            break;
+        case EXORL_INTR_SMM:               // train is required: smm_step refuses without
+            p.add(true, ST_LOSS, EXORL_INTR_XCHG_GRAD);
+            p.add(true, ST_ADAM);
+            p.add(dp && states, ST_MOMENTS, EXORL_INTR_XCHG_MOMENTS);
+            p.add(true, ST_REWARD);
+            break;
+        case EXORL_INTR_PROTO:
+            p.add(train, ST_FORWARD, rep);
+            p.add(train, ST_LOSS, EXORL_INTR_XCHG_GRAD);
+            p.add(train, ST_ADAM);
+            p.add(reward, ST_ROWS, rep);
+            p.add(reward, ST_REWARD);
+            break;
+        default:                           // ICM, Disagreement, DIAYN
+            p.add(train, ST_LOSS, EXORL_INTR_XCHG_GRAD);
+            p.add(train, ST_ADAM);
+            p.add(true, ST_REWARD);
+    }
+    return p;
+}
+
+static bool intr_exchanges(const exorl_intr_cfg& c, int xchg) {      // does this configuration's full step (train = 1) name the exchange?
+    const IntrPlan p = intr_plan(c, 1);
+    for (int i = 0; i < p.n; ++i)
+        if (p.xchg[i] == xchg) return true;
+    return false;
+}
 
 // ---- RND -------------------------------------------------------------------------------------------
 static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_target, float* dpred, hipStream_t s) {
@@ -1264,44 +1303,32 @@ static int rnd_forward(exorl_intr* it, const exorl_intr_batch& b, bool with_targ
     return 0;
 }
 
-// train: 0 reward only, 1 step + reward on the same rows, 2 step only (pixels: the reward pass draws a new augmentation and runs the
-// encoder the step has just moved, rnd.py:98-103, so the caller encodes again in between).
-// On state rows with world_size > 1 a stage of its own comes first (stage -1, the first phase of either call): each rank's BatchNorm1d
-// moments, gathered before anything reads the normalised rows. The reward pass normalises the same rows in training mode again
-// (rnd.py:98-100): the merged moments are still in place, so rnd_forward steps the running statistics a second time without an exchange.
-static int rnd_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+// On state rows with world_size > 1 each rank's BatchNorm1d moments are gathered before anything reads the normalised rows. The reward pass
+// normalises the same rows in training mode again (rnd.py:98-100): the merged moments are still in place, so rnd_forward steps the running
+// statistics a second time without an exchange.
+static int rnd_step(exorl_intr* it, const exorl_intr_batch& b, int train, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch;
     const bool enc = (c.flags & EXORL_INTR_ENCODED) != 0;
     EXORL_REQUIRE(enc || train != 2, "intr_update: RND's step-only call belongs to the encoded (pixel) variant");
-    *next = -1;
-    if (stage < 0) {
+    if (step == ST_BN_MOMENTS) {
         hipLaunchKernelGGL(bn_moments_kernel, dim3(c.obs_dim), dim3(256), 0, s, b.obs, b.obs_ld, B, c.obs_dim, it->bnmom + (int64_t)3 * c.obs_dim * it->rank);
         EXORL_LAUNCH_CHECK();
-        *next = EXORL_INTR_XCHG_BN;
         return 0;
     }
-    if (stage == 0) {                                                                                // rnd.py:79-96
+    if (step == ST_LOSS) {                                                                           // rnd.py:79-96
         EXORL_TRY(rnd_forward(it, b, true, it->net[0].dact[2], s));
         EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)it->Bg(), it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(mlp_backward(it->net[0], it->flat[EXORL_T_PARAM], it->flat[EXORL_T_GRAD], enc ? b.obs : it->xn, enc ? b.obs_ld : (int64_t)c.obs_dim, B,
-                               enc ? b.dobs_out : nullptr, c.precision, s));
-        *next = EXORL_INTR_XCHG_GRAD;
-        return 0;
+        return mlp_backward(it->net[0], it->flat[EXORL_T_PARAM], it->flat[EXORL_T_GRAD], enc ? b.obs : it->xn, enc ? b.obs_ld : (int64_t)c.obs_dim, B,
+                            enc ? b.dobs_out : nullptr, c.precision, s);
     }
-    if (stage == 1) {
-        if (train) {
-            EXORL_TRY(intr_adam(it, s));
-            if (train == 2) return 0;
-        }
-        // compute_intr_reward (rnd.py:98-103); states: same batch -> same BatchNorm output and frozen target, only the predictor moved
-        EXORL_TRY(rnd_forward(it, b, !train, nullptr, s));
-        if (it->world > 1) {                        // exchange the batch moments of the error; the reward is stage 2
-            hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->fe, B, 1, 0, it->mom + 3 * it->rank);
-            EXORL_LAUNCH_CHECK();
-            *next = EXORL_INTR_XCHG_MOMENTS;
-            return 0;
-        }
+    if (step == ST_ADAM) return intr_adam(it, s);
+    // compute_intr_reward (rnd.py:98-103); states: same batch -> same BatchNorm output and frozen target, only the predictor moved
+    if (step == ST_FORWARD) return rnd_forward(it, b, !train, nullptr, s);
+    if (step == ST_MOMENTS) {                       // the batch moments of the error
+        hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->fe, B, 1, 0, it->mom + 3 * it->rank);
+        EXORL_LAUNCH_CHECK();
+        return 0;
     }
     hipLaunchKernelGGL(rnd_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, it->Bg(), c.scale, it->rms,
                        it->world > 1 ? (const double*)it->mom : nullptr, it->world, it->metrics);
@@ -1320,14 +1347,13 @@ static int icm_errors(exorl_intr* it, const float* tgt, int64_t ldt, const float
     return 0;
 }
 
-static int icm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+static int icm_step(exorl_intr* it, const exorl_intr_batch& b, int train, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, A = c.act_dim, prec = c.precision;
     const float invBg = 1.0f / (float)it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
-    *next = -1;
-    if (stage == 0) {                                                                                // icm.py:64-84
+    if (step == ST_LOSS) {                                                                           // icm.py:64-84
         EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
         EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.next_obs, b.next_obs_ld, O, it->xb, B, s));
         EXORL_TRY(mlp_forward(it->net[0], P, it->xf, O + A, B, prec, s));
@@ -1341,11 +1367,10 @@ static int icm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
             hipLaunchKernelGGL(icm_dobs_kernel, dim3(grid_for((int64_t)B * O)), dim3(256), 0, s, it->dxf, (int64_t)(O + A), it->dxb, (int64_t)(2 * O), b.dobs_out, B, O);
             EXORL_LAUNCH_CHECK();
         }
-        *next = EXORL_INTR_XCHG_GRAD;
         return 0;
     }
-    if (train) EXORL_TRY(intr_adam(it, s));
-    else EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
+    if (step == ST_ADAM) return intr_adam(it, s);
+    if (!train) EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));      // after LOSS xf is in place
     EXORL_TRY(mlp_forward(it->net[0], P, it->xf, O + A, B, prec, s));                                // icm.py:86-92
     EXORL_TRY(icm_errors(it, b.next_obs, b.next_obs_ld, b.action, b.action_ld, false, false, s));
     hipLaunchKernelGGL(icm_reward_kernel, dim3(1), dim3(1024), 0, s, it->fe, b.extr_reward, b.reward_out, B, c.scale, it->metrics, it->Bg());
@@ -1361,28 +1386,19 @@ static int apt_trunk(exorl_intr* it, const float* x, int64_t ldx, int rows, hipS
     return ln_tanh_fwd(it->z, P + it->ln_g, P + it->ln_b, it->rep, it->xhat, it->rstd, rows, c.rep_dim, 1, 0, 0, s);
 }
 
-// utils.PBE on the representation rows `rep` (batch x rep_dim) of ICM-APT / APS: stage 1 (after the optimiser step and the forward pass that
-// made rep), 2 (the rows gathered: this rank's rows against the global batch) and 3 (the moments gathered)
-static int pbe_stage(exorl_intr* it, const exorl_intr_batch& b, const float* rep, int stage, int* next, hipStream_t s) {
+// utils.PBE on the representation rows `rep` (batch x rep_dim) of ICM-APT / APS: the steps after FORWARD, which made rep
+static int pbe_step(exorl_intr* it, const exorl_intr_batch& b, const float* rep, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, R = c.rep_dim;
-    *next = -1;
-    if (stage == 1) {
-        if (it->world > 1) {                            // gather the rows: the neighbours are sought in the global batch (stage 2)
-            EXORL_CHECK_HIP(hipMemcpyAsync(it->gat + (int64_t)it->rank * B * R, rep, sizeof(float) * B * R, hipMemcpyDeviceToDevice, s));
-            *next = EXORL_INTR_XCHG_REP;
-            return 0;
-        }
-        EXORL_TRY(knn_topk(rep, B, rep, B, R, c.knn_k, it->topk, it->d2, s));
+    if (step == ST_ROWS) {                              // gather the rows: the neighbours are sought in the global batch
+        EXORL_CHECK_HIP(hipMemcpyAsync(it->gat + (int64_t)it->rank * B * R, rep, sizeof(float) * B * R, hipMemcpyDeviceToDevice, s));
+        return 0;
     }
-    if (stage == 2) {
-        EXORL_TRY(knn_topk(rep, B, it->gat, it->Bg(), R, c.knn_k, it->topk, it->d2, s));
-        if (c.knn_rms) {
-            hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->topk, B, c.knn_k, c.knn_avg, it->mom + 3 * it->rank);
-            EXORL_LAUNCH_CHECK();
-            *next = EXORL_INTR_XCHG_MOMENTS;
-            return 0;
-        }
+    if (step == ST_KNN) return knn_topk(rep, B, it->world > 1 ? it->gat : rep, it->Bg(), R, c.knn_k, it->topk, it->d2, s);
+    if (step == ST_MOMENTS) {
+        hipLaunchKernelGGL(rms_moments_kernel, dim3(1), dim3(1024), 0, s, it->topk, B, c.knn_k, c.knn_avg, it->mom + 3 * it->rank);
+        EXORL_LAUNCH_CHECK();
+        return 0;
     }
     hipLaunchKernelGGL(pbe_reward_kernel, dim3(1), dim3(1024), 0, s, it->topk, b.extr_reward, b.reward_out, B, it->Bg(), c.knn_k, c.knn_avg, c.knn_rms,
                        c.knn_clip, it->rms, it->world > 1 ? (const double*)it->mom : nullptr, it->world, it->metrics);
@@ -1390,14 +1406,13 @@ static int pbe_stage(exorl_intr* it, const exorl_intr_batch& b, const float* rep
     return 0;
 }
 
-static int apt_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+static int apt_step(exorl_intr* it, const exorl_intr_batch& b, int train, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, A = c.act_dim, R = c.rep_dim, prec = c.precision;
     const float invBg = 1.0f / (float)it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
-    *next = -1;
-    if (stage == 0) {                                                                                // icm_apt.py:33-50,86-104
+    if (step == ST_LOSS) {                                                                           // icm_apt.py:33-50,86-104
         EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, nullptr, 0, 0, it->x2, B, s));                   // x2 = [obs; next_obs] stacked by rows
         EXORL_TRY(launch_concat(b.next_obs, b.next_obs_ld, O, nullptr, 0, 0, it->x2 + (int64_t)B * O, B, s));
         EXORL_TRY(apt_trunk(it, it->x2, O, 2 * B, s));
@@ -1423,25 +1438,21 @@ static int apt_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
             GemmProblem gx{it->dz, P + it->trunk.W, b.dobs_out, nullptr, B, O, R, R, O, O};
             EXORL_TRY(gemm_grouped(prec, 0, 1, &gx, 1, false, false, s));
         }
-        *next = EXORL_INTR_XCHG_GRAD;
         return 0;
     }
-    if (stage == 1) {
-        if (train) EXORL_TRY(intr_adam(it, s));
-        EXORL_TRY(apt_trunk(it, b.obs, b.obs_ld, B, s));                                             // icm_apt.py:106-110
-    }
-    return pbe_stage(it, b, it->rep, stage, next, s);
+    if (step == ST_ADAM) return intr_adam(it, s);
+    if (step == ST_FORWARD) return apt_trunk(it, b.obs, b.obs_ld, B, s);                             // icm_apt.py:106-110
+    return pbe_step(it, b, it->rep, step, s);
 }
 
 // ---- Disagreement ----------------------------------------------------------------------------------
-static int disagreement_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+static int disagreement_step(exorl_intr* it, const exorl_intr_batch& b, int train, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, A = c.act_dim, prec = c.precision, n = it->n_nets;
     const float invBg = 1.0f / (float)it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
-    *next = -1;
-    if (stage == 0) {                                                                                // disagreement.py:19-33,64-80
+    if (step == ST_LOSS) {                                                                           // disagreement.py:19-33,64-80
         EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
         EXORL_TRY(mlp_forward_many(it->net, n, P, it->xf, O + A, B, prec, s));          // the 5 models' layers share launches
         for (int m = 0; m < n; ++m) {
@@ -1451,12 +1462,10 @@ static int disagreement_stage(exorl_intr* it, const exorl_intr_batch& b, int tra
         }
         EXORL_TRY(mlp_backward_many(it->net, n, P, G, it->xf, O + A, B, prec, s, b.dobs_out ? it->dxf : nullptr));
         if (b.dobs_out) EXORL_TRY(launch_concat(it->dxf, O + A, O, nullptr, 0, 0, b.dobs_out, B, s));
-        EXORL_TRY(launch_mean(it->fe, B * n, 1.0f / ((float)it->Bg() * (float)n), it->metrics + EXORL_IM_LOSS, 0, s));
-        *next = EXORL_INTR_XCHG_GRAD;
-        return 0;
+        return launch_mean(it->fe, B * n, 1.0f / ((float)it->Bg() * (float)n), it->metrics + EXORL_IM_LOSS, 0, s);
     }
-    if (train) EXORL_TRY(intr_adam(it, s));
-    else EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));
+    if (step == ST_ADAM) return intr_adam(it, s);
+    if (!train) EXORL_TRY(launch_concat(b.obs, b.obs_ld, O, b.action, b.action_ld, A, it->xf, B, s));      // after LOSS xf is in place
     PredSet ps{};
     EXORL_TRY(mlp_forward_many(it->net, n, P, it->xf, O + A, B, prec, s));                           // disagreement.py:35-47
     for (int m = 0; m < n; ++m) ps.p[m] = it->net[m].act[1];
@@ -1470,24 +1479,21 @@ static int disagreement_stage(exorl_intr* it, const exorl_intr_batch& b, int tra
 }
 
 // ---- DIAYN -----------------------------------------------------------------------------------------
-static int diayn_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+static int diayn_step(exorl_intr* it, const exorl_intr_batch& b, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, S = c.rep_dim, prec = c.precision, Bg = it->Bg();
     const float invBg = 1.0f / (float)Bg;
     const float* P = it->flat[EXORL_T_PARAM];
-    *next = -1;
-    if (stage == 0) {                                                                                // diayn.py:78-92,107-127
+    if (step == ST_LOSS) {                                                                           // diayn.py:78-92,107-127
         EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));
         hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, S, it->fe, it->be,
                            it->net[0].dact[2], (float*)nullptr, c.scale, B, Bg);
         EXORL_LAUNCH_CHECK();
         EXORL_TRY(launch_mean(it->fe, B, invBg, it->metrics + EXORL_IM_LOSS, 0, s));
         EXORL_TRY(launch_mean(it->be, B, invBg, it->metrics + EXORL_IM_ACC, 0, s));
-        EXORL_TRY(mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s));   // dobs_out: d/d(next_obs)
-        *next = EXORL_INTR_XCHG_GRAD;
-        return 0;
+        return mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s);      // dobs_out: d/d(next_obs)
     }
-    if (train) EXORL_TRY(intr_adam(it, s));
+    if (step == ST_ADAM) return intr_adam(it, s);
     EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));                    // diayn.py:94-105
     if (b.extr_reward) EXORL_TRY(launch_mean(b.extr_reward, B, invBg, it->metrics + EXORL_IM_EXTR_REWARD, 0, s));
     hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, S, (float*)nullptr,
@@ -1505,9 +1511,9 @@ static int adam_range(exorl_intr* it, int64_t off, int64_t n, float lr, int opt,
                      lr, 0.9f, 0.999f, 1e-8f, it->t, nullptr, 0.f, s);
 }
 
-// Both optimisers' gradients (vae_opt's and pred_opt's ranges) are ready after stage 0: one exchange, then the two Adam steps. update_pred
+// Both optimisers' gradients (vae_opt's and pred_opt's ranges) are ready after LOSS: one exchange, then the two Adam steps. update_pred
 // neither reads the VAE's parameters nor writes its range, so running its passes before vae_opt.step() changes nothing.
-static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+static int smm_step(exorl_intr* it, const exorl_intr_batch& b, int train, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, Z = c.rep_dim, W = O + Z, V = SMM_VAE_HIDDEN, C = SMM_CODE_DIM, prec = c.precision, Bg = it->Bg();
     EXORL_REQUIRE(b.obs_ld >= W, "intr_update: SMM reads [obs | z] rows (obs_ld >= obs_dim + z_dim)");
@@ -1515,19 +1521,16 @@ static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
     const float* P = it->flat[EXORL_T_PARAM];
     float* G = it->flat[EXORL_T_GRAD];
     Mlp &zp = it->net[0], &enc = it->net[1], &dec = it->net[2];
-    *next = -1;
-    if (stage == 1) {
+    if (step == ST_ADAM) {
         EXORL_TRY(adam_range(it, it->vae_off, it->trainable - it->vae_off, c.vae_lr, 2, s));
-        EXORL_TRY(adam_range(it, 0, it->vae_off, c.sp_lr, 1, s));
-        if (it->world > 1 && !(c.flags & EXORL_INTR_ENCODED)) {      // mean_j and var_j of log p*(s_j) are over the global batch: stage 2
-            hipLaunchKernelGGL(smm_logp_moments_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, B, c.goal_x, c.goal_y, it->mom + 3 * it->rank);
-            EXORL_LAUNCH_CHECK();
-            *next = EXORL_INTR_XCHG_MOMENTS;
-            return 0;
-        }
+        return adam_range(it, 0, it->vae_off, c.sp_lr, 1, s);
     }
-    if (stage >= 1) {
-        // ---- reward (smm.py:229-246)
+    if (step == ST_MOMENTS) {                      // mean_j and var_j of log p*(s_j) are over the global batch
+        hipLaunchKernelGGL(smm_logp_moments_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, B, c.goal_x, c.goal_y, it->mom + 3 * it->rank);
+        EXORL_LAUNCH_CHECK();
+        return 0;
+    }
+    if (step == ST_REWARD) {                       // smm.py:229-246
         const bool merged = it->world > 1 && !(c.flags & EXORL_INTR_ENCODED);
         hipLaunchKernelGGL(smm_reward_kernel, dim3(1), dim3(1024), 0, s, b.obs, b.obs_ld, it->hsz, it->hzs, b.extr_reward, b.reward_out, B, Z,
                            c.state_ent_coef, c.latent_ent_coef, c.latent_cond_ent_coef, c.goal_x, c.goal_y, it->metrics, (c.flags & EXORL_INTR_ENCODED) ? 1 : 0, Bg,
@@ -1535,7 +1538,7 @@ static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
         EXORL_LAUNCH_CHECK();
         return 0;
     }
-    it->t += 1;
+    it->t += 1;                                    // LOSS: both updates' passes; the ADAM step reads the t of this step
     // ---- update_vae (smm.py:173-185, VAE.loss :61-70) on obs_z
     EXORL_TRY(mlp_forward(enc, P, b.obs, b.obs_ld, B, prec, s));
     GemmProblem hd[2] = {{enc.act[1], P + it->enc_mu.W, it->mu, P + it->enc_mu.b, B, C, V, V, V, C},
@@ -1572,48 +1575,29 @@ static int smm_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int s
     hipLaunchKernelGGL(diayn_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, zp.act[2], b.skill, b.skill_ld, Z, it->hzs, it->be, zp.dact[2], (float*)nullptr, 1.0f, B, Bg);
     EXORL_LAUNCH_CHECK();
     EXORL_TRY(launch_mean(it->hzs, B, 1.0f / (float)Bg, it->metrics + 5, 0, s));
-    EXORL_TRY(mlp_backward(zp, P, G, b.obs, b.obs_ld, B, nullptr, prec, s));
-    *next = EXORL_INTR_XCHG_GRAD;
-    return 0;
+    return mlp_backward(zp, P, G, b.obs, b.obs_ld, B, nullptr, prec, s);
 }
 
 // ---- APS -------------------------------------------------------------------------------------------
-static int aps_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
+static int aps_step(exorl_intr* it, const exorl_intr_batch& b, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, D = c.rep_dim, prec = c.precision, Bg = it->Bg();
     const float* P = it->flat[EXORL_T_PARAM];
     const float* rep = it->net[0].act[2];
-    *next = -1;
-    if (stage == 0) {                                                                                // aps.py:147-159,170-175
+    if (step == ST_LOSS) {                                                                           // aps.py:147-159,170-175
         EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));
         hipLaunchKernelGGL(aps_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, it->net[0].act[2], b.skill, b.skill_ld, it->net[0].dact[2], it->fe, B, D, Bg);
         EXORL_LAUNCH_CHECK();
         EXORL_TRY(launch_mean(it->fe, B, 1.0f / (float)Bg, it->metrics + EXORL_IM_LOSS, 0, s));
-        EXORL_TRY(mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s));   // dobs_out: d/d(next_obs)
-        *next = EXORL_INTR_XCHG_GRAD;
-        return 0;
+        return mlp_backward(it->net[0], P, it->flat[EXORL_T_GRAD], b.next_obs, b.next_obs_ld, B, b.dobs_out, prec, s);      // dobs_out: d/d(next_obs)
     }
-    if (stage == 1) {
-        if (train) EXORL_TRY(intr_adam(it, s));
-        EXORL_TRY(mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s));                // aps.py:161-168
-    }
-    EXORL_TRY(pbe_stage(it, b, rep, stage, next, s));
-    if (*next >= 0) return 0;
+    if (step == ST_ADAM) return intr_adam(it, s);
+    if (step == ST_FORWARD) return mlp_forward(it->net[0], P, b.next_obs, b.next_obs_ld, B, prec, s);      // aps.py:161-168
+    EXORL_TRY(pbe_step(it, b, rep, step, s));
+    if (step != ST_REWARD) return 0;
     hipLaunchKernelGGL(aps_sf_reward_kernel, dim3(1), dim3(1024), 0, s, rep, b.skill, b.skill_ld, b.reward_out, B, D, it->metrics, Bg);
     EXORL_LAUNCH_CHECK();
     return 0;
-}
-
-static int intr_stage(exorl_intr* it, const exorl_intr_batch& b, int train, int stage, int* next, hipStream_t s) {
-    switch (it->cfg.kind) {
-        case EXORL_INTR_RND: return rnd_stage(it, b, train, stage, next, s);
-        case EXORL_INTR_ICM: return icm_stage(it, b, train, stage, next, s);
-        case EXORL_INTR_ICM_APT: return apt_stage(it, b, train, stage, next, s);
-        case EXORL_INTR_DISAGREEMENT: return disagreement_stage(it, b, train, stage, next, s);
-        case EXORL_INTR_APS: return aps_stage(it, b, train, stage, next, s);
-        case EXORL_INTR_SMM: return smm_stage(it, b, train, stage, next, s);
-        default: return diayn_stage(it, b, train, stage, next, s);
-    }
 }
 
 // ---- Proto ------------------------------------------------------------------------------------------
@@ -1658,20 +1642,16 @@ static int proto_candidates(exorl_intr* it, const float* scores, const float* z,
     return 0;
 }
 
-// Proto's step in stages (proto.py:103-157):
-//   0  normalize_protos; the online branch on this rank's rows (scores_s); the target branch's normalised rows, written into this rank's
-//      slot of the gather buffer                                                                      -> EXORL_INTR_XCHG_REP (world > 1)
-//   1  the targets' scores and Sinkhorn-Knopp over all Bg gathered rows (every rank the same, in the same order); loss and dscores of this
-//      rank's rows against its rows of the assignment, as means over Bg; backward into the gradients and dobs_out -> EXORL_INTR_XCHG_GRAD
-//   2  Adam; predictor_target's Polyak step
-//   3  the reward pass: normalize_protos; z = l2norm(predictor(next_obs)) of this rank's rows into its slot -> EXORL_INTR_XCHG_REP (world > 1)
-//   4  scores of all Bg rows; the candidate draw over them (same seed and counter on every rank: the same queue rows, queue_ptr and
-//      counter); kNN of this rank's rows against the queue; the k-th-distance reward; the metrics as partial means over Bg
-// train 2 runs stages 0-2, train 1 stages 0-4, train 0 stages 3-4. A phase runs stages until one names an exchange; with world_size 1
-// only stage 1 names one (a sum over one rank: the identity), so the stages run as before, back to back.
-static bool proto_ends_phase(int stage, int world) { return stage == 1 || (world > 1 && (stage == 0 || stage == 3)); }
-
-static int proto_stage(exorl_intr* it, const exorl_intr_batch& b, int stage, hipStream_t s) {
+// Proto's steps (proto.py:103-157); train 2 plans FORWARD to ADAM, train 1 all five, train 0 ROWS and REWARD:
+//   FORWARD  normalize_protos; the online branch on this rank's rows (scores_s); the target branch's normalised rows, written into this
+//            rank's slot of the gather buffer                                                                -> REP (world > 1)
+//   LOSS     the targets' scores and Sinkhorn-Knopp over all Bg gathered rows (every rank the same, in the same order); loss and dscores of
+//            this rank's rows against its rows of the assignment, as means over Bg; backward into the gradients and dobs_out -> GRAD
+//   ADAM     Adam; predictor_target's Polyak step
+//   ROWS     the reward pass: normalize_protos; z = l2norm(predictor(next_obs)) of this rank's rows into its slot -> REP (world > 1)
+//   REWARD   scores of all Bg rows; the candidate draw over them (same seed and counter on every rank: the same queue rows, queue_ptr and
+//            counter); kNN of this rank's rows against the queue; the k-th-distance reward; the metrics as partial means over Bg
+static int proto_step(exorl_intr* it, const exorl_intr_batch& b, int step, hipStream_t s) {
     const auto& c = it->cfg;
     const int B = c.batch, O = c.obs_dim, D = c.rep_dim, P = c.num_protos, prec = c.precision, Bg = it->Bg();
     float* Pm = it->flat[EXORL_T_PARAM];
@@ -1679,7 +1659,7 @@ static int proto_stage(exorl_intr* it, const exorl_intr_batch& b, int stage, hip
     float* C = Pm + it->protos;
     const float inv_tau = 1.0f / c.tau;
     float* mine = it->world > 1 ? it->gat + (int64_t)it->rank * B * D : nullptr;      // this rank's slot of the gathered rows
-    if (stage == 0) {                                                                                // proto.py:126-157
+    if (step == ST_FORWARD) {                                                                        // proto.py:126-157
         EXORL_TRY(launch_l2norm(C, C, nullptr, P, D, s));                                            // normalize_protos
         EXORL_TRY(proto_predict(it, b.obs, b.obs_ld, Pm + it->pred.W, Pm + it->pred.b, it->z1, s));
         EXORL_TRY(mlp_forward(it->net[0], Pm, it->z1, D, B, prec, s));
@@ -1692,7 +1672,7 @@ static int proto_stage(exorl_intr* it, const exorl_intr_batch& b, int stage, hip
         EXORL_TRY(proto_predict(it, nt, nt_ld, Pm + it->pred_t.W, Pm + it->pred_t.b, it->tn, s));
         return launch_l2norm(it->tn, mine ? mine : it->tn, nullptr, B, D, s);
     }
-    if (stage == 1) {
+    if (step == ST_LOSS) {
         const float* t = it->world > 1 ? it->gat : it->tn;
         GemmProblem pq{t, C, it->scores_t, nullptr, Bg, P, D, D, D, P};
         EXORL_TRY(gemm_grouped(prec, 0, 0, &pq, 1, false, false, s));
@@ -1726,12 +1706,12 @@ static int proto_stage(exorl_intr* it, const exorl_intr_batch& b, int stage, hip
         }
         return 0;
     }
-    if (stage == 2) {
+    if (step == ST_ADAM) {
         EXORL_TRY(intr_adam(it, s));
         // utils.soft_update_params(predictor, predictor_target, encoder_target_tau) (proto.py:202-203): nothing reads the target before the next update
         return soft_update(Pm + it->pred.W, Pm + it->pred_t.W, it->pred_t.b + round_up(c.rep_dim, 4) - it->pred_t.W, c.target_tau, s);
     }
-    if (stage == 3) {                                                                                // compute_intr_reward(next_obs) (proto.py:103-124)
+    if (step == ST_ROWS) {                                                                           // compute_intr_reward(next_obs) (proto.py:103-124)
         EXORL_TRY(launch_l2norm(C, C, nullptr, P, D, s));
         EXORL_TRY(proto_predict(it, b.next_obs, b.next_obs_ld, Pm + it->pred.W, Pm + it->pred.b, it->sn, s));
         return launch_l2norm(it->sn, mine ? mine : it->sn, nullptr, B, D, s);
@@ -1746,22 +1726,27 @@ static int proto_stage(exorl_intr* it, const exorl_intr_batch& b, int stage, hip
     return 0;
 }
 
-// one phase of the staged step: the stages of the phases before it are skipped, then stages run until one names an exchange
-static int proto_phase(exorl_intr* it, const exorl_intr_batch& b, int train, int phase, int* next, hipStream_t s) {
-    const int last = train == 2 ? 2 : 4;
-    int stage = train ? 0 : 3;
-    for (int p = 0; p < phase && stage <= last; ++p) {
-        while (stage < last && !proto_ends_phase(stage, it->world)) ++stage;
-        ++stage;
+// one phase of the step: the steps of the phases before it are skipped, then steps run until one is followed by an exchange
+static int intr_phase(exorl_intr* it, const exorl_intr_batch& b, int train, int phase, int* next, hipStream_t s) {
+    const IntrPlan p = intr_plan(it->cfg, train);
+    int i = 0;
+    for (int ph = 0; ph < phase && i < p.n; ++ph) {
+        while (i < p.n - 1 && p.xchg[i] < 0) ++i;
+        ++i;
     }
-    EXORL_REQUIRE(phase >= 0 && stage <= last, "intr_update_phase: phase %d out of range", phase);
-    *next = -1;
-    for (; stage <= last; ++stage) {
-        EXORL_TRY(proto_stage(it, b, stage, s));
-        if (proto_ends_phase(stage, it->world)) {
-            *next = stage == 1 ? EXORL_INTR_XCHG_GRAD : EXORL_INTR_XCHG_REP;
-            return 0;
+    EXORL_REQUIRE(phase >= 0 && i < p.n, "intr_update_phase: phase %d out of range", phase);
+    for (*next = -1; i < p.n && *next < 0; ++i) {
+        switch (it->cfg.kind) {
+            case EXORL_INTR_RND: EXORL_TRY(rnd_step(it, b, train, p.step[i], s)); break;
+            case EXORL_INTR_ICM: EXORL_TRY(icm_step(it, b, train, p.step[i], s)); break;
+            case EXORL_INTR_ICM_APT: EXORL_TRY(apt_step(it, b, train, p.step[i], s)); break;
+            case EXORL_INTR_DISAGREEMENT: EXORL_TRY(disagreement_step(it, b, train, p.step[i], s)); break;
+            case EXORL_INTR_APS: EXORL_TRY(aps_step(it, b, p.step[i], s)); break;
+            case EXORL_INTR_SMM: EXORL_TRY(smm_step(it, b, train, p.step[i], s)); break;
+            case EXORL_INTR_PROTO: EXORL_TRY(proto_step(it, b, p.step[i], s)); break;
+            default: EXORL_TRY(diayn_step(it, b, p.step[i], s));
         }
+        *next = p.xchg[i];
     }
     return 0;
 }
@@ -2004,19 +1989,11 @@ static int check_intr_batch(exorl_intr* it, const exorl_intr_batch* b) {
     return 0;
 }
 
-// the one-rank step: its stages back to back
+// the one-rank step: its phases back to back (the gradient exchange between them is the identity)
 static int intr_run_stages(exorl_intr* it, const exorl_intr_batch& b, int train, hipStream_t s) {
-    int next = -1;
-    if (it->cfg.kind == EXORL_INTR_PROTO) {           // one rank: the gradient exchange after stage 1 is the identity
-        for (int phase = 0;; ++phase) {
-            EXORL_TRY(proto_phase(it, b, train, phase, &next, s));
-            if (next < 0) return 0;
-        }
-    }
-    for (int stage = train ? 0 : 1;; ++stage) {      // one rank: the gradient exchange is the identity and no later stage names one
-        EXORL_TRY(intr_stage(it, b, train, stage, &next, s));
-        if (next < 0) return 0;
-    }
+    int next = 0;
+    for (int phase = 0; next >= 0; ++phase) EXORL_TRY(intr_phase(it, b, train, phase, &next, s));
+    return 0;
 }
 }  // namespace exorl
 
@@ -2035,18 +2012,7 @@ int exorl_intr_update_phase(exorl_intr_t* it, const exorl_intr_batch* b, int32_t
     *next_exchange = -1;
     EXORL_TRY(check_intr_batch(it, b));
     it->dev_stale = true;
-    int next = -1;
-    if (it->cfg.kind == EXORL_INTR_PROTO) {
-        EXORL_TRY(proto_phase(it, *b, train, phase, &next, as_stream(stream)));
-        *next_exchange = next;
-        return 0;
-    }
-    int stage = phase + (train ? 0 : 1);
-    if (it->bn_dp()) stage = phase == 0 ? -1 : stage - 1;          // RND on state rows: the BatchNorm1d exchange comes first
-    EXORL_REQUIRE(phase >= 0 && stage <= 3, "intr_update_phase: phase %d out of range", phase);
-    EXORL_TRY(intr_stage(it, *b, train, stage, &next, as_stream(stream)));
-    *next_exchange = next;
-    return 0;
+    return intr_phase(it, *b, train, phase, next_exchange, as_stream(stream));
 }
 
 int exorl_intr_exchange(exorl_intr_t* it, int32_t id, void** ptr_dev, int64_t* count, int32_t* dtype, int32_t* op) {

@@ -19,6 +19,17 @@ INTR_BYTES = {('aps', 128, 16, 64, 0): 506624, ('aps', 1024, 16, 1024, 2): 38589
               ('icm_apt', 1024, 16, 1024, 2): 23761408, ('proto', 128, 16, 64, 0): 228096, ('proto', 1024, 16, 1024, 2): 10160896,
               ('rnd', 128, 16, 64, 0): 652800, ('rnd', 1024, 16, 1024, 2): 47302656, ('smm', 128, 16, 64, 0): 2905600,
               ('smm', 1024, 16, 1024, 2): 45316608}
+# the same at world_size 2, as (kind, hidden_dim, rep_dim, batch, precision, flags, knn_rms): every kind, EXORL_INTR_ENCODED (flags 1) where the
+# kind accepts it, and ICM-APT / APS without the RMS; computed with the library of the commit before the module steps became plans
+INTR_BYTES_DP = {('aps', 128, 16, 64, 0, 0, 1): 531456, ('aps', 128, 16, 64, 0, 0, 0): 531456, ('aps', 1024, 16, 1024, 2, 0, 1): 42915584,
+                 ('aps', 1024, 16, 1024, 2, 0, 0): 42915584, ('diayn', 128, 16, 64, 0, 0, 1): 489472, ('diayn', 1024, 16, 1024, 2, 0, 1): 34383360,
+                 ('disagreement', 128, 16, 64, 0, 0, 1): 971776, ('disagreement', 1024, 16, 1024, 2, 0, 1): 47704576,
+                 ('icm', 128, 16, 64, 0, 0, 1): 413696, ('icm', 1024, 16, 1024, 2, 0, 1): 19473920, ('icm_apt', 128, 16, 64, 0, 0, 1): 434688,
+                 ('icm_apt', 128, 16, 64, 0, 0, 0): 434688, ('icm_apt', 1024, 16, 1024, 2, 0, 1): 28087040,
+                 ('icm_apt', 1024, 16, 1024, 2, 0, 0): 28087040, ('proto', 128, 16, 64, 0, 0, 1): 244992, ('proto', 1024, 16, 1024, 2, 0, 1): 10431232,
+                 ('rnd', 128, 16, 64, 0, 0, 1): 654336, ('rnd', 128, 16, 64, 0, 1, 1): 646656, ('rnd', 1024, 16, 1024, 2, 0, 1): 47304192,
+                 ('rnd', 1024, 16, 1024, 2, 1, 1): 47204352, ('smm', 128, 16, 64, 0, 0, 1): 2905856, ('smm', 128, 16, 64, 0, 1, 1): 2905600,
+                 ('smm', 1024, 16, 1024, 2, 0, 1): 45316864, ('smm', 1024, 16, 1024, 2, 1, 1): 45316608}
 # exorl_agent_workspace_bytes(kind, obs_dim, hidden_dim, batch, precision, sf_dim), the same way
 AGENT_BYTES = {('ddpg', 24, 128, 64, 0, 0): 2001408, ('ddpg', 40, 128, 64, 2, 0): 2935296, ('aps', 40, 128, 64, 0, 16): 2504192,
                ('ddpg', 24, 1024, 1024, 2, 0): 218986496, ('aps', 34, 1024, 1024, 2, 10): 242188800}
@@ -51,14 +62,14 @@ def test_abi_version_is_unchanged_and_the_header_names_the_export():
     assert version and NAME in version.group(1)
 
 
-@pytest.mark.parametrize('key', sorted(INTR_BYTES))
+@pytest.mark.parametrize('key', sorted(INTR_BYTES) + sorted(INTR_BYTES_DP))
 def test_the_module_workspace_is_what_it_was(key):
     from exorl_amd import _lib as L
     from exorl_amd.engine import IntrEngine
-    kind, H, R, B, prec = key
-    cfg = L.IntrCfg(IntrEngine.KINDS[kind], O, A, H, R, B, prec, 3, 1, 1, 0, 0, 1e-4, 1.0, 0.0, 5.0, 16, 80, 0.1, 0.05, 1e-3, 1e-2, 0.5, 1.0,
-                    1.0, 1.0, 150.0, 75.0, 1, 0)
-    assert L.load().exorl_intr_workspace_bytes(ctypes.byref(cfg)) == INTR_BYTES[key]
+    kind, H, R, B, prec, flags, knn_rms, world = key + ((0, 1, 1) if len(key) == 5 else (2,))
+    cfg = L.IntrCfg(IntrEngine.KINDS[kind], O, A, H, R, B, prec, 3, 1, knn_rms, 0, flags, 1e-4, 1.0, 0.0, 5.0, 16, 80, 0.1, 0.05, 1e-3, 1e-2, 0.5,
+                    1.0, 1.0, 1.0, 150.0, 75.0, world, 0)
+    assert L.load().exorl_intr_workspace_bytes(ctypes.byref(cfg)) == {**INTR_BYTES, **INTR_BYTES_DP}[key]
 
 
 @pytest.mark.parametrize('key', sorted(AGENT_BYTES))
