@@ -47,6 +47,11 @@ class AgentCfg(C.Structure):
                 ('target_cql_penalty', c_float), ('reserved3', c_int32)]
 
 
+class WeightImages(C.Structure):
+    _fields_ = [('n_trunks', c_int32), ('n_heads', c_int32), ('in_dim', c_int32), ('hidden_dim', c_int32), ('w0t', c_void_p),
+                ('w0_hi', c_void_p), ('w0_lo', c_void_p), ('w1_hi', c_void_p), ('w1_mid', c_void_p), ('w1_lo', c_void_p)]
+
+
 class IntrCfg(C.Structure):
     _fields_ = [('kind', c_int32), ('obs_dim', c_int32), ('act_dim', c_int32), ('hidden_dim', c_int32), ('rep_dim', c_int32),
                 ('batch', c_int32), ('precision', c_int32), ('knn_k', c_int32), ('knn_avg', c_int32), ('knn_rms', c_int32),
@@ -170,6 +175,7 @@ PROTOTYPES = {
     'exorl_agent_noise_counter': (C.c_int, [c_void_p, P(c_uint64), c_void_p]),
     'exorl_debug_philox_normal': (C.c_int, [c_uint64, c_uint64, c_int64, c_void_p, c_void_p]),
     'exorl_debug_agent_poison_scratch': (C.c_int, [c_void_p, c_void_p]),
+    'exorl_debug_agent_weight_images': (C.c_int, [c_void_p, c_int32, P(WeightImages)]),
     'exorl_agent_disable_graph': (C.c_int, [c_void_p]),
     'exorl_gemm': (C.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                              c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p]),

@@ -1308,6 +1308,15 @@ int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream) {
     return 0;
 }
 
+int exorl_debug_agent_weight_images(exorl_agent_t* a, int32_t net, exorl_weight_images* out) {
+    EXORL_REQUIRE(a && out, "debug_agent_weight_images: null argument");
+    const NetDesc* d = net_of(a, net);
+    EXORL_REQUIRE(d, "debug_agent_weight_images: agent has no net %d", net);
+    const NetShadow& sh = net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_CRITIC ? a->sh_critic : a->sh_target;
+    *out = exorl_weight_images{d->n_trunks, d->n_heads, d->in_dim, d->H, sh.w0t, sh.w0q.hi, sh.w0q.lo, sh.w1q.hi, sh.w1q.mid, sh.w1q.lo};
+    return 0;
+}
+
 int exorl_agent_cql_alpha(exorl_agent_t* a, float* host, int32_t set) {
     EXORL_REQUIRE(a && host && a->cql, "agent_cql_alpha: not a CQL agent / null argument");
     const int nsc = a->cfg.use_critic_lagrange ? 2 : 1;      // [1] = log_critic_alpha (cql.py:103-105)

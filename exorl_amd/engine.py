@@ -241,6 +241,26 @@ class AgentEngine(_Phased):
         the next step must not notice)."""
         L.check(self.lib.exorl_debug_agent_poison_scratch(self.h, L.current_stream()))
 
+    def weight_images(self, net):
+        """The derived weight copies of `net` (exorl_debug_agent_weight_images) as views of this engine's workspace: 'w0t' float32
+        (n_trunks, in, H); 'w0_hi' / 'w0_lo' (n_trunks, H, round_up(in, 32)) and 'w1_hi' / 'w1_mid' / 'w1_lo' (n_heads, H, H), bf16 bit
+        patterns as int16. An image the configuration does not have is None. Launches nothing (test hook)."""
+        w = L.WeightImages()
+        L.check(self.lib.exorl_debug_agent_weight_images(self.h, net, C.byref(w)))
+        H, kp = w.hidden_dim, (w.in_dim + 31) // 32 * 32
+
+        def planes(ptr, shape):
+            if not ptr:
+                return None
+            n = int(np.prod(shape))
+            return self._view(ptr, (n + 1) // 2).view(torch.int16)[:n].view(*shape)
+        out = {'w0t': self._view(w.w0t, w.n_trunks * w.in_dim * H).view(w.n_trunks, w.in_dim, H)}
+        for k in ('w0_hi', 'w0_lo'):
+            out[k] = planes(getattr(w, k), (w.n_trunks, H, kp))
+        for k in ('w1_hi', 'w1_mid', 'w1_lo'):
+            out[k] = planes(getattr(w, k), (w.n_heads, H, H))
+        return out
+
     def set_parallel_branches(self, enable):
         L.check(self.lib.exorl_agent_set_parallel_branches(self.h, int(bool(enable))))
 

@@ -38,7 +38,7 @@ extern "C" {
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
-                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr) */
+                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -291,6 +291,31 @@ int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float*
  * metrics and act()'s scratch keep their contents. A step after this call must give bit-identical results: anything else is a read of
  * memory the step did not write. Enqueued on `stream`. */
 int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream);
+/* The derived weight images of one net. The kernels do not read the first-layer weight W0 ([H][in] per trunk) and the H x H weight W1 (per
+ * head) from the fp32 parameters but from copies of them in the workspace, which every writer of the parameters keeps equal, bit for bit,
+ * to the image of the current fp32 value x:
+ *   w0t                     W0 transposed, fp32 [n_trunks][in][H]: the value itself
+ *   hi                      bf16(x), round to nearest even
+ *   lo  (two-plane image)   bf16(x - hi)
+ *   mid, lo (three planes)  mid = bf16(x - hi), lo = bf16(x - hi - mid); the differences are formed in fp32, where they are exact
+ *   w0_hi / w0_lo           [n_trunks][H][round_up(in, 32)]: columns in .. round_up(in, 32) - 1 of every row are zero
+ *   w1_hi / w1_mid / w1_lo  [n_heads][H][H]
+ * Which images a configuration has (a pointer is NULL where it has none; w0t always exists):
+ *   EXORL_PREC_BF16                                                                   w0_hi, w1_hi
+ *   EXORL_PREC_BF16X3, hidden_dim % 128 == 0 and batch % 64 == 0 (the plane pipeline)  w0_hi, w0_lo, w1_hi, w1_lo
+ *   EXORL_PREC_BF16X6, hidden_dim % 128 == 0 and batch % 128 == 0 (the plane route)    w1_hi, w1_mid, w1_lo; none of W0
+ *   everything else (fp32; bf16x3 / bf16x6 at other shapes: the GEMM splits fp32)     none
+ * Written by exorl_agent_params_changed, by the optimiser launch of every step route (for the critic also the Polyak target's) and, three
+ * planes, by a conversion pass behind it. */
+typedef struct {
+    int32_t n_trunks, n_heads, in_dim, hidden_dim;
+    float* w0t;
+    uint16_t *w0_hi, *w0_lo;
+    uint16_t *w1_hi, *w1_mid, *w1_lo;
+} exorl_weight_images;
+/* Diagnostic only: the derived weight copies of one net (EXORL_NET_*), device pointers into the workspace, NULL where the configuration
+ * carves none. Launches nothing and synchronises nothing: the caller orders its reads behind the steps it enqueued. */
+int exorl_debug_agent_weight_images(exorl_agent_t* a, int32_t net, exorl_weight_images* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Stand-alone operators (used by the agents above; exported for tests and for callers' own nets)

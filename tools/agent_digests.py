@@ -8,7 +8,8 @@ must leave every line equal). Run it from each tree in a fresh process per listi
     python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
 
 A listing has one line per entry, `case what value`; a value is the first 32 hex digits of a sha256 or a float.hex(). Inputs come from
-tests/_synth.py and seeded numpy streams only. Needs a GPU (there is no CPU path)."""
+tests/_synth.py and seeded numpy streams only. The state engines' derived weight images (AgentEngine.weight_images) are listed one by one next
+to the whole-workspace digest; against a listing of a tree from before that export they show as `<missing>`. Needs a GPU (there is no CPU path)."""
 import hashlib
 import json
 import os
@@ -153,6 +154,9 @@ def digest(ag, emit):
         for net in [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else []):
             for what in ((L.T_PARAM,) if net == L.NET_CRITIC_TARGET else (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V, L.T_GRAD)):
                 emit(f'engine.net{net}.what{what}', sha(eng.flat(net, what)))
+            for name, image in eng.weight_images(net).items():      # the derived weight copies one by one: a differing workspace digest gets a name
+                if image is not None:
+                    emit(f'engine.net{net}.image.{name}', sha(image))
         emit('engine.opt_steps', sha(repr(eng.opt_steps()))), emit('engine.noise_counter', sha(repr(eng.noise_counter())))
         if ag.KIND == 'cql':
             emit('engine.cql_alpha', sha(eng.cql_alpha_state()))
