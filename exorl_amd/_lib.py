@@ -12,6 +12,7 @@ P = C.POINTER
 
 # constants mirrored from include/exorl_hip.h
 SAMPLER_MT19937, SAMPLER_PHILOX, SAMPLER_GIVEN = 0, 1, 2
+WEIGHT_EPISODES, WEIGHT_TRANSITIONS = 0, 1
 AGENT_TD3_BC, AGENT_TD3, AGENT_BC, AGENT_DDPG, AGENT_CRR, AGENT_CQL, AGENT_APS = 0, 1, 2, 3, 4, 5, 6
 M_CRITIC_CQL, M_CRITIC_CQL_LOGSUM, M_ACTOR_ALPHA, M_ACTOR_ALPHA_LOSS, M_ACTOR_ENT = 10, 11, 12, 13, 14
 CRR_WEIGHT = {'identity': 0, 'indicator': 1, 'exp': 2}
@@ -134,6 +135,7 @@ PROTOTYPES = {
     'exorl_replay_append_episode': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, P(c_int32)]),
     'exorl_replay_evict': (C.c_int, [c_void_p, c_int32]),
     'exorl_replay_set_order': (C.c_int, [c_void_p, c_void_p, c_int32]),
+    'exorl_replay_set_weights': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32]),
     'exorl_replay_num_rows': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_replay_seed_mt': (C.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
     'exorl_replay_seed_mt_ints': (C.c_int, [c_void_p, c_uint64, c_uint32]),

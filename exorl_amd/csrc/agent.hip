@@ -405,6 +405,7 @@ struct exorl_agent {
     hipGraph_t graph = nullptr;
     hipStream_t capture_stream = nullptr;
     exorl_replay* graph_replay = nullptr;
+    uint64_t graph_weights_epoch = 0;        // the replay's exorl_replay_set_weights count at capture: the graph samples that table
     uint64_t graph_replay_ctr = 0;           // host mirror of state->replay_counter: eager samples drawn between two launches move the replay's own
     exorl_intr* graph_intr = nullptr;        // joint graph (exorl_agent_enable_graph_intr): the module whose step rides in front of the agent's
     bool capturing = false;
@@ -1269,6 +1270,7 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     a->graph = g;
     EXORL_CHECK_HIP(hipGraphInstantiate(&a->graph_exec, g, nullptr, nullptr, 0));
     a->graph_replay = r;
+    a->graph_weights_epoch = replay_weights_epoch(r);
     a->graph_replay_ctr = ctr;
     a->graph_intr = it;
     return 0;
@@ -1400,6 +1402,8 @@ int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
         EXORL_TRY(set_device_float(&a->state->stddev, stddev, as_stream(stream)));
         a->dev_stddev = stddev;
     }
+    EXORL_REQUIRE(replay_weights_epoch(a->graph_replay) == a->graph_weights_epoch, "agent_step_graph: exorl_replay_set_weights was called after "
+                  "the capture: the graph samples the table it was captured with (call exorl_agent_enable_graph again)");
     const uint64_t ctr = replay_philox_counter(a->graph_replay);
     if (ctr != a->graph_replay_ctr) EXORL_TRY(set_device_u64(&a->state->replay_counter, ctr, as_stream(stream)));      // eager batches were drawn in between
     a->graph_replay_ctr = ctr + 1;

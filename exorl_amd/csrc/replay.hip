@@ -12,6 +12,11 @@
 // Index streams: EXORL_SAMPLER_MT19937 reproduces the reference's two MT19937 streams on the host
 // (CPython random.choice -> _randbelow_with_getrandbits; NumPy legacy randint masked rejection) and ships the
 // B index pairs with one async copy; EXORL_SAMPLER_PHILOX draws them in the kernel (Philox4x32-10).
+//
+// Weighted sampling (exorl_replay_set_weights, Philox only): every slot carries an integer weight q_e and the table gains a uint64
+// prefix sum `cum` of the episode masses (TRANSITIONS: q_e * span_e, EPISODES: q_e where span_e > 0; span_e = len_e - nstep + 1
+// clamped at 0). The kernel scales 64 Philox bits onto [0, cum[n]) and binary-searches the episode; zero-mass episodes own an empty
+// interval and are never drawn. With unit weights TRANSITIONS mode is uniform over transitions.
 #include <algorithm>
 #include <vector>
 
@@ -111,6 +116,19 @@ struct exorl_replay {
     std::vector<int32_t> h_pairs;
     std::vector<int64_t> h_row0;
     std::vector<int32_t> h_len;
+    // weighted sampling: q per slot, the mode, and the prefix sum of the masses in table order for `cum_nstep`
+    std::vector<uint32_t> weight;
+    int32_t weight_mode = EXORL_WEIGHT_EPISODES;
+    bool weighted = false;            // false: the unweighted sampler, no cum table
+    uint64_t* d_cum = nullptr;        // max_episodes + 1 entries, allocated at create: its address is stable across graph replays
+    std::vector<uint64_t> h_cum;
+    int32_t cum_nstep = -1;           // -1: stale
+    // cut-point table over the top guide_bits bits of the 64 random bits: guide[k] = the episode of the smallest g of bucket k, so the
+    // search of a draw in bucket k runs over [guide[k], guide[k + 1]] only (>= 2 buckets per episode: O(1) expected loads)
+    int32_t* d_guide = nullptr;       // guide_cap + 1 entries, allocated at create
+    std::vector<int32_t> h_guide;
+    int32_t guide_cap = 0, guide_bits = 0;
+    uint64_t weights_epoch = 0;       // counts exorl_replay_set_weights calls (a captured step graph refuses to replay across one)
 };
 
 namespace exorl {
@@ -121,6 +139,9 @@ struct ReplayView {
     const int64_t* row0;
     const int32_t* len;
     int32_t obs_bytes, act_dim, meta_dim, n_episodes;
+    const uint64_t* cum;      // null: unweighted; else n_episodes + 1 prefix sums of the episode masses, cum[n_episodes] the total
+    const int32_t* guide;     // (1 << guide_bits) + 1 cut points into cum, indexed by the top guide_bits bits of the draw
+    int32_t guide_bits;
 };
 
 __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
@@ -151,7 +172,19 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
     if (sampler == EXORL_SAMPLER_PHILOX) {
         uint32_t c[4] = {(uint32_t)b, (uint32_t)counter, (uint32_t)(counter >> 32), 0u};
         Philox::gen(c, seed);
-        pos = (int)(((uint64_t)c[0] * (uint64_t)v.n_episodes) >> 32);
+        if (v.cum) {           // wave-uniform: g in [0, total), pos = the episode whose interval [cum[pos], cum[pos+1]) holds g
+            const uint64_t u = ((uint64_t)c[2] << 32) | c[3];
+            const uint64_t g = __umul64hi(u, v.cum[v.n_episodes]);
+            const uint32_t k = (uint32_t)(u >> (64 - v.guide_bits));
+            int lo = v.guide[k], hi = v.guide[k + 1] + 1;      // g is monotone in u: the answer lies between the buckets' first episodes
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (v.cum[mid] <= g) lo = mid; else hi = mid;
+            }
+            pos = lo;
+        } else {
+            pos = (int)(((uint64_t)c[0] * (uint64_t)v.n_episodes) >> 32);
+        }
         const int span = v.len[pos] - nstep + 1;
         idx = (int)(((uint64_t)c[1] * (uint64_t)span) >> 32) + 1;
         if (lane == 0) { pairs_out[2 * b] = pos; pairs_out[2 * b + 1] = idx; }
@@ -198,8 +231,49 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
     }
 }
 
-static int upload_table(exorl_replay* r, hipStream_t s) {
+// Prefix sum of the episode masses for `nstep`, checked on the host before anything is enqueued.
+static int build_cum(exorl_replay* r, int32_t nstep) {
+    const int n = (int)r->order.size();
+    r->h_cum.resize((size_t)n + 1);
+    uint64_t total = 0;
+    r->h_cum[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        const int slot = r->order[i];
+        const int64_t span = std::max<int64_t>((int64_t)r->slots[slot].rows - 1 - nstep + 1, 0);
+        const uint64_t q = r->weight[slot];
+        const uint64_t mass = r->weight_mode == EXORL_WEIGHT_TRANSITIONS ? q * (uint64_t)span : (span > 0 ? q : 0);   // < 2^32 * 2^31
+        EXORL_REQUIRE(mass < (1ull << 63) - total, "replay_sample: total sampling mass reaches 2^63 at position %d of %d: use smaller "
+                      "weights", i, n);
+        total += mass;
+        r->h_cum[i + 1] = total;
+    }
+    EXORL_REQUIRE(total > 0, "replay_sample: total sampling mass is 0: no episode with a positive weight holds nstep=%d transitions", nstep);
+    int bits = 1;
+    while ((1 << bits) < 2 * n && (2 << bits) <= r->guide_cap) ++bits;
+    const int G = 1 << bits;
+    r->guide_bits = bits;
+    r->h_guide.resize((size_t)G + 1);
+    int p = 0;
+    for (int k = 0; k <= G; ++k) {       // bucket k starts at u = k << (64 - bits); entry G: the last drawable g
+        const uint64_t g = k < G ? (uint64_t)(((unsigned __int128)((uint64_t)k << (64 - bits)) * total) >> 64) : total - 1;
+        while (r->h_cum[p + 1] <= g) ++p;
+        r->h_guide[k] = p;
+    }
+    return 0;
+}
+
+// nstep: the Philox sampler's (the cum table depends on it); 0 for the host-side samplers, which read no cum table.
+static int upload_table(exorl_replay* r, int32_t nstep, hipStream_t s) {
+    const bool want_cum = r->weighted && nstep > 0;
+    if (want_cum && (r->table_dirty || r->cum_nstep != nstep)) {
+        r->cum_nstep = -1;
+        EXORL_TRY(build_cum(r, nstep));
+        EXORL_CHECK_HIP(hipMemcpyAsync(r->d_cum, r->h_cum.data(), r->h_cum.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        EXORL_CHECK_HIP(hipMemcpyAsync(r->d_guide, r->h_guide.data(), r->h_guide.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        r->cum_nstep = nstep;
+    }
     if (!r->table_dirty) return 0;
+    if (!want_cum) r->cum_nstep = -1;      // the table moved under a cum built earlier
     const int n = (int)r->order.size();
     r->h_row0.resize(n);
     r->h_len.resize(n);
@@ -277,6 +351,10 @@ int exorl_replay_create(const exorl_replay_cfg* cfg, exorl_replay_t** out) {
     if (cfg->meta_dim) EXORL_CHECK_HIP(hipMalloc((void**)&r->meta, rows * cfg->meta_dim * 4));
     EXORL_CHECK_HIP(hipMalloc((void**)&r->d_row0, (size_t)cfg->max_episodes * sizeof(int64_t)));
     EXORL_CHECK_HIP(hipMalloc((void**)&r->d_len, (size_t)cfg->max_episodes * sizeof(int32_t)));
+    EXORL_CHECK_HIP(hipMalloc((void**)&r->d_cum, ((size_t)cfg->max_episodes + 1) * sizeof(uint64_t)));
+    r->guide_cap = 2;
+    while (r->guide_cap < 2 * (int64_t)cfg->max_episodes && r->guide_cap < (1 << 28)) r->guide_cap <<= 1;
+    EXORL_CHECK_HIP(hipMalloc((void**)&r->d_guide, ((size_t)r->guide_cap + 1) * sizeof(int32_t)));
     *out = r;
     return 0;
 }
@@ -285,7 +363,7 @@ int exorl_replay_destroy(exorl_replay_t* r) {
     if (!r) return 0;
     (void)hipFree(r->obs); (void)hipFree(r->act); (void)hipFree(r->rew); (void)hipFree(r->disc);
     if (r->meta) (void)hipFree(r->meta);
-    (void)hipFree(r->d_row0); (void)hipFree(r->d_len);
+    (void)hipFree(r->d_row0); (void)hipFree(r->d_len); (void)hipFree(r->d_cum); (void)hipFree(r->d_guide);
     if (r->d_pairs) (void)hipFree(r->d_pairs);
     delete r;
     return 0;
@@ -309,6 +387,7 @@ int exorl_replay_append_episode(exorl_replay_t* r, const void* obs, const float*
         EXORL_REQUIRE((int)r->slots.size() < r->cfg.max_episodes, "replay_append_episode: more than max_episodes=%d resident",
                       r->cfg.max_episodes);
         r->slots.push_back(Slot{0, 0, false});
+        r->weight.push_back(1u);
         slot = (int)r->slots.size() - 1;
     }
     const int64_t row0 = r->used_rows;
@@ -318,6 +397,7 @@ int exorl_replay_append_episode(exorl_replay_t* r, const void* obs, const float*
     EXORL_CHECK_HIP(hipMemcpy(r->disc + row0, disc, (size_t)rows * 4, hipMemcpyHostToDevice));
     if (meta) EXORL_CHECK_HIP(hipMemcpy(r->meta + row0 * r->cfg.meta_dim, meta, (size_t)rows * r->cfg.meta_dim * 4, hipMemcpyHostToDevice));
     r->slots[slot] = Slot{row0, rows, true};
+    r->weight[slot] = 1u;                           // a reused slot does not inherit the evicted episode's weight
     r->used_rows += rows;
     r->live_rows += rows;
     *slot_out = slot;
@@ -341,6 +421,19 @@ int exorl_replay_set_order(exorl_replay_t* r, const int32_t* slots, int32_t n) {
                       "replay_set_order: slot %d (position %d) not resident", slots[i], i);
     r->order.assign(slots, slots + n);
     r->table_dirty = true;
+    return 0;
+}
+
+int exorl_replay_set_weights(exorl_replay_t* r, int32_t mode, const uint32_t* q_per_slot, int32_t n_slots) {
+    EXORL_REQUIRE(r, "replay_set_weights: null handle");
+    EXORL_REQUIRE(mode == EXORL_WEIGHT_EPISODES || mode == EXORL_WEIGHT_TRANSITIONS, "replay_set_weights: unknown mode %d", mode);
+    EXORL_REQUIRE(!q_per_slot || (n_slots >= 0 && n_slots <= (int)r->slots.size()),
+                  "replay_set_weights: %d weights for %d slots", n_slots, (int)r->slots.size());
+    for (size_t i = 0; i < r->weight.size(); ++i) r->weight[i] = q_per_slot && (int)i < n_slots ? q_per_slot[i] : 1u;
+    r->weight_mode = mode;
+    r->weighted = q_per_slot != nullptr || mode == EXORL_WEIGHT_TRANSITIONS;
+    r->cum_nstep = -1;
+    r->weights_epoch += 1;
     return 0;
 }
 
@@ -389,13 +482,13 @@ namespace exorl {
 int replay_prepare(exorl_replay* r, int32_t batch, int32_t nstep, hipStream_t s) {
     EXORL_REQUIRE(r && batch > 0, "replay_prepare: bad arguments");
     EXORL_REQUIRE(!r->order.empty(), "replay_sample: no resident episodes (IndexError in random.choice, replay_buffer.py:169)");
-    EXORL_TRY(upload_table(r, s));
+    EXORL_TRY(upload_table(r, nstep, s));
     if (batch > r->pairs_cap) {
         if (r->d_pairs) EXORL_CHECK_HIP(hipFree(r->d_pairs));
         EXORL_CHECK_HIP(hipMalloc((void**)&r->d_pairs, (size_t)batch * 2 * sizeof(int32_t)));
         r->pairs_cap = batch;
     }
-    if (nstep > 0)      // Philox draws a start inside every episode: all of them must hold nstep transitions
+    if (nstep > 0 && !r->weighted)      // unweighted Philox draws a start inside every episode: all of them must hold nstep transitions
         EXORL_REQUIRE(r->min_len - nstep + 1 >= 1, "replay_sample: shortest episode (%d) shorter than nstep=%d", r->min_len, nstep);
     return 0;
 }
@@ -412,6 +505,8 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
     EXORL_REQUIRE(out->obs && out->action && out->reward && out->discount && out->next_obs, "replay_sample: null output");
     EXORL_REQUIRE((r->cfg.meta_dim > 0) || out->meta == nullptr, "replay_sample: meta output without meta columns");
     const int n = (int)r->order.size();
+    EXORL_REQUIRE(!(r->weighted && sampler == EXORL_SAMPLER_MT19937), "replay_sample: weighted sampling needs EXORL_SAMPLER_PHILOX: the MT19937 "
+                  "sampler reproduces the reference's unweighted index stream (exorl_replay_set_weights(EPISODES, NULL) turns weighting off)");
     EXORL_TRY(replay_prepare(r, batch, sampler == EXORL_SAMPLER_PHILOX ? nstep : 0, s));
     if (sampler == EXORL_SAMPLER_MT19937 || sampler == EXORL_SAMPLER_GIVEN) {
         r->h_pairs.resize((size_t)batch * 2);
@@ -443,7 +538,8 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
         set_error("replay_sample: unknown sampler %d", sampler);
         return 2;
     }
-    ReplayView v{r->obs, r->act, r->rew, r->disc, r->meta, r->d_row0, r->d_len, r->cfg.obs_bytes, r->cfg.act_dim, r->cfg.meta_dim, n};
+    ReplayView v{r->obs, r->act, r->rew, r->disc, r->meta, r->d_row0, r->d_len, r->cfg.obs_bytes, r->cfg.act_dim, r->cfg.meta_dim, n,
+                 r->weighted && sampler == EXORL_SAMPLER_PHILOX ? r->d_cum : nullptr, r->d_guide, r->guide_bits};
     const int vec16 = (r->cfg.obs_bytes % 16 == 0) && (out->obs_stride % 16 == 0) && (out->next_obs_stride % 16 == 0) &&
                       ((uintptr_t)out->obs % 16 == 0) && ((uintptr_t)out->next_obs % 16 == 0);
     hipLaunchKernelGGL(gather_nstep_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch, nstep,
@@ -454,6 +550,7 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
 }
 
 uint64_t replay_philox_counter(exorl_replay* r) { return r->philox_counter; }
+uint64_t replay_weights_epoch(exorl_replay* r) { return r->weights_epoch; }
 int replay_obs_bytes(exorl_replay* r) { return r->cfg.obs_bytes; }
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }
 void replay_advance_philox(exorl_replay* r, uint64_t n) { r->philox_counter += n; }

@@ -699,6 +699,21 @@ class PixelEngine(_Phased):
         return self._view(ptr, self.batch * n).view(self.batch, n)
 
 
+WEIGHTING = {'episodes': L.WEIGHT_EPISODES, 'transitions': L.WEIGHT_TRANSITIONS}
+
+
+def quantise_weights(w):
+    """Float episode weights -> the uint32 weights the device sampler sums: q = rint(w / max(w) * 2^24), computed in float64. The largest
+    weight maps to 2^24, a positive weight never maps to 0 (floor at 1: a ratio below 2^-25 is rounded up, not dropped), zero stays zero
+    (the episode is never drawn). Negative, non-finite or all-zero weights raise ValueError."""
+    w = np.asarray(w, np.float64).reshape(-1)
+    if w.size == 0 or not np.all(np.isfinite(w)) or np.any(w < 0) or not np.any(w > 0):
+        raise ValueError('episode weights must be finite, non-negative and not all zero')
+    q = np.rint(w / w.max() * float(1 << 24))
+    q[(w > 0) & (q < 1)] = 1
+    return q.astype(np.uint32)
+
+
 class ReplayEngine:
     """HBM-resident episodic arena (exorl_replay_t)."""
 
@@ -748,6 +763,20 @@ class ReplayEngine:
     def set_order(self, slots):
         arr = np.ascontiguousarray(slots, np.int32)
         L.check(self.lib.exorl_replay_set_order(self.h, arr.ctypes.data, len(arr)))
+
+    def set_weights(self, weighting='episodes', weights=None):
+        """Weighted sampling for the Philox sampler. weighting='episodes': an episode is drawn with probability proportional to its
+        weight, then a start uniformly inside it (weights=None: the unweighted sampler, the default). weighting='transitions': an
+        episode is drawn with probability proportional to weight x (len - nstep + 1), i.e. weights=None is uniform over transitions
+        whatever the episode lengths. `weights`: one float per slot id (as returned by append_episode), quantised by
+        quantise_weights(); slots past the end of the array, and slots reused by a later append_episode, have weight 1. Episodes
+        shorter than nstep are skipped rather than refused. The MT19937 sampler refuses a weighted arena. A captured step graph
+        (agent.enable_graph) samples from the table of its capture: after changing weights, mode or resident episodes call
+        enable_graph again (a graph step after a later set_weights raises ExorlError instead of sampling the stale table)."""
+        if weighting not in WEIGHTING:
+            raise ValueError(f"weighting={weighting!r}: expected 'episodes' or 'transitions'")
+        q = None if weights is None else np.ascontiguousarray(quantise_weights(weights))
+        L.check(self.lib.exorl_replay_set_weights(self.h, WEIGHTING[weighting], L.ptr(q), 0 if q is None else len(q)))
 
     def seed_mt_from_globals(self):
         """Adopts the CURRENT state of Python's `random` and NumPy's legacy global generator — the two

@@ -137,6 +137,20 @@ class _Shard:
         self.dir_stamp = None
         self.engine = None
         self.seeded = False
+        self.weight = {}               # fn -> float episode weight (episode_weight callable or mix); empty: unit weights
+
+    def _reorder(self):
+        """The episode table in `fns` order, and with it the sampling weights: slot ids move when episodes are evicted and stored."""
+        ld = self.loader
+        self.engine.set_order([self.slot[f] for f in self.fns])
+        if ld.weighting is None:
+            return
+        w = None
+        if self.weight:
+            w = np.zeros(max(self.slot.values()) + 1, np.float64)      # slots no resident episode holds: 0, out of the quantisation's scale
+            for f in self.fns:
+                w[self.slot[f]] = self.weight[f]
+        self.engine.set_weights(ld.weighting, w)
 
     def _ensure_engine(self, episode):
         if self.engine is not None:
@@ -162,13 +176,16 @@ class _Shard:
             early = self.fns.pop(0)                       # lexicographically first (replay_buffer.py:178-182)
             self.engine.evict(self.slot.pop(early))
             self.size -= self.length.pop(early)
+            self.weight.pop(early, None)
             early.unlink(missing_ok=True)
         self.slot[fn] = self.engine.append_episode(episode, ld.meta_keys)
         self.length[fn] = n
+        if ld.episode_weight is not None:
+            self.weight[fn] = float(ld.episode_weight(episode))
         bisect.insort(self.fns, fn)                       # == append + sort (replay_buffer.py:185-186), without re-sorting per episode
         self.size += n
         if reorder:
-            self.engine.set_order([self.slot[f] for f in self.fns])
+            self._reorder()
         if not ld.save_snapshot:
             fn.unlink(missing_ok=True)
         return True
@@ -207,7 +224,7 @@ class _Shard:
                 break
             stored = True
         if stored:
-            self.engine.set_order([self.slot[f] for f in self.fns])
+            self._reorder()
         self.dir_stamp = os.stat(d).st_mtime_ns
 
 
@@ -227,6 +244,27 @@ def relabel_episode(env, episode):
     episode = dict(episode)
     episode['reward'] = out
     return episode
+
+
+def mix_weights(lengths, mix, weighting='transitions', nstep=1):
+    """Per-episode weight of each dataset d so that a fraction mix[d] of the samples comes from it: mix[d] / M_d, where M_d is the
+    dataset's total span sum(max(len - nstep + 1, 0)) under weighting='transitions' (every transition of d equally likely) and its number
+    of sampleable episodes (len >= nstep) under weighting='episodes' (every episode of d equally likely). `lengths`: one list of episode
+    lengths per dataset. The fractions need not sum to 1 (only their ratios matter); a dataset with a positive fraction and nothing to
+    sample is an error."""
+    if len(mix) != len(lengths):
+        raise ValueError(f'mix has {len(mix)} fractions for {len(lengths)} datasets')
+    out = []
+    for d, (f, lens) in enumerate(zip(mix, lengths)):
+        f = float(f)
+        if not np.isfinite(f) or f < 0:
+            raise ValueError(f'mix[{d}]={f}: fractions must be finite and non-negative')
+        spans = [max(int(n) - nstep + 1, 0) for n in lens]
+        m = sum(spans) if weighting == 'transitions' else sum(1 for x in spans if x > 0)
+        if f > 0 and m == 0:
+            raise ValueError(f'mix[{d}]={f}: dataset {d} has no episode of at least nstep={nstep} transitions')
+        out.append(f / m if m else 0.0)
+    return out
 
 
 class _OfflineShard(_Shard):
@@ -249,13 +287,22 @@ class _OfflineShard(_Shard):
             size += n
         return todo, size
 
+    @classmethod
+    def select_many(cls, replay_dirs, max_size, num_workers, worker_id):
+        """select() on every directory by itself (each with the whole max_size): [(files, total length), ...] in the order given."""
+        return [cls.select(d, max_size, num_workers, worker_id) for d in replay_dirs]
+
     def try_fetch(self):
         if self.engine is not None or self.since_fetch < 0:
             return
         ld = self.loader
-        todo, size = self.select(ld.storage._replay_dir, ld.max_size, ld.num_workers, self.worker_id)
+        picks = self.select_many(ld.storage._replay_dirs, ld.max_size, ld.num_workers, self.worker_id)
+        todo, size = [fn for t, _ in picks for fn in t], sum(n for _, n in picks)
         if not todo:
             return
+        if ld.mix is not None:                   # normalised over what THIS shard holds of each dataset
+            per = mix_weights([[int(fn.stem.split('_')[2]) for fn in t] for t, _ in picks], ld.mix, ld.weighting, ld.nstep)
+            self.weight = {fn: w for (t, _), w in zip(picks, per) for fn in t}
         ld.max_episodes, ld.capacity_rows = len(todo) + 8, size + len(todo) + 64
         for fn, episode in zip(todo, _load_many(todo, ld.load_threads)):
             if episode is None:
@@ -265,18 +312,41 @@ class _OfflineShard(_Shard):
             self._ensure_engine(episode)
             self.slot[fn] = self.engine.append_episode(episode, ld.meta_keys)
             self.length[fn] = episode_len(episode)
+            if ld.episode_weight is not None:
+                self.weight[fn] = float(ld.episode_weight(episode))
             self.fns.append(fn)
             self.size += self.length[fn]
-        self.engine.set_order([self.slot[f] for f in self.fns])
+        self._reorder()
         self.since_fetch = -(1 << 62)            # loaded once (replay_buffer.py:78-80)
 
 
+def _weighting_args(sampler, weighting, episode_weight, mix=None):
+    """The weighting mode a loader applies (None: it never touches the arena's weights), after refusing what cannot be honoured."""
+    if weighting is None and episode_weight is None and mix is None:
+        return None
+    if weighting not in (None, 'episodes', 'transitions'):
+        raise ValueError(f"weighting={weighting!r}: expected 'episodes' or 'transitions'")
+    if sampler != 'philox':
+        raise ValueError(f"weighting / episode_weight / mix need sampler='philox': sampler={sampler!r} reproduces the reference's "
+                         'unweighted index stream')
+    if episode_weight is not None and not callable(episode_weight):
+        raise ValueError('episode_weight must be a callable: episode dict -> float')
+    if episode_weight is not None and mix is not None:
+        raise ValueError('mix sets the episode weights itself: pass either mix or episode_weight')
+    return weighting or 'episodes'
+
+
 class DeviceReplayLoader:
-    """What make_replay_loader returns: iterable whose iterator yields device-resident minibatches."""
+    """What make_replay_loader returns: iterable whose iterator yields device-resident minibatches.
+
+    weighting='episodes'|'transitions' and episode_weight (a callable: episode dict -> non-negative float, e.g.
+    `lambda ep: 4.0 if ep['constraint'].any() else 1.0`) select ReplayEngine.set_weights' weighted sampling; they are re-applied
+    whenever episodes are stored, evicted or re-ordered, and need sampler='philox'. mix: see make_offline_replay_loader."""
 
     def __init__(self, storage, max_size, batch_size, num_workers, save_snapshot, nstep, discount, fetch_every=1000,
                  device='cuda', sampler='mt19937', seed=None, worker_ids=None, max_episodes=None, capacity_rows=None, static=False,
-                 load_threads=None, offline=False, env=None, relabel=False):
+                 load_threads=None, offline=False, env=None, relabel=False, weighting=None, episode_weight=None, mix=None):
+        self.weighting, self.episode_weight, self.mix = _weighting_args(sampler, weighting, episode_weight, mix), episode_weight, mix
         self.storage = storage
         self.offline, self.env, self.relabel = offline, env, relabel      # OfflineReplayBuffer semantics (see _OfflineShard)
         self.static = static                # the directory will not change (offline datasets): load once, never re-scan
@@ -406,9 +476,16 @@ class ArenaIterator:
     """Iterator over an already-filled ReplayEngine (no directory behind it): what bench.py and callers that
     ingest datasets themselves use. Same next()/sample_into() contract as DeviceReplayIterator."""
 
-    def __init__(self, engine, batch_size, nstep, discount, sampler='philox'):
+    def __init__(self, engine, batch_size, nstep, discount, sampler='philox', weighting=None, episode_weight=None, episodes=None):
+        """weighting / episode_weight: as DeviceReplayLoader's, applied once here through engine.set_weights. The arena keeps no episode
+        dicts, so a callable episode_weight needs `episodes`: the dicts that were appended, indexed by slot id."""
         self.engine, self.batch_size, self.nstep, self.discount = engine, batch_size, nstep, discount
         self.sampler = {'mt19937': L.SAMPLER_MT19937, 'philox': L.SAMPLER_PHILOX}[sampler]
+        mode = _weighting_args(sampler, weighting, episode_weight)
+        if mode is not None:
+            if episode_weight is not None and episodes is None:
+                raise ValueError('ArenaIterator: episode_weight needs episodes=[episode dict per slot id]')
+            engine.set_weights(mode, None if episode_weight is None else [float(episode_weight(ep)) for ep in episodes])
 
     def __iter__(self):
         return self
@@ -423,8 +500,9 @@ class ArenaIterator:
 def make_replay_loader(storage, max_size, batch_size, num_workers, save_snapshot, nstep=None, discount=None, **kw):
     """replay_buffer.py:260-261 signature. Also accepts the 6-argument offline call shape that
     train_offline.py:90-93 uses — (env, replay_dir, max_size, batch_size, num_workers, discount) — which the
-    reference's own 7-parameter function rejects."""
-    if discount is None and isinstance(max_size, (str, os.PathLike)):
+    reference's own 7-parameter function rejects; there replay_dir may be a list of directories with mix=[...]
+    (make_offline_replay_loader)."""
+    if discount is None and isinstance(max_size, (str, os.PathLike, list, tuple)):
         env, replay_dir, max_size, batch_size, num_workers, discount = (storage, max_size, batch_size, num_workers,
                                                                        save_snapshot, nstep)
         return make_offline_replay_loader(env, replay_dir, max_size, batch_size, num_workers, discount, **kw)
@@ -435,18 +513,37 @@ class _DirStorage:
     """Minimal storage stand-in for a directory of pre-collected episodes (offline datasets)."""
 
     def __init__(self, replay_dir, meta_specs=()):
-        self._replay_dir = Path(replay_dir)
+        many = isinstance(replay_dir, (list, tuple))
+        self._replay_dirs = [Path(d) for d in replay_dir] if many else [Path(replay_dir)]
+        self._replay_dir = self._replay_dirs[0]
         self._meta_specs = tuple(meta_specs)
 
 
-def make_offline_replay_loader(env, replay_dir, max_size, batch_size, num_workers, discount, relabel=None, **kw):
+def make_offline_replay_loader(env, replay_dir, max_size, batch_size, num_workers, discount, relabel=None, mix=None, **kw):
     """replay_buffer.py:246-258 with OfflineReplayBuffer's semantics (:45-100): ascending one-shot load up to the first episode
     that takes the size past max_size // workers, nstep = 1, files never touched. relabel=None follows the reference's intent —
     rewards are relabelled through `env` (relabel_episode, :31-42) whenever an env is given; pass relabel=False (or env=None) to
-    train on the stored rewards. The reference's own class fails before loading anything (`_relable_reward` typo, :72 vs :84)."""
+    train on the stored rewards. The reference's own class fails before loading anything (`_relable_reward` typo, :72 vs :84).
+
+    replay_dir may be a list of directories (datasets collected by different agents, or the reward / constraint episode sets that
+    prioritized_sampling.py copies into one directory): each is selected by itself with the rule above and the same max_size, ascending
+    within a directory, directories in the order given, all in one arena. mix=[f_0, f_1, ...] (needs sampler='philox') gives the
+    fraction of samples drawn from each: every episode of dataset d gets the weight f_d / M_d (mix_weights), where
+      weighting='transitions': M_d = the dataset's total span, sum of (len - nstep + 1) over its episodes: all its transitions equally likely;
+      weighting='episodes' (the default): M_d = its number of sampleable episodes: all its episodes equally likely, then a uniform start.
+    Under data parallelism (worker_ids) every rank normalises over its own shard of each dataset. Without mix the datasets are simply
+    concatenated under `weighting`. A directory may be listed only once. weighting= and episode_weight= are DeviceReplayLoader's."""
+    many = isinstance(replay_dir, (list, tuple))
+    if mix is not None and (not many or len(mix) != len(replay_dir)):
+        raise ValueError('make_offline_replay_loader: mix needs a list of directories and one fraction per directory')
+    if many and not replay_dir:
+        raise ValueError('make_offline_replay_loader: empty list of directories')
+    if many and len({Path(d).resolve() for d in replay_dir}) != len(replay_dir):
+        raise ValueError('make_offline_replay_loader: a directory is listed twice (episodes are keyed by their path): list it once and '
+                         'give it a larger mix fraction or episode_weight instead')
     if relabel is None:
         relabel = env is not None
     if relabel and env is None:
         raise ValueError('make_offline_replay_loader: relabel=True needs the env whose task defines the reward')
     return DeviceReplayLoader(_DirStorage(replay_dir), max_size, batch_size, num_workers, True, 1, discount, static=True, offline=True,
-                              env=env, relabel=bool(relabel), **kw)
+                              env=env, relabel=bool(relabel), mix=None if mix is None else [float(f) for f in mix], **kw)

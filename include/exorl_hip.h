@@ -38,7 +38,7 @@ extern "C" {
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
-                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images) */
+                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -83,6 +83,19 @@ int exorl_replay_evict(exorl_replay_t* r, int32_t slot);
 /* Sampling order of resident episodes = the reference's sorted `_episode_fns` list (replay_buffer.py:184). */
 int exorl_replay_set_order(exorl_replay_t* r, const int32_t* slots_host, int32_t n);
 int exorl_replay_num_rows(exorl_replay_t* r, int64_t* live_rows, int64_t* used_rows);
+/* Weighted sampling for EXORL_SAMPLER_PHILOX. q_per_slot_host: one integer weight per slot id (n_slots <= slots handed out so far; the
+ * rest, and NULL, mean 1); a slot reused by exorl_replay_append_episode goes back to 1. With span_e = max(len_e - nstep + 1, 0):
+ *   EXORL_WEIGHT_EPISODES     P(episode e) ~ q_e where span_e > 0, then a uniform start        (NULL weights: the unweighted sampler)
+ *   EXORL_WEIGHT_TRANSITIONS  P(episode e) ~ q_e * span_e, then a uniform start                (NULL weights: uniform over transitions)
+ * Draw: x = philox(sample, batch counter) as unweighted; g = mulhi64(x2 << 32 | x3, total mass); the episode is the one whose interval
+ * of the running mass sum holds g; start = mulhi32(x1, span_e) + 1. Episodes shorter than nstep have mass 0 and are skipped instead of
+ * refused. A sample call fails, launching nothing, when the total mass is 0 or reaches 2^63, or when the sampler is
+ * EXORL_SAMPLER_MT19937 (the reference's stream stays unweighted); EXORL_SAMPLER_GIVEN ignores the weights. A captured graph
+ * (exorl_agent_enable_graph) holds the table of its capture: re-capture after changing weights, mode or resident episodes;
+ * exorl_agent_step_graph refuses to replay a graph captured before the latest exorl_replay_set_weights call. */
+#define EXORL_WEIGHT_EPISODES    0
+#define EXORL_WEIGHT_TRANSITIONS 1
+int exorl_replay_set_weights(exorl_replay_t* r, int32_t mode, const uint32_t* q_per_slot_host, int32_t n_slots);
 /* MT19937 states as exposed by random.getstate()[1] / np.random.get_state()[1:3]. */
 int exorl_replay_seed_mt(exorl_replay_t* r, const uint32_t* py_key624, int32_t py_pos,
                          const uint32_t* np_key624, int32_t np_pos);

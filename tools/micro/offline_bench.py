@@ -7,6 +7,9 @@
     python tools/micro/offline_bench.py td3_bc 24 6 1024 bf16x3 --metrics window --steps 2000 --warmup 200 --repeats 3
         # --metrics off (default): use_tb=False; step: use_tb=True, every update() reads its metrics; window: enable_metric_window(),
         # pop_metrics() every 1000 steps. --hidden H (default 1024). One line per repeat, then the median.
+    python tools/micro/offline_bench.py td3_bc 24 6 1024 bf16x3 --weighting transitions --episodes 10000 --steps 2000 --warmup 200 --repeats 3
+        # --weighting episodes|transitions: the weighted sampler (ReplayEngine.set_weights; the cum table and its binary search); default
+        # off: set_weights is never called. --episodes E (default 300) x --ep-len T (default 1000) transitions resident.
 """
 import json
 import sys
@@ -34,7 +37,9 @@ def option(name, default):
 METRICS, STEPS, WARMUP, REPEATS = option('--metrics', 'off'), option('--steps', 0), option('--warmup', -1), option('--repeats', 1)
 assert METRICS in ('off', 'step', 'window'), METRICS
 TB = METRICS == 'step'
-H, EPISODES, EP_LEN = option('--hidden', 1024), 300, 1000
+H, EPISODES, EP_LEN, WEIGHTING = option('--hidden', 1024), option('--episodes', 300), option('--ep-len', 1000), option('--weighting', 'off')
+assert WEIGHTING in ('off', 'episodes', 'transitions'), WEIGHTING
+TAG = '' if (WEIGHTING, EPISODES, EP_LEN) == ('off', 300, 1000) else f' weighting={WEIGHTING} episodes={EPISODES}x{EP_LEN}'
 
 
 def make(precision):
@@ -58,6 +63,8 @@ for e in range(EPISODES):
                                          action=rs.uniform(-1, 1, (rows, A)).astype(np.float32),
                                          reward=rs.uniform(0, 1, (rows, 1)).astype(np.float32), discount=np.ones((rows, 1), np.float32))))
 eng.set_order(slots)
+if WEIGHTING != 'off':       # 'episodes' with explicit unit weights: the weighted code path on the unweighted distribution
+    eng.set_weights(WEIGHTING, np.ones(EPISODES) if WEIGHTING == 'episodes' else None)
 for prec in precisions:
     torch.manual_seed(1)
     eng.seed_philox(2)
@@ -84,9 +91,9 @@ for prec in precisions:
         dt = time.perf_counter() - t0
         done += w + n
         rates.append(n / dt)
-        print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} graph={graph} metrics={METRICS}: {n / dt:8.1f} update()/s  {1e3 * dt / n:7.3f} ms', flush=True)
+        print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} graph={graph} metrics={METRICS}{TAG}: {n / dt:8.1f} update()/s  {1e3 * dt / n:7.3f} ms', flush=True)
     if REPEATS > 1:
-        print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} metrics={METRICS}: median {float(np.median(rates)):8.1f} update()/s, min {min(rates):.1f}, '
+        print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} metrics={METRICS}{TAG}: median {float(np.median(rates)):8.1f} update()/s, min {min(rates):.1f}, '
               f'max {max(rates):.1f} over {REPEATS} repeats of {n} steps', flush=True)
     if ROOFLINE:
         # the dominant kernel's launches bracketed by HIP events on the stream they run on (an instrumented eager pass of the same loop,
