@@ -101,7 +101,6 @@ struct FwdBufs {
     }
 };
 struct BwdBufs { float *dz2, *dh1; Planes dz2q; };
-struct NetShadow { float* w0t; Planes w1q, w0q; };   // W0 transposed per trunk; W1 per head ([n_heads][H][H]); W0 K-padded per trunk (hi, lo only)
 
 // Which operands the H x H products of a net read.
 enum class Route {
@@ -145,38 +144,35 @@ static int products(Route rt, int prec, int a_layout, int b_layout, const Produc
 }
 // W1 of every head -> its three plane images, one launch. Once per optimiser step (and per exorl_agent_params_changed) rather than once per use:
 // a TD3+BC step reads the critic's W1 in five launches and the actor's in two.
-static int refresh_w1_planes(const NetDesc& d, const float* P, const NetShadow& sh, hipStream_t s) {
-    if (!sh.w1q.mid) return 0;
-    return to_planes3(P + d.W1, d.H, d.H, d.H, sh.w1q.hi, sh.w1q.mid, sh.w1q.lo, d.H, d.H, d.n_heads, d.head_stride, (int64_t)d.H * d.H, s);
+static int refresh_w1_planes(const NetDesc& d, const float* P, const WeightImages& sh, hipStream_t s) {
+    if (!sh.w1.mid) return 0;
+    return to_planes3(P + d.W1, d.H, d.H, d.H, sh.w1.hi, sh.w1.mid, sh.w1.lo, d.H, d.H, d.n_heads, d.head_stride, w1_plane_size(d.H), s);
 }
 struct Partials { float *Ph, *Pt, *Pw; };                  // per-chunk partial gradients (fused.hip)
 
-static ShadowSpec shadow_spec(const NetDesc& d, const NetShadow& sh, const NetShadow* target) {
+static ShadowSpec shadow_spec(const NetDesc& d, const WeightImages& sh, const WeightImages* target) {
     ShadowSpec s{};
     s.n_trunks = d.n_trunks; s.n_heads = d.n_heads; s.in_dim = d.in_dim; s.H = d.H;
     for (int t = 0; t < d.n_trunks; ++t) s.w0_off[t] = d.W0 + t * d.trunk_stride;
     for (int i = 0; i < d.n_heads; ++i) s.w1_off[i] = d.W1 + i * d.head_stride;
+    s.own = sh;
+    if (target) s.target = *target;
     // the optimiser kernel keeps the one- and two-plane images current; three-plane images are refresh_w1_planes' and stay out of its sight
-    const NetShadow none{};
-    const NetShadow& t = target ? *target : none;
-    const bool own = !sh.w1q.mid;
-    s.w0t = sh.w0t; s.t_w0t = t.w0t;
-    if (own) { s.w1b = sh.w1q.hi; s.w1l = sh.w1q.lo; s.t_w1b = t.w1q.hi; s.t_w1l = t.w1q.lo; }
-    s.w0b = sh.w0q.hi; s.w0l = sh.w0q.lo; s.t_w0b = t.w0q.hi; s.t_w0l = t.w0q.lo;
+    if (sh.w1.mid) s.own.w1 = s.target.w1 = Planes{};
     return s;
 }
 
-static int net_forward(const NetDesc& d, const float* P, const NetShadow& sh, const float* x, int64_t ldx, int rows,
+static int net_forward(const NetDesc& d, const float* P, const WeightImages& sh, const float* x, int64_t ldx, int rows,
                        const FwdBufs& f, bool save, bool tanh_out, int prec, hipStream_t s, const SampleSpec* sample = nullptr,
                        bool no_head = false) {
     const int H = d.H;
     const int64_t act = (int64_t)rows * H;
-    const Route rt = route_of(prec, f.h1q, sh.w1q, rows);
+    const Route rt = route_of(prec, f.h1q, sh.w1, rows);
     const bool bf = rt == Route::Planes;
     // fast mode keeps the trunk activations as bf16 only (MFMA operand + LN backward input): 4 B/elem written instead of 10. The MFMA trunk needs
     // W0's image and H % 128 == 0; plain bf16 at other widths (H = 192) takes the fp32 trunk kernel with bf16 outputs.
-    if (bf && sh.w0q && trunk_fwd16_supported(H))
-        EXORL_TRY(trunk_fwd16(x, ldx, sh.w0q, P + d.b0, P + d.g, P + d.beta, save ? f.rstd : nullptr, f.h1q, save ? f.xhatq : Planes{}, rows,
+    if (bf && sh.w0 && trunk_fwd16_supported(H))
+        EXORL_TRY(trunk_fwd16(x, ldx, sh.w0, P + d.b0, P + d.g, P + d.beta, save ? f.rstd : nullptr, f.h1q, save ? f.xhatq : Planes{}, rows,
                               d.in_dim, H, d.n_trunks, act, d.trunk_stride, s));
     else
         EXORL_TRY(trunk_fwd(x, ldx, sh.w0t, P + d.b0, P + d.g, P + d.beta, bf ? nullptr : f.h1, (save && !bf) ? f.xhat : nullptr,
@@ -186,7 +182,7 @@ static int net_forward(const NetDesc& d, const float* P, const NetShadow& sh, co
     Product p[2];
     for (int i = 0; i < d.n_heads; ++i) {        // h2_i = relu(h1 W1_i^T + b1_i), head i on trunk i (paired) or on the one trunk (shared)
         const int64_t t = (d.n_trunks == d.n_heads ? i : 0) * act;
-        p[i] = Product{Operand(f.h1, t, f.h1q, t), Operand(P + d.W1, i * d.head_stride, sh.w1q, (int64_t)i * H * H), f.h2 + i * act,
+        p[i] = Product{Operand(f.h1, t, f.h1q, t), Operand(P + d.W1, i * d.head_stride, sh.w1, i * w1_plane_size(H)), f.h2 + i * act,
                        P + d.b1 + i * d.head_stride, rows, H, H};
     }
     EXORL_TRY(products(rt, prec, 0, 0, p, d.n_heads, H, true, false, s));
@@ -202,19 +198,19 @@ static int net_forward(const NetDesc& d, const float* P, const NetShadow& sh, co
 
 // The critic on (obs, a_data) and its Polyak target on (next_obs, next_action) in shared launches (bf16 mode): the two forward
 // chains are independent, same shapes, different weights -> 3 launches instead of 6, each filling the chip twice as deep.
-static bool forward2_supported(const NetDesc& d, int prec, const NetShadow& sa, const FwdBufs& fa, const NetShadow& sb, const FwdBufs& fb, int rows) {
-    const bool planes = route_of(prec, fa.h1q, sa.w1q, rows) == Route::Planes && route_of(prec, fb.h1q, sb.w1q, rows) == Route::Planes;
-    return planes && sa.w0q && sb.w0q && trunk_fwd16_supported(d.H) && d.out_dim == 1 && d.n_heads == 2 && d.H % 4 == 0;
+static bool forward2_supported(const NetDesc& d, int prec, const WeightImages& sa, const FwdBufs& fa, const WeightImages& sb, const FwdBufs& fb, int rows) {
+    const bool planes = route_of(prec, fa.h1q, sa.w1, rows) == Route::Planes && route_of(prec, fb.h1q, sb.w1, rows) == Route::Planes;
+    return planes && sa.w0 && sb.w0 && trunk_fwd16_supported(d.H) && d.out_dim == 1 && d.n_heads == 2 && d.H % 4 == 0;
 }
 // fold_a (with no_head): net A's scalar heads are folded into the GEMM epilogue (Gemm16Problem::head_part) when the launch takes the 128 x TN
 // kernels — A's h2 buffer then holds, per head, rows x *slots_a partial dots instead of hidden activations (qhead sums them)
-static int net_forward2(const NetDesc& d, const float* Pa, const NetShadow& sa, const float* xa, const FwdBufs& fa, bool save_a,
-                        const float* Pb, const NetShadow& sb, const float* xb, const FwdBufs& fb, bool save_b, int64_t ldx, int rows,
+static int net_forward2(const NetDesc& d, const float* Pa, const WeightImages& sa, const float* xa, const FwdBufs& fa, bool save_a,
+                        const float* Pb, const WeightImages& sb, const float* xb, const FwdBufs& fb, bool save_b, int64_t ldx, int rows,
                         hipStream_t s, bool no_head = false, bool fold_a = false, int* slots_a = nullptr) {
     const int H = d.H;
-    const int64_t act = (int64_t)rows * H, wst = (int64_t)H * round_up(d.in_dim, 32);
+    const int64_t act = (int64_t)rows * H, wst = w0_plane_size(d.in_dim, H);
     const float* P[2] = {Pa, Pb};
-    const NetShadow* sh[2] = {&sa, &sb};
+    const WeightImages* sh[2] = {&sa, &sb};
     const float* x[2] = {xa, xb};
     const FwdBufs* f[2] = {&fa, &fb};
     const bool save[2] = {save_a, save_b};
@@ -222,7 +218,7 @@ static int net_forward2(const NetDesc& d, const float* Pa, const NetShadow& sa, 
     int nt = 0;
     for (int k = 0; k < 2; ++k)
         for (int t = 0; t < d.n_trunks; ++t) {
-            const Planes w = sh[k]->w0q.at(t * wst), h = f[k]->h1q.at(t * act), xh = save[k] ? f[k]->xhatq.at(t * act) : Planes{};
+            const Planes w = sh[k]->w0.at(t * wst), h = f[k]->h1q.at(t * act), xh = save[k] ? f[k]->xhatq.at(t * act) : Planes{};
             tb.it[nt++] = TrunkItem{x[k], w.hi, P[k] + d.b0 + t * d.trunk_stride, P[k] + d.g + t * d.trunk_stride, P[k] + d.beta + t * d.trunk_stride,
                                     save[k] ? f[k]->rstd + (int64_t)t * rows : nullptr, h.hi, xh.hi, w.lo, h.lo, xh.lo};
         }
@@ -232,7 +228,7 @@ static int net_forward2(const NetDesc& d, const float* Pa, const NetShadow& sa, 
     int nq = 0;
     for (int k = 0; k < 2; ++k)
         for (int i = 0; i < d.n_heads; ++i) {
-            q[nq] = g16(f[k]->h1q.at((d.n_trunks == d.n_heads ? i : 0) * act), sh[k]->w1q.at((int64_t)i * H * H), f[k]->h2 + i * act,
+            q[nq] = g16(f[k]->h1q.at((d.n_trunks == d.n_heads ? i : 0) * act), sh[k]->w1.at(i * w1_plane_size(H)), f[k]->h2 + i * act,
                         P[k] + d.b1 + i * d.head_stride, rows, H, H, H);
             hb.it[nq] = HeadItem{f[k]->h2 + i * act, P[k] + d.W2 + i * d.head_stride, P[k] + d.b2 + i * d.head_stride, f[k]->out + (int64_t)i * rows};
             ++nq;
@@ -255,13 +251,13 @@ static int net_forward2(const NetDesc& d, const float* Pa, const NetShadow& sa, 
 
 // G == nullptr: dgrad only (no parameter gradients). dx (n_trunks x rows x dx_cols, one slab per trunk — the
 // consumer adds them) receives d/dx[:, col0:col0+dx_cols].
-static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, float* G, const Partials& pt, const float* x,
+static int net_backward(const NetDesc& d, const float* P, const WeightImages& sh, float* G, const Partials& pt, const float* x,
                         int64_t ldx, int rows, const FwdBufs& f, const DoutSpec& dout, const BwdBufs& b, float* dx, int dx_col0,
                         int dx_cols, int prec, hipStream_t s, const Fork& fk, FinalizeArgs* defer = nullptr, bool have_dz2 = false) {
     const int H = d.H;
     const int64_t act = (int64_t)rows * H;
     const bool paired = d.n_trunks == d.n_heads;
-    Route rt = route_of(prec, f.h1q, sh.w1q, rows);
+    Route rt = route_of(prec, f.h1q, sh.w1, rows);
     if (rt == Route::Planes3 && !b.dz2q) rt = Route::F32;      // the three-plane kernel wants dz2's images too
     const bool bf = rt == Route::Planes;
     // the bf16 route's row kernels read and write the images in place of the fp32 buffers; on the other routes they see no image
@@ -286,7 +282,7 @@ static int net_backward(const NetDesc& d, const float* P, const NetShadow& sh, f
                        G + d.W1 + i * d.head_stride, nullptr, H, H, kr};
     };
     auto dgrad = [&](int i) {                      // dh1[m][k] = sum_n dz2_i[m][n] W1_i[n][k]
-        return Product{Operand(b.dz2, i * act, b.dz2q, i * act), Operand(P + d.W1, i * d.head_stride, sh.w1q, (int64_t)i * H * H),
+        return Product{Operand(b.dz2, i * act, b.dz2q, i * act), Operand(P + d.W1, i * d.head_stride, sh.w1, i * w1_plane_size(H)),
                        b.dh1 + trunk_of(i), nullptr, rows, H, H};
     };
     Product p[2];
@@ -387,7 +383,7 @@ struct exorl_agent {
     CqlScalars* cql = nullptr;                      // CQL: log_actor_alpha + Adam moments + alpha (device)
     float *xc_rep = nullptr, *crr_w = nullptr;     // CRR: repeated (obs, sampled action) inputs; advantage weights
     FwdBufs fr{};                                   // CRR: critic forward on B*num_value_samples rows (no grad)
-    NetShadow sh_actor{}, sh_critic{}, sh_target{};
+    WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
     float *stats = nullptr, *metrics = nullptr;      // contiguous: stats[4] then metrics[EXORL_N_METRICS]
@@ -480,8 +476,8 @@ static void carve(exorl_agent* a, Carver& c) {
         return b;
     };
     auto take_shadow = [&](int64_t n_trunks, int64_t n_heads, int64_t in_dim) {      // W0 has no three-plane image: the trunk kernels read fp32
-        NetShadow sh{c.take(n_trunks * in_dim * H), {}, {}};
-        take_hi_lo(sh.w1q, n_heads * H * H, &sh.w0q, n_trunks * H * round_up(in_dim, 32), nb);
+        WeightImages sh{c.take(n_trunks * w0t_size(in_dim, H)), {}, {}};
+        take_hi_lo(sh.w1, n_heads * w1_plane_size(H), &sh.w0, n_trunks * w0_plane_size(in_dim, H), nb);
         return sh;
     };
     c.scratch = true;       // from here on: c.scratch says whether a step writes the sub-buffer before it reads it (see Carver)
@@ -492,7 +488,7 @@ static void carve(exorl_agent* a, Carver& c) {
     three_planes(a->ba.dz2q, B * H);
     c.scratch = false;
     a->sh_actor = take_shadow(1, 1, O);
-    three_planes(a->sh_actor.w1q, H * H);
+    three_planes(a->sh_actor.w1, w1_plane_size(H));
     c.scratch = true;
     a->pa = Partials{c.take((int64_t)head_chunks(B) * ((AO + 1) * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
                      c.take((int64_t)outer_chunks(B) * O * H)};
@@ -538,8 +534,8 @@ static void carve(exorl_agent* a, Carver& c) {
         c.scratch = false;
         a->sh_critic = take_shadow(nt, 2, W);
         a->sh_target = take_shadow(nt, 2, W);
-        three_planes(a->sh_critic.w1q, 2 * H * H);
-        three_planes(a->sh_target.w1q, 2 * H * H);
+        three_planes(a->sh_critic.w1, 2 * w1_plane_size(H));
+        three_planes(a->sh_target.w1, 2 * w1_plane_size(H));
         c.scratch = true;
         a->pc = Partials{c.take(2 * (int64_t)qhead_chunks(RC) * ((od + 1) * H + 32)), c.take(nt * (int64_t)trunk_chunks(RC) * 3 * H),
                          c.take(nt * (int64_t)outer_chunks(RC) * W * H)};
@@ -650,7 +646,7 @@ static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
     const int64_t act = (int64_t)B * H;
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
     const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
-    const bool bf = route_of(a->cfg.precision, a->fc.h1q, a->sh_critic.w1q, B) == Route::Planes;       // as net_backward decides it
+    const bool bf = route_of(a->cfg.precision, a->fc.h1q, a->sh_critic.w1, B) == Route::Planes;       // as net_backward decides it
     QHeadArgs q{};
     for (int i = 0; i < 2; ++i) {
         q.a[i] = a->fc.h2 + i * act; q.W[i] = Pc + d.W2 + i * d.head_stride; q.b[i] = Pc + d.b2 + i * d.head_stride;
@@ -1157,8 +1153,8 @@ int exorl_agent_act(exorl_agent_t* a, const float* obs, int32_t n, float stddev,
     if (act_fast_ok(a, n)) return act_fast_launch(a, obs, nullptr, n, stddev, eval_mode, noise, nullptr, out, s);
     for (int r0 = 0; r0 < n; r0 += ACT_ROWS) {
         const int rows = n - r0 < ACT_ROWS ? n - r0 : ACT_ROWS;
-        NetShadow sh = a->sh_actor;                 // act() rows do not tile by 64: split-bf16 takes the in-GEMM split here
-        sh.w1q.lo = sh.w0q.lo = nullptr;
+        WeightImages sh = a->sh_actor;              // act() rows do not tile by 64: split-bf16 takes the in-GEMM split here
+        sh.w1.lo = sh.w0.lo = nullptr;
         EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], sh, obs + (int64_t)r0 * O, O, rows, a->fact, false,
                               a->cfg.kind != EXORL_AGENT_CQL,
                               a->cfg.precision, s));
@@ -1314,8 +1310,8 @@ int exorl_debug_agent_weight_images(exorl_agent_t* a, int32_t net, exorl_weight_
     EXORL_REQUIRE(a && out, "debug_agent_weight_images: null argument");
     const NetDesc* d = net_of(a, net);
     EXORL_REQUIRE(d, "debug_agent_weight_images: agent has no net %d", net);
-    const NetShadow& sh = net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_CRITIC ? a->sh_critic : a->sh_target;
-    *out = exorl_weight_images{d->n_trunks, d->n_heads, d->in_dim, d->H, sh.w0t, sh.w0q.hi, sh.w0q.lo, sh.w1q.hi, sh.w1q.mid, sh.w1q.lo};
+    const WeightImages& sh = net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_CRITIC ? a->sh_critic : a->sh_target;
+    *out = exorl_weight_images{d->n_trunks, d->n_heads, d->in_dim, d->H, sh.w0t, sh.w0.hi, sh.w0.lo, sh.w1.hi, sh.w1.mid, sh.w1.lo};
     return 0;
 }
 

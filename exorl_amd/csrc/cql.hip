@@ -6,20 +6,8 @@
 
 namespace exorl {
 
-__device__ __forceinline__ float philox_normal_k(uint64_t seed, uint64_t counter, uint32_t elem) {
-    uint32_t c[4] = {elem, 0u, (uint32_t)counter, (uint32_t)(counter >> 32)};
-    Philox::gen(c, seed);
-    const float u1 = ((float)c[0] + 1.0f) * 2.3283064365386963e-10f;
-    const float u2 = (float)c[1] * 2.3283064365386963e-10f;
-    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-}
-__device__ __forceinline__ float philox_uniform_pm1(uint64_t seed, uint64_t counter, uint32_t elem) {
-    uint32_t c[4] = {elem, 1u, (uint32_t)counter, (uint32_t)(counter >> 32)};
-    Philox::gen(c, seed);
-    return -1.0f + 2.0f * ((float)c[0] * 2.3283064365386963e-10f);
-}
 __device__ __forceinline__ float draw(const float* buf, const CqlNoise& nz, int k, int64_t e) {
-    return buf ? buf[e] : philox_normal_k(nz.seed, (nz.counter_ptr ? *nz.counter_ptr : 0ull) * 8 + k, (uint32_t)e);
+    return buf ? buf[e] : philox_normal(nz.seed, (nz.counter_ptr ? *nz.counter_ptr : 0ull) * 8 + k, (uint32_t)e);
 }
 
 // mu = tanh(raw[:A]); std = exp(clamp(raw[A:], -10, 2))   (cql.py:24-28)
@@ -57,7 +45,7 @@ __global__ __launch_bounds__(256) void cql_build_inputs_kernel(const float* __re
         if (blk == 3) {
             v = action[(int64_t)b * A + j];
         } else if (blk == 0) {
-            v = nz.u_rand ? nz.u_rand[e] : philox_uniform_pm1(nz.seed, (nz.counter_ptr ? *nz.counter_ptr : 0ull) * 8 + 1, (uint32_t)e);
+            v = nz.u_rand ? nz.u_rand[e] : philox_uniform_pm1(nz.seed, (nz.counter_ptr ? *nz.counter_ptr : 0ull) * 8 + 1, (uint32_t)e, PHILOX_CQL_UNIFORM);
         } else {
             float mu, sd;
             policy_of(raw2 + (int64_t)(blk == 1 ? B + b : b) * 2 * A, A, j, mu, sd);      // rows B.. = obs half of the stacked forward
@@ -75,25 +63,6 @@ int cql_build_inputs(const float* obs, const float* action, const float* raw2, C
     hipLaunchKernelGGL(cql_build_inputs_kernel, dim3(blocks), dim3(256), 0, s, obs, action, raw2, nz, xc_next, x_all, B, O, A, n);
     EXORL_LAUNCH_CHECK();
     return 0;
-}
-
-template <int NV>
-__device__ __forceinline__ void block_sum_c(float (&v)[NV], float (*sm)[16]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float s = wave_sum(v[i]);
-        if (lane == 0) sm[i][wave] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        float t = 0.f;
-        for (int w = 0; w < nw; ++w) t += sm[i][w];
-        v[i] = t;
-    }
-    __syncthreads();
 }
 
 // critic_loss = mse(Q1,y) + mse(Q2,y) + alpha * (mean_b lse1 + mean_b lse2 - mean(Q1+Q2))      (cql.py:162-223)
@@ -128,7 +97,7 @@ __global__ __launch_bounds__(1024) void cql_critic_dq_kernel(const float* __rest
             v[6] += qd;
         }
     }
-    block_sum_c<7>(v, sm);
+    block_sum<7>(v, sm);
     // Data parallel with the Lagrange multiplier (mode 1, then 2; gsum = two floats of the agent's statistics block): the multiplier's step
     // needs the penalty of the GLOBAL batch before any gradient can be formed, so a first launch only leaves this rank's two sums
     // (sum lse, sum Q1 + Q2), the host sum-all-reduces them, and the second launch steps the multiplier from the global penalty — the same
@@ -214,7 +183,7 @@ __global__ __launch_bounds__(1024) void cql_actor_sample_kernel(const float* __r
         xc_pi[(int64_t)b * ld + O + j] = tanhf(x);
         v[0] += squashed_log_prob(x, z, sd);
     }
-    block_sum_c<1>(v, sm);
+    block_sum<1>(v, sm);
     if (threadIdx.x == 0) { stats[0] = v[0]; stats[1] = 0.f; stats[2] = 0.f; stats[3] = 0.f; }
 }
 
@@ -233,7 +202,7 @@ __global__ __launch_bounds__(1024) void cql_alpha_step_kernel(CqlScalars* sc, co
     __shared__ float sm[1][16];
     float v[1] = {0.f};
     for (int b = threadIdx.x; b < B; b += blockDim.x) v[0] += fminf(q[b], q[B + b]);
-    block_sum_c<1>(v, sm);
+    block_sum<1>(v, sm);
     if (threadIdx.x != 0) return;
     const AdamConst c = *cp;
     const float mean_lp = stats[0] * inv_bg / (float)A;
@@ -269,7 +238,7 @@ __global__ void cql_act_kernel(const float* __restrict__ raw, const float* __res
         const int b = i / A, j = i % A;
         float mu, sd;
         policy_of(raw + (int64_t)b * 2 * A, A, j, mu, sd);
-        const float z = eval_mode ? 0.f : (noise ? noise[i] : philox_normal_k(seed, counter, (uint32_t)i));
+        const float z = eval_mode ? 0.f : (noise ? noise[i] : philox_normal(seed, counter, (uint32_t)i));
         out[i] = tanhf(mu + sd * z);
     }
 }

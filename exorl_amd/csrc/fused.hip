@@ -16,16 +16,6 @@ namespace exorl {
 
 constexpr int MAX_IN = 256;       // first-layer fan-in limit of the fused trunk kernels
 constexpr float LN_EPS2 = 1e-5f;
-typedef __bf16 bf16_t;
-
-__device__ __forceinline__ unsigned short f2bf(float x) {
-    bf16_t b = (bf16_t)x;
-    return __builtin_bit_cast(unsigned short, b);
-}
-// lo plane of the split-bf16 representation x = hi + lo, hi = bf16(x)
-__device__ __forceinline__ unsigned short f2bf_lo(float x) { return f2bf(x - __uint_as_float((unsigned)f2bf(x) << 16)); }
-__device__ __forceinline__ ushort4 f4_to_bf4(const float4& v) { ushort4 q; q.x = f2bf(v.x); q.y = f2bf(v.y); q.z = f2bf(v.z); q.w = f2bf(v.w); return q; }
-__device__ __forceinline__ ushort4 f4_to_bf4_lo(const float4& v) { ushort4 q; q.x = f2bf_lo(v.x); q.y = f2bf_lo(v.y); q.z = f2bf_lo(v.z); q.w = f2bf_lo(v.w); return q; }
 
 // ------------------------------------------------------------------------------------------------
 // trunk forward: h = tanh(LN(x W0^T + b0) * g + beta).
@@ -152,12 +142,12 @@ __global__ __launch_bounds__(512) void trunk_fwd_kernel(const float* __restrict_
         if (xhat) reinterpret_cast<float4*>(xhat + o)[c4] = xh;
         if (hb) {
             ushort4 q;
-            q.x = f2bf(hv.x); q.y = f2bf(hv.y); q.z = f2bf(hv.z); q.w = f2bf(hv.w);
+            q.x = bf16_bits(hv.x); q.y = bf16_bits(hv.y); q.z = bf16_bits(hv.z); q.w = bf16_bits(hv.w);
             reinterpret_cast<ushort4*>(hb + o)[c4] = q;
         }
         if (xhb) {
             ushort4 q;
-            q.x = f2bf(xh.x); q.y = f2bf(xh.y); q.z = f2bf(xh.z); q.w = f2bf(xh.w);
+            q.x = bf16_bits(xh.x); q.y = bf16_bits(xh.y); q.z = bf16_bits(xh.z); q.w = bf16_bits(xh.w);
             reinterpret_cast<ushort4*>(xhb + o)[c4] = q;
         }
     }
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(512) void trunk_fwd16_kernel(const TrunkBatch tb, i
         for (int j = 0; j < 8; ++j) {
             const float xv = (live && kb + j < in_dim) ? xs[j] : 0.f;
             bx[j] = (__bf16)xv;
-            if constexpr (X3) bxl[j] = (__bf16)(xv - (float)bx[j]);
+            if constexpr (X3) bxl[j] = (__bf16)bf16_residual(xv);
         }
         bf16x8_t aw[T];
 #pragma unroll
@@ -295,7 +285,7 @@ __global__ __launch_bounds__(512) void trunk_fwd16_kernel(const TrunkBatch tb, i
     auto flush = [&](unsigned short* __restrict__ plane, const float4 (&v)[T], bool lo) {
 #pragma unroll
         for (int t = 0; t < T; ++t)
-            *reinterpret_cast<ushort4*>(mine + rn * TF16_LD(T) + t * 16 + 4 * kq) = lo ? f4_to_bf4_lo(v[t]) : f4_to_bf4(v[t]);
+            *reinterpret_cast<ushort4*>(mine + rn * TF16_LD(T) + t * 16 + 4 * kq) = lo ? bf16_lo_bits4(v[t]) : bf16_bits4(v[t]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int idx = lane; idx < 32 * T; idx += 64) {
@@ -370,7 +360,7 @@ __global__ __launch_bounds__(512) void trunk_fwd8_kernel(const TrunkBatch tb, in
         for (int j = 0; j < 8; ++j) {
             const float xv = (live && kb + j < in_dim) ? xs[j] : 0.f;
             const __bf16 hi = (__bf16)xv;
-            const __bf16 lo = (__bf16)(xv - (float)hi);
+            const __bf16 lo = (__bf16)bf16_residual(xv);
             const __bf16 zero = (__bf16)0.f;
             b0[j] = half ? zero : hi; b1[j] = half ? hi : zero;
             b0l[j] = half ? zero : lo; b1l[j] = half ? lo : zero;
@@ -439,7 +429,7 @@ __global__ __launch_bounds__(512) void trunk_fwd8_kernel(const TrunkBatch tb, in
     auto flush = [&](unsigned short* __restrict__ plane, const float4 (&v)[TP], bool lo) {
 #pragma unroll
         for (int p = 0; p < TP; ++p)
-            *reinterpret_cast<ushort4*>(mine + r8 * TF16_LD(T) + (p + TP * half) * 16 + 4 * kq) = lo ? f4_to_bf4_lo(v[p]) : f4_to_bf4(v[p]);
+            *reinterpret_cast<ushort4*>(mine + r8 * TF16_LD(T) + (p + TP * half) * 16 + 4 * kq) = lo ? bf16_lo_bits4(v[p]) : bf16_bits4(v[p]);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int idx = lane; idx < 16 * T; idx += 64) {
@@ -829,14 +819,6 @@ int outer_chunks(int rows) { return cdiv(rows, OR_ROWS * or_iters(rows)); }
 // 8-lane groups. Returns the wave total of value (lane & 7) in every lane.
 // ------------------------------------------------------------------------------------------------
 // head forward v2: out[m][j] = b[j] + sum_c a[m][c] W[j][c]; one wave per row, float4 streams (H % 4 == 0)
-__device__ __forceinline__ float philox_normal_f(uint64_t seed, uint64_t counter, uint32_t elem) {
-    uint32_t c[4] = {elem, 0u, (uint32_t)counter, (uint32_t)(counter >> 32)};
-    Philox::gen(c, seed);
-    const float u1 = ((float)c[0] + 1.0f) * 2.3283064365386963e-10f;
-    const float u2 = (float)c[1] * 2.3283064365386963e-10f;
-    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-}
-
 template <int NO>
 __global__ __launch_bounds__(256) void head_fwd4_kernel(const float* __restrict__ a, const float* __restrict__ W,
                                                         const float* __restrict__ b, float* __restrict__ out, int rows,
@@ -887,7 +869,7 @@ __global__ __launch_bounds__(256) void head_fwd4_kernel(const float* __restrict_
                 if (sp.dst_next) {                   // TruncatedNormal(mu, std).sample(clip) (utils.py:139-149)
                     const int half = row >= sp.B, m = half ? row - sp.B : row, e = m * nout + j;
                     const float* nb = half ? sp.noise_a : sp.noise_c;
-                    const float z = nb ? nb[e] : philox_normal_f(sp.seed, (uint64_t)half + (sp.counter_ptr ? *sp.counter_ptr : 0ull), (uint32_t)e);
+                    const float z = nb ? nb[e] : philox_normal(sp.seed, (uint64_t)half + (sp.counter_ptr ? *sp.counter_ptr : 0ull), (uint32_t)e);
                     const float eps = fminf(fmaxf(z * (sp.stddev_ptr ? *sp.stddev_ptr : sp.stddev), -sp.clip), sp.clip);
                     const float x = fminf(fmaxf(v + eps, -1.0f + 1e-6f), 1.0f - 1e-6f);
                     (half ? sp.dst_pi : sp.dst_next)[(int64_t)m * sp.dst_ld + j] = x;
@@ -959,7 +941,7 @@ __device__ __forceinline__ float dout_value(const DoutSpec& d, int net, int m, i
         const float ls = rr[A + jj];
         const float sd = expf(fminf(fmaxf(ls, -10.0f), 2.0f));
         const int e = m * A + jj;
-        const float z = d.z ? d.z[e] : philox_normal_f(d.seed, (d.counter_ptr ? *d.counter_ptr : 0ull) * 8 + d.counter, (uint32_t)e);
+        const float z = d.z ? d.z[e] : philox_normal(d.seed, (d.counter_ptr ? *d.counter_ptr : 0ull) * 8 + d.counter, (uint32_t)e);
         const float y = tanhf(mu + sd * z);
         float dy = 0.f;
         for (int t = 0; t < d.da_nets; ++t) dy += d.da[((int64_t)t * rows + m) * A + jj];
@@ -1095,8 +1077,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
         v.x = av.x > 0.f ? sacc.x : 0.f; v.y = av.y > 0.f ? sacc.y : 0.f;
         v.z = av.z > 0.f ? sacc.z : 0.f; v.w = av.w > 0.f ? sacc.w : 0.f;
         if (dz) reinterpret_cast<float4*>(dz + o)[c4] = v;
-        if (dzb) reinterpret_cast<ushort4*>(dzb + o)[c4] = f4_to_bf4(v);
-        if (dzl) reinterpret_cast<ushort4*>(dzl + o)[c4] = f4_to_bf4_lo(v);
+        if (dzb) reinterpret_cast<ushort4*>(dzb + o)[c4] = bf16_bits4(v);
+        if (dzl) reinterpret_cast<ushort4*>(dzl + o)[c4] = bf16_lo_bits4(v);
         pb.x += v.x; pb.y += v.y; pb.z += v.z; pb.w += v.w;
     }
     if (want_params) {
@@ -1168,8 +1150,8 @@ __global__ __launch_bounds__(256) void head_bwd_wide_kernel(const DoutSpec dspec
         }
         const float v = av > 0.f ? sacc : 0.f;
         if (dz) dz[o] = v;
-        if (dzb) dzb[o] = f2bf(v);
-        if (dzl) dzl[o] = f2bf_lo(v);
+        if (dzb) dzb[o] = bf16_bits(v);
+        if (dzl) dzl[o] = bf16_lo_bits(v);
         pb += v;
     }
     if (want_params) {
@@ -1319,8 +1301,8 @@ __global__ __launch_bounds__(256) void qhead_kernel(const QHeadArgs g) {
             v.z = av.z > 0.f ? d * w[n].z : 0.f; v.w = av.w > 0.f ? d * w[n].w : 0.f;
             const int64_t o = n * g.act + (int64_t)(row0 + r) * H;
             if (g.dz) reinterpret_cast<float4*>(g.dz + o)[c4] = v;
-            if (g.dzb) reinterpret_cast<ushort4*>(g.dzb + o)[c4] = f4_to_bf4(v);
-            if (g.dzl) reinterpret_cast<ushort4*>(g.dzl + o)[c4] = f4_to_bf4_lo(v);
+            if (g.dzb) reinterpret_cast<ushort4*>(g.dzb + o)[c4] = bf16_bits4(v);
+            if (g.dzl) reinterpret_cast<ushort4*>(g.dzl + o)[c4] = bf16_lo_bits4(v);
             pb.x += v.x; pb.y += v.y; pb.z += v.z; pb.w += v.w;
         }
         if (Pn) {
@@ -1403,7 +1385,18 @@ __device__ __forceinline__ void step_small(const FusedAdamArgs& a, const AdamCon
 __device__ __forceinline__ float4 ld4(const float* p, int64_t i4) { return reinterpret_cast<const float4*>(p)[i4]; }
 __device__ __forceinline__ void st4(float* p, int64_t i4, const float4& v) { reinterpret_cast<float4*>(p)[i4] = v; }
 
-__global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, FusedAdamArgs a, ShadowSpec sh, int nb_fin) {
+// This kernel's view of a ShadowSpec: the image pointers loose (t_*: the Polyak target's; *l: lo planes) behind the geometry, which the kernel
+// does not read. It is the argument block the kernel's code was tuned with: with ShadowSpec itself as the argument the CQL step came out slower
+// than the run-to-run spread, so finalize_adam converts at the launch.
+struct FlatShadows {
+    int n_trunks, n_heads, in_dim, H;
+    int64_t w0_off[2], w1_off[2];
+    float* w0t; unsigned short *w1b, *w0b;
+    float* t_w0t; unsigned short *t_w1b, *t_w0b;
+    unsigned short *w1l, *w0l, *t_w1l, *t_w0l;
+};
+
+__global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, FusedAdamArgs a, FlatShadows sh, int nb_fin) {
     const AdamConst c = *a.c;
     if (a.bump && blockIdx.x == 0 && threadIdx.x == 0) *a.bump += 1ull;
     const int H = f.H;
@@ -1431,12 +1424,12 @@ __global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, Fuse
                 st4(a.p, gi4 + u, pv[u]);
                 st4(a.m, gi4 + u, mv[u]);
                 st4(a.v, gi4 + u, vv[u]);
-                bh[u] = f4_to_bf4(pv[u]); bl[u] = f4_to_bf4_lo(pv[u]);
+                bh[u] = bf16_bits4(pv[u]); bl[u] = bf16_lo_bits4(pv[u]);
                 if (a.target) {
                     tv[u].x = polyak(pv[u].x, tv[u].x, c.tau, c.one_minus_tau); tv[u].y = polyak(pv[u].y, tv[u].y, c.tau, c.one_minus_tau);
                     tv[u].z = polyak(pv[u].z, tv[u].z, c.tau, c.one_minus_tau); tv[u].w = polyak(pv[u].w, tv[u].w, c.tau, c.one_minus_tau);
                     st4(a.target, gi4 + u, tv[u]);
-                    th[u] = f4_to_bf4(tv[u]); tl[u] = f4_to_bf4_lo(tv[u]);
+                    th[u] = bf16_bits4(tv[u]); tl[u] = bf16_lo_bits4(tv[u]);
                 }
             }
             auto pack = [](const ushort4& x, const ushort4& y) {
@@ -1458,7 +1451,7 @@ __global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, Fuse
     const int64_t nt = 3 * (int64_t)H;
     const int64_t nw = (int64_t)f.in_dim * H;
     const int64_t total = f.n_heads * nh + f.n_trunks * (nt + nw);
-    const int64_t Kp = (f.in_dim + 31) / 32 * 32;
+    const int64_t Kp = (f.in_dim + 31) / 32 * 32;      // w0_kp(f.in_dim)
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)nb_fin * blockDim.x) {
         float pn, tn;
         if (i < f.n_heads * nh) {
@@ -1484,14 +1477,14 @@ __global__ __launch_bounds__(256) void finalize_adam_kernel(FinalizeArgs f, Fuse
                 const float sacc = chunk_sum(f.Pw + (int64_t)net * f.w_chunks * nw + ew, f.w_chunks, nw);
                 const int k = (int)(ew / H), cc = (int)(ew % H);
                 step_small(a, c, base + f.gW0 + (int64_t)cc * f.in_dim + k, sacc, pn, tn);
-                // derived copies of the first-layer weight (ShadowSpec): transposed fp32 and K-padded bf16
+                // W0's images (w0t_index, w0_plane_index of kernels.h, spelled as this kernel has always had them)
                 sh.w0t[net * nw + (int64_t)k * H + cc] = pn;
-                if (sh.w0b) sh.w0b[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = f2bf(pn);
-                if (sh.w0l) sh.w0l[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = f2bf_lo(pn);
+                if (sh.w0b) sh.w0b[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = bf16_bits(pn);
+                if (sh.w0l) sh.w0l[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = bf16_lo_bits(pn);
                 if (a.target && sh.t_w0t) {
                     sh.t_w0t[net * nw + (int64_t)k * H + cc] = tn;
-                    if (sh.t_w0b) sh.t_w0b[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = f2bf(tn);
-                    if (sh.t_w0l) sh.t_w0l[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = f2bf_lo(tn);
+                    if (sh.t_w0b) sh.t_w0b[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = bf16_bits(tn);
+                    if (sh.t_w0l) sh.t_w0l[(int64_t)net * H * Kp + (int64_t)cc * Kp + k] = bf16_lo_bits(tn);
                 }
             }
         }
@@ -1505,7 +1498,12 @@ int finalize_adam(const FinalizeArgs& f, const FusedAdamArgs& a, const ShadowSpe
     const int nb_fin = cdiv(total, 256);
     int nb_w1 = cdiv((int64_t)a.n_heads * H * H / 8, 256);
     if (nb_w1 > 2048) nb_w1 = 2048;
-    hipLaunchKernelGGL(finalize_adam_kernel, dim3(nb_fin + nb_w1), dim3(256), 0, s, f, a, sh, nb_fin);
+    FlatShadows flat{};
+    flat.n_trunks = sh.n_trunks; flat.n_heads = sh.n_heads; flat.in_dim = sh.in_dim; flat.H = sh.H;
+    for (int i = 0; i < 2; ++i) { flat.w0_off[i] = sh.w0_off[i]; flat.w1_off[i] = sh.w1_off[i]; }
+    flat.w0t = sh.own.w0t;      flat.w1b = sh.own.w1.hi;      flat.w1l = sh.own.w1.lo;      flat.w0b = sh.own.w0.hi;      flat.w0l = sh.own.w0.lo;
+    flat.t_w0t = sh.target.w0t; flat.t_w1b = sh.target.w1.hi; flat.t_w1l = sh.target.w1.lo; flat.t_w0b = sh.target.w0.hi; flat.t_w0l = sh.target.w0.lo;
+    hipLaunchKernelGGL(finalize_adam_kernel, dim3(nb_fin + nb_w1), dim3(256), 0, s, f, a, flat, nb_fin);
     EXORL_LAUNCH_CHECK();
     return 0;
 }

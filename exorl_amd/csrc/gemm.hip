@@ -107,18 +107,12 @@ struct GemmBatch {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TILE = 64;        // BM = BN
 constexpr int ROWB = 128;       // bytes per LDS tile row
 constexpr int TILEB = TILE * ROWB;
 
 __device__ __forceinline__ int lds_off(int row, int unit) { return row * ROWB + ((unit ^ ((row >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, v);
-}
 
 // L == 0: element (r,k) at ptr[r*ld + k]   (k contiguous)
 // L == 1: element (r,k) at ptr[k*ld + r]   (r contiguous)
@@ -161,9 +155,6 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ ptr, int64_t
         }
     }
 }
-
-// x = hi + lo with hi = bf16(x), lo = bf16(x - hi): 16 significand bits in two bf16 MFMA operands
-__device__ __forceinline__ float bf16_residual(float x) { return x - (float)(__bf16)x; }
 
 template <int L, int PREC, int KU>
 __device__ __forceinline__ void store_tile(unsigned char* lds, int tid, const float (&reg)[2][KU]) {

@@ -619,7 +619,7 @@ __global__ __launch_bounds__(256) void proto_candidates_kernel(const float* __re
         for (int i = 0; i < NBL; ++i) acc += csum[i][pl];
         float u;
         if (u_in) u = u_in[p];
-        else { uint32_t c[4] = {(uint32_t)p, 7u, (uint32_t)counter, (uint32_t)(counter >> 32)}; Philox::gen(c, seed); u = (float)c[0] * 2.3283064365386963e-10f; }
+        else u = philox_uniform(seed, counter, (uint32_t)p, PHILOX_PROTO_CATEGORICAL);
         const double thr = (double)u * acc;
         double run = 0.0;
         int j = 0;
@@ -706,7 +706,7 @@ __global__ __launch_bounds__(256) void proto_cand_pick_kernel(const float* __res
         for (int c = 0; c < nch; ++c) total += csum[(int64_t)c * P + p];
         float u;
         if (u_in) u = u_in[p];
-        else { uint32_t c4[4] = {(uint32_t)p, 7u, (uint32_t)counter, (uint32_t)(counter >> 32)}; Philox::gen(c4, seed); u = (float)c4[0] * 2.3283064365386963e-10f; }
+        else u = philox_uniform(seed, counter, (uint32_t)p, PHILOX_PROTO_CATEGORICAL);
         const double thr = (double)u * total;
         double run = 0.0;
         int j = 0;
@@ -786,12 +786,6 @@ __global__ __launch_bounds__(1024) void aps_sf_reward_kernel(const float* __rest
 
 // ---- SMM (smm.py) -----------------------------------------------------------------------------------
 constexpr int SMM_VAE_HIDDEN = 150, SMM_CODE_DIM = 128;      // smm.py:38-45,98-101: fixed by the reference
-__device__ __forceinline__ float philox_normal_i(uint64_t seed, uint64_t counter, uint32_t elem) {
-    uint32_t c[4] = {elem, 11u, (uint32_t)counter, (uint32_t)(counter >> 32)};
-    Philox::gen(c, seed);
-    const float u1 = ((float)c[0] + 1.0f) * 2.3283064365386963e-10f, u2 = (float)c[1] * 2.3283064365386963e-10f;
-    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-}
 // code = eps * exp(0.5 logvar) + mu (smm.py:54-58); eps kept for the backward pass. elem0: element index of this rank's first row in the
 // global batch, so that each rank draws the single-process epsilon of its rows
 __global__ __launch_bounds__(256) void vae_code_kernel(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ eps_in,
@@ -799,7 +793,7 @@ __global__ __launch_bounds__(256) void vae_code_kernel(const float* __restrict__
                                                        int64_t elem0, const IntrStepState* __restrict__ st) {
     if (st) counter = st->draw_counter;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float e = eps_in ? eps_in[i] : philox_normal_i(seed, counter, (uint32_t)(elem0 + i));
+        const float e = eps_in ? eps_in[i] : philox_normal(seed, counter, (uint32_t)(elem0 + i), PHILOX_SMM_EPSILON);
         eps[i] = e;
         code[i] = e * expf(0.5f * lv[i]) + mu[i];
     }

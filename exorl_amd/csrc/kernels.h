@@ -2,7 +2,7 @@
 #pragma once
 #include <vector>
 
-#include "common.h"
+#include "numerics.h"
 
 namespace exorl {
 
@@ -19,8 +19,8 @@ struct SimpleCarver {
 // plane pipeline), or hi + mid + lo = the 24 significand bits of x (bf16x6 on the plane route). A plane the precision does not use is null.
 struct Planes {
     unsigned short *hi = nullptr, *mid = nullptr, *lo = nullptr;
-    Planes at(int64_t off) const { return Planes{hi ? hi + off : nullptr, mid ? mid + off : nullptr, lo ? lo + off : nullptr}; }
-    explicit operator bool() const { return hi != nullptr; }
+    __host__ __device__ Planes at(int64_t off) const { return Planes{hi ? hi + off : nullptr, mid ? mid + off : nullptr, lo ? lo + off : nullptr}; }
+    __host__ __device__ explicit operator bool() const { return hi != nullptr; }
 };
 
 struct GemmProblem {
@@ -273,18 +273,25 @@ struct FusedAdamArgs {
 struct ShadowSpec;
 int finalize_adam(const FinalizeArgs& f, const FusedAdamArgs& a, const ShadowSpec& sh, hipStream_t s);
 
-// Derived copies of a net's weights that the kernels read: W0T[in][H] per trunk (coalesced first-layer reads)
-// and, in bf16 mode, W1 as bf16 per head (MFMA operand). Kept current by the Adam kernel itself.
+// The derived images of one net's weights, which the kernels read in place of the fp32 parameters (exorl_hip.h, exorl_weight_images, defines
+// them): W0 transposed, fp32, per trunk (coalesced first-layer reads); W1 per head and W0 per trunk, K-padded with zeros, as bf16 planes
+// (MFMA operands; W0 has hi and lo at most). The functions below are the one statement of where an element sits and how large an image is.
+struct WeightImages { float* w0t = nullptr; Planes w1, w0; };
+__host__ __device__ inline int64_t w0_kp(int64_t in_dim) { return (in_dim + 31) / 32 * 32; }      // row pitch of a W0 plane
+// sizes per trunk / per head, in elements
+__host__ __device__ inline int64_t w0t_size(int64_t in_dim, int64_t H) { return in_dim * H; }
+__host__ __device__ inline int64_t w0_plane_size(int64_t in_dim, int64_t H) { return H * w0_kp(in_dim); }
+__host__ __device__ inline int64_t w1_plane_size(int64_t H) { return H * H; }
+// W0[c][k] of a trunk: in W0T [trunk][k][c], in a W0 plane [trunk][c][Kp]. (W1[r][c] of a head sits at head * w1_plane_size(H) + r * H + c.)
+__host__ __device__ inline int64_t w0t_index(int64_t trunk, int64_t k, int64_t c, int64_t in_dim, int64_t H) { return trunk * w0t_size(in_dim, H) + k * H + c; }
+__host__ __device__ inline int64_t w0_plane_index(int64_t trunk, int64_t c, int64_t k, int64_t in_dim, int64_t H) {
+    return trunk * w0_plane_size(in_dim, H) + c * w0_kp(in_dim) + k;
+}
+// What the optimiser kernels need to keep the images of a net (and of its Polyak target, if any: empty otherwise) current.
 struct ShadowSpec {
     int n_trunks, n_heads, in_dim, H;
     int64_t w0_off[2], w1_off[2];      // flat offsets of W0 (per trunk) and W1 (per head)
-    float* w0t;                        // [n_trunks][in][H]
-    unsigned short* w1b;               // [n_heads][H][H] bf16, or nullptr
-    unsigned short* w0b;               // [n_trunks][H][round_up(in, 32)] bf16 (zero padded), or nullptr
-    float* t_w0t;                      // same for the Polyak target (nullptr if none)
-    unsigned short* t_w1b;
-    unsigned short* t_w0b;
-    unsigned short *w1l, *w0l, *t_w1l, *t_w0l;     // lo planes of the bf16 copies (split-bf16 mode), same shapes; or nullptr
+    WeightImages own, target;
 };
 int refresh_shadows(const float* p, int64_t n, const ShadowSpec& sh, bool target, hipStream_t s);
 

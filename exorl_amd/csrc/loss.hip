@@ -11,25 +11,6 @@
 
 namespace exorl {
 
-template <int NV>
-__device__ __forceinline__ void block_sum(float (&v)[NV], float (*sm)[16]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float s = wave_sum(v[i]);
-        if (lane == 0) sm[i][wave] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        float t = 0.f;
-        for (int w = 0; w < nw; ++w) t += sm[i][w];
-        v[i] = t;
-    }
-    __syncthreads();
-}
-
 // xa = [next_obs ; obs] (2B x O); xc_cur = [obs | action]; xc_next[:, :O] = next_obs; xc_pi[:, :O] = obs
 __global__ void prepare_inputs_kernel(const float* __restrict__ obs, const float* __restrict__ action,
                                       const float* __restrict__ next_obs, float* __restrict__ xa,
@@ -63,14 +44,6 @@ int prepare_inputs(const float* obs, const float* action, const float* next_obs,
                        xc_next, xc_pi, B, O, A, has_critic, st, advance_replay);
     EXORL_LAUNCH_CHECK();
     return 0;
-}
-
-__device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t counter, uint32_t elem) {
-    uint32_t c[4] = {elem, 0u, (uint32_t)counter, (uint32_t)(counter >> 32)};
-    Philox::gen(c, seed);
-    const float u1 = ((float)c[0] + 1.0f) * 2.3283064365386963e-10f;     // (0, 1]
-    const float u2 = (float)c[1] * 2.3283064365386963e-10f;
-    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
 }
 
 __global__ __launch_bounds__(256) void reduce_pairs_kernel(const float* __restrict__ parts, int chunks, float* __restrict__ out) {

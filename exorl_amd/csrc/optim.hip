@@ -7,28 +7,27 @@
 
 namespace exorl {
 
-typedef __bf16 bf16s_t;
-__device__ __forceinline__ unsigned short to_bf16(float x) {
-    bf16s_t b = (bf16s_t)x;
-    return __builtin_bit_cast(unsigned short, b);
+// W0[c][k] = v into every W0 image `im` has
+__device__ __forceinline__ void write_w0_images(const WeightImages& im, int64_t trunk, int64_t c, int64_t k, int64_t in_dim, int64_t H, float v) {
+    im.w0t[w0t_index(trunk, k, c, in_dim, H)] = v;
+    if (im.w0) {
+        const int64_t j = w0_plane_index(trunk, c, k, in_dim, H);
+        im.w0.hi[j] = bf16_bits(v);
+        if (im.w0.lo) im.w0.lo[j] = bf16_lo_bits(v);
+    }
 }
-
-// Writes the derived copies (ShadowSpec) of the 4 parameters at flat index 4*i4.
-__device__ __forceinline__ unsigned short to_bf16_lo(float x) { return to_bf16(x - __uint_as_float((unsigned)to_bf16(x) << 16)); }
-
-// w1l / w0l: lo planes (split-bf16 mode) or null
-__device__ __forceinline__ void write_shadows(int64_t i4, const float4& pv, const ShadowSpec& sh, float* w0t,
-                                              unsigned short* w1b, unsigned short* w0b, unsigned short* w1l, unsigned short* w0l) {
+// Writes the 4 parameters at flat index 4*i4 into the derived images `im` (sh.own or sh.target) that hold them.
+__device__ __forceinline__ void write_shadows(int64_t i4, const float4& pv, const ShadowSpec& sh, const WeightImages& im) {
     const int64_t idx = 4 * i4;
-    const int64_t hh = (int64_t)sh.H * sh.H, w0n = (int64_t)sh.H * sh.in_dim;
+    const int64_t hh = w1_plane_size(sh.H), w0n = (int64_t)sh.H * sh.in_dim;
     for (int t = 0; t < sh.n_heads; ++t) {
-        if (w1b && idx >= sh.w1_off[t] && idx < sh.w1_off[t] + hh) {          // W1 is 4-aligned, hh % 4 == 0 for H % 2 == 0
-            unsigned short* d = w1b + t * hh + (idx - sh.w1_off[t]);
+        if (im.w1 && idx >= sh.w1_off[t] && idx < sh.w1_off[t] + hh) {          // W1 is 4-aligned, hh % 4 == 0 for H % 2 == 0
+            const Planes d = im.w1.at(t * hh + (idx - sh.w1_off[t]));
             const float e[4] = {pv.x, pv.y, pv.z, pv.w};
             for (int q = 0; q < 4; ++q)
                 if (idx + q < sh.w1_off[t] + hh) {
-                    d[q] = to_bf16(e[q]);
-                    if (w1l) w1l[t * hh + (idx - sh.w1_off[t]) + q] = to_bf16_lo(e[q]);
+                    d.hi[q] = bf16_bits(e[q]);
+                    if (d.lo) d.lo[q] = bf16_lo_bits(e[q]);
                 }
             return;
         }
@@ -38,14 +37,7 @@ __device__ __forceinline__ void write_shadows(int64_t i4, const float4& pv, cons
             const float e[4] = {pv.x, pv.y, pv.z, pv.w};
             for (int q = 0; q < 4; ++q) {
                 const int64_t l = idx + q - sh.w0_off[t];
-                if (l >= 0 && l < w0n) {
-                    w0t[t * w0n + (l % sh.in_dim) * sh.H + l / sh.in_dim] = e[q];
-                    if (w0b) {
-                        const int64_t Kp = (sh.in_dim + 31) / 32 * 32;
-                        w0b[t * (int64_t)sh.H * Kp + (l / sh.in_dim) * Kp + l % sh.in_dim] = to_bf16(e[q]);
-                        if (w0l) w0l[t * (int64_t)sh.H * Kp + (l / sh.in_dim) * Kp + l % sh.in_dim] = to_bf16_lo(e[q]);
-                    }
-                }
+                if (l >= 0 && l < w0n) write_w0_images(im, t, l / sh.in_dim, l % sh.in_dim, sh.in_dim, sh.H, e[q]);
             }
             return;
         }
@@ -55,8 +47,7 @@ __device__ __forceinline__ void write_shadows(int64_t i4, const float4& pv, cons
 __global__ __launch_bounds__(256) void refresh_shadows_kernel(const float* __restrict__ p, int64_t n4, ShadowSpec sh,
                                                               int target) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
-        write_shadows(i, reinterpret_cast<const float4*>(p)[i], sh, target ? sh.t_w0t : sh.w0t, target ? sh.t_w1b : sh.w1b,
-                      target ? sh.t_w0b : sh.w0b, target ? sh.t_w1l : sh.w1l, target ? sh.t_w0l : sh.w0l);
+        write_shadows(i, reinterpret_cast<const float4*>(p)[i], sh, target ? sh.target : sh.own);
 }
 
 int refresh_shadows(const float* p, int64_t n, const ShadowSpec& sh, bool target, hipStream_t s) {
@@ -95,9 +86,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
             tv.z = polyak(pv.z, tv.z, c.tau, c.one_minus_tau);
             tv.w = polyak(pv.w, tv.w, c.tau, c.one_minus_tau);
             reinterpret_cast<float4*>(target)[i] = tv;
-            if (has_shadows) write_shadows(i, tv, sh, sh.t_w0t, sh.t_w1b, sh.t_w0b, sh.t_w1l, sh.t_w0l);
+            if (has_shadows) write_shadows(i, tv, sh, sh.target);
         }
-        if (has_shadows) write_shadows(i, pv, sh, sh.w0t, sh.w1b, sh.w0b, sh.w1l, sh.w0l);
+        if (has_shadows) write_shadows(i, pv, sh, sh.own);
     }
 }
 

@@ -38,10 +38,10 @@ __global__ __launch_bounds__(256) void aug_shift_kernel(const unsigned char* __r
         int sx, sy;
         if (shifts) { sx = shifts[2 * b]; sy = shifts[2 * b + 1]; }
         else {      // torch.randint(0, 2 pad + 1, (n,1,1,2)): one Philox draw per image
-            uint32_t r[4] = {(uint32_t)b, 13u, (uint32_t)counter, (uint32_t)(counter >> 32)};
-            Philox::gen(r, seed);
-            sx = (int)(((uint64_t)r[0] * (uint64_t)(2 * pad + 1)) >> 32);
-            sy = (int)(((uint64_t)r[1] * (uint64_t)(2 * pad + 1)) >> 32);
+            uint32_t r[4];
+            philox_block(r, seed, counter, (uint32_t)b, PHILOX_AUG_SHIFT);
+            sx = philox_below(r[0], 2 * pad + 1);
+            sy = philox_below(r[1], 2 * pad + 1);
         }
         const float gx = lin_f32(start, end, step, j, P) + (float)sx * unit;
         const float gy = lin_f32(start, end, step, i, P) + (float)sy * unit;
@@ -74,8 +74,8 @@ __global__ __launch_bounds__(256) void aug_shift_rows_kernel(const unsigned char
     const float unit = (float)(2.0 / P);
     int sxy[2];
     if (shifts) { sxy[0] = shifts[2 * b]; sxy[1] = shifts[2 * b + 1]; }
-    else {      // torch.randint(0, 2 pad + 1, (n,1,1,2)): one Philox draw per image
-        uint32_t r[4] = {(uint32_t)b, 13u, (uint32_t)counter, (uint32_t)(counter >> 32)};
+    else {      // aug_shift_kernel's draw (philox_block, then philox_below on words 0 and 1), written out: the helpers compile to other scalar code here
+        uint32_t r[4] = {(uint32_t)b, PHILOX_AUG_SHIFT, (uint32_t)counter, (uint32_t)(counter >> 32)};
         Philox::gen(r, seed);
         sxy[0] = (int)(((uint64_t)r[0] * (uint64_t)(2 * pad + 1)) >> 32);
         sxy[1] = (int)(((uint64_t)r[1] * (uint64_t)(2 * pad + 1)) >> 32);
@@ -130,11 +130,9 @@ __global__ void conv_weight_shadow_kernel(const float* __restrict__ W, float* __
             const int cin = (st & 1) * 16 + 8 * kg + j;
             // forward: Wt[ci][tap][co] = W[co][ci][tap]; dgrad: the flipped shadow read with the roles of ci and co exchanged
             const float w = dir == 0 ? W[(col * CONV_CO + cin) * 9 + tap] : W[(cin * CONV_CO + col) * 9 + (8 - tap)];
-            const __bf16 h = (__bf16)w;
-            const float r1 = w - (float)h;
-            const __bf16 l = (__bf16)r1;                         // second plane: the lo plane of the two-plane mode = the mid plane of the three-plane mode
-            const __bf16 t = (__bf16)(r1 - (float)l);            // third plane (EXORL_PREC_BF16X6)
-            const unsigned hb = __builtin_bit_cast(unsigned short, h), lb = __builtin_bit_cast(unsigned short, l), tb = __builtin_bit_cast(unsigned short, t);
+            const float r1 = bf16_residual(w);
+            // second plane: the lo plane of the two-plane mode = the mid plane of the three-plane mode; third plane: EXORL_PREC_BF16X6
+            const unsigned hb = bf16_bits(w), lb = bf16_bits(r1), tb = bf16_bits(bf16_residual(r1));
             if (j & 1) { hi[j >> 1] |= hb << 16; lo[j >> 1] |= lb << 16; l3[j >> 1] |= tb << 16; } else { hi[j >> 1] = hb; lo[j >> 1] = lb; l3[j >> 1] = tb; }
         }
         uint4* dst = dir == 0 ? ff : fb;
@@ -1031,9 +1029,8 @@ __global__ __launch_bounds__(WM_THREADS) void conv_wgrad_mfma_kernel(const float
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
     auto pack = [](float a, float b, int plane) -> unsigned {     // plane 0: bf16(x); 1: bf16(x - p0); 2: bf16(x - p0 - p1)
-        for (int q = 0; q < plane; ++q) { a -= (float)(__bf16)a; b -= (float)(__bf16)b; }
-        const __bf16 h0 = (__bf16)a, h1 = (__bf16)b;
-        return (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+        for (int q = 0; q < plane; ++q) { a = bf16_residual(a); b = bf16_residual(b); }
+        return (unsigned)bf16_bits(a) | ((unsigned)bf16_bits(b) << 16);
     };
     const int tiles_x = (ow + TW - 1) / TW, tiles_y = (oh + TH - 1) / TH;
     for (int tile = 0; tile < tiles_x * tiles_y; ++tile) {
@@ -1530,7 +1527,7 @@ __global__ __launch_bounds__(W1_THREADS) void conv1_wgrad_mfma_kernel(const floa
 #pragma unroll
         for (int c = 0; c < NPL; ++c)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const __bf16 h = (__bf16)r[j]; out[c][j] = h; r[j] -= (float)h; }
+            for (int j = 0; j < 8; ++j) { out[c][j] = (__bf16)r[j]; r[j] = bf16_residual(r[j]); }
     };
     for (int r0 = 0; r0 < oh; r0 += W1_RC) {
         const int nr = oh - r0 < W1_RC ? oh - r0 : W1_RC, npx = nr * ow, nsteps = (npx + 15) / 16;

@@ -319,7 +319,8 @@ int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream);
  *   EXORL_PREC_BF16X6, hidden_dim % 128 == 0 and batch % 128 == 0 (the plane route)    w1_hi, w1_mid, w1_lo; none of W0
  *   everything else (fp32; bf16x3 / bf16x6 at other shapes: the GEMM splits fp32)     none
  * Written by exorl_agent_params_changed, by the optimiser launch of every step route (for the critic also the Polyak target's) and, three
- * planes, by a conversion pass behind it. */
+ * planes, by a conversion pass behind it. Inside the library this layout is stated once, by the index and size functions next to
+ * WeightImages in exorl_amd/csrc/kernels.h, and the planes' values by bf16_bits / bf16_lo_bits / bf16_residual in csrc/numerics.h. */
 typedef struct {
     int32_t n_trunks, n_heads, in_dim, hidden_dim;
     float* w0t;
