@@ -1204,6 +1204,8 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     EXORL_REQUIRE(a->cfg.world_size == 1 || a->comm, "agent_enable_graph: a data-parallel step needs the library's communicator (exorl_agent_set_comm) to be captured; "
                   "steps whose collectives run in the caller's code are enqueued eagerly");
     EXORL_REQUIRE(stddev > 0.f && nstep >= 1, "agent_enable_graph: bad stddev/nstep");
+    EXORL_REQUIRE(replay_frame_stack(r) == 1, "agent_enable_graph: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): the "
+                  "captured step stages its inputs from whole arena rows; sample a frame-stacked arena eagerly", replay_frame_stack(r));
     EXORL_TRY(release_graph(a));
     if (!a->capture_stream) EXORL_CHECK_HIP(hipStreamCreateWithFlags(&a->capture_stream, hipStreamNonBlocking));
     exorl_batch_out slots;

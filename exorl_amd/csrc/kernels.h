@@ -535,7 +535,8 @@ struct StageOut {
 int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
                        const uint64_t* dev_counter, const StageOut* stage = nullptr);
-int replay_obs_bytes(exorl_replay* r);
+int replay_obs_bytes(exorl_replay* r);        // bytes of one SAMPLED observation (frames x the arena's row on a frame-stacked arena)
+int replay_frame_stack(exorl_replay* r);      // frames per sampled observation (exorl_replay_set_frame_stack; 1: none)
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim);
 // comm.cpp (exorl_comm is the C ABI's opaque struct, declared at global scope in exorl_hip.h)
 int comm_allreduce_sum(exorl_comm* c, float* buf, int64_t n, hipStream_t s);

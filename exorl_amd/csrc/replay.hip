@@ -17,6 +17,11 @@
 // prefix sum `cum` of the episode masses (TRANSITIONS: q_e * span_e, EPISODES: q_e where span_e > 0; span_e = len_e - nstep + 1
 // clamped at 0). The kernel scales 64 Philox bits onto [0, cum[n]) and binary-searches the episode; zero-mass episodes own an empty
 // interval and are never drawn. With unit weights TRANSITIONS mode is uniform over transitions.
+//
+// Frame stacking (exorl_replay_set_frame_stack(k), k > 1): an obs row holds the ONE frame the env produced at that step (obs_bytes = one
+// frame) and a sampled observation is k of them, oldest first: the stack at step t is rows max(t - k + 1, 0) .. t of the episode, what the
+// wrapper's deque(maxlen=k), filled with the reset frame, held (utils/env_constructor.py:144-188). gather_frames_kernel gives one wave to
+// each of the 2 k frames of a sample; gather_nstep_kernel, its arguments and its launch are those of an arena without stacking.
 #include <algorithm>
 #include <vector>
 
@@ -129,6 +134,7 @@ struct exorl_replay {
     std::vector<int32_t> h_guide;
     int32_t guide_cap = 0, guide_bits = 0;
     uint64_t weights_epoch = 0;       // counts exorl_replay_set_weights calls (a captured step graph refuses to replay across one)
+    int32_t frames = 1;               // frames per sampled observation (exorl_replay_set_frame_stack); 1: a row is the whole observation
 };
 
 namespace exorl {
@@ -157,18 +163,10 @@ __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ src, 
     }
 }
 
-__global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const int32_t* pairs_in,
-                                                           int32_t* pairs_out, exorl_batch_out out,
-                                                           int batch, int nstep, float gamma, int sampler,
-                                                           uint64_t seed, uint64_t counter_val,
-                                                           const uint64_t* counter_ptr, int vec16, StageOut stage) {
-#pragma clang fp contract(off)
-    if (stage.st && blockIdx.x == 0 && threadIdx.x == 0) step_begin_device(stage.st, 0);   // noise counter, Adam scalars of this step
-    const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (b >= batch) return;
-    int pos, idx;
+// The (episode position, start idx) pair of sample b, the same in every wave that asks for it: a Philox counter block (the cum / guide
+// search on a weighted arena), or the pair the host sampler shipped. Lane 0 of a `writer` wave records a drawn pair in pairs_out.
+__device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pairs_in, int32_t* pairs_out, int b, int nstep, int sampler,
+                                          uint64_t seed, uint64_t counter, int lane, bool writer, int& pos, int& idx) {
     if (sampler == EXORL_SAMPLER_PHILOX) {
         uint32_t c[4] = {(uint32_t)b, (uint32_t)counter, (uint32_t)(counter >> 32), 0u};
         Philox::gen(c, seed);
@@ -187,11 +185,26 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         }
         const int span = v.len[pos] - nstep + 1;
         idx = (int)(((uint64_t)c[1] * (uint64_t)span) >> 32) + 1;
-        if (lane == 0) { pairs_out[2 * b] = pos; pairs_out[2 * b + 1] = idx; }
+        if (writer && lane == 0) { pairs_out[2 * b] = pos; pairs_out[2 * b + 1] = idx; }
     } else {
         pos = pairs_in[2 * b];
         idx = pairs_in[2 * b + 1];
     }
+}
+
+__global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const int32_t* pairs_in,
+                                                           int32_t* pairs_out, exorl_batch_out out,
+                                                           int batch, int nstep, float gamma, int sampler,
+                                                           uint64_t seed, uint64_t counter_val,
+                                                           const uint64_t* counter_ptr, int vec16, StageOut stage) {
+#pragma clang fp contract(off)
+    if (stage.st && blockIdx.x == 0 && threadIdx.x == 0) step_begin_device(stage.st, 0);   // noise counter, Adam scalars of this step
+    const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= batch) return;
+    int pos, idx;
+    draw_pair(v, pairs_in, pairs_out, b, nstep, sampler, seed, counter, lane, true, pos, idx);
     const int64_t row = v.row0[pos] + idx;
     copy_row(v.obs + (row - 1) * v.obs_bytes, static_cast<unsigned char*>(out.obs) + (int64_t)b * out.obs_stride,
              v.obs_bytes, lane, vec16);
@@ -223,6 +236,63 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         for (int i = 0; i < nstep; ++i) {
             const float t = D * v.rew[row + i];        // replay_buffer.py:233  reward += discount * step_reward
             R = R + t;
+            const float u = v.disc[row + i] * gamma;   // replay_buffer.py:234  discount *= ep_discount * gamma
+            D = D * u;
+        }
+        out.reward[b] = R;
+        out.discount[b] = D;
+    }
+}
+
+// copy_row with four loads of a lane in flight before the first store (the compiler keeps copy_row's loop at one load, one wait, one store):
+// a frame is 21 KB at (3, 84, 84), 21 wave-wide 16-byte passes, and a wave that waits out every miss by itself leaves HBM idle.
+template <typename W>
+__device__ __forceinline__ void stream_words(const W* __restrict__ s, W* __restrict__ d, int n, int lane) {
+    int i = lane;
+    for (; i + 192 < n; i += 256) {
+        const W a = s[i], b = s[i + 64], c = s[i + 128], e = s[i + 192];
+        d[i] = a; d[i + 64] = b; d[i + 128] = c; d[i + 192] = e;
+    }
+    for (; i < n; i += 64) d[i] = s[i];
+}
+
+// Frame-stacked arenas: one wave per output frame, 2 * frames * batch of them. Wave (b, which, j) streams frame j (0 = oldest) of sample b's
+// obs (which = 0, the stack at t = idx - 1) or next_obs (which = 1, t = idx + nstep - 1) from episode row max(t - (frames - 1 - j), 0): steps
+// before the reset repeat the reset frame. The first wave of a sample also writes what is per sample: action, meta, the n-step return
+// (same operation order as gather_nstep_kernel) and the drawn pair.
+__global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const int32_t* pairs_in, int32_t* pairs_out, exorl_batch_out out,
+                                                            int batch, int nstep, float gamma, int sampler, uint64_t seed,
+                                                            uint64_t counter_val, const uint64_t* counter_ptr, int frames) {
+#pragma clang fp contract(off)
+    const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int b = w / (2 * frames), part = w % (2 * frames);
+    if (b >= batch) return;
+    const int which = part / frames, j = part % frames;
+    const bool first = part == 0;
+    int pos, idx;
+    draw_pair(v, pairs_in, pairs_out, b, nstep, sampler, seed, counter, lane, first, pos, idx);
+    const int64_t row0 = v.row0[pos];
+    const int t = idx - 1 + (which ? nstep : 0);
+    const int f = t - (frames - 1 - j);
+    const unsigned char* src = v.obs + (row0 + (f > 0 ? f : 0)) * v.obs_bytes;
+    unsigned char* dst = static_cast<unsigned char*>(which ? out.next_obs : out.obs) +
+                         (int64_t)b * (which ? out.next_obs_stride : out.obs_stride) + (int64_t)j * v.obs_bytes;
+    // wave-uniform; the arena rows are 16-byte aligned whenever a frame is a multiple of 16 bytes, the destination need not be
+    const bool vec16 = v.obs_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0;
+    if (vec16) stream_words(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), v.obs_bytes / 16, lane);
+    else stream_words(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(dst), v.obs_bytes / 4, lane);
+    if (!first) return;
+    const int64_t row = row0 + idx;
+    for (int i = lane; i < v.act_dim; i += 64) out.action[(int64_t)b * out.action_stride + i] = v.act[row * v.act_dim + i];
+    if (out.meta)
+        for (int i = lane; i < v.meta_dim; i += 64) out.meta[(int64_t)b * out.meta_stride + i] = v.meta[(row - 1) * v.meta_dim + i];
+    if (lane == 0) {
+        float R = 0.0f, D = 1.0f;
+        for (int i = 0; i < nstep; ++i) {
+            const float x = D * v.rew[row + i];        // replay_buffer.py:233  reward += discount * step_reward
+            R = R + x;
             const float u = v.disc[row + i] * gamma;   // replay_buffer.py:234  discount *= ep_discount * gamma
             D = D * u;
         }
@@ -437,6 +507,17 @@ int exorl_replay_set_weights(exorl_replay_t* r, int32_t mode, const uint32_t* q_
     return 0;
 }
 
+int exorl_replay_set_frame_stack(exorl_replay_t* r, int32_t frames) {
+    EXORL_REQUIRE(r, "replay_set_frame_stack: null handle");
+    EXORL_REQUIRE(frames >= 1 && frames <= 16, "replay_set_frame_stack: frames=%d outside [1, 16]", frames);
+    EXORL_REQUIRE(r->slots.empty(), "replay_set_frame_stack: the arena has handed out %d slots already: rows stored as whole observations "
+                  "cannot be re-read as single frames", (int)r->slots.size());
+    EXORL_REQUIRE((int64_t)frames * r->cfg.obs_bytes <= INT32_MAX, "replay_set_frame_stack: %d frames of %d bytes overflow an observation's "
+                  "32-bit size", frames, r->cfg.obs_bytes);
+    r->frames = frames;
+    return 0;
+}
+
 int exorl_replay_num_rows(exorl_replay_t* r, int64_t* live_rows, int64_t* used_rows) {
     EXORL_REQUIRE(r, "replay_num_rows: null handle");
     if (live_rows) *live_rows = r->live_rows;
@@ -499,11 +580,18 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
                        const uint64_t* dev_counter, const StageOut* stage) {
     EXORL_REQUIRE(r && out, "replay_sample: null argument");
-    EXORL_REQUIRE(!stage || (r->cfg.obs_bytes == stage->O * 4 && r->cfg.act_dim == stage->A && stage->B == batch),
+    EXORL_REQUIRE(!stage || (r->frames == 1 && r->cfg.obs_bytes == stage->O * 4 && r->cfg.act_dim == stage->A && stage->B == batch),
                   "replay_sample: staged outputs need fp32 state observations of the agent's dimensions");
     EXORL_REQUIRE(batch > 0 && nstep >= 1, "replay_sample: batch=%d nstep=%d", batch, nstep);
     EXORL_REQUIRE(out->obs && out->action && out->reward && out->discount && out->next_obs, "replay_sample: null output");
     EXORL_REQUIRE((r->cfg.meta_dim > 0) || out->meta == nullptr, "replay_sample: meta output without meta columns");
+    if (r->frames > 1) {
+        const int64_t need = (int64_t)r->frames * r->cfg.obs_bytes;
+        EXORL_REQUIRE(out->obs_stride >= need && out->next_obs_stride >= need, "replay_sample: obs_stride=%lld / next_obs_stride=%lld cannot "
+                      "hold an observation of %d frames x %d bytes", (long long)out->obs_stride, (long long)out->next_obs_stride, r->frames,
+                      r->cfg.obs_bytes);
+        EXORL_REQUIRE(2ll * r->frames * batch <= INT32_MAX, "replay_sample: batch=%d x %d frames: too many output frames", batch, r->frames);
+    }
     const int n = (int)r->order.size();
     EXORL_REQUIRE(!(r->weighted && sampler == EXORL_SAMPLER_MT19937), "replay_sample: weighted sampling needs EXORL_SAMPLER_PHILOX: the MT19937 "
                   "sampler reproduces the reference's unweighted index stream (exorl_replay_set_weights(EPISODES, NULL) turns weighting off)");
@@ -540,10 +628,15 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
     }
     ReplayView v{r->obs, r->act, r->rew, r->disc, r->meta, r->d_row0, r->d_len, r->cfg.obs_bytes, r->cfg.act_dim, r->cfg.meta_dim, n,
                  r->weighted && sampler == EXORL_SAMPLER_PHILOX ? r->d_cum : nullptr, r->d_guide, r->guide_bits};
-    const int vec16 = (r->cfg.obs_bytes % 16 == 0) && (out->obs_stride % 16 == 0) && (out->next_obs_stride % 16 == 0) &&
-                      ((uintptr_t)out->obs % 16 == 0) && ((uintptr_t)out->next_obs % 16 == 0);
-    hipLaunchKernelGGL(gather_nstep_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch, nstep,
-                       gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16, stage ? *stage : StageOut{});
+    if (r->frames > 1) {
+        hipLaunchKernelGGL(gather_frames_kernel, dim3(cdiv(2 * r->frames * batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch,
+                           nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, r->frames);
+    } else {
+        const int vec16 = (r->cfg.obs_bytes % 16 == 0) && (out->obs_stride % 16 == 0) && (out->next_obs_stride % 16 == 0) &&
+                          ((uintptr_t)out->obs % 16 == 0) && ((uintptr_t)out->next_obs % 16 == 0);
+        hipLaunchKernelGGL(gather_nstep_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch, nstep,
+                           gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16, stage ? *stage : StageOut{});
+    }
     EXORL_LAUNCH_CHECK();
     if (sampler == EXORL_SAMPLER_PHILOX) r->philox_counter += 1;
     return 0;
@@ -551,7 +644,8 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
 
 uint64_t replay_philox_counter(exorl_replay* r) { return r->philox_counter; }
 uint64_t replay_weights_epoch(exorl_replay* r) { return r->weights_epoch; }
-int replay_obs_bytes(exorl_replay* r) { return r->cfg.obs_bytes; }
+int replay_obs_bytes(exorl_replay* r) { return r->frames * r->cfg.obs_bytes; }      // of one SAMPLED observation
+int replay_frame_stack(exorl_replay* r) { return r->frames; }
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }
 void replay_advance_philox(exorl_replay* r, uint64_t n) { r->philox_counter += n; }
 }  // namespace exorl

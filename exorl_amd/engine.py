@@ -714,31 +714,60 @@ def quantise_weights(w):
     return q.astype(np.uint32)
 
 
-class ReplayEngine:
-    """HBM-resident episodic arena (exorl_replay_t)."""
+def frame_shape(obs_shape, frame_stack):
+    """(c0, H, W) of one frame of a (k * c0, H, W) observation stacked along the channel axis; ValueError for what cannot be one."""
+    k, shape = int(frame_stack), tuple(int(d) for d in obs_shape)
+    if not 1 <= k <= 16:
+        raise ValueError(f'frame_stack={frame_stack}: expected 1 .. 16')
+    if k > 1 and len(shape) != 3:
+        raise ValueError(f'frame_stack={k} needs a (channels, H, W) observation, got shape {shape}')
+    if k > 1 and shape[0] % k:
+        raise ValueError(f'frame_stack={k} does not divide the {shape[0]} channels of an observation of shape {shape}')
+    return ((shape[0] // k,) + shape[1:]) if k > 1 else shape
 
-    def __init__(self, obs_shape, obs_dtype, act_dim, meta_dim, capacity_rows, max_episodes, device='cuda'):
-        self.lib = L.load()
-        self.device = _require_gpu(device)
+
+class ReplayEngine:
+    """HBM-resident episodic arena (exorl_replay_t).
+
+    frame_stack=k > 1: obs_shape is still the sampled (k * c0, H, W) observation, but an arena row holds one (c0, H, W) frame
+    (frame_bytes = obs_bytes / k) and the gather assembles every sampled observation from the k rows max(t - k + 1, 0) .. t of its
+    episode: byte for byte what an arena of the stacked episodes returns, at 1/k of its memory and upload."""
+
+    def __init__(self, obs_shape, obs_dtype, act_dim, meta_dim, capacity_rows, max_episodes, device='cuda', frame_stack=1):
         self.obs_shape = tuple(obs_shape)
         self.obs_dtype = np.dtype(obs_dtype)
+        self.frame_stack = int(frame_stack)
+        self.frame_shape = frame_shape(self.obs_shape, frame_stack)
+        self.lib = L.load()
+        self.device = _require_gpu(device)
         self.obs_bytes = int(np.prod(self.obs_shape)) * self.obs_dtype.itemsize
+        self.frame_bytes = self.obs_bytes // self.frame_stack
         self.act_dim, self.meta_dim = act_dim, meta_dim
-        cfg = L.ReplayCfg(self.obs_bytes, act_dim, meta_dim, max_episodes, capacity_rows)
+        cfg = L.ReplayCfg(self.frame_bytes, act_dim, meta_dim, max_episodes, capacity_rows)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(self.lib.exorl_replay_create(C.byref(cfg), C.byref(h)))
         self.h = h
+        if self.frame_stack > 1:
+            self.set_frame_stack(self.frame_stack)
 
     def __del__(self):
         h, self.h = getattr(self, 'h', None), None
         if h:
             self.lib.exorl_replay_destroy(h)
 
+    def set_frame_stack(self, frames):
+        """exorl_replay_set_frame_stack: refused once an episode has been appended. The constructor's frame_stack= is the way in; this is
+        the raw call, which leaves obs_shape / frame_bytes as they are."""
+        L.check(self.lib.exorl_replay_set_frame_stack(self.h, frames))
+
     def append_episode(self, ep, meta_keys=()):
         obs = np.ascontiguousarray(ep['observation'])
         rows = obs.shape[0]
-        assert obs.dtype == self.obs_dtype and obs.reshape(rows, -1).shape[1] * obs.itemsize == self.obs_bytes
+        if self.frame_stack > 1 and obs.shape[1:] == self.obs_shape:      # the stacked episode as the reference stores it: keep the newest frames
+            from .replay_buffer import unstack_frames
+            obs = np.ascontiguousarray(unstack_frames(obs, self.frame_stack))
+        assert obs.dtype == self.obs_dtype and obs.reshape(rows, -1).shape[1] * obs.itemsize == self.frame_bytes
         act = np.ascontiguousarray(ep['action'], np.float32).reshape(rows, -1)
         rew = np.ascontiguousarray(ep['reward'], np.float32).reshape(rows)
         disc = np.ascontiguousarray(ep['discount'], np.float32).reshape(rows)

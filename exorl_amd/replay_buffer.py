@@ -72,6 +72,35 @@ def _load_many(fns, threads):
             yield ep
 
 
+def stack_frames(frames, k):
+    """The frame-stack wrapper's deque(maxlen=k) (utils/env_constructor.py:144-188) over one episode: (rows, c0, ...) single frames ->
+    (rows, k * c0, ...) observations. Row t is frames max(t - k + 1, 0) .. t along the channel axis, oldest first: the deque is filled
+    with the reset frame k times, then takes one frame per step."""
+    frames = np.asarray(frames)
+    t = np.arange(len(frames))
+    return np.concatenate([frames[np.maximum(t - (k - 1 - j), 0)] for j in range(k)], axis=1)
+
+
+def unstack_frames(obs, k):
+    """Inverse of stack_frames: the newest frame obs[:, -c0:] of every row, after checking that `obs` IS a sliding window over one frame
+    sequence (row 0 is k copies of one frame; every later row is its predecessor shifted by one frame). Anything else (episodes cut or
+    spliced after collection, a wrapper that does not fill with the reset frame) cannot be stored one frame per row without changing
+    what is sampled: ValueError naming the first offending row."""
+    obs = np.asarray(obs)
+    if obs.ndim < 2 or obs.shape[1] % k:
+        raise ValueError(f'unstack_frames: {k} frames do not divide the channel axis of observations of shape {obs.shape[1:]}')
+    c0 = obs.shape[1] // k
+    if k == 1 or len(obs) == 0:
+        return obs
+    if not np.array_equal(obs[0, :-c0], obs[0, c0:]):
+        raise ValueError(f'unstack_frames: row 0 is not {k} copies of the reset frame: the episode is not a frame-stack window')
+    bad = np.flatnonzero((obs[1:, :-c0] != obs[:-1, c0:]).reshape(len(obs) - 1, -1).any(axis=1))
+    if len(bad):
+        raise ValueError(f'unstack_frames: row {int(bad[0]) + 1} does not continue row {int(bad[0])} (its {k - 1} older frames differ): the '
+                         'episode is not a frame-stack window')
+    return obs[:, -c0:]
+
+
 class ReplayBufferStorage:
     """Accumulates time-steps and writes finished episodes as episode_{idx}_{len}.npz."""
 
@@ -161,7 +190,7 @@ class _Shard:
         max_eps = ld.max_episodes or max(4096, ld.max_size // 64)
         cap = ld.capacity_rows or (ld.max_size + max_eps + obs.shape[0] + 1024)
         self.engine = ReplayEngine(obs.shape[1:], obs.dtype, int(np.prod(episode['action'].shape[1:])), meta_dim, cap,
-                                   max_eps, ld.device)
+                                   max_eps, ld.device, frame_stack=getattr(ld, 'frame_stack', None) or 1)
 
     def _store(self, fn, episode=None, reorder=True):
         ld = self.loader
@@ -341,11 +370,20 @@ class DeviceReplayLoader:
 
     weighting='episodes'|'transitions' and episode_weight (a callable: episode dict -> non-negative float, e.g.
     `lambda ep: 4.0 if ep['constraint'].any() else 1.0`) select ReplayEngine.set_weights' weighted sampling; they are re-applied
-    whenever episodes are stored, evicted or re-ordered, and need sampler='philox'. mix: see make_offline_replay_loader."""
+    whenever episodes are stored, evicted or re-ordered, and need sampler='philox'. mix: see make_offline_replay_loader.
+
+    frame_stack=k (the run's cfg.frame_stack; None or 1: rows are stored as they come): the episodes on disk and from the storage are
+    the frame-stack wrapper's (k * c0, H, W) observations; the arena keeps one (c0, H, W) frame per step, 1/k of the memory and of the
+    upload, and the gather rebuilds the stacks: the batches are byte-identical. An episode that is not such a window raises ValueError
+    at ingest (unstack_frames)."""
 
     def __init__(self, storage, max_size, batch_size, num_workers, save_snapshot, nstep, discount, fetch_every=1000,
                  device='cuda', sampler='mt19937', seed=None, worker_ids=None, max_episodes=None, capacity_rows=None, static=False,
-                 load_threads=None, offline=False, env=None, relabel=False, weighting=None, episode_weight=None, mix=None):
+                 load_threads=None, offline=False, env=None, relabel=False, weighting=None, episode_weight=None, mix=None,
+                 frame_stack=None):
+        if frame_stack is not None and not 1 <= int(frame_stack) <= 16:
+            raise ValueError(f'frame_stack={frame_stack}: expected 1 .. 16')
+        self.frame_stack = None if frame_stack is None else int(frame_stack)
         self.weighting, self.episode_weight, self.mix = _weighting_args(sampler, weighting, episode_weight, mix), episode_weight, mix
         self.storage = storage
         self.offline, self.env, self.relabel = offline, env, relabel      # OfflineReplayBuffer semantics (see _OfflineShard)

@@ -38,7 +38,8 @@ extern "C" {
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
-                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights) */
+                                        exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights,
+                                        exorl_replay_set_frame_stack) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -96,6 +97,14 @@ int exorl_replay_num_rows(exorl_replay_t* r, int64_t* live_rows, int64_t* used_r
 #define EXORL_WEIGHT_EPISODES    0
 #define EXORL_WEIGHT_TRANSITIONS 1
 int exorl_replay_set_weights(exorl_replay_t* r, int32_t mode, const uint32_t* q_per_slot_host, int32_t n_slots);
+/* Frame stacking, frames in [1, 16] (1, the default: none), allowed only before the first exorl_replay_append_episode. With frames = k > 1
+ * cfg.obs_bytes is ONE frame (c0*H*W of the k*c0 stacked channels) and row t of an episode holds the single frame the env produced at
+ * step t; a sampled observation is frames * obs_bytes bytes, the frames of steps max(t-k+1, 0) .. t oldest first (t = idx-1 for obs,
+ * idx+nstep-1 for next_obs): what a frame-stack wrapper's deque, filled with the reset frame, held at step t. Samples are byte-identical
+ * to those of an arena without stacking that was fed the stacked episodes, for every sampler, weighting, eviction and compaction, at
+ * 1/k of the arena's observation bytes. exorl_replay_sample fails, launching nothing, unless out->obs_stride and out->next_obs_stride
+ * are >= frames * obs_bytes. exorl_agent_enable_graph / _intr refuse such an arena (the captured step reads whole arena rows). */
+int exorl_replay_set_frame_stack(exorl_replay_t* r, int32_t frames);
 /* MT19937 states as exposed by random.getstate()[1] / np.random.get_state()[1:3]. */
 int exorl_replay_seed_mt(exorl_replay_t* r, const uint32_t* py_key624, int32_t py_pos,
                          const uint32_t* np_key624, int32_t np_pos);
