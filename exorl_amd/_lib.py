@@ -14,6 +14,7 @@ P = C.POINTER
 SAMPLER_MT19937, SAMPLER_PHILOX, SAMPLER_GIVEN = 0, 1, 2
 WEIGHT_EPISODES, WEIGHT_TRANSITIONS = 0, 1
 AGENT_TD3_BC, AGENT_TD3, AGENT_BC, AGENT_DDPG, AGENT_CRR, AGENT_CQL, AGENT_APS = 0, 1, 2, 3, 4, 5, 6
+AGENT_XCHG_CRITIC_GRAD, AGENT_XCHG_STATS, AGENT_XCHG_ACTOR_GRAD = 0, 1, 2
 M_CRITIC_CQL, M_CRITIC_CQL_LOGSUM, M_ACTOR_ALPHA, M_ACTOR_ALPHA_LOSS, M_ACTOR_ENT = 10, 11, 12, 13, 14
 CRR_WEIGHT = {'identity': 0, 'indicator': 1, 'exp': 2}
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2, 3
@@ -160,6 +161,7 @@ PROTOTYPES = {
     'exorl_agent_set_batch': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_update': (C.c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_update_phase': (C.c_int, [c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    'exorl_agent_update_plan': (C.c_int, [P(AgentCfg), P(c_int32), P(c_int32), c_int32, P(c_int32)]),
     'exorl_agent_stats_buffer': (C.c_int, [c_void_p, P(c_void_p), P(c_int64)]),
     'exorl_agent_cql_alpha': (C.c_int, [c_void_p, c_void_p, c_int32]),
     'exorl_agent_act': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),

@@ -70,10 +70,14 @@ static NetDesc make_net(int in_dim, int out_dim, int H, int n_trunks, int n_head
 // Second stream for independent branches of the step (target forward || critic forward, wgrad || dgrad chain).
 // Used while capturing: the hipGraph then has parallel branches, so kernels that fill only part of the 256 CUs
 // (64x64-tile GEMMs, row kernels) overlap instead of queueing behind each other.
-struct Fork {
+struct ForkStreams {                           // lives on the handle; whether a call forks is the call's (Step::fk)
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+};
+struct Fork : ForkStreams {
     bool on = false;
+    Fork() = default;
+    Fork(const ForkStreams& st, bool enabled) : ForkStreams(st), on(enabled) {}
     int fork(hipStream_t s) const {            // aux continues after everything enqueued on s so far
         if (!on) return 0;
         EXORL_CHECK_HIP(hipEventRecord(ev_fork, s));
@@ -391,7 +395,6 @@ struct exorl_agent {
     float* act_part = nullptr; unsigned int* act_ticket = nullptr;      // one-launch act(): head shares per workgroup, arrival ticket
     FwdBufs fact{};
     StepState* state = nullptr;  // device-resident counters + Adam scalars (graph-replayable)
-    const float *noise_c = nullptr, *noise_a = nullptr;   // caller-supplied noise of the step in flight (parity tests)
     int64_t actor_t = 0, critic_t = 0;       // host mirrors of state->t_*
     uint64_t act_noise_counter = 0;
     float inv_bg = 0.f;
@@ -404,19 +407,14 @@ struct exorl_agent {
     uint64_t graph_weights_epoch = 0;        // the replay's exorl_replay_set_weights count at capture: the graph samples that table
     uint64_t graph_replay_ctr = 0;           // host mirror of state->replay_counter: eager samples drawn between two launches move the replay's own
     exorl_intr* graph_intr = nullptr;        // joint graph (exorl_agent_enable_graph_intr): the module whose step rides in front of the agent's
-    bool capturing = false;
-    Fork fk{};                   // parallel-branch plumbing (active while capturing)
+    ForkStreams fk{};            // parallel-branch plumbing (a captured step forks when parallel_branches is set)
     bool parallel_branches = false;  // measured slower than one chain on MI355X (2987 vs 3259 steps/s): opt-in
-    bool fuse_opt = false;           // whole-step call on one GPU: partial-gradient reduction happens inside the optimiser launch
-    bool whole_step = false;         // exorl_agent_update / the captured graph drive all four phases: the fused scalar-head kernels may run
     // data parallel: RCCL communicator attached by exorl_agent_set_comm; the library enqueues the all-reduces between the phases
     exorl_comm* comm = nullptr;
     hipStream_t comm_stream = nullptr;           // the 16-byte statistic travels here while the critic's backward pass runs
     hipEvent_t ev_stats_ready = nullptr, ev_stats_done = nullptr;
-    FinalizeArgs pend_c{}, pend_a{};
-    bool staged_by_sampler = false;  // captured step: the sampler's gather kernel writes the staged inputs and runs step_begin
+    FinalizeArgs pend_c{}, pend_a{};             // fused optimiser launch: the partials a gradient phase left for the optimiser phase behind it
     bool want_metrics = true;    // the (B,1)-sized metric reductions are skipped when the caller never reads them (use_tb=False)
-    int tq_slots = 0;            // > 0: this step's target critic left per-row partial head dots in ft.h2 (folded into the forward GEMM)
     // windowed metrics (exorl_agent_set_metric_window; win_sums != nullptr is the mode): views of the caller's buffer, laid out as
     // [EXORL_N_METRICS double sums | int64 steps | pad to 256 B][qhead_chunks(B) x 6 critic partials][head_chunks(B) BC partials]
     double* win_sums = nullptr; long long* win_steps = nullptr;
@@ -601,46 +599,72 @@ static FusedAdamArgs fused_adam_args(exorl_agent* a, int net, const NetDesc& d, 
     return FusedAdamArgs{f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], target, c, d.n_heads,
                          {d.W1, d.W1 + d.head_stride}, reinterpret_cast<unsigned long long*>(bump)};
 }
-static int opt_step(exorl_agent* a, int net, const NetDesc& d, const FinalizeArgs& pend, const AdamConst* c, float* target, const ShadowSpec& spec,
-                    uint64_t* bump, hipStream_t s) {
+// How one driver call runs the step. Each driver builds one (make_step) before its first launch and hands it to every phase, so a step's launch
+// decisions are taken once, from the call's arguments and the handle's settings, and nothing of one call carries over to the next.
+//   exorl_agent_update_phase   one phase:                   whole = capture = staged = fork = false
+//   exorl_agent_update         all phases:                  whole
+//   enable_graph_impl          all phases under capture:    whole, capture; staged and fork as the replay and parallel_branches say
+struct Step {
+    hipStream_t s;
+    float stddev;
+    const float *noise_c, *noise_a;      // caller-supplied noise (parity tests), nullptr: device Philox
+    bool whole;                          // this call drives every phase: the fused scalar-head kernels may run
+    bool capture;                        // the launches are captured with the sampler in front: the step advances the replay counter itself
+    bool staged;                         // the sampler's gather kernel wrote the staged inputs and advanced the step state
+    Fork fk;                             // fk.on: independent branches go to the side stream
+    // derived once
+    bool fuse_opt;                       // one GPU, one chain: the optimiser launches reduce the gradient partials themselves
+    bool qfuse;                          // fused scalar-head path: whole-step call on one GPU, twin scalar heads, and nobody reads the step's metrics
+                                         // or they are collected in a window (the kernels' metrics variants then leave per-chunk sums for metrics_window)
+    bool metric_kernels;                 // critic_loss, actor_dmu run: always in window mode off the fused path, else when the caller reads the metrics
+    bool stats_in_phase2;                // TD3+BC on the fused path with a communicator: phase 2 reduces sum |Q| itself, on the side stream
+};
+static Step make_step(const exorl_agent* a, hipStream_t s, float stddev, const float* noise_c, const float* noise_a, bool whole, bool capture,
+                      bool staged, bool fork) {
+    const int kind = a->cfg.kind;
+    Step st{s, stddev, noise_c, noise_a, whole, capture, staged, Fork(a->fk, fork)};
+    st.fuse_opt = whole && !a->comm && !fork;
+    st.qfuse = whole && !fork && (!a->want_metrics || a->win_sums) && a->has_critic && a->critic.n_heads == 2 && a->critic.out_dim == 1 &&
+               a->cfg.hidden_dim % 4 == 0 && (kind == EXORL_AGENT_TD3_BC || kind == EXORL_AGENT_TD3 || kind == EXORL_AGENT_DDPG);
+    st.metric_kernels = a->win_sums ? !st.qfuse : a->want_metrics;
+    st.stats_in_phase2 = st.qfuse && a->comm && kind == EXORL_AGENT_TD3_BC;
+    return st;
+}
+
+static int opt_step(exorl_agent* a, const Step& st, int net, const NetDesc& d, const FinalizeArgs& pend, const AdamConst* c, float* target,
+                    const ShadowSpec& spec, uint64_t* bump) {
     float** f = a->flat[net];
-    if (a->fuse_opt) EXORL_TRY(finalize_adam(pend, fused_adam_args(a, net, d, c, target, bump), spec, s));
+    hipStream_t s = st.s;
+    if (st.fuse_opt) EXORL_TRY(finalize_adam(pend, fused_adam_args(a, net, d, c, target, bump), spec, s));
     else EXORL_TRY(adam_step_dev(f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], d.total, c, target, &spec, s, bump));
     // bf16x6 on the plane kernel: the stepped W1 (and the Polyak target's) as three planes for the next step's launches
     EXORL_TRY(refresh_w1_planes(d, f[EXORL_T_PARAM], net == EXORL_NET_ACTOR ? a->sh_actor : a->sh_critic, s));
     if (target) EXORL_TRY(refresh_w1_planes(d, target, a->sh_target, s));
     return 0;
 }
-static int opt_step_critic(exorl_agent* a, hipStream_t s) {
-    return opt_step(a, EXORL_NET_CRITIC, a->critic, a->pend_c, &a->state->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->spec_critic,
-                    nullptr, s);
+static int opt_step_critic(exorl_agent* a, const Step& st) {
+    return opt_step(a, st, EXORL_NET_CRITIC, a->critic, a->pend_c, &a->state->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM],
+                    a->spec_critic, nullptr);
 }
 
-// fused scalar-head path: whole-step call on one GPU, twin scalar heads, and nobody reads the step's metrics or they are collected in a window
-// (the kernels' metrics variants then leave per-chunk sums for metrics_window)
-static bool qfuse(const exorl_agent* a) {
-    return a->whole_step && !a->fk.on && (!a->want_metrics || a->win_sums) && a->has_critic && a->critic.n_heads == 2 && a->critic.out_dim == 1 && a->cfg.hidden_dim % 4 == 0 &&
-           (a->cfg.kind == EXORL_AGENT_TD3_BC || a->cfg.kind == EXORL_AGENT_TD3 || a->cfg.kind == EXORL_AGENT_DDPG);
-}
-// the step's metric kernels (critic_loss, actor_dmu) run: always in window mode off the fused path, else when the caller reads the metrics
-static bool step_metrics(const exorl_agent* a) { return a->win_sums ? !qfuse(a) : a->want_metrics; }
 constexpr size_t WIN_HEAD_BYTES = 256;       // the window's sums and step count
 static_assert(EXORL_N_METRICS * sizeof(double) + sizeof(long long) <= WIN_HEAD_BYTES, "the window's sums and step count fit its head");
 static size_t window_bytes(const exorl_agent_cfg& cfg) {
     return WIN_HEAD_BYTES + sizeof(float) * (size_t)round_up(6 * (int64_t)qhead_chunks(cfg.batch) + head_chunks(cfg.batch), 64);
 }
-static int run_metrics_window(exorl_agent* a, hipStream_t s) {
+static int run_metrics_window(exorl_agent* a, const Step& st) {
     const int B = a->cfg.batch;
     MetricsWindowArgs w{};
-    w.fused = qfuse(a) ? 1 : 0;
+    w.fused = st.qfuse ? 1 : 0;
     w.crit_part = a->win_crit; w.abs_part = a->abs_part; w.bc_part = a->win_bc;
     w.q_chunks = qhead_chunks(B); w.bc_chunks = a->cfg.kind == EXORL_AGENT_TD3_BC ? head_chunks(B) : 0;
     w.kind = a->cfg.kind; w.act_dim = a->cfg.act_dim; w.ent_from_std = a->cfg.kind != EXORL_AGENT_CQL;
     w.inv_bg = a->inv_bg; w.alpha = a->cfg.alpha; w.stddev = &a->state->stddev;
     w.metrics = a->metrics; w.sums = a->win_sums; w.steps = a->win_steps;
-    return metrics_window(w, s);
+    return metrics_window(w, st.s);
 }
-static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
+// tq_slots > 0 (mode 0): this step's target critic left per-row partial head dots in ft.h2 (folded into the forward GEMM, net_forward2)
+static int run_qhead(exorl_agent* a, const Step& st, int mode, int tq_slots) {
     const NetDesc& d = a->critic;
     const int B = a->cfg.batch, H = d.H;
     const int64_t act = (int64_t)B * H;
@@ -654,25 +678,25 @@ static int run_qhead(exorl_agent* a, int mode, hipStream_t s) {
     }
     q.q = a->fc.out; q.tq = a->ft.out; q.reward = a->reward; q.discount = a->discount;
     q.tpart[0] = q.tpart[1] = nullptr; q.tslots = 0;
-    if (mode == 0 && a->tq_slots > 0) {          // the target's heads were folded into its forward GEMM (net_forward2): ft.h2 holds partial dots
-        q.tpart[0] = a->ft.h2; q.tpart[1] = a->ft.h2 + act; q.tslots = a->tq_slots;
-    }
+    if (mode == 0 && tq_slots > 0) { q.tpart[0] = a->ft.h2; q.tpart[1] = a->ft.h2 + act; q.tslots = tq_slots; }
     q.dz = bf ? nullptr : a->bc.dz2; q.dzb = bf ? a->bc.dz2q.hi : nullptr; q.dzl = bf ? a->bc.dz2q.lo : nullptr; q.act = act;
     q.P = mode == 0 ? a->pc.Ph : nullptr;
     const bool met = mode == 0 && a->win_sums;       // the critic metrics' per-chunk sums ride in mode 0's otherwise unused abs_part
     q.abs_part = met ? a->win_crit : a->abs_part;
     q.rows = B; q.H = H; q.mode = mode; q.inv_bg = a->inv_bg;
-    return qhead(q, s, met);
+    return qhead(q, st.s, met);
 }
 
 // -- phase 0: everything up to the critic gradients -------------------------------------------------
-static int phase0(exorl_agent* a, float stddev, const float* noise_c, hipStream_t s) {
+static int phase0(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
+    const float stddev = st.stddev, *noise_c = st.noise_c;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
     // stages the inputs and (thread 0) advances the device-side step state: counters, Adam scalars of this step
-    if (!a->staged_by_sampler)
+    if (!st.staged)
         EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, a->has_critic, a->state,
-                                 a->capturing ? 1 : 0, s));
+                                 st.capture ? 1 : 0, s));
     a->actor_t += 1;
     if (a->has_critic) a->critic_t += 1;
     if (!a->has_critic) return 0;
@@ -682,26 +706,26 @@ static int phase0(exorl_agent* a, float stddev, const float* noise_c, hipStream_
     // actor on [next_obs; obs] in one pass (td3_bc.py:124 and :149 use the same weights)
     // next_action = dist.sample(clip) (td3_bc.py:125) and the actor-step sample pi(obs) (:151, it does not depend on the
     // critic update) straight into the two critic input buffers, as the epilogue of the actor head
-    a->noise_c = noise_c;
     const bool fused_sample = cfg.hidden_dim % 4 == 0 && A > 1;
-    SampleSpec sp{&a->state->stddev, noise_c, cfg.kind == EXORL_AGENT_CRR ? nullptr : a->noise_a, cfg.seed, &a->state->noise_counter, stddev, cfg.stddev_clip,
+    SampleSpec sp{&a->state->stddev, noise_c, cfg.kind == EXORL_AGENT_CRR ? nullptr : st.noise_a, cfg.seed, &a->state->noise_counter, stddev, cfg.stddev_clip,
                   a->xc_next + O, a->xc_pi + O, W, B};
     EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, true, true, prec, s, fused_sample ? &sp : nullptr));
     if (!fused_sample)
-        EXORL_TRY(sample_actions2(a->fa.out, noise_c, cfg.kind == EXORL_AGENT_CRR ? nullptr : a->noise_a, cfg.seed,
+        EXORL_TRY(sample_actions2(a->fa.out, noise_c, cfg.kind == EXORL_AGENT_CRR ? nullptr : st.noise_a, cfg.seed,
                                   &a->state->noise_counter, stddev, cfg.stddev_clip, a->xc_next + O, a->xc_pi + O, W, B, A, s, &a->state->stddev));
-    const bool qf = qfuse(a);
-    a->tq_slots = 0;
-    if (!a->fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
+    const bool qf = st.qfuse;
+    const Fork& fk = st.fk;
+    int tq_slots = 0;
+    if (!fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
         EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s, qf, qf,
-                               &a->tq_slots));
+                               &tq_slots));
     } else {
-        EXORL_TRY(a->fk.fork(s));               // target critic (td3_bc.py:126) and critic (td3_bc.py:130) forwards are independent
-        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, a->fk.side(s), nullptr, qf));
+        EXORL_TRY(fk.fork(s));                  // target critic (td3_bc.py:126) and critic (td3_bc.py:130) forwards are independent
+        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, fk.side(s), nullptr, qf));
         EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, true, false, prec, s, nullptr, qf));
-        EXORL_TRY(a->fk.join(s));
+        EXORL_TRY(fk.join(s));
     }
-    if (qf) EXORL_TRY(run_qhead(a, 0, s));       // Q, Q', TD gradient, dz2 and head partials in one kernel
+    if (qf) EXORL_TRY(run_qhead(a, st, 0, tq_slots));      // Q, Q', TD gradient, dz2 and head partials in one kernel
     const bool aps = cfg.kind == EXORL_AGENT_APS;
     const float* task = aps ? a->obs + (O - cfg.sf_dim) : nullptr;          // obs rows are [observation | task] (aps.py:236-238)
     const float *qv = a->fc.out, *tqv = a->ft.out;
@@ -710,22 +734,24 @@ static int phase0(exorl_agent* a, float stddev, const float* noise_c, hipStream_
         EXORL_TRY(sf_q(a->fc.out, task, O, a->sfq, B, cfg.sf_dim, 2, s));
         qv = a->sfq; tqv = a->sftq;
     }
-    if (step_metrics(a))
+    if (st.metric_kernels)
         EXORL_TRY(critic_loss(qv, tqv, a->reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));   // :133-137
     DoutSpec td{};                              // d(2 x MSE)/dQ computed where it is consumed (:127-131)
     td.mode = EXORL_DOUT_TD; td.q = qv; td.tq = tqv; td.reward = a->reward; td.discount = a->discount; td.inv_bg = a->inv_bg;
     td.task = task; td.task_ld = O;
     EXORL_TRY(net_backward(a->critic, Pc, a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc, a->xc_cur, W, B, a->fc, td,
-                           a->bc, nullptr, 0, 0, prec, s, a->fk, a->fuse_opt ? &a->pend_c : nullptr, qf));                  // :141
+                           a->bc, nullptr, 0, 0, prec, s, fk, st.fuse_opt ? &a->pend_c : nullptr, qf));                     // :141
     return 0;
 }
 
 // -- phase 1: critic optimiser step (+ fused soft update), critic re-evaluated at pi(obs) -------------
-static int phase1(exorl_agent* a, float stddev, const float* noise_a, hipStream_t s) {
+static int phase1(exorl_agent* a, const Step& st) {
     if (!a->has_critic) return 0;
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
+    const float stddev = st.stddev, *noise_a = st.noise_a;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
-    EXORL_TRY(opt_step_critic(a, s));
+    EXORL_TRY(opt_step_critic(a, st));
     if (cfg.kind == EXORL_AGENT_CRR) {          // crr.py:170-179 with the updated critic, no gradients
         const int n = cfg.num_value_samples;
         const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
@@ -740,7 +766,7 @@ static int phase1(exorl_agent* a, float stddev, const float* noise_a, hipStream_
     if ((cfg.kind == EXORL_AGENT_DDPG || cfg.kind == EXORL_AGENT_APS) && (a->want_metrics || a->win_sums))
         EXORL_TRY(sample_action(a->fa.out + (int64_t)B * A, noise_spec(a, noise_a, 1), stddev, cfg.stddev_clip, 1, a->xc_pi + O, W, B, A,
                                 a->metrics + EXORL_M_ACTOR_LOGPROB, s, &a->state->stddev, cfg.world_size));
-    const bool qf = qfuse(a);
+    const bool qf = st.qfuse;
     EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->xc_pi, W, B, a->fc, true, false, prec, s,
                           nullptr, qf));
     if (cfg.kind == EXORL_AGENT_APS) {
@@ -753,8 +779,11 @@ static int phase1(exorl_agent* a, float stddev, const float* noise_a, hipStream_
 }
 
 // -- phase 2: actor gradients -----------------------------------------------------------------------
-static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
+static int phase2(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
+    const float stddev = st.stddev;
+    const bool qf = st.qfuse;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
     if (a->has_critic && cfg.kind != EXORL_AGENT_CRR) {
@@ -762,9 +791,8 @@ static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
         dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.alpha = cfg.alpha;
         if (cfg.kind == EXORL_AGENT_APS) { dq.q = a->sfq; dq.task = a->obs + (O - cfg.sf_dim); dq.task_ld = O; }
         dq.use_lambda = cfg.kind == EXORL_AGENT_TD3_BC;
-        const bool qf = qfuse(a);
-        if (qf) EXORL_TRY(run_qhead(a, 1, s));   // Q(s, pi(s)), its min-routing gradient (lambda applied later), dz2, sum|Q| partials
-        if (qf && a->comm && dq.use_lambda) {    // lambda needs sum|Q| over the GLOBAL batch (td3_bc.py:154): reduce it while the critic's
+        if (qf) EXORL_TRY(run_qhead(a, st, 1, 0));   // Q(s, pi(s)), its min-routing gradient (lambda applied later), dz2, sum|Q| partials
+        if (st.stats_in_phase2) {                // lambda needs sum|Q| over the GLOBAL batch (td3_bc.py:154): reduce it while the critic's
             EXORL_TRY(reduce_pairs(a->abs_part, qhead_chunks(B), a->stats, s));          // backward pass runs (it does not depend on lambda)
             EXORL_CHECK_HIP(hipEventRecord(a->ev_stats_ready, s));
             EXORL_CHECK_HIP(hipStreamWaitEvent(a->comm_stream, a->ev_stats_ready, 0));
@@ -772,63 +800,64 @@ static int phase2(exorl_agent* a, float stddev, hipStream_t s) {
             EXORL_CHECK_HIP(hipEventRecord(a->ev_stats_done, a->comm_stream));
         }
         EXORL_TRY(net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, nullptr, a->pc, a->xc_pi, W, B, a->fc,
-                               dq, a->bc, a->da, O, A, prec, s, a->fk, nullptr, qf));
+                               dq, a->bc, a->da, O, A, prec, s, st.fk, nullptr, qf));
     }
     // the obs half (rows B..2B) of the stacked actor forward
     const FwdBufs f = a->fa.rows_from(B, H, A);
     if (!a->has_critic)       // BC (bc.py:82): the only forward of the step
         EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa + (int64_t)B * O, O, B, f, true, true, prec, s));
-    if (step_metrics(a))                        // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
+    if (st.metric_kernels)                      // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
         EXORL_TRY(actor_dmu(a->da, A, a->has_critic ? a->critic.n_trunks : 0, (int64_t)B * A, f.out, a->action,
                             a->has_critic ? nullptr : a->reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A, a->inv_bg, cfg.alpha,
                             cfg.kind, stddev, s, &a->state->stddev));
     DoutSpec dm{};
     dm.mode = EXORL_DOUT_ACTOR_MU; dm.da = a->da; dm.da_nets = a->has_critic ? a->critic.n_trunks : 0; dm.mu = f.out; dm.a_data = a->action;
     dm.kind = cfg.kind; dm.inv_bg = a->inv_bg; dm.stddev = stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
-    if (qfuse(a)) {                             // lambda = alpha / mean|Q| from the per-chunk sums qhead left behind
+    if (qf) {                                   // lambda = alpha / mean|Q| from the per-chunk sums qhead left behind
         dm.lam_parts = a->abs_part; dm.lam_chunks = qhead_chunks(B); dm.use_lambda = cfg.kind == EXORL_AGENT_TD3_BC; dm.alpha = cfg.alpha;
-        if (a->comm && dm.use_lambda) {          // the all-reduced statistic (one 'chunk': stats[0] = global sum |Q|)
+        if (st.stats_in_phase2) {                // the all-reduced statistic (one 'chunk': stats[0] = global sum |Q|)
             EXORL_CHECK_HIP(hipStreamWaitEvent(s, a->ev_stats_done, 0));
             dm.lam_parts = a->stats; dm.lam_chunks = 1;
         }
         if (a->win_sums && cfg.kind == EXORL_AGENT_TD3_BC) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
     }
     EXORL_TRY(net_backward(a->actor, Pa, a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa, a->xa + (int64_t)B * O, O, B, f,
-                           dm, a->ba, nullptr, 0, 0, prec, s, a->fk, a->fuse_opt ? &a->pend_a : nullptr));
+                           dm, a->ba, nullptr, 0, 0, prec, s, st.fk, st.fuse_opt ? &a->pend_a : nullptr));
     return 0;
 }
 
-static int phase3(exorl_agent* a, hipStream_t s) {
-    return opt_step(a, EXORL_NET_ACTOR, a->actor, a->pend_a, &a->state->actor, nullptr, a->spec_actor,
-                    a->staged_by_sampler ? &a->state->replay_counter : nullptr, s);
+static int phase3(exorl_agent* a, const Step& st) {
+    return opt_step(a, st, EXORL_NET_ACTOR, a->actor, a->pend_a, &a->state->actor, nullptr, a->spec_actor,
+                    st.staged ? &a->state->replay_counter : nullptr);
 }
 
 // ---- CQL (cql.py:152-263) ---------------------------------------------------------------------------
-static CqlNoise cql_noise(exorl_agent* a) {
+static CqlNoise cql_noise(exorl_agent* a, const Step& st) {
     const int64_t BA = (int64_t)a->cfg.batch * a->cfg.act_dim, n = a->cfg.n_samples;
-    const float* nc = a->noise_c;
+    const float* nc = st.noise_c;
     CqlNoise z{};
     z.z_next = nc; z.u_rand = nc ? nc + BA : nullptr; z.z_cur = nc ? nc + (1 + n) * BA : nullptr;
-    z.z_nxt = nc ? nc + (1 + 2 * n) * BA : nullptr; z.z_actor = a->noise_a;
+    z.z_nxt = nc ? nc + (1 + 2 * n) * BA : nullptr; z.z_actor = st.noise_a;
     z.seed = a->cfg.seed; z.counter_ptr = &a->state->noise_counter;
     return z;
 }
 
 // Phase 0 in two halves. One GPU (and data parallel without the Lagrange multiplier) runs them back to back. With use_critic_lagrange under
 // torch.distributed the host drives them as phases 4 and 5 and sum-all-reduces the statistics block in between (cql.hip, cql_critic_dq_kernel).
-static int cql_phase0a(exorl_agent* a, hipStream_t s, bool split) {
+static int cql_phase0a(exorl_agent* a, const Step& st, bool split) {
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, n = cfg.n_samples, prec = cfg.precision;
     const int R = (3 * n + 1) * B;
-    if (!a->staged_by_sampler)
+    if (!st.staged)
         EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, a->state,
-                                 a->capturing ? 1 : 0, s));
+                                 st.capture ? 1 : 0, s));
     a->actor_t += 1;
     a->critic_t += 1;
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
     EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, true, false, prec, s));      // raw (mu | log_std) on [next_obs; obs]
-    EXORL_TRY(cql_build_inputs(a->obs, a->action, a->fa.out, cql_noise(a), a->xc_next, a->x_all, B, O, A, n, s));
+    EXORL_TRY(cql_build_inputs(a->obs, a->action, a->fa.out, cql_noise(a, st), a->xc_next, a->x_all, B, O, A, n, s));
     EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->sh_target, a->xc_next, W, B, a->ft, false, false,
                           prec, s));                                                                     // cql.py:160
     EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->x_all, W, R, a->fc, true, false, prec, s));     // cql.py:166,179-184 in one pass
@@ -838,8 +867,9 @@ static int cql_phase0a(exorl_agent* a, hipStream_t s, bool split) {
     return 0;
 }
 
-static int cql_phase0b(exorl_agent* a, hipStream_t s, bool split) {
+static int cql_phase0b(exorl_agent* a, const Step& st, bool split) {
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, n = cfg.n_samples, prec = cfg.precision;
     const int R = (3 * n + 1) * B;
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
@@ -848,40 +878,122 @@ static int cql_phase0b(exorl_agent* a, hipStream_t s, bool split) {
     DoutSpec d{};
     d.mode = EXORL_DOUT_BUFFER; d.buf = a->dq_all;
     EXORL_TRY(net_backward(a->critic, Pc, a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc, a->x_all, W, R, a->fc, d, a->bc,
-                           nullptr, 0, 0, prec, s, a->fk, a->fuse_opt ? &a->pend_c : nullptr));
+                           nullptr, 0, 0, prec, s, st.fk, st.fuse_opt ? &a->pend_c : nullptr));
     return 0;
 }
 
-static int cql_phase0(exorl_agent* a, hipStream_t s) {
+static int cql_phase0(exorl_agent* a, const Step& st) {
     EXORL_REQUIRE(!(a->cfg.use_critic_lagrange && a->cfg.world_size > 1), "agent_update_phase: CQL with use_critic_lagrange under data parallelism "
                   "runs phase 0 as phases 4 and 5 with a sum-all-reduce of exorl_agent_stats in between");
-    EXORL_TRY(cql_phase0a(a, s, false));
-    return cql_phase0b(a, s, false);
+    EXORL_TRY(cql_phase0a(a, st, false));
+    return cql_phase0b(a, st, false);
 }
 
-static int cql_phase1(exorl_agent* a, hipStream_t s) {
+static int cql_phase1(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
-    EXORL_TRY(opt_step_critic(a, s));
-    EXORL_TRY(cql_actor_sample(a->fa.out + (int64_t)B * 2 * A, cql_noise(a), a->xc_pi, W, a->stats, B, O, A, s));    // cql.py:237-239
+    EXORL_TRY(opt_step_critic(a, st));
+    EXORL_TRY(cql_actor_sample(a->fa.out + (int64_t)B * 2 * A, cql_noise(a, st), a->xc_pi, W, a->stats, B, O, A, s));    // cql.py:237-239
     EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->xc_pi, W, B, a->fc, true, false, prec, s));
     return 0;
 }
 
-static int cql_phase2(exorl_agent* a, hipStream_t s) {
+static int cql_phase2(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
     EXORL_TRY(cql_alpha_step(a->cql, a->stats, &a->state->actor, a->metrics, B, A, a->inv_bg, a->fc.out, s));    // cql.py:241-247
     DoutSpec dq{};
     dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.use_lambda = 0;
     EXORL_TRY(net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, nullptr, a->pc, a->xc_pi, W, B, a->fc, dq,
-                           a->bc, a->da, O, A, prec, s, a->fk));
+                           a->bc, a->da, O, A, prec, s, st.fk));
     const FwdBufs f = a->fa.rows_from(B, H, 2 * A);
     DoutSpec dm{};
-    dm.mode = EXORL_DOUT_CQL_ACTOR; dm.da = a->da; dm.da_nets = a->critic.n_trunks; dm.raw = f.out; dm.z = a->noise_a;
+    dm.mode = EXORL_DOUT_CQL_ACTOR; dm.da = a->da; dm.da_nets = a->critic.n_trunks; dm.raw = f.out; dm.z = st.noise_a;
     dm.alpha_ptr = &a->cql->alpha; dm.inv_bg = a->inv_bg; dm.seed = cfg.seed; dm.counter = 4; dm.counter_ptr = &a->state->noise_counter;
     EXORL_TRY(net_backward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa,
-                           a->xa + (int64_t)B * O, O, B, f, dm, a->ba, nullptr, 0, 0, prec, s, a->fk, a->fuse_opt ? &a->pend_a : nullptr));
+                           a->xa + (int64_t)B * O, O, B, f, dm, a->ba, nullptr, 0, 0, prec, s, st.fk, st.fuse_opt ? &a->pend_a : nullptr));
+    return 0;
+}
+
+// ---- the step as a plan -----------------------------------------------------------------------------
+// One update is the ordered list of its phases; where the data-parallel step (dp) needs a global batch quantity before the next phase, the plan
+// names the exchange that follows (EXORL_AGENT_XCHG_*, each a sum all-reduce), else -1. Both drivers read it: whole_step_body, which runs the
+// exchanges on the library's communicator, and through exorl_agent_update_plan the caller that runs them itself (AgentEngine.update_steps).
+//   critic gradients   after phase 0, every kind with a critic
+//   statistics         after phase 1: TD3+BC's sum |Q| behind lambda (td3_bc.py:154), unless phase 2 reduces it itself on the side stream
+//                      (stats_in_phase2); CQL's sum of log pi for the entropy temperature (cql.py:242-243)
+//   actor gradients    after phase 2
+// CQL's Lagrange multiplier steps on the penalty of the GLOBAL batch inside phase 0 (cql.py:199-213): data parallel, phases 4 and 5 stand for
+// phase 0 with the statistics (this rank's penalty sums) exchanged in between.
+struct AgentPlan {
+    int n = 0;
+    int phase[5], xchg[5];         // xchg: the exchange that follows the phase, or -1
+    void add(int ph, int x = -1) { phase[n] = ph; xchg[n++] = x; }
+};
+static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_phase2) {
+    const int kind = c.kind;
+    auto after = [&](bool on, int x) { return dp && on ? x : -1; };
+    AgentPlan p;
+    if (dp && kind == EXORL_AGENT_CQL && c.use_critic_lagrange) {
+        p.add(4, EXORL_AGENT_XCHG_STATS);
+        p.add(5, EXORL_AGENT_XCHG_CRITIC_GRAD);
+    } else {
+        p.add(0, after(kind != EXORL_AGENT_BC, EXORL_AGENT_XCHG_CRITIC_GRAD));
+    }
+    p.add(1, after((kind == EXORL_AGENT_TD3_BC && !stats_in_phase2) || kind == EXORL_AGENT_CQL, EXORL_AGENT_XCHG_STATS));
+    p.add(2, after(true, EXORL_AGENT_XCHG_ACTOR_GRAD));
+    p.add(3);
+    return p;
+}
+
+static int run_phase(exorl_agent* a, const Step& st, int phase) {
+    if (a->cfg.kind == EXORL_AGENT_CQL) {
+        switch (phase) {
+            case 0: return cql_phase0(a, st);
+            case 1: return cql_phase1(a, st);
+            case 2: return cql_phase2(a, st);
+            case 3: return phase3(a, st);
+            case 4: return cql_phase0a(a, st, true);       // use_critic_lagrange under data parallelism: phase 0 up to the penalty sums ...
+            case 5: return cql_phase0b(a, st, true);       // ... and from the global penalty on
+        }
+    }
+    switch (phase) {
+        case 0: return phase0(a, st);
+        case 1: return phase1(a, st);
+        case 2: return phase2(a, st);
+        case 3: return phase3(a, st);
+    }
+    set_error("agent_update_phase: phase %d out of range", phase);
+    return 2;
+}
+
+// the kernels read the exploration std from the device step state; enqueue a new value only when the schedule moved (a captured graph is
+// std-agnostic: exorl_agent_step_graph writes it before the launch)
+static int push_stddev(exorl_agent* a, float stddev, hipStream_t s) {
+    EXORL_REQUIRE(stddev > 0.f || a->cfg.kind == EXORL_AGENT_CQL, "agent_update_phase: stddev must be > 0");
+    if (a->cfg.kind != EXORL_AGENT_CQL && stddev != a->dev_stddev) {
+        EXORL_TRY(set_device_float(&a->state->stddev, stddev, s));
+        a->dev_stddev = stddev;
+    }
+    return 0;
+}
+
+// One whole update, eager (exorl_agent_update) or under capture: the plan's phases, each followed by its exchange on the library's communicator.
+// one GPU: nothing is exchanged between the phases, the optimiser launches reduce the gradient partials themselves.
+// data parallel: gradients are finalised into the flat buffers, sum-all-reduced over RCCL on this stream, then stepped.
+static int whole_step_body(exorl_agent* a, const Step& st) {
+    const AgentPlan p = agent_plan(a->cfg, a->comm != nullptr, st.stats_in_phase2);
+    for (int i = 0; i < p.n; ++i) {
+        EXORL_TRY(run_phase(a, st, p.phase[i]));
+        switch (p.xchg[i]) {
+            case EXORL_AGENT_XCHG_CRITIC_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->critic.total, st.s)); break;
+            case EXORL_AGENT_XCHG_STATS: EXORL_TRY(comm_allreduce_sum(a->comm, a->stats, 4, st.s)); break;
+            case EXORL_AGENT_XCHG_ACTOR_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->actor.total, st.s)); break;
+        }
+    }
+    if (a->win_sums) EXORL_TRY(run_metrics_window(a, st));      // the step's metrics into the window (and, on the fused path, into a->metrics)
     return 0;
 }
 
@@ -1031,71 +1143,29 @@ int exorl_agent_set_batch(exorl_agent_t* a, const float* obs, const float* actio
 
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_c, const float* noise_a, void* stream) {
     EXORL_REQUIRE(a, "agent_update_phase: null handle");
-    EXORL_REQUIRE(stddev > 0.f || a->cfg.kind == EXORL_AGENT_CQL, "agent_update_phase: stddev must be > 0");
     hipStream_t s = as_stream(stream);
-    a->noise_a = noise_a;
-    // the kernels read the exploration std from the device step state; enqueue a new value only when the schedule moved
-    // (never while capturing: a captured graph is std-agnostic, exorl_agent_step_graph writes it before the launch)
-    if (!a->capturing && a->cfg.kind != EXORL_AGENT_CQL && stddev != a->dev_stddev) {
-        EXORL_TRY(set_device_float(&a->state->stddev, stddev, s));
-        a->dev_stddev = stddev;
-    }
-    if (a->cfg.kind == EXORL_AGENT_CQL) {
-        a->noise_c = noise_c;
-        switch (phase) {
-            case 0: return cql_phase0(a, s);
-            case 1: return cql_phase1(a, s);
-            case 2: return cql_phase2(a, s);
-            case 3: return phase3(a, s);
-            case 4: return cql_phase0a(a, s, true);        // use_critic_lagrange under data parallelism: phase 0 up to the penalty sums ...
-            case 5: return cql_phase0b(a, s, true);        // ... and from the global penalty on
-        }
-    }
-    switch (phase) {
-        case 0: return phase0(a, stddev, noise_c, s);
-        case 1: return phase1(a, stddev, noise_a, s);
-        case 2: return phase2(a, stddev, s);
-        case 3: return phase3(a, s);
-    }
-    set_error("agent_update_phase: phase %d out of range", phase);
-    return 2;
-}
-
-// The four phases of one update with the data-parallel exchanges between them (a->comm != nullptr); shared by the eager whole-step call
-// and by the graph capture.
-// one GPU: nothing is exchanged between the phases, the optimiser launches reduce the gradient partials themselves.
-// data parallel: gradients are finalised into the flat buffers, sum-all-reduced over RCCL on this stream, then stepped.
-static int whole_step_body(exorl_agent* a, float stddev, const float* noise_c, const float* noise_a, hipStream_t s) {
-    const bool dp = a->comm != nullptr;
-    const int kind = a->cfg.kind;
-    // CQL's Lagrange multiplier steps on the penalty of the GLOBAL batch inside phase 0: with a communicator phase 0 runs as 4 | all-reduce | 5
-    const bool lag_dp = dp && kind == EXORL_AGENT_CQL && a->cfg.use_critic_lagrange;
-    int rc = exorl_agent_update_phase(a, lag_dp ? 4 : 0, stddev, noise_c, noise_a, s);
-    if (rc == 0 && lag_dp) rc = comm_allreduce_sum(a->comm, a->stats, 4, s);
-    if (rc == 0 && lag_dp) rc = exorl_agent_update_phase(a, 5, stddev, noise_c, noise_a, s);
-    if (rc == 0 && dp && a->has_critic) rc = comm_allreduce_sum(a->comm, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->critic.total, s);
-    if (rc == 0) rc = exorl_agent_update_phase(a, 1, stddev, noise_c, noise_a, s);
-    // TD3+BC's sum |Q| (lambda) / CQL's sum log pi (entropy temperature); the fused scalar-head path moves it inside phase 2
-    if (rc == 0 && dp && ((kind == EXORL_AGENT_TD3_BC && !qfuse(a)) || kind == EXORL_AGENT_CQL)) rc = comm_allreduce_sum(a->comm, a->stats, 4, s);
-    if (rc == 0) rc = exorl_agent_update_phase(a, 2, stddev, noise_c, noise_a, s);
-    if (rc == 0 && dp) rc = comm_allreduce_sum(a->comm, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->actor.total, s);
-    if (rc == 0) rc = exorl_agent_update_phase(a, 3, stddev, noise_c, noise_a, s);
-    if (rc == 0 && a->win_sums) rc = run_metrics_window(a, s);      // the step's metrics into the window (and, on the fused path, into a->metrics)
-    return rc;
+    EXORL_TRY(push_stddev(a, stddev, s));
+    return run_phase(a, make_step(a, s, stddev, noise_c, noise_a, false, false, false, false), phase);
 }
 
 int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_c, const float* noise_a, void* stream) {
     EXORL_REQUIRE(a, "agent_update: null handle");
-    const bool dp = a->comm != nullptr;
-    EXORL_REQUIRE(a->cfg.world_size == 1 || dp, "agent_update: world_size=%d needs a communicator (exorl_agent_set_comm), or drive "
+    EXORL_REQUIRE(a->cfg.world_size == 1 || a->comm, "agent_update: world_size=%d needs a communicator (exorl_agent_set_comm), or drive "
                   "exorl_agent_update_phase and all-reduce between the phases yourself", a->cfg.world_size);
     hipStream_t s = as_stream(stream);
-    a->whole_step = true;
-    a->fuse_opt = !dp && !a->fk.on;
-    const int rc = whole_step_body(a, stddev, noise_c, noise_a, s);
-    a->fuse_opt = false;
-    a->whole_step = false;
-    return rc;
+    EXORL_TRY(push_stddev(a, stddev, s));
+    return whole_step_body(a, make_step(a, s, stddev, noise_c, noise_a, true, false, false, false));
+}
+
+int exorl_agent_update_plan(const exorl_agent_cfg* cfg, int32_t* phases, int32_t* exchanges, int32_t capacity, int32_t* n) {
+    EXORL_REQUIRE(cfg && phases && exchanges && n, "agent_update_plan: null argument");
+    exorl_agent tmp;
+    EXORL_TRY(describe(&tmp, cfg));
+    const AgentPlan p = agent_plan(*cfg, cfg->world_size > 1, false);
+    EXORL_REQUIRE(capacity >= p.n, "agent_update_plan: capacity %d, the plan has %d phases", capacity, p.n);
+    for (int i = 0; i < p.n; ++i) { phases[i] = p.phase[i]; exchanges[i] = p.xchg[i]; }
+    *n = p.n;
+    return 0;
 }
 
 int exorl_agent_set_comm(exorl_agent_t* a, exorl_comm_t* c) {
@@ -1239,26 +1309,18 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
         EXORL_CHECK_HIP(hipEventCreateWithFlags(&a->fk.ev_join, hipEventDisableTiming));
     }
     EXORL_CHECK_HIP(hipStreamBeginCapture(a->capture_stream, hipStreamCaptureModeThreadLocal));
-    a->capturing = true;
-    a->fk.on = a->parallel_branches;
-    // fp32 state observations: the gather kernel writes the networks' staged inputs itself and runs step_begin (one kernel
+    // fp32 state observations: the gather kernel writes the networks' staged inputs itself and runs step_begin_device (one kernel
     // boundary less per step); the replay counter is then advanced by the step's last kernel (the actor's optimiser pass)
     StageOut stage{a->xa, a->xc_cur, a->xc_next, a->xc_pi, a->cfg.obs_dim, a->cfg.act_dim, a->cfg.batch, a->has_critic ? 1 : 0, a->state};
-    a->staged_by_sampler = replay_obs_bytes(r) == a->cfg.obs_dim * 4;
+    const bool staged = replay_obs_bytes(r) == a->cfg.obs_dim * 4;
     int rc = replay_sample_impl(r, a->cfg.batch, nstep, gamma, EXORL_SAMPLER_PHILOX, nullptr, &slots, nullptr, a->capture_stream,
-                                &a->state->replay_counter, a->staged_by_sampler ? &stage : nullptr);
+                                &a->state->replay_counter, staged ? &stage : nullptr);
     if (rc == 0 && meta_dim > 0) rc = copy_meta_columns(a->obs, a->next_obs, a->cfg.obs_dim, a->cfg.batch, O_raw, meta_dim, a->capture_stream);
     // the module reads the batch slots and writes the reward slot only: what the sampler staged for the networks (observations and actions)
     // stays valid, and the agent's step reads the reward from its slot after this
     if (rc == 0 && it) rc = intr_graph_capture(it, ib, a->capture_stream);
-    a->fuse_opt = !a->comm && !a->fk.on;
-    a->whole_step = true;
-    if (rc == 0) rc = whole_step_body(a, stddev, nullptr, nullptr, a->capture_stream);      // RCCL's all-reduces are captured with the kernels around them
-    a->fuse_opt = false;
-    a->whole_step = false;
-    a->staged_by_sampler = false;
-    a->capturing = false;
-    a->fk.on = false;
+    // RCCL's all-reduces are captured with the kernels around them
+    if (rc == 0) rc = whole_step_body(a, make_step(a, a->capture_stream, stddev, nullptr, nullptr, true, true, staged, a->parallel_branches));
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(a->capture_stream, &g);
     a->actor_t = t_a; a->critic_t = t_c;             // capture enqueued nothing: undo the host-side bookkeeping

@@ -93,10 +93,6 @@ int linear_splitk(int prec, const float* x, int64_t ldx, const float* W, const f
                   int splits, hipStream_t s);
 int head_fwd(const float* a, const float* W, const float* b, float* out, int rows, int H, int nout, int tanh_out,
              int nets, int64_t astride, int64_t pstride, int64_t ostride, hipStream_t s);
-int head_bwd_dx(const float* dout, const float* W, const float* a, float* dz, int rows, int H, int nout,
-                int nets, int64_t astride, int64_t pstride, int64_t dstride, hipStream_t s);
-int head_bwd_params(const float* dout, const float* a, const float* dz, float* dW, float* db_hidden, float* db_out,
-                    int rows, int H, int nout, int nets, int64_t astride, int64_t pstride, int64_t dstride, hipStream_t s);
 
 // ---- fused layer kernels (fused.hip)
 int trunk_fwd(const float* x, int64_t ldx, const float* W0T, const float* b0, const float* gain, const float* beta,
@@ -300,7 +296,7 @@ struct NoiseSpec {           // where TruncatedNormal noise comes from
     const float* buf;        // (B,A) standard normal draws, or nullptr -> Philox(seed, counter)
     uint64_t seed;
     uint64_t counter;              // draw id = counter + (counter_ptr ? *counter_ptr : 0)
-    const uint64_t* counter_ptr;   // device-resident base (advanced by step_begin) so a captured graph replays fresh draws
+    const uint64_t* counter_ptr;   // device-resident base (advanced by step_begin_device) so a captured graph replays fresh draws
 };
 
 struct AdamConst {           // fp32 scalars of one torch.optim.Adam step (bias corrections folded in)
@@ -330,7 +326,6 @@ struct StepState {
     float stddev;                // exploration std of the step (utils.schedule value): read through a pointer, so a schedule
                                  // that moves every step needs no re-capture of the hipGraph
 };
-int step_begin(StepState* st, int advance_replay, hipStream_t s);
 
 // The same for an intrinsic-reward module (intr.hip): what changes from one exorl_intr_update to the next. The host keeps the truth
 // (exorl_intr::t, cat_counter, queue_ptr) and pushes it here before a graph launch whenever an eager step or a setter moved it; a captured

@@ -122,10 +122,6 @@ int adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const
     return 0;
 }
 
-__global__ void step_begin_kernel(StepState* st, int advance_replay) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) step_begin_device(st, advance_replay);
-}
-
 __global__ void set_device_float_kernel(float* dst, float value) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *dst = value;
 }
@@ -143,12 +139,6 @@ __global__ void set_device_u64_kernel(uint64_t* dst, uint64_t value) {
 
 int set_device_u64(uint64_t* dst, uint64_t value, hipStream_t s) {
     hipLaunchKernelGGL(set_device_u64_kernel, dim3(1), dim3(64), 0, s, dst, value);
-    EXORL_LAUNCH_CHECK();
-    return 0;
-}
-
-int step_begin(StepState* st, int advance_replay, hipStream_t s) {
-    hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(64), 0, s, st, advance_replay);
     EXORL_LAUNCH_CHECK();
     return 0;
 }

@@ -375,88 +375,6 @@ int head_fwd(const float* a, const float* W, const float* b, float* out, int row
     return 0;
 }
 
-// dz[m][c] = (sum_j dout[m][j] W[j][c]) * (a[m][c] > 0)     (Linear(H,n) dgrad fused with the ReLU mask)
-__global__ __launch_bounds__(256) void head_bwd_dx_kernel(const float* __restrict__ dout, const float* __restrict__ W,
-                                                          const float* __restrict__ a, float* __restrict__ dz, int rows,
-                                                          int H, int nout, int64_t astride, int64_t pstride,
-                                                          int64_t dstride) {
-    const int net = blockIdx.z;
-    const int row = blockIdx.y;
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= H) return;
-    const float* d = dout + net * dstride + (int64_t)row * nout;
-    const float* Wn = W + net * pstride;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAX_NOUT; ++j)
-        if (j < nout) s += d[j] * Wn[(int64_t)j * H + c];
-    const int64_t i = net * astride + (int64_t)row * H + c;
-    dz[i] = a[i] > 0.f ? s : 0.f;
-}
-
-int head_bwd_dx(const float* dout, const float* W, const float* a, float* dz, int rows, int H, int nout,
-                int nets, int64_t astride, int64_t pstride, int64_t dstride, hipStream_t s) {
-    EXORL_REQUIRE(nout >= 1 && nout <= MAX_NOUT, "head_bwd_dx: nout=%d unsupported", nout);
-    dim3 grid(cdiv(H, 256), rows, nets);
-    hipLaunchKernelGGL(head_bwd_dx_kernel, grid, dim3(256), 0, s, dout, W, a, dz, rows, H, nout, astride, pstride, dstride);
-    EXORL_LAUNCH_CHECK();
-    return 0;
-}
-
-// dW[j][c] = sum_m dout[m][j] a[m][c];  db_hidden[c] = sum_m dz[m][c];  db_out[j] = sum_m dout[m][j]
-__global__ __launch_bounds__(1024) void head_bwd_params_kernel(const float* __restrict__ dout, const float* __restrict__ a,
-                                                               const float* __restrict__ dz, float* __restrict__ dW,
-                                                               float* __restrict__ db_hidden, float* __restrict__ db_out,
-                                                               int rows, int H, int nout, int64_t astride,
-                                                               int64_t pstride, int64_t dstride) {
-    __shared__ float red[16][64];
-    const int net = blockIdx.y;
-    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cx;
-    const float* d = dout + net * dstride;
-    float acc[MAX_NOUT];
-#pragma unroll
-    for (int j = 0; j < MAX_NOUT; ++j) acc[j] = 0.f;
-    float sb = 0.f;
-    if (c < H) {
-        for (int r = ry; r < rows; r += 16) {
-            const int64_t i = net * astride + (int64_t)r * H + c;
-            const float av = a[i];
-            sb += dz[i];
-#pragma unroll
-            for (int j = 0; j < MAX_NOUT; ++j)
-                if (j < nout) acc[j] += d[(int64_t)r * nout + j] * av;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < MAX_NOUT; ++j) {
-        if (j < nout) {
-            const float t = block_colreduce(acc[j], red, cx, ry);
-            if (ry == 0 && c < H) dW[net * pstride + (int64_t)j * H + c] = t;
-        }
-    }
-    const float tb = block_colreduce(sb, red, cx, ry);
-    if (ry == 0 && c < H) db_hidden[net * pstride + c] = tb;
-    if (blockIdx.x == 0 && ry == 0) {     // wave 0: db_out
-        for (int j = 0; j < nout; ++j) {
-            float sj = 0.f;
-            for (int r = cx; r < rows; r += 64) sj += d[(int64_t)r * nout + j];
-            sj = wave_sum(sj);
-            if (cx == 0) db_out[net * pstride + j] = sj;
-        }
-    }
-}
-
-int head_bwd_params(const float* dout, const float* a, const float* dz, float* dW, float* db_hidden, float* db_out,
-                    int rows, int H, int nout, int nets, int64_t astride, int64_t pstride, int64_t dstride, hipStream_t s) {
-    EXORL_REQUIRE(nout >= 1 && nout <= MAX_NOUT, "head_bwd_params: nout=%d unsupported", nout);
-    dim3 grid(cdiv(H, 64), nets);
-    hipLaunchKernelGGL(head_bwd_params_kernel, grid, dim3(1024), 0, s, dout, a, dz, dW, db_hidden, db_out, rows, H, nout,
-                       astride, pstride, dstride);
-    EXORL_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace exorl
 
 extern "C" int exorl_ln_tanh_fwd(const float* z, const float* gain, const float* beta, float* h, float* xhat,

@@ -93,7 +93,7 @@ class AgentEngine(_Phased):
                               lr, tau, alpha, stddev_clip if stddev_clip is not None else 0.0, seed, num_value_samples,
                               L.CRR_WEIGHT[weight_func], n_samples, int(bool(use_critic_lagrange)), target_cql_penalty, 0)
         self.obs_dim, self.act_dim, self.hidden_dim, self.batch = obs_dim, act_dim, hidden_dim, batch
-        self.world_size, self.lagrange = world_size, kind == 'cql' and bool(use_critic_lagrange)
+        self.world_size = world_size
         self._create('agent', cfg)
         self.has_critic = kind != 'bc'
 
@@ -143,27 +143,23 @@ class AgentEngine(_Phased):
         L.check(self.lib.exorl_agent_update_phase(self.h, phase, stddev, L.ptr(nc), L.ptr(na), L.current_stream()))
         self._keep_noise = (nc, na)
 
+    def exchange(self, xid):
+        """The buffer of exchange `xid` (L.AGENT_XCHG_*); every one is sum-all-reduced in place."""
+        if xid == L.AGENT_XCHG_STATS:
+            return self.stats()
+        return self.flat({L.AGENT_XCHG_CRITIC_GRAD: L.NET_CRITIC, L.AGENT_XCHG_ACTOR_GRAD: L.NET_ACTOR}[xid], L.T_GRAD)
+
     def update_steps(self, stddev, noise_critic=None, noise_actor=None):
-        """update() as its phases, for run_steps: yields the (buffer, op) to exchange across the ranks before the next phase. The
-        three global quantities are sum-all-reduced: the critic's gradients, the batch statistic of the kinds that have one (TD3+BC's
-        lambda; CQL's sum of log_pi for the entropy temperature, cql.py:242-243), the actor's gradients. With CQL's Lagrange weight
-        phases 4, 5 stand for phase 0: the multiplier steps on the GLOBAL penalty (this rank's sum of logsumexp and of Q1 + Q2) before
-        any critic gradient is formed (cql.py:199-213)."""
-        phase = lambda p: self.update_phase(p, stddev, noise_critic, noise_actor)
-        if self.lagrange:
-            phase(4)
-            yield self.stats(), L.XCHG_SUM
-            phase(5)
-        else:
-            phase(0)
-        if self.has_critic:
-            yield self.flat(L.NET_CRITIC, L.T_GRAD), L.XCHG_SUM
-        phase(1)
-        if self.kind in ('td3_bc', 'cql'):
-            yield self.stats(), L.XCHG_SUM
-        phase(2)
-        yield self.flat(L.NET_ACTOR, L.T_GRAD), L.XCHG_SUM
-        phase(3)
+        """update() as its phases, for run_steps: yields the (buffer, op) to exchange across the ranks before the next phase. The library
+        names the phases and the exchange behind each (exorl_agent_update_plan): the critic's gradients, the batch statistic of the
+        kinds that have one (TD3+BC's lambda; CQL's sum of log_pi for the entropy temperature and, with the Lagrange weight, the penalty
+        sums between phases 4 and 5), the actor's gradients."""
+        phases, xids, n = (C.c_int32 * 8)(), (C.c_int32 * 8)(), C.c_int32()
+        L.check(self.lib.exorl_agent_update_plan(C.byref(self.cfg), phases, xids, 8, C.byref(n)))
+        for phase, xid in zip(phases[:n.value], xids[:n.value]):
+            self.update_phase(phase, stddev, noise_critic, noise_actor)
+            if xid >= 0:
+                yield self.exchange(xid), L.XCHG_SUM
 
     def run_update(self, *a, **k):
         """One gradient step on any world size: update() — one host call; with a communicator the library all-reduces between its

@@ -39,7 +39,7 @@ extern "C" {
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
                                         exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights,
-                                        exorl_replay_set_frame_stack) */
+                                        exorl_replay_set_frame_stack, exorl_agent_update_plan) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -243,18 +243,24 @@ int exorl_agent_set_batch(exorl_agent_t* a, const float* obs_dev, const float* a
  * z_nxt (n,B,A)] back to back, noise_actor_dev = z_actor (B,A). Runs phases 0..3 back to back (world_size 1). */
 int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_critic_dev,
                        const float* noise_actor_dev, void* stream);
-/* Data-parallel form: the caller all-reduces (sum) between phases:
- *   phase 0 -> critic grads ready       (all-reduce EXORL_NET_CRITIC / EXORL_T_GRAD flat buffer)
- *   phase 1 -> critic Adam + soft update, actor-side Q statistics ready (all-reduce the 4-float stats buffer)
- *   phase 2 -> actor grads ready        (all-reduce EXORL_NET_ACTOR / EXORL_T_GRAD flat buffer)
- *   phase 3 -> actor Adam
- * BC has phases 2 and 3 only.
- * CQL with use_critic_lagrange under data parallelism (cql.py:199-213: the multiplier's own step needs the penalty of the GLOBAL batch before
- * any critic gradient exists): phase 0 is driven as
- *   phase 4 -> forwards done, this rank's penalty sums in the stats buffer (all-reduce the 4-float stats buffer)
- *   phase 5 -> multiplier stepped from the global penalty, critic grads ready (then as after phase 0). */
+/* One phase of the step, for the caller that runs the data-parallel exchanges itself. What each phase leaves ready:
+ *   phase 0 -> critic grads             (BC: the staged inputs only, and phase 1 does nothing)
+ *   phase 1 -> critic Adam + soft update done, actor-side Q statistics in the 4-float stats buffer
+ *   phase 2 -> actor grads
+ *   phase 3 -> actor Adam done
+ *   phase 4 -> CQL, phase 0's first half: forwards done, this rank's penalty sums in the stats buffer
+ *   phase 5 -> CQL, phase 0's second half: multiplier stepped from the global penalty (cql.py:199-213), critic grads
+ * Which phases a configuration's step runs, in which order, and which exchange follows each: exorl_agent_update_plan. Phase 0 is refused for
+ * CQL with use_critic_lagrange and world_size > 1 (phases 4 and 5 stand for it). */
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_critic_dev,
                              const float* noise_actor_dev, void* stream);
+/* The step as its phases: phases[i] is the i-th exorl_agent_update_phase id and exchanges[i] the sum all-reduce over the ranks that must
+ * follow it before the next phase, or -1. Exchanges are named only for world_size > 1. Needs no device. Writes *n (<= 5) entries; fails,
+ * writing nothing, when capacity is smaller. */
+#define EXORL_AGENT_XCHG_CRITIC_GRAD 0   /* exorl_agent_flat(EXORL_NET_CRITIC, EXORL_T_GRAD) */
+#define EXORL_AGENT_XCHG_STATS       1   /* exorl_agent_stats_buffer */
+#define EXORL_AGENT_XCHG_ACTOR_GRAD  2   /* exorl_agent_flat(EXORL_NET_ACTOR, EXORL_T_GRAD) */
+int exorl_agent_update_plan(const exorl_agent_cfg* cfg, int32_t* phases, int32_t* exchanges, int32_t capacity, int32_t* n);
 int exorl_agent_stats_buffer(exorl_agent_t* a, void** ptr_dev, int64_t* numel);
 /* Attach a communicator of cfg.world_size ranks (NULL detaches): exorl_agent_update then runs the four phases AND the all-reduces
  * between them on `stream` — no host round trip inside a step. The 16-byte statistic is reduced on a second stream while the critic's

@@ -5,6 +5,7 @@ must leave every line equal). Run it from each tree in a fresh process per listi
     python tools/agent_digests.py part2 OUT.txt PICKLE_DIR     loads those pickles (written by either tree), one more update()
     python tools/agent_digests.py part3 OUT.txt                the five two-process gloo workers of tests/, every array and json they save
     python tools/agent_digests.py grid OUT.txt                 one update() of every case of the state agents' kernel dispatch grids, per route
+    python tools/agent_digests.py modes OUT.txt                one state-agent handle through every driver of its step in turn (see modes)
     python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
 
 A listing has one line per entry, `case what value`; a value is the first 32 hex digits of a sha256 or a float.hex(). Inputs come from
@@ -328,6 +329,47 @@ def grid(out):
     listing(out, body)
 
 
+def modes(out):
+    """TD3+BC and CQL, one handle each per precision and metrics setting, driven in turn by a captured graph step, disable_graph, the four
+    phased calls, an eager update() and a newly captured graph step, with the digests after every driver: what one driver sets up for its
+    own launches (fused optimiser and scalar-head kernels, staged inputs, capture) must not reach the next one's. Uses only calls that
+    trees from before exorl_agent_update_plan have, so the same file runs against either library."""
+    def body(emitter):
+        for kind in ('td3_bc', 'cql'):
+            for precision in ('fp32', 'bf16x3'):
+                for metrics in ('tb', 'no_tb', 'window'):
+                    name = f'modes/{kind}/{precision}/{metrics}'
+                    emit = emitter(name)
+                    ag = build(kind, 'states', False, precision, metrics == 'tb')
+                    if metrics == 'window':
+                        assert ag.enable_metric_window()
+                    it = arena(kind, 'states')
+                    stddev = 1.0 if kind == 'cql' else ag._stddev(0)
+
+                    def after(tag):
+                        emit(f'{tag}.metrics_raw', sha(ag.engine.metrics_raw()))
+                        digest(ag, lambda what, value: emit(f'{tag}.{what}', value))
+                    assert ag.enable_graph(it)
+                    emit_metrics(emit, 'graph0', ag.update(it, 0))
+                    after('graph0')
+                    ag.disable_graph()
+                    ag._load_batch(it)
+                    for phase in range(4):
+                        ag.engine.update_phase(phase, stddev)
+                    after('phased')
+                    emit_metrics(emit, 'eager', ag.update(it, 2))
+                    after('eager')
+                    assert ag.enable_graph(it)
+                    emit_metrics(emit, 'graph1', ag.update(it, 3))
+                    after('graph1')
+                    if metrics == 'window':
+                        sums, steps = ag.engine.metric_window_read(reset=False)
+                        emit('window.sums', sha(sums)), emit('window.steps', str(steps))
+                    ag.disable_graph()
+                    print(name, flush=True)
+    listing(out, body)
+
+
 def compare(a, b):
     la, lb = Path(a).read_text().splitlines(), Path(b).read_text().splitlines()
     key = lambda l: l.rsplit(' ', 1)[0]
@@ -342,4 +384,4 @@ def compare(a, b):
 
 if __name__ == '__main__':
     cmd, args = sys.argv[1], sys.argv[2:]
-    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'compare': compare}[cmd](*args))
+    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'compare': compare}[cmd](*args))
