@@ -138,6 +138,8 @@ PROTOTYPES = {
     'exorl_replay_set_order': (C.c_int, [c_void_p, c_void_p, c_int32]),
     'exorl_replay_set_weights': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32]),
     'exorl_replay_set_frame_stack': (C.c_int, [c_void_p, c_int32]),
+    'exorl_replay_obs_moments': (C.c_int, [c_void_p, c_int32, P(c_int64), c_void_p, c_void_p, c_void_p]),
+    'exorl_replay_set_obs_norm': (C.c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_replay_num_rows': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_replay_seed_mt': (C.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
     'exorl_replay_seed_mt_ints': (C.c_int, [c_void_p, c_uint64, c_uint32]),

@@ -396,8 +396,31 @@ class _AgentBase:
     def _module_metrics(self, metrics):
         pass
 
+    # -- observation normalisation: the HBM sampler normalises what update() trains on, act() what the environment hands it
+    obs_norm_mean = obs_norm_inv = None          # plain host arrays once set: they ride in __getstate__'s attrs
+
+    def set_obs_normalizer(self, mean32, inv32):
+        """act() from now on feeds the policy utils.normalize_obs(obs, mean32, inv32): the pair of a normalize_obs=True loader
+        (replay_iter.obs_normalizer), whose HBM gather applies the same formula to every sampled batch. States only; for the reward-free
+        agents the observation part, before meta is appended. update() on a plain iterator of 5-tuples (the H2D fallback) is NOT
+        normalised: normalisation lives in the HBM sampler, such batches are trained on as they come."""
+        if getattr(self, 'obs_type', 'states') == 'pixels':
+            raise ValueError('set_obs_normalizer: pixel agents are not normalised (the encoder does its own /255 - 0.5)')
+        m, w = (np.array(a, np.float32).reshape(-1) for a in (mean32, inv32))
+        O = self.obs_shape[0] if hasattr(self, 'obs_shape') else self.engine.obs_dim      # without the reward-free agents' meta columns
+        if m.size != O or w.size != O:
+            raise ValueError(f'set_obs_normalizer: {m.size} means and {w.size} scales for {O} observation columns')
+        self.obs_norm_mean, self.obs_norm_inv = m, w
+
+    def clear_obs_normalizer(self):
+        self.obs_norm_mean = self.obs_norm_inv = None
+
+    def _norm_obs(self, obs):
+        obs = np.asarray(obs, np.float32)
+        return obs if self.obs_norm_mean is None else utils.normalize_obs(obs.reshape(-1), self.obs_norm_mean, self.obs_norm_inv)
+
     def act(self, obs, step, eval_mode):
-        return self._act(np.asarray(obs, np.float32), step, eval_mode)
+        return self._act(self._norm_obs(obs), step, eval_mode)
 
     def update(self, replay_iter, step):
         stddev = self._stddev(step)
@@ -687,7 +710,7 @@ class DDPGAgent(_AgentBase):
             if not eval_mode and step < self.num_expl_steps:
                 a.uniform_(-1.0, 1.0)
             return a.cpu().numpy()
-        parts = [np.asarray(obs, np.float32).reshape(-1)] + [np.asarray(v, np.float32).reshape(-1) for v in meta.values()]
+        parts = [self._norm_obs(obs).reshape(-1)] + [np.asarray(v, np.float32).reshape(-1) for v in meta.values()]
         return self._act(np.concatenate(parts), step, eval_mode)
 
     def update(self, replay_iter, step):

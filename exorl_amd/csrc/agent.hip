@@ -405,6 +405,7 @@ struct exorl_agent {
     hipStream_t capture_stream = nullptr;
     exorl_replay* graph_replay = nullptr;
     uint64_t graph_weights_epoch = 0;        // the replay's exorl_replay_set_weights count at capture: the graph samples that table
+    bool graph_norm_on = false;              // the replay's normaliser at capture, on or off: the graph holds the normalising or the copying gather
     uint64_t graph_replay_ctr = 0;           // host mirror of state->replay_counter: eager samples drawn between two launches move the replay's own
     exorl_intr* graph_intr = nullptr;        // joint graph (exorl_agent_enable_graph_intr): the module whose step rides in front of the agent's
     ForkStreams fk{};            // parallel-branch plumbing (a captured step forks when parallel_branches is set)
@@ -1331,6 +1332,7 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     EXORL_CHECK_HIP(hipGraphInstantiate(&a->graph_exec, g, nullptr, nullptr, 0));
     a->graph_replay = r;
     a->graph_weights_epoch = replay_weights_epoch(r);
+    a->graph_norm_on = replay_norm_on(r);
     a->graph_replay_ctr = ctr;
     a->graph_intr = it;
     return 0;
@@ -1345,6 +1347,8 @@ int exorl_agent_enable_graph_intr(exorl_agent_t* a, exorl_intr_t* intr, const ex
     EXORL_REQUIRE(a, "agent_enable_graph_intr: null argument");
     EXORL_REQUIRE(meta_dim >= 0 && meta_dim < a->cfg.obs_dim, "agent_enable_graph_intr: meta_dim=%d out of range", meta_dim);
     EXORL_REQUIRE(!intr || a->cfg.world_size == 1, "agent_enable_graph_intr: the joint graph is the one-process step");
+    EXORL_REQUIRE(!r || !replay_norm_on(r), "agent_enable_graph_intr: the arena has an observation normaliser (exorl_replay_set_obs_norm): the "
+                  "reward-free [obs | meta] step trains on raw observations; turn it off (n_cols = 0) first");
     return enable_graph_impl(a, intr, batch, meta_dim, r, nstep, gamma, stddev, stream);
 }
 
@@ -1464,6 +1468,9 @@ int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
     }
     EXORL_REQUIRE(replay_weights_epoch(a->graph_replay) == a->graph_weights_epoch, "agent_step_graph: exorl_replay_set_weights was called after "
                   "the capture: the graph samples the table it was captured with (call exorl_agent_enable_graph again)");
+    EXORL_REQUIRE(replay_norm_on(a->graph_replay) == a->graph_norm_on, "agent_step_graph: exorl_replay_set_obs_norm switched the "
+                  "normaliser %s after the capture: the graph holds the other gather kernel (call exorl_agent_enable_graph again)",
+                  a->graph_norm_on ? "off" : "on");
     const uint64_t ctr = replay_philox_counter(a->graph_replay);
     if (ctr != a->graph_replay_ctr) EXORL_TRY(set_device_u64(&a->state->replay_counter, ctr, as_stream(stream)));      // eager batches were drawn in between
     a->graph_replay_ctr = ctr + 1;

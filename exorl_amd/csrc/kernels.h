@@ -539,6 +539,7 @@ int comm_nranks(const exorl_comm* c);
 
 uint64_t replay_philox_counter(exorl_replay* r);
 uint64_t replay_weights_epoch(exorl_replay* r);      // number of exorl_replay_set_weights calls: a captured graph is bound to one value
+bool replay_norm_on(exorl_replay* r);                // exorl_replay_set_obs_norm: the normalising gather is launched; a captured graph holds one of the two
 // what a sample call does before its launch, without drawing: episode table upload, pair buffer, nstep vs the shortest episode
 int replay_prepare(exorl_replay* r, int32_t batch, int32_t nstep, hipStream_t s);
 void replay_advance_philox(exorl_replay* r, uint64_t n);

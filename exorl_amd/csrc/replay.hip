@@ -22,6 +22,11 @@
 // frame) and a sampled observation is k of them, oldest first: the stack at step t is rows max(t - k + 1, 0) .. t of the episode, what the
 // wrapper's deque(maxlen=k), filled with the reset frame, held (utils/env_constructor.py:144-188). gather_frames_kernel gives one wave to
 // each of the 2 k frames of a sample; gather_nstep_kernel, its arguments and its launch are those of an arena without stacking.
+//
+// Observation normalisation (fp32 state arenas): exorl_replay_obs_moments reduces the resident rows to fp64 column moments in two launches
+// (obs_moments_partial_kernel: Welford per thread, Chan between threads, one partial per workgroup in a slab; obs_moments_combine_kernel: the
+// slab in slab order), and exorl_replay_set_obs_norm makes gather_nstep_kernel<true> write y = (x - mean[j]) * inv_scale[j] wherever the plain
+// instantiation copies an observation element, the staged network inputs included.
 #include <algorithm>
 #include <vector>
 
@@ -135,6 +140,15 @@ struct exorl_replay {
     int32_t guide_cap = 0, guide_bits = 0;
     uint64_t weights_epoch = 0;       // counts exorl_replay_set_weights calls (a captured step graph refuses to replay across one)
     int32_t frames = 1;               // frames per sampled observation (exorl_replay_set_frame_stack); 1: a row is the whole observation
+    // observation normaliser: mean[obs_bytes / 4] then inv_scale[obs_bytes / 4], allocated at create (its address is stable across graph replays)
+    float* d_norm = nullptr;
+    std::vector<float> h_norm;
+    bool norm_on = false;             // which gather_nstep_kernel is launched (a captured step graph holds the kernel of its capture)
+    // exorl_replay_obs_moments' scratch, allocated on first use: the item prefix per episode and the slab of workgroup partials + the result
+    int32_t* d_item0 = nullptr;
+    double* d_slab = nullptr;
+    std::vector<int32_t> h_item0;
+    std::vector<double> h_moments;
 };
 
 namespace exorl {
@@ -148,6 +162,7 @@ struct ReplayView {
     const uint64_t* cum;      // null: unweighted; else n_episodes + 1 prefix sums of the episode masses, cum[n_episodes] the total
     const int32_t* guide;     // (1 << guide_bits) + 1 cut points into cum, indexed by the top guide_bits bits of the draw
     int32_t guide_bits;
+    const float *norm_mean, *norm_inv;      // null: observations are copied; else obs_bytes / 4 floats each, y = (x - mean[j]) * inv[j]
 };
 
 __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
@@ -160,6 +175,28 @@ __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ src, 
         const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
         uint32_t* d = reinterpret_cast<uint32_t*>(dst);
         for (int i = lane; i < bytes / 4; i += 64) d[i] = s[i];
+    }
+}
+
+// copy_row of an fp32 row through the normaliser: two roundings per element, the subtraction then the product.
+__device__ __forceinline__ void norm_row(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int bytes, int lane, bool vec16,
+                                         const float* __restrict__ mean, const float* __restrict__ inv) {
+#pragma clang fp contract(off)
+    if (vec16) {
+        const float4* s = reinterpret_cast<const float4*>(src);
+        const float4* m = reinterpret_cast<const float4*>(mean);
+        const float4* w = reinterpret_cast<const float4*>(inv);
+        float4* d = reinterpret_cast<float4*>(dst);
+        for (int i = lane; i < bytes / 16; i += 64) {
+            const float4 x = s[i], mu = m[i], sc = w[i];
+            float4 y;
+            y.x = (x.x - mu.x) * sc.x; y.y = (x.y - mu.y) * sc.y; y.z = (x.z - mu.z) * sc.z; y.w = (x.w - mu.w) * sc.w;
+            d[i] = y;
+        }
+    } else {
+        const float* s = reinterpret_cast<const float*>(src);
+        float* d = reinterpret_cast<float*>(dst);
+        for (int i = lane; i < bytes / 4; i += 64) d[i] = (s[i] - mean[i]) * inv[i];
     }
 }
 
@@ -192,6 +229,8 @@ __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pa
     }
 }
 
+// NORM = false is the copying gather; NORM = true (exorl_replay_set_obs_norm) differs only where an observation element is written.
+template <bool NORM>
 __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const int32_t* pairs_in,
                                                            int32_t* pairs_out, exorl_batch_out out,
                                                            int batch, int nstep, float gamma, int sampler,
@@ -206,10 +245,17 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
     int pos, idx;
     draw_pair(v, pairs_in, pairs_out, b, nstep, sampler, seed, counter, lane, true, pos, idx);
     const int64_t row = v.row0[pos] + idx;
-    copy_row(v.obs + (row - 1) * v.obs_bytes, static_cast<unsigned char*>(out.obs) + (int64_t)b * out.obs_stride,
-             v.obs_bytes, lane, vec16);
-    copy_row(v.obs + (row + nstep - 1) * v.obs_bytes,
-             static_cast<unsigned char*>(out.next_obs) + (int64_t)b * out.next_obs_stride, v.obs_bytes, lane, vec16);
+    if constexpr (NORM) {
+        norm_row(v.obs + (row - 1) * v.obs_bytes, static_cast<unsigned char*>(out.obs) + (int64_t)b * out.obs_stride,
+                 v.obs_bytes, lane, vec16, v.norm_mean, v.norm_inv);
+        norm_row(v.obs + (row + nstep - 1) * v.obs_bytes,
+                 static_cast<unsigned char*>(out.next_obs) + (int64_t)b * out.next_obs_stride, v.obs_bytes, lane, vec16, v.norm_mean, v.norm_inv);
+    } else {
+        copy_row(v.obs + (row - 1) * v.obs_bytes, static_cast<unsigned char*>(out.obs) + (int64_t)b * out.obs_stride,
+                 v.obs_bytes, lane, vec16);
+        copy_row(v.obs + (row + nstep - 1) * v.obs_bytes,
+                 static_cast<unsigned char*>(out.next_obs) + (int64_t)b * out.next_obs_stride, v.obs_bytes, lane, vec16);
+    }
     for (int j = lane; j < v.act_dim; j += 64) out.action[(int64_t)b * out.action_stride + j] = v.act[row * v.act_dim + j];
     if (out.meta)
         for (int j = lane; j < v.meta_dim; j += 64)
@@ -219,7 +265,12 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         const float* so = reinterpret_cast<const float*>(v.obs + (row - 1) * v.obs_bytes);
         const float* sn = reinterpret_cast<const float*>(v.obs + (row + nstep - 1) * v.obs_bytes);
         for (int j = lane; j < O; j += 64) {
-            const float o = so[j], no = sn[j];
+            float o = so[j], no = sn[j];
+            if constexpr (NORM) {
+                const float mu = v.norm_mean[j], sc = v.norm_inv[j];
+                o = (o - mu) * sc;
+                no = (no - mu) * sc;
+            }
             stage.xa[(int64_t)b * O + j] = no;
             stage.xa[(int64_t)(stage.B + b) * O + j] = o;
             if (stage.has_critic) {
@@ -298,6 +349,117 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const 
         }
         out.reward[b] = R;
         out.discount[b] = D;
+    }
+}
+
+// ---- column moments of the resident observations (exorl_replay_obs_moments) -----------------------------------------------------------
+// (count, mean, M2 = sum (x - mean)^2) of one column over some rows, in fp64. A value is added with Welford's update, two such triples are
+// merged with Chan's; neither forms sum x^2, so a column of mean 1000 and spread 0.01 keeps its M2, and a constant column keeps M2 == 0
+// exactly (every delta is 0).
+struct Moments {
+    double n, mean, m2;
+};
+
+__device__ __forceinline__ void moments_add(Moments& a, double x) {
+    a.n += 1.0;
+    const double d = x - a.mean;
+    a.mean += d / a.n;
+    a.m2 += d * (x - a.mean);
+}
+
+__device__ __forceinline__ Moments moments_merge(const Moments& a, const Moments& b) {
+    if (b.n == 0.0) return a;
+    if (a.n == 0.0) return b;
+    const double n = a.n + b.n, d = b.mean - a.mean;
+    return Moments{n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
+}
+
+constexpr int MOMENTS_CHUNK = 64;          // rows of one work item: an episode of `rows` rows is cdiv(rows, 64) items
+constexpr int MOMENTS_MAX_GROUPS = 1024;   // workgroups of the first launch = partials in the slab
+
+// Launch 1. Work item i is a run of <= 64 consecutive rows of one episode (item0[e] = the first item of the episode at table position e);
+// workgroup g owns items [g * items_per_group, (g + 1) * items_per_group), a fixed assignment. The 256 threads tile rows x columns: with
+// ct = min(n_cols, 256) columns per tile and rp = 256 / ct rows per pass, thread (tr, tc) keeps column cb + tc and walks rows tr, tr + rp, ...
+// of every item, so a pass reads rp whole rows, contiguous in the arena. Per column tile the rp threads of a column are merged through LDS
+// in a fixed tree and the workgroup stores one partial: slab = count[G] | mean[G][n_cols] | m2[G][n_cols].
+__global__ __launch_bounds__(256) void obs_moments_partial_kernel(const float* __restrict__ obs, const int64_t* __restrict__ row0,
+                                                                  const int32_t* __restrict__ len, const int32_t* __restrict__ item0,
+                                                                  int n_episodes, int n_cols, int items_per_group, int n_items,
+                                                                  double* __restrict__ slab) {
+    __shared__ double s_n[256], s_mean[256], s_m2[256];
+    const int g = blockIdx.x, G = gridDim.x, t = threadIdx.x;
+    const int ct = n_cols < 256 ? n_cols : 256, rp = 256 / ct;
+    const int tc = t % ct, tr = t / ct;
+    const int i0 = g * items_per_group, i1 = min(i0 + items_per_group, n_items);
+    int e0 = 0;                                   // the episode of item i0: item0[e0] <= i0 < item0[e0 + 1]
+    for (int hi = n_episodes; hi - e0 > 1;) {
+        const int mid = (e0 + hi) >> 1;
+        if (item0[mid] <= i0) e0 = mid; else hi = mid;
+    }
+    for (int cb = 0; cb < n_cols; cb += ct) {
+        const int j = cb + tc;
+        Moments acc{0.0, 0.0, 0.0};
+        if (tr < rp && j < n_cols) {
+            int e = e0;
+            for (int it = i0; it < i1; ++it) {
+                while (item0[e + 1] <= it) ++e;
+                const int r0 = (it - item0[e]) * MOMENTS_CHUNK;
+                const int nr = min(len[e] + 1 - r0, MOMENTS_CHUNK);
+                const float* x = obs + (row0[e] + r0) * (int64_t)n_cols + j;
+                int r = tr;
+                for (; r + 3 * rp < nr; r += 4 * rp) {          // four loads in flight ahead of the dependent updates
+                    const float a = x[(int64_t)r * n_cols], b = x[(int64_t)(r + rp) * n_cols], c = x[(int64_t)(r + 2 * rp) * n_cols],
+                                d = x[(int64_t)(r + 3 * rp) * n_cols];
+                    moments_add(acc, a); moments_add(acc, b); moments_add(acc, c); moments_add(acc, d);
+                }
+                for (; r < nr; r += rp) moments_add(acc, x[(int64_t)r * n_cols]);
+            }
+        }
+        s_n[t] = acc.n; s_mean[t] = acc.mean; s_m2[t] = acc.m2;
+        __syncthreads();
+        int half = 1;
+        while (half < rp) half <<= 1;
+        for (half >>= 1; half >= 1; half >>= 1) {               // row slots tr and tr + half of one column, the same pairs every run
+            if (tr < half && tr + half < rp) {
+                const int u = t + half * ct;
+                const Moments m = moments_merge(Moments{s_n[t], s_mean[t], s_m2[t]}, Moments{s_n[u], s_mean[u], s_m2[u]});
+                s_n[t] = m.n; s_mean[t] = m.mean; s_m2[t] = m.m2;
+            }
+            __syncthreads();
+        }
+        if (tr == 0 && j < n_cols) {
+            if (j == 0) slab[g] = s_n[t];
+            slab[G + (int64_t)g * n_cols + j] = s_mean[t];
+            slab[G + (int64_t)G * n_cols + (int64_t)g * n_cols + j] = s_m2[t];
+        }
+        __syncthreads();
+    }
+}
+
+// Launch 2. One wave per column, four columns per workgroup: lane l merges its run of cdiv(G, 64) consecutive partials in slab order, then
+// neighbouring runs are merged pairwise through LDS, the earlier run on the left: the slab in slab order, as a fixed tree.
+// result = count | mean[n_cols] | m2[n_cols].
+__global__ __launch_bounds__(256) void obs_moments_combine_kernel(const double* __restrict__ slab, int G, int n_cols, double* __restrict__ result) {
+    __shared__ double s_n[256], s_mean[256], s_m2[256];
+    const int t = threadIdx.x, lane = t & 63, j = blockIdx.x * 4 + (t >> 6);
+    const int run = (G + 63) / 64;
+    Moments acc{0.0, 0.0, 0.0};
+    if (j < n_cols)
+        for (int g = lane * run; g < min((lane + 1) * run, G); ++g)
+            acc = moments_merge(acc, Moments{slab[g], slab[G + (int64_t)g * n_cols + j], slab[G + (int64_t)G * n_cols + (int64_t)g * n_cols + j]});
+    s_n[t] = acc.n; s_mean[t] = acc.mean; s_m2[t] = acc.m2;
+    __syncthreads();
+    for (int step = 1; step < 64; step <<= 1) {
+        if (lane % (2 * step) == 0) {
+            const Moments m = moments_merge(Moments{s_n[t], s_mean[t], s_m2[t]}, Moments{s_n[t + step], s_mean[t + step], s_m2[t + step]});
+            s_n[t] = m.n; s_mean[t] = m.mean; s_m2[t] = m.m2;
+        }
+        __syncthreads();
+    }
+    if (lane == 0 && j < n_cols) {
+        if (j == 0) result[0] = s_n[t];
+        result[1 + j] = s_mean[t];
+        result[1 + n_cols + j] = s_m2[t];
     }
 }
 
@@ -425,6 +587,7 @@ int exorl_replay_create(const exorl_replay_cfg* cfg, exorl_replay_t** out) {
     r->guide_cap = 2;
     while (r->guide_cap < 2 * (int64_t)cfg->max_episodes && r->guide_cap < (1 << 28)) r->guide_cap <<= 1;
     EXORL_CHECK_HIP(hipMalloc((void**)&r->d_guide, ((size_t)r->guide_cap + 1) * sizeof(int32_t)));
+    EXORL_CHECK_HIP(hipMalloc((void**)&r->d_norm, 2 * (size_t)(cfg->obs_bytes / 4) * sizeof(float)));
     *out = r;
     return 0;
 }
@@ -435,6 +598,9 @@ int exorl_replay_destroy(exorl_replay_t* r) {
     if (r->meta) (void)hipFree(r->meta);
     (void)hipFree(r->d_row0); (void)hipFree(r->d_len); (void)hipFree(r->d_cum); (void)hipFree(r->d_guide);
     if (r->d_pairs) (void)hipFree(r->d_pairs);
+    (void)hipFree(r->d_norm);
+    if (r->d_item0) (void)hipFree(r->d_item0);
+    if (r->d_slab) (void)hipFree(r->d_slab);
     delete r;
     return 0;
 }
@@ -514,7 +680,69 @@ int exorl_replay_set_frame_stack(exorl_replay_t* r, int32_t frames) {
                   "cannot be re-read as single frames", (int)r->slots.size());
     EXORL_REQUIRE((int64_t)frames * r->cfg.obs_bytes <= INT32_MAX, "replay_set_frame_stack: %d frames of %d bytes overflow an observation's "
                   "32-bit size", frames, r->cfg.obs_bytes);
+    EXORL_REQUIRE(frames == 1 || !r->norm_on, "replay_set_frame_stack: the arena has an observation normaliser (exorl_replay_set_obs_norm), which "
+                  "reads a row as one fp32 observation");
     r->frames = frames;
+    return 0;
+}
+
+int exorl_replay_obs_moments(exorl_replay_t* r, int32_t n_cols, int64_t* count_host, double* mean_host, double* m2_host, void* stream) {
+    EXORL_REQUIRE(r && count_host && mean_host && m2_host, "replay_obs_moments: null argument");
+    EXORL_REQUIRE(r->frames == 1, "replay_obs_moments: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): column moments "
+                  "are defined for fp32 state rows", r->frames);
+    EXORL_REQUIRE(n_cols > 0 && (int64_t)n_cols * 4 == r->cfg.obs_bytes, "replay_obs_moments: n_cols=%d fp32 columns do not fill a row of %d bytes",
+                  n_cols, r->cfg.obs_bytes);
+    EXORL_REQUIRE(!r->order.empty(), "replay_obs_moments: no resident episode in the order table");
+    hipStream_t s = as_stream(stream);
+    const int n = (int)r->order.size();
+    r->h_item0.resize((size_t)n + 1);
+    int64_t items = 0, rows = 0;
+    for (int i = 0; i < n; ++i) {
+        r->h_item0[i] = (int32_t)items;
+        items += cdiv(r->slots[r->order[i]].rows, MOMENTS_CHUNK);
+        rows += r->slots[r->order[i]].rows;
+        EXORL_REQUIRE(items < INT32_MAX, "replay_obs_moments: more than 2^31 work items of %d rows", MOMENTS_CHUNK);
+    }
+    r->h_item0[n] = (int32_t)items;
+    const size_t res = 1 + 2 * (size_t)n_cols, slab = MOMENTS_MAX_GROUPS * res;
+    if (!r->d_item0) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_item0, ((size_t)r->cfg.max_episodes + 1) * sizeof(int32_t)));
+    if (!r->d_slab) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_slab, (slab + res) * sizeof(double)));
+    EXORL_TRY(upload_table(r, 0, s));
+    EXORL_CHECK_HIP(hipMemcpyAsync(r->d_item0, r->h_item0.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    const int per = (int)cdiv(items, (int64_t)MOMENTS_MAX_GROUPS), G = (int)cdiv(items, (int64_t)per);      // no workgroup without an item
+    hipLaunchKernelGGL(obs_moments_partial_kernel, dim3(G), dim3(256), 0, s, reinterpret_cast<const float*>(r->obs), r->d_row0, r->d_len,
+                       r->d_item0, n, n_cols, per, (int)items, r->d_slab);
+    EXORL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(obs_moments_combine_kernel, dim3(cdiv(n_cols, 4)), dim3(256), 0, s, r->d_slab, G, n_cols, r->d_slab + slab);
+    EXORL_LAUNCH_CHECK();
+    r->h_moments.resize(res);
+    EXORL_CHECK_HIP(hipMemcpyAsync(r->h_moments.data(), r->d_slab + slab, res * sizeof(double), hipMemcpyDeviceToHost, s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    EXORL_REQUIRE((int64_t)r->h_moments[0] == rows, "replay_obs_moments: the kernels counted %lld rows, the table holds %lld",
+                  (long long)r->h_moments[0], (long long)rows);
+    *count_host = rows;
+    memcpy(mean_host, r->h_moments.data() + 1, (size_t)n_cols * sizeof(double));
+    memcpy(m2_host, r->h_moments.data() + 1 + n_cols, (size_t)n_cols * sizeof(double));
+    return 0;
+}
+
+int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* mean_host, const float* inv_scale_host, void* stream) {
+    EXORL_REQUIRE(r, "replay_set_obs_norm: null handle");
+    if (n_cols == 0) {
+        r->norm_on = false;
+        return 0;
+    }
+    EXORL_REQUIRE(mean_host && inv_scale_host, "replay_set_obs_norm: null argument");
+    EXORL_REQUIRE(r->frames == 1, "replay_set_obs_norm: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): only fp32 "
+                  "state rows are normalised", r->frames);
+    EXORL_REQUIRE(n_cols > 0 && (int64_t)n_cols * 4 == r->cfg.obs_bytes, "replay_set_obs_norm: n_cols=%d fp32 columns do not fill a row of %d bytes",
+                  n_cols, r->cfg.obs_bytes);
+    r->h_norm.resize(2 * (size_t)n_cols);
+    memcpy(r->h_norm.data(), mean_host, (size_t)n_cols * sizeof(float));
+    memcpy(r->h_norm.data() + n_cols, inv_scale_host, (size_t)n_cols * sizeof(float));
+    // a pageable source: the runtime stages it before returning, so the vector may be rewritten by the next call
+    EXORL_CHECK_HIP(hipMemcpyAsync(r->d_norm, r->h_norm.data(), r->h_norm.size() * sizeof(float), hipMemcpyHostToDevice, as_stream(stream)));
+    r->norm_on = true;
     return 0;
 }
 
@@ -627,15 +855,17 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
         return 2;
     }
     ReplayView v{r->obs, r->act, r->rew, r->disc, r->meta, r->d_row0, r->d_len, r->cfg.obs_bytes, r->cfg.act_dim, r->cfg.meta_dim, n,
-                 r->weighted && sampler == EXORL_SAMPLER_PHILOX ? r->d_cum : nullptr, r->d_guide, r->guide_bits};
+                 r->weighted && sampler == EXORL_SAMPLER_PHILOX ? r->d_cum : nullptr, r->d_guide, r->guide_bits,
+                 r->norm_on ? r->d_norm : nullptr, r->norm_on ? r->d_norm + r->cfg.obs_bytes / 4 : nullptr};
     if (r->frames > 1) {
         hipLaunchKernelGGL(gather_frames_kernel, dim3(cdiv(2 * r->frames * batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch,
                            nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, r->frames);
     } else {
         const int vec16 = (r->cfg.obs_bytes % 16 == 0) && (out->obs_stride % 16 == 0) && (out->next_obs_stride % 16 == 0) &&
                           ((uintptr_t)out->obs % 16 == 0) && ((uintptr_t)out->next_obs % 16 == 0);
-        hipLaunchKernelGGL(gather_nstep_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch, nstep,
-                           gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16, stage ? *stage : StageOut{});
+        hipLaunchKernelGGL(r->norm_on ? gather_nstep_kernel<true> : gather_nstep_kernel<false>, dim3(cdiv(batch, 4)), dim3(256), 0, s, v,
+                           r->d_pairs, r->d_pairs, *out, batch, nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16,
+                           stage ? *stage : StageOut{});
     }
     EXORL_LAUNCH_CHECK();
     if (sampler == EXORL_SAMPLER_PHILOX) r->philox_counter += 1;
@@ -644,6 +874,7 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
 
 uint64_t replay_philox_counter(exorl_replay* r) { return r->philox_counter; }
 uint64_t replay_weights_epoch(exorl_replay* r) { return r->weights_epoch; }
+bool replay_norm_on(exorl_replay* r) { return r->norm_on; }
 int replay_obs_bytes(exorl_replay* r) { return r->frames * r->cfg.obs_bytes; }      // of one SAMPLED observation
 int replay_frame_stack(exorl_replay* r) { return r->frames; }
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }

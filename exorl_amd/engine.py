@@ -803,6 +803,37 @@ class ReplayEngine:
         q = None if weights is None else np.ascontiguousarray(quantise_weights(weights))
         L.check(self.lib.exorl_replay_set_weights(self.h, WEIGHTING[weighting], L.ptr(q), 0 if q is None else len(q)))
 
+    def _state_cols(self, what):
+        if self.obs_dtype != np.float32:
+            raise ValueError(f'{what}: the arena holds {self.obs_dtype} observations; only float32 state arenas are normalised (the pixel '
+                             'encoder does its own /255 - 0.5)')
+        return self.obs_bytes // 4
+
+    def obs_moments(self):
+        """(count, mean, M2) of the float32 observation columns over every row (len + 1 per episode, the reset row included) of the
+        episodes in the order table: count an int, mean and M2 = sum (x - mean)^2 float64 arrays of obs_shape. One pass over the arena in
+        HBM, bitwise reproducible (exorl_replay_obs_moments). A set-up call: it synchronises the current stream."""
+        n = self._state_cols('obs_moments')
+        cnt, mean, m2 = C.c_int64(), np.zeros(n, np.float64), np.zeros(n, np.float64)
+        L.check(self.lib.exorl_replay_obs_moments(self.h, n, C.byref(cnt), mean.ctypes.data, m2.ctypes.data, L.current_stream()))
+        return cnt.value, mean.reshape(self.obs_shape), m2.reshape(self.obs_shape)
+
+    def set_obs_normalizer(self, mean32, inv32):
+        """Every obs / next_obs element sampled from now on is (x - mean32[j]) * inv32[j] (utils.normalize_obs), in the captured step's
+        staged gather too; action, reward, discount and meta are untouched. Calling it again replaces the values in place: a captured
+        graph uses them from its next step. Switching the normaliser on or off changes the captured kernel: call enable_graph again (a
+        graph step across the switch raises ExorlError)."""
+        n = self._state_cols('set_obs_normalizer')
+        m, w = (np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1)) for a in (mean32, inv32))
+        if m.size != n or w.size != n:
+            raise ValueError(f'set_obs_normalizer: {m.size} means and {w.size} scales for {n} observation columns')
+        L.check(self.lib.exorl_replay_set_obs_norm(self.h, n, m.ctypes.data, w.ctypes.data, L.current_stream()))
+
+    def clear_obs_normalizer(self):
+        """Back to the copying gather: samples are the arena's raw rows again."""
+        self._state_cols('clear_obs_normalizer')
+        L.check(self.lib.exorl_replay_set_obs_norm(self.h, 0, None, None, L.current_stream()))
+
     def seed_mt_from_globals(self):
         """Adopts the CURRENT state of Python's `random` and NumPy's legacy global generator — the two
         streams replay_buffer.py:169,222 draw from — so the index stream continues exactly where the

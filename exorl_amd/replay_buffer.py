@@ -375,14 +375,30 @@ class DeviceReplayLoader:
     frame_stack=k (the run's cfg.frame_stack; None or 1: rows are stored as they come): the episodes on disk and from the storage are
     the frame-stack wrapper's (k * c0, H, W) observations; the arena keeps one (c0, H, W) frame per step, 1/k of the memory and of the
     upload, and the gather rebuilds the stacks: the batches are byte-identical. An episode that is not such a window raises ValueError
-    at ingest (unstack_frames)."""
+    at ingest (unstack_frames).
+
+    normalize_obs=True (offline loaders, float32 states): after the one-shot load the iterator takes the column moments of EVERY shard
+    arena it holds (ReplayEngine.obs_moments: all rows of all resident episodes, several mix directories in one arena included), exchanges
+    them between the ranks of an initialised torch.distributed (all_gather_object of a handful of doubles; `gather`, a callable
+    own partials -> [partials of rank 0, partials of rank 1, ...], replaces that exchange), merges them with utils.combine_moments, ranks in
+    rank order and each rank's shards in shard order, and sets utils.obs_normalizer(count, mean, M2, norm_eps) on all its arenas: every
+    sampled obs / next_obs is (x - mean) / (std + norm_eps) of the whole dataset, whatever the sampler. The iterator's .obs_normalizer is
+    the (mean32, inv32) pair to hand to agent.set_obs_normalizer, so that act() sees what update() trained on. It is in place before
+    .engine is handed to agent.enable_graph. A growing online buffer is refused: its statistic would move under the policy."""
 
     def __init__(self, storage, max_size, batch_size, num_workers, save_snapshot, nstep, discount, fetch_every=1000,
                  device='cuda', sampler='mt19937', seed=None, worker_ids=None, max_episodes=None, capacity_rows=None, static=False,
                  load_threads=None, offline=False, env=None, relabel=False, weighting=None, episode_weight=None, mix=None,
-                 frame_stack=None):
+                 frame_stack=None, normalize_obs=False, norm_eps=1e-3, gather=None):
         if frame_stack is not None and not 1 <= int(frame_stack) <= 16:
             raise ValueError(f'frame_stack={frame_stack}: expected 1 .. 16')
+        if normalize_obs and not offline:
+            raise ValueError('normalize_obs=True needs an offline loader (make_offline_replay_loader): the statistic of a growing online '
+                             'buffer would move under the policy')
+        if normalize_obs and frame_stack is not None and int(frame_stack) > 1:
+            raise ValueError(f'normalize_obs=True with frame_stack={frame_stack}: only float32 state observations are normalised (the pixel '
+                             'encoder does its own /255 - 0.5)')
+        self.normalize_obs, self.norm_eps, self.gather = bool(normalize_obs), float(norm_eps), gather
         self.frame_stack = None if frame_stack is None else int(frame_stack)
         self.weighting, self.episode_weight, self.mix = _weighting_args(sampler, weighting, episode_weight, mix), episode_weight, mix
         self.storage = storage
@@ -417,6 +433,43 @@ class DeviceReplayIterator:
         self._seeded = False
         # what agent.enable_graph reads; .engine is only set for a static single-shard dataset (see static_engine)
         self.sampler, self.nstep, self.discount, self.batch_size = loader.sampler, loader.nstep, loader.discount, loader.batch_size
+        self._normalizer = None
+
+    def _load_shard(self, shard):
+        """The scan that the shard's first sample would trigger, and its index streams."""
+        if shard.engine is None:
+            shard.try_fetch()
+            if shard.engine is None:
+                raise IndexError('replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)')
+        if not shard.seeded:
+            self._seed(shard)
+
+    @property
+    def obs_normalizer(self):
+        """(mean32, inv32) of a normalize_obs=True loader, for agent.set_obs_normalizer; None otherwise. The first look loads every shard,
+        takes and exchanges the moments and sets the normaliser on all the shard arenas (DeviceReplayLoader)."""
+        return self._ensure_normalizer()
+
+    def _ensure_normalizer(self):
+        ld = self.loader
+        if not getattr(ld, 'normalize_obs', False) or self._normalizer is not None:
+            return self._normalizer
+        from .utils import combine_moments, obs_normalizer
+        for shard in self.shards:
+            self._load_shard(shard)
+        own = [shard.engine.obs_moments() for shard in self.shards]
+        gather = ld.gather
+        if gather is None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            def gather(parts):
+                out = [None] * torch.distributed.get_world_size()
+                torch.distributed.all_gather_object(out, parts)
+                return out
+        ranks = [own] if gather is None else gather(own)
+        count, mean, m2 = combine_moments([part for parts in ranks for part in parts])
+        self._normalizer = obs_normalizer(count, mean, m2, ld.norm_eps)
+        for shard in self.shards:
+            shard.engine.set_obs_normalizer(*self._normalizer)
+        return self._normalizer
 
     @property
     def engine(self):
@@ -431,6 +484,7 @@ class DeviceReplayIterator:
             if shard.engine is None:
                 raise IndexError('replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)')
             self._seed(shard)
+        self._ensure_normalizer()           # normalize_obs: in place before the arena is captured
         shard.since_fetch = -(1 << 62)      # the captured graph samples without passing through the fetch counter
         return shard.engine
 
@@ -468,6 +522,7 @@ class DeviceReplayIterator:
         """Zero-copy path: writes the next minibatch straight into caller-owned device memory (exorl_batch_out)."""
         ld = self.loader
         batch = batch or ld.batch_size
+        self._ensure_normalizer()           # normalize_obs: set on every shard before the first sample
         shard = self.shards[self.turn % len(self.shards)]
         self.turn += 1
         for start, n in self._segments(shard, batch):
@@ -483,6 +538,7 @@ class DeviceReplayIterator:
     def __next__(self):
         ld = self.loader
         B = ld.batch_size
+        self._ensure_normalizer()
         shard = self.shards[self.turn % len(self.shards)]
         if shard.engine is None:                              # first batch: the scan that sample 0 would trigger
             shard.try_fetch()

@@ -13,7 +13,7 @@ from .replay_buffer import make_replay_loader
 
 def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, replay_buffer_size=10**7, eval_every_steps=10000,
                   log_every_steps=1000, eval_fn=None, log_fn=None, env=None, sampler='philox', use_graph=True, start_step=0,
-                  metric_window=False, mix=None, weighting=None):
+                  metric_window=False, mix=None, weighting=None, normalize_obs=False):
     """train_offline.py:90-123. Returns the list of (step, metrics) rows that were logged.
 
     eval_fn(step, agent): called every eval_every_steps (train_offline.py:108-112).
@@ -23,10 +23,17 @@ def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, repla
     carries agent.pop_metrics(): the means over the steps since the previous row, which is what the reference's averaging meters write.
     An agent without the window (enable_metric_window() returns False) logs its per-step metrics as before.
     replay_dir may be a list of directories with mix=[fraction per directory]; weighting='episodes'|'transitions' selects the weighted
-    sampler (make_offline_replay_loader; both need sampler='philox'). The graph is captured after the weights are in place."""
+    sampler (make_offline_replay_loader; both need sampler='philox'). The graph is captured after the weights are in place.
+    normalize_obs=True: the TD3+BC authors' state normalisation. The loader z-scores every sampled observation with the dataset's own mean
+    and standard deviation in the HBM gather (DeviceReplayLoader) and the agent gets the same pair (agent.set_obs_normalizer) before the
+    capture, so eval_fn's agent.act() normalises the environment's observations the way update() saw the data."""
     extra = {k: v for k, v in (('mix', mix), ('weighting', weighting)) if v is not None}
+    if normalize_obs:
+        extra['normalize_obs'] = True
     loader = make_replay_loader(env, replay_dir, replay_buffer_size, batch_size, 0, discount, sampler=sampler, **extra)
     replay_iter = iter(loader)
+    if normalize_obs:
+        agent.set_obs_normalizer(*replay_iter.obs_normalizer)
     windowed = bool(metric_window) and hasattr(agent, 'enable_metric_window') and agent.enable_metric_window()      # before the capture
     if use_graph and hasattr(agent, 'enable_graph'):
         agent.enable_graph(replay_iter, start_step)      # False (and eager launches) when the pairing cannot be captured

@@ -91,6 +91,41 @@ def soft_update_params(net, target_net, tau):
         target_net._on_change()
 
 
+def combine_moments(parts):
+    """Merges column moments [(count, mean, M2), ...] (M2 = sum (x - mean)^2 per column) into one triple, in float64, with Chan's pairwise
+    update applied in list order; parts with count 0 are skipped. No sum of squares is formed, so columns whose mean dwarfs their spread
+    keep their M2, and parts that agree on a constant column keep M2 == 0 exactly. Returns (0, None, None) when every part is empty."""
+    n, mean, m2 = 0, None, None
+    for cnt, mu, s in parts:
+        cnt = int(cnt)
+        if cnt == 0:
+            continue
+        mu, s = np.asarray(mu, np.float64), np.asarray(s, np.float64)
+        if n == 0:
+            n, mean, m2 = cnt, mu.copy(), s.copy()
+            continue
+        tot = n + cnt
+        d = mu - mean
+        mean = mean + d * (cnt / tot)
+        m2 = m2 + s + d * d * (n * cnt / tot)
+        n = tot
+    return n, mean, m2
+
+
+def obs_normalizer(count, mean, m2, eps=1e-3):
+    """(mean32, inv32) of the TD3+BC authors' state normalisation (s - mean) / (std + eps), std = sqrt(M2 / count) the POPULATION standard
+    deviation (their states.std(0)). inv32 = float32(1 / (std + eps)) is computed in float64 and rounded once, mean32 = float32(mean). This is
+    the one definition of the normaliser: the HBM gather and act() multiply by inv32 (normalize_obs), which differs from a true division by
+    std + eps by at most the rounding of the reciprocal (a relative 2^-24 ahead of the product's own rounding)."""
+    std = np.sqrt(np.asarray(m2, np.float64) / float(count))
+    return np.asarray(mean, np.float64).astype(np.float32), (1.0 / (std + float(eps))).astype(np.float32)
+
+
+def normalize_obs(x, mean32, inv32):
+    """(x - mean32) * inv32 in float32, two rounded operations: the formula of the normalising gather and of act()."""
+    return (np.asarray(x).astype(np.float32) - np.asarray(mean32, np.float32)) * np.asarray(inv32, np.float32)
+
+
 class _StepGate:
     """Shared arithmetic of the training loops' step predicates (pretrain.py:209-215, train_offline.py:84-88): the configured frame count is
     converted to agent steps by integer division with `action_repeat`, at call time; a count of None switches the gate off."""

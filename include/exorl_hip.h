@@ -39,7 +39,7 @@ extern "C" {
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
                                         exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights,
-                                        exorl_replay_set_frame_stack, exorl_agent_update_plan) */
+                                        exorl_replay_set_frame_stack, exorl_agent_update_plan, exorl_replay_obs_moments, exorl_replay_set_obs_norm) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -105,6 +105,22 @@ int exorl_replay_set_weights(exorl_replay_t* r, int32_t mode, const uint32_t* q_
  * 1/k of the arena's observation bytes. exorl_replay_sample fails, launching nothing, unless out->obs_stride and out->next_obs_stride
  * are >= frames * obs_bytes. exorl_agent_enable_graph / _intr refuse such an arena (the captured step reads whole arena rows). */
 int exorl_replay_set_frame_stack(exorl_replay_t* r, int32_t frames);
+/* Column moments of the fp32 observations, in fp64: over ALL rows (len + 1 each, the reset row included: every observation the sampler can
+ * return as obs or next_obs) of the episodes in the current order table, *count_host = the number of rows, mean_host[j] the mean of column
+ * j and m2_host[j] = sum (x - mean_j)^2. Evicted slots and holes awaiting compaction are not read. Two launches: fixed ranges of
+ * (episode, 64-row chunk) items per workgroup, Welford per thread, Chan's pairwise update between threads and workgroups, one fp64
+ * partial per workgroup in a slab the replay owns; then the slab combined in slab order. No atomics: two calls on the same arena return
+ * the same bits, and a constant column returns m2 == 0. Fails, launching nothing, unless n_cols * 4 == obs_bytes, the arena is not
+ * frame-stacked and at least one episode is resident. A set-up call: it synchronises `stream`; never call it inside a capture. */
+int exorl_replay_obs_moments(exorl_replay_t* r, int32_t n_cols, int64_t* count_host, double* mean_host, double* m2_host, void* stream);
+/* Observation normaliser of the gather: with n_cols = obs_bytes / 4 values each in mean_host and inv_scale_host, every obs and next_obs
+ * element exorl_replay_sample (and the captured step's staged gather) writes is y = (x - mean[j]) * inv_scale[j], two fp32 operations in
+ * that order, never contracted; action, reward, discount, meta and the pairs are untouched. n_cols = 0 turns it off (the default: the
+ * gather copies the rows). The values live in a device buffer allocated at create; calling again with new values writes them in place
+ * on `stream` and later launches, graph replays included, use them. Switching between off and on changes the captured kernel:
+ * exorl_agent_step_graph refuses a graph captured in the other state. Fails for n_cols * 4 != obs_bytes and on a frame-stacked arena;
+ * exorl_agent_enable_graph_intr refuses a normalised arena. */
+int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* mean_host, const float* inv_scale_host, void* stream);
 /* MT19937 states as exposed by random.getstate()[1] / np.random.get_state()[1:3]. */
 int exorl_replay_seed_mt(exorl_replay_t* r, const uint32_t* py_key624, int32_t py_pos,
                          const uint32_t* np_key624, int32_t np_pos);
