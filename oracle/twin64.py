@@ -83,6 +83,37 @@ def _margin_min(q1, q2):
     return ((q1 - q2).abs() / torch.maximum(q1.abs(), q2.abs()).clamp_min(1e-300)).reshape(-1)
 
 
+def backward_with_kinks(res, step, loss, all_params, params, tape, kink_delta, kink_cap):
+    """loss.backward() with the bookkeeping a tight comparison needs, shared by every twin (this file, oracle/intr64.py). Clears the
+    .grad of all_params, returns the gradients of `params` (float64 numpy, None where a tensor gets none) and fills res.relus[step],
+    res.n_kinks[step] and res.kinks[step] from the tape of pre-ReLU tensors: dict(net, name, w1, b1, z, a) with `a` retaining its grad."""
+    for p in all_params:
+        p.grad = None
+    loss.backward(retain_graph=kink_delta is not None)
+    grads = [None if p.grad is None else p.grad.detach().double().numpy().copy() for p in params]
+    res.relus[step] = [dict(net=r['net'], name=r['name'], w1=r['w1'], b1=r['b1'], z=r['z'].detach(),
+                            da=r['a'].grad.detach() if r['a'].grad is not None else torch.zeros_like(r['z'])) for r in tape]
+    if kink_delta is not None:
+        found = []
+        for r, rec in zip(tape, res.relus[step]):
+            z = rec['z']
+            idx = (z.abs() < kink_delta * z.abs().max()).nonzero()
+            found += [(r, rec, int(m), int(c)) for m, c in idx.tolist()]
+        res.n_kinks[step] = len(found)
+        res.kinks[step] = None
+        if len(found) <= kink_cap:
+            res.kinks[step] = []
+            for r, rec, m, c in found:
+                gz = torch.autograd.grad(r['z'][m, c], params, retain_graph=True, allow_unused=True)
+                # on in this arithmetic (z > 0): a flip removes the element's path; off: a flip adds it
+                f = -1.0 if float(rec['z'][m, c]) > 0 else 1.0
+                da = float(rec['da'][m, c])
+                D = [None if g is None else (f * da * g.detach().double()).numpy() for g in gz]
+                res.kinks[step].append(dict(net=rec['net'], name=rec['name'], w1=rec['w1'], b1=rec['b1'], row=m, unit=c,
+                                            z=float(rec['z'][m, c]), D=D))
+    return grads
+
+
 class Result:
     """metrics: dict of floats. critic_grads / actor_grads: lists of float64 numpy arrays in parameters() order (None for a net the
     step has no gradient for). decisions: name -> (int64 numpy array of the choices, float64 numpy array of relative margins).
@@ -152,30 +183,7 @@ class Twin:
 
     # ---- one optimiser step with the bookkeeping -----------------------------------------------------------------------------
     def _step(self, res, step, loss, params, opt, tape, kink_delta, kink_cap):
-        for p in self.actor + (self.critic or []):
-            p.grad = None
-        loss.backward(retain_graph=kink_delta is not None)
-        grads = [None if p.grad is None else p.grad.detach().double().numpy().copy() for p in params]
-        res.relus[step] = [dict(net=r['net'], name=r['name'], w1=r['w1'], b1=r['b1'], z=r['z'].detach(),
-                                da=r['a'].grad.detach() if r['a'].grad is not None else torch.zeros_like(r['z'])) for r in tape]
-        if kink_delta is not None:
-            found = []
-            for r, rec in zip(tape, res.relus[step]):
-                z = rec['z']
-                idx = (z.abs() < kink_delta * z.abs().max()).nonzero()
-                found += [(r, rec, int(m), int(c)) for m, c in idx.tolist()]
-            res.n_kinks[step] = len(found)
-            res.kinks[step] = None
-            if len(found) <= kink_cap:
-                res.kinks[step] = []
-                for r, rec, m, c in found:
-                    gz = torch.autograd.grad(r['z'][m, c], params, retain_graph=True, allow_unused=True)
-                    # on in this arithmetic (z > 0): a flip removes the element's path; off: a flip adds it
-                    f = -1.0 if float(rec['z'][m, c]) > 0 else 1.0
-                    da = float(rec['da'][m, c])
-                    D = [None if g is None else (f * da * g.detach().double()).numpy() for g in gz]
-                    res.kinks[step].append(dict(net=rec['net'], name=rec['name'], w1=rec['w1'], b1=rec['b1'], row=m, unit=c,
-                                                z=float(rec['z'][m, c]), D=D))
+        grads = backward_with_kinks(res, step, loss, self.actor + (self.critic or []), params, tape, kink_delta, kink_cap)
         opt.step()
         if step == 'critic' and self._critic_after is not None:
             with torch.no_grad():

@@ -302,7 +302,10 @@ def test_adam_fused_soft_update_equals_separate(lib):
     assert torch.equal(pa, pb) and torch.equal(ta, tb)
 
 
-@pytest.mark.parametrize('ns,nt,dim,k', [(16, 16, 8, 3), (10, 20, 6, 3), (1024, 1024, 512, 12), (1024, 2048, 128, 3), (7, 100, 70, 5)])
+@pytest.mark.parametrize('ns,nt,dim,k', [(16, 16, 8, 3), (10, 20, 6, 3), (1024, 1024, 512, 12), (1024, 2048, 128, 3), (7, 100, 70, 5),
+                                         (5, 4096, 6, 3),       # last target count of the LDS knn_select_kernel (64 KB dynamic)
+                                         (7, 70, 5, 64),        # KNN_MAX_K
+                                         (9, 9, 4, 9)])         # k = n_tgt behind 55 padded +inf columns
 def test_knn_topk(lib, gold, ns, nt, dim, k):
     from exorl_amd import _lib as L
     from oracle import knn
