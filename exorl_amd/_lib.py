@@ -28,6 +28,8 @@ N_INTR_METRICS = 8
 INTR_XCHG_GRAD, INTR_XCHG_REP, INTR_XCHG_MOMENTS, INTR_XCHG_BN = 0, 1, 2, 3
 XCHG_F32, XCHG_F64 = 0, 1
 XCHG_SUM, XCHG_GATHER = 0, 1
+PIXEL_IMAGES_FRESH, PIXEL_IMAGES_AUGMENTED, PIXEL_IMAGES_ENCODED = 0, 1, 2
+PIXEL_XCHG_CRITIC_GRAD, PIXEL_XCHG_ACTOR_GRAD, PIXEL_XCHG_ENCODER_GRAD, PIXEL_XCHG_BN = 0, 1, 2, 3
 
 
 class ReplayCfg(C.Structure):
@@ -75,6 +77,11 @@ class PixelCfg(C.Structure):
                 ('seed', c_uint64), ('world_size', c_int32)]
 
 
+class PixelStep(C.Structure):
+    _fields_ = [('stddev', c_float), ('images', c_int32), ('shifts_obs_dev', c_void_p), ('shifts_next_dev', c_void_p),
+                ('noise_critic_dev', c_void_p), ('noise_actor_dev', c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/exorl_hip.h
 PROTOTYPES = {
     'exorl_u8_to_f32': (C.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -86,7 +93,7 @@ PROTOTYPES = {
     'exorl_pixel_agent_sync_target': (C.c_int, [c_void_p, c_void_p]),
     'exorl_pixel_agent_batch_slots': (C.c_int, [c_void_p, P(BatchOut)]),
     'exorl_pixel_agent_set_batch': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'exorl_pixel_agent_update': (C.c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exorl_pixel_agent_update': (C.c_int, [c_void_p, P(PixelStep), c_void_p]),
     'exorl_pixel_agent_augment': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_pixel_agent_encode': (C.c_int, [c_void_p, c_int32, c_int32, P(c_void_p), c_void_p]),
     'exorl_pixel_agent_encoder_step': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
@@ -98,12 +105,11 @@ PROTOTYPES = {
     'exorl_pixel_agent_state': (C.c_int, [c_void_p, c_void_p, c_void_p]),
     'exorl_pixel_agent_set_state': (C.c_int, [c_void_p, c_void_p, c_void_p]),
     'exorl_pixel_agent_encoder_opt2': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    'exorl_pixel_agent_update_phase': (C.c_int, [c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'exorl_pixel_agent_grad_buffer': (C.c_int, [c_void_p, c_int32, P(c_void_p), P(c_int64)]),
+    'exorl_pixel_agent_update_phase': (C.c_int, [c_void_p, c_int32, P(PixelStep), P(c_int32), c_void_p]),
+    'exorl_pixel_agent_exchange': (C.c_int, [c_void_p, c_int32, P(c_void_p), P(c_int64), P(c_int32), P(c_int32)]),
     'exorl_pixel_agent_set_comm': (C.c_int, [c_void_p, c_void_p]),
-    'exorl_pixel_agent_encoder_step_phase': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
-    'exorl_pixel_agent_rnd_features_phase': (C.c_int, [c_void_p, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    'exorl_pixel_agent_bn_partials': (C.c_int, [c_void_p, P(c_void_p), P(c_int64)]),
+    'exorl_pixel_agent_encoder_step_phase': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, P(c_int32), c_void_p]),
+    'exorl_pixel_agent_rnd_features_phase': (C.c_int, [c_void_p, c_int32, c_void_p, c_float, c_void_p, c_void_p, P(c_int32), c_void_p]),
     'exorl_pixel_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
     'exorl_pixel_agent_act': (C.c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_aug_shift': (C.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),

@@ -235,31 +235,41 @@ static void pcarve(exorl_pixel_agent* a, SimpleCarver& c) {
     a->act_ticket = reinterpret_cast<unsigned int*>(c.take(8));
 }
 
+// The split-K slabs of one trunk's x W0^T over the encoding's columns as GEMM problems p[0], p[stride], ...: slab i covers columns
+// [i * kc, (i + 1) * kc) and writes part + i * rows * F. Returns their number.
+static int trunk_slabs(const exorl_pixel_agent* a, const PNet& n, const float* P, const float* x, int rows, float* part, GemmProblem* p, int stride) {
+    const int F = n.F, R = a->R, kc = (int)round_up(cdiv(R, SPLITK), 4);
+    int cnt = 0;
+    for (int k0 = 0; cnt < SPLITK && k0 < R; k0 += kc, ++cnt) {
+        const int k = R - k0 < kc ? R - k0 : kc;
+        p[stride * cnt] = GemmProblem{x + k0, P + n.trunk.W + k0, part + (int64_t)cnt * rows * F, nullptr, rows, F, k, R, n.D, F};
+    }
+    return cnt;
+}
+static void trunk_reduce(const PNet& n, const float* P, const float* part, int cnt, int rows, const TrunkAct& t, hipStream_t s) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid1((int64_t)rows * n.F)), dim3(256), 0, s, part, P + n.trunk.b, t.z, (int64_t)rows * n.F, n.F, cnt);
+}
+static int trunk_ln_tanh(const PNet& n, const float* P, int rows, const TrunkAct& t, hipStream_t s) {
+    return ln_tanh_fwd(t.z, P + n.g, P + n.beta, t.h, t.xhat, t.rstd, rows, n.F, 1, 0, 0, s);
+}
+
 // z = [x | meta] W0^T + b0 (split-K over the encoding's columns, one more slab for the meta columns), then LayerNorm + tanh.
 // The trunk's input is cat([encoding, skill]) for the meta-conditioned agents (diayn.py:163-165, ddpg.py:305-312): the two parts stay
 // where they are (x: rows x R inside the encoder workspace, meta: rows x M) and enter as separate GEMM problems.
 static int trunk_forward(exorl_pixel_agent* a, const PNet& n, const float* P, const float* x, const float* meta, int rows, const TrunkAct& t, int prec,
                          hipStream_t s) {
     const int D = n.D, F = n.F, R = a->R, M = D - R;
-    int kc = (int)round_up(cdiv(R, SPLITK), 4);
     GemmProblem p[SPLITK + 1];                 // all slabs in one launch: SPLITK x rows/64 workgroups
-    int cnt = 0;
-    for (int i = 0; i < SPLITK; ++i) {
-        const int k0 = i * kc;
-        if (k0 >= R) break;
-        const int k = R - k0 < kc ? R - k0 : kc;
-        p[cnt] = GemmProblem{x + k0, P + n.trunk.W + k0, a->splitk + (int64_t)cnt * rows * F, nullptr, rows, F, k, R, D, F};
-        ++cnt;
-    }
+    int cnt = trunk_slabs(a, n, P, x, rows, a->splitk, p, 1);
     if (M > 0) {
         EXORL_REQUIRE(meta, "pixel_agent: the trunk takes %d meta columns but no meta rows were given", M);
         p[cnt] = GemmProblem{meta, P + n.trunk.W + R, a->splitk + (int64_t)cnt * rows * F, nullptr, rows, F, M, M, D, F};
         ++cnt;
     }
     EXORL_TRY(gemm_grouped(prec, 0, 0, p, cnt, false, false, s));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid1((int64_t)rows * F)), dim3(256), 0, s, a->splitk, P + n.trunk.b, t.z, (int64_t)rows * F, F, cnt);
+    trunk_reduce(n, P, a->splitk, cnt, rows, t, s);
     EXORL_LAUNCH_CHECK();
-    return ln_tanh_fwd(t.z, P + n.g, P + n.beta, t.h, t.xhat, t.rstd, rows, F, 1, 0, 0, s);
+    return trunk_ln_tanh(n, P, rows, t, s);
 }
 
 // Two trunks on the SAME encoding (actor + target critic on next_obs, actor + critic on obs) in one launch with their k-slabs interleaved:
@@ -267,25 +277,16 @@ static int trunk_forward(exorl_pixel_agent* a, const PNet& n, const float* P, co
 // and the second reads the 160 MB of encodings from L2 instead of HBM. Without meta columns only (2 x 16 problems = the launch limit).
 static int trunk_forward_pair(exorl_pixel_agent* a, const PNet& na, const float* Pa, const TrunkAct& ta, const PNet& nb, const float* Pb, const TrunkAct& tb,
                               const float* x, int rows, int prec, hipStream_t s) {
-    const int F = na.F, R = a->R, D = na.D;
-    EXORL_REQUIRE(D == R && nb.D == R && nb.F == F, "trunk_forward_pair: needs two meta-free trunks of one width");
-    const int kc = (int)round_up(cdiv(R, SPLITK), 4);
+    EXORL_REQUIRE(na.D == a->R && nb.D == a->R && nb.F == na.F, "trunk_forward_pair: needs two meta-free trunks of one width");
     GemmProblem p[2 * SPLITK];
-    int cnt = 0;
-    for (int i = 0; i < SPLITK; ++i) {
-        const int k0 = i * kc;
-        if (k0 >= R) break;
-        const int k = R - k0 < kc ? R - k0 : kc;
-        p[2 * cnt] = GemmProblem{x + k0, Pa + na.trunk.W + k0, a->splitk + (int64_t)cnt * rows * F, nullptr, rows, F, k, R, D, F};
-        p[2 * cnt + 1] = GemmProblem{x + k0, Pb + nb.trunk.W + k0, a->splitk2 + (int64_t)cnt * rows * F, nullptr, rows, F, k, R, D, F};
-        ++cnt;
-    }
+    const int cnt = trunk_slabs(a, na, Pa, x, rows, a->splitk, p, 2);
+    trunk_slabs(a, nb, Pb, x, rows, a->splitk2, p + 1, 2);
     EXORL_TRY(gemm_grouped(prec, 0, 0, p, 2 * cnt, false, false, s));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid1((int64_t)rows * F)), dim3(256), 0, s, a->splitk, Pa + na.trunk.b, ta.z, (int64_t)rows * F, F, cnt);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid1((int64_t)rows * F)), dim3(256), 0, s, a->splitk2, Pb + nb.trunk.b, tb.z, (int64_t)rows * F, F, cnt);
+    trunk_reduce(na, Pa, a->splitk, cnt, rows, ta, s);
+    trunk_reduce(nb, Pb, a->splitk2, cnt, rows, tb, s);
     EXORL_LAUNCH_CHECK();
-    EXORL_TRY(ln_tanh_fwd(ta.z, Pa + na.g, Pa + na.beta, ta.h, ta.xhat, ta.rstd, rows, F, 1, 0, 0, s));
-    return ln_tanh_fwd(tb.z, Pb + nb.g, Pb + nb.beta, tb.h, tb.xhat, tb.rstd, rows, F, 1, 0, 0, s);
+    EXORL_TRY(trunk_ln_tanh(na, Pa, rows, ta, s));
+    return trunk_ln_tanh(nb, Pb, rows, tb, s);
 }
 
 // dh (rows, F) at the trunk output -> parameter grads (W0, b0, gain, beta) and optionally d/d(encoding) (rows, R)
@@ -311,6 +312,37 @@ static int trunk_backward(exorl_pixel_agent* a, const PNet& n, const float* P, f
 static int padam(exorl_pixel_agent* a, int net, int64_t n, float* target, hipStream_t s) {
     return adam_step(a->flat[net][0], a->flat[net][1], a->flat[net][2], a->flat[net][3], n, a->cfg.lr, 0.9f, 0.999f, 1e-8f, net == 0 ? a->t_enc : a->t,
                      target, target ? a->cfg.tau : 0.f, s);
+}
+
+// What the ranks exchange between the phases of a call (EXORL_PIXEL_XCHG_*): the one table behind exorl_pixel_agent_exchange and run_phases.
+static int pixel_exchange(exorl_pixel_agent* a, int32_t id, void** ptr, int64_t* count, int32_t* dtype) {
+    *dtype = id == EXORL_PIXEL_XCHG_BN ? EXORL_XCHG_F64 : EXORL_XCHG_F32;
+    switch (id) {
+        // the critic's gradients and right behind them the encoder's (pcarve): one range while the encoder trains with the critic's loss
+        case EXORL_PIXEL_XCHG_CRITIC_GRAD: *ptr = a->flat[2][1]; *count = a->critic.total + (a->train_encoder ? a->enc_total : 0); return 0;
+        case EXORL_PIXEL_XCHG_ACTOR_GRAD: *ptr = a->flat[1][1]; *count = a->actor.total; return 0;
+        case EXORL_PIXEL_XCHG_ENCODER_GRAD: *ptr = a->flat[0][1]; *count = a->enc_total; return 0;
+        case EXORL_PIXEL_XCHG_BN: *ptr = a->bn_scratch + 32; *count = (int64_t)a->cfg.c_in * BN2_CHUNKS; return 0;
+    }
+    set_error("pixel_agent_exchange: exchange %d out of range (0..3)", id);
+    return 2;
+}
+
+// The one loop behind every whole call: phase(0, &next), phase(1, &next), ... until a phase names no exchange. With a communicator the
+// exchange a phase names is sum-all-reduced on s before the next phase runs, except `own`, which the phase has reduced itself.
+template <class Phase>
+static int run_phases(exorl_pixel_agent* a, exorl_comm* comm, int32_t own, hipStream_t s, Phase phase) {
+    for (int32_t k = 0, next = 0; next >= 0; ++k) {
+        EXORL_TRY(phase(k, &next));
+        if (!comm || next < 0 || next == own) continue;
+        void* buf = nullptr;
+        int64_t n = 0;
+        int32_t dtype = 0;
+        EXORL_TRY(pixel_exchange(a, next, &buf, &n, &dtype));
+        EXORL_REQUIRE(dtype == EXORL_XCHG_F32, "pixel_agent: exchange %d is not fp32: the communicator reduces fp32 only", next);
+        EXORL_TRY(comm_allreduce_sum(comm, static_cast<float*>(buf), n, s));
+    }
+    return 0;
 }
 
 }  // namespace exorl
@@ -466,13 +498,15 @@ int exorl_pixel_agent_encode(exorl_pixel_agent_t* a, int32_t which, int32_t targ
 
 // Backward through the encoder pass last run by exorl_pixel_agent_encode(which, 0) from dfeat_dev (batch, repr_dim; overwritten), then
 // one Adam step of the encoder with optimiser state `opt` (0: encoder_opt, ddpg.py:188-190; 1: the encoder's slots in proto_opt, proto.py:75-78)
-// Data parallel: phase 0 is the backward pass (the encoder's gradients, exchange 2 of exorl_pixel_agent_grad_buffer, are this rank's partial
-// sum), phase 1 the optimiser step(s).
-int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, int32_t phase, void* stream) {
-    EXORL_REQUIRE(a && (which == 0 || which == 1) && opt >= 0 && opt <= 2 && (phase == 1 || (phase == 0 && dfeat_dev)),
+// Data parallel: phase 0 is the backward pass (the encoder's gradients, EXORL_PIXEL_XCHG_ENCODER_GRAD, are this rank's partial sum),
+// phase 1 the optimiser step(s).
+int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, int32_t phase, int32_t* next_exchange,
+                                         void* stream) {
+    EXORL_REQUIRE(a && next_exchange && (which == 0 || which == 1) && opt >= 0 && opt <= 2 && (phase == 1 || (phase == 0 && dfeat_dev)),
                   "pixel_agent_encoder_step: bad arguments");
     hipStream_t s = as_stream(stream);
     const auto& c = a->cfg;
+    *next_exchange = phase == 0 ? EXORL_PIXEL_XCHG_ENCODER_GRAD : -1;
     if (phase == 0)
         return exorl_encoder_backward_prec(a->flat[0][0], c.c_in, c.hw, which ? a->aug_n : a->aug_o, c.batch, which ? a->enc_ws_n : a->enc_ws_o, dfeat_dev,
                                            a->flat[0][1], a->cfg.precision, s);
@@ -485,20 +519,22 @@ int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, 
 
 int exorl_pixel_agent_encoder_step(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, void* stream) {
     EXORL_REQUIRE(a && dfeat_dev, "pixel_agent_encoder_step: bad arguments");
-    EXORL_REQUIRE(a->world == 1, "pixel_agent_encoder_step: world_size=%d: run exorl_pixel_agent_encoder_step_phase 0, sum-all-reduce "
-                  "exorl_pixel_agent_grad_buffer 2, then phase 1", a->world);
-    EXORL_TRY(exorl_pixel_agent_encoder_step_phase(a, which, dfeat_dev, opt, 0, stream));
-    return exorl_pixel_agent_encoder_step_phase(a, which, dfeat_dev, opt, 1, stream);
+    EXORL_REQUIRE(a->world == 1, "pixel_agent_encoder_step: world_size=%d: run the phases of exorl_pixel_agent_encoder_step_phase and "
+                  "sum-all-reduce the exchange each one names (exorl_pixel_agent_exchange)", a->world);
+    return run_phases(a, nullptr, -1, as_stream(stream), [&](int32_t phase, int32_t* next) {
+        return exorl_pixel_agent_encoder_step_phase(a, which, dfeat_dev, opt, phase, next, stream);
+    });
 }
 
 // RND on pixels (rnd.py:47-53): x = clamp(BatchNorm2d(RandomShiftsAug(obs))) -> the agent's encoder (*feat_pred_dev, kept for
 // exorl_pixel_agent_encoder_step(0, ...)) and the frozen copy held in the encoder_target slot (*feat_target_dev). shifts_dev: (batch, 2) or null.
-// Data parallel: phases 0 and 1 end in the per-channel double partials of the BatchNorm2d statistics (exorl_pixel_agent_bn_partials), which
+// Data parallel: phases 0 and 1 end in the per-channel double partials of the BatchNorm2d statistics (EXORL_PIXEL_XCHG_BN), which
 // the ranks sum-all-reduce; the statistics are then over batch * world_size images and the running statistics stay replicated.
 int exorl_pixel_agent_rnd_features_phase(exorl_pixel_agent_t* a, int32_t phase, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev,
-                                         float** feat_target_dev, void* stream) {
-    EXORL_REQUIRE(a && clip_val > 0.f && phase >= 0 && phase <= 2 && (phase < 2 || (feat_pred_dev && feat_target_dev)),
+                                         float** feat_target_dev, int32_t* next_exchange, void* stream) {
+    EXORL_REQUIRE(a && next_exchange && clip_val > 0.f && phase >= 0 && phase <= 2 && (phase < 2 || (feat_pred_dev && feat_target_dev)),
                   "pixel_agent_rnd_features: bad arguments");
+    *next_exchange = phase < 2 ? EXORL_PIXEL_XCHG_BN : -1;
     hipStream_t s = as_stream(stream);
     const auto& c = a->cfg;
     const int64_t hw = (int64_t)c.hw * c.hw, total = (int64_t)c.batch * c.c_in * hw;
@@ -529,17 +565,17 @@ int exorl_pixel_agent_rnd_features_phase(exorl_pixel_agent_t* a, int32_t phase, 
 int exorl_pixel_agent_rnd_features(exorl_pixel_agent_t* a, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev, float** feat_target_dev,
                                    void* stream) {
     EXORL_REQUIRE(a && feat_pred_dev && feat_target_dev && clip_val > 0.f, "pixel_agent_rnd_features: bad arguments");
-    EXORL_REQUIRE(a->world == 1, "pixel_agent_rnd_features: world_size=%d: run exorl_pixel_agent_rnd_features_phase 0, 1, 2 and sum-all-reduce "
-                  "exorl_pixel_agent_bn_partials after phases 0 and 1", a->world);
-    for (int phase = 0; phase < 3; ++phase) EXORL_TRY(exorl_pixel_agent_rnd_features_phase(a, phase, shifts_dev, clip_val, feat_pred_dev, feat_target_dev, stream));
-    return 0;
+    EXORL_REQUIRE(a->world == 1, "pixel_agent_rnd_features: world_size=%d: run the phases of exorl_pixel_agent_rnd_features_phase and "
+                  "sum-all-reduce the exchange each one names (exorl_pixel_agent_exchange)", a->world);
+    return run_phases(a, nullptr, -1, as_stream(stream), [&](int32_t phase, int32_t* next) {
+        return exorl_pixel_agent_rnd_features_phase(a, phase, shifts_dev, clip_val, feat_pred_dev, feat_target_dev, next, stream);
+    });
 }
 
-// the BatchNorm2d partial sums the ranks add up between the phases of exorl_pixel_agent_rnd_features_phase: c_in x BN2_CHUNKS doubles
-int exorl_pixel_agent_bn_partials(exorl_pixel_agent_t* a, void** ptr_dev, int64_t* n_doubles) {
-    EXORL_REQUIRE(a && ptr_dev && n_doubles, "pixel_agent_bn_partials: null argument");
-    *ptr_dev = a->bn_scratch + 32; *n_doubles = (int64_t)a->cfg.c_in * BN2_CHUNKS;
-    return 0;
+int exorl_pixel_agent_exchange(exorl_pixel_agent_t* a, int32_t id, void** ptr_dev, int64_t* count, int32_t* dtype, int32_t* op) {
+    EXORL_REQUIRE(a && ptr_dev && count && dtype && op, "pixel_agent_exchange: null argument");
+    *op = EXORL_XCHG_SUM;
+    return pixel_exchange(a, id, ptr_dev, count, dtype);
 }
 
 // BatchNorm2d buffers of RND's normalize_obs: running_mean[c_in], running_var[c_in], num_batches_tracked (as float)
@@ -614,69 +650,114 @@ static int sf_dout(exorl_pixel_agent* a, hipStream_t s) {       // dQ_n -> gradi
     return 0;
 }
 
-// Phase 0: aug_and_encode, update_critic's forward and backward (ddpg.py:213-215, 240-268). Leaves the critic's and (train_encoder) the
-// encoder's gradients in exchange 0. side != nullptr (exorl_pixel_agent_update with a communicator): the critic's gradients are final when
-// its trunk backward returns, so they are all-reduced on comm_stream while the encoder's backward pass runs, the encoder's after it on s.
-static int pphase0(exorl_pixel_agent* a, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next, const float* noise_c, exorl_comm* side,
-                   hipStream_t s) {
+// Policy mean of `rows` encodings x: the actor's trunk, policy, tanh -> mu. Pb != nullptr: the critic's trunk with parameters Pb runs on the
+// same rows into tb — in the actor's launch with the k-slabs interleaved where the trunks take no meta columns, else on its own behind the policy.
+static int policy_mean(exorl_pixel_agent* a, const float* x, const float* meta, int rows, const TrunkAct& ta, float* mu, const float* Pb,
+                       const TrunkAct* tb, hipStream_t s) {
     const auto& c = a->cfg;
-    const int B = c.batch, A = c.act_dim, F = c.feature_dim, FA = F + A, prec = c.precision;
-    float *Pe = a->flat[0][0], *Pa = a->flat[1][0], *Pc = a->flat[2][0], *Pt = a->flat[3][0];
-    float *Ge = a->flat[0][1], *Gc = a->flat[2][1];
-    const float* mt = c.meta_dim > 0 ? a->meta : nullptr;
-    // ---- aug_and_encode (ddpg.py:213-215, 312-315); shifts_obs == (const int32_t*)-1: keep the images exorl_pixel_agent_augment made;
-    // (const int32_t*)-2: keep the encodings exorl_pixel_agent_encode(0 / 1, online) made as well — the agents that step the encoder
-    // through their own module pass the critic the encodings computed BEFORE that step (icm.py:97-131, diayn.py:137-170), detached
-    const bool keep_feat = shifts_obs == reinterpret_cast<const int32_t*>(-2);
-    if (keep_feat) {
+    const int A = c.act_dim, F = c.feature_dim, prec = c.precision;
+    const float* Pa = a->flat[1][0];
+    const bool pair = Pb && c.meta_dim == 0;
+    if (pair) EXORL_TRY(trunk_forward_pair(a, a->actor, Pa, ta, a->critic, Pb, *tb, x, rows, prec, s));
+    else EXORL_TRY(trunk_forward(a, a->actor, Pa, x, meta, rows, ta, prec, s));
+    Mlp& pol = a->actor.head[0];
+    EXORL_TRY(mlp_forward(pol, Pa, ta.h, F, rows, prec, s));
+    EXORL_CHECK_HIP(hipMemcpyAsync(mu, pol.act[2], sizeof(float) * rows * A, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(tanh_kernel, dim3(grid1((int64_t)rows * A)), dim3(256), 0, s, mu, (int64_t)rows * A);
+    EXORL_LAUNCH_CHECK();
+    if (Pb && !pair) EXORL_TRY(trunk_forward(a, a->critic, Pb, x, meta, rows, *tb, prec, s));
+    return 0;
+}
+
+// How one driver call runs the step. Each driver builds one (make_pix_step) before its first launch and hands it to every phase, so what a
+// step does is decided once, from the call's exorl_pixel_step and the handle's settings, and nothing of one call carries over to the next.
+//   exorl_pixel_agent_update_phase   one phase:    whole = false, comm = nullptr
+//   exorl_pixel_agent_update         all phases:   whole; comm = the handle's communicator
+struct PixStep {
+    hipStream_t s;
+    exorl_pixel_step in;                 // stddev, what the image buffers hold, caller-supplied shifts and noise (nullptr: device Philox)
+    bool whole;                          // this call drives every phase
+    exorl_comm* comm;                    // whole-step call on a handle with a communicator: phase 0 reduces exchange 0 itself, the
+                                         // critic's part on comm_stream beside the encoder's backward pass
+    // derived once
+    int B, A, F, FA, prec;
+    bool pair;                           // no meta columns: two trunks on one encoding share a launch
+    const float* mt;                     // the meta rows the trunks read, or nullptr
+    float *Pe, *Pa, *Pc, *Pt, *Ge, *Ga, *Gc;
+};
+static int make_pix_step(exorl_pixel_agent* a, const exorl_pixel_step* in, bool whole, void* stream, const char* fn, PixStep* out) {
+    EXORL_REQUIRE(a && in && in->stddev > 0.f, "%s: bad arguments", fn);
+    EXORL_REQUIRE(in->images >= EXORL_PIXEL_IMAGES_FRESH && in->images <= EXORL_PIXEL_IMAGES_ENCODED, "%s: images=%d is no EXORL_PIXEL_IMAGES_* value (0..2)",
+                  fn, in->images);
+    EXORL_REQUIRE(in->images == EXORL_PIXEL_IMAGES_FRESH || (!in->shifts_obs_dev && !in->shifts_next_dev),
+                  "%s: shifts given with images=%d: only EXORL_PIXEL_IMAGES_FRESH augments", fn, in->images);
+    const auto& c = a->cfg;
+    PixStep st{as_stream(stream), *in, whole, whole ? a->comm : nullptr};
+    st.B = c.batch; st.A = c.act_dim; st.F = c.feature_dim; st.FA = st.F + st.A; st.prec = c.precision;
+    st.pair = c.meta_dim == 0;
+    st.mt = c.meta_dim > 0 ? a->meta : nullptr;
+    st.Pe = a->flat[0][0]; st.Pa = a->flat[1][0]; st.Pc = a->flat[2][0]; st.Pt = a->flat[3][0];
+    st.Ge = a->flat[0][1]; st.Ga = a->flat[1][1]; st.Gc = a->flat[2][1];
+    *out = st;
+    return 0;
+}
+
+// Both Q heads of the critic with parameters P on [h | act]: the rows into xq, with `draw` the action columns overwritten by the
+// TruncatedNormal sample around act, then Q1 and Q2 layer by layer in shared launches (outputs: the halves of a->q).
+static int twin_q(exorl_pixel_agent* a, const PixStep& st, const float* P, const float* h, const float* act, float* xq, const NoiseSpec* draw = nullptr,
+                  float* logprob = nullptr) {
+    EXORL_TRY(launch_concat(h, st.F, st.F, act, st.A, st.A, xq, st.B, st.s));
+    if (draw)
+        EXORL_TRY(sample_action(act, *draw, st.in.stddev, a->cfg.stddev_clip, 1, xq + st.F, st.FA, st.B, st.A, logprob, st.s, nullptr, logprob ? a->world : 1));
+    EXORL_TRY(mlp_forward_many(a->critic.head, 2, P, xq, st.FA, st.B, st.prec, st.s));
+    return sf_q(a, st.s);
+}
+
+// Phase 0: aug_and_encode, update_critic's forward and backward (ddpg.py:213-215, 240-268). Leaves the critic's and (train_encoder) the
+// encoder's gradients in exchange 0. st.comm: the critic's gradients are final when its trunk backward returns, so they are all-reduced on
+// comm_stream while the encoder's backward pass runs, the encoder's after it on s.
+static int pphase0(exorl_pixel_agent* a, const PixStep& st) {
+    const auto& c = a->cfg;
+    const int B = st.B, F = st.F, FA = st.FA, prec = st.prec;
+    hipStream_t s = st.s;
+    // ---- aug_and_encode (ddpg.py:213-215, 312-315). ENCODED: the agents that step the encoder through their own module pass the critic the
+    // encodings computed BEFORE that step (icm.py:97-131, diayn.py:137-170), detached
+    if (st.in.images == EXORL_PIXEL_IMAGES_ENCODED) {
         EXORL_REQUIRE(a->have_feat_o && a->have_feat_n && !a->train_encoder, "pixel_agent_update: kept encodings need exorl_pixel_agent_encode(0) and (1) "
                       "with the online encoder first, and set_train_encoder(0) (they are detached)");
     } else {
-        if (shifts_obs != reinterpret_cast<const int32_t*>(-1)) EXORL_TRY(exorl_pixel_agent_augment(a, shifts_obs, shifts_next, s));
+        if (st.in.images == EXORL_PIXEL_IMAGES_FRESH) EXORL_TRY(exorl_pixel_agent_augment(a, st.in.shifts_obs_dev, st.in.shifts_next_dev, s));
         EXORL_REQUIRE(a->augmented, "pixel_agent_update: no augmented batch");
-        EXORL_TRY(exorl_encoder_forward_prec(Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, &a->feat_o, a->cfg.precision, s));
-        EXORL_TRY(exorl_encoder_forward_prec(Pe, c.c_in, c.hw, a->aug_n, B, a->enc_ws_n, &a->feat_n, a->cfg.precision, s));
+        EXORL_TRY(exorl_encoder_forward_prec(st.Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, &a->feat_o, prec, s));
+        EXORL_TRY(exorl_encoder_forward_prec(st.Pe, c.c_in, c.hw, a->aug_n, B, a->enc_ws_n, &a->feat_n, prec, s));
     }
     a->have_feat_o = a->have_feat_n = false;
     // ---- update_critic (ddpg.py:240-268)
-    const bool pair = c.meta_dim == 0;
-    if (pair) EXORL_TRY(trunk_forward_pair(a, a->actor, Pa, a->ta_n, a->critic, Pt, a->tt, a->feat_n, B, prec, s));
-    else EXORL_TRY(trunk_forward(a, a->actor, Pa, a->feat_n, mt, B, a->ta_n, prec, s));
-    Mlp& pol = a->actor.head[0];
-    EXORL_TRY(mlp_forward(pol, Pa, a->ta_n.h, F, B, prec, s));
-    EXORL_CHECK_HIP(hipMemcpyAsync(a->mu_n, pol.act[2], sizeof(float) * B * A, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(tanh_kernel, dim3(grid1((int64_t)B * A)), dim3(256), 0, s, a->mu_n, (int64_t)B * A);
-    EXORL_LAUNCH_CHECK();
-    if (!pair) EXORL_TRY(trunk_forward(a, a->critic, Pt, a->feat_n, mt, B, a->tt, prec, s));
-    EXORL_TRY(launch_concat(a->tt.h, F, F, a->mu_n, A, A, a->xq_t, B, s));           // action columns overwritten by the sample below
-    NoiseSpec nc{noise_c, c.seed, 2 * a->noise_counter, nullptr};
-    EXORL_TRY(sample_action(a->mu_n, nc, stddev, c.stddev_clip, 1, a->xq_t + F, FA, B, A, nullptr, s));
+    EXORL_TRY(policy_mean(a, a->feat_n, st.mt, B, a->ta_n, a->mu_n, st.Pt, &a->tt, s));
+    NoiseSpec nc{st.in.noise_critic_dev, c.seed, 2 * a->noise_counter, nullptr};
     // the target's Q heads reuse the critic's Mlp buffers (outputs to q), then are copied to tq
-    EXORL_TRY(mlp_forward_many(a->critic.head, 2, Pt, a->xq_t, FA, B, prec, s));          // Q1 and Q2 layer by layer in shared launches
-    EXORL_TRY(sf_q(a, s));
+    EXORL_TRY(twin_q(a, st, st.Pt, a->tt.h, a->mu_n, a->xq_t, &nc));
     EXORL_CHECK_HIP(hipMemcpyAsync(a->tq, a->q, sizeof(float) * 2 * B, hipMemcpyDeviceToDevice, s));
-    EXORL_TRY(trunk_forward(a, a->critic, Pc, a->feat_o, mt, B, a->tc, prec, s));
-    EXORL_TRY(launch_concat(a->tc.h, F, F, a->action, A, A, a->xq_c, B, s));
-    EXORL_TRY(mlp_forward_many(a->critic.head, 2, Pc, a->xq_c, FA, B, prec, s));
-    EXORL_TRY(sf_q(a, s));
+    EXORL_TRY(trunk_forward(a, a->critic, st.Pc, a->feat_o, st.mt, B, a->tc, prec, s));
+    EXORL_TRY(twin_q(a, st, st.Pc, a->tc.h, a->action, a->xq_c));
     EXORL_TRY(critic_loss(a->q, a->tq, a->reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));
     EXORL_TRY(sf_dout(a, s));
     // both heads' backward passes layer by layer in shared launches; d/d(input) of the two is summed by the second head's accumulating dgrad
     // (dx0 + dx1, the same fp32 addition add_cols_kernel used to make of two buffers)
-    EXORL_TRY(mlp_backward_many(a->critic.head, 2, Pc, Gc, a->xq_c, FA, B, prec, s, a->dxq[0]));
+    EXORL_TRY(mlp_backward_many(a->critic.head, 2, st.Pc, st.Gc, a->xq_c, FA, B, prec, s, a->dxq[0]));
     hipLaunchKernelGGL(add_cols_kernel, dim3(grid1((int64_t)B * F)), dim3(256), 0, s, a->dxq[0], (int64_t)FA, (const float*)nullptr, (int64_t)FA, 0, F, a->dh, B);
     EXORL_LAUNCH_CHECK();
-    EXORL_TRY(trunk_backward(a, a->critic, Pc, Gc, a->feat_o, mt, B, a->tc, a->dh, a->train_encoder ? a->dfeat : nullptr, prec, s));
-    if (!a->train_encoder) return side ? comm_allreduce_sum(side, Gc, a->critic.total, s) : 0;
-    if (side) {
+    EXORL_TRY(trunk_backward(a, a->critic, st.Pc, st.Gc, a->feat_o, st.mt, B, a->tc, a->dh, a->train_encoder ? a->dfeat : nullptr, prec, s));
+    if (!a->train_encoder) return st.comm ? comm_allreduce_sum(st.comm, st.Gc, a->critic.total, s) : 0;
+    if (st.comm) {
         EXORL_CHECK_HIP(hipEventRecord(a->ev_critic_ready, s));
         EXORL_CHECK_HIP(hipStreamWaitEvent(a->comm_stream, a->ev_critic_ready, 0));
-        EXORL_TRY(comm_allreduce_sum(side, Gc, a->critic.total, a->comm_stream));
+        EXORL_TRY(comm_allreduce_sum(st.comm, st.Gc, a->critic.total, a->comm_stream));
         EXORL_CHECK_HIP(hipEventRecord(a->ev_critic_done, a->comm_stream));
     }
-    EXORL_TRY(exorl_encoder_backward_prec(Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, a->dfeat, Ge, a->cfg.precision, s));
-    if (side) {
-        EXORL_TRY(comm_allreduce_sum(side, Ge, a->enc_total, s));
+    EXORL_TRY(exorl_encoder_backward_prec(st.Pe, c.c_in, c.hw, a->aug_o, B, a->enc_ws_o, a->dfeat, st.Ge, prec, s));
+    if (st.comm) {
+        EXORL_TRY(comm_allreduce_sum(st.comm, st.Ge, a->enc_total, s));
         EXORL_CHECK_HIP(hipStreamWaitEvent(s, a->ev_critic_done, 0));          // Adam (phase 1) reads both halves of exchange 0
     }
     return 0;
@@ -684,83 +765,64 @@ static int pphase0(exorl_pixel_agent* a, float stddev, const int32_t* shifts_obs
 
 // Phase 1: critic_opt / encoder_opt step, then update_actor's forward and backward on obs.detach() with the stepped critic (ddpg.py:270-292).
 // Leaves the actor's gradients in exchange 1.
-static int pphase1(exorl_pixel_agent* a, float stddev, const float* noise_a, hipStream_t s) {
+static int pphase1(exorl_pixel_agent* a, const PixStep& st) {
     const auto& c = a->cfg;
-    const int B = c.batch, A = c.act_dim, F = c.feature_dim, FA = F + A, prec = c.precision;
-    float *Pa = a->flat[1][0], *Pc = a->flat[2][0];
-    float *Ga = a->flat[1][1], *Gc = a->flat[2][1];
-    const float* mt = c.meta_dim > 0 ? a->meta : nullptr;
+    const int B = st.B, A = st.A, F = st.F, FA = st.FA, prec = st.prec;
+    hipStream_t s = st.s;
     a->t += 1;
     EXORL_TRY(padam(a, 2, a->critic.total, nullptr, s));
     if (a->train_encoder) { a->t_enc += 1; EXORL_TRY(padam(a, 0, a->enc_total, nullptr, s)); }
-    const bool pair = c.meta_dim == 0;
     Mlp& pol = a->actor.head[0];
-    if (pair) EXORL_TRY(trunk_forward_pair(a, a->actor, Pa, a->ta_o, a->critic, Pc, a->tc, a->feat_o, B, prec, s));
-    else EXORL_TRY(trunk_forward(a, a->actor, Pa, a->feat_o, mt, B, a->ta_o, prec, s));
-    EXORL_TRY(mlp_forward(pol, Pa, a->ta_o.h, F, B, prec, s));
-    EXORL_CHECK_HIP(hipMemcpyAsync(a->mu_o, pol.act[2], sizeof(float) * B * A, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(tanh_kernel, dim3(grid1((int64_t)B * A)), dim3(256), 0, s, a->mu_o, (int64_t)B * A);
-    EXORL_LAUNCH_CHECK();
-    if (!pair) EXORL_TRY(trunk_forward(a, a->critic, Pc, a->feat_o, mt, B, a->tc, prec, s));
-    EXORL_TRY(launch_concat(a->tc.h, F, F, a->mu_o, A, A, a->xq_c, B, s));
-    NoiseSpec na{noise_a, c.seed, 2 * a->noise_counter + 1, nullptr};
-    EXORL_TRY(sample_action(a->mu_o, na, stddev, c.stddev_clip, 1, a->xq_c + F, FA, B, A, a->metrics + EXORL_M_ACTOR_LOGPROB, s, nullptr, a->world));
+    EXORL_TRY(policy_mean(a, a->feat_o, st.mt, B, a->ta_o, a->mu_o, st.Pc, &a->tc, s));
+    NoiseSpec na{st.in.noise_actor_dev, c.seed, 2 * a->noise_counter + 1, nullptr};
+    EXORL_TRY(twin_q(a, st, st.Pc, a->tc.h, a->mu_o, a->xq_c, &na, a->metrics + EXORL_M_ACTOR_LOGPROB));
     a->noise_counter += 1;
-    EXORL_TRY(mlp_forward_many(a->critic.head, 2, Pc, a->xq_c, FA, B, prec, s));
-    EXORL_TRY(sf_q(a, s));
     EXORL_TRY(actor_stats(a->q, a->stats, B, s));
     EXORL_TRY(actor_dq(a->q, a->stats, a->dq, B, a->inv_bg, 0.f, 0, s));
     EXORL_TRY(sf_dout(a, s));
-    EXORL_TRY(mlp_backward_many(a->critic.head, 2, Pc, Gc, a->xq_c, FA, B, prec, s, a->dxq[0]));     // Gc: scratch now
+    EXORL_TRY(mlp_backward_many(a->critic.head, 2, st.Pc, st.Gc, a->xq_c, FA, B, prec, s, a->dxq[0]));     // Gc: scratch now
     hipLaunchKernelGGL(add_cols_kernel, dim3(grid1((int64_t)B * A)), dim3(256), 0, s, a->dxq[0], (int64_t)FA, (const float*)nullptr, (int64_t)FA, F, A, a->dmu, B);
     hipLaunchKernelGGL(dpre_kernel, dim3(grid1((int64_t)B * A)), dim3(256), 0, s, a->dmu, a->mu_o, pol.dact[2], (int64_t)B * A);
     EXORL_LAUNCH_CHECK();
-    EXORL_TRY(mlp_backward(pol, Pa, Ga, a->ta_o.h, F, B, a->dh, prec, s));
-    return trunk_backward(a, a->actor, Pa, Ga, a->feat_o, mt, B, a->ta_o, a->dh, nullptr, prec, s);
+    EXORL_TRY(mlp_backward(pol, st.Pa, st.Ga, a->ta_o.h, F, B, a->dh, prec, s));
+    return trunk_backward(a, a->actor, st.Pa, st.Ga, a->feat_o, st.mt, B, a->ta_o, a->dh, nullptr, prec, s);
 }
 
 // Phase 2: actor_opt step and the critic's soft update (ddpg.py:326-327).
-static int pphase2(exorl_pixel_agent* a, hipStream_t s) {
-    EXORL_TRY(padam(a, 1, a->actor.total, nullptr, s));
-    return soft_update(a->flat[2][0], a->flat[3][0], a->critic.total, a->cfg.tau, s);
+static int pphase2(exorl_pixel_agent* a, const PixStep& st) {
+    EXORL_TRY(padam(a, 1, a->actor.total, nullptr, st.s));
+    return soft_update(st.Pc, st.Pt, a->critic.total, a->cfg.tau, st.s);
+}
+
+// phase -> the exchange behind it: the table in the header
+static int pixel_phase(exorl_pixel_agent* a, const PixStep& st, int32_t phase, int32_t* next) {
+    switch (phase) {
+        case 0: *next = EXORL_PIXEL_XCHG_CRITIC_GRAD; return pphase0(a, st);
+        case 1: *next = EXORL_PIXEL_XCHG_ACTOR_GRAD; return pphase1(a, st);
+        case 2: *next = -1; return pphase2(a, st);
+    }
+    set_error("pixel_agent_update_phase: phase %d out of range (0..2)", phase);
+    return 2;
 }
 
 }  // namespace exorl
 
 extern "C" {
 
-int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next,
-                                   const float* noise_c, const float* noise_a, void* stream) {
-    EXORL_REQUIRE(a && stddev > 0.f, "pixel_agent_update_phase: bad arguments");
-    hipStream_t s = as_stream(stream);
-    switch (phase) {
-        case 0: return pphase0(a, stddev, shifts_obs, shifts_next, noise_c, nullptr, s);
-        case 1: return pphase1(a, stddev, noise_a, s);
-        case 2: return pphase2(a, s);
-    }
-    set_error("pixel_agent_update_phase: phase %d out of range (0..2)", phase);
-    return 2;
+int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, const exorl_pixel_step* step, int32_t* next_exchange, void* stream) {
+    EXORL_REQUIRE(next_exchange, "pixel_agent_update_phase: null next_exchange");
+    *next_exchange = -1;
+    PixStep st;
+    EXORL_TRY(make_pix_step(a, step, false, stream, "pixel_agent_update_phase", &st));
+    return pixel_phase(a, st, phase, next_exchange);
 }
 
-int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t* shifts_obs, const int32_t* shifts_next, const float* noise_c,
-                             const float* noise_a, void* stream) {
-    EXORL_REQUIRE(a && stddev > 0.f, "pixel_agent_update: bad arguments");
+int exorl_pixel_agent_update(exorl_pixel_agent_t* a, const exorl_pixel_step* step, void* stream) {
+    PixStep st;
+    EXORL_TRY(make_pix_step(a, step, true, stream, "pixel_agent_update", &st));
     EXORL_REQUIRE(a->world == 1 || a->comm, "pixel_agent_update: world_size=%d needs a communicator (exorl_pixel_agent_set_comm), or drive "
-                  "exorl_pixel_agent_update_phase and all-reduce exorl_pixel_agent_grad_buffer 0 / 1 between the phases yourself", a->world);
-    hipStream_t s = as_stream(stream);
-    EXORL_TRY(pphase0(a, stddev, shifts_obs, shifts_next, noise_c, a->comm, s));
-    EXORL_TRY(pphase1(a, stddev, noise_a, s));
-    if (a->comm) EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[1][1], a->actor.total, s));
-    return pphase2(a, s);
-}
-
-// exchange 0: critic gradients, then (train_encoder) the encoder's, contiguous; exchange 1: actor gradients
-int exorl_pixel_agent_grad_buffer(exorl_pixel_agent_t* a, int32_t exchange, float** ptr, int64_t* n) {
-    EXORL_REQUIRE(a && ptr && n && exchange >= 0 && exchange <= 2, "pixel_agent_grad_buffer: bad arguments (exchange 0, 1 or 2)");
-    if (exchange == 0) { *ptr = a->flat[2][1]; *n = a->critic.total + (a->train_encoder ? a->enc_total : 0); }
-    else if (exchange == 2) { *ptr = a->flat[0][1]; *n = a->enc_total; }
-    else { *ptr = a->flat[1][1]; *n = a->actor.total; }
-    return 0;
+                  "exorl_pixel_agent_update_phase and all-reduce the exchange each phase names (exorl_pixel_agent_exchange) yourself", a->world);
+    return run_phases(a, st.comm, EXORL_PIXEL_XCHG_CRITIC_GRAD, st.s, [&](int32_t phase, int32_t* next) { return pixel_phase(a, st, phase, next); });
 }
 
 int exorl_pixel_agent_set_comm(exorl_pixel_agent_t* a, exorl_comm_t* c) {
@@ -794,7 +856,7 @@ int exorl_pixel_agent_act(exorl_pixel_agent_t* a, const unsigned char* obs_dev, 
                   a ? a->cfg.meta_dim : 0);
     hipStream_t s = as_stream(stream);
     const auto& c = a->cfg;
-    const int A = c.act_dim, F = c.feature_dim, prec = c.precision;
+    const int A = c.act_dim, F = c.feature_dim;
     const int64_t img = (int64_t)c.c_in * c.hw * c.hw;
     float* ws = a->act_ws;
     float* x = ws; ws += round_up(img, 64);
@@ -822,12 +884,7 @@ int exorl_pixel_agent_act(exorl_pixel_agent_t* a, const unsigned char* obs_dev, 
         return act_fast(f, s);
     }
     // B = 1 reuses the batch-sized trunk / policy buffers (act() is never called inside update())
-    EXORL_TRY(trunk_forward(a, a->actor, a->flat[1][0], feat, meta_dev, 1, a->ta_n, prec, s));
-    Mlp& pol = a->actor.head[0];
-    EXORL_TRY(mlp_forward(pol, a->flat[1][0], a->ta_n.h, F, 1, prec, s));
-    EXORL_CHECK_HIP(hipMemcpyAsync(a->mu_n, pol.act[2], sizeof(float) * A, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(tanh_kernel, dim3(1), dim3(256), 0, s, a->mu_n, (int64_t)A);
-    EXORL_LAUNCH_CHECK();
+    EXORL_TRY(policy_mean(a, feat, meta_dev, 1, a->ta_n, a->mu_n, nullptr, nullptr, s));
     if (eval_mode) {
         EXORL_CHECK_HIP(hipMemcpyAsync(action_out_dev, a->mu_n, sizeof(float) * A, hipMemcpyDeviceToDevice, s));
         return 0;

@@ -76,6 +76,18 @@ class _Phased:
         v = self._view(p.value, r.value * c.value)
         return v.view(r.value, c.value) if c.value > 1 else v
 
+    def exchange(self, xid):
+        """(device tensor, op) of exchange `xid` (exorl_intr_exchange, exorl_pixel_agent_exchange): op L.XCHG_SUM -> sum-all-reduce the
+        tensor in place; L.XCHG_GATHER -> the tensor is (world_size, count), rank r's row being its slot, all-gathered in rank order."""
+        p, n, dt, op = C.c_void_p(), C.c_int64(), C.c_int32(), C.c_int32()
+        L.check(self._fn('exchange')(self.h, xid, C.byref(p), C.byref(n), C.byref(dt), C.byref(op)))
+        slots = self.world_size if op.value == L.XCHG_GATHER else 1
+        words = 2 if dt.value == L.XCHG_F64 else 1
+        t = self._view(p.value, slots * n.value * words)
+        if dt.value == L.XCHG_F64:
+            t = t.view(torch.float64)
+        return (t.view(slots, n.value) if op.value == L.XCHG_GATHER else t), op.value
+
     def _run(self, one_call, steps, *a, **k):
         """one_call(*a, **k) on one rank, else its phases steps(*a, **k) with the exchanges run over torch.distributed."""
         if self.world_size == 1:
@@ -383,18 +395,6 @@ class IntrEngine(_Phased):
         """update(), or for a sharded module its phases with the exchanges each one names."""
         self._run(self.update, self.update_steps, *a, **k)
 
-    def exchange(self, xid):
-        """(device tensor, op) of exchange `xid`: op L.XCHG_SUM -> sum-all-reduce the tensor in place; L.XCHG_GATHER -> the tensor is
-        (world_size, count), rank r's row being its slot, all-gathered in rank order."""
-        p, n, dt, op = C.c_void_p(), C.c_int64(), C.c_int32(), C.c_int32()
-        L.check(self.lib.exorl_intr_exchange(self.h, xid, C.byref(p), C.byref(n), C.byref(dt), C.byref(op)))
-        slots = self.world_size if op.value == L.XCHG_GATHER else 1
-        words = 2 if dt.value == L.XCHG_F64 else 1
-        t = self._view(p.value, slots * n.value * words)
-        if dt.value == L.XCHG_F64:
-            t = t.view(torch.float64)
-        return (t.view(slots, n.value) if op.value == L.XCHG_GATHER else t), op.value
-
     def metrics_raw(self):
         host = np.zeros(L.N_INTR_METRICS, np.float32)
         L.check(self.lib.exorl_intr_metrics(self.h, host.ctypes.data, L.current_stream()))
@@ -428,9 +428,13 @@ def run_exchange(buf, op, rank=None, dist=None):
 
 def phase_steps(phase_fn, exchange_fn):
     """The steps of a call whose phases name their own exchange: phase_fn(0), phase_fn(1), ... each return the exchange id to run before
-    the next phase (-1: done), and exchange_fn(id) -> (buffer, op) names its buffer."""
+    the next phase (-1: done), or (id, value), and exchange_fn(id) -> (buffer, op) names its buffer. Returns the last phase's value."""
     phase = 0
-    while (xid := phase_fn(phase)) >= 0:
+    while True:
+        out = phase_fn(phase)
+        xid, value = out if isinstance(out, tuple) else (out, None)
+        if xid < 0:
+            return value
         yield exchange_fn(xid)
         phase += 1
 
@@ -506,36 +510,34 @@ class PixelEngine(_Phased):
     def _i32(self, x):
         return None if x is None else torch.as_tensor(np.ascontiguousarray(x, np.int32)).to(self.device)
 
-    def _update_args(self, shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded):
+    def _update_args(self, stddev, shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded):
+        """The call's exorl_pixel_step: keep_augmented reuses the images augment() made, keep_encoded also the encodings of the last
+        encode(0) / encode(1); a keep flag leaves the shifts out (they are read by a fresh augmentation only)."""
+        images = L.PIXEL_IMAGES_ENCODED if keep_encoded else L.PIXEL_IMAGES_AUGMENTED if keep_augmented else L.PIXEL_IMAGES_FRESH
         f32 = lambda x: None if x is None else self._f(x)
-        ts = [self._i32(shifts_obs), self._i32(shifts_next), f32(noise_critic), f32(noise_actor)]
-        ptrs = [L.ptr(t) for t in ts]
-        if keep_encoded:                    # reuse the encodings of the last encode(0) / encode(1) (sentinel pointer, see the header)
-            ptrs[0] = C.c_void_p(-2)
-        elif keep_augmented:                # reuse the images exorl_pixel_agent_augment made
-            ptrs[0] = C.c_void_p(-1)
-        self._keep_u = ts
-        return ptrs
+        shifts = [self._i32(shifts_obs), self._i32(shifts_next)] if images == L.PIXEL_IMAGES_FRESH else [None, None]
+        self._keep_u = ts = shifts + [f32(noise_critic), f32(noise_actor)]
+        return C.byref(L.PixelStep(stddev, images, *[L.ptr(t) for t in ts]))
 
     def update(self, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False, keep_encoded=False):
-        ptrs = self._update_args(shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
-        L.check(self.lib.exorl_pixel_agent_update(self.h, stddev, *ptrs, L.current_stream()))
+        step = self._update_args(stddev, shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
+        L.check(self.lib.exorl_pixel_agent_update(self.h, step, L.current_stream()))
 
     def update_phase(self, phase, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False,
                      keep_encoded=False):
-        """One of the three phases of update() (exorl_pixel_agent_update_phase): 0 -> grad_buffer(0) ready, 1 -> grad_buffer(1) ready, 2."""
-        ptrs = self._update_args(shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
-        L.check(self.lib.exorl_pixel_agent_update_phase(self.h, phase, stddev, *ptrs, L.current_stream()))
+        """One of the three phases of update() (exorl_pixel_agent_update_phase); returns the exchange to run before the next phase
+        (L.PIXEL_XCHG_*) or -1 when the step is complete."""
+        step = self._update_args(stddev, shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
+        nxt = C.c_int32()
+        L.check(self.lib.exorl_pixel_agent_update_phase(self.h, phase, step, C.byref(nxt), L.current_stream()))
+        return nxt.value
 
     def update_steps(self, stddev, shifts_obs=None, shifts_next=None, noise_critic=None, noise_actor=None, keep_augmented=False,
                      keep_encoded=False):
         """update() as its phases, for run_steps. Each rank runs the step on its rows and every mean in it is over the global batch, so
         the gradients are sum-all-reduced between the phases: the critic's (+ the encoder's), then the actor's."""
-        self.update_phase(0, stddev, shifts_obs, shifts_next, noise_critic, None, keep_augmented=keep_augmented, keep_encoded=keep_encoded)
-        yield self.grad_buffer(0), L.XCHG_SUM
-        self.update_phase(1, stddev, noise_actor=noise_actor)
-        yield self.grad_buffer(1), L.XCHG_SUM
-        self.update_phase(2, stddev)
+        a = (stddev, shifts_obs, shifts_next, noise_critic, noise_actor, keep_augmented, keep_encoded)
+        return phase_steps(lambda phase: self.update_phase(phase, *a), self.exchange)
 
     def run_update(self, *a, **k):
         """The DDPG pixel step on any world size, as AgentEngine.run_update."""
@@ -546,9 +548,7 @@ class PixelEngine(_Phased):
     def grad_buffer(self, exchange):
         """Device view of what a data-parallel step sum-all-reduces: 0 critic (+ encoder) gradients, 1 actor gradients, 2 the encoder's
         gradients of encoder_step."""
-        p, n = C.c_void_p(), C.c_int64()
-        L.check(self.lib.exorl_pixel_agent_grad_buffer(self.h, exchange, C.byref(p), C.byref(n)))
-        return self._view(p.value, n.value)
+        return self.exchange(exchange)[0]
 
     def set_comm(self, comm):
         """Attach an exorl_amd.comm.Comm of world_size ranks: update() then runs the data-parallel step in one call."""
@@ -570,14 +570,15 @@ class PixelEngine(_Phased):
         L.check(self.lib.exorl_pixel_agent_encoder_step(self.h, which, dfeat_ptr, opt, L.current_stream()))
 
     def encoder_step_phase(self, phase, which, dfeat_ptr, opt):
-        """encoder_step in two phases: 0 the backward pass (then sum-all-reduce grad_buffer(2)), 1 the optimiser step(s)."""
-        L.check(self.lib.exorl_pixel_agent_encoder_step_phase(self.h, which, dfeat_ptr, opt, phase, L.current_stream()))
+        """encoder_step in two phases: 0 the backward pass, 1 the optimiser step(s); returns the exchange to run before the next phase
+        (the encoder's gradients) or -1."""
+        nxt = C.c_int32()
+        L.check(self.lib.exorl_pixel_agent_encoder_step_phase(self.h, which, dfeat_ptr, opt, phase, C.byref(nxt), L.current_stream()))
+        return nxt.value
 
     def encoder_step_steps(self, which, dfeat_ptr, opt):
         """encoder_step() as its phases, for run_steps."""
-        self.encoder_step_phase(0, which, dfeat_ptr, opt)
-        yield self.grad_buffer(2), L.XCHG_SUM
-        self.encoder_step_phase(1, which, dfeat_ptr, opt)
+        return phase_steps(lambda phase: self.encoder_step_phase(phase, which, dfeat_ptr, opt), self.exchange)
 
     def run_encoder_step(self, *a):
         self._run(self.encoder_step, self.encoder_step_steps, *a)
@@ -659,30 +660,29 @@ class PixelEngine(_Phased):
         self._keep_r = sh
         return fp.value, ft.value
 
-    def rnd_features_phase(self, phase, shifts=None, clip_val=5.0):
-        """rnd_features in three phases: sum-all-reduce bn_partials() after phases 0 and 1; phase 2 returns the two feature pointers."""
-        fp, ft = C.c_void_p(), C.c_void_p()
+    def _rnd_features_phase(self, phase, shifts=None, clip_val=5.0):
+        """(exchange to run before the next phase or -1, the two feature pointers once phase 2 has run)"""
+        fp, ft, nxt = C.c_void_p(), C.c_void_p(), C.c_int32()
         if phase == 0:
             self._keep_r = self._i32(shifts)
         L.check(self.lib.exorl_pixel_agent_rnd_features_phase(self.h, phase, L.ptr(self._keep_r) if phase == 0 else None, clip_val,
-                                                              C.byref(fp), C.byref(ft), L.current_stream()))
-        return (fp.value, ft.value) if phase == 2 else None
+                                                              C.byref(fp), C.byref(ft), C.byref(nxt), L.current_stream()))
+        return nxt.value, ((fp.value, ft.value) if phase == 2 else None)
+
+    def rnd_features_phase(self, phase, shifts=None, clip_val=5.0):
+        """rnd_features in three phases: sum-all-reduce bn_partials() after phases 0 and 1; phase 2 returns the two feature pointers."""
+        return self._rnd_features_phase(phase, shifts, clip_val)[1]
 
     def rnd_features_steps(self, shifts=None, clip_val=5.0):
         """rnd_features() as its phases, for run_steps: the BatchNorm2d statistics are over every rank's frames."""
-        for phase in range(2):
-            self.rnd_features_phase(phase, shifts, clip_val)
-            yield self.bn_partials(), L.XCHG_SUM
-        return self.rnd_features_phase(2, None, clip_val)
+        return phase_steps(lambda phase: self._rnd_features_phase(phase, shifts, clip_val), self.exchange)
 
     def run_rnd_features(self, *a):
         return self._run(self.rnd_features, self.rnd_features_steps, *a)
 
     def bn_partials(self):
         """(c_in * chunks,) float64 device view of the BatchNorm2d partial sums the ranks add up between the rnd_features phases."""
-        p, n = C.c_void_p(), C.c_int64()
-        L.check(self.lib.exorl_pixel_agent_bn_partials(self.h, C.byref(p), C.byref(n)))
-        return self._view(p.value, 2 * n.value).view(torch.float64)
+        return self.exchange(L.PIXEL_XCHG_BN)[0]
 
     def meta_rows(self):
         """(batch, meta_dim) device view of the skill / task rows the trunks read (filled by the sampler or by the caller)."""

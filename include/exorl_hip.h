@@ -32,14 +32,16 @@
 extern "C" {
 #endif
 
-#define EXORL_ABI_VERSION 12     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
+#define EXORL_ABI_VERSION 13     /* 8 (round 3): EXORL_PREC_BF16X6, exorl_agent_act_host, exorl_debug_precision_override
                                     9: exorl_debug_gemm_stamps and exorl_debug_conv_stamps removed; exorl_gemm_tune keeps five bits
                                     10: exorl_pixel_cfg.world_size; exorl_pixel_agent_update_phase / _grad_buffer / _set_comm
                                     11: exorl_intr_cfg.world_size / rank; exorl_intr_update_phase / _exchange; exorl_pixel_agent_encoder_step_phase /
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
                                         exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights,
-                                        exorl_replay_set_frame_stack, exorl_agent_update_plan, exorl_replay_obs_moments, exorl_replay_set_obs_norm) */
+                                        exorl_replay_set_frame_stack, exorl_agent_update_plan, exorl_replay_obs_moments, exorl_replay_set_obs_norm)
+                                    13: exorl_pixel_step replaces the loose arguments of exorl_pixel_agent_update / _update_phase; the three phased pixel
+                                        calls return next_exchange; exorl_pixel_agent_exchange replaces _grad_buffer and _bn_partials */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -627,39 +629,62 @@ int exorl_pixel_agent_sync_target(exorl_pixel_agent_t* a, void* stream);       /
 int exorl_pixel_agent_batch_slots(exorl_pixel_agent_t* a, exorl_batch_out* out);   /* uint8 obs / next_obs rows for the HBM sampler */
 int exorl_pixel_agent_set_batch(exorl_pixel_agent_t* a, const unsigned char* obs_dev, const float* action_dev, const float* reward_dev,
                                 const float* discount_dev, const unsigned char* next_obs_dev, void* stream);
-/* One update() on the batch in the slots. shifts_*: (batch, 2) int32 RandomShiftsAug draws for obs / next_obs or null -> Philox;
- * noise_*: (batch, act_dim) standard normals for the TruncatedNormal draws (critic target first, actor second) or null. */
-int exorl_pixel_agent_update(exorl_pixel_agent_t* a, float stddev, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev,
-                             const float* noise_critic_dev, const float* noise_actor_dev, void* stream);
-/* The same update as three phases, for data parallelism (world_size > 1; exorl_pixel_agent_update then refuses without a communicator).
- * Arguments as exorl_pixel_agent_update's; each phase reads only its own (phase 0 the shifts and noise_critic, phase 1 noise_actor).
- *   phase 0 -> augmentation (or the -1 / -2 sentinels), encoding, critic forward + backward, encoder backward when it trains:
- *              exchange 0 ready (sum-all-reduce it)
- *   phase 1 -> critic Adam, encoder Adam, actor forward + backward on the stepped critic: exchange 1 ready (sum-all-reduce it)
- *   phase 2 -> actor Adam, critic soft update
- * With world_size == 1, phases 0, 1, 2 back to back are exorl_pixel_agent_update bit for bit. */
-int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, float stddev, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev,
-                                   const float* noise_critic_dev, const float* noise_actor_dev, void* stream);
-/* The gradients a rank contributes: exchange 0 = the critic's then (set_train_encoder(1)) the encoder's, one contiguous range; exchange 1 = the
- * actor's; exchange 2 = the encoder's alone (exorl_pixel_agent_encoder_step_phase). *n in floats (padding included: it stays zero). */
-int exorl_pixel_agent_grad_buffer(exorl_pixel_agent_t* a, int32_t exchange, float** ptr_dev, int64_t* n);
+/* One update() on the batch in the slots. `images` says what the handle's image buffers hold when the call starts; shifts_*: (batch, 2)
+ * int32 RandomShiftsAug draws for obs / next_obs or null -> Philox (EXORL_PIXEL_IMAGES_FRESH only: the other two refuse shifts);
+ * noise_*: (batch, act_dim) standard normals for the TruncatedNormal draws (critic target first, actor second) or null -> Philox. */
+#define EXORL_PIXEL_IMAGES_FRESH     0  /* augment with shifts_* (null: Philox), then encode */
+#define EXORL_PIXEL_IMAGES_AUGMENTED 1  /* the images exorl_pixel_agent_augment left; shifts_* must be null */
+#define EXORL_PIXEL_IMAGES_ENCODED   2  /* also the encodings of encode(0,0)/(1,0); needs set_train_encoder(0); shifts_* must be null */
+typedef struct exorl_pixel_step {
+    float stddev; int32_t images;
+    const int32_t *shifts_obs_dev, *shifts_next_dev;
+    const float *noise_critic_dev, *noise_actor_dev;
+} exorl_pixel_step;
+int exorl_pixel_agent_update(exorl_pixel_agent_t* a, const exorl_pixel_step* step, void* stream);
+/* The phased calls, for data parallelism (world_size > 1: exorl_pixel_agent_update refuses without a communicator, the other two one-call
+ * forms refuse). Call phase 0, 1, ... with the same arguments; each returns in *next_exchange the exchange (EXORL_PIXEL_XCHG_*) the ranks
+ * run before the next phase, or -1 when the call is complete. With world_size 1 the phases back to back are the one-call form bit for bit.
+ *   call                 phase  work                                                                                   next_exchange
+ *   _update_phase        0      augmentation and encoding as `images` says, critic forward + backward, encoder        CRITIC_GRAD
+ *                               backward when it trains (reads shifts_*, noise_critic)
+ *                        1      critic Adam, encoder Adam, actor forward + backward on the stepped critic             ACTOR_GRAD
+ *                               (reads noise_actor)
+ *                        2      actor Adam, critic soft update                                                         -1
+ *   _encoder_step_phase  0      encoder backward from dfeat_dev                                                        ENCODER_GRAD
+ *                        1      the optimiser step(s) `opt` chooses (dfeat_dev unused)                                 -1
+ *   _rnd_features_phase  0      augmentation (reads shifts_dev), per-channel sums of the BatchNorm2d input             BN
+ *                        1      mean, per-channel sums of the centred squares                                          BN
+ *                        2      normalisation over batch * world_size images, running statistics, both encodings      -1
+ *                               (fills the feature pointers)
+ * exorl_pixel_agent_exchange names the buffer of an exchange; every one is a sum all-reduce in place (*op = EXORL_XCHG_SUM):
+ *   CRITIC_GRAD   the critic's gradients, then (set_train_encoder(1)) the encoder's: one contiguous range            EXORL_XCHG_F32
+ *   ACTOR_GRAD    the actor's gradients                                                                               EXORL_XCHG_F32
+ *   ENCODER_GRAD  the encoder's gradients alone                                                                       EXORL_XCHG_F32
+ *   BN            c_in * 128 partial sums of the BatchNorm2d statistics                                               EXORL_XCHG_F64
+ * *count in elements (padding of the gradient ranges included: it stays zero). */
+#define EXORL_PIXEL_XCHG_CRITIC_GRAD  0
+#define EXORL_PIXEL_XCHG_ACTOR_GRAD   1
+#define EXORL_PIXEL_XCHG_ENCODER_GRAD 2
+#define EXORL_PIXEL_XCHG_BN           3
+int exorl_pixel_agent_update_phase(exorl_pixel_agent_t* a, int32_t phase, const exorl_pixel_step* step, int32_t* next_exchange, void* stream);
+int exorl_pixel_agent_exchange(exorl_pixel_agent_t* a, int32_t id, void** ptr_dev, int64_t* count, int32_t* dtype /* EXORL_XCHG_F32 / _F64 */,
+                               int32_t* op /* EXORL_XCHG_SUM */);
 /* Attach a communicator of world_size ranks (NULL detaches): exorl_pixel_agent_update then all-reduces both exchanges between its phases on
  * `stream`. The critic's part of exchange 0 is reduced on a second stream while the encoder's backward pass runs. */
 int exorl_pixel_agent_set_comm(exorl_pixel_agent_t* a, exorl_comm_t* c);
 int exorl_pixel_agent_metrics(exorl_pixel_agent_t* a, float* host_out /* EXORL_N_METRICS */, void* stream);
 /* Primitives for agents that put a module between augmentation and the DDPG step (Proto on pixels, proto.py:159-207): augment once,
  * encode with the online or the target encoder, push a feature gradient back through the encoder with a chosen optimiser state,
- * maintain encoder_target; exorl_pixel_agent_update with shifts_obs_dev == (const int32_t*)-1 then reuses the augmented batch, and with
- * (const int32_t*)-2 also the encodings the last exorl_pixel_agent_encode(0, 0) / (1, 0) calls left (what the agents that step the encoder
- * through their own module hand the critic: computed before that step, detached — icm.py:97-131, diayn.py:137-170; needs
+ * maintain encoder_target; exorl_pixel_agent_update with images = EXORL_PIXEL_IMAGES_AUGMENTED then reuses the augmented batch, and with
+ * EXORL_PIXEL_IMAGES_ENCODED also the encodings the last exorl_pixel_agent_encode(0, 0) / (1, 0) calls left (what the agents that step the
+ * encoder through their own module hand the critic: computed before that step, detached — icm.py:97-131, diayn.py:137-170; needs
  * set_train_encoder(0)). */
 int exorl_pixel_agent_augment(exorl_pixel_agent_t* a, const int32_t* shifts_obs_dev, const int32_t* shifts_next_dev, void* stream);
 int exorl_pixel_agent_encode(exorl_pixel_agent_t* a, int32_t which, int32_t target, float** feat_out_dev, void* stream);
 int exorl_pixel_agent_encoder_step(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt /* 0 encoder_opt, 1 second state, 2 both */, void* stream);
-/* The same in two phases (world_size > 1: exorl_pixel_agent_encoder_step then refuses): phase 0 the backward pass into exchange 2 of
- * exorl_pixel_agent_grad_buffer (sum-all-reduce it), phase 1 the optimiser step(s) `opt` chooses (dfeat_dev unused). With world_size 1 the two
- * phases are exorl_pixel_agent_encoder_step bit for bit. */
-int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, int32_t phase, void* stream);
+/* The same in two phases (the table above). */
+int exorl_pixel_agent_encoder_step_phase(exorl_pixel_agent_t* a, int32_t which, float* dfeat_dev, int32_t opt, int32_t phase, int32_t* next_exchange,
+                                         void* stream);
 int exorl_pixel_agent_encoder_target(exorl_pixel_agent_t* a, float tau, int32_t init, void* stream);
 /* RND on pixels (rnd.py:26-27,35-39,47-53): x = clamp(BatchNorm2d(RandomShiftsAug(obs)), +-clip_val), then the agent's encoder on x
  * (*feat_pred_dev; exorl_pixel_agent_encoder_step(0, dfeat, 2) continues its backward pass and steps the encoder with rnd_opt's state and
@@ -667,13 +692,9 @@ int exorl_pixel_agent_encoder_target(exorl_pixel_agent_t* a, float tau, int32_t 
  * augmentation and updates the BatchNorm running statistics, as RND.forward does. */
 int exorl_pixel_agent_rnd_features(exorl_pixel_agent_t* a, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev, float** feat_target_dev,
                                    void* stream);
-/* The same in three phases (world_size > 1: exorl_pixel_agent_rnd_features then refuses): phase 0 augments and sums the BatchNorm2d inputs,
- * phase 1 the centred squares, each into the per-channel double partials of exorl_pixel_agent_bn_partials (sum-all-reduce them after each);
- * phase 2 normalises over batch * world_size images, updates the running statistics and encodes (the feature pointers are read in phase 2
- * only, shifts_dev in phase 0 only). With world_size 1 the three phases are exorl_pixel_agent_rnd_features bit for bit. */
+/* The same in three phases (the table above). */
 int exorl_pixel_agent_rnd_features_phase(exorl_pixel_agent_t* a, int32_t phase, const int32_t* shifts_dev, float clip_val, float** feat_pred_dev,
-                                         float** feat_target_dev, void* stream);
-int exorl_pixel_agent_bn_partials(exorl_pixel_agent_t* a, void** ptr_dev, int64_t* n_doubles);
+                                         float** feat_target_dev, int32_t* next_exchange, void* stream);
 int exorl_pixel_agent_bn_state(exorl_pixel_agent_t* a, void** ptr_dev, int64_t* n_floats);   /* running_mean[c] running_var[c] num_batches_tracked */
 int exorl_pixel_agent_encoder_target_ptr(exorl_pixel_agent_t* a, void** ptr_dev);
 /* Whole-agent pickling (pretrain.py:293-300): steps3 = {Adam step count of critic_opt/actor_opt, of proto_opt's encoder state, of encoder_opt},

@@ -107,4 +107,4 @@ def test_constants_and_declaration_match_the_header():
     assert ids == {'CRITIC_GRAD': _lib.AGENT_XCHG_CRITIC_GRAD, 'STATS': _lib.AGENT_XCHG_STATS, 'ACTOR_GRAD': _lib.AGENT_XCHG_ACTOR_GRAD}
     assert ids == {'CRITIC_GRAD': CRITIC_GRAD, 'STATS': STATS, 'ACTOR_GRAD': ACTOR_GRAD}
     assert 'int exorl_agent_update_plan(const exorl_agent_cfg* cfg, int32_t* phases, int32_t* exchanges, int32_t capacity, int32_t* n);' in h
-    assert re.search(r'#define EXORL_ABI_VERSION 12\b', h) and 'exorl_agent_update_plan' in h.split('const char* exorl_last_error')[0]
+    assert re.search(r'#define EXORL_ABI_VERSION 13\b', h) and 'exorl_agent_update_plan' in h.split('const char* exorl_last_error')[0]

@@ -56,9 +56,9 @@ def test_the_export_is_in_the_library_the_header_and_the_ctypes_table():
 
 def test_abi_version_is_unchanged_and_the_header_names_the_export():
     from exorl_amd import _lib
-    assert _lib.load().exorl_abi_version() == 12
+    assert _lib.load().exorl_abi_version() == 13
     header = (ROOT / 'include' / 'exorl_hip.h').read_text()
-    version = re.search(r'#define EXORL_ABI_VERSION 12\s+/\*(.*?)\*/', header, re.S)
+    version = re.search(r'#define EXORL_ABI_VERSION 13\s+/\*(.*?)\*/', header, re.S)
     assert version and NAME in version.group(1)
 
 

@@ -29,8 +29,8 @@ def test_symbols_declared_exported_and_bound(lib):
 
 def test_abi_version_is_unchanged(lib):
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12
-    assert re.search(r'#define EXORL_ABI_VERSION 12\b', (ROOT / 'include' / 'exorl_hip.h').read_text())
+    assert lib.exorl_abi_version() == 13
+    assert re.search(r'#define EXORL_ABI_VERSION 13\b', (ROOT / 'include' / 'exorl_hip.h').read_text())
 
 
 def test_window_bytes(lib):

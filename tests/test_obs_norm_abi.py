@@ -37,8 +37,8 @@ def test_abi_version_and_replay_cfg_are_unchanged(lib):
     from exorl_amd import _lib as L
     header = (ROOT / 'include' / 'exorl_hip.h').read_text()
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12
-    assert re.search(r'#define EXORL_ABI_VERSION 12\b', header)
+    assert lib.exorl_abi_version() == 13
+    assert re.search(r'#define EXORL_ABI_VERSION 13\b', header)
     comment = header[header.index('#define EXORL_ABI_VERSION'):header.index('const char* exorl_last_error')]
     for name in NAMES:
         assert name in comment                       # the version-12 comment names the additive exports

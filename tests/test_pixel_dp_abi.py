@@ -5,7 +5,7 @@ import re
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-NEW = ['exorl_pixel_agent_update_phase', 'exorl_pixel_agent_grad_buffer', 'exorl_pixel_agent_set_comm']
+NEW = ['exorl_pixel_agent_update_phase', 'exorl_pixel_agent_exchange', 'exorl_pixel_agent_set_comm']
 
 
 def _header_pixel_cfg_fields():
@@ -34,8 +34,8 @@ def test_prototypes_declare_the_pixel_dp_entry_points():
     for s in NEW:
         assert s in _lib.PROTOTYPES, s
     res, args = _lib.PROTOTYPES['exorl_pixel_agent_update_phase']
-    assert res is ctypes.c_int and len(args) == 8 and args[1] is ctypes.c_int32 and args[2] is ctypes.c_float
-    assert len(_lib.PROTOTYPES['exorl_pixel_agent_grad_buffer'][1]) == 4
+    assert res is ctypes.c_int and len(args) == 5 and args[1] is ctypes.c_int32 and args[2] is ctypes.POINTER(_lib.PixelStep)
+    assert len(_lib.PROTOTYPES['exorl_pixel_agent_exchange'][1]) == 6
     assert len(_lib.PROTOTYPES['exorl_pixel_agent_set_comm'][1]) == 2
 
 

@@ -7,7 +7,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 NEW = ['exorl_intr_update_phase', 'exorl_intr_exchange', 'exorl_pixel_agent_encoder_step_phase', 'exorl_pixel_agent_rnd_features_phase',
-       'exorl_pixel_agent_bn_partials']
+       'exorl_pixel_agent_exchange']
 
 
 def _header():
@@ -33,7 +33,7 @@ def test_library_exports_the_module_dp_entry_points():
     for s in NEW:
         assert hasattr(lib, s), f'{s} is not exported by libexorl_hip.so'
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12
+    assert lib.exorl_abi_version() == 13
 
 
 def test_prototypes_declare_the_module_dp_entry_points():
@@ -43,9 +43,9 @@ def test_prototypes_declare_the_module_dp_entry_points():
     res, args = _lib.PROTOTYPES['exorl_intr_update_phase']
     assert res is ctypes.c_int and len(args) == 6 and args[2] is ctypes.c_int32 and args[3] is ctypes.c_int32
     assert len(_lib.PROTOTYPES['exorl_intr_exchange'][1]) == 6
-    assert len(_lib.PROTOTYPES['exorl_pixel_agent_encoder_step_phase'][1]) == 6
-    assert len(_lib.PROTOTYPES['exorl_pixel_agent_rnd_features_phase'][1]) == 7
-    assert len(_lib.PROTOTYPES['exorl_pixel_agent_bn_partials'][1]) == 3
+    assert len(_lib.PROTOTYPES['exorl_pixel_agent_encoder_step_phase'][1]) == 7
+    assert len(_lib.PROTOTYPES['exorl_pixel_agent_rnd_features_phase'][1]) == 8
+    assert len(_lib.PROTOTYPES['exorl_pixel_agent_exchange'][1]) == 6
 
 
 def test_intr_cfg_matches_the_header():

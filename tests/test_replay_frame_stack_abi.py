@@ -32,7 +32,7 @@ def test_abi_version_and_cfg_layout_are_unchanged(lib):
     from exorl_amd import _lib as L
     header = (ROOT / 'include' / 'exorl_hip.h').read_text()
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12 and re.search(r'#define EXORL_ABI_VERSION 12\b', header)
+    assert lib.exorl_abi_version() == 13 and re.search(r'#define EXORL_ABI_VERSION 13\b', header)
     comment = header[header.index('#define EXORL_ABI_VERSION'):header.index('const char* exorl_last_error')]
     assert 'exorl_replay_set_frame_stack' in comment          # the version-12 comment names the additive export
     assert [f[0] for f in L.ReplayCfg._fields_] == ['obs_bytes', 'act_dim', 'meta_dim', 'max_episodes', 'capacity_rows']

@@ -34,8 +34,8 @@ def test_symbol_declared_exported_and_bound(lib):
 def test_abi_version_is_unchanged(lib):
     header = (ROOT / 'include' / 'exorl_hip.h').read_text()
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12
-    assert re.search(r'#define EXORL_ABI_VERSION 12\b', header)
+    assert lib.exorl_abi_version() == 13
+    assert re.search(r'#define EXORL_ABI_VERSION 13\b', header)
     comment = header[header.index('#define EXORL_ABI_VERSION'):header.index('const char* exorl_last_error')]
     assert 'exorl_replay_set_weights' in comment          # the version-12 comment names the additive export
 

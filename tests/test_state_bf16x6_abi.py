@@ -38,7 +38,7 @@ def test_binding_matches_the_header():
 
 def test_abi_version_is_unchanged(lib):
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12
+    assert lib.exorl_abi_version() == 13
 
 
 # (kind, O, A, H, B, precision) -> exorl_agent_workspace_bytes computed on the parent commit

@@ -102,4 +102,4 @@ def test_abi_version_is_unchanged():
     from exorl_amd import build
     lib = ctypes.CDLL(str(build.build(force=False, verbose=False)))
     lib.exorl_abi_version.restype = ctypes.c_int
-    assert lib.exorl_abi_version() == 12
+    assert lib.exorl_abi_version() == 13

@@ -55,8 +55,8 @@ def test_struct_matches_the_header():
 
 def test_abi_version_is_unchanged(lib):
     header = (ROOT / 'include' / 'exorl_hip.h').read_text()
-    assert lib.exorl_abi_version() == 12
-    m = re.search(r'#define EXORL_ABI_VERSION 12\b.*?\*/', header, re.S)
+    assert lib.exorl_abi_version() == 13
+    m = re.search(r'#define EXORL_ABI_VERSION 13\b.*?\*/', header, re.S)
     assert m and NAME in m.group(0).split('no version change')[1]
 
 

@@ -6,6 +6,7 @@ must leave every line equal). Run it from each tree in a fresh process per listi
     python tools/agent_digests.py part3 OUT.txt                the five two-process gloo workers of tests/, every array and json they save
     python tools/agent_digests.py grid OUT.txt                 one update() of every case of the state agents' kernel dispatch grids, per route
     python tools/agent_digests.py modes OUT.txt                one state-agent handle through every driver of its step in turn (see modes)
+    python tools/agent_digests.py pixel_modes OUT.txt          one pixel handle through every driver of its step in turn (see pixel_modes)
     python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
 
 A listing has one line per entry, `case what value`; a value is the first 32 hex digits of a sha256 or a float.hex(). Inputs come from
@@ -370,6 +371,48 @@ def modes(out):
     listing(out, body)
 
 
+def pixel_modes(out):
+    """Plain DDPG and ICM on pixels, one handle each per precision, driven in turn by the three phased calls, a one-call update(), a
+    one-call step on kept images, one on kept encodings and a one-call update() again, with the digests after every driver: what one call
+    decides for its own launches (image mode, phase, communicator) must not reach the next one's. Uses only calls that trees from before
+    exorl_pixel_step have, so the same file runs against either library."""
+    def body(emitter):
+        for kind in ('ddpg', 'icm'):
+            for precision in PRECISIONS['pixels']:
+                name = f'pixel_modes/{kind}/{precision}'
+                emit = emitter(name)
+                ag = build(kind, 'pixels', True, precision)
+                eng, it, stddev = ag.engine, arena(kind, 'pixels'), ag._stddev(0)
+
+                def after(tag):
+                    emit(f'{tag}.metrics_raw', sha(eng.metrics_raw()))
+                    digest(ag, lambda what, value: emit(f'{tag}.{what}', value))
+                ag._load_batch(it)
+                images = ag._pix_before_step()          # ICM: its module and encoder step, then keep_encoded
+                eng.update_phase(0, stddev, **images)
+                eng.update_phase(1, stddev)
+                eng.update_phase(2, stddev)
+                ag._pix_after_step()
+                after('phased')
+                emit_metrics(emit, 'one_call', ag.update(it, 1))
+                after('one_call')
+                ag._load_batch(it)
+                eng.augment()
+                eng.update(stddev, keep_augmented=True)
+                after('keep_augmented')
+                ag._load_batch(it)
+                eng.augment()
+                eng.encode(0), eng.encode(1)
+                eng.set_train_encoder(False)
+                eng.update(stddev, keep_encoded=True)
+                eng.set_train_encoder(kind == 'ddpg')
+                after('keep_encoded')
+                emit_metrics(emit, 'one_call_again', ag.update(it, 4))
+                after('one_call_again')
+                print(name, flush=True)
+    listing(out, body)
+
+
 def compare(a, b):
     la, lb = Path(a).read_text().splitlines(), Path(b).read_text().splitlines()
     key = lambda l: l.rsplit(' ', 1)[0]
@@ -384,4 +427,4 @@ def compare(a, b):
 
 if __name__ == '__main__':
     cmd, args = sys.argv[1], sys.argv[2:]
-    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'compare': compare}[cmd](*args))
+    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'pixel_modes': pixel_modes, 'compare': compare}[cmd](*args))

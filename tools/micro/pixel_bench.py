@@ -1,6 +1,6 @@
 """update()/s at BASELINE config 4 shapes (Proto or plain DDPG on jaco pixels (3,84,84) uint8, A=9, batch 1024, nstep 3) on one MI355X.
 
-    python tools/micro/pixel_bench.py [batch=1024] [proto|ddpg|rnd|icm|icm_apt|disagreement|diayn|aps|smm] [fp32|bf16x3|bf16]
+    python tools/micro/pixel_bench.py [batch=1024] [proto|ddpg|rnd|icm|icm_apt|disagreement|diayn|aps|smm] [fp32|bf16x3|bf16] [timed updates=10]
 
 Not the bench.py metric (that is TD3+BC on states); the numbers go to DESIGN.md's pixel section."""
 import sys
@@ -63,7 +63,7 @@ else:
 for i in range(3):
     ag.update(it, 2 * i)
 torch.cuda.synchronize()
-n = 10
+n = int(sys.argv[4]) if len(sys.argv) > 4 else 10
 t0 = time.perf_counter()
 for i in range(n):
     ag.update(it, 2 * (i + 3))
