@@ -22,6 +22,8 @@ NET_ACTOR, NET_CRITIC, NET_CRITIC_TARGET = 0, 1, 2
 T_PARAM, T_GRAD, T_ADAM_M, T_ADAM_V = 0, 1, 2, 3
 M_BATCH_REWARD, M_CRITIC_TARGET_Q, M_CRITIC_Q1, M_CRITIC_Q2, M_CRITIC_LOSS, M_ACTOR_LOSS, M_ACTOR_LOGPROB = range(7)
 N_METRICS = 16
+E_BC_SQ, E_Q_DATA, E_Q_PI, E_Q1_ERR, E_Q2_ERR, E_TARGET_Q, E_ROWS = range(7)        # exorl_agent_evaluate's window (EXORL_E_*)
+N_EVAL = 7
 INTR_RND, INTR_ICM, INTR_ICM_APT, INTR_DISAGREEMENT, INTR_DIAYN, INTR_PROTO, INTR_APS, INTR_SMM = 0, 1, 2, 3, 4, 5, 6, 7
 IM_LOSS, IM_INTR_REWARD, IM_EXTR_REWARD, IM_RMS_MEAN, IM_RMS_STD, IM_ACC, IM_ENT_REWARD, IM_SF_REWARD = range(8)
 N_INTR_METRICS = 8
@@ -179,6 +181,10 @@ PROTOTYPES = {
     'exorl_agent_metric_window_bytes': (c_size_t, [P(AgentCfg)]),
     'exorl_agent_set_metric_window': (C.c_int, [c_void_p, c_void_p, c_size_t]),
     'exorl_agent_metric_window_read': (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    'exorl_agent_eval_bytes': (c_size_t, [P(AgentCfg)]),
+    'exorl_agent_set_eval': (C.c_int, [c_void_p, c_void_p, c_size_t]),
+    'exorl_agent_evaluate': (C.c_int, [c_void_p, c_void_p]),
+    'exorl_agent_eval_read': (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     'exorl_agent_set_parallel_branches': (C.c_int, [c_void_p, c_int32]),
     'exorl_agent_opt_steps': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_agent_set_opt_steps': (C.c_int, [c_void_p, c_int64, c_int64]),

@@ -329,6 +329,40 @@ class _AgentBase:
         m['metric_steps'] = steps
         return m
 
+    # -- held-out validation: forward-only passes over batches the agent does not train on
+    def evaluate(self, replay_iter, num_batches=1, gather=None):
+        """Validation without an environment: `num_batches` batches are pulled from `replay_iter` the way update() pulls its own
+        (sample_into of an HBM iterator such as iter(loader).holdout, else next() of any iterator of 5-tuples) and each goes through one
+        forward-only pass (AgentEngine.evaluate): no parameter, optimiser state, counter or noise draw moves, a captured graph and its bound
+        iterator are not disturbed, and update() continues bit for bit as if evaluate() had not run. One device-to-host copy, at the end.
+        Returns means over the rows seen, with mu the policy's mean action and y = r + discount * min_i Q'_i(s', mu(s')):
+          val_bc_mse            mean over rows and action columns of (mu(s) - a)^2: does the policy still fit actions it has not trained on
+          val_q_data, val_q_pi  mean min_i Q_i(s, a) and mean min_i Q_i(s, mu(s))
+          val_q_gap             val_q_pi - val_q_data: is the critic's value of the policy's actions running away from the data's
+          val_critic_loss       mse(Q_1(s, a), y) + mse(Q_2(s, a), y): the training key's definition with a noise-free target
+          val_critic_target_q   mean y
+          val_rows              rows behind the means
+        BC returns val_bc_mse and val_rows only. Under an initialised torch.distributed every rank evaluates its own batches and the
+        sums and row counts are added over the ranks before dividing (all_gather_object of a handful of doubles; `gather`, a callable own
+        (sums, rows) -> [(sums, rows) of rank 0, of rank 1, ...], replaces that exchange). Not between the phases of a step."""
+        if self.KIND not in EVAL_KINDS or getattr(self, 'obs_type', 'states') == 'pixels' or hasattr(self, 'intr'):
+            raise NotImplementedError(f'{type(self).__name__}.evaluate(): the forward-only validation pass covers TD3BCAgent, TD3Agent, '
+                                      'CRRAgent, CQLAgent and BCAgent on state observations')
+        eng = self.engine
+        if getattr(eng, '_eval', None) is None:      # the window is the engine's own torch buffer: nothing of it is pickled
+            eng.set_eval()
+        for _ in range(int(num_batches)):
+            self._load_batch(replay_iter)
+            eng.evaluate()
+        own = eng.eval_read(reset=True)
+        if gather is None and self.world_size != 1:
+            def gather(part):
+                out = [None] * torch.distributed.get_world_size()
+                torch.distributed.all_gather_object(out, part)
+                return out
+        sums, rows = merge_eval_sums([own] if gather is None else gather(own))
+        return eval_values(sums, rows, self.action_dim, self.KIND != 'bc')
+
     def disable_graph(self):
         if self._graph_iter is not None:
             self.engine.disable_graph()
@@ -442,6 +476,30 @@ class _AgentBase:
             if explore:
                 a.uniform_(-1.0, 1.0)
         return a.cpu().numpy()[0]
+
+
+EVAL_KINDS = ('td3_bc', 'td3', 'crr', 'cql', 'bc')      # what exorl_agent_evaluate accepts
+
+
+def merge_eval_sums(parts):
+    """[(sums, rows) per rank] -> (sums, rows) of all of them: float64 adds in rank order, so every rank forms the same bits."""
+    total, rows = np.zeros(L.N_EVAL, np.float64), 0
+    for s, r in parts:
+        total = total + np.asarray(s, np.float64)
+        rows += int(r)
+    return total, rows
+
+
+def eval_values(sums, rows, action_dim, has_critic=True):
+    """evaluate()'s dict from the window's sums (L.E_*) over `rows` rows."""
+    n = max(int(rows), 1)
+    out = {'val_bc_mse': float(sums[L.E_BC_SQ] / (n * action_dim))}
+    if has_critic:
+        q_data, q_pi = float(sums[L.E_Q_DATA] / n), float(sums[L.E_Q_PI] / n)
+        out.update(val_q_data=q_data, val_q_pi=q_pi, val_q_gap=q_pi - q_data,
+                   val_critic_loss=float(sums[L.E_Q1_ERR] / n + sums[L.E_Q2_ERR] / n), val_critic_target_q=float(sums[L.E_TARGET_Q] / n))
+    out['val_rows'] = int(rows)
+    return out
 
 
 _CRITIC_METRICS = [(L.M_BATCH_REWARD, 'batch_reward'), (L.M_CRITIC_TARGET_Q, 'critic_target_q'), (L.M_CRITIC_Q1, 'critic_q1'),

@@ -420,6 +420,10 @@ struct exorl_agent {
     // [EXORL_N_METRICS double sums | int64 steps | pad to 256 B][qhead_chunks(B) x 6 critic partials][head_chunks(B) BC partials]
     double* win_sums = nullptr; long long* win_steps = nullptr;
     float *win_crit = nullptr, *win_bc = nullptr;
+    // forward-only evaluation (exorl_agent_set_eval): views of the caller's buffer, [EXORL_N_EVAL double sums | pad to 256 B][eval_chunks(B) x
+    // EVAL_PARTS partials]
+    double* eval_sums = nullptr;
+    float* eval_part = nullptr;
 };
 
 namespace exorl {
@@ -1449,6 +1453,88 @@ int exorl_agent_metric_window_read(exorl_agent_t* a, double* sums_host, int64_t*
     EXORL_CHECK_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < EXORL_N_METRICS; ++i) sums_host[i] = host.sums[i];
     *steps_host = host.steps;
+    return 0;
+}
+
+static_assert(EXORL_N_EVAL * sizeof(double) <= WIN_HEAD_BYTES && EXORL_E_ROWS == EVAL_PARTS, "the eval window's sums fit its head; the row count follows the partials");
+static size_t eval_bytes(const exorl_agent_cfg& cfg) {
+    return WIN_HEAD_BYTES + sizeof(float) * (size_t)round_up((int64_t)EVAL_PARTS * eval_chunks(cfg.batch), 64);
+}
+static bool eval_kind_ok(int kind) {
+    return kind == EXORL_AGENT_TD3_BC || kind == EXORL_AGENT_TD3 || kind == EXORL_AGENT_CRR || kind == EXORL_AGENT_CQL || kind == EXORL_AGENT_BC;
+}
+
+size_t exorl_agent_eval_bytes(const exorl_agent_cfg* cfg) {
+    exorl_agent tmp;
+    if (describe(&tmp, cfg) != 0) return 0;
+    return eval_bytes(*cfg);
+}
+
+int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
+    EXORL_REQUIRE(a, "agent_set_eval: null handle");
+    if (!buf_dev) {
+        a->eval_sums = nullptr; a->eval_part = nullptr;
+        return 0;
+    }
+    EXORL_REQUIRE(eval_kind_ok(a->cfg.kind), "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
+    const size_t need = eval_bytes(a->cfg);
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_eval: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
+    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));      // an empty window; the partials behind it are written before they are read
+    a->eval_sums = static_cast<double*>(buf_dev);
+    a->eval_part = reinterpret_cast<float*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
+    return 0;
+}
+
+// The forwards of phases 0 and 1 with the mean action in place of the draws and nothing saved for a backward pass: same kernels, same routes.
+// Writes the staged inputs, forward scratch (fa, ft, fc, dq: takes carve() marks as scratch) and the eval buffer; reads everything else.
+int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
+    EXORL_REQUIRE(a, "agent_evaluate: null handle");
+    EXORL_REQUIRE(eval_kind_ok(a->cfg.kind), "agent_evaluate: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
+    EXORL_REQUIRE(a->eval_sums, "agent_evaluate: no eval buffer (exorl_agent_set_eval)");
+    hipStream_t s = as_stream(stream);
+    const auto& cfg = a->cfg;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
+    const bool cql = cfg.kind == EXORL_AGENT_CQL;
+    const int AO = a->actor.out_dim;
+    const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
+    // st = nullptr: the inputs are staged, the step state stays where it is
+    EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, a->has_critic ? 1 : 0, nullptr, 0, s));
+    EvalArgs e{};
+    e.mu = a->fa.out + (int64_t)B * AO; e.mu_ld = AO; e.raw = cql ? 1 : 0;
+    e.a_data = a->action; e.A = A; e.reward = a->reward; e.discount = a->discount;
+    e.part = a->eval_part; e.sums = a->eval_sums; e.rows = B;
+    if (!a->has_critic) {          // BC: the obs half alone, as its step runs it (phase 2)
+        EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa + (int64_t)B * O, O, B, a->fa.rows_from(B, H, AO), false, true, prec, s));
+        return eval_reduce(e, s);
+    }
+    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
+    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
+    EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, false, !cql, prec, s));
+    EXORL_TRY(eval_mean_actions(a->fa.out, AO, cql ? 1 : 0, a->xc_next + O, a->xc_pi + O, W, B, A, s));
+    // Q'(s', mu(s')) and Q(s, a) as phase 0 launches them; then Q(s, mu(s)) as phase 1 does, its two columns into dq (fc.out holds Q(s, a))
+    if (forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
+        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, false, W, B, s));
+    } else {
+        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, s));
+        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, false, false, prec, s));
+    }
+    FwdBufs fpi = a->fc;
+    fpi.out = a->dq;
+    EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_pi, W, B, fpi, false, false, prec, s));
+    e.q_data = a->fc.out; e.q_pi = a->dq; e.tq = a->ft.out;
+    return eval_reduce(e, s);
+}
+
+int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream) {
+    EXORL_REQUIRE(a && sums_host && rows_host, "agent_eval_read: null argument");
+    EXORL_REQUIRE(a->eval_sums, "agent_eval_read: no eval buffer (exorl_agent_set_eval)");
+    hipStream_t s = as_stream(stream);
+    double host[EXORL_N_EVAL];
+    EXORL_CHECK_HIP(hipMemcpyAsync(host, a->eval_sums, sizeof(host), hipMemcpyDeviceToHost, s));
+    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(a->eval_sums, 0, sizeof(host), s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < EXORL_N_EVAL; ++i) sums_host[i] = host[i];
+    *rows_host = (int64_t)host[EXORL_E_ROWS];
     return 0;
 }
 

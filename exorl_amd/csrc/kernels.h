@@ -379,6 +379,25 @@ struct MetricsWindowArgs {
     double* sums; long long* steps;                // the window: EXORL_N_METRICS sums, one step count
 };
 int metrics_window(const MetricsWindowArgs& w, hipStream_t s);
+// Forward-only evaluation (exorl_agent_evaluate; loss.hip). eval_mean_actions: the policy's mean action of the stacked actor forward, rows
+// 0..B-1 of mu2 (next_obs) into dst_next, rows B..2B-1 (obs) into dst_pi, the action columns of the critic's inputs; raw: mu2 holds CQL's raw
+// (mu | log_std) head, tanh of its first A columns is taken here. No draw, no counter.
+int eval_mean_actions(const float* mu2, int64_t mu_ld, int raw, float* dst_next, float* dst_pi, int64_t dst_ld, int B, int A, hipStream_t s);
+// eval_partials: one thread per row, per chunk of EVAL_CHUNK_ROWS rows the EXORL_N_EVAL - 1 sums of the header's EXORL_E_* slots, y = r + D min Q'.
+// eval_window: thread i adds slot i's partials in chunk order as doubles to sums[i], thread EXORL_E_ROWS adds the rows.
+constexpr int EVAL_CHUNK_ROWS = 256;
+constexpr int EVAL_PARTS = EXORL_N_EVAL - 1;
+inline int eval_chunks(int rows) { return cdiv(rows, EVAL_CHUNK_ROWS); }
+struct EvalArgs {
+    const float* mu; int64_t mu_ld; int raw;       // mu(s): the obs rows of the actor's output (raw: CQL's head before tanh)
+    const float* a_data; int A;
+    const float *q_data, *q_pi, *tq;               // (2, rows) each; all null without a critic (BC)
+    const float *reward, *discount;
+    float* part;                                   // [eval_chunks(rows)][EVAL_PARTS]
+    double* sums;                                  // EXORL_N_EVAL
+    int rows;
+};
+int eval_reduce(const EvalArgs& e, hipStream_t s);
 int set_device_float(float* dst, float value, hipStream_t s);
 int set_device_u64(uint64_t* dst, uint64_t value, hipStream_t s);
 

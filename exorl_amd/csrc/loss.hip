@@ -641,6 +641,75 @@ int metrics_window(const MetricsWindowArgs& w, hipStream_t s) {
     return 0;
 }
 
+// ---- forward-only evaluation (exorl_agent_evaluate): the mean action in place of the step's sampling epilogue, and the window's sums -----------
+__global__ __launch_bounds__(256) void eval_mean_actions_kernel(const float* __restrict__ mu2, int64_t mu_ld, int raw, float* __restrict__ dst_next,
+                                                                float* __restrict__ dst_pi, int64_t dst_ld, int B, int A) {
+    const int n = 2 * B * A;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int m = i / A, j = i % A;          // row of the stacked forward: 0..B-1 next_obs, B..2B-1 obs
+        float v = mu2[(int64_t)m * mu_ld + j];
+        if (raw) v = tanhf(v);
+        if (m < B) dst_next[(int64_t)m * dst_ld + j] = v;
+        else dst_pi[(int64_t)(m - B) * dst_ld + j] = v;
+    }
+}
+
+int eval_mean_actions(const float* mu2, int64_t mu_ld, int raw, float* dst_next, float* dst_pi, int64_t dst_ld, int B, int A, hipStream_t s) {
+    hipLaunchKernelGGL(eval_mean_actions_kernel, dim3(cdiv(2 * B * A, 256)), dim3(256), 0, s, mu2, mu_ld, raw, dst_next, dst_pi, dst_ld, B, A);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+// One thread per row, one workgroup per chunk of EVAL_CHUNK_ROWS rows; rows past the end add zeros.
+static_assert(EVAL_CHUNK_ROWS == 256, "eval_partials_kernel: one thread per row of the chunk");
+__global__ __launch_bounds__(256) void eval_partials_kernel(const EvalArgs e) {
+    __shared__ float sm[EVAL_PARTS][16];
+    const int m = blockIdx.x * EVAL_CHUNK_ROWS + threadIdx.x;
+    float v[EVAL_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (m < e.rows) {
+        float bc = 0.f;
+        for (int j = 0; j < e.A; ++j) {
+            float mu = e.mu[(int64_t)m * e.mu_ld + j];
+            if (e.raw) mu = tanhf(mu);
+            const float d = mu - e.a_data[(int64_t)m * e.A + j];
+            bc += d * d;
+        }
+        v[EXORL_E_BC_SQ] = bc;
+        if (e.q_data) {
+            const float q1 = e.q_data[m], q2 = e.q_data[e.rows + m];
+            const float y = e.reward[m] + e.discount[m] * fminf(e.tq[m], e.tq[e.rows + m]);
+            v[EXORL_E_Q_DATA] = fminf(q1, q2);
+            v[EXORL_E_Q_PI] = fminf(e.q_pi[m], e.q_pi[e.rows + m]);
+            v[EXORL_E_Q1_ERR] = (q1 - y) * (q1 - y);
+            v[EXORL_E_Q2_ERR] = (q2 - y) * (q2 - y);
+            v[EXORL_E_TARGET_Q] = y;
+        }
+    }
+    block_sum<EVAL_PARTS>(v, sm);
+    if (threadIdx.x < EVAL_PARTS) e.part[(int64_t)blockIdx.x * EVAL_PARTS + threadIdx.x] = v[threadIdx.x];
+}
+
+// One wave. Thread i < EVAL_PARTS owns slot i: its partials in chunk order, as doubles, then one add to the window. Thread EXORL_E_ROWS counts.
+__global__ __launch_bounds__(64) void eval_window_kernel(const float* __restrict__ part, int chunks, int rows, double* sums) {
+    const int t = threadIdx.x;
+    if (t < EVAL_PARTS) {
+        double acc = 0.0;
+        for (int ch = 0; ch < chunks; ++ch) acc += (double)part[(int64_t)ch * EVAL_PARTS + t];
+        sums[t] += acc;
+    } else if (t == EXORL_E_ROWS) {
+        sums[t] += (double)rows;
+    }
+}
+
+int eval_reduce(const EvalArgs& e, hipStream_t s) {
+    const int chunks = eval_chunks(e.rows);
+    hipLaunchKernelGGL(eval_partials_kernel, dim3(chunks), dim3(EVAL_CHUNK_ROWS), 0, s, e);
+    EXORL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(eval_window_kernel, dim3(1), dim3(64), 0, s, e.part, chunks, e.rows, e.sums);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace exorl
 
 extern "C" int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float* out_dev, void* stream) {

@@ -297,6 +297,32 @@ class AgentEngine(_Phased):
         L.check(self.lib.exorl_agent_metric_window_read(self.h, sums.ctypes.data, C.byref(steps), int(bool(reset)), L.current_stream()))
         return sums, int(steps.value)
 
+    def eval_bytes(self):
+        return int(self.lib.exorl_agent_eval_bytes(C.byref(self.cfg)))
+
+    def set_eval(self, buf=True):
+        """The forward-only evaluation's window (exorl_agent_set_eval) on a torch-owned buffer: True allocates eval_bytes(), a uint8 tensor of
+        at least that size is taken as it is, None detaches."""
+        if buf is None:
+            L.check(self.lib.exorl_agent_set_eval(self.h, None, 0))
+            self._eval = None
+            return
+        if buf is True:
+            buf = torch.empty(self.eval_bytes(), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
+        L.check(self.lib.exorl_agent_set_eval(self.h, buf.data_ptr(), buf.numel()))
+        self._eval = buf
+
+    def evaluate(self):
+        """One forward-only pass on the rows in the batch slots, added to the window (exorl_agent_evaluate): no step state moves."""
+        L.check(self.lib.exorl_agent_evaluate(self.h, L.current_stream()))
+
+    def eval_read(self, reset=True):
+        """(sums, rows) of the window: float64 sums per L.E_* slot and the rows in them; reset empties the window."""
+        sums, rows = np.zeros(L.N_EVAL, np.float64), C.c_int64()
+        L.check(self.lib.exorl_agent_eval_read(self.h, sums.ctypes.data, C.byref(rows), int(bool(reset)), L.current_stream()))
+        return sums, int(rows.value)
+
     def cql_alpha_state(self):
         host = np.zeros(6, np.float32)
         L.check(self.lib.exorl_agent_cql_alpha(self.h, host.ctypes.data, 0))

@@ -321,14 +321,54 @@ class _OfflineShard(_Shard):
         """select() on every directory by itself (each with the whole max_size): [(files, total length), ...] in the order given."""
         return [cls.select(d, max_size, num_workers, worker_id) for d in replay_dirs]
 
+    @staticmethod
+    def split_holdout(files, every):
+        """(training files, held-out files) of one directory's selection: counted from 0 in the order given, positions every - 1,
+        2 * every - 1, ... are held out, every other file trains. From the list alone."""
+        if int(every) < 2:
+            raise ValueError(f'holdout_every={every}: expected an integer >= 2 (every k-th selected file is held out)')
+        files = list(files)
+        held = files[int(every) - 1::int(every)]
+        return [fn for i, fn in enumerate(files) if (i + 1) % int(every)], held
+
+    holdout_engine = None              # the second, small arena (holdout_every): the held-out episodes of this shard
+    holdout_fns = ()
+
+    def _load_holdout(self, held):
+        """The held-out files into an arena of their own, sampled transition-uniformly (the training side's weights do not apply)."""
+        ld = self.loader
+        self.holdout_fns = list(held)
+        if not held:
+            return
+        rows, slots = sum(int(fn.stem.split('_')[2]) for fn in held), []
+        for fn, episode in zip(held, _load_many(held, ld.load_threads)):
+            if episode is None:
+                raise IOError(f'offline dataset: cannot read {fn}')
+            if ld.relabel:
+                episode = relabel_episode(ld.env, episode)
+            if self.holdout_engine is None:
+                obs = episode['observation']
+                self.holdout_engine = ReplayEngine(obs.shape[1:], obs.dtype, int(np.prod(episode['action'].shape[1:])),
+                                                   sum(int(np.prod(episode[k].shape[1:])) for k in ld.meta_keys), rows + len(held) + 64,
+                                                   len(held) + 8, ld.device, frame_stack=getattr(ld, 'frame_stack', None) or 1)
+            slots.append(self.holdout_engine.append_episode(episode, ld.meta_keys))
+        self.holdout_engine.set_order(slots)
+        self.holdout_engine.set_weights('transitions', None)
+
     def try_fetch(self):
         if self.engine is not None or self.since_fetch < 0:
             return
         ld = self.loader
         picks = self.select_many(ld.storage._replay_dirs, ld.max_size, ld.num_workers, self.worker_id)
+        held = []
+        if getattr(ld, 'holdout_every', None):      # per directory, in select's ascending order; mix and the weights see the training files only
+            split = [self.split_holdout(t, ld.holdout_every) for t, _ in picks]
+            picks = [(train, sum(int(fn.stem.split('_')[2]) for fn in train)) for train, _ in split]
+            held = [fn for _, h in split for fn in h]
         todo, size = [fn for t, _ in picks for fn in t], sum(n for _, n in picks)
         if not todo:
             return
+        self._load_holdout(held)
         if ld.mix is not None:                   # normalised over what THIS shard holds of each dataset
             per = mix_weights([[int(fn.stem.split('_')[2]) for fn in t] for t, _ in picks], ld.mix, ld.weighting, ld.nstep)
             self.weight = {fn: w for (t, _), w in zip(picks, per) for fn in t}
@@ -381,15 +421,29 @@ class DeviceReplayLoader:
     arena it holds (ReplayEngine.obs_moments: all rows of all resident episodes, several mix directories in one arena included), exchanges
     them between the ranks of an initialised torch.distributed (all_gather_object of a handful of doubles; `gather`, a callable
     own partials -> [partials of rank 0, partials of rank 1, ...], replaces that exchange), merges them with utils.combine_moments, ranks in
-    rank order and each rank's shards in shard order, and sets utils.obs_normalizer(count, mean, M2, norm_eps) on all its arenas: every
+    rank order and each rank's shards in shard order (training arenas only: a hold-out split's arenas get the pair, not a vote), and sets utils.obs_normalizer(count, mean, M2, norm_eps) on all its arenas: every
     sampled obs / next_obs is (x - mean) / (std + norm_eps) of the whole dataset, whatever the sampler. The iterator's .obs_normalizer is
     the (mean32, inv32) pair to hand to agent.set_obs_normalizer, so that act() sees what update() trained on. It is in place before
-    .engine is handed to agent.enable_graph. A growing online buffer is refused: its statistic would move under the policy."""
+    .engine is handed to agent.enable_graph. A growing online buffer is refused: its statistic would move under the policy.
+
+    holdout_every=k (offline loaders, k >= 2): of the files _OfflineShard.select keeps, per directory and in its ascending order, every
+    k-th (positions k - 1, 2k - 1, ... counted from 0) goes to a second, small arena of the same shard and never trains; the rest load
+    as before. weighting, episode_weight and mix apply to the training arena only (mix normalises over the training files); the hold-out
+    arena is sampled transition-uniformly by the Philox sampler, whatever the loader's. iter(loader).holdout is the iterator over it
+    (HoldoutIterator: same next() / sample_into() contract, same nstep and discount, a seed derived from the loader's), None without
+    holdout_every. With normalize_obs the moments are the training arenas' alone and the same pair is set on the hold-out arenas."""
 
     def __init__(self, storage, max_size, batch_size, num_workers, save_snapshot, nstep, discount, fetch_every=1000,
                  device='cuda', sampler='mt19937', seed=None, worker_ids=None, max_episodes=None, capacity_rows=None, static=False,
                  load_threads=None, offline=False, env=None, relabel=False, weighting=None, episode_weight=None, mix=None,
-                 frame_stack=None, normalize_obs=False, norm_eps=1e-3, gather=None):
+                 frame_stack=None, normalize_obs=False, norm_eps=1e-3, gather=None, holdout_every=None):
+        if holdout_every is not None:
+            if not offline:
+                raise ValueError('holdout_every needs an offline loader (make_offline_replay_loader): an online buffer evicts and re-scans, '
+                                 'a fixed split of its files does not exist')
+            if isinstance(holdout_every, bool) or int(holdout_every) != holdout_every or int(holdout_every) < 2:
+                raise ValueError(f'holdout_every={holdout_every!r}: expected an integer >= 2 (every k-th selected file is held out)')
+        self.holdout_every = None if holdout_every is None else int(holdout_every)
         if frame_stack is not None and not 1 <= int(frame_stack) <= 16:
             raise ValueError(f'frame_stack={frame_stack}: expected 1 .. 16')
         if normalize_obs and not offline:
@@ -434,6 +488,30 @@ class DeviceReplayIterator:
         # what agent.enable_graph reads; .engine is only set for a static single-shard dataset (see static_engine)
         self.sampler, self.nstep, self.discount, self.batch_size = loader.sampler, loader.nstep, loader.discount, loader.batch_size
         self._normalizer = None
+        self._holdout = None
+
+    @property
+    def holdout(self):
+        """The iterator over the held-out episodes of a holdout_every loader (HoldoutIterator), None otherwise. The first look loads
+        every shard; a split that left a shard nothing to sample raises ValueError."""
+        ld = self.loader
+        if getattr(ld, 'holdout_every', None) is None:
+            return None
+        if self._holdout is None:
+            for shard in self.shards:
+                self._load_shard(shard)
+            self._ensure_normalizer()
+            for shard in self.shards:
+                if shard.holdout_engine is None or not any(int(fn.stem.split('_')[2]) >= ld.nstep for fn in shard.holdout_fns):
+                    raise ValueError(f'holdout_every={ld.holdout_every}: the split left worker {shard.worker_id} no held-out episode of at '
+                                     f'least nstep={ld.nstep} transitions ({len(shard.fns)} training files, {len(shard.holdout_fns)} held out): '
+                                     'use a smaller holdout_every or more episodes')
+            self._holdout = HoldoutIterator(self)
+        return self._holdout
+
+    def _philox_base(self):
+        ld = self.loader
+        return int(np.random.get_state()[1][0]) if ld.seed is None else int(ld.seed)
 
     def _load_shard(self, shard):
         """The scan that the shard's first sample would trigger, and its index streams."""
@@ -469,6 +547,8 @@ class DeviceReplayIterator:
         self._normalizer = obs_normalizer(count, mean, m2, ld.norm_eps)
         for shard in self.shards:
             shard.engine.set_obs_normalizer(*self._normalizer)
+            if shard.holdout_engine is not None:      # validation sees the inputs the policy sees; the held-out rows had no part in the moments
+                shard.holdout_engine.set_obs_normalizer(*self._normalizer)
         return self._normalizer
 
     @property
@@ -566,6 +646,36 @@ class DeviceReplayIterator:
         return tuple(res)
 
 
+HOLDOUT_SEED_SALT = 0x5851F42D4C957F2D       # the hold-out arenas' Philox seed: the training arena's xor this, so the two streams differ
+
+
+class HoldoutIterator:
+    """Iterator over the hold-out arenas of a holdout_every loader, shard after shard in turn: the next() / sample_into() contract of
+    ArenaIterator, the loader's nstep and discount, the Philox sampler with transition-uniform weights (set at load)."""
+
+    def __init__(self, parent):
+        ld = parent.loader
+        self.batch_size, self.nstep, self.discount, self.sampler = ld.batch_size, ld.nstep, ld.discount, L.SAMPLER_PHILOX
+        self.engines = [shard.holdout_engine for shard in parent.shards]
+        for shard in parent.shards:
+            shard.holdout_engine.seed_philox(((parent._philox_base() + shard.worker_id) ^ HOLDOUT_SEED_SALT) & 0x7FFFFFFFFFFFFFFF)
+        self.turn = 0
+
+    def __iter__(self):
+        return self
+
+    def _next_engine(self):
+        eng = self.engines[self.turn % len(self.engines)]
+        self.turn += 1
+        return eng
+
+    def sample_into(self, out, batch=None):
+        self._next_engine().sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler)
+
+    def __next__(self):
+        return self._next_engine().sample(self.batch_size, self.nstep, self.discount, self.sampler)
+
+
 class ArenaIterator:
     """Iterator over an already-filled ReplayEngine (no directory behind it): what bench.py and callers that
     ingest datasets themselves use. Same next()/sample_into() contract as DeviceReplayIterator."""
@@ -626,7 +736,9 @@ def make_offline_replay_loader(env, replay_dir, max_size, batch_size, num_worker
       weighting='transitions': M_d = the dataset's total span, sum of (len - nstep + 1) over its episodes: all its transitions equally likely;
       weighting='episodes' (the default): M_d = its number of sampleable episodes: all its episodes equally likely, then a uniform start.
     Under data parallelism (worker_ids) every rank normalises over its own shard of each dataset. Without mix the datasets are simply
-    concatenated under `weighting`. A directory may be listed only once. weighting= and episode_weight= are DeviceReplayLoader's."""
+    concatenated under `weighting`. A directory may be listed only once. weighting= and episode_weight= are DeviceReplayLoader's, and so
+    is holdout_every=k: every k-th selected file of each directory is held out for agent.evaluate(iter(loader).holdout) and mix is
+    normalised over the files that train."""
     many = isinstance(replay_dir, (list, tuple))
     if mix is not None and (not many or len(mix) != len(replay_dir)):
         raise ValueError('make_offline_replay_loader: mix needs a list of directories and one fraction per directory')

@@ -13,7 +13,7 @@ from .replay_buffer import make_replay_loader
 
 def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, replay_buffer_size=10**7, eval_every_steps=10000,
                   log_every_steps=1000, eval_fn=None, log_fn=None, env=None, sampler='philox', use_graph=True, start_step=0,
-                  metric_window=False, mix=None, weighting=None, normalize_obs=False):
+                  metric_window=False, mix=None, weighting=None, normalize_obs=False, holdout_every=None, val_batches=0):
     """train_offline.py:90-123. Returns the list of (step, metrics) rows that were logged.
 
     eval_fn(step, agent): called every eval_every_steps (train_offline.py:108-112).
@@ -26,10 +26,17 @@ def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, repla
     sampler (make_offline_replay_loader; both need sampler='philox'). The graph is captured after the weights are in place.
     normalize_obs=True: the TD3+BC authors' state normalisation. The loader z-scores every sampled observation with the dataset's own mean
     and standard deviation in the HBM gather (DeviceReplayLoader) and the agent gets the same pair (agent.set_obs_normalizer) before the
-    capture, so eval_fn's agent.act() normalises the environment's observations the way update() saw the data."""
+    capture, so eval_fn's agent.act() normalises the environment's observations the way update() saw the data.
+    holdout_every=k with val_batches=n > 0: every k-th episode file of each directory is held out of training (DeviceReplayLoader) and, at
+    every eval_every_steps boundary, before eval_fn, agent.evaluate(replay_iter.holdout, n) runs n forward-only batches on the held-out
+    episodes: its val_* dict goes to the returned rows and to log_fn as (step, dict(val, step=step)). It needs no environment. With
+    either left at its default nothing is split, nothing is evaluated and the rows are what they were."""
     extra = {k: v for k, v in (('mix', mix), ('weighting', weighting)) if v is not None}
     if normalize_obs:
         extra['normalize_obs'] = True
+    validate = holdout_every is not None and int(val_batches) > 0
+    if holdout_every is not None:
+        extra['holdout_every'] = holdout_every
     loader = make_replay_loader(env, replay_dir, replay_buffer_size, batch_size, 0, discount, sampler=sampler, **extra)
     replay_iter = iter(loader)
     if normalize_obs:
@@ -41,6 +48,11 @@ def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, repla
     rows = []
     t_start = t_last = time.time()
     for global_step in range(start_step, start_step + num_grad_steps):
+        if validate and eval_every_steps and global_step % eval_every_steps == 0:
+            val = dict(agent.evaluate(replay_iter.holdout, int(val_batches)), step=global_step)
+            rows.append((global_step, val))
+            if log_fn is not None:
+                log_fn(global_step, val)
         if eval_fn is not None and eval_every_steps and global_step % eval_every_steps == 0:
             eval_fn(global_step, agent)
         metrics = agent.update(replay_iter, global_step)

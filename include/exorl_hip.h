@@ -39,9 +39,9 @@ extern "C" {
                                         _rnd_features_phase / _bn_partials; exorl_pixel_agent_grad_buffer exchange 2
                                     12: exorl_debug_agent_poison_scratch; (added since, no version change: exorl_gemm_planes3, EXORL_PREC_BF16X6 for
                                         exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights,
-                                        exorl_replay_set_frame_stack, exorl_agent_update_plan, exorl_replay_obs_moments, exorl_replay_set_obs_norm)
-                                    13: exorl_pixel_step replaces the loose arguments of exorl_pixel_agent_update / _update_phase; the three phased pixel
-                                        calls return next_exchange; exorl_pixel_agent_exchange replaces _grad_buffer and _bn_partials */
+                                        exorl_replay_set_frame_stack, exorl_agent_update_plan, exorl_replay_obs_moments, exorl_replay_set_obs_norm)                                    13: exorl_pixel_step replaces the loose arguments of exorl_pixel_agent_update / _update_phase; the three phased pixel
+                                        calls return next_exchange; exorl_pixel_agent_exchange replaces _grad_buffer and _bn_partials; (added since, no version change:
+                                        exorl_agent_eval_bytes / _set_eval / _evaluate / _eval_read) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -313,6 +313,35 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
 /* Synchronous: sums_host[EXORL_N_METRICS] and *steps_host = the window since the last reset (mean of slot i = sums_host[i] / *steps_host).
  * One copy and, with reset != 0, one hipMemsetAsync, both enqueued on `stream`: they order against the graph replays on it. */
 int exorl_agent_metric_window_read(exorl_agent_t* a, double* sums_host, int64_t* steps_host, int32_t reset, void* stream);
+/* Held-out validation: a forward-only pass over the networks, for TD3+BC, TD3, CRR, CQL and BC (every other kind is refused). Nothing is
+ * sampled, no Philox draw is made and no counter moves; mu is the policy's mean action (tanh of the head; CQL: tanh of the first act_dim of
+ * its 2 act_dim outputs), y = reward + discount * min_i Q'_i(s', mu(s')) the noise-free target. One call adds, over the rows of the batch,
+ * to a window of double sums: */
+#define EXORL_E_BC_SQ     0   /* sum over rows and action columns of (mu(s) - a)^2 */
+#define EXORL_E_Q_DATA    1   /* sum of min_i Q_i(s, a) */
+#define EXORL_E_Q_PI      2   /* sum of min_i Q_i(s, mu(s)) */
+#define EXORL_E_Q1_ERR    3   /* sum of (Q_1(s, a) - y)^2 */
+#define EXORL_E_Q2_ERR    4   /* sum of (Q_2(s, a) - y)^2 */
+#define EXORL_E_TARGET_Q  5   /* sum of y */
+#define EXORL_E_ROWS      6   /* rows in the window */
+#define EXORL_N_EVAL      7
+/* Bytes of the window and its per-chunk partials for a configuration (0 for one exorl_agent_create refuses). Needs no device. */
+size_t exorl_agent_eval_bytes(const exorl_agent_cfg* cfg);
+/* Attach the window: exorl_agent_eval_bytes(cfg) bytes of the caller's device memory, 256-byte aligned, alive while it is set; the call
+ * empties it. NULL detaches. The buffer is the caller's, as the metric window is: the agent workspace keeps its size and layout. */
+int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes);
+/* One forward-only pass on the cfg.batch rows currently in the batch slots (exorl_agent_batch_slots / exorl_agent_set_batch), through the
+ * step's own forward kernels in the agent's precision, then one row kernel and a one-wave kernel that adds the per-chunk partials to the window
+ * in chunk order (the sums are bitwise reproducible). BC runs the actor alone and adds to EXORL_E_BC_SQ and EXORL_E_ROWS only.
+ * Read-only towards everything a step leaves behind or reads: parameters, targets, weight images, gradients, Adam moments, the step state,
+ * the metrics and their window, the statistics, CQL's scalars and exorl_agent_act's buffers. It writes the staged network inputs, the
+ * scratch a whole step writes before it reads (what exorl_debug_agent_poison_scratch fills) and its own window. Eager launches on `stream`:
+ * it may run between exorl_agent_update or exorl_agent_step_graph calls on that stream, and must NOT be called between the phases of a step
+ * driven through exorl_agent_update_phase (the phases hand their activations to each other in that scratch). */
+int exorl_agent_evaluate(exorl_agent_t* a, void* stream);
+/* Synchronous: sums_host[EXORL_N_EVAL] and *rows_host = the window since the last reset (val mean of slot i = sums_host[i] / *rows_host).
+ * One copy and, with reset != 0, one hipMemsetAsync, both enqueued on `stream`. */
+int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream);
 /* Captured graphs run independent parts of the step (target || critic forward, wgrad || dgrad chain) as parallel
  * branches on a second stream (default: off — one chain measured faster on MI355X). */
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable);
