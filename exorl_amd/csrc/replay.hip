@@ -229,6 +229,28 @@ __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pa
     }
 }
 
+// What one wave writes per sample, whatever the shape of the observation gather: the action of arena row `row` (= row0 + idx), the meta
+// row of the step before it, and the n-step return and discount in the reference's operation order. fp contract is off INSIDE this body
+// (the pragma is lexically scoped): an FMA in the recurrence would stop matching NumPy.
+__device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_batch_out& out, int b, int64_t row, int nstep, float gamma,
+                                            int lane) {
+#pragma clang fp contract(off)
+    for (int j = lane; j < v.act_dim; j += 64) out.action[(int64_t)b * out.action_stride + j] = v.act[row * v.act_dim + j];
+    if (out.meta)
+        for (int j = lane; j < v.meta_dim; j += 64) out.meta[(int64_t)b * out.meta_stride + j] = v.meta[(row - 1) * v.meta_dim + j];
+    if (lane == 0) {
+        float R = 0.0f, D = 1.0f;
+        for (int i = 0; i < nstep; ++i) {
+            const float t = D * v.rew[row + i];        // replay_buffer.py:233  reward += discount * step_reward
+            R = R + t;
+            const float u = v.disc[row + i] * gamma;   // replay_buffer.py:234  discount *= ep_discount * gamma
+            D = D * u;
+        }
+        out.reward[b] = R;
+        out.discount[b] = D;
+    }
+}
+
 // NORM = false is the copying gather; NORM = true (exorl_replay_set_obs_norm) differs only where an observation element is written.
 template <bool NORM>
 __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const int32_t* pairs_in,
@@ -256,10 +278,6 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         copy_row(v.obs + (row + nstep - 1) * v.obs_bytes,
                  static_cast<unsigned char*>(out.next_obs) + (int64_t)b * out.next_obs_stride, v.obs_bytes, lane, vec16);
     }
-    for (int j = lane; j < v.act_dim; j += 64) out.action[(int64_t)b * out.action_stride + j] = v.act[row * v.act_dim + j];
-    if (out.meta)
-        for (int j = lane; j < v.meta_dim; j += 64)
-            out.meta[(int64_t)b * out.meta_stride + j] = v.meta[(row - 1) * v.meta_dim + j];
     if (stage.xa) {                                  // the agent's staged network inputs, straight from the arena rows
         const int O = stage.O, A = stage.A, W = O + A;
         const float* so = reinterpret_cast<const float*>(v.obs + (row - 1) * v.obs_bytes);
@@ -282,17 +300,7 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         if (stage.has_critic)
             for (int j = lane; j < A; j += 64) stage.xc_cur[(int64_t)b * W + O + j] = v.act[row * v.act_dim + j];
     }
-    if (lane == 0) {
-        float R = 0.0f, D = 1.0f;
-        for (int i = 0; i < nstep; ++i) {
-            const float t = D * v.rew[row + i];        // replay_buffer.py:233  reward += discount * step_reward
-            R = R + t;
-            const float u = v.disc[row + i] * gamma;   // replay_buffer.py:234  discount *= ep_discount * gamma
-            D = D * u;
-        }
-        out.reward[b] = R;
-        out.discount[b] = D;
-    }
+    sample_tail(v, out, b, row, nstep, gamma, lane);
 }
 
 // copy_row with four loads of a lane in flight before the first store (the compiler keeps copy_row's loop at one load, one wait, one store):
@@ -309,12 +317,10 @@ __device__ __forceinline__ void stream_words(const W* __restrict__ s, W* __restr
 
 // Frame-stacked arenas: one wave per output frame, 2 * frames * batch of them. Wave (b, which, j) streams frame j (0 = oldest) of sample b's
 // obs (which = 0, the stack at t = idx - 1) or next_obs (which = 1, t = idx + nstep - 1) from episode row max(t - (frames - 1 - j), 0): steps
-// before the reset repeat the reset frame. The first wave of a sample also writes what is per sample: action, meta, the n-step return
-// (same operation order as gather_nstep_kernel) and the drawn pair.
+// before the reset repeat the reset frame. The first wave of a sample also writes what is per sample: sample_tail and the drawn pair.
 __global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const int32_t* pairs_in, int32_t* pairs_out, exorl_batch_out out,
                                                             int batch, int nstep, float gamma, int sampler, uint64_t seed,
                                                             uint64_t counter_val, const uint64_t* counter_ptr, int frames) {
-#pragma clang fp contract(off)
     const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -335,21 +341,7 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const 
     if (vec16) stream_words(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), v.obs_bytes / 16, lane);
     else stream_words(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(dst), v.obs_bytes / 4, lane);
     if (!first) return;
-    const int64_t row = row0 + idx;
-    for (int i = lane; i < v.act_dim; i += 64) out.action[(int64_t)b * out.action_stride + i] = v.act[row * v.act_dim + i];
-    if (out.meta)
-        for (int i = lane; i < v.meta_dim; i += 64) out.meta[(int64_t)b * out.meta_stride + i] = v.meta[(row - 1) * v.meta_dim + i];
-    if (lane == 0) {
-        float R = 0.0f, D = 1.0f;
-        for (int i = 0; i < nstep; ++i) {
-            const float x = D * v.rew[row + i];        // replay_buffer.py:233  reward += discount * step_reward
-            R = R + x;
-            const float u = v.disc[row + i] * gamma;   // replay_buffer.py:234  discount *= ep_discount * gamma
-            D = D * u;
-        }
-        out.reward[b] = R;
-        out.discount[b] = D;
-    }
+    sample_tail(v, out, b, row0 + idx, nstep, gamma, lane);
 }
 
 // ---- column moments of the resident observations (exorl_replay_obs_moments) -----------------------------------------------------------

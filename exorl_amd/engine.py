@@ -889,8 +889,8 @@ class ReplayEngine:
         L.check(self.lib.exorl_replay_last_pairs(self.h, batch, out.ctypes.data, L.current_stream()))
         return out
 
-    def sample(self, batch, nstep, gamma, sampler=L.SAMPLER_MT19937, pairs=None, want_pairs=False):
-        """Allocates fresh output tensors (B,*obs_shape) (B,A) (B,1) (B,1) (B,*obs_shape) [(B,meta)]."""
+    def alloc_batch(self, batch):
+        """Fresh output tensors (B,*obs_shape) (B,A) (B,1) (B,1) (B,*obs_shape) [(B,meta)] and the BatchOut that points at them."""
         tdt = torch.uint8 if self.obs_dtype == np.uint8 else torch.float32
         dev = self.device
         obs = torch.empty((batch,) + self.obs_shape, dtype=tdt, device=dev)
@@ -901,6 +901,10 @@ class ReplayEngine:
         meta = torch.empty(batch, self.meta_dim, dtype=torch.float32, device=dev) if self.meta_dim else None
         out = L.BatchOut(obs.data_ptr(), self.obs_bytes, act.data_ptr(), self.act_dim, rew.data_ptr(), disc.data_ptr(),
                          nobs.data_ptr(), self.obs_bytes, L.ptr(meta), self.meta_dim)
+        return (obs, act, rew, disc, nobs) + ((meta,) if meta is not None else ()), out
+
+    def sample(self, batch, nstep, gamma, sampler=L.SAMPLER_MT19937, pairs=None, want_pairs=False):
+        """One batch into fresh tensors (alloc_batch); with want_pairs also the (episode position, start idx) pairs drawn."""
+        res, out = self.alloc_batch(batch)
         p = self.sample_into(out, batch, nstep, gamma, sampler, pairs, want_pairs)
-        res = (obs, act, rew, disc, nobs) + ((meta,) if meta is not None else ())
         return (res, p) if want_pairs else res

@@ -44,6 +44,12 @@ def load_episode(fn):
         return {k: z[k] for k in z.files}
 
 
+def parse_episode_fn(fn):
+    """(idx, length) of an episode_{idx}_{len}.npz path: everything the selection rules need is in the name."""
+    idx, n = Path(fn).stem.split('_')[1:3]
+    return int(idx), int(n)
+
+
 def _load_or_none(fn):
     try:
         return load_episode(fn)
@@ -118,7 +124,7 @@ class ReplayBufferStorage:
         self._fresh_max = 64
         for fn in self._replay_dir.glob('*.npz'):           # resume counters from what is on disk
             self._num_episodes += 1
-            self._num_transitions += int(fn.stem.split('_')[2])
+            self._num_transitions += parse_episode_fn(fn)[1]
 
     def __len__(self):
         return self._num_transitions
@@ -152,6 +158,17 @@ class ReplayBufferStorage:
             self._fresh.popitem(last=False)
 
 
+EMPTY_BUFFER = 'replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)'
+
+
+def _make_arena(loader, episode, capacity_rows, max_episodes):
+    """The arena a loader's shard keeps its episodes in, shaped after the first episode it will hold."""
+    obs = episode['observation']
+    meta_dim = sum(int(np.prod(episode[k].shape[1:])) for k in loader.meta_keys)
+    return ReplayEngine(obs.shape[1:], obs.dtype, int(np.prod(episode['action'].shape[1:])), meta_dim, capacity_rows, max_episodes,
+                        loader.device, frame_stack=loader.frame_stack or 1)
+
+
 class _Shard:
     """One reference 'worker': its own resident set, limits and index streams (replay_buffer.py:153-212)."""
 
@@ -163,6 +180,7 @@ class _Shard:
         self.slot = {}                 # fn -> arena slot
         self.length = {}
         self.since_fetch = loader.fetch_every
+        self.frozen = False            # loaded once, never re-scanned: an offline shard, or an arena handed out for graph capture
         self.dir_stamp = None
         self.engine = None
         self.seeded = False
@@ -181,16 +199,15 @@ class _Shard:
                 w[self.slot[f]] = self.weight[f]
         self.engine.set_weights(ld.weighting, w)
 
-    def _ensure_engine(self, episode):
+    def _ensure_engine(self, episode, capacity_rows=None, max_episodes=None):
+        """The arena, made when the first episode arrives. Sizes: the caller's (an offline shard knows its files), else the loader's
+        max_episodes= / capacity_rows=, else room for max_size transitions."""
         if self.engine is not None:
             return
         ld = self.loader
-        obs = episode['observation']
-        meta_dim = sum(int(np.prod(episode[k].shape[1:])) for k in ld.meta_keys)
-        max_eps = ld.max_episodes or max(4096, ld.max_size // 64)
-        cap = ld.capacity_rows or (ld.max_size + max_eps + obs.shape[0] + 1024)
-        self.engine = ReplayEngine(obs.shape[1:], obs.dtype, int(np.prod(episode['action'].shape[1:])), meta_dim, cap,
-                                   max_eps, ld.device, frame_stack=getattr(ld, 'frame_stack', None) or 1)
+        max_eps = max_episodes or ld.max_episodes or max(4096, ld.max_size // 64)
+        cap = capacity_rows or ld.capacity_rows or (ld.max_size + max_eps + len(episode['observation']) + 1024)
+        self.engine = _make_arena(ld, episode, cap, max_eps)
 
     def _store(self, fn, episode=None, reorder=True):
         ld = self.loader
@@ -221,7 +238,7 @@ class _Shard:
 
     def try_fetch(self):
         ld = self.loader
-        if self.since_fetch < ld.fetch_every:
+        if self.frozen or self.since_fetch < ld.fetch_every:
             return
         self.since_fetch = 0
         d = ld.storage._replay_dir
@@ -230,7 +247,7 @@ class _Shard:
             return                                         # nothing was added since the last scan
         fetched, todo = 0, []
         for fn in sorted(d.glob('*.npz'), reverse=True):  # the reference's selection (replay_buffer.py:196-212) ...
-            idx, n = (int(x) for x in fn.stem.split('_')[1:])
+            idx, n = parse_episode_fn(fn)
             if idx % ld.num_workers != self.worker_id:
                 continue
             if fn in self.slot:
@@ -309,7 +326,7 @@ class _OfflineShard(_Shard):
         for fn in sorted(Path(replay_dir).glob('*.npz')):
             if size > max_size:
                 break
-            idx, n = (int(x) for x in fn.stem.split('_')[1:])
+            idx, n = parse_episode_fn(fn)
             if idx % num_workers != worker_id:
                 continue
             todo.append(fn)
@@ -334,51 +351,52 @@ class _OfflineShard(_Shard):
     holdout_engine = None              # the second, small arena (holdout_every): the held-out episodes of this shard
     holdout_fns = ()
 
+    @staticmethod
+    def _arena_sizes(fns):
+        """(capacity_rows, max_episodes) of an arena that holds exactly `fns`: an episode takes len + 1 rows."""
+        return sum(parse_episode_fn(fn)[1] for fn in fns) + len(fns) + 64, len(fns) + 8
+
+    def _episodes(self, fns):
+        """(fn, episode) of every file of `fns` in order: decoded by the thread pool, rewards relabelled when the loader asks for it."""
+        ld = self.loader
+        for fn, episode in zip(fns, _load_many(fns, ld.load_threads)):
+            if episode is None:
+                raise IOError(f'offline dataset: cannot read {fn}')
+            yield fn, (relabel_episode(ld.env, episode) if ld.relabel else episode)
+
     def _load_holdout(self, held):
         """The held-out files into an arena of their own, sampled transition-uniformly (the training side's weights do not apply)."""
         ld = self.loader
         self.holdout_fns = list(held)
         if not held:
             return
-        rows, slots = sum(int(fn.stem.split('_')[2]) for fn in held), []
-        for fn, episode in zip(held, _load_many(held, ld.load_threads)):
-            if episode is None:
-                raise IOError(f'offline dataset: cannot read {fn}')
-            if ld.relabel:
-                episode = relabel_episode(ld.env, episode)
+        slots = []
+        for fn, episode in self._episodes(held):
             if self.holdout_engine is None:
-                obs = episode['observation']
-                self.holdout_engine = ReplayEngine(obs.shape[1:], obs.dtype, int(np.prod(episode['action'].shape[1:])),
-                                                   sum(int(np.prod(episode[k].shape[1:])) for k in ld.meta_keys), rows + len(held) + 64,
-                                                   len(held) + 8, ld.device, frame_stack=getattr(ld, 'frame_stack', None) or 1)
+                self.holdout_engine = _make_arena(ld, episode, *self._arena_sizes(held))
             slots.append(self.holdout_engine.append_episode(episode, ld.meta_keys))
         self.holdout_engine.set_order(slots)
         self.holdout_engine.set_weights('transitions', None)
 
     def try_fetch(self):
-        if self.engine is not None or self.since_fetch < 0:
+        if self.frozen or self.engine is not None:
             return
         ld = self.loader
-        picks = self.select_many(ld.storage._replay_dirs, ld.max_size, ld.num_workers, self.worker_id)
+        picks = [t for t, _ in self.select_many(ld.storage._replay_dirs, ld.max_size, ld.num_workers, self.worker_id)]
         held = []
-        if getattr(ld, 'holdout_every', None):      # per directory, in select's ascending order; mix and the weights see the training files only
-            split = [self.split_holdout(t, ld.holdout_every) for t, _ in picks]
-            picks = [(train, sum(int(fn.stem.split('_')[2]) for fn in train)) for train, _ in split]
-            held = [fn for _, h in split for fn in h]
-        todo, size = [fn for t, _ in picks for fn in t], sum(n for _, n in picks)
+        if ld.holdout_every:      # per directory, in select's ascending order; mix and the weights see the training files only
+            split = [self.split_holdout(t, ld.holdout_every) for t in picks]
+            picks, held = [train for train, _ in split], [fn for _, h in split for fn in h]
+        todo = [fn for t in picks for fn in t]
         if not todo:
             return
         self._load_holdout(held)
         if ld.mix is not None:                   # normalised over what THIS shard holds of each dataset
-            per = mix_weights([[int(fn.stem.split('_')[2]) for fn in t] for t, _ in picks], ld.mix, ld.weighting, ld.nstep)
-            self.weight = {fn: w for (t, _), w in zip(picks, per) for fn in t}
-        ld.max_episodes, ld.capacity_rows = len(todo) + 8, size + len(todo) + 64
-        for fn, episode in zip(todo, _load_many(todo, ld.load_threads)):
-            if episode is None:
-                raise IOError(f'offline dataset: cannot read {fn}')
-            if ld.relabel:
-                episode = relabel_episode(ld.env, episode)
-            self._ensure_engine(episode)
+            per = mix_weights([[parse_episode_fn(fn)[1] for fn in t] for t in picks], ld.mix, ld.weighting, ld.nstep)
+            self.weight = {fn: w for t, w in zip(picks, per) for fn in t}
+        sizes = self._arena_sizes(todo)
+        for fn, episode in self._episodes(todo):
+            self._ensure_engine(episode, *sizes)
             self.slot[fn] = self.engine.append_episode(episode, ld.meta_keys)
             self.length[fn] = episode_len(episode)
             if ld.episode_weight is not None:
@@ -386,7 +404,7 @@ class _OfflineShard(_Shard):
             self.fns.append(fn)
             self.size += self.length[fn]
         self._reorder()
-        self.since_fetch = -(1 << 62)            # loaded once (replay_buffer.py:78-80)
+        self.frozen = True                       # loaded once (replay_buffer.py:78-80)
 
 
 def _weighting_args(sampler, weighting, episode_weight, mix=None):
@@ -484,7 +502,6 @@ class DeviceReplayIterator:
         self.loader = loader
         self.shards = [(_OfflineShard if loader.offline else _Shard)(loader, w) for w in loader.worker_ids]
         self.turn = 0
-        self._seeded = False
         # what agent.enable_graph reads; .engine is only set for a static single-shard dataset (see static_engine)
         self.sampler, self.nstep, self.discount, self.batch_size = loader.sampler, loader.nstep, loader.discount, loader.batch_size
         self._normalizer = None
@@ -495,30 +512,44 @@ class DeviceReplayIterator:
         """The iterator over the held-out episodes of a holdout_every loader (HoldoutIterator), None otherwise. The first look loads
         every shard; a split that left a shard nothing to sample raises ValueError."""
         ld = self.loader
-        if getattr(ld, 'holdout_every', None) is None:
+        if ld.holdout_every is None:
             return None
         if self._holdout is None:
             for shard in self.shards:
                 self._load_shard(shard)
             self._ensure_normalizer()
             for shard in self.shards:
-                if shard.holdout_engine is None or not any(int(fn.stem.split('_')[2]) >= ld.nstep for fn in shard.holdout_fns):
+                if shard.holdout_engine is None or not any(parse_episode_fn(fn)[1] >= ld.nstep for fn in shard.holdout_fns):
                     raise ValueError(f'holdout_every={ld.holdout_every}: the split left worker {shard.worker_id} no held-out episode of at '
                                      f'least nstep={ld.nstep} transitions ({len(shard.fns)} training files, {len(shard.holdout_fns)} held out): '
                                      'use a smaller holdout_every or more episodes')
             self._holdout = HoldoutIterator(self)
         return self._holdout
 
-    def _philox_base(self):
+    def _seed_base(self):
+        """What every index stream of this iterator is derived from: the loader's seed, else word 0 of NumPy's global state."""
         ld = self.loader
         return int(np.random.get_state()[1][0]) if ld.seed is None else int(ld.seed)
 
+    def _seed(self, shard):
+        ld = self.loader
+        if ld.sampler == L.SAMPLER_MT19937 and ld.num_workers == 1 and ld.seed is None:
+            shard.engine.seed_mt_from_globals()              # continue random / np.random exactly (num_workers=0 case)
+        else:
+            seed = self._seed_base() + shard.worker_id       # _worker_init_fn: seed = np state word 0 + worker_id
+            if ld.sampler == L.SAMPLER_MT19937:
+                shard.engine.seed_mt_ints(seed, seed & 0xFFFFFFFF)
+            else:
+                shard.engine.seed_philox(seed)
+        shard.seeded = True
+
     def _load_shard(self, shard):
-        """The scan that the shard's first sample would trigger, and its index streams."""
+        """The scan that the shard's first sample would trigger, and its index streams: every way into the iterator comes through here,
+        so a shard is loaded and seeded once whichever of next(), sample_into(), .engine, .obs_normalizer and .holdout is touched first."""
         if shard.engine is None:
             shard.try_fetch()
             if shard.engine is None:
-                raise IndexError('replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)')
+                raise IndexError(EMPTY_BUFFER)
         if not shard.seeded:
             self._seed(shard)
 
@@ -530,7 +561,7 @@ class DeviceReplayIterator:
 
     def _ensure_normalizer(self):
         ld = self.loader
-        if not getattr(ld, 'normalize_obs', False) or self._normalizer is not None:
+        if not ld.normalize_obs or self._normalizer is not None:
             return self._normalizer
         from .utils import combine_moments, obs_normalizer
         for shard in self.shards:
@@ -559,40 +590,26 @@ class DeviceReplayIterator:
         if not (ld.static and len(self.shards) == 1 and ld.sampler == L.SAMPLER_PHILOX):
             return None
         shard = self.shards[0]
-        if shard.engine is None:
-            shard.try_fetch()
-            if shard.engine is None:
-                raise IndexError('replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)')
-            self._seed(shard)
+        self._load_shard(shard)
         self._ensure_normalizer()           # normalize_obs: in place before the arena is captured
-        shard.since_fetch = -(1 << 62)      # the captured graph samples without passing through the fetch counter
+        shard.frozen = True                 # the captured graph samples without passing through the fetch counter
         return shard.engine
 
     def __iter__(self):
         return self
 
-    def _seed(self, shard):
-        ld = self.loader
-        if ld.sampler == L.SAMPLER_MT19937:
-            if ld.num_workers == 1 and ld.seed is None:
-                shard.engine.seed_mt_from_globals()          # continue random / np.random exactly (num_workers=0 case)
-            else:                                            # _worker_init_fn: seed = np state word 0 + worker_id
-                base = int(np.random.get_state()[1][0]) if ld.seed is None else int(ld.seed)
-                shard.engine.seed_mt_ints(base + shard.worker_id, (base + shard.worker_id) & 0xFFFFFFFF)
-        else:
-            base = int(np.random.get_state()[1][0]) if ld.seed is None else int(ld.seed)
-            shard.engine.seed_philox(base + shard.worker_id)
-        shard.seeded = True
-
     def _segments(self, shard, batch):
         """Splits a batch where the reference would re-scan the directory mid-batch: it checks before EVERY
-        sample (replay_buffer.py:216,193) and scans once `fetch_every` samples have been drawn."""
+        sample (replay_buffer.py:216,193) and scans once `fetch_every` samples have been drawn. A frozen shard never re-scans:
+        the whole batch is one segment."""
+        self._load_shard(shard)
+        if shard.frozen:
+            yield 0, batch
+            return
         done = 0
         while done < batch:
             if shard.since_fetch >= self.loader.fetch_every:
                 shard.try_fetch()
-                if not getattr(shard, 'seeded', False) and shard.engine is not None:
-                    self._seed(shard)
             n = min(self.loader.fetch_every - shard.since_fetch, batch - done)
             yield done, n
             shard.since_fetch += n
@@ -606,8 +623,8 @@ class DeviceReplayIterator:
         shard = self.shards[self.turn % len(self.shards)]
         self.turn += 1
         for start, n in self._segments(shard, batch):
-            if shard.engine is None or not shard.fns:
-                raise IndexError('replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)')
+            if not shard.fns:                                 # loaded, then emptied by an eviction
+                raise IndexError(EMPTY_BUFFER)
             seg = L.BatchOut(out.obs + start * out.obs_stride, out.obs_stride,
                              out.action + start * out.action_stride * 4, out.action_stride,
                              out.reward + start * 4, out.discount + start * 4,
@@ -620,60 +637,17 @@ class DeviceReplayIterator:
         B = ld.batch_size
         self._ensure_normalizer()
         shard = self.shards[self.turn % len(self.shards)]
-        if shard.engine is None:                              # first batch: the scan that sample 0 would trigger
-            shard.try_fetch()
-            if shard.engine is None:
-                raise IndexError('replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)')
-            self._seed(shard)
-        eng = shard.engine
-        tdt = torch.uint8 if eng.obs_dtype == np.uint8 else torch.float32
-        obs = torch.empty((B,) + eng.obs_shape, dtype=tdt, device=eng.device)
-        nobs = torch.empty_like(obs)
-        act = torch.empty(B, eng.act_dim, dtype=torch.float32, device=eng.device)
-        rew = torch.empty(B, 1, dtype=torch.float32, device=eng.device)
-        disc = torch.empty(B, 1, dtype=torch.float32, device=eng.device)
-        meta = torch.empty(B, eng.meta_dim, dtype=torch.float32, device=eng.device) if eng.meta_dim else None
-        out = L.BatchOut(obs.data_ptr(), eng.obs_bytes, act.data_ptr(), eng.act_dim, rew.data_ptr(), disc.data_ptr(),
-                         nobs.data_ptr(), eng.obs_bytes, L.ptr(meta), eng.meta_dim)
+        self._load_shard(shard)                               # first batch: the scan that sample 0 would trigger
+        res, out = shard.engine.alloc_batch(B)
         self.sample_into(out, B)
-        res = [obs, act, rew, disc, nobs]
-        if meta is not None:                                  # one tensor per meta spec, like the reference's *meta
-            o = 0
-            for spec in ld.storage._meta_specs:
-                w = int(np.prod(spec.shape))
-                res.append(meta[:, o:o + w].reshape((B,) + tuple(spec.shape)))
-                o += w
+        if len(res) == 5:
+            return res
+        meta, res, o = res[5], list(res[:5]), 0               # one tensor per meta spec, like the reference's *meta
+        for spec in ld.storage._meta_specs:
+            w = int(np.prod(spec.shape))
+            res.append(meta[:, o:o + w].reshape((B,) + tuple(spec.shape)))
+            o += w
         return tuple(res)
-
-
-HOLDOUT_SEED_SALT = 0x5851F42D4C957F2D       # the hold-out arenas' Philox seed: the training arena's xor this, so the two streams differ
-
-
-class HoldoutIterator:
-    """Iterator over the hold-out arenas of a holdout_every loader, shard after shard in turn: the next() / sample_into() contract of
-    ArenaIterator, the loader's nstep and discount, the Philox sampler with transition-uniform weights (set at load)."""
-
-    def __init__(self, parent):
-        ld = parent.loader
-        self.batch_size, self.nstep, self.discount, self.sampler = ld.batch_size, ld.nstep, ld.discount, L.SAMPLER_PHILOX
-        self.engines = [shard.holdout_engine for shard in parent.shards]
-        for shard in parent.shards:
-            shard.holdout_engine.seed_philox(((parent._philox_base() + shard.worker_id) ^ HOLDOUT_SEED_SALT) & 0x7FFFFFFFFFFFFFFF)
-        self.turn = 0
-
-    def __iter__(self):
-        return self
-
-    def _next_engine(self):
-        eng = self.engines[self.turn % len(self.engines)]
-        self.turn += 1
-        return eng
-
-    def sample_into(self, out, batch=None):
-        self._next_engine().sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler)
-
-    def __next__(self):
-        return self._next_engine().sample(self.batch_size, self.nstep, self.discount, self.sampler)
 
 
 class ArenaIterator:
@@ -694,11 +668,35 @@ class ArenaIterator:
     def __iter__(self):
         return self
 
+    def _next_engine(self):
+        return self.engine
+
     def sample_into(self, out, batch=None):
-        self.engine.sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler)
+        self._next_engine().sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler)
 
     def __next__(self):
-        return self.engine.sample(self.batch_size, self.nstep, self.discount, self.sampler)
+        return self._next_engine().sample(self.batch_size, self.nstep, self.discount, self.sampler)
+
+
+HOLDOUT_SEED_SALT = 0x5851F42D4C957F2D       # the hold-out arenas' Philox seed: the training arena's xor this, so the two streams differ
+
+
+class HoldoutIterator(ArenaIterator):
+    """ArenaIterator over the hold-out arenas of a holdout_every loader, shard after shard in turn: the loader's nstep and discount, the
+    Philox sampler with transition-uniform weights (set at load)."""
+
+    def __init__(self, parent):
+        ld = parent.loader
+        self.batch_size, self.nstep, self.discount, self.sampler = ld.batch_size, ld.nstep, ld.discount, L.SAMPLER_PHILOX
+        self.engines = [shard.holdout_engine for shard in parent.shards]
+        for shard in parent.shards:
+            shard.holdout_engine.seed_philox(((parent._seed_base() + shard.worker_id) ^ HOLDOUT_SEED_SALT) & 0x7FFFFFFFFFFFFFFF)
+        self.turn = 0
+
+    def _next_engine(self):
+        eng = self.engines[self.turn % len(self.engines)]
+        self.turn += 1
+        return eng
 
 
 def make_replay_loader(storage, max_size, batch_size, num_workers, save_snapshot, nstep=None, discount=None, **kw):

@@ -212,10 +212,15 @@ def test_offline_file_selection_rule(tmp_path):
     """OfflineReplayBuffer._load's selection (replay_buffer.py:58-75) from file names alone: ascending lexicographic order, stop once
     the running size EXCEEDS max_size, per-worker modulo. A dataset larger than max_size keeps its FIRST episodes (the online buffer's
     reverse scan would keep the last ones)."""
-    from exorl_amd.replay_buffer import _OfflineShard
+    from exorl_amd.replay_buffer import _OfflineShard, parse_episode_fn
     lengths = [7, 3, 12, 5, 9, 4, 3, 15, 6, 8, 10, 3, 11]
     for i, n in enumerate(lengths):
         (tmp_path / f'episode_{i}_{n}.npz').write_bytes(b'')
+    # the one file-name parser the rule reads: (idx, length), from a Path or a string, whatever the directory is called
+    assert [parse_episode_fn(tmp_path / f'episode_{i}_{n}.npz') for i, n in enumerate(lengths)] == list(enumerate(lengths))
+    assert parse_episode_fn('some_dir_7/episode_12_1000.npz') == (12, 1000) and parse_episode_fn('episode_0_1.npz') == (0, 1)
+    with pytest.raises(ValueError):
+        parse_episode_fn('episode_3.npz')
     idx = lambda fns: [int(f.stem.split('_')[1]) for f in fns]
     todo, size = _OfflineShard.select(tmp_path, 40, 1, 0)
     assert idx(todo) == [0, 10, 11, 12, 1, 2] and size == 46            # == tests/golden/replay_offline_b_cap.npz 'resident'

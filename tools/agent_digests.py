@@ -7,6 +7,7 @@ must leave every line equal). Run it from each tree in a fresh process per listi
     python tools/agent_digests.py grid OUT.txt                 one update() of every case of the state agents' kernel dispatch grids, per route
     python tools/agent_digests.py modes OUT.txt                one state-agent handle through every driver of its step in turn (see modes)
     python tools/agent_digests.py pixel_modes OUT.txt          one pixel handle through every driver of its step in turn (see pixel_modes)
+    python tools/agent_digests.py replay OUT.txt               the replay loaders, online and offline: batches and index pairs (see replay)
     python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
 
 A listing has one line per entry, `case what value`; a value is the first 32 hex digits of a sha256 or a float.hex(). Inputs come from
@@ -413,6 +414,102 @@ def pixel_modes(out):
     listing(out, body)
 
 
+REPLAY_LENGTHS = [5, 9, 3, 12, 7, 4]
+
+
+def replay(out):
+    """The replay loaders, first three batches of 16 each: every output tensor and the (episode, start) pairs of every arena call behind
+    it (ReplayEngine.last_pairs). Online loaders (MT19937 with fetch_every below the batch, so a batch is split where the reference would
+    re-scan; Philox with two workers) over states with one 4-wide meta spec; offline loaders over one directory, two mixed ones under both
+    weightings, stacked uint8 frames, normalize_obs on two shards, and a hold-out split with its hold-out iterator and its training
+    arena behind an ArenaIterator. Uses only calls that trees from before ReplayEngine.alloc_batch have,
+    so the same file runs against either library."""
+    import random
+    import _synth
+    from exorl_amd import replay_buffer as R
+    from exorl_amd.engine import ReplayEngine
+    NB, RB, K = 3, 16, 3
+
+    class Spec:
+        def __init__(self, shape, dtype, name):
+            self.shape, self.dtype, self.name = tuple(shape), np.dtype(dtype), name
+
+    pairs, inner = [], ReplayEngine.sample_into
+
+    def sample_into(self, out_, batch, *a, **k):            # every arena call of a batch, in order: a split batch makes several
+        r = inner(self, out_, batch, *a, **k)
+        pairs.append(self.last_pairs(batch))
+        return r
+    ReplayEngine.sample_into = sample_into
+
+    def record(emit, tag, it, nb=NB):
+        for bi in range(nb):
+            del pairs[:]
+            for ti, t in enumerate(next(it)):
+                emit(f'{tag}{bi}.t{ti}', sha(t))
+            emit(f'{tag}{bi}.pairs', sha(np.concatenate(pairs)))
+
+    def states(seed, lengths=REPLAY_LENGTHS, meta=0):
+        return _synth.synth_episodes(seed, lengths, O, A, meta)
+
+    def frames(seed):
+        eps = _synth.synth_episodes(seed, REPLAY_LENGTHS, 3 * 8 * 8, A, obs_u8=True)
+        return [dict(ep, observation=R.stack_frames(ep['observation'].reshape(-1, 3, 8, 8), K)) for ep in eps]
+
+    def write(tmp, name, eps):
+        d = tmp / name
+        d.mkdir()
+        for i, ep in enumerate(eps):
+            R.save_episode(ep, d / f'episode_{i}_{R.episode_len(ep)}.npz')
+        return d
+
+    def online(tmp, **kw):
+        st = R.ReplayBufferStorage((), (Spec((4,), np.float32, 'skill'),), tmp / 'buffer')
+        for ep in states(21, meta=4):
+            st._store_episode(ep)
+        random.seed(3), np.random.seed(3)
+        return iter(R.make_replay_loader(st, 10**6, RB, kw.pop('num_workers', 0), True, 3, 0.99, **kw))
+
+    def offline(dirs, **kw):
+        random.seed(3), np.random.seed(3)
+        kw.setdefault('sampler', 'philox'), kw.setdefault('seed', 4)
+        return iter(R.make_offline_replay_loader(None, dirs, 10**6, RB, kw.pop('num_workers', 1), 0.99, **kw))
+
+    def body(emitter):
+        def case(name, run):
+            with tempfile.TemporaryDirectory(prefix='agent_digests_') as tmp:
+                run(emitter(f'replay/{name}'), Path(tmp))
+            print(name, flush=True)
+        case('online/mt19937/segments', lambda emit, tmp: record(emit, 'batch', online(tmp, fetch_every=5)))
+        case('online/philox/workers', lambda emit, tmp: record(emit, 'batch', online(tmp, num_workers=2, sampler='philox', seed=11,
+                                                                                     worker_ids=[0, 1])))
+        case('offline/one_dir', lambda emit, tmp: record(emit, 'batch', offline(write(tmp, 'a', states(22)))))
+        case('offline/one_dir/mt19937', lambda emit, tmp: record(emit, 'batch', offline(write(tmp, 'a', states(22)), sampler='mt19937',
+                                                                                       seed=None)))
+        for weighting in ('episodes', 'transitions'):
+            case(f'offline/mix/{weighting}', lambda emit, tmp: record(emit, 'batch', offline(
+                [write(tmp, 'a', states(22)), write(tmp, 'b', states(23, REPLAY_LENGTHS[::-1]))], mix=[0.75, 0.25], weighting=weighting)))
+        case('offline/frame_stack', lambda emit, tmp: record(emit, 'batch', offline(write(tmp, 'a', frames(24)), frame_stack=K)))
+
+        def normalized(emit, tmp):
+            it = offline(write(tmp, 'a', states(22)), num_workers=2, normalize_obs=True)
+            record(emit, 'batch', it)
+            emit('obs_normalizer', sha(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in it.obs_normalizer])))
+        case('offline/normalize_obs/two_shards', normalized)
+
+        def holdout(emit, tmp):
+            it = offline(write(tmp, 'a', states(22)), holdout_every=2)
+            record(emit, 'batch', it)
+            record(emit, 'holdout', it.holdout)
+            record(emit, 'arena', R.ArenaIterator(it.engine, RB, 1, 0.99, 'philox'))
+            emit('files', sha(','.join(fn.name for sh in it.shards for fn in [*sh.fns, *sh.holdout_fns])))
+        case('offline/holdout', holdout)
+    try:
+        listing(out, body)
+    finally:
+        ReplayEngine.sample_into = inner
+
+
 def compare(a, b):
     la, lb = Path(a).read_text().splitlines(), Path(b).read_text().splitlines()
     key = lambda l: l.rsplit(' ', 1)[0]
@@ -427,4 +524,4 @@ def compare(a, b):
 
 if __name__ == '__main__':
     cmd, args = sys.argv[1], sys.argv[2:]
-    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'pixel_modes': pixel_modes, 'compare': compare}[cmd](*args))
+    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'pixel_modes': pixel_modes, 'replay': replay, 'compare': compare}[cmd](*args))
