@@ -10,6 +10,7 @@ Reference classes mirrored (file:line in /root/reference):
   DIAYNAgent  agents/unsupervised_learning/diayn.py:32-176     ProtoAgent agents/unsupervised_learning/proto.py:46-207 (states)
   DDPGAgent with obs_type='pixels': Encoder ddpg.py:12-39, pixel Actor/Critic :42-123, update :213-328 (RandomShiftsAug utils.py:222-254)
   APSAgent    agents/unsupervised_learning/aps.py:82-320       SMMAgent   agents/unsupervised_learning/smm.py:115-281 (states)
+  IQLAgent    no reference file: implicit Q-learning on the offline nets (the class's docstring is its definition)
 
 Python here is orchestration only: it builds the initial weights with torch's CPU RNG in the reference's
 construction order (so a given torch.manual_seed yields the reference's initial parameters), hands batches
@@ -30,6 +31,7 @@ from .engine import AgentEngine, IntrEngine, PixelEngine, global_means
 _OFFLINE_ACTOR_KEYS = ['policy.0.weight', 'policy.0.bias', 'policy.1.weight', 'policy.1.bias',
                        'policy.3.weight', 'policy.3.bias', 'policy.5.weight', 'policy.5.bias']
 _OFFLINE_CRITIC_KEYS = [f'{q}.{i}.{w}' for q in ('q1_net', 'q2_net') for i in (0, 1, 3, 5) for w in ('weight', 'bias')]
+_VALUE_KEYS = [f'net.{i}.{w}' for i in (0, 1, 3, 5) for w in ('weight', 'bias')]
 _DDPG_ACTOR_KEYS = ['trunk.0.weight', 'trunk.0.bias', 'trunk.1.weight', 'trunk.1.bias',
                     'policy.0.weight', 'policy.0.bias', 'policy.2.weight', 'policy.2.bias']
 _DDPG_CRITIC_KEYS = (['trunk.0.weight', 'trunk.0.bias', 'trunk.1.weight', 'trunk.1.bias'] +
@@ -163,7 +165,7 @@ class _AgentBase:
             st = {'ctor': self._ctor, 'pixel': eng.export_state(), 'training': getattr(self, 'training', True)}
         else:
             st = {'ctor': self._ctor, 'flat': {}, 'opt_steps': eng.opt_steps(), 'training': getattr(self, 'training', True)}
-            nets = [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else [])
+            nets = [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else []) + ([L.NET_VALUE] if eng.has_value else [])
             for net in nets:
                 whats = [L.T_PARAM] if net == L.NET_CRITIC_TARGET else [L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V]
                 st['flat'][net] = {w: eng.flat(net, w).cpu() for w in whats}
@@ -174,7 +176,7 @@ class _AgentBase:
             st['intr'] = {'flat': {w: it.flat(w).cpu() for w in (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V)}, 'rms': it.rms_state(),
                           'bn': it.bn.cpu() if it.bn is not None else None, 'opt_steps': it.opt_steps(),
                           'queue': (it.queue.cpu(), it.queue_ptr()) if it.queue is not None else None, 'counter': it.counter()}
-        skip = {'engine', 'intr', 'actor', 'critic', 'critic_target', 'rnd', 'icm', 'pbe', 'intrinsic_reward_rms', 'disagreement', 'diayn',
+        skip = {'engine', 'intr', 'actor', 'critic', 'critic_target', 'value', 'rnd', 'icm', 'pbe', 'intrinsic_reward_rms', 'disagreement', 'diayn',
                 'predictor', 'predictor_target', 'projector', 'protos', 'queue', 'encoder_target', 'cat_hook', 'aps', 'smm', 'eps_hook', 'aug', 'encoder',
                 'noise_hook', 'shift_hook', '_slots', '_graph_iter', '_graph_stddev', '_ctor', 'rnd_target_encoder', '_dobs', '_dp',
                 '_metric_window'}
@@ -227,6 +229,7 @@ class _AgentBase:
             if self.KIND == 'aps':      # APSAgent builds DDPG's scalar critics first, then replaces both with CriticSF (aps.py:94-104)
                 critic0 = _mlp_init(obs_dim + action_dim, hidden_dim, engine_kw['sf_dim'], 1, 2)
                 _mlp_init(obs_dim + action_dim, hidden_dim, engine_kw['sf_dim'], 1, 2)
+        value0 = _mlp_init(obs_dim, hidden_dim, 1, 1, 1) if self.KIND == 'iql' else None      # drawn last: actor, critic, critic_target, value
         self._dp_engine(seed, lambda ws, seed: AgentEngine(self.KIND, obs_dim, action_dim, hidden_dim, batch_size, lr=lr, tau=tau, alpha=alpha,
                                                            stddev_clip=stddev_clip, precision=precision, world_size=ws, seed=seed,
                                                            device=device, **engine_kw))
@@ -237,6 +240,9 @@ class _AgentBase:
             self.critic = _net_view(self.engine, L.NET_CRITIC, keys, self.params_changed)
             self.critic_target = _net_view(self.engine, L.NET_CRITIC_TARGET, keys, self.params_changed)
             _load(self.critic, critic0)
+        if value0 is not None:
+            self.value = _net_view(self.engine, L.NET_VALUE, _VALUE_KEYS, self.params_changed)
+            _load(self.value, value0)
         self.engine.params_changed(sync_target=True)                   # critic_target.load_state_dict(critic.state_dict())
         self.engine.set_metrics(bool(getattr(self, 'use_tb', False) or getattr(self, 'use_wandb', False)))
 
@@ -271,6 +277,8 @@ class _AgentBase:
         self.actor.train(training)
         if hasattr(self, 'critic'):
             self.critic.train(training)
+        if hasattr(self, 'value'):
+            self.value.train(training)
 
     def _stddev(self, step):
         return utils.schedule(self.stddev_schedule, step)
@@ -399,7 +407,7 @@ class _AgentBase:
 
     def _run_update(self, stddev):
         """One gradient step on the loaded batch."""
-        if self.KIND == 'bc':
+        if self.KIND in ('bc', 'iql'):          # no draw in the step
             nc = na = None
         else:
             # reference draw order: critic target, then actor (SURVEY A9); CRR's second draw is (B*n, A) (crr.py:125)
@@ -557,6 +565,34 @@ class CRRAgent(_AgentBase):
         self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, stddev_clip, device, precision,
                     seed, num_value_samples=num_value_samples, weight_func=weight_func)
         self._second_noise_rows = batch_size * num_value_samples
+        self.train()
+        self.critic_target.train()
+
+
+class IQLAgent(_AgentBase):
+    """Implicit Q-learning on the offline Actor and twin Critic plus a value net V(s) (`.value`: one Q-net without the action columns, keys
+    net.{0,1,3,5}.{weight,bias}). One update() on (s, a, r, D, s'), D the sampler's discount, every forward on the parameters from before the step:
+        u = min(Q'_1, Q'_2)(s, a) - V(s);   L_V = mean(|expectile - 1[u < 0]| u^2)
+        y = r + D V(s');                    L_Q = mse(Q_1(s, a), y) + mse(Q_2(s, a), y)
+        w = min(exp(temperature u), max_weight);   L_pi = -mean(w sum_a log N(a; mu(s), std))      (CRR's actor loss with this w)
+    then Adam on value, critic and actor (all at lr) and the soft update of critic_target. Nothing is sampled: the noise counter does not
+    move and noise_hook is never called. No evaluate() and no metric window for this class."""
+    KIND = 'iql'
+    METRIC_WINDOW = False
+    METRICS = _CRITIC_METRICS + [(L.M_VALUE_LOSS, 'value_loss'), (L.M_VALUE, 'value'), (L.M_ADV, 'adv'), (L.M_ACTOR_WEIGHT, 'actor_weight')]
+
+    def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, stddev_schedule, nstep, batch_size, use_tb,
+                 expectile=0.7, temperature=3.0, max_weight=100.0, has_next_action=False, *, precision='fp32', seed=0):
+        self.action_dim = action_shape[0]
+        self.hidden_dim = hidden_dim
+        self.lr = lr
+        self.device = device
+        self.critic_target_tau = critic_target_tau
+        self.use_tb = use_tb
+        self.stddev_schedule = stddev_schedule
+        self.expectile, self.temperature, self.max_weight = expectile, temperature, max_weight
+        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, 0.0, device, precision, seed)
+        self.engine.set_iql(expectile, temperature, max_weight)
         self.train()
         self.critic_target.train()
 

@@ -368,13 +368,13 @@ using namespace exorl;
 
 struct exorl_agent {
     exorl_agent_cfg cfg;
-    NetDesc actor, critic;
-    bool has_critic = false;
+    NetDesc actor, critic, value;             // value: IQL's V(s), one Q-net without the action columns
+    bool has_critic = false, has_value = false;
     bool owns_ws = false;
     float* ws = nullptr;
     size_t ws_bytes = 0;
     // flat parameter state: [net][what]
-    float* flat[3][4] = {{nullptr}};
+    float* flat[4][4] = {{nullptr}};
     // batch slots
     float *obs = nullptr, *action = nullptr, *reward = nullptr, *discount = nullptr, *next_obs = nullptr;
     // staged inputs
@@ -387,6 +387,11 @@ struct exorl_agent {
     CqlScalars* cql = nullptr;                      // CQL: log_actor_alpha + Adam moments + alpha (device)
     float *xc_rep = nullptr, *crr_w = nullptr;     // CRR: repeated (obs, sampled action) inputs; advantage weights
     FwdBufs fr{};                                   // CRR: critic forward on B*num_value_samples rows (no grad)
+    // IQL: the value net on the stacked [next_obs; obs] rows (2B forward, B backward: the actor's arrangement), the row kernel's outputs
+    FwdBufs fv{}; BwdBufs bv{};
+    WeightImages sh_value{}; ShadowSpec spec_value{}; Partials pv{};
+    float *iql_dv = nullptr, *iql_part = nullptr;   // d L_V / d v (B); per-chunk metric sums [iql_chunks(B)][IQL_PARTS]; w goes to crr_w
+    float expectile = 0.7f, temperature = 3.0f, max_weight = 100.0f;      // exorl_agent_set_iql
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -414,7 +419,7 @@ struct exorl_agent {
     exorl_comm* comm = nullptr;
     hipStream_t comm_stream = nullptr;           // the 16-byte statistic travels here while the critic's backward pass runs
     hipEvent_t ev_stats_ready = nullptr, ev_stats_done = nullptr;
-    FinalizeArgs pend_c{}, pend_a{};             // fused optimiser launch: the partials a gradient phase left for the optimiser phase behind it
+    FinalizeArgs pend_c{}, pend_a{}, pend_v{};           // fused optimiser launch: the partials a gradient phase left for the optimiser phase behind it
     bool want_metrics = true;    // the (B,1)-sized metric reductions are skipped when the caller never reads them (use_tb=False)
     // windowed metrics (exorl_agent_set_metric_window; win_sums != nullptr is the mode): views of the caller's buffer, laid out as
     // [EXORL_N_METRICS double sums | int64 steps | pad to 256 B][qhead_chunks(B) x 6 critic partials][head_chunks(B) BC partials]
@@ -544,11 +549,29 @@ static void carve(exorl_agent* a, Carver& c) {
                          c.take(nt * (int64_t)outer_chunks(RC) * W * H)};
     }
     c.scratch = false;
+    if (cfg.kind == EXORL_AGENT_IQL) {          // behind everything the other kinds take: their layouts stay as they are
+        for (int w = 0; w < 4; ++w) a->flat[EXORL_NET_VALUE][w] = c.take(a->value.total);
+        c.scratch = true;
+        a->fv = take_fwd(2 * B, 2 * B, 1, true, true, nb);
+        a->bv = take_bwd(B, B);
+        three_planes(a->fv.h1q, 2 * B * H);
+        three_planes(a->bv.dz2q, B * H);
+        c.scratch = false;
+        a->sh_value = take_shadow(1, 1, O);
+        three_planes(a->sh_value.w1, w1_plane_size(H));
+        c.scratch = true;
+        a->pv = Partials{c.take((int64_t)head_chunks(B) * (2 * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
+                         c.take((int64_t)outer_chunks(B) * O * H)};
+        a->iql_dv = c.take(B);
+        a->crr_w = c.take(B);
+        a->iql_part = c.take((int64_t)iql_chunks(B) * IQL_PARTS);
+        c.scratch = false;
+    }
 }
 
 static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
     EXORL_REQUIRE(cfg, "agent: null cfg");
-    EXORL_REQUIRE(cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS, "agent: unknown kind %d", cfg->kind);
+    EXORL_REQUIRE((cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS) || cfg->kind == EXORL_AGENT_IQL, "agent: unknown kind %d", cfg->kind);
     EXORL_REQUIRE(cfg->kind != EXORL_AGENT_APS || (cfg->sf_dim >= 1 && cfg->sf_dim <= 16 && cfg->sf_dim < cfg->obs_dim),
                   "agent: APS needs 1 <= sf_dim <= 16 and obs_dim = observation + sf_dim (got sf_dim=%d obs_dim=%d)", cfg->sf_dim, cfg->obs_dim);
     EXORL_REQUIRE(cfg->kind != EXORL_AGENT_CQL || (cfg->n_samples >= 1 && cfg->n_samples <= 16 && cfg->act_dim <= 16),
@@ -572,6 +595,8 @@ static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
     if (a->has_critic)
         a->critic = make_net(cfg->obs_dim + cfg->act_dim, cfg->kind == EXORL_AGENT_APS ? cfg->sf_dim : 1, cfg->hidden_dim,
                              (cfg->kind == EXORL_AGENT_DDPG || cfg->kind == EXORL_AGENT_APS) ? 1 : 2, 2);
+    a->has_value = cfg->kind == EXORL_AGENT_IQL;
+    if (a->has_value) a->value = make_net(cfg->obs_dim, 1, cfg->hidden_dim, 1, 1);
     a->inv_bg = 1.0f / ((float)cfg->batch * (float)cfg->world_size);
     return 0;
 }
@@ -643,7 +668,7 @@ static int opt_step(exorl_agent* a, const Step& st, int net, const NetDesc& d, c
     if (st.fuse_opt) EXORL_TRY(finalize_adam(pend, fused_adam_args(a, net, d, c, target, bump), spec, s));
     else EXORL_TRY(adam_step_dev(f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], d.total, c, target, &spec, s, bump));
     // bf16x6 on the plane kernel: the stepped W1 (and the Polyak target's) as three planes for the next step's launches
-    EXORL_TRY(refresh_w1_planes(d, f[EXORL_T_PARAM], net == EXORL_NET_ACTOR ? a->sh_actor : a->sh_critic, s));
+    EXORL_TRY(refresh_w1_planes(d, f[EXORL_T_PARAM], net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_VALUE ? a->sh_value : a->sh_critic, s));
     if (target) EXORL_TRY(refresh_w1_planes(d, target, a->sh_target, s));
     return 0;
 }
@@ -922,6 +947,79 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
     return 0;
 }
 
+// ---- IQL: expectile value net, V-target critic, advantage-weighted actor --------------------------------
+// Every forward of the step reads the parameters as they were before it, so the four passes are independent of each other and of the three
+// optimiser steps, which all come last. Nothing is drawn. Phases 6..9:
+//   6  Q'(s, a), Q(s, a), V on [s'; s] (one 2B-row pass), the row kernel (dv, dq, w, metric partials), value backward on the s rows -> value grads
+//   7  critic backward from dq -> critic grads
+//   8  actor forward on s and the weighted log-likelihood backward (CRR's actor path with w) -> actor grads
+//   9  Adam on value, critic (Polyak target fused into its pass) and actor
+static int iql_phase6(exorl_agent* a, const Step& st) {
+    const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
+    if (!st.staged)
+        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, a->state,
+                                 st.capture ? 1 : 0, s));
+    a->actor_t += 1;
+    a->critic_t += 1;
+    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
+    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
+    const float* Pv = a->flat[EXORL_NET_VALUE][EXORL_T_PARAM];
+    const Fork& fk = st.fk;
+    if (!fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
+        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_cur, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s));
+    } else {
+        EXORL_TRY(fk.fork(s));                  // the target's and the critic's forwards on (s, a) are independent
+        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_cur, W, B, a->ft, false, false, prec, fk.side(s)));
+        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, true, false, prec, s));
+        EXORL_TRY(fk.join(s));
+    }
+    EXORL_TRY(net_forward(a->value, Pv, a->sh_value, a->xa, O, 2 * B, a->fv, true, false, prec, s));      // rows 0..B-1: V(s'), B..2B-1: V(s)
+    IqlRowsArgs r{a->ft.out, a->fc.out, a->fv.out + B, a->fv.out, a->reward, a->discount, a->iql_dv, a->dq, a->crr_w, a->iql_part, B,
+                  a->inv_bg, a->expectile, a->temperature, a->max_weight};
+    EXORL_TRY(iql_rows(r, s));
+    if (st.metric_kernels) EXORL_TRY(iql_sums(a->iql_part, B, a->inv_bg, nullptr, a->metrics, s));
+    DoutSpec d{};
+    d.mode = EXORL_DOUT_BUFFER; d.buf = a->iql_dv;
+    return net_backward(a->value, Pv, a->sh_value, a->flat[EXORL_NET_VALUE][EXORL_T_GRAD], a->pv, a->xa + (int64_t)B * O, O, B,
+                        a->fv.rows_from(B, H, 1), d, a->bv, nullptr, 0, 0, prec, s, fk, st.fuse_opt ? &a->pend_v : nullptr);
+}
+
+static int iql_phase7(exorl_agent* a, const Step& st) {
+    const auto& cfg = a->cfg;
+    const int B = cfg.batch, W = cfg.obs_dim + cfg.act_dim;
+    DoutSpec d{};
+    d.mode = EXORL_DOUT_BUFFER; d.buf = a->dq;
+    return net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc,
+                        a->xc_cur, W, B, a->fc, d, a->bc, nullptr, 0, 0, cfg.precision, st.s, st.fk, st.fuse_opt ? &a->pend_c : nullptr);
+}
+
+static int iql_phase8(exorl_agent* a, const Step& st) {
+    const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, H = cfg.hidden_dim, prec = cfg.precision;
+    const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
+    const float* x = a->xa + (int64_t)B * O;
+    const FwdBufs f = a->fa.rows_from(B, H, A);       // the obs half, as BC runs it: the only actor forward of the step
+    EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, x, O, B, f, true, true, prec, s));
+    if (st.metric_kernels)                      // actor_loss = -(w * log N(a; mu, std)).mean(): CRR's metric with IQL's weights
+        EXORL_TRY(actor_dmu(a->da, A, 0, 0, f.out, a->action, nullptr, a->crr_w, a->dpre, a->stats, a->metrics, B, A, a->inv_bg, 0.f,
+                            EXORL_AGENT_CRR, st.stddev, s, &a->state->stddev));
+    DoutSpec dm{};
+    dm.mode = EXORL_DOUT_ACTOR_MU; dm.mu = f.out; dm.a_data = a->action; dm.kind = EXORL_AGENT_CRR; dm.inv_bg = a->inv_bg;
+    dm.stddev = st.stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
+    return net_backward(a->actor, Pa, a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa, x, O, B, f, dm, a->ba, nullptr, 0, 0, prec, s,
+                        st.fk, st.fuse_opt ? &a->pend_a : nullptr);
+}
+
+static int iql_phase9(exorl_agent* a, const Step& st) {
+    // the value net steps with the critic (one step count, exorl_agent_opt_steps): it reads the critic's Adam scalars and has no target
+    EXORL_TRY(opt_step(a, st, EXORL_NET_VALUE, a->value, a->pend_v, &a->state->critic, nullptr, a->spec_value, nullptr));
+    EXORL_TRY(opt_step_critic(a, st));
+    return phase3(a, st);
+}
+
 // ---- the step as a plan -----------------------------------------------------------------------------
 // One update is the ordered list of its phases; where the data-parallel step (dp) needs a global batch quantity before the next phase, the plan
 // names the exchange that follows (EXORL_AGENT_XCHG_*, each a sum all-reduce), else -1. Both drivers read it: whole_step_body, which runs the
@@ -930,6 +1028,7 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
 //   statistics         after phase 1: TD3+BC's sum |Q| behind lambda (td3_bc.py:154), unless phase 2 reduces it itself on the side stream
 //                      (stats_in_phase2); CQL's sum of log pi for the entropy temperature (cql.py:242-243)
 //   actor gradients    after phase 2
+//   IQL                value, critic and actor gradients after phases 6, 7 and 8; phase 9 steps all three nets
 // CQL's Lagrange multiplier steps on the penalty of the GLOBAL batch inside phase 0 (cql.py:199-213): data parallel, phases 4 and 5 stand for
 // phase 0 with the statistics (this rank's penalty sums) exchanged in between.
 struct AgentPlan {
@@ -941,6 +1040,13 @@ static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_pha
     const int kind = c.kind;
     auto after = [&](bool on, int x) { return dp && on ? x : -1; };
     AgentPlan p;
+    if (kind == EXORL_AGENT_IQL) {      // three gradient sums and no batch statistic
+        p.add(6, after(true, EXORL_AGENT_XCHG_VALUE_GRAD));
+        p.add(7, after(true, EXORL_AGENT_XCHG_CRITIC_GRAD));
+        p.add(8, after(true, EXORL_AGENT_XCHG_ACTOR_GRAD));
+        p.add(9);
+        return p;
+    }
     if (dp && kind == EXORL_AGENT_CQL && c.use_critic_lagrange) {
         p.add(4, EXORL_AGENT_XCHG_STATS);
         p.add(5, EXORL_AGENT_XCHG_CRITIC_GRAD);
@@ -963,6 +1069,16 @@ static int run_phase(exorl_agent* a, const Step& st, int phase) {
             case 4: return cql_phase0a(a, st, true);       // use_critic_lagrange under data parallelism: phase 0 up to the penalty sums ...
             case 5: return cql_phase0b(a, st, true);       // ... and from the global penalty on
         }
+    }
+    if (a->cfg.kind == EXORL_AGENT_IQL) {
+        switch (phase) {
+            case 6: return iql_phase6(a, st);
+            case 7: return iql_phase7(a, st);
+            case 8: return iql_phase8(a, st);
+            case 9: return iql_phase9(a, st);
+        }
+        set_error("agent_update_phase: phase %d is not one of IQL's (6..9, exorl_agent_update_plan)", phase);
+        return 2;
     }
     switch (phase) {
         case 0: return phase0(a, st);
@@ -996,6 +1112,7 @@ static int whole_step_body(exorl_agent* a, const Step& st) {
             case EXORL_AGENT_XCHG_CRITIC_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->critic.total, st.s)); break;
             case EXORL_AGENT_XCHG_STATS: EXORL_TRY(comm_allreduce_sum(a->comm, a->stats, 4, st.s)); break;
             case EXORL_AGENT_XCHG_ACTOR_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->actor.total, st.s)); break;
+            case EXORL_AGENT_XCHG_VALUE_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_VALUE][EXORL_T_GRAD], a->value.total, st.s)); break;
         }
     }
     if (a->win_sums) EXORL_TRY(run_metrics_window(a, st));      // the step's metrics into the window (and, on the fused path, into a->metrics)
@@ -1048,9 +1165,11 @@ int exorl_agent_create(const exorl_agent_cfg* cfg, void* workspace, size_t works
     carve(a, c);
     a->spec_actor = shadow_spec(a->actor, a->sh_actor, nullptr);
     if (a->has_critic) a->spec_critic = shadow_spec(a->critic, a->sh_critic, &a->sh_target);
+    if (a->has_value) a->spec_value = shadow_spec(a->value, a->sh_value, nullptr);
     StepState st{};
     st.lr = dec7(cfg->lr); st.b1 = 0.9; st.b2 = 0.999; st.eps = 1e-8; st.tau = dec7(cfg->tau);      // torch.optim.Adam defaults
     st.has_critic = a->has_critic ? 1 : 0;
+    st.no_noise = cfg->kind == EXORL_AGENT_IQL ? 1 : 0;
     st.b1t = st.b2t = st.b1t_c = st.b2t_c = 1.0;
     if (a->cql) { CqlScalars sc{0.f, 0.f, 0.f, 1.0f}; (void)hipMemcpy(a->cql, &sc, sizeof(sc), hipMemcpyHostToDevice); }
     e = hipMemcpy(a->state, &st, sizeof(st), hipMemcpyHostToDevice);
@@ -1073,6 +1192,7 @@ int exorl_agent_destroy(exorl_agent_t* a) {
 static const NetDesc* net_of(exorl_agent_t* a, int32_t net) {
     if (net == EXORL_NET_ACTOR) return &a->actor;
     if ((net == EXORL_NET_CRITIC || net == EXORL_NET_CRITIC_TARGET) && a->has_critic) return &a->critic;
+    if (net == EXORL_NET_VALUE && a->has_value) return &a->value;
     return nullptr;
 }
 
@@ -1119,6 +1239,10 @@ int exorl_agent_params_changed(exorl_agent_t* a, int32_t sync_target, void* stre
         EXORL_TRY(refresh_w1_planes(a->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->sh_target, s));
     }
     EXORL_TRY(refresh_w1_planes(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, s));
+    if (a->has_value) {
+        EXORL_TRY(refresh_shadows(a->flat[EXORL_NET_VALUE][EXORL_T_PARAM], a->value.total, a->spec_value, false, s));
+        EXORL_TRY(refresh_w1_planes(a->value, a->flat[EXORL_NET_VALUE][EXORL_T_PARAM], a->sh_value, s));
+    }
     return 0;
 }
 
@@ -1369,6 +1493,7 @@ int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream) {
     hipStream_t s = as_stream(stream);
     exorl_agent layout;              // a second carve over the same configuration: same offsets, nothing of `a` is touched
     layout.cfg = a->cfg; layout.actor = a->actor; layout.critic = a->critic; layout.has_critic = a->has_critic;
+    layout.value = a->value; layout.has_value = a->has_value;
     std::vector<std::pair<int64_t, int64_t>> runs;
     Carver c(nullptr);
     c.fill = &runs;
@@ -1382,7 +1507,7 @@ int exorl_debug_agent_weight_images(exorl_agent_t* a, int32_t net, exorl_weight_
     EXORL_REQUIRE(a && out, "debug_agent_weight_images: null argument");
     const NetDesc* d = net_of(a, net);
     EXORL_REQUIRE(d, "debug_agent_weight_images: agent has no net %d", net);
-    const WeightImages& sh = net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_CRITIC ? a->sh_critic : a->sh_target;
+    const WeightImages& sh = net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_CRITIC ? a->sh_critic : net == EXORL_NET_VALUE ? a->sh_value : a->sh_target;
     *out = exorl_weight_images{d->n_trunks, d->n_heads, d->in_dim, d->H, sh.w0t, sh.w0.hi, sh.w0.lo, sh.w1.hi, sh.w1.mid, sh.w1.lo};
     return 0;
 }
@@ -1401,6 +1526,17 @@ int exorl_agent_cql_alpha(exorl_agent_t* a, float* host, int32_t set) {
             h[0] = sc.log_alpha; h[1] = sc.m; h[2] = sc.v;
         }
     }
+    return 0;
+}
+
+int exorl_agent_set_iql(exorl_agent_t* a, float expectile, float temperature, float max_weight) {
+    // the values first: a bad triple is refused whatever the handle is (NaN fails every comparison)
+    EXORL_REQUIRE(expectile > 0.f && expectile < 1.f && temperature >= 0.f && max_weight > 0.f,
+                  "agent_set_iql: needs 0 < expectile < 1, temperature >= 0 and max_weight > 0 (got %g, %g, %g)", expectile, temperature, max_weight);
+    EXORL_REQUIRE(a, "agent_set_iql: null handle");
+    EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_IQL, "agent_set_iql: kind %d is not IQL", a->cfg.kind);
+    EXORL_REQUIRE(!a->graph_exec, "agent_set_iql: disable the captured graph first (it holds the values as kernel arguments)");
+    a->expectile = expectile; a->temperature = temperature; a->max_weight = max_weight;
     return 0;
 }
 
@@ -1431,6 +1567,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
         a->win_sums = nullptr; a->win_steps = nullptr; a->win_crit = a->win_bc = nullptr;
         return 0;
     }
+    EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_IQL, "agent_set_metric_window: IQL has no metric window");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     const size_t need = window_bytes(a->cfg);

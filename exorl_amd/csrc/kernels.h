@@ -325,6 +325,7 @@ struct StepState {
     int has_critic;
     float stddev;                // exploration std of the step (utils.schedule value): read through a pointer, so a schedule
                                  // that moves every step needs no re-capture of the hipGraph
+    int no_noise;                // 1: the kind's update() draws nothing and the noise counter stays put (IQL); 0 keeps the bytes every other kind has
 };
 
 // The same for an intrinsic-reward module (intr.hip): what changes from one exorl_intr_update to the next. The host keeps the truth
@@ -419,7 +420,7 @@ __host__ __device__ inline void fill_adam_const(AdamConst& c, double b1t, double
 // One thread: advance the counters and pre-compute both optimisers' scalars for this step.
 __device__ inline void step_begin_device(StepState* st, int advance_replay) {
     if (advance_replay) st->replay_counter += 1;
-    st->noise_counter += 2;
+    if (!st->no_noise) st->noise_counter += 2;
     st->t_actor += 1;
     st->b1t *= st->b1;
     st->b2t *= st->b2;
@@ -489,6 +490,22 @@ int repeat_sample(const float* obs, const float* mu, const float* noise, uint64_
                   float stddev, float clip, float* xc_rep, int B, int O, int A, int n, hipStream_t s, const float* stddev_ptr = nullptr);
 // w_b = f(min(Q1,Q2)(s_b, a_b) - mean_i min(Q1,Q2)(s_b, a_bi))
 int crr_weights(const float* q_rep, const float* q_data, float* w, int B, int n, int weight_func, hipStream_t s);
+// IQL's row kernel (loss.hip, iql_rows_kernel): from the target heads tq (2, rows), the critic heads q (2, rows), v = V(s), vn = V(s'), reward and
+// discount, in one pass: dv (rows) = d L_V / d v, dq (2, rows) = d L_Q / d Q_j, w (rows) = the actor step's advantage weights, and per chunk of
+// IQL_CHUNK_ROWS rows the IQL_PARTS sums below. iql_sums adds them in chunk order: into sums (raw, IQL_P_* order) and / or as partial means over
+// the global batch into metrics' EXORL_M_* slots; either may be null.
+constexpr int IQL_CHUNK_ROWS = 256;
+constexpr int IQL_MAX_WG = 32;               // above 32 chunks (8192 rows) a workgroup takes a second chunk
+enum { IQL_P_REWARD, IQL_P_TARGET, IQL_P_Q1, IQL_P_Q2, IQL_P_ERR1, IQL_P_ERR2, IQL_P_VLOSS, IQL_P_V, IQL_P_ADV, IQL_P_W, IQL_PARTS };
+__host__ __device__ inline int iql_chunks(int rows) { return (rows + IQL_CHUNK_ROWS - 1) / IQL_CHUNK_ROWS; }
+struct IqlRowsArgs {
+    const float *tq, *q, *v, *vn, *reward, *discount;
+    float *dv, *dq, *w, *part;               // part: [iql_chunks(rows)][IQL_PARTS]
+    int rows;
+    float inv_bg, expectile, temperature, max_weight;
+};
+int iql_rows(const IqlRowsArgs& a, hipStream_t s);
+int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
 int critic_loss(const float* q, const float* tq, const float* reward, const float* discount, float* dq,
                 float* metrics, int B, float inv_bg, hipStream_t s);
 int actor_stats(const float* q, float* stats, int B, hipStream_t s);

@@ -710,7 +710,96 @@ int eval_reduce(const EvalArgs& e, hipStream_t s) {
     return 0;
 }
 
+// ---- IQL: the five head outputs of a step -> all three loss gradients, the advantage weights and the metrics' per-chunk sums, one pass --------
+// One thread per row, IQL_CHUNK_ROWS rows per chunk; at most IQL_MAX_WG workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...
+// The partials are per chunk, not per workgroup, so the sums do not depend on the grid. Rows past the end add zeros.
+//   u = min(Q'_1, Q'_2)(s, a) - V(s);  k = u < 0 ? 1 - expectile : expectile;  dV = -2 k u / Bg          (expectile regression of V on Q')
+//   y = r + D V(s');                   dQ_j = 2 (Q_j - y) / Bg, with Q_j - (r + D V(s')) formed in double and rounded once: where Q_j is close
+//                                      to y the difference cancels, and two fp32 roundings at the size of y would be many ulp of the result
+//   w = expf(temperature u), max_weight where that is larger: an expf that overflows is +inf and gives max_weight exactly; a NaN u (a diverged
+//                                      net) stays NaN in w, as it does in dv and dq, rather than turning into max_weight
+static_assert(IQL_CHUNK_ROWS == 256, "iql_rows_kernel: one thread per row of the chunk");
+__global__ __launch_bounds__(256) void iql_rows_kernel(const IqlRowsArgs a) {
+    __shared__ float sm[IQL_PARTS][16];
+    const int chunks = iql_chunks(a.rows);
+    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+        const int m = ch * IQL_CHUNK_ROWS + threadIdx.x;
+        float p[IQL_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (m < a.rows) {
+            const float v = a.v[m], r = a.reward[m];
+            const float u = fminf(a.tq[m], a.tq[a.rows + m]) - v;
+            const float k = u < 0.f ? 1.0f - a.expectile : a.expectile;
+            a.dv[m] = -2.0f * k * u * a.inv_bg;
+            const float y = r + a.discount[m] * a.vn[m];
+            const float q1 = a.q[m], q2 = a.q[a.rows + m];
+            const double yd = (double)r + (double)a.discount[m] * (double)a.vn[m];
+            const float e1 = (float)((double)q1 - yd), e2 = (float)((double)q2 - yd);
+            a.dq[m] = 2.0f * e1 * a.inv_bg;
+            a.dq[a.rows + m] = 2.0f * e2 * a.inv_bg;
+            const float ex = expf(a.temperature * u);
+            const float w = ex > a.max_weight ? a.max_weight : ex;
+            a.w[m] = w;
+            p[IQL_P_REWARD] = r; p[IQL_P_TARGET] = y; p[IQL_P_Q1] = q1; p[IQL_P_Q2] = q2; p[IQL_P_ERR1] = e1 * e1; p[IQL_P_ERR2] = e2 * e2;
+            p[IQL_P_VLOSS] = k * u * u; p[IQL_P_V] = v; p[IQL_P_ADV] = u; p[IQL_P_W] = w;
+        }
+        block_sum<IQL_PARTS>(p, sm);
+#pragma unroll
+        for (int i = 0; i < IQL_PARTS; ++i)       // constant indices: p stays in registers
+            if (threadIdx.x == i) a.part[(int64_t)ch * IQL_PARTS + i] = p[i];
+    }
+}
+
+// One wave. Thread i < IQL_PARTS adds quantity i's partials in chunk order (chunk_sum): no atomics, the same bits on every run. sums (the unit
+// export): the raw sums. metrics (the step): the partial means over the global batch in their EXORL_M_* slots.
+__global__ __launch_bounds__(64) void iql_sums_kernel(const float* __restrict__ part, int chunks, float inv_bg, float* __restrict__ sums,
+                                                      float* __restrict__ metrics) {
+    __shared__ float tot[IQL_PARTS];
+    const int t = threadIdx.x;
+    const float sum = chunk_sum(part + (t < IQL_PARTS ? t : 0), t < IQL_PARTS ? chunks : 0, IQL_PARTS);
+    if (t < IQL_PARTS) {
+        tot[t] = sum;
+        if (sums) sums[t] = sum;
+    }
+    __syncthreads();
+    if (t == 0 && metrics) {
+        metrics[EXORL_M_BATCH_REWARD] = tot[IQL_P_REWARD] * inv_bg;
+        metrics[EXORL_M_CRITIC_TARGET_Q] = tot[IQL_P_TARGET] * inv_bg;
+        metrics[EXORL_M_CRITIC_Q1] = tot[IQL_P_Q1] * inv_bg;
+        metrics[EXORL_M_CRITIC_Q2] = tot[IQL_P_Q2] * inv_bg;
+        metrics[EXORL_M_CRITIC_LOSS] = (tot[IQL_P_ERR1] + tot[IQL_P_ERR2]) * inv_bg;
+        metrics[EXORL_M_VALUE_LOSS] = tot[IQL_P_VLOSS] * inv_bg;
+        metrics[EXORL_M_VALUE] = tot[IQL_P_V] * inv_bg;
+        metrics[EXORL_M_ADV] = tot[IQL_P_ADV] * inv_bg;
+        metrics[EXORL_M_ACTOR_WEIGHT] = tot[IQL_P_W] * inv_bg;
+    }
+}
+
+int iql_rows(const IqlRowsArgs& a, hipStream_t s) {
+    const int chunks = iql_chunks(a.rows);
+    hipLaunchKernelGGL(iql_rows_kernel, dim3(chunks < IQL_MAX_WG ? chunks : IQL_MAX_WG), dim3(IQL_CHUNK_ROWS), 0, s, a);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
+    hipLaunchKernelGGL(iql_sums_kernel, dim3(1), dim3(64), 0, s, part, iql_chunks(rows), inv_bg, sums, metrics);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace exorl
+
+extern "C" int32_t exorl_iql_rows_chunks(int32_t rows) { return rows > 0 ? exorl::iql_chunks(rows) : 0; }
+
+extern "C" int exorl_iql_rows(const float* tq, const float* q, const float* v, const float* v_next, const float* reward, const float* discount,
+                              int32_t rows, float inv_bg, float expectile, float temperature, float max_weight, float* dv, float* dq, float* w,
+                              float* part, float* sums, void* stream) {
+    using namespace exorl;
+    EXORL_REQUIRE(tq && q && v && v_next && reward && discount && dv && dq && w && part && sums && rows > 0, "iql_rows: bad arguments");
+    IqlRowsArgs a{tq, q, v, v_next, reward, discount, dv, dq, w, part, rows, inv_bg, expectile, temperature, max_weight};
+    EXORL_TRY(iql_rows(a, as_stream(stream)));
+    return iql_sums(part, rows, inv_bg, sums, nullptr, as_stream(stream));
+}
 
 extern "C" int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float* out_dev, void* stream) {
     using namespace exorl;

@@ -13,10 +13,16 @@ from . import _lib as L
 
 KIND = {'td3_bc': L.AGENT_TD3_BC, 'td3': L.AGENT_TD3, 'bc': L.AGENT_BC, 'ddpg': L.AGENT_DDPG, 'crr': L.AGENT_CRR, 'cql': L.AGENT_CQL,
         'aps': L.AGENT_APS}
+KIND_BEYOND_REFERENCE = {'iql': L.AGENT_IQL}        # kinds the reference does not have; KIND stays the reference's seven
 PRECISION = {'fp32': L.PREC_F32, 'f32': L.PREC_F32, 'bf16': L.PREC_BF16, 'bf16x3': L.PREC_BF16X3, 'bf16x6': L.PREC_BF16X6}
 METRIC_KEYS = {L.M_BATCH_REWARD: 'batch_reward', L.M_CRITIC_TARGET_Q: 'critic_target_q', L.M_CRITIC_Q1: 'critic_q1',
                L.M_CRITIC_Q2: 'critic_q2', L.M_CRITIC_LOSS: 'critic_loss', L.M_ACTOR_LOSS: 'actor_loss',
                L.M_ACTOR_LOGPROB: 'actor_logprob'}
+
+
+def kind_id(name):
+    """EXORL_AGENT_* of an agent kind by name: the one lookup, over the reference's kinds and the ones beyond it."""
+    return KIND[name] if name in KIND else KIND_BEYOND_REFERENCE[name]
 
 
 def _require_gpu(device):
@@ -101,13 +107,14 @@ class AgentEngine(_Phased):
                  n_samples=3, use_critic_lagrange=False, target_cql_penalty=5.0, sf_dim=0):
         self.device = _require_gpu(device)
         self.kind = kind
-        cfg = L.AgentCfg(KIND[kind], obs_dim, act_dim, hidden_dim, batch, PRECISION[precision], world_size, sf_dim,
+        cfg = L.AgentCfg(kind_id(kind), obs_dim, act_dim, hidden_dim, batch, PRECISION[precision], world_size, sf_dim,
                               lr, tau, alpha, stddev_clip if stddev_clip is not None else 0.0, seed, num_value_samples,
                               L.CRR_WEIGHT[weight_func], n_samples, int(bool(use_critic_lagrange)), target_cql_penalty, 0)
         self.obs_dim, self.act_dim, self.hidden_dim, self.batch = obs_dim, act_dim, hidden_dim, batch
         self.world_size = world_size
         self._create('agent', cfg)
         self.has_critic = kind != 'bc'
+        self.has_value = kind == 'iql'
 
     def flat(self, net, what=L.T_PARAM):
         p, n = C.c_void_p(), C.c_int64()
@@ -159,13 +166,14 @@ class AgentEngine(_Phased):
         """The buffer of exchange `xid` (L.AGENT_XCHG_*); every one is sum-all-reduced in place."""
         if xid == L.AGENT_XCHG_STATS:
             return self.stats()
-        return self.flat({L.AGENT_XCHG_CRITIC_GRAD: L.NET_CRITIC, L.AGENT_XCHG_ACTOR_GRAD: L.NET_ACTOR}[xid], L.T_GRAD)
+        return self.flat({L.AGENT_XCHG_CRITIC_GRAD: L.NET_CRITIC, L.AGENT_XCHG_ACTOR_GRAD: L.NET_ACTOR, L.AGENT_XCHG_VALUE_GRAD: L.NET_VALUE}[xid],
+                         L.T_GRAD)
 
     def update_steps(self, stddev, noise_critic=None, noise_actor=None):
         """update() as its phases, for run_steps: yields the (buffer, op) to exchange across the ranks before the next phase. The library
         names the phases and the exchange behind each (exorl_agent_update_plan): the critic's gradients, the batch statistic of the
         kinds that have one (TD3+BC's lambda; CQL's sum of log_pi for the entropy temperature and, with the Lagrange weight, the penalty
-        sums between phases 4 and 5), the actor's gradients."""
+        sums between phases 4 and 5), the actor's gradients; for IQL the value net's, the critic's and the actor's gradients."""
         phases, xids, n = (C.c_int32 * 8)(), (C.c_int32 * 8)(), C.c_int32()
         L.check(self.lib.exorl_agent_update_plan(C.byref(self.cfg), phases, xids, 8, C.byref(n)))
         for phase, xid in zip(phases[:n.value], xids[:n.value]):
@@ -331,6 +339,10 @@ class AgentEngine(_Phased):
     def set_cql_alpha_state(self, log_alpha, m=0.0, v=0.0, log_critic_alpha=0.0, cm=0.0, cv=0.0):
         host = np.array([log_alpha, m, v, log_critic_alpha, cm, cv], np.float32)
         L.check(self.lib.exorl_agent_cql_alpha(self.h, host.ctypes.data, 1))
+
+    def set_iql(self, expectile, temperature, max_weight):
+        """IQL's hyper-parameters (exorl_agent_set_iql); refused while a graph is captured."""
+        L.check(self.lib.exorl_agent_set_iql(self.h, expectile, temperature, max_weight))
 
     def metrics_raw(self):
         host = np.zeros(L.N_METRICS, np.float32)

@@ -17,7 +17,7 @@ from collections import OrderedDict
 
 import torch
 
-NETS = ('encoder', 'actor', 'critic', 'critic_target', 'rnd', 'icm', 'disagreement', 'diayn', 'aps', 'smm', 'predictor',
+NETS = ('encoder', 'actor', 'critic', 'critic_target', 'value', 'rnd', 'icm', 'disagreement', 'diayn', 'aps', 'smm', 'predictor',
         'predictor_target', 'projector', 'protos', 'encoder_target')
 
 

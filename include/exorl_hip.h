@@ -169,6 +169,11 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_AGENT_CQL    5   /* agents/offline_learning/cql.py:59-286 */
 #define EXORL_AGENT_APS    6   /* agents/unsupervised_learning/aps.py:12-60,268-320: DDPG with the successor-feature critic
                                   (heads emit sf_dim features, Q = task . features; the task is the last sf_dim columns of obs) */
+/* kind 7 is unassigned and refused */
+#define EXORL_AGENT_IQL    8   /* implicit Q-learning, no reference file: a value net V(s) regressed on min Q'(s, a) by expectile regression,
+                                  critics regressed on r + D V(s'), actor by the advantage-weighted log-likelihood (CRR's actor step with
+                                  w = min(exp(temperature (min Q' - V)), max_weight)). Hyper-parameters: exorl_agent_set_iql. update() draws no
+                                  noise: the noise arguments are ignored and the Philox counter stays where it is. */
 
 #define EXORL_CRR_IDENTITY  0   /* crr.py:132-142 adv_transform */
 #define EXORL_CRR_INDICATOR 1
@@ -191,6 +196,7 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_NET_ACTOR         0
 #define EXORL_NET_CRITIC        1
 #define EXORL_NET_CRITIC_TARGET 2
+#define EXORL_NET_VALUE         3   /* IQL only: Linear(O,H) LayerNorm Tanh Linear(H,H) ReLU Linear(H,1), keys net.{0,1,3,5}.{weight,bias} */
 
 #define EXORL_T_PARAM 0
 #define EXORL_T_GRAD  1
@@ -213,6 +219,12 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_M_ACTOR_ALPHA       12
 #define EXORL_M_ACTOR_ALPHA_LOSS  13
 #define EXORL_M_ACTOR_ENT         14
+/* EXORL_AGENT_IQL only: slots 10..13 carry IQL's own quantities (the four names above are CQL's and mean nothing for IQL). Slots 0..5 keep
+ * their meaning, with critic_target_q = mean of y = r + D V(s'). */
+#define EXORL_M_VALUE_LOSS   10   /* (1/Bg) sum k u^2, u = min Q'(s, a) - V(s), k = u < 0 ? 1 - expectile : expectile */
+#define EXORL_M_VALUE        11   /* mean V(s) */
+#define EXORL_M_ADV          12   /* mean u */
+#define EXORL_M_ACTOR_WEIGHT 13   /* mean w */
 #define EXORL_N_METRICS        16
 
 typedef struct {
@@ -268,6 +280,9 @@ int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_critic
  *   phase 3 -> actor Adam done
  *   phase 4 -> CQL, phase 0's first half: forwards done, this rank's penalty sums in the stats buffer
  *   phase 5 -> CQL, phase 0's second half: multiplier stepped from the global penalty (cql.py:199-213), critic grads
+ *   phase 6 -> IQL: Q'(s,a), Q(s,a), V on [s'; s], the row kernel (dv, dq, w, metric sums), value grads
+ *   phase 7 -> IQL: critic grads          phase 8 -> IQL: actor forward on s, actor grads
+ *   phase 9 -> IQL: Adam on value, critic (+ soft update) and actor. IQL runs phases 6..9 only; the other kinds refuse them.
  * Which phases a configuration's step runs, in which order, and which exchange follows each: exorl_agent_update_plan. Phase 0 is refused for
  * CQL with use_critic_lagrange and world_size > 1 (phases 4 and 5 stand for it). */
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_critic_dev,
@@ -278,6 +293,7 @@ int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, cons
 #define EXORL_AGENT_XCHG_CRITIC_GRAD 0   /* exorl_agent_flat(EXORL_NET_CRITIC, EXORL_T_GRAD) */
 #define EXORL_AGENT_XCHG_STATS       1   /* exorl_agent_stats_buffer */
 #define EXORL_AGENT_XCHG_ACTOR_GRAD  2   /* exorl_agent_flat(EXORL_NET_ACTOR, EXORL_T_GRAD) */
+#define EXORL_AGENT_XCHG_VALUE_GRAD  3   /* exorl_agent_flat(EXORL_NET_VALUE, EXORL_T_GRAD): IQL, after phase 6 */
 int exorl_agent_update_plan(const exorl_agent_cfg* cfg, int32_t* phases, int32_t* exchanges, int32_t capacity, int32_t* n);
 int exorl_agent_stats_buffer(exorl_agent_t* a, void** ptr_dev, int64_t* numel);
 /* Attach a communicator of cfg.world_size ranks (NULL detaches): exorl_agent_update then runs the four phases AND the all-reduces
@@ -287,6 +303,10 @@ int exorl_agent_set_comm(exorl_agent_t* a, exorl_comm_t* c);
 /* CQL: entropy temperature state (log_actor_alpha and its Adam moments), host <-> device: host[0..2]; with
  * use_critic_lagrange also host[3..5] = log_critic_alpha and its Adam moments (pass a 6-float array). */
 int exorl_agent_cql_alpha(exorl_agent_t* a, float* log_alpha_host, int32_t set);
+/* IQL's hyper-parameters (at creation: expectile 0.7, temperature 3.0, max_weight 100.0). Refuses, in this order: expectile outside (0, 1),
+ * temperature < 0 or max_weight <= 0 (or NaN); a null handle; a kind other than EXORL_AGENT_IQL; a handle with a captured graph (the graph
+ * holds the values: disable it, set, capture again). */
+int exorl_agent_set_iql(exorl_agent_t* a, float expectile, float temperature, float max_weight);
 /* Policy inference for n rows: out = mean (eval) or TruncatedNormal sample (clip=None). */
 int exorl_agent_act(exorl_agent_t* a, const float* obs_dev, int32_t n, float stddev, int32_t eval_mode,
                     const float* noise_dev, float* action_out_dev, void* stream);
@@ -345,6 +365,7 @@ int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_hos
 /* Captured graphs run independent parts of the step (target || critic forward, wgrad || dgrad chain) as parallel
  * branches on a second stream (default: off — one chain measured faster on MI355X). */
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable);
+/* IQL's value net always steps with the critic: critic_steps is its Adam step count too. */
 int exorl_agent_opt_steps(exorl_agent_t* a, int64_t* actor_steps, int64_t* critic_steps);
 int exorl_agent_set_opt_steps(exorl_agent_t* a, int64_t actor_steps, int64_t critic_steps);
 /* Captures exorl_replay_sample(PHILOX) into the agent's batch slots + exorl_agent_update into one hipGraph;
@@ -445,6 +466,14 @@ int exorl_ln_tanh_fwd(const float* z_dev, const float* gain_dev, const float* be
  * k <= 64; up to 4096 targets a wave holds a row of distances in LDS, above it walks the row in fixed chunks with a running top-k. */
 int exorl_knn_topk(const float* src_dev, int32_t n_src, const float* tgt_dev, int32_t n_tgt, int32_t dim,
                    int32_t k, float* out_dev, void* stream);
+/* IQL's row kernel on caller-made rows (unit test hook): tq, q (2, rows) target and critic heads, v = V(s), v_next = V(s'), reward, discount
+ * (rows) in; dv (rows), dq (2, rows), w (rows) out as the step forms them (EXORL_AGENT_IQL above), and sums[10] = the sums over the rows of
+ * r, y, Q_1, Q_2, (Q_1 - y)^2, (Q_2 - y)^2, k u^2, v, u, w, added per chunk in chunk order with no atomics (the same bits on every run).
+ * part: scratch of 10 * exorl_iql_rows_chunks(rows) floats. */
+int32_t exorl_iql_rows_chunks(int32_t rows);
+int exorl_iql_rows(const float* tq_dev, const float* q_dev, const float* v_dev, const float* v_next_dev, const float* reward_dev,
+                   const float* discount_dev, int32_t rows, float inv_bg, float expectile, float temperature, float max_weight,
+                   float* dv_dev, float* dq_dev, float* w_dev, float* part_dev, float* sums_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Intrinsic-reward modules of the reward-free DDPG-backbone agents (states observations).

@@ -10,6 +10,9 @@
     python tools/micro/offline_bench.py td3_bc 24 6 1024 bf16x3 --weighting transitions --episodes 10000 --steps 2000 --warmup 200 --repeats 3
         # --weighting episodes|transitions: the weighted sampler (ReplayEngine.set_weights; the cum table and its binary search); default
         # off: set_weights is never called. --episodes E (default 300) x --ep-len T (default 1000) transitions resident.
+    python tools/micro/offline_bench.py iql 24 6 1024 bf16x3,fp32 --steps 2000 --warmup 200 --repeats 3      # IQLAgent at its defaults
+    python tools/micro/offline_bench.py crr 24 6 1024 bf16x3,fp32 --weight-func exp --steps 2000 --warmup 200 --repeats 3
+        # --weight-func identity|indicator|exp: CRR's advantage transform (default indicator)
 """
 import json
 import sys
@@ -39,6 +42,7 @@ assert METRICS in ('off', 'step', 'window'), METRICS
 TB = METRICS == 'step'
 H, EPISODES, EP_LEN, WEIGHTING = option('--hidden', 1024), option('--episodes', 300), option('--ep-len', 1000), option('--weighting', 'off')
 assert WEIGHTING in ('off', 'episodes', 'transitions'), WEIGHTING
+WEIGHT_FUNC = option('--weight-func', 'indicator')
 TAG = '' if (WEIGHTING, EPISODES, EP_LEN) == ('off', 300, 1000) else f' weighting={WEIGHTING} episodes={EPISODES}x{EP_LEN}'
 
 
@@ -48,7 +52,9 @@ def make(precision):
     if kind == 'td3':
         return agents.TD3Agent('td3', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, TB, precision=precision)
     if kind == 'crr':
-        return agents.CRRAgent('crr', (O,), (A,), 'cuda', 1e-4, H, 0.01, 10, 'indicator', 0.2, 1, B, 0.3, TB, precision=precision)
+        return agents.CRRAgent('crr', (O,), (A,), 'cuda', 1e-4, H, 0.01, 10, WEIGHT_FUNC, 0.2, 1, B, 0.3, TB, precision=precision)
+    if kind == 'iql':
+        return agents.IQLAgent('iql', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, TB, precision=precision)
     if kind == 'bc':
         return agents.BCAgent('bc', (O,), (A,), 'cuda', 1e-4, H, B, 0.2, TB, precision=precision)
     return agents.TD3BCAgent('td3_bc', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, TB, 2.5, precision=precision)
