@@ -15,6 +15,7 @@ SAMPLER_MT19937, SAMPLER_PHILOX, SAMPLER_GIVEN = 0, 1, 2
 WEIGHT_EPISODES, WEIGHT_TRANSITIONS = 0, 1
 AGENT_TD3_BC, AGENT_TD3, AGENT_BC, AGENT_DDPG, AGENT_CRR, AGENT_CQL, AGENT_APS = 0, 1, 2, 3, 4, 5, 6
 AGENT_IQL = 8             # 7 is unassigned
+AGENT_FQE = 9
 AGENT_XCHG_CRITIC_GRAD, AGENT_XCHG_STATS, AGENT_XCHG_ACTOR_GRAD, AGENT_XCHG_VALUE_GRAD = 0, 1, 2, 3
 M_CRITIC_CQL, M_CRITIC_CQL_LOGSUM, M_ACTOR_ALPHA, M_ACTOR_ALPHA_LOSS, M_ACTOR_ENT = 10, 11, 12, 13, 14
 M_VALUE_LOSS, M_VALUE, M_ADV, M_ACTOR_WEIGHT = 10, 11, 12, 13        # IQL's use of slots 10..13
@@ -26,6 +27,8 @@ M_BATCH_REWARD, M_CRITIC_TARGET_Q, M_CRITIC_Q1, M_CRITIC_Q2, M_CRITIC_LOSS, M_AC
 N_METRICS = 16
 E_BC_SQ, E_Q_DATA, E_Q_PI, E_Q1_ERR, E_Q2_ERR, E_TARGET_Q, E_ROWS = range(7)        # exorl_agent_evaluate's window (EXORL_E_*)
 N_EVAL = 7
+FQE_V_Q1, FQE_V_Q2, FQE_V_MEAN_SQ, FQE_V_DIFF_SQ, FQE_V_ROWS = range(5)     # exorl_agent_fqe_value's window (EXORL_FQE_V_*)
+N_FQE_VALUE = 5
 INTR_RND, INTR_ICM, INTR_ICM_APT, INTR_DISAGREEMENT, INTR_DIAYN, INTR_PROTO, INTR_APS, INTR_SMM = 0, 1, 2, 3, 4, 5, 6, 7
 IM_LOSS, IM_INTR_REWARD, IM_EXTR_REWARD, IM_RMS_MEAN, IM_RMS_STD, IM_ACC, IM_ENT_REWARD, IM_SF_REWARD = range(8)
 N_INTR_METRICS = 8
@@ -149,6 +152,8 @@ PROTOTYPES = {
     'exorl_replay_set_weights': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32]),
     'exorl_replay_set_frame_stack': (C.c_int, [c_void_p, c_int32]),
     'exorl_replay_obs_moments': (C.c_int, [c_void_p, c_int32, P(c_int64), c_void_p, c_void_p, c_void_p]),
+    'exorl_replay_episode_returns': (C.c_int, [c_void_p, c_float, c_void_p, c_int32, c_void_p]),
+    'exorl_replay_num_episodes': (C.c_int, [c_void_p, P(c_int32)]),
     'exorl_replay_set_obs_norm': (C.c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_replay_num_rows': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_replay_seed_mt': (C.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
@@ -188,6 +193,10 @@ PROTOTYPES = {
     'exorl_agent_set_eval': (C.c_int, [c_void_p, c_void_p, c_size_t]),
     'exorl_agent_evaluate': (C.c_int, [c_void_p, c_void_p]),
     'exorl_agent_eval_read': (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    'exorl_agent_fqe_value_bytes': (c_size_t, [P(AgentCfg)]),
+    'exorl_agent_set_fqe_value': (C.c_int, [c_void_p, c_void_p, c_size_t]),
+    'exorl_agent_fqe_value': (C.c_int, [c_void_p, c_int32, c_void_p]),
+    'exorl_agent_fqe_value_read': (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     'exorl_agent_set_parallel_branches': (C.c_int, [c_void_p, c_int32]),
     'exorl_agent_opt_steps': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_agent_set_opt_steps': (C.c_int, [c_void_p, c_int64, c_int64]),
@@ -218,6 +227,8 @@ PROTOTYPES = {
     'exorl_ln_tanh_fwd': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'exorl_knn_topk': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'exorl_iql_rows_chunks': (c_int32, [c_int32]),
+    'exorl_fqe_rows_chunks': (c_int32, [c_int32]),
+    'exorl_fqe_rows': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_iql_rows': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }

@@ -11,6 +11,7 @@ Reference classes mirrored (file:line in /root/reference):
   DDPGAgent with obs_type='pixels': Encoder ddpg.py:12-39, pixel Actor/Critic :42-123, update :213-328 (RandomShiftsAug utils.py:222-254)
   APSAgent    agents/unsupervised_learning/aps.py:82-320       SMMAgent   agents/unsupervised_learning/smm.py:115-281 (states)
   IQLAgent    no reference file: implicit Q-learning on the offline nets (the class's docstring is its definition)
+  FQEAgent    no reference file: fitted Q evaluation of a frozen policy (the class's docstring is its definition)
 
 Python here is orchestration only: it builds the initial weights with torch's CPU RNG in the reference's
 construction order (so a given torch.manual_seed yields the reference's initial parameters), hands batches
@@ -26,7 +27,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import utils
 from .comm import all_ranks, native_comm
-from .engine import AgentEngine, IntrEngine, PixelEngine, global_means
+from .engine import PRECISION, AgentEngine, IntrEngine, PixelEngine, global_means
 
 _OFFLINE_ACTOR_KEYS = ['policy.0.weight', 'policy.0.bias', 'policy.1.weight', 'policy.1.bias',
                        'policy.3.weight', 'policy.3.bias', 'policy.5.weight', 'policy.5.bias']
@@ -277,7 +278,7 @@ class _AgentBase:
         self.actor.train(training)
         if hasattr(self, 'critic'):
             self.critic.train(training)
-        if hasattr(self, 'value'):
+        if isinstance(getattr(self, 'value', None), NetView):      # IQL's V(s) net (FQEAgent.value is a method)
             self.value.train(training)
 
     def _stddev(self, step):
@@ -407,7 +408,7 @@ class _AgentBase:
 
     def _run_update(self, stddev):
         """One gradient step on the loaded batch."""
-        if self.KIND in ('bc', 'iql'):          # no draw in the step
+        if self.KIND in ('bc', 'iql', 'fqe'):          # no draw in the step
             nc = na = None
         else:
             # reference draw order: critic target, then actor (SURVEY A9); CRR's second draw is (B*n, A) (crr.py:125)
@@ -595,6 +596,139 @@ class IQLAgent(_AgentBase):
         self.engine.set_iql(expectile, temperature, max_weight)
         self.train()
         self.critic_target.train()
+
+
+def merge_fqe_sums(parts):
+    """[(sums, rows, return_sum, return_count) per rank] -> the same four over all of them: float64 adds in rank order, as merge_eval_sums,
+    so every rank forms the same bits."""
+    total, rows, g_sum, g_n = np.zeros(L.N_FQE_VALUE, np.float64), 0, np.float64(0.0), 0
+    for s, r, g, n in parts:
+        total = total + np.asarray(s, np.float64)
+        rows += int(r)
+        g_sum = g_sum + np.float64(g)
+        g_n += int(n)
+    return total, rows, float(g_sum), g_n
+
+
+def fqe_values(sums, rows, return_sum, return_count):
+    """FQEAgent.value()'s dict from the value window's sums (L.FQE_V_*) over `rows` episodes and the sum of `return_count` episode returns."""
+    n = max(int(rows), 1)
+    q1, q2 = float(sums[L.FQE_V_Q1] / n), float(sums[L.FQE_V_Q2] / n)
+    mean = float((sums[L.FQE_V_Q1] + sums[L.FQE_V_Q2]) / (2 * n))
+    # sample variance of the per-episode (Q_1 + Q_2) / 2 from its sum of squares (float64 from the rows on); one episode has no spread
+    var = max(float(sums[L.FQE_V_MEAN_SQ] - n * mean * mean) / (n - 1), 0.0) if n > 1 else 0.0
+    return {'fqe_value': mean, 'fqe_value_q1': q1, 'fqe_value_q2': q2, 'fqe_value_stderr': float(np.sqrt(var / n)),
+            'fqe_twin_rms': float(np.sqrt(max(float(sums[L.FQE_V_DIFF_SQ]), 0.0) / n)),
+            'behavior_value': float(return_sum / max(int(return_count), 1)), 'episodes': int(rows)}
+
+
+class FQEAgent(_AgentBase):
+    """Fitted Q evaluation: scores a FROZEN policy from the dataset alone. The actor is the policy (set_policy / for_policy) and is never
+    stepped: no gradient, no Adam pass, its weight images are not rewritten. A fresh twin critic with its Polyak target, in TD3's offline
+    layout, is regressed on the policy's own Bellman target. One update() on (s, a, r, D, s'), D the sampler's discount, every forward on the
+    parameters from before the step, mu the actor's mean action:
+        y_i = r + D Q'_i(s', mu(s'))    per net, with its OWN target: no min over the twins. FQE is an estimate, not a pessimistic bound;
+                                        the two nets are a two-member ensemble and their disagreement is reported (fqe_twin_rms)
+        L = mse(Q_1(s, a), y_1) + mse(Q_2(s, a), y_2);   Adam on the critic, soft update of critic_target
+    Nothing is sampled: the noise counter does not move and noise_hook is never called. value() reads the estimate. The replay must run
+    nstep = 1 (the offline loaders do): an n-step target follows the BEHAVIOUR policy's actions for n - 1 steps and biases the estimate
+    towards the behaviour value. No evaluate() and no metric window for this class."""
+    KIND = 'fqe'
+    METRIC_WINDOW = False
+    METRICS = _CRITIC_METRICS[:5]
+    POLICY_CLASSES = ('TD3BCAgent', 'TD3Agent', 'BCAgent', 'CRRAgent', 'IQLAgent')
+
+    def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, nstep, batch_size, use_tb, *,
+                 precision='fp32', seed=0):
+        self.obs_shape = tuple(obs_shape)
+        self.action_dim = action_shape[0]
+        self.hidden_dim = hidden_dim
+        self.lr = lr
+        self.device = device
+        self.critic_target_tau = critic_target_tau
+        self.use_tb = use_tb
+        self.nstep = nstep
+        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, 0.0, device, precision, seed)
+        self.train()
+        self.critic_target.train()
+
+    def _stddev(self, step):
+        return 1.0          # nothing is drawn; the step's std argument only has to be positive
+
+    def _metrics(self, keys, stddev):
+        raw = global_means(self.engine)
+        return {name: float(raw[idx]) for idx, name in keys}          # no actor_ent: the policy is deterministic here
+
+    @staticmethod
+    def _check_policy(agent, dims=None):
+        """ValueError unless `agent` is one of POLICY_CLASSES and, with dims = the evaluator's (obs_dim, action_dim, hidden_dim), of that shape."""
+        if type(agent).__name__ not in FQEAgent.POLICY_CLASSES or not isinstance(agent, _AgentBase):
+            raise ValueError(f'FQEAgent: cannot evaluate a {type(agent).__name__}: the frozen actor is the offline tanh-mean Actor of '
+                             'TD3BCAgent, TD3Agent, BCAgent, CRRAgent or IQLAgent. CQLAgent (a 2A-wide tanh-Gaussian head) and the DDPG '
+                             'family (a trunk / policy layout) are out of scope')
+        theirs = (agent.engine.obs_dim, agent.engine.act_dim, agent.engine.hidden_dim)
+        if dims is not None and tuple(dims) != theirs:
+            raise ValueError(f'FQEAgent.set_policy: (obs_dim, action_dim, hidden_dim) = {theirs} of the policy, {tuple(dims)} of the evaluator')
+
+    def set_policy(self, agent):
+        """Copies `agent`'s actor (the policy to score) and its observation normaliser. ValueError for a class other than TD3BCAgent,
+        TD3Agent, BCAgent, CRRAgent and IQLAgent (CQLAgent's 2A-wide head and the DDPG family's trunk layout are out of scope) or when
+        obs_dim, action_dim or hidden_dim differ."""
+        self._check_policy(agent, (self.engine.obs_dim, self.engine.act_dim, self.engine.hidden_dim))
+        self.actor.load_state_dict(agent.actor.state_dict())
+        if agent.obs_norm_mean is not None:
+            self.set_obs_normalizer(agent.obs_norm_mean, agent.obs_norm_inv)
+        else:
+            self.clear_obs_normalizer()
+        return self
+
+    @classmethod
+    def for_policy(cls, agent, **overrides):
+        """An evaluator shaped after `agent` with its actor copied in: obs / action / hidden sizes, device, batch size and precision are the
+        policy's, lr and critic_target_tau its own where it has them (else 1e-4 and 0.01); `overrides` replaces any constructor argument."""
+        cls._check_policy(agent)
+        eng = agent.engine
+        prec = {v: k for k, v in reversed(list(PRECISION.items()))}[eng.cfg.precision]
+        kw = dict(name='fqe', obs_shape=(eng.obs_dim,), action_shape=(eng.act_dim,), device=agent.device, lr=getattr(agent, 'lr', 1e-4),
+                  hidden_dim=eng.hidden_dim, critic_target_tau=getattr(agent, 'critic_target_tau', 0.01), nstep=1, batch_size=eng.batch,
+                  use_tb=False, precision=prec, seed=0)
+        kw.update(overrides)
+        return cls(**kw).set_policy(agent)
+
+    def act(self, obs, step=0, eval_mode=True):
+        """The frozen policy's mean action, whatever eval_mode says."""
+        return self._act(self._norm_obs(obs), step, True)
+
+    def value(self, replay_iter, gather=None):
+        """The policy's value from the critic as it stands: Q(s_0, mu(s_0)) over the first observation of EVERY resident episode of every
+        arena `replay_iter` samples from (its episode_starts(): an ArenaIterator, a loader's iterator or its .holdout), each once, through
+        forward-only passes (AgentEngine.fqe_value) that move no parameter, optimiser state or counter; the iterator's Philox stream and a
+        captured graph bound to it are not disturbed, and update() continues bit for bit. Returns
+          fqe_value                      mean over episodes of (Q_1 + Q_2) / 2 at (s_0, mu(s_0))
+          fqe_value_q1, fqe_value_q2     the two nets' means separately
+          fqe_value_stderr               standard error of fqe_value over episodes
+          fqe_twin_rms                   root-mean-square of Q_1 - Q_2
+          behavior_value                 mean discounted return of the episodes themselves (episode_returns()): the anchor to read against
+          episodes                       episodes behind the means
+        Under an initialised torch.distributed every rank covers its own arenas and the sums and counts are added in rank order before
+        dividing (all_gather_object; `gather`, a callable own part -> [part of rank 0, of rank 1, ...], replaces that exchange)."""
+        if not hasattr(replay_iter, 'episode_starts'):
+            raise ValueError('FQEAgent.value(): needs an HBM iterator (ArenaIterator, iter(loader) or its .holdout): it enumerates the '
+                             'episodes resident in the arena')
+        eng = self.engine
+        if getattr(eng, '_fqe_value', None) is None:      # the window is the engine's own torch buffer: nothing of it is pickled
+            eng.set_fqe_value()
+        for _, rows in replay_iter.episode_starts(eng.batch, self._batch_slots()):
+            eng.fqe_value(rows)
+        sums, rows = eng.fqe_value_read(reset=True)
+        g = replay_iter.episode_returns()
+        own = (sums, rows, float(np.sum(g, dtype=np.float64)), int(g.size))
+        if gather is None and self.world_size != 1:
+            def gather(part):
+                out = [None] * torch.distributed.get_world_size()
+                torch.distributed.all_gather_object(out, part)
+                return out
+        return fqe_values(*merge_fqe_sums([own] if gather is None else gather(own)))
 
 
 class CQLAgent(_AgentBase):

@@ -392,6 +392,7 @@ struct exorl_agent {
     WeightImages sh_value{}; ShadowSpec spec_value{}; Partials pv{};
     float *iql_dv = nullptr, *iql_part = nullptr;   // d L_V / d v (B); per-chunk metric sums [iql_chunks(B)][IQL_PARTS]; w goes to crr_w
     float expectile = 0.7f, temperature = 3.0f, max_weight = 100.0f;      // exorl_agent_set_iql
+    float* fqe_part = nullptr;                      // FQE: per-chunk metric sums [iql_chunks(B)][FQE_PARTS]
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -429,6 +430,9 @@ struct exorl_agent {
     // EVAL_PARTS partials]
     double* eval_sums = nullptr;
     float* eval_part = nullptr;
+    // FQE's value pass (exorl_agent_set_fqe_value): views of the caller's buffer, [EXORL_N_FQE_VALUE double sums | pad to 256 B][iql_chunks(B) x
+    // FQE_VALUE_PARTS double partials]
+    double *fqe_value_sums = nullptr, *fqe_value_part = nullptr;
 };
 
 namespace exorl {
@@ -567,11 +571,17 @@ static void carve(exorl_agent* a, Carver& c) {
         a->iql_part = c.take((int64_t)iql_chunks(B) * IQL_PARTS);
         c.scratch = false;
     }
+    if (cfg.kind == EXORL_AGENT_FQE) {          // TD3's layout with the row kernel's partials behind it
+        c.scratch = true;
+        a->fqe_part = c.take((int64_t)iql_chunks(B) * FQE_PARTS);
+        c.scratch = false;
+    }
 }
 
 static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
     EXORL_REQUIRE(cfg, "agent: null cfg");
-    EXORL_REQUIRE((cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS) || cfg->kind == EXORL_AGENT_IQL, "agent: unknown kind %d", cfg->kind);
+    EXORL_REQUIRE((cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS) || cfg->kind == EXORL_AGENT_IQL || cfg->kind == EXORL_AGENT_FQE,
+                  "agent: unknown kind %d", cfg->kind);
     EXORL_REQUIRE(cfg->kind != EXORL_AGENT_APS || (cfg->sf_dim >= 1 && cfg->sf_dim <= 16 && cfg->sf_dim < cfg->obs_dim),
                   "agent: APS needs 1 <= sf_dim <= 16 and obs_dim = observation + sf_dim (got sf_dim=%d obs_dim=%d)", cfg->sf_dim, cfg->obs_dim);
     EXORL_REQUIRE(cfg->kind != EXORL_AGENT_CQL || (cfg->n_samples >= 1 && cfg->n_samples <= 16 && cfg->act_dim <= 16),
@@ -1020,6 +1030,48 @@ static int iql_phase9(exorl_agent* a, const Step& st) {
     return phase3(a, st);
 }
 
+// ---- FQE: a frozen actor, each critic regressed on its own target ----------------------------------------
+// TD3's critic step with the mean action in place of the draw, a target per net in place of the min, and no actor step at all: the actor is read
+// (one B-row forward on the next_obs rows, nothing saved for a backward pass) and never written. Nothing is drawn. Phases 10 and 11:
+//   10  mu(s') into the target critic's action columns, Q'(s', mu(s')), Q(s, a), the row kernel (dq, metric partials), critic backward -> critic grads
+//   11  Adam on the critic with the Polyak target fused into its pass; under a staged capture this last kernel of the step advances the replay counter
+static int fqe_phase10(exorl_agent* a, const Step& st) {
+    const auto& cfg = a->cfg;
+    hipStream_t s = st.s;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
+    if (!st.staged)
+        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, a->state,
+                                 st.capture ? 1 : 0, s));
+    a->actor_t += 1;                            // the step state counts steps for both nets (step_begin_device); the actor's Adam never runs
+    a->critic_t += 1;
+    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
+    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
+    // rows 0..B-1 of the stacked input are next_obs: the actor runs on those alone
+    EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa, O, B, a->fa, false, true, prec, s));
+    EXORL_TRY(fqe_mean_actions(a->fa.out, a->xc_next + O, W, B, A, s));
+    const Fork& fk = st.fk;
+    if (!fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
+        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s));
+    } else {
+        EXORL_TRY(fk.fork(s));                  // the target's forward on (s', mu(s')) and the critic's on (s, a) are independent
+        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, fk.side(s)));
+        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, true, false, prec, s));
+        EXORL_TRY(fk.join(s));
+    }
+    FqeRowsArgs r{a->ft.out, a->fc.out, a->reward, a->discount, a->dq, a->fqe_part, B, a->inv_bg};
+    EXORL_TRY(fqe_rows(r, s));
+    if (st.metric_kernels) EXORL_TRY(fqe_sums(a->fqe_part, B, a->inv_bg, nullptr, a->metrics, s));
+    DoutSpec d{};
+    d.mode = EXORL_DOUT_BUFFER; d.buf = a->dq;
+    return net_backward(a->critic, Pc, a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc, a->xc_cur, W, B, a->fc, d, a->bc, nullptr, 0, 0,
+                        prec, s, fk, st.fuse_opt ? &a->pend_c : nullptr);
+}
+
+static int fqe_phase11(exorl_agent* a, const Step& st) {
+    return opt_step(a, st, EXORL_NET_CRITIC, a->critic, a->pend_c, &a->state->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM],
+                    a->spec_critic, st.staged ? &a->state->replay_counter : nullptr);
+}
+
 // ---- the step as a plan -----------------------------------------------------------------------------
 // One update is the ordered list of its phases; where the data-parallel step (dp) needs a global batch quantity before the next phase, the plan
 // names the exchange that follows (EXORL_AGENT_XCHG_*, each a sum all-reduce), else -1. Both drivers read it: whole_step_body, which runs the
@@ -1029,6 +1081,7 @@ static int iql_phase9(exorl_agent* a, const Step& st) {
 //                      (stats_in_phase2); CQL's sum of log pi for the entropy temperature (cql.py:242-243)
 //   actor gradients    after phase 2
 //   IQL                value, critic and actor gradients after phases 6, 7 and 8; phase 9 steps all three nets
+//   FQE                critic gradients after phase 10; phase 11 steps the critic (the actor is frozen)
 // CQL's Lagrange multiplier steps on the penalty of the GLOBAL batch inside phase 0 (cql.py:199-213): data parallel, phases 4 and 5 stand for
 // phase 0 with the statistics (this rank's penalty sums) exchanged in between.
 struct AgentPlan {
@@ -1045,6 +1098,11 @@ static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_pha
         p.add(7, after(true, EXORL_AGENT_XCHG_CRITIC_GRAD));
         p.add(8, after(true, EXORL_AGENT_XCHG_ACTOR_GRAD));
         p.add(9);
+        return p;
+    }
+    if (kind == EXORL_AGENT_FQE) {
+        p.add(10, after(true, EXORL_AGENT_XCHG_CRITIC_GRAD));
+        p.add(11);
         return p;
     }
     if (dp && kind == EXORL_AGENT_CQL && c.use_critic_lagrange) {
@@ -1078,6 +1136,18 @@ static int run_phase(exorl_agent* a, const Step& st, int phase) {
             case 9: return iql_phase9(a, st);
         }
         set_error("agent_update_phase: phase %d is not one of IQL's (6..9, exorl_agent_update_plan)", phase);
+        return 2;
+    }
+    if (a->cfg.kind == EXORL_AGENT_FQE) {
+        switch (phase) {
+            case 10: return fqe_phase10(a, st);
+            case 11: return fqe_phase11(a, st);
+        }
+        set_error("agent_update_phase: phase %d is not one of FQE's (10, 11, exorl_agent_update_plan)", phase);
+        return 2;
+    }
+    if (phase == 10 || phase == 11) {
+        set_error("agent_update_phase: phase %d is FQE's (EXORL_AGENT_FQE); kind %d does not run it", phase, a->cfg.kind);
         return 2;
     }
     switch (phase) {
@@ -1169,7 +1239,7 @@ int exorl_agent_create(const exorl_agent_cfg* cfg, void* workspace, size_t works
     StepState st{};
     st.lr = dec7(cfg->lr); st.b1 = 0.9; st.b2 = 0.999; st.eps = 1e-8; st.tau = dec7(cfg->tau);      // torch.optim.Adam defaults
     st.has_critic = a->has_critic ? 1 : 0;
-    st.no_noise = cfg->kind == EXORL_AGENT_IQL ? 1 : 0;
+    st.no_noise = (cfg->kind == EXORL_AGENT_IQL || cfg->kind == EXORL_AGENT_FQE) ? 1 : 0;
     st.b1t = st.b2t = st.b1t_c = st.b2t_c = 1.0;
     if (a->cql) { CqlScalars sc{0.f, 0.f, 0.f, 1.0f}; (void)hipMemcpy(a->cql, &sc, sizeof(sc), hipMemcpyHostToDevice); }
     e = hipMemcpy(a->state, &st, sizeof(st), hipMemcpyHostToDevice);
@@ -1568,6 +1638,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
         return 0;
     }
     EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_IQL, "agent_set_metric_window: IQL has no metric window");
+    EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_FQE, "agent_set_metric_window: FQE has no metric window");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     const size_t need = window_bytes(a->cfg);
@@ -1672,6 +1743,64 @@ int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_hos
     EXORL_CHECK_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < EXORL_N_EVAL; ++i) sums_host[i] = host[i];
     *rows_host = (int64_t)host[EXORL_E_ROWS];
+    return 0;
+}
+
+static size_t fqe_value_bytes(const exorl_agent_cfg& cfg) {
+    return WIN_HEAD_BYTES + sizeof(double) * (size_t)round_up((int64_t)FQE_VALUE_PARTS * iql_chunks(cfg.batch), 32);
+}
+static_assert(EXORL_N_FQE_VALUE * sizeof(double) <= WIN_HEAD_BYTES && EXORL_FQE_V_ROWS == FQE_VALUE_PARTS, "the value window's sums fit its head; the row count follows the partials");
+
+size_t exorl_agent_fqe_value_bytes(const exorl_agent_cfg* cfg) {
+    exorl_agent tmp;
+    if (describe(&tmp, cfg) != 0 || cfg->kind != EXORL_AGENT_FQE) return 0;
+    return fqe_value_bytes(*cfg);
+}
+
+int exorl_agent_set_fqe_value(exorl_agent_t* a, void* buf_dev, size_t bytes) {
+    EXORL_REQUIRE(a, "agent_set_fqe_value: null handle");
+    if (!buf_dev) {
+        a->fqe_value_sums = a->fqe_value_part = nullptr;
+        return 0;
+    }
+    EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_FQE, "agent_set_fqe_value: kind %d is not FQE", a->cfg.kind);
+    const size_t need = fqe_value_bytes(a->cfg);
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_fqe_value: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
+    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));      // an empty window; the partials behind it are written before they are read
+    a->fqe_value_sums = static_cast<double*>(buf_dev);
+    a->fqe_value_part = reinterpret_cast<double*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
+    return 0;
+}
+
+// Forward-only, as exorl_agent_evaluate: the inputs are staged with the step state left where it is, the actor runs on the obs rows (the half of
+// the stacked buffers BC's step uses), mu(s) goes into xc_pi's action columns and the critic runs on (s, mu(s)) with nothing saved. All B rows
+// go through the nets (their kernels are row-wise: a padding row cannot reach another row's output); only rows < `rows` are reduced.
+int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream) {
+    EXORL_REQUIRE(a, "agent_fqe_value: null handle");
+    EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_FQE, "agent_fqe_value: kind %d is not FQE", a->cfg.kind);
+    EXORL_REQUIRE(a->fqe_value_sums, "agent_fqe_value: no value window (exorl_agent_set_fqe_value)");
+    EXORL_REQUIRE(rows >= 1 && rows <= a->cfg.batch, "agent_fqe_value: rows=%d outside [1, batch=%d]", rows, a->cfg.batch);
+    hipStream_t s = as_stream(stream);
+    const auto& cfg = a->cfg;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
+    EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, nullptr, 0, s));
+    const FwdBufs f = a->fa.rows_from(B, H, A);
+    EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa + (int64_t)B * O, O, B, f, false, true, prec, s));
+    EXORL_TRY(fqe_mean_actions(f.out, a->xc_pi + O, W, B, A, s));
+    EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->xc_pi, W, B, a->fc, false, false, prec, s));
+    return fqe_value_reduce(a->fc.out, B, rows, a->fqe_value_part, a->fqe_value_sums, s);
+}
+
+int exorl_agent_fqe_value_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream) {
+    EXORL_REQUIRE(a && sums_host && rows_host, "agent_fqe_value_read: null argument");
+    EXORL_REQUIRE(a->fqe_value_sums, "agent_fqe_value_read: no value window (exorl_agent_set_fqe_value)");
+    hipStream_t s = as_stream(stream);
+    double host[EXORL_N_FQE_VALUE];
+    EXORL_CHECK_HIP(hipMemcpyAsync(host, a->fqe_value_sums, sizeof(host), hipMemcpyDeviceToHost, s));
+    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(a->fqe_value_sums, 0, sizeof(host), s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < EXORL_N_FQE_VALUE; ++i) sums_host[i] = host[i];
+    *rows_host = (int64_t)host[EXORL_FQE_V_ROWS];
     return 0;
 }
 

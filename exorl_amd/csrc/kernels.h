@@ -325,7 +325,7 @@ struct StepState {
     int has_critic;
     float stddev;                // exploration std of the step (utils.schedule value): read through a pointer, so a schedule
                                  // that moves every step needs no re-capture of the hipGraph
-    int no_noise;                // 1: the kind's update() draws nothing and the noise counter stays put (IQL); 0 keeps the bytes every other kind has
+    int no_noise;                // 1: the kind's update() draws nothing and the noise counter stays put (IQL, FQE); 0 keeps the bytes every other kind has
 };
 
 // The same for an intrinsic-reward module (intr.hip): what changes from one exorl_intr_update to the next. The host keeps the truth
@@ -506,6 +506,24 @@ struct IqlRowsArgs {
 };
 int iql_rows(const IqlRowsArgs& a, hipStream_t s);
 int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
+// FQE's row kernel (loss.hip, fqe_rows_kernel), on iql_rows' chunking: from the target heads tq (2, rows), the critic heads q (2, rows), reward
+// and discount: dq (2, rows) = d L / d Q_i with each net regressed on its OWN target y_i = r + D Q'_i (no min), and per chunk the FQE_PARTS sums
+// below. fqe_sums adds them in chunk order: into sums (raw, FQE_P_* order) and / or as partial means over the global batch into metrics' slots.
+enum { FQE_P_REWARD, FQE_P_TARGET, FQE_P_Q1, FQE_P_Q2, FQE_P_ERR1, FQE_P_ERR2, FQE_PARTS };
+struct FqeRowsArgs {
+    const float *tq, *q, *reward, *discount;
+    float *dq, *part;                        // part: [iql_chunks(rows)][FQE_PARTS]
+    int rows;
+    float inv_bg;
+};
+int fqe_rows(const FqeRowsArgs& a, hipStream_t s);
+int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
+// mu (rows, A) of a tanh-mean actor forward into the action columns of a critic input (ld = dst_ld): FQE's a' = mu(s') and the value pass's mu(s)
+int fqe_mean_actions(const float* mu, float* dst, int64_t dst_ld, int rows, int A, hipStream_t s);
+// FQE's value pass: q (2, ld) at (s, mu(s)); rows < `rows` -> per-chunk fp64 partials [iql_chunks(rows)][FQE_VALUE_PARTS], added in chunk order to
+// sums[EXORL_N_FQE_VALUE] (the last slot counts the rows)
+constexpr int FQE_VALUE_PARTS = EXORL_N_FQE_VALUE - 1;
+int fqe_value_reduce(const float* q, int ld, int rows, double* part, double* sums, hipStream_t s);
 int critic_loss(const float* q, const float* tq, const float* reward, const float* discount, float* dq,
                 float* metrics, int B, float inv_bg, hipStream_t s);
 int actor_stats(const float* q, float* stats, int B, hipStream_t s);

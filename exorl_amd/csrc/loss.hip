@@ -787,7 +787,138 @@ int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metr
     return 0;
 }
 
+// ---- FQE: target and critic heads of a step -> the critic loss gradient and the metrics' per-chunk sums, one pass ------------------------------
+// iql_rows_kernel's arrangement: one thread per row, IQL_CHUNK_ROWS rows per chunk, at most IQL_MAX_WG workgroups striding over the chunks, the
+// partials per chunk so that the sums do not depend on the grid. Each net has its own target (no min over the twins):
+//   y_i = r + D Q'_i(s', mu(s'));   dQ_i = 2 (Q_i - y_i) / Bg
+// Q_i - (r + D Q'_i) is formed in double (exact products and a 53-bit sum of three fp32-sized terms) and rounded once to fp32; 2 e is exact and
+// the product with 1/Bg rounds once more: two roundings, so dq is within 1 ulp of the float64 value of 2 (Q_i - y_i) inv_bg. A row where Q_i is
+// within 1e-6 of y_i keeps its own ulp: the cancellation happens in double.
+__global__ __launch_bounds__(256) void fqe_rows_kernel(const FqeRowsArgs a) {
+    __shared__ float sm[FQE_PARTS][16];
+    const int chunks = iql_chunks(a.rows);
+    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+        const int m = ch * IQL_CHUNK_ROWS + threadIdx.x;
+        float p[FQE_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (m < a.rows) {
+            const float r = a.reward[m], D = a.discount[m];
+            const float q1 = a.q[m], q2 = a.q[a.rows + m];
+            const double y1 = (double)r + (double)D * (double)a.tq[m], y2 = (double)r + (double)D * (double)a.tq[a.rows + m];
+            const float e1 = (float)((double)q1 - y1), e2 = (float)((double)q2 - y2);
+            a.dq[m] = 2.0f * e1 * a.inv_bg;
+            a.dq[a.rows + m] = 2.0f * e2 * a.inv_bg;
+            p[FQE_P_REWARD] = r; p[FQE_P_TARGET] = (float)(0.5 * (y1 + y2)); p[FQE_P_Q1] = q1; p[FQE_P_Q2] = q2;
+            p[FQE_P_ERR1] = e1 * e1; p[FQE_P_ERR2] = e2 * e2;
+        }
+        block_sum<FQE_PARTS>(p, sm);
+#pragma unroll
+        for (int i = 0; i < FQE_PARTS; ++i)       // constant indices: p stays in registers
+            if (threadIdx.x == i) a.part[(int64_t)ch * FQE_PARTS + i] = p[i];
+    }
+}
+
+// One wave, iql_sums_kernel's arrangement: thread i < FQE_PARTS adds quantity i's partials in chunk order.
+__global__ __launch_bounds__(64) void fqe_sums_kernel(const float* __restrict__ part, int chunks, float inv_bg, float* __restrict__ sums,
+                                                      float* __restrict__ metrics) {
+    __shared__ float tot[FQE_PARTS];
+    const int t = threadIdx.x;
+    const float sum = chunk_sum(part + (t < FQE_PARTS ? t : 0), t < FQE_PARTS ? chunks : 0, FQE_PARTS);
+    if (t < FQE_PARTS) {
+        tot[t] = sum;
+        if (sums) sums[t] = sum;
+    }
+    __syncthreads();
+    if (t == 0 && metrics) {
+        metrics[EXORL_M_BATCH_REWARD] = tot[FQE_P_REWARD] * inv_bg;
+        metrics[EXORL_M_CRITIC_TARGET_Q] = tot[FQE_P_TARGET] * inv_bg;
+        metrics[EXORL_M_CRITIC_Q1] = tot[FQE_P_Q1] * inv_bg;
+        metrics[EXORL_M_CRITIC_Q2] = tot[FQE_P_Q2] * inv_bg;
+        metrics[EXORL_M_CRITIC_LOSS] = (tot[FQE_P_ERR1] + tot[FQE_P_ERR2]) * inv_bg;
+    }
+}
+
+int fqe_rows(const FqeRowsArgs& a, hipStream_t s) {
+    const int chunks = iql_chunks(a.rows);
+    hipLaunchKernelGGL(fqe_rows_kernel, dim3(chunks < IQL_MAX_WG ? chunks : IQL_MAX_WG), dim3(IQL_CHUNK_ROWS), 0, s, a);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
+    hipLaunchKernelGGL(fqe_sums_kernel, dim3(1), dim3(64), 0, s, part, iql_chunks(rows), inv_bg, sums, metrics);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void fqe_mean_actions_kernel(const float* __restrict__ mu, float* __restrict__ dst, int64_t dst_ld, int rows, int A) {
+    const int n = rows * A;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[(int64_t)(i / A) * dst_ld + i % A] = mu[i];
+}
+
+int fqe_mean_actions(const float* mu, float* dst, int64_t dst_ld, int rows, int A, hipStream_t s) {
+    hipLaunchKernelGGL(fqe_mean_actions_kernel, dim3(cdiv(rows * A, 256)), dim3(256), 0, s, mu, dst, dst_ld, rows, A);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
+// The value pass's reduction. One thread per row, one workgroup per chunk of IQL_CHUNK_ROWS rows; rows >= `rows` (the padding of a last batch)
+// are not loaded. The four terms are formed and summed in double from the fp32 heads on (a tree through LDS, the same pairs every run): the
+// squared sums feed a variance, and fp32 partials would lose it to cancellation where the spread is small beside the mean.
+__global__ __launch_bounds__(256) void fqe_value_partials_kernel(const float* __restrict__ q, int ld, int rows, double* __restrict__ part) {
+    __shared__ double sm[FQE_VALUE_PARTS][IQL_CHUNK_ROWS];
+    const int t = threadIdx.x, m = blockIdx.x * IQL_CHUNK_ROWS + t;
+    double v[FQE_VALUE_PARTS] = {0.0, 0.0, 0.0, 0.0};
+    if (m < rows) {
+        const double q1 = (double)q[m], q2 = (double)q[ld + m];
+        const double mean = 0.5 * (q1 + q2), diff = q1 - q2;
+        v[EXORL_FQE_V_Q1] = q1; v[EXORL_FQE_V_Q2] = q2; v[EXORL_FQE_V_MEAN_SQ] = mean * mean; v[EXORL_FQE_V_DIFF_SQ] = diff * diff;
+    }
+#pragma unroll
+    for (int i = 0; i < FQE_VALUE_PARTS; ++i) sm[i][t] = v[i];
+    __syncthreads();
+    for (int half = IQL_CHUNK_ROWS / 2; half >= 1; half >>= 1) {
+        if (t < half) {
+#pragma unroll
+            for (int i = 0; i < FQE_VALUE_PARTS; ++i) sm[i][t] += sm[i][t + half];
+        }
+        __syncthreads();
+    }
+    if (t < FQE_VALUE_PARTS) part[(int64_t)blockIdx.x * FQE_VALUE_PARTS + t] = sm[t][0];
+}
+
+// One wave. Thread i < FQE_VALUE_PARTS owns slot i: its partials in chunk order, then one add to the window. Thread EXORL_FQE_V_ROWS counts.
+__global__ __launch_bounds__(64) void fqe_value_window_kernel(const double* __restrict__ part, int chunks, int rows, double* sums) {
+    const int t = threadIdx.x;
+    if (t < FQE_VALUE_PARTS) {
+        double acc = 0.0;
+        for (int ch = 0; ch < chunks; ++ch) acc += part[(int64_t)ch * FQE_VALUE_PARTS + t];
+        sums[t] += acc;
+    } else if (t == EXORL_FQE_V_ROWS) {
+        sums[t] += (double)rows;
+    }
+}
+
+int fqe_value_reduce(const float* q, int ld, int rows, double* part, double* sums, hipStream_t s) {
+    const int chunks = iql_chunks(rows);
+    hipLaunchKernelGGL(fqe_value_partials_kernel, dim3(chunks), dim3(IQL_CHUNK_ROWS), 0, s, q, ld, rows, part);
+    EXORL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fqe_value_window_kernel, dim3(1), dim3(64), 0, s, part, chunks, rows, sums);
+    EXORL_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace exorl
+
+extern "C" int32_t exorl_fqe_rows_chunks(int32_t rows) { return rows > 0 ? exorl::iql_chunks(rows) : 0; }
+
+extern "C" int exorl_fqe_rows(const float* tq, const float* q, const float* reward, const float* discount, int32_t rows, float inv_bg, float* dq,
+                              float* part, float* sums, void* stream) {
+    using namespace exorl;
+    EXORL_REQUIRE(tq && q && reward && discount && dq && part && sums && rows > 0, "fqe_rows: bad arguments");
+    FqeRowsArgs a{tq, q, reward, discount, dq, part, rows, inv_bg};
+    EXORL_TRY(fqe_rows(a, as_stream(stream)));
+    return fqe_sums(part, rows, inv_bg, sums, nullptr, as_stream(stream));
+}
 
 extern "C" int32_t exorl_iql_rows_chunks(int32_t rows) { return rows > 0 ? exorl::iql_chunks(rows) : 0; }
 

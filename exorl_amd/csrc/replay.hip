@@ -149,6 +149,7 @@ struct exorl_replay {
     double* d_slab = nullptr;
     std::vector<int32_t> h_item0;
     std::vector<double> h_moments;
+    double* d_returns = nullptr;      // exorl_replay_episode_returns' output, max_episodes doubles, allocated on first use
 };
 
 namespace exorl {
@@ -455,6 +456,38 @@ __global__ __launch_bounds__(256) void obs_moments_combine_kernel(const double* 
     }
 }
 
+// ---- discounted return of every resident episode (exorl_replay_episode_returns) --------------------------------------------------------
+// The gather's n-step recurrence (sample_tail) from idx 1 over the whole episode, in fp64: a run of steps is the pair (R, D) = (its return
+// discounted to its first step, the product of its gamma d), and two adjacent runs combine as (R1 + D1 R2, D1 D2). The operation is
+// associative, not commutative: the earlier run is always the left operand. One workgroup per episode (table position blockIdx.x); thread t
+// folds steps [t run + 1, (t + 1) run] sequentially, run = cdiv(len, 256), then the 256 pairs combine through LDS in a fixed tree, neighbours
+// first. A thread past the end holds the identity (0, 1). Reads rows row0 + 1 .. row0 + len of the episode only.
+__global__ __launch_bounds__(256) void episode_returns_kernel(const float* __restrict__ rew, const float* __restrict__ disc,
+                                                              const int64_t* __restrict__ row0, const int32_t* __restrict__ len, double gamma,
+                                                              double* __restrict__ out) {
+    __shared__ double s_r[256], s_d[256];
+    const int e = blockIdx.x, t = threadIdx.x;
+    const int n = len[e];
+    const int64_t base = row0[e];
+    const int run = (n + 255) / 256;
+    const int t0 = t * run + 1, t1 = min(t0 + run - 1, n);
+    double R = 0.0, D = 1.0;
+    for (int i = t0; i <= t1; ++i) {
+        R += D * (double)rew[base + i];
+        D *= gamma * (double)disc[base + i];
+    }
+    s_r[t] = R; s_d[t] = D;
+    __syncthreads();
+    for (int step = 1; step < 256; step <<= 1) {
+        if (t % (2 * step) == 0) {
+            s_r[t] = s_r[t] + s_d[t] * s_r[t + step];
+            s_d[t] = s_d[t] * s_d[t + step];
+        }
+        __syncthreads();
+    }
+    if (t == 0) out[e] = s_r[0];
+}
+
 // Prefix sum of the episode masses for `nstep`, checked on the host before anything is enqueued.
 static int build_cum(exorl_replay* r, int32_t nstep) {
     const int n = (int)r->order.size();
@@ -593,6 +626,7 @@ int exorl_replay_destroy(exorl_replay_t* r) {
     (void)hipFree(r->d_norm);
     if (r->d_item0) (void)hipFree(r->d_item0);
     if (r->d_slab) (void)hipFree(r->d_slab);
+    if (r->d_returns) (void)hipFree(r->d_returns);
     delete r;
     return 0;
 }
@@ -718,6 +752,20 @@ int exorl_replay_obs_moments(exorl_replay_t* r, int32_t n_cols, int64_t* count_h
     return 0;
 }
 
+int exorl_replay_episode_returns(exorl_replay_t* r, float gamma, double* returns_host, int32_t n, void* stream) {
+    EXORL_REQUIRE(r && returns_host, "replay_episode_returns: null argument");
+    EXORL_REQUIRE(!r->order.empty(), "replay_episode_returns: no resident episode in the order table");
+    EXORL_REQUIRE(n == (int)r->order.size(), "replay_episode_returns: n=%d, the order table holds %d episodes", n, (int)r->order.size());
+    hipStream_t s = as_stream(stream);
+    if (!r->d_returns) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_returns, (size_t)r->cfg.max_episodes * sizeof(double)));
+    EXORL_TRY(upload_table(r, 0, s));
+    hipLaunchKernelGGL(episode_returns_kernel, dim3(n), dim3(256), 0, s, r->rew, r->disc, r->d_row0, r->d_len, (double)gamma, r->d_returns);
+    EXORL_LAUNCH_CHECK();
+    EXORL_CHECK_HIP(hipMemcpyAsync(returns_host, r->d_returns, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* mean_host, const float* inv_scale_host, void* stream) {
     EXORL_REQUIRE(r, "replay_set_obs_norm: null handle");
     if (n_cols == 0) {
@@ -742,6 +790,12 @@ int exorl_replay_num_rows(exorl_replay_t* r, int64_t* live_rows, int64_t* used_r
     EXORL_REQUIRE(r, "replay_num_rows: null handle");
     if (live_rows) *live_rows = r->live_rows;
     if (used_rows) *used_rows = r->used_rows;
+    return 0;
+}
+
+int exorl_replay_num_episodes(exorl_replay_t* r, int32_t* n) {
+    EXORL_REQUIRE(r && n, "replay_num_episodes: null argument");
+    *n = (int32_t)r->order.size();
     return 0;
 }
 

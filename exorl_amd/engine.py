@@ -13,7 +13,7 @@ from . import _lib as L
 
 KIND = {'td3_bc': L.AGENT_TD3_BC, 'td3': L.AGENT_TD3, 'bc': L.AGENT_BC, 'ddpg': L.AGENT_DDPG, 'crr': L.AGENT_CRR, 'cql': L.AGENT_CQL,
         'aps': L.AGENT_APS}
-KIND_BEYOND_REFERENCE = {'iql': L.AGENT_IQL}        # kinds the reference does not have; KIND stays the reference's seven
+KIND_BEYOND_REFERENCE = {'iql': L.AGENT_IQL, 'fqe': L.AGENT_FQE}        # kinds the reference does not have; KIND stays the reference's seven
 PRECISION = {'fp32': L.PREC_F32, 'f32': L.PREC_F32, 'bf16': L.PREC_BF16, 'bf16x3': L.PREC_BF16X3, 'bf16x6': L.PREC_BF16X6}
 METRIC_KEYS = {L.M_BATCH_REWARD: 'batch_reward', L.M_CRITIC_TARGET_Q: 'critic_target_q', L.M_CRITIC_Q1: 'critic_q1',
                L.M_CRITIC_Q2: 'critic_q2', L.M_CRITIC_LOSS: 'critic_loss', L.M_ACTOR_LOSS: 'actor_loss',
@@ -173,7 +173,8 @@ class AgentEngine(_Phased):
         """update() as its phases, for run_steps: yields the (buffer, op) to exchange across the ranks before the next phase. The library
         names the phases and the exchange behind each (exorl_agent_update_plan): the critic's gradients, the batch statistic of the
         kinds that have one (TD3+BC's lambda; CQL's sum of log_pi for the entropy temperature and, with the Lagrange weight, the penalty
-        sums between phases 4 and 5), the actor's gradients; for IQL the value net's, the critic's and the actor's gradients."""
+        sums between phases 4 and 5), the actor's gradients; for IQL the value net's, the critic's and the actor's gradients; for FQE the
+        critic's alone."""
         phases, xids, n = (C.c_int32 * 8)(), (C.c_int32 * 8)(), C.c_int32()
         L.check(self.lib.exorl_agent_update_plan(C.byref(self.cfg), phases, xids, 8, C.byref(n)))
         for phase, xid in zip(phases[:n.value], xids[:n.value]):
@@ -329,6 +330,32 @@ class AgentEngine(_Phased):
         """(sums, rows) of the window: float64 sums per L.E_* slot and the rows in them; reset empties the window."""
         sums, rows = np.zeros(L.N_EVAL, np.float64), C.c_int64()
         L.check(self.lib.exorl_agent_eval_read(self.h, sums.ctypes.data, C.byref(rows), int(bool(reset)), L.current_stream()))
+        return sums, int(rows.value)
+
+    def fqe_value_bytes(self):
+        return int(self.lib.exorl_agent_fqe_value_bytes(C.byref(self.cfg)))
+
+    def set_fqe_value(self, buf=True):
+        """The value pass's window (exorl_agent_set_fqe_value) on a torch-owned buffer: True allocates fqe_value_bytes(), a uint8 tensor of at
+        least that size is taken as it is, None detaches."""
+        if buf is None:
+            L.check(self.lib.exorl_agent_set_fqe_value(self.h, None, 0))
+            self._fqe_value = None
+            return
+        if buf is True:
+            buf = torch.empty(self.fqe_value_bytes(), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
+        L.check(self.lib.exorl_agent_set_fqe_value(self.h, buf.data_ptr(), buf.numel()))
+        self._fqe_value = buf
+
+    def fqe_value(self, rows):
+        """One forward-only pass of Q(s, mu(s)) on the first `rows` obs rows in the batch slots, added to the window (exorl_agent_fqe_value)."""
+        L.check(self.lib.exorl_agent_fqe_value(self.h, int(rows), L.current_stream()))
+
+    def fqe_value_read(self, reset=True):
+        """(sums, rows) of the window: float64 sums per L.FQE_V_* slot and the rows in them; reset empties the window."""
+        sums, rows = np.zeros(L.N_FQE_VALUE, np.float64), C.c_int64()
+        L.check(self.lib.exorl_agent_fqe_value_read(self.h, sums.ctypes.data, C.byref(rows), int(bool(reset)), L.current_stream()))
         return sums, int(rows.value)
 
     def cql_alpha_state(self):
@@ -855,6 +882,20 @@ class ReplayEngine:
         cnt, mean, m2 = C.c_int64(), np.zeros(n, np.float64), np.zeros(n, np.float64)
         L.check(self.lib.exorl_replay_obs_moments(self.h, n, C.byref(cnt), mean.ctypes.data, m2.ctypes.data, L.current_stream()))
         return cnt.value, mean.reshape(self.obs_shape), m2.reshape(self.obs_shape)
+
+    def num_episodes(self):
+        """Episodes in the order table: the positions a SAMPLER_GIVEN pair may name."""
+        n = C.c_int32()
+        L.check(self.lib.exorl_replay_num_episodes(self.h, C.byref(n)))
+        return n.value
+
+    def episode_returns(self, gamma):
+        """float64 array, one entry per episode of the order table: its discounted return sum_t r[t] prod_{k<t} (gamma d[k]) from the first
+        step, gamma rounded to float32 as the gather does (exorl_replay_episode_returns). Bitwise reproducible. A set-up call: it
+        synchronises the current stream."""
+        out = np.zeros(self.num_episodes(), np.float64)
+        L.check(self.lib.exorl_replay_episode_returns(self.h, float(gamma), out.ctypes.data, out.size, L.current_stream()))
+        return out
 
     def set_obs_normalizer(self, mean32, inv32):
         """Every obs / next_obs element sampled from now on is (x - mean32[j]) * inv32[j] (utils.normalize_obs), in the captured step's

@@ -497,7 +497,47 @@ class DeviceReplayLoader:
         return DeviceReplayIterator(self)
 
 
-class DeviceReplayIterator:
+def start_pair_batches(n_episodes, batch):
+    """The (position, 1) pairs of episodes 0 .. n_episodes - 1 of one arena's order table, cut into batches of `batch`: yields
+    (pairs, valid_rows) with pairs an int32 (batch, 2) array for the GIVEN sampler at nstep = 1 (idx 1 gathers row 0 of the episode as obs) and
+    valid_rows the rows that are episodes. The last batch is padded with copies of position 0 (a pair the sampler accepts); a consumer leaves
+    rows >= valid_rows out. Pure: no device, no arena."""
+    n, batch = int(n_episodes), int(batch)
+    if batch < 1:
+        raise ValueError(f'start_pair_batches: batch={batch}')
+    for first in range(0, n, batch):
+        valid = min(batch, n - first)
+        pairs = np.zeros((batch, 2), np.int32)
+        pairs[:valid, 0] = np.arange(first, first + valid, dtype=np.int32)
+        pairs[:, 1] = 1
+        yield pairs, valid
+
+
+class _EpisodeStarts:
+    """What FQEAgent.value() asks of an HBM iterator: every resident episode of every arena it samples from, once, and their returns.
+    Neither touches an arena's Philox stream (the GIVEN sampler draws nothing), so a captured graph bound to the iterator is undisturbed."""
+
+    def _arenas(self):
+        raise NotImplementedError
+
+    def episode_starts(self, batch=None, out=None):
+        """Yields (pairs, valid_rows) per batch (start_pair_batches), arena after arena in shard order; a batch never straddles two arenas.
+        With `out` (an exorl_batch_out, e.g. an agent's batch slots) each batch has been gathered into it before it is yielded: GIVEN
+        sampler, nstep = 1, so obs is the episode's first observation, normalised if the arena normalises."""
+        batch = batch or self.batch_size
+        for eng in self._arenas():
+            for pairs, valid in start_pair_batches(eng.num_episodes(), batch):
+                if out is not None:
+                    eng.sample_into(out, batch, 1, self.discount, L.SAMPLER_GIVEN, pairs)
+                yield pairs, valid
+
+    def episode_returns(self):
+        """float64 discounted returns of every episode episode_starts() enumerates, in its order (ReplayEngine.episode_returns at the
+        iterator's discount): the behaviour policy's value, the anchor an FQE estimate is read against."""
+        return np.concatenate([eng.episode_returns(self.discount) for eng in self._arenas()])
+
+
+class DeviceReplayIterator(_EpisodeStarts):
     def __init__(self, loader):
         self.loader = loader
         self.shards = [(_OfflineShard if loader.offline else _Shard)(loader, w) for w in loader.worker_ids]
@@ -552,6 +592,12 @@ class DeviceReplayIterator:
                 raise IndexError(EMPTY_BUFFER)
         if not shard.seeded:
             self._seed(shard)
+
+    def _arenas(self):
+        for shard in self.shards:
+            self._load_shard(shard)
+        self._ensure_normalizer()
+        return [shard.engine for shard in self.shards]
 
     @property
     def obs_normalizer(self):
@@ -650,7 +696,7 @@ class DeviceReplayIterator:
         return tuple(res)
 
 
-class ArenaIterator:
+class ArenaIterator(_EpisodeStarts):
     """Iterator over an already-filled ReplayEngine (no directory behind it): what bench.py and callers that
     ingest datasets themselves use. Same next()/sample_into() contract as DeviceReplayIterator."""
 
@@ -670,6 +716,9 @@ class ArenaIterator:
 
     def _next_engine(self):
         return self.engine
+
+    def _arenas(self):
+        return [self.engine]
 
     def sample_into(self, out, batch=None):
         self._next_engine().sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler)
@@ -697,6 +746,9 @@ class HoldoutIterator(ArenaIterator):
         eng = self.engines[self.turn % len(self.engines)]
         self.turn += 1
         return eng
+
+    def _arenas(self):
+        return list(self.engines)
 
 
 def make_replay_loader(storage, max_size, batch_size, num_workers, save_snapshot, nstep=None, discount=None, **kw):

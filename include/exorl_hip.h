@@ -41,7 +41,9 @@ extern "C" {
                                         exorl_agent_cfg.precision, exorl_agent_enable_graph_intr, exorl_debug_agent_weight_images, exorl_replay_set_weights,
                                         exorl_replay_set_frame_stack, exorl_agent_update_plan, exorl_replay_obs_moments, exorl_replay_set_obs_norm)                                    13: exorl_pixel_step replaces the loose arguments of exorl_pixel_agent_update / _update_phase; the three phased pixel
                                         calls return next_exchange; exorl_pixel_agent_exchange replaces _grad_buffer and _bn_partials; (added since, no version change:
-                                        exorl_agent_eval_bytes / _set_eval / _evaluate / _eval_read) */
+                                        exorl_agent_eval_bytes / _set_eval / _evaluate / _eval_read; EXORL_AGENT_IQL, exorl_agent_set_iql;
+                                        EXORL_AGENT_FQE, exorl_agent_fqe_value_bytes / _set_fqe_value / _fqe_value / _fqe_value_read,
+                                        exorl_replay_episode_returns, exorl_replay_num_episodes) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -115,6 +117,15 @@ int exorl_replay_set_frame_stack(exorl_replay_t* r, int32_t frames);
  * the same bits, and a constant column returns m2 == 0. Fails, launching nothing, unless n_cols * 4 == obs_bytes, the arena is not
  * frame-stacked and at least one episode is resident. A set-up call: it synchronises `stream`; never call it inside a capture. */
 int exorl_replay_obs_moments(exorl_replay_t* r, int32_t n_cols, int64_t* count_host, double* mean_host, double* m2_host, void* stream);
+/* Discounted return of every episode of the current order table, in fp64: returns_host[e] = sum_{t=1..len} r[t] prod_{k<t} (gamma d[k]) for
+ * the episode at table position e, gamma the float32 the gather uses widened to double, r and d the stored float32 values widened: the
+ * gather's n-step recurrence started at idx 1 with nstep = len. n must equal the number of episodes in the table. One workgroup per episode:
+ * a thread folds a contiguous run of steps into a pair (R, D), pairs combine in step order with (R1, D1) o (R2, D2) = (R1 + D1 R2, D1 D2)
+ * in a fixed tree. No atomics: two calls return the same bits. Evicted slots and holes are not read. A set-up call: it synchronises `stream`;
+ * never call it inside a capture. */
+int exorl_replay_episode_returns(exorl_replay_t* r, float gamma, double* returns_host, int32_t n, void* stream);
+/* Episodes in the current order table: the positions EXORL_SAMPLER_GIVEN accepts are [0, *n). */
+int exorl_replay_num_episodes(exorl_replay_t* r, int32_t* n);
 /* Observation normaliser of the gather: with n_cols = obs_bytes / 4 values each in mean_host and inv_scale_host, every obs and next_obs
  * element exorl_replay_sample (and the captured step's staged gather) writes is y = (x - mean[j]) * inv_scale[j], two fp32 operations in
  * that order, never contracted; action, reward, discount, meta and the pairs are untouched. n_cols = 0 turns it off (the default: the
@@ -174,6 +185,11 @@ typedef struct exorl_agent exorl_agent_t;
                                   critics regressed on r + D V(s'), actor by the advantage-weighted log-likelihood (CRR's actor step with
                                   w = min(exp(temperature (min Q' - V)), max_weight)). Hyper-parameters: exorl_agent_set_iql. update() draws no
                                   noise: the noise arguments are ignored and the Philox counter stays where it is. */
+#define EXORL_AGENT_FQE    9   /* fitted Q evaluation, no reference file: a FROZEN actor (no gradient, no Adam pass, its weight images never
+                                  rewritten) and a twin critic with its Polyak target in TD3's offline layout. One update regresses each net on
+                                  its own target, y_i = r + D Q'_i(s', mu(s')), mu the actor's mean action: no min over the twins (an estimate,
+                                  not a pessimistic bound; the two nets are a two-member ensemble). update() draws no noise, as IQL's. The
+                                  policy's value is read with exorl_agent_fqe_value. */
 
 #define EXORL_CRR_IDENTITY  0   /* crr.py:132-142 adv_transform */
 #define EXORL_CRR_INDICATOR 1
@@ -283,6 +299,8 @@ int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_critic
  *   phase 6 -> IQL: Q'(s,a), Q(s,a), V on [s'; s], the row kernel (dv, dq, w, metric sums), value grads
  *   phase 7 -> IQL: critic grads          phase 8 -> IQL: actor forward on s, actor grads
  *   phase 9 -> IQL: Adam on value, critic (+ soft update) and actor. IQL runs phases 6..9 only; the other kinds refuse them.
+ *   phase 10 -> FQE: mu(s') on the next_obs rows, Q'(s', mu(s')), Q(s, a), the row kernel (dq, metric sums), critic grads
+ *   phase 11 -> FQE: critic Adam (+ soft update). FQE runs phases 10 and 11 only; the other kinds refuse them.
  * Which phases a configuration's step runs, in which order, and which exchange follows each: exorl_agent_update_plan. Phase 0 is refused for
  * CQL with use_critic_lagrange and world_size > 1 (phases 4 and 5 stand for it). */
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_critic_dev,
@@ -362,6 +380,25 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream);
 /* Synchronous: sums_host[EXORL_N_EVAL] and *rows_host = the window since the last reset (val mean of slot i = sums_host[i] / *rows_host).
  * One copy and, with reset != 0, one hipMemsetAsync, both enqueued on `stream`. */
 int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream);
+/* EXORL_AGENT_FQE only: the value pass. Forward-only on the first `rows` (1 <= rows <= cfg.batch) of the obs rows in the batch slots: the actor's
+ * mean action mu(s), then both critics at (s, mu(s)), through the step's own forward kernels; then a row kernel and a one-wave kernel add, in
+ * chunk order (bitwise reproducible, no atomics, fp64 from the rows on), to a window of double sums: */
+#define EXORL_FQE_V_Q1       0   /* sum of Q_1(s, mu(s)) */
+#define EXORL_FQE_V_Q2       1   /* sum of Q_2(s, mu(s)) */
+#define EXORL_FQE_V_MEAN_SQ  2   /* sum of ((Q_1 + Q_2) / 2)^2 */
+#define EXORL_FQE_V_DIFF_SQ  3   /* sum of (Q_1 - Q_2)^2 */
+#define EXORL_FQE_V_ROWS     4   /* rows in the window */
+#define EXORL_N_FQE_VALUE    5
+/* The window is the caller's, as the eval window is: exorl_agent_fqe_value_bytes(cfg) bytes of device memory (0 for a configuration that is
+ * refused or not FQE), 256-byte aligned, alive while it is set; setting empties it, NULL detaches. The pass reads the action, reward, discount and
+ * next_obs slots only to stage them (rows >= `rows` and those slots may hold anything, NaN included: nothing of them reaches the sums) and is
+ * read-only towards parameters, targets, weight images, gradients, Adam moments, the step state and the metrics: exorl_agent_update or
+ * exorl_agent_step_graph afterwards continue bit for bit. Not between the phases of a step driven through exorl_agent_update_phase. */
+size_t exorl_agent_fqe_value_bytes(const exorl_agent_cfg* cfg);
+int exorl_agent_set_fqe_value(exorl_agent_t* a, void* buf_dev, size_t bytes);
+int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream);
+/* Synchronous: sums_host[EXORL_N_FQE_VALUE] and *rows_host = the window since the last reset; with reset != 0 one hipMemsetAsync on `stream`. */
+int exorl_agent_fqe_value_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream);
 /* Captured graphs run independent parts of the step (target || critic forward, wgrad || dgrad chain) as parallel
  * branches on a second stream (default: off — one chain measured faster on MI355X). */
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable);
@@ -471,6 +508,13 @@ int exorl_knn_topk(const float* src_dev, int32_t n_src, const float* tgt_dev, in
  * r, y, Q_1, Q_2, (Q_1 - y)^2, (Q_2 - y)^2, k u^2, v, u, w, added per chunk in chunk order with no atomics (the same bits on every run).
  * part: scratch of 10 * exorl_iql_rows_chunks(rows) floats. */
 int32_t exorl_iql_rows_chunks(int32_t rows);
+/* FQE's row kernel on caller-made rows (unit test hook): tq, q (2, rows) target and critic heads, reward, discount (rows) in; dq (2, rows) =
+ * 2 inv_bg (Q_i - y_i), y_i = r + D Q'_i, out as the step forms them (EXORL_AGENT_FQE above), and sums[6] = the sums over the rows of r,
+ * (y_1 + y_2) / 2, Q_1, Q_2, (Q_1 - y_1)^2, (Q_2 - y_2)^2, added per chunk in chunk order with no atomics (the same bits on every run).
+ * part: scratch of 6 * exorl_fqe_rows_chunks(rows) floats. */
+int32_t exorl_fqe_rows_chunks(int32_t rows);
+int exorl_fqe_rows(const float* tq_dev, const float* q_dev, const float* reward_dev, const float* discount_dev, int32_t rows, float inv_bg,
+                   float* dq_dev, float* part_dev, float* sums_dev, void* stream);
 int exorl_iql_rows(const float* tq_dev, const float* q_dev, const float* v_dev, const float* v_next_dev, const float* reward_dev,
                    const float* discount_dev, int32_t rows, float inv_bg, float expectile, float temperature, float max_weight,
                    float* dv_dev, float* dq_dev, float* w_dev, float* part_dev, float* sums_dev, void* stream);

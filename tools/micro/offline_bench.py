@@ -13,6 +13,9 @@
     python tools/micro/offline_bench.py iql 24 6 1024 bf16x3,fp32 --steps 2000 --warmup 200 --repeats 3      # IQLAgent at its defaults
     python tools/micro/offline_bench.py crr 24 6 1024 bf16x3,fp32 --weight-func exp --steps 2000 --warmup 200 --repeats 3
         # --weight-func identity|indicator|exp: CRR's advantage transform (default indicator)
+    python tools/micro/offline_bench.py fqe 24 6 1024 bf16x3,fp32 --steps 2000 --warmup 200 --repeats 3      # FQEAgent: frozen actor, critic step only
+    python tools/micro/offline_bench.py fqe 24 6 1024 bf16x3 --episodes 1000 --steps 200 --warmup 20 --value
+        # --value (fqe): after the timed steps, the time of FQEAgent.value() over every resident episode and of ReplayEngine.episode_returns
 """
 import json
 import sys
@@ -30,7 +33,7 @@ from exorl_amd.replay_buffer import ArenaIterator
 
 kind, O, A, B = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 precisions = (sys.argv[5] if len(sys.argv) > 5 and not sys.argv[5].startswith('--') else 'fp32,bf16x3,bf16').split(',')
-ROOFLINE, EAGER = '--roofline' in sys.argv, '--eager' in sys.argv
+ROOFLINE, EAGER, VALUE = '--roofline' in sys.argv, '--eager' in sys.argv, '--value' in sys.argv
 
 
 def option(name, default):
@@ -55,6 +58,8 @@ def make(precision):
         return agents.CRRAgent('crr', (O,), (A,), 'cuda', 1e-4, H, 0.01, 10, WEIGHT_FUNC, 0.2, 1, B, 0.3, TB, precision=precision)
     if kind == 'iql':
         return agents.IQLAgent('iql', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, TB, precision=precision)
+    if kind == 'fqe':
+        return agents.FQEAgent('fqe', (O,), (A,), 'cuda', 1e-4, H, 0.01, 1, B, TB, precision=precision)
     if kind == 'bc':
         return agents.BCAgent('bc', (O,), (A,), 'cuda', 1e-4, H, B, 0.2, TB, precision=precision)
     return agents.TD3BCAgent('td3_bc', (O,), (A,), 'cuda', 1e-4, H, 0.01, 0.2, 1, B, 0.3, TB, 2.5, precision=precision)
@@ -101,6 +106,19 @@ for prec in precisions:
     if REPEATS > 1:
         print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} metrics={METRICS}{TAG}: median {float(np.median(rates)):8.1f} update()/s, min {min(rates):.1f}, '
               f'max {max(rates):.1f} over {REPEATS} repeats of {n} steps', flush=True)
+    if VALUE:
+        assert kind == 'fqe', '--value times FQEAgent.value()'
+        ag.value(it)                                  # the window and the returns scratch are allocated on first use
+        for what, fn in (('value()', lambda: ag.value(it)), ('episode_returns', lambda: eng.episode_returns(0.99))):
+            ts = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            print(f'{kind} O={O} A={A} B={B} H={H} {prec:7s} {what} over {EPISODES} episodes x {EP_LEN} steps: median {float(np.median(ts)):.3f} ms, '
+                  f'min {min(ts):.3f}, max {max(ts):.3f} of 5 calls', flush=True)
     if ROOFLINE:
         # the dominant kernel's launches bracketed by HIP events on the stream they run on (an instrumented eager pass of the same loop,
         # as bench.py does for the headline): algorithmic FLOPs = 2 M N K per problem, the 0.7 x event-bracket calibration of bench.py
