@@ -13,6 +13,7 @@
 // Data parallel: the step is split in 4 phases at the three points where a global batch quantity is needed
 // (critic grads, sum|Q| for lambda (td3_bc.py:154), actor grads); the caller all-reduces between phases.
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "kernels.h"
@@ -634,10 +635,31 @@ static int push_opt_steps(exorl_agent* a) {
     return 0;
 }
 
-static FusedAdamArgs fused_adam_args(exorl_agent* a, int net, const NetDesc& d, const AdamConst* c, float* target, uint64_t* bump) {
-    float** f = a->flat[net];
-    return FusedAdamArgs{f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], target, c, d.n_heads,
-                         {d.W1, d.W1 + d.head_stride}, reinterpret_cast<unsigned long long*>(bump)};
+// Everything the handle keeps for one net (EXORL_NET_*), by reference: what a forward, a backward or an optimiser launch of that net is given.
+// The critic's Polyak target has parameters and weight images of its own and borrows the rest from the critic.
+struct NetView {
+    const NetDesc& d;
+    float* const* flat;                  // [EXORL_T_*]: parameters, gradients, Adam moments
+    const WeightImages& sh;
+    const Partials& pt;
+    const BwdBufs& b;
+    FinalizeArgs& pend;                  // the partials a gradient phase left for the optimiser phase behind it (fused optimiser launch)
+    const ShadowSpec& spec;
+    float* P() const { return flat[EXORL_T_PARAM]; }
+    float* G() const { return flat[EXORL_T_GRAD]; }
+};
+static bool has_net(const exorl_agent* a, int net) {
+    if (net == EXORL_NET_ACTOR) return true;
+    if (net == EXORL_NET_CRITIC || net == EXORL_NET_CRITIC_TARGET) return a->has_critic;
+    return net == EXORL_NET_VALUE && a->has_value;
+}
+static NetView net_view(exorl_agent* a, int net) {
+    switch (net) {
+        case EXORL_NET_ACTOR: return NetView{a->actor, a->flat[net], a->sh_actor, a->pa, a->ba, a->pend_a, a->spec_actor};
+        case EXORL_NET_VALUE: return NetView{a->value, a->flat[net], a->sh_value, a->pv, a->bv, a->pend_v, a->spec_value};
+        case EXORL_NET_CRITIC_TARGET: return NetView{a->critic, a->flat[net], a->sh_target, a->pc, a->bc, a->pend_c, a->spec_critic};
+        default: return NetView{a->critic, a->flat[net], a->sh_critic, a->pc, a->bc, a->pend_c, a->spec_critic};
+    }
 }
 // How one driver call runs the step. Each driver builds one (make_step) before its first launch and hands it to every phase, so a step's launch
 // decisions are taken once, from the call's arguments and the handle's settings, and nothing of one call carries over to the next.
@@ -671,20 +693,86 @@ static Step make_step(const exorl_agent* a, hipStream_t s, float stddev, const f
     return st;
 }
 
-static int opt_step(exorl_agent* a, const Step& st, int net, const NetDesc& d, const FinalizeArgs& pend, const AdamConst* c, float* target,
-                    const ShadowSpec& spec, uint64_t* bump) {
-    float** f = a->flat[net];
+// Adam on net n with the step scalars c. target: the Polyak target stepped in the same pass (the critic's), or nullptr. bump: the replay counter a
+// staged capture's last kernel advances, or nullptr.
+static int opt_step(const Step& st, const NetView& n, const AdamConst* c, const NetView* target, uint64_t* bump) {
+    float* const* f = n.flat;
+    float* tp = target ? target->P() : nullptr;
     hipStream_t s = st.s;
-    if (st.fuse_opt) EXORL_TRY(finalize_adam(pend, fused_adam_args(a, net, d, c, target, bump), spec, s));
-    else EXORL_TRY(adam_step_dev(f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], d.total, c, target, &spec, s, bump));
+    if (st.fuse_opt)
+        EXORL_TRY(finalize_adam(n.pend, FusedAdamArgs{f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], tp, c, n.d.n_heads,
+                                                      {n.d.W1, n.d.W1 + n.d.head_stride}, reinterpret_cast<unsigned long long*>(bump)}, n.spec, s));
+    else EXORL_TRY(adam_step_dev(f[EXORL_T_PARAM], f[EXORL_T_GRAD], f[EXORL_T_ADAM_M], f[EXORL_T_ADAM_V], n.d.total, c, tp, &n.spec, s, bump));
     // bf16x6 on the plane kernel: the stepped W1 (and the Polyak target's) as three planes for the next step's launches
-    EXORL_TRY(refresh_w1_planes(d, f[EXORL_T_PARAM], net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_VALUE ? a->sh_value : a->sh_critic, s));
-    if (target) EXORL_TRY(refresh_w1_planes(d, target, a->sh_target, s));
+    EXORL_TRY(refresh_w1_planes(n.d, n.P(), n.sh, s));
+    if (target) EXORL_TRY(refresh_w1_planes(n.d, tp, target->sh, s));
     return 0;
 }
-static int opt_step_critic(exorl_agent* a, const Step& st) {
-    return opt_step(a, st, EXORL_NET_CRITIC, a->critic, a->pend_c, &a->state->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM],
-                    a->spec_critic, nullptr);
+static int opt_step_critic(exorl_agent* a, const Step& st, uint64_t* bump = nullptr) {
+    const NetView target = net_view(a, EXORL_NET_CRITIC_TARGET);
+    return opt_step(st, net_view(a, EXORL_NET_CRITIC), &a->state->critic, &target, bump);
+}
+
+// ---- the blocks every kind's step is made of --------------------------------------------------------
+// Opens a step: stages the inputs and (thread 0 of the kernel) advances the device-side step state — counters, this step's Adam scalars — with the
+// host's mirrors of the counters. A staged capture's gather kernel has done the device side already. st == nullptr: a forward-only pass
+// (exorl_agent_evaluate, exorl_agent_fqe_value): the inputs are staged and nothing advances.
+static int open_step(exorl_agent* a, const Step* st, hipStream_t s) {
+    const auto& cfg = a->cfg;
+    if (!st || !st->staged)
+        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, cfg.batch, cfg.obs_dim, cfg.act_dim,
+                                 a->has_critic ? 1 : 0, st ? a->state : nullptr, st && st->capture ? 1 : 0, s));
+    if (!st) return 0;
+    a->actor_t += 1;                            // the step state counts steps for both nets (step_begin_device), whichever of them steps
+    if (a->has_critic) a->critic_t += 1;
+    return 0;
+}
+
+// The Polyak target on x_target (into ft, nothing saved) and the critic on (obs, a_data) (into fc): independent chains of one shape, so one set
+// of shared launches where forward2 applies, else two chains, the target's on the side stream when the call forks. save: the critic keeps what a
+// backward pass needs. fused_heads: the scalar heads are left to qhead (no_head), the target's folded into its GEMM where the launch allows
+// (*tq_slots, see net_forward2).
+static int twin_forward(exorl_agent* a, hipStream_t s, const Fork& fk, const float* x_target, bool save, bool fused_heads = false,
+                        int* tq_slots = nullptr) {
+    const NetView c = net_view(a, EXORL_NET_CRITIC), t = net_view(a, EXORL_NET_CRITIC_TARGET);
+    const int B = a->cfg.batch, W = c.d.in_dim, prec = a->cfg.precision;
+    if (!fk.on && forward2_supported(c.d, prec, t.sh, a->ft, c.sh, a->fc, B))
+        return net_forward2(c.d, t.P(), t.sh, x_target, a->ft, false, c.P(), c.sh, a->xc_cur, a->fc, save, W, B, s, fused_heads, fused_heads, tq_slots);
+    EXORL_TRY(fk.fork(s));
+    EXORL_TRY(net_forward(c.d, t.P(), t.sh, x_target, W, B, a->ft, false, false, prec, fk.side(s), nullptr, fused_heads));
+    EXORL_TRY(net_forward(c.d, c.P(), c.sh, a->xc_cur, W, B, a->fc, save, false, prec, s, nullptr, fused_heads));
+    return fk.join(s);
+}
+
+// Parameter gradients of net n from dout: finalised into its flat gradients, or left as partials where the optimiser launch sums them itself.
+static int net_grads(const exorl_agent* a, const Step& st, const NetView& n, const float* x, int rows, const FwdBufs& f, const DoutSpec& dout,
+                     bool have_dz2 = false) {
+    return net_backward(n.d, n.P(), n.sh, n.G(), n.pt, x, n.d.in_dim, rows, f, dout, n.b, nullptr, 0, 0, a->cfg.precision, st.s, st.fk,
+                        st.fuse_opt ? &n.pend : nullptr, have_dz2);
+}
+// ... from a buffer that holds d L / d out, row by row (a row kernel wrote it)
+static int net_grads_from(const exorl_agent* a, const Step& st, const NetView& n, const float* x, int rows, const FwdBufs& f, const float* buf) {
+    DoutSpec d{};
+    d.mode = EXORL_DOUT_BUFFER; d.buf = buf;
+    return net_grads(a, st, n, x, rows, f, d);
+}
+
+// The actor's gradients on the obs half (rows B..2B of the stacked buffers) from d L / d mu: the forward where the step has not run it, the
+// actor_loss metric kernel, the backward pass. kind: whose gradient form (TD3+BC's, BC's, CRR's weighted log-likelihood, else the critic's da
+// alone); da_nets: how many slabs of a->da add up. dm: the caller's additions (phase 2's fused path); the common fields are set here.
+static int actor_mu_step(exorl_agent* a, const Step& st, bool forward, int kind, int da_nets, const float* reward, DoutSpec dm) {
+    const auto& cfg = a->cfg;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim;
+    const NetView n = net_view(a, EXORL_NET_ACTOR);
+    const float* x = a->xa + (int64_t)B * O;
+    const FwdBufs f = a->fa.rows_from(B, cfg.hidden_dim, A);
+    if (forward) EXORL_TRY(net_forward(n.d, n.P(), n.sh, x, O, B, f, true, true, cfg.precision, st.s));
+    if (st.metric_kernels)                      // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
+        EXORL_TRY(actor_dmu(a->da, A, da_nets, (int64_t)B * A, f.out, a->action, reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A,
+                            a->inv_bg, cfg.alpha, kind, st.stddev, st.s, &a->state->stddev));
+    dm.mode = EXORL_DOUT_ACTOR_MU; dm.da = da_nets ? a->da : nullptr; dm.da_nets = da_nets; dm.mu = f.out; dm.a_data = a->action;
+    dm.kind = kind; dm.inv_bg = a->inv_bg; dm.stddev = st.stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
+    return net_grads(a, st, n, x, B, f, dm);
 }
 
 constexpr size_t WIN_HEAD_BYTES = 256;       // the window's sums and step count
@@ -733,16 +821,9 @@ static int phase0(exorl_agent* a, const Step& st) {
     hipStream_t s = st.s;
     const float stddev = st.stddev, *noise_c = st.noise_c;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
-    // stages the inputs and (thread 0) advances the device-side step state: counters, Adam scalars of this step
-    if (!st.staged)
-        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, a->has_critic, a->state,
-                                 st.capture ? 1 : 0, s));
-    a->actor_t += 1;
-    if (a->has_critic) a->critic_t += 1;
+    EXORL_TRY(open_step(a, &st, s));
     if (!a->has_critic) return 0;
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
-    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
-    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
     // actor on [next_obs; obs] in one pass (td3_bc.py:124 and :149 use the same weights)
     // next_action = dist.sample(clip) (td3_bc.py:125) and the actor-step sample pi(obs) (:151, it does not depend on the
     // critic update) straight into the two critic input buffers, as the epilogue of the actor head
@@ -754,17 +835,8 @@ static int phase0(exorl_agent* a, const Step& st) {
         EXORL_TRY(sample_actions2(a->fa.out, noise_c, cfg.kind == EXORL_AGENT_CRR ? nullptr : st.noise_a, cfg.seed,
                                   &a->state->noise_counter, stddev, cfg.stddev_clip, a->xc_next + O, a->xc_pi + O, W, B, A, s, &a->state->stddev));
     const bool qf = st.qfuse;
-    const Fork& fk = st.fk;
     int tq_slots = 0;
-    if (!fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
-        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s, qf, qf,
-                               &tq_slots));
-    } else {
-        EXORL_TRY(fk.fork(s));                  // target critic (td3_bc.py:126) and critic (td3_bc.py:130) forwards are independent
-        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, fk.side(s), nullptr, qf));
-        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, true, false, prec, s, nullptr, qf));
-        EXORL_TRY(fk.join(s));
-    }
+    EXORL_TRY(twin_forward(a, s, st.fk, a->xc_next, true, qf, &tq_slots));      // target critic (td3_bc.py:126) and critic (td3_bc.py:130)
     if (qf) EXORL_TRY(run_qhead(a, st, 0, tq_slots));      // Q, Q', TD gradient, dz2 and head partials in one kernel
     const bool aps = cfg.kind == EXORL_AGENT_APS;
     const float* task = aps ? a->obs + (O - cfg.sf_dim) : nullptr;          // obs rows are [observation | task] (aps.py:236-238)
@@ -779,9 +851,7 @@ static int phase0(exorl_agent* a, const Step& st) {
     DoutSpec td{};                              // d(2 x MSE)/dQ computed where it is consumed (:127-131)
     td.mode = EXORL_DOUT_TD; td.q = qv; td.tq = tqv; td.reward = a->reward; td.discount = a->discount; td.inv_bg = a->inv_bg;
     td.task = task; td.task_ld = O;
-    EXORL_TRY(net_backward(a->critic, Pc, a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc, a->xc_cur, W, B, a->fc, td,
-                           a->bc, nullptr, 0, 0, prec, s, fk, st.fuse_opt ? &a->pend_c : nullptr, qf));                     // :141
-    return 0;
+    return net_grads(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, B, a->fc, td, qf);                                       // :141
 }
 
 // -- phase 1: critic optimiser step (+ fused soft update), critic re-evaluated at pi(obs) -------------
@@ -822,10 +892,8 @@ static int phase1(exorl_agent* a, const Step& st) {
 static int phase2(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
     hipStream_t s = st.s;
-    const float stddev = st.stddev;
     const bool qf = st.qfuse;
-    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
-    const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
     if (a->has_critic && cfg.kind != EXORL_AGENT_CRR) {
         DoutSpec dq{};                          // -lambda/Bg routed to the smaller Q (td3_bc.py:152-155)
         dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.alpha = cfg.alpha;
@@ -842,17 +910,7 @@ static int phase2(exorl_agent* a, const Step& st) {
         EXORL_TRY(net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, nullptr, a->pc, a->xc_pi, W, B, a->fc,
                                dq, a->bc, a->da, O, A, prec, s, st.fk, nullptr, qf));
     }
-    // the obs half (rows B..2B) of the stacked actor forward
-    const FwdBufs f = a->fa.rows_from(B, H, A);
-    if (!a->has_critic)       // BC (bc.py:82): the only forward of the step
-        EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa + (int64_t)B * O, O, B, f, true, true, prec, s));
-    if (st.metric_kernels)                      // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
-        EXORL_TRY(actor_dmu(a->da, A, a->has_critic ? a->critic.n_trunks : 0, (int64_t)B * A, f.out, a->action,
-                            a->has_critic ? nullptr : a->reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A, a->inv_bg, cfg.alpha,
-                            cfg.kind, stddev, s, &a->state->stddev));
     DoutSpec dm{};
-    dm.mode = EXORL_DOUT_ACTOR_MU; dm.da = a->da; dm.da_nets = a->has_critic ? a->critic.n_trunks : 0; dm.mu = f.out; dm.a_data = a->action;
-    dm.kind = cfg.kind; dm.inv_bg = a->inv_bg; dm.stddev = stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
     if (qf) {                                   // lambda = alpha / mean|Q| from the per-chunk sums qhead left behind
         dm.lam_parts = a->abs_part; dm.lam_chunks = qhead_chunks(B); dm.use_lambda = cfg.kind == EXORL_AGENT_TD3_BC; dm.alpha = cfg.alpha;
         if (st.stats_in_phase2) {                // the all-reduced statistic (one 'chunk': stats[0] = global sum |Q|)
@@ -861,14 +919,12 @@ static int phase2(exorl_agent* a, const Step& st) {
         }
         if (a->win_sums && cfg.kind == EXORL_AGENT_TD3_BC) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
     }
-    EXORL_TRY(net_backward(a->actor, Pa, a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa, a->xa + (int64_t)B * O, O, B, f,
-                           dm, a->ba, nullptr, 0, 0, prec, s, st.fk, st.fuse_opt ? &a->pend_a : nullptr));
-    return 0;
+    // BC (bc.py:82) runs its only forward here; the other kinds' is the obs half of phase 0's stacked pass
+    return actor_mu_step(a, st, !a->has_critic, cfg.kind, a->has_critic ? a->critic.n_trunks : 0, a->has_critic ? nullptr : a->reward, dm);
 }
 
 static int phase3(exorl_agent* a, const Step& st) {
-    return opt_step(a, st, EXORL_NET_ACTOR, a->actor, a->pend_a, &a->state->actor, nullptr, a->spec_actor,
-                    st.staged ? &a->state->replay_counter : nullptr);
+    return opt_step(st, net_view(a, EXORL_NET_ACTOR), &a->state->actor, nullptr, st.staged ? &a->state->replay_counter : nullptr);
 }
 
 // ---- CQL (cql.py:152-263) ---------------------------------------------------------------------------
@@ -889,11 +945,7 @@ static int cql_phase0a(exorl_agent* a, const Step& st, bool split) {
     hipStream_t s = st.s;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, n = cfg.n_samples, prec = cfg.precision;
     const int R = (3 * n + 1) * B;
-    if (!st.staged)
-        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, a->state,
-                                 st.capture ? 1 : 0, s));
-    a->actor_t += 1;
-    a->critic_t += 1;
+    EXORL_TRY(open_step(a, &st, s));
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
     EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, true, false, prec, s));      // raw (mu | log_std) on [next_obs; obs]
@@ -910,16 +962,10 @@ static int cql_phase0a(exorl_agent* a, const Step& st, bool split) {
 static int cql_phase0b(exorl_agent* a, const Step& st, bool split) {
     const auto& cfg = a->cfg;
     hipStream_t s = st.s;
-    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, n = cfg.n_samples, prec = cfg.precision;
-    const int R = (3 * n + 1) * B;
-    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
+    const int B = cfg.batch, n = cfg.n_samples;
     EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
                             cfg.use_critic_lagrange ? a->cql + 1 : nullptr, &a->state->critic, cfg.target_cql_penalty, split ? 2 : 0, a->stats + 2));
-    DoutSpec d{};
-    d.mode = EXORL_DOUT_BUFFER; d.buf = a->dq_all;
-    EXORL_TRY(net_backward(a->critic, Pc, a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc, a->x_all, W, R, a->fc, d, a->bc,
-                           nullptr, 0, 0, prec, s, st.fk, st.fuse_opt ? &a->pend_c : nullptr));
-    return 0;
+    return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->x_all, (3 * n + 1) * B, a->fc, a->dq_all);
 }
 
 static int cql_phase0(exorl_agent* a, const Step& st) {
@@ -928,6 +974,9 @@ static int cql_phase0(exorl_agent* a, const Step& st) {
     EXORL_TRY(cql_phase0a(a, st, false));
     return cql_phase0b(a, st, false);
 }
+// use_critic_lagrange under data parallelism: phase 0 up to the penalty sums, and from the global penalty on
+static int cql_phase4(exorl_agent* a, const Step& st) { return cql_phase0a(a, st, true); }
+static int cql_phase5(exorl_agent* a, const Step& st) { return cql_phase0b(a, st, true); }
 
 static int cql_phase1(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
@@ -952,9 +1001,7 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
     DoutSpec dm{};
     dm.mode = EXORL_DOUT_CQL_ACTOR; dm.da = a->da; dm.da_nets = a->critic.n_trunks; dm.raw = f.out; dm.z = st.noise_a;
     dm.alpha_ptr = &a->cql->alpha; dm.inv_bg = a->inv_bg; dm.seed = cfg.seed; dm.counter = 4; dm.counter_ptr = &a->state->noise_counter;
-    EXORL_TRY(net_backward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa,
-                           a->xa + (int64_t)B * O, O, B, f, dm, a->ba, nullptr, 0, 0, prec, s, st.fk, st.fuse_opt ? &a->pend_a : nullptr));
-    return 0;
+    return net_grads(a, st, net_view(a, EXORL_NET_ACTOR), a->xa + (int64_t)B * O, B, f, dm);
 }
 
 // ---- IQL: expectile value net, V-target critic, advantage-weighted actor --------------------------------
@@ -967,65 +1014,29 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
 static int iql_phase6(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
     hipStream_t s = st.s;
-    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
-    if (!st.staged)
-        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, a->state,
-                                 st.capture ? 1 : 0, s));
-    a->actor_t += 1;
-    a->critic_t += 1;
-    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
-    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
-    const float* Pv = a->flat[EXORL_NET_VALUE][EXORL_T_PARAM];
-    const Fork& fk = st.fk;
-    if (!fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
-        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_cur, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s));
-    } else {
-        EXORL_TRY(fk.fork(s));                  // the target's and the critic's forwards on (s, a) are independent
-        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_cur, W, B, a->ft, false, false, prec, fk.side(s)));
-        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, true, false, prec, s));
-        EXORL_TRY(fk.join(s));
-    }
-    EXORL_TRY(net_forward(a->value, Pv, a->sh_value, a->xa, O, 2 * B, a->fv, true, false, prec, s));      // rows 0..B-1: V(s'), B..2B-1: V(s)
+    const int B = cfg.batch, O = cfg.obs_dim, H = cfg.hidden_dim;
+    EXORL_TRY(open_step(a, &st, s));
+    const NetView v = net_view(a, EXORL_NET_VALUE);
+    EXORL_TRY(twin_forward(a, s, st.fk, a->xc_cur, true));      // the target's and the critic's forwards on (s, a)
+    EXORL_TRY(net_forward(v.d, v.P(), v.sh, a->xa, O, 2 * B, a->fv, true, false, cfg.precision, s));      // rows 0..B-1: V(s'), B..2B-1: V(s)
     IqlRowsArgs r{a->ft.out, a->fc.out, a->fv.out + B, a->fv.out, a->reward, a->discount, a->iql_dv, a->dq, a->crr_w, a->iql_part, B,
                   a->inv_bg, a->expectile, a->temperature, a->max_weight};
     EXORL_TRY(iql_rows(r, s));
     if (st.metric_kernels) EXORL_TRY(iql_sums(a->iql_part, B, a->inv_bg, nullptr, a->metrics, s));
-    DoutSpec d{};
-    d.mode = EXORL_DOUT_BUFFER; d.buf = a->iql_dv;
-    return net_backward(a->value, Pv, a->sh_value, a->flat[EXORL_NET_VALUE][EXORL_T_GRAD], a->pv, a->xa + (int64_t)B * O, O, B,
-                        a->fv.rows_from(B, H, 1), d, a->bv, nullptr, 0, 0, prec, s, fk, st.fuse_opt ? &a->pend_v : nullptr);
+    return net_grads_from(a, st, v, a->xa + (int64_t)B * O, B, a->fv.rows_from(B, H, 1), a->iql_dv);
 }
 
 static int iql_phase7(exorl_agent* a, const Step& st) {
-    const auto& cfg = a->cfg;
-    const int B = cfg.batch, W = cfg.obs_dim + cfg.act_dim;
-    DoutSpec d{};
-    d.mode = EXORL_DOUT_BUFFER; d.buf = a->dq;
-    return net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc,
-                        a->xc_cur, W, B, a->fc, d, a->bc, nullptr, 0, 0, cfg.precision, st.s, st.fk, st.fuse_opt ? &a->pend_c : nullptr);
+    return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, a->cfg.batch, a->fc, a->dq);
 }
 
-static int iql_phase8(exorl_agent* a, const Step& st) {
-    const auto& cfg = a->cfg;
-    hipStream_t s = st.s;
-    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, H = cfg.hidden_dim, prec = cfg.precision;
-    const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
-    const float* x = a->xa + (int64_t)B * O;
-    const FwdBufs f = a->fa.rows_from(B, H, A);       // the obs half, as BC runs it: the only actor forward of the step
-    EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, x, O, B, f, true, true, prec, s));
-    if (st.metric_kernels)                      // actor_loss = -(w * log N(a; mu, std)).mean(): CRR's metric with IQL's weights
-        EXORL_TRY(actor_dmu(a->da, A, 0, 0, f.out, a->action, nullptr, a->crr_w, a->dpre, a->stats, a->metrics, B, A, a->inv_bg, 0.f,
-                            EXORL_AGENT_CRR, st.stddev, s, &a->state->stddev));
-    DoutSpec dm{};
-    dm.mode = EXORL_DOUT_ACTOR_MU; dm.mu = f.out; dm.a_data = a->action; dm.kind = EXORL_AGENT_CRR; dm.inv_bg = a->inv_bg;
-    dm.stddev = st.stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
-    return net_backward(a->actor, Pa, a->sh_actor, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->pa, x, O, B, f, dm, a->ba, nullptr, 0, 0, prec, s,
-                        st.fk, st.fuse_opt ? &a->pend_a : nullptr);
-}
+// the obs half, as BC runs it: the only actor forward of the step. actor_loss = -(w * log N(a; mu, std)).mean(): CRR's metric and gradient
+// with IQL's weights (the row kernel left them in crr_w)
+static int iql_phase8(exorl_agent* a, const Step& st) { return actor_mu_step(a, st, true, EXORL_AGENT_CRR, 0, nullptr, DoutSpec{}); }
 
 static int iql_phase9(exorl_agent* a, const Step& st) {
     // the value net steps with the critic (one step count, exorl_agent_opt_steps): it reads the critic's Adam scalars and has no target
-    EXORL_TRY(opt_step(a, st, EXORL_NET_VALUE, a->value, a->pend_v, &a->state->critic, nullptr, a->spec_value, nullptr));
+    EXORL_TRY(opt_step(st, net_view(a, EXORL_NET_VALUE), &a->state->critic, nullptr, nullptr));
     EXORL_TRY(opt_step_critic(a, st));
     return phase3(a, st);
 }
@@ -1038,39 +1049,19 @@ static int iql_phase9(exorl_agent* a, const Step& st) {
 static int fqe_phase10(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
     hipStream_t s = st.s;
-    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, prec = cfg.precision;
-    if (!st.staged)
-        EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, a->state,
-                                 st.capture ? 1 : 0, s));
-    a->actor_t += 1;                            // the step state counts steps for both nets (step_begin_device); the actor's Adam never runs
-    a->critic_t += 1;
-    const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
-    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A;
+    EXORL_TRY(open_step(a, &st, s));            // the actor's step count moves with the critic's; its Adam never runs
     // rows 0..B-1 of the stacked input are next_obs: the actor runs on those alone
-    EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa, O, B, a->fa, false, true, prec, s));
+    EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa, O, B, a->fa, false, true, cfg.precision, s));
     EXORL_TRY(fqe_mean_actions(a->fa.out, a->xc_next + O, W, B, A, s));
-    const Fork& fk = st.fk;
-    if (!fk.on && forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
-        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, true, W, B, s));
-    } else {
-        EXORL_TRY(fk.fork(s));                  // the target's forward on (s', mu(s')) and the critic's on (s, a) are independent
-        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, fk.side(s)));
-        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, true, false, prec, s));
-        EXORL_TRY(fk.join(s));
-    }
+    EXORL_TRY(twin_forward(a, s, st.fk, a->xc_next, true));      // the target's forward on (s', mu(s')) and the critic's on (s, a)
     FqeRowsArgs r{a->ft.out, a->fc.out, a->reward, a->discount, a->dq, a->fqe_part, B, a->inv_bg};
     EXORL_TRY(fqe_rows(r, s));
     if (st.metric_kernels) EXORL_TRY(fqe_sums(a->fqe_part, B, a->inv_bg, nullptr, a->metrics, s));
-    DoutSpec d{};
-    d.mode = EXORL_DOUT_BUFFER; d.buf = a->dq;
-    return net_backward(a->critic, Pc, a->sh_critic, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->pc, a->xc_cur, W, B, a->fc, d, a->bc, nullptr, 0, 0,
-                        prec, s, fk, st.fuse_opt ? &a->pend_c : nullptr);
+    return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, B, a->fc, a->dq);
 }
 
-static int fqe_phase11(exorl_agent* a, const Step& st) {
-    return opt_step(a, st, EXORL_NET_CRITIC, a->critic, a->pend_c, &a->state->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM],
-                    a->spec_critic, st.staged ? &a->state->replay_counter : nullptr);
-}
+static int fqe_phase11(exorl_agent* a, const Step& st) { return opt_step_critic(a, st, st.staged ? &a->state->replay_counter : nullptr); }
 
 // ---- the step as a plan -----------------------------------------------------------------------------
 // One update is the ordered list of its phases; where the data-parallel step (dp) needs a global batch quantity before the next phase, the plan
@@ -1084,86 +1075,104 @@ static int fqe_phase11(exorl_agent* a, const Step& st) {
 //   FQE                critic gradients after phase 10; phase 11 steps the critic (the actor is frozen)
 // CQL's Lagrange multiplier steps on the penalty of the GLOBAL batch inside phase 0 (cql.py:199-213): data parallel, phases 4 and 5 stand for
 // phase 0 with the statistics (this rank's penalty sums) exchanged in between.
+// All of that is one table per kind: a row is a phase id, the function it means, the exchange behind it and the rule both hang on. agent_plan
+// walks the kind's table in order (the rows the configuration runs are the step); run_phase looks an id up in it (a kind accepts exactly its
+// table's ids, whether or not this configuration's plan runs them).
+using PhaseFn = int (*)(exorl_agent*, const Step&);
+enum PhaseRule {
+    EVERY_STEP,        // runs in every plan; under dp its exchange follows
+    IF_CRITIC,         // ... its exchange only for a kind with a critic (BC's phase 0 leaves no critic gradients)
+    IF_LAMBDA,         // ... its exchange only for TD3+BC, and not where phase 2 reduces the statistic itself (stats_in_phase2)
+    IF_SPLIT,          // runs only where CQL's phase 0 is split (use_critic_lagrange under dp); its exchange follows
+    UNLESS_SPLIT,      // runs where it is not; under dp its exchange follows
+};
+struct PhaseRow { int id; PhaseFn fn; int xchg; PhaseRule rule; };
+struct PhaseTable { const char* owner; const char* ids; const PhaseRow* rows; int n; };
+static const PhaseRow DDPG_ROWS[] = {         // TD3+BC, TD3, BC, DDPG, CRR, APS (BC's phase 1 is a no-op)
+    {0, phase0, EXORL_AGENT_XCHG_CRITIC_GRAD, IF_CRITIC},
+    {1, phase1, EXORL_AGENT_XCHG_STATS, IF_LAMBDA},
+    {2, phase2, EXORL_AGENT_XCHG_ACTOR_GRAD, EVERY_STEP},
+    {3, phase3, -1, EVERY_STEP},
+};
+static const PhaseRow CQL_ROWS[] = {
+    {4, cql_phase4, EXORL_AGENT_XCHG_STATS, IF_SPLIT},
+    {5, cql_phase5, EXORL_AGENT_XCHG_CRITIC_GRAD, IF_SPLIT},
+    {0, cql_phase0, EXORL_AGENT_XCHG_CRITIC_GRAD, UNLESS_SPLIT},
+    {1, cql_phase1, EXORL_AGENT_XCHG_STATS, EVERY_STEP},
+    {2, cql_phase2, EXORL_AGENT_XCHG_ACTOR_GRAD, EVERY_STEP},
+    {3, phase3, -1, EVERY_STEP},
+};
+static const PhaseRow IQL_ROWS[] = {          // three gradient sums and no batch statistic
+    {6, iql_phase6, EXORL_AGENT_XCHG_VALUE_GRAD, EVERY_STEP},
+    {7, iql_phase7, EXORL_AGENT_XCHG_CRITIC_GRAD, EVERY_STEP},
+    {8, iql_phase8, EXORL_AGENT_XCHG_ACTOR_GRAD, EVERY_STEP},
+    {9, iql_phase9, -1, EVERY_STEP},
+};
+static const PhaseRow FQE_ROWS[] = {
+    {10, fqe_phase10, EXORL_AGENT_XCHG_CRITIC_GRAD, EVERY_STEP},
+    {11, fqe_phase11, -1, EVERY_STEP},
+};
+template <int N>
+static constexpr PhaseTable phase_rows(const char* owner, const char* ids, const PhaseRow (&rows)[N]) { return PhaseTable{owner, ids, rows, N}; }
+static const PhaseTable PHASE_TABLES[] = {phase_rows("the DDPG family", "0..3", DDPG_ROWS), phase_rows("CQL", "0..5", CQL_ROWS),
+                                          phase_rows("IQL", "6..9", IQL_ROWS), phase_rows("FQE", "10, 11", FQE_ROWS)};
+static const PhaseTable& phase_table(int kind) {
+    return PHASE_TABLES[kind == EXORL_AGENT_CQL ? 1 : kind == EXORL_AGENT_IQL ? 2 : kind == EXORL_AGENT_FQE ? 3 : 0];
+}
+static const PhaseRow* find_phase(const PhaseTable& t, int id) {
+    for (int i = 0; i < t.n; ++i)
+        if (t.rows[i].id == id) return &t.rows[i];
+    return nullptr;
+}
+
 struct AgentPlan {
     int n = 0;
-    int phase[5], xchg[5];         // xchg: the exchange that follows the phase, or -1
-    void add(int ph, int x = -1) { phase[n] = ph; xchg[n++] = x; }
+    int phase[6], xchg[6];         // xchg: the exchange that follows the phase, or -1
 };
 static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_phase2) {
-    const int kind = c.kind;
-    auto after = [&](bool on, int x) { return dp && on ? x : -1; };
+    const bool split = dp && c.kind == EXORL_AGENT_CQL && c.use_critic_lagrange;
+    const PhaseTable& t = phase_table(c.kind);
     AgentPlan p;
-    if (kind == EXORL_AGENT_IQL) {      // three gradient sums and no batch statistic
-        p.add(6, after(true, EXORL_AGENT_XCHG_VALUE_GRAD));
-        p.add(7, after(true, EXORL_AGENT_XCHG_CRITIC_GRAD));
-        p.add(8, after(true, EXORL_AGENT_XCHG_ACTOR_GRAD));
-        p.add(9);
-        return p;
+    for (int i = 0; i < t.n; ++i) {
+        const PhaseRow& r = t.rows[i];
+        if (r.rule == (split ? UNLESS_SPLIT : IF_SPLIT)) continue;
+        const bool on = r.rule == IF_CRITIC ? c.kind != EXORL_AGENT_BC : r.rule == IF_LAMBDA ? c.kind == EXORL_AGENT_TD3_BC && !stats_in_phase2 : true;
+        p.phase[p.n] = r.id;
+        p.xchg[p.n++] = dp && on ? r.xchg : -1;
     }
-    if (kind == EXORL_AGENT_FQE) {
-        p.add(10, after(true, EXORL_AGENT_XCHG_CRITIC_GRAD));
-        p.add(11);
-        return p;
-    }
-    if (dp && kind == EXORL_AGENT_CQL && c.use_critic_lagrange) {
-        p.add(4, EXORL_AGENT_XCHG_STATS);
-        p.add(5, EXORL_AGENT_XCHG_CRITIC_GRAD);
-    } else {
-        p.add(0, after(kind != EXORL_AGENT_BC, EXORL_AGENT_XCHG_CRITIC_GRAD));
-    }
-    p.add(1, after((kind == EXORL_AGENT_TD3_BC && !stats_in_phase2) || kind == EXORL_AGENT_CQL, EXORL_AGENT_XCHG_STATS));
-    p.add(2, after(true, EXORL_AGENT_XCHG_ACTOR_GRAD));
-    p.add(3);
     return p;
 }
 
 static int run_phase(exorl_agent* a, const Step& st, int phase) {
-    if (a->cfg.kind == EXORL_AGENT_CQL) {
-        switch (phase) {
-            case 0: return cql_phase0(a, st);
-            case 1: return cql_phase1(a, st);
-            case 2: return cql_phase2(a, st);
-            case 3: return phase3(a, st);
-            case 4: return cql_phase0a(a, st, true);       // use_critic_lagrange under data parallelism: phase 0 up to the penalty sums ...
-            case 5: return cql_phase0b(a, st, true);       // ... and from the global penalty on
-        }
-    }
-    if (a->cfg.kind == EXORL_AGENT_IQL) {
-        switch (phase) {
-            case 6: return iql_phase6(a, st);
-            case 7: return iql_phase7(a, st);
-            case 8: return iql_phase8(a, st);
-            case 9: return iql_phase9(a, st);
-        }
-        set_error("agent_update_phase: phase %d is not one of IQL's (6..9, exorl_agent_update_plan)", phase);
-        return 2;
-    }
-    if (a->cfg.kind == EXORL_AGENT_FQE) {
-        switch (phase) {
-            case 10: return fqe_phase10(a, st);
-            case 11: return fqe_phase11(a, st);
-        }
-        set_error("agent_update_phase: phase %d is not one of FQE's (10, 11, exorl_agent_update_plan)", phase);
-        return 2;
-    }
-    if (phase == 10 || phase == 11) {
-        set_error("agent_update_phase: phase %d is FQE's (EXORL_AGENT_FQE); kind %d does not run it", phase, a->cfg.kind);
-        return 2;
-    }
-    switch (phase) {
-        case 0: return phase0(a, st);
-        case 1: return phase1(a, st);
-        case 2: return phase2(a, st);
-        case 3: return phase3(a, st);
-    }
-    set_error("agent_update_phase: phase %d out of range", phase);
+    const PhaseTable& t = phase_table(a->cfg.kind);
+    if (const PhaseRow* r = find_phase(t, phase)) return r->fn(a, st);
+    const PhaseTable* owner = nullptr;       // whose phase it is, if anybody's
+    for (const PhaseTable& o : PHASE_TABLES)
+        if (!owner && find_phase(o, phase)) owner = &o;
+    if (owner)
+        set_error("agent_update_phase: phase %d out of range for kind %d: it is not one of %s's (%s, exorl_agent_update_plan); phase %d is %s's",
+                  phase, a->cfg.kind, t.owner, t.ids, phase, owner->owner);
+    else
+        set_error("agent_update_phase: phase %d out of range for kind %d: it is not one of %s's (%s, exorl_agent_update_plan)", phase,
+                  a->cfg.kind, t.owner, t.ids);
     return 2;
+}
+
+// What exchange `xid` (EXORL_AGENT_XCHG_*) sum-all-reduces: the statistics block, or a net's flat gradients.
+struct Exchange { float* ptr; int64_t count; };
+static Exchange exchange_of(exorl_agent* a, int xid) {
+    static const int net[] = {EXORL_NET_CRITIC, -1, EXORL_NET_ACTOR, EXORL_NET_VALUE};      // by EXORL_AGENT_XCHG_*; -1: the statistics
+    static_assert(EXORL_AGENT_XCHG_CRITIC_GRAD == 0 && EXORL_AGENT_XCHG_STATS == 1 && EXORL_AGENT_XCHG_ACTOR_GRAD == 2 &&
+                  EXORL_AGENT_XCHG_VALUE_GRAD == 3, "exchange_of: the table is indexed by exchange id");
+    if (net[xid] < 0) return Exchange{a->stats, 4};
+    const NetView n = net_view(a, net[xid]);
+    return Exchange{n.G(), n.d.total};
 }
 
 // the kernels read the exploration std from the device step state; enqueue a new value only when the schedule moved (a captured graph is
 // std-agnostic: exorl_agent_step_graph writes it before the launch)
-static int push_stddev(exorl_agent* a, float stddev, hipStream_t s) {
-    EXORL_REQUIRE(stddev > 0.f || a->cfg.kind == EXORL_AGENT_CQL, "agent_update_phase: stddev must be > 0");
+static int push_stddev(exorl_agent* a, const char* who, float stddev, hipStream_t s) {
+    EXORL_REQUIRE(stddev > 0.f || a->cfg.kind == EXORL_AGENT_CQL, "%s: stddev must be > 0", who);
     if (a->cfg.kind != EXORL_AGENT_CQL && stddev != a->dev_stddev) {
         EXORL_TRY(set_device_float(&a->state->stddev, stddev, s));
         a->dev_stddev = stddev;
@@ -1178,14 +1187,36 @@ static int whole_step_body(exorl_agent* a, const Step& st) {
     const AgentPlan p = agent_plan(a->cfg, a->comm != nullptr, st.stats_in_phase2);
     for (int i = 0; i < p.n; ++i) {
         EXORL_TRY(run_phase(a, st, p.phase[i]));
-        switch (p.xchg[i]) {
-            case EXORL_AGENT_XCHG_CRITIC_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_CRITIC][EXORL_T_GRAD], a->critic.total, st.s)); break;
-            case EXORL_AGENT_XCHG_STATS: EXORL_TRY(comm_allreduce_sum(a->comm, a->stats, 4, st.s)); break;
-            case EXORL_AGENT_XCHG_ACTOR_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_ACTOR][EXORL_T_GRAD], a->actor.total, st.s)); break;
-            case EXORL_AGENT_XCHG_VALUE_GRAD: EXORL_TRY(comm_allreduce_sum(a->comm, a->flat[EXORL_NET_VALUE][EXORL_T_GRAD], a->value.total, st.s)); break;
-        }
+        if (p.xchg[i] < 0) continue;
+        const Exchange x = exchange_of(a, p.xchg[i]);
+        EXORL_TRY(comm_allreduce_sum(a->comm, x.ptr, x.count, st.s));
     }
     if (a->win_sums) EXORL_TRY(run_metrics_window(a, st));      // the step's metrics into the window (and, on the fused path, into a->metrics)
+    return 0;
+}
+
+// A sum window is a caller's device buffer: [double sums (and, the metric window, an int64 count behind them) | pad to WIN_HEAD_BYTES][per-chunk
+// partials]. The metric window, the evaluation's and FQE's value pass each have one; attaching and reading is the same for all three.
+// attach_window: `need` bytes, 256-byte aligned, refused in `who`'s name; clears the head (an empty window: the partials behind it are written
+// before they are read) and hands out the two parts. buf_dev == nullptr detaches; a refused buffer leaves the window as it was.
+template <typename Part>
+static int attach_window(const char* who, void* buf_dev, size_t bytes, size_t need, double** sums, Part** part) {
+    if (!buf_dev) { *sums = nullptr; *part = nullptr; return 0; }
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "%s: buffer %zu B (need %zu B, 256-byte aligned)", who, bytes, need);
+    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));
+    *sums = static_cast<double*>(buf_dev);
+    *part = reinterpret_cast<Part*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
+    return 0;
+}
+// read_window: the n sums and, where count_host is given, the int64 behind them; reset empties what was read. Synchronises the stream.
+static int read_window(const double* sums_dev, int n, double* sums_host, int64_t* count_host, int reset, hipStream_t s) {
+    struct { double sums[WIN_HEAD_BYTES / sizeof(double) - 1]; long long count; } host;
+    const size_t bytes = n * sizeof(double) + (count_host ? sizeof(long long) : 0);
+    EXORL_CHECK_HIP(hipMemcpyAsync(&host, sums_dev, bytes, hipMemcpyDeviceToHost, s));
+    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(const_cast<double*>(sums_dev), 0, bytes, s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) sums_host[i] = host.sums[i];
+    if (count_host) memcpy(count_host, &host.sums[n], sizeof(long long));
     return 0;
 }
 
@@ -1259,12 +1290,7 @@ int exorl_agent_destroy(exorl_agent_t* a) {
     return 0;
 }
 
-static const NetDesc* net_of(exorl_agent_t* a, int32_t net) {
-    if (net == EXORL_NET_ACTOR) return &a->actor;
-    if ((net == EXORL_NET_CRITIC || net == EXORL_NET_CRITIC_TARGET) && a->has_critic) return &a->critic;
-    if (net == EXORL_NET_VALUE && a->has_value) return &a->value;
-    return nullptr;
-}
+static const NetDesc* net_of(exorl_agent_t* a, int32_t net) { return has_net(a, net) ? &net_view(a, net).d : nullptr; }
 
 int exorl_agent_num_tensors(exorl_agent_t* a, int32_t net, int32_t* n) {
     EXORL_REQUIRE(a && n, "agent_num_tensors: null argument");
@@ -1343,7 +1369,7 @@ int exorl_agent_set_batch(exorl_agent_t* a, const float* obs, const float* actio
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_c, const float* noise_a, void* stream) {
     EXORL_REQUIRE(a, "agent_update_phase: null handle");
     hipStream_t s = as_stream(stream);
-    EXORL_TRY(push_stddev(a, stddev, s));
+    EXORL_TRY(push_stddev(a, "agent_update_phase", stddev, s));
     return run_phase(a, make_step(a, s, stddev, noise_c, noise_a, false, false, false, false), phase);
 }
 
@@ -1352,7 +1378,7 @@ int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_c, con
     EXORL_REQUIRE(a->cfg.world_size == 1 || a->comm, "agent_update: world_size=%d needs a communicator (exorl_agent_set_comm), or drive "
                   "exorl_agent_update_phase and all-reduce between the phases yourself", a->cfg.world_size);
     hipStream_t s = as_stream(stream);
-    EXORL_TRY(push_stddev(a, stddev, s));
+    EXORL_TRY(push_stddev(a, "agent_update_phase", stddev, s));
     return whole_step_body(a, make_step(a, s, stddev, noise_c, noise_a, true, false, false, false));
 }
 
@@ -1577,7 +1603,7 @@ int exorl_debug_agent_weight_images(exorl_agent_t* a, int32_t net, exorl_weight_
     EXORL_REQUIRE(a && out, "debug_agent_weight_images: null argument");
     const NetDesc* d = net_of(a, net);
     EXORL_REQUIRE(d, "debug_agent_weight_images: agent has no net %d", net);
-    const WeightImages& sh = net == EXORL_NET_ACTOR ? a->sh_actor : net == EXORL_NET_CRITIC ? a->sh_critic : net == EXORL_NET_VALUE ? a->sh_value : a->sh_target;
+    const WeightImages& sh = net_view(a, net).sh;
     *out = exorl_weight_images{d->n_trunks, d->n_heads, d->in_dim, d->H, sh.w0t, sh.w0.hi, sh.w0.lo, sh.w1.hi, sh.w1.mid, sh.w1.lo};
     return 0;
 }
@@ -1634,19 +1660,15 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
     EXORL_REQUIRE(a, "agent_set_metric_window: null handle");
     EXORL_REQUIRE(!a->graph_exec, "agent_set_metric_window: disable the captured graph first");
     if (!buf_dev) {
-        a->win_sums = nullptr; a->win_steps = nullptr; a->win_crit = a->win_bc = nullptr;
-        return 0;
+        a->win_steps = nullptr; a->win_bc = nullptr;
+        return attach_window("agent_set_metric_window", nullptr, 0, 0, &a->win_sums, &a->win_crit);
     }
     EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_IQL, "agent_set_metric_window: IQL has no metric window");
     EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_FQE, "agent_set_metric_window: FQE has no metric window");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
-    const size_t need = window_bytes(a->cfg);
-    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_metric_window: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
-    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));      // an empty window; the partials behind it are written before they are read
-    a->win_sums = static_cast<double*>(buf_dev);
+    EXORL_TRY(attach_window("agent_set_metric_window", buf_dev, bytes, window_bytes(a->cfg), &a->win_sums, &a->win_crit));
     a->win_steps = reinterpret_cast<long long*>(a->win_sums + EXORL_N_METRICS);
-    a->win_crit = reinterpret_cast<float*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
     a->win_bc = a->win_crit + 6 * (int64_t)qhead_chunks(a->cfg.batch);
     return 0;
 }
@@ -1654,14 +1676,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
 int exorl_agent_metric_window_read(exorl_agent_t* a, double* sums_host, int64_t* steps_host, int32_t reset, void* stream) {
     EXORL_REQUIRE(a && sums_host && steps_host, "agent_metric_window_read: null argument");
     EXORL_REQUIRE(a->win_sums, "agent_metric_window_read: no metric window (exorl_agent_set_metric_window)");
-    hipStream_t s = as_stream(stream);
-    struct { double sums[EXORL_N_METRICS]; long long steps; } host;
-    EXORL_CHECK_HIP(hipMemcpyAsync(&host, a->win_sums, sizeof(host), hipMemcpyDeviceToHost, s));
-    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(a->win_sums, 0, sizeof(host), s));
-    EXORL_CHECK_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < EXORL_N_METRICS; ++i) sums_host[i] = host.sums[i];
-    *steps_host = host.steps;
-    return 0;
+    return read_window(a->win_sums, EXORL_N_METRICS, sums_host, steps_host, reset, as_stream(stream));
 }
 
 static_assert(EXORL_N_EVAL * sizeof(double) <= WIN_HEAD_BYTES && EXORL_E_ROWS == EVAL_PARTS, "the eval window's sums fit its head; the row count follows the partials");
@@ -1680,17 +1695,9 @@ size_t exorl_agent_eval_bytes(const exorl_agent_cfg* cfg) {
 
 int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     EXORL_REQUIRE(a, "agent_set_eval: null handle");
-    if (!buf_dev) {
-        a->eval_sums = nullptr; a->eval_part = nullptr;
-        return 0;
-    }
+    if (!buf_dev) return attach_window("agent_set_eval", nullptr, 0, 0, &a->eval_sums, &a->eval_part);
     EXORL_REQUIRE(eval_kind_ok(a->cfg.kind), "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
-    const size_t need = eval_bytes(a->cfg);
-    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_eval: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
-    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));      // an empty window; the partials behind it are written before they are read
-    a->eval_sums = static_cast<double*>(buf_dev);
-    a->eval_part = reinterpret_cast<float*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
-    return 0;
+    return attach_window("agent_set_eval", buf_dev, bytes, eval_bytes(a->cfg), &a->eval_sums, &a->eval_part);
 }
 
 // The forwards of phases 0 and 1 with the mean action in place of the draws and nothing saved for a backward pass: same kernels, same routes.
@@ -1705,8 +1712,7 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
     const bool cql = cfg.kind == EXORL_AGENT_CQL;
     const int AO = a->actor.out_dim;
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
-    // st = nullptr: the inputs are staged, the step state stays where it is
-    EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, a->has_critic ? 1 : 0, nullptr, 0, s));
+    EXORL_TRY(open_step(a, nullptr, s));         // no step: the inputs are staged, the step state stays where it is
     EvalArgs e{};
     e.mu = a->fa.out + (int64_t)B * AO; e.mu_ld = AO; e.raw = cql ? 1 : 0;
     e.a_data = a->action; e.A = A; e.reward = a->reward; e.discount = a->discount;
@@ -1716,16 +1722,10 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
         return eval_reduce(e, s);
     }
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
-    const float* Pt = a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM];
     EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, false, !cql, prec, s));
     EXORL_TRY(eval_mean_actions(a->fa.out, AO, cql ? 1 : 0, a->xc_next + O, a->xc_pi + O, W, B, A, s));
     // Q'(s', mu(s')) and Q(s, a) as phase 0 launches them; then Q(s, mu(s)) as phase 1 does, its two columns into dq (fc.out holds Q(s, a))
-    if (forward2_supported(a->critic, prec, a->sh_target, a->ft, a->sh_critic, a->fc, B)) {
-        EXORL_TRY(net_forward2(a->critic, Pt, a->sh_target, a->xc_next, a->ft, false, Pc, a->sh_critic, a->xc_cur, a->fc, false, W, B, s));
-    } else {
-        EXORL_TRY(net_forward(a->critic, Pt, a->sh_target, a->xc_next, W, B, a->ft, false, false, prec, s));
-        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, false, false, prec, s));
-    }
+    EXORL_TRY(twin_forward(a, s, Fork{}, a->xc_next, false));
     FwdBufs fpi = a->fc;
     fpi.out = a->dq;
     EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_pi, W, B, fpi, false, false, prec, s));
@@ -1736,13 +1736,8 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
 int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream) {
     EXORL_REQUIRE(a && sums_host && rows_host, "agent_eval_read: null argument");
     EXORL_REQUIRE(a->eval_sums, "agent_eval_read: no eval buffer (exorl_agent_set_eval)");
-    hipStream_t s = as_stream(stream);
-    double host[EXORL_N_EVAL];
-    EXORL_CHECK_HIP(hipMemcpyAsync(host, a->eval_sums, sizeof(host), hipMemcpyDeviceToHost, s));
-    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(a->eval_sums, 0, sizeof(host), s));
-    EXORL_CHECK_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < EXORL_N_EVAL; ++i) sums_host[i] = host[i];
-    *rows_host = (int64_t)host[EXORL_E_ROWS];
+    EXORL_TRY(read_window(a->eval_sums, EXORL_N_EVAL, sums_host, nullptr, reset, as_stream(stream)));
+    *rows_host = (int64_t)sums_host[EXORL_E_ROWS];
     return 0;
 }
 
@@ -1759,17 +1754,9 @@ size_t exorl_agent_fqe_value_bytes(const exorl_agent_cfg* cfg) {
 
 int exorl_agent_set_fqe_value(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     EXORL_REQUIRE(a, "agent_set_fqe_value: null handle");
-    if (!buf_dev) {
-        a->fqe_value_sums = a->fqe_value_part = nullptr;
-        return 0;
-    }
+    if (!buf_dev) return attach_window("agent_set_fqe_value", nullptr, 0, 0, &a->fqe_value_sums, &a->fqe_value_part);
     EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_FQE, "agent_set_fqe_value: kind %d is not FQE", a->cfg.kind);
-    const size_t need = fqe_value_bytes(a->cfg);
-    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_fqe_value: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
-    EXORL_CHECK_HIP(hipMemset(buf_dev, 0, WIN_HEAD_BYTES));      // an empty window; the partials behind it are written before they are read
-    a->fqe_value_sums = static_cast<double*>(buf_dev);
-    a->fqe_value_part = reinterpret_cast<double*>(static_cast<char*>(buf_dev) + WIN_HEAD_BYTES);
-    return 0;
+    return attach_window("agent_set_fqe_value", buf_dev, bytes, fqe_value_bytes(a->cfg), &a->fqe_value_sums, &a->fqe_value_part);
 }
 
 // Forward-only, as exorl_agent_evaluate: the inputs are staged with the step state left where it is, the actor runs on the obs rows (the half of
@@ -1783,7 +1770,7 @@ int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream) {
     hipStream_t s = as_stream(stream);
     const auto& cfg = a->cfg;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
-    EXORL_TRY(prepare_inputs(a->obs, a->action, a->next_obs, a->xa, a->xc_cur, a->xc_next, a->xc_pi, B, O, A, 1, nullptr, 0, s));
+    EXORL_TRY(open_step(a, nullptr, s));
     const FwdBufs f = a->fa.rows_from(B, H, A);
     EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa + (int64_t)B * O, O, B, f, false, true, prec, s));
     EXORL_TRY(fqe_mean_actions(f.out, a->xc_pi + O, W, B, A, s));
@@ -1794,13 +1781,8 @@ int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream) {
 int exorl_agent_fqe_value_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream) {
     EXORL_REQUIRE(a && sums_host && rows_host, "agent_fqe_value_read: null argument");
     EXORL_REQUIRE(a->fqe_value_sums, "agent_fqe_value_read: no value window (exorl_agent_set_fqe_value)");
-    hipStream_t s = as_stream(stream);
-    double host[EXORL_N_FQE_VALUE];
-    EXORL_CHECK_HIP(hipMemcpyAsync(host, a->fqe_value_sums, sizeof(host), hipMemcpyDeviceToHost, s));
-    if (reset) EXORL_CHECK_HIP(hipMemsetAsync(a->fqe_value_sums, 0, sizeof(host), s));
-    EXORL_CHECK_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < EXORL_N_FQE_VALUE; ++i) sums_host[i] = host[i];
-    *rows_host = (int64_t)host[EXORL_FQE_V_ROWS];
+    EXORL_TRY(read_window(a->fqe_value_sums, EXORL_N_FQE_VALUE, sums_host, nullptr, reset, as_stream(stream)));
+    *rows_host = (int64_t)sums_host[EXORL_FQE_V_ROWS];
     return 0;
 }
 
@@ -1810,14 +1792,10 @@ int exorl_agent_disable_graph(exorl_agent_t* a) {
     return release_graph(a);
 }
 
-// One captured step: replay sample (Philox) + update phases 0..3, one hipGraphLaunch.
+// One captured step: replay sample (Philox) + the kind's whole update plan, one hipGraphLaunch.
 int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
     EXORL_REQUIRE(a && a->graph_exec, "agent_step_graph: no captured graph (call exorl_agent_enable_graph)");
-    EXORL_REQUIRE(stddev > 0.f || a->cfg.kind == EXORL_AGENT_CQL, "agent_step_graph: stddev must be > 0");
-    if (a->cfg.kind != EXORL_AGENT_CQL && stddev != a->dev_stddev) {       // schedule moved: one scalar write ahead of the launch, same stream
-        EXORL_TRY(set_device_float(&a->state->stddev, stddev, as_stream(stream)));
-        a->dev_stddev = stddev;
-    }
+    EXORL_TRY(push_stddev(a, "agent_step_graph", stddev, as_stream(stream)));      // schedule moved: one scalar write ahead of the launch, same stream
     EXORL_REQUIRE(replay_weights_epoch(a->graph_replay) == a->graph_weights_epoch, "agent_step_graph: exorl_replay_set_weights was called after "
                   "the capture: the graph samples the table it was captured with (call exorl_agent_enable_graph again)");
     EXORL_REQUIRE(replay_norm_on(a->graph_replay) == a->graph_norm_on, "agent_step_graph: exorl_replay_set_obs_norm switched the "

@@ -490,7 +490,7 @@ int repeat_sample(const float* obs, const float* mu, const float* noise, uint64_
                   float stddev, float clip, float* xc_rep, int B, int O, int A, int n, hipStream_t s, const float* stddev_ptr = nullptr);
 // w_b = f(min(Q1,Q2)(s_b, a_b) - mean_i min(Q1,Q2)(s_b, a_bi))
 int crr_weights(const float* q_rep, const float* q_data, float* w, int B, int n, int weight_func, hipStream_t s);
-// IQL's row kernel (loss.hip, iql_rows_kernel): from the target heads tq (2, rows), the critic heads q (2, rows), v = V(s), vn = V(s'), reward and
+// IQL's row kernel (loss.hip, chunk_rows_kernel<IqlRow>): from the target heads tq (2, rows), the critic heads q (2, rows), v = V(s), vn = V(s'), reward and
 // discount, in one pass: dv (rows) = d L_V / d v, dq (2, rows) = d L_Q / d Q_j, w (rows) = the actor step's advantage weights, and per chunk of
 // IQL_CHUNK_ROWS rows the IQL_PARTS sums below. iql_sums adds them in chunk order: into sums (raw, IQL_P_* order) and / or as partial means over
 // the global batch into metrics' EXORL_M_* slots; either may be null.
@@ -506,7 +506,7 @@ struct IqlRowsArgs {
 };
 int iql_rows(const IqlRowsArgs& a, hipStream_t s);
 int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
-// FQE's row kernel (loss.hip, fqe_rows_kernel), on iql_rows' chunking: from the target heads tq (2, rows), the critic heads q (2, rows), reward
+// FQE's row kernel (loss.hip, chunk_rows_kernel<FqeRow>), on iql_rows' chunking: from the target heads tq (2, rows), the critic heads q (2, rows), reward
 // and discount: dq (2, rows) = d L / d Q_i with each net regressed on its OWN target y_i = r + D Q'_i (no min), and per chunk the FQE_PARTS sums
 // below. fqe_sums adds them in chunk order: into sums (raw, FQE_P_* order) and / or as partial means over the global batch into metrics' slots.
 enum { FQE_P_REWARD, FQE_P_TARGET, FQE_P_Q1, FQE_P_Q2, FQE_P_ERR1, FQE_P_ERR2, FQE_PARTS };

@@ -689,14 +689,16 @@ __global__ __launch_bounds__(256) void eval_partials_kernel(const EvalArgs e) {
     if (threadIdx.x < EVAL_PARTS) e.part[(int64_t)blockIdx.x * EVAL_PARTS + threadIdx.x] = v[threadIdx.x];
 }
 
-// One wave. Thread i < EVAL_PARTS owns slot i: its partials in chunk order, as doubles, then one add to the window. Thread EXORL_E_ROWS counts.
-__global__ __launch_bounds__(64) void eval_window_kernel(const float* __restrict__ part, int chunks, int rows, double* sums) {
+// One wave, for the evaluation's window (float partials) and FQE's value window (double partials). Thread i < PARTS owns slot i: its partials in
+// chunk order, as doubles, then one add to the window. Thread PARTS, the slot behind the sums (EXORL_E_ROWS, EXORL_FQE_V_ROWS), counts the rows.
+template <int PARTS, typename Part>
+__global__ __launch_bounds__(64) void sum_window_kernel(const Part* __restrict__ part, int chunks, int rows, double* sums) {
     const int t = threadIdx.x;
-    if (t < EVAL_PARTS) {
+    if (t < PARTS) {
         double acc = 0.0;
-        for (int ch = 0; ch < chunks; ++ch) acc += (double)part[(int64_t)ch * EVAL_PARTS + t];
+        for (int ch = 0; ch < chunks; ++ch) acc += (double)part[(int64_t)ch * PARTS + t];
         sums[t] += acc;
-    } else if (t == EXORL_E_ROWS) {
+    } else if (t == PARTS) {
         sums[t] += (double)rows;
     }
 }
@@ -705,149 +707,126 @@ int eval_reduce(const EvalArgs& e, hipStream_t s) {
     const int chunks = eval_chunks(e.rows);
     hipLaunchKernelGGL(eval_partials_kernel, dim3(chunks), dim3(EVAL_CHUNK_ROWS), 0, s, e);
     EXORL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(eval_window_kernel, dim3(1), dim3(64), 0, s, e.part, chunks, e.rows, e.sums);
+    hipLaunchKernelGGL((sum_window_kernel<EVAL_PARTS, float>), dim3(1), dim3(64), 0, s, e.part, chunks, e.rows, e.sums);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- IQL: the five head outputs of a step -> all three loss gradients, the advantage weights and the metrics' per-chunk sums, one pass --------
+// ---- chunked row kernels: IQL's and FQE's loss rows -> gradients and the metrics' per-chunk sums, one pass -------------------------------------
 // One thread per row, IQL_CHUNK_ROWS rows per chunk; at most IQL_MAX_WG workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...
-// The partials are per chunk, not per workgroup, so the sums do not depend on the grid. Rows past the end add zeros.
+// The partials are per chunk, not per workgroup, so the sums do not depend on the grid. Rows past the end add zeros. Row is the functor of one
+// kind: its arguments (rows, part among them), Row::PARTS and row(m, p), which writes row m's outputs and fills p[PARTS] with its terms.
+static_assert(IQL_CHUNK_ROWS == 256, "chunk_rows_kernel: one thread per row of the chunk");
+template <typename Row>
+__global__ __launch_bounds__(256) void chunk_rows_kernel(const Row a) {
+    constexpr int PARTS = Row::PARTS;
+    __shared__ float sm[PARTS][16];
+    const int chunks = iql_chunks(a.rows);
+    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+        const int m = ch * IQL_CHUNK_ROWS + threadIdx.x;
+        float p[PARTS] = {};
+        if (m < a.rows) a.row(m, p);
+        block_sum<PARTS>(p, sm);
+#pragma unroll
+        for (int i = 0; i < PARTS; ++i)           // constant indices: p stays in registers
+            if (threadIdx.x == i) a.part[(int64_t)ch * PARTS + i] = p[i];
+    }
+}
+
+// IQL: the five head outputs of a step -> all three loss gradients, the advantage weights and the metric terms
 //   u = min(Q'_1, Q'_2)(s, a) - V(s);  k = u < 0 ? 1 - expectile : expectile;  dV = -2 k u / Bg          (expectile regression of V on Q')
 //   y = r + D V(s');                   dQ_j = 2 (Q_j - y) / Bg, with Q_j - (r + D V(s')) formed in double and rounded once: where Q_j is close
 //                                      to y the difference cancels, and two fp32 roundings at the size of y would be many ulp of the result
 //   w = expf(temperature u), max_weight where that is larger: an expf that overflows is +inf and gives max_weight exactly; a NaN u (a diverged
 //                                      net) stays NaN in w, as it does in dv and dq, rather than turning into max_weight
-static_assert(IQL_CHUNK_ROWS == 256, "iql_rows_kernel: one thread per row of the chunk");
-__global__ __launch_bounds__(256) void iql_rows_kernel(const IqlRowsArgs a) {
-    __shared__ float sm[IQL_PARTS][16];
-    const int chunks = iql_chunks(a.rows);
-    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
-        const int m = ch * IQL_CHUNK_ROWS + threadIdx.x;
-        float p[IQL_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (m < a.rows) {
-            const float v = a.v[m], r = a.reward[m];
-            const float u = fminf(a.tq[m], a.tq[a.rows + m]) - v;
-            const float k = u < 0.f ? 1.0f - a.expectile : a.expectile;
-            a.dv[m] = -2.0f * k * u * a.inv_bg;
-            const float y = r + a.discount[m] * a.vn[m];
-            const float q1 = a.q[m], q2 = a.q[a.rows + m];
-            const double yd = (double)r + (double)a.discount[m] * (double)a.vn[m];
-            const float e1 = (float)((double)q1 - yd), e2 = (float)((double)q2 - yd);
-            a.dq[m] = 2.0f * e1 * a.inv_bg;
-            a.dq[a.rows + m] = 2.0f * e2 * a.inv_bg;
-            const float ex = expf(a.temperature * u);
-            const float w = ex > a.max_weight ? a.max_weight : ex;
-            a.w[m] = w;
-            p[IQL_P_REWARD] = r; p[IQL_P_TARGET] = y; p[IQL_P_Q1] = q1; p[IQL_P_Q2] = q2; p[IQL_P_ERR1] = e1 * e1; p[IQL_P_ERR2] = e2 * e2;
-            p[IQL_P_VLOSS] = k * u * u; p[IQL_P_V] = v; p[IQL_P_ADV] = u; p[IQL_P_W] = w;
-        }
-        block_sum<IQL_PARTS>(p, sm);
-#pragma unroll
-        for (int i = 0; i < IQL_PARTS; ++i)       // constant indices: p stays in registers
-            if (threadIdx.x == i) a.part[(int64_t)ch * IQL_PARTS + i] = p[i];
+struct IqlRow : IqlRowsArgs {
+    static constexpr int PARTS = IQL_PARTS;
+    __device__ void row(int m, float* p) const {
+        const float v = this->v[m], r = reward[m];
+        const float u = fminf(tq[m], tq[rows + m]) - v;
+        const float k = u < 0.f ? 1.0f - expectile : expectile;
+        dv[m] = -2.0f * k * u * inv_bg;
+        const float y = r + discount[m] * vn[m];
+        const float q1 = q[m], q2 = q[rows + m];
+        const double yd = (double)r + (double)discount[m] * (double)vn[m];
+        const float e1 = (float)((double)q1 - yd), e2 = (float)((double)q2 - yd);
+        dq[m] = 2.0f * e1 * inv_bg;
+        dq[rows + m] = 2.0f * e2 * inv_bg;
+        const float ex = expf(temperature * u);
+        const float w = ex > max_weight ? max_weight : ex;
+        this->w[m] = w;
+        p[IQL_P_REWARD] = r; p[IQL_P_TARGET] = y; p[IQL_P_Q1] = q1; p[IQL_P_Q2] = q2; p[IQL_P_ERR1] = e1 * e1; p[IQL_P_ERR2] = e2 * e2;
+        p[IQL_P_VLOSS] = k * u * u; p[IQL_P_V] = v; p[IQL_P_ADV] = u; p[IQL_P_W] = w;
     }
-}
+};
 
-// One wave. Thread i < IQL_PARTS adds quantity i's partials in chunk order (chunk_sum): no atomics, the same bits on every run. sums (the unit
-// export): the raw sums. metrics (the step): the partial means over the global batch in their EXORL_M_* slots.
-__global__ __launch_bounds__(64) void iql_sums_kernel(const float* __restrict__ part, int chunks, float inv_bg, float* __restrict__ sums,
-                                                      float* __restrict__ metrics) {
-    __shared__ float tot[IQL_PARTS];
-    const int t = threadIdx.x;
-    const float sum = chunk_sum(part + (t < IQL_PARTS ? t : 0), t < IQL_PARTS ? chunks : 0, IQL_PARTS);
-    if (t < IQL_PARTS) {
-        tot[t] = sum;
-        if (sums) sums[t] = sum;
-    }
-    __syncthreads();
-    if (t == 0 && metrics) {
-        metrics[EXORL_M_BATCH_REWARD] = tot[IQL_P_REWARD] * inv_bg;
-        metrics[EXORL_M_CRITIC_TARGET_Q] = tot[IQL_P_TARGET] * inv_bg;
-        metrics[EXORL_M_CRITIC_Q1] = tot[IQL_P_Q1] * inv_bg;
-        metrics[EXORL_M_CRITIC_Q2] = tot[IQL_P_Q2] * inv_bg;
-        metrics[EXORL_M_CRITIC_LOSS] = (tot[IQL_P_ERR1] + tot[IQL_P_ERR2]) * inv_bg;
-        metrics[EXORL_M_VALUE_LOSS] = tot[IQL_P_VLOSS] * inv_bg;
-        metrics[EXORL_M_VALUE] = tot[IQL_P_V] * inv_bg;
-        metrics[EXORL_M_ADV] = tot[IQL_P_ADV] * inv_bg;
-        metrics[EXORL_M_ACTOR_WEIGHT] = tot[IQL_P_W] * inv_bg;
-    }
-}
-
-int iql_rows(const IqlRowsArgs& a, hipStream_t s) {
-    const int chunks = iql_chunks(a.rows);
-    hipLaunchKernelGGL(iql_rows_kernel, dim3(chunks < IQL_MAX_WG ? chunks : IQL_MAX_WG), dim3(IQL_CHUNK_ROWS), 0, s, a);
-    EXORL_LAUNCH_CHECK();
-    return 0;
-}
-
-int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
-    hipLaunchKernelGGL(iql_sums_kernel, dim3(1), dim3(64), 0, s, part, iql_chunks(rows), inv_bg, sums, metrics);
-    EXORL_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- FQE: target and critic heads of a step -> the critic loss gradient and the metrics' per-chunk sums, one pass ------------------------------
-// iql_rows_kernel's arrangement: one thread per row, IQL_CHUNK_ROWS rows per chunk, at most IQL_MAX_WG workgroups striding over the chunks, the
-// partials per chunk so that the sums do not depend on the grid. Each net has its own target (no min over the twins):
+// FQE: target and critic heads of a step -> the critic loss gradient and the metric terms. Each net has its own target (no min over the twins):
 //   y_i = r + D Q'_i(s', mu(s'));   dQ_i = 2 (Q_i - y_i) / Bg
 // Q_i - (r + D Q'_i) is formed in double (exact products and a 53-bit sum of three fp32-sized terms) and rounded once to fp32; 2 e is exact and
 // the product with 1/Bg rounds once more: two roundings, so dq is within 1 ulp of the float64 value of 2 (Q_i - y_i) inv_bg. A row where Q_i is
 // within 1e-6 of y_i keeps its own ulp: the cancellation happens in double.
-__global__ __launch_bounds__(256) void fqe_rows_kernel(const FqeRowsArgs a) {
-    __shared__ float sm[FQE_PARTS][16];
-    const int chunks = iql_chunks(a.rows);
-    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
-        const int m = ch * IQL_CHUNK_ROWS + threadIdx.x;
-        float p[FQE_PARTS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (m < a.rows) {
-            const float r = a.reward[m], D = a.discount[m];
-            const float q1 = a.q[m], q2 = a.q[a.rows + m];
-            const double y1 = (double)r + (double)D * (double)a.tq[m], y2 = (double)r + (double)D * (double)a.tq[a.rows + m];
-            const float e1 = (float)((double)q1 - y1), e2 = (float)((double)q2 - y2);
-            a.dq[m] = 2.0f * e1 * a.inv_bg;
-            a.dq[a.rows + m] = 2.0f * e2 * a.inv_bg;
-            p[FQE_P_REWARD] = r; p[FQE_P_TARGET] = (float)(0.5 * (y1 + y2)); p[FQE_P_Q1] = q1; p[FQE_P_Q2] = q2;
-            p[FQE_P_ERR1] = e1 * e1; p[FQE_P_ERR2] = e2 * e2;
-        }
-        block_sum<FQE_PARTS>(p, sm);
-#pragma unroll
-        for (int i = 0; i < FQE_PARTS; ++i)       // constant indices: p stays in registers
-            if (threadIdx.x == i) a.part[(int64_t)ch * FQE_PARTS + i] = p[i];
+struct FqeRow : FqeRowsArgs {
+    static constexpr int PARTS = FQE_PARTS;
+    __device__ void row(int m, float* p) const {
+        const float r = reward[m], D = discount[m];
+        const float q1 = q[m], q2 = q[rows + m];
+        const double y1 = (double)r + (double)D * (double)tq[m], y2 = (double)r + (double)D * (double)tq[rows + m];
+        const float e1 = (float)((double)q1 - y1), e2 = (float)((double)q2 - y2);
+        dq[m] = 2.0f * e1 * inv_bg;
+        dq[rows + m] = 2.0f * e2 * inv_bg;
+        p[FQE_P_REWARD] = r; p[FQE_P_TARGET] = (float)(0.5 * (y1 + y2)); p[FQE_P_Q1] = q1; p[FQE_P_Q2] = q2;
+        p[FQE_P_ERR1] = e1 * e1; p[FQE_P_ERR2] = e2 * e2;
     }
-}
+};
 
-// One wave, iql_sums_kernel's arrangement: thread i < FQE_PARTS adds quantity i's partials in chunk order.
-__global__ __launch_bounds__(64) void fqe_sums_kernel(const float* __restrict__ part, int chunks, float inv_bg, float* __restrict__ sums,
-                                                      float* __restrict__ metrics) {
-    __shared__ float tot[FQE_PARTS];
+// Part index -> metric slot; -1: no slot of its own. EXORL_M_CRITIC_LOSS is the sum of the two error parts, which sit side by side at err1.
+template <int PARTS> struct SumSlots { int slot[PARTS]; int err1; };
+constexpr SumSlots<IQL_PARTS> IQL_SLOTS = {{EXORL_M_BATCH_REWARD, EXORL_M_CRITIC_TARGET_Q, EXORL_M_CRITIC_Q1, EXORL_M_CRITIC_Q2, -1, -1,
+                                            EXORL_M_VALUE_LOSS, EXORL_M_VALUE, EXORL_M_ADV, EXORL_M_ACTOR_WEIGHT}, IQL_P_ERR1};
+constexpr SumSlots<FQE_PARTS> FQE_SLOTS = {{EXORL_M_BATCH_REWARD, EXORL_M_CRITIC_TARGET_Q, EXORL_M_CRITIC_Q1, EXORL_M_CRITIC_Q2, -1, -1}, FQE_P_ERR1};
+static_assert(IQL_P_ERR2 == IQL_P_ERR1 + 1 && FQE_P_ERR2 == FQE_P_ERR1 + 1, "chunk_sums_kernel adds err1 and the part behind it");
+
+// One wave. Thread i < PARTS adds quantity i's partials in chunk order (chunk_sum): no atomics, the same bits on every run. sums (the unit
+// exports): the raw sums. metrics (the step): the partial means over the global batch in their EXORL_M_* slots.
+template <int PARTS>
+__global__ __launch_bounds__(64) void chunk_sums_kernel(const float* __restrict__ part, int chunks, float inv_bg, float* __restrict__ sums,
+                                                        float* __restrict__ metrics, const SumSlots<PARTS> to) {
+    __shared__ float tot[PARTS];
     const int t = threadIdx.x;
-    const float sum = chunk_sum(part + (t < FQE_PARTS ? t : 0), t < FQE_PARTS ? chunks : 0, FQE_PARTS);
-    if (t < FQE_PARTS) {
+    const float sum = chunk_sum(part + (t < PARTS ? t : 0), t < PARTS ? chunks : 0, PARTS);
+    if (t < PARTS) {
         tot[t] = sum;
         if (sums) sums[t] = sum;
     }
     __syncthreads();
     if (t == 0 && metrics) {
-        metrics[EXORL_M_BATCH_REWARD] = tot[FQE_P_REWARD] * inv_bg;
-        metrics[EXORL_M_CRITIC_TARGET_Q] = tot[FQE_P_TARGET] * inv_bg;
-        metrics[EXORL_M_CRITIC_Q1] = tot[FQE_P_Q1] * inv_bg;
-        metrics[EXORL_M_CRITIC_Q2] = tot[FQE_P_Q2] * inv_bg;
-        metrics[EXORL_M_CRITIC_LOSS] = (tot[FQE_P_ERR1] + tot[FQE_P_ERR2]) * inv_bg;
+#pragma unroll
+        for (int i = 0; i < PARTS; ++i)
+            if (to.slot[i] >= 0) metrics[to.slot[i]] = tot[i] * inv_bg;
+        metrics[EXORL_M_CRITIC_LOSS] = (tot[to.err1] + tot[to.err1 + 1]) * inv_bg;
     }
 }
 
-int fqe_rows(const FqeRowsArgs& a, hipStream_t s) {
+template <typename Row, typename Args>
+static int chunk_rows(const Args& a, hipStream_t s) {
     const int chunks = iql_chunks(a.rows);
-    hipLaunchKernelGGL(fqe_rows_kernel, dim3(chunks < IQL_MAX_WG ? chunks : IQL_MAX_WG), dim3(IQL_CHUNK_ROWS), 0, s, a);
+    hipLaunchKernelGGL(chunk_rows_kernel<Row>, dim3(chunks < IQL_MAX_WG ? chunks : IQL_MAX_WG), dim3(IQL_CHUNK_ROWS), 0, s, Row{a});
     EXORL_LAUNCH_CHECK();
     return 0;
 }
-
-int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
-    hipLaunchKernelGGL(fqe_sums_kernel, dim3(1), dim3(64), 0, s, part, iql_chunks(rows), inv_bg, sums, metrics);
+template <int PARTS>
+static int chunk_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, const SumSlots<PARTS>& to, hipStream_t s) {
+    hipLaunchKernelGGL(chunk_sums_kernel<PARTS>, dim3(1), dim3(64), 0, s, part, iql_chunks(rows), inv_bg, sums, metrics, to);
     EXORL_LAUNCH_CHECK();
     return 0;
+}
+int iql_rows(const IqlRowsArgs& a, hipStream_t s) { return chunk_rows<IqlRow>(a, s); }
+int fqe_rows(const FqeRowsArgs& a, hipStream_t s) { return chunk_rows<FqeRow>(a, s); }
+int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
+    return chunk_sums(part, rows, inv_bg, sums, metrics, IQL_SLOTS, s);
+}
+int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
+    return chunk_sums(part, rows, inv_bg, sums, metrics, FQE_SLOTS, s);
 }
 
 __global__ __launch_bounds__(256) void fqe_mean_actions_kernel(const float* __restrict__ mu, float* __restrict__ dst, int64_t dst_ld, int rows, int A) {
@@ -886,23 +865,11 @@ __global__ __launch_bounds__(256) void fqe_value_partials_kernel(const float* __
     if (t < FQE_VALUE_PARTS) part[(int64_t)blockIdx.x * FQE_VALUE_PARTS + t] = sm[t][0];
 }
 
-// One wave. Thread i < FQE_VALUE_PARTS owns slot i: its partials in chunk order, then one add to the window. Thread EXORL_FQE_V_ROWS counts.
-__global__ __launch_bounds__(64) void fqe_value_window_kernel(const double* __restrict__ part, int chunks, int rows, double* sums) {
-    const int t = threadIdx.x;
-    if (t < FQE_VALUE_PARTS) {
-        double acc = 0.0;
-        for (int ch = 0; ch < chunks; ++ch) acc += part[(int64_t)ch * FQE_VALUE_PARTS + t];
-        sums[t] += acc;
-    } else if (t == EXORL_FQE_V_ROWS) {
-        sums[t] += (double)rows;
-    }
-}
-
 int fqe_value_reduce(const float* q, int ld, int rows, double* part, double* sums, hipStream_t s) {
     const int chunks = iql_chunks(rows);
     hipLaunchKernelGGL(fqe_value_partials_kernel, dim3(chunks), dim3(IQL_CHUNK_ROWS), 0, s, q, ld, rows, part);
     EXORL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fqe_value_window_kernel, dim3(1), dim3(64), 0, s, part, chunks, rows, sums);
+    hipLaunchKernelGGL((sum_window_kernel<FQE_VALUE_PARTS, double>), dim3(1), dim3(64), 0, s, part, chunks, rows, sums);
     EXORL_LAUNCH_CHECK();
     return 0;
 }

@@ -284,79 +284,70 @@ class AgentEngine(_Phased):
     def set_metrics(self, enable):
         L.check(self.lib.exorl_agent_set_metrics(self.h, int(bool(enable))))
 
+    # ---- the three sum windows (metric window, evaluation, FQE's value pass): exorl_agent_<name>_bytes / set_<name> / <name>_read ------
+    def _window_bytes(self, name):
+        return int(getattr(self.lib, f'exorl_agent_{name}_bytes')(C.byref(self.cfg)))
+
+    def _set_window(self, name, keep, buf):
+        """Attach a torch-owned buffer: True allocates one of the window's size, a uint8 tensor of at least that size is taken as it is
+        (its contents do not matter), None detaches. The tensor is kept on the engine as `keep`."""
+        fn = getattr(self.lib, f'exorl_agent_set_{name}')
+        if buf is None:
+            L.check(fn(self.h, None, 0))
+            setattr(self, keep, None)
+            return
+        if buf is True:
+            buf = torch.empty(self._window_bytes(name), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
+        L.check(fn(self.h, buf.data_ptr(), buf.numel()))
+        setattr(self, keep, buf)
+
+    def _read_window(self, name, n, reset):
+        """(sums, count) of the window: n float64 sums and the steps or rows in them; reset empties the window."""
+        sums, count = np.zeros(n, np.float64), C.c_int64()
+        L.check(getattr(self.lib, f'exorl_agent_{name}_read')(self.h, sums.ctypes.data, C.byref(count), int(bool(reset)), L.current_stream()))
+        return sums, int(count.value)
+
     def metric_window_bytes(self):
-        return int(self.lib.exorl_agent_metric_window_bytes(C.byref(self.cfg)))
+        return self._window_bytes('metric_window')
 
     def set_metric_window(self, buf=True):
-        """Windowed metrics (exorl_agent_set_metric_window) on a torch-owned buffer: True allocates one, a uint8 tensor of at least
-        metric_window_bytes() is taken as it is (its contents do not matter), None switches the mode off."""
-        if buf is None:
-            L.check(self.lib.exorl_agent_set_metric_window(self.h, None, 0))
-            self._window = None
-            return
-        if buf is True:
-            buf = torch.empty(self.metric_window_bytes(), dtype=torch.uint8, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
-        L.check(self.lib.exorl_agent_set_metric_window(self.h, buf.data_ptr(), buf.numel()))
-        self._window = buf
+        """Windowed metrics (exorl_agent_set_metric_window); None switches the mode off."""
+        self._set_window('metric_window', '_window', buf)
 
     def metric_window_read(self, reset=True):
-        """(sums, steps) of the window: float64 sums per metric slot and the number of steps in them; reset empties the window."""
-        sums, steps = np.zeros(L.N_METRICS, np.float64), C.c_int64()
-        L.check(self.lib.exorl_agent_metric_window_read(self.h, sums.ctypes.data, C.byref(steps), int(bool(reset)), L.current_stream()))
-        return sums, int(steps.value)
+        """(sums, steps): float64 sums per metric slot and the number of steps in them."""
+        return self._read_window('metric_window', L.N_METRICS, reset)
 
     def eval_bytes(self):
-        return int(self.lib.exorl_agent_eval_bytes(C.byref(self.cfg)))
+        return self._window_bytes('eval')
 
     def set_eval(self, buf=True):
-        """The forward-only evaluation's window (exorl_agent_set_eval) on a torch-owned buffer: True allocates eval_bytes(), a uint8 tensor of
-        at least that size is taken as it is, None detaches."""
-        if buf is None:
-            L.check(self.lib.exorl_agent_set_eval(self.h, None, 0))
-            self._eval = None
-            return
-        if buf is True:
-            buf = torch.empty(self.eval_bytes(), dtype=torch.uint8, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
-        L.check(self.lib.exorl_agent_set_eval(self.h, buf.data_ptr(), buf.numel()))
-        self._eval = buf
+        """The forward-only evaluation's window (exorl_agent_set_eval)."""
+        self._set_window('eval', '_eval', buf)
 
     def evaluate(self):
         """One forward-only pass on the rows in the batch slots, added to the window (exorl_agent_evaluate): no step state moves."""
         L.check(self.lib.exorl_agent_evaluate(self.h, L.current_stream()))
 
     def eval_read(self, reset=True):
-        """(sums, rows) of the window: float64 sums per L.E_* slot and the rows in them; reset empties the window."""
-        sums, rows = np.zeros(L.N_EVAL, np.float64), C.c_int64()
-        L.check(self.lib.exorl_agent_eval_read(self.h, sums.ctypes.data, C.byref(rows), int(bool(reset)), L.current_stream()))
-        return sums, int(rows.value)
+        """(sums, rows): float64 sums per L.E_* slot and the rows in them."""
+        return self._read_window('eval', L.N_EVAL, reset)
 
     def fqe_value_bytes(self):
-        return int(self.lib.exorl_agent_fqe_value_bytes(C.byref(self.cfg)))
+        return self._window_bytes('fqe_value')
 
     def set_fqe_value(self, buf=True):
-        """The value pass's window (exorl_agent_set_fqe_value) on a torch-owned buffer: True allocates fqe_value_bytes(), a uint8 tensor of at
-        least that size is taken as it is, None detaches."""
-        if buf is None:
-            L.check(self.lib.exorl_agent_set_fqe_value(self.h, None, 0))
-            self._fqe_value = None
-            return
-        if buf is True:
-            buf = torch.empty(self.fqe_value_bytes(), dtype=torch.uint8, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()      # the call clears the window's sums itself, behind whatever wrote `buf`
-        L.check(self.lib.exorl_agent_set_fqe_value(self.h, buf.data_ptr(), buf.numel()))
-        self._fqe_value = buf
+        """The value pass's window (exorl_agent_set_fqe_value)."""
+        self._set_window('fqe_value', '_fqe_value', buf)
 
     def fqe_value(self, rows):
         """One forward-only pass of Q(s, mu(s)) on the first `rows` obs rows in the batch slots, added to the window (exorl_agent_fqe_value)."""
         L.check(self.lib.exorl_agent_fqe_value(self.h, int(rows), L.current_stream()))
 
     def fqe_value_read(self, reset=True):
-        """(sums, rows) of the window: float64 sums per L.FQE_V_* slot and the rows in them; reset empties the window."""
-        sums, rows = np.zeros(L.N_FQE_VALUE, np.float64), C.c_int64()
-        L.check(self.lib.exorl_agent_fqe_value_read(self.h, sums.ctypes.data, C.byref(rows), int(bool(reset)), L.current_stream()))
-        return sums, int(rows.value)
+        """(sums, rows): float64 sums per L.FQE_V_* slot and the rows in them."""
+        return self._read_window('fqe_value', L.N_FQE_VALUE, reset)
 
     def cql_alpha_state(self):
         host = np.zeros(6, np.float32)

@@ -397,3 +397,10 @@ def test_train_offline_with_validation(tmp_path):
     assert strip(rows0) == strip(rows1) and [s for s, _ in strip(rows0)] == [0, 3, 6, 9]
     assert all(torch.equal(a, b) for a, b in zip(p0, p1))
     assert val[0][1]['val_bc_mse'] > 0
+
+
+def test_window_attach_read_reset_detach():
+    """The evaluation's window through its whole life at batch 259, and the buffers exorl_agent_set_eval refuses (tests/_windows.py)."""
+    import _windows as W
+    eng = W.engine('td3_bc')
+    W.check_window(eng, 'eval', eng.evaluate, W.B, 'no eval buffer')

@@ -39,3 +39,54 @@ def test_update_steps_yields_the_plans_exchanges(kind, lagrange):
     assert got == want
     after = eng.opt_steps()
     assert after == (before[0] + 1, before[1] + (kind != 'bc')), (before, after)
+
+
+# The phase ids exorl_agent_update_phase accepts per kind, in an order in which every phase finds the buffers of the ones before it filled
+# (written down from run_phase as it stood before the phase tables: BC takes phase 1 as a no-op; CQL takes its split phases 4 and 5 with or
+# without the Lagrange weight and refuses phase 0 only with it under data parallelism). Every other id in 0..11 is refused.
+FAMILY = [0, 1, 2, 3]
+ACCEPTED = [
+    # kind, act_dim, world_size, lagrange, accepted ids in a runnable order
+    ('td3_bc', 2, 1, False, FAMILY), ('td3', 2, 1, False, FAMILY), ('bc', 2, 1, False, FAMILY), ('ddpg', 2, 1, False, FAMILY),
+    ('crr', 2, 1, False, FAMILY), ('aps', 2, 1, False, FAMILY),
+    ('td3_bc', 1, 1, False, FAMILY),                       # act_dim 1: the actor head's unfused sampling path
+    ('cql', 2, 1, False, [0, 1, 2, 3, 4, 5]),
+    ('cql', 2, 1, True, [0, 1, 2, 3, 4, 5]),
+    ('cql', 2, 2, True, [4, 5, 1, 2, 3]),
+    ('iql', 2, 1, False, [6, 7, 8, 9]),
+    ('fqe', 2, 1, False, [10, 11]),
+]
+
+
+@pytest.mark.parametrize('kind, act_dim, world_size, lagrange, accepted', ACCEPTED)
+def test_update_phase_accepts_exactly_the_kinds_phases(kind, act_dim, world_size, lagrange, accepted):
+    import hashlib
+
+    from exorl_amd import _lib as L
+    from exorl_amd.engine import AgentEngine
+    Bp = 259                                                # a ragged second chunk of the 256-row kernels
+    eng = AgentEngine(kind, O, act_dim, 4, Bp, precision='fp32', world_size=world_size, use_critic_lagrange=lagrange,
+                      sf_dim=2 if kind == 'aps' else 0, alpha=0.01 if kind == 'cql' else 2.5, num_value_samples=2, n_samples=1)
+    gen = torch.Generator().manual_seed(5)
+    for net in [L.NET_ACTOR] + ([L.NET_CRITIC] if kind != 'bc' else []) + ([L.NET_VALUE] if kind == 'iql' else []):
+        flat = eng.flat(net)
+        flat.copy_(0.3 * torch.randn(flat.numel(), generator=gen))
+    eng.params_changed(sync_target=True)
+    eng.set_batch(*[torch.randn(n, generator=gen) for n in (Bp * O, Bp * act_dim, Bp, Bp, Bp * O)])
+
+    def digest():
+        torch.cuda.synchronize()
+        return hashlib.sha256(eng.workspace.cpu().numpy().tobytes()).hexdigest()
+
+    for phase in accepted:
+        eng.update_phase(phase, 0.2)
+    torch.cuda.synchronize()
+    assert torch.isfinite(eng.flat(L.NET_ACTOR)).all()
+    before = digest()
+    for phase in range(12):
+        if phase in accepted:
+            continue
+        with pytest.raises(L.ExorlError) as err:
+            eng.update_phase(phase, 0.2)
+        assert str(err.value).strip(), phase
+        assert digest() == before, phase

@@ -54,15 +54,26 @@ def _ulp(x):
     return np.spacing(np.abs(np.asarray(x, np.float64)).astype(np.float32)).astype(np.float64)
 
 
-@pytest.mark.parametrize('rows', [1, 7, 256, 257, 1000, 8200])
+def _chunk_ordered_sums(part, parts):
+    """The sums kernel's order on the host: one float32 accumulator per quantity over the per-chunk partials, first chunk first (up to 1024
+    chunks chunk_sum adds them one by one)."""
+    part = part.reshape(-1, parts)
+    assert len(part) <= 1024
+    acc = np.zeros(parts, np.float32)
+    for row in part:
+        acc = (acc + row).astype(np.float32)
+    return acc
+
+
+@pytest.mark.parametrize('rows', [1, 7, 255, 256, 257, 1000, 8193, 8200])
 def test_row_kernel_vs_float64(rows):
     """exorl_fqe_rows on random rows in (-0.5, 0.5) and two crafted ones: row 2 has D = 0 (y = r for both nets) and row 3 has Q_1 within 1e-6
     of y_1. dq against the float64 value of 2 (Q_i - y_i) inv_bg, in ulp of fp32 at that value. Count of roundings: 2. The kernel forms
     Q_i - (r + D Q'_i) in double (the products of two fp32 are exact there) and rounds it once to fp32, at most 0.5 ulp of the difference,
     which is a relative 2^-24 and so at most 1 ulp of the product it is carried into; 2 e is exact; the product with inv_bg rounds once more,
     0.5 ulp. 1.5 ulp in all: the bar is 2 ulp, half of the 4 ulp tests/test_gpu_iql.py holds iql_rows' dq to. Row 3 is held to its own
-    (tiny) ulp like every other row: its cancellation happens in double. The six sums: bitwise equal on a second run, and within 1e-5 of
-    sum |term| of the float64 sums."""
+    (tiny) ulp like every other row: its cancellation happens in double. The six sums: bitwise equal on a second run, equal to the float32
+    sum of the per-chunk partials in chunk order (8193 rows: 33 chunks on 32 workgroups), and within 1e-5 of sum |term| of the float64 sums."""
     from exorl_amd import _lib as L
     lib = L.load()
     rs = np.random.RandomState(rows)
@@ -82,8 +93,9 @@ def test_row_kernel_vs_float64(rows):
         part, sums = torch.full((chunks * 6,), float('nan'), device='cuda'), torch.full((6,), float('nan'), device='cuda')
         L.check(lib.exorl_fqe_rows(*[x.data_ptr() for x in d], rows, inv_bg, dq.data_ptr(), part.data_ptr(), sums.data_ptr(), None))
         torch.cuda.synchronize()
-        outs.append([x.cpu().numpy() for x in (dq, sums)])
-    dq, sums = outs[0]
+        outs.append([x.cpu().numpy() for x in (dq, sums, part)])
+    dq, sums, part = outs[0]
+    assert sums.tobytes() == _chunk_ordered_sums(part, 6).tobytes(), 'the sums are not the chunk-ordered float32 sums of the partials'
     assert sums.tobytes() == outs[1][1].tobytes(), 'the sums differ between two runs'
     assert dq.tobytes() == outs[1][0].tobytes()
     x = lambda a: a.astype(np.float64)
@@ -525,3 +537,10 @@ def test_fitted_q_evaluation_equals_driving_the_agent_by_hand(tmp_path):
     from exorl_amd.replay_buffer import ArenaIterator
     with pytest.raises(ValueError, match='nstep=1'):
         fitted_q_evaluation(policy, ArenaIterator(_arena(9)[0], B, 3, 0.99, 'philox'), 1)
+
+
+def test_value_window_attach_read_reset_detach():
+    """FQE's value window through its whole life at batch 259, and the buffers exorl_agent_set_fqe_value refuses (tests/_windows.py)."""
+    import _windows as W
+    eng = W.engine('fqe')
+    W.check_window(eng, 'fqe_value', lambda: eng.fqe_value(W.B), W.B, 'no value window')

@@ -48,7 +48,18 @@ def _ulp(x):
     return np.spacing(np.abs(np.asarray(x, np.float64)).astype(np.float32)).astype(np.float64)
 
 
-@pytest.mark.parametrize('rows', [1, CHUNK - 1, CHUNK, CHUNK + 1, CHUNK * MAX_WG + CHUNK + 37])
+def _chunk_ordered_sums(part, parts):
+    """The sums kernel's order on the host: one float32 accumulator per quantity over the per-chunk partials, first chunk first (up to 1024
+    chunks chunk_sum adds them one by one)."""
+    part = part.reshape(-1, parts)
+    assert len(part) <= 1024
+    acc = np.zeros(parts, np.float32)
+    for row in part:
+        acc = (acc + row).astype(np.float32)
+    return acc
+
+
+@pytest.mark.parametrize('rows', [1, CHUNK - 1, CHUNK, CHUNK + 1, CHUNK * MAX_WG + 1, CHUNK * MAX_WG + CHUNK + 37])
 def test_row_kernel_vs_float64(rows):
     """exorl_iql_rows on random rows in (-0.5, 0.5) with temperature 0.5 (|temperature u| <= 0.5) and three crafted ones:
       row 0   v = min(tq) exactly: u = 0, dv = 0 and w = 1 (u = 0 takes the `expectile` branch; with u = 0 both branches give dv = 0)
@@ -57,7 +68,9 @@ def test_row_kernel_vs_float64(rows):
     dv, dq and w each to 4 ulp of fp32 of its own float64 value. Count of roundings: dv 4 (u, k, k u, inv_bg); dq 2 (the kernel forms
     Q - (r + D v') in double and rounds once, since the difference cancels where Q is close to y, then inv_bg); w 1 (temperature u, worth
     |x| 2^-23 relative = at most one ulp at |x| <= 0.5) plus expf's 1 to 2 ulp. Row 3 has Q_1 within 1e-6 of y: dq there is held to its own
-    ulp like every other row. The ten sums: bitwise equal on a second run, and within 1e-5 of sum |term| of the float64 sums."""
+    ulp like every other row. The ten sums: bitwise equal on a second run, equal to the float32 sum of the per-chunk partials in chunk order
+    (8193 rows: 33 chunks on 32 workgroups, so the first workgroup's second chunk is the last partial), and within 1e-5 of sum |term| of the
+    float64 sums."""
     from exorl_amd import _lib as L
     lib = L.load()
     rs = np.random.RandomState(rows)
@@ -83,8 +96,9 @@ def test_row_kernel_vs_float64(rows):
         L.check(lib.exorl_iql_rows(*[x.data_ptr() for x in d], rows, inv_bg, e, t, mw, dv.data_ptr(), dq.data_ptr(), w.data_ptr(),
                                    part.data_ptr(), sums.data_ptr(), None))
         torch.cuda.synchronize()
-        outs.append([x.cpu().numpy() for x in (dv, dq, w, sums)])
-    dv, dq, w, sums = outs[0]
+        outs.append([x.cpu().numpy() for x in (dv, dq, w, sums, part)])
+    dv, dq, w, sums, part = outs[0]
+    assert sums.tobytes() == _chunk_ordered_sums(part, 10).tobytes(), 'the sums are not the chunk-ordered float32 sums of the partials'
     assert sums.tobytes() == outs[1][3].tobytes(), 'the sums differ between two runs'
     for a, b in zip(outs[0][:3], outs[1][:3]):
         assert a.tobytes() == b.tobytes()

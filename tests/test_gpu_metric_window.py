@@ -322,3 +322,10 @@ def test_window_refusals(gold):
     back = pickle.loads(pickle.dumps(win))
     with pytest.raises(RuntimeError, match='enable_metric_window'):
         back.pop_metrics()
+
+
+def test_window_attach_read_reset_detach():
+    """The metric window through its whole life at batch 259, and the buffers exorl_agent_set_metric_window refuses (tests/_windows.py)."""
+    import _windows as W
+    eng = W.engine('td3_bc')
+    W.check_window(eng, 'metric_window', lambda: eng.update(0.2), 1, 'no metric window')

@@ -6,6 +6,7 @@ must leave every line equal). Run it from each tree in a fresh process per listi
     python tools/agent_digests.py part3 OUT.txt                the five two-process gloo workers of tests/, every array and json they save
     python tools/agent_digests.py grid OUT.txt                 one update() of every case of the state agents' kernel dispatch grids, per route
     python tools/agent_digests.py modes OUT.txt                one state-agent handle through every driver of its step in turn (see modes)
+    python tools/agent_digests.py summary PARENT.txt THIS.txt  the per-case table profiles/*_digests.txt keep of two listings (see summary)
     python tools/agent_digests.py pixel_modes OUT.txt          one pixel handle through every driver of its step in turn (see pixel_modes)
     python tools/agent_digests.py replay OUT.txt               the replay loaders, online and offline: batches and index pairs (see replay)
     python tools/agent_digests.py compare A.txt B.txt          "N entries, K differ" and every differing line; exit status 1 if K > 0
@@ -32,6 +33,7 @@ sys.path.insert(0, str(ROOT / 'tests'))
 O, A, H, B = 24, 6, 256, 256                        # states
 PC, PHW, PF, PH, PB = 3, 64, 32, 128, 64            # pixels: the two-process workers' frames and widths
 OFFLINE = ['td3_bc', 'td3', 'bc', 'crr', 'cql', 'cql_lagrange']
+OFFLINE_LATER = ['iql', 'fqe']                      # their cases follow every older one, so that a listing's older part keeps its order
 MODULES = ['rnd', 'icm', 'icm_apt', 'disagreement', 'diayn', 'aps', 'smm', 'proto']
 META = {'states': {'diayn': 16, 'aps': 10, 'smm': 4}, 'pixels': {'diayn': 8, 'aps': 5, 'smm': 4}}
 PRECISIONS = {'states': ('fp32', 'bf16', 'bf16x3', 'bf16x6'), 'pixels': ('fp32', 'bf16x6')}
@@ -51,8 +53,12 @@ def build(kind, obs_type, reward_free, precision, use_tb=True):
     import torch
     from exorl_amd import agents
     torch.manual_seed(7)
-    if kind in OFFLINE:
+    if kind in OFFLINE + OFFLINE_LATER:
         a = ('x', (O,), (A,), 'cuda:0', 1e-4, H, 0.01)
+        if kind == 'iql':
+            return agents.IQLAgent(*a, '0.2', 1, B, use_tb, precision=precision)
+        if kind == 'fqe':           # the policy it scores: a TD3+BC agent from the same seed
+            return agents.FQEAgent(*a, 1, B, use_tb, precision=precision).set_policy(build('td3_bc', obs_type, reward_free, precision, use_tb))
         if kind == 'td3_bc':
             return agents.TD3BCAgent(*a, '0.2', 1, B, 0.3, use_tb, 2.5, precision=precision)
         if kind == 'td3':
@@ -102,7 +108,7 @@ def arena(kind, obs_type, seed=5):
     eng = ReplayEngine(shape, np.uint8 if pix else np.float32, A, M, 3 * (rows + 1) + 64, 16, 'cuda:0')
     eng.set_order([eng.append_episode(ep, ('skill',) if M else ()) for ep in eps])
     eng.seed_philox(seed)
-    return ArenaIterator(eng, batch, 1 if kind in OFFLINE else 3, 0.99, 'philox')
+    return ArenaIterator(eng, batch, 1 if kind in OFFLINE + OFFLINE_LATER else 3, 0.99, 'philox')
 
 
 def batches(kind, obs_type, first, n):
@@ -154,7 +160,7 @@ def digest(ag, emit):
         for name in ('encoder', 'actor', 'critic'):
             emit(f'engine.{name}.grads', sha(torch.cat([g.reshape(-1) for g in getattr(ag, name).grads()])))
     else:
-        for net in [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else []):
+        for net in [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else []) + ([L.NET_VALUE] if getattr(eng, 'has_value', False) else []):
             for what in ((L.T_PARAM,) if net == L.NET_CRITIC_TARGET else (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V, L.T_GRAD)):
                 emit(f'engine.net{net}.what{what}', sha(eng.flat(net, what)))
             for name, image in eng.weight_images(net).items():      # the derived weight copies one by one: a differing workspace digest gets a name
@@ -189,7 +195,7 @@ def emit_metrics(emit, tag, m):
 def act_inputs(ag, kind, obs_type):
     rs = np.random.RandomState(77)
     obs = rs.randint(0, 256, (PC, PHW, PHW)).astype(np.uint8) if obs_type == 'pixels' else rs.standard_normal(O).astype(np.float32)
-    if kind in OFFLINE:
+    if kind in OFFLINE + OFFLINE_LATER:
         return (obs,)
     M = META[obs_type].get(kind, 0)
     meta = {'m': np.eye(M, dtype=np.float32)[1]} if M else {}
@@ -233,6 +239,11 @@ def cases():
                         yield case(kind, obs_type, reward_free, precision, mode)
     yield case('td3_bc', 'states', False, 'bf16x3', 'graph', use_tb=False)
     yield case('smm', 'states', True, 'fp32', 'hooks', use_tb=False)     # SMM reports its module's metrics whatever use_tb says
+    for kind in OFFLINE_LATER:
+        for mode in ('arena', 'hooks'):
+            for precision in PRECISIONS['states']:
+                yield case(kind, 'states', False, precision, mode)
+        yield case(kind, 'states', False, 'bf16x3', 'graph', use_tb=False)
 
 
 def listing(path, body):
@@ -332,14 +343,22 @@ def grid(out):
 
 
 def modes(out):
-    """TD3+BC and CQL, one handle each per precision and metrics setting, driven in turn by a captured graph step, disable_graph, the four
-    phased calls, an eager update() and a newly captured graph step, with the digests after every driver: what one driver sets up for its
-    own launches (fused optimiser and scalar-head kernels, staged inputs, capture) must not reach the next one's. Uses only calls that
-    trees from before exorl_agent_update_plan have, so the same file runs against either library."""
+    """TD3+BC, CQL, IQL and FQE, one handle each per precision and metrics setting, driven in turn by a captured graph step, disable_graph,
+    the phased calls, an eager update() and a newly captured graph step, with the digests after every driver: what one driver sets up for
+    its own launches (fused optimiser and scalar-head kernels, staged inputs, capture) must not reach the next one's. TD3+BC and CQL run
+    phases 0..3 and use only calls that trees from before exorl_agent_update_plan have; IQL and FQE (no metric window) run the phase ids
+    of their own plan, as AgentEngine.update_steps reads it."""
+    def plan_phases(eng):
+        import ctypes as C
+        from exorl_amd import _lib as L
+        phases, xids, n = (C.c_int32 * 8)(), (C.c_int32 * 8)(), C.c_int32()
+        L.check(eng.lib.exorl_agent_update_plan(C.byref(eng.cfg), phases, xids, 8, C.byref(n)))
+        return list(phases[:n.value])
+
     def body(emitter):
-        for kind in ('td3_bc', 'cql'):
+        for kind in ['td3_bc', 'cql'] + OFFLINE_LATER:
             for precision in ('fp32', 'bf16x3'):
-                for metrics in ('tb', 'no_tb', 'window'):
+                for metrics in ('tb', 'no_tb') + (('window',) if kind not in OFFLINE_LATER else ()):
                     name = f'modes/{kind}/{precision}/{metrics}'
                     emit = emitter(name)
                     ag = build(kind, 'states', False, precision, metrics == 'tb')
@@ -356,7 +375,7 @@ def modes(out):
                     after('graph0')
                     ag.disable_graph()
                     ag._load_batch(it)
-                    for phase in range(4):
+                    for phase in (plan_phases(ag.engine) if kind in OFFLINE_LATER else range(4)):
                         ag.engine.update_phase(phase, stddev)
                     after('phased')
                     emit_metrics(emit, 'eager', ag.update(it, 2))
@@ -522,6 +541,28 @@ def compare(a, b):
     return 1 if diff else 0
 
 
+def summary(a, b):
+    """One line per case of two listings, in listing order: case | entries | lines digest and engine.workspace of each. The lines digest is
+    the md5 of the case's `what value` lines joined by newlines."""
+    def table(path):
+        cases = {}
+        for line in Path(path).read_text().splitlines():
+            case, rest = line.split(' ', 1)
+            cases.setdefault(case, []).append(rest)
+        return cases
+
+    def cell(lines):
+        ws = [l.rsplit(' ', 1)[1] for l in lines if l.split(' ')[0].endswith('engine.workspace')]
+        return f"{hashlib.md5(chr(10).join(lines).encode()).hexdigest()} {ws[-1] if ws else '-'}"
+    ta, tb = table(a), table(b)
+    for path in (a, b):
+        print(f'# {path}: sha256 {hashlib.sha256(Path(path).read_bytes()).hexdigest()}, {Path(path).stat().st_size} bytes')
+    print('Columns: case | entries | parent: lines digest, engine.workspace | this tree: lines digest, engine.workspace')
+    for case in ta:
+        print(f"{case} | {len(ta[case])} | {cell(ta[case])} | {cell(tb.get(case, []))}")
+    return 0
+
+
 if __name__ == '__main__':
     cmd, args = sys.argv[1], sys.argv[2:]
-    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'pixel_modes': pixel_modes, 'replay': replay, 'compare': compare}[cmd](*args))
+    sys.exit({'part1': part1, 'part2': part2, 'part3': part3, 'grid': grid, 'modes': modes, 'pixel_modes': pixel_modes, 'replay': replay, 'compare': compare, 'summary': summary}[cmd](*args))
