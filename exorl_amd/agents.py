@@ -137,12 +137,16 @@ def _world_size():
     return 1
 
 
+EVAL_KINDS = ('td3_bc', 'td3', 'crr', 'cql', 'bc')      # what exorl_agent_evaluate accepts: evaluate() applies to these classes (_EVALUATES)
+
+
 class _AgentBase:
     KIND = None
 
     # -- pickling (pretrain.py:293-300 torch.save's the whole agent; finetune.py:222-252 loads it back) ---------------
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
+        cls._EVALUATES = cls.KIND in EVAL_KINDS
         orig = cls.__dict__.get('__init__')
         if orig is None:
             return
@@ -154,35 +158,55 @@ class _AgentBase:
             orig(self, *a, **k)
         cls.__init__ = init
 
-    def _engines(self):
-        return [('agent', self.engine)] + ([('intr', self.intr)] if hasattr(self, 'intr') else [])
+    # Per-class facts, declared next to KIND / METRICS: _build, _run_update, evaluate() and train() read these and never ask what `self` is.
+    _ACTOR_KEYS, _CRITIC_KEYS = _OFFLINE_ACTOR_KEYS, _OFFLINE_CRITIC_KEYS      # the reference's state_dict names of the two nets
+    _ACTOR_OUT = 1               # actor outputs per action dimension (CQL: mean and log-std)
+    _CRITIC_TRUNKS = 2           # trunks under the critic's two heads: one each offline, one shared in DDPG's Critic, 0 for no critic (BC)
+    _VALUE_NET = False           # IQL's V(s)
+    _DRAWS_NOISE = True          # the step draws the critic target's and the actor's noise (False: noise_hook is never called)
+    # defaults of what only some classes or some runs set on the instance
+    training, world_size = True, 1
+    _pix_meta_dim = _meta_dim = 0       # DDPG on pixels: width of the 6th batch tensor; _MetaObsMixin: meta columns appended to obs
+    _second_noise_rows = None           # CRR: rows of the actor's draw
+    _dp = None                          # _IntrAgent._dp_buffers, allocated on first use
+
+    @property
+    def _pixels(self):          # obs_type is an instance attribute of the DDPG family alone: the offline classes have no such public name
+        return vars(self).get('obs_type') == 'pixels'
+
+    @property
+    def _logs(self):
+        return bool(self.use_tb)
+
+    # One record of the device-backed members (engines, views over their buffers, device tensors), made where each is created. The
+    # constructor rebuilds them, so __getstate__ leaves them out of attrs; train() walks those with the role _TRAINS, snapshot.py those
+    # with the role _NET, in the order they were recorded.
+    _NET, _TRAINS = 'net', 'trains'
+
+    def _own(self, name, member, *roles):
+        vars(self).setdefault('_members', {})[name] = roles
+        setattr(self, name, member)
+        return member
+
+    def _members_with(self, role):
+        return [name for name, roles in self._members.items() if role in roles]
+
+    # What else __getstate__ leaves out of attrs: the test hooks (any name ending in _hook), the buffers kept alive across a launch
+    # (_keep*) and this transient step state.
+    _TRANSIENT = {'_members', '_ctor', '_slots', '_graph_iter', '_graph_stddev', '_metric_window', '_dp'}
+    _STATE_KEYS = ('ctor', 'flat', 'opt_steps', 'pixel', 'training', 'cql_alpha', 'intr', 'attrs')     # the pickled dict's keys, in its order
 
     def __getstate__(self):
-        """Constructor arguments + every device buffer that defines the training state (parameters, Adam moments and step
-        counts, running statistics) as CPU tensors; host attributes that are plain data ride along."""
+        """Constructor arguments + each engine's training state (export_state: parameters, Adam moments and step counts, running
+        statistics, as CPU tensors) + the host attributes that are plain data + the training flag."""
         torch.cuda.synchronize()
-        eng = self.engine
-        if getattr(self, 'obs_type', 'states') == 'pixels':
-            st = {'ctor': self._ctor, 'pixel': eng.export_state(), 'training': getattr(self, 'training', True)}
-        else:
-            st = {'ctor': self._ctor, 'flat': {}, 'opt_steps': eng.opt_steps(), 'training': getattr(self, 'training', True)}
-            nets = [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if eng.has_critic else []) + ([L.NET_VALUE] if eng.has_value else [])
-            for net in nets:
-                whats = [L.T_PARAM] if net == L.NET_CRITIC_TARGET else [L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V]
-                st['flat'][net] = {w: eng.flat(net, w).cpu() for w in whats}
-            if self.KIND == 'cql':
-                st['cql_alpha'] = eng.cql_alpha_state().tolist()
-        if hasattr(self, 'intr'):
-            it = self.intr
-            st['intr'] = {'flat': {w: it.flat(w).cpu() for w in (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V)}, 'rms': it.rms_state(),
-                          'bn': it.bn.cpu() if it.bn is not None else None, 'opt_steps': it.opt_steps(),
-                          'queue': (it.queue.cpu(), it.queue_ptr()) if it.queue is not None else None, 'counter': it.counter()}
-        skip = {'engine', 'intr', 'actor', 'critic', 'critic_target', 'value', 'rnd', 'icm', 'pbe', 'intrinsic_reward_rms', 'disagreement', 'diayn',
-                'predictor', 'predictor_target', 'projector', 'protos', 'queue', 'encoder_target', 'cat_hook', 'aps', 'smm', 'eps_hook', 'aug', 'encoder',
-                'noise_hook', 'shift_hook', '_slots', '_graph_iter', '_graph_stddev', '_ctor', 'rnd_target_encoder', '_dobs', '_dp',
-                '_metric_window'}
-        st['attrs'] = {k: v for k, v in self.__dict__.items() if k not in skip and not k.startswith('_keep')}
-        return st
+        st = {'pixel': self.engine.export_state()} if self._pixels else self.engine.export_state()
+        if 'intr' in self._members:
+            st['intr'] = self.intr.export_state()
+        st.update(ctor=self._ctor, training=self.training,
+                  attrs={k: v for k, v in vars(self).items()
+                         if k not in self._members and k not in self._TRANSIENT and not k.endswith('_hook') and not k.startswith('_keep')})
+        return {k: st[k] for k in self._STATE_KEYS if k in st}
 
     def __setstate__(self, st):
         a, k = st['ctor']
@@ -190,62 +214,52 @@ class _AgentBase:
         self._ctor = (a, dict(k))
         type(self).__init__(self, *a, **k)
         torch.set_rng_state(rng)
-        eng = self.engine
-        if 'pixel' in st:
-            eng.import_state(st['pixel'])
-        else:
-            for net, bufs in st['flat'].items():
-                for w, t in bufs.items():
-                    eng.flat(net, w).copy_(t)
-            eng.set_opt_steps(*st['opt_steps'])
-            if 'cql_alpha' in st:
-                eng.set_cql_alpha_state(*st['cql_alpha'])
-            eng.params_changed(sync_target=False)
+        self.engine.import_state(st['pixel'] if 'pixel' in st else st)
         if 'intr' in st:
-            it, si = self.intr, st['intr']
-            for w, t in si['flat'].items():
-                it.flat(w).copy_(t)
-            it.set_rms_state(*si['rms'])
-            if si['bn'] is not None:
-                it.bn.copy_(si['bn'])
-            it.set_opt_steps(si['opt_steps'])
-            if si.get('queue') is not None:
-                it.queue.copy_(si['queue'][0])
-                it.queue_ptr(si['queue'][1])
-            if 'counter' in si:
-                it.counter(si['counter'])
-        self.__dict__.update(st['attrs'])
+            self.intr.import_state(st['intr'])
+        vars(self).update(st['attrs'])
         self.train(st['training'])
 
-    def _build(self, obs_dim, action_dim, hidden_dim, batch_size, lr, tau, alpha, stddev_clip, device, precision, seed,
-               **engine_kw):
-        ddpg = self.KIND in ('ddpg', 'aps')
+    def _build(self, obs_dim, action_dim, hidden_dim, batch_size, lr, tau, device, precision, seed, alpha=0.0, stddev_clip=0.0, **engine_kw):
         # initial weights first (CPU RNG order: actor, critic, critic_target — td3_bc.py:86-93)
-        actor0 = _mlp_init(obs_dim, hidden_dim, 2 * action_dim if self.KIND == 'cql' else action_dim, 1, 1)
-        critic0 = None
-        if self.KIND != 'bc':
-            nt = 1 if ddpg else 2
-            critic0 = _mlp_init(obs_dim + action_dim, hidden_dim, 1, nt, 2)
-            _mlp_init(obs_dim + action_dim, hidden_dim, 1, nt, 2)       # critic_target's draws, overwritten by the copy
-            if self.KIND == 'aps':      # APSAgent builds DDPG's scalar critics first, then replaces both with CriticSF (aps.py:94-104)
-                critic0 = _mlp_init(obs_dim + action_dim, hidden_dim, engine_kw['sf_dim'], 1, 2)
-                _mlp_init(obs_dim + action_dim, hidden_dim, engine_kw['sf_dim'], 1, 2)
-        value0 = _mlp_init(obs_dim, hidden_dim, 1, 1, 1) if self.KIND == 'iql' else None      # drawn last: actor, critic, critic_target, value
+        actor0 = _mlp_init(obs_dim, hidden_dim, self._ACTOR_OUT * action_dim, 1, 1)
+        critic0 = value0 = None
+        if self._CRITIC_TRUNKS:
+            # scalar heads; with sf_dim, APSAgent builds DDPG's scalar critics first, then replaces both with CriticSF (aps.py:94-104)
+            for out in (1, engine_kw['sf_dim']) if engine_kw.get('sf_dim') else (1,):
+                critic0 = _mlp_init(obs_dim + action_dim, hidden_dim, out, self._CRITIC_TRUNKS, 2)
+                _mlp_init(obs_dim + action_dim, hidden_dim, out, self._CRITIC_TRUNKS, 2)       # critic_target's draws, overwritten by the copy
+        if self._VALUE_NET:
+            value0 = _mlp_init(obs_dim, hidden_dim, 1, 1, 1)      # drawn last: actor, critic, critic_target, value
         self._dp_engine(seed, lambda ws, seed: AgentEngine(self.KIND, obs_dim, action_dim, hidden_dim, batch_size, lr=lr, tau=tau, alpha=alpha,
                                                            stddev_clip=stddev_clip, precision=precision, world_size=ws, seed=seed,
                                                            device=device, **engine_kw))
-        self.actor = _net_view(self.engine, L.NET_ACTOR, _DDPG_ACTOR_KEYS if ddpg else _OFFLINE_ACTOR_KEYS, self.params_changed)
-        _load(self.actor, actor0)
+        nets = [('actor', L.NET_ACTOR, self._ACTOR_KEYS, actor0, True)]
         if critic0 is not None:
-            keys = _DDPG_CRITIC_KEYS if ddpg else _OFFLINE_CRITIC_KEYS
-            self.critic = _net_view(self.engine, L.NET_CRITIC, keys, self.params_changed)
-            self.critic_target = _net_view(self.engine, L.NET_CRITIC_TARGET, keys, self.params_changed)
-            _load(self.critic, critic0)
+            nets += [('critic', L.NET_CRITIC, self._CRITIC_KEYS, critic0, True), ('critic_target', L.NET_CRITIC_TARGET, self._CRITIC_KEYS, None, False)]
         if value0 is not None:
-            self.value = _net_view(self.engine, L.NET_VALUE, _VALUE_KEYS, self.params_changed)
-            _load(self.value, value0)
+            nets += [('value', L.NET_VALUE, _VALUE_KEYS, value0, True)]
+        for name, net, keys, init, trains in nets:
+            view = self._own(name, _net_view(self.engine, net, keys, self.params_changed), self._NET, *([self._TRAINS] if trains else []))
+            if init is not None:
+                _load(view, init)
         self.engine.params_changed(sync_target=True)                   # critic_target.load_state_dict(critic.state_dict())
-        self.engine.set_metrics(bool(getattr(self, 'use_tb', False) or getattr(self, 'use_wandb', False)))
+        self.engine.set_metrics(self._logs)
+
+    def _offline(self, obs_shape, action_shape, device, lr, hidden_dim, batch_size, use_tb, precision, seed, tau, engine=(), **hyper):
+        """The head the offline constructors share: the common host attributes, then the class's own hyper-parameters `hyper` as
+        attributes (plain data that rides in __getstate__'s attrs), then the engine and its views; `engine` names the hyper-parameters
+        that AgentEngine takes too."""
+        self.action_dim, self.hidden_dim, self.lr, self.device = action_shape[0], hidden_dim, lr, device
+        self.critic_target_tau, self.use_tb = tau, use_tb
+        vars(self).update(hyper)
+        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, tau, device, precision, seed, **{k: hyper[k] for k in engine})
+
+    def _train_all(self):
+        """The last step of every constructor (td3_bc.py:95-96)."""
+        self.train()
+        if self._CRITIC_TRUNKS:
+            self.critic_target.train()
 
     def _dp_engine(self, seed, make):
         """self.engine = make(world_size, seed) for this process, on states and on pixels: under torch.distributed the rank is folded into
@@ -255,7 +269,7 @@ class _AgentBase:
             # every rank draws its own rows of the global batch's shifts and noise: without this all ranks share one Philox stream and the
             # global batch repeats each noise block world_size times (the reference's single process draws B x A iid normals)
             seed = (seed + 0x9E3779B1 * torch.distributed.get_rank()) & 0x7FFFFFFFFFFFFFFF
-        self.engine = make(ws, seed)
+        self._own('engine', make(ws, seed))
         if ws > 1:
             comm = native_comm(self.engine.device)          # RCCL inside the library when torch.distributed runs on nccl
             if comm is not None:
@@ -275,11 +289,8 @@ class _AgentBase:
     # -- nn.Module-ish surface used by utils.eval_mode and the training scripts
     def train(self, training=True):
         self.training = training
-        self.actor.train(training)
-        if hasattr(self, 'critic'):
-            self.critic.train(training)
-        if isinstance(getattr(self, 'value', None), NetView):      # IQL's V(s) net (FQEAgent.value is a method)
-            self.value.train(training)
+        for name in self._members_with(self._TRAINS):
+            vars(self)[name].train(training)
 
     def _stddev(self, step):
         return utils.schedule(self.stddev_schedule, step)
@@ -317,7 +328,7 @@ class _AgentBase:
         says) and pop_metrics() returns their means over the steps since the last pop. TD3+BC, TD3 and DDPG keep the fused fast path.
         Returns False, and changes nothing, for pixel agents, the module agents and under data parallelism. Call it before enable_graph
         (the capture holds the window's kernels); with a graph captured it raises. Not pickled: an unpickled agent has no window."""
-        if not self.METRIC_WINDOW or getattr(self, 'obs_type', 'states') == 'pixels' or self.world_size != 1:
+        if not self.METRIC_WINDOW or self._pixels or self.world_size != 1:
             return False
         if self._graph_iter is not None:
             raise RuntimeError('enable_metric_window() must be called before enable_graph(): the captured step has no window kernels')
@@ -354,11 +365,11 @@ class _AgentBase:
         BC returns val_bc_mse and val_rows only. Under an initialised torch.distributed every rank evaluates its own batches and the
         sums and row counts are added over the ranks before dividing (all_gather_object of a handful of doubles; `gather`, a callable own
         (sums, rows) -> [(sums, rows) of rank 0, of rank 1, ...], replaces that exchange). Not between the phases of a step."""
-        if self.KIND not in EVAL_KINDS or getattr(self, 'obs_type', 'states') == 'pixels' or hasattr(self, 'intr'):
+        if not self._EVALUATES or self._pixels:
             raise NotImplementedError(f'{type(self).__name__}.evaluate(): the forward-only validation pass covers TD3BCAgent, TD3Agent, '
                                       'CRRAgent, CQLAgent and BCAgent on state observations')
         eng = self.engine
-        if getattr(eng, '_eval', None) is None:      # the window is the engine's own torch buffer: nothing of it is pickled
+        if eng._eval is None:      # the window is the engine's own torch buffer: nothing of it is pickled
             eng.set_eval()
         for _ in range(int(num_batches)):
             self._load_batch(replay_iter)
@@ -370,7 +381,7 @@ class _AgentBase:
                 torch.distributed.all_gather_object(out, part)
                 return out
         sums, rows = merge_eval_sums([own] if gather is None else gather(own))
-        return eval_values(sums, rows, self.action_dim, self.KIND != 'bc')
+        return eval_values(sums, rows, self.action_dim, self._CRITIC_TRUNKS > 0)
 
     def disable_graph(self):
         if self._graph_iter is not None:
@@ -397,7 +408,7 @@ class _AgentBase:
         else:
             batch = next(replay_iter)                                                   # any iterator of 5-tuples
             eng.set_batch(*batch[:5])
-            M = getattr(self, '_pix_meta_dim', 0)
+            M = self._pix_meta_dim
             if M:                                                                       # pixels: the skill / task rows, a 6th tensor
                 eng.meta_rows().copy_(torch.as_tensor(batch[5]).to(eng.device, torch.float32).reshape(eng.batch, M))
 
@@ -408,11 +419,9 @@ class _AgentBase:
 
     def _run_update(self, stddev):
         """One gradient step on the loaded batch."""
-        if self.KIND in ('bc', 'iql', 'fqe'):          # no draw in the step
-            nc = na = None
-        else:
-            # reference draw order: critic target, then actor (SURVEY A9); CRR's second draw is (B*n, A) (crr.py:125)
-            nc, na = self._noise(), self._noise(getattr(self, '_second_noise_rows', None))
+        nc = na = None
+        if self._DRAWS_NOISE:        # reference draw order: critic target, then actor (SURVEY A9); CRR's second draw is (B*n, A) (crr.py:125)
+            nc, na = self._noise(), self._noise(self._second_noise_rows)
         self.engine.run_update(stddev, nc, na)
 
     def _metrics(self, keys, stddev):
@@ -431,7 +440,7 @@ class _AgentBase:
         metrics = dict()
         if self._metric_window:         # collected on the device: pop_metrics()
             return metrics
-        if self.use_tb or getattr(self, 'use_wandb', False):
+        if self._logs:
             metrics.update(self._metrics(self.METRICS, stddev))
             self._module_metrics(metrics)
         return metrics
@@ -447,13 +456,16 @@ class _AgentBase:
         (replay_iter.obs_normalizer), whose HBM gather applies the same formula to every sampled batch. States only; for the reward-free
         agents the observation part, before meta is appended. update() on a plain iterator of 5-tuples (the H2D fallback) is NOT
         normalised: normalisation lives in the HBM sampler, such batches are trained on as they come."""
-        if getattr(self, 'obs_type', 'states') == 'pixels':
+        if self._pixels:
             raise ValueError('set_obs_normalizer: pixel agents are not normalised (the encoder does its own /255 - 0.5)')
         m, w = (np.array(a, np.float32).reshape(-1) for a in (mean32, inv32))
-        O = self.obs_shape[0] if hasattr(self, 'obs_shape') else self.engine.obs_dim      # without the reward-free agents' meta columns
+        O = self._norm_columns()
         if m.size != O or w.size != O:
             raise ValueError(f'set_obs_normalizer: {m.size} means and {w.size} scales for {O} observation columns')
         self.obs_norm_mean, self.obs_norm_inv = m, w
+
+    def _norm_columns(self):
+        return self.engine.obs_dim
 
     def clear_obs_normalizer(self):
         self.obs_norm_mean = self.obs_norm_inv = None
@@ -487,9 +499,6 @@ class _AgentBase:
         return a.cpu().numpy()[0]
 
 
-EVAL_KINDS = ('td3_bc', 'td3', 'crr', 'cql', 'bc')      # what exorl_agent_evaluate accepts
-
-
 def merge_eval_sums(parts):
     """[(sums, rows) per rank] -> (sums, rows) of all of them: float64 adds in rank order, so every rank forms the same bits."""
     total, rows = np.zeros(L.N_EVAL, np.float64), 0
@@ -521,19 +530,9 @@ class TD3BCAgent(_AgentBase):
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, stddev_schedule, nstep,
                  batch_size, stddev_clip, use_tb, alpha, has_next_action=False, *, precision='fp32', seed=0):
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.lr = lr
-        self.device = device
-        self.critic_target_tau = critic_target_tau
-        self.use_tb = use_tb
-        self.stddev_schedule = stddev_schedule
-        self.stddev_clip = stddev_clip
-        self.alpha = alpha
-        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, alpha, stddev_clip, device,
-                    precision, seed)
-        self.train()
-        self.critic_target.train()
+        self._offline(obs_shape, action_shape, device, lr, hidden_dim, batch_size, use_tb, precision, seed, critic_target_tau,
+                      ('alpha', 'stddev_clip'), stddev_schedule=stddev_schedule, stddev_clip=stddev_clip, alpha=alpha)
+        self._train_all()
 
 
 class TD3Agent(TD3BCAgent):
@@ -553,21 +552,11 @@ class CRRAgent(_AgentBase):
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, num_value_samples, weight_func,
                  stddev_schedule, nstep, batch_size, stddev_clip, use_tb, has_next_action=False, *, precision='fp32', seed=0):
         assert weight_func in ['identity', 'indicator', 'exp']
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.lr = lr
-        self.device = device
-        self.critic_target_tau = critic_target_tau
-        self.use_tb = use_tb
-        self.stddev_schedule = stddev_schedule
-        self.stddev_clip = stddev_clip
-        self.num_value_samples = num_value_samples
-        self.weight_func = weight_func
-        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, stddev_clip, device, precision,
-                    seed, num_value_samples=num_value_samples, weight_func=weight_func)
+        self._offline(obs_shape, action_shape, device, lr, hidden_dim, batch_size, use_tb, precision, seed, critic_target_tau,
+                      ('stddev_clip', 'num_value_samples', 'weight_func'),
+                      stddev_schedule=stddev_schedule, stddev_clip=stddev_clip, num_value_samples=num_value_samples, weight_func=weight_func)
         self._second_noise_rows = batch_size * num_value_samples
-        self.train()
-        self.critic_target.train()
+        self._train_all()
 
 
 class IQLAgent(_AgentBase):
@@ -579,23 +568,29 @@ class IQLAgent(_AgentBase):
     then Adam on value, critic and actor (all at lr) and the soft update of critic_target. Nothing is sampled: the noise counter does not
     move and noise_hook is never called. No evaluate() and no metric window for this class."""
     KIND = 'iql'
+    _VALUE_NET = True
+    _DRAWS_NOISE = False
     METRIC_WINDOW = False
     METRICS = _CRITIC_METRICS + [(L.M_VALUE_LOSS, 'value_loss'), (L.M_VALUE, 'value'), (L.M_ADV, 'adv'), (L.M_ACTOR_WEIGHT, 'actor_weight')]
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, stddev_schedule, nstep, batch_size, use_tb,
                  expectile=0.7, temperature=3.0, max_weight=100.0, has_next_action=False, *, precision='fp32', seed=0):
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.lr = lr
-        self.device = device
-        self.critic_target_tau = critic_target_tau
-        self.use_tb = use_tb
-        self.stddev_schedule = stddev_schedule
-        self.expectile, self.temperature, self.max_weight = expectile, temperature, max_weight
-        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, 0.0, device, precision, seed)
+        self._offline(obs_shape, action_shape, device, lr, hidden_dim, batch_size, use_tb, precision, seed, critic_target_tau,
+                      stddev_schedule=stddev_schedule, expectile=expectile, temperature=temperature, max_weight=max_weight)
         self.engine.set_iql(expectile, temperature, max_weight)
-        self.train()
-        self.critic_target.train()
+        self._train_all()
+
+
+class _UnitStd:
+    """For the classes whose step takes no exploration std from a schedule (FQE draws nothing; CQL's std is the policy's own output): the
+    step's std argument is 1.0 and update() reports the class's table alone, without the base's entropy of N(mu, std)."""
+
+    def _stddev(self, step):
+        return 1.0
+
+    def _metrics(self, keys, stddev):
+        raw = global_means(self.engine)
+        return {name: float(raw[idx]) for idx, name in keys}
 
 
 def merge_fqe_sums(parts):
@@ -622,7 +617,7 @@ def fqe_values(sums, rows, return_sum, return_count):
             'behavior_value': float(return_sum / max(int(return_count), 1)), 'episodes': int(rows)}
 
 
-class FQEAgent(_AgentBase):
+class FQEAgent(_UnitStd, _AgentBase):
     """Fitted Q evaluation: scores a FROZEN policy from the dataset alone. The actor is the policy (set_policy / for_policy) and is never
     stepped: no gradient, no Adam pass, its weight images are not rewritten. A fresh twin critic with its Polyak target, in TD3's offline
     layout, is regressed on the policy's own Bellman target. One update() on (s, a, r, D, s'), D the sampler's discount, every forward on the
@@ -634,6 +629,7 @@ class FQEAgent(_AgentBase):
     nstep = 1 (the offline loaders do): an n-step target follows the BEHAVIOUR policy's actions for n - 1 steps and biases the estimate
     towards the behaviour value. No evaluate() and no metric window for this class."""
     KIND = 'fqe'
+    _DRAWS_NOISE = False
     METRIC_WINDOW = False
     METRICS = _CRITIC_METRICS[:5]
     POLICY_CLASSES = ('TD3BCAgent', 'TD3Agent', 'BCAgent', 'CRRAgent', 'IQLAgent')
@@ -641,23 +637,8 @@ class FQEAgent(_AgentBase):
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, nstep, batch_size, use_tb, *,
                  precision='fp32', seed=0):
         self.obs_shape = tuple(obs_shape)
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.lr = lr
-        self.device = device
-        self.critic_target_tau = critic_target_tau
-        self.use_tb = use_tb
-        self.nstep = nstep
-        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, 0.0, device, precision, seed)
-        self.train()
-        self.critic_target.train()
-
-    def _stddev(self, step):
-        return 1.0          # nothing is drawn; the step's std argument only has to be positive
-
-    def _metrics(self, keys, stddev):
-        raw = global_means(self.engine)
-        return {name: float(raw[idx]) for idx, name in keys}          # no actor_ent: the policy is deterministic here
+        self._offline(obs_shape, action_shape, device, lr, hidden_dim, batch_size, use_tb, precision, seed, critic_target_tau, nstep=nstep)
+        self._train_all()
 
     @staticmethod
     def _check_policy(agent, dims=None):
@@ -716,7 +697,7 @@ class FQEAgent(_AgentBase):
             raise ValueError('FQEAgent.value(): needs an HBM iterator (ArenaIterator, iter(loader) or its .holdout): it enumerates the '
                              'episodes resident in the arena')
         eng = self.engine
-        if getattr(eng, '_fqe_value', None) is None:      # the window is the engine's own torch buffer: nothing of it is pickled
+        if eng._fqe_value is None:      # the window is the engine's own torch buffer: nothing of it is pickled
             eng.set_fqe_value()
         for _, rows in replay_iter.episode_starts(eng.batch, self._batch_slots()):
             eng.fqe_value(rows)
@@ -731,31 +712,22 @@ class FQEAgent(_AgentBase):
         return fqe_values(*merge_fqe_sums([own] if gather is None else gather(own)))
 
 
-class CQLAgent(_AgentBase):
+class CQLAgent(_UnitStd, _AgentBase):
     """agents/offline_learning/cql.py:59-286 (both the shipped cql.yaml and use_critic_lagrange=True; under torch.distributed the latter splits
     phase 0 around a sum-all-reduce of the penalty, _run_update)."""
     KIND = 'cql'
+    _ACTOR_OUT = 2               # a tanh-Gaussian head: mean and log-std per action
     METRICS = _CRITIC_METRICS + [(L.M_CRITIC_CQL, 'critic_cql'), (L.M_CRITIC_CQL_LOGSUM, 'critic_cql_logsum'), (L.M_ACTOR_ENT, 'actor_ent'),
                                  (L.M_ACTOR_ALPHA, 'actor_alpha'), (L.M_ACTOR_ALPHA_LOSS, 'actor_alpha_loss')]
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, critic_target_tau, nstep, batch_size, use_tb, alpha,
                  n_samples, target_cql_penalty, use_critic_lagrange, has_next_action=False, *, precision='fp32', seed=0):
-        self.action_dim = action_shape[0]
-        self.hidden_dim = hidden_dim
-        self.lr = lr
-        self.device = device
-        self.critic_target_tau = critic_target_tau
-        self.use_tb = use_tb
-        self.use_critic_lagrange = use_critic_lagrange
-        self.target_cql_penalty = target_cql_penalty
-        self.alpha = alpha
-        self.n_samples = n_samples
-        self.target_entropy = -self.action_dim
-        self.stddev_schedule = '1.0'          # unused by CQL (state-dependent std); keeps the shared plumbing uniform
-        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, alpha, 0.0, device, precision, seed,
-                    n_samples=n_samples, use_critic_lagrange=use_critic_lagrange, target_cql_penalty=target_cql_penalty)
-        self.train()
-        self.critic_target.train()
+        # stddev_schedule: unused by CQL (state-dependent std); keeps the shared plumbing uniform
+        self._offline(obs_shape, action_shape, device, lr, hidden_dim, batch_size, use_tb, precision, seed, critic_target_tau,
+                      ('alpha', 'n_samples', 'use_critic_lagrange', 'target_cql_penalty'),
+                      use_critic_lagrange=use_critic_lagrange, target_cql_penalty=target_cql_penalty, alpha=alpha, n_samples=n_samples,
+                      target_entropy=-action_shape[0], stddev_schedule='1.0')
+        self._train_all()
 
     @property
     def log_actor_alpha(self):
@@ -778,20 +750,13 @@ class CQLAgent(_AgentBase):
             z_cur, z_nxt = self.noise_hook((n, B, A)), self.noise_hook((n, B, A))
             nc = np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in (z_next, u_rand, z_cur, z_nxt)])
             na = np.asarray(self.noise_hook((B, A)), np.float32)
-        self.engine.run_update(1.0, nc, na)
-
-    def update(self, replay_iter, step):
-        metrics = dict()
-        self._step(replay_iter, 1.0)
-        if self.use_tb and not self._metric_window:
-            raw = global_means(self.engine)
-            for idx, name in self.METRICS:
-                metrics[name] = float(raw[idx])
-        return metrics
+        self.engine.run_update(stddev, nc, na)
 
 
 class BCAgent(_AgentBase):
     KIND = 'bc'
+    _CRITIC_TRUNKS = 0
+    _DRAWS_NOISE = False
     METRICS = [(L.M_BATCH_REWARD, 'batch_reward'), (L.M_ACTOR_LOSS, 'actor_loss')]
 
     def __init__(self, name, obs_shape, action_shape, device, lr, hidden_dim, batch_size, stddev_schedule, use_tb,
@@ -802,24 +767,25 @@ class BCAgent(_AgentBase):
         self.device = device
         self.stddev_schedule = stddev_schedule
         self.use_tb = use_tb
-        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, 0.0, 0.0, 0.0, device, precision, seed)
-        self.train()
+        self._build(obs_shape[0], action_shape[0], hidden_dim, batch_size, lr, 0.0, device, precision, seed)
+        self._train_all()
 
 
 class DDPGAgent(_AgentBase):
     KIND = 'ddpg'
+    _ACTOR_KEYS, _CRITIC_KEYS, _CRITIC_TRUNKS = _DDPG_ACTOR_KEYS, _DDPG_CRITIC_KEYS, 1
     METRICS = _CRITIC_METRICS + [(L.M_ACTOR_LOGPROB, 'actor_logprob')]
 
     def __init__(self, name, reward_free, obs_type, obs_shape, action_shape, device, lr, feature_dim, hidden_dim,
                  critic_target_tau, num_expl_steps, update_every_steps, stddev_schedule, nstep, batch_size, stddev_clip,
                  init_critic, use_tb, use_wandb, meta_dim=0, skill_type='uniform', *, precision='fp32', seed=0):
         pixels = obs_type == 'pixels'
-        if pixels and not (type(self) is DDPGAgent or getattr(self, '_PIXELS_OK', False)):
+        if pixels and not self._PIXELS_OK:
             raise NotImplementedError(f"exorl_amd: obs_type='pixels' is not built for {type(self).__name__} yet (DDPG, Proto, ICM, ICM-APT, "
                                       "Disagreement, DIAYN, APS, SMM and RND are)")
         if obs_type not in ('pixels', 'states'):
             raise NotImplementedError(f"exorl_amd DDPGAgent: unknown obs_type {obs_type!r}")
-        if (pixels and reward_free and isinstance(self, ProtoAgent) and not getattr(self, 'shard_pretraining', False) and
+        if (pixels and reward_free and isinstance(self, ProtoAgent) and not self.shard_pretraining and
                 _world_size() > 1):
             raise NotImplementedError(f"exorl_amd: {type(self).__name__}(obs_type='pixels', reward_free=True) is single-GPU by default: Proto is the "
                                       "one pixel agent whose sharded pretraining step is opt-in (its candidate queue draws rows from the global "
@@ -850,12 +816,20 @@ class DDPGAgent(_AgentBase):
         else:
             self.obs_shape = obs_shape
             self.obs_dim = obs_shape[0] + meta_dim
-            self.aug = self.encoder = _Identity()
+            self._own('encoder', self._own('aug', _Identity()), self._TRAINS)
             self.encoder_opt = None
-            self._build(self.obs_dim, action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, 0.0, stddev_clip, device,
-                        precision, seed, **self._engine_kw())
-        self.train()
-        self.critic_target.train()
+            self._build(self.obs_dim, action_shape[0], hidden_dim, batch_size, lr, critic_target_tau, device, precision, seed,
+                        stddev_clip=stddev_clip, **self._engine_kw())
+        self._train_all()
+
+    _PIXELS_OK = True           # obs_type='pixels' is built for this class (False on _IntrAgent: every module class states it)
+
+    @property
+    def _logs(self):
+        return bool(self.use_tb or self.use_wandb)
+
+    def _norm_columns(self):
+        return self.obs_shape[0]                # without the reward-free agents' meta columns
 
     def _engine_kw(self):
         return {}
@@ -870,14 +844,14 @@ class DDPGAgent(_AgentBase):
                                                            precision=self._precision, seed=seed, device=self.device, meta_dim=meta_dim,
                                                            sf_dim=sf_dim, world_size=ws))
         self.obs_dim = w['repr_dim'] + meta_dim          # ddpg.py:176 obs_dim = encoder.repr_dim + meta_dim
-        self.encoder = _net_view(self.engine, 0, _ENC_KEYS, shapes=_conv_shapes(c))
-        self.actor = _net_view(self.engine, 1, _PIX_ACTOR_KEYS)
-        self.critic = _net_view(self.engine, 2, _PIX_CRITIC_KEYS)
-        self.critic_target = _net_view(self.engine, 3, _PIX_CRITIC_KEYS)
+        self._own('encoder', _net_view(self.engine, 0, _ENC_KEYS, shapes=_conv_shapes(c)), self._NET, self._TRAINS)
+        self._own('actor', _net_view(self.engine, 1, _PIX_ACTOR_KEYS), self._NET, self._TRAINS)
+        self._own('critic', _net_view(self.engine, 2, _PIX_CRITIC_KEYS), self._NET, self._TRAINS)
+        self._own('critic_target', _net_view(self.engine, 3, _PIX_CRITIC_KEYS), self._NET)
         for view, ts in ((self.encoder, w['encoder']), (self.actor, w['actor']), (self.critic, w['critic'])):
             _load(view, ts)
         self.engine.sync_target()
-        self.aug = _Identity()
+        self._own('aug', _Identity())
         self.encoder_opt = True            # the reference's `if self.encoder_opt is not None` checks hold for pixels
         self.shift_hook = None             # tests: callable(batch) -> (batch, 2) RandomShiftsAug draws
 
@@ -901,15 +875,6 @@ class DDPGAgent(_AgentBase):
         self.engine.run_update(stddev, noise_critic=self._noise(), noise_actor=self._noise(), **images)
         self._pix_after_step()
         return self._update_metrics(stddev)
-
-    def train(self, training=True):
-        if getattr(self, 'obs_type', 'states') == 'pixels':
-            self.training = training
-            for n in (self.encoder, self.actor, self.critic):
-                n.train(training)
-            return
-        super().train(training)
-        self.encoder.train(training)
 
     def init_from(self, other):
         if self.obs_type == 'pixels':
@@ -1014,23 +979,23 @@ class _IntrAgent(DDPGAgent):
     METRIC_WINDOW = False       # the modules' metrics live in their own engines
     MODULE_METRICS = ()         # per class: (slot, name) pairs of the module's metrics reported while reward_free (_module_table)
     STATE_METRICS = ()          # ... and those reported on state observations only
+    _HOOKS = ('noise_hook', 'cat_hook', 'eps_hook')      # the test hooks of the state step, each on the classes that draw it
+    _PIXELS_OK = False
 
     def __init__(self, shard_pretraining=False, **kwargs):
         self.shard_pretraining = bool(shard_pretraining)        # before the base constructor: Proto's pixel refusal reads it
         super().__init__(**kwargs)
 
-    def _module(self, kind, obs_dim, hidden_dim, keys, tensors, dp=None, **kw):
+    def _module(self, kind, obs_dim, hidden_dim, keys, tensors, dp=None, name=None, **kw):
         """The tail of every subclass constructor: builds the module engine self.intr from the shared arguments plus the kind's own
-        keywords, loads the initial `tensors` and allocates the pixel path's gradient buffer. Returns the view of the module's tensors
-        under the reference's state_dict `keys` (None: the subclass wraps them itself)."""
-        self.intr = IntrEngine(kind, obs_dim, self.action_dim, hidden_dim, **(self._intr_dp() if dp is None else dp), lr=self.lr,
-                               precision=self._precision, device=self.device, **kw)
-        view = _net_view(self.intr, None, keys) if keys is not None else None
-        if view is not None:
-            _load(view, tensors)
+        keywords and allocates the pixel path's gradient buffer. With `keys`, the module's tensors under the reference's state_dict names
+        become the view self.<name> (default: the kind) and take the initial `tensors`; None: the subclass wraps them itself."""
+        self._own('intr', IntrEngine(kind, obs_dim, self.action_dim, hidden_dim, **(self._intr_dp() if dp is None else dp), lr=self.lr,
+                                     precision=self._precision, device=self.device, **kw))
+        if keys is not None:
+            _load(self._own(name or kind, _net_view(self.intr, None, keys), self._NET), tensors)
         if self.obs_type == 'pixels':       # d(module loss)/d(encoding), see _pix_module
-            self._dobs = torch.zeros(self.engine.batch, self.obs_dim - self._pix_meta_dim, dtype=torch.float32, device=self.engine.device)
-        return view
+            self._own('_dobs', torch.zeros(self.engine.batch, self.obs_dim - self._pix_meta_dim, dtype=torch.float32, device=self.engine.device))
 
     def _intr_args(self):
         """The module's view of the batch slots on states: IntrEngine.update's five pointers and its stride keywords."""
@@ -1046,7 +1011,7 @@ class _IntrAgent(DDPGAgent):
         self.intr.run_update(*a, True, **k, **self._intr_hooks())
 
     def _hooked(self):
-        return any(getattr(self, h, None) is not None for h in ('noise_hook', 'cat_hook', 'eps_hook'))
+        return any(vars(self).get(h) is not None for h in self._HOOKS)
 
     def enable_graph(self, replay_iter, step=0):
         """One hipGraph per update on state observations in one process: sample -> module step and intrinsic reward -> DDPG step
@@ -1062,7 +1027,7 @@ class _IntrAgent(DDPGAgent):
         if self.reward_free:
             a, k = self._intr_args()
             intr, batch = self.intr, self.intr._batch(*a, **k)
-        self.engine.enable_graph_intr(eng, replay_iter.nstep, replay_iter.discount, self._graph_stddev, intr, batch, getattr(self, '_meta_dim', 0))
+        self.engine.enable_graph_intr(eng, replay_iter.nstep, replay_iter.discount, self._graph_stddev, intr, batch, self._meta_dim)
         self._graph_iter = replay_iter
         return True
 
@@ -1083,23 +1048,22 @@ class _IntrAgent(DDPGAgent):
 
     @property
     def _module_batch(self):
-        return self.engine.batch * getattr(self, 'world_size', 1)
+        return self.engine.batch * self.world_size
 
     def _intr_dp(self):
         """IntrEngine's batch arguments. Under torch.distributed the module is sharded on pixels, and on states where shard_pretraining asks
         for it: this rank's rows, with world_size and rank (exorl_intr_update_phase and its exchanges). Otherwise it stays replicated on
         the gathered global batch (_intr_step_dp)."""
-        if self.world_size > 1 and (getattr(self, 'obs_type', 'states') == 'pixels' or self._sharded_states):
+        if self.world_size > 1 and (self.obs_type == 'pixels' or self._sharded_states):
             return dict(batch=self.engine.batch, world_size=self.world_size, rank=torch.distributed.get_rank())
         return dict(batch=self._module_batch)
 
     @property
     def _sharded_states(self):
-        return (getattr(self, 'obs_type', 'states') == 'states' and self.shard_pretraining and self.reward_free and
-                getattr(self, 'world_size', 1) > 1)
+        return self.obs_type == 'states' and self.shard_pretraining and self.reward_free and self.world_size > 1
 
     def _dp_buffers(self):
-        if getattr(self, '_dp', None) is None:
+        if self._dp is None:
             eng, ws = self.engine, self.world_size
             B, W, A = eng.batch, self.obs_dim, self.action_dim
             dev = eng.device
@@ -1107,7 +1071,7 @@ class _IntrAgent(DDPGAgent):
             gpack = torch.empty(ws * B, 2 * W + A + 1, device=dev)
             g = dict(obs=torch.empty(ws * B, W, device=dev), action=torch.empty(ws * B, A, device=dev),
                      next_obs=torch.empty(ws * B, W, device=dev), reward=torch.empty(ws * B, device=dev))
-            O = W - getattr(self, '_meta_dim', 0)
+            O = W - self._meta_dim
             slots = L.BatchOut(g['obs'].data_ptr(), W, g['action'].data_ptr(), A, g['reward'].data_ptr(), None, g['next_obs'].data_ptr(), W,
                                g['obs'].data_ptr() + 4 * O, W)
             self._dp = (pack, gpack, g, slots)
@@ -1255,13 +1219,13 @@ class RNDAgent(_IntrAgent):
             w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, rnd_rep_dim)] * 2)      # predictor then target (rnd.py:28-43)
         self._module('rnd', O, H, None, None, rep_dim=rnd_rep_dim, scale=rnd_scale, encoded=pixels)
         if pixels:
-            self.rnd_target_encoder = NetView(_ENC_KEYS, self.engine.encoder_target_tensors(conv_shapes))
+            self._own('rnd_target_encoder', NetView(_ENC_KEYS, self.engine.encoder_target_tensors(conv_shapes)))
             _load(self.rnd_target_encoder, convs[1])
-            self.rnd = _RndPixelView(self.intr, self.engine, self.encoder, self.rnd_target_encoder)
+            self._own('rnd', _RndPixelView(self.intr, self.engine, self.encoder, self.rnd_target_encoder), self._NET)
         else:
-            self.rnd = _RndView(self.intr)
+            self._own('rnd', _RndView(self.intr), self._NET)
         _load(self.rnd, w)
-        self.intrinsic_reward_rms = _RmsView(self.intr)
+        self._own('intrinsic_reward_rms', _RmsView(self.intr))
 
     def _pix_before_step(self):
         """rnd.py:110-159 on pixels. RND.forward augments the raw frames itself, normalises them with a BatchNorm2d and runs the agent's
@@ -1298,7 +1262,7 @@ class ICMAgent(_IntrAgent):
         self.update_encoder = update_encoder
         O, A, H = self.obs_dim, self.action_dim, self.hidden_dim
         w = _seq_init([('lin', O + A, H), ('lin', H, O), ('lin', 2 * O, H), ('lin', H, A)])
-        self.icm = self._module('icm', O, H, _ICM_KEYS, w, scale=icm_scale)
+        self._module('icm', O, H, _ICM_KEYS, w, scale=icm_scale)
 
 
 class _PbeView:
@@ -1317,9 +1281,9 @@ class ICMAPTAgent(_IntrAgent):
         self.update_encoder = update_encoder
         O, A, H, R = self.obs_dim, self.action_dim, self.hidden_dim, icm_rep_dim
         w = _seq_init([('lin', O, R), ('ln', R), ('lin', R + A, H), ('lin', H, R), ('lin', 2 * R, H), ('lin', H, A)])
-        self.icm = self._module('icm_apt', O, H, _APT_KEYS, w, rep_dim=R, scale=icm_scale, knn_k=knn_k, knn_avg=knn_avg, knn_rms=knn_rms,
-                                knn_clip=knn_clip)
-        self.pbe = _PbeView(self.intr)
+        self._module('icm_apt', O, H, _APT_KEYS, w, name='icm', rep_dim=R, scale=icm_scale, knn_k=knn_k, knn_avg=knn_avg, knn_rms=knn_rms,
+                     knn_clip=knn_clip)
+        self._own('pbe', _PbeView(self.intr))
 
 
 _DIS_KEYS = [f'ensemble.{m}.{i}.{w}' for m in range(5) for i in (0, 2) for w in ('weight', 'bias')]
@@ -1340,7 +1304,7 @@ class DisagreementAgent(_IntrAgent):
         for _ in range(5):
             for m in (nn.Linear(O + A, H), nn.Linear(H, O)):
                 w += [m.weight.data, m.bias.data]
-        self.disagreement = self._module('disagreement', O, H, _DIS_KEYS, w, n_models=5)
+        self._module('disagreement', O, H, _DIS_KEYS, w, n_models=5)
 
 
 class _Spec:
@@ -1354,8 +1318,6 @@ class _MetaObsMixin:
     """Agents whose batch carries a 6th tensor (DIAYN's skill, APS's task) that is appended to obs / next_obs for the actor and
     critic (diayn.py:162-164, aps.py:236-238) while the module sees the raw observation: the agent's batch slots hold
     [obs | meta] rows, the module gets strided views of them."""
-    _meta_dim = 0
-
     def _views(self):
         s = self._batch_slots()
         B, W = self.engine.batch, self.obs_dim
@@ -1398,7 +1360,7 @@ class DIAYNAgent(_MetaObsMixin, _IntrAgent):
         super().__init__(shard_pretraining, **kwargs)
         O, H = self.obs_dim - self.skill_dim, self.hidden_dim
         w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, skill_dim)])
-        self.diayn = self._module('diayn', O, H, _DIAYN_KEYS, w, rep_dim=skill_dim, scale=diayn_scale)
+        self._module('diayn', O, H, _DIAYN_KEYS, w, rep_dim=skill_dim, scale=diayn_scale)
 
     def _pix_module(self, fo, fn, s):          # the discriminator reads the next frame's encoding (diayn.py:141-147)
         self.intr.run_update(fo, None, fn, s.reward, s.reward, True, skill=s.meta, skill_ld=self.skill_dim, dobs_out=self._dobs.data_ptr())
@@ -1447,8 +1409,8 @@ class APSAgent(_MetaObsMixin, _IntrAgent):
         super().__init__(shard_pretraining, **kwargs)
         O, H = self.obs_dim - self.sf_dim, self.hidden_dim
         w = _seq_init([('lin', O, H), ('lin', H, H), ('lin', H, sf_dim)])
-        self.aps = self._module('aps', O, H, _APS_KEYS, w, rep_dim=sf_dim, knn_k=knn_k, knn_avg=knn_avg, knn_rms=knn_rms, knn_clip=knn_clip)
-        self.pbe = _PbeView(self.intr)
+        self._module('aps', O, H, _APS_KEYS, w, rep_dim=sf_dim, knn_k=knn_k, knn_avg=knn_avg, knn_rms=knn_rms, knn_clip=knn_clip)
+        self._own('pbe', _PbeView(self.intr))
 
     def _engine_kw(self):
         return {'sf_dim': self.sf_dim}
@@ -1551,9 +1513,9 @@ class SMMAgent(_MetaObsMixin, _IntrAgent):
         O, H = self.obs_dim - z_dim, self.hidden_dim
         self.goal = (150, 75)
         w = _smm_init(O, z_dim, H)
-        self.smm = self._module('smm', O, H, _SMM_KEYS, w, rep_dim=z_dim, sp_lr=sp_lr, vae_lr=vae_lr, vae_beta=vae_beta,
-                                state_ent_coef=state_ent_coef, latent_ent_coef=latent_ent_coef, latent_cond_ent_coef=latent_cond_ent_coef,
-                                goal=self.goal, encoded=self.obs_type == 'pixels')
+        self._module('smm', O, H, _SMM_KEYS, w, rep_dim=z_dim, sp_lr=sp_lr, vae_lr=vae_lr, vae_beta=vae_beta,
+                     state_ent_coef=state_ent_coef, latent_ent_coef=latent_ent_coef, latent_cond_ent_coef=latent_cond_ent_coef,
+                     goal=self.goal, encoded=self.obs_type == 'pixels')
         self.ft_returns = np.zeros(z_dim, dtype=np.float32)
         self.ft_not_finished = [True for _ in range(z_dim)]
         self.eps_hook = None            # tests: callable(shape) -> the VAE's epsilon (torch.randn in smm.py:62)
@@ -1678,22 +1640,22 @@ class ProtoAgent(_IntrAgent):
         self.topk = topk
         self.num_protos = num_protos
         self.update_encoder = update_encoder
-        self.encoder_target = _Identity()
         if self.obs_type == 'pixels':            # encoder_target = deepcopy(encoder) (proto.py:55): no RNG draws
             self.engine.encoder_target(init=True)
-            self.encoder_target = NetView(_ENC_KEYS, self.engine.encoder_target_tensors(_conv_shapes(self.obs_shape[0])))
         O = self.obs_dim
         w = _proto_init(O, pred_dim, proj_dim, num_protos)
         dp = self._intr_dp() if self.shard_pretraining else dict(batch=self._module_batch)
         self._module('proto', O, proj_dim, None, None, dp=dp, rep_dim=pred_dim, knn_k=topk, num_protos=num_protos, queue_size=queue_size,
                      tau=tau, target_tau=encoder_target_tau)
-        self.predictor = _net_view(self.intr, None, ['weight', 'bias'], indices=[0, 1])
-        self.projector = _net_view(self.intr, None, ['trunk.0.weight', 'trunk.0.bias', 'trunk.2.weight', 'trunk.2.bias'], indices=[2, 3, 4, 5])
-        self.protos = _net_view(self.intr, None, ['weight'], indices=[6])
-        self.predictor_target = _net_view(self.intr, None, ['weight', 'bias'], indices=[7, 8])
-        for view, ts in ((self.predictor, w[0:2]), (self.projector, w[2:6]), (self.protos, w[6:7]), (self.predictor_target, w[0:2])):
-            _load(view, ts)
-        self.queue = self.intr.queue
+        for name, keys, indices, ts in (('predictor', ['weight', 'bias'], [0, 1], w[0:2]), ('predictor_target', ['weight', 'bias'], [7, 8], w[0:2]),
+                                        ('projector', ['trunk.0.weight', 'trunk.0.bias', 'trunk.2.weight', 'trunk.2.bias'], [2, 3, 4, 5], w[2:6]),
+                                        ('protos', ['weight'], [6], w[6:7])):
+            _load(self._own(name, _net_view(self.intr, None, keys, indices=indices), self._NET), ts)
+        if self.obs_type == 'pixels':
+            self._own('encoder_target', NetView(_ENC_KEYS, self.engine.encoder_target_tensors(_conv_shapes(self.obs_shape[0]))), self._NET)
+        else:
+            self._own('encoder_target', _Identity())
+        self._own('queue', self.intr.queue)
         self.cat_hook = None            # tests: callable(num_protos) -> uniforms standing in for Categorical(prob).sample()
 
     queue_ptr = property(lambda self: self.intr.queue_ptr(), lambda self, v: self.intr.queue_ptr(v))
@@ -1804,3 +1766,4 @@ class _Identity:
 
     def __call__(self, x):
         return x
+

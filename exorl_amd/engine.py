@@ -115,6 +115,26 @@ class AgentEngine(_Phased):
         self._create('agent', cfg)
         self.has_critic = kind != 'bc'
         self.has_value = kind == 'iql'
+        self.has_alpha = kind == 'cql'
+        self._eval = self._fqe_value = None       # the evaluation and value windows (set_eval, set_fqe_value): attached on first use
+
+    # -- pickling support, as PixelEngine's: everything that defines the training state, as CPU data
+    def export_state(self):
+        nets = [L.NET_ACTOR] + ([L.NET_CRITIC, L.NET_CRITIC_TARGET] if self.has_critic else []) + ([L.NET_VALUE] if self.has_value else [])
+        whats = lambda net: [L.T_PARAM] if net == L.NET_CRITIC_TARGET else [L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V]
+        st = {'flat': {net: {w: self.flat(net, w).cpu() for w in whats(net)} for net in nets}, 'opt_steps': self.opt_steps()}
+        if self.has_alpha:
+            st['cql_alpha'] = self.cql_alpha_state().tolist()
+        return st
+
+    def import_state(self, st):
+        for net, bufs in st['flat'].items():
+            for w, t in bufs.items():
+                self.flat(net, w).copy_(t)
+        self.set_opt_steps(*st['opt_steps'])
+        if 'cql_alpha' in st:
+            self.set_cql_alpha_state(*st['cql_alpha'])
+        self.params_changed(sync_target=False)
 
     def flat(self, net, what=L.T_PARAM):
         p, n = C.c_void_p(), C.c_int64()
@@ -469,6 +489,25 @@ class IntrEngine(_Phased):
         c = C.c_uint64(0 if set_to is None else int(set_to))
         L.check(self.lib.exorl_intr_counter(self.h, C.byref(c), 0 if set_to is None else 1))
         return int(c.value)
+
+    # -- pickling support, as PixelEngine's
+    def export_state(self):
+        return {'flat': {w: self.flat(w).cpu() for w in (L.T_PARAM, L.T_ADAM_M, L.T_ADAM_V)}, 'rms': self.rms_state(),
+                'bn': self.bn.cpu() if self.bn is not None else None, 'opt_steps': self.opt_steps(),
+                'queue': (self.queue.cpu(), self.queue_ptr()) if self.queue is not None else None, 'counter': self.counter()}
+
+    def import_state(self, st):
+        for w, t in st['flat'].items():
+            self.flat(w).copy_(t)
+        self.set_rms_state(*st['rms'])
+        if st['bn'] is not None:
+            self.bn.copy_(st['bn'])
+        self.set_opt_steps(st['opt_steps'])
+        if st.get('queue') is not None:         # pickles from before the queue and the counter were saved lack these keys
+            self.queue.copy_(st['queue'][0])
+            self.queue_ptr(st['queue'][1])
+        if 'counter' in st:
+            self.counter(st['counter'])
 
 
 def run_exchange(buf, op, rank=None, dist=None):

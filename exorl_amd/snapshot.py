@@ -17,18 +17,11 @@ from collections import OrderedDict
 
 import torch
 
-NETS = ('encoder', 'actor', 'critic', 'critic_target', 'value', 'rnd', 'icm', 'disagreement', 'diayn', 'aps', 'smm', 'predictor',
-        'predictor_target', 'projector', 'protos', 'encoder_target')
-
 
 def state_dicts(agent):
     """{net name: state_dict on the CPU} for every network the agent has, names and keys as in the reference."""
-    out = OrderedDict()
-    for name in NETS:
-        net = getattr(agent, name, None)
-        if net is not None and hasattr(net, 'state_dict'):
-            out[name] = OrderedDict((k, v.detach().cpu().clone()) for k, v in net.state_dict().items())
-    return out
+    return OrderedDict((name, OrderedDict((k, v.detach().cpu().clone()) for k, v in getattr(agent, name).state_dict().items()))
+                       for name in agent._members_with(agent._NET))      # the agent's own record of its networks, in construction order
 
 
 def save_state_dicts(agent, path):
@@ -38,15 +31,14 @@ def save_state_dicts(agent, path):
 def load_state_dicts(agent, path_or_dict, strict=True):
     """Loads what save_state_dicts (or the reference-side snippet above) wrote. Only tensors are read: weights_only=True."""
     d = path_or_dict if isinstance(path_or_dict, dict) else torch.load(path_or_dict, map_location='cpu', weights_only=True)
-    loaded = []
+    nets, loaded = agent._members_with(agent._NET), []
     for name, sd in d.items():
-        net = getattr(agent, name, None)
-        if net is None:
+        if name not in nets:
             if strict:
                 raise KeyError(f'snapshot has a network {name!r} this agent ({type(agent).__name__}) does not')
             continue
-        net.load_state_dict(sd)
+        getattr(agent, name).load_state_dict(sd)
         loaded.append(name)
-    if 'critic' in d and 'critic_target' not in d and hasattr(agent, 'critic_target'):
+    if 'critic' in d and 'critic_target' not in d and 'critic_target' in nets:
         agent.critic_target.load_state_dict(agent.critic.state_dict())       # td3_bc.py:93
     return loaded

@@ -95,7 +95,9 @@ def test_defaults():
     sig = inspect.signature(agents._AgentBase.evaluate).parameters
     assert list(sig) == ['self', 'replay_iter', 'num_batches', 'gather'] and sig['num_batches'].default == 1 and sig['gather'].default is None
     for cls in (agents.TD3BCAgent, agents.TD3Agent, agents.CRRAgent, agents.CQLAgent, agents.BCAgent):
-        assert cls.evaluate is agents._AgentBase.evaluate and cls.KIND in agents.EVAL_KINDS
+        assert cls.evaluate is agents._AgentBase.evaluate and cls.KIND in agents.EVAL_KINDS and cls._EVALUATES
+    for cls in (agents.IQLAgent, agents.FQEAgent, agents.DDPGAgent, agents.RNDAgent, agents.APSAgent, agents.ProtoAgent):
+        assert not cls._EVALUATES and cls.KIND not in agents.EVAL_KINDS
 
 
 def test_holdout_every_is_refused_online_and_below_two(tmp_path):

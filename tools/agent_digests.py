@@ -183,7 +183,12 @@ def digest(ag, emit):
         view = getattr(ag, name, None)
         if hasattr(view, 'state_dict'):
             emit(f'{name}.state_dict', sha(','.join(f'{k}={sha(v)}' for k, v in view.state_dict().items())))
-    emit('getstate.attrs', sha(','.join(sorted(ag.__getstate__()['attrs']))))
+    from exorl_amd import snapshot
+    st = ag.__getstate__()
+    emit('getstate.attrs', sha(','.join(sorted(st['attrs']))))
+    emit('getstate.keys', sha(','.join(list(st) + [f'intr.{k}' for k in st.get('intr', ())])))      # the pickled dict's layout, in its order
+    emit('snapshot.names', sha(','.join(snapshot.state_dicts(ag))))
+    emit('surface.public', sha(','.join(n for n in dir(ag) if not n.startswith('_') and hasattr(ag, n))))
 
 
 def emit_metrics(emit, tag, m):
