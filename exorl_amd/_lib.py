@@ -16,9 +16,11 @@ WEIGHT_EPISODES, WEIGHT_TRANSITIONS = 0, 1
 AGENT_TD3_BC, AGENT_TD3, AGENT_BC, AGENT_DDPG, AGENT_CRR, AGENT_CQL, AGENT_APS = 0, 1, 2, 3, 4, 5, 6
 AGENT_IQL = 8             # 7 is unassigned
 AGENT_FQE = 9
+AGENT_PRDC = 11           # 10 is unassigned, as 7
 AGENT_XCHG_CRITIC_GRAD, AGENT_XCHG_STATS, AGENT_XCHG_ACTOR_GRAD, AGENT_XCHG_VALUE_GRAD = 0, 1, 2, 3
 M_CRITIC_CQL, M_CRITIC_CQL_LOGSUM, M_ACTOR_ALPHA, M_ACTOR_ALPHA_LOSS, M_ACTOR_ENT = 10, 11, 12, 13, 14
 M_VALUE_LOSS, M_VALUE, M_ADV, M_ACTOR_WEIGHT = 10, 11, 12, 13        # IQL's use of slots 10..13
+M_NN_DIST = 10            # PRDC's use of slot 10
 CRR_WEIGHT = {'identity': 0, 'indicator': 1, 'exp': 2}
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2, 3
 NET_ACTOR, NET_CRITIC, NET_CRITIC_TARGET, NET_VALUE = 0, 1, 2, 3
@@ -155,6 +157,9 @@ PROTOTYPES = {
     'exorl_replay_episode_returns': (C.c_int, [c_void_p, c_float, c_void_p, c_int32, c_void_p]),
     'exorl_replay_num_episodes': (C.c_int, [c_void_p, P(c_int32)]),
     'exorl_replay_set_obs_norm': (C.c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    'exorl_replay_build_keys': (C.c_int, [c_void_p, c_float, c_int32, c_void_p]),
+    'exorl_replay_keys': (C.c_int, [c_void_p, P(c_void_p), P(c_int64), P(c_int32), P(c_uint64)]),
+    'exorl_replay_keys_read': (C.c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     'exorl_replay_num_rows': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_replay_seed_mt': (C.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
     'exorl_replay_seed_mt_ints': (C.c_int, [c_void_p, c_uint64, c_uint32]),
@@ -182,6 +187,8 @@ PROTOTYPES = {
     'exorl_agent_stats_buffer': (C.c_int, [c_void_p, P(c_void_p), P(c_int64)]),
     'exorl_agent_cql_alpha': (C.c_int, [c_void_p, c_void_p, c_int32]),
     'exorl_agent_set_iql': (C.c_int, [c_void_p, c_float, c_float, c_float]),
+    'exorl_agent_set_prdc': (C.c_int, [c_void_p, c_void_p, c_float]),
+    'exorl_agent_nn_result': (C.c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p), P(c_int32)]),
     'exorl_agent_act': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_act_host': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
@@ -226,6 +233,7 @@ PROTOTYPES = {
     'exorl_soft_update': (C.c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     'exorl_ln_tanh_fwd': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'exorl_knn_topk': (C.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'exorl_nn_search': (C.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_iql_rows_chunks': (c_int32, [c_int32]),
     'exorl_fqe_rows_chunks': (c_int32, [c_int32]),
     'exorl_fqe_rows': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -12,6 +12,7 @@ Reference classes mirrored (file:line in /root/reference):
   APSAgent    agents/unsupervised_learning/aps.py:82-320       SMMAgent   agents/unsupervised_learning/smm.py:115-281 (states)
   IQLAgent    no reference file: implicit Q-learning on the offline nets (the class's docstring is its definition)
   FQEAgent    no reference file: fitted Q evaluation of a frozen policy (the class's docstring is its definition)
+  PRDCAgent   no reference file: TD3+BC regularised to the nearest dataset point; defined in exorl_amd/prdc.py, reachable as agents.PRDCAgent
 
 Python here is orchestration only: it builds the initial weights with torch's CPU RNG in the reference's
 construction order (so a given torch.manual_seed yields the reference's initial parameters), hands batches
@@ -1767,3 +1768,11 @@ class _Identity:
     def __call__(self, x):
         return x
 
+
+def __getattr__(name):
+    """agents.PRDCAgent (Hydra: `_target_: exorl_amd.agents.PRDCAgent`) resolves to exorl_amd.prdc.PRDCAgent on first use: the class is
+    defined beside its dataset binding, as exorl_amd.fqe holds FQE's driver, and is not one of this module's own names."""
+    if name == 'PRDCAgent':
+        from .prdc import PRDCAgent
+        return PRDCAgent
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -394,6 +394,13 @@ struct exorl_agent {
     float *iql_dv = nullptr, *iql_part = nullptr;   // d L_V / d v (B); per-chunk metric sums [iql_chunks(B)][IQL_PARTS]; w goes to crr_w
     float expectile = 0.7f, temperature = 3.0f, max_weight = 100.0f;      // exorl_agent_set_iql
     float* fqe_part = nullptr;                      // FQE: per-chunk metric sums [iql_chunks(B)][FQE_PARTS]
+    // PRDC: the query rows [beta obs | mu(obs) | 0-pad], the search's partial minima and its results; a_nn stands where TD3+BC's actor phase
+    // reads the batch's action. The table is the replay's (exorl_agent_set_prdc): pointer, rows and key ranges are fixed while it is bound.
+    float *nn_q = nullptr, *nn_d2 = nullptr, *a_nn = nullptr, *nn_part_d2 = nullptr;
+    int *nn_idx = nullptr, *nn_part_idx = nullptr;
+    exorl_replay* prdc_replay = nullptr;
+    ReplayKeys prdc_keys{};
+    NnPlan prdc_plan{};
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -450,6 +457,13 @@ static bool planes_ok(const exorl_agent_cfg& cfg) {
 static bool planes3_ok(const exorl_agent_cfg& cfg) {
     return cfg.precision == EXORL_PREC_BF16X6 && cfg.hidden_dim % 128 == 0 && cfg.batch % 128 == 0;
 }
+
+// PRDC is TD3+BC with another BC target: wherever the step asks for lambda, the BC term or the window's bc_part it answers as TD3+BC, and the
+// kernels that take a kind are given TD3+BC's.
+static bool bc_regularised(int kind) { return kind == EXORL_AGENT_TD3_BC || kind == EXORL_AGENT_PRDC; }
+static int loss_kind(int kind) { return kind == EXORL_AGENT_PRDC ? EXORL_AGENT_TD3_BC : kind; }
+static const float* bc_target(const exorl_agent* a) { return a->cfg.kind == EXORL_AGENT_PRDC ? a->a_nn : a->action; }
+static int prdc_pitch(const exorl_agent_cfg& cfg) { return (int)round_up(cfg.obs_dim + cfg.act_dim, 4); }
 
 static void carve(exorl_agent* a, Carver& c) {
     const auto& cfg = a->cfg;
@@ -577,12 +591,24 @@ static void carve(exorl_agent* a, Carver& c) {
         a->fqe_part = c.take((int64_t)iql_chunks(B) * FQE_PARTS);
         c.scratch = false;
     }
+    if (cfg.kind == EXORL_AGENT_PRDC) {         // TD3+BC's layout with the search's buffers behind it: all written before they are read
+        c.scratch = true;
+        a->nn_q = c.take(B * prdc_pitch(cfg));
+        a->nn_part_d2 = c.take((int64_t)NN_MAX_SPLITS * B);
+        a->nn_part_idx = reinterpret_cast<int*>(c.take((int64_t)NN_MAX_SPLITS * B));
+        a->nn_idx = reinterpret_cast<int*>(c.take(B));
+        a->nn_d2 = c.take(B);
+        a->a_nn = c.take(B * A);
+        c.scratch = false;
+    }
 }
 
 static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
     EXORL_REQUIRE(cfg, "agent: null cfg");
-    EXORL_REQUIRE((cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS) || cfg->kind == EXORL_AGENT_IQL || cfg->kind == EXORL_AGENT_FQE,
-                  "agent: unknown kind %d", cfg->kind);
+    EXORL_REQUIRE((cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS) || cfg->kind == EXORL_AGENT_IQL || cfg->kind == EXORL_AGENT_FQE ||
+                  cfg->kind == EXORL_AGENT_PRDC, "agent: unknown kind %d", cfg->kind);
+    EXORL_REQUIRE(cfg->kind != EXORL_AGENT_PRDC || cfg->world_size == 1, "agent: PRDC searches the whole dataset on every step and a rank's shard "
+                  "is not the dataset: world_size=%d is not supported for this kind", cfg->world_size);
     EXORL_REQUIRE(cfg->kind != EXORL_AGENT_APS || (cfg->sf_dim >= 1 && cfg->sf_dim <= 16 && cfg->sf_dim < cfg->obs_dim),
                   "agent: APS needs 1 <= sf_dim <= 16 and obs_dim = observation + sf_dim (got sf_dim=%d obs_dim=%d)", cfg->sf_dim, cfg->obs_dim);
     EXORL_REQUIRE(cfg->kind != EXORL_AGENT_CQL || (cfg->n_samples >= 1 && cfg->n_samples <= 16 && cfg->act_dim <= 16),
@@ -687,9 +713,9 @@ static Step make_step(const exorl_agent* a, hipStream_t s, float stddev, const f
     Step st{s, stddev, noise_c, noise_a, whole, capture, staged, Fork(a->fk, fork)};
     st.fuse_opt = whole && !a->comm && !fork;
     st.qfuse = whole && !fork && (!a->want_metrics || a->win_sums) && a->has_critic && a->critic.n_heads == 2 && a->critic.out_dim == 1 &&
-               a->cfg.hidden_dim % 4 == 0 && (kind == EXORL_AGENT_TD3_BC || kind == EXORL_AGENT_TD3 || kind == EXORL_AGENT_DDPG);
+               a->cfg.hidden_dim % 4 == 0 && (bc_regularised(kind) || kind == EXORL_AGENT_TD3 || kind == EXORL_AGENT_DDPG);
     st.metric_kernels = a->win_sums ? !st.qfuse : a->want_metrics;
-    st.stats_in_phase2 = st.qfuse && a->comm && kind == EXORL_AGENT_TD3_BC;
+    st.stats_in_phase2 = st.qfuse && a->comm && bc_regularised(kind);
     return st;
 }
 
@@ -768,9 +794,9 @@ static int actor_mu_step(exorl_agent* a, const Step& st, bool forward, int kind,
     const FwdBufs f = a->fa.rows_from(B, cfg.hidden_dim, A);
     if (forward) EXORL_TRY(net_forward(n.d, n.P(), n.sh, x, O, B, f, true, true, cfg.precision, st.s));
     if (st.metric_kernels)                      // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
-        EXORL_TRY(actor_dmu(a->da, A, da_nets, (int64_t)B * A, f.out, a->action, reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A,
+        EXORL_TRY(actor_dmu(a->da, A, da_nets, (int64_t)B * A, f.out, bc_target(a), reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A,
                             a->inv_bg, cfg.alpha, kind, st.stddev, st.s, &a->state->stddev));
-    dm.mode = EXORL_DOUT_ACTOR_MU; dm.da = da_nets ? a->da : nullptr; dm.da_nets = da_nets; dm.mu = f.out; dm.a_data = a->action;
+    dm.mode = EXORL_DOUT_ACTOR_MU; dm.da = da_nets ? a->da : nullptr; dm.da_nets = da_nets; dm.mu = f.out; dm.a_data = bc_target(a);
     dm.kind = kind; dm.inv_bg = a->inv_bg; dm.stddev = st.stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
     return net_grads(a, st, n, x, B, f, dm);
 }
@@ -785,8 +811,8 @@ static int run_metrics_window(exorl_agent* a, const Step& st) {
     MetricsWindowArgs w{};
     w.fused = st.qfuse ? 1 : 0;
     w.crit_part = a->win_crit; w.abs_part = a->abs_part; w.bc_part = a->win_bc;
-    w.q_chunks = qhead_chunks(B); w.bc_chunks = a->cfg.kind == EXORL_AGENT_TD3_BC ? head_chunks(B) : 0;
-    w.kind = a->cfg.kind; w.act_dim = a->cfg.act_dim; w.ent_from_std = a->cfg.kind != EXORL_AGENT_CQL;
+    w.q_chunks = qhead_chunks(B); w.bc_chunks = bc_regularised(a->cfg.kind) ? head_chunks(B) : 0;
+    w.kind = loss_kind(a->cfg.kind); w.act_dim = a->cfg.act_dim; w.ent_from_std = a->cfg.kind != EXORL_AGENT_CQL;
     w.inv_bg = a->inv_bg; w.alpha = a->cfg.alpha; w.stddev = &a->state->stddev;
     w.metrics = a->metrics; w.sums = a->win_sums; w.steps = a->win_steps;
     return metrics_window(w, st.s);
@@ -898,7 +924,7 @@ static int phase2(exorl_agent* a, const Step& st) {
         DoutSpec dq{};                          // -lambda/Bg routed to the smaller Q (td3_bc.py:152-155)
         dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.alpha = cfg.alpha;
         if (cfg.kind == EXORL_AGENT_APS) { dq.q = a->sfq; dq.task = a->obs + (O - cfg.sf_dim); dq.task_ld = O; }
-        dq.use_lambda = cfg.kind == EXORL_AGENT_TD3_BC;
+        dq.use_lambda = bc_regularised(cfg.kind);
         if (qf) EXORL_TRY(run_qhead(a, st, 1, 0));   // Q(s, pi(s)), its min-routing gradient (lambda applied later), dz2, sum|Q| partials
         if (st.stats_in_phase2) {                // lambda needs sum|Q| over the GLOBAL batch (td3_bc.py:154): reduce it while the critic's
             EXORL_TRY(reduce_pairs(a->abs_part, qhead_chunks(B), a->stats, s));          // backward pass runs (it does not depend on lambda)
@@ -912,15 +938,15 @@ static int phase2(exorl_agent* a, const Step& st) {
     }
     DoutSpec dm{};
     if (qf) {                                   // lambda = alpha / mean|Q| from the per-chunk sums qhead left behind
-        dm.lam_parts = a->abs_part; dm.lam_chunks = qhead_chunks(B); dm.use_lambda = cfg.kind == EXORL_AGENT_TD3_BC; dm.alpha = cfg.alpha;
+        dm.lam_parts = a->abs_part; dm.lam_chunks = qhead_chunks(B); dm.use_lambda = bc_regularised(cfg.kind); dm.alpha = cfg.alpha;
         if (st.stats_in_phase2) {                // the all-reduced statistic (one 'chunk': stats[0] = global sum |Q|)
             EXORL_CHECK_HIP(hipStreamWaitEvent(s, a->ev_stats_done, 0));
             dm.lam_parts = a->stats; dm.lam_chunks = 1;
         }
-        if (a->win_sums && cfg.kind == EXORL_AGENT_TD3_BC) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
+        if (a->win_sums && bc_regularised(cfg.kind)) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
     }
     // BC (bc.py:82) runs its only forward here; the other kinds' is the obs half of phase 0's stacked pass
-    return actor_mu_step(a, st, !a->has_critic, cfg.kind, a->has_critic ? a->critic.n_trunks : 0, a->has_critic ? nullptr : a->reward, dm);
+    return actor_mu_step(a, st, !a->has_critic, loss_kind(cfg.kind), a->has_critic ? a->critic.n_trunks : 0, a->has_critic ? nullptr : a->reward, dm);
 }
 
 static int phase3(exorl_agent* a, const Step& st) {
@@ -1063,6 +1089,32 @@ static int fqe_phase10(exorl_agent* a, const Step& st) {
 
 static int fqe_phase11(exorl_agent* a, const Step& st) { return opt_step_critic(a, st, st.staged ? &a->state->replay_counter : nullptr); }
 
+// ---- PRDC: the BC target is the action of the dataset point nearest to (beta s, mu(s)) ----------------------
+// Phase 12, between phases 0 and 1: the query rows from the obs slot and the obs half of phase 0's stacked actor forward (the mu the actor
+// step differentiates), the search over the bound table (nn.hip: partial minima per key range, then the merge that also gathers a_nn), and
+// nn_dist where the step's metrics are read. a_nn is a constant of the actor step: nothing flows back through the search.
+static int prdc_bound(const exorl_agent* a, const char* who) {
+    if (a->cfg.kind != EXORL_AGENT_PRDC) return 0;
+    EXORL_REQUIRE(a->prdc_replay, "%s: no key table bound (exorl_replay_build_keys, then exorl_agent_set_prdc)", who);
+    const ReplayKeys k = replay_keys(a->prdc_replay);
+    EXORL_REQUIRE(k.valid && k.epoch == a->prdc_keys.epoch, "%s: the bound key table is stale: the arena, its order or its normaliser changed, or "
+                  "the table was rebuilt (exorl_replay_build_keys and exorl_agent_set_prdc again)", who);
+    return 0;
+}
+static int prdc_phase12(exorl_agent* a, const Step& st) {
+    const auto& cfg = a->cfg;
+    const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, pitch = prdc_pitch(cfg);      // every driver has checked the binding (prdc_bound)
+    EXORL_TRY(nn_query(a->obs, a->fa.out + (int64_t)B * A, a->prdc_keys.beta, B, O, A, pitch, a->nn_q, st.s));
+    NnSearch n{};
+    n.keys = a->prdc_keys.ptr; n.n = (int)a->prdc_keys.n; n.pitch = pitch; n.dim = O + A;
+    n.q = a->nn_q; n.q_ld = pitch; n.rows = B; n.plan = a->prdc_plan;
+    n.part_d2 = a->nn_part_d2; n.part_idx = a->nn_part_idx; n.idx_out = a->nn_idx; n.d2_out = a->nn_d2;
+    n.a_nn = a->a_nn; n.act_col0 = O; n.act_dim = A;
+    EXORL_TRY(nn_search(n, st.s));
+    if (st.metric_kernels) EXORL_TRY(nn_dist(a->nn_d2, B, a->inv_bg, a->metrics + EXORL_M_NN_DIST, st.s));
+    return 0;
+}
+
 // ---- the step as a plan -----------------------------------------------------------------------------
 // One update is the ordered list of its phases; where the data-parallel step (dp) needs a global batch quantity before the next phase, the plan
 // names the exchange that follows (EXORL_AGENT_XCHG_*, each a sum all-reduce), else -1. Both drivers read it: whole_step_body, which runs the
@@ -1112,12 +1164,20 @@ static const PhaseRow FQE_ROWS[] = {
     {10, fqe_phase10, EXORL_AGENT_XCHG_CRITIC_GRAD, EVERY_STEP},
     {11, fqe_phase11, -1, EVERY_STEP},
 };
+static const PhaseRow PRDC_ROWS[] = {         // TD3+BC's with the search behind phase 0; one process only, so no exchange is ever named
+    {0, phase0, EXORL_AGENT_XCHG_CRITIC_GRAD, IF_CRITIC},
+    {12, prdc_phase12, -1, EVERY_STEP},
+    {1, phase1, EXORL_AGENT_XCHG_STATS, IF_LAMBDA},
+    {2, phase2, EXORL_AGENT_XCHG_ACTOR_GRAD, EVERY_STEP},
+    {3, phase3, -1, EVERY_STEP},
+};
 template <int N>
 static constexpr PhaseTable phase_rows(const char* owner, const char* ids, const PhaseRow (&rows)[N]) { return PhaseTable{owner, ids, rows, N}; }
 static const PhaseTable PHASE_TABLES[] = {phase_rows("the DDPG family", "0..3", DDPG_ROWS), phase_rows("CQL", "0..5", CQL_ROWS),
-                                          phase_rows("IQL", "6..9", IQL_ROWS), phase_rows("FQE", "10, 11", FQE_ROWS)};
+                                          phase_rows("IQL", "6..9", IQL_ROWS), phase_rows("FQE", "10, 11", FQE_ROWS),
+                                          phase_rows("PRDC", "0..3, 12", PRDC_ROWS)};
 static const PhaseTable& phase_table(int kind) {
-    return PHASE_TABLES[kind == EXORL_AGENT_CQL ? 1 : kind == EXORL_AGENT_IQL ? 2 : kind == EXORL_AGENT_FQE ? 3 : 0];
+    return PHASE_TABLES[kind == EXORL_AGENT_CQL ? 1 : kind == EXORL_AGENT_IQL ? 2 : kind == EXORL_AGENT_FQE ? 3 : kind == EXORL_AGENT_PRDC ? 4 : 0];
 }
 static const PhaseRow* find_phase(const PhaseTable& t, int id) {
     for (int i = 0; i < t.n; ++i)
@@ -1136,7 +1196,7 @@ static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_pha
     for (int i = 0; i < t.n; ++i) {
         const PhaseRow& r = t.rows[i];
         if (r.rule == (split ? UNLESS_SPLIT : IF_SPLIT)) continue;
-        const bool on = r.rule == IF_CRITIC ? c.kind != EXORL_AGENT_BC : r.rule == IF_LAMBDA ? c.kind == EXORL_AGENT_TD3_BC && !stats_in_phase2 : true;
+        const bool on = r.rule == IF_CRITIC ? c.kind != EXORL_AGENT_BC : r.rule == IF_LAMBDA ? bc_regularised(c.kind) && !stats_in_phase2 : true;
         p.phase[p.n] = r.id;
         p.xchg[p.n++] = dp && on ? r.xchg : -1;
     }
@@ -1368,6 +1428,7 @@ int exorl_agent_set_batch(exorl_agent_t* a, const float* obs, const float* actio
 
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_c, const float* noise_a, void* stream) {
     EXORL_REQUIRE(a, "agent_update_phase: null handle");
+    EXORL_TRY(prdc_bound(a, "agent_update_phase"));
     hipStream_t s = as_stream(stream);
     EXORL_TRY(push_stddev(a, "agent_update_phase", stddev, s));
     return run_phase(a, make_step(a, s, stddev, noise_c, noise_a, false, false, false, false), phase);
@@ -1377,6 +1438,7 @@ int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_c, con
     EXORL_REQUIRE(a, "agent_update: null handle");
     EXORL_REQUIRE(a->cfg.world_size == 1 || a->comm, "agent_update: world_size=%d needs a communicator (exorl_agent_set_comm), or drive "
                   "exorl_agent_update_phase and all-reduce between the phases yourself", a->cfg.world_size);
+    EXORL_TRY(prdc_bound(a, "agent_update"));
     hipStream_t s = as_stream(stream);
     EXORL_TRY(push_stddev(a, "agent_update_phase", stddev, s));
     return whole_step_body(a, make_step(a, s, stddev, noise_c, noise_a, true, false, false, false));
@@ -1499,6 +1561,7 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     EXORL_REQUIRE(a->cfg.world_size == 1 || a->comm, "agent_enable_graph: a data-parallel step needs the library's communicator (exorl_agent_set_comm) to be captured; "
                   "steps whose collectives run in the caller's code are enqueued eagerly");
     EXORL_REQUIRE(stddev > 0.f && nstep >= 1, "agent_enable_graph: bad stddev/nstep");
+    EXORL_TRY(prdc_bound(a, "agent_enable_graph"));
     EXORL_REQUIRE(replay_frame_stack(r) == 1, "agent_enable_graph: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): the "
                   "captured step stages its inputs from whole arena rows; sample a frame-stacked arena eagerly", replay_frame_stack(r));
     EXORL_TRY(release_graph(a));
@@ -1636,6 +1699,32 @@ int exorl_agent_set_iql(exorl_agent_t* a, float expectile, float temperature, fl
     return 0;
 }
 
+int exorl_agent_set_prdc(exorl_agent_t* a, exorl_replay_t* r, float beta) {
+    EXORL_REQUIRE(a && r, "agent_set_prdc: null argument");
+    EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_PRDC, "agent_set_prdc: kind %d is not PRDC", a->cfg.kind);
+    EXORL_REQUIRE(!a->graph_exec, "agent_set_prdc: disable the captured graph first (it holds the table's pointer, row count and key ranges)");
+    const ReplayKeys k = replay_keys(r);
+    EXORL_REQUIRE(k.valid, "agent_set_prdc: the replay has no key table, or a stale one: the arena, its order or its normaliser changed since "
+                  "exorl_replay_build_keys (call it again)");
+    EXORL_REQUIRE(k.obs_cols == a->cfg.obs_dim && k.act_dim == a->cfg.act_dim, "agent_set_prdc: the table's keys are %d observation + %d action "
+                  "columns, the agent's %d + %d", k.obs_cols, k.act_dim, a->cfg.obs_dim, a->cfg.act_dim);
+    EXORL_REQUIRE(k.beta == beta, "agent_set_prdc: the table was built with beta=%g, not %g", k.beta, beta);
+    int cus = 0;
+    EXORL_TRY(nn_device_cus(&cus));
+    a->prdc_replay = r;
+    a->prdc_keys = k;
+    a->prdc_plan = nn_plan((int)k.n, a->cfg.batch, 0, cus);      // fixed here, not per call: a captured graph replays the same launches
+    return 0;
+}
+
+int exorl_agent_nn_result(exorl_agent_t* a, void** idx_dev, void** d2_dev, void** a_nn_dev, int32_t* splits) {
+    EXORL_REQUIRE(a && idx_dev && d2_dev && a_nn_dev, "agent_nn_result: null argument");
+    EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_PRDC, "agent_nn_result: kind %d is not PRDC", a->cfg.kind);
+    *idx_dev = a->nn_idx; *d2_dev = a->nn_d2; *a_nn_dev = a->a_nn;
+    if (splits) *splits = a->prdc_replay ? a->prdc_plan.splits : 0;
+    return 0;
+}
+
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable) {
     EXORL_REQUIRE(a, "agent_set_parallel_branches: null handle");
     EXORL_REQUIRE(!a->graph_exec, "agent_set_parallel_branches: disable the captured graph first");
@@ -1665,6 +1754,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
     }
     EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_IQL, "agent_set_metric_window: IQL has no metric window");
     EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_FQE, "agent_set_metric_window: FQE has no metric window");
+    EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_PRDC, "agent_set_metric_window: PRDC has no metric window");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     EXORL_TRY(attach_window("agent_set_metric_window", buf_dev, bytes, window_bytes(a->cfg), &a->win_sums, &a->win_crit));
@@ -1795,6 +1885,7 @@ int exorl_agent_disable_graph(exorl_agent_t* a) {
 // One captured step: replay sample (Philox) + the kind's whole update plan, one hipGraphLaunch.
 int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
     EXORL_REQUIRE(a && a->graph_exec, "agent_step_graph: no captured graph (call exorl_agent_enable_graph)");
+    EXORL_TRY(prdc_bound(a, "agent_step_graph"));      // the graph holds the table's pointer, row count and key ranges
     EXORL_TRY(push_stddev(a, "agent_step_graph", stddev, as_stream(stream)));      // schedule moved: one scalar write ahead of the launch, same stream
     EXORL_REQUIRE(replay_weights_epoch(a->graph_replay) == a->graph_weights_epoch, "agent_step_graph: exorl_replay_set_weights was called after "
                   "the capture: the graph samples the table it was captured with (call exorl_agent_enable_graph again)");

@@ -572,6 +572,40 @@ void intr_graph_release(exorl_intr* it);
 // meta agents: next_obs[:, O:O+M] = obs[:, O:O+M] on [obs | meta] rows of `ld` floats (the replay gather fills the obs rows' meta columns)
 int copy_meta_columns(const float* obs, float* next_obs, int64_t ld, int rows, int O, int M, hipStream_t s);
 
+// ---- exact 1-nearest-neighbour search against a key table in HBM (nn.hip): PRDC's BC target
+constexpr int NN_MAX_SPLITS = 256;        // key ranges of one search: what a workspace sizes its partials for
+constexpr int NN_MAX_DIM = 512;           // columns of a key: a 64-query tile of whole rows stays in LDS
+// The table's build from the arena: one work item per (episode of the order table, 64-transition chunk), item0 / trans0 the item and
+// transition prefix per episode (n_episodes + 1 entries). mean / inv null: the observations are taken as they are stored.
+struct NnKeyBuild {
+    const float *obs, *act;
+    const int64_t* row0; const int32_t* len; const int32_t* item0; const int64_t* trans0;
+    int n_episodes, n_items, O, A, pitch;
+    const float *mean, *inv;
+    float beta; int every;
+    float* keys;
+};
+int nn_build_keys(const NnKeyBuild& b, hipStream_t s);
+// q (rows, pitch) = [beta obs | mu | 0-pad]
+int nn_query(const float* obs, const float* mu, float beta, int rows, int O, int A, int pitch, float* q, hipStream_t s);
+struct NnPlan { int splits, tiles_per_split, q_tiles; };
+NnPlan nn_plan(int n, int rows, int want_splits, int cus);       // want_splits 0: chosen from n, rows and the CU count
+int nn_device_cus(int* cus);
+// part_d2 / part_idx: plan.splits x rows scratch. a_nn (rows, act_dim), may be null: columns act_col0.. of each winning key row.
+struct NnSearch {
+    const float* keys; int n, pitch, dim;
+    const float* q; int64_t q_ld; int rows;
+    NnPlan plan;
+    float* part_d2; int* part_idx;
+    int* idx_out; float* d2_out;
+    float* a_nn; int act_col0, act_dim;
+};
+int nn_search(const NnSearch& a, hipStream_t s);
+int nn_dist(const float* d2, int rows, float inv_bg, float* out, hipStream_t s);      // *out = inv_bg sum sqrt(d2), a fixed order
+// the replay's key table as exorl_replay_build_keys left it (replay.hip); valid = false once the arena, its order or its normaliser changed
+struct ReplayKeys { const float* ptr; int64_t n; int pitch, obs_cols, act_dim; float beta; uint64_t epoch; bool valid; };
+ReplayKeys replay_keys(exorl_replay* r);
+
 // ---- replay (replay.hip) internal entry points used by the agent's graph capture
 // Optional fan-out of the sampled rows into the agent's staged network inputs (what prepare_inputs would do in a second
 // kernel): xa = [next_obs ; obs], xc_cur = [obs | action], xc_next[:, :O] = next_obs, xc_pi[:, :O] = obs. fp32 state

@@ -150,6 +150,19 @@ struct exorl_replay {
     std::vector<int32_t> h_item0;
     std::vector<double> h_moments;
     double* d_returns = nullptr;      // exorl_replay_episode_returns' output, max_episodes doubles, allocated on first use
+    // exorl_replay_build_keys' table (nn.hip): a snapshot of the resident transitions, stale once the arena, its order or its normaliser moves
+    float* d_keys = nullptr;
+    size_t keys_cap = 0;              // floats allocated
+    int64_t keys_n = 0;
+    float keys_beta = 0.f;
+    int32_t keys_every = 1;
+    bool keys_valid = false;
+    uint64_t keys_epoch = 0;          // counts builds and invalidations: an agent bound to the table holds the value of its build
+    int32_t* d_kitem0 = nullptr;      // the build's item and transition prefix per episode, max_episodes + 1 entries each, allocated on first use
+    int64_t* d_ktrans0 = nullptr;
+    std::vector<int32_t> h_kitem0;
+    std::vector<int64_t> h_ktrans0;
+    void keys_stale() { if (keys_valid) { keys_valid = false; keys_epoch += 1; } }
 };
 
 namespace exorl {
@@ -627,6 +640,9 @@ int exorl_replay_destroy(exorl_replay_t* r) {
     if (r->d_item0) (void)hipFree(r->d_item0);
     if (r->d_slab) (void)hipFree(r->d_slab);
     if (r->d_returns) (void)hipFree(r->d_returns);
+    if (r->d_keys) (void)hipFree(r->d_keys);
+    if (r->d_kitem0) (void)hipFree(r->d_kitem0);
+    if (r->d_ktrans0) (void)hipFree(r->d_ktrans0);
     delete r;
     return 0;
 }
@@ -636,6 +652,7 @@ int exorl_replay_append_episode(exorl_replay_t* r, const void* obs, const float*
     EXORL_REQUIRE(r && obs && act && rew && disc && slot_out, "replay_append_episode: null argument");
     EXORL_REQUIRE(rows >= 2, "replay_append_episode: rows=%d (an episode is a dummy row + >=1 transition)", rows);
     EXORL_REQUIRE((r->cfg.meta_dim == 0) == (meta == nullptr), "replay_append_episode: meta pointer/meta_dim mismatch");
+    r->keys_stale();
     if (r->used_rows + rows > r->cfg.capacity_rows) {
         EXORL_REQUIRE(r->live_rows + rows <= r->cfg.capacity_rows,
                       "replay_append_episode: arena full (%lld live + %d > capacity %lld rows)", (long long)r->live_rows, rows,
@@ -668,6 +685,7 @@ int exorl_replay_append_episode(exorl_replay_t* r, const void* obs, const float*
 
 int exorl_replay_evict(exorl_replay_t* r, int32_t slot) {
     EXORL_REQUIRE(r && slot >= 0 && slot < (int)r->slots.size() && r->slots[slot].live, "replay_evict: slot %d not resident", slot);
+    r->keys_stale();
     r->slots[slot].live = false;
     r->live_rows -= r->slots[slot].rows;
     for (size_t i = 0; i < r->order.size(); ++i)
@@ -681,6 +699,7 @@ int exorl_replay_set_order(exorl_replay_t* r, const int32_t* slots, int32_t n) {
     for (int i = 0; i < n; ++i)
         EXORL_REQUIRE(slots[i] >= 0 && slots[i] < (int)r->slots.size() && r->slots[slots[i]].live,
                       "replay_set_order: slot %d (position %d) not resident", slots[i], i);
+    r->keys_stale();
     r->order.assign(slots, slots + n);
     r->table_dirty = true;
     return 0;
@@ -768,6 +787,7 @@ int exorl_replay_episode_returns(exorl_replay_t* r, float gamma, double* returns
 
 int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* mean_host, const float* inv_scale_host, void* stream) {
     EXORL_REQUIRE(r, "replay_set_obs_norm: null handle");
+    r->keys_stale();
     if (n_cols == 0) {
         r->norm_on = false;
         return 0;
@@ -783,6 +803,77 @@ int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* me
     // a pageable source: the runtime stages it before returning, so the vector may be rewritten by the next call
     EXORL_CHECK_HIP(hipMemcpyAsync(r->d_norm, r->h_norm.data(), r->h_norm.size() * sizeof(float), hipMemcpyHostToDevice, as_stream(stream)));
     r->norm_on = true;
+    return 0;
+}
+
+int exorl_replay_build_keys(exorl_replay_t* r, float beta, int32_t key_every, void* stream) {
+    EXORL_REQUIRE(r, "replay_build_keys: null handle");
+    EXORL_REQUIRE(beta >= 0.f && key_every >= 1, "replay_build_keys: needs beta >= 0 and key_every >= 1 (got %g, %d)", beta, key_every);
+    EXORL_REQUIRE(r->frames == 1, "replay_build_keys: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): keys are built "
+                  "from fp32 state rows", r->frames);
+    EXORL_REQUIRE(!r->order.empty(), "replay_build_keys: no resident episode in the order table");
+    hipStream_t s = as_stream(stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    EXORL_CHECK_HIP(hipStreamIsCapturing(s, &cs));
+    EXORL_REQUIRE(cs == hipStreamCaptureStatusNone, "replay_build_keys: a set-up call (it allocates and synchronises): not inside a capture");
+    const int n = (int)r->order.size(), O = r->cfg.obs_bytes / 4, A = r->cfg.act_dim;
+    const int pitch = (int)round_up(O + A, 4);
+    EXORL_REQUIRE(O + A <= NN_MAX_DIM, "replay_build_keys: %d observation + %d action columns (max %d)", O, A, NN_MAX_DIM);
+    r->h_kitem0.resize((size_t)n + 1);
+    r->h_ktrans0.resize((size_t)n + 1);
+    int64_t items = 0, trans = 0;
+    for (int i = 0; i < n; ++i) {
+        const int len = r->slots[r->order[i]].rows - 1;
+        r->h_kitem0[i] = (int32_t)items;
+        r->h_ktrans0[i] = trans;
+        items += cdiv(len, 64);
+        trans += len;
+        EXORL_REQUIRE(items < INT32_MAX, "replay_build_keys: more than 2^31 work items of 64 transitions");
+    }
+    r->h_kitem0[n] = (int32_t)items;
+    r->h_ktrans0[n] = trans;
+    const int64_t rows = (trans + key_every - 1) / key_every;
+    EXORL_REQUIRE(rows < INT32_MAX - 64, "replay_build_keys: %lld key rows (the search indexes them with 32 bits)", (long long)rows);
+    r->keys_stale();
+    EXORL_CHECK_HIP(hipDeviceSynchronize());      // a search enqueued earlier may still read the table that is replaced
+    const size_t need = (size_t)rows * pitch;
+    if (need > r->keys_cap) {
+        if (r->d_keys) EXORL_CHECK_HIP(hipFree(r->d_keys));
+        r->d_keys = nullptr; r->keys_cap = 0;
+        EXORL_CHECK_HIP(hipMalloc((void**)&r->d_keys, need * sizeof(float)));
+        r->keys_cap = need;
+    }
+    if (!r->d_kitem0) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_kitem0, ((size_t)r->cfg.max_episodes + 1) * sizeof(int32_t)));
+    if (!r->d_ktrans0) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_ktrans0, ((size_t)r->cfg.max_episodes + 1) * sizeof(int64_t)));
+    EXORL_TRY(upload_table(r, 0, s));
+    EXORL_CHECK_HIP(hipMemcpyAsync(r->d_kitem0, r->h_kitem0.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    EXORL_CHECK_HIP(hipMemcpyAsync(r->d_ktrans0, r->h_ktrans0.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    NnKeyBuild b{reinterpret_cast<const float*>(r->obs), r->act, r->d_row0, r->d_len, r->d_kitem0, r->d_ktrans0, n, (int)items, O, A, pitch,
+                 r->norm_on ? r->d_norm : nullptr, r->norm_on ? r->d_norm + O : nullptr, beta, key_every, r->d_keys};
+    EXORL_TRY(nn_build_keys(b, s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    r->keys_n = rows; r->keys_beta = beta; r->keys_every = key_every;
+    r->keys_valid = true;
+    r->keys_epoch += 1;
+    return 0;
+}
+
+int exorl_replay_keys(exorl_replay_t* r, void** ptr_dev, int64_t* n, int32_t* pitch, uint64_t* epoch) {
+    EXORL_REQUIRE(r && ptr_dev && n && pitch && epoch, "replay_keys: null argument");
+    EXORL_REQUIRE(r->keys_valid, "replay_keys: no key table, or a stale one: the arena, its order or its normaliser changed since "
+                  "exorl_replay_build_keys (call it again)");
+    const ReplayKeys k = replay_keys(r);
+    *ptr_dev = const_cast<float*>(k.ptr); *n = k.n; *pitch = k.pitch; *epoch = k.epoch;
+    return 0;
+}
+
+int exorl_replay_keys_read(exorl_replay_t* r, void* dst_dev, size_t bytes, void* stream) {
+    EXORL_REQUIRE(r && dst_dev, "replay_keys_read: null argument");
+    EXORL_REQUIRE(r->keys_valid, "replay_keys_read: no key table, or a stale one (exorl_replay_build_keys)");
+    const ReplayKeys k = replay_keys(r);
+    EXORL_REQUIRE(bytes == (size_t)k.n * k.pitch * sizeof(float), "replay_keys_read: buffer of %zu bytes, the table has %lld rows of %d floats",
+                  bytes, (long long)k.n, k.pitch);
+    EXORL_CHECK_HIP(hipMemcpyAsync(dst_dev, k.ptr, bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
     return 0;
 }
 
@@ -923,6 +1014,10 @@ uint64_t replay_weights_epoch(exorl_replay* r) { return r->weights_epoch; }
 bool replay_norm_on(exorl_replay* r) { return r->norm_on; }
 int replay_obs_bytes(exorl_replay* r) { return r->frames * r->cfg.obs_bytes; }      // of one SAMPLED observation
 int replay_frame_stack(exorl_replay* r) { return r->frames; }
+ReplayKeys replay_keys(exorl_replay* r) {
+    return ReplayKeys{r->d_keys, r->keys_n, (int)round_up(r->cfg.obs_bytes / 4 + r->cfg.act_dim, 4), r->cfg.obs_bytes / 4, r->cfg.act_dim, r->keys_beta,
+                      r->keys_epoch, r->keys_valid};
+}
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }
 void replay_advance_philox(exorl_replay* r, uint64_t n) { r->philox_counter += n; }
 }  // namespace exorl

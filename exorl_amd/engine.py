@@ -13,7 +13,7 @@ from . import _lib as L
 
 KIND = {'td3_bc': L.AGENT_TD3_BC, 'td3': L.AGENT_TD3, 'bc': L.AGENT_BC, 'ddpg': L.AGENT_DDPG, 'crr': L.AGENT_CRR, 'cql': L.AGENT_CQL,
         'aps': L.AGENT_APS}
-KIND_BEYOND_REFERENCE = {'iql': L.AGENT_IQL, 'fqe': L.AGENT_FQE}        # kinds the reference does not have; KIND stays the reference's seven
+KIND_BEYOND_REFERENCE = {'iql': L.AGENT_IQL, 'fqe': L.AGENT_FQE, 'prdc': L.AGENT_PRDC}        # kinds the reference does not have; KIND stays the reference's seven
 PRECISION = {'fp32': L.PREC_F32, 'f32': L.PREC_F32, 'bf16': L.PREC_BF16, 'bf16x3': L.PREC_BF16X3, 'bf16x6': L.PREC_BF16X6}
 METRIC_KEYS = {L.M_BATCH_REWARD: 'batch_reward', L.M_CRITIC_TARGET_Q: 'critic_target_q', L.M_CRITIC_Q1: 'critic_q1',
                L.M_CRITIC_Q2: 'critic_q2', L.M_CRITIC_LOSS: 'critic_loss', L.M_ACTOR_LOSS: 'actor_loss',
@@ -381,6 +381,20 @@ class AgentEngine(_Phased):
     def set_iql(self, expectile, temperature, max_weight):
         """IQL's hyper-parameters (exorl_agent_set_iql); refused while a graph is captured."""
         L.check(self.lib.exorl_agent_set_iql(self.h, expectile, temperature, max_weight))
+
+    def set_prdc(self, replay_engine, beta):
+        """PRDC: bind the key table `replay_engine.build_keys(beta)` made (exorl_agent_set_prdc). Refused while a graph is captured, for
+        another kind, for a stale table and for one built with another beta or another observation / action split."""
+        L.check(self.lib.exorl_agent_set_prdc(self.h, replay_engine.h, float(beta)))
+        self._prdc_keep = replay_engine             # the step reads the replay's table
+
+    def nn_result(self):
+        """PRDC: (idx int32 (B,), d2 float32 (B,), a_nn float32 (B, A)) views of the last search's results, and the bound table's key
+        ranges (0: nothing bound)."""
+        i, d, a, s = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        L.check(self.lib.exorl_agent_nn_result(self.h, C.byref(i), C.byref(d), C.byref(a), C.byref(s)))
+        B, A = self.batch, self.act_dim
+        return self._view(i.value, B).view(torch.int32), self._view(d.value, B), self._view(a.value, B * A).view(B, A), s.value
 
     def metrics_raw(self):
         host = np.zeros(L.N_METRICS, np.float32)
@@ -912,6 +926,32 @@ class ReplayEngine:
         cnt, mean, m2 = C.c_int64(), np.zeros(n, np.float64), np.zeros(n, np.float64)
         L.check(self.lib.exorl_replay_obs_moments(self.h, n, C.byref(cnt), mean.ctypes.data, m2.ctypes.data, L.current_stream()))
         return cnt.value, mean.reshape(self.obs_shape), m2.reshape(self.obs_shape)
+
+    def build_keys(self, beta, key_every=1):
+        """The key table of PRDC's nearest-neighbour search (exorl_replay_build_keys): one row [beta * s | a | 0-pad] per resident
+        transition, s as the gather emits it (normalised when a normaliser is set), every key_every-th transition kept. A snapshot:
+        append_episode, evict, set_order and set_obs_normalizer / clear_obs_normalizer make it stale. float32 state arenas only. A set-up
+        call: it allocates and synchronises. Returns the number of rows."""
+        self._state_cols('build_keys')
+        if self.frame_stack > 1:
+            raise ValueError('build_keys: a frame-stacked arena holds pixels; keys are built from float32 state rows')
+        L.check(self.lib.exorl_replay_build_keys(self.h, float(beta), int(key_every), L.current_stream()))
+        return self.keys_info()[1]
+
+    def keys_info(self):
+        """(device pointer, rows, pitch, epoch) of the key table as last built (exorl_replay_keys); ExorlError when there is none or it
+        is stale."""
+        p, n, pitch, epoch = C.c_void_p(), C.c_int64(), C.c_int32(), C.c_uint64()
+        L.check(self.lib.exorl_replay_keys(self.h, C.byref(p), C.byref(n), C.byref(pitch), C.byref(epoch)))
+        return p.value, n.value, pitch.value, epoch.value
+
+    def keys(self):
+        """A copy of the key table as last built: a (rows, pitch) float32 device tensor, pitch = round_up(O + A, 4). ExorlError when
+        there is none or it is stale."""
+        _, n, pitch, _ = self.keys_info()
+        out = torch.empty(n, pitch, dtype=torch.float32, device=self.device)
+        L.check(self.lib.exorl_replay_keys_read(self.h, out.data_ptr(), out.numel() * 4, L.current_stream()))
+        return out
 
     def num_episodes(self):
         """Episodes in the order table: the positions a SAMPLER_GIVEN pair may name."""

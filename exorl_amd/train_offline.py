@@ -41,6 +41,8 @@ def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, repla
     replay_iter = iter(loader)
     if normalize_obs:
         agent.set_obs_normalizer(*replay_iter.obs_normalizer)
+    if hasattr(agent, 'bind_dataset'):          # PRDCAgent: the key table, built through the normaliser, before the capture
+        agent.bind_dataset(replay_iter)
     windowed = bool(metric_window) and hasattr(agent, 'enable_metric_window') and agent.enable_metric_window()      # before the capture
     if use_graph and hasattr(agent, 'enable_graph'):
         agent.enable_graph(replay_iter, start_step)      # False (and eager launches) when the pairing cannot be captured

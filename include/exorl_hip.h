@@ -43,7 +43,8 @@ extern "C" {
                                         calls return next_exchange; exorl_pixel_agent_exchange replaces _grad_buffer and _bn_partials; (added since, no version change:
                                         exorl_agent_eval_bytes / _set_eval / _evaluate / _eval_read; EXORL_AGENT_IQL, exorl_agent_set_iql;
                                         EXORL_AGENT_FQE, exorl_agent_fqe_value_bytes / _set_fqe_value / _fqe_value / _fqe_value_read,
-                                        exorl_replay_episode_returns, exorl_replay_num_episodes) */
+                                        exorl_replay_episode_returns, exorl_replay_num_episodes; EXORL_AGENT_PRDC, exorl_replay_build_keys,
+                                        exorl_replay_keys, exorl_replay_keys_read, exorl_nn_search, exorl_agent_set_prdc, exorl_agent_nn_result) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -134,6 +135,21 @@ int exorl_replay_num_episodes(exorl_replay_t* r, int32_t* n);
  * exorl_agent_step_graph refuses a graph captured in the other state. Fails for n_cols * 4 != obs_bytes and on a frame-stacked arena;
  * exorl_agent_enable_graph_intr refuses a normalised arena. */
 int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* mean_host, const float* inv_scale_host, void* stream);
+/* The key table of the nearest-neighbour search (EXORL_AGENT_PRDC): one row per resident transition, episodes in order-table order and
+ * t = 1 .. len inside each, row = [beta * s | a | 0-pad] with s = obs[t - 1] as the gather would emit it (with a normaliser set,
+ * (x - mean) * inv_scale in the same two uncontracted fp32 operations), beta * s one further fp32 product, a = action[t]; the pitch is
+ * round_up(obs_bytes / 4 + act_dim, 4) floats. key_every = m >= 1 keeps the transitions whose running index i has i % m == 0, as row i / m.
+ * One launch over (episode, 64-transition chunk) items into a device buffer the replay owns; evicted slots and holes are not read. Fails,
+ * launching nothing, on a frame-stacked arena, with no resident episode, for beta < 0 and inside a capture. The arena must hold fp32 state
+ * rows (the C side cannot tell: a u8 arena is refused by the caller that knows the type). A set-up call: it allocates and synchronises.
+ * The table is a snapshot: exorl_replay_append_episode, exorl_replay_evict, exorl_replay_set_order and exorl_replay_set_obs_norm all mark
+ * it stale, and a new build replaces it. */
+int exorl_replay_build_keys(exorl_replay_t* r, float beta, int32_t key_every, void* stream);
+/* The table as last built: device pointer, rows, pitch in floats and the epoch of this build (it moves with every build and every
+ * invalidation). Fails when there is no table or it is stale. */
+int exorl_replay_keys(exorl_replay_t* r, void** ptr_dev, int64_t* n, int32_t* pitch, uint64_t* epoch);
+/* Copies the table (n * pitch floats, `bytes` must be exactly that) into the caller's device buffer, on `stream`. Same refusals. */
+int exorl_replay_keys_read(exorl_replay_t* r, void* dst_dev, size_t bytes, void* stream);
 /* MT19937 states as exposed by random.getstate()[1] / np.random.get_state()[1:3]. */
 int exorl_replay_seed_mt(exorl_replay_t* r, const uint32_t* py_key624, int32_t py_pos,
                          const uint32_t* np_key624, int32_t np_pos);
@@ -191,6 +207,13 @@ typedef struct exorl_agent exorl_agent_t;
                                   not a pessimistic bound; the two nets are a two-member ensemble). update() draws no noise, as IQL's. The
                                   policy's value is read with exorl_agent_fqe_value. */
 
+/* kind 10 is unassigned and refused, as 7 is */
+#define EXORL_AGENT_PRDC   11  /* policy regularisation with dataset constraint (Ran et al., ICML 2023), no reference file: TD3+BC with the BC target
+                                  replaced by the action of the dataset point nearest to (beta s, mu(s)), searched exactly over the replay's key
+                                  table on every step (exorl_replay_build_keys, exorl_agent_set_prdc):
+                                  actor loss = -lambda mean(min Q(s, pi(s))) + mse(mu(s), a_nn), lambda = alpha / mean|Q|, a_nn a constant.
+                                  Nets, critic step, noise and soft update are TD3+BC's. One process only: world_size > 1 is refused. */
+
 #define EXORL_CRR_IDENTITY  0   /* crr.py:132-142 adv_transform */
 #define EXORL_CRR_INDICATOR 1
 #define EXORL_CRR_EXP       2
@@ -241,6 +264,8 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_M_VALUE        11   /* mean V(s) */
 #define EXORL_M_ADV          12   /* mean u */
 #define EXORL_M_ACTOR_WEIGHT 13   /* mean w */
+/* EXORL_AGENT_PRDC only: slot 10 (CQL's and IQL's names above mean nothing for PRDC); slots 0..9 are TD3+BC's. */
+#define EXORL_M_NN_DIST      10   /* mean over the batch of sqrt(d2) to the nearest key */
 #define EXORL_N_METRICS        16
 
 typedef struct {
@@ -301,6 +326,7 @@ int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_critic
  *   phase 9 -> IQL: Adam on value, critic (+ soft update) and actor. IQL runs phases 6..9 only; the other kinds refuse them.
  *   phase 10 -> FQE: mu(s') on the next_obs rows, Q'(s', mu(s')), Q(s, a), the row kernel (dq, metric sums), critic grads
  *   phase 11 -> FQE: critic Adam (+ soft update). FQE runs phases 10 and 11 only; the other kinds refuse them.
+ *   phase 12 -> PRDC, between phases 0 and 1: the queries [beta obs | mu(obs)], the search, a_nn gathered. PRDC's plan is 0, 12, 1, 2, 3.
  * Which phases a configuration's step runs, in which order, and which exchange follows each: exorl_agent_update_plan. Phase 0 is refused for
  * CQL with use_critic_lagrange and world_size > 1 (phases 4 and 5 stand for it). */
 int exorl_agent_update_phase(exorl_agent_t* a, int32_t phase, float stddev, const float* noise_critic_dev,
@@ -325,6 +351,15 @@ int exorl_agent_cql_alpha(exorl_agent_t* a, float* log_alpha_host, int32_t set);
  * temperature < 0 or max_weight <= 0 (or NaN); a null handle; a kind other than EXORL_AGENT_IQL; a handle with a captured graph (the graph
  * holds the values: disable it, set, capture again). */
 int exorl_agent_set_iql(exorl_agent_t* a, float expectile, float temperature, float max_weight);
+/* EXORL_AGENT_PRDC: bind the key table of `r`, built with this beta. Refuses another kind, a handle with a captured graph (the graph holds
+ * the table's pointer, row count and key ranges), a replay without a valid table, a table whose observation / action split is not the
+ * agent's and a table built with another beta. The number of key ranges is chosen here, from the table's rows, the batch and the CU count.
+ * exorl_agent_update, exorl_agent_update_phase, exorl_agent_enable_graph and exorl_agent_step_graph refuse, launching nothing, while no
+ * table is bound or the bound one is stale or was rebuilt; `r` must outlive the binding. */
+int exorl_agent_set_prdc(exorl_agent_t* a, exorl_replay_t* r, float beta);
+/* EXORL_AGENT_PRDC: the last search's results in the workspace, idx (batch) int32, d2 (batch) and a_nn (batch, act_dim) float32, and the
+ * number of key ranges of the bound table (0: none bound). */
+int exorl_agent_nn_result(exorl_agent_t* a, void** idx_dev, void** d2_dev, void** a_nn_dev, int32_t* splits);
 /* Policy inference for n rows: out = mean (eval) or TruncatedNormal sample (clip=None). */
 int exorl_agent_act(exorl_agent_t* a, const float* obs_dev, int32_t n, float stddev, int32_t eval_mode,
                     const float* noise_dev, float* action_out_dev, void* stream);
@@ -503,6 +538,15 @@ int exorl_ln_tanh_fwd(const float* z_dev, const float* gain_dev, const float* be
  * k <= 64; up to 4096 targets a wave holds a row of distances in LDS, above it walks the row in fixed chunks with a running top-k. */
 int exorl_knn_topk(const float* src_dev, int32_t n_src, const float* tgt_dev, int32_t n_tgt, int32_t dim,
                    int32_t k, float* out_dev, void* stream);
+/* Exact nearest neighbour of every query row among n key rows (PRDC's search on caller-made rows): keys (n, pitch) and queries (rows, q_ld)
+ * float32, the first `dim` columns of each count (dim <= 512; key columns past dim are not read as data). idx_out[i] (int32) = argmin_j d2(i, j),
+ * d2_out[i] = that minimum, d2 = sum_c (q_c - k_c)^2 in the difference form, fp32, columns ascending in one accumulator per pair: its bits do
+ * not depend on how the work is split. Ties go to the lowest key index; a query equal to a key row returns exactly 0.0. The keys are cut
+ * into `splits` contiguous ranges (0: the library's choice from n, rows and the CU count; at most 256, never an empty one), a first launch
+ * leaves one (d2, index) per (query, range) and a second merges them in range order: the results are the same bits for every value of
+ * `splits`, and no atomics are used. Library-owned scratch, grown outside captures. */
+int exorl_nn_search(const float* keys_dev, int64_t n, int32_t pitch, int32_t dim, const float* queries_dev, int64_t q_ld, int32_t rows,
+                    int32_t splits, int32_t* idx_out_dev, float* d2_out_dev, void* stream);
 /* IQL's row kernel on caller-made rows (unit test hook): tq, q (2, rows) target and critic heads, v = V(s), v_next = V(s'), reward, discount
  * (rows) in; dv (rows), dq (2, rows), w (rows) out as the step forms them (EXORL_AGENT_IQL above), and sums[10] = the sums over the rows of
  * r, y, Q_1, Q_2, (Q_1 - y)^2, (Q_2 - y)^2, k u^2, v, u, w, added per chunk in chunk order with no atomics (the same bits on every run).
