@@ -363,12 +363,40 @@ struct Carver : SimpleCarver {
 
 constexpr int ACT_ROWS = 64;
 
+// What an agent kind is, as one row of data (KINDS, behind the phase tables): every fact that more than one kind answers is read from here, so
+// a new kind is one row, its phases and its block in carve(). A direct comparison against EXORL_AGENT_* is right only where the code reaches
+// for that kind's own machinery (CQL's sample rows and scalars, APS's sf_q, CRR's value samples, PRDC's binding, the kind-only setters).
+struct PhaseTable;
+struct KindTraits {
+    int kind;                      // EXORL_AGENT_*
+    const char* name;
+    int critic_trunks;             // 0: no critic (and no target); 1: two heads on a shared trunk; 2: twin nets
+    int actor_outs;                // actor outputs per action dimension (2: CQL's mean and log-std)
+    bool sf_heads;                 // the critic's heads emit cfg.sf_dim successor features, not a scalar
+    bool value_net;                // V(s) beside the critic
+    bool draws_noise;              // update() draws (StepState::no_noise is its negation)
+    bool uses_stddev;              // a tanh-mean policy explored with the caller's stddev; false: a squashed normal with a std of its own
+    ActorLoss actor_loss;          // the form handed to the actor-step kernels
+    bool bc_nearest;               // the BC term pulls towards the searched a_nn, not the batch's action
+    bool qfuse;                    // the fused scalar-head path may run (make_step decides per call)
+    bool logs_logprob;             // phase 1 writes the log-prob of the pi(obs) sample among the metrics (ddpg.py:276,289)
+    bool evaluates;                // forward-only evaluation (exorl_agent_evaluate)
+    bool metric_window;            // exorl_agent_set_metric_window
+    const char* one_process_why;   // non-null: world_size > 1 is refused, for this reason
+    const PhaseTable* plan;
+    int (*check)(const exorl_agent_cfg&);      // the kind's own configuration checks
+    bool has_critic() const { return critic_trunks > 0; }
+    bool uses_lambda() const { return actor_loss == ACTOR_LOSS_Q_BC; }      // lambda = alpha / mean |Q| scales the Q term beside a BC term
+};
+static const KindTraits* traits_of(int kind);      // nullptr: no such kind
+
 }  // namespace exorl
 
 using namespace exorl;
 
 struct exorl_agent {
     exorl_agent_cfg cfg;
+    const KindTraits* traits = nullptr;       // cfg.kind's row (describe)
     NetDesc actor, critic, value;             // value: IQL's V(s), one Q-net without the action columns
     bool has_critic = false, has_value = false;
     bool owns_ws = false;
@@ -383,24 +411,40 @@ struct exorl_agent {
     FwdBufs fa{}, ft{}, fc{};    // actor (2B rows), target critic, critic
     BwdBufs bc{}, ba{};
     float *dq = nullptr, *da = nullptr, *dpre = nullptr, *abs_part = nullptr;
-    float *sfq = nullptr, *sftq = nullptr;           // APS: scalar Q = task . successor features of critic / target (2, B)
-    float *x_all = nullptr, *dq_all = nullptr;     // CQL: (3n+1)B critic rows and their per-row loss gradients
-    CqlScalars* cql = nullptr;                      // CQL: log_actor_alpha + Adam moments + alpha (device)
-    float *xc_rep = nullptr, *crr_w = nullptr;     // CRR: repeated (obs, sampled action) inputs; advantage weights
-    FwdBufs fr{};                                   // CRR: critic forward on B*num_value_samples rows (no grad)
-    // IQL: the value net on the stacked [next_obs; obs] rows (2B forward, B backward: the actor's arrangement), the row kernel's outputs
-    FwdBufs fv{}; BwdBufs bv{};
-    WeightImages sh_value{}; ShadowSpec spec_value{}; Partials pv{};
-    float *iql_dv = nullptr, *iql_part = nullptr;   // d L_V / d v (B); per-chunk metric sums [iql_chunks(B)][IQL_PARTS]; w goes to crr_w
-    float expectile = 0.7f, temperature = 3.0f, max_weight = 100.0f;      // exorl_agent_set_iql
-    float* fqe_part = nullptr;                      // FQE: per-chunk metric sums [iql_chunks(B)][FQE_PARTS]
-    // PRDC: the query rows [beta obs | mu(obs) | 0-pad], the search's partial minima and its results; a_nn stands where TD3+BC's actor phase
-    // reads the batch's action. The table is the replay's (exorl_agent_set_prdc): pointer, rows and key ranges are fixed while it is bound.
-    float *nn_q = nullptr, *nn_d2 = nullptr, *a_nn = nullptr, *nn_part_d2 = nullptr;
-    int *nn_idx = nullptr, *nn_part_idx = nullptr;
-    exorl_replay* prdc_replay = nullptr;
-    ReplayKeys prdc_keys{};
-    NnPlan prdc_plan{};
+    float* row_w = nullptr;      // per-row weight of the weighted log-likelihood actor step (B): CRR's weights kernel and IQL's row kernel write it
+    // ---- what one kind alone has
+    struct {
+        float *sfq = nullptr, *sftq = nullptr;       // scalar Q = task . successor features of critic / target (2, B)
+    } aps;
+    struct {
+        float *x_all = nullptr, *dq_all = nullptr;   // (3n+1)B critic rows and their per-row loss gradients
+        CqlScalars* sc = nullptr;                    // log_actor_alpha + Adam moments + alpha (device)
+    } cql;
+    struct {
+        float* xc_rep = nullptr;                     // repeated (obs, sampled action) inputs
+        FwdBufs fr{};                                // critic forward on B*num_value_samples rows (no grad)
+    } crr;
+    struct {      // the value net on the stacked [next_obs; obs] rows (2B forward, B backward: the actor's arrangement), the row kernel's outputs
+        FwdBufs fv{}; BwdBufs bv{};
+        WeightImages sh{}; ShadowSpec spec{}; Partials pv{};
+        float *dv = nullptr, *part = nullptr;        // d L_V / d v (B); per-chunk metric sums [iql_chunks(B)][IQL_PARTS]; w goes to row_w
+        float expectile = 0.7f, temperature = 3.0f, max_weight = 100.0f;      // exorl_agent_set_iql
+    } iql;
+    struct {
+        float* part = nullptr;                       // per-chunk metric sums [iql_chunks(B)][FQE_PARTS]
+        // the value pass (exorl_agent_set_fqe_value): views of the caller's buffer, [EXORL_N_FQE_VALUE double sums | pad to 256 B][iql_chunks(B) x
+        // FQE_VALUE_PARTS double partials]
+        double *value_sums = nullptr, *value_part = nullptr;
+    } fqe;
+    // the query rows [beta obs | mu(obs) | 0-pad], the search's partial minima and its results; a_nn stands where TD3+BC's actor phase reads
+    // the batch's action. The table is the replay's (exorl_agent_set_prdc): pointer, rows and key ranges are fixed while it is bound.
+    struct {
+        float *q = nullptr, *d2 = nullptr, *a_nn = nullptr, *part_d2 = nullptr;
+        int *idx = nullptr, *part_idx = nullptr;
+        exorl_replay* replay = nullptr;
+        ReplayKeys keys{};
+        NnPlan plan{};
+    } prdc;
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -438,9 +482,6 @@ struct exorl_agent {
     // EVAL_PARTS partials]
     double* eval_sums = nullptr;
     float* eval_part = nullptr;
-    // FQE's value pass (exorl_agent_set_fqe_value): views of the caller's buffer, [EXORL_N_FQE_VALUE double sums | pad to 256 B][iql_chunks(B) x
-    // FQE_VALUE_PARTS double partials]
-    double *fqe_value_sums = nullptr, *fqe_value_part = nullptr;
 };
 
 namespace exorl {
@@ -458,11 +499,7 @@ static bool planes3_ok(const exorl_agent_cfg& cfg) {
     return cfg.precision == EXORL_PREC_BF16X6 && cfg.hidden_dim % 128 == 0 && cfg.batch % 128 == 0;
 }
 
-// PRDC is TD3+BC with another BC target: wherever the step asks for lambda, the BC term or the window's bc_part it answers as TD3+BC, and the
-// kernels that take a kind are given TD3+BC's.
-static bool bc_regularised(int kind) { return kind == EXORL_AGENT_TD3_BC || kind == EXORL_AGENT_PRDC; }
-static int loss_kind(int kind) { return kind == EXORL_AGENT_PRDC ? EXORL_AGENT_TD3_BC : kind; }
-static const float* bc_target(const exorl_agent* a) { return a->cfg.kind == EXORL_AGENT_PRDC ? a->a_nn : a->action; }
+static const float* bc_target(const exorl_agent* a) { return a->traits->bc_nearest ? a->prdc.a_nn : a->action; }
 static int prdc_pitch(const exorl_agent_cfg& cfg) { return (int)round_up(cfg.obs_dim + cfg.act_dim, 4); }
 
 static void carve(exorl_agent* a, Carver& c) {
@@ -541,22 +578,22 @@ static void carve(exorl_agent* a, Carver& c) {
         three_planes(a->fc.h1q, nt * RC * H);
         three_planes(a->bc.dz2q, 2 * RC * H);
         if (cfg.kind == EXORL_AGENT_CQL) {
-            a->x_all = c.take(RC * W);
-            a->dq_all = c.take(2 * RC);
+            a->cql.x_all = c.take(RC * W);
+            a->cql.dq_all = c.take(2 * RC);
             c.scratch = false;
-            a->cql = reinterpret_cast<CqlScalars*>(c.take(16));
+            a->cql.sc = reinterpret_cast<CqlScalars*>(c.take(16));
             c.scratch = true;
         }
         a->dq = c.take(2 * B);
-        if (cfg.kind == EXORL_AGENT_APS) { a->sfq = c.take(2 * B); a->sftq = c.take(2 * B); }
+        if (cfg.kind == EXORL_AGENT_APS) { a->aps.sfq = c.take(2 * B); a->aps.sftq = c.take(2 * B); }
         a->abs_part = c.take(2 * (int64_t)qhead_chunks(B));
         a->da = c.take(nt * B * A);
         if (cfg.kind == EXORL_AGENT_CRR) {
             const int64_t R = B * cfg.num_value_samples;
-            a->xc_rep = c.take(R * W);
-            a->crr_w = c.take(B);
-            a->fr = take_fwd(nt * R, 2 * R, 1, false, nb == 0, nb);
-            three_planes(a->fr.h1q, nt * R * H);
+            a->crr.xc_rep = c.take(R * W);
+            a->row_w = c.take(B);
+            a->crr.fr = take_fwd(nt * R, 2 * R, 1, false, nb == 0, nb);
+            three_planes(a->crr.fr.h1q, nt * R * H);
         }
         c.scratch = false;
         a->sh_critic = take_shadow(nt, 2, W);
@@ -571,52 +608,47 @@ static void carve(exorl_agent* a, Carver& c) {
     if (cfg.kind == EXORL_AGENT_IQL) {          // behind everything the other kinds take: their layouts stay as they are
         for (int w = 0; w < 4; ++w) a->flat[EXORL_NET_VALUE][w] = c.take(a->value.total);
         c.scratch = true;
-        a->fv = take_fwd(2 * B, 2 * B, 1, true, true, nb);
-        a->bv = take_bwd(B, B);
-        three_planes(a->fv.h1q, 2 * B * H);
-        three_planes(a->bv.dz2q, B * H);
+        a->iql.fv = take_fwd(2 * B, 2 * B, 1, true, true, nb);
+        a->iql.bv = take_bwd(B, B);
+        three_planes(a->iql.fv.h1q, 2 * B * H);
+        three_planes(a->iql.bv.dz2q, B * H);
         c.scratch = false;
-        a->sh_value = take_shadow(1, 1, O);
-        three_planes(a->sh_value.w1, w1_plane_size(H));
+        a->iql.sh = take_shadow(1, 1, O);
+        three_planes(a->iql.sh.w1, w1_plane_size(H));
         c.scratch = true;
-        a->pv = Partials{c.take((int64_t)head_chunks(B) * (2 * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
+        a->iql.pv = Partials{c.take((int64_t)head_chunks(B) * (2 * H + 32)), c.take((int64_t)trunk_chunks(B) * 3 * H),
                          c.take((int64_t)outer_chunks(B) * O * H)};
-        a->iql_dv = c.take(B);
-        a->crr_w = c.take(B);
-        a->iql_part = c.take((int64_t)iql_chunks(B) * IQL_PARTS);
+        a->iql.dv = c.take(B);
+        a->row_w = c.take(B);
+        a->iql.part = c.take((int64_t)iql_chunks(B) * IQL_PARTS);
         c.scratch = false;
     }
     if (cfg.kind == EXORL_AGENT_FQE) {          // TD3's layout with the row kernel's partials behind it
         c.scratch = true;
-        a->fqe_part = c.take((int64_t)iql_chunks(B) * FQE_PARTS);
+        a->fqe.part = c.take((int64_t)iql_chunks(B) * FQE_PARTS);
         c.scratch = false;
     }
     if (cfg.kind == EXORL_AGENT_PRDC) {         // TD3+BC's layout with the search's buffers behind it: all written before they are read
         c.scratch = true;
-        a->nn_q = c.take(B * prdc_pitch(cfg));
-        a->nn_part_d2 = c.take((int64_t)NN_MAX_SPLITS * B);
-        a->nn_part_idx = reinterpret_cast<int*>(c.take((int64_t)NN_MAX_SPLITS * B));
-        a->nn_idx = reinterpret_cast<int*>(c.take(B));
-        a->nn_d2 = c.take(B);
-        a->a_nn = c.take(B * A);
+        a->prdc.q = c.take(B * prdc_pitch(cfg));
+        a->prdc.part_d2 = c.take((int64_t)NN_MAX_SPLITS * B);
+        a->prdc.part_idx = reinterpret_cast<int*>(c.take((int64_t)NN_MAX_SPLITS * B));
+        a->prdc.idx = reinterpret_cast<int*>(c.take(B));
+        a->prdc.d2 = c.take(B);
+        a->prdc.a_nn = c.take(B * A);
         c.scratch = false;
     }
 }
 
-static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
+// Whether the library accepts a configuration, from the configuration alone: the kind's row, the row's own checks, then what every kind asks
+// of the dimensions and the precision. The order of the refusals is the library's interface (the first failing check names the error).
+static int check_cfg(const exorl_agent_cfg* cfg) {
     EXORL_REQUIRE(cfg, "agent: null cfg");
-    EXORL_REQUIRE((cfg->kind >= EXORL_AGENT_TD3_BC && cfg->kind <= EXORL_AGENT_APS) || cfg->kind == EXORL_AGENT_IQL || cfg->kind == EXORL_AGENT_FQE ||
-                  cfg->kind == EXORL_AGENT_PRDC, "agent: unknown kind %d", cfg->kind);
-    EXORL_REQUIRE(cfg->kind != EXORL_AGENT_PRDC || cfg->world_size == 1, "agent: PRDC searches the whole dataset on every step and a rank's shard "
-                  "is not the dataset: world_size=%d is not supported for this kind", cfg->world_size);
-    EXORL_REQUIRE(cfg->kind != EXORL_AGENT_APS || (cfg->sf_dim >= 1 && cfg->sf_dim <= 16 && cfg->sf_dim < cfg->obs_dim),
-                  "agent: APS needs 1 <= sf_dim <= 16 and obs_dim = observation + sf_dim (got sf_dim=%d obs_dim=%d)", cfg->sf_dim, cfg->obs_dim);
-    EXORL_REQUIRE(cfg->kind != EXORL_AGENT_CQL || (cfg->n_samples >= 1 && cfg->n_samples <= 16 && cfg->act_dim <= 16),
-                  "agent: CQL needs 1 <= n_samples <= 16 and action_dim <= 16 (got %d, %d)", cfg->n_samples, cfg->act_dim);
-    EXORL_REQUIRE(!cfg->use_critic_lagrange || cfg->kind == EXORL_AGENT_CQL, "agent: use_critic_lagrange is a CQL option");
-    EXORL_REQUIRE(cfg->kind != EXORL_AGENT_CRR || (cfg->num_value_samples >= 1 && cfg->num_value_samples <= 64 &&
-                  cfg->weight_func >= EXORL_CRR_IDENTITY && cfg->weight_func <= EXORL_CRR_EXP),
-                  "agent: CRR needs 1 <= num_value_samples <= 64 and a valid weight_func (got %d, %d)", cfg->num_value_samples, cfg->weight_func);
+    const KindTraits* t = traits_of(cfg->kind);
+    EXORL_REQUIRE(t, "agent: unknown kind %d", cfg->kind);
+    EXORL_REQUIRE(!t->one_process_why || cfg->world_size == 1, "agent: %s: world_size=%d is not supported for this kind", t->one_process_why,
+                  cfg->world_size);
+    EXORL_TRY(t->check(*cfg));
     EXORL_REQUIRE(cfg->obs_dim > 0 && cfg->act_dim > 0 && cfg->act_dim <= 16 && cfg->hidden_dim >= 4 && cfg->hidden_dim <= 1024 && cfg->hidden_dim % 4 == 0 &&
                   cfg->obs_dim + cfg->act_dim <= 256 &&
                   cfg->batch > 0, "agent: unsupported dims O=%d A=%d (<=16) H=%d (multiple of 4, <=1024) B=%d; O+A <= 256", cfg->obs_dim, cfg->act_dim,
@@ -626,13 +658,19 @@ static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
     EXORL_REQUIRE(cfg->world_size >= 1, "agent: world_size must be >= 1");
     EXORL_REQUIRE(cfg->precision != EXORL_PREC_BF16 || (cfg->hidden_dim % 8 == 0 && cfg->batch % 8 == 0),
                   "agent: bf16 precision needs hidden_dim and batch to be multiples of 8 (got H=%d B=%d)", cfg->hidden_dim, cfg->batch);
+    return 0;
+}
+
+// Everything the handle derives from an accepted configuration: the row and the nets. carve() and every reader start from this.
+static int describe(exorl_agent* a, const exorl_agent_cfg* cfg) {
+    EXORL_TRY(check_cfg(cfg));
+    const KindTraits& t = *traits_of(cfg->kind);
     a->cfg = *cfg;
-    a->has_critic = cfg->kind != EXORL_AGENT_BC;
-    a->actor = make_net(cfg->obs_dim, cfg->kind == EXORL_AGENT_CQL ? 2 * cfg->act_dim : cfg->act_dim, cfg->hidden_dim, 1, 1);
-    if (a->has_critic)
-        a->critic = make_net(cfg->obs_dim + cfg->act_dim, cfg->kind == EXORL_AGENT_APS ? cfg->sf_dim : 1, cfg->hidden_dim,
-                             (cfg->kind == EXORL_AGENT_DDPG || cfg->kind == EXORL_AGENT_APS) ? 1 : 2, 2);
-    a->has_value = cfg->kind == EXORL_AGENT_IQL;
+    a->traits = &t;
+    a->has_critic = t.has_critic();
+    a->actor = make_net(cfg->obs_dim, t.actor_outs * cfg->act_dim, cfg->hidden_dim, 1, 1);
+    if (a->has_critic) a->critic = make_net(cfg->obs_dim + cfg->act_dim, t.sf_heads ? cfg->sf_dim : 1, cfg->hidden_dim, t.critic_trunks, 2);
+    a->has_value = t.value_net;
     if (a->has_value) a->value = make_net(cfg->obs_dim, 1, cfg->hidden_dim, 1, 1);
     a->inv_bg = 1.0f / ((float)cfg->batch * (float)cfg->world_size);
     return 0;
@@ -682,7 +720,7 @@ static bool has_net(const exorl_agent* a, int net) {
 static NetView net_view(exorl_agent* a, int net) {
     switch (net) {
         case EXORL_NET_ACTOR: return NetView{a->actor, a->flat[net], a->sh_actor, a->pa, a->ba, a->pend_a, a->spec_actor};
-        case EXORL_NET_VALUE: return NetView{a->value, a->flat[net], a->sh_value, a->pv, a->bv, a->pend_v, a->spec_value};
+        case EXORL_NET_VALUE: return NetView{a->value, a->flat[net], a->iql.sh, a->iql.pv, a->iql.bv, a->pend_v, a->iql.spec};
         case EXORL_NET_CRITIC_TARGET: return NetView{a->critic, a->flat[net], a->sh_target, a->pc, a->bc, a->pend_c, a->spec_critic};
         default: return NetView{a->critic, a->flat[net], a->sh_critic, a->pc, a->bc, a->pend_c, a->spec_critic};
     }
@@ -709,13 +747,13 @@ struct Step {
 };
 static Step make_step(const exorl_agent* a, hipStream_t s, float stddev, const float* noise_c, const float* noise_a, bool whole, bool capture,
                       bool staged, bool fork) {
-    const int kind = a->cfg.kind;
+    const KindTraits& k = *a->traits;
     Step st{s, stddev, noise_c, noise_a, whole, capture, staged, Fork(a->fk, fork)};
     st.fuse_opt = whole && !a->comm && !fork;
-    st.qfuse = whole && !fork && (!a->want_metrics || a->win_sums) && a->has_critic && a->critic.n_heads == 2 && a->critic.out_dim == 1 &&
-               a->cfg.hidden_dim % 4 == 0 && (bc_regularised(kind) || kind == EXORL_AGENT_TD3 || kind == EXORL_AGENT_DDPG);
+    st.qfuse = whole && !fork && (!a->want_metrics || a->win_sums) && k.qfuse && a->critic.n_heads == 2 && a->critic.out_dim == 1 &&
+               a->cfg.hidden_dim % 4 == 0;
     st.metric_kernels = a->win_sums ? !st.qfuse : a->want_metrics;
-    st.stats_in_phase2 = st.qfuse && a->comm && bc_regularised(kind);
+    st.stats_in_phase2 = st.qfuse && a->comm && k.uses_lambda();
     return st;
 }
 
@@ -784,9 +822,9 @@ static int net_grads_from(const exorl_agent* a, const Step& st, const NetView& n
 }
 
 // The actor's gradients on the obs half (rows B..2B of the stacked buffers) from d L / d mu: the forward where the step has not run it, the
-// actor_loss metric kernel, the backward pass. kind: whose gradient form (TD3+BC's, BC's, CRR's weighted log-likelihood, else the critic's da
+// actor_loss metric kernel, the backward pass. form: the loss's (Q + BC, BC, weighted log-likelihood, else the critic's da
 // alone); da_nets: how many slabs of a->da add up. dm: the caller's additions (phase 2's fused path); the common fields are set here.
-static int actor_mu_step(exorl_agent* a, const Step& st, bool forward, int kind, int da_nets, const float* reward, DoutSpec dm) {
+static int actor_mu_step(exorl_agent* a, const Step& st, bool forward, ActorLoss form, int da_nets, const float* reward, DoutSpec dm) {
     const auto& cfg = a->cfg;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim;
     const NetView n = net_view(a, EXORL_NET_ACTOR);
@@ -794,10 +832,10 @@ static int actor_mu_step(exorl_agent* a, const Step& st, bool forward, int kind,
     const FwdBufs f = a->fa.rows_from(B, cfg.hidden_dim, A);
     if (forward) EXORL_TRY(net_forward(n.d, n.P(), n.sh, x, O, B, f, true, true, cfg.precision, st.s));
     if (st.metric_kernels)                      // actor_loss / batch_reward(BC) metrics only (the gradient is formed in head_bwd)
-        EXORL_TRY(actor_dmu(a->da, A, da_nets, (int64_t)B * A, f.out, bc_target(a), reward, a->crr_w, a->dpre, a->stats, a->metrics, B, A,
-                            a->inv_bg, cfg.alpha, kind, st.stddev, st.s, &a->state->stddev));
+        EXORL_TRY(actor_dmu(a->da, A, da_nets, (int64_t)B * A, f.out, bc_target(a), reward, a->row_w, a->dpre, a->stats, a->metrics, B, A,
+                            a->inv_bg, cfg.alpha, form, st.stddev, st.s, &a->state->stddev));
     dm.mode = EXORL_DOUT_ACTOR_MU; dm.da = da_nets ? a->da : nullptr; dm.da_nets = da_nets; dm.mu = f.out; dm.a_data = bc_target(a);
-    dm.kind = kind; dm.inv_bg = a->inv_bg; dm.stddev = st.stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->crr_w;
+    dm.form = form; dm.inv_bg = a->inv_bg; dm.stddev = st.stddev; dm.stddev_ptr = &a->state->stddev; dm.w = a->row_w;
     return net_grads(a, st, n, x, B, f, dm);
 }
 
@@ -811,8 +849,8 @@ static int run_metrics_window(exorl_agent* a, const Step& st) {
     MetricsWindowArgs w{};
     w.fused = st.qfuse ? 1 : 0;
     w.crit_part = a->win_crit; w.abs_part = a->abs_part; w.bc_part = a->win_bc;
-    w.q_chunks = qhead_chunks(B); w.bc_chunks = bc_regularised(a->cfg.kind) ? head_chunks(B) : 0;
-    w.kind = loss_kind(a->cfg.kind); w.act_dim = a->cfg.act_dim; w.ent_from_std = a->cfg.kind != EXORL_AGENT_CQL;
+    w.q_chunks = qhead_chunks(B); w.bc_chunks = a->traits->uses_lambda() ? head_chunks(B) : 0;
+    w.form = a->traits->actor_loss; w.act_dim = a->cfg.act_dim; w.ent_from_std = a->traits->uses_stddev;
     w.inv_bg = a->inv_bg; w.alpha = a->cfg.alpha; w.stddev = &a->state->stddev;
     w.metrics = a->metrics; w.sums = a->win_sums; w.steps = a->win_steps;
     return metrics_window(w, st.s);
@@ -868,9 +906,9 @@ static int phase0(exorl_agent* a, const Step& st) {
     const float* task = aps ? a->obs + (O - cfg.sf_dim) : nullptr;          // obs rows are [observation | task] (aps.py:236-238)
     const float *qv = a->fc.out, *tqv = a->ft.out;
     if (aps) {                                  // Q = task . successor features (aps.py:55-58)
-        EXORL_TRY(sf_q(a->ft.out, task, O, a->sftq, B, cfg.sf_dim, 2, s));
-        EXORL_TRY(sf_q(a->fc.out, task, O, a->sfq, B, cfg.sf_dim, 2, s));
-        qv = a->sfq; tqv = a->sftq;
+        EXORL_TRY(sf_q(a->ft.out, task, O, a->aps.sftq, B, cfg.sf_dim, 2, s));
+        EXORL_TRY(sf_q(a->fc.out, task, O, a->aps.sfq, B, cfg.sf_dim, 2, s));
+        qv = a->aps.sfq; tqv = a->aps.sftq;
     }
     if (st.metric_kernels)
         EXORL_TRY(critic_loss(qv, tqv, a->reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));   // :133-137
@@ -892,22 +930,22 @@ static int phase1(exorl_agent* a, const Step& st) {
         const int n = cfg.num_value_samples;
         const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
         EXORL_TRY(repeat_sample(a->obs, a->fa.out + (int64_t)B * A, noise_a, cfg.seed, noise_a ? nullptr : &a->state->noise_counter, 1,
-                                stddev, cfg.stddev_clip, a->xc_rep, B, O, A, n, s, &a->state->stddev));
-        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_rep, W, B * n, a->fr, false, false, prec, s));      // compute_value
+                                stddev, cfg.stddev_clip, a->crr.xc_rep, B, O, A, n, s, &a->state->stddev));
+        EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->crr.xc_rep, W, B * n, a->crr.fr, false, false, prec, s));      // compute_value
         EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->xc_cur, W, B, a->fc, false, false, prec, s));          // Q(s, a_data)
-        EXORL_TRY(crr_weights(a->fr.out, a->fc.out, a->crr_w, B, n, cfg.weight_func, s));
+        EXORL_TRY(crr_weights(a->crr.fr.out, a->fc.out, a->row_w, B, n, cfg.weight_func, s));
         return 0;
     }
     // pi(obs) sample already sits in xc_pi (phase 0); DDPG logs its log-prob (ddpg.py:276,289)
-    if ((cfg.kind == EXORL_AGENT_DDPG || cfg.kind == EXORL_AGENT_APS) && (a->want_metrics || a->win_sums))
+    if (a->traits->logs_logprob && (a->want_metrics || a->win_sums))
         EXORL_TRY(sample_action(a->fa.out + (int64_t)B * A, noise_spec(a, noise_a, 1), stddev, cfg.stddev_clip, 1, a->xc_pi + O, W, B, A,
                                 a->metrics + EXORL_M_ACTOR_LOGPROB, s, &a->state->stddev, cfg.world_size));
     const bool qf = st.qfuse;
     EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->xc_pi, W, B, a->fc, true, false, prec, s,
                           nullptr, qf));
     if (cfg.kind == EXORL_AGENT_APS) {
-        EXORL_TRY(sf_q(a->fc.out, a->obs + (O - cfg.sf_dim), O, a->sfq, B, cfg.sf_dim, 2, s));
-        EXORL_TRY(actor_stats(a->sfq, a->stats, B, s));
+        EXORL_TRY(sf_q(a->fc.out, a->obs + (O - cfg.sf_dim), O, a->aps.sfq, B, cfg.sf_dim, 2, s));
+        EXORL_TRY(actor_stats(a->aps.sfq, a->stats, B, s));
     } else if (!qf) {
         EXORL_TRY(actor_stats(a->fc.out, a->stats, B, s));
     }
@@ -923,8 +961,8 @@ static int phase2(exorl_agent* a, const Step& st) {
     if (a->has_critic && cfg.kind != EXORL_AGENT_CRR) {
         DoutSpec dq{};                          // -lambda/Bg routed to the smaller Q (td3_bc.py:152-155)
         dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.alpha = cfg.alpha;
-        if (cfg.kind == EXORL_AGENT_APS) { dq.q = a->sfq; dq.task = a->obs + (O - cfg.sf_dim); dq.task_ld = O; }
-        dq.use_lambda = bc_regularised(cfg.kind);
+        if (cfg.kind == EXORL_AGENT_APS) { dq.q = a->aps.sfq; dq.task = a->obs + (O - cfg.sf_dim); dq.task_ld = O; }
+        dq.use_lambda = a->traits->uses_lambda();
         if (qf) EXORL_TRY(run_qhead(a, st, 1, 0));   // Q(s, pi(s)), its min-routing gradient (lambda applied later), dz2, sum|Q| partials
         if (st.stats_in_phase2) {                // lambda needs sum|Q| over the GLOBAL batch (td3_bc.py:154): reduce it while the critic's
             EXORL_TRY(reduce_pairs(a->abs_part, qhead_chunks(B), a->stats, s));          // backward pass runs (it does not depend on lambda)
@@ -938,15 +976,15 @@ static int phase2(exorl_agent* a, const Step& st) {
     }
     DoutSpec dm{};
     if (qf) {                                   // lambda = alpha / mean|Q| from the per-chunk sums qhead left behind
-        dm.lam_parts = a->abs_part; dm.lam_chunks = qhead_chunks(B); dm.use_lambda = bc_regularised(cfg.kind); dm.alpha = cfg.alpha;
+        dm.lam_parts = a->abs_part; dm.lam_chunks = qhead_chunks(B); dm.use_lambda = a->traits->uses_lambda(); dm.alpha = cfg.alpha;
         if (st.stats_in_phase2) {                // the all-reduced statistic (one 'chunk': stats[0] = global sum |Q|)
             EXORL_CHECK_HIP(hipStreamWaitEvent(s, a->ev_stats_done, 0));
             dm.lam_parts = a->stats; dm.lam_chunks = 1;
         }
-        if (a->win_sums && bc_regularised(cfg.kind)) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
+        if (a->win_sums && a->traits->uses_lambda()) dm.bc_part = a->win_bc;       // head_bwd's metrics variant: actor_loss's (mu - a)^2 term
     }
     // BC (bc.py:82) runs its only forward here; the other kinds' is the obs half of phase 0's stacked pass
-    return actor_mu_step(a, st, !a->has_critic, loss_kind(cfg.kind), a->has_critic ? a->critic.n_trunks : 0, a->has_critic ? nullptr : a->reward, dm);
+    return actor_mu_step(a, st, !a->has_critic, a->traits->actor_loss, a->has_critic ? a->critic.n_trunks : 0, a->has_critic ? nullptr : a->reward, dm);
 }
 
 static int phase3(exorl_agent* a, const Step& st) {
@@ -975,13 +1013,13 @@ static int cql_phase0a(exorl_agent* a, const Step& st, bool split) {
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
     EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, true, false, prec, s));      // raw (mu | log_std) on [next_obs; obs]
-    EXORL_TRY(cql_build_inputs(a->obs, a->action, a->fa.out, cql_noise(a, st), a->xc_next, a->x_all, B, O, A, n, s));
+    EXORL_TRY(cql_build_inputs(a->obs, a->action, a->fa.out, cql_noise(a, st), a->xc_next, a->cql.x_all, B, O, A, n, s));
     EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC_TARGET][EXORL_T_PARAM], a->sh_target, a->xc_next, W, B, a->ft, false, false,
                           prec, s));                                                                     // cql.py:160
-    EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->x_all, W, R, a->fc, true, false, prec, s));     // cql.py:166,179-184 in one pass
+    EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->cql.x_all, W, R, a->fc, true, false, prec, s));     // cql.py:166,179-184 in one pass
     if (split)      // this rank's penalty sums into stats[2], stats[3]
-        EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
-                                a->cql + 1, &a->state->critic, cfg.target_cql_penalty, 1, a->stats + 2));
+        EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->cql.dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
+                                a->cql.sc + 1, &a->state->critic, cfg.target_cql_penalty, 1, a->stats + 2));
     return 0;
 }
 
@@ -989,9 +1027,9 @@ static int cql_phase0b(exorl_agent* a, const Step& st, bool split) {
     const auto& cfg = a->cfg;
     hipStream_t s = st.s;
     const int B = cfg.batch, n = cfg.n_samples;
-    EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
-                            cfg.use_critic_lagrange ? a->cql + 1 : nullptr, &a->state->critic, cfg.target_cql_penalty, split ? 2 : 0, a->stats + 2));
-    return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->x_all, (3 * n + 1) * B, a->fc, a->dq_all);
+    EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->cql.dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
+                            cfg.use_critic_lagrange ? a->cql.sc + 1 : nullptr, &a->state->critic, cfg.target_cql_penalty, split ? 2 : 0, a->stats + 2));
+    return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->cql.x_all, (3 * n + 1) * B, a->fc, a->cql.dq_all);
 }
 
 static int cql_phase0(exorl_agent* a, const Step& st) {
@@ -1018,7 +1056,7 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
     hipStream_t s = st.s;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
-    EXORL_TRY(cql_alpha_step(a->cql, a->stats, &a->state->actor, a->metrics, B, A, a->inv_bg, a->fc.out, s));    // cql.py:241-247
+    EXORL_TRY(cql_alpha_step(a->cql.sc, a->stats, &a->state->actor, a->metrics, B, A, a->inv_bg, a->fc.out, s));    // cql.py:241-247
     DoutSpec dq{};
     dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.use_lambda = 0;
     EXORL_TRY(net_backward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, nullptr, a->pc, a->xc_pi, W, B, a->fc, dq,
@@ -1026,7 +1064,7 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
     const FwdBufs f = a->fa.rows_from(B, H, 2 * A);
     DoutSpec dm{};
     dm.mode = EXORL_DOUT_CQL_ACTOR; dm.da = a->da; dm.da_nets = a->critic.n_trunks; dm.raw = f.out; dm.z = st.noise_a;
-    dm.alpha_ptr = &a->cql->alpha; dm.inv_bg = a->inv_bg; dm.seed = cfg.seed; dm.counter = 4; dm.counter_ptr = &a->state->noise_counter;
+    dm.alpha_ptr = &a->cql.sc->alpha; dm.inv_bg = a->inv_bg; dm.seed = cfg.seed; dm.counter = 4; dm.counter_ptr = &a->state->noise_counter;
     return net_grads(a, st, net_view(a, EXORL_NET_ACTOR), a->xa + (int64_t)B * O, B, f, dm);
 }
 
@@ -1035,7 +1073,7 @@ static int cql_phase2(exorl_agent* a, const Step& st) {
 // optimiser steps, which all come last. Nothing is drawn. Phases 6..9:
 //   6  Q'(s, a), Q(s, a), V on [s'; s] (one 2B-row pass), the row kernel (dv, dq, w, metric partials), value backward on the s rows -> value grads
 //   7  critic backward from dq -> critic grads
-//   8  actor forward on s and the weighted log-likelihood backward (CRR's actor path with w) -> actor grads
+//   8  actor forward on s and the weighted log-likelihood backward (w from the row kernel) -> actor grads
 //   9  Adam on value, critic (Polyak target fused into its pass) and actor
 static int iql_phase6(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
@@ -1044,21 +1082,21 @@ static int iql_phase6(exorl_agent* a, const Step& st) {
     EXORL_TRY(open_step(a, &st, s));
     const NetView v = net_view(a, EXORL_NET_VALUE);
     EXORL_TRY(twin_forward(a, s, st.fk, a->xc_cur, true));      // the target's and the critic's forwards on (s, a)
-    EXORL_TRY(net_forward(v.d, v.P(), v.sh, a->xa, O, 2 * B, a->fv, true, false, cfg.precision, s));      // rows 0..B-1: V(s'), B..2B-1: V(s)
-    IqlRowsArgs r{a->ft.out, a->fc.out, a->fv.out + B, a->fv.out, a->reward, a->discount, a->iql_dv, a->dq, a->crr_w, a->iql_part, B,
-                  a->inv_bg, a->expectile, a->temperature, a->max_weight};
+    EXORL_TRY(net_forward(v.d, v.P(), v.sh, a->xa, O, 2 * B, a->iql.fv, true, false, cfg.precision, s));      // rows 0..B-1: V(s'), B..2B-1: V(s)
+    IqlRowsArgs r{a->ft.out, a->fc.out, a->iql.fv.out + B, a->iql.fv.out, a->reward, a->discount, a->iql.dv, a->dq, a->row_w, a->iql.part, B,
+                  a->inv_bg, a->iql.expectile, a->iql.temperature, a->iql.max_weight};
     EXORL_TRY(iql_rows(r, s));
-    if (st.metric_kernels) EXORL_TRY(iql_sums(a->iql_part, B, a->inv_bg, nullptr, a->metrics, s));
-    return net_grads_from(a, st, v, a->xa + (int64_t)B * O, B, a->fv.rows_from(B, H, 1), a->iql_dv);
+    if (st.metric_kernels) EXORL_TRY(iql_sums(a->iql.part, B, a->inv_bg, nullptr, a->metrics, s));
+    return net_grads_from(a, st, v, a->xa + (int64_t)B * O, B, a->iql.fv.rows_from(B, H, 1), a->iql.dv);
 }
 
 static int iql_phase7(exorl_agent* a, const Step& st) {
     return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, a->cfg.batch, a->fc, a->dq);
 }
 
-// the obs half, as BC runs it: the only actor forward of the step. actor_loss = -(w * log N(a; mu, std)).mean(): CRR's metric and gradient
-// with IQL's weights (the row kernel left them in crr_w)
-static int iql_phase8(exorl_agent* a, const Step& st) { return actor_mu_step(a, st, true, EXORL_AGENT_CRR, 0, nullptr, DoutSpec{}); }
+// the obs half, as BC runs it: the only actor forward of the step. actor_loss = -(w * log N(a; mu, std)).mean(): the weighted
+// log-likelihood form with IQL's weights (the row kernel left them in row_w)
+static int iql_phase8(exorl_agent* a, const Step& st) { return actor_mu_step(a, st, true, a->traits->actor_loss, 0, nullptr, DoutSpec{}); }
 
 static int iql_phase9(exorl_agent* a, const Step& st) {
     // the value net steps with the critic (one step count, exorl_agent_opt_steps): it reads the critic's Adam scalars and has no target
@@ -1081,9 +1119,9 @@ static int fqe_phase10(exorl_agent* a, const Step& st) {
     EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa, O, B, a->fa, false, true, cfg.precision, s));
     EXORL_TRY(fqe_mean_actions(a->fa.out, a->xc_next + O, W, B, A, s));
     EXORL_TRY(twin_forward(a, s, st.fk, a->xc_next, true));      // the target's forward on (s', mu(s')) and the critic's on (s, a)
-    FqeRowsArgs r{a->ft.out, a->fc.out, a->reward, a->discount, a->dq, a->fqe_part, B, a->inv_bg};
+    FqeRowsArgs r{a->ft.out, a->fc.out, a->reward, a->discount, a->dq, a->fqe.part, B, a->inv_bg};
     EXORL_TRY(fqe_rows(r, s));
-    if (st.metric_kernels) EXORL_TRY(fqe_sums(a->fqe_part, B, a->inv_bg, nullptr, a->metrics, s));
+    if (st.metric_kernels) EXORL_TRY(fqe_sums(a->fqe.part, B, a->inv_bg, nullptr, a->metrics, s));
     return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, B, a->fc, a->dq);
 }
 
@@ -1095,23 +1133,23 @@ static int fqe_phase11(exorl_agent* a, const Step& st) { return opt_step_critic(
 // nn_dist where the step's metrics are read. a_nn is a constant of the actor step: nothing flows back through the search.
 static int prdc_bound(const exorl_agent* a, const char* who) {
     if (a->cfg.kind != EXORL_AGENT_PRDC) return 0;
-    EXORL_REQUIRE(a->prdc_replay, "%s: no key table bound (exorl_replay_build_keys, then exorl_agent_set_prdc)", who);
-    const ReplayKeys k = replay_keys(a->prdc_replay);
-    EXORL_REQUIRE(k.valid && k.epoch == a->prdc_keys.epoch, "%s: the bound key table is stale: the arena, its order or its normaliser changed, or "
+    EXORL_REQUIRE(a->prdc.replay, "%s: no key table bound (exorl_replay_build_keys, then exorl_agent_set_prdc)", who);
+    const ReplayKeys k = replay_keys(a->prdc.replay);
+    EXORL_REQUIRE(k.valid && k.epoch == a->prdc.keys.epoch, "%s: the bound key table is stale: the arena, its order or its normaliser changed, or "
                   "the table was rebuilt (exorl_replay_build_keys and exorl_agent_set_prdc again)", who);
     return 0;
 }
 static int prdc_phase12(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, pitch = prdc_pitch(cfg);      // every driver has checked the binding (prdc_bound)
-    EXORL_TRY(nn_query(a->obs, a->fa.out + (int64_t)B * A, a->prdc_keys.beta, B, O, A, pitch, a->nn_q, st.s));
+    EXORL_TRY(nn_query(a->obs, a->fa.out + (int64_t)B * A, a->prdc.keys.beta, B, O, A, pitch, a->prdc.q, st.s));
     NnSearch n{};
-    n.keys = a->prdc_keys.ptr; n.n = (int)a->prdc_keys.n; n.pitch = pitch; n.dim = O + A;
-    n.q = a->nn_q; n.q_ld = pitch; n.rows = B; n.plan = a->prdc_plan;
-    n.part_d2 = a->nn_part_d2; n.part_idx = a->nn_part_idx; n.idx_out = a->nn_idx; n.d2_out = a->nn_d2;
-    n.a_nn = a->a_nn; n.act_col0 = O; n.act_dim = A;
+    n.keys = a->prdc.keys.ptr; n.n = (int)a->prdc.keys.n; n.pitch = pitch; n.dim = O + A;
+    n.q = a->prdc.q; n.q_ld = pitch; n.rows = B; n.plan = a->prdc.plan;
+    n.part_d2 = a->prdc.part_d2; n.part_idx = a->prdc.part_idx; n.idx_out = a->prdc.idx; n.d2_out = a->prdc.d2;
+    n.a_nn = a->prdc.a_nn; n.act_col0 = O; n.act_dim = A;
     EXORL_TRY(nn_search(n, st.s));
-    if (st.metric_kernels) EXORL_TRY(nn_dist(a->nn_d2, B, a->inv_bg, a->metrics + EXORL_M_NN_DIST, st.s));
+    if (st.metric_kernels) EXORL_TRY(nn_dist(a->prdc.d2, B, a->inv_bg, a->metrics + EXORL_M_NN_DIST, st.s));
     return 0;
 }
 
@@ -1173,11 +1211,54 @@ static const PhaseRow PRDC_ROWS[] = {         // TD3+BC's with the search behind
 };
 template <int N>
 static constexpr PhaseTable phase_rows(const char* owner, const char* ids, const PhaseRow (&rows)[N]) { return PhaseTable{owner, ids, rows, N}; }
-static const PhaseTable PHASE_TABLES[] = {phase_rows("the DDPG family", "0..3", DDPG_ROWS), phase_rows("CQL", "0..5", CQL_ROWS),
-                                          phase_rows("IQL", "6..9", IQL_ROWS), phase_rows("FQE", "10, 11", FQE_ROWS),
-                                          phase_rows("PRDC", "0..3, 12", PRDC_ROWS)};
-static const PhaseTable& phase_table(int kind) {
-    return PHASE_TABLES[kind == EXORL_AGENT_CQL ? 1 : kind == EXORL_AGENT_IQL ? 2 : kind == EXORL_AGENT_FQE ? 3 : kind == EXORL_AGENT_PRDC ? 4 : 0];
+static const PhaseTable DDPG_PLAN = phase_rows("the DDPG family", "0..3", DDPG_ROWS), CQL_PLAN = phase_rows("CQL", "0..5", CQL_ROWS),
+                        IQL_PLAN = phase_rows("IQL", "6..9", IQL_ROWS), FQE_PLAN = phase_rows("FQE", "10, 11", FQE_ROWS),
+                        PRDC_PLAN = phase_rows("PRDC", "0..3, 12", PRDC_ROWS);
+
+// ---- the kinds ----------------------------------------------------------------------------------------
+// A kind's own configuration checks (KindTraits::check). use_critic_lagrange is refused for every kind but CQL; it sits in these functions, not
+// in check_cfg, because its place among a kind's refusals is part of the interface: behind APS's check, in front of CRR's.
+static int check_plain(const exorl_agent_cfg& c) {
+    EXORL_REQUIRE(!c.use_critic_lagrange, "agent: use_critic_lagrange is a CQL option");
+    return 0;
+}
+static int check_aps(const exorl_agent_cfg& c) {
+    EXORL_REQUIRE(c.sf_dim >= 1 && c.sf_dim <= 16 && c.sf_dim < c.obs_dim,
+                  "agent: APS needs 1 <= sf_dim <= 16 and obs_dim = observation + sf_dim (got sf_dim=%d obs_dim=%d)", c.sf_dim, c.obs_dim);
+    return check_plain(c);
+}
+static int check_cql(const exorl_agent_cfg& c) {
+    EXORL_REQUIRE(c.n_samples >= 1 && c.n_samples <= 16 && c.act_dim <= 16, "agent: CQL needs 1 <= n_samples <= 16 and action_dim <= 16 (got %d, %d)",
+                  c.n_samples, c.act_dim);
+    return 0;
+}
+static int check_crr(const exorl_agent_cfg& c) {
+    EXORL_TRY(check_plain(c));
+    EXORL_REQUIRE(c.num_value_samples >= 1 && c.num_value_samples <= 64 && c.weight_func >= EXORL_CRR_IDENTITY && c.weight_func <= EXORL_CRR_EXP,
+                  "agent: CRR needs 1 <= num_value_samples <= 64 and a valid weight_func (got %d, %d)", c.num_value_samples, c.weight_func);
+    return 0;
+}
+constexpr ActorLoss Q_BC = ACTOR_LOSS_Q_BC, Q = ACTOR_LOSS_Q, BC = ACTOR_LOSS_BC, WLL = ACTOR_LOSS_WLL;
+static const char PRDC_ONE_PROCESS[] = "PRDC searches the whole dataset on every step and a rank's shard is not the dataset";
+// Columns as KindTraits declares them. FQE's actor is frozen: its loss form is never read. Ids 7 and 10 are not agents of this library.
+static const KindTraits KINDS[] = {
+    //                             critic actor sf     value  draws  uses          bc             logs           metric one
+    // kind              name      trunks outs  heads  net    noise  stddev loss   nearest qfuse  logprob eval   window process           plan        check
+    {EXORL_AGENT_TD3_BC, "TD3+BC", 2,     1,    false, false, true,  true,  Q_BC,  false,  true,  false,  true,  true,  nullptr,          &DDPG_PLAN, check_plain},
+    {EXORL_AGENT_TD3,    "TD3",    2,     1,    false, false, true,  true,  Q,     false,  true,  false,  true,  true,  nullptr,          &DDPG_PLAN, check_plain},
+    {EXORL_AGENT_BC,     "BC",     0,     1,    false, false, true,  true,  BC,    false,  false, false,  true,  true,  nullptr,          &DDPG_PLAN, check_plain},
+    {EXORL_AGENT_DDPG,   "DDPG",   1,     1,    false, false, true,  true,  Q,     false,  true,  true,   false, true,  nullptr,          &DDPG_PLAN, check_plain},
+    {EXORL_AGENT_CRR,    "CRR",    2,     1,    false, false, true,  true,  WLL,   false,  false, false,  true,  true,  nullptr,          &DDPG_PLAN, check_crr},
+    {EXORL_AGENT_CQL,    "CQL",    2,     2,    false, false, true,  false, Q,     false,  false, false,  true,  true,  nullptr,          &CQL_PLAN,  check_cql},
+    {EXORL_AGENT_APS,    "APS",    1,     1,    true,  false, true,  true,  Q,     false,  false, true,   false, true,  nullptr,          &DDPG_PLAN, check_aps},
+    {EXORL_AGENT_IQL,    "IQL",    2,     1,    false, true,  false, true,  WLL,   false,  false, false,  false, false, nullptr,          &IQL_PLAN,  check_plain},
+    {EXORL_AGENT_FQE,    "FQE",    2,     1,    false, false, false, true,  Q,     false,  false, false,  false, false, nullptr,          &FQE_PLAN,  check_plain},
+    {EXORL_AGENT_PRDC,   "PRDC",   2,     1,    false, false, true,  true,  Q_BC,  true,   true,  false,  false, false, PRDC_ONE_PROCESS, &PRDC_PLAN, check_plain},
+};
+static const KindTraits* traits_of(int kind) {
+    for (const KindTraits& k : KINDS)
+        if (k.kind == kind) return &k;
+    return nullptr;
 }
 static const PhaseRow* find_phase(const PhaseTable& t, int id) {
     for (int i = 0; i < t.n; ++i)
@@ -1190,13 +1271,14 @@ struct AgentPlan {
     int phase[6], xchg[6];         // xchg: the exchange that follows the phase, or -1
 };
 static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_phase2) {
-    const bool split = dp && c.kind == EXORL_AGENT_CQL && c.use_critic_lagrange;
-    const PhaseTable& t = phase_table(c.kind);
+    const KindTraits& k = *traits_of(c.kind);
+    const bool split = dp && c.use_critic_lagrange;      // a CQL option (check_cfg): the only table with IF_SPLIT rows
+    const PhaseTable& t = *k.plan;
     AgentPlan p;
     for (int i = 0; i < t.n; ++i) {
         const PhaseRow& r = t.rows[i];
         if (r.rule == (split ? UNLESS_SPLIT : IF_SPLIT)) continue;
-        const bool on = r.rule == IF_CRITIC ? c.kind != EXORL_AGENT_BC : r.rule == IF_LAMBDA ? bc_regularised(c.kind) && !stats_in_phase2 : true;
+        const bool on = r.rule == IF_CRITIC ? k.has_critic() : r.rule == IF_LAMBDA ? k.uses_lambda() && !stats_in_phase2 : true;
         p.phase[p.n] = r.id;
         p.xchg[p.n++] = dp && on ? r.xchg : -1;
     }
@@ -1204,11 +1286,11 @@ static AgentPlan agent_plan(const exorl_agent_cfg& c, bool dp, bool stats_in_pha
 }
 
 static int run_phase(exorl_agent* a, const Step& st, int phase) {
-    const PhaseTable& t = phase_table(a->cfg.kind);
+    const PhaseTable& t = *a->traits->plan;
     if (const PhaseRow* r = find_phase(t, phase)) return r->fn(a, st);
-    const PhaseTable* owner = nullptr;       // whose phase it is, if anybody's
-    for (const PhaseTable& o : PHASE_TABLES)
-        if (!owner && find_phase(o, phase)) owner = &o;
+    const PhaseTable* owner = nullptr;       // whose phase it is, if anybody's: the first table in kind order that has it
+    for (const KindTraits& k : KINDS)
+        if (!owner && find_phase(*k.plan, phase)) owner = k.plan;
     if (owner)
         set_error("agent_update_phase: phase %d out of range for kind %d: it is not one of %s's (%s, exorl_agent_update_plan); phase %d is %s's",
                   phase, a->cfg.kind, t.owner, t.ids, phase, owner->owner);
@@ -1232,8 +1314,8 @@ static Exchange exchange_of(exorl_agent* a, int xid) {
 // the kernels read the exploration std from the device step state; enqueue a new value only when the schedule moved (a captured graph is
 // std-agnostic: exorl_agent_step_graph writes it before the launch)
 static int push_stddev(exorl_agent* a, const char* who, float stddev, hipStream_t s) {
-    EXORL_REQUIRE(stddev > 0.f || a->cfg.kind == EXORL_AGENT_CQL, "%s: stddev must be > 0", who);
-    if (a->cfg.kind != EXORL_AGENT_CQL && stddev != a->dev_stddev) {
+    EXORL_REQUIRE(stddev > 0.f || !a->traits->uses_stddev, "%s: stddev must be > 0", who);
+    if (a->traits->uses_stddev && stddev != a->dev_stddev) {
         EXORL_TRY(set_device_float(&a->state->stddev, stddev, s));
         a->dev_stddev = stddev;
     }
@@ -1326,13 +1408,13 @@ int exorl_agent_create(const exorl_agent_cfg* cfg, void* workspace, size_t works
     carve(a, c);
     a->spec_actor = shadow_spec(a->actor, a->sh_actor, nullptr);
     if (a->has_critic) a->spec_critic = shadow_spec(a->critic, a->sh_critic, &a->sh_target);
-    if (a->has_value) a->spec_value = shadow_spec(a->value, a->sh_value, nullptr);
+    if (a->has_value) a->iql.spec = shadow_spec(a->value, a->iql.sh, nullptr);
     StepState st{};
     st.lr = dec7(cfg->lr); st.b1 = 0.9; st.b2 = 0.999; st.eps = 1e-8; st.tau = dec7(cfg->tau);      // torch.optim.Adam defaults
     st.has_critic = a->has_critic ? 1 : 0;
-    st.no_noise = (cfg->kind == EXORL_AGENT_IQL || cfg->kind == EXORL_AGENT_FQE) ? 1 : 0;
+    st.no_noise = a->traits->draws_noise ? 0 : 1;
     st.b1t = st.b2t = st.b1t_c = st.b2t_c = 1.0;
-    if (a->cql) { CqlScalars sc{0.f, 0.f, 0.f, 1.0f}; (void)hipMemcpy(a->cql, &sc, sizeof(sc), hipMemcpyHostToDevice); }
+    if (a->cql.sc) { CqlScalars sc{0.f, 0.f, 0.f, 1.0f}; (void)hipMemcpy(a->cql.sc, &sc, sizeof(sc), hipMemcpyHostToDevice); }
     e = hipMemcpy(a->state, &st, sizeof(st), hipMemcpyHostToDevice);
     if (e != hipSuccess) { set_error("agent_create: state upload -> %s", hipGetErrorString(e)); if (a->owns_ws) (void)hipFree(a->ws); delete a; return 1; }
     *out = a;
@@ -1396,8 +1478,8 @@ int exorl_agent_params_changed(exorl_agent_t* a, int32_t sync_target, void* stre
     }
     EXORL_TRY(refresh_w1_planes(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, s));
     if (a->has_value) {
-        EXORL_TRY(refresh_shadows(a->flat[EXORL_NET_VALUE][EXORL_T_PARAM], a->value.total, a->spec_value, false, s));
-        EXORL_TRY(refresh_w1_planes(a->value, a->flat[EXORL_NET_VALUE][EXORL_T_PARAM], a->sh_value, s));
+        EXORL_TRY(refresh_shadows(a->flat[EXORL_NET_VALUE][EXORL_T_PARAM], a->value.total, a->iql.spec, false, s));
+        EXORL_TRY(refresh_w1_planes(a->value, a->flat[EXORL_NET_VALUE][EXORL_T_PARAM], a->iql.sh, s));
     }
     return 0;
 }
@@ -1440,14 +1522,13 @@ int exorl_agent_update(exorl_agent_t* a, float stddev, const float* noise_c, con
                   "exorl_agent_update_phase and all-reduce between the phases yourself", a->cfg.world_size);
     EXORL_TRY(prdc_bound(a, "agent_update"));
     hipStream_t s = as_stream(stream);
-    EXORL_TRY(push_stddev(a, "agent_update_phase", stddev, s));
+    EXORL_TRY(push_stddev(a, "agent_update_phase", stddev, s));      // the phased call's prefix: the refusal's text is part of the interface as it is
     return whole_step_body(a, make_step(a, s, stddev, noise_c, noise_a, true, false, false, false));
 }
 
 int exorl_agent_update_plan(const exorl_agent_cfg* cfg, int32_t* phases, int32_t* exchanges, int32_t capacity, int32_t* n) {
     EXORL_REQUIRE(cfg && phases && exchanges && n, "agent_update_plan: null argument");
-    exorl_agent tmp;
-    EXORL_TRY(describe(&tmp, cfg));
+    EXORL_TRY(check_cfg(cfg));
     const AgentPlan p = agent_plan(*cfg, cfg->world_size > 1, false);
     EXORL_REQUIRE(capacity >= p.n, "agent_update_plan: capacity %d, the plan has %d phases", capacity, p.n);
     for (int i = 0; i < p.n; ++i) { phases[i] = p.phase[i]; exchanges[i] = p.xchg[i]; }
@@ -1478,7 +1559,7 @@ int exorl_agent_stats_buffer(exorl_agent_t* a, void** ptr, int64_t* numel) {
 
 // one launch for <= ACT_FAST_ROWS rows of a tanh-mean policy (every agent kind but CQL's tanh-Gaussian); obs / noise on the device or on the host
 static bool act_fast_ok(const exorl_agent* a, int n) {
-    return a->cfg.kind != EXORL_AGENT_CQL && act_fast_supported(n, a->cfg.obs_dim, a->cfg.hidden_dim, a->actor.out_dim) && !(tune_variant() & TUNE_ACT_GENERIC);
+    return a->traits->uses_stddev && act_fast_supported(n, a->cfg.obs_dim, a->cfg.hidden_dim, a->actor.out_dim) && !(tune_variant() & TUNE_ACT_GENERIC);
 }
 static int act_fast_launch(exorl_agent* a, const float* obs_dev, const float* obs_host, int n, float stddev, int eval_mode, const float* noise_dev,
                            const float* noise_host, float* out, hipStream_t s) {
@@ -1513,9 +1594,8 @@ int exorl_agent_act(exorl_agent_t* a, const float* obs, int32_t n, float stddev,
         WeightImages sh = a->sh_actor;              // act() rows do not tile by 64: split-bf16 takes the in-GEMM split here
         sh.w1.lo = sh.w0.lo = nullptr;
         EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], sh, obs + (int64_t)r0 * O, O, rows, a->fact, false,
-                              a->cfg.kind != EXORL_AGENT_CQL,
-                              a->cfg.precision, s));
-        if (a->cfg.kind == EXORL_AGENT_CQL) {       // SquashedNormal: mean = tanh(loc), sample = tanh(loc + std z)  (cql.py:122-131)
+                              a->traits->uses_stddev, a->cfg.precision, s));
+        if (!a->traits->uses_stddev) {               // SquashedNormal: mean = tanh(loc), sample = tanh(loc + std z)  (cql.py:122-131)
             EXORL_TRY(cql_act(a->fact.out, noise ? noise + (int64_t)r0 * A : nullptr, a->cfg.seed, (1ull << 63) | a->act_noise_counter++,
                               eval_mode, out + (int64_t)r0 * A, rows, A, s));
         } else if (eval_mode) {
@@ -1651,8 +1731,7 @@ int exorl_debug_agent_poison_scratch(exorl_agent_t* a, void* stream) {
     EXORL_REQUIRE(a, "debug_agent_poison_scratch: null handle");
     hipStream_t s = as_stream(stream);
     exorl_agent layout;              // a second carve over the same configuration: same offsets, nothing of `a` is touched
-    layout.cfg = a->cfg; layout.actor = a->actor; layout.critic = a->critic; layout.has_critic = a->has_critic;
-    layout.value = a->value; layout.has_value = a->has_value;
+    EXORL_TRY(describe(&layout, &a->cfg));
     std::vector<std::pair<int64_t, int64_t>> runs;
     Carver c(nullptr);
     c.fill = &runs;
@@ -1672,16 +1751,16 @@ int exorl_debug_agent_weight_images(exorl_agent_t* a, int32_t net, exorl_weight_
 }
 
 int exorl_agent_cql_alpha(exorl_agent_t* a, float* host, int32_t set) {
-    EXORL_REQUIRE(a && host && a->cql, "agent_cql_alpha: not a CQL agent / null argument");
+    EXORL_REQUIRE(a && host && a->cql.sc, "agent_cql_alpha: not a CQL agent / null argument");
     const int nsc = a->cfg.use_critic_lagrange ? 2 : 1;      // [1] = log_critic_alpha (cql.py:103-105)
     for (int i = 0; i < nsc; ++i) {
         float* h = host + 3 * i;
         if (set) {
             CqlScalars sc{h[0], h[1], h[2], expf(h[0])};
-            EXORL_CHECK_HIP(hipMemcpy(a->cql + i, &sc, sizeof(sc), hipMemcpyHostToDevice));
+            EXORL_CHECK_HIP(hipMemcpy(a->cql.sc + i, &sc, sizeof(sc), hipMemcpyHostToDevice));
         } else {
             CqlScalars sc;
-            EXORL_CHECK_HIP(hipMemcpy(&sc, a->cql + i, sizeof(sc), hipMemcpyDeviceToHost));
+            EXORL_CHECK_HIP(hipMemcpy(&sc, a->cql.sc + i, sizeof(sc), hipMemcpyDeviceToHost));
             h[0] = sc.log_alpha; h[1] = sc.m; h[2] = sc.v;
         }
     }
@@ -1695,7 +1774,7 @@ int exorl_agent_set_iql(exorl_agent_t* a, float expectile, float temperature, fl
     EXORL_REQUIRE(a, "agent_set_iql: null handle");
     EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_IQL, "agent_set_iql: kind %d is not IQL", a->cfg.kind);
     EXORL_REQUIRE(!a->graph_exec, "agent_set_iql: disable the captured graph first (it holds the values as kernel arguments)");
-    a->expectile = expectile; a->temperature = temperature; a->max_weight = max_weight;
+    a->iql.expectile = expectile; a->iql.temperature = temperature; a->iql.max_weight = max_weight;
     return 0;
 }
 
@@ -1711,17 +1790,17 @@ int exorl_agent_set_prdc(exorl_agent_t* a, exorl_replay_t* r, float beta) {
     EXORL_REQUIRE(k.beta == beta, "agent_set_prdc: the table was built with beta=%g, not %g", k.beta, beta);
     int cus = 0;
     EXORL_TRY(nn_device_cus(&cus));
-    a->prdc_replay = r;
-    a->prdc_keys = k;
-    a->prdc_plan = nn_plan((int)k.n, a->cfg.batch, 0, cus);      // fixed here, not per call: a captured graph replays the same launches
+    a->prdc.replay = r;
+    a->prdc.keys = k;
+    a->prdc.plan = nn_plan((int)k.n, a->cfg.batch, 0, cus);      // fixed here, not per call: a captured graph replays the same launches
     return 0;
 }
 
 int exorl_agent_nn_result(exorl_agent_t* a, void** idx_dev, void** d2_dev, void** a_nn_dev, int32_t* splits) {
     EXORL_REQUIRE(a && idx_dev && d2_dev && a_nn_dev, "agent_nn_result: null argument");
     EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_PRDC, "agent_nn_result: kind %d is not PRDC", a->cfg.kind);
-    *idx_dev = a->nn_idx; *d2_dev = a->nn_d2; *a_nn_dev = a->a_nn;
-    if (splits) *splits = a->prdc_replay ? a->prdc_plan.splits : 0;
+    *idx_dev = a->prdc.idx; *d2_dev = a->prdc.d2; *a_nn_dev = a->prdc.a_nn;
+    if (splits) *splits = a->prdc.replay ? a->prdc.plan.splits : 0;
     return 0;
 }
 
@@ -1740,8 +1819,7 @@ int exorl_agent_set_metrics(exorl_agent_t* a, int32_t enable) {
 }
 
 size_t exorl_agent_metric_window_bytes(const exorl_agent_cfg* cfg) {
-    exorl_agent tmp;
-    if (describe(&tmp, cfg) != 0) return 0;
+    if (check_cfg(cfg) != 0) return 0;
     return window_bytes(*cfg);
 }
 
@@ -1752,9 +1830,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
         a->win_steps = nullptr; a->win_bc = nullptr;
         return attach_window("agent_set_metric_window", nullptr, 0, 0, &a->win_sums, &a->win_crit);
     }
-    EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_IQL, "agent_set_metric_window: IQL has no metric window");
-    EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_FQE, "agent_set_metric_window: FQE has no metric window");
-    EXORL_REQUIRE(a->cfg.kind != EXORL_AGENT_PRDC, "agent_set_metric_window: PRDC has no metric window");
+    EXORL_REQUIRE(a->traits->metric_window, "agent_set_metric_window: %s has no metric window", a->traits->name);
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     EXORL_TRY(attach_window("agent_set_metric_window", buf_dev, bytes, window_bytes(a->cfg), &a->win_sums, &a->win_crit));
@@ -1773,20 +1849,16 @@ static_assert(EXORL_N_EVAL * sizeof(double) <= WIN_HEAD_BYTES && EXORL_E_ROWS ==
 static size_t eval_bytes(const exorl_agent_cfg& cfg) {
     return WIN_HEAD_BYTES + sizeof(float) * (size_t)round_up((int64_t)EVAL_PARTS * eval_chunks(cfg.batch), 64);
 }
-static bool eval_kind_ok(int kind) {
-    return kind == EXORL_AGENT_TD3_BC || kind == EXORL_AGENT_TD3 || kind == EXORL_AGENT_CRR || kind == EXORL_AGENT_CQL || kind == EXORL_AGENT_BC;
-}
 
 size_t exorl_agent_eval_bytes(const exorl_agent_cfg* cfg) {
-    exorl_agent tmp;
-    if (describe(&tmp, cfg) != 0) return 0;
+    if (check_cfg(cfg) != 0) return 0;
     return eval_bytes(*cfg);
 }
 
 int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     EXORL_REQUIRE(a, "agent_set_eval: null handle");
     if (!buf_dev) return attach_window("agent_set_eval", nullptr, 0, 0, &a->eval_sums, &a->eval_part);
-    EXORL_REQUIRE(eval_kind_ok(a->cfg.kind), "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
+    EXORL_REQUIRE(a->traits->evaluates, "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
     return attach_window("agent_set_eval", buf_dev, bytes, eval_bytes(a->cfg), &a->eval_sums, &a->eval_part);
 }
 
@@ -1794,17 +1866,17 @@ int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
 // Writes the staged inputs, forward scratch (fa, ft, fc, dq: takes carve() marks as scratch) and the eval buffer; reads everything else.
 int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
     EXORL_REQUIRE(a, "agent_evaluate: null handle");
-    EXORL_REQUIRE(eval_kind_ok(a->cfg.kind), "agent_evaluate: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
+    EXORL_REQUIRE(a->traits->evaluates, "agent_evaluate: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
     EXORL_REQUIRE(a->eval_sums, "agent_evaluate: no eval buffer (exorl_agent_set_eval)");
     hipStream_t s = as_stream(stream);
     const auto& cfg = a->cfg;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
-    const bool cql = cfg.kind == EXORL_AGENT_CQL;
+    const bool raw = !a->traits->uses_stddev;      // the head holds (mu | log_std) before the tanh
     const int AO = a->actor.out_dim;
     const float* Pa = a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM];
     EXORL_TRY(open_step(a, nullptr, s));         // no step: the inputs are staged, the step state stays where it is
     EvalArgs e{};
-    e.mu = a->fa.out + (int64_t)B * AO; e.mu_ld = AO; e.raw = cql ? 1 : 0;
+    e.mu = a->fa.out + (int64_t)B * AO; e.mu_ld = AO; e.raw = raw ? 1 : 0;
     e.a_data = a->action; e.A = A; e.reward = a->reward; e.discount = a->discount;
     e.part = a->eval_part; e.sums = a->eval_sums; e.rows = B;
     if (!a->has_critic) {          // BC: the obs half alone, as its step runs it (phase 2)
@@ -1812,8 +1884,8 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
         return eval_reduce(e, s);
     }
     const float* Pc = a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM];
-    EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, false, !cql, prec, s));
-    EXORL_TRY(eval_mean_actions(a->fa.out, AO, cql ? 1 : 0, a->xc_next + O, a->xc_pi + O, W, B, A, s));
+    EXORL_TRY(net_forward(a->actor, Pa, a->sh_actor, a->xa, O, 2 * B, a->fa, false, !raw, prec, s));
+    EXORL_TRY(eval_mean_actions(a->fa.out, AO, raw ? 1 : 0, a->xc_next + O, a->xc_pi + O, W, B, A, s));
     // Q'(s', mu(s')) and Q(s, a) as phase 0 launches them; then Q(s, mu(s)) as phase 1 does, its two columns into dq (fc.out holds Q(s, a))
     EXORL_TRY(twin_forward(a, s, Fork{}, a->xc_next, false));
     FwdBufs fpi = a->fc;
@@ -1837,16 +1909,15 @@ static size_t fqe_value_bytes(const exorl_agent_cfg& cfg) {
 static_assert(EXORL_N_FQE_VALUE * sizeof(double) <= WIN_HEAD_BYTES && EXORL_FQE_V_ROWS == FQE_VALUE_PARTS, "the value window's sums fit its head; the row count follows the partials");
 
 size_t exorl_agent_fqe_value_bytes(const exorl_agent_cfg* cfg) {
-    exorl_agent tmp;
-    if (describe(&tmp, cfg) != 0 || cfg->kind != EXORL_AGENT_FQE) return 0;
+    if (check_cfg(cfg) != 0 || cfg->kind != EXORL_AGENT_FQE) return 0;
     return fqe_value_bytes(*cfg);
 }
 
 int exorl_agent_set_fqe_value(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     EXORL_REQUIRE(a, "agent_set_fqe_value: null handle");
-    if (!buf_dev) return attach_window("agent_set_fqe_value", nullptr, 0, 0, &a->fqe_value_sums, &a->fqe_value_part);
+    if (!buf_dev) return attach_window("agent_set_fqe_value", nullptr, 0, 0, &a->fqe.value_sums, &a->fqe.value_part);
     EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_FQE, "agent_set_fqe_value: kind %d is not FQE", a->cfg.kind);
-    return attach_window("agent_set_fqe_value", buf_dev, bytes, fqe_value_bytes(a->cfg), &a->fqe_value_sums, &a->fqe_value_part);
+    return attach_window("agent_set_fqe_value", buf_dev, bytes, fqe_value_bytes(a->cfg), &a->fqe.value_sums, &a->fqe.value_part);
 }
 
 // Forward-only, as exorl_agent_evaluate: the inputs are staged with the step state left where it is, the actor runs on the obs rows (the half of
@@ -1855,7 +1926,7 @@ int exorl_agent_set_fqe_value(exorl_agent_t* a, void* buf_dev, size_t bytes) {
 int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream) {
     EXORL_REQUIRE(a, "agent_fqe_value: null handle");
     EXORL_REQUIRE(a->cfg.kind == EXORL_AGENT_FQE, "agent_fqe_value: kind %d is not FQE", a->cfg.kind);
-    EXORL_REQUIRE(a->fqe_value_sums, "agent_fqe_value: no value window (exorl_agent_set_fqe_value)");
+    EXORL_REQUIRE(a->fqe.value_sums, "agent_fqe_value: no value window (exorl_agent_set_fqe_value)");
     EXORL_REQUIRE(rows >= 1 && rows <= a->cfg.batch, "agent_fqe_value: rows=%d outside [1, batch=%d]", rows, a->cfg.batch);
     hipStream_t s = as_stream(stream);
     const auto& cfg = a->cfg;
@@ -1865,13 +1936,13 @@ int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream) {
     EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa + (int64_t)B * O, O, B, f, false, true, prec, s));
     EXORL_TRY(fqe_mean_actions(f.out, a->xc_pi + O, W, B, A, s));
     EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->xc_pi, W, B, a->fc, false, false, prec, s));
-    return fqe_value_reduce(a->fc.out, B, rows, a->fqe_value_part, a->fqe_value_sums, s);
+    return fqe_value_reduce(a->fc.out, B, rows, a->fqe.value_part, a->fqe.value_sums, s);
 }
 
 int exorl_agent_fqe_value_read(exorl_agent_t* a, double* sums_host, int64_t* rows_host, int32_t reset, void* stream) {
     EXORL_REQUIRE(a && sums_host && rows_host, "agent_fqe_value_read: null argument");
-    EXORL_REQUIRE(a->fqe_value_sums, "agent_fqe_value_read: no value window (exorl_agent_set_fqe_value)");
-    EXORL_TRY(read_window(a->fqe_value_sums, EXORL_N_FQE_VALUE, sums_host, nullptr, reset, as_stream(stream)));
+    EXORL_REQUIRE(a->fqe.value_sums, "agent_fqe_value_read: no value window (exorl_agent_set_fqe_value)");
+    EXORL_TRY(read_window(a->fqe.value_sums, EXORL_N_FQE_VALUE, sums_host, nullptr, reset, as_stream(stream)));
     *rows_host = (int64_t)sums_host[EXORL_FQE_V_ROWS];
     return 0;
 }

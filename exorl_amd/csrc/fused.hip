@@ -967,17 +967,17 @@ __device__ __forceinline__ float dout_value(const DoutSpec& d, int net, int m, i
     const int i = m * nout + j;
     const float mv = d.mu[i];
     float dmu;
-    if (d.kind == EXORL_AGENT_BC) {
+    if (d.form == ACTOR_LOSS_BC) {
         const float sd = d.stddev_ptr ? *d.stddev_ptr : d.stddev;
         dmu = -(d.a_data[i] - mv) / (sd * sd) * d.inv_bg;
-    } else if (d.kind == EXORL_AGENT_CRR) {
+    } else if (d.form == ACTOR_LOSS_WLL) {
         const float sd = d.stddev_ptr ? *d.stddev_ptr : d.stddev;
         dmu = -d.w[m] * (d.a_data[i] - mv) / (sd * sd) * d.inv_bg;     // -(log_prob * w).mean(), crr.py:185-186
     } else {
         dmu = 0.f;
         for (int t = 0; t < d.da_nets; ++t) dmu += d.da[((int64_t)t * rows + m) * nout + j];
         dmu *= lam;
-        if (d.kind == EXORL_AGENT_TD3_BC) dmu += 2.0f * d.inv_bg / (float)nout * (mv - d.a_data[i]);
+        if (d.form == ACTOR_LOSS_Q_BC) dmu += 2.0f * d.inv_bg / (float)nout * (mv - d.a_data[i]);
     }
     return dmu * (1.0f - mv * mv);
 }
@@ -1009,7 +1009,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
     for (int r = 0; r < HB_ROWS; ++r)          // row clamped; rows past nr are skipped below
         avs[r] = reinterpret_cast<const float4*>(a + net * astride + (int64_t)(row0 + (r < nr ? r : 0)) * H)[c4c];
     // deterministic-actor gradient (TD3 / TD3+BC / DDPG): its inputs are read now, lambda is applied after the reduction below
-    const bool mu_path = dspec.mode == EXORL_DOUT_ACTOR_MU && dspec.kind != EXORL_AGENT_BC && dspec.kind != EXORL_AGENT_CRR;
+    const bool mu_path = dspec.mode == EXORL_DOUT_ACTOR_MU && dspec.form != ACTOR_LOSS_BC && dspec.form != ACTOR_LOSS_WLL;
     const int dr = (threadIdx.x >> 4) & (HB_ROWS - 1), dj = threadIdx.x & 15;
     const bool dlive = threadIdx.x < HB_ROWS * 16 && row0 + dr < rows && dj < nout;
     float mu_v = 0.f, da_v = 0.f, ad_v = 0.f;
@@ -1017,7 +1017,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
         const int i = (dlive ? row0 + dr : 0) * nout + (dlive ? dj : 0);
         mu_v = dspec.mu[i];
         for (int t = 0; t < dspec.da_nets; ++t) da_v += dspec.da[(int64_t)t * rows * nout + i];
-        if (dspec.kind == EXORL_AGENT_TD3_BC) ad_v = dspec.a_data[i];
+        if (dspec.form == ACTOR_LOSS_Q_BC) ad_v = dspec.a_data[i];
     }
     float lam = 1.0f;
     if (dspec.mode == EXORL_DOUT_ACTOR_MU && dspec.lam_parts && dspec.use_lambda) {     // lambda = alpha / mean |min(Q1,Q2)| (td3_bc.py:154)
@@ -1034,7 +1034,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const DoutSpec dspec, con
         float dv = 0.f;
         if (mu_path) {            // same arithmetic as dout_value's last branch
             float dmu = da_v * lam;
-            if (dspec.kind == EXORL_AGENT_TD3_BC) dmu += 2.0f * dspec.inv_bg / (float)nout * (mu_v - ad_v);
+            if (dspec.form == ACTOR_LOSS_Q_BC) dmu += 2.0f * dspec.inv_bg / (float)nout * (mu_v - ad_v);
             dv = dlive ? dmu * (1.0f - mu_v * mu_v) : 0.f;
         } else if (dlive) {
             dv = dout_value(dspec, net, row0 + dr, dj, rows, nout, lam);
@@ -1095,7 +1095,7 @@ int head_bwd(const DoutSpec& dspec, const float* W, const float* a, float* dz, c
     EXORL_REQUIRE(nout >= 1 && nout <= 16 && H % 4 == 0 && H <= 1024, "head_bwd: nout=%d H=%d unsupported", nout, H);
     dim3 grid(cdiv(rows, HB_ROWS), nets);
     if (metrics) {
-        EXORL_REQUIRE(dspec.mode == EXORL_DOUT_ACTOR_MU && dspec.kind == EXORL_AGENT_TD3_BC && nets == 1 && dspec.bc_part,
+        EXORL_REQUIRE(dspec.mode == EXORL_DOUT_ACTOR_MU && dspec.form == ACTOR_LOSS_Q_BC && nets == 1 && dspec.bc_part,
                       "head_bwd: the metrics variant is TD3+BC's actor gradient on one net");
         if (nout == 1) hipLaunchKernelGGL((head_bwd_kernel<1, true>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);
         else if (nout <= 8) hipLaunchKernelGGL((head_bwd_kernel<8, true>), grid, dim3(256), 0, s, dspec, W, a, dz, dz_bf16, P, rows, H, nout, astride, pstride, want_params, dz_lo);

@@ -147,6 +147,15 @@ int head_fwd4(const float* a, const float* W, const float* b, float* out, int ro
 #define EXORL_DOUT_ACTOR_Q  2   /* -lambda * inv_bg * [q_net is the min] (0.5 on ties)            td3_bc.py:152-155 */
 #define EXORL_DOUT_CQL_ACTOR 4  /* tanh-Gaussian actor, 2A outputs: reparameterised (alpha*log_pi - Q).mean()   cql.py:236-255 */
 #define EXORL_DOUT_ACTOR_MU 3   /* (sum_t da_t + bc term) * (1 - mu^2)  /  BC: -(a-mu)/std^2*inv_bg td3_bc.py:155, bc.py:83 */
+// The form of the actor's loss, which is all head_bwd, actor_dmu and metrics_window ask of an agent kind. The values are those of the agent kinds
+// the kernels compared against before the form had a name of its own (TD3+BC 0, TD3 1, BC 2, CRR 4), so the device code is what it was,
+// instruction for instruction; a kernel parameter that carries a form stays `int`, which keeps the kernel's symbol.
+enum ActorLoss : int {
+    ACTOR_LOSS_Q_BC = 0,     // -lambda Q(s, mu) + (mu - a)^2                            td3_bc.py:152-155
+    ACTOR_LOSS_Q = 1,        // -Q(s, mu)                                                td3.py, ddpg.py
+    ACTOR_LOSS_BC = 2,       // -log N(a; mu, std)                                       bc.py:83
+    ACTOR_LOSS_WLL = 4,      // -w log N(a; mu, std), w per row: CRR's and IQL's         crr.py:185-186
+};
 struct DoutSpec {
     int mode;
     union {
@@ -167,7 +176,7 @@ struct DoutSpec {
     const float* lam_parts;  // ACTOR_MU after qhead(ACTOR): per-chunk [sum |min Q|, sum min Q]; lambda = alpha / mean|Q| is applied here
     int lam_chunks;          //   (the critic backward is linear in its output gradient, so it ran with lambda = 1)
     int da_nets;
-    int kind;                // EXORL_AGENT_*
+    ActorLoss form;          // ACTOR_MU: which terms d L / d mu has
     int use_lambda;
     float inv_bg, alpha, stddev;
     const float* stddev_ptr;   // BC / CRR: device-resident std (StepState::stddev); null -> `stddev`
@@ -373,7 +382,7 @@ struct MetricsWindowArgs {
     const float *crit_part, *abs_part, *bc_part;   // fused: qhead mode 0's [chunk][6], mode 1's [chunk][2], head_bwd's [chunk] (TD3+BC)
     int q_chunks, bc_chunks;                       // qhead_chunks(B); head_chunks(B), or 0 when the kind has no BC term
     int fused;                                     // 1: form the step's metrics from the partials; 0: the step's metric kernels wrote them
-    int kind, act_dim, ent_from_std;
+    ActorLoss form; int act_dim, ent_from_std;
     float inv_bg, alpha;
     const float* stddev;                           // StepState::stddev
     float* metrics;                                // EXORL_N_METRICS slots (EXORL_M_*)
@@ -532,7 +541,7 @@ int sf_q(const float* feat, const float* task, int64_t task_ld, float* q, int B,
 int actor_dq(const float* q, const float* stats, float* dq, int B, float inv_bg, float alpha, int use_lambda,
              hipStream_t s);
 int actor_dmu(const float* da, int64_t da_ld, int da_nets, int64_t da_net_stride, const float* mu, const float* a_data, const float* reward, const float* w, float* dpre, float* stats,
-              float* metrics, int B, int A, float inv_bg, float alpha, int kind, float stddev, hipStream_t s, const float* stddev_ptr = nullptr);
+              float* metrics, int B, int A, float inv_bg, float alpha, ActorLoss form, float stddev, hipStream_t s, const float* stddev_ptr = nullptr);
 
 // ---- optimiser (optim.hip)
 int adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,

@@ -524,7 +524,7 @@ __global__ __launch_bounds__(1024) void actor_dmu_kernel(const float* __restrict
                                                          const float* __restrict__ reward, const float* __restrict__ w,
                                                          float* __restrict__ dpre, const float* __restrict__ stats,
                                                          float* __restrict__ metrics, int B, int A, float inv_bg,
-                                                         float alpha, int kind, float stddev_val, const float* stddev_ptr) {
+                                                         float alpha, int form, float stddev_val, const float* stddev_ptr) {
     const float stddev = stddev_ptr ? *stddev_ptr : stddev_val;
     __shared__ float sm[2][16];
     float v[2] = {0.f, 0.f};
@@ -537,17 +537,17 @@ __global__ __launch_bounds__(1024) void actor_dmu_kernel(const float* __restrict
         const int m = i / A, j = i % A;
         const float mv = mu[i];
         float dmu;
-        if (kind == EXORL_AGENT_TD3_BC) {
+        if (form == ACTOR_LOSS_Q_BC) {
             const float d = mv - a_data[i];
             float dav = 0.f;
             for (int t = 0; t < da_nets; ++t) dav += da[t * da_net_stride + (int64_t)m * da_ld + j];
             dmu = dav + bc_coef * d;
             v[0] += d * d;
-        } else if (kind == EXORL_AGENT_BC) {
+        } else if (form == ACTOR_LOSS_BC) {
             const float d = a_data[i] - mv;
             dmu = -d * inv_var * inv_bg;
             v[0] += d * d * 0.5f * inv_var - log_norm;     // -log N(a; mu, std)
-        } else if (kind == EXORL_AGENT_CRR) {
+        } else if (form == ACTOR_LOSS_WLL) {
             const float d = a_data[i] - mv;
             dmu = -w[m] * d * inv_var * inv_bg;
             v[0] += w[m] * (d * d * 0.5f * inv_var - log_norm);   // -(log_prob * w), crr.py:186
@@ -561,11 +561,11 @@ __global__ __launch_bounds__(1024) void actor_dmu_kernel(const float* __restrict
     if (threadIdx.x == 0) {
         if (reward) metrics[EXORL_M_BATCH_REWARD] = v[1] * inv_bg;
         float loss;
-        if (kind == EXORL_AGENT_TD3_BC) {
+        if (form == ACTOR_LOSS_Q_BC) {
             const float lambda = alpha / (stats[0] * inv_bg);
             loss = -lambda * metrics[EXORL_M_Q_SUM] * inv_bg + v[0] * inv_bg / (float)A;
             metrics[EXORL_M_BC_SUM] = v[0];
-        } else if (kind == EXORL_AGENT_BC || kind == EXORL_AGENT_CRR) {
+        } else if (form == ACTOR_LOSS_BC || form == ACTOR_LOSS_WLL) {
             loss = v[0] * inv_bg;
         } else {
             loss = -metrics[EXORL_M_Q_SUM] * inv_bg;
@@ -575,9 +575,9 @@ __global__ __launch_bounds__(1024) void actor_dmu_kernel(const float* __restrict
 }
 
 int actor_dmu(const float* da, int64_t da_ld, int da_nets, int64_t da_net_stride, const float* mu, const float* a_data, const float* reward, const float* w, float* dpre, float* stats,
-              float* metrics, int B, int A, float inv_bg, float alpha, int kind, float stddev, hipStream_t s, const float* stddev_ptr) {
+              float* metrics, int B, int A, float inv_bg, float alpha, ActorLoss form, float stddev, hipStream_t s, const float* stddev_ptr) {
     hipLaunchKernelGGL(actor_dmu_kernel, dim3(1), dim3(1024), 0, s, da, da_ld, da_nets, da_net_stride, mu, a_data, reward, w, dpre, stats, metrics, B, A,
-                       inv_bg, alpha, kind, stddev, stddev_ptr);
+                       inv_bg, alpha, (int)form, stddev, stddev_ptr);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(64) void metrics_window_kernel(const MetricsWindowA
             m[EXORL_M_CRITIC_LOSS] = (tot[4] + tot[5]) * w.inv_bg;
             m[EXORL_M_Q_ABS_SUM] = tot[6];
             m[EXORL_M_Q_SUM] = tot[7];
-            if (w.kind == EXORL_AGENT_TD3_BC) {
+            if (w.form == ACTOR_LOSS_Q_BC) {
                 const float lambda = w.alpha / (tot[6] * w.inv_bg);
                 m[EXORL_M_ACTOR_LOSS] = -lambda * tot[7] * w.inv_bg + tot[8] * w.inv_bg / (float)w.act_dim;
                 m[EXORL_M_BC_SUM] = tot[8];

@@ -33,7 +33,7 @@ sys.path.insert(0, str(ROOT / 'tests'))
 O, A, H, B = 24, 6, 256, 256                        # states
 PC, PHW, PF, PH, PB = 3, 64, 32, 128, 64            # pixels: the two-process workers' frames and widths
 OFFLINE = ['td3_bc', 'td3', 'bc', 'crr', 'cql', 'cql_lagrange']
-OFFLINE_LATER = ['iql', 'fqe']                      # their cases follow every older one, so that a listing's older part keeps its order
+OFFLINE_LATER = ['iql', 'fqe', 'prdc']              # their cases follow every older one, so that a listing's older part keeps its order
 MODULES = ['rnd', 'icm', 'icm_apt', 'disagreement', 'diayn', 'aps', 'smm', 'proto']
 META = {'states': {'diayn': 16, 'aps': 10, 'smm': 4}, 'pixels': {'diayn': 8, 'aps': 5, 'smm': 4}}
 PRECISIONS = {'states': ('fp32', 'bf16', 'bf16x3', 'bf16x6'), 'pixels': ('fp32', 'bf16x6')}
@@ -59,6 +59,8 @@ def build(kind, obs_type, reward_free, precision, use_tb=True):
             return agents.IQLAgent(*a, '0.2', 1, B, use_tb, precision=precision)
         if kind == 'fqe':           # the policy it scores: a TD3+BC agent from the same seed
             return agents.FQEAgent(*a, 1, B, use_tb, precision=precision).set_policy(build('td3_bc', obs_type, reward_free, precision, use_tb))
+        if kind == 'prdc':          # searches a bound table: bind_prdc() before the first update()
+            return agents.PRDCAgent(*a, '0.2', 1, B, 0.3, use_tb, 2.5, beta=2.0, precision=precision)
         if kind == 'td3_bc':
             return agents.TD3BCAgent(*a, '0.2', 1, B, 0.3, use_tb, 2.5, precision=precision)
         if kind == 'td3':
@@ -109,6 +111,17 @@ def arena(kind, obs_type, seed=5):
     eng.set_order([eng.append_episode(ep, ('skill',) if M else ()) for ep in eps])
     eng.seed_philox(seed)
     return ArenaIterator(eng, batch, 1 if kind in OFFLINE + OFFLINE_LATER else 3, 0.99, 'philox')
+
+
+def bind_prdc(ag, it, seed=5):
+    """PRDC's key table, built from a small arena and bound, as tests/_prdc_cases.bind does: the arena `it` samples from when it is an
+    ArenaIterator, else one of its own (a plain iterator of batches has no dataset). Returns what must stay alive while the agent steps; a
+    no-op for every other class."""
+    if ag.KIND != 'prdc':
+        return None
+    table = it if hasattr(it, '_arenas') else arena('prdc', 'states', seed)
+    assert ag.bind_dataset(table) == 900
+    return table
 
 
 def batches(kind, obs_type, first, n):
@@ -218,13 +231,15 @@ def run_case(emit, kind, obs_type, reward_free, precision, mode, first, n, ag=No
         it = batches(kind, obs_type, first, n)
     else:
         it = arena(kind, obs_type, 5 + first)
-        if mode == 'graph':
-            assert ag.enable_graph(it)
+    table = bind_prdc(ag, it, 5 + first)       # an unpickled agent (part2) binds again: the table is the arena's, not the agent's
+    if mode == 'graph':
+        assert ag.enable_graph(it)
     for i in range(first, first + n):
         emit_metrics(emit, f'metrics{i}', ag.update(it, i))
     digest(ag, emit)
     for eval_mode in (True, False):
         emit(f'act.eval{int(eval_mode)}', sha(np.asarray(ag.act(*act_inputs(ag, kind, obs_type), 10, eval_mode), np.float32)))
+    del table
     return ag
 
 
@@ -329,10 +344,12 @@ def part3(out):
 
 def grid(out):
     """tests/_grad_grid.CASES and tests/_state_bf16x6_cases.CASES on the three routes of tests/test_gpu_grad_grid.py: one update() as its run()
-    does it, then every tensor of its state_of()."""
+    does it, then every tensor of its state_of(). Behind them tests/_prdc_cases.CASES on the two routes of tests/test_gpu_prdc.py, likewise."""
     import _grad_grid as G
+    import _prdc_cases as P
     import _state_bf16x6_cases as S
     import test_gpu_grad_grid as T
+    import test_gpu_prdc as TP
 
     def body(emitter):
         for c in list(G.CASES) + list(S.CASES):
@@ -344,15 +361,25 @@ def grid(out):
                 for k, v in T.state_of(ag).items():
                     emit(k, sha(v))
                 print(name, flush=True)
+        for c in P.CASES:
+            for route in ('metrics', 'fast'):
+                name = f'grid/{P.case_id(c)}/{route}'
+                ag, m, keep = TP.run(c, route)
+                emit = emitter(name)
+                emit_metrics(emit, 'metrics', m)
+                for k, v in TP.state_of(ag).items():
+                    emit(k, sha(v))
+                del keep
+                print(name, flush=True)
     listing(out, body)
 
 
 def modes(out):
-    """TD3+BC, CQL, IQL and FQE, one handle each per precision and metrics setting, driven in turn by a captured graph step, disable_graph,
+    """TD3+BC, CQL, IQL, FQE and PRDC, one handle each per precision and metrics setting, driven in turn by a captured graph step, disable_graph,
     the phased calls, an eager update() and a newly captured graph step, with the digests after every driver: what one driver sets up for
     its own launches (fused optimiser and scalar-head kernels, staged inputs, capture) must not reach the next one's. TD3+BC and CQL run
-    phases 0..3 and use only calls that trees from before exorl_agent_update_plan have; IQL and FQE (no metric window) run the phase ids
-    of their own plan, as AgentEngine.update_steps reads it."""
+    phases 0..3 and use only calls that trees from before exorl_agent_update_plan have; IQL, FQE and PRDC (no metric window) run the phase
+    ids of their own plan, as AgentEngine.update_steps reads it; PRDC searches the table of the arena it samples from."""
     def plan_phases(eng):
         import ctypes as C
         from exorl_amd import _lib as L
@@ -370,6 +397,7 @@ def modes(out):
                     if metrics == 'window':
                         assert ag.enable_metric_window()
                     it = arena(kind, 'states')
+                    bind_prdc(ag, it)
                     stddev = 1.0 if kind == 'cql' else ag._stddev(0)
 
                     def after(tag):
