@@ -49,7 +49,9 @@ class ReplayCfg(C.Structure):
 class BatchOut(C.Structure):
     _fields_ = [('obs', c_void_p), ('obs_stride', c_int64), ('action', c_void_p), ('action_stride', c_int64),
                 ('reward', c_void_p), ('discount', c_void_p), ('next_obs', c_void_p), ('next_obs_stride', c_int64),
-                ('meta', c_void_p), ('meta_stride', c_int64)]
+                ('meta', c_void_p), ('meta_stride', c_int64),
+                # trailing and optional: a BatchOut built from the ten values above leaves them NULL / 0 and the gather writes neither
+                ('next_action', c_void_p), ('next_action_stride', c_int64), ('next_valid', c_void_p)]
 
 
 class AgentCfg(C.Structure):

@@ -1492,6 +1492,7 @@ int exorl_agent_batch_slots(exorl_agent_t* a, exorl_batch_out* out) {
     out->reward = a->reward; out->discount = a->discount;
     out->next_obs = a->next_obs; out->next_obs_stride = O * 4;
     out->meta = nullptr; out->meta_stride = 0;
+    out->next_action = nullptr; out->next_action_stride = 0; out->next_valid = nullptr;      // no agent kind reads the next action yet
     return 0;
 }
 

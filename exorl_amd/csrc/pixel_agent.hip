@@ -468,6 +468,7 @@ int exorl_pixel_agent_batch_slots(exorl_pixel_agent_t* a, exorl_batch_out* out) 
     out->reward = a->reward; out->discount = a->discount;
     out->next_obs = a->next_obs; out->next_obs_stride = img;
     out->meta = a->cfg.meta_dim > 0 ? a->meta : nullptr; out->meta_stride = a->cfg.meta_dim;
+    out->next_action = nullptr; out->next_action_stride = 0; out->next_valid = nullptr;
     return 0;
 }
 

@@ -246,10 +246,22 @@ __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pa
 // What one wave writes per sample, whatever the shape of the observation gather: the action of arena row `row` (= row0 + idx), the meta
 // row of the step before it, and the n-step return and discount in the reference's operation order. fp contract is off INSIDE this body
 // (the pragma is lexically scoped): an FMA in the recurrence would stop matching NumPy.
+// next_ok (idx + nstep <= len[pos], the caller has both): the episode holds the action taken at next_obs, arena row `row + nstep`. Where
+// it does not, that row is the next episode's dummy row or lies past the arena's end and is not read: the sample gets zeros.
 __device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_batch_out& out, int b, int64_t row, int nstep, float gamma,
-                                            int lane) {
+                                            int lane, bool next_ok) {
 #pragma clang fp contract(off)
     for (int j = lane; j < v.act_dim; j += 64) out.action[(int64_t)b * out.action_stride + j] = v.act[row * v.act_dim + j];
+    if (out.next_action) {                           // wave-uniform, as next_ok is
+        float* dst = out.next_action + (int64_t)b * out.next_action_stride;
+        if (next_ok) {
+            const float* src = v.act + (row + nstep) * v.act_dim;
+            for (int j = lane; j < v.act_dim; j += 64) dst[j] = src[j];
+        } else {
+            for (int j = lane; j < v.act_dim; j += 64) dst[j] = 0.0f;
+        }
+        if (lane == 0) out.next_valid[b] = next_ok ? 1.0f : 0.0f;
+    }
     if (out.meta)
         for (int j = lane; j < v.meta_dim; j += 64) out.meta[(int64_t)b * out.meta_stride + j] = v.meta[(row - 1) * v.meta_dim + j];
     if (lane == 0) {
@@ -314,7 +326,7 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         if (stage.has_critic)
             for (int j = lane; j < A; j += 64) stage.xc_cur[(int64_t)b * W + O + j] = v.act[row * v.act_dim + j];
     }
-    sample_tail(v, out, b, row, nstep, gamma, lane);
+    sample_tail(v, out, b, row, nstep, gamma, lane, idx + nstep <= v.len[pos]);
 }
 
 // copy_row with four loads of a lane in flight before the first store (the compiler keeps copy_row's loop at one load, one wait, one store):
@@ -355,7 +367,7 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const 
     if (vec16) stream_words(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), v.obs_bytes / 16, lane);
     else stream_words(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(dst), v.obs_bytes / 4, lane);
     if (!first) return;
-    sample_tail(v, out, b, row0 + idx, nstep, gamma, lane);
+    sample_tail(v, out, b, row0 + idx, nstep, gamma, lane, idx + nstep <= v.len[pos]);
 }
 
 // ---- column moments of the resident observations (exorl_replay_obs_moments) -----------------------------------------------------------
@@ -950,6 +962,7 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
     EXORL_REQUIRE(batch > 0 && nstep >= 1, "replay_sample: batch=%d nstep=%d", batch, nstep);
     EXORL_REQUIRE(out->obs && out->action && out->reward && out->discount && out->next_obs, "replay_sample: null output");
     EXORL_REQUIRE((r->cfg.meta_dim > 0) || out->meta == nullptr, "replay_sample: meta output without meta columns");
+    EXORL_REQUIRE((out->next_action == nullptr) == (out->next_valid == nullptr), "replay_sample: next_action and next_valid go together");
     if (r->frames > 1) {
         const int64_t need = (int64_t)r->frames * r->cfg.obs_bytes;
         EXORL_REQUIRE(out->obs_stride >= need && out->next_obs_stride >= need, "replay_sample: obs_stride=%lld / next_obs_stride=%lld cannot "

@@ -675,7 +675,9 @@ class DeviceReplayIterator(_EpisodeStarts):
                              out.action + start * out.action_stride * 4, out.action_stride,
                              out.reward + start * 4, out.discount + start * 4,
                              out.next_obs + start * out.next_obs_stride, out.next_obs_stride,
-                             (out.meta + start * out.meta_stride * 4) if out.meta else None, out.meta_stride)
+                             (out.meta + start * out.meta_stride * 4) if out.meta else None, out.meta_stride,
+                             (out.next_action + start * out.next_action_stride * 4) if out.next_action else None, out.next_action_stride,
+                             (out.next_valid + start * 4) if out.next_valid else None)
             shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler)
 
     def __next__(self):

@@ -44,7 +44,8 @@ extern "C" {
                                         exorl_agent_eval_bytes / _set_eval / _evaluate / _eval_read; EXORL_AGENT_IQL, exorl_agent_set_iql;
                                         EXORL_AGENT_FQE, exorl_agent_fqe_value_bytes / _set_fqe_value / _fqe_value / _fqe_value_read,
                                         exorl_replay_episode_returns, exorl_replay_num_episodes; EXORL_AGENT_PRDC, exorl_replay_build_keys,
-                                        exorl_replay_keys, exorl_replay_keys_read, exorl_nn_search, exorl_agent_set_prdc, exorl_agent_nn_result) */
+                                        exorl_replay_keys, exorl_replay_keys_read, exorl_nn_search, exorl_agent_set_prdc, exorl_agent_nn_result;
+                                        exorl_batch_out.next_action / next_action_stride / next_valid (trailing)) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -73,6 +74,12 @@ typedef struct {            /* where one sampled minibatch is written (device me
     float*  discount;                            /* (B) contiguous */
     void*   next_obs;  int64_t next_obs_stride;  /* bytes */
     float*  meta;      int64_t meta_stride;      /* floats; may be NULL when meta_dim == 0 */
+    /* Trailing and optional (a caller that zero-fills the struct gets neither): the action taken at next_obs, action[idx + nstep], and whether
+     * the episode holds it (idx + nstep <= len). An invalid sample gets next_valid = 0 and a row of zeros; the arena row behind the episode's last
+     * (the next episode's dummy row, or past the arena's end) is never read. A plain copy: bit-exact, untouched by exorl_replay_set_obs_norm.
+     * Written by the same gather launch; with next_action NULL every other output keeps its bits. */
+    float*  next_action;  int64_t next_action_stride;   /* floats between samples; NULL: not written */
+    float*  next_valid;                                 /* (B) contiguous, 1.0f or 0.0f; NULL iff next_action is NULL */
 } exorl_batch_out;
 
 #define EXORL_SAMPLER_MT19937 0   /* reference-exact index stream (CPython random + NumPy legacy RandomState) */
@@ -158,7 +165,8 @@ int exorl_replay_seed_mt_ints(exorl_replay_t* r, uint64_t py_seed, uint32_t np_s
 int exorl_replay_get_mt(exorl_replay_t* r, uint32_t* py_key624, int32_t* py_pos,
                         uint32_t* np_key624, int32_t* np_pos);
 int exorl_replay_seed_philox(exorl_replay_t* r, uint64_t seed);
-/* One minibatch: B x (obs[idx-1], action[idx], n-step reward, n-step discount, obs[idx+n-1], meta[idx-1]).
+/* One minibatch: B x (obs[idx-1], action[idx], n-step reward, n-step discount, obs[idx+n-1], meta[idx-1]) and, where out->next_action is set,
+ * (action[idx+n] or zeros, next_valid). Fails, launching nothing, when exactly one of out->next_action and out->next_valid is NULL.
  * pairs_host: for EXORL_SAMPLER_GIVEN, B x {position in order, start idx >= 1};
  * pairs_out_host: if non-NULL receives the pairs drawn (MT19937 mode only; host-generated). */
 int exorl_replay_sample(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
@@ -301,7 +309,8 @@ int exorl_agent_flat(exorl_agent_t* a, int32_t net, int32_t what, void** ptr_dev
 /* Must be called after parameters were written from outside (load_state_dict, init): refreshes derived
  * copies (bf16 shadows) and, if sync_target != 0, copies critic -> critic_target (td3_bc.py:93). */
 int exorl_agent_params_changed(exorl_agent_t* a, int32_t sync_target, void* stream);
-/* Where the sampler should write this agent's minibatch (zero-copy hand-off replay -> update). */
+/* Where the sampler should write this agent's minibatch (zero-copy hand-off replay -> update). Every field is written: next_action /
+ * next_valid are NULL (no agent kind reads the next action yet). */
 int exorl_agent_batch_slots(exorl_agent_t* a, exorl_batch_out* out);
 /* Copies a caller-provided device batch (contiguous f32 (B,O) (B,A) (B) (B) (B,O)) into the batch slots. */
 int exorl_agent_set_batch(exorl_agent_t* a, const float* obs_dev, const float* action_dev,
