@@ -21,6 +21,8 @@ AGENT_XCHG_CRITIC_GRAD, AGENT_XCHG_STATS, AGENT_XCHG_ACTOR_GRAD, AGENT_XCHG_VALU
 M_CRITIC_CQL, M_CRITIC_CQL_LOGSUM, M_ACTOR_ALPHA, M_ACTOR_ALPHA_LOSS, M_ACTOR_ENT = 10, 11, 12, 13, 14
 M_VALUE_LOSS, M_VALUE, M_ADV, M_ACTOR_WEIGHT = 10, 11, 12, 13        # IQL's use of slots 10..13
 M_NN_DIST = 10            # PRDC's use of slot 10
+M_REBRAC_PENALTY, M_REBRAC_VALID = 10, 11       # TD3+BC's use of slots 10 and 11 while ReBRAC is set
+REBRAC_PARTS = 3          # the row kernel's sums per chunk (kernels.h REBRAC_P_*): penalty, valid, reward
 CRR_WEIGHT = {'identity': 0, 'indicator': 1, 'exp': 2}
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2, 3
 NET_ACTOR, NET_CRITIC, NET_CRITIC_TARGET, NET_VALUE = 0, 1, 2, 3
@@ -191,6 +193,8 @@ PROTOTYPES = {
     'exorl_agent_set_iql': (C.c_int, [c_void_p, c_float, c_float, c_float]),
     'exorl_agent_set_prdc': (C.c_int, [c_void_p, c_void_p, c_float]),
     'exorl_agent_nn_result': (C.c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p), P(c_int32)]),
+    'exorl_agent_rebrac_bytes': (c_size_t, [P(AgentCfg)]),
+    'exorl_agent_set_rebrac': (C.c_int, [c_void_p, c_void_p, c_size_t, c_float]),
     'exorl_agent_act': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_act_host': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
@@ -241,6 +245,8 @@ PROTOTYPES = {
     'exorl_fqe_rows': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_iql_rows': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exorl_rebrac_rows': (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

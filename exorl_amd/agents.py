@@ -13,6 +13,7 @@ Reference classes mirrored (file:line in /root/reference):
   IQLAgent    no reference file: implicit Q-learning on the offline nets (the class's docstring is its definition)
   FQEAgent    no reference file: fitted Q evaluation of a frozen policy (the class's docstring is its definition)
   PRDCAgent   no reference file: TD3+BC regularised to the nearest dataset point; defined in exorl_amd/prdc.py, reachable as agents.PRDCAgent
+  ReBRACAgent no reference file: TD3+BC with a critic penalty on the dataset's next action; defined in exorl_amd/rebrac.py, agents.ReBRACAgent
 
 Python here is orchestration only: it builds the initial weights with torch's CPU RNG in the reference's
 construction order (so a given torch.manual_seed yields the reference's initial parameters), hands batches
@@ -143,11 +144,17 @@ EVAL_KINDS = ('td3_bc', 'td3', 'crr', 'cql', 'bc')      # what exorl_agent_evalu
 
 class _AgentBase:
     KIND = None
+    _evaluates_declared = False         # True on a class whose body sets _EVALUATES itself, and on its subclasses that keep its KIND
 
     # -- pickling (pretrain.py:293-300 torch.save's the whole agent; finetune.py:222-252 loads it back) ---------------
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
-        cls._EVALUATES = cls.KIND in EVAL_KINDS
+        # a class may say so itself (ReBRACAgent: TD3+BC's kind with the evaluation refused), and its subclasses inherit that unless they
+        # declare a KIND of their own; every other class gets its KIND's answer
+        if '_EVALUATES' in vars(cls):
+            cls._evaluates_declared = True
+        elif 'KIND' in vars(cls) or not cls._evaluates_declared:
+            cls._EVALUATES, cls._evaluates_declared = cls.KIND in EVAL_KINDS, False
         orig = cls.__dict__.get('__init__')
         if orig is None:
             return
@@ -1775,4 +1782,7 @@ def __getattr__(name):
     if name == 'PRDCAgent':
         from .prdc import PRDCAgent
         return PRDCAgent
+    if name == 'ReBRACAgent':          # likewise: exorl_amd.rebrac.ReBRACAgent, defined beside its buffer and batch handling
+        from .rebrac import ReBRACAgent
+        return ReBRACAgent
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -445,6 +445,14 @@ struct exorl_agent {
         ReplayKeys keys{};
         NnPlan plan{};
     } prdc;
+    // ReBRAC, a setting of the TD3+BC kind (exorl_agent_set_rebrac; `on` is the mode): views of the caller's buffer, laid out by rebrac_carve.
+    // The sampler writes next_action / next_valid (exorl_agent_batch_slots); the row kernel writes reward (r~) and part on every step before
+    // anything reads them.
+    struct {
+        float *next_action = nullptr, *next_valid = nullptr, *reward = nullptr, *part = nullptr;
+        float beta = 0.f;
+        bool on = false;
+    } rebrac;
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -856,7 +864,7 @@ static int run_metrics_window(exorl_agent* a, const Step& st) {
     return metrics_window(w, st.s);
 }
 // tq_slots > 0 (mode 0): this step's target critic left per-row partial head dots in ft.h2 (folded into the forward GEMM, net_forward2)
-static int run_qhead(exorl_agent* a, const Step& st, int mode, int tq_slots) {
+static int run_qhead(exorl_agent* a, const Step& st, int mode, int tq_slots, const float* reward) {
     const NetDesc& d = a->critic;
     const int B = a->cfg.batch, H = d.H;
     const int64_t act = (int64_t)B * H;
@@ -868,7 +876,7 @@ static int run_qhead(exorl_agent* a, const Step& st, int mode, int tq_slots) {
         q.a[i] = a->fc.h2 + i * act; q.W[i] = Pc + d.W2 + i * d.head_stride; q.b[i] = Pc + d.b2 + i * d.head_stride;
         q.a[2 + i] = a->ft.h2 + i * act; q.W[2 + i] = Pt + d.W2 + i * d.head_stride; q.b[2 + i] = Pt + d.b2 + i * d.head_stride;
     }
-    q.q = a->fc.out; q.tq = a->ft.out; q.reward = a->reward; q.discount = a->discount;
+    q.q = a->fc.out; q.tq = a->ft.out; q.reward = reward; q.discount = a->discount;
     q.tpart[0] = q.tpart[1] = nullptr; q.tslots = 0;
     if (mode == 0 && tq_slots > 0) { q.tpart[0] = a->ft.h2; q.tpart[1] = a->ft.h2 + act; q.tslots = tq_slots; }
     q.dz = bf ? nullptr : a->bc.dz2; q.dzb = bf ? a->bc.dz2q.hi : nullptr; q.dzl = bf ? a->bc.dz2q.lo : nullptr; q.act = act;
@@ -898,10 +906,18 @@ static int phase0(exorl_agent* a, const Step& st) {
     if (!fused_sample)
         EXORL_TRY(sample_actions2(a->fa.out, noise_c, cfg.kind == EXORL_AGENT_CRR ? nullptr : st.noise_a, cfg.seed,
                                   &a->state->noise_counter, stddev, cfg.stddev_clip, a->xc_next + O, a->xc_pi + O, W, B, A, s, &a->state->stddev));
+    // ReBRAC: the critic target's penalty on (a~' - a')^2 as a correction of the reward, r~ = r - D (beta p), from the sample the launch above
+    // left in xc_next's action columns; every reader of the reward below takes r~ (y = r~ + D min Q' = r + D (min Q' - beta p))
+    const float* reward = a->reward;
+    if (a->rebrac.on) {
+        EXORL_TRY(rebrac_rows(RebracRowsArgs{a->xc_next + O, W, a->rebrac.next_action, A, a->rebrac.next_valid, a->reward, a->discount,
+                                             a->rebrac.reward, a->rebrac.part, B, A, a->rebrac.beta}, s));
+        reward = a->rebrac.reward;
+    }
     const bool qf = st.qfuse;
     int tq_slots = 0;
     EXORL_TRY(twin_forward(a, s, st.fk, a->xc_next, true, qf, &tq_slots));      // target critic (td3_bc.py:126) and critic (td3_bc.py:130)
-    if (qf) EXORL_TRY(run_qhead(a, st, 0, tq_slots));      // Q, Q', TD gradient, dz2 and head partials in one kernel
+    if (qf) EXORL_TRY(run_qhead(a, st, 0, tq_slots, reward));      // Q, Q', TD gradient, dz2 and head partials in one kernel
     const bool aps = cfg.kind == EXORL_AGENT_APS;
     const float* task = aps ? a->obs + (O - cfg.sf_dim) : nullptr;          // obs rows are [observation | task] (aps.py:236-238)
     const float *qv = a->fc.out, *tqv = a->ft.out;
@@ -911,9 +927,11 @@ static int phase0(exorl_agent* a, const Step& st) {
         qv = a->aps.sfq; tqv = a->aps.sftq;
     }
     if (st.metric_kernels)
-        EXORL_TRY(critic_loss(qv, tqv, a->reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));   // :133-137
+        EXORL_TRY(critic_loss(qv, tqv, reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));   // :133-137
+    // behind critic_loss, which reported the mean of r~ as batch_reward: the row kernel's sums put the dataset's r there, and the penalty's slots
+    if (a->rebrac.on && st.metric_kernels) EXORL_TRY(rebrac_sums(a->rebrac.part, B, a->inv_bg, nullptr, a->metrics, s));
     DoutSpec td{};                              // d(2 x MSE)/dQ computed where it is consumed (:127-131)
-    td.mode = EXORL_DOUT_TD; td.q = qv; td.tq = tqv; td.reward = a->reward; td.discount = a->discount; td.inv_bg = a->inv_bg;
+    td.mode = EXORL_DOUT_TD; td.q = qv; td.tq = tqv; td.reward = reward; td.discount = a->discount; td.inv_bg = a->inv_bg;
     td.task = task; td.task_ld = O;
     return net_grads(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, B, a->fc, td, qf);                                       // :141
 }
@@ -963,7 +981,7 @@ static int phase2(exorl_agent* a, const Step& st) {
         dq.mode = EXORL_DOUT_ACTOR_Q; dq.q = a->fc.out; dq.stats = a->stats; dq.inv_bg = a->inv_bg; dq.alpha = cfg.alpha;
         if (cfg.kind == EXORL_AGENT_APS) { dq.q = a->aps.sfq; dq.task = a->obs + (O - cfg.sf_dim); dq.task_ld = O; }
         dq.use_lambda = a->traits->uses_lambda();
-        if (qf) EXORL_TRY(run_qhead(a, st, 1, 0));   // Q(s, pi(s)), its min-routing gradient (lambda applied later), dz2, sum|Q| partials
+        if (qf) EXORL_TRY(run_qhead(a, st, 1, 0, a->reward));   // Q(s, pi(s)), its min-routing gradient (lambda applied later), dz2, sum|Q| partials
         if (st.stats_in_phase2) {                // lambda needs sum|Q| over the GLOBAL batch (td3_bc.py:154): reduce it while the critic's
             EXORL_TRY(reduce_pairs(a->abs_part, qhead_chunks(B), a->stats, s));          // backward pass runs (it does not depend on lambda)
             EXORL_CHECK_HIP(hipEventRecord(a->ev_stats_ready, s));
@@ -1492,7 +1510,10 @@ int exorl_agent_batch_slots(exorl_agent_t* a, exorl_batch_out* out) {
     out->reward = a->reward; out->discount = a->discount;
     out->next_obs = a->next_obs; out->next_obs_stride = O * 4;
     out->meta = nullptr; out->meta_stride = 0;
-    out->next_action = nullptr; out->next_action_stride = 0; out->next_valid = nullptr;      // no agent kind reads the next action yet
+    // ReBRAC is the column's one reader: while it is set the sampler fills the caller's buffer, otherwise the gather writes neither field
+    out->next_action = a->rebrac.on ? a->rebrac.next_action : nullptr;
+    out->next_action_stride = a->rebrac.on ? A : 0;
+    out->next_valid = a->rebrac.on ? a->rebrac.next_valid : nullptr;
     return 0;
 }
 
@@ -1805,6 +1826,44 @@ int exorl_agent_nn_result(exorl_agent_t* a, void** idx_dev, void** d2_dev, void*
     return 0;
 }
 
+// The ReBRAC buffer's four runs, each padded to 64 floats as every take is: what exorl_agent_rebrac_bytes sizes and exorl_agent_set_rebrac views.
+struct RebracViews { float *next_action, *next_valid, *reward, *part; };
+static RebracViews rebrac_carve(const exorl_agent_cfg& cfg, SimpleCarver& c) {
+    const int64_t B = cfg.batch, A = cfg.act_dim;
+    RebracViews v{};
+    v.next_action = c.take(B * A); v.next_valid = c.take(B); v.reward = c.take(B); v.part = c.take((int64_t)iql_chunks(cfg.batch) * REBRAC_PARTS);
+    return v;
+}
+static int rebrac_cfg_ok(const exorl_agent_cfg* cfg, const char* who) {
+    EXORL_TRY(check_cfg(cfg));
+    EXORL_REQUIRE(cfg->kind == EXORL_AGENT_TD3_BC, "%s: kind %d is not TD3+BC (ReBRAC is a setting of that kind)", who, cfg->kind);
+    return 0;
+}
+
+size_t exorl_agent_rebrac_bytes(const exorl_agent_cfg* cfg) {
+    if (rebrac_cfg_ok(cfg, "agent_rebrac_bytes") != 0) return 0;
+    SimpleCarver c(nullptr);
+    rebrac_carve(*cfg, c);
+    return (size_t)c.off * sizeof(float);
+}
+
+int exorl_agent_set_rebrac(exorl_agent_t* a, void* buf_dev, size_t bytes, float critic_beta) {
+    EXORL_REQUIRE(a, "agent_set_rebrac: null handle");
+    EXORL_TRY(rebrac_cfg_ok(&a->cfg, "agent_set_rebrac"));
+    EXORL_REQUIRE(!a->graph_exec, "agent_set_rebrac: disable the captured graph first (it holds critic_beta and the buffer's pointers)");
+    if (!buf_dev) { a->rebrac = {}; return 0; }      // detach: bytes and critic_beta are not looked at
+    EXORL_REQUIRE(critic_beta >= 0.f, "agent_set_rebrac: critic_beta must be >= 0 (got %g)", critic_beta);      // NaN fails the comparison
+    EXORL_REQUIRE(!a->win_sums && !a->eval_sums, "agent_set_rebrac: ReBRAC has no metric window and no forward-only evaluation: detach the %s first",
+                  a->win_sums ? "metric window (exorl_agent_set_metric_window)" : "eval buffer (exorl_agent_set_eval)");
+    SimpleCarver c(static_cast<float*>(buf_dev));
+    const RebracViews v = rebrac_carve(a->cfg, c);
+    const size_t need = (size_t)c.off * sizeof(float);
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_rebrac: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
+    a->rebrac.next_action = v.next_action; a->rebrac.next_valid = v.next_valid; a->rebrac.reward = v.reward; a->rebrac.part = v.part;
+    a->rebrac.beta = critic_beta; a->rebrac.on = true;
+    return 0;
+}
+
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable) {
     EXORL_REQUIRE(a, "agent_set_parallel_branches: null handle");
     EXORL_REQUIRE(!a->graph_exec, "agent_set_parallel_branches: disable the captured graph first");
@@ -1832,6 +1891,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
         return attach_window("agent_set_metric_window", nullptr, 0, 0, &a->win_sums, &a->win_crit);
     }
     EXORL_REQUIRE(a->traits->metric_window, "agent_set_metric_window: %s has no metric window", a->traits->name);
+    EXORL_REQUIRE(!a->rebrac.on, "agent_set_metric_window: ReBRAC has no metric window (detach it first: exorl_agent_set_rebrac with a null buffer)");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     EXORL_TRY(attach_window("agent_set_metric_window", buf_dev, bytes, window_bytes(a->cfg), &a->win_sums, &a->win_crit));
@@ -1860,6 +1920,7 @@ int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     EXORL_REQUIRE(a, "agent_set_eval: null handle");
     if (!buf_dev) return attach_window("agent_set_eval", nullptr, 0, 0, &a->eval_sums, &a->eval_part);
     EXORL_REQUIRE(a->traits->evaluates, "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
+    EXORL_REQUIRE(!a->rebrac.on, "agent_set_eval: ReBRAC has no forward-only evaluation (detach it first: exorl_agent_set_rebrac with a null buffer)");
     return attach_window("agent_set_eval", buf_dev, bytes, eval_bytes(a->cfg), &a->eval_sums, &a->eval_part);
 }
 
@@ -1868,6 +1929,7 @@ int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
 int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
     EXORL_REQUIRE(a, "agent_evaluate: null handle");
     EXORL_REQUIRE(a->traits->evaluates, "agent_evaluate: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
+    EXORL_REQUIRE(!a->rebrac.on, "agent_evaluate: ReBRAC has no forward-only evaluation (detach it first: exorl_agent_set_rebrac with a null buffer)");
     EXORL_REQUIRE(a->eval_sums, "agent_evaluate: no eval buffer (exorl_agent_set_eval)");
     hipStream_t s = as_stream(stream);
     const auto& cfg = a->cfg;

@@ -527,6 +527,24 @@ struct FqeRowsArgs {
 };
 int fqe_rows(const FqeRowsArgs& a, hipStream_t s);
 int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
+// ReBRAC's row kernel (loss.hip, chunk_rows_kernel<RebracRow>), on iql_rows' chunking: the critic target's penalty as a per-row correction of the
+// reward. From the clipped target-policy sample a~' (rows, A at ld sample_ld), the dataset's next action a' (rows, A at next_ld) with its validity
+// v (rows), reward and discount, in fp32 and in this order (nothing contracted):
+//   s = sum over j ascending of (a~'_j - a'_j)^2;   p = v s;   t = critic_beta p;   r~ = r - D t        (steps 2 and 3: rebrac_reward)
+// so that y = r~ + D min Q' = r + D (min Q' - critic_beta p). critic_beta = 0 and v = 0 leave r~ = r bit for bit. Per chunk the REBRAC_PARTS sums
+// below (the reward's is the dataset's r, not r~). rebrac_sums adds them in chunk order: into sums (raw, REBRAC_P_* order) and / or as partial
+// means over the global batch into EXORL_M_REBRAC_PENALTY, EXORL_M_REBRAC_VALID and EXORL_M_BATCH_REWARD.
+enum { REBRAC_P_PENALTY, REBRAC_P_VALID, REBRAC_P_REWARD, REBRAC_PARTS };
+struct RebracRowsArgs {
+    const float* sample; int64_t sample_ld;
+    const float* next_action; int64_t next_ld;
+    const float *next_valid, *reward, *discount;
+    float *reward_out, *part;                // part: [iql_chunks(rows)][REBRAC_PARTS]
+    int rows, act_dim;
+    float critic_beta;
+};
+int rebrac_rows(const RebracRowsArgs& a, hipStream_t s);
+int rebrac_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
 // mu (rows, A) of a tanh-mean actor forward into the action columns of a critic input (ld = dst_ld): FQE's a' = mu(s') and the value pass's mu(s)
 int fqe_mean_actions(const float* mu, float* dst, int64_t dst_ld, int rows, int A, hipStream_t s);
 // FQE's value pass: q (2, ld) at (s, mu(s)); rows < `rows` -> per-chunk fp64 partials [iql_chunks(rows)][FQE_VALUE_PARTS], added in chunk order to

@@ -712,7 +712,7 @@ int eval_reduce(const EvalArgs& e, hipStream_t s) {
     return 0;
 }
 
-// ---- chunked row kernels: IQL's and FQE's loss rows -> gradients and the metrics' per-chunk sums, one pass -------------------------------------
+// ---- chunked row kernels: IQL's and FQE's loss rows -> gradients, ReBRAC's penalty rows -> the corrected reward; the metrics' per-chunk sums, one pass
 // One thread per row, IQL_CHUNK_ROWS rows per chunk; at most IQL_MAX_WG workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...
 // The partials are per chunk, not per workgroup, so the sums do not depend on the grid. Rows past the end add zeros. Row is the functor of one
 // kind: its arguments (rows, part among them), Row::PARTS and row(m, p), which writes row m's outputs and fills p[PARTS] with its terms.
@@ -779,8 +779,38 @@ struct FqeRow : FqeRowsArgs {
     }
 };
 
-// Part index -> metric slot; -1: no slot of its own. EXORL_M_CRITIC_LOSS is the sum of the two error parts, which sit side by side at err1.
+// ReBRAC: the critic target's penalty folded into the reward the critic step reads (kernels.h has the formula and its order). The one place
+// steps 2 and 3 are written: t = critic_beta p, r~ = r - D t, two products and one subtraction, each rounded on its own.
+__device__ __forceinline__ float rebrac_reward(float r, float D, float critic_beta, float p) {
+#pragma clang fp contract(off)
+    const float t = critic_beta * p;
+    const float Dt = D * t;
+    return r - Dt;
+}
+// A <= 16: the thread walks its row of the sample (pitch O + A, inside the critic's input rows) and of the next action (pitch A)
+struct RebracRow : RebracRowsArgs {
+    static constexpr int PARTS = REBRAC_PARTS;
+    __device__ void row(int m, float* p) const {
+#pragma clang fp contract(off)
+        const float* x = sample + (int64_t)m * sample_ld;
+        const float* y = next_action + (int64_t)m * next_ld;
+        float s = 0.f;
+        for (int j = 0; j < act_dim; ++j) {
+            const float d = x[j] - y[j];
+            const float dd = d * d;
+            s = s + dd;
+        }
+        const float v = next_valid[m], r = reward[m];
+        const float pen = v * s;
+        reward_out[m] = rebrac_reward(r, discount[m], critic_beta, pen);
+        p[REBRAC_P_PENALTY] = pen; p[REBRAC_P_VALID] = v; p[REBRAC_P_REWARD] = r;
+    }
+};
+
+// Part index -> metric slot; -1: no slot of its own. EXORL_M_CRITIC_LOSS is the sum of the two error parts, which sit side by side at err1
+// (err1 < 0: the kind's row kernel forms no loss and the slot is left alone).
 template <int PARTS> struct SumSlots { int slot[PARTS]; int err1; };
+constexpr SumSlots<REBRAC_PARTS> REBRAC_SLOTS = {{EXORL_M_REBRAC_PENALTY, EXORL_M_REBRAC_VALID, EXORL_M_BATCH_REWARD}, -1};
 constexpr SumSlots<IQL_PARTS> IQL_SLOTS = {{EXORL_M_BATCH_REWARD, EXORL_M_CRITIC_TARGET_Q, EXORL_M_CRITIC_Q1, EXORL_M_CRITIC_Q2, -1, -1,
                                             EXORL_M_VALUE_LOSS, EXORL_M_VALUE, EXORL_M_ADV, EXORL_M_ACTOR_WEIGHT}, IQL_P_ERR1};
 constexpr SumSlots<FQE_PARTS> FQE_SLOTS = {{EXORL_M_BATCH_REWARD, EXORL_M_CRITIC_TARGET_Q, EXORL_M_CRITIC_Q1, EXORL_M_CRITIC_Q2, -1, -1}, FQE_P_ERR1};
@@ -803,7 +833,7 @@ __global__ __launch_bounds__(64) void chunk_sums_kernel(const float* __restrict_
 #pragma unroll
         for (int i = 0; i < PARTS; ++i)
             if (to.slot[i] >= 0) metrics[to.slot[i]] = tot[i] * inv_bg;
-        metrics[EXORL_M_CRITIC_LOSS] = (tot[to.err1] + tot[to.err1 + 1]) * inv_bg;
+        if (to.err1 >= 0) metrics[EXORL_M_CRITIC_LOSS] = (tot[to.err1] + tot[to.err1 + 1]) * inv_bg;
     }
 }
 
@@ -827,6 +857,10 @@ int iql_sums(const float* part, int rows, float inv_bg, float* sums, float* metr
 }
 int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
     return chunk_sums(part, rows, inv_bg, sums, metrics, FQE_SLOTS, s);
+}
+int rebrac_rows(const RebracRowsArgs& a, hipStream_t s) { return chunk_rows<RebracRow>(a, s); }
+int rebrac_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
+    return chunk_sums(part, rows, inv_bg, sums, metrics, REBRAC_SLOTS, s);
 }
 
 __global__ __launch_bounds__(256) void fqe_mean_actions_kernel(const float* __restrict__ mu, float* __restrict__ dst, int64_t dst_ld, int rows, int A) {
@@ -897,6 +931,20 @@ extern "C" int exorl_iql_rows(const float* tq, const float* q, const float* v, c
     IqlRowsArgs a{tq, q, v, v_next, reward, discount, dv, dq, w, part, rows, inv_bg, expectile, temperature, max_weight};
     EXORL_TRY(iql_rows(a, as_stream(stream)));
     return iql_sums(part, rows, inv_bg, sums, nullptr, as_stream(stream));
+}
+
+extern "C" int exorl_rebrac_rows(const float* sample, int64_t sample_ld, const float* next_action, int64_t next_action_stride, const float* next_valid,
+                                 const float* reward, const float* discount, int32_t rows, int32_t act_dim, float critic_beta, float inv_bg,
+                                 float* reward_out, float* part, float* sums, void* stream) {
+    using namespace exorl;
+    EXORL_REQUIRE(sample && next_action && next_valid && reward && discount && reward_out && part && sums && rows > 0, "rebrac_rows: bad arguments");
+    EXORL_REQUIRE(act_dim >= 1 && act_dim <= 16 && sample_ld >= act_dim && next_action_stride >= act_dim,
+                  "rebrac_rows: needs 1 <= act_dim <= 16 and both pitches >= act_dim (got %d, %lld, %lld)", act_dim, (long long)sample_ld,
+                  (long long)next_action_stride);
+    EXORL_REQUIRE(critic_beta >= 0.f, "rebrac_rows: critic_beta must be >= 0 (got %g)", critic_beta);
+    RebracRowsArgs a{sample, sample_ld, next_action, next_action_stride, next_valid, reward, discount, reward_out, part, rows, act_dim, critic_beta};
+    EXORL_TRY(rebrac_rows(a, as_stream(stream)));
+    return rebrac_sums(part, rows, inv_bg, sums, nullptr, as_stream(stream));
 }
 
 extern "C" int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float* out_dev, void* stream) {

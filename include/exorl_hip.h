@@ -45,7 +45,8 @@ extern "C" {
                                         EXORL_AGENT_FQE, exorl_agent_fqe_value_bytes / _set_fqe_value / _fqe_value / _fqe_value_read,
                                         exorl_replay_episode_returns, exorl_replay_num_episodes; EXORL_AGENT_PRDC, exorl_replay_build_keys,
                                         exorl_replay_keys, exorl_replay_keys_read, exorl_nn_search, exorl_agent_set_prdc, exorl_agent_nn_result;
-                                        exorl_batch_out.next_action / next_action_stride / next_valid (trailing)) */
+                                        exorl_batch_out.next_action / next_action_stride / next_valid (trailing);
+                                        exorl_agent_rebrac_bytes, exorl_agent_set_rebrac, exorl_rebrac_rows) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -77,7 +78,8 @@ typedef struct {            /* where one sampled minibatch is written (device me
     /* Trailing and optional (a caller that zero-fills the struct gets neither): the action taken at next_obs, action[idx + nstep], and whether
      * the episode holds it (idx + nstep <= len). An invalid sample gets next_valid = 0 and a row of zeros; the arena row behind the episode's last
      * (the next episode's dummy row, or past the arena's end) is never read. A plain copy: bit-exact, untouched by exorl_replay_set_obs_norm.
-     * Written by the same gather launch; with next_action NULL every other output keeps its bits. */
+     * Written by the same gather launch; with next_action NULL every other output keeps its bits. Read by the TD3+BC step while ReBRAC is
+     * set on the handle (exorl_agent_set_rebrac): the critic target's penalty on (a~' - a')^2. */
     float*  next_action;  int64_t next_action_stride;   /* floats between samples; NULL: not written */
     float*  next_valid;                                 /* (B) contiguous, 1.0f or 0.0f; NULL iff next_action is NULL */
 } exorl_batch_out;
@@ -274,6 +276,10 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_M_ACTOR_WEIGHT 13   /* mean w */
 /* EXORL_AGENT_PRDC only: slot 10 (CQL's and IQL's names above mean nothing for PRDC); slots 0..9 are TD3+BC's. */
 #define EXORL_M_NN_DIST      10   /* mean over the batch of sqrt(d2) to the nearest key */
+/* EXORL_AGENT_TD3_BC while ReBRAC is set (exorl_agent_set_rebrac) only: slots 10 and 11. Slots 0..9 are TD3+BC's, with critic_target_q the mean
+ * of the penalised y and batch_reward the mean of the dataset's r (never of the corrected reward). */
+#define EXORL_M_REBRAC_PENALTY 10 /* mean over the global batch of p = v sum_j (a~'_j - a'_j)^2, before critic_beta */
+#define EXORL_M_REBRAC_VALID   11 /* mean of v, the share of rows whose episode holds the next action */
 #define EXORL_N_METRICS        16
 
 typedef struct {
@@ -310,7 +316,8 @@ int exorl_agent_flat(exorl_agent_t* a, int32_t net, int32_t what, void** ptr_dev
  * copies (bf16 shadows) and, if sync_target != 0, copies critic -> critic_target (td3_bc.py:93). */
 int exorl_agent_params_changed(exorl_agent_t* a, int32_t sync_target, void* stream);
 /* Where the sampler should write this agent's minibatch (zero-copy hand-off replay -> update). Every field is written: next_action /
- * next_valid are NULL (no agent kind reads the next action yet). */
+ * next_valid point into the ReBRAC buffer (next_action_stride = act_dim) while one is set (exorl_agent_set_rebrac), the only reader of the
+ * column, and are NULL otherwise. */
 int exorl_agent_batch_slots(exorl_agent_t* a, exorl_batch_out* out);
 /* Copies a caller-provided device batch (contiguous f32 (B,O) (B,A) (B) (B) (B,O)) into the batch slots. */
 int exorl_agent_set_batch(exorl_agent_t* a, const float* obs_dev, const float* action_dev,
@@ -369,6 +376,23 @@ int exorl_agent_set_prdc(exorl_agent_t* a, exorl_replay_t* r, float beta);
 /* EXORL_AGENT_PRDC: the last search's results in the workspace, idx (batch) int32, d2 (batch) and a_nn (batch, act_dim) float32, and the
  * number of key ranges of the bound table (0: none bound). */
 int exorl_agent_nn_result(exorl_agent_t* a, void** idx_dev, void** d2_dev, void** a_nn_dev, int32_t* splits);
+/* ReBRAC (Tarasov et al., NeurIPS 2023) as a per-handle setting of EXORL_AGENT_TD3_BC: the critic target gains a penalty on the distance
+ * between the clipped target-policy sample a~' and the action a' the dataset took at s',
+ *   y = r + D (min_i Q'_i(s', a~') - critic_beta p),   p = v sum_j (a~'_j - a'_j)^2,   v = next_valid,
+ * formed as a per-row correction of the reward, r~ = r - D (critic_beta p) in fp32 in that order (p = v s with s summed over j ascending),
+ * which every reader of the reward in the critic step then reads: one more row kernel per step, the plan stays 0, 1, 2, 3 and no exchange
+ * is added under data parallelism. critic_beta = 0, and v = 0 on a row, leave that row's step TD3+BC's bit for bit. The actor loss
+ * beta_a sum_j (pi(s) - a)^2 - Q / mean|Q| is TD3+BC's times beta_a act_dim with cfg.alpha = 1 / (beta_a act_dim).
+ * The buffer is the caller's device memory, exorl_agent_rebrac_bytes(cfg) bytes, 256-byte aligned, alive while set: four runs, each padded
+ * to 64 floats, next_action (batch, act_dim), next_valid (batch), r~ (batch) and the row kernel's per-chunk sums
+ * [exorl_iql_rows_chunks(batch)][3]; r~ and the sums are written before they are read on every step. exorl_agent_rebrac_bytes needs no
+ * device and returns 0, with exorl_last_error set, for another kind and for every configuration exorl_agent_create refuses.
+ * exorl_agent_set_rebrac refuses, launching nothing: a null handle; another kind; a handle with a captured graph (the graph holds
+ * critic_beta and the pointers); and, attaching, critic_beta < 0 or NaN; a handle with a metric window or an eval window attached; a buffer
+ * too small or misaligned. buf_dev NULL detaches, whatever bytes and critic_beta are: the handle is TD3+BC again. While set, exorl_agent_batch_slots hands out the buffer's next_action / next_valid,
+ * exorl_agent_set_batch leaves them to the caller, and exorl_agent_set_metric_window, exorl_agent_set_eval and exorl_agent_evaluate refuse. */
+size_t exorl_agent_rebrac_bytes(const exorl_agent_cfg* cfg);
+int exorl_agent_set_rebrac(exorl_agent_t* a, void* buf_dev, size_t bytes, float critic_beta);
 /* Policy inference for n rows: out = mean (eval) or TruncatedNormal sample (clip=None). */
 int exorl_agent_act(exorl_agent_t* a, const float* obs_dev, int32_t n, float stddev, int32_t eval_mode,
                     const float* noise_dev, float* action_out_dev, void* stream);
@@ -571,6 +595,14 @@ int exorl_fqe_rows(const float* tq_dev, const float* q_dev, const float* reward_
 int exorl_iql_rows(const float* tq_dev, const float* q_dev, const float* v_dev, const float* v_next_dev, const float* reward_dev,
                    const float* discount_dev, int32_t rows, float inv_bg, float expectile, float temperature, float max_weight,
                    float* dv_dev, float* dq_dev, float* w_dev, float* part_dev, float* sums_dev, void* stream);
+/* ReBRAC's row kernel on caller-made rows (unit test hook): sample (rows, act_dim at pitch sample_ld) the clipped target-policy sample,
+ * next_action (rows, act_dim at pitch next_action_stride), next_valid, reward, discount (rows) in; reward_out (rows) = r - D (critic_beta p),
+ * p = next_valid sum_j (sample_j - next_action_j)^2, as the step forms it (exorl_agent_set_rebrac above), and sums[3] = the sums over the rows
+ * of p, next_valid and r, added per chunk in chunk order with no atomics (the same bits on every run). 1 <= act_dim <= 16; inv_bg is unused by
+ * the raw sums. part: scratch of 3 * exorl_iql_rows_chunks(rows) floats. */
+int exorl_rebrac_rows(const float* sample_dev, int64_t sample_ld, const float* next_action_dev, int64_t next_action_stride,
+                      const float* next_valid_dev, const float* reward_dev, const float* discount_dev, int32_t rows, int32_t act_dim,
+                      float critic_beta, float inv_bg, float* reward_out_dev, float* part_dev, float* sums_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Intrinsic-reward modules of the reward-free DDPG-backbone agents (states observations).
