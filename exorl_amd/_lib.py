@@ -22,6 +22,8 @@ M_CRITIC_CQL, M_CRITIC_CQL_LOGSUM, M_ACTOR_ALPHA, M_ACTOR_ALPHA_LOSS, M_ACTOR_EN
 M_VALUE_LOSS, M_VALUE, M_ADV, M_ACTOR_WEIGHT = 10, 11, 12, 13        # IQL's use of slots 10..13
 M_NN_DIST = 10            # PRDC's use of slot 10
 M_REBRAC_PENALTY, M_REBRAC_VALID = 10, 11       # TD3+BC's use of slots 10 and 11 while ReBRAC is set
+M_SARSA_VALID = 11        # TD3+BC's, TD3's, CRR's and FQE's use of slot 11 while the SARSA setting is on
+SARSA_PARTS = 1           # its row kernel's sums per chunk (kernels.h SARSA_P_*): valid
 REBRAC_PARTS = 3          # the row kernel's sums per chunk (kernels.h REBRAC_P_*): penalty, valid, reward
 CRR_WEIGHT = {'identity': 0, 'indicator': 1, 'exp': 2}
 PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2, 3
@@ -195,6 +197,8 @@ PROTOTYPES = {
     'exorl_agent_nn_result': (C.c_int, [c_void_p, P(c_void_p), P(c_void_p), P(c_void_p), P(c_int32)]),
     'exorl_agent_rebrac_bytes': (c_size_t, [P(AgentCfg)]),
     'exorl_agent_set_rebrac': (C.c_int, [c_void_p, c_void_p, c_size_t, c_float]),
+    'exorl_agent_sarsa_bytes': (c_size_t, [P(AgentCfg)]),
+    'exorl_agent_set_sarsa': (C.c_int, [c_void_p, c_void_p, c_size_t]),
     'exorl_agent_act': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_act_host': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
@@ -247,6 +251,7 @@ PROTOTYPES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_rebrac_rows': (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    'exorl_next_action_rows': (C.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -14,6 +14,8 @@ Reference classes mirrored (file:line in /root/reference):
   FQEAgent    no reference file: fitted Q evaluation of a frozen policy (the class's docstring is its definition)
   PRDCAgent   no reference file: TD3+BC regularised to the nearest dataset point; defined in exorl_amd/prdc.py, reachable as agents.PRDCAgent
   ReBRACAgent no reference file: TD3+BC with a critic penalty on the dataset's next action; defined in exorl_amd/rebrac.py, agents.ReBRACAgent
+  OneStepTD3BCAgent, OneStepCRRAgent   no reference file: one-step RL, the parent's step with a SARSA critic target; exorl_amd/onestep.py
+  BehaviorQAgent   no reference file: FQE's machinery on the dataset's next action, Q^beta; exorl_amd/fqe.py
 
 Python here is orchestration only: it builds the initial weights with torch's CPU RNG in the reference's
 construction order (so a given torch.manual_seed yields the reference's initial parameters), hands batches
@@ -528,6 +530,30 @@ def eval_values(sums, rows, action_dim, has_critic=True):
     return out
 
 
+class _NextActionBatch:
+    """For the classes whose step reads the dataset's action at next_obs from a buffer set on the engine (ReBRACAgent: set_rebrac; the
+    one-step agents and BehaviorQAgent: set_sarsa), in front of an _AgentBase class in the bases. An HBM iterator (iter(loader),
+    ArenaIterator) writes next_action / next_valid into the buffer in its gather launch; a plain iterator yields
+    (obs, action, reward, discount, next_obs, next_action[, next_valid]), next_valid all ones when absent."""
+
+    def _load_batch(self, replay_iter):
+        if hasattr(replay_iter, 'sample_into'):          # HBM sampler: the gather writes the next action into the slots
+            return super()._load_batch(replay_iter)
+        batch = next(replay_iter)
+        if len(batch) < 6:
+            raise ValueError(f'{type(self).__name__}: a batch of {len(batch)} tensors has no next_action: the iterator must yield (obs, action, '
+                             'reward, discount, next_obs, next_action[, next_valid]), as a has_next_action=True loader does')
+        self.engine.set_batch(*batch[:5])
+        self.engine.set_next_action(batch[5], batch[6] if len(batch) > 6 else None)
+
+    def _attach_sarsa(self):
+        """The SARSA buffer, allocated and set on the fresh engine (AgentEngine.set_sarsa): the last step of a constructor, and so of
+        unpickling. Zeros: a plain iterator's first batch may bring no next_valid."""
+        eng = self.engine
+        eng.set_sarsa(torch.zeros(eng.sarsa_bytes(), dtype=torch.uint8, device=eng.device))
+        self._slots = None          # the slots now carry next_action / next_valid
+
+
 _CRITIC_METRICS = [(L.M_BATCH_REWARD, 'batch_reward'), (L.M_CRITIC_TARGET_Q, 'critic_target_q'), (L.M_CRITIC_Q1, 'critic_q1'),
                    (L.M_CRITIC_Q2, 'critic_q2'), (L.M_CRITIC_LOSS, 'critic_loss'), (L.M_ACTOR_LOSS, 'actor_loss')]
 
@@ -649,21 +675,22 @@ class FQEAgent(_UnitStd, _AgentBase):
         self._train_all()
 
     @staticmethod
-    def _check_policy(agent, dims=None):
-        """ValueError unless `agent` is one of POLICY_CLASSES and, with dims = the evaluator's (obs_dim, action_dim, hidden_dim), of that shape."""
+    def _check_policy(agent, dims=None, who='FQEAgent'):
+        """ValueError unless `agent` is one of POLICY_CLASSES and, with dims = the evaluator's (obs_dim, action_dim, hidden_dim), of that shape.
+        who: the class the caller used, for the message."""
         if type(agent).__name__ not in FQEAgent.POLICY_CLASSES or not isinstance(agent, _AgentBase):
-            raise ValueError(f'FQEAgent: cannot evaluate a {type(agent).__name__}: the frozen actor is the offline tanh-mean Actor of '
+            raise ValueError(f'{who}: cannot evaluate a {type(agent).__name__}: the frozen actor is the offline tanh-mean Actor of '
                              'TD3BCAgent, TD3Agent, BCAgent, CRRAgent or IQLAgent. CQLAgent (a 2A-wide tanh-Gaussian head) and the DDPG '
                              'family (a trunk / policy layout) are out of scope')
         theirs = (agent.engine.obs_dim, agent.engine.act_dim, agent.engine.hidden_dim)
         if dims is not None and tuple(dims) != theirs:
-            raise ValueError(f'FQEAgent.set_policy: (obs_dim, action_dim, hidden_dim) = {theirs} of the policy, {tuple(dims)} of the evaluator')
+            raise ValueError(f'{who}.set_policy: (obs_dim, action_dim, hidden_dim) = {theirs} of the policy, {tuple(dims)} of the evaluator')
 
     def set_policy(self, agent):
         """Copies `agent`'s actor (the policy to score) and its observation normaliser. ValueError for a class other than TD3BCAgent,
         TD3Agent, BCAgent, CRRAgent and IQLAgent (CQLAgent's 2A-wide head and the DDPG family's trunk layout are out of scope) or when
         obs_dim, action_dim or hidden_dim differ."""
-        self._check_policy(agent, (self.engine.obs_dim, self.engine.act_dim, self.engine.hidden_dim))
+        self._check_policy(agent, (self.engine.obs_dim, self.engine.act_dim, self.engine.hidden_dim), type(self).__name__)
         self.actor.load_state_dict(agent.actor.state_dict())
         if agent.obs_norm_mean is not None:
             self.set_obs_normalizer(agent.obs_norm_mean, agent.obs_norm_inv)
@@ -675,7 +702,7 @@ class FQEAgent(_UnitStd, _AgentBase):
     def for_policy(cls, agent, **overrides):
         """An evaluator shaped after `agent` with its actor copied in: obs / action / hidden sizes, device, batch size and precision are the
         policy's, lr and critic_target_tau its own where it has them (else 1e-4 and 0.01); `overrides` replaces any constructor argument."""
-        cls._check_policy(agent)
+        cls._check_policy(agent, who=cls.__name__)
         eng = agent.engine
         prec = {v: k for k, v in reversed(list(PRECISION.items()))}[eng.cfg.precision]
         kw = dict(name='fqe', obs_shape=(eng.obs_dim,), action_shape=(eng.act_dim,), device=agent.device, lr=getattr(agent, 'lr', 1e-4),
@@ -1785,4 +1812,10 @@ def __getattr__(name):
     if name == 'ReBRACAgent':          # likewise: exorl_amd.rebrac.ReBRACAgent, defined beside its buffer and batch handling
         from .rebrac import ReBRACAgent
         return ReBRACAgent
+    if name in ('OneStepTD3BCAgent', 'OneStepCRRAgent'):      # exorl_amd.onestep: the SARSA-critic agents
+        from . import onestep
+        return getattr(onestep, name)
+    if name == 'BehaviorQAgent':       # exorl_amd.fqe.BehaviorQAgent, beside its driver
+        from .fqe import BehaviorQAgent
+        return BehaviorQAgent
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

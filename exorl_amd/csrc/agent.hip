@@ -453,6 +453,13 @@ struct exorl_agent {
         float beta = 0.f;
         bool on = false;
     } rebrac;
+    // The SARSA setting of the TD3+BC, TD3, CRR and FQE kinds (exorl_agent_set_sarsa; `on` is the mode): views of the caller's buffer, laid out by
+    // sarsa_carve. The sampler writes next_action / next_valid (exorl_agent_batch_slots); the row kernel writes part on every step before
+    // anything reads it. Never on together with rebrac.
+    struct {
+        float *next_action = nullptr, *next_valid = nullptr, *part = nullptr;
+        bool on = false;
+    } sarsa;
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -887,6 +894,20 @@ static int run_qhead(exorl_agent* a, const Step& st, int mode, int tq_slots, con
     return qhead(q, st.s, met);
 }
 
+// The SARSA setting (exorl_agent_set_sarsa), off: nothing. Behind the launch that wrote the kind's own target action into xc_next's action columns
+// and ahead of the target critic's forward: the dataset's a' over it on the rows with next_valid != 0, a masked copy in a launch of its own (the
+// actor head's sample epilogue, which writes those columns for TD3+BC, keeps its bits and the base kind its launch count).
+static int sarsa_rows(exorl_agent* a, hipStream_t s) {
+    if (!a->sarsa.on) return 0;
+    const int B = a->cfg.batch, O = a->cfg.obs_dim, A = a->cfg.act_dim;
+    return next_action_rows(NextActionRowsArgs{a->sarsa.next_action, A, a->sarsa.next_valid, a->xc_next + O, O + A, a->sarsa.part, B, A}, s);
+}
+// ... and its metric, the partial mean of next_valid over the global batch, where the step's other metrics are written
+static int sarsa_sums(exorl_agent* a, hipStream_t s) {
+    if (!a->sarsa.on) return 0;
+    return next_action_sums(a->sarsa.part, a->cfg.batch, a->inv_bg, nullptr, a->metrics, s);
+}
+
 // -- phase 0: everything up to the critic gradients -------------------------------------------------
 static int phase0(exorl_agent* a, const Step& st) {
     const auto& cfg = a->cfg;
@@ -914,6 +935,7 @@ static int phase0(exorl_agent* a, const Step& st) {
                                              a->rebrac.reward, a->rebrac.part, B, A, a->rebrac.beta}, s));
         reward = a->rebrac.reward;
     }
+    EXORL_TRY(sarsa_rows(a, s));                // the SARSA setting: the dataset's a' over a~' where the episode holds it
     const bool qf = st.qfuse;
     int tq_slots = 0;
     EXORL_TRY(twin_forward(a, s, st.fk, a->xc_next, true, qf, &tq_slots));      // target critic (td3_bc.py:126) and critic (td3_bc.py:130)
@@ -930,6 +952,7 @@ static int phase0(exorl_agent* a, const Step& st) {
         EXORL_TRY(critic_loss(qv, tqv, reward, a->discount, a->dq, a->metrics, B, a->inv_bg, s));   // :133-137
     // behind critic_loss, which reported the mean of r~ as batch_reward: the row kernel's sums put the dataset's r there, and the penalty's slots
     if (a->rebrac.on && st.metric_kernels) EXORL_TRY(rebrac_sums(a->rebrac.part, B, a->inv_bg, nullptr, a->metrics, s));
+    if (st.metric_kernels) EXORL_TRY(sarsa_sums(a, s));
     DoutSpec td{};                              // d(2 x MSE)/dQ computed where it is consumed (:127-131)
     td.mode = EXORL_DOUT_TD; td.q = qv; td.tq = tqv; td.reward = reward; td.discount = a->discount; td.inv_bg = a->inv_bg;
     td.task = task; td.task_ld = O;
@@ -1136,10 +1159,12 @@ static int fqe_phase10(exorl_agent* a, const Step& st) {
     // rows 0..B-1 of the stacked input are next_obs: the actor runs on those alone
     EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa, O, B, a->fa, false, true, cfg.precision, s));
     EXORL_TRY(fqe_mean_actions(a->fa.out, a->xc_next + O, W, B, A, s));
+    EXORL_TRY(sarsa_rows(a, s));                // the SARSA setting: the dataset's a' over mu(s') where the episode holds it (behaviour Q)
     EXORL_TRY(twin_forward(a, s, st.fk, a->xc_next, true));      // the target's forward on (s', mu(s')) and the critic's on (s, a)
     FqeRowsArgs r{a->ft.out, a->fc.out, a->reward, a->discount, a->dq, a->fqe.part, B, a->inv_bg};
     EXORL_TRY(fqe_rows(r, s));
     if (st.metric_kernels) EXORL_TRY(fqe_sums(a->fqe.part, B, a->inv_bg, nullptr, a->metrics, s));
+    if (st.metric_kernels) EXORL_TRY(sarsa_sums(a, s));
     return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->xc_cur, B, a->fc, a->dq);
 }
 
@@ -1510,10 +1535,12 @@ int exorl_agent_batch_slots(exorl_agent_t* a, exorl_batch_out* out) {
     out->reward = a->reward; out->discount = a->discount;
     out->next_obs = a->next_obs; out->next_obs_stride = O * 4;
     out->meta = nullptr; out->meta_stride = 0;
-    // ReBRAC is the column's one reader: while it is set the sampler fills the caller's buffer, otherwise the gather writes neither field
-    out->next_action = a->rebrac.on ? a->rebrac.next_action : nullptr;
-    out->next_action_stride = a->rebrac.on ? A : 0;
-    out->next_valid = a->rebrac.on ? a->rebrac.next_valid : nullptr;
+    // ReBRAC and the SARSA setting read the column (never both on one handle): while one is set the sampler fills the caller's buffer, otherwise
+    // the gather writes neither field
+    float* const na = a->rebrac.on ? a->rebrac.next_action : a->sarsa.on ? a->sarsa.next_action : nullptr;
+    out->next_action = na;
+    out->next_action_stride = na ? A : 0;
+    out->next_valid = a->rebrac.on ? a->rebrac.next_valid : a->sarsa.on ? a->sarsa.next_valid : nullptr;
     return 0;
 }
 
@@ -1853,6 +1880,7 @@ int exorl_agent_set_rebrac(exorl_agent_t* a, void* buf_dev, size_t bytes, float 
     EXORL_REQUIRE(!a->graph_exec, "agent_set_rebrac: disable the captured graph first (it holds critic_beta and the buffer's pointers)");
     if (!buf_dev) { a->rebrac = {}; return 0; }      // detach: bytes and critic_beta are not looked at
     EXORL_REQUIRE(critic_beta >= 0.f, "agent_set_rebrac: critic_beta must be >= 0 (got %g)", critic_beta);      // NaN fails the comparison
+    EXORL_REQUIRE(!a->sarsa.on, "agent_set_rebrac: the SARSA setting is on (detach it first: exorl_agent_set_sarsa with a null buffer)");
     EXORL_REQUIRE(!a->win_sums && !a->eval_sums, "agent_set_rebrac: ReBRAC has no metric window and no forward-only evaluation: detach the %s first",
                   a->win_sums ? "metric window (exorl_agent_set_metric_window)" : "eval buffer (exorl_agent_set_eval)");
     SimpleCarver c(static_cast<float*>(buf_dev));
@@ -1861,6 +1889,47 @@ int exorl_agent_set_rebrac(exorl_agent_t* a, void* buf_dev, size_t bytes, float 
     EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_rebrac: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
     a->rebrac.next_action = v.next_action; a->rebrac.next_valid = v.next_valid; a->rebrac.reward = v.reward; a->rebrac.part = v.part;
     a->rebrac.beta = critic_beta; a->rebrac.on = true;
+    return 0;
+}
+
+// The SARSA buffer's three runs, each padded to 64 floats as every take is: what exorl_agent_sarsa_bytes sizes and exorl_agent_set_sarsa views.
+struct SarsaViews { float *next_action, *next_valid, *part; };
+static SarsaViews sarsa_carve(const exorl_agent_cfg& cfg, SimpleCarver& c) {
+    const int64_t B = cfg.batch, A = cfg.act_dim;
+    SarsaViews v{};
+    v.next_action = c.take(B * A); v.next_valid = c.take(B); v.part = c.take((int64_t)iql_chunks(cfg.batch) * SARSA_PARTS);
+    return v;
+}
+// the kinds whose critic step feeds the target critic one action per row that the setting can replace: phase0's three and FQE
+static int sarsa_cfg_ok(const exorl_agent_cfg* cfg, const char* who) {
+    EXORL_TRY(check_cfg(cfg));
+    const int k = cfg->kind;
+    EXORL_REQUIRE(k == EXORL_AGENT_TD3_BC || k == EXORL_AGENT_TD3 || k == EXORL_AGENT_CRR || k == EXORL_AGENT_FQE,
+                  "%s: kind %d is not TD3+BC, TD3, CRR or FQE (the SARSA target is a setting of those kinds)", who, k);
+    return 0;
+}
+
+size_t exorl_agent_sarsa_bytes(const exorl_agent_cfg* cfg) {
+    if (sarsa_cfg_ok(cfg, "agent_sarsa_bytes") != 0) return 0;
+    SimpleCarver c(nullptr);
+    sarsa_carve(*cfg, c);
+    return (size_t)c.off * sizeof(float);
+}
+
+int exorl_agent_set_sarsa(exorl_agent_t* a, void* buf_dev, size_t bytes) {
+    EXORL_REQUIRE(a, "agent_set_sarsa: null handle");
+    EXORL_TRY(sarsa_cfg_ok(&a->cfg, "agent_set_sarsa"));
+    EXORL_REQUIRE(!a->graph_exec, "agent_set_sarsa: disable the captured graph first (it holds the buffer's pointers)");
+    if (!buf_dev) { a->sarsa = {}; return 0; }      // detach: bytes is not looked at
+    EXORL_REQUIRE(!a->rebrac.on, "agent_set_sarsa: ReBRAC is set on this handle (detach it first: exorl_agent_set_rebrac with a null buffer)");
+    EXORL_REQUIRE(!a->win_sums && !a->eval_sums, "agent_set_sarsa: the SARSA setting has no metric window and no forward-only evaluation: detach the %s first",
+                  a->win_sums ? "metric window (exorl_agent_set_metric_window)" : "eval buffer (exorl_agent_set_eval)");
+    SimpleCarver c(static_cast<float*>(buf_dev));
+    const SarsaViews v = sarsa_carve(a->cfg, c);
+    const size_t need = (size_t)c.off * sizeof(float);
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_sarsa: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
+    a->sarsa.next_action = v.next_action; a->sarsa.next_valid = v.next_valid; a->sarsa.part = v.part;
+    a->sarsa.on = true;
     return 0;
 }
 
@@ -1892,6 +1961,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
     }
     EXORL_REQUIRE(a->traits->metric_window, "agent_set_metric_window: %s has no metric window", a->traits->name);
     EXORL_REQUIRE(!a->rebrac.on, "agent_set_metric_window: ReBRAC has no metric window (detach it first: exorl_agent_set_rebrac with a null buffer)");
+    EXORL_REQUIRE(!a->sarsa.on, "agent_set_metric_window: the SARSA setting has no metric window (detach it first: exorl_agent_set_sarsa with a null buffer)");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     EXORL_TRY(attach_window("agent_set_metric_window", buf_dev, bytes, window_bytes(a->cfg), &a->win_sums, &a->win_crit));
@@ -1921,6 +1991,7 @@ int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     if (!buf_dev) return attach_window("agent_set_eval", nullptr, 0, 0, &a->eval_sums, &a->eval_part);
     EXORL_REQUIRE(a->traits->evaluates, "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
     EXORL_REQUIRE(!a->rebrac.on, "agent_set_eval: ReBRAC has no forward-only evaluation (detach it first: exorl_agent_set_rebrac with a null buffer)");
+    EXORL_REQUIRE(!a->sarsa.on, "agent_set_eval: the SARSA setting has no forward-only evaluation (detach it first: exorl_agent_set_sarsa with a null buffer)");
     return attach_window("agent_set_eval", buf_dev, bytes, eval_bytes(a->cfg), &a->eval_sums, &a->eval_part);
 }
 
@@ -1930,6 +2001,7 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
     EXORL_REQUIRE(a, "agent_evaluate: null handle");
     EXORL_REQUIRE(a->traits->evaluates, "agent_evaluate: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
     EXORL_REQUIRE(!a->rebrac.on, "agent_evaluate: ReBRAC has no forward-only evaluation (detach it first: exorl_agent_set_rebrac with a null buffer)");
+    EXORL_REQUIRE(!a->sarsa.on, "agent_evaluate: the SARSA setting has no forward-only evaluation (detach it first: exorl_agent_set_sarsa with a null buffer)");
     EXORL_REQUIRE(a->eval_sums, "agent_evaluate: no eval buffer (exorl_agent_set_eval)");
     hipStream_t s = as_stream(stream);
     const auto& cfg = a->cfg;
@@ -1995,6 +2067,10 @@ int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream) {
     const auto& cfg = a->cfg;
     const int B = cfg.batch, O = cfg.obs_dim, A = cfg.act_dim, W = O + A, H = cfg.hidden_dim, prec = cfg.precision;
     EXORL_TRY(open_step(a, nullptr, s));
+    if (a->sarsa.on) {      // behaviour Q: the critic at the staged (s, a) of the obs and action slots, Q^beta(s0, a0) on episode starts; no actor forward
+        EXORL_TRY(net_forward(a->critic, a->flat[EXORL_NET_CRITIC][EXORL_T_PARAM], a->sh_critic, a->xc_cur, W, B, a->fc, false, false, prec, s));
+        return fqe_value_reduce(a->fc.out, B, rows, a->fqe.value_part, a->fqe.value_sums, s);
+    }
     const FwdBufs f = a->fa.rows_from(B, H, A);
     EXORL_TRY(net_forward(a->actor, a->flat[EXORL_NET_ACTOR][EXORL_T_PARAM], a->sh_actor, a->xa + (int64_t)B * O, O, B, f, false, true, prec, s));
     EXORL_TRY(fqe_mean_actions(f.out, a->xc_pi + O, W, B, A, s));

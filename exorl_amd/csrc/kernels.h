@@ -545,6 +545,21 @@ struct RebracRowsArgs {
 };
 int rebrac_rows(const RebracRowsArgs& a, hipStream_t s);
 int rebrac_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
+// The SARSA setting's row kernel (loss.hip, chunk_rows_kernel<NextActionRow>), on the same chunking: the dataset's next action a' (rows, A at
+// next_ld) over the action columns the kind's own launch left in the target critic's input (dst: rows, A at dst_ld = O + A), on the rows whose
+// validity v (rows) is not 0. A masked copy, bit-exact; a row with v = 0 is not written and the columns outside the A are never touched. Per
+// chunk the one sum of v. next_action_sums adds them in chunk order: into sums[0] (raw) and / or as the partial mean over the global batch
+// into EXORL_M_SARSA_VALID.
+enum { SARSA_P_VALID, SARSA_PARTS };
+struct NextActionRowsArgs {
+    const float* next_action; int64_t next_ld;
+    const float* next_valid;
+    float* dst; int64_t dst_ld;
+    float* part;                             // [iql_chunks(rows)][SARSA_PARTS]
+    int rows, act_dim;
+};
+int next_action_rows(const NextActionRowsArgs& a, hipStream_t s);
+int next_action_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s);
 // mu (rows, A) of a tanh-mean actor forward into the action columns of a critic input (ld = dst_ld): FQE's a' = mu(s') and the value pass's mu(s)
 int fqe_mean_actions(const float* mu, float* dst, int64_t dst_ld, int rows, int A, hipStream_t s);
 // FQE's value pass: q (2, ld) at (s, mu(s)); rows < `rows` -> per-chunk fp64 partials [iql_chunks(rows)][FQE_VALUE_PARTS], added in chunk order to

@@ -712,7 +712,8 @@ int eval_reduce(const EvalArgs& e, hipStream_t s) {
     return 0;
 }
 
-// ---- chunked row kernels: IQL's and FQE's loss rows -> gradients, ReBRAC's penalty rows -> the corrected reward; the metrics' per-chunk sums, one pass
+// ---- chunked row kernels: IQL's and FQE's loss rows -> gradients, ReBRAC's penalty rows -> the corrected reward, the SARSA setting's next-action
+// rows -> the target critic's action columns; the metrics' per-chunk sums, one pass
 // One thread per row, IQL_CHUNK_ROWS rows per chunk; at most IQL_MAX_WG workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...
 // The partials are per chunk, not per workgroup, so the sums do not depend on the grid. Rows past the end add zeros. Row is the functor of one
 // kind: its arguments (rows, part among them), Row::PARTS and row(m, p), which writes row m's outputs and fills p[PARTS] with its terms.
@@ -807,10 +808,26 @@ struct RebracRow : RebracRowsArgs {
     }
 };
 
+// The SARSA setting: the dataset's a' over the kind's own target action where the episode holds a' (kernels.h). A <= 16: the thread copies its
+// row's A floats (pitch A in, pitch O + A out); v = 0 leaves the row as the launch before wrote it, so that row's step is the base kind's.
+struct NextActionRow : NextActionRowsArgs {
+    static constexpr int PARTS = SARSA_PARTS;
+    __device__ void row(int m, float* p) const {
+        const float v = next_valid[m];
+        if (v != 0.f) {
+            const float* y = next_action + (int64_t)m * next_ld;
+            float* x = dst + (int64_t)m * dst_ld;
+            for (int j = 0; j < act_dim; ++j) x[j] = y[j];
+        }
+        p[SARSA_P_VALID] = v;
+    }
+};
+
 // Part index -> metric slot; -1: no slot of its own. EXORL_M_CRITIC_LOSS is the sum of the two error parts, which sit side by side at err1
 // (err1 < 0: the kind's row kernel forms no loss and the slot is left alone).
 template <int PARTS> struct SumSlots { int slot[PARTS]; int err1; };
 constexpr SumSlots<REBRAC_PARTS> REBRAC_SLOTS = {{EXORL_M_REBRAC_PENALTY, EXORL_M_REBRAC_VALID, EXORL_M_BATCH_REWARD}, -1};
+constexpr SumSlots<SARSA_PARTS> SARSA_SLOTS = {{EXORL_M_SARSA_VALID}, -1};
 constexpr SumSlots<IQL_PARTS> IQL_SLOTS = {{EXORL_M_BATCH_REWARD, EXORL_M_CRITIC_TARGET_Q, EXORL_M_CRITIC_Q1, EXORL_M_CRITIC_Q2, -1, -1,
                                             EXORL_M_VALUE_LOSS, EXORL_M_VALUE, EXORL_M_ADV, EXORL_M_ACTOR_WEIGHT}, IQL_P_ERR1};
 constexpr SumSlots<FQE_PARTS> FQE_SLOTS = {{EXORL_M_BATCH_REWARD, EXORL_M_CRITIC_TARGET_Q, EXORL_M_CRITIC_Q1, EXORL_M_CRITIC_Q2, -1, -1}, FQE_P_ERR1};
@@ -861,6 +878,10 @@ int fqe_sums(const float* part, int rows, float inv_bg, float* sums, float* metr
 int rebrac_rows(const RebracRowsArgs& a, hipStream_t s) { return chunk_rows<RebracRow>(a, s); }
 int rebrac_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
     return chunk_sums(part, rows, inv_bg, sums, metrics, REBRAC_SLOTS, s);
+}
+int next_action_rows(const NextActionRowsArgs& a, hipStream_t s) { return chunk_rows<NextActionRow>(a, s); }
+int next_action_sums(const float* part, int rows, float inv_bg, float* sums, float* metrics, hipStream_t s) {
+    return chunk_sums(part, rows, inv_bg, sums, metrics, SARSA_SLOTS, s);
 }
 
 __global__ __launch_bounds__(256) void fqe_mean_actions_kernel(const float* __restrict__ mu, float* __restrict__ dst, int64_t dst_ld, int rows, int A) {
@@ -945,6 +966,18 @@ extern "C" int exorl_rebrac_rows(const float* sample, int64_t sample_ld, const f
     RebracRowsArgs a{sample, sample_ld, next_action, next_action_stride, next_valid, reward, discount, reward_out, part, rows, act_dim, critic_beta};
     EXORL_TRY(rebrac_rows(a, as_stream(stream)));
     return rebrac_sums(part, rows, inv_bg, sums, nullptr, as_stream(stream));
+}
+
+extern "C" int exorl_next_action_rows(const float* next_action, int64_t next_action_stride, const float* next_valid, int32_t rows, int32_t act_dim,
+                                      float inv_bg, float* dst, int64_t dst_ld, float* part, float* sums, void* stream) {
+    using namespace exorl;
+    EXORL_REQUIRE(next_action && next_valid && dst && part && sums && rows > 0, "next_action_rows: bad arguments");
+    EXORL_REQUIRE(act_dim >= 1 && act_dim <= 16 && next_action_stride >= act_dim && dst_ld >= act_dim,
+                  "next_action_rows: needs 1 <= act_dim <= 16 and both pitches >= act_dim (got %d, %lld, %lld)", act_dim, (long long)next_action_stride,
+                  (long long)dst_ld);
+    NextActionRowsArgs a{next_action, next_action_stride, next_valid, dst, dst_ld, part, rows, act_dim};
+    EXORL_TRY(next_action_rows(a, as_stream(stream)));
+    return next_action_sums(part, rows, inv_bg, sums, nullptr, as_stream(stream));
 }
 
 extern "C" int exorl_debug_philox_normal(uint64_t seed, uint64_t counter, int64_t n, float* out_dev, void* stream) {

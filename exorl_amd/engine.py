@@ -118,6 +118,7 @@ class AgentEngine(_Phased):
         self.has_alpha = kind == 'cql'
         self._eval = self._fqe_value = None       # the evaluation and value windows (set_eval, set_fqe_value): attached on first use
         self._rebrac = None                       # the ReBRAC buffer (set_rebrac): the caller's, kept alive here while set
+        self._sarsa = None                        # the SARSA buffer (set_sarsa), likewise; never both
 
     # -- pickling support, as PixelEngine's: everything that defines the training state, as CPU data
     def export_state(self):
@@ -408,21 +409,42 @@ class AgentEngine(_Phased):
         L.check(self.lib.exorl_agent_set_rebrac(self.h, buf.data_ptr(), buf.numel(), float(critic_beta)))
         self._rebrac = buf
 
+    def sarsa_bytes(self):
+        """Bytes of the SARSA buffer for this configuration (exorl_agent_sarsa_bytes); raises for a kind other than TD3+BC, TD3, CRR and FQE."""
+        n = int(self.lib.exorl_agent_sarsa_bytes(C.byref(self.cfg)))
+        if n == 0:
+            raise L.ExorlError(self.lib.exorl_last_error().decode())
+        return n
+
+    def set_sarsa(self, buf):
+        """The SARSA target on a TD3+BC, TD3, CRR or FQE engine (exorl_agent_set_sarsa): `buf` a uint8 device tensor of at least
+        sarsa_bytes(), 256-byte aligned, kept alive here; None detaches and the engine is the base kind again. Refused while a graph is
+        captured, while ReBRAC is set and while a metric window or an eval window is attached. Batch slots handed out before the call are
+        stale: ask batch_slots() again."""
+        torch.cuda.current_stream(self.device).synchronize()      # a step in flight may still read the buffer this call replaces or lets go
+        if buf is None:
+            L.check(self.lib.exorl_agent_set_sarsa(self.h, None, 0))
+            self._sarsa = None
+            return
+        L.check(self.lib.exorl_agent_set_sarsa(self.h, buf.data_ptr(), buf.numel()))
+        self._sarsa = buf
+
     def set_next_action(self, next_action, next_valid=None):
         """The dataset's action at next_obs, (B, A), and whether the episode holds it, (B) of 1.0 / 0.0 (None: every row valid), into the
-        ReBRAC buffer: what the HBM sampler writes there itself, for batches that come from a plain iterator (set_batch). A row with
-        next_valid 0 is stored as zeros whatever the caller's row holds, as the gather stores it."""
-        if self._rebrac is None:
-            raise L.ExorlError('set_next_action: no ReBRAC buffer is set (set_rebrac)')
+        ReBRAC or the SARSA buffer, whichever is set: what the HBM sampler writes there itself, for batches that come from a plain iterator
+        (set_batch). A row with next_valid 0 is stored as zeros whatever the caller's row holds, as the gather stores it."""
+        buf = self._rebrac if self._rebrac is not None else self._sarsa
+        if buf is None:
+            raise L.ExorlError('set_next_action: no ReBRAC buffer is set (set_rebrac) and no SARSA buffer (set_sarsa)')
         B, A = self.batch, self.act_dim
         na = self._dev(next_action)
         nv = torch.ones(B, dtype=torch.float32, device=self.device) if next_valid is None else self._dev(next_valid)
         if na.numel() != B * A or nv.numel() != B:
             raise L.ExorlError(f'next_action has {na.numel()} elements and next_valid {nv.numel()}, expected {B * A} and {B}')
         na = torch.where(nv.reshape(B, 1) != 0, na.reshape(B, A), torch.zeros((), device=self.device))      # the gather's rule: zeros where invalid
-        slots, f32 = self.batch_slots(), self._rebrac[:self._rebrac.numel() // 4 * 4].view(torch.float32)     # the library says where the two runs lie
+        slots, f32 = self.batch_slots(), buf[:buf.numel() // 4 * 4].view(torch.float32)     # the library says where the two runs lie
         for ptr, src in ((slots.next_action, na), (slots.next_valid, nv)):
-            o = (ptr - self._rebrac.data_ptr()) // 4
+            o = (ptr - buf.data_ptr()) // 4
             f32[o:o + src.numel()].copy_(src.reshape(-1))
 
     def nn_result(self):

@@ -9,10 +9,10 @@ which the HBM replay emits from its gather launch. Also reachable as exorl_amd.a
 import torch
 
 from . import _lib as L
-from .agents import _CRITIC_METRICS, TD3BCAgent
+from .agents import _CRITIC_METRICS, TD3BCAgent, _NextActionBatch
 
 
-class ReBRACAgent(TD3BCAgent):
+class ReBRACAgent(_NextActionBatch, TD3BCAgent):
     """ReBRAC on TD3+BC's nets (the critics have LayerNorm already) and step. With a~' the clipped target-policy sample TD3+BC draws, a' the
     action the dataset took at s' and v = 1 where the episode holds it (0 where the sample's n steps end the episode: no penalty there),
         y    = r + D (min_i Q'_i(s', a~') - critic_bc_coef v sum_j (a~'_j - a'_j)^2)
@@ -51,13 +51,3 @@ class ReBRACAgent(TD3BCAgent):
         buf = torch.zeros(eng.rebrac_bytes(), dtype=torch.uint8, device=eng.device)      # zeros: a plain iterator's first batch may bring no next_valid
         eng.set_rebrac(buf, self.critic_bc_coef)
         self._slots = None          # the slots now carry next_action / next_valid
-
-    def _load_batch(self, replay_iter):
-        if hasattr(replay_iter, 'sample_into'):          # HBM sampler: the gather writes the next action into the slots
-            return super()._load_batch(replay_iter)
-        batch = next(replay_iter)
-        if len(batch) < 6:
-            raise ValueError(f'{type(self).__name__}: a batch of {len(batch)} tensors has no next_action: the iterator must yield (obs, action, '
-                             'reward, discount, next_obs, next_action[, next_valid]), as a has_next_action=True loader does')
-        self.engine.set_batch(*batch[:5])
-        self.engine.set_next_action(batch[5], batch[6] if len(batch) > 6 else None)

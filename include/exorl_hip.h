@@ -46,7 +46,8 @@ extern "C" {
                                         exorl_replay_episode_returns, exorl_replay_num_episodes; EXORL_AGENT_PRDC, exorl_replay_build_keys,
                                         exorl_replay_keys, exorl_replay_keys_read, exorl_nn_search, exorl_agent_set_prdc, exorl_agent_nn_result;
                                         exorl_batch_out.next_action / next_action_stride / next_valid (trailing);
-                                        exorl_agent_rebrac_bytes, exorl_agent_set_rebrac, exorl_rebrac_rows) */
+                                        exorl_agent_rebrac_bytes, exorl_agent_set_rebrac, exorl_rebrac_rows;
+                                        exorl_agent_sarsa_bytes, exorl_agent_set_sarsa, exorl_next_action_rows) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -79,7 +80,8 @@ typedef struct {            /* where one sampled minibatch is written (device me
      * the episode holds it (idx + nstep <= len). An invalid sample gets next_valid = 0 and a row of zeros; the arena row behind the episode's last
      * (the next episode's dummy row, or past the arena's end) is never read. A plain copy: bit-exact, untouched by exorl_replay_set_obs_norm.
      * Written by the same gather launch; with next_action NULL every other output keeps its bits. Read by the TD3+BC step while ReBRAC is
-     * set on the handle (exorl_agent_set_rebrac): the critic target's penalty on (a~' - a')^2. */
+     * set on the handle (exorl_agent_set_rebrac): the critic target's penalty on (a~' - a')^2; and by the critic step of TD3+BC, TD3, CRR and FQE
+     * while the SARSA setting is on (exorl_agent_set_sarsa): the action the target critic is fed at s'. */
     float*  next_action;  int64_t next_action_stride;   /* floats between samples; NULL: not written */
     float*  next_valid;                                 /* (B) contiguous, 1.0f or 0.0f; NULL iff next_action is NULL */
 } exorl_batch_out;
@@ -280,6 +282,8 @@ typedef struct exorl_agent exorl_agent_t;
  * of the penalised y and batch_reward the mean of the dataset's r (never of the corrected reward). */
 #define EXORL_M_REBRAC_PENALTY 10 /* mean over the global batch of p = v sum_j (a~'_j - a'_j)^2, before critic_beta */
 #define EXORL_M_REBRAC_VALID   11 /* mean of v, the share of rows whose episode holds the next action */
+/* EXORL_AGENT_TD3_BC, _TD3, _CRR and _FQE while the SARSA setting is on (exorl_agent_set_sarsa) only: slot 11; the other slots are the kind's. */
+#define EXORL_M_SARSA_VALID    11 /* mean over the global batch of v = next_valid, the share of rows whose target is at the dataset's a' */
 #define EXORL_N_METRICS        16
 
 typedef struct {
@@ -316,8 +320,8 @@ int exorl_agent_flat(exorl_agent_t* a, int32_t net, int32_t what, void** ptr_dev
  * copies (bf16 shadows) and, if sync_target != 0, copies critic -> critic_target (td3_bc.py:93). */
 int exorl_agent_params_changed(exorl_agent_t* a, int32_t sync_target, void* stream);
 /* Where the sampler should write this agent's minibatch (zero-copy hand-off replay -> update). Every field is written: next_action /
- * next_valid point into the ReBRAC buffer (next_action_stride = act_dim) while one is set (exorl_agent_set_rebrac), the only reader of the
- * column, and are NULL otherwise. */
+ * next_valid point into the ReBRAC buffer or the SARSA buffer (next_action_stride = act_dim) while one is set (exorl_agent_set_rebrac,
+ * exorl_agent_set_sarsa: the column's readers, never both on one handle), and are NULL otherwise. */
 int exorl_agent_batch_slots(exorl_agent_t* a, exorl_batch_out* out);
 /* Copies a caller-provided device batch (contiguous f32 (B,O) (B,A) (B) (B) (B,O)) into the batch slots. */
 int exorl_agent_set_batch(exorl_agent_t* a, const float* obs_dev, const float* action_dev,
@@ -393,6 +397,28 @@ int exorl_agent_nn_result(exorl_agent_t* a, void** idx_dev, void** d2_dev, void*
  * exorl_agent_set_batch leaves them to the caller, and exorl_agent_set_metric_window, exorl_agent_set_eval and exorl_agent_evaluate refuse. */
 size_t exorl_agent_rebrac_bytes(const exorl_agent_cfg* cfg);
 int exorl_agent_set_rebrac(exorl_agent_t* a, void* buf_dev, size_t bytes, float critic_beta);
+/* The SARSA target as a per-handle setting of EXORL_AGENT_TD3_BC, _TD3, _CRR (critic step in phase 0) and _FQE (phase 10): the critic learns
+ * Q^beta, the behaviour policy's value, from the dataset's own (s, a, r, s', a'). One-step RL (Brandfonbrener et al., NeurIPS 2021) is this
+ * critic under the kind's unchanged actor step; on FQE it is behaviour Q evaluation. With v = next_valid, the action fed to the target critic
+ * at s' is the dataset's a' where v != 0 and the kind's own target action where v = 0 (the sample's n steps end the episode there and the
+ * dataset holds no a'): TD3's clipped sample a~', FQE's mu(s'). One row kernel, launched behind the launch that writes the kind's own action
+ * and ahead of the critics' forward, copies a' over the action columns of the target critic's input on the rows with v != 0: a bit-exact
+ * masked copy, one more launch per step (and one single-wave sums launch on a step whose metrics are read), no other kernel changes, the plan
+ * stays the kind's and data parallelism needs no new exchange (the rule is per row). A row with v = 0 is the base kind's row bit for bit and
+ * a batch of them its step; with v = 1 on every row the critic's trajectory does not depend on the actor. The copy is a launch of its own and
+ * not part of the actor head's sample epilogue, which TD3+BC's step keeps as it is, bits and launch count.
+ * The buffer is the caller's device memory, exorl_agent_sarsa_bytes(cfg) bytes (the same at every precision and world_size), 256-byte
+ * aligned, alive while set: three runs, each padded to 64 floats, next_action (batch, act_dim), next_valid (batch) and the row kernel's
+ * per-chunk sums [exorl_iql_rows_chunks(batch)][1], written before they are read on every step. exorl_agent_sarsa_bytes needs no device and
+ * returns 0, with exorl_last_error set, for another kind and for every configuration exorl_agent_create refuses.
+ * exorl_agent_set_sarsa refuses, launching nothing: a null handle; another kind; a handle with a captured graph (the graph holds the
+ * pointers); and, attaching, a handle with ReBRAC set, a metric window or an eval window attached; a buffer too small or misaligned. buf_dev
+ * NULL detaches, whatever bytes is: the handle is the base kind again. While set, exorl_agent_batch_slots hands out the buffer's next_action /
+ * next_valid, exorl_agent_set_batch leaves them to the caller, exorl_agent_set_rebrac, exorl_agent_set_metric_window, exorl_agent_set_eval and
+ * exorl_agent_evaluate refuse, and exorl_agent_fqe_value reads Q(s, a) at the obs and action slots (the critic on its own input rows, no actor
+ * forward): Q^beta(s0, a0) when the slots hold episode starts. */
+size_t exorl_agent_sarsa_bytes(const exorl_agent_cfg* cfg);
+int exorl_agent_set_sarsa(exorl_agent_t* a, void* buf_dev, size_t bytes);
 /* Policy inference for n rows: out = mean (eval) or TruncatedNormal sample (clip=None). */
 int exorl_agent_act(exorl_agent_t* a, const float* obs_dev, int32_t n, float stddev, int32_t eval_mode,
                     const float* noise_dev, float* action_out_dev, void* stream);
@@ -461,7 +487,9 @@ int exorl_agent_eval_read(exorl_agent_t* a, double* sums_host, int64_t* rows_hos
  * refused or not FQE), 256-byte aligned, alive while it is set; setting empties it, NULL detaches. The pass reads the action, reward, discount and
  * next_obs slots only to stage them (rows >= `rows` and those slots may hold anything, NaN included: nothing of them reaches the sums) and is
  * read-only towards parameters, targets, weight images, gradients, Adam moments, the step state and the metrics: exorl_agent_update or
- * exorl_agent_step_graph afterwards continue bit for bit. Not between the phases of a step driven through exorl_agent_update_phase. */
+ * exorl_agent_step_graph afterwards continue bit for bit. Not between the phases of a step driven through exorl_agent_update_phase.
+ * While the SARSA setting is on (exorl_agent_set_sarsa) the pass runs no actor forward: both critics at (s, a) of the obs AND action slots,
+ * rows < `rows` of both then being read, into the same sums (Q_i(s, a) for Q_i(s, mu(s))). */
 size_t exorl_agent_fqe_value_bytes(const exorl_agent_cfg* cfg);
 int exorl_agent_set_fqe_value(exorl_agent_t* a, void* buf_dev, size_t bytes);
 int exorl_agent_fqe_value(exorl_agent_t* a, int32_t rows, void* stream);
@@ -603,6 +631,13 @@ int exorl_iql_rows(const float* tq_dev, const float* q_dev, const float* v_dev, 
 int exorl_rebrac_rows(const float* sample_dev, int64_t sample_ld, const float* next_action_dev, int64_t next_action_stride,
                       const float* next_valid_dev, const float* reward_dev, const float* discount_dev, int32_t rows, int32_t act_dim,
                       float critic_beta, float inv_bg, float* reward_out_dev, float* part_dev, float* sums_dev, void* stream);
+/* The SARSA setting's row kernel on caller-made rows (unit test hook): next_action (rows, act_dim at pitch next_action_stride) and next_valid
+ * (rows) in; dst (rows, act_dim at pitch dst_ld) takes next_action's row where next_valid != 0 and keeps its own elsewhere, bit for bit, and
+ * nothing of dst outside those act_dim columns is written (dst_ld = obs_dim + act_dim with dst at the action columns in the step); sums[1] =
+ * the sum of next_valid, added per chunk in chunk order with no atomics. 1 <= act_dim <= 16; inv_bg is unused by the raw sum. part: scratch of
+ * exorl_iql_rows_chunks(rows) floats. */
+int exorl_next_action_rows(const float* next_action_dev, int64_t next_action_stride, const float* next_valid_dev, int32_t rows, int32_t act_dim,
+                           float inv_bg, float* dst_dev, int64_t dst_ld, float* part_dev, float* sums_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Intrinsic-reward modules of the reward-free DDPG-backbone agents (states observations).
