@@ -23,6 +23,7 @@ M_VALUE_LOSS, M_VALUE, M_ADV, M_ACTOR_WEIGHT = 10, 11, 12, 13        # IQL's use
 M_NN_DIST = 10            # PRDC's use of slot 10
 M_REBRAC_PENALTY, M_REBRAC_VALID = 10, 11       # TD3+BC's use of slots 10 and 11 while ReBRAC is set
 M_SARSA_VALID = 11        # TD3+BC's, TD3's, CRR's and FQE's use of slot 11 while the SARSA setting is on
+M_CALQL_BOUND = 15        # CQL's use of slot 15 while Cal-QL is set: the share of policy-action entries held up by the return-to-go
 SARSA_PARTS = 1           # its row kernel's sums per chunk (kernels.h SARSA_P_*): valid
 REBRAC_PARTS = 3          # the row kernel's sums per chunk (kernels.h REBRAC_P_*): penalty, valid, reward
 CRR_WEIGHT = {'identity': 0, 'indicator': 1, 'exp': 2}
@@ -172,6 +173,10 @@ PROTOTYPES = {
     'exorl_replay_get_mt': (C.c_int, [c_void_p, c_void_p, P(c_int32), c_void_p, P(c_int32)]),
     'exorl_replay_seed_philox': (C.c_int, [c_void_p, c_uint64]),
     'exorl_replay_sample': (C.c_int, [c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p, P(BatchOut), c_void_p, c_void_p]),
+    'exorl_replay_sample_mc': (C.c_int, [c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p, P(BatchOut), c_void_p, c_void_p, c_void_p]),
+    'exorl_replay_build_returns': (C.c_int, [c_void_p, c_float, c_void_p]),
+    'exorl_replay_returns': (C.c_int, [c_void_p, P(c_void_p), P(c_float), P(c_uint64), P(c_int32)]),
+    'exorl_replay_returns_read': (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'exorl_replay_last_pairs': (C.c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'exorl_comm_unique_id': (C.c_int, [c_void_p]),
     'exorl_comm_init': (C.c_int, [c_int32, c_int32, c_void_p, P(c_void_p)]),
@@ -199,6 +204,8 @@ PROTOTYPES = {
     'exorl_agent_set_rebrac': (C.c_int, [c_void_p, c_void_p, c_size_t, c_float]),
     'exorl_agent_sarsa_bytes': (c_size_t, [P(AgentCfg)]),
     'exorl_agent_set_sarsa': (C.c_int, [c_void_p, c_void_p, c_size_t]),
+    'exorl_agent_calql_bytes': (c_size_t, [P(AgentCfg)]),
+    'exorl_agent_set_calql': (C.c_int, [c_void_p, c_void_p, c_size_t]),
     'exorl_agent_act': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_act_host': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p]),
     'exorl_agent_metrics': (C.c_int, [c_void_p, c_void_p, c_void_p]),
@@ -252,6 +259,7 @@ PROTOTYPES = {
     'exorl_rebrac_rows': (C.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     'exorl_next_action_rows': (C.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'exorl_cql_dq_rows': (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -16,6 +16,7 @@ Reference classes mirrored (file:line in /root/reference):
   ReBRACAgent no reference file: TD3+BC with a critic penalty on the dataset's next action; defined in exorl_amd/rebrac.py, agents.ReBRACAgent
   OneStepTD3BCAgent, OneStepCRRAgent   no reference file: one-step RL, the parent's step with a SARSA critic target; exorl_amd/onestep.py
   BehaviorQAgent   no reference file: FQE's machinery on the dataset's next action, Q^beta; exorl_amd/fqe.py
+  CalQLAgent  no reference file: CQL bounded below by the dataset's return-to-go (Cal-QL); defined in exorl_amd/calql.py, agents.CalQLAgent
 
 Python here is orchestration only: it builds the initial weights with torch's CPU RNG in the reference's
 construction order (so a given torch.manual_seed yields the reference's initial parameters), hands batches
@@ -1815,6 +1816,9 @@ def __getattr__(name):
     if name in ('OneStepTD3BCAgent', 'OneStepCRRAgent'):      # exorl_amd.onestep: the SARSA-critic agents
         from . import onestep
         return getattr(onestep, name)
+    if name == 'CalQLAgent':           # exorl_amd.calql.CalQLAgent, defined beside its buffer and batch handling
+        from .calql import CalQLAgent
+        return CalQLAgent
     if name == 'BehaviorQAgent':       # exorl_amd.fqe.BehaviorQAgent, beside its driver
         from .fqe import BehaviorQAgent
         return BehaviorQAgent

@@ -460,6 +460,12 @@ struct exorl_agent {
         float *next_action = nullptr, *next_valid = nullptr, *part = nullptr;
         bool on = false;
     } sarsa;
+    // Cal-QL, a setting of the CQL kind (exorl_agent_set_calql; `on` is the mode): the caller's buffer holds mc_return (B), the dataset's
+    // return-to-go of each row, written by the sampler (exorl_replay_sample_mc; the captured gather) or by the caller before every step.
+    struct {
+        float* mc_return = nullptr;
+        bool on = false;
+    } calql;
     WeightImages sh_actor{}, sh_critic{}, sh_target{};
     ShadowSpec spec_actor{}, spec_critic{};
     Partials pa{}, pc{};
@@ -478,6 +484,7 @@ struct exorl_agent {
     hipStream_t capture_stream = nullptr;
     exorl_replay* graph_replay = nullptr;
     uint64_t graph_weights_epoch = 0;        // the replay's exorl_replay_set_weights count at capture: the graph samples that table
+    float graph_gamma = 0.f;                 // the capture's gamma: Cal-QL's gather reads a return-to-go column built with the same bits
     bool graph_norm_on = false;              // the replay's normaliser at capture, on or off: the graph holds the normalising or the copying gather
     uint64_t graph_replay_ctr = 0;           // host mirror of state->replay_counter: eager samples drawn between two launches move the replay's own
     exorl_intr* graph_intr = nullptr;        // joint graph (exorl_agent_enable_graph_intr): the module whose step rides in front of the agent's
@@ -1060,7 +1067,7 @@ static int cql_phase0a(exorl_agent* a, const Step& st, bool split) {
     EXORL_TRY(net_forward(a->critic, Pc, a->sh_critic, a->cql.x_all, W, R, a->fc, true, false, prec, s));     // cql.py:166,179-184 in one pass
     if (split)      // this rank's penalty sums into stats[2], stats[3]
         EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->cql.dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
-                                a->cql.sc + 1, &a->state->critic, cfg.target_cql_penalty, 1, a->stats + 2));
+                                a->cql.sc + 1, &a->state->critic, cfg.target_cql_penalty, 1, a->stats + 2, a->calql.mc_return));
     return 0;
 }
 
@@ -1069,7 +1076,8 @@ static int cql_phase0b(exorl_agent* a, const Step& st, bool split) {
     hipStream_t s = st.s;
     const int B = cfg.batch, n = cfg.n_samples;
     EXORL_TRY(cql_critic_dq(a->fc.out, a->ft.out, a->reward, a->discount, a->cql.dq_all, a->metrics, B, n, cfg.alpha, a->inv_bg, s,
-                            cfg.use_critic_lagrange ? a->cql.sc + 1 : nullptr, &a->state->critic, cfg.target_cql_penalty, split ? 2 : 0, a->stats + 2));
+                            cfg.use_critic_lagrange ? a->cql.sc + 1 : nullptr, &a->state->critic, cfg.target_cql_penalty, split ? 2 : 0, a->stats + 2,
+                            a->calql.mc_return));
     return net_grads_from(a, st, net_view(a, EXORL_NET_CRITIC), a->cql.x_all, (3 * n + 1) * B, a->fc, a->cql.dq_all);
 }
 
@@ -1693,6 +1701,11 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     EXORL_TRY(prdc_bound(a, "agent_enable_graph"));
     EXORL_REQUIRE(replay_frame_stack(r) == 1, "agent_enable_graph: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): the "
                   "captured step stages its inputs from whole arena rows; sample a frame-stacked arena eagerly", replay_frame_stack(r));
+    if (a->calql.on) {      // the captured gather reads the replay's return-to-go column: it must stand, built with this gamma
+        const ReplayReturns g = replay_returns(r);
+        EXORL_REQUIRE(g.valid && memcmp(&g.gamma, &gamma, sizeof(float)) == 0, "agent_enable_graph: Cal-QL is set (exorl_agent_set_calql) and the replay "
+                      "has %s (exorl_replay_build_returns)", g.valid ? "a return-to-go column built with another gamma" : "no return-to-go column, or a stale one");
+    }
     EXORL_TRY(release_graph(a));
     if (!a->capture_stream) EXORL_CHECK_HIP(hipStreamCreateWithFlags(&a->capture_stream, hipStreamNonBlocking));
     exorl_batch_out slots;
@@ -1731,7 +1744,7 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     StageOut stage{a->xa, a->xc_cur, a->xc_next, a->xc_pi, a->cfg.obs_dim, a->cfg.act_dim, a->cfg.batch, a->has_critic ? 1 : 0, a->state};
     const bool staged = replay_obs_bytes(r) == a->cfg.obs_dim * 4;
     int rc = replay_sample_impl(r, a->cfg.batch, nstep, gamma, EXORL_SAMPLER_PHILOX, nullptr, &slots, nullptr, a->capture_stream,
-                                &a->state->replay_counter, staged ? &stage : nullptr);
+                                &a->state->replay_counter, staged ? &stage : nullptr, a->calql.mc_return);
     if (rc == 0 && meta_dim > 0) rc = copy_meta_columns(a->obs, a->next_obs, a->cfg.obs_dim, a->cfg.batch, O_raw, meta_dim, a->capture_stream);
     // the module reads the batch slots and writes the reward slot only: what the sampler staged for the networks (observations and actions)
     // stays valid, and the agent's step reads the reward from its slot after this
@@ -1749,6 +1762,7 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     a->graph_replay = r;
     a->graph_weights_epoch = replay_weights_epoch(r);
     a->graph_norm_on = replay_norm_on(r);
+    a->graph_gamma = gamma;
     a->graph_replay_ctr = ctr;
     a->graph_intr = it;
     return 0;
@@ -1933,6 +1947,36 @@ int exorl_agent_set_sarsa(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     return 0;
 }
 
+// Cal-QL's buffer: one run, mc_return (B), padded to 64 floats as every take is.
+static int calql_cfg_ok(const exorl_agent_cfg* cfg, const char* who) {
+    EXORL_TRY(check_cfg(cfg));
+    EXORL_REQUIRE(cfg->kind == EXORL_AGENT_CQL, "%s: kind %d is not CQL (Cal-QL is a setting of that kind)", who, cfg->kind);
+    return 0;
+}
+
+size_t exorl_agent_calql_bytes(const exorl_agent_cfg* cfg) {
+    if (calql_cfg_ok(cfg, "agent_calql_bytes") != 0) return 0;
+    SimpleCarver c(nullptr);
+    c.take(cfg->batch);
+    return (size_t)c.off * sizeof(float);
+}
+
+int exorl_agent_set_calql(exorl_agent_t* a, void* buf_dev, size_t bytes) {
+    EXORL_REQUIRE(a, "agent_set_calql: null handle");
+    EXORL_TRY(calql_cfg_ok(&a->cfg, "agent_set_calql"));
+    EXORL_REQUIRE(!a->graph_exec, "agent_set_calql: disable the captured graph first (it holds the buffer's pointer)");
+    if (!buf_dev) { a->calql = {}; return 0; }      // detach: bytes is not looked at
+    EXORL_REQUIRE(!a->win_sums && !a->eval_sums, "agent_set_calql: Cal-QL has no metric window and no forward-only evaluation: detach the %s first",
+                  a->win_sums ? "metric window (exorl_agent_set_metric_window)" : "eval buffer (exorl_agent_set_eval)");
+    SimpleCarver c(static_cast<float*>(buf_dev));
+    float* const mc = c.take(a->cfg.batch);
+    const size_t need = (size_t)c.off * sizeof(float);
+    EXORL_REQUIRE(bytes >= need && (uintptr_t)buf_dev % 256 == 0, "agent_set_calql: buffer %zu B (need %zu B, 256-byte aligned)", bytes, need);
+    a->calql.mc_return = mc;
+    a->calql.on = true;
+    return 0;
+}
+
 int exorl_agent_set_parallel_branches(exorl_agent_t* a, int32_t enable) {
     EXORL_REQUIRE(a, "agent_set_parallel_branches: null handle");
     EXORL_REQUIRE(!a->graph_exec, "agent_set_parallel_branches: disable the captured graph first");
@@ -1962,6 +2006,7 @@ int exorl_agent_set_metric_window(exorl_agent_t* a, void* buf_dev, size_t bytes)
     EXORL_REQUIRE(a->traits->metric_window, "agent_set_metric_window: %s has no metric window", a->traits->name);
     EXORL_REQUIRE(!a->rebrac.on, "agent_set_metric_window: ReBRAC has no metric window (detach it first: exorl_agent_set_rebrac with a null buffer)");
     EXORL_REQUIRE(!a->sarsa.on, "agent_set_metric_window: the SARSA setting has no metric window (detach it first: exorl_agent_set_sarsa with a null buffer)");
+    EXORL_REQUIRE(!a->calql.on, "agent_set_metric_window: Cal-QL has no metric window (detach it first: exorl_agent_set_calql with a null buffer)");
     EXORL_REQUIRE(a->cfg.world_size == 1, "agent_set_metric_window: the metric window belongs to the one-process step; this agent was built for "
                   "world_size=%d (its metrics are partial means that the caller all-reduces)", a->cfg.world_size);
     EXORL_TRY(attach_window("agent_set_metric_window", buf_dev, bytes, window_bytes(a->cfg), &a->win_sums, &a->win_crit));
@@ -1992,6 +2037,7 @@ int exorl_agent_set_eval(exorl_agent_t* a, void* buf_dev, size_t bytes) {
     EXORL_REQUIRE(a->traits->evaluates, "agent_set_eval: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
     EXORL_REQUIRE(!a->rebrac.on, "agent_set_eval: ReBRAC has no forward-only evaluation (detach it first: exorl_agent_set_rebrac with a null buffer)");
     EXORL_REQUIRE(!a->sarsa.on, "agent_set_eval: the SARSA setting has no forward-only evaluation (detach it first: exorl_agent_set_sarsa with a null buffer)");
+    EXORL_REQUIRE(!a->calql.on, "agent_set_eval: Cal-QL has no forward-only evaluation (detach it first: exorl_agent_set_calql with a null buffer)");
     return attach_window("agent_set_eval", buf_dev, bytes, eval_bytes(a->cfg), &a->eval_sums, &a->eval_part);
 }
 
@@ -2002,6 +2048,7 @@ int exorl_agent_evaluate(exorl_agent_t* a, void* stream) {
     EXORL_REQUIRE(a->traits->evaluates, "agent_evaluate: kind %d has no forward-only evaluation (TD3+BC, TD3, CRR, CQL and BC have)", a->cfg.kind);
     EXORL_REQUIRE(!a->rebrac.on, "agent_evaluate: ReBRAC has no forward-only evaluation (detach it first: exorl_agent_set_rebrac with a null buffer)");
     EXORL_REQUIRE(!a->sarsa.on, "agent_evaluate: the SARSA setting has no forward-only evaluation (detach it first: exorl_agent_set_sarsa with a null buffer)");
+    EXORL_REQUIRE(!a->calql.on, "agent_evaluate: Cal-QL has no forward-only evaluation (detach it first: exorl_agent_set_calql with a null buffer)");
     EXORL_REQUIRE(a->eval_sums, "agent_evaluate: no eval buffer (exorl_agent_set_eval)");
     hipStream_t s = as_stream(stream);
     const auto& cfg = a->cfg;
@@ -2102,6 +2149,11 @@ int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
     EXORL_REQUIRE(replay_norm_on(a->graph_replay) == a->graph_norm_on, "agent_step_graph: exorl_replay_set_obs_norm switched the "
                   "normaliser %s after the capture: the graph holds the other gather kernel (call exorl_agent_enable_graph again)",
                   a->graph_norm_on ? "off" : "on");
+    if (a->calql.on) {
+        const ReplayReturns g = replay_returns(a->graph_replay);
+        EXORL_REQUIRE(g.valid && memcmp(&g.gamma, &a->graph_gamma, sizeof(float)) == 0, "agent_step_graph: the replay's return-to-go column is stale "
+                      "or was rebuilt with another gamma after the capture: Cal-QL's gather reads it (call exorl_replay_build_returns with the capture's gamma)");
+    }
     const uint64_t ctr = replay_philox_counter(a->graph_replay);
     if (ctr != a->graph_replay_ctr) EXORL_TRY(set_device_u64(&a->state->replay_counter, ctr, as_stream(stream)));      // eager batches were drawn in between
     a->graph_replay_ctr = ctr + 1;

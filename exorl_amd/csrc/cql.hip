@@ -67,29 +67,46 @@ int cql_build_inputs(const float* obs, const float* action, const float* raw2, C
 
 // critic_loss = mse(Q1,y) + mse(Q2,y) + alpha * (mean_b lse1 + mean_b lse2 - mean(Q1+Q2))      (cql.py:162-223)
 // d/dq[net][row]: alpha * softmax_row / Bg on every row; data rows add 2 (q - y)/Bg - alpha/Bg.
+// Cal-QL (mc != nullptr, exorl_agent_set_calql): the policy-action entries k in [n, 3n) of row b enter the penalty as q^ = (q >= m) ? q : m with
+// m = mc[b], the dataset's return-to-go: the row maximum, the exponent sum, lse and the softmax use q^, and a bounded entry (q^ = m, a constant
+// of the critic) gets dq = +0. The random entries, the data entry, y, the mse and the Lagrange step are CQL's. metrics[EXORL_M_CALQL_BOUND] =
+// (bounded entries of both nets) / (4 n Bg), 0 without mc. With mc null, or -inf everywhere, every value is CQL's bit for bit.
+__device__ __forceinline__ float calql_entry(const float* __restrict__ q, int k, int B, int b, int n, bool cal, float m, bool& bounded) {
+    const float x = q[(int64_t)k * B + b];
+    bounded = cal && k >= n && !(x >= m);
+    return bounded ? m : x;
+}
+
 __global__ __launch_bounds__(1024) void cql_critic_dq_kernel(const float* __restrict__ q_all, const float* __restrict__ tq,
                                                              const float* __restrict__ reward, const float* __restrict__ discount,
                                                              float* __restrict__ dq_all, float* __restrict__ metrics, int B, int n,
                                                              float cql_alpha_in, float inv_bg, CqlScalars* lag,
-                                                             const AdamConst* __restrict__ cp, float target_penalty, int mode, float* gsum) {
+                                                             const AdamConst* __restrict__ cp, float target_penalty, int mode, float* gsum,
+                                                             const float* __restrict__ mc) {
 #pragma clang fp contract(off)
-    __shared__ float sm[7][16];
+    __shared__ float sm[8][16];
     __shared__ float sh_alpha;
     const int K = 3 * n;                     // re-evaluated rows per sample; the data row is the (K+1)-th entry
     const int64_t R = (int64_t)(K + 1) * B;
     // pass 1: the batch scalars (the penalty decides the Lagrange multiplier before any gradient can be formed)
-    float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // r, y, q1, q2, mse, lse, (q1+q2)
+    const bool cal = mc != nullptr;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // r, y, q1, q2, mse, lse, (q1+q2), bounded entries
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         const float r = reward[b];
+        const float m = cal ? mc[b] : 0.f;
+        bool bd;
         const float y = r + discount[b] * fminf(tq[b], tq[B + b]);
         v[0] += r; v[1] += y;
         for (int net = 0; net < 2; ++net) {
             const float* q = q_all + net * R;
             const float qd = q[(int64_t)K * B + b];
             float mx = qd;
-            for (int k = 0; k < K; ++k) mx = fmaxf(mx, q[(int64_t)k * B + b]);
+            for (int k = 0; k < K; ++k) {
+                mx = fmaxf(mx, calql_entry(q, k, B, b, n, cal, m, bd));
+                v[7] += bd ? 1.f : 0.f;
+            }
             float se = expf(qd - mx);
-            for (int k = 0; k < K; ++k) se += expf(q[(int64_t)k * B + b] - mx);
+            for (int k = 0; k < K; ++k) se += expf(calql_entry(q, k, B, b, n, cal, m, bd) - mx);
             const float e = qd - y;
             v[2 + net] += qd;
             v[4] += e * e;
@@ -97,7 +114,7 @@ __global__ __launch_bounds__(1024) void cql_critic_dq_kernel(const float* __rest
             v[6] += qd;
         }
     }
-    block_sum<7>(v, sm);
+    block_sum<8>(v, sm);
     // Data parallel with the Lagrange multiplier (mode 1, then 2; gsum = two floats of the agent's statistics block): the multiplier's step
     // needs the penalty of the GLOBAL batch before any gradient can be formed, so a first launch only leaves this rank's two sums
     // (sum lse, sum Q1 + Q2), the host sum-all-reduces them, and the second launch steps the multiplier from the global penalty — the same
@@ -132,22 +149,28 @@ __global__ __launch_bounds__(1024) void cql_critic_dq_kernel(const float* __rest
         metrics[EXORL_M_CRITIC_CQL_LOGSUM] = lse;
         metrics[EXORL_M_CRITIC_CQL] = pen;
         metrics[EXORL_M_CRITIC_LOSS] = v[4] * inv_bg + alpha * pen;
+        metrics[EXORL_M_CALQL_BOUND] = v[7] * inv_bg / (float)(4 * n);
     }
     __syncthreads();
     const float cql_alpha = sh_alpha;
     // pass 2: per-row gradients
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         const float y = reward[b] + discount[b] * fminf(tq[b], tq[B + b]);
+        const float m = cal ? mc[b] : 0.f;
+        bool bd;
         for (int net = 0; net < 2; ++net) {
             const float* q = q_all + net * R;
             float* dq = dq_all + net * R;
             const float qd = q[(int64_t)K * B + b];
             float mx = qd;
-            for (int k = 0; k < K; ++k) mx = fmaxf(mx, q[(int64_t)k * B + b]);
+            for (int k = 0; k < K; ++k) mx = fmaxf(mx, calql_entry(q, k, B, b, n, cal, m, bd));
             float se = expf(qd - mx);
-            for (int k = 0; k < K; ++k) se += expf(q[(int64_t)k * B + b] - mx);
+            for (int k = 0; k < K; ++k) se += expf(calql_entry(q, k, B, b, n, cal, m, bd) - mx);
             const float inv = 1.0f / se;
-            for (int k = 0; k < K; ++k) dq[(int64_t)k * B + b] = cql_alpha * expf(q[(int64_t)k * B + b] - mx) * inv * inv_bg;
+            for (int k = 0; k < K; ++k) {
+                const float qh = calql_entry(q, k, B, b, n, cal, m, bd);
+                dq[(int64_t)k * B + b] = bd ? 0.0f : cql_alpha * expf(qh - mx) * inv * inv_bg;
+            }
             const float e = qd - y;
             dq[(int64_t)K * B + b] = cql_alpha * expf(qd - mx) * inv * inv_bg + 2.0f * e * inv_bg - cql_alpha * inv_bg;
         }
@@ -156,10 +179,10 @@ __global__ __launch_bounds__(1024) void cql_critic_dq_kernel(const float* __rest
 
 int cql_critic_dq(const float* q_all, const float* tq, const float* reward, const float* discount, float* dq_all, float* metrics,
                   int B, int n, float cql_alpha, float inv_bg, hipStream_t s, CqlScalars* lag, const AdamConst* c_dev, float target_penalty,
-                  int mode, float* gsum) {
+                  int mode, float* gsum, const float* mc) {
     EXORL_REQUIRE(mode == 0 || gsum, "cql_critic_dq: the data-parallel modes need the statistics block");
     hipLaunchKernelGGL(cql_critic_dq_kernel, dim3(1), dim3(1024), 0, s, q_all, tq, reward, discount, dq_all, metrics, B, n, cql_alpha, inv_bg,
-                       lag, c_dev, target_penalty, mode, gsum);
+                       lag, c_dev, target_penalty, mode, gsum, mc);
     EXORL_LAUNCH_CHECK();
     return 0;
 }
@@ -250,3 +273,12 @@ int cql_act(const float* raw, const float* noise, uint64_t seed, uint64_t counte
 }
 
 }  // namespace exorl
+
+// Mode 0 with no multiplier on caller-made rows (unit test hook).
+extern "C" int exorl_cql_dq_rows(const float* q_all, const float* tq, const float* reward, const float* discount, const float* mc_or_null,
+                                 int32_t B, int32_t n, float alpha, float inv_bg, float* dq_all_out, float* metrics_out, void* stream) {
+    using namespace exorl;
+    EXORL_REQUIRE(q_all && tq && reward && discount && dq_all_out && metrics_out && B > 0 && n > 0, "cql_dq_rows: bad arguments");
+    return cql_critic_dq(q_all, tq, reward, discount, dq_all_out, metrics_out, B, n, alpha, inv_bg, as_stream(stream), nullptr, nullptr, 0.f, 0,
+                         nullptr, mc_or_null);
+}

@@ -483,7 +483,7 @@ int cql_build_inputs(const float* obs, const float* action, const float* raw2, C
 int cql_critic_dq(const float* q_all, const float* tq, const float* reward, const float* discount, float* dq_all, float* metrics,
                   int B, int n, float cql_alpha, float inv_bg, hipStream_t s, CqlScalars* lag = nullptr, const AdamConst* c_dev = nullptr,
                   float target_penalty = 0.f,
-                  int mode = 0, float* gsum = nullptr);
+                  int mode = 0, float* gsum = nullptr, const float* mc = nullptr);      // mc: Cal-QL's per-row lower bound (B), null: CQL
 // rsample of pi(obs): y = tanh(mu + std z) -> xc_pi[:, O:]; stats[0] = sum log_pi (per element, cql.py:239)
 int cql_actor_sample(const float* raw_obs, CqlNoise nz, float* xc_pi, int64_t ld, float* stats, int B, int O, int A, hipStream_t s);
 // scalar Adam step on log_actor_alpha from the (all-reduced) sum of log_pi; writes alpha = exp(log_alpha) and metrics
@@ -659,7 +659,11 @@ struct StageOut {
 };
 int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
-                       const uint64_t* dev_counter, const StageOut* stage = nullptr);
+                       const uint64_t* dev_counter, const StageOut* stage = nullptr, float* mc_return = nullptr);
+// the return-to-go column as exorl_replay_build_returns left it; valid = false once an episode was appended or evicted or the order was set.
+// ptr never moves once allocated.
+struct ReplayReturns { const float* ptr; float gamma; uint64_t epoch; bool valid; };
+ReplayReturns replay_returns(exorl_replay* r);
 int replay_obs_bytes(exorl_replay* r);        // bytes of one SAMPLED observation (frames x the arena's row on a frame-stacked arena)
 int replay_frame_stack(exorl_replay* r);      // frames per sampled observation (exorl_replay_set_frame_stack; 1: none)
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim);

@@ -27,6 +27,10 @@
 // (obs_moments_partial_kernel: Welford per thread, Chan between threads, one partial per workgroup in a slab; obs_moments_combine_kernel: the
 // slab in slab order), and exorl_replay_set_obs_norm makes gather_nstep_kernel<true> write y = (x - mean[j]) * inv_scale[j] wherever the plain
 // instantiation copies an observation element, the staged network inputs included.
+//
+// Return-to-go column (exorl_replay_build_returns): one float per arena row, G_i = r_i + (gamma d_i) G_{i+1} carried to the episode's end in fp64
+// (returns_to_go_kernel, one launch over the order table). The gather writes G[row0 + idx] beside reward and discount when
+// exorl_replay_sample_mc names a destination: Cal-QL's lower bound on the critic. Stale once an episode is appended or evicted or the order changes.
 #include <algorithm>
 #include <vector>
 
@@ -163,6 +167,14 @@ struct exorl_replay {
     std::vector<int32_t> h_kitem0;
     std::vector<int64_t> h_ktrans0;
     void keys_stale() { if (keys_valid) { keys_valid = false; keys_epoch += 1; } }
+    // exorl_replay_build_returns' column: capacity_rows floats, allocated at the first build and never moved (a captured graph holds the
+    // pointer); stale once an episode is appended or evicted or the order table is set. Weights, the normaliser and the frame stack leave it.
+    float* d_rtg = nullptr;
+    float rtg_gamma = 0.f;
+    bool rtg_valid = false;
+    uint64_t rtg_epoch = 0;           // counts builds and invalidations
+    std::vector<float> h_rtg;         // exorl_replay_returns_read's bounce buffer
+    void returns_stale() { if (rtg_valid) { rtg_valid = false; rtg_epoch += 1; } }
 };
 
 namespace exorl {
@@ -177,6 +189,7 @@ struct ReplayView {
     const int32_t* guide;     // (1 << guide_bits) + 1 cut points into cum, indexed by the top guide_bits bits of the draw
     int32_t guide_bits;
     const float *norm_mean, *norm_inv;      // null: observations are copied; else obs_bytes / 4 floats each, y = (x - mean[j]) * inv[j]
+    const float* rtg;         // the return-to-go column, one float per arena row; read only where the launch has a destination for it
 };
 
 __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
@@ -248,8 +261,9 @@ __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pa
 // (the pragma is lexically scoped): an FMA in the recurrence would stop matching NumPy.
 // next_ok (idx + nstep <= len[pos], the caller has both): the episode holds the action taken at next_obs, arena row `row + nstep`. Where
 // it does not, that row is the next episode's dummy row or lies past the arena's end and is not read: the sample gets zeros.
+// mc (null: not written): the sample's Monte-Carlo return-to-go, the column's value at `row`, a plain copy.
 __device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_batch_out& out, int b, int64_t row, int nstep, float gamma,
-                                            int lane, bool next_ok) {
+                                            int lane, bool next_ok, float* mc) {
 #pragma clang fp contract(off)
     for (int j = lane; j < v.act_dim; j += 64) out.action[(int64_t)b * out.action_stride + j] = v.act[row * v.act_dim + j];
     if (out.next_action) {                           // wave-uniform, as next_ok is
@@ -274,6 +288,7 @@ __device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_bat
         }
         out.reward[b] = R;
         out.discount[b] = D;
+        if (mc) mc[b] = v.rtg[row];
     }
 }
 
@@ -283,7 +298,7 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
                                                            int32_t* pairs_out, exorl_batch_out out,
                                                            int batch, int nstep, float gamma, int sampler,
                                                            uint64_t seed, uint64_t counter_val,
-                                                           const uint64_t* counter_ptr, int vec16, StageOut stage) {
+                                                           const uint64_t* counter_ptr, int vec16, StageOut stage, float* mc) {
 #pragma clang fp contract(off)
     if (stage.st && blockIdx.x == 0 && threadIdx.x == 0) step_begin_device(stage.st, 0);   // noise counter, Adam scalars of this step
     const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
@@ -326,7 +341,7 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         if (stage.has_critic)
             for (int j = lane; j < A; j += 64) stage.xc_cur[(int64_t)b * W + O + j] = v.act[row * v.act_dim + j];
     }
-    sample_tail(v, out, b, row, nstep, gamma, lane, idx + nstep <= v.len[pos]);
+    sample_tail(v, out, b, row, nstep, gamma, lane, idx + nstep <= v.len[pos], mc);
 }
 
 // copy_row with four loads of a lane in flight before the first store (the compiler keeps copy_row's loop at one load, one wait, one store):
@@ -346,7 +361,7 @@ __device__ __forceinline__ void stream_words(const W* __restrict__ s, W* __restr
 // before the reset repeat the reset frame. The first wave of a sample also writes what is per sample: sample_tail and the drawn pair.
 __global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const int32_t* pairs_in, int32_t* pairs_out, exorl_batch_out out,
                                                             int batch, int nstep, float gamma, int sampler, uint64_t seed,
-                                                            uint64_t counter_val, const uint64_t* counter_ptr, int frames) {
+                                                            uint64_t counter_val, const uint64_t* counter_ptr, int frames, float* mc) {
     const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -367,7 +382,7 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(ReplayView v, const 
     if (vec16) stream_words(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), v.obs_bytes / 16, lane);
     else stream_words(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(dst), v.obs_bytes / 4, lane);
     if (!first) return;
-    sample_tail(v, out, b, row0 + idx, nstep, gamma, lane, idx + nstep <= v.len[pos]);
+    sample_tail(v, out, b, row0 + idx, nstep, gamma, lane, idx + nstep <= v.len[pos], mc);
 }
 
 // ---- column moments of the resident observations (exorl_replay_obs_moments) -----------------------------------------------------------
@@ -513,6 +528,52 @@ __global__ __launch_bounds__(256) void episode_returns_kernel(const float* __res
     if (t == 0) out[e] = s_r[0];
 }
 
+// ---- return-to-go of every resident transition (exorl_replay_build_returns) ------------------------------------------------------------
+// episode_returns_kernel's recurrence carried to the episode's end and kept per step: G_len = r_len, G_i = r_i + (gamma d_i) G_{i+1}, in fp64,
+// stored as float (round to nearest) at arena row row0 + i; the dummy row gets 0. An episode cut by a time limit (d = 1 on its last step) gets
+// the return of its recorded remainder and no bootstrap: a lower bound on the true return only where rewards are >= 0.
+// One workgroup per episode of the order table. Thread t folds its run of cdiv(len, 256) steps backwards into the pair (R, D) of
+// episode_returns_kernel (a step is the pair (r_i, gamma d_i), the earlier run the left operand of (R1 + D1 R2, D1 D2)); the 256 pairs go
+// through an inclusive suffix scan in LDS, 8 rounds of doubling distance, every round reading before any thread writes; a thread past the end
+// holds the identity (0, 1). The return behind thread t's run is the R of thread t + 1's suffix; from it the thread walks its run backwards a
+// second time and stores. No atomics, nothing read but rew and disc of rows row0 + 1 .. row0 + len: an episode's bits depend on nothing else.
+__global__ __launch_bounds__(256) void returns_to_go_kernel(const float* __restrict__ rew, const float* __restrict__ disc,
+                                                            const int64_t* __restrict__ row0, const int32_t* __restrict__ len, double gamma,
+                                                            float* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double s_r[256], s_d[256];
+    const int e = blockIdx.x, t = threadIdx.x;
+    const int n = len[e];
+    const int64_t base = row0[e];
+    const int run = (n + 255) / 256;
+    const int t0 = t * run + 1, t1 = min(t0 + run - 1, n);
+    double R = 0.0, D = 1.0;
+    for (int i = t1; i >= t0; --i) {
+        const double c = gamma * (double)disc[base + i];
+        R = (double)rew[base + i] + c * R;
+        D = c * D;
+    }
+    s_r[t] = R; s_d[t] = D;
+    __syncthreads();
+    for (int step = 1; step < 256; step <<= 1) {
+        const bool has = t + step < 256;
+        const double r2 = has ? s_r[t + step] : 0.0, d2 = has ? s_d[t + step] : 1.0;
+        __syncthreads();
+        if (has) {
+            R = R + D * r2;
+            D = D * d2;
+            s_r[t] = R; s_d[t] = D;
+        }
+        __syncthreads();
+    }
+    double G = t + 1 < 256 ? s_r[t + 1] : 0.0;
+    for (int i = t1; i >= t0; --i) {
+        G = (double)rew[base + i] + (gamma * (double)disc[base + i]) * G;
+        out[base + i] = (float)G;
+    }
+    if (t == 0) out[base] = 0.0f;
+}
+
 // Prefix sum of the episode masses for `nstep`, checked on the host before anything is enqueued.
 static int build_cum(exorl_replay* r, int32_t nstep) {
     const int n = (int)r->order.size();
@@ -652,6 +713,7 @@ int exorl_replay_destroy(exorl_replay_t* r) {
     if (r->d_item0) (void)hipFree(r->d_item0);
     if (r->d_slab) (void)hipFree(r->d_slab);
     if (r->d_returns) (void)hipFree(r->d_returns);
+    if (r->d_rtg) (void)hipFree(r->d_rtg);
     if (r->d_keys) (void)hipFree(r->d_keys);
     if (r->d_kitem0) (void)hipFree(r->d_kitem0);
     if (r->d_ktrans0) (void)hipFree(r->d_ktrans0);
@@ -665,6 +727,7 @@ int exorl_replay_append_episode(exorl_replay_t* r, const void* obs, const float*
     EXORL_REQUIRE(rows >= 2, "replay_append_episode: rows=%d (an episode is a dummy row + >=1 transition)", rows);
     EXORL_REQUIRE((r->cfg.meta_dim == 0) == (meta == nullptr), "replay_append_episode: meta pointer/meta_dim mismatch");
     r->keys_stale();
+    r->returns_stale();
     if (r->used_rows + rows > r->cfg.capacity_rows) {
         EXORL_REQUIRE(r->live_rows + rows <= r->cfg.capacity_rows,
                       "replay_append_episode: arena full (%lld live + %d > capacity %lld rows)", (long long)r->live_rows, rows,
@@ -698,6 +761,7 @@ int exorl_replay_append_episode(exorl_replay_t* r, const void* obs, const float*
 int exorl_replay_evict(exorl_replay_t* r, int32_t slot) {
     EXORL_REQUIRE(r && slot >= 0 && slot < (int)r->slots.size() && r->slots[slot].live, "replay_evict: slot %d not resident", slot);
     r->keys_stale();
+    r->returns_stale();
     r->slots[slot].live = false;
     r->live_rows -= r->slots[slot].rows;
     for (size_t i = 0; i < r->order.size(); ++i)
@@ -712,6 +776,7 @@ int exorl_replay_set_order(exorl_replay_t* r, const int32_t* slots, int32_t n) {
         EXORL_REQUIRE(slots[i] >= 0 && slots[i] < (int)r->slots.size() && r->slots[slots[i]].live,
                       "replay_set_order: slot %d (position %d) not resident", slots[i], i);
     r->keys_stale();
+    r->returns_stale();
     r->order.assign(slots, slots + n);
     r->table_dirty = true;
     return 0;
@@ -794,6 +859,57 @@ int exorl_replay_episode_returns(exorl_replay_t* r, float gamma, double* returns
     EXORL_LAUNCH_CHECK();
     EXORL_CHECK_HIP(hipMemcpyAsync(returns_host, r->d_returns, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int exorl_replay_build_returns(exorl_replay_t* r, float gamma, void* stream) {
+    EXORL_REQUIRE(r, "replay_build_returns: null handle");
+    EXORL_REQUIRE(!r->order.empty(), "replay_build_returns: no resident episode in the order table");
+    hipStream_t s = as_stream(stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    EXORL_CHECK_HIP(hipStreamIsCapturing(s, &cs));
+    EXORL_REQUIRE(cs == hipStreamCaptureStatusNone, "replay_build_returns: a set-up call (it allocates and synchronises): not inside a capture");
+    r->returns_stale();
+    if (!r->d_rtg) {
+        EXORL_CHECK_HIP(hipMalloc((void**)&r->d_rtg, (size_t)r->cfg.capacity_rows * sizeof(float)));
+        EXORL_CHECK_HIP(hipMemsetAsync(r->d_rtg, 0, (size_t)r->cfg.capacity_rows * sizeof(float), s));
+    }
+    EXORL_TRY(upload_table(r, 0, s));
+    hipLaunchKernelGGL(returns_to_go_kernel, dim3((int)r->order.size()), dim3(256), 0, s, r->rew, r->disc, r->d_row0, r->d_len, (double)gamma,
+                       r->d_rtg);
+    EXORL_LAUNCH_CHECK();
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    r->rtg_gamma = gamma;
+    r->rtg_valid = true;
+    r->rtg_epoch += 1;
+    return 0;
+}
+
+int exorl_replay_returns(exorl_replay_t* r, float** ptr_dev, float* gamma, uint64_t* epoch, int32_t* valid) {
+    EXORL_REQUIRE(r, "replay_returns: null handle");
+    if (ptr_dev) *ptr_dev = r->d_rtg;
+    if (gamma) *gamma = r->rtg_gamma;
+    if (epoch) *epoch = r->rtg_epoch;
+    if (valid) *valid = r->rtg_valid ? 1 : 0;
+    return 0;
+}
+
+int exorl_replay_returns_read(exorl_replay_t* r, float* dst_host, int64_t n, void* stream) {
+    EXORL_REQUIRE(r && dst_host, "replay_returns_read: null argument");
+    EXORL_REQUIRE(r->rtg_valid, "replay_returns_read: no return-to-go column, or a stale one: an episode was appended or evicted or the order was "
+                  "set since exorl_replay_build_returns (call it again)");
+    int64_t total = 0;
+    for (int slot : r->order) total += r->slots[slot].rows - 1;
+    EXORL_REQUIRE(n == total, "replay_returns_read: n=%lld, the order table holds %lld transitions", (long long)n, (long long)total);
+    hipStream_t s = as_stream(stream);
+    r->h_rtg.resize((size_t)r->used_rows);
+    EXORL_CHECK_HIP(hipMemcpyAsync(r->h_rtg.data(), r->d_rtg, (size_t)r->used_rows * sizeof(float), hipMemcpyDeviceToHost, s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    for (int slot : r->order) {
+        const Slot& sl = r->slots[slot];
+        memcpy(dst_host, r->h_rtg.data() + sl.row0 + 1, (size_t)(sl.rows - 1) * sizeof(float));
+        dst_host += sl.rows - 1;
+    }
     return 0;
 }
 
@@ -955,8 +1071,14 @@ int replay_prepare(exorl_replay* r, int32_t batch, int32_t nstep, hipStream_t s)
 // still advanced so eager sampling continues the stream afterwards.
 int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
-                       const uint64_t* dev_counter, const StageOut* stage) {
+                       const uint64_t* dev_counter, const StageOut* stage, float* mc_return) {
     EXORL_REQUIRE(r && out, "replay_sample: null argument");
+    if (mc_return) {
+        EXORL_REQUIRE(r->rtg_valid, "replay_sample_mc: no return-to-go column, or a stale one: an episode was appended or evicted or the order was "
+                      "set since exorl_replay_build_returns (call it again)");
+        EXORL_REQUIRE(memcmp(&gamma, &r->rtg_gamma, sizeof(float)) == 0, "replay_sample_mc: gamma=%.9g, the column was built with %.9g", gamma,
+                      r->rtg_gamma);
+    }
     EXORL_REQUIRE(!stage || (r->frames == 1 && r->cfg.obs_bytes == stage->O * 4 && r->cfg.act_dim == stage->A && stage->B == batch),
                   "replay_sample: staged outputs need fp32 state observations of the agent's dimensions");
     EXORL_REQUIRE(batch > 0 && nstep >= 1, "replay_sample: batch=%d nstep=%d", batch, nstep);
@@ -1006,16 +1128,16 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
     }
     ReplayView v{r->obs, r->act, r->rew, r->disc, r->meta, r->d_row0, r->d_len, r->cfg.obs_bytes, r->cfg.act_dim, r->cfg.meta_dim, n,
                  r->weighted && sampler == EXORL_SAMPLER_PHILOX ? r->d_cum : nullptr, r->d_guide, r->guide_bits,
-                 r->norm_on ? r->d_norm : nullptr, r->norm_on ? r->d_norm + r->cfg.obs_bytes / 4 : nullptr};
+                 r->norm_on ? r->d_norm : nullptr, r->norm_on ? r->d_norm + r->cfg.obs_bytes / 4 : nullptr, r->d_rtg};
     if (r->frames > 1) {
         hipLaunchKernelGGL(gather_frames_kernel, dim3(cdiv(2 * r->frames * batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch,
-                           nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, r->frames);
+                           nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, r->frames, mc_return);
     } else {
         const int vec16 = (r->cfg.obs_bytes % 16 == 0) && (out->obs_stride % 16 == 0) && (out->next_obs_stride % 16 == 0) &&
                           ((uintptr_t)out->obs % 16 == 0) && ((uintptr_t)out->next_obs % 16 == 0);
         hipLaunchKernelGGL(r->norm_on ? gather_nstep_kernel<true> : gather_nstep_kernel<false>, dim3(cdiv(batch, 4)), dim3(256), 0, s, v,
                            r->d_pairs, r->d_pairs, *out, batch, nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16,
-                           stage ? *stage : StageOut{});
+                           stage ? *stage : StageOut{}, mc_return);
     }
     EXORL_LAUNCH_CHECK();
     if (sampler == EXORL_SAMPLER_PHILOX) r->philox_counter += 1;
@@ -1033,6 +1155,7 @@ ReplayKeys replay_keys(exorl_replay* r) {
 }
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }
 void replay_advance_philox(exorl_replay* r, uint64_t n) { r->philox_counter += n; }
+ReplayReturns replay_returns(exorl_replay* r) { return ReplayReturns{r->d_rtg, r->rtg_gamma, r->rtg_epoch, r->rtg_valid}; }
 }  // namespace exorl
 
 extern "C" {
@@ -1040,6 +1163,11 @@ extern "C" {
 int exorl_replay_sample(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                         const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, void* stream) {
     return replay_sample_impl(r, batch, nstep, gamma, sampler, pairs_host, out, pairs_out_host, as_stream(stream), nullptr);
+}
+
+int exorl_replay_sample_mc(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler, const int32_t* pairs_host,
+                           const exorl_batch_out* out, float* mc_return_dev, int32_t* pairs_out_host, void* stream) {
+    return replay_sample_impl(r, batch, nstep, gamma, sampler, pairs_host, out, pairs_out_host, as_stream(stream), nullptr, nullptr, mc_return_dev);
 }
 
 int exorl_replay_last_pairs(exorl_replay_t* r, int32_t batch, int32_t* pairs_host, void* stream) {

@@ -119,6 +119,7 @@ class AgentEngine(_Phased):
         self._eval = self._fqe_value = None       # the evaluation and value windows (set_eval, set_fqe_value): attached on first use
         self._rebrac = None                       # the ReBRAC buffer (set_rebrac): the caller's, kept alive here while set
         self._sarsa = None                        # the SARSA buffer (set_sarsa), likewise; never both
+        self._calql = None                        # Cal-QL's buffer (set_calql), likewise
 
     # -- pickling support, as PixelEngine's: everything that defines the training state, as CPU data
     def export_state(self):
@@ -446,6 +447,39 @@ class AgentEngine(_Phased):
         for ptr, src in ((slots.next_action, na), (slots.next_valid, nv)):
             o = (ptr - buf.data_ptr()) // 4
             f32[o:o + src.numel()].copy_(src.reshape(-1))
+
+    def calql_bytes(self):
+        """Bytes of Cal-QL's buffer for this configuration (exorl_agent_calql_bytes); raises for a kind other than CQL."""
+        n = int(self.lib.exorl_agent_calql_bytes(C.byref(self.cfg)))
+        if n == 0:
+            raise L.ExorlError(self.lib.exorl_last_error().decode())
+        return n
+
+    def set_calql(self, buf):
+        """Cal-QL on a CQL engine (exorl_agent_set_calql): `buf` a uint8 device tensor of at least calql_bytes(), 256-byte aligned, kept
+        alive here; None detaches and the engine is CQL again. Refused while a graph is captured and while a metric window or an eval window
+        is attached."""
+        torch.cuda.current_stream(self.device).synchronize()      # a step in flight may still read the buffer this call replaces or lets go
+        if buf is None:
+            L.check(self.lib.exorl_agent_set_calql(self.h, None, 0))
+            self._calql = None
+            return
+        L.check(self.lib.exorl_agent_set_calql(self.h, buf.data_ptr(), buf.numel()))
+        self._calql = buf
+
+    def mc_return_view(self):
+        """The (B,) float32 view of Cal-QL's buffer the critic step reads: where the HBM sampler writes the rows' return-to-go."""
+        if self._calql is None:
+            raise L.ExorlError('mc_return_view: no Cal-QL buffer is set (set_calql)')
+        return self._calql[:self.batch * 4].view(torch.float32)
+
+    def set_mc_return(self, mc_return):
+        """The dataset's return-to-go of each row of the batch, (B), into Cal-QL's buffer: what the HBM sampler writes there itself, for
+        batches that come from a plain iterator (set_batch)."""
+        m = self._dev(mc_return)
+        if m.numel() != self.batch:
+            raise L.ExorlError(f'mc_return has {m.numel()} elements, expected {self.batch}')
+        self.mc_return_view().copy_(m.reshape(-1))
 
     def nn_result(self):
         """PRDC: (idx int32 (B,), d2 float32 (B,), a_nn float32 (B, A)) views of the last search's results, and the bound table's key
@@ -912,6 +946,7 @@ class ReplayEngine:
         with torch.cuda.device(self.device):
             L.check(self.lib.exorl_replay_create(C.byref(cfg), C.byref(h)))
         self.h = h
+        self._slot_len, self._order = {}, []      # the length of every resident slot and the order table: how returns_to_go() splits the column
         if self.frame_stack > 1:
             self.set_frame_stack(self.frame_stack)
 
@@ -942,10 +977,14 @@ class ReplayEngine:
         slot = C.c_int32()
         L.check(self.lib.exorl_replay_append_episode(self.h, obs.ctypes.data, act.ctypes.data, rew.ctypes.data,
                                                      disc.ctypes.data, L.ptr(meta), rows, C.byref(slot)))
+        self._slot_len[slot.value] = rows - 1
         return slot.value
 
     def evict(self, slot):
         L.check(self.lib.exorl_replay_evict(self.h, slot))
+        self._slot_len.pop(slot, None)
+        if slot in self._order:
+            self._order.remove(slot)
 
     def num_rows(self):
         """(live rows, used rows) of the arena; a row is one time-step, an episode holds len+1."""
@@ -956,6 +995,7 @@ class ReplayEngine:
     def set_order(self, slots):
         arr = np.ascontiguousarray(slots, np.int32)
         L.check(self.lib.exorl_replay_set_order(self.h, arr.ctypes.data, len(arr)))
+        self._order = [int(x) for x in arr]
 
     def set_weights(self, weighting='episodes', weights=None):
         """Weighted sampling for the Philox sampler. weighting='episodes': an episode is drawn with probability proportional to its
@@ -1026,6 +1066,28 @@ class ReplayEngine:
         L.check(self.lib.exorl_replay_episode_returns(self.h, float(gamma), out.ctypes.data, out.size, L.current_stream()))
         return out
 
+    def build_returns(self, gamma):
+        """Builds the return-to-go column with one launch over the order table (exorl_replay_build_returns): per transition
+        G_i = r_i + (gamma d_i) G_{i+1} to the episode's end, in float64, stored as float32; gamma rounded to float32 as the gather does. An
+        episode cut by a time limit (d = 1 on its last step) gets the return of its recorded remainder and no bootstrap: a lower bound on the
+        true return only where rewards are >= 0. Appending or evicting an episode and set_order make the column stale. A set-up call: it
+        synchronises the current stream."""
+        L.check(self.lib.exorl_replay_build_returns(self.h, float(gamma), L.current_stream()))
+
+    def returns_info(self):
+        """(device pointer or None, the build's gamma, epoch, valid) of the return-to-go column (exorl_replay_returns)."""
+        p, g, e, v = C.c_void_p(), C.c_float(), C.c_uint64(), C.c_int32()
+        L.check(self.lib.exorl_replay_returns(self.h, C.byref(p), C.byref(g), C.byref(e), C.byref(v)))
+        return p.value, g.value, e.value, bool(v.value)
+
+    def returns_to_go(self):
+        """A list of float32 arrays, one per episode of the order table: G_1 .. G_L of the column as last built
+        (exorl_replay_returns_read). ExorlError when there is none or it is stale."""
+        lens = [self._slot_len[s] for s in self._order]
+        flat = np.zeros(sum(lens), np.float32)
+        L.check(self.lib.exorl_replay_returns_read(self.h, flat.ctypes.data, flat.size, L.current_stream()))
+        return np.split(flat, np.cumsum(lens)[:-1]) if lens else []
+
     def set_obs_normalizer(self, mean32, inv32):
         """Every obs / next_obs element sampled from now on is (x - mean32[j]) * inv32[j] (utils.normalize_obs), in the captured step's
         staged gather too; action, reward, discount and meta are untouched. Calling it again replaces the values in place: a captured
@@ -1059,11 +1121,19 @@ class ReplayEngine:
     def seed_philox(self, seed):
         L.check(self.lib.exorl_replay_seed_philox(self.h, seed))
 
-    def sample_into(self, out, batch, nstep, gamma, sampler, pairs=None, want_pairs=False):
+    def sample_into(self, out, batch, nstep, gamma, sampler, pairs=None, want_pairs=False, mc_return=None):
+        """mc_return: a (batch,) float32 device tensor that takes each sample's return-to-go from the column of build_returns, written by
+        the same gather launch (exorl_replay_sample_mc); None: exorl_replay_sample."""
         pin = np.ascontiguousarray(pairs, np.int32) if pairs is not None else None
         pout = np.zeros((batch, 2), np.int32) if want_pairs else None
-        L.check(self.lib.exorl_replay_sample(self.h, batch, nstep, gamma, sampler, L.ptr(pin), C.byref(out), L.ptr(pout),
-                                             L.current_stream()))
+        if mc_return is None:
+            L.check(self.lib.exorl_replay_sample(self.h, batch, nstep, gamma, sampler, L.ptr(pin), C.byref(out), L.ptr(pout),
+                                                 L.current_stream()))
+            return pout
+        if mc_return.dtype != torch.float32 or mc_return.numel() < batch or not mc_return.is_contiguous():
+            raise L.ExorlError(f'sample_into: mc_return must be a contiguous float32 tensor of at least {batch} elements')
+        L.check(self.lib.exorl_replay_sample_mc(self.h, batch, nstep, gamma, sampler, L.ptr(pin), C.byref(out), mc_return.data_ptr(), L.ptr(pout),
+                                                L.current_stream()))
         return pout
 
     def last_pairs(self, batch):

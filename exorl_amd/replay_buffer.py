@@ -513,6 +513,14 @@ def start_pair_batches(n_episodes, batch):
         yield pairs, valid
 
 
+def _ensure_returns(engine, discount):
+    """The arena's return-to-go column, standing and built with `discount`: built on the first request and again once it is stale (an
+    online loader's fetch appends, evicts and reorders) or was built with another discount."""
+    _, gamma, _, valid = engine.returns_info()
+    if not valid or np.float32(gamma).tobytes() != np.float32(discount).tobytes():
+        engine.build_returns(discount)
+
+
 class _EpisodeStarts:
     """What FQEAgent.value() asks of an HBM iterator: every resident episode of every arena it samples from, once, and their returns.
     Neither touches an arena's Philox stream (the GIVEN sampler draws nothing), so a captured graph bound to the iterator is undisturbed."""
@@ -661,8 +669,11 @@ class DeviceReplayIterator(_EpisodeStarts):
             shard.since_fetch += n
             done += n
 
-    def sample_into(self, out, batch=None):
-        """Zero-copy path: writes the next minibatch straight into caller-owned device memory (exorl_batch_out)."""
+    def sample_into(self, out, batch=None, mc_return=None):
+        """Zero-copy path: writes the next minibatch straight into caller-owned device memory (exorl_batch_out). mc_return: a (batch,)
+        float32 device tensor that takes each sample's Monte-Carlo return-to-go at the loader's discount, written by the same gather launch;
+        the shard's column is built on the first request and again when a fetch made it stale. An episode cut by a time limit gets the
+        return of its recorded remainder, a lower bound only where rewards are >= 0."""
         ld = self.loader
         batch = batch or ld.batch_size
         self._ensure_normalizer()           # normalize_obs: set on every shard before the first sample
@@ -678,7 +689,11 @@ class DeviceReplayIterator(_EpisodeStarts):
                              (out.meta + start * out.meta_stride * 4) if out.meta else None, out.meta_stride,
                              (out.next_action + start * out.next_action_stride * 4) if out.next_action else None, out.next_action_stride,
                              (out.next_valid + start * 4) if out.next_valid else None)
-            shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler)
+            if mc_return is None:
+                shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler)
+            else:
+                _ensure_returns(shard.engine, ld.discount)
+                shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler, mc_return=mc_return[start:start + n])
 
     def __next__(self):
         ld = self.loader
@@ -722,8 +737,14 @@ class ArenaIterator(_EpisodeStarts):
     def _arenas(self):
         return [self.engine]
 
-    def sample_into(self, out, batch=None):
-        self._next_engine().sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler)
+    def sample_into(self, out, batch=None, mc_return=None):
+        """mc_return: a (batch,) float32 device tensor that takes each sample's Monte-Carlo return-to-go at this iterator's discount, written
+        by the same gather launch; the arena's column is built on the first request and again when it is stale. An episode cut by a time limit
+        gets the return of its recorded remainder, a lower bound only where rewards are >= 0."""
+        eng = self._next_engine()
+        if mc_return is not None:
+            _ensure_returns(eng, self.discount)
+        eng.sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler, mc_return=mc_return)
 
     def __next__(self):
         return self._next_engine().sample(self.batch_size, self.nstep, self.discount, self.sampler)

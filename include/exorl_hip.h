@@ -47,7 +47,9 @@ extern "C" {
                                         exorl_replay_keys, exorl_replay_keys_read, exorl_nn_search, exorl_agent_set_prdc, exorl_agent_nn_result;
                                         exorl_batch_out.next_action / next_action_stride / next_valid (trailing);
                                         exorl_agent_rebrac_bytes, exorl_agent_set_rebrac, exorl_rebrac_rows;
-                                        exorl_agent_sarsa_bytes, exorl_agent_set_sarsa, exorl_next_action_rows) */
+                                        exorl_agent_sarsa_bytes, exorl_agent_set_sarsa, exorl_next_action_rows;
+                                        exorl_replay_build_returns, exorl_replay_returns, exorl_replay_returns_read, exorl_replay_sample_mc,
+                                        exorl_agent_calql_bytes, exorl_agent_set_calql, exorl_cql_dq_rows, EXORL_M_CALQL_BOUND) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -136,6 +138,24 @@ int exorl_replay_obs_moments(exorl_replay_t* r, int32_t n_cols, int64_t* count_h
  * in a fixed tree. No atomics: two calls return the same bits. Evicted slots and holes are not read. A set-up call: it synchronises `stream`;
  * never call it inside a capture. */
 int exorl_replay_episode_returns(exorl_replay_t* r, float gamma, double* returns_host, int32_t n, void* stream);
+/* The Monte-Carlo return-to-go of every transition of the order table, one float per arena row, built by one launch. For an episode of
+ * length L at rows row0 + 1 .. row0 + L, with gamma widened to double: G_L = r_L, G_i = r_i + (gamma d_i) G_{i+1}, all in fp64, stored as
+ * float (round to nearest) at row row0 + i; the dummy row gets 0. This is the gather's n-step recurrence carried to the episode's end: G_1 is
+ * what exorl_replay_episode_returns reports. An episode cut by a time limit (d = 1 on its last step) gets the return of its recorded
+ * remainder and no bootstrap, which is a lower bound on the true return only where rewards are >= 0 (as the DMC tasks' are).
+ * One workgroup per episode: a thread folds its run of steps backwards into episode_returns' (R, D) pair, the pairs go through a suffix scan
+ * in a fixed order (the earlier run is always the left operand), and the thread walks its run a second time to store. No atomics; the kernel
+ * reads reward and discount of the episode's own rows only, so an episode's bits do not depend on where it sits or on what else is resident.
+ * The column (capacity_rows floats) is allocated at the first build and never moves; a rebuild is one launch over the current order table.
+ * exorl_replay_append_episode, _evict and _set_order make it stale; weights, the normaliser and the frame stack do not.
+ * A set-up call (it synchronises `stream`). Refuses, launching nothing: a null handle, an empty order table, a stream that is being captured. */
+int exorl_replay_build_returns(exorl_replay_t* r, float gamma, void* stream);
+/* The column as the last build left it: its device pointer (NULL before the first build), the build's gamma, a count of builds and
+ * invalidations, and whether it stands (1) or is stale or absent (0). Any output may be NULL. */
+int exorl_replay_returns(exorl_replay_t* r, float** ptr_dev, float* gamma, uint64_t* epoch, int32_t* valid);
+/* G_1 .. G_L of every order-table episode, concatenated in table order, into n host floats. Synchronous. Refuses a stale or absent column and
+ * an n other than the table's transition count. */
+int exorl_replay_returns_read(exorl_replay_t* r, float* dst_host, int64_t n, void* stream);
 /* Episodes in the current order table: the positions EXORL_SAMPLER_GIVEN accepts are [0, *n). */
 int exorl_replay_num_episodes(exorl_replay_t* r, int32_t* n);
 /* Observation normaliser of the gather: with n_cols = obs_bytes / 4 values each in mean_host and inv_scale_host, every obs and next_obs
@@ -176,6 +196,15 @@ int exorl_replay_seed_philox(exorl_replay_t* r, uint64_t seed);
 int exorl_replay_sample(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                         const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host,
                         void* stream);
+
+/* exorl_replay_sample with one more destination: mc_return_dev[b] = G[row0[pos] + idx], the sample's return-to-go from the column of
+ * exorl_replay_build_returns, a plain copy written by the same gather launch (both gather kernels: the lane that writes reward and discount
+ * writes it). With mc_return_dev NULL this is exorl_replay_sample: same bits, same launch. With a destination it refuses, launching nothing,
+ * a missing or stale column and a gamma whose bits differ from the build's. (The destination is an argument because exorl_batch_out
+ * keeps its size.) */
+int exorl_replay_sample_mc(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
+                           const int32_t* pairs_host, const exorl_batch_out* out, float* mc_return_dev, int32_t* pairs_out_host,
+                           void* stream);
 
 /* Synchronous: the (position, start idx) pairs of the last sample call, read back from the device. */
 int exorl_replay_last_pairs(exorl_replay_t* r, int32_t batch, int32_t* pairs_host, void* stream);
@@ -284,6 +313,8 @@ typedef struct exorl_agent exorl_agent_t;
 #define EXORL_M_REBRAC_VALID   11 /* mean of v, the share of rows whose episode holds the next action */
 /* EXORL_AGENT_TD3_BC, _TD3, _CRR and _FQE while the SARSA setting is on (exorl_agent_set_sarsa) only: slot 11; the other slots are the kind's. */
 #define EXORL_M_SARSA_VALID    11 /* mean over the global batch of v = next_valid, the share of rows whose target is at the dataset's a' */
+/* EXORL_AGENT_CQL: slot 15. 0 unless Cal-QL is set on the handle (exorl_agent_set_calql). */
+#define EXORL_M_CALQL_BOUND    15 /* mean over the global batch of (bounded policy-action entries of row b, both nets) / (4 n_samples) */
 #define EXORL_N_METRICS        16
 
 typedef struct {
@@ -419,6 +450,23 @@ int exorl_agent_set_rebrac(exorl_agent_t* a, void* buf_dev, size_t bytes, float 
  * forward): Q^beta(s0, a0) when the slots hold episode starts. */
 size_t exorl_agent_sarsa_bytes(const exorl_agent_cfg* cfg);
 int exorl_agent_set_sarsa(exorl_agent_t* a, void* buf_dev, size_t bytes);
+/* Cal-QL (Nakamoto et al., NeurIPS 2023) as a per-handle setting of EXORL_AGENT_CQL: in the conservative penalty the critic's value on the
+ * policy actions, entries k in [n, 3n) of a row (the actions of pi(s) and pi(s') evaluated at s), enters as q^ = (q >= m_b) ? q : m_b with
+ * m_b = mc_return[b], the dataset's Monte-Carlo return-to-go of the row (exorl_replay_build_returns, exorl_replay_sample_mc). The row
+ * maximum, the exponent sum, lse and the penalty use q^; dq of a bounded entry is +0, every other dq keeps its formula with q^ inside the
+ * softmax; the random entries, the data entry, y, the mse and the Lagrange step are CQL's, in all three modes of the critic kernel (under
+ * data parallelism the mode-1 sums are sums of q^ terms; the bound is per row and needs no exchange). No launch is added: the plan and the
+ * dispatch count are CQL's. With the setting off, or on with m = -inf everywhere, the step is CQL's bit for bit. m is a lower bound on the
+ * value of the behaviour only where an episode's recorded remainder is one (see exorl_replay_build_returns).
+ * The buffer is the caller's device memory, exorl_agent_calql_bytes(cfg) bytes (4 * batch rounded up to 64 floats, the same at every
+ * precision and world_size), 256-byte aligned: mc_return (batch), which the sampler or the caller writes before every step.
+ * exorl_agent_calql_bytes needs no device and returns 0 (exorl_last_error set) for another kind or a configuration exorl_agent_create
+ * refuses. exorl_agent_set_calql refuses, launching nothing: a null handle; another kind; a handle with a captured graph (the graph holds the
+ * pointer); when attaching, a metric window or eval buffer already attached; a buffer too small or misaligned. A NULL buffer detaches.
+ * While set, exorl_agent_set_metric_window, exorl_agent_set_eval and exorl_agent_evaluate refuse; exorl_agent_enable_graph hands the buffer to
+ * the captured gather and refuses a replay without a valid column at its gamma; exorl_agent_step_graph refuses once the column is stale. */
+size_t exorl_agent_calql_bytes(const exorl_agent_cfg* cfg);
+int exorl_agent_set_calql(exorl_agent_t* a, void* buf_dev, size_t bytes);
 /* Policy inference for n rows: out = mean (eval) or TruncatedNormal sample (clip=None). */
 int exorl_agent_act(exorl_agent_t* a, const float* obs_dev, int32_t n, float stddev, int32_t eval_mode,
                     const float* noise_dev, float* action_out_dev, void* stream);
@@ -638,6 +686,13 @@ int exorl_rebrac_rows(const float* sample_dev, int64_t sample_ld, const float* n
  * exorl_iql_rows_chunks(rows) floats. */
 int exorl_next_action_rows(const float* next_action_dev, int64_t next_action_stride, const float* next_valid_dev, int32_t rows, int32_t act_dim,
                            float inv_bg, float* dst_dev, int64_t dst_ld, float* part_dev, float* sums_dev, void* stream);
+/* CQL's critic loss-gradient kernel on caller-made rows, one process, a fixed alpha and no multiplier (unit test hook). q_all (2, (3n + 1) B):
+ * per net the entries k = 0 .. 3n of sample b at [k B + b], k < n random actions, n <= k < 3n policy actions, k = 3n the data action; tq (2, B)
+ * the target critics at s'; reward, discount (B); mc_or_null (B) Cal-QL's bound or NULL for CQL. Writes dq_all_out (the shape of q_all, every
+ * element) and metrics_out (EXORL_N_METRICS floats: the slots the critic kernel owns). Per row and net, in this order: mx = the maximum over
+ * the data entry then k ascending; se = exp(q_data - mx) + sum over k ascending of exp(q^_k - mx); lse = log(se) + mx. */
+int exorl_cql_dq_rows(const float* q_all_dev, const float* tq_dev, const float* reward_dev, const float* discount_dev, const float* mc_or_null_dev,
+                      int32_t B, int32_t n, float alpha, float inv_bg, float* dq_all_out_dev, float* metrics_out_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Intrinsic-reward modules of the reward-free DDPG-backbone agents (states observations).
