@@ -13,6 +13,7 @@ P = C.POINTER
 # constants mirrored from include/exorl_hip.h
 SAMPLER_MT19937, SAMPLER_PHILOX, SAMPLER_GIVEN = 0, 1, 2
 WEIGHT_EPISODES, WEIGHT_TRANSITIONS = 0, 1
+GOAL_KEEP, GOAL_NEG, GOAL_SPARSE = 0, 1, 2
 AGENT_TD3_BC, AGENT_TD3, AGENT_BC, AGENT_DDPG, AGENT_CRR, AGENT_CQL, AGENT_APS = 0, 1, 2, 3, 4, 5, 6
 AGENT_IQL = 8             # 7 is unassigned
 AGENT_FQE = 9
@@ -178,6 +179,10 @@ PROTOTYPES = {
     'exorl_replay_returns': (C.c_int, [c_void_p, P(c_void_p), P(c_float), P(c_uint64), P(c_int32)]),
     'exorl_replay_returns_read': (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'exorl_replay_last_pairs': (C.c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    'exorl_replay_set_goal': (C.c_int, [c_void_p, c_void_p, c_int32, C.c_double, C.c_double, C.c_double, C.c_double, c_int32]),
+    'exorl_replay_sample_goal': (C.c_int, [c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, P(BatchOut), c_void_p, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'exorl_replay_last_goals': (C.c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     'exorl_comm_unique_id': (C.c_int, [c_void_p]),
     'exorl_comm_init': (C.c_int, [c_int32, c_int32, c_void_p, P(c_void_p)]),
     'exorl_comm_destroy': (C.c_int, [c_void_p]),
@@ -225,6 +230,7 @@ PROTOTYPES = {
     'exorl_agent_opt_steps': (C.c_int, [c_void_p, P(c_int64), P(c_int64)]),
     'exorl_agent_set_opt_steps': (C.c_int, [c_void_p, c_int64, c_int64]),
     'exorl_agent_enable_graph': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_float, c_void_p]),
+    'exorl_agent_enable_graph_goal': (C.c_int, [c_void_p, c_void_p, c_int32, c_float, c_float, c_void_p]),
     'exorl_agent_enable_graph_intr': (C.c_int, [c_void_p, c_void_p, P(IntrBatch), c_int32, c_void_p, c_int32, c_float, c_float, c_void_p]),
     'exorl_agent_step_graph': (C.c_int, [c_void_p, c_float, c_void_p]),
     'exorl_agent_noise_counter': (C.c_int, [c_void_p, P(c_uint64), c_void_p]),

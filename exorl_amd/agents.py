@@ -318,8 +318,9 @@ class _AgentBase:
             return False
         self._graph_stddev = self._stddev(step)
         ok = True
+        goal = getattr(replay_iter, 'goal', None) is not None      # a goal iterator: the capture takes the gather's goal path, [obs | g] rows
         try:
-            self.engine.enable_graph(eng, replay_iter.nstep, replay_iter.discount, self._graph_stddev)
+            (self.engine.enable_graph_goal if goal else self.engine.enable_graph)(eng, replay_iter.nstep, replay_iter.discount, self._graph_stddev)
         except L.ExorlError:
             if self.world_size == 1:
                 raise
@@ -1049,11 +1050,18 @@ class _IntrAgent(DDPGAgent):
     def _hooked(self):
         return any(vars(self).get(h) is not None for h in self._HOOKS)
 
+    def _refuse_goal(self, replay_iter):
+        if getattr(replay_iter, 'goal', None) is not None:
+            raise ValueError(f'{type(self).__name__}: a goal iterator (goal=GoalRelabel) relabels the reward and fills [obs | g] rows; the '
+                             'reward-free agents train on their own intrinsic reward with the skill behind the observation: goal '
+                             'conditioning covers the offline state agents')
+
     def enable_graph(self, replay_iter, step=0):
         """One hipGraph per update on state observations in one process: sample -> module step and intrinsic reward -> DDPG step
         (reward_free), or sample -> DDPG step (fine-tuning: the module is not stepped). Returns False and stays eager on pixels, under
         torch.distributed (the replicated and the sharded module step run their collectives in Python), for an iterator without the
         Philox HBM sampler, and while a test hook supplies draws from the host. A hook set later sends that step down the eager path."""
+        self._refuse_goal(replay_iter)
         eng = getattr(replay_iter, 'engine', None)
         if (self.obs_type != 'states' or self.world_size != 1 or eng is None or getattr(replay_iter, 'sampler', None) != L.SAMPLER_PHILOX or
                 self._hooked()):
@@ -1181,6 +1189,7 @@ class _IntrAgent(DDPGAgent):
             metrics['extr_reward'] = metrics['batch_reward']
 
     def _step(self, replay_iter, stddev):
+        self._refuse_goal(replay_iter)
         if replay_iter is self._graph_iter and not self._hooked():
             self.engine.step_graph(stddev)            # the module's counters and the std live in device memory: no re-capture
             return

@@ -41,7 +41,14 @@ class CalQLAgent(CQLAgent):
         eng = self.engine
         eng.set_calql(torch.zeros(eng.calql_bytes(), dtype=torch.uint8, device=eng.device))       # last: unpickling attaches it again
 
+    def _refuse_goal(self, replay_iter):
+        goal = getattr(replay_iter, 'goal', None)
+        if goal is not None and goal.reward != 'keep':
+            raise ValueError(f"{type(self).__name__}: the goal iterator relabels the reward (reward={goal.reward!r}) and the return-to-go column "
+                             "that bounds the critic is the arena reward's: use GoalRelabel(reward='keep'), or CQLAgent")
+
     def _load_batch(self, replay_iter):
+        self._refuse_goal(replay_iter)
         eng = self.engine
         if hasattr(replay_iter, 'sample_into'):          # HBM sampler: the gather writes the return-to-go into the buffer
             replay_iter.sample_into(self._batch_slots(), eng.batch, mc_return=eng.mc_return_view())
@@ -54,6 +61,7 @@ class CalQLAgent(CQLAgent):
         eng.set_mc_return(batch[5])
 
     def enable_graph(self, replay_iter, step=0):
+        self._refuse_goal(replay_iter)
         eng = getattr(replay_iter, 'engine', None)
         if eng is not None and getattr(replay_iter, 'sampler', None) == L.SAMPLER_PHILOX:
             _ensure_returns(eng, replay_iter.discount)      # the captured gather reads the column: it stands before the capture

@@ -484,6 +484,8 @@ struct exorl_agent {
     hipStream_t capture_stream = nullptr;
     exorl_replay* graph_replay = nullptr;
     uint64_t graph_weights_epoch = 0;        // the replay's exorl_replay_set_weights count at capture: the graph samples that table
+    bool graph_goal = false;                 // captured by exorl_agent_enable_graph_goal: the gather relabels with the rule of ...
+    uint64_t graph_goal_epoch = 0;           // ... this exorl_replay_set_goal count
     float graph_gamma = 0.f;                 // the capture's gamma: Cal-QL's gather reads a return-to-go column built with the same bits
     bool graph_norm_on = false;              // the replay's normaliser at capture, on or off: the graph holds the normalising or the copying gather
     uint64_t graph_replay_ctr = 0;           // host mirror of state->replay_counter: eager samples drawn between two launches move the replay's own
@@ -1689,9 +1691,16 @@ int exorl_agent_set_opt_steps(exorl_agent_t* a, int64_t actor_steps, int64_t cri
 }
 
 // sample -> [meta columns into the next_obs rows] -> [module step + intrinsic reward] -> the agent's step, captured once
+// goal: the gather is the replay's goal path (exorl_replay_set_goal) into [obs | g] slots, the step un-staged on them
 static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_intr_batch* ib, int32_t meta_dim, exorl_replay_t* r, int32_t nstep,
-                             float gamma, float stddev, void* stream) {
+                             float gamma, float stddev, void* stream, bool goal = false) {
     EXORL_REQUIRE(a && r, "agent_enable_graph: null argument");
+    if (goal) {
+        const int G = replay_goal_cols(r), O = replay_obs_bytes(r) / 4;
+        EXORL_REQUIRE(G > 0, "agent_enable_graph_goal: the replay has no goal rule (exorl_replay_set_goal)");
+        EXORL_REQUIRE(O + G == a->cfg.obs_dim, "agent_enable_graph_goal: the replay's %d observation + %d goal columns do not fill the agent's rows "
+                      "of obs_dim=%d", O, G, a->cfg.obs_dim);
+    }
     // a previous step (eager or a graph launch) may still be running on the caller's stream and reads the buffers the new graph is
     // built over; releasing a graph exec that is executing is not allowed either. Setup call: a full stream sync is fine here.
     EXORL_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));
@@ -1743,8 +1752,10 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     // boundary less per step); the replay counter is then advanced by the step's last kernel (the actor's optimiser pass)
     StageOut stage{a->xa, a->xc_cur, a->xc_next, a->xc_pi, a->cfg.obs_dim, a->cfg.act_dim, a->cfg.batch, a->has_critic ? 1 : 0, a->state};
     const bool staged = replay_obs_bytes(r) == a->cfg.obs_dim * 4;
+    const int O_goal = replay_obs_bytes(r) / 4;
+    const GoalOut go{nullptr, a->obs + O_goal, a->cfg.obs_dim, a->next_obs + O_goal, a->cfg.obs_dim};
     int rc = replay_sample_impl(r, a->cfg.batch, nstep, gamma, EXORL_SAMPLER_PHILOX, nullptr, &slots, nullptr, a->capture_stream,
-                                &a->state->replay_counter, staged ? &stage : nullptr, a->calql.mc_return);
+                                &a->state->replay_counter, staged ? &stage : nullptr, a->calql.mc_return, goal ? &go : nullptr);
     if (rc == 0 && meta_dim > 0) rc = copy_meta_columns(a->obs, a->next_obs, a->cfg.obs_dim, a->cfg.batch, O_raw, meta_dim, a->capture_stream);
     // the module reads the batch slots and writes the reward slot only: what the sampler staged for the networks (observations and actions)
     // stays valid, and the agent's step reads the reward from its slot after this
@@ -1762,6 +1773,8 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
     a->graph_replay = r;
     a->graph_weights_epoch = replay_weights_epoch(r);
     a->graph_norm_on = replay_norm_on(r);
+    a->graph_goal = goal;
+    a->graph_goal_epoch = replay_goal_epoch(r);
     a->graph_gamma = gamma;
     a->graph_replay_ctr = ctr;
     a->graph_intr = it;
@@ -1770,6 +1783,10 @@ static int enable_graph_impl(exorl_agent_t* a, exorl_intr_t* it, const exorl_int
 
 int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep, float gamma, float stddev, void* stream) {
     return enable_graph_impl(a, nullptr, nullptr, 0, r, nstep, gamma, stddev, stream);
+}
+
+int exorl_agent_enable_graph_goal(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep, float gamma, float stddev, void* stream) {
+    return enable_graph_impl(a, nullptr, nullptr, 0, r, nstep, gamma, stddev, stream, true);
 }
 
 int exorl_agent_enable_graph_intr(exorl_agent_t* a, exorl_intr_t* intr, const exorl_intr_batch* batch, int32_t meta_dim, exorl_replay_t* r,
@@ -2149,6 +2166,8 @@ int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream) {
     EXORL_REQUIRE(replay_norm_on(a->graph_replay) == a->graph_norm_on, "agent_step_graph: exorl_replay_set_obs_norm switched the "
                   "normaliser %s after the capture: the graph holds the other gather kernel (call exorl_agent_enable_graph again)",
                   a->graph_norm_on ? "off" : "on");
+    EXORL_REQUIRE(!a->graph_goal || replay_goal_epoch(a->graph_replay) == a->graph_goal_epoch, "agent_step_graph: exorl_replay_set_goal was called "
+                  "after the capture: the graph relabels with the rule it was captured with (call exorl_agent_enable_graph_goal again)");
     if (a->calql.on) {
         const ReplayReturns g = replay_returns(a->graph_replay);
         EXORL_REQUIRE(g.valid && memcmp(&g.gamma, &a->graph_gamma, sizeof(float)) == 0, "agent_step_graph: the replay's return-to-go column is stale "

@@ -657,9 +657,18 @@ struct StageOut {
     int O, A, B, has_critic;
     StepState* st;
 };
+// The goal path of the gather (exorl_replay_set_goal): goals_host is the (pos_g, tau) per sample of the GIVEN / MT19937 samplers (Philox draws
+// them in the kernel), goal / next_goal take the goal's columns behind obs and behind next_obs, strides in floats. Un-staged only.
+struct GoalOut {
+    const int32_t* goals_host;
+    float* goal; int64_t goal_stride;
+    float* next_goal; int64_t next_goal_stride;
+};
 int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
-                       const uint64_t* dev_counter, const StageOut* stage = nullptr, float* mc_return = nullptr);
+                       const uint64_t* dev_counter, const StageOut* stage = nullptr, float* mc_return = nullptr, const GoalOut* goal = nullptr);
+int replay_goal_cols(exorl_replay* r);           // G of the goal rule in force, 0: none (exorl_replay_set_goal)
+uint64_t replay_goal_epoch(exorl_replay* r);     // number of exorl_replay_set_goal calls: a captured goal graph is bound to one value
 // the return-to-go column as exorl_replay_build_returns left it; valid = false once an episode was appended or evicted or the order was set.
 // ptr never moves once allocated.
 struct ReplayReturns { const float* ptr; float gamma; uint64_t epoch; bool valid; };

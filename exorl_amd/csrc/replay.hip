@@ -31,6 +31,13 @@
 // Return-to-go column (exorl_replay_build_returns): one float per arena row, G_i = r_i + (gamma d_i) G_{i+1} carried to the episode's end in fp64
 // (returns_to_go_kernel, one launch over the order table). The gather writes G[row0 + idx] beside reward and discount when
 // exorl_replay_sample_mc names a destination: Cal-QL's lower bound on the critic. Stale once an episode is appended or evicted or the order changes.
+//
+// Goal relabelling (exorl_replay_set_goal, exorl_replay_sample_goal; fp32 state arenas): every sample also gets a goal, a pair (pos_g, tau)
+// naming arena row row0[pos_g] + tau: the state its own trajectory reaches at next_obs (CUR) or later (TRAJ), or any state of the arena (RAND),
+// drawn from Philox blocks 1 and 2 of the sample's counter (block 0, the sample's own pair, keeps its bits) or shipped by the caller. The same
+// gather launch writes the goal's columns g = o[cols] (through the normaliser when it is on) behind obs and behind next_obs, and in the 'neg' and
+// 'sparse' modes feeds sample_tail's recurrence "reached / not reached" per-step inputs instead of the arena's reward and discount. The goal
+// path is gather_nstep_kernel<NORM, GoalView>, chosen on the host; the instantiations without a goal take no further argument and are unchanged.
 #include <algorithm>
 #include <vector>
 
@@ -175,6 +182,18 @@ struct exorl_replay {
     uint64_t rtg_epoch = 0;           // counts builds and invalidations
     std::vector<float> h_rtg;         // exorl_replay_returns_read's bounce buffer
     void returns_stale() { if (rtg_valid) { rtg_valid = false; rtg_epoch += 1; } }
+    // exorl_replay_set_goal: the goal columns and the geometric horizon's table, allocated at the first call and never moved (a captured graph
+    // holds the pointers; every other value below is a kernel argument, so a graph is bound to the goal_epoch of its capture)
+    int32_t* d_goal_cols = nullptr;   // obs_bytes / 4 entries, the first goal_n in use
+    uint32_t* d_goal_tab = nullptr;   // GOAL_TAB_MAX entries, the first goal_tab_n in use
+    int32_t goal_n = 0;               // 0: no goal rule set
+    int32_t goal_tab_n = 0;           // 0: the uniform horizon
+    uint64_t goal_t_cur = 0, goal_t_traj = 0;
+    int32_t goal_mode = EXORL_GOAL_KEEP;
+    uint64_t goal_epoch = 0;          // counts exorl_replay_set_goal calls
+    int32_t* d_goals = nullptr;       // the (pos_g, tau) pairs of the last goal launch, goals_cap of them
+    int goals_cap = 0;
+    std::vector<int32_t> h_goals;
 };
 
 namespace exorl {
@@ -190,6 +209,21 @@ struct ReplayView {
     int32_t guide_bits;
     const float *norm_mean, *norm_inv;      // null: observations are copied; else obs_bytes / 4 floats each, y = (x - mean[j]) * inv[j]
     const float* rtg;         // the return-to-go column, one float per arena row; read only where the launch has a destination for it
+};
+
+constexpr int GOAL_TAB_MAX = 4096;
+
+// What the goal path of the gather reads beside the ReplayView: the rule of exorl_replay_set_goal and the destinations of this launch.
+struct GoalView {
+    const int32_t* cols;      // n_cols observation column indices: g[j] = o[cols[j]]
+    int32_t n_cols;
+    uint64_t t_cur, t_traj;   // the source thresholds on x[0]: floor(p_cur 2^32), floor((p_cur + p_traj) 2^32)
+    const uint32_t* tab;      // the geometric horizon's table, tab[k] = floor(2^32 (1 - gamma_h^(k+1))), ascending; n_tab == 0: uniform
+    int32_t n_tab;
+    int32_t reward_mode;      // EXORL_GOAL_KEEP / _NEG / _SPARSE
+    int32_t* goals;           // batch (pos_g, tau) pairs: written by a Philox launch, read by the others
+    float *goal, *next_goal;  // destinations, strides in floats
+    int64_t goal_stride, next_goal_stride;
 };
 
 __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
@@ -227,6 +261,24 @@ __device__ __forceinline__ void norm_row(const unsigned char* __restrict__ src, 
     }
 }
 
+// The episode a Philox block picks, wave-uniform: on a weighted arena 64 of its bits scaled onto [0, total) and searched in cum through the
+// guide table (pos = the episode whose interval [cum[pos], cum[pos+1]) holds g), else word 0 scaled onto the episode count.
+__device__ __forceinline__ void pick_episode(const ReplayView& v, const uint32_t (&c)[4], int& pos) {
+    if (v.cum) {
+        const uint64_t u = ((uint64_t)c[2] << 32) | c[3];
+        const uint64_t g = __umul64hi(u, v.cum[v.n_episodes]);
+        const uint32_t k = (uint32_t)(u >> (64 - v.guide_bits));
+        int lo = v.guide[k], hi = v.guide[k + 1] + 1;      // g is monotone in u: the answer lies between the buckets' first episodes
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (v.cum[mid] <= g) lo = mid; else hi = mid;
+        }
+        pos = lo;
+    } else {
+        pos = (int)(((uint64_t)c[0] * (uint64_t)v.n_episodes) >> 32);
+    }
+}
+
 // The (episode position, start idx) pair of sample b, the same in every wave that asks for it: a Philox counter block (the cum / guide
 // search on a weighted arena), or the pair the host sampler shipped. Lane 0 of a `writer` wave records a drawn pair in pairs_out.
 __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pairs_in, int32_t* pairs_out, int b, int nstep, int sampler,
@@ -234,19 +286,7 @@ __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pa
     if (sampler == EXORL_SAMPLER_PHILOX) {
         uint32_t c[4] = {(uint32_t)b, (uint32_t)counter, (uint32_t)(counter >> 32), 0u};
         Philox::gen(c, seed);
-        if (v.cum) {           // wave-uniform: g in [0, total), pos = the episode whose interval [cum[pos], cum[pos+1]) holds g
-            const uint64_t u = ((uint64_t)c[2] << 32) | c[3];
-            const uint64_t g = __umul64hi(u, v.cum[v.n_episodes]);
-            const uint32_t k = (uint32_t)(u >> (64 - v.guide_bits));
-            int lo = v.guide[k], hi = v.guide[k + 1] + 1;      // g is monotone in u: the answer lies between the buckets' first episodes
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (v.cum[mid] <= g) lo = mid; else hi = mid;
-            }
-            pos = lo;
-        } else {
-            pos = (int)(((uint64_t)c[0] * (uint64_t)v.n_episodes) >> 32);
-        }
+        pick_episode(v, c, pos);
         const int span = v.len[pos] - nstep + 1;
         idx = (int)(((uint64_t)c[1] * (uint64_t)span) >> 32) + 1;
         if (writer && lane == 0) { pairs_out[2 * b] = pos; pairs_out[2 * b + 1] = idx; }
@@ -256,14 +296,58 @@ __device__ __forceinline__ void draw_pair(const ReplayView& v, const int32_t* pa
     }
 }
 
+// The goal (pos_g, tau) of sample b, whose own pair is (pos, idx): obs at time t = idx - 1, next_obs at t + nstep <= len[pos]. Philox: block
+// (b, counter, 1) gives the source on x[0] and the offset on x[1]; CUR is next_obs itself, TRAJ a state d steps behind it in the same episode
+// (uniform over what is left of it, or geometric from the table, the mass past the episode's end on its last state), RAND an episode from
+// block (b, counter, 2) through pick_episode and a time uniform over its len + 1 rows. Lane 0 records the drawn goal. Other samplers: the
+// goal the host shipped (range-checked there).
+__device__ __forceinline__ void draw_goal(const ReplayView& v, const GoalView& g, int b, int nstep, int sampler, uint64_t seed, uint64_t counter,
+                                          int lane, int pos, int idx, int& pos_g, int& tau) {
+    if (sampler == EXORL_SAMPLER_PHILOX) {
+        uint32_t x[4] = {(uint32_t)b, (uint32_t)counter, (uint32_t)(counter >> 32), 1u};
+        Philox::gen(x, seed);
+        const int tn = idx - 1 + nstep;
+        pos_g = pos;
+        if (x[0] < g.t_cur) {
+            tau = tn;
+        } else if (x[0] < g.t_traj) {
+            const int room = v.len[pos] - tn;
+            int d;
+            if (g.n_tab) {                     // d = #{k : tab[k] <= x[1]}, capped at the episode's end
+                int lo = 0, hi = g.n_tab;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (g.tab[mid] <= x[1]) lo = mid + 1; else hi = mid;
+                }
+                d = lo < room ? lo : room;
+            } else {
+                d = (int)(((uint64_t)x[1] * (uint64_t)(room + 1)) >> 32);
+            }
+            tau = tn + d;
+        } else {
+            uint32_t y[4] = {(uint32_t)b, (uint32_t)counter, (uint32_t)(counter >> 32), 2u};
+            Philox::gen(y, seed);
+            pick_episode(v, y, pos_g);
+            tau = (int)(((uint64_t)y[1] * (uint64_t)(v.len[pos_g] + 1)) >> 32);
+        }
+        if (lane == 0) { g.goals[2 * b] = pos_g; g.goals[2 * b + 1] = tau; }
+    } else {
+        pos_g = g.goals[2 * b];
+        tau = g.goals[2 * b + 1];
+    }
+}
+
 // What one wave writes per sample, whatever the shape of the observation gather: the action of arena row `row` (= row0 + idx), the meta
 // row of the step before it, and the n-step return and discount in the reference's operation order. fp contract is off INSIDE this body
 // (the pragma is lexically scoped): an FMA in the recurrence would stop matching NumPy.
 // next_ok (idx + nstep <= len[pos], the caller has both): the episode holds the action taken at next_obs, arena row `row + nstep`. Where
 // it does not, that row is the next episode's dummy row or lies past the arena's end and is not read: the sample gets zeros.
 // mc (null: not written): the sample's Monte-Carlo return-to-go, the column's value at `row`, a plain copy.
+// RELABEL (the goal path) with a mode other than EXORL_GOAL_KEEP: the recurrence runs on "reached / not reached" inputs instead of the arena's,
+// rho_i = (NEG: 0 on the reaching step, else -1; SPARSE: 1 on it, else 0), c_i = 0 on it, else 1; only step nstep - 1 can be the reaching one.
+template <bool RELABEL = false>
 __device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_batch_out& out, int b, int64_t row, int nstep, float gamma,
-                                            int lane, bool next_ok, float* mc) {
+                                            int lane, bool next_ok, float* mc, int mode = EXORL_GOAL_KEEP, bool reached = false) {
 #pragma clang fp contract(off)
     for (int j = lane; j < v.act_dim; j += 64) out.action[(int64_t)b * out.action_stride + j] = v.act[row * v.act_dim + j];
     if (out.next_action) {                           // wave-uniform, as next_ok is
@@ -281,9 +365,18 @@ __device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_bat
     if (lane == 0) {
         float R = 0.0f, D = 1.0f;
         for (int i = 0; i < nstep; ++i) {
-            const float t = D * v.rew[row + i];        // replay_buffer.py:233  reward += discount * step_reward
+            float rho, c;
+            if (RELABEL && mode != EXORL_GOAL_KEEP) {
+                const bool hit = reached && i == nstep - 1;
+                rho = mode == EXORL_GOAL_NEG ? (hit ? 0.0f : -1.0f) : (hit ? 1.0f : 0.0f);
+                c = hit ? 0.0f : 1.0f;
+            } else {
+                rho = v.rew[row + i];
+                c = v.disc[row + i];
+            }
+            const float t = D * rho;                   // replay_buffer.py:233  reward += discount * step_reward
             R = R + t;
-            const float u = v.disc[row + i] * gamma;   // replay_buffer.py:234  discount *= ep_discount * gamma
+            const float u = c * gamma;                 // replay_buffer.py:234  discount *= ep_discount * gamma
             D = D * u;
         }
         out.reward[b] = R;
@@ -292,13 +385,18 @@ __device__ __forceinline__ void sample_tail(const ReplayView& v, const exorl_bat
     }
 }
 
+template <typename T>
+__device__ __forceinline__ const T& only(const T& x) { return x; }
+
 // NORM = false is the copying gather; NORM = true (exorl_replay_set_obs_norm) differs only where an observation element is written.
-template <bool NORM>
+// Goal is empty (the kernel as it always was, argument for argument) or one GoalView: the goal path, which also draws the sample's goal,
+// writes its columns behind obs and next_obs and hands sample_tail the reward mode and whether next_obs IS the goal.
+template <bool NORM, typename... Goal>
 __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const int32_t* pairs_in,
                                                            int32_t* pairs_out, exorl_batch_out out,
                                                            int batch, int nstep, float gamma, int sampler,
                                                            uint64_t seed, uint64_t counter_val,
-                                                           const uint64_t* counter_ptr, int vec16, StageOut stage, float* mc) {
+                                                           const uint64_t* counter_ptr, int vec16, StageOut stage, float* mc, Goal... goal) {
 #pragma clang fp contract(off)
     if (stage.st && blockIdx.x == 0 && threadIdx.x == 0) step_begin_device(stage.st, 0);   // noise counter, Adam scalars of this step
     const uint64_t counter = counter_ptr ? *counter_ptr : counter_val;
@@ -341,7 +439,23 @@ __global__ __launch_bounds__(256) void gather_nstep_kernel(ReplayView v, const i
         if (stage.has_critic)
             for (int j = lane; j < A; j += 64) stage.xc_cur[(int64_t)b * W + O + j] = v.act[row * v.act_dim + j];
     }
-    sample_tail(v, out, b, row, nstep, gamma, lane, idx + nstep <= v.len[pos], mc);
+    if constexpr (sizeof...(Goal) > 0) {
+        const GoalView& gv = only(goal...);
+        int pos_g, tau;
+        draw_goal(v, gv, b, nstep, sampler, seed, counter, lane, pos, idx, pos_g, tau);
+        const float* gs = reinterpret_cast<const float*>(v.obs + (v.row0[pos_g] + tau) * v.obs_bytes);
+        for (int j = lane; j < gv.n_cols; j += 64) {
+            const int c = gv.cols[j];
+            float x = gs[c];
+            if constexpr (NORM) x = (x - v.norm_mean[c]) * v.norm_inv[c];      // norm_row's two roundings
+            gv.goal[(int64_t)b * gv.goal_stride + j] = x;
+            gv.next_goal[(int64_t)b * gv.next_goal_stride + j] = x;
+        }
+        sample_tail<true>(v, out, b, row, nstep, gamma, lane, idx + nstep <= v.len[pos], mc, gv.reward_mode,
+                          pos_g == pos && tau == idx - 1 + nstep);
+    } else {
+        sample_tail(v, out, b, row, nstep, gamma, lane, idx + nstep <= v.len[pos], mc);
+    }
 }
 
 // copy_row with four loads of a lane in flight before the first store (the compiler keeps copy_row's loop at one load, one wait, one store):
@@ -714,6 +828,9 @@ int exorl_replay_destroy(exorl_replay_t* r) {
     if (r->d_slab) (void)hipFree(r->d_slab);
     if (r->d_returns) (void)hipFree(r->d_returns);
     if (r->d_rtg) (void)hipFree(r->d_rtg);
+    if (r->d_goal_cols) (void)hipFree(r->d_goal_cols);
+    if (r->d_goal_tab) (void)hipFree(r->d_goal_tab);
+    if (r->d_goals) (void)hipFree(r->d_goals);
     if (r->d_keys) (void)hipFree(r->d_keys);
     if (r->d_kitem0) (void)hipFree(r->d_kitem0);
     if (r->d_ktrans0) (void)hipFree(r->d_ktrans0);
@@ -934,6 +1051,52 @@ int exorl_replay_set_obs_norm(exorl_replay_t* r, int32_t n_cols, const float* me
     return 0;
 }
 
+int exorl_replay_set_goal(exorl_replay_t* r, const int32_t* cols_host, int32_t n_cols, double p_cur, double p_traj, double p_rand,
+                          double horizon_gamma, int32_t reward_mode) {
+    EXORL_REQUIRE(r, "replay_set_goal: null handle");
+    if (n_cols == 0) {
+        r->goal_n = 0;
+        r->goal_epoch += 1;
+        return 0;
+    }
+    const int O = r->cfg.obs_bytes / 4;
+    EXORL_REQUIRE(r->frames == 1, "replay_set_goal: the arena stacks %d frames per observation (exorl_replay_set_frame_stack): goals are columns "
+                  "of fp32 state rows", r->frames);
+    EXORL_REQUIRE(r->cfg.meta_dim == 0, "replay_set_goal: the arena has %d meta columns: the goal takes the place behind the observation that "
+                  "[obs | meta] rows give them", r->cfg.meta_dim);
+    EXORL_REQUIRE(cols_host && n_cols >= 1 && n_cols <= O, "replay_set_goal: n_cols=%d goal columns of %d fp32 observation columns", n_cols, O);
+    for (int j = 0; j < n_cols; ++j)
+        EXORL_REQUIRE(cols_host[j] >= 0 && cols_host[j] < O, "replay_set_goal: cols[%d]=%d outside [0, %d)", j, cols_host[j], O);
+    EXORL_REQUIRE(p_cur >= 0.0 && p_traj >= 0.0 && p_rand >= 0.0 && fabs(p_cur + p_traj + p_rand - 1.0) <= 1e-6,
+                  "replay_set_goal: p_cur=%g p_traj=%g p_rand=%g must be non-negative and sum to 1", p_cur, p_traj, p_rand);
+    EXORL_REQUIRE(horizon_gamma < 1.0, "replay_set_goal: horizon_gamma=%g must be below 1 (<= 0: the uniform horizon)", horizon_gamma);
+    EXORL_REQUIRE(reward_mode == EXORL_GOAL_KEEP || reward_mode == EXORL_GOAL_NEG || reward_mode == EXORL_GOAL_SPARSE,
+                  "replay_set_goal: unknown reward_mode %d", reward_mode);
+    // tab[k] = floor(2^32 (1 - gamma_h^(k+1))), the power by repeated multiplication in double (no libm: a reference restates it to the bit);
+    // cut at the first entry >= 2^32 - 1, which is left out, or at GOAL_TAB_MAX entries
+    std::vector<uint32_t> tab;
+    if (horizon_gamma > 0.0) {
+        double p = horizon_gamma;
+        for (int k = 0; k < GOAL_TAB_MAX; ++k, p *= horizon_gamma) {
+            const double e = floor(4294967296.0 * (1.0 - p));
+            if (e >= 4294967295.0) break;
+            tab.push_back((uint32_t)e);
+        }
+    }
+    EXORL_CHECK_HIP(hipDeviceSynchronize());      // a gather enqueued earlier may still read the columns and the table that are replaced
+    if (!r->d_goal_cols) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_goal_cols, (size_t)O * sizeof(int32_t)));
+    if (!r->d_goal_tab) EXORL_CHECK_HIP(hipMalloc((void**)&r->d_goal_tab, (size_t)GOAL_TAB_MAX * sizeof(uint32_t)));
+    EXORL_CHECK_HIP(hipMemcpy(r->d_goal_cols, cols_host, (size_t)n_cols * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!tab.empty()) EXORL_CHECK_HIP(hipMemcpy(r->d_goal_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    r->goal_n = n_cols;
+    r->goal_tab_n = (int32_t)tab.size();
+    r->goal_t_cur = (uint64_t)floor(p_cur * 4294967296.0);
+    r->goal_t_traj = (uint64_t)floor((p_cur + p_traj) * 4294967296.0);
+    r->goal_mode = reward_mode;
+    r->goal_epoch += 1;
+    return 0;
+}
+
 int exorl_replay_build_keys(exorl_replay_t* r, float beta, int32_t key_every, void* stream) {
     EXORL_REQUIRE(r, "replay_build_keys: null handle");
     EXORL_REQUIRE(beta >= 0.f && key_every >= 1, "replay_build_keys: needs beta >= 0 and key_every >= 1 (got %g, %d)", beta, key_every);
@@ -1062,6 +1225,12 @@ int replay_prepare(exorl_replay* r, int32_t batch, int32_t nstep, hipStream_t s)
         EXORL_CHECK_HIP(hipMalloc((void**)&r->d_pairs, (size_t)batch * 2 * sizeof(int32_t)));
         r->pairs_cap = batch;
     }
+    if (r->goal_n && batch > r->goals_cap) {
+        if (r->d_goals) EXORL_CHECK_HIP(hipFree(r->d_goals));
+        r->d_goals = nullptr; r->goals_cap = 0;
+        EXORL_CHECK_HIP(hipMalloc((void**)&r->d_goals, (size_t)batch * 2 * sizeof(int32_t)));
+        r->goals_cap = batch;
+    }
     if (nstep > 0 && !r->weighted)      // unweighted Philox draws a start inside every episode: all of them must hold nstep transitions
         EXORL_REQUIRE(r->min_len - nstep + 1 >= 1, "replay_sample: shortest episode (%d) shorter than nstep=%d", r->min_len, nstep);
     return 0;
@@ -1071,8 +1240,19 @@ int replay_prepare(exorl_replay* r, int32_t batch, int32_t nstep, hipStream_t s)
 // still advanced so eager sampling continues the stream afterwards.
 int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler,
                        const int32_t* pairs_host, const exorl_batch_out* out, int32_t* pairs_out_host, hipStream_t s,
-                       const uint64_t* dev_counter, const StageOut* stage, float* mc_return) {
+                       const uint64_t* dev_counter, const StageOut* stage, float* mc_return, const GoalOut* goal) {
     EXORL_REQUIRE(r && out, "replay_sample: null argument");
+    if (goal) {
+        EXORL_REQUIRE(r->goal_n > 0, "replay_sample_goal: no goal rule is set (exorl_replay_set_goal)");
+        EXORL_REQUIRE(r->frames == 1 && !stage, "replay_sample_goal: goals are gathered from fp32 state rows into the caller's rows, un-staged");
+        EXORL_REQUIRE(goal->goal && goal->next_goal && goal->goal_stride >= r->goal_n && goal->next_goal_stride >= r->goal_n,
+                      "replay_sample_goal: goal / next_goal destinations of %d floats per row (strides %lld / %lld)", r->goal_n,
+                      (long long)goal->goal_stride, (long long)goal->next_goal_stride);
+        EXORL_REQUIRE(!mc_return || r->goal_mode == EXORL_GOAL_KEEP, "replay_sample_goal: an mc_return destination with a relabelled reward: the "
+                      "return-to-go column is the arena reward's, which only reward_mode keep emits");
+        EXORL_REQUIRE(sampler == EXORL_SAMPLER_PHILOX || goal->goals_host, "replay_sample_goal: EXORL_SAMPLER_GIVEN and EXORL_SAMPLER_MT19937 need "
+                      "goals_host, the (pos_g, tau) of every sample");
+    }
     if (mc_return) {
         EXORL_REQUIRE(r->rtg_valid, "replay_sample_mc: no return-to-go column, or a stale one: an episode was appended or evicted or the order was "
                       "set since exorl_replay_build_returns (call it again)");
@@ -1126,6 +1306,18 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
         set_error("replay_sample: unknown sampler %d", sampler);
         return 2;
     }
+    if (goal && sampler != EXORL_SAMPLER_PHILOX) {
+        r->h_goals.resize((size_t)batch * 2);
+        for (int b = 0; b < batch; ++b) {
+            const int pos = goal->goals_host[2 * b], tau = goal->goals_host[2 * b + 1];
+            EXORL_REQUIRE(pos >= 0 && pos < n, "replay_sample_goal: goal %d: position %d out of range [0,%d)", b, pos, n);
+            const int len = r->slots[r->order[pos]].rows - 1;
+            EXORL_REQUIRE(tau >= 0 && tau <= len, "replay_sample_goal: goal %d: time %d out of range [0,%d]", b, tau, len);
+            r->h_goals[2 * b] = pos;
+            r->h_goals[2 * b + 1] = tau;
+        }
+        EXORL_CHECK_HIP(hipMemcpyAsync(r->d_goals, r->h_goals.data(), (size_t)batch * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
     ReplayView v{r->obs, r->act, r->rew, r->disc, r->meta, r->d_row0, r->d_len, r->cfg.obs_bytes, r->cfg.act_dim, r->cfg.meta_dim, n,
                  r->weighted && sampler == EXORL_SAMPLER_PHILOX ? r->d_cum : nullptr, r->d_guide, r->guide_bits,
                  r->norm_on ? r->d_norm : nullptr, r->norm_on ? r->d_norm + r->cfg.obs_bytes / 4 : nullptr, r->d_rtg};
@@ -1135,9 +1327,17 @@ int replay_sample_impl(exorl_replay* r, int32_t batch, int32_t nstep, float gamm
     } else {
         const int vec16 = (r->cfg.obs_bytes % 16 == 0) && (out->obs_stride % 16 == 0) && (out->next_obs_stride % 16 == 0) &&
                           ((uintptr_t)out->obs % 16 == 0) && ((uintptr_t)out->next_obs % 16 == 0);
-        hipLaunchKernelGGL(r->norm_on ? gather_nstep_kernel<true> : gather_nstep_kernel<false>, dim3(cdiv(batch, 4)), dim3(256), 0, s, v,
-                           r->d_pairs, r->d_pairs, *out, batch, nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16,
-                           stage ? *stage : StageOut{}, mc_return);
+        if (goal) {
+            const GoalView gv{r->d_goal_cols, r->goal_n, r->goal_t_cur, r->goal_t_traj, r->d_goal_tab, r->goal_tab_n, r->goal_mode, r->d_goals,
+                              goal->goal, goal->next_goal, goal->goal_stride, goal->next_goal_stride};
+            const auto kernel = r->norm_on ? gather_nstep_kernel<true, GoalView> : gather_nstep_kernel<false, GoalView>;
+            hipLaunchKernelGGL(kernel, dim3(cdiv(batch, 4)), dim3(256), 0, s, v, r->d_pairs, r->d_pairs, *out, batch, nstep, gamma, sampler,
+                               r->philox_seed, r->philox_counter, dev_counter, vec16, StageOut{}, mc_return, gv);
+        } else {
+            hipLaunchKernelGGL(r->norm_on ? gather_nstep_kernel<true> : gather_nstep_kernel<false>, dim3(cdiv(batch, 4)), dim3(256), 0, s, v,
+                               r->d_pairs, r->d_pairs, *out, batch, nstep, gamma, sampler, r->philox_seed, r->philox_counter, dev_counter, vec16,
+                               stage ? *stage : StageOut{}, mc_return);
+        }
     }
     EXORL_LAUNCH_CHECK();
     if (sampler == EXORL_SAMPLER_PHILOX) r->philox_counter += 1;
@@ -1156,6 +1356,8 @@ ReplayKeys replay_keys(exorl_replay* r) {
 void replay_dims(exorl_replay* r, int* act_dim, int* meta_dim) { *act_dim = r->cfg.act_dim; *meta_dim = r->cfg.meta_dim; }
 void replay_advance_philox(exorl_replay* r, uint64_t n) { r->philox_counter += n; }
 ReplayReturns replay_returns(exorl_replay* r) { return ReplayReturns{r->d_rtg, r->rtg_gamma, r->rtg_epoch, r->rtg_valid}; }
+int replay_goal_cols(exorl_replay* r) { return r->goal_n; }
+uint64_t replay_goal_epoch(exorl_replay* r) { return r->goal_epoch; }
 }  // namespace exorl
 
 extern "C" {
@@ -1168,6 +1370,21 @@ int exorl_replay_sample(exorl_replay_t* r, int32_t batch, int32_t nstep, float g
 int exorl_replay_sample_mc(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler, const int32_t* pairs_host,
                            const exorl_batch_out* out, float* mc_return_dev, int32_t* pairs_out_host, void* stream) {
     return replay_sample_impl(r, batch, nstep, gamma, sampler, pairs_host, out, pairs_out_host, as_stream(stream), nullptr, nullptr, mc_return_dev);
+}
+
+int exorl_replay_sample_goal(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler, const int32_t* pairs_host,
+                             const int32_t* goals_host, const exorl_batch_out* out, float* goal_dev, int64_t goal_stride, float* next_goal_dev,
+                             int64_t next_goal_stride, float* mc_return_dev, int32_t* pairs_out_host, void* stream) {
+    const GoalOut g{goals_host, goal_dev, goal_stride, next_goal_dev, next_goal_stride};
+    return replay_sample_impl(r, batch, nstep, gamma, sampler, pairs_host, out, pairs_out_host, as_stream(stream), nullptr, nullptr, mc_return_dev, &g);
+}
+
+int exorl_replay_last_goals(exorl_replay_t* r, int32_t batch, int32_t* goals_host, void* stream) {
+    EXORL_REQUIRE(r && goals_host && batch > 0 && batch <= r->goals_cap, "replay_last_goals: bad arguments (no goal launch of that batch yet?)");
+    hipStream_t s = as_stream(stream);
+    EXORL_CHECK_HIP(hipMemcpyAsync(goals_host, r->d_goals, (size_t)batch * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    EXORL_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
 }
 
 int exorl_replay_last_pairs(exorl_replay_t* r, int32_t batch, int32_t* pairs_host, void* stream) {

@@ -248,6 +248,12 @@ class AgentEngine(_Phased):
         L.check(self.lib.exorl_agent_enable_graph(self.h, replay_engine.h, nstep, gamma, stddev, L.current_stream()))
         self.graph_captures = getattr(self, 'graph_captures', 0) + 1
 
+    def enable_graph_goal(self, replay_engine, nstep, gamma, stddev):
+        """enable_graph on an arena with a goal rule (ReplayEngine.set_goal): the captured gather relabels and writes [obs | g] rows into the
+        batch slots (exorl_agent_enable_graph_goal); needs the arena's O + G == obs_dim. A later set_goal makes the graph stale."""
+        L.check(self.lib.exorl_agent_enable_graph_goal(self.h, replay_engine.h, nstep, gamma, stddev, L.current_stream()))
+        self.graph_captures = getattr(self, 'graph_captures', 0) + 1
+
     def enable_graph_intr(self, replay_engine, nstep, gamma, stddev, intr=None, batch=None, meta_dim=0):
         """enable_graph with a reward-free agent's module step in front of the agent's (exorl_agent_enable_graph_intr): `batch` is the
         module's L.IntrBatch over this engine's batch slots; meta_dim > 0 for [obs | meta] rows. intr=None: the agent's step alone."""
@@ -947,6 +953,7 @@ class ReplayEngine:
             L.check(self.lib.exorl_replay_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self._slot_len, self._order = {}, []      # the length of every resident slot and the order table: how returns_to_go() splits the column
+        self.goal = None                          # the GoalRelabel in force (set_goal)
         if self.frame_stack > 1:
             self.set_frame_stack(self.frame_stack)
 
@@ -1104,6 +1111,39 @@ class ReplayEngine:
         self._state_cols('clear_obs_normalizer')
         L.check(self.lib.exorl_replay_set_obs_norm(self.h, 0, None, None, L.current_stream()))
 
+    GOAL_REWARD = {'keep': L.GOAL_KEEP, 'neg': L.GOAL_NEG, 'sparse': L.GOAL_SPARSE}
+
+    def set_goal(self, goal):
+        """Hindsight relabelling in the gather (exorl_replay_set_goal). `goal`: a replay_buffer.GoalRelabel (cols, p_cur, p_traj, p_rand,
+        horizon_discount, reward), or None to clear the rule. From then on sample_into(..., goal=...) draws a goal per sample (the state the
+        trajectory reaches at next_obs, a later state of it, or any state of the arena), emits its columns behind obs and next_obs and, for
+        reward 'neg' / 'sparse', a reached / not-reached reward and discount. float32 state arenas without meta columns only. A set-up
+        call: it synchronises the device; a graph captured on the arena's goal path must be captured again afterwards."""
+        if goal is None:
+            L.check(self.lib.exorl_replay_set_goal(self.h, None, 0, 0.0, 0.0, 0.0, 0.0, 0))
+            self.goal = None
+            return
+        n = self._state_cols('set_goal')
+        if self.frame_stack > 1 or len(self.obs_shape) != 1:
+            raise ValueError(f'set_goal: the arena holds observations of shape {self.obs_shape} (frame_stack={self.frame_stack}); goals are '
+                             'columns of float32 state rows, not pixels')
+        if self.meta_dim:
+            raise ValueError(f'set_goal: the arena has {self.meta_dim} meta columns: the goal takes the place behind the observation that '
+                             '[obs | meta] rows give them')
+        cols = np.ascontiguousarray(goal.cols, np.int32)
+        if cols.size and (cols.min() < 0 or cols.max() >= n):
+            raise ValueError(f'set_goal: goal columns {cols.tolist()} outside the arena\'s {n} observation columns')
+        L.check(self.lib.exorl_replay_set_goal(self.h, cols.ctypes.data, cols.size, goal.p_cur, goal.p_traj, goal.p_rand,
+                                               0.0 if goal.horizon_discount is None else float(goal.horizon_discount),
+                                               self.GOAL_REWARD[goal.reward]))
+        self.goal = goal
+
+    def last_goals(self, batch):
+        """(batch, 2) int32: the (pos_g, tau) goal of every sample of the last goal launch, as last_pairs gives the pairs."""
+        out = np.zeros((batch, 2), np.int32)
+        L.check(self.lib.exorl_replay_last_goals(self.h, batch, out.ctypes.data, L.current_stream()))
+        return out
+
     def seed_mt_from_globals(self):
         """Adopts the CURRENT state of Python's `random` and NumPy's legacy global generator — the two
         streams replay_buffer.py:169,222 draw from — so the index stream continues exactly where the
@@ -1121,17 +1161,43 @@ class ReplayEngine:
     def seed_philox(self, seed):
         L.check(self.lib.exorl_replay_seed_philox(self.h, seed))
 
-    def sample_into(self, out, batch, nstep, gamma, sampler, pairs=None, want_pairs=False, mc_return=None):
+    def sample_into(self, out, batch, nstep, gamma, sampler, pairs=None, want_pairs=False, mc_return=None, goal=None, goals=None):
         """mc_return: a (batch,) float32 device tensor that takes each sample's return-to-go from the column of build_returns, written by
-        the same gather launch (exorl_replay_sample_mc); None: exorl_replay_sample."""
+        the same gather launch (exorl_replay_sample_mc); None: exorl_replay_sample.
+        goal (needs set_goal): True writes the goal's G columns at column O of the rows of out.obs and out.next_obs, which must be
+        4 * (O + G) bytes apart; a pair (goal, next_goal) of 2-D float32 device tensors with unit column stride and at least G columns takes
+        them instead. goals: the (batch, 2) int32 (pos_g, tau) of every sample for the GIVEN and MT19937 samplers; Philox draws them in the
+        kernel (last_goals reads them back). None: the gather without goals, bit for bit what it was."""
         pin = np.ascontiguousarray(pairs, np.int32) if pairs is not None else None
         pout = np.zeros((batch, 2), np.int32) if want_pairs else None
+        if mc_return is not None and (mc_return.dtype != torch.float32 or mc_return.numel() < batch or not mc_return.is_contiguous()):
+            raise L.ExorlError(f'sample_into: mc_return must be a contiguous float32 tensor of at least {batch} elements')
+        if goal is not None and goal is not False:
+            if self.goal is None:
+                raise ValueError('sample_into: goal= needs a goal rule (set_goal)')
+            O, G = self.obs_bytes // 4, len(self.goal.cols)
+            if goal is True:
+                if out.obs_stride != 4 * (O + G) or out.next_obs_stride != 4 * (O + G):
+                    raise ValueError(f'sample_into: goal=True writes [obs | g] rows of {O} + {G} floats: obs_stride={out.obs_stride} and '
+                                     f'next_obs_stride={out.next_obs_stride} must both be {4 * (O + G)} bytes')
+                dst = (out.obs + 4 * O, O + G, out.next_obs + 4 * O, O + G)
+            else:
+                g, ng = goal
+                for t in (g, ng):
+                    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < batch or t.shape[1] < G or t.stride(1) != 1:
+                        raise ValueError(f'sample_into: goal destinations must be 2-D float32 tensors of at least {batch} x {G} with unit '
+                                         'column stride')
+                dst = (g.data_ptr(), g.stride(0), ng.data_ptr(), ng.stride(0))
+            gin = np.ascontiguousarray(goals, np.int32) if goals is not None else None
+            if gin is not None and gin.shape != (batch, 2):
+                raise ValueError(f'sample_into: goals must be ({batch}, 2) (pos_g, tau) pairs, got {gin.shape}')
+            L.check(self.lib.exorl_replay_sample_goal(self.h, batch, nstep, gamma, sampler, L.ptr(pin), L.ptr(gin), C.byref(out), dst[0], dst[1],
+                                                      dst[2], dst[3], L.ptr(mc_return), L.ptr(pout), L.current_stream()))
+            return pout
         if mc_return is None:
             L.check(self.lib.exorl_replay_sample(self.h, batch, nstep, gamma, sampler, L.ptr(pin), C.byref(out), L.ptr(pout),
                                                  L.current_stream()))
             return pout
-        if mc_return.dtype != torch.float32 or mc_return.numel() < batch or not mc_return.is_contiguous():
-            raise L.ExorlError(f'sample_into: mc_return must be a contiguous float32 tensor of at least {batch} elements')
         L.check(self.lib.exorl_replay_sample_mc(self.h, batch, nstep, gamma, sampler, L.ptr(pin), C.byref(out), mc_return.data_ptr(), L.ptr(pout),
                                                 L.current_stream()))
         return pout
@@ -1141,10 +1207,20 @@ class ReplayEngine:
         L.check(self.lib.exorl_replay_last_pairs(self.h, batch, out.ctypes.data, L.current_stream()))
         return out
 
-    def alloc_batch(self, batch):
-        """Fresh output tensors (B,*obs_shape) (B,A) (B,1) (B,1) (B,*obs_shape) [(B,meta)] and the BatchOut that points at them."""
+    def alloc_batch(self, batch, goal_cols=0):
+        """Fresh output tensors (B,*obs_shape) (B,A) (B,1) (B,1) (B,*obs_shape) [(B,meta)] and the BatchOut that points at them.
+        goal_cols=G > 0 (a state arena with a goal rule): obs and next_obs are (B, O + G), the [obs | g] rows of sample_into(goal=True)."""
         tdt = torch.uint8 if self.obs_dtype == np.uint8 else torch.float32
         dev = self.device
+        if goal_cols:
+            W = self.obs_bytes // 4 + int(goal_cols)
+            obs = torch.empty(batch, W, dtype=torch.float32, device=dev)
+            nobs = torch.empty_like(obs)
+            act = torch.empty(batch, self.act_dim, dtype=torch.float32, device=dev)
+            rew = torch.empty(batch, 1, dtype=torch.float32, device=dev)
+            disc = torch.empty(batch, 1, dtype=torch.float32, device=dev)
+            out = L.BatchOut(obs.data_ptr(), 4 * W, act.data_ptr(), self.act_dim, rew.data_ptr(), disc.data_ptr(), nobs.data_ptr(), 4 * W, None, 0)
+            return (obs, act, rew, disc, nobs), out
         obs = torch.empty((batch,) + self.obs_shape, dtype=tdt, device=dev)
         nobs = torch.empty_like(obs)
         act = torch.empty(batch, self.act_dim, dtype=torch.float32, device=dev)

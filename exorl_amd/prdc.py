@@ -41,6 +41,9 @@ class PRDCAgent(TD3BCAgent):
         """Builds the key table from `replay_iter`'s arena (after the loader's normaliser is in place, so the keys are what the gather
         emits) and binds it; every key_every-th transition is kept. Call it before enable_graph (with a graph captured the engine
         refuses) and again whenever the arena, its order or its normaliser changed. Returns the number of rows."""
+        if getattr(replay_iter, 'goal', None) is not None:
+            raise ValueError('PRDCAgent.bind_dataset: a goal iterator (goal=GoalRelabel) fills [obs | g] rows with a goal drawn per sample; '
+                             'the key table holds [beta s | a] rows of the arena and has no goal to match: goal-conditioned PRDC is not built')
         arenas = getattr(replay_iter, '_arenas', None)
         if arenas is None:
             raise ValueError('PRDCAgent.bind_dataset: needs an iterator over an HBM arena (iter(loader) or an ArenaIterator); a plain '

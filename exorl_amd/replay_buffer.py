@@ -158,6 +158,81 @@ class ReplayBufferStorage:
             self._fresh.popitem(last=False)
 
 
+class GoalRelabel:
+    """Hindsight goal relabelling in the HBM gather (ReplayEngine.set_goal): what goal= of the iterators, loaders and train_offline takes.
+
+    cols: the observation columns that make a goal, g = o[cols] (1 <= G <= O distinct-or-not indices; range(O) is the whole state).
+    Per sample a goal state is drawn: with probability p_cur the state the sample's own trajectory reaches at next_obs, with p_traj a
+    state d >= 0 steps behind next_obs in the same episode, with p_rand any state of the arena (a weighted arena picks the episode by its
+    weights). horizon_discount=h in (0, 1): d is geometric, P(d = k) = (1 - h) h^k, the mass past the episode's end on its last state;
+    None: d is uniform over what is left of the episode. The batches become [obs | g] and [next_obs | g] rows of O + G floats.
+    reward: 'neg' (0 where next_obs IS the goal state, else -1; the discount is 0 where it is reached), 'sparse' (1 / 0, same discount)
+    or 'keep' (the arena's reward and discount: the goal is context only, as goal-conditioned BC uses it). Reached is equality of the
+    indices (episode, time), not a distance. Agents are built with obs_shape=(O + G,) and act on goal_obs(obs, goal_observation)."""
+    REWARDS = ('neg', 'sparse', 'keep')
+
+    def __init__(self, cols, p_cur=0.2, p_traj=0.5, p_rand=0.3, horizon_discount=0.99, reward='neg'):
+        cols = [cols] if isinstance(cols, (int, np.integer)) else list(cols)
+        if not cols:
+            raise ValueError('GoalRelabel: cols is empty: a goal is at least one observation column')
+        if any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0 for c in cols):
+            raise ValueError(f'GoalRelabel: cols={cols!r}: expected non-negative integer observation column indices')
+        ps = (float(p_cur), float(p_traj), float(p_rand))
+        if any(not np.isfinite(p) or p < 0 for p in ps) or abs(sum(ps) - 1.0) > 1e-6:
+            raise ValueError(f'GoalRelabel: p_cur={p_cur} p_traj={p_traj} p_rand={p_rand} must be non-negative and sum to 1')
+        if horizon_discount is not None and not 0.0 < float(horizon_discount) < 1.0:
+            raise ValueError(f'GoalRelabel: horizon_discount={horizon_discount}: expected a value in (0, 1), or None for the uniform horizon')
+        if reward not in self.REWARDS:
+            raise ValueError(f"GoalRelabel: reward={reward!r}: expected 'neg', 'sparse' or 'keep'")
+        self.cols = tuple(int(c) for c in cols)
+        self.p_cur, self.p_traj, self.p_rand = ps
+        self.horizon_discount = None if horizon_discount is None else float(horizon_discount)
+        self.reward = reward
+
+    def __repr__(self):
+        return (f'GoalRelabel(cols={list(self.cols)}, p_cur={self.p_cur}, p_traj={self.p_traj}, p_rand={self.p_rand}, '
+                f'horizon_discount={self.horizon_discount}, reward={self.reward!r})')
+
+    def goal_obs(self, obs, goal_observation):
+        """[obs | goal_observation[cols]] along the last axis, for agent.act(): numpy arrays or torch tensors, a vector or a batch."""
+        cols = list(self.cols)
+        if hasattr(obs, 'data_ptr'):
+            return torch.cat([obs, torch.as_tensor(goal_observation).to(obs)[..., cols]], -1)
+        return np.concatenate([np.asarray(obs), np.asarray(goal_observation, np.asarray(obs).dtype)[..., cols]], -1)
+
+    def widen_normalizer(self, mean32, inv32):
+        """The (mean, inv) pair of [obs | g] rows from the observation's: [mu | mu[cols]], [inv | inv[cols]]."""
+        cols = list(self.cols)
+        m, w = np.asarray(mean32, np.float32).reshape(-1), np.asarray(inv32, np.float32).reshape(-1)
+        return np.concatenate([m, m[cols]]), np.concatenate([w, w[cols]])
+
+
+def _goal_args(goal, sampler, frame_stack=None, meta_keys=()):
+    """The GoalRelabel a loader or iterator applies (None: none), after refusing what the goal path of the gather cannot honour."""
+    if goal is None:
+        return None
+    if not isinstance(goal, GoalRelabel):
+        raise ValueError(f'goal={goal!r}: expected a GoalRelabel')
+    if sampler != 'philox':
+        raise ValueError(f"goal= needs sampler='philox' (the goals are drawn in the gather kernel): sampler={sampler!r} reproduces the "
+                         "reference's index stream, which has no goals")
+    if frame_stack is not None and int(frame_stack) > 1:
+        raise ValueError(f'goal= with frame_stack={frame_stack}: goals are columns of float32 state rows, not pixels')
+    if meta_keys:
+        raise ValueError(f'goal= on a storage with meta specs {tuple(meta_keys)}: the goal takes the place behind the observation that '
+                         '[obs | meta] rows give them')
+    return goal
+
+
+def _check_goal_rows(out, engine, goal):
+    """A goal iterator fills [obs | g] rows: the caller's rows must be exactly O + G floats apart."""
+    want = engine.obs_bytes + 4 * len(goal.cols)
+    if out.obs_stride != want or out.next_obs_stride != want:
+        raise ValueError(f'goal iterator: it writes [obs | g] rows of {engine.obs_bytes // 4} + {len(goal.cols)} floats, the destination has '
+                         f'obs_stride={out.obs_stride} / next_obs_stride={out.next_obs_stride} bytes (expected {want}): build the agent '
+                         f'with obs_shape=({want // 4},)')
+
+
 EMPTY_BUFFER = 'replay buffer is empty (random.choice on an empty list, replay_buffer.py:169)'
 
 
@@ -454,7 +529,8 @@ class DeviceReplayLoader:
     def __init__(self, storage, max_size, batch_size, num_workers, save_snapshot, nstep, discount, fetch_every=1000,
                  device='cuda', sampler='mt19937', seed=None, worker_ids=None, max_episodes=None, capacity_rows=None, static=False,
                  load_threads=None, offline=False, env=None, relabel=False, weighting=None, episode_weight=None, mix=None,
-                 frame_stack=None, normalize_obs=False, norm_eps=1e-3, gather=None, holdout_every=None):
+                 frame_stack=None, normalize_obs=False, norm_eps=1e-3, gather=None, holdout_every=None, goal=None):
+        self.goal = _goal_args(goal, sampler, frame_stack, tuple(s.name for s in getattr(storage, '_meta_specs', ())))
         if holdout_every is not None:
             if not offline:
                 raise ValueError('holdout_every needs an offline loader (make_offline_replay_loader): an online buffer evicts and re-scans, '
@@ -495,6 +571,12 @@ class DeviceReplayLoader:
 
     def __iter__(self):
         return DeviceReplayIterator(self)
+
+    def goal_obs(self, obs, goal_observation):
+        """[obs | goal_observation[cols]] of a goal= loader, for agent.act() (GoalRelabel.goal_obs)."""
+        if self.goal is None:
+            raise ValueError('goal_obs: the loader was made without goal=')
+        return self.goal.goal_obs(obs, goal_observation)
 
 
 def start_pair_batches(n_episodes, batch):
@@ -546,6 +628,8 @@ class _EpisodeStarts:
 
 
 class DeviceReplayIterator(_EpisodeStarts):
+    goal = None             # the loader's GoalRelabel: what agents read, a goal iterator fills [obs | g] rows
+
     def __init__(self, loader):
         self.loader = loader
         self.shards = [(_OfflineShard if loader.offline else _Shard)(loader, w) for w in loader.worker_ids]
@@ -554,6 +638,7 @@ class DeviceReplayIterator(_EpisodeStarts):
         self.sampler, self.nstep, self.discount, self.batch_size = loader.sampler, loader.nstep, loader.discount, loader.batch_size
         self._normalizer = None
         self._holdout = None
+        self.goal = loader.goal
 
     @property
     def holdout(self):
@@ -600,6 +685,11 @@ class DeviceReplayIterator(_EpisodeStarts):
                 raise IndexError(EMPTY_BUFFER)
         if not shard.seeded:
             self._seed(shard)
+        if self.goal is not None and shard.engine.goal is not self.goal:
+            shard.engine.set_goal(self.goal)
+
+    def goal_obs(self, obs, goal_observation):
+        return self.loader.goal_obs(obs, goal_observation)
 
     def _arenas(self):
         for shard in self.shards:
@@ -610,8 +700,10 @@ class DeviceReplayIterator(_EpisodeStarts):
     @property
     def obs_normalizer(self):
         """(mean32, inv32) of a normalize_obs=True loader, for agent.set_obs_normalizer; None otherwise. The first look loads every shard,
-        takes and exchanges the moments and sets the normaliser on all the shard arenas (DeviceReplayLoader)."""
-        return self._ensure_normalizer()
+        takes and exchanges the moments and sets the normaliser on all the shard arenas (DeviceReplayLoader). On a goal= loader the pair
+        is widened to the [obs | g] rows the agent sees."""
+        pair = self._ensure_normalizer()
+        return pair if pair is None or self.goal is None else self.goal.widen_normalizer(*pair)
 
     def _ensure_normalizer(self):
         ld = self.loader
@@ -682,6 +774,8 @@ class DeviceReplayIterator(_EpisodeStarts):
         for start, n in self._segments(shard, batch):
             if not shard.fns:                                 # loaded, then emptied by an eviction
                 raise IndexError(EMPTY_BUFFER)
+            if self.goal is not None:
+                _check_goal_rows(out, shard.engine, self.goal)
             seg = L.BatchOut(out.obs + start * out.obs_stride, out.obs_stride,
                              out.action + start * out.action_stride * 4, out.action_stride,
                              out.reward + start * 4, out.discount + start * 4,
@@ -689,11 +783,12 @@ class DeviceReplayIterator(_EpisodeStarts):
                              (out.meta + start * out.meta_stride * 4) if out.meta else None, out.meta_stride,
                              (out.next_action + start * out.next_action_stride * 4) if out.next_action else None, out.next_action_stride,
                              (out.next_valid + start * 4) if out.next_valid else None)
+            kw = {} if self.goal is None else {'goal': True}
             if mc_return is None:
-                shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler)
+                shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler, **kw)
             else:
                 _ensure_returns(shard.engine, ld.discount)
-                shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler, mc_return=mc_return[start:start + n])
+                shard.engine.sample_into(seg, n, ld.nstep, ld.discount, ld.sampler, mc_return=mc_return[start:start + n], **kw)
 
     def __next__(self):
         ld = self.loader
@@ -701,7 +796,7 @@ class DeviceReplayIterator(_EpisodeStarts):
         self._ensure_normalizer()
         shard = self.shards[self.turn % len(self.shards)]
         self._load_shard(shard)                               # first batch: the scan that sample 0 would trigger
-        res, out = shard.engine.alloc_batch(B)
+        res, out = shard.engine.alloc_batch(B) if self.goal is None else shard.engine.alloc_batch(B, len(self.goal.cols))
         self.sample_into(out, B)
         if len(res) == 5:
             return res
@@ -716,11 +811,16 @@ class DeviceReplayIterator(_EpisodeStarts):
 class ArenaIterator(_EpisodeStarts):
     """Iterator over an already-filled ReplayEngine (no directory behind it): what bench.py and callers that
     ingest datasets themselves use. Same next()/sample_into() contract as DeviceReplayIterator."""
+    goal = None
 
-    def __init__(self, engine, batch_size, nstep, discount, sampler='philox', weighting=None, episode_weight=None, episodes=None):
+    def __init__(self, engine, batch_size, nstep, discount, sampler='philox', weighting=None, episode_weight=None, episodes=None, goal=None):
         """weighting / episode_weight: as DeviceReplayLoader's, applied once here through engine.set_weights. The arena keeps no episode
-        dicts, so a callable episode_weight needs `episodes`: the dicts that were appended, indexed by slot id."""
+        dicts, so a callable episode_weight needs `episodes`: the dicts that were appended, indexed by slot id.
+        goal: a GoalRelabel, set on the arena here (engine.set_goal): the iterator then fills and yields [obs | g] rows (DeviceReplayLoader)."""
         self.engine, self.batch_size, self.nstep, self.discount = engine, batch_size, nstep, discount
+        self.goal = _goal_args(goal, sampler)
+        if self.goal is not None:
+            engine.set_goal(self.goal)
         self.sampler = {'mt19937': L.SAMPLER_MT19937, 'philox': L.SAMPLER_PHILOX}[sampler]
         mode = _weighting_args(sampler, weighting, episode_weight)
         if mode is not None:
@@ -742,12 +842,26 @@ class ArenaIterator(_EpisodeStarts):
         by the same gather launch; the arena's column is built on the first request and again when it is stale. An episode cut by a time limit
         gets the return of its recorded remainder, a lower bound only where rewards are >= 0."""
         eng = self._next_engine()
+        if self.goal is not None:
+            _check_goal_rows(out, eng, self.goal)
         if mc_return is not None:
             _ensure_returns(eng, self.discount)
-        eng.sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler, mc_return=mc_return)
+        eng.sample_into(out, batch or self.batch_size, self.nstep, self.discount, self.sampler, mc_return=mc_return,
+                        **({} if self.goal is None else {'goal': True}))
 
     def __next__(self):
-        return self._next_engine().sample(self.batch_size, self.nstep, self.discount, self.sampler)
+        if self.goal is None:
+            return self._next_engine().sample(self.batch_size, self.nstep, self.discount, self.sampler)
+        eng = self._next_engine()
+        res, out = eng.alloc_batch(self.batch_size, len(self.goal.cols))
+        eng.sample_into(out, self.batch_size, self.nstep, self.discount, self.sampler, goal=True)
+        return res
+
+    def goal_obs(self, obs, goal_observation):
+        """[obs | goal_observation[cols]] of a goal iterator, for agent.act() (GoalRelabel.goal_obs)."""
+        if self.goal is None:
+            raise ValueError('goal_obs: the iterator was made without goal=')
+        return self.goal.goal_obs(obs, goal_observation)
 
 
 HOLDOUT_SEED_SALT = 0x5851F42D4C957F2D       # the hold-out arenas' Philox seed: the training arena's xor this, so the two streams differ
@@ -761,7 +875,10 @@ class HoldoutIterator(ArenaIterator):
         ld = parent.loader
         self.batch_size, self.nstep, self.discount, self.sampler = ld.batch_size, ld.nstep, ld.discount, L.SAMPLER_PHILOX
         self.engines = [shard.holdout_engine for shard in parent.shards]
+        self.goal = ld.goal                       # validation batches are relabelled by the training rule
         for shard in parent.shards:
+            if self.goal is not None:
+                shard.holdout_engine.set_goal(self.goal)
             shard.holdout_engine.seed_philox(((parent._seed_base() + shard.worker_id) ^ HOLDOUT_SEED_SALT) & 0x7FFFFFFFFFFFFFFF)
         self.turn = 0
 

@@ -13,7 +13,7 @@ from .replay_buffer import make_replay_loader
 
 def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, replay_buffer_size=10**7, eval_every_steps=10000,
                   log_every_steps=1000, eval_fn=None, log_fn=None, env=None, sampler='philox', use_graph=True, start_step=0,
-                  metric_window=False, mix=None, weighting=None, normalize_obs=False, holdout_every=None, val_batches=0):
+                  metric_window=False, mix=None, weighting=None, normalize_obs=False, holdout_every=None, val_batches=0, goal=None):
     """train_offline.py:90-123. Returns the list of (step, metrics) rows that were logged.
 
     eval_fn(step, agent): called every eval_every_steps (train_offline.py:108-112).
@@ -30,13 +30,18 @@ def train_offline(agent, replay_dir, num_grad_steps, batch_size, discount, repla
     holdout_every=k with val_batches=n > 0: every k-th episode file of each directory is held out of training (DeviceReplayLoader) and, at
     every eval_every_steps boundary, before eval_fn, agent.evaluate(replay_iter.holdout, n) runs n forward-only batches on the held-out
     episodes: its val_* dict goes to the returned rows and to log_fn as (step, dict(val, step=step)). It needs no environment. With
-    either left at its default nothing is split, nothing is evaluated and the rows are what they were."""
+    either left at its default nothing is split, nothing is evaluated and the rows are what they were.
+    goal=GoalRelabel(...): goal-conditioned training. The loader relabels every batch in its gather launch ([obs | g] rows, a reached /
+    not-reached reward unless reward='keep'; DeviceReplayLoader), so `agent` is built with obs_shape=(O + G,); with normalize_obs it gets
+    the widened pair. eval_fn acts on goal.goal_obs(obs, goal_observation)."""
     extra = {k: v for k, v in (('mix', mix), ('weighting', weighting)) if v is not None}
     if normalize_obs:
         extra['normalize_obs'] = True
     validate = holdout_every is not None and int(val_batches) > 0
     if holdout_every is not None:
         extra['holdout_every'] = holdout_every
+    if goal is not None:
+        extra['goal'] = goal
     loader = make_replay_loader(env, replay_dir, replay_buffer_size, batch_size, 0, discount, sampler=sampler, **extra)
     replay_iter = iter(loader)
     if normalize_obs:

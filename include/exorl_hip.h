@@ -49,7 +49,9 @@ extern "C" {
                                         exorl_agent_rebrac_bytes, exorl_agent_set_rebrac, exorl_rebrac_rows;
                                         exorl_agent_sarsa_bytes, exorl_agent_set_sarsa, exorl_next_action_rows;
                                         exorl_replay_build_returns, exorl_replay_returns, exorl_replay_returns_read, exorl_replay_sample_mc,
-                                        exorl_agent_calql_bytes, exorl_agent_set_calql, exorl_cql_dq_rows, EXORL_M_CALQL_BOUND) */
+                                        exorl_agent_calql_bytes, exorl_agent_set_calql, exorl_cql_dq_rows, EXORL_M_CALQL_BOUND;
+                                        exorl_replay_set_goal, exorl_replay_sample_goal, exorl_replay_last_goals, exorl_agent_enable_graph_goal,
+                                        EXORL_GOAL_KEEP / _NEG / _SPARSE) */
 
 const char* exorl_last_error(void);
 int exorl_abi_version(void);
@@ -208,6 +210,49 @@ int exorl_replay_sample_mc(exorl_replay_t* r, int32_t batch, int32_t nstep, floa
 
 /* Synchronous: the (position, start idx) pairs of the last sample call, read back from the device. */
 int exorl_replay_last_pairs(exorl_replay_t* r, int32_t batch, int32_t* pairs_host, void* stream);
+
+/* Goal relabelling in the gather (fp32 state arenas). Sample b is the pair (pos, idx): obs at time t = idx - 1, next_obs at t + n, n = nstep,
+ * T = len[pos] >= t + n. Its goal is a pair (pos_g, tau), arena row row0[pos_g] + tau, and g[j] = o_goal[cols[j]] for the n_cols column indices
+ * of cols_host, with a normaliser set (x - mean[cols[j]]) * inv_scale[cols[j]] in the gather's two uncontracted operations: bit for bit the
+ * normalised observation's columns. The same g is written behind obs and behind next_obs.
+ * EXORL_SAMPLER_PHILOX draws the goal in the kernel; block (b, counter_lo, counter_hi, 0), the sample's own pair, keeps its bits.
+ *   x = philox4x32_10((b, counter_lo, counter_hi, 1), seed); t_cur = floor(p_cur 2^32), t_traj = floor((p_cur + p_traj) 2^32) as uint64
+ *   x[0] < t_cur   CUR   pos_g = pos, tau = t + n
+ *   x[0] < t_traj  TRAJ  pos_g = pos, room = T - (t + n), tau = t + n + d;
+ *                        horizon_gamma <= 0 (uniform):  d = (x[1] (room + 1)) >> 32
+ *                        0 < horizon_gamma < 1:         d = min(#{k : tab[k] <= x[1]}, room), tab[k] = floor(2^32 (1 - p_k)), p_0 = horizon_gamma,
+ *                                                       p_(k+1) = p_k horizon_gamma in double on the host; the table ends before its first entry
+ *                                                       >= 2^32 - 1, or after 4096 entries; mass past the episode's end piles on its last state
+ *   else           RAND  y = philox4x32_10((b, counter_lo, counter_hi, 2), seed); pos_g = the sampler's own episode choice on y (y[0] scaled
+ *                        onto the episode count, or the cum / guide search on y[2], y[3] of a weighted arena: a zero-mass episode is never a
+ *                        goal); tau = (y[1] (len[pos_g] + 1)) >> 32, any of the episode's len + 1 states
+ * The other samplers take the goals from the caller (exorl_replay_sample_goal's goals_host).
+ * reached = (pos_g == pos && tau == t + n), an equality of indices whatever the source. Reward and discount run through the n-step recurrence
+ * of exorl_replay_sample in its operation order (t = D rho_i; R += t; u = c_i gamma; D *= u), only its per-step inputs substituted; only step
+ * i = n - 1 can reach the goal:
+ *   EXORL_GOAL_KEEP    rho_i = the arena's reward, c_i = the arena's discount (the goal is context only)
+ *   EXORL_GOAL_NEG     rho_i = 0 on the reaching step, else -1;  c_i = 0 on the reaching step, else 1
+ *   EXORL_GOAL_SPARSE  rho_i = 1 on the reaching step, else 0;   c_i = 0 on the reaching step, else 1
+ * p_cur + p_traj + p_rand must be 1 within 1e-6. n_cols = 0 clears the rule. Refused on a frame-stacked arena and on one with meta columns; the
+ * arena must hold fp32 state rows (the C side cannot tell: a u8 arena is refused by the caller that knows the type). A set-up call: it
+ * synchronises the device. A graph captured by exorl_agent_enable_graph_goal is bound to the rule of its capture. */
+#define EXORL_GOAL_KEEP   0
+#define EXORL_GOAL_NEG    1
+#define EXORL_GOAL_SPARSE 2
+int exorl_replay_set_goal(exorl_replay_t* r, const int32_t* cols_host, int32_t n_cols, double p_cur, double p_traj, double p_rand,
+                          double horizon_gamma /* <= 0: uniform */, int32_t reward_mode);
+/* exorl_replay_sample_mc under the rule of exorl_replay_set_goal, the same single gather launch: goal_dev[b * goal_stride + j] and
+ * next_goal_dev[b * next_goal_stride + j], j < n_cols, take g (strides in floats; [obs | g] rows: out->obs + 4 * O with stride
+ * out->obs_stride / 4). goals_host: B x {pos_g, tau in [0, len[pos_g]]} for EXORL_SAMPLER_GIVEN and EXORL_SAMPLER_MT19937, range-checked on the
+ * host as the pairs are; ignored by EXORL_SAMPLER_PHILOX. out->next_action / next_valid work as in exorl_replay_sample. mc_return_dev is
+ * refused unless the reward mode is EXORL_GOAL_KEEP. The drawn (pos, idx) and every output of exorl_replay_sample other than reward and
+ * discount are what exorl_replay_sample gives for the same seed and counter. (The destinations are arguments because exorl_batch_out keeps
+ * its size.) */
+int exorl_replay_sample_goal(exorl_replay_t* r, int32_t batch, int32_t nstep, float gamma, int32_t sampler, const int32_t* pairs_host,
+                             const int32_t* goals_host, const exorl_batch_out* out, float* goal_dev, int64_t goal_stride, float* next_goal_dev,
+                             int64_t next_goal_stride, float* mc_return_dev, int32_t* pairs_out_host, void* stream);
+/* Synchronous: the (pos_g, tau) goals of the last exorl_replay_sample_goal call (or captured goal step), read back from the device. */
+int exorl_replay_last_goals(exorl_replay_t* r, int32_t batch, int32_t* goals_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel communicator: RCCL over xGMI, one per process / GPU. The reference has no distributed path; these
@@ -555,6 +600,10 @@ int exorl_agent_set_opt_steps(exorl_agent_t* a, int64_t actor_steps, int64_t cri
  * enable_graph synchronises `stream` (the caller's stream, where earlier steps may still run) before touching anything and does not
  * consume a Philox batch. step_graph launches on `stream`; stddev is the schedule's value for this step. */
 int exorl_agent_enable_graph(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep, float gamma, float stddev, void* stream);
+/* exorl_agent_enable_graph on a replay with a goal rule (exorl_replay_set_goal): captures exorl_replay_sample_goal(PHILOX) into the agent's
+ * [obs | g] batch slots (g at column O of the obs and next_obs rows), then the step on those rows. Requires the replay's O + n_cols ==
+ * cfg.obs_dim. exorl_agent_step_graph refuses to replay the graph once exorl_replay_set_goal was called after the capture. */
+int exorl_agent_enable_graph_goal(exorl_agent_t* a, exorl_replay_t* r, int32_t nstep, float gamma, float stddev, void* stream);
 int exorl_agent_step_graph(exorl_agent_t* a, float stddev, void* stream);
 int exorl_agent_disable_graph(exorl_agent_t* a);
 /* Test hooks for the device-side noise stream (synchronous): the Philox draw counter after the steps enqueued so far, and the
